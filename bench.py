@@ -19,9 +19,15 @@ whose flat arrays are already resident in HBM (mag_upload happens before the tim
           --partition strong: the workload at its BASELINE size split over the N GPUs (configs 4 and 5).
 
 value = elements of the global mesh * steps / wall time of the timed region (max over ranks).
-The line carries `roofline` (dominant kernel: bound, algorithmic bytes or flops per launch / live HIP-event time, peak,
-PMC traffic), `spmv`, `hbm_resident` (the same kernels on the 16M-triangle mesh, beyond the Infinity Cache) and
-`cpu_baseline` (the oracle timed on this host).
+
+A plain run sets up, warms up, times the steps and prints the line: the headline figure and what the library's own
+statistics of the last step say (iterations, phase times).  --full adds everything that takes work of its own:
+`roofline` (dominant kernel: bound, algorithmic bytes or flops per launch / live HIP-event time, peak, PMC traffic),
+`spmv`, `verify` (true residual of the returned solution), `hbm_resident` (the same kernels on the 16M-triangle mesh,
+beyond the Infinity Cache), `unstructured` (whole solves of the frontal-like 1M mesh) and `cpu_baseline` (the oracle
+timed on this host).
+
+--dump-outputs DIR writes what the last timed step returned (u, f, stress: mag_download) as DIR/<name>.npy, float64.
 """
 import argparse
 import json
@@ -37,6 +43,27 @@ FP64_VECTOR_PEAK_TFLOPS = 78.65  # half the guide's 157.3 TFLOP/s fp32 vector pe
 INFINITY_CACHE_BYTES = 256 << 20
 PMC_SUMMARY = os.path.join(ROOT, "profiles", "pmc_summary.json")  # scripts/pmc_summarize.py (not round-specific)
 CPU_RECORD = os.path.join(ROOT, "profiles", "cpu_baseline.json")  # scripts/cpu_baseline_record.py
+DUMP_BUDGET_BYTES = 60 << 20  # --dump-outputs: below 64 MB in all, the .npy headers included
+DUMP_SEED = 20250101
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, seed=DUMP_SEED):
+    """Writes every array as out_dir/<name>.npy in float64.  When they hold more than `budget` bytes in all, each is cut
+    to the same share of its positions, a fixed seeded sample (sorted), so that two builds fed the same arguments write
+    files that compare position for position.  Returns {name: (length of the output, entries written)}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    share = 1.0 if total <= budget else budget / total
+    written = {}
+    for name, a in arrays.items():
+        if share < 1.0:
+            k = int(a.size * share)
+            a = a[np.sort(np.random.default_rng(seed).choice(a.size, k, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = (int(arrays[name].size), int(a.size))
+    return written
 
 
 def bytes_spmv(E, N):
@@ -382,11 +409,19 @@ def main():
     ap.add_argument("--precision", default="fp64", choices=["fp64", "fp32"],
                     help="fp32: the fp32 leg of BASELINE config 5's sweep (CG state and operator in fp32, dots in fp64; "
                          "streaming kernels; cannot meet the 1e-8 parity bar) -- the line then says dtype f32")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline does not need: roofline and "
+                         "SpMV kernel timings, the true residual of the solution, the HBM-resident and unstructured legs "
+                         "and the CPU baseline (each leg can still be dropped with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (u, f, stress) as DIR/<name>.npy, float64; a fixed "
+                         "seeded sample of each when they exceed 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-unstructured", action="store_true",
-                    help="N = 1, default workload: skip the unstructured leg (whole solves of the 1M-triangle frontal-like mesh)")
+                    help="--full, N = 1, default workload: skip the unstructured leg (whole solves of the 1M-triangle "
+                         "frontal-like mesh)")
     ap.add_argument("--no-hbm-resident", action="store_true",
-                    help="N = 1: skip the HBM-resident leg (SpMV and iteration kernel timed on the 16M-triangle mesh)")
+                    help="--full, N = 1: skip the HBM-resident leg (SpMV and iteration kernel timed on the 16M-triangle mesh)")
     ap.add_argument("--partition", default="weak", choices=["weak", "strong"],
                     help="N > 1.  weak (default, the scaling curve): every GPU gets the workload's mesh, stacked N times "
                          "along y.  strong: the workload at its BASELINE size split over the N GPUs (config 4 = "
@@ -414,6 +449,8 @@ def main():
                          "positions; needs --partition strong at N > 1, --stop rel and the fixture's tolerance); the line "
                          "carries `fixture_parity`, exit code 6 on a miss")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -577,22 +614,31 @@ def main():
     st = ctx.stats()
     if args.tile == 0:  # what the library chose (mag_options.tile_nodes = 0): the tile size that gives its tile count
         args.tile = next(b for b in (256, 512, 1024) if (N + b - 1) // b == int(st["num_tiles"]))
-    # HIP events on the library's own stream around op_reps back-to-back launches (mag_time_operator / mag_time_spmv);
-    # with several ranks each launch covers the tiles this rank owns (its per-GPU share)
-    ms_op = ctx.time_operator(args.op_reps)   # the streaming CG iteration kernel (one launch per iteration)
-    ms_spmv = ctx.time_spmv(args.op_reps)     # the plain matrix-free SpMV y = M K M v
-    u, f_out, s_out = ctx.download()
-    # Self-check of the returned solution, independent of how it was produced and gathered: the true residual
-    # f - K u on the unknown DOFs, with K applied matrix-free to the whole mesh by this rank alone, against |b|.  A
-    # converged solve sits at about the stop tolerance; an exchange or gather that went wrong would not.
-    import numpy as np
-    y = ctx.apply_operator(u, masked=False)
-    free = prob.u_known == 0
-    verify = float(np.linalg.norm((prob.f_in - y)[free]) / max(st["rhs_norm"], 1e-300))
-    verify_bar = max(1e-6, 100.0 * args.tol) if args.precision == "fp64" else 1e-3
-    verify_ok = bool(verify <= verify_bar) if st["converged"] else None
-    if use_dist:
-        verify_ok = all_agree(verify_ok is not False)
+    u = f_out = s_out = None
+    if args.full or args.check_fixture or args.dump_outputs:
+        u, f_out, s_out = ctx.download()  # what the last timed step returned (the timing helpers below leave it alone)
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"u": u, "f": f_out, "stress": s_out})
+        if any(n != k for n, k in dumped.values()):
+            print(f"bench.py: --dump-outputs wrote a seeded sample (entries written of each output): {dumped}",
+                  file=sys.stderr, flush=True)
+    verify_ok = None
+    if args.full:
+        # HIP events on the library's own stream around op_reps back-to-back launches (mag_time_operator / mag_time_spmv);
+        # with several ranks each launch covers the tiles this rank owns (its per-GPU share)
+        ms_op = ctx.time_operator(args.op_reps)   # the streaming CG iteration kernel (one launch per iteration)
+        ms_spmv = ctx.time_spmv(args.op_reps)     # the plain matrix-free SpMV y = M K M v
+        # Self-check of the returned solution, independent of how it was produced and gathered: the true residual
+        # f - K u on the unknown DOFs, with K applied matrix-free to the whole mesh by this rank alone, against |b|.  A
+        # converged solve sits at about the stop tolerance; an exchange or gather that went wrong would not.
+        import numpy as np
+        y = ctx.apply_operator(u, masked=False)
+        free = prob.u_known == 0
+        verify = float(np.linalg.norm((prob.f_in - y)[free]) / max(st["rhs_norm"], 1e-300))
+        verify_bar = max(1e-6, 100.0 * args.tol) if args.precision == "fp64" else 1e-3
+        verify_ok = bool(verify <= verify_bar) if st["converged"] else None
+        if use_dist:
+            verify_ok = all_agree(verify_ok is not False)
     parity = None
     if args.check_fixture:
         if world > 1 and args.partition != "strong":
@@ -610,23 +656,6 @@ def main():
         ms_step = elapsed * 1e3 / args.steps
         Eloc, Nloc = E / world, N / world  # per-GPU share: what one launch of the kernels processes
         kind = int(st["cg_kernel"])  # what ran: 2 on-chip single launch, 1 one fused launch per iteration, 0 two launches
-        tile_key = f"{args.workload}:tile{args.tile}"
-        if world > 1:  # the committed PMC passes are single-GPU runs of the single-GPU kernels: no counters for N > 1
-            tile_key = "none"
-        if kind == 2:
-            roofline = roofline_onchip(Eloc, Nloc, iters, st["ms_cg"], load_pmc(f"{tile_key}:kernel2"), args.tile,
-                                       int(st.get("edge_blocks", 0)), int(st.get("tiles_per_workgroup", 0)) or None)
-        elif kind == 4:  # fp32 leg: value terms halved (r, q, p, x in and out 64N, coordinates 8N, mask 1N); no timing
-            # hook of its own, so the launch time is the CG phase / iterations (graph gaps and early exits included)
-            roofline = kernel_line("k_cg_fused32<%d> (whole CG iteration in one launch, fp32 state)" % args.tile,
-                                   12.0 * Eloc + 73.0 * Nloc, "12E+73N (fused iteration, fp32 values)",
-                                   st["ms_cg"] / max(iters, 1), None)
-        else:
-            roofline = roofline_streaming(kind, Eloc, Nloc, ms_op, load_pmc(f"{tile_key}:kernel{kind}"), args.tile)
-        roofline["us_per_iteration"] = st["ms_cg"] * 1e3 / max(iters, 1)
-        spmv = kernel_line("k_operator_lds<%d,false> (plain matrix-free SpMV y = M K M v)" % args.tile,
-                           bytes_spmv(Eloc, Nloc), "12E+50N (SpMV, SURVEY 8d), per-GPU share", ms_spmv,
-                           load_pmc(f"{tile_key}:spmv"))
         asm_ms = st["ms_element"] + st["ms_assemble"] + st["ms_bc"]
         out = {
             # BASELINE.json's metric; quoted on the 1M-triangle mesh, other workloads say which mesh they ran
@@ -646,11 +675,7 @@ def main():
                        "partition": args.partition if world > 1 else None,
                        "exchange": exchange, "exchange_kind": int(st["exchange"]), "exchange_autotune": autotune,
                        "ranks": comm["ranks"], "transport": comm["transport"], "rccl_ranks": comm["rccl_ranks"]},
-            "roofline": roofline,
-            "spmv": spmv,
             "fallback": fallback,
-            "verify": {"rel_true_residual": verify, "bar": verify_bar, "ok_on_every_rank": verify_ok,
-                       "what": "|f - K u| on the unknown DOFs / |b|, K applied matrix-free to the whole mesh"},
             "cg_iterations": iters, "cg_converged": int(st["converged"]), "cg_final_cost": st["final_cost"],
             "cg_termination": {0: "none", 1: "target_cost", 2: "max_iters", 3: "breakdown"}.get(int(st["termination"])),
             "cg_best_iteration": int(st["best_iteration"]),
@@ -659,7 +684,7 @@ def main():
             "capped": bool(capped), "fixture_parity": parity,
             "cg_iters_per_sec": iters / (st["ms_cg"] * 1e-3) if st["ms_cg"] > 0 else None,
             # the SURVEY 8(d) figure of the metric's name: bytes an UNFUSED iteration streams / time per iteration.  An
-            # equivalent rate, not HBM utilisation (the fused and on-chip kernels move far less): see roofline
+            # equivalent rate, not HBM utilisation (the fused and on-chip kernels move far less): see roofline (--full)
             "cg_iteration_gbps_unfused_equivalent":
                 bytes_iteration_unfused(E, N) * iters / (st["ms_cg"] * 1e-3) / 1e9 if st["ms_cg"] > 0 else None,
             "assembly_elements_per_sec": E / (asm_ms * 1e-3) if asm_ms > 0 else None,
@@ -673,29 +698,50 @@ def main():
                          if asm_ms > 0 else None),
             "phases_ms": {k: st[k] for k in ("ms_order", "ms_csr_symbolic", "ms_element", "ms_assemble", "ms_bc",
                                              "ms_cg", "ms_post", "ms_total")},
-            "u_max": float(abs(u).max()),
         }
-        if world == 1 and not args.no_hbm_resident and args.workload != "multihole16m":
-            ctx.close()  # its buffers are not needed any more; the 16M leg allocates ~5 GB of its own
-            out["hbm_resident"] = hbm_resident_leg(local_rank, args.op_reps)
-        if world == 1 and not args.no_unstructured and args.workload == "hole1m":
-            ctx.close()  # (idempotent)
-            out["unstructured"] = unstructured_leg(local_rank, args.tol)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(prob, iters, stop_mode, args.tol, args.cpu_sample_iters, args.cpu_threads)
-            out["cpu_baseline"]["cores_available"] = os.cpu_count()
-            rec = CPU_RECORD if os.path.exists(CPU_RECORD) else os.path.join(ROOT, "profiles", "r02_cpu_baseline.json")
-            if os.path.exists(rec):  # scripts/cpu_baseline_record.py: BASELINE.md section 2 items 1-3, timed once
-                rj = json.load(open(rec))
-                out["cpu_baseline"]["config1_dense_s"] = rj.get("config1_dense_s")
-                c3 = rj.get("config3_hole1m", {}).get("sparse_1_thread")
-                if c3:  # the UNSCALED 1-thread solve of this very workload, timed once on rj["host"]
-                    out["cpu_baseline"]["config3_full_solve_s"] = c3["assembly_and_bc_s"] + c3["cg_s"]
-                    out["cpu_baseline"]["config3_full_solve_elements_per_s"] = c3["elements_per_s"]
-                out["cpu_baseline"]["record_host"] = rj.get("host")
-                out["cpu_baseline"]["record"] = os.path.relpath(rec, ROOT)
-        else:
-            out["cpu_baseline"] = None
+        if args.full:
+            tile_key = f"{args.workload}:tile{args.tile}"
+            if world > 1:  # the committed PMC passes are single-GPU runs of the single-GPU kernels: no counters for N > 1
+                tile_key = "none"
+            if kind == 2:
+                roofline = roofline_onchip(Eloc, Nloc, iters, st["ms_cg"], load_pmc(f"{tile_key}:kernel2"), args.tile,
+                                           int(st.get("edge_blocks", 0)), int(st.get("tiles_per_workgroup", 0)) or None)
+            elif kind == 4:  # fp32 leg: value terms halved (r, q, p, x in and out 64N, coordinates 8N, mask 1N); no timing
+                # hook of its own, so the launch time is the CG phase / iterations (graph gaps and early exits included)
+                roofline = kernel_line("k_cg_fused32<%d> (whole CG iteration in one launch, fp32 state)" % args.tile,
+                                       12.0 * Eloc + 73.0 * Nloc, "12E+73N (fused iteration, fp32 values)",
+                                       st["ms_cg"] / max(iters, 1), None)
+            else:
+                roofline = roofline_streaming(kind, Eloc, Nloc, ms_op, load_pmc(f"{tile_key}:kernel{kind}"), args.tile)
+            roofline["us_per_iteration"] = st["ms_cg"] * 1e3 / max(iters, 1)
+            out["roofline"] = roofline
+            out["spmv"] = kernel_line("k_operator_lds<%d,false> (plain matrix-free SpMV y = M K M v)" % args.tile,
+                                      bytes_spmv(Eloc, Nloc), "12E+50N (SpMV, SURVEY 8d), per-GPU share", ms_spmv,
+                                      load_pmc(f"{tile_key}:spmv"))
+            out["verify"] = {"rel_true_residual": verify, "bar": verify_bar, "ok_on_every_rank": verify_ok,
+                             "what": "|f - K u| on the unknown DOFs / |b|, K applied matrix-free to the whole mesh"}
+            out["u_max"] = float(abs(u).max())
+            if world == 1 and not args.no_hbm_resident and args.workload != "multihole16m":
+                ctx.close()  # its buffers are not needed any more; the 16M leg allocates ~5 GB of its own
+                out["hbm_resident"] = hbm_resident_leg(local_rank, args.op_reps)
+            if world == 1 and not args.no_unstructured and args.workload == "hole1m":
+                ctx.close()  # (idempotent)
+                out["unstructured"] = unstructured_leg(local_rank, args.tol)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(prob, iters, stop_mode, args.tol, args.cpu_sample_iters, args.cpu_threads)
+                out["cpu_baseline"]["cores_available"] = os.cpu_count()
+                rec = CPU_RECORD if os.path.exists(CPU_RECORD) else os.path.join(ROOT, "profiles", "r02_cpu_baseline.json")
+                if os.path.exists(rec):  # scripts/cpu_baseline_record.py: BASELINE.md section 2 items 1-3, timed once
+                    rj = json.load(open(rec))
+                    out["cpu_baseline"]["config1_dense_s"] = rj.get("config1_dense_s")
+                    c3 = rj.get("config3_hole1m", {}).get("sparse_1_thread")
+                    if c3:  # the UNSCALED 1-thread solve of this very workload, timed once on rj["host"]
+                        out["cpu_baseline"]["config3_full_solve_s"] = c3["assembly_and_bc_s"] + c3["cg_s"]
+                        out["cpu_baseline"]["config3_full_solve_elements_per_s"] = c3["elements_per_s"]
+                    out["cpu_baseline"]["record_host"] = rj.get("host")
+                    out["cpu_baseline"]["record"] = os.path.relpath(rec, ROOT)
+            else:
+                out["cpu_baseline"] = None
         if args.share_gpu:
             out["rehearsal"] = "ranks share GPU 0, collectives through gloo: exercises the N > 1 code path, not a result"
         print(json.dumps(out), flush=True)

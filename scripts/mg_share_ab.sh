@@ -7,7 +7,7 @@ export MAG_TUNE_PERSIST_K=4
 for round in 1 2; do
 for lib in "$@"; do
     MAG_LIB_PATH=$PWD/$lib timeout -k 10 300 python bench.py --gpus 2 --share-gpu --partition strong --workload hole1m \
-        --exchange inboxes --no-cpu-baseline --no-hbm-resident --steps 3 --warmup 1 2> /dev/null | python -c "
+        --exchange inboxes --full --no-cpu-baseline --no-hbm-resident --steps 3 --warmup 1 2> /dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -23,7 +23,7 @@ COMM = ["waiting_for_this_ranks_records", "summing_and_storing_the_rank_sum_into
 def bench(env_extra, k):
     env = dict(os.environ, MAG_TUNE_PERSIST_K=str(k), **env_extra)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--partition", "strong", "--workload", "hole1m",
-           "--exchange", "inboxes", "--no-cpu-baseline", "--no-hbm-resident", "--steps", "2", "--warmup", "1"]
+           "--exchange", "inboxes", "--full", "--no-cpu-baseline", "--no-hbm-resident", "--steps", "2", "--warmup", "1"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if not lines:

@@ -22,19 +22,19 @@ if [ "${PART:-AB}" != "B" ]; then  # PART=A / PART=B: the session in two halves 
 bash scripts/pmc_onchip_compare.sh "$OUT/pmc_cmp" "frontal1m hole1m" > "$OUT/pmc_cmp.log" 2>&1
 python3 scripts/pmc_onchip_compare.py "$OUT/pmc_cmp" "$OUT/pmc_onchip_compare.json" > "$OUT/pmc_onchip_compare.txt" 2>&1
 echo "on-chip counter comparison done" >> "$OUT/progress.txt"
-(cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/stats" -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 > "$ROOT/$OUT/bench_under_rocprof.json" 2> "$ROOT/$OUT/bench_under_rocprof.err")
+(cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/stats" -- python3 "$ROOT/bench.py" --full --steps 2 --warmup 1 > "$ROOT/$OUT/bench_under_rocprof.json" 2> "$ROOT/$OUT/bench_under_rocprof.err")
 echo "kernel stats done" >> "$OUT/progress.txt"
-python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
-python3 bench.py --steps 20 --warmup 5 > "$OUT/bench_driver_cmd.json" 2> "$OUT/bench_driver_cmd.err"
+python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 bench.py --full --steps 20 --warmup 5 > "$OUT/bench_driver_cmd.json" 2> "$OUT/bench_driver_cmd.err"
 echo "bench done" >> "$OUT/progress.txt"
 fi
 if [ "${PART:-AB}" = "A" ]; then exit 0; fi
 : > "$OUT/size_scaling.jsonl"
 for wl in plate100k hole1m frontal1m plate4m multihole16m; do
-    python3 bench.py --workload $wl --no-cpu-baseline --no-hbm-resident --no-unstructured >> "$OUT/size_scaling.jsonl" 2>> "$OUT/size_scaling.err"
+    python3 bench.py --full --workload $wl --no-cpu-baseline --no-hbm-resident --no-unstructured >> "$OUT/size_scaling.jsonl" 2>> "$OUT/size_scaling.err"
 done
-python3 bench.py --workload multihole16m --precision fp32 --no-cpu-baseline --no-hbm-resident >> "$OUT/size_scaling.jsonl" 2>> "$OUT/size_scaling.err"
-MAG_TUNE_PERSIST_TRIANGLES=1 python3 bench.py --workload frontal1m --no-cpu-baseline --no-hbm-resident --no-unstructured >> "$OUT/size_scaling.jsonl" 2>> "$OUT/size_scaling.err"
+python3 bench.py --full --workload multihole16m --precision fp32 --no-cpu-baseline --no-hbm-resident >> "$OUT/size_scaling.jsonl" 2>> "$OUT/size_scaling.err"
+MAG_TUNE_PERSIST_TRIANGLES=1 python3 bench.py --full --workload frontal1m --no-cpu-baseline --no-hbm-resident --no-unstructured >> "$OUT/size_scaling.jsonl" 2>> "$OUT/size_scaling.err"
 echo "size scaling done" >> "$OUT/progress.txt"
 # in-kernel phase stamps (diagnostic build; round 3's GPU fault of this build was an SGPR hazard of the inline-asm stores, fixed
 # in round 4: DESIGN.md R4.1): the edge-block kernel on the structured meshes and the overflow instantiation on the frontal
@@ -46,10 +46,10 @@ echo "phases done" >> "$OUT/progress.txt"
 # multi-GPU rehearsals (ranks share the ONE GPU, gloo): two ranks at four tiles per workgroup, edge blocks and triangle walk;
 # config 4 across four ranks against its fixture
 : > "$OUT/multirank_rehearsals.jsonl"
-MAG_TUNE_PERSIST_K=4 python3 bench.py --gpus 2 --share-gpu --partition strong --workload hole1m --exchange inboxes --no-cpu-baseline --no-hbm-resident --steps 3 --warmup 1 --check-fixture >> "$OUT/multirank_rehearsals.jsonl" 2>> "$OUT/multirank_rehearsals.err"
-MAG_TUNE_PERSIST_K=4 MAG_TUNE_PERSIST_MG_BLOCKS=0 python3 bench.py --gpus 2 --share-gpu --partition strong --workload hole1m --exchange inboxes --no-cpu-baseline --no-hbm-resident --steps 3 --warmup 1 --check-fixture >> "$OUT/multirank_rehearsals.jsonl" 2>> "$OUT/multirank_rehearsals.err"
+MAG_TUNE_PERSIST_K=4 python3 bench.py --full --gpus 2 --share-gpu --partition strong --workload hole1m --exchange inboxes --no-cpu-baseline --no-hbm-resident --steps 3 --warmup 1 --check-fixture >> "$OUT/multirank_rehearsals.jsonl" 2>> "$OUT/multirank_rehearsals.err"
+MAG_TUNE_PERSIST_K=4 MAG_TUNE_PERSIST_MG_BLOCKS=0 python3 bench.py --full --gpus 2 --share-gpu --partition strong --workload hole1m --exchange inboxes --no-cpu-baseline --no-hbm-resident --steps 3 --warmup 1 --check-fixture >> "$OUT/multirank_rehearsals.jsonl" 2>> "$OUT/multirank_rehearsals.err"
 # the unstructured 1M mesh across two ranks: edge blocks with overflow records (round 4) and the triangle walk; its fixture stops at 1e-10
-MAG_TUNE_PERSIST_K=4 python3 bench.py --gpus 2 --share-gpu --partition strong --workload frontal1m --tol 1e-10 --exchange inboxes --no-cpu-baseline --no-hbm-resident --no-unstructured --steps 2 --warmup 1 --check-fixture >> "$OUT/multirank_rehearsals.jsonl" 2>> "$OUT/multirank_rehearsals.err"
-MAG_TUNE_PERSIST_K=4 MAG_TUNE_PERSIST_MG_OVERFLOW=0 python3 bench.py --gpus 2 --share-gpu --partition strong --workload frontal1m --tol 1e-10 --exchange inboxes --no-cpu-baseline --no-hbm-resident --no-unstructured --steps 2 --warmup 1 --check-fixture >> "$OUT/multirank_rehearsals.jsonl" 2>> "$OUT/multirank_rehearsals.err"
-python3 bench.py --gpus 4 --share-gpu --partition strong --workload plate4m --exchange inboxes --cg-variant 1 --no-cpu-baseline --no-hbm-resident --steps 1 --warmup 1 --check-fixture >> "$OUT/multirank_rehearsals.jsonl" 2>> "$OUT/multirank_rehearsals.err"
+MAG_TUNE_PERSIST_K=4 python3 bench.py --full --gpus 2 --share-gpu --partition strong --workload frontal1m --tol 1e-10 --exchange inboxes --no-cpu-baseline --no-hbm-resident --no-unstructured --steps 2 --warmup 1 --check-fixture >> "$OUT/multirank_rehearsals.jsonl" 2>> "$OUT/multirank_rehearsals.err"
+MAG_TUNE_PERSIST_K=4 MAG_TUNE_PERSIST_MG_OVERFLOW=0 python3 bench.py --full --gpus 2 --share-gpu --partition strong --workload frontal1m --tol 1e-10 --exchange inboxes --no-cpu-baseline --no-hbm-resident --no-unstructured --steps 2 --warmup 1 --check-fixture >> "$OUT/multirank_rehearsals.jsonl" 2>> "$OUT/multirank_rehearsals.err"
+python3 bench.py --full --gpus 4 --share-gpu --partition strong --workload plate4m --exchange inboxes --cg-variant 1 --no-cpu-baseline --no-hbm-resident --steps 1 --warmup 1 --check-fixture >> "$OUT/multirank_rehearsals.jsonl" 2>> "$OUT/multirank_rehearsals.err"
 echo "all done" >> "$OUT/progress.txt"

@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: scripts/tune.sh "<env assignments>" <tile> -> one summary line
-out=$(env $1 timeout -k 10 300 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --tile $2 2>/dev/null | grep '^{' | tail -1)
+out=$(env $1 timeout -k 10 300 python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --tile $2 2>/dev/null | grep '^{' | tail -1)
 python3 - "$1" "$2" <<PY
 import json,sys
 d=json.loads('''$out''')

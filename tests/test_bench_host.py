@@ -16,13 +16,16 @@ def test_bare_multi_gpu_launch_spawns_its_ranks_and_relays_their_exit_code(built
     """`python bench.py --gpus 2` with no RANK/WORLD_SIZE in the environment: the parent runs the two ranks under
     torch.distributed.run as a child.  There is no GPU here, so every rank stops at bench.py's own "needs a HIP device"
     exit -- reached only INSIDE a rank (RANK set by the launcher), and the parent returns the launcher's non-zero code."""
+    # probed in a child: torch's HIP runtime initialised in this process would be a second one next to the runtime
+    # libmagnetite_hip.so loaded here, and the library's in-process GPU tests that follow would find no device
+    probe = subprocess.run([sys.executable, "-c", "import torch,sys; sys.exit(0 if torch.cuda.is_available() else 3)"],
+                           capture_output=True)
+    if probe.returncode == 0:
+        pytest.skip("GPU present: covered by tests/test_entry_points_gpu.py")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--workload",
                         "plate100k", "--steps", "1", "--warmup", "0"], cwd=ROOT, env=env, capture_output=True, text=True,
                        timeout=600)
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("GPU present: covered by tests/test_entry_points_gpu.py")
     assert r.returncode != 0
     assert "bench.py needs a HIP device" in r.stderr, r.stderr[-2000:]
     assert "but WORLD_SIZE=1" not in r.stderr
@@ -86,3 +89,21 @@ def test_size_sweep_workloads():
         bench.build_problem("plate:24", 2)
     with pytest.raises(SystemExit):
         bench.build_problem("no-such-workload", 1)
+
+
+def test_dump_outputs_writes_float64_and_a_fixed_sample_above_the_budget(tmp_path):
+    """--dump-outputs: every output as <name>.npy in float64; above the budget each is cut to the same share of its
+    positions by a seeded sample, identical from run to run, so that two builds compare output for output."""
+    import numpy as np
+    u, s = np.linspace(-1.0, 1.0, 1000), np.arange(300, dtype=np.float32)
+    assert bench.dump_outputs(str(tmp_path / "a"), {"u": u, "stress": s}) == {"u": (1000, 1000), "stress": (300, 300)}
+    assert np.array_equal(np.load(tmp_path / "a" / "u.npy"), u)
+    got = np.load(tmp_path / "a" / "stress.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, s)
+    budget = 8 * 650
+    w1 = bench.dump_outputs(str(tmp_path / "b"), {"u": u, "stress": s}, budget=budget)
+    w2 = bench.dump_outputs(str(tmp_path / "c"), {"u": u, "stress": s}, budget=budget)
+    assert w1 == w2 and w1["u"][1] == 500 and w1["stress"][1] == 150
+    b, c = np.load(tmp_path / "b" / "u.npy"), np.load(tmp_path / "c" / "u.npy")
+    assert b.dtype == np.float64 and np.array_equal(b, c) and np.all(np.diff(b) > 0) and np.all(np.isin(b, u))
+    assert sum(w[1] for w in w1.values()) * 8 <= budget

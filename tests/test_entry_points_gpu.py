@@ -33,7 +33,7 @@ def check_roofline(d):
 def test_bench_default_config_roofline_is_a_fraction(built):
     """the DEFAULT line (hole1m, on-chip kernel) -- what the driver records as BENCH: frac in (0, 1]"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-hbm-resident", "--op-reps", "50"],
+                        "--full", "--no-cpu-baseline", "--no-hbm-resident", "--op-reps", "50"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -46,7 +46,7 @@ def test_bench_default_config_roofline_is_a_fraction(built):
 
 def test_bench_prints_one_contract_line(built):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "plate100k", "--steps", "2",
-                        "--warmup", "1", "--cpu-sample-iters", "20", "--op-reps", "50"],
+                        "--warmup", "1", "--full", "--cpu-sample-iters", "20", "--op-reps", "50"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -75,6 +75,34 @@ def test_bench_prints_one_contract_line(built):
     assert d["value"] > 10.0 * cb["value"]          # north_star: >= 10x the CPU solver at 1 GPU
 
 
+def test_bench_plain_run_is_lean_and_dumps_what_it_returned(built, tmp_path):
+    """Without --full the line holds the headline and the library's statistics, nothing measured after the steps;
+    --dump-outputs writes what the last timed step returned (u, f, stress) in float64."""
+    import numpy as np
+
+    import bench
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "plate100k", "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["cg_converged"] == 1
+    assert d["unit"] == "elements/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert abs(d["value"] - d["config"]["elements"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    for key in ("roofline", "spmv", "verify", "hbm_resident", "unstructured", "cpu_baseline"):
+        assert key not in d, key
+    prob, _ = bench.build_problem("plate100k", 1)
+    N, E = prob.mesh.num_nodes, prob.mesh.num_elements
+    got = {name: np.load(out / f"{name}.npy") for name in ("u", "f", "stress")}
+    assert sorted(os.listdir(out)) == ["f.npy", "stress.npy", "u.npy"]
+    assert got["u"].shape == got["f"].shape == (2 * N,) and got["stress"].shape == (E,)
+    assert all(a.dtype == np.float64 and np.all(np.isfinite(a)) for a in got.values())
+    known = prob.u_known == 1  # prescribed displacements come back as given, the free ones moved
+    assert np.array_equal(got["u"][known], prob.u_in[known]) and np.abs(got["u"][~known]).max() > 0
+
+
 @pytest.mark.parametrize("window", ["allreduce", "auto", "host-window"])
 def test_bench_multi_rank_code_path_on_one_gpu(built, window):
     """bench.py as the driver launches it for N > 1 (torch.distributed.run, one process per rank), rehearsed with both
@@ -82,7 +110,7 @@ def test_bench_multi_rank_code_path_on_one_gpu(built, window):
     timing, rank 0 prints the single line."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
            "127.0.0.1", "--master-port", str(29581 + len(window)), os.path.join(ROOT, "bench.py"), "--gpus", "2",
-           "--share-gpu", "--workload", "plate100k", "--steps", "1", "--warmup", "1", "--op-reps", "20",
+           "--share-gpu", "--workload", "plate100k", "--steps", "1", "--warmup", "1", "--full", "--op-reps", "20",
            "--exchange", window]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
@@ -114,7 +142,7 @@ def test_bench_streaming_kernels_exchange_through_inboxes(built):
     solve reproduced the all-reduce solve on both ranks."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
            "127.0.0.1", "--master-port", "29613", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu",
-           "--workload", "plate100k", "--steps", "1", "--warmup", "1", "--op-reps", "20", "--cg-variant", "1",
+           "--workload", "plate100k", "--steps", "1", "--warmup", "1", "--full", "--op-reps", "20", "--cg-variant", "1",
            "--exchange", "inboxes"]
     r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"), capture_output=True,
                        text=True, timeout=900)
@@ -132,7 +160,7 @@ def test_bench_strong_partition_keeps_the_baseline_size(built):
     two ranks on the one GPU."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
            "127.0.0.1", "--master-port", "29611", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu",
-           "--workload", "plate100k", "--steps", "1", "--warmup", "1", "--op-reps", "20", "--exchange", "allreduce",
+           "--workload", "plate100k", "--steps", "1", "--warmup", "1", "--full", "--op-reps", "20", "--exchange", "allreduce",
            "--partition", "strong"]
     r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"), capture_output=True,
                        text=True, timeout=900)
@@ -150,7 +178,7 @@ def test_bench_bare_multi_gpu_launch(built):
     single line comes through and the exit code is the children's."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--workload",
-                        "plate100k", "--steps", "1", "--warmup", "1", "--op-reps", "20"], cwd=ROOT, env=env,
+                        "plate100k", "--steps", "1", "--warmup", "1", "--full", "--op-reps", "20"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -173,7 +201,7 @@ def test_config4_four_ranks_at_baseline_size_against_the_oracle_fixture(built, e
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--share-gpu", "--partition",
                         "strong", "--workload", "plate4m", "--cg-variant", "1", "--exchange", exchange, "--steps", "1",
-                        "--warmup", "0", "--op-reps", "20", "--check-fixture"], cwd=ROOT, env=env, capture_output=True,
+                        "--warmup", "0", "--full", "--op-reps", "20", "--check-fixture"], cwd=ROOT, env=env, capture_output=True,
                        text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -196,7 +224,7 @@ def test_on_chip_kernels_of_two_ranks_with_four_tiles_per_workgroup_against_the_
     env["MAG_TUNE_PERSIST_K"] = "4"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--partition",
                         "strong", "--workload", "hole1m", "--exchange", "inboxes", "--steps", "1", "--warmup", "1",
-                        "--op-reps", "20", "--no-cpu-baseline", "--no-hbm-resident", "--check-fixture"], cwd=ROOT, env=env,
+                        "--full", "--op-reps", "20", "--no-cpu-baseline", "--no-hbm-resident", "--check-fixture"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
