@@ -2,6 +2,7 @@
 // orchestration of solver::run (solver.rs:543-586) on one MI355X.
 // No CPU fallback exists: without a HIP device every compute entry point
 // returns MAG_ERR_HIP with the runtime's message.
+#include <cassert>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -9,6 +10,7 @@
 #include <algorithm>
 #include <array>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -147,6 +149,8 @@ struct mag_ctx {
     uint32_t solve_seq = 0;
     double best_cost = 0.0;   // argmin's best_param bookkeeping, as the CG phase that just ran reported it
     long long best_iter = 0;
+    // the on-chip kernel gave up at its grid barrier / an inbox exchange gave up in this run (mag_stats.persist_timeout /
+    // exchange_timeout)
     bool persist_timed_out = false, exchange_timed_out = false;
     bool b_from_order = false; // the ordering phase of this run wrote b = 0.0 + f for every node (k_apply_order)
     int edge_blocks = 0; // instantiation of the on-chip kernel of the last run: 1 edge blocks, 2 with overflow records (mag_stats.edge_blocks)
@@ -154,7 +158,7 @@ struct mag_ctx {
     // an all-reduce; si_failed: a wait ran out once, this context uses the all-reduce from then on
     bool si = false, si_failed = false;
     uint32_t si_tag_base = 0, si_spin = 1u << 20; // polls (~2 us each) before an exchange gives up
-    int32_t exchange_kind = 0; // mag_stats.exchange of the last run // the on-chip kernel gave up at its grid barrier in this run (mag_stats.persist_timeout)
+    int32_t exchange_kind = 0; // mag_stats.exchange of the last run
     int nsums() const { return pre ? 5 : 4; }
     DevBuf pstamps; // diagnostic build of the on-chip kernel: phase stamps
     DevBuf xy32, hxy32, rqp32a, rqp32b, x32; // fp32 leg (mag_options.precision = 1)
@@ -247,6 +251,69 @@ int scan_i64(mag_ctx *ctx, const int64_t *in, int64_t *out, size_t n)
     return MAG_OK;
 }
 
+// ---- collectives of the multi-GPU paths ----
+// in-place sum over ranks of n doubles at dev, ordered on the stream
+int allreduce(mag_ctx *ctx, double *dev, int64_t n)
+{
+    std::string msg;
+    if (int rc = ctx->comm.allreduce_sum(dev, n, ctx->stream, msg)) return fail(ctx, rc, "%s", msg.c_str());
+    return MAG_OK;
+}
+
+int allgather(mag_ctx *ctx, const double *send, double *recv, int64_t n)
+{
+    std::string msg;
+    if (int rc = ctx->comm.allgather(send, recv, n, ctx->stream, msg)) return fail(ctx, rc, "%s", msg.c_str());
+    return MAG_OK;
+}
+
+// n host doubles summed over ranks through comm_pq (128 bytes); the host waits for the result
+int allreduce_host(mag_ctx *ctx, double *v, int n)
+{
+    assert(n <= 16);
+    hipStream_t s = ctx->stream;
+    HIPCHK(hipMemcpyAsync(ctx->comm_pq.p, v, 8 * (size_t)n, hipMemcpyHostToDevice, s));
+    if (int rc = allreduce(ctx, ctx->comm_pq.as<double>(), n)) return rc;
+    HIPCHK(hipMemcpyAsync(v, ctx->comm_pq.p, 8 * (size_t)n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
+// what all ranks must decide alike: flag becomes true on every rank when it is true on any
+int any_rank(mag_ctx *ctx, bool &flag)
+{
+    double v = flag ? 1.0 : 0.0;
+    if (int rc = allreduce_host(ctx, &v, 1)) return rc;
+    flag = v != 0.0;
+    return MAG_OK;
+}
+
+// rank r owns tiles [rank_tile_lo(r), rank_tile_lo(r + 1)): contiguous ranges of the Hilbert order, identical arithmetic on
+// every rank, equal up to one tile
+int32_t rank_tile_lo(int64_t T, int R, int r) { return (int32_t)((T * r) / R); }
+
+// the most tiles any rank runs: T mod R ranks get the ceiling
+int32_t most_rank_tiles(int64_t T, int R) { return (int32_t)((T + R - 1) / R); }
+
+// sequence number of a solve across ranks (1..255, the same on every rank: all ranks run the same solves), kept above 24
+// bits of iteration count in the tags of the inbox exchanges
+uint32_t next_solve_seq(mag_ctx *ctx)
+{
+    ctx->solve_seq = (ctx->solve_seq + 1) & 0xffu;
+    if (ctx->solve_seq == 0) ctx->solve_seq = 1;
+    return ctx->solve_seq;
+}
+
+// the material constants of the operator kernels (the fp32 leg rounds the fp64 values)
+template <class Params>
+void set_material(const mag_ctx *ctx, Params &P)
+{
+    using F = decltype(P.c0);
+    P.c0 = (F)(ctx->youngs * ctx->thick / (2.0 * (1.0 - ctx->nu * ctx->nu)));
+    P.nu = (F)ctx->nu;
+    P.h = (F)((1.0 - ctx->nu) / 2.0);
+}
+
 // ---- symbolic phase 1: Hilbert order, incidence lists, per-tile ELL table ----
 int ensure_order(mag_ctx *ctx)
 {
@@ -327,9 +394,8 @@ int ensure_order(mag_ctx *ctx)
 
     // ---- partition: contiguous tile ranges of the Hilbert order, identical arithmetic on every rank ----
     const int R = ctx->comm.nranks, me = ctx->comm.rank;
-    auto tile_lo = [&](int s_) { return (int32_t)(((int64_t)T * s_) / R); };
-    ctx->t0 = tile_lo(me);
-    ctx->t1 = tile_lo(me + 1);
+    ctx->t0 = rank_tile_lo(T, R, me);
+    ctx->t1 = rank_tile_lo(T, R, me + 1);
     // (T < R, not "my range is empty": every rank must take this exit together -- the others would wait in a collective)
     if (R > 1 && T < R) return fail(ctx, MAG_ERR_BAD_ARGS, "mesh has %d tiles, fewer than %d ranks", (int)T, R);
     // Several ranks, inside mag_run (every rank is here: the phase then ends with two small all-reduces), K assembled from the
@@ -345,7 +411,7 @@ int ensure_order(mag_ctx *ctx)
         HIPCHK(ctx->need_tile.reserve((size_t)T + 64));
         magk::RankTiles rt = {};
         rt.R = R;
-        for (int r_ = 0; r_ <= R; ++r_) rt.lo[r_] = tile_lo(r_);
+        for (int r_ = 0; r_ <= R; ++r_) rt.lo[r_] = rank_tile_lo(T, R, r_);
         HIPCHK(ctx->iface_mask.reserve((size_t)N + 64));
         magk::need_tiles(ctx->conn.as<int32_t>(), E, ctx->iperm.as<int32_t>(), ctx->maskP.as<uint8_t>(), N, B, T, ctx->t0, ctx->t1,
                          true, ctx->need_tile.as<uint8_t>(), rt, ctx->iface_mask.as<uint8_t>(), s);
@@ -462,9 +528,10 @@ int ensure_order(mag_ctx *ctx)
             std::vector<int32_t> iface;
             std::vector<std::pair<int32_t, int32_t>> reads; // (node, reading rank)
             for (int r_ = 0; r_ < R; ++r_) {
-                const int64_t lo = std::min<int64_t>((int64_t)tile_lo(r_) * B, N);
-                const int64_t hi = std::min<int64_t>((int64_t)tile_lo(r_ + 1) * B, N);
-                for (int32_t t = tile_lo(r_); t < tile_lo(r_ + 1); ++t)
+                const int32_t ta = rank_tile_lo(T, R, r_), tb = rank_tile_lo(T, R, r_ + 1);
+                const int64_t lo = std::min<int64_t>((int64_t)ta * B, N);
+                const int64_t hi = std::min<int64_t>((int64_t)tb * B, N);
+                for (int32_t t = ta; t < tb; ++t)
                     for (int32_t k = hoff[t]; k < hoff[t + 1]; ++k)
                         if (hg[k] < lo || hg[k] >= hi) {
                             iface.push_back(hg[k]);
@@ -496,11 +563,7 @@ int ensure_order(mag_ctx *ctx)
         // rank puts the largest of the tiles it built into its own word of a vector, one sum-all-reduce, the maximum
         double hv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         hv[me] = (double)max_halo;
-        std::string msg;
-        HIPCHK(hipMemcpyAsync(ctx->comm_pq.p, hv, 64, hipMemcpyHostToDevice, s));
-        if (int rc = ctx->comm.allreduce_sum(ctx->comm_pq.as<double>(), 8, s, msg)) return fail(ctx, rc, "%s", msg.c_str());
-        HIPCHK(hipMemcpyAsync(hv, ctx->comm_pq.p, 64, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
+        if (int rc = allreduce_host(ctx, hv, 8)) return rc;
         for (int r_ = 0; r_ < R; ++r_) max_halo = std::max(max_halo, (int32_t)hv[r_]);
     }
     ctx->max_halo = max_halo;
@@ -538,11 +601,7 @@ int ensure_order(mag_ctx *ctx)
             HIPCHK(hipMemcpyAsync(&ff, ctx->tile_rdeg.as<int32_t>() + 2 * (size_t)T, 4, hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             double fv[2] = {(double)(ff & 1), (double)((ff >> 1) & 1)};
-            std::string msg;
-            HIPCHK(hipMemcpyAsync(ctx->comm_pq.p, fv, 16, hipMemcpyHostToDevice, s));
-            if (int rc = ctx->comm.allreduce_sum(ctx->comm_pq.as<double>(), 2, s, msg)) return fail(ctx, rc, "%s", msg.c_str());
-            HIPCHK(hipMemcpyAsync(fv, ctx->comm_pq.p, 16, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
+            if (int rc = allreduce_host(ctx, fv, 2)) return rc;
             ctx->fan_flags_global = (fv[0] > 0.0 ? 1 : 0) | (fv[1] > 0.0 ? 2 : 0);
         }
     } else {
@@ -570,7 +629,7 @@ int ensure_order(mag_ctx *ctx)
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         const int pthreads = magk::persist_threads();
         const int kmax = magk::persist_tiles_per_wg(B, pthreads);
-        const int32_t tiles_max = (T + R - 1) / R; // the most tiles any rank runs
+        const int32_t tiles_max = most_rank_tiles(T, R);
         int k = cus > 0 ? (tiles_max + cus - 1) / cus : 0;
         // a mesh of at most kmax tiles on one GPU (up to 2048 nodes: the size of the reference's own examples) goes to ONE
         // workgroup: every tile is a sibling of every other, nothing is exchanged through memory (persist_single_workgroup)
@@ -798,9 +857,7 @@ magk::OpParams op_params(mag_ctx *ctx)
         P.ell = ctx->ell.as<int2>();
     }
     P.wt = ctx->tune_wt;
-    P.c0 = ctx->youngs * ctx->thick / (2.0 * (1.0 - ctx->nu * ctx->nu));
-    P.nu = ctx->nu;
-    P.h = (1.0 - ctx->nu) / 2.0;
+    set_material(ctx, P);
     return P;
 }
 
@@ -886,9 +943,7 @@ int launch_block(mag_ctx *ctx, int G)
             // p.q: sum of this rank's partials -> comm_pq[0] -> sum over ranks
             magk::iface_pack(ctx->partPQ.as<double>(), nloc, nullptr, nullptr, 0, 0, 0, ctx->comm_pq.as<double>(),
                              ctx->stream);
-            std::string msg;
-            if (int rc = ctx->comm.allreduce_sum(ctx->comm_pq.as<double>(), 1, ctx->stream, msg))
-                return fail(ctx, rc, "%s", msg.c_str());
+            if (int rc = allreduce(ctx, ctx->comm_pq.as<double>(), 1)) return rc;
         }
         magk::upd_launch(U, ctx->B, ctx->stream);
         if (ctx->dist) {
@@ -896,9 +951,7 @@ int launch_block(mag_ctx *ctx, int G)
             // then the other ranks' interface residuals are written into this rank's copy of r
             magk::iface_pack(ctx->partRR.as<double>(), nloc, ctx->r.as<double2>(), ctx->iface.as<int32_t>(),
                              ctx->n_iface, ctx->own0, ctx->own1, ctx->comm_rr.as<double>(), ctx->stream);
-            std::string msg;
-            if (int rc = ctx->comm.allreduce_sum(ctx->comm_rr.as<double>(), 1 + 2 * (int64_t)ctx->n_iface, ctx->stream, msg))
-                return fail(ctx, rc, "%s", msg.c_str());
+            if (int rc = allreduce(ctx, ctx->comm_rr.as<double>(), 1 + 2 * (int64_t)ctx->n_iface)) return rc;
             magk::iface_unpack(ctx->comm_rr.as<double>(), ctx->iface.as<int32_t>(), ctx->n_iface, ctx->own0,
                                ctx->own1, ctx->r.as<double2>(), ctx->stream);
         }
@@ -907,23 +960,27 @@ int launch_block(mag_ctx *ctx, int G)
     return MAG_OK;
 }
 
-int ensure_graph(mag_ctx *ctx, int G)
+// the fields every graph key holds: the buffers and scalars the captured launches read (at most 18 words), the sizes, and
+// the material constants, which are baked into the kernel arguments too
+mag_ctx::GraphKey graph_key(const mag_ctx *ctx, int G, std::initializer_list<void *> ptrs)
 {
     mag_ctx::GraphKey k = {};
-    void *ptrs[] = {ctx->x.p,  ctx->r.p,      ctx->p0.p,     ctx->p1.p,    ctx->q.p,        ctx->partRR.p,
-                    ctx->partPQ.p, ctx->state.p, ctx->hist.p,   ctx->xyP.p,   ctx->maskP.p,    ctx->tile_deg.p,
-                    ctx->tile_off.p, ctx->ell.p, ctx->tile_hoff.p, ctx->halo_g.p,
-                    (void *)(intptr_t)(ctx->use_lds ? ctx->cap : -1), ctx->halo_xy.p};
-    for (size_t i = 0; i < sizeof(ptrs) / sizeof(ptrs[0]); ++i) k.ptrs[i] = ptrs[i];
+    assert(ptrs.size() <= 18);
+    std::copy(ptrs.begin(), ptrs.end(), k.ptrs);
     k.N = ctx->N;
     k.T = ctx->T;
     k.B = ctx->B;
     k.G = G;
     k.hist_len = ctx->opt.history_len;
-    // material constants are baked into the kernel arguments too
-    double mat[2] = {ctx->youngs * ctx->thick, ctx->nu};
-    memcpy(&k.ptrs[18], &mat[0], 8);
-    memcpy(&k.ptrs[19], &mat[1], 8);
+    const double mat[2] = {ctx->youngs * ctx->thick, ctx->nu};
+    memcpy(&k.ptrs[18], mat, sizeof mat);
+    return k;
+}
+
+// ctx->graph: the block `enqueue` puts on the stream, captured again whenever the key differs from the last one
+template <class Enqueue>
+int capture_graph(mag_ctx *ctx, const mag_ctx::GraphKey &k, Enqueue enqueue)
+{
     if (ctx->graph && memcmp(&k, &ctx->gkey, sizeof k) == 0) return MAG_OK;
     if (ctx->graph) {
         (void)hipGraphExecDestroy(ctx->graph);
@@ -931,7 +988,7 @@ int ensure_graph(mag_ctx *ctx, int G)
     }
     hipGraph_t g = nullptr;
     HIPCHK(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = launch_block(ctx, G);
+    const int rc = enqueue();
     const hipError_t e = hipStreamEndCapture(ctx->stream, &g);
     if (rc) return rc;
     if (e != hipSuccess) return fail(ctx, MAG_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
@@ -945,6 +1002,57 @@ int ensure_graph(mag_ctx *ctx, int G)
     return MAG_OK;
 }
 
+int ensure_graph(mag_ctx *ctx, int G)
+{
+    const mag_ctx::GraphKey k =
+        graph_key(ctx, G, {ctx->x.p, ctx->r.p, ctx->p0.p, ctx->p1.p, ctx->q.p, ctx->partRR.p, ctx->partPQ.p, ctx->state.p,
+                           ctx->hist.p, ctx->xyP.p, ctx->maskP.p, ctx->tile_deg.p, ctx->tile_off.p, ctx->ell.p,
+                           ctx->tile_hoff.p, ctx->halo_g.p, (void *)(intptr_t)(ctx->use_lds ? ctx->cap : -1), ctx->halo_xy.p});
+    return capture_graph(ctx, k, [&] { return launch_block(ctx, G); });
+}
+
+int launch_graph(mag_ctx *ctx)
+{
+    HIPCHK(hipGraphLaunch(ctx->graph, ctx->stream));
+    return MAG_OK;
+}
+
+// solver.rs:139-176's loop, G iterations per block (enqueue_block): the host polls the device-side state one block behind
+// the one it has just queued, so the GPU never waits for the host.  Iterate j is produced by launch j and judged by launch
+// j+1: up to two launches more than iterations.
+template <class State, class Enqueue>
+int run_blocks(mag_ctx *ctx, const DevBuf &dev_state, State *host_slots, Enqueue enqueue_block)
+{
+    hipStream_t s = ctx->stream;
+    const long long max_blocks = (long long)(ctx->opt.max_iter / ctx->opt.check_every) + 3;
+    bool done = false;
+    int slot = 0;
+    for (long long blk = 0; blk < max_blocks && !done; ++blk) {
+        if (int rc = enqueue_block()) return rc;
+        HIPCHK(hipMemcpyAsync(&host_slots[slot], dev_state.p, sizeof(State), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipEventRecord(ctx->evPoll[slot], s));
+        if (blk >= 1) {
+            HIPCHK(hipEventSynchronize(ctx->evPoll[slot ^ 1]));
+            done = host_slots[slot ^ 1].done != 0;
+        }
+        slot ^= 1;
+    }
+    return MAG_OK;
+}
+
+// the final state of a solve (CgState or FusedState) into the statistics and argmin's best_param bookkeeping
+template <class State>
+void take_stats(mag_ctx *ctx, const State &st)
+{
+    ctx->stats.iterations = st.iterations;
+    ctx->stats.final_cost = st.final_cost;
+    ctx->stats.rhs_norm = std::sqrt(st.bb);
+    ctx->stats.converged = st.converged;
+    ctx->stats.breakdown = st.breakdown;
+    ctx->best_cost = st.best_cost;
+    ctx->best_iter = st.best_iter;
+}
+
 // Every rank returns the whole solution, as solver::run would: the owned node ranges (contiguous in the Hilbert order,
 // equal up to one tile) are all-gathered -- (R-1)/R of the vector per GPU over the ring, half of what summing a
 // zero-padded full vector costs -- and copied to their places.
@@ -954,7 +1062,7 @@ int gather_solution(mag_ctx *ctx)
     if (R <= 1 && !ctx->dist) return MAG_OK;
     hipStream_t s = ctx->stream;
     const int64_t N = ctx->N, B = ctx->B, T = ctx->T;
-    auto lo = [&](int r) { return std::min<int64_t>((((int64_t)T * r) / R) * B, N); };
+    auto lo = [&](int r) { return std::min<int64_t>(rank_tile_lo(T, R, r) * B, N); };
     int64_t most = 0;
     for (int r = 0; r < R; ++r) most = std::max(most, lo(r + 1) - lo(r));
     const size_t cnt = 2 * (size_t)most; // doubles per rank
@@ -964,9 +1072,7 @@ int gather_solution(mag_ctx *ctx)
     HIPCHK(hipMemsetAsync(ctx->gath_send.p, 0, 8 * cnt, s));
     HIPCHK(hipMemcpyAsync(ctx->gath_send.p, ctx->x.as<double>() + 2 * (size_t)ctx->own0, 16 * (size_t)mine,
                           hipMemcpyDeviceToDevice, s));
-    std::string msg;
-    if (int rc = ctx->comm.allgather(ctx->gath_send.as<double>(), ctx->gath_recv.as<double>(), (int64_t)cnt, s, msg))
-        return fail(ctx, rc, "%s", msg.c_str());
+    if (int rc = allgather(ctx, ctx->gath_send.as<double>(), ctx->gath_recv.as<double>(), (int64_t)cnt)) return rc;
     for (int r = 0; r < R; ++r)
         if (lo(r + 1) > lo(r))
             HIPCHK(hipMemcpyAsync(ctx->x.as<double>() + 2 * (size_t)lo(r), ctx->gath_recv.as<double>() + cnt * (size_t)r,
@@ -974,8 +1080,7 @@ int gather_solution(mag_ctx *ctx)
     return MAG_OK;
 }
 
-// solver.rs:139-176 on the device: blocks of G iterations; the host polls the device-side state one
-// block behind the one it has just queued, so the GPU never waits for the host.
+// solver.rs:139-176 on the device: two launches per iteration (operator, update)
 int cg_phase(mag_ctx *ctx)
 {
     hipStream_t s = ctx->stream;
@@ -988,9 +1093,7 @@ int cg_phase(mag_ctx *ctx)
     if (ctx->dist) {
         magk::iface_pack(ctx->partRR.as<double>(), magk::cg_grid(ctx->T), nullptr, nullptr, 0, 0, 0,
                          ctx->comm_rr.as<double>(), s);
-        std::string msg;
-        if (int rc = ctx->comm.allreduce_sum(ctx->comm_rr.as<double>(), 1, s, msg))
-            return fail(ctx, rc, "%s", msg.c_str());
+        if (int rc = allreduce(ctx, ctx->comm_rr.as<double>(), 1)) return rc;
         magk::cg_setup(ctx->comm_rr.as<double>(), 1, ctx->opt.stop_mode, ctx->opt.tol, (long long)ctx->opt.max_iter,
                        ctx->state.as<CgState>(), s);
     } else {
@@ -1004,39 +1107,77 @@ int cg_phase(mag_ctx *ctx)
     const bool graph = ctx->opt.use_graph != 0 && !ctx->dist;
     if (graph)
         if (int rc = ensure_graph(ctx, G)) return rc;
-    const long long max_blocks = (long long)(ctx->opt.max_iter / G) + 3;
-    bool done = false;
-    int slot = 0;
-    for (long long blk = 0; blk < max_blocks && !done; ++blk) {
-        if (graph) {
-            HIPCHK(hipGraphLaunch(ctx->graph, s));
-        } else if (int rc = launch_block(ctx, G)) {
-            return rc;
-        }
-        HIPCHK(hipMemcpyAsync(&ctx->h_state[slot], ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipEventRecord(ctx->evPoll[slot], s));
-        if (blk >= 1) {
-            HIPCHK(hipEventSynchronize(ctx->evPoll[slot ^ 1]));
-            done = ctx->h_state[slot ^ 1].done != 0;
-        }
-        slot ^= 1;
-    }
+    if (int rc = run_blocks(ctx, ctx->state, ctx->h_state, [&] { return graph ? launch_graph(ctx) : launch_block(ctx, G); }))
+        return rc;
     if (ctx->dist)
         if (int rc = gather_solution(ctx)) return rc;
     HIPCHK(hipMemcpyAsync(&ctx->h_state[2], ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    const CgState &st = ctx->h_state[2];
-    ctx->stats.iterations = st.iterations;
-    ctx->stats.final_cost = st.final_cost;
-    ctx->stats.rhs_norm = std::sqrt(st.bb);
-    ctx->stats.converged = st.converged;
-    ctx->stats.breakdown = st.breakdown;
-    ctx->best_cost = st.best_cost;
-    ctx->best_iter = st.best_iter;
+    take_stats(ctx, ctx->h_state[2]);
     return MAG_OK;
 }
 
 // ---- fused variant: one launch per CG iteration (cg.hip, k_cg_fused) ----
+// interface slot tables of the multi-GPU exchange (k_comm_slots): where the q of an owned or a halo node sits in it
+int ensure_qslots(mag_ctx *ctx)
+{
+    HIPCHK(ctx->own_qslot.reserve(4 * (size_t)ctx->N));
+    HIPCHK(ctx->halo_qslot.reserve(4 * (size_t)std::max<int64_t>(ctx->halo_total, 1)));
+    magk::comm_slots(ctx->iface.as<int32_t>(), ctx->n_iface, ctx->own0, ctx->own1, ctx->halo_g.as<int32_t>(),
+                     ctx->halo_total, ctx->N, ctx->own_qslot.as<int32_t>(), ctx->halo_qslot.as<int32_t>(), ctx->stream);
+    return MAG_OK;
+}
+
+// exchange buffers of the streaming kernels across ranks, one per parity: [nsums x g_all dot partials | q of the interface
+// nodes].  Every rank computes the same g_all: same device, same cap, the most tiles of any rank.
+int reserve_exchange(mag_ctx *ctx, int32_t g_all, int nsums)
+{
+    ctx->g_all = g_all;
+    ctx->cwords = (size_t)nsums * g_all + 2 * (size_t)ctx->n_iface;
+    HIPCHK(ctx->comm_f.reserve(8 * 2 * ctx->cwords + 64));
+    return ensure_qslots(ctx);
+}
+
+// a fused launch's view of the exchange buffers: launch `par` reads the all-reduced buffer [par], fills buffer [par ^ 1]
+template <class Params>
+void set_exchange(const mag_ctx *ctx, int par, int nsums, Params &P)
+{
+    double *cin = ctx->comm_f.as<double>() + (size_t)par * ctx->cwords;
+    double *cout = ctx->comm_f.as<double>() + (size_t)(par ^ 1) * ctx->cwords;
+    P.part_in = cin;
+    P.part_stride_in = ctx->g_all;
+    P.nPart = ctx->g_all;
+    P.part_out = cout;
+    P.part_stride = ctx->g_all;
+    P.comm_in_q = (const double2 *)(cin + (size_t)nsums * ctx->g_all);
+    P.comm_out_q = (double2 *)(cout + (size_t)nsums * ctx->g_all);
+    P.own_qslot = ctx->own_qslot.as<int32_t>();
+    P.halo_qslot = ctx->halo_qslot.as<int32_t>();
+}
+
+// start of a fused solve (fp64 or fp32): init(part, stride) writes the b.b partials into partial buffer 0, then the state is
+// set up from them.  One GPU: the kernel's own buffers of part_words sums per slot, `grid` slots.  Across ranks: exchange
+// buffer 0 (its q part = q_{-1} = 0), summed over ranks in place.
+template <class Init>
+int setup_exchange(mag_ctx *ctx, int32_t grid, int part_words, Init init)
+{
+    using magk::FusedState;
+    hipStream_t s = ctx->stream;
+    const bool dist = ctx->dist;
+    double *part = (dist ? ctx->comm_f : ctx->fpart).as<double>();
+    const int32_t stride = dist ? ctx->g_all : magk::kMaxGrid;
+    HIPCHK(hipMemsetAsync(part, 0, 8 * 2 * (dist ? ctx->cwords : (size_t)part_words * stride), s));
+    init(part, stride);
+    if (dist)
+        if (int rc = allreduce(ctx, part, (int64_t)ctx->cwords)) return rc;
+    magk::fused_setup(part, dist ? ctx->g_all : grid, stride, ctx->opt.stop_mode, ctx->opt.tol, (long long)ctx->opt.max_iter,
+                      ctx->fstate.as<FusedState>(), s);
+    if (dist && ctx->si) // tags of this solve's exchanges: sequence number << 24 + the launch counter (k_stream_exchange)
+        HIPCHK(hipMemcpyAsync((char *)ctx->fstate.p + offsetof(FusedState, exchange_tag_base), &ctx->si_tag_base, 4,
+                              hipMemcpyHostToDevice, s));
+    return MAG_OK;
+}
+
 magk::FusedParams fused_params(mag_ctx *ctx, int par)
 {
     magk::FusedParams P = {};
@@ -1059,25 +1200,12 @@ magk::FusedParams fused_params(mag_ctx *ctx, int par)
     P.halo_g = ctx->halo_g.as<int32_t>();
     P.halo_xy = ctx->halo_xy.as<double2>();
     P.iface = ctx->iface.as<int32_t>();
-    P.c0 = ctx->youngs * ctx->thick / (2.0 * (1.0 - ctx->nu * ctx->nu));
-    P.nu = ctx->nu;
-    P.h = (1.0 - ctx->nu) / 2.0;
+    set_material(ctx, P);
     P.in = (par ? ctx->rqp1 : ctx->rqp0).as<magk::Rqp>();
     P.out = (par ? ctx->rqp0 : ctx->rqp1).as<magk::Rqp>();
     P.x = ctx->x.as<double2>();
     if (ctx->dist) {
-        // exchange buffers, one per parity: launch `par` reads the all-reduced buffer [par], fills buffer [par ^ 1]
-        double *cin = ctx->comm_f.as<double>() + (size_t)par * ctx->cwords;
-        double *cout = ctx->comm_f.as<double>() + (size_t)(par ^ 1) * ctx->cwords;
-        P.part_in = cin;
-        P.part_stride_in = ctx->g_all;
-        P.nPart = ctx->g_all;
-        P.part_out = cout;
-        P.part_stride = ctx->g_all;
-        P.comm_in_q = (const double2 *)(cin + (size_t)ctx->nsums() * ctx->g_all);
-        P.comm_out_q = (double2 *)(cout + (size_t)ctx->nsums() * ctx->g_all);
-        P.own_qslot = ctx->own_qslot.as<int32_t>();
-        P.halo_qslot = ctx->halo_qslot.as<int32_t>();
+        set_exchange(ctx, par, ctx->nsums(), P);
     } else {
         double *part = ctx->fpart.as<double>();
         P.part_out = part + (size_t)(par ^ 1) * 5 * stride;
@@ -1110,9 +1238,7 @@ int fused_block(mag_ctx *ctx, int G)
         } else if (ctx->dist) {
             // the iteration's ONE collective, in place on the buffer the launch just filled:
             // [r.r, p.q, r.q, q.q partials, slot by slot | q on interface nodes (owner's value + zeros)]
-            std::string msg;
-            if (int rc = ctx->comm.allreduce_sum(P.part_out, (int64_t)ctx->cwords, ctx->stream, msg))
-                return fail(ctx, rc, "%s", msg.c_str());
+            if (int rc = allreduce(ctx, P.part_out, (int64_t)ctx->cwords)) return rc;
         }
     }
     HIPCHK(hipGetLastError());
@@ -1137,42 +1263,19 @@ int reserve_fused(mag_ctx *ctx)
                         ctx->halo_minv.as<float4>(), ctx->stream);
     }
     ctx->fgrid = magk::fused_grid(ctx->B, ctx->cap, ctx->t1 - ctx->t0, ctx->dist, ctx->pre);
-    if (ctx->dist) {
-        // every rank computes the same g_all: same device, same cap, tile counts from the same arithmetic
-        const int R = ctx->comm.nranks;
-        int32_t most = 1;
-        for (int r = 0; r < R; ++r) {
-            const int32_t n = (int32_t)(((int64_t)ctx->T * (r + 1)) / R - ((int64_t)ctx->T * r) / R);
-            most = std::max(most, n);
-        }
-        ctx->g_all = magk::fused_grid(ctx->B, ctx->cap, most, true, ctx->pre);
-        ctx->cwords = (size_t)ctx->nsums() * ctx->g_all + 2 * (size_t)ctx->n_iface;
-        HIPCHK(ctx->comm_f.reserve(8 * 2 * ctx->cwords + 64));
-        HIPCHK(ctx->own_qslot.reserve(4 * (size_t)ctx->N));
-        HIPCHK(ctx->halo_qslot.reserve(4 * (size_t)std::max<int64_t>(ctx->halo_total, 1)));
-        magk::comm_slots(ctx->iface.as<int32_t>(), ctx->n_iface, ctx->own0, ctx->own1, ctx->halo_g.as<int32_t>(),
-                         ctx->halo_total, ctx->N, ctx->own_qslot.as<int32_t>(), ctx->halo_qslot.as<int32_t>(),
-                         ctx->stream);
-    }
+    if (ctx->dist)
+        return reserve_exchange(
+            ctx, magk::fused_grid(ctx->B, ctx->cap, most_rank_tiles(ctx->T, ctx->comm.nranks), true, ctx->pre), ctx->nsums());
     return MAG_OK;
 }
 
 int ensure_fused_graph(mag_ctx *ctx, int G)
 {
-    mag_ctx::GraphKey k = {};
-    void *ptrs[] = {ctx->x.p,   ctx->rqp0.p,  ctx->rqp1.p,     ctx->fpart.p,  ctx->fstate.p, ctx->hist.p,
-                    ctx->xyP.p, ctx->maskP.p, ctx->tmeta.p,    ctx->ell.p,    ctx->halo_g.p, ctx->halo_xy.p,
-                    ctx->iface.p, (void *)(intptr_t)ctx->cap, (void *)(intptr_t)(1 + ctx->fgrid) /* fused */,
-                    ctx->pre ? ctx->minvP.p : nullptr, ctx->pre ? ctx->halo_minv.p : nullptr};
-    for (size_t i = 0; i < sizeof(ptrs) / sizeof(ptrs[0]); ++i) k.ptrs[i] = ptrs[i];
-    k.N = ctx->N;
-    k.T = ctx->T;
-    k.B = ctx->B;
-    k.G = G;
-    k.hist_len = ctx->opt.history_len;
-    double mat[2] = {ctx->youngs * ctx->thick, ctx->nu};
-    memcpy(&k.ptrs[18], &mat[0], 8);
-    memcpy(&k.ptrs[19], &mat[1], 8);
+    mag_ctx::GraphKey k =
+        graph_key(ctx, G, {ctx->x.p, ctx->rqp0.p, ctx->rqp1.p, ctx->fpart.p, ctx->fstate.p, ctx->hist.p, ctx->xyP.p,
+                           ctx->maskP.p, ctx->tmeta.p, ctx->ell.p, ctx->halo_g.p, ctx->halo_xy.p, ctx->iface.p,
+                           (void *)(intptr_t)ctx->cap, (void *)(intptr_t)(1 + ctx->fgrid) /* fused */,
+                           ctx->pre ? ctx->minvP.p : nullptr, ctx->pre ? ctx->halo_minv.p : nullptr});
     if (ctx->dist) { // only the inbox exchange is captured (two kernels per iteration, no host work)
         void *dp[] = {ctx->comm_f.p, ctx->own_qslot.p, ctx->halo_qslot.p, ctx->iface_readers.p};
         for (int i = 0; i < 4; ++i) k.dptrs[i] = dp[i];
@@ -1181,25 +1284,7 @@ int ensure_fused_graph(mag_ctx *ctx, int G)
                               ctx->t0, ctx->t1, (int32_t)ctx->si_spin, (int32_t)ctx->cwords, ctx->nsums()};
         for (int i = 0; i < 12; ++i) k.d[i] = dv[i];
     }
-    if (ctx->graph && memcmp(&k, &ctx->gkey, sizeof k) == 0) return MAG_OK;
-    if (ctx->graph) {
-        (void)hipGraphExecDestroy(ctx->graph);
-        ctx->graph = nullptr;
-    }
-    hipGraph_t g = nullptr;
-    HIPCHK(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = fused_block(ctx, G);
-    const hipError_t e = hipStreamEndCapture(ctx->stream, &g);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(ctx, MAG_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
-    const hipError_t ei = hipGraphInstantiate(&ctx->graph, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (ei != hipSuccess) {
-        ctx->graph = nullptr;
-        return fail(ctx, MAG_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ei));
-    }
-    ctx->gkey = k;
-    return MAG_OK;
+    return capture_graph(ctx, k, [&] { return fused_block(ctx, G); });
 }
 
 int cg_phase_fused(mag_ctx *ctx)
@@ -1207,7 +1292,6 @@ int cg_phase_fused(mag_ctx *ctx)
     using magk::FusedState;
     hipStream_t s = ctx->stream;
     if (int rc = reserve_fused(ctx)) return rc;
-    const int32_t stride = magk::kMaxGrid;
     HIPCHK(hipMemsetAsync(ctx->x.p, 0, 16 * (size_t)ctx->N, s));
     ctx->si = false;
     if (ctx->dist) {
@@ -1220,34 +1304,18 @@ int cg_phase_fused(mag_ctx *ctx)
                   ctx->inbox_bytes >= 64 + 128 * (size_t)R + 64 * (size_t)ctx->n_iface &&
                   ctx->opt.max_iter < (int64_t(1) << 24) - 4;
         if (ctx->si) {
-            ctx->solve_seq = (ctx->solve_seq + 1) & 0xffu;
-            if (ctx->solve_seq == 0) ctx->solve_seq = 1;
-            ctx->si_tag_base = ctx->solve_seq << 24;
+            ctx->si_tag_base = next_solve_seq(ctx) << 24;
             ctx->si_spin = 1u << 20;
             if (const char *sp = getenv("MAG_TUNE_STREAM_SPIN")) ctx->si_spin = (uint32_t)atoi(sp); // tests: force the fallback
             // nothing of an earlier use of the inbox may look current: cleared before the all-reduce below lines the ranks up
             HIPCHK(hipMemsetAsync(ctx->inbox_own, 0, 64 + 128 * (size_t)R + 64 * (size_t)ctx->n_iface, s));
         }
-        // b.b partials go straight into exchange buffer 0 (its q part = q_{-1} = 0), summed over ranks in place
-        double *c0 = ctx->comm_f.as<double>();
-        HIPCHK(hipMemsetAsync(c0, 0, 8 * 2 * ctx->cwords, s));
-        magk::fused_init(ctx->bP.as<double2>(), ctx->pre ? ctx->minvP.as<float4>() : nullptr, ctx->rqp0.as<magk::Rqp>(),
-                         ctx->rqp1.as<magk::Rqp>(), ctx->N, ctx->B, ctx->T, ctx->t0, ctx->t1, c0, ctx->g_all, ctx->fgrid, s);
-        std::string msg;
-        if (int rc = ctx->comm.allreduce_sum(c0, (int64_t)ctx->cwords, s, msg)) return fail(ctx, rc, "%s", msg.c_str());
-        magk::fused_setup(c0, ctx->g_all, ctx->g_all, ctx->opt.stop_mode, ctx->opt.tol, (long long)ctx->opt.max_iter,
-                          ctx->fstate.as<FusedState>(), s);
-        if (ctx->si) // tags of this solve's exchanges: sequence number << 24 + the launch counter (k_stream_exchange)
-            HIPCHK(hipMemcpyAsync((char *)ctx->fstate.p + offsetof(FusedState, exchange_tag_base), &ctx->si_tag_base, 4,
-                                  hipMemcpyHostToDevice, s));
-    } else {
-        HIPCHK(hipMemsetAsync(ctx->fpart.p, 0, 8 * 2 * 5 * (size_t)stride, s));
-        magk::fused_init(ctx->bP.as<double2>(), ctx->pre ? ctx->minvP.as<float4>() : nullptr, ctx->rqp0.as<magk::Rqp>(),
-                         ctx->rqp1.as<magk::Rqp>(), ctx->N, ctx->B, ctx->T, ctx->t0, ctx->t1, ctx->fpart.as<double>(),
-                         stride, ctx->fgrid, s);
-        magk::fused_setup(ctx->fpart.as<double>(), ctx->fgrid, stride, ctx->opt.stop_mode, ctx->opt.tol,
-                          (long long)ctx->opt.max_iter, ctx->fstate.as<FusedState>(), s);
     }
+    if (int rc = setup_exchange(ctx, ctx->fgrid, 5, [&](double *part, int32_t stride) {
+            magk::fused_init(ctx->bP.as<double2>(), ctx->pre ? ctx->minvP.as<float4>() : nullptr, ctx->rqp0.as<magk::Rqp>(),
+                             ctx->rqp1.as<magk::Rqp>(), ctx->N, ctx->B, ctx->T, ctx->t0, ctx->t1, part, stride, ctx->fgrid, s);
+        }))
+        return rc;
     HIPCHK(hipGetLastError());
 
     const int G = ctx->opt.check_every;
@@ -1257,35 +1325,15 @@ int cg_phase_fused(mag_ctx *ctx)
     if (graph)
         if (int rc = ensure_fused_graph(ctx, G)) return rc;
     ctx->exchange_kind = ctx->dist ? (ctx->si ? 3 : 1) : 0;
-    // iterate j is produced by launch j and judged by launch j+1: two launches more than iterations
-    const long long max_blocks = (long long)(ctx->opt.max_iter / G) + 3;
-    bool done = false;
-    int slot = 0;
-    for (long long blk = 0; blk < max_blocks && !done; ++blk) {
-        if (graph) {
-            HIPCHK(hipGraphLaunch(ctx->graph, s));
-        } else if (int rc = fused_block(ctx, G)) {
-            return rc;
-        }
-        HIPCHK(hipMemcpyAsync(&ctx->h_fstate[slot], ctx->fstate.p, sizeof(FusedState), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipEventRecord(ctx->evPoll[slot], s));
-        if (blk >= 1) {
-            HIPCHK(hipEventSynchronize(ctx->evPoll[slot ^ 1]));
-            done = ctx->h_fstate[slot ^ 1].done != 0;
-        }
-        slot ^= 1;
-    }
+    if (int rc = run_blocks(ctx, ctx->fstate, ctx->h_fstate, [&] { return graph ? launch_graph(ctx) : fused_block(ctx, G); }))
+        return rc;
     if (ctx->si) {
         // did any rank's exchange give up?  All ranks must agree before anyone changes path (as for the on-chip kernel)
         HIPCHK(hipMemcpyAsync(&ctx->h_fstate[2], ctx->fstate.p, sizeof(FusedState), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-        double flag = (ctx->h_fstate[2].exchange_timeout || !ctx->h_fstate[2].done) ? 1.0 : 0.0;
-        std::string msg;
-        HIPCHK(hipMemcpyAsync(ctx->comm_pq.p, &flag, 8, hipMemcpyHostToDevice, s));
-        if (int rc = ctx->comm.allreduce_sum(ctx->comm_pq.as<double>(), 1, s, msg)) return fail(ctx, rc, "%s", msg.c_str());
-        HIPCHK(hipMemcpyAsync(&flag, ctx->comm_pq.p, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (flag != 0.0) {
+        bool gave_up = ctx->h_fstate[2].exchange_timeout || !ctx->h_fstate[2].done;
+        if (int rc = any_rank(ctx, gave_up)) return rc;
+        if (gave_up) {
             HIPCHK(hipMemsetAsync(ctx->inbox_own, 0, 64, s)); // the timeout word
             ctx->si_failed = true;
             ctx->exchange_timed_out = true;
@@ -1297,18 +1345,81 @@ int cg_phase_fused(mag_ctx *ctx)
         if (int rc = gather_solution(ctx)) return rc;
     HIPCHK(hipMemcpyAsync(&ctx->h_fstate[2], ctx->fstate.p, sizeof(FusedState), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    const FusedState &st = ctx->h_fstate[2];
-    ctx->stats.iterations = st.iterations;
-    ctx->stats.final_cost = st.final_cost;
-    ctx->stats.rhs_norm = std::sqrt(st.bb);
-    ctx->stats.converged = st.converged;
-    ctx->stats.breakdown = st.breakdown;
-    ctx->best_cost = st.best_cost;
-    ctx->best_iter = st.best_iter;
+    take_stats(ctx, ctx->h_fstate[2]);
     return MAG_OK;
 }
 
 // ---- on-chip variant: ONE launch for the whole solve (persist.hip, k_cg_persist) ----
+// Which instantiation (mode): edge blocks in registers when every row of the mesh is one short fan (1; k_ring16 left the
+// answer behind tile_rdeg's two arrays), the triangle walk with cached weights otherwise (0).  One 4-byte read per solve.
+// Round 4: a mesh whose rows are single fans of ANY length (flag word 1: gmsh-type meshes, a quarter of their nodes with
+// seven neighbours) runs the edge-block kernel too, the blocks beyond six per node as 32-byte records in an LDS pool -- if
+// every workgroup's records fit the LDS its more compact layout leaves free (2; P then carries the pool); the walk otherwise.
+// (several ranks: the ordering phase is replicated, so every rank reads the same flag.  The multi-GPU edge-block
+// instantiation is the default since round 4 -- two ranks sharing the GPU at four tiles per workgroup: 9.1 against 10.7 us
+// per iteration, fixture parity on both ranks --; MAG_TUNE_PERSIST_MG_BLOCKS=0 keeps the triangle walk across ranks)
+int choose_edge_blocks(mag_ctx *ctx, bool mg, magk::PersistParams &P, int &mode)
+{
+    hipStream_t s = ctx->stream;
+    mode = 0;
+    const char *mgb = getenv("MAG_TUNE_PERSIST_MG_BLOCKS");
+    if ((mg && mgb && atoi(mgb) == 0) || getenv("MAG_TUNE_PERSIST_TRIANGLES")) return MAG_OK;
+    int32_t fan_flags = 3;
+    if (ctx->order_sharded) { // (this rank's ring words cover its own tiles only: the ordering phase has OR-ed the flags over the ranks)
+        fan_flags = ctx->fan_flags_global;
+    } else {
+        HIPCHK(hipMemcpyAsync(&fan_flags, ctx->tile_rdeg.as<int32_t>() + 2 * (size_t)ctx->T, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    if (fan_flags == 0) mode = 1;
+    const char *no_ovf = getenv("MAG_TUNE_PERSIST_NO_OVERFLOW");
+    const char *mgo = getenv("MAG_TUNE_PERSIST_MG_OVERFLOW"); // =0: several ranks keep the triangle walk on such meshes
+    if (!((fan_flags == 1 && !(no_ovf && atoi(no_ovf))) || (fan_flags == 0 && getenv("MAG_TUNE_PERSIST_FORCE_OVERFLOW"))) ||
+        (mg && mgo && atoi(mgo) == 0))
+        return MAG_OK;
+    // per-node overflow counts -> scan -> the limits the LDS must meet
+    const int nb = magk::persist_block_entries();
+    const int64_t npad = (int64_t)ctx->T * ctx->B;
+    HIPCHK(ctx->ovf_cnt.reserve(4 * ((size_t)npad + 1)));
+    HIPCHK(ctx->ovf_off.reserve(4 * ((size_t)npad + 1) + 16));
+    magk::ovf_counts(ctx->row_info.as<uint8_t>(), npad, nb, ctx->ovf_cnt.as<int32_t>(), s);
+    if (int rc = scan_i32(ctx, ctx->ovf_cnt.as<int32_t>(), ctx->ovf_off.as<int32_t>(), (size_t)npad + 1)) return rc;
+    int32_t *lim_d = ctx->ovf_cnt.as<int32_t>(); // (the counts are not needed after the scan: their first words hold the limits)
+    HIPCHK(hipMemsetAsync(lim_d, 0, 8, s));
+    // (several ranks: the limits over EVERY rank's workgroups -- the ordering phase is replicated --, so that all ranks reach
+    // the same decision; sharded ordering phase: only the own tiles' rows are known here -- the ranks vote below)
+    const int R = ctx->comm.nranks;
+    for (int r_ = 0; r_ < R; ++r_) {
+        if (ctx->order_sharded && r_ != ctx->comm.rank) continue;
+        magk::ovf_limits(ctx->ovf_off.as<int32_t>(), ctx->B, ctx->persist_k, rank_tile_lo(ctx->T, R, r_),
+                         rank_tile_lo(ctx->T, R, r_ + 1), lim_d, s);
+    }
+    int32_t lim[3] = {0, 0, 0};
+    HIPCHK(hipMemcpyAsync(lim, lim_d, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&lim[2], ctx->ovf_off.as<int32_t>() + npad, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const int32_t pool = ((lim[0] + 1 + 7) / 8) * 8; // + record 0, the zero block
+    // 12 bits of pool position and 4 bits of count per node slot; the kernel's static LDS on top of the dynamic
+    bool walk = !(lim[0] + 1 <= 4095 && lim[1] <= 15 &&
+                  magk::persist_lds_bytes(ctx->B, ctx->cap, ctx->persist_maxh, magk::persist_threads(), 2, pool, mg) + 256 <=
+                      160 * 1024);
+    // one instantiation for all ranks: a rank whose pool does not fit sends everybody to the walk
+    if (ctx->order_sharded)
+        if (int rc = any_rank(ctx, walk)) return rc;
+    if (walk) {
+        if (ctx->opt.verbose)
+            printf("info: edge blocks with overflow do not fit (%d records in a workgroup, %d at a node): triangle walk\n", lim[0], lim[1]);
+        return MAG_OK;
+    }
+    mode = 2;
+    P.pool_cap = pool;
+    HIPCHK(ctx->ovf_rec.reserve(32 * (size_t)std::max(lim[2], 1)));
+    P.row_info = ctx->row_info.as<uint8_t>();
+    P.ovf_off = ctx->ovf_off.as<int32_t>();
+    P.ovf_rec = ctx->ovf_rec.as<double>();
+    return MAG_OK;
+}
+
 int cg_phase_persist(mag_ctx *ctx)
 {
     using magk::FusedState;
@@ -1330,23 +1441,18 @@ int cg_phase_persist(mag_ctx *ctx)
     P.nranks = 1;
     if (mg) {
         // interface slot tables (as the streaming multi-GPU path uses them), the republished-sums record, the window
-        HIPCHK(ctx->own_qslot.reserve(4 * (size_t)ctx->N));
-        HIPCHK(ctx->halo_qslot.reserve(4 * (size_t)std::max<int64_t>(ctx->halo_total, 1)));
-        magk::comm_slots(ctx->iface.as<int32_t>(), ctx->n_iface, ctx->own0, ctx->own1, ctx->halo_g.as<int32_t>(),
-                         ctx->halo_total, ctx->N, ctx->own_qslot.as<int32_t>(), ctx->halo_qslot.as<int32_t>(), s);
+        if (int rc = ensure_qslots(ctx)) return rc;
         HIPCHK(ctx->grec.reserve(2 * 64));
         HIPCHK(hipMemsetAsync(ctx->grec.p, 0, 2 * 64, s));
         // The window is never zeroed: tags carry the solve's sequence number (same on every rank: all ranks run the
         // same solves) above 24 bits of iteration count, so nothing of an earlier solve can look current (every solve
         // overwrites the slots of the one before; 255 sequence numbers go round).
-        ctx->solve_seq = (ctx->solve_seq + 1) & 0xffu;
-        if (ctx->solve_seq == 0) ctx->solve_seq = 1;
+        P.tag_base = next_solve_seq(ctx) << 24;
         P.t0 = ctx->t0;
         P.t1 = ctx->t1;
         P.rank = ctx->comm.rank;
         P.nranks = R;
         P.n_iface = ctx->n_iface;
-        P.tag_base = ctx->solve_seq << 24;
         P.own_qslot = ctx->own_qslot.as<int32_t>();
         P.halo_qslot = ctx->halo_qslot.as<int32_t>();
         P.win_shared = ctx->inbox_ready ? 0 : 1;
@@ -1358,8 +1464,7 @@ int cg_phase_persist(mag_ctx *ctx)
         // it on every rank -- the grids differ by at most one workgroup, so the largest decides for all
         int cus = 0;
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-        const int32_t tiles_max = (ctx->T + R - 1) / R;
-        const int32_t grid_max = (tiles_max + ctx->persist_k - 1) / ctx->persist_k;
+        const int32_t grid_max = (most_rank_tiles(ctx->T, R) + ctx->persist_k - 1) / ctx->persist_k;
         const char *cw = getenv("MAG_TUNE_COMM_WG");
         P.comm_wg = (ctx->inbox_ready && grid_max + 1 <= cus && (!cw || atoi(cw) != 0)) ? 1 : 0;
     }
@@ -1375,9 +1480,7 @@ int cg_phase_persist(mag_ctx *ctx)
     if (const char *e = getenv("MAG_TUNE_PERSIST_SPIN")) P.spin_limit = (uint32_t)atoi(e); // tests: force the fallback
     P.max_iter = (long long)ctx->opt.max_iter;
     P.tol = ctx->opt.tol;
-    P.c0 = ctx->youngs * ctx->thick / (2.0 * (1.0 - ctx->nu * ctx->nu));
-    P.nu = ctx->nu;
-    P.h = (1.0 - ctx->nu) / 2.0;
+    set_material(ctx, P);
     P.xyP = ctx->xyP.as<double2>();
     P.maskP = ctx->maskP.as<uint8_t>();
     P.meta = ctx->tmeta.as<magk::TileMeta>();
@@ -1394,7 +1497,6 @@ int cg_phase_persist(mag_ctx *ctx)
     if (mg) {
         // every rank's kernel must be running before anybody's spin budget runs out: line the streams up first
         if (!getenv("MAG_TUNE_PERSIST_SPIN")) P.spin_limit = 1u << 21; // ranks start apart: a longer budget
-        std::string msg;
         // Nothing of an earlier use may look current: a window handed over from another context, or slots of the solve
         // 255 sequence numbers ago, could carry this solve's tags.  Every rank clears the extent of ITS inbox this solve
         // will use (rank 0 the shared host window) before the line-up all-reduce: nobody stores into an inbox before
@@ -1407,7 +1509,7 @@ int cg_phase_persist(mag_ctx *ctx)
                 HIPCHK(hipMemsetAsync(ctx->win_dev, 0, used, s));
         }
         HIPCHK(hipMemsetAsync(ctx->comm_pq.p, 0, 8, s));
-        if (int rc = ctx->comm.allreduce_sum(ctx->comm_pq.as<double>(), 1, s, msg)) return fail(ctx, rc, "%s", msg.c_str());
+        if (int rc = allreduce(ctx, ctx->comm_pq.as<double>(), 1)) return rc;
     }
     const bool stamps = magk::persist_stamps_built() && getenv("MAG_TUNE_PERSIST_STAMPS") != nullptr;
     if (stamps) { // diagnostic build only (scripts/persist_phases.sh): phase times per workgroup
@@ -1415,82 +1517,15 @@ int cg_phase_persist(mag_ctx *ctx)
         HIPCHK(hipMemsetAsync(ctx->pstamps.p, 0, 8 * (size_t)magk::persist_stamp_words() * (size_t)(grid + 1), s));
         P.stamps = ctx->pstamps.as<unsigned long long>();
     }
-    // Which instantiation: edge blocks in registers when every row of the mesh is one short fan (k_ring16 left the answer
-    // behind tile_rdeg's two arrays), the triangle walk with cached weights otherwise.  One 4-byte read per solve.
-    // Round 4: a mesh whose rows are single fans of ANY length (flag word 1: gmsh-type meshes, a quarter of their nodes with
-    // seven neighbours) runs the edge-block kernel too, the blocks beyond six per node as 32-byte records in an LDS pool --
-    // if every workgroup's records fit the LDS its more compact layout leaves free (mode 2); the triangle walk otherwise.
     int eb_mode = 0;
-    const int64_t npad = (int64_t)ctx->T * ctx->B;
-    // (several ranks: the ordering phase is replicated, so every rank reads the same flag.  The multi-GPU edge-block
-    // instantiation is the default since round 4 -- two ranks sharing the GPU at four tiles per workgroup: 9.1 against 10.7 us
-    // per iteration, fixture parity on both ranks --; MAG_TUNE_PERSIST_MG_BLOCKS=0 keeps the triangle walk across ranks)
-    const char *mgb = getenv("MAG_TUNE_PERSIST_MG_BLOCKS");
-    if ((!mg || !(mgb && atoi(mgb) == 0)) && !getenv("MAG_TUNE_PERSIST_TRIANGLES")) {
-        int32_t fan_flags = 3;
-        if (ctx->order_sharded) { // (this rank's ring words cover its own tiles only: the ordering phase has OR-ed the flags over the ranks)
-            fan_flags = ctx->fan_flags_global;
-        } else {
-            HIPCHK(hipMemcpyAsync(&fan_flags, ctx->tile_rdeg.as<int32_t>() + 2 * (size_t)ctx->T, 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-        }
-        if (fan_flags == 0) eb_mode = 1;
-        const char *no_ovf = getenv("MAG_TUNE_PERSIST_NO_OVERFLOW");
-        const char *mgo = getenv("MAG_TUNE_PERSIST_MG_OVERFLOW"); // =0: several ranks keep the triangle walk on such meshes
-        if (((fan_flags == 1 && !(no_ovf && atoi(no_ovf))) || (fan_flags == 0 && getenv("MAG_TUNE_PERSIST_FORCE_OVERFLOW"))) &&
-            !(mg && mgo && atoi(mgo) == 0)) {
-            // per-node overflow counts -> scan -> the limits the LDS must meet
-            const int nb = magk::persist_block_entries();
-            HIPCHK(ctx->ovf_cnt.reserve(4 * ((size_t)npad + 1)));
-            HIPCHK(ctx->ovf_off.reserve(4 * ((size_t)npad + 1) + 16));
-            magk::ovf_counts(ctx->row_info.as<uint8_t>(), npad, nb, ctx->ovf_cnt.as<int32_t>(), s);
-            if (int rc = scan_i32(ctx, ctx->ovf_cnt.as<int32_t>(), ctx->ovf_off.as<int32_t>(), (size_t)npad + 1)) return rc;
-            int32_t *lim_d = ctx->ovf_cnt.as<int32_t>(); // (the counts are not needed after the scan: their first words hold the limits)
-            HIPCHK(hipMemsetAsync(lim_d, 0, 8, s));
-            // (several ranks: the limits over EVERY rank's workgroups -- the ordering phase is replicated --, so that all ranks
-            // reach the same decision)
-            // (sharded ordering phase: only the own tiles' rows are known here -- the ranks vote below)
-            for (int r_ = 0; r_ < ctx->comm.nranks; ++r_) {
-                if (ctx->order_sharded && r_ != ctx->comm.rank) continue;
-                const int32_t ta = mg ? (int32_t)(((int64_t)ctx->T * r_) / ctx->comm.nranks) : ctx->t0;
-                const int32_t tb = mg ? (int32_t)(((int64_t)ctx->T * (r_ + 1)) / ctx->comm.nranks) : ctx->t1;
-                magk::ovf_limits(ctx->ovf_off.as<int32_t>(), ctx->B, ctx->persist_k, ta, tb, lim_d, s);
-            }
-            int32_t lim[3] = {0, 0, 0};
-            HIPCHK(hipMemcpyAsync(lim, lim_d, 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(&lim[2], ctx->ovf_off.as<int32_t>() + npad, 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            const int32_t pool = ((lim[0] + 1 + 7) / 8) * 8; // + record 0, the zero block
-            // 12 bits of pool position and 4 bits of count per node slot; the kernel's static LDS on top of the dynamic
-            bool fits = lim[0] + 1 <= 4095 && lim[1] <= 15 &&
-                        magk::persist_lds_bytes(ctx->B, ctx->cap, ctx->persist_maxh, magk::persist_threads(), 2, pool, mg) + 256 <= 160 * 1024;
-            if (ctx->order_sharded) { // one instantiation for all ranks: a rank whose pool does not fit sends everybody to the walk
-                double v = fits ? 0.0 : 1.0;
-                std::string msg;
-                HIPCHK(hipMemcpyAsync(ctx->comm_pq.p, &v, 8, hipMemcpyHostToDevice, s));
-                if (int rc = ctx->comm.allreduce_sum(ctx->comm_pq.as<double>(), 1, s, msg)) return fail(ctx, rc, "%s", msg.c_str());
-                HIPCHK(hipMemcpyAsync(&v, ctx->comm_pq.p, 8, hipMemcpyDeviceToHost, s));
-                HIPCHK(hipStreamSynchronize(s));
-                fits = v == 0.0;
-            }
-            if (fits) {
-                eb_mode = 2;
-                P.pool_cap = pool;
-                HIPCHK(ctx->ovf_rec.reserve(32 * (size_t)std::max(lim[2], 1)));
-                P.row_info = ctx->row_info.as<uint8_t>();
-                P.ovf_off = ctx->ovf_off.as<int32_t>();
-                P.ovf_rec = ctx->ovf_rec.as<double>();
-            } else if (ctx->opt.verbose) {
-                printf("info: edge blocks with overflow do not fit (%d records in a workgroup, %d at a node): triangle walk\n", lim[0], lim[1]);
-            }
-        }
-    }
+    if (int rc = choose_edge_blocks(ctx, mg, P, eb_mode)) return rc;
     ctx->edge_blocks = eb_mode;
     // which nodes are read through memory at all by this rank's tiles, with persist_k tiles per workgroup (the others publish
     // nothing on this GPU; what other ranks read goes through the inboxes)
     magk::mark_external(ctx->halo_g.as<int32_t>(), ctx->tmeta.as<magk::TileMeta>(), ctx->t0, ctx->t1, ctx->B, ctx->persist_k,
                         ctx->maskP.as<uint8_t>(), eb_mode == 2, s);
     if (eb_mode) { // the nodes' blocks, once per solve (18 doubles per node of the padded order, value-major)
+        const int64_t npad = (int64_t)ctx->T * ctx->B;
         HIPCHK(ctx->kblocks.reserve(8 * (size_t)(3 * magk::persist_block_entries()) * (size_t)npad));
         P.kblocks = ctx->kblocks.as<double>();
         P.kb_stride = npad;
@@ -1521,14 +1556,8 @@ int cg_phase_persist(mag_ctx *ctx)
     HIPCHK(hipStreamSynchronize(s));
     const FusedState &st = ctx->h_fstate[2];
     bool failed = h_sync[9] != 0 || !st.done;
-    if (mg) { // all ranks must agree before anyone changes path: sum of the failure flags
-        double flag = failed ? 1.0 : 0.0;
-        std::string msg;
-        HIPCHK(hipMemcpyAsync(ctx->comm_pq.p, &flag, 8, hipMemcpyHostToDevice, s));
-        if (int rc = ctx->comm.allreduce_sum(ctx->comm_pq.as<double>(), 1, s, msg)) return fail(ctx, rc, "%s", msg.c_str());
-        HIPCHK(hipMemcpyAsync(&flag, ctx->comm_pq.p, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        failed = flag != 0.0;
+    if (mg) { // all ranks must agree before anyone changes path
+        if (int rc = any_rank(ctx, failed)) return rc;
         if (failed) { // the timeout word, for the next context
             if (ctx->inbox_ready)
                 HIPCHK(hipMemsetAsync(ctx->inbox_own, 0, 64, s));
@@ -1555,13 +1584,7 @@ int cg_phase_persist(mag_ctx *ctx)
         if (int rc = gather_solution(ctx)) return rc;
         HIPCHK(hipStreamSynchronize(s));
     }
-    ctx->stats.iterations = st.iterations;
-    ctx->stats.final_cost = st.final_cost;
-    ctx->stats.rhs_norm = std::sqrt(st.bb);
-    ctx->stats.converged = st.converged;
-    ctx->stats.breakdown = st.breakdown;
-    ctx->best_cost = st.best_cost;
-    ctx->best_iter = st.best_iter;
+    take_stats(ctx, st);
     return MAG_OK;
 }
 
@@ -1621,10 +1644,7 @@ int cg_phase_csr(mag_ctx *ctx)
                    ctx->state.as<CgState>(), s);
     HIPCHK(hipGetLastError());
     const int G = ctx->opt.check_every;
-    const long long max_blocks = (long long)(ctx->opt.max_iter / G) + 3;
-    bool done = false;
-    int slot = 0;
-    for (long long blk = 0; blk < max_blocks && !done; ++blk) {
+    auto block = [&]() -> int {
         for (int i = 0; i < G; ++i) {
             magk::CsrCgParams P = {};
             P.n = nf;
@@ -1648,32 +1668,58 @@ int cg_phase_csr(mag_ctx *ctx)
                                     ctx->state.as<CgState>(), s);
         }
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&ctx->h_state[slot], ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipEventRecord(ctx->evPoll[slot], s));
-        if (blk >= 1) {
-            HIPCHK(hipEventSynchronize(ctx->evPoll[slot ^ 1]));
-            done = ctx->h_state[slot ^ 1].done != 0;
-        }
-        slot ^= 1;
-    }
+        return MAG_OK;
+    };
+    if (int rc = run_blocks(ctx, ctx->state, ctx->h_state, block)) return rc;
     HIPCHK(hipMemcpyAsync(&ctx->h_state[2], ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
     // solver.rs:443-454: the solution goes back into the unknown slots in ascending DOF order
     magk::expand_free(x, ctx->fidx.as<int32_t>(), ctx->uknown.as<uint8_t>(), ctx->uin.as<double>(), 2 * ctx->N,
                       ctx->u.as<double>(), s);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
-    const CgState &st = ctx->h_state[2];
-    ctx->stats.iterations = st.iterations;
-    ctx->stats.final_cost = st.final_cost;
-    ctx->stats.rhs_norm = std::sqrt(st.bb);
-    ctx->stats.converged = st.converged;
-    ctx->stats.breakdown = st.breakdown;
-    ctx->best_cost = st.best_cost;
-    ctx->best_iter = st.best_iter;
+    take_stats(ctx, ctx->h_state[2]);
     return MAG_OK;
 }
 
-// fp32 leg of BASELINE config 5: same fused iteration, CG state and operator arithmetic in fp32 (cg.hip, k_cg_fused32)
+// ---- fp32 leg of BASELINE config 5: same fused iteration, CG state and operator arithmetic in fp32 (cg.hip, k_cg_fused32) ----
+magk::Fused32Params fused32_params(mag_ctx *ctx, int par, int grid)
+{
+    magk::Fused32Params P = {};
+    const int32_t stride = magk::kMaxGrid;
+    P.N = ctx->N;
+    P.T = ctx->T;
+    P.cap = ctx->cap;
+    P.par = par;
+    P.hist_len = ctx->opt.history_len;
+    P.xyP32 = ctx->xy32.as<float2>();
+    P.maskP = ctx->maskP.as<uint8_t>();
+    P.meta = ctx->tmeta.as<magk::TileMeta>();
+    P.ell16 = ctx->ell.as<uint32_t>();
+    P.halo_g = ctx->halo_g.as<int32_t>();
+    P.halo_xy32 = ctx->hxy32.as<float2>();
+    set_material(ctx, P);
+    P.in = (par ? ctx->rqp32b : ctx->rqp32a).as<magk::Rqp32>();
+    P.out = (par ? ctx->rqp32a : ctx->rqp32b).as<magk::Rqp32>();
+    P.x = ctx->x32.as<float2>();
+    if (ctx->dist) { // (one GPU: the range fields stay zero)
+        P.t0 = ctx->t0;
+        P.t1 = ctx->t1;
+        P.own0 = ctx->own0;
+        P.own1 = ctx->own1;
+        P.n_iface = ctx->n_iface;
+        P.iface = ctx->iface.as<int32_t>();
+        set_exchange(ctx, par, 4, P);
+    } else {
+        P.nPart = grid;
+        P.part_in = ctx->fpart.as<double>() + (size_t)par * 4 * stride;
+        P.part_out = ctx->fpart.as<double>() + (size_t)(par ^ 1) * 4 * stride;
+        P.part_stride = stride;
+    }
+    P.st = ctx->fstate.as<magk::FusedState>();
+    P.hist = ctx->hist.as<double>();
+    return P;
+}
+
 int cg_phase_fused32(mag_ctx *ctx)
 {
     using magk::FusedState;
@@ -1682,7 +1728,6 @@ int cg_phase_fused32(mag_ctx *ctx)
         return fail(ctx, MAG_ERR_BAD_ARGS, "precision fp32 needs the LDS-halo operator and tile_nodes 256|512");
     const int64_t N = ctx->N;
     const int32_t stride = magk::kMaxGrid;
-    const bool dist = ctx->dist;
     HIPCHK(ctx->xy32.reserve(8 * (size_t)N));
     HIPCHK(ctx->hxy32.reserve(8 * (size_t)std::max<int64_t>(ctx->halo_total, 1)));
     HIPCHK(ctx->rqp32a.reserve(sizeof(magk::Rqp32) * (size_t)N));
@@ -1693,120 +1738,38 @@ int cg_phase_fused32(mag_ctx *ctx)
     magk::coords32(ctx->xyP.as<double>(), ctx->halo_g.as<int32_t>(), ctx->tile_hoff.as<int32_t>(), N, ctx->B, ctx->T,
                    ctx->xy32.as<float>(), ctx->hxy32.as<float>(), s);
     const int grid = magk::fused32_grid(ctx->B, ctx->cap, ctx->t1 - ctx->t0);
-    if (dist) {
-        // the streaming protocol of cg_phase_fused, in fp32: the exchange buffer stays in doubles ([4 x g_all dot
-        // partials | q of the interface nodes]), one in-place all-reduce per iteration
+    if (ctx->dist) {
+        // the streaming protocol of cg_phase_fused, in fp32: the exchange buffer stays in doubles, one in-place all-reduce
+        // per iteration
         ctx->pre = false;
-        const int R = ctx->comm.nranks;
-        int32_t most = 1;
-        for (int r = 0; r < R; ++r)
-            most = std::max(most, (int32_t)(((int64_t)ctx->T * (r + 1)) / R - ((int64_t)ctx->T * r) / R));
-        ctx->g_all = magk::fused32_grid(ctx->B, ctx->cap, most);
-        ctx->cwords = 4 * (size_t)ctx->g_all + 2 * (size_t)ctx->n_iface;
-        HIPCHK(ctx->comm_f.reserve(8 * 2 * ctx->cwords + 64));
-        HIPCHK(ctx->own_qslot.reserve(4 * (size_t)N));
-        HIPCHK(ctx->halo_qslot.reserve(4 * (size_t)std::max<int64_t>(ctx->halo_total, 1)));
-        magk::comm_slots(ctx->iface.as<int32_t>(), ctx->n_iface, ctx->own0, ctx->own1, ctx->halo_g.as<int32_t>(),
-                         ctx->halo_total, N, ctx->own_qslot.as<int32_t>(), ctx->halo_qslot.as<int32_t>(), s);
-        double *c0 = ctx->comm_f.as<double>();
-        HIPCHK(hipMemsetAsync(c0, 0, 8 * 2 * ctx->cwords, s));
-        magk::fused32_init(ctx->bP.as<double2>(), ctx->rqp32a.as<magk::Rqp32>(), ctx->rqp32b.as<magk::Rqp32>(),
-                           ctx->x32.as<float2>(), N, ctx->B, ctx->T, ctx->t0, ctx->t1, c0, ctx->g_all, grid, s);
-        std::string msg;
-        if (int rc = ctx->comm.allreduce_sum(c0, (int64_t)ctx->cwords, s, msg)) return fail(ctx, rc, "%s", msg.c_str());
-        magk::fused_setup(c0, ctx->g_all, ctx->g_all, ctx->opt.stop_mode, ctx->opt.tol, (long long)ctx->opt.max_iter,
-                          ctx->fstate.as<FusedState>(), s);
-        if (ctx->si) // tags of this solve's exchanges: sequence number << 24 + the launch counter (k_stream_exchange)
-            HIPCHK(hipMemcpyAsync((char *)ctx->fstate.p + offsetof(FusedState, exchange_tag_base), &ctx->si_tag_base, 4,
-                                  hipMemcpyHostToDevice, s));
-    } else {
-        HIPCHK(hipMemsetAsync(ctx->fpart.p, 0, 8 * 2 * 4 * (size_t)stride, s));
-        magk::fused32_init(ctx->bP.as<double2>(), ctx->rqp32a.as<magk::Rqp32>(), ctx->rqp32b.as<magk::Rqp32>(),
-                           ctx->x32.as<float2>(), N, ctx->B, ctx->T, 0, ctx->T, ctx->fpart.as<double>(), stride, grid, s);
-        magk::fused_setup(ctx->fpart.as<double>(), grid, stride, ctx->opt.stop_mode, ctx->opt.tol,
-                          (long long)ctx->opt.max_iter, ctx->fstate.as<FusedState>(), s);
+        if (int rc = reserve_exchange(ctx, magk::fused32_grid(ctx->B, ctx->cap, most_rank_tiles(ctx->T, ctx->comm.nranks)), 4))
+            return rc;
     }
+    // (one GPU: ctx->t0 = 0, ctx->t1 = T)
+    if (int rc = setup_exchange(ctx, grid, 4, [&](double *part, int32_t stride) {
+            magk::fused32_init(ctx->bP.as<double2>(), ctx->rqp32a.as<magk::Rqp32>(), ctx->rqp32b.as<magk::Rqp32>(),
+                               ctx->x32.as<float2>(), N, ctx->B, ctx->T, ctx->t0, ctx->t1, part, stride, grid, s);
+        }))
+        return rc;
     HIPCHK(hipGetLastError());
     const int G = ctx->opt.check_every;
-    const long long max_blocks = (long long)(ctx->opt.max_iter / G) + 3;
-    bool done = false;
-    int slot = 0;
-    for (long long blk = 0; blk < max_blocks && !done; ++blk) {
+    auto block = [&]() -> int {
         for (int i = 0; i < G; ++i) {
-            magk::Fused32Params P = {};
-            const int par = i & 1;
-            P.N = N;
-            P.T = ctx->T;
-            P.cap = ctx->cap;
-            P.par = par;
-            P.hist_len = ctx->opt.history_len;
-            P.xyP32 = ctx->xy32.as<float2>();
-            P.maskP = ctx->maskP.as<uint8_t>();
-            P.meta = ctx->tmeta.as<magk::TileMeta>();
-            P.ell16 = ctx->ell.as<uint32_t>();
-            P.halo_g = ctx->halo_g.as<int32_t>();
-            P.halo_xy32 = ctx->hxy32.as<float2>();
-            P.c0 = (float)(ctx->youngs * ctx->thick / (2.0 * (1.0 - ctx->nu * ctx->nu)));
-            P.nu = (float)ctx->nu;
-            P.h = (float)((1.0 - ctx->nu) / 2.0);
-            P.in = (par ? ctx->rqp32b : ctx->rqp32a).as<magk::Rqp32>();
-            P.out = (par ? ctx->rqp32a : ctx->rqp32b).as<magk::Rqp32>();
-            P.x = ctx->x32.as<float2>();
-            if (dist) {
-                double *cin = ctx->comm_f.as<double>() + (size_t)par * ctx->cwords;
-                double *cout = ctx->comm_f.as<double>() + (size_t)(par ^ 1) * ctx->cwords;
-                P.t0 = ctx->t0;
-                P.t1 = ctx->t1;
-                P.own0 = ctx->own0;
-                P.own1 = ctx->own1;
-                P.n_iface = ctx->n_iface;
-                P.iface = ctx->iface.as<int32_t>();
-                P.own_qslot = ctx->own_qslot.as<int32_t>();
-                P.halo_qslot = ctx->halo_qslot.as<int32_t>();
-                P.part_in = cin;
-                P.part_stride_in = ctx->g_all;
-                P.nPart = ctx->g_all;
-                P.part_out = cout;
-                P.part_stride = ctx->g_all;
-                P.comm_in_q = (const double2 *)(cin + 4 * (size_t)ctx->g_all);
-                P.comm_out_q = (double2 *)(cout + 4 * (size_t)ctx->g_all);
-            } else {
-                P.nPart = grid;
-                P.part_in = ctx->fpart.as<double>() + (size_t)par * 4 * stride;
-                P.part_out = ctx->fpart.as<double>() + (size_t)(par ^ 1) * 4 * stride;
-                P.part_stride = stride;
-            }
-            P.st = ctx->fstate.as<FusedState>();
-            P.hist = ctx->hist.as<double>();
+            const magk::Fused32Params P = fused32_params(ctx, i & 1, grid);
             magk::fused32_launch(P, ctx->B, grid, s);
-            if (dist) {
-                std::string msg;
-                if (int rc = ctx->comm.allreduce_sum(P.part_out, (int64_t)ctx->cwords, s, msg))
-                    return fail(ctx, rc, "%s", msg.c_str());
-            }
+            if (ctx->dist)
+                if (int rc = allreduce(ctx, P.part_out, (int64_t)ctx->cwords)) return rc;
         }
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&ctx->h_fstate[slot], ctx->fstate.p, sizeof(FusedState), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipEventRecord(ctx->evPoll[slot], s));
-        if (blk >= 1) {
-            HIPCHK(hipEventSynchronize(ctx->evPoll[slot ^ 1]));
-            done = ctx->h_fstate[slot ^ 1].done != 0;
-        }
-        slot ^= 1;
-    }
+        return MAG_OK;
+    };
+    if (int rc = run_blocks(ctx, ctx->fstate, ctx->h_fstate, block)) return rc;
     magk::x32_to_f64(ctx->x32.as<float2>(), N, ctx->x.as<double2>(), s);
-    if (dist)
+    if (ctx->dist)
         if (int rc = gather_solution(ctx)) return rc;
     HIPCHK(hipMemcpyAsync(&ctx->h_fstate[2], ctx->fstate.p, sizeof(FusedState), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    const FusedState &st = ctx->h_fstate[2];
-    ctx->stats.iterations = st.iterations;
-    ctx->stats.final_cost = st.final_cost;
-    ctx->stats.rhs_norm = std::sqrt(st.bb);
-    ctx->stats.converged = st.converged;
-    ctx->stats.breakdown = st.breakdown;
-    ctx->best_cost = st.best_cost;
-    ctx->best_iter = st.best_iter;
+    take_stats(ctx, ctx->h_fstate[2]);
     return MAG_OK;
 }
 
@@ -1837,6 +1800,23 @@ double ev_ms(hipEvent_t a, hipEvent_t b)
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, a, b) != hipSuccess) return 0.0;
     return (double)ms;
+}
+
+// ms per call of launch(): 3 warm-up calls, then reps calls between events 8 and 9
+template <class Launch>
+int time_launches(mag_ctx *ctx, int32_t reps, Launch launch, double *ms_out)
+{
+    hipStream_t s = ctx->stream;
+    for (int i = 0; i < 3; ++i)
+        if (int rc = launch()) return rc;
+    HIPCHK(hipEventRecord(ctx->ev[8], s));
+    for (int i = 0; i < reps; ++i)
+        if (int rc = launch()) return rc;
+    HIPCHK(hipEventRecord(ctx->ev[9], s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    *ms_out = ev_ms(ctx->ev[8], ctx->ev[9]) / reps;
+    return MAG_OK;
 }
 
 } // namespace
@@ -2336,14 +2316,7 @@ int mag_time_operator(mag_ctx *ctx, int32_t reps, double *ms_per_launch)
         P.own_qslot = P.halo_qslot = nullptr; // single-GPU kernel: the figure is the operator's, not the exchange's
         P.comm_in_q = nullptr;
         P.comm_out_q = nullptr;
-        for (int i = 0; i < 3; ++i) magk::fused_launch(P, ctx->B, ctx->fgrid, s);
-        HIPCHK(hipEventRecord(ctx->ev[8], s));
-        for (int i = 0; i < reps; ++i) magk::fused_launch(P, ctx->B, ctx->fgrid, s);
-        HIPCHK(hipEventRecord(ctx->ev[9], s));
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s));
-        *ms_per_launch = ev_ms(ctx->ev[8], ctx->ev[9]) / reps;
-        return MAG_OK;
+        return time_launches(ctx, reps, [&] { magk::fused_launch(P, ctx->B, ctx->fgrid, s); return 0; }, ms_per_launch);
     }
     // The CG buffers are free after a run: time the CG-mode operator kernel exactly as the solve launches it,
     // on a scratch state that never reports convergence.
@@ -2355,14 +2328,7 @@ int mag_time_operator(mag_ctx *ctx, int32_t reps, double *ms_per_launch)
     magk::UpdParams U;
     iteration_params(ctx, 0, P, U);
     P.hist_len = 0;
-    for (int i = 0; i < 3; ++i) magk::op_launch(P, ctx->B, true, s);
-    HIPCHK(hipEventRecord(ctx->ev[8], s));
-    for (int i = 0; i < reps; ++i) magk::op_launch(P, ctx->B, true, s);
-    HIPCHK(hipEventRecord(ctx->ev[9], s));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
-    *ms_per_launch = ev_ms(ctx->ev[8], ctx->ev[9]) / reps;
-    return MAG_OK;
+    return time_launches(ctx, reps, [&] { magk::op_launch(P, ctx->B, true, s); return 0; }, ms_per_launch);
 }
 
 int mag_time_spmv(mag_ctx *ctx, int32_t reps, double *ms_per_launch)
@@ -2370,18 +2336,10 @@ int mag_time_spmv(mag_ctx *ctx, int32_t reps, double *ms_per_launch)
     if (int rc = enter(ctx)) return rc;
     if (reps < 1 || !ms_per_launch) return fail(ctx, MAG_ERR_BAD_ARGS, "reps < 1 or null output");
     if (int rc = prepare_timing(ctx)) return rc;
-    hipStream_t s = ctx->stream;
     // y = M K M v, nothing fused: the SpMV proper (tmpP holds a leftover vector of the run, q is free), on the tile
     // range this rank owns -- the whole mesh on one GPU, this GPU's share with several ranks
-    for (int i = 0; i < 3; ++i)
-        if (int rc = apply_plain(ctx, ctx->tmpP.as<double>(), ctx->q.as<double>(), 1, true)) return rc;
-    HIPCHK(hipEventRecord(ctx->ev[8], s));
-    for (int i = 0; i < reps; ++i)
-        if (int rc = apply_plain(ctx, ctx->tmpP.as<double>(), ctx->q.as<double>(), 1, true)) return rc;
-    HIPCHK(hipEventRecord(ctx->ev[9], s));
-    HIPCHK(hipStreamSynchronize(s));
-    *ms_per_launch = ev_ms(ctx->ev[8], ctx->ev[9]) / reps;
-    return MAG_OK;
+    return time_launches(
+        ctx, reps, [&] { return apply_plain(ctx, ctx->tmpP.as<double>(), ctx->q.as<double>(), 1, true); }, ms_per_launch);
 }
 
 int mag_comm_get_unique_id(void *id_out) { return magc::get_unique_id(id_out); }
