@@ -55,6 +55,31 @@ struct DevBuf {
     T *as() const { return (T *)p; }
 };
 
+// Run-time knobs (environment, read at every call: tests switch them between calls in one process).  None is needed in
+// production; each one either is set by a test or forces a path the library can take on its own.
+//   MAG_TUNE_FORCE_DIST=1                one rank runs the distributed protocol (tests/dist_worker.py: rccl1 rehearsal)
+//   MAG_TUNE_SHARD_ORDER=0               several ranks build the whole mesh's tables (replicated ordering phase; tests)
+//   MAG_TUNE_PERSIST_K=k                 at least k tiles per on-chip workgroup: ranks sharing one GPU co-resident (tests)
+//   MAG_TUNE_PERSIST_MIN_K=k             small meshes / 256-node tiles reach the on-chip kernel (tests)
+//   MAG_TUNE_PERSIST_SPIN=n              the on-chip kernel's spin budget (0 forces its fall-back; tests)
+//   MAG_TUNE_PERSIST_TRIANGLES=1         the triangle walk where the mesh qualifies for edge blocks (tests)
+//   MAG_TUNE_PERSIST_MG_BLOCKS=0         several ranks: the triangle walk instead of edge blocks (tests)
+//   MAG_TUNE_PERSIST_MG_OVERFLOW=0       several ranks: the triangle walk instead of overflow records (tests)
+//   MAG_TUNE_PERSIST_NO_OVERFLOW=1       a row of more than six blocks sends the mesh to the triangle walk (tests)
+//   MAG_TUNE_PERSIST_FORCE_OVERFLOW=1    a structured mesh through the overflow instantiation (tests)
+//   MAG_TUNE_PERSIST_STAMPS=<file>       stamped build only: the on-chip kernel's phase times (scripts/persist_phases.py)
+//   MAG_TUNE_STREAM_SPIN=n               k_stream_exchange's spin budget (0 forces the all-reduce fall-back; tests)
+//   MAG_TUNE_STREAM_INBOX=0              the all-reduce although inboxes are open: the only way past them on multi-GPU hardware
+//   MAG_TUNE_ASSEMBLY=tiles|ctile        numeric assembly: k_assemble_tiles / k_assemble_fan where it fits (tests)
+//   MAG_TUNE_PATTERN_SORT=1              the sort-based CSR pattern, the fall-back for rows of valence >= 16 (tests)
+//   MAG_TUNE_GRID, MAG_TUNE_DMA          streaming kernels: grid cap, LDS-DMA staging off (cg.hip; tests)
+//   MAG_LIB_PATH                         Python binding: load another build of this library (magnetite_amd/_lib.py)
+int env_int(const char *name, int dflt)
+{
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
 int ceil_log2(int64_t n)
 {
     int b = 0;
@@ -94,8 +119,6 @@ struct mag_ctx {
     bool asm_ctile = false; // K is assembled from the CG tiles (k_assemble_fan), ell_asm holds its corner words
     // tile-local numbering for the LDS-halo operator
     bool use_lds = false;
-    int tune_wt = 1;       // two-launch variant: write-through (sc1) stores of p, q, x, r
-    int tune_wt_fused = 1; // fused variant (LDS-DMA kernel stores linear 1-KiB pieces; the AoS kernel ignores it)
     int32_t cap = 0, max_halo = 0;
     int64_t halo_total = 0;
     DevBuf hcnt, hoffn, hk0, hk1, halo_g, halo_xy, tile_hcnt, tile_hoff;
@@ -374,16 +397,13 @@ int ensure_order(mag_ctx *ctx)
     // triangles per node it needs are counted in caller numbering (inc_off is free until the scan below) and carried into
     // the new numbering by apply_order: k_incidence_keys then counts nothing.
     bool counted = false;
-    {
-        const char *vs = getenv("MAG_TUNE_VALENCE_SORT");
-        if ((B == 256 || B == 512) && !(vs && atoi(vs) == 0)) {
-            HIPCHK(hipMemsetAsync(ctx->inc_off.p, 0, 4 * ((size_t)N + 1), s));
-            magk::count_degree(ctx->conn.as<int32_t>(), E, N, ctx->inc_off.as<int32_t>(), s);
-            magk::tile_valence_partition(ctx->sV1.as<uint32_t>(), ctx->inc_off.as<int32_t>(), N, B, T, ctx->perm.as<uint32_t>(), s);
-            counted = true;
-        } else {
-            HIPCHK(hipMemcpyAsync(ctx->perm.p, ctx->sV1.p, 4 * (size_t)N, hipMemcpyDeviceToDevice, s));
-        }
+    if (B == 256 || B == 512) {
+        HIPCHK(hipMemsetAsync(ctx->inc_off.p, 0, 4 * ((size_t)N + 1), s));
+        magk::count_degree(ctx->conn.as<int32_t>(), E, N, ctx->inc_off.as<int32_t>(), s);
+        magk::tile_valence_partition(ctx->sV1.as<uint32_t>(), ctx->inc_off.as<int32_t>(), N, B, T, ctx->perm.as<uint32_t>(), s);
+        counted = true;
+    } else {
+        HIPCHK(hipMemcpyAsync(ctx->perm.p, ctx->sV1.p, 4 * (size_t)N, hipMemcpyDeviceToDevice, s));
     }
     HIPCHK(hipMemsetAsync(errflag, 0, 8, s)); // {error flag, prescribed-displacement count}
     magk::apply_order(ctx->perm.as<uint32_t>(), ctx->xy.as<double>(), ctx->uknown.as<uint8_t>(), N,
@@ -402,9 +422,8 @@ int ensure_order(mag_ctx *ctx)
     // rows a rank keeps: the tables below are built for the tiles this rank needs only (symbolic.hip, need_tiles).  Any other
     // entry point -- and MAG_TUNE_SHARD_ORDER=0 -- builds them for the whole mesh, as every rank did until round 4.
     const bool csr_rows = ctx->opt.assemble_csr != 0 || ctx->opt.cg_operator == MAG_OP_CSR;
-    const char *so = getenv("MAG_TUNE_SHARD_ORDER");
-    const bool sh = R > 1 && ctx->order_allow_shard && csr_rows && !ctx->want_full_csr && !(so && atoi(so) == 0) &&
-                    getenv("MAG_TUNE_FORCE_DIST") == nullptr;
+    const bool sh = R > 1 && ctx->order_allow_shard && csr_rows && !ctx->want_full_csr &&
+                    env_int("MAG_TUNE_SHARD_ORDER", 1) != 0 && getenv("MAG_TUNE_FORCE_DIST") == nullptr;
     ctx->order_sharded = sh;
     if (!counted) HIPCHK(hipMemsetAsync(ctx->deg.p, 0, 4 * ((size_t)N + 1), s));
     if (sh) {
@@ -578,8 +597,8 @@ int ensure_order(mag_ctx *ctx)
         // accumulators per row node + 20 B per staged node) fits a CU's LDS
         const bool csr_wanted = ctx->opt.assemble_csr != 0 || ctx->opt.cg_operator == MAG_OP_CSR;
         const char *how_asm = getenv("MAG_TUNE_ASSEMBLY");
-        ctx->asm_ctile = csr_wanted && !(how_asm && strcmp(how_asm, "ctile") != 0) && !getenv("MAG_TUNE_KE_BUFFER") &&
-                         (B == 256 || B == 512) && ctx->cap <= 4096 && magk::assemble_ctiles_lds(B, ctx->cap) <= 64 * 1024;
+        ctx->asm_ctile = csr_wanted && !(how_asm && strcmp(how_asm, "ctile") != 0) && (B == 256 || B == 512) &&
+                         ctx->cap <= 4096 && magk::assemble_ctiles_lds(B, ctx->cap) <= 64 * 1024;
         if (ctx->asm_ctile) HIPCHK(ctx->ell_asm.reserve(4 * (size_t)(h_total > 0 ? h_total : 1)));
         if (ctx->asm_ctile) HIPCHK(ctx->ell_pos.reserve(2 * (size_t)(h_total > 0 ? h_total : 1)));
         magk::fill_ell16(ctx->inc_off.as<int32_t>(), ctx->inc.as<uint32_t>(), ctx->conn.as<int32_t>(),
@@ -627,25 +646,22 @@ int ensure_order(mag_ctx *ctx)
         int dev = 0, cus = 0;
         (void)hipGetDevice(&dev);
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        const int pthreads = magk::persist_threads();
-        const int kmax = magk::persist_tiles_per_wg(B, pthreads);
+        const int kmax = magk::persist_tiles_per_wg(B);
         const int32_t tiles_max = most_rank_tiles(T, R);
         int k = cus > 0 ? (tiles_max + cus - 1) / cus : 0;
         // a mesh of at most kmax tiles on one GPU (up to 2048 nodes: the size of the reference's own examples) goes to ONE
         // workgroup: every tile is a sibling of every other, nothing is exchanged through memory (persist_single_workgroup)
-        const char *sw = getenv("MAG_TUNE_PERSIST_SINGLE_WG");
-        if (!mg && tiles_max <= kmax && !(sw && atoi(sw) == 0)) k = std::max(k, (int)tiles_max);
+        if (!mg && tiles_max <= kmax) k = std::max(k, (int)tiles_max);
         // rehearsals: several ranks share ONE GPU and must all be co-resident -- fewer, fuller workgroups per rank
-        if (const char *e = getenv("MAG_TUNE_PERSIST_K")) k = std::max(k, atoi(e));
+        k = std::max(k, env_int("MAG_TUNE_PERSIST_K", 0));
         // Measured against the streaming kernel on the same 512-node tiles the on-chip kernel wins from one tile per
         // workgroup up (6.2 vs 7.9 us per iteration at 115 tiles, 12.6 vs 20.3 at 982); with 256-node tiles it does not
         // (and eight of them rarely fit the LDS), so those only run it when a test asks (MAG_TUNE_PERSIST_MIN_K=1).
-        int kmin = B == 512 ? 1 : 9;
-        if (const char *e = getenv("MAG_TUNE_PERSIST_MIN_K")) kmin = atoi(e);
+        const int kmin = env_int("MAG_TUNE_PERSIST_MIN_K", B == 512 ? 1 : 9);
         ctx->persist_maxh = ((max_halo + 3) / 4) * 4;
         if (kmax > 0 && k >= 1 && k >= kmin && k <= kmax && (tiles_max + k - 1) / k <= 256 && // the gather holds 256
-            (int64_t)k * max_halo <= 2 * pthreads && // a workgroup's halo entries are dealt out two per thread
-            magk::persist_lds_bytes(B, ctx->cap, ctx->persist_maxh, pthreads, 0, 0, mg) + 256 <= 160 * 1024 && // + the static 256 bytes
+            (int64_t)k * max_halo <= 2 * 512 && // a workgroup's halo entries are dealt out two per thread (of 512)
+            magk::persist_lds_bytes(B, ctx->cap, ctx->persist_maxh, 0, 0, mg) + 256 <= 160 * 1024 && // + the static 256 bytes
             (!mg || ctx->n_iface < (1 << 24))) { // (interface slots are kept in 24 bits on the chip)
             ctx->persist = true;
             ctx->persist_k = k;
@@ -683,10 +699,8 @@ int csr_symbolic(mag_ctx *ctx)
     HIPCHK(ctx->bptr.reserve(4 * ((size_t)N + 1)));
     // Default: the pattern straight from the incidence lists (k_pattern_rows: no pair list, no 9E-key sort -- 0.15 ms
     // instead of 0.9 ms at 1M triangles).  The sort-based pattern below serves rows too long for its register array
-    // (valence >= 16) and the A/B assembly modes that walk the sorted pair list.
-    const char *how = getenv("MAG_TUNE_ASSEMBLY");
-    const bool want_pairs = getenv("MAG_TUNE_KE_BUFFER") || (how && !strcmp(how, "rows")) || getenv("MAG_TUNE_PATTERN_SORT");
-    if (!want_pairs) {
+    // (valence >= 16); MAG_TUNE_PATTERN_SORT=1 takes it for every mesh.
+    if (!getenv("MAG_TUNE_PATTERN_SORT")) {
         int32_t *ovf = (int32_t *)(ctx->small.as<double>() + 4 * 256 + 4) + 2;
         const uint8_t *local = shard ? ctx->local_node.as<uint8_t>() : nullptr;
         HIPCHK(hipMemsetAsync(ovf, 0, 4, s));
@@ -774,23 +788,12 @@ int element_phase(mag_ctx *ctx)
     return MAG_OK;
 }
 
-// numeric assembly, atomic-free, K_e evaluated on the fly (no 288-byte-per-element buffer).  Default: per element tile
-// with LDS staging (k_assemble_tiles).  MAG_TUNE_ASSEMBLY=rows: one thread per block straight from global memory
-// (round 1's kernel); MAG_TUNE_KE_BUFFER=1: the two-step form (K_e for every element, then a gather over the sorted
-// pairs).  All three are bit-identical.
+// numeric assembly, atomic-free, K_e evaluated on the fly (no 288-byte-per-element buffer): from the CG tiles
+// (k_assemble_fan) where their image fits, otherwise per element tile with LDS staging (k_assemble_tiles).  Bit-identical.
 int gather_phase(mag_ctx *ctx)
 {
     const char *how = getenv("MAG_TUNE_ASSEMBLY");
-    if (getenv("MAG_TUNE_KE_BUFFER")) {
-        if (int rc = element_phase(ctx)) return rc;
-        magk::assemble_gather(ctx->pk1.as<uint64_t>(), ctx->pv1.as<uint32_t>(), ctx->seg_start.as<int32_t>(), ctx->nb,
-                              ctx->bptr.as<int32_t>(), ctx->ke.as<double>(), ctx->kval.as<double>(), ctx->stream);
-    } else if (how && !strcmp(how, "rows")) {
-        magk::assemble_rows(ctx->brow.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->bptr.as<int32_t>(), ctx->nb,
-                            ctx->inc_off.as<int32_t>(), ctx->inc.as<uint32_t>(), ctx->iperm.as<int32_t>(),
-                            ctx->conn.as<int32_t>(), ctx->xy.as<double>(), ctx->nu, ctx->youngs, ctx->thick,
-                            ctx->kval.as<double>(), ctx->stream);
-    } else if (ctx->asm_ctile && ctx->use_lds && !(how && !strcmp(how, "tiles")) &&
+    if (ctx->asm_ctile && ctx->use_lds && !(how && !strcmp(how, "tiles")) &&
                magk::assemble_ctiles(ctx->bcol.as<int32_t>(), ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(),
                                      ctx->xyP.as<double>(), ctx->halo_xy.as<double>(),
                                      ctx->tile_hoff.as<int32_t>(), ctx->tile_deg.as<int32_t>(), ctx->tile_off.as<int64_t>(),
@@ -856,7 +859,7 @@ magk::OpParams op_params(mag_ctx *ctx)
     } else {
         P.ell = ctx->ell.as<int2>();
     }
-    P.wt = ctx->tune_wt;
+    P.wt = 1; // write-through (sc1) stores of p, q, x, r
     set_material(ctx, P);
     return P;
 }
@@ -927,7 +930,7 @@ void iteration_params(mag_ctx *ctx, int parity, magk::OpParams &P, magk::UpdPara
     U.partPQ = ctx->dist ? ctx->comm_pq.as<double>() : ctx->partPQ.as<double>();
     U.partRR = ctx->partRR.as<double>();
     U.st = ctx->state.as<CgState>();
-    U.wt = ctx->tune_wt;
+    U.wt = 1; // write-through stores
 }
 
 // one block of G CG iterations on the stream (parity 0 first: p_prev = p1, p_new = p0)
@@ -1190,7 +1193,7 @@ magk::FusedParams fused_params(mag_ctx *ctx, int par)
     P.own1 = ctx->own1;
     P.n_iface = ctx->n_iface;
     P.cap = ctx->cap;
-    P.wt = ctx->tune_wt_fused;
+    P.wt = 1; // write-through stores (the LDS-DMA kernel stores linear 1-KiB pieces; the AoS kernel ignores it)
     P.par = par;
     P.hist_len = ctx->opt.history_len;
     P.xyP = ctx->xyP.as<double2>();
@@ -1299,14 +1302,13 @@ int cg_phase_fused(mag_ctx *ctx)
         // mesh does not fit the chips, or the on-chip kernel is not wanted): k_stream_exchange instead of one RCCL
         // all-reduce per iteration.  Same decision on every rank: it depends on replicated quantities only.
         const int R = ctx->comm.nranks;
-        const char *e = getenv("MAG_TUNE_STREAM_INBOX");
-        ctx->si = R > 1 && R <= 8 && ctx->inbox_ready && !ctx->si_failed && !ctx->pre && (!e || atoi(e) != 0) &&
+        ctx->si = R > 1 && R <= 8 && ctx->inbox_ready && !ctx->si_failed && !ctx->pre &&
+                  env_int("MAG_TUNE_STREAM_INBOX", 1) != 0 &&
                   ctx->inbox_bytes >= 64 + 128 * (size_t)R + 64 * (size_t)ctx->n_iface &&
                   ctx->opt.max_iter < (int64_t(1) << 24) - 4;
         if (ctx->si) {
             ctx->si_tag_base = next_solve_seq(ctx) << 24;
-            ctx->si_spin = 1u << 20;
-            if (const char *sp = getenv("MAG_TUNE_STREAM_SPIN")) ctx->si_spin = (uint32_t)atoi(sp); // tests: force the fallback
+            ctx->si_spin = (uint32_t)env_int("MAG_TUNE_STREAM_SPIN", 1 << 20); // tests: 0 forces the fallback
             // nothing of an earlier use of the inbox may look current: cleared before the all-reduce below lines the ranks up
             HIPCHK(hipMemsetAsync(ctx->inbox_own, 0, 64 + 128 * (size_t)R + 64 * (size_t)ctx->n_iface, s));
         }
@@ -1362,8 +1364,7 @@ int choose_edge_blocks(mag_ctx *ctx, bool mg, magk::PersistParams &P, int &mode)
 {
     hipStream_t s = ctx->stream;
     mode = 0;
-    const char *mgb = getenv("MAG_TUNE_PERSIST_MG_BLOCKS");
-    if ((mg && mgb && atoi(mgb) == 0) || getenv("MAG_TUNE_PERSIST_TRIANGLES")) return MAG_OK;
+    if ((mg && env_int("MAG_TUNE_PERSIST_MG_BLOCKS", 1) == 0) || getenv("MAG_TUNE_PERSIST_TRIANGLES")) return MAG_OK;
     int32_t fan_flags = 3;
     if (ctx->order_sharded) { // (this rank's ring words cover its own tiles only: the ordering phase has OR-ed the flags over the ranks)
         fan_flags = ctx->fan_flags_global;
@@ -1372,10 +1373,9 @@ int choose_edge_blocks(mag_ctx *ctx, bool mg, magk::PersistParams &P, int &mode)
         HIPCHK(hipStreamSynchronize(s));
     }
     if (fan_flags == 0) mode = 1;
-    const char *no_ovf = getenv("MAG_TUNE_PERSIST_NO_OVERFLOW");
-    const char *mgo = getenv("MAG_TUNE_PERSIST_MG_OVERFLOW"); // =0: several ranks keep the triangle walk on such meshes
-    if (!((fan_flags == 1 && !(no_ovf && atoi(no_ovf))) || (fan_flags == 0 && getenv("MAG_TUNE_PERSIST_FORCE_OVERFLOW"))) ||
-        (mg && mgo && atoi(mgo) == 0))
+    if (!((fan_flags == 1 && env_int("MAG_TUNE_PERSIST_NO_OVERFLOW", 0) == 0) ||
+          (fan_flags == 0 && getenv("MAG_TUNE_PERSIST_FORCE_OVERFLOW"))) ||
+        (mg && env_int("MAG_TUNE_PERSIST_MG_OVERFLOW", 1) == 0)) // =0: several ranks keep the triangle walk on such meshes
         return MAG_OK;
     // per-node overflow counts -> scan -> the limits the LDS must meet
     const int nb = magk::persist_block_entries();
@@ -1401,7 +1401,7 @@ int choose_edge_blocks(mag_ctx *ctx, bool mg, magk::PersistParams &P, int &mode)
     const int32_t pool = ((lim[0] + 1 + 7) / 8) * 8; // + record 0, the zero block
     // 12 bits of pool position and 4 bits of count per node slot; the kernel's static LDS on top of the dynamic
     bool walk = !(lim[0] + 1 <= 4095 && lim[1] <= 15 &&
-                  magk::persist_lds_bytes(ctx->B, ctx->cap, ctx->persist_maxh, magk::persist_threads(), 2, pool, mg) + 256 <=
+                  magk::persist_lds_bytes(ctx->B, ctx->cap, ctx->persist_maxh, 2, pool, mg) + 256 <=
                       160 * 1024);
     // one instantiation for all ranks: a rank whose pool does not fit sends everybody to the walk
     if (ctx->order_sharded)
@@ -1465,8 +1465,7 @@ int cg_phase_persist(mag_ctx *ctx)
         int cus = 0;
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
         const int32_t grid_max = (most_rank_tiles(ctx->T, R) + ctx->persist_k - 1) / ctx->persist_k;
-        const char *cw = getenv("MAG_TUNE_COMM_WG");
-        P.comm_wg = (ctx->inbox_ready && grid_max + 1 <= cus && (!cw || atoi(cw) != 0)) ? 1 : 0;
+        P.comm_wg = (ctx->inbox_ready && grid_max + 1 <= cus) ? 1 : 0;
     }
     P.N = ctx->N;
     P.T = ctx->T;
@@ -1475,9 +1474,9 @@ int cg_phase_persist(mag_ctx *ctx)
     P.maxh = ctx->persist_maxh;
     P.hist_len = ctx->opt.history_len;
     P.stop_mode = ctx->opt.stop_mode;
-    // ~0.3 s of polling (each poll is a memory round trip) before a workgroup concludes that the grid is not resident
-    P.spin_limit = 1u << 19;
-    if (const char *e = getenv("MAG_TUNE_PERSIST_SPIN")) P.spin_limit = (uint32_t)atoi(e); // tests: force the fallback
+    // ~0.3 s of polling (each poll is a memory round trip) before a workgroup concludes that the grid is not resident;
+    // several ranks start apart: a longer budget
+    P.spin_limit = (uint32_t)env_int("MAG_TUNE_PERSIST_SPIN", mg ? 1 << 21 : 1 << 19);
     P.max_iter = (long long)ctx->opt.max_iter;
     P.tol = ctx->opt.tol;
     set_material(ctx, P);
@@ -1496,7 +1495,6 @@ int cg_phase_persist(mag_ctx *ctx)
     P.hist = ctx->hist.as<double>();
     if (mg) {
         // every rank's kernel must be running before anybody's spin budget runs out: line the streams up first
-        if (!getenv("MAG_TUNE_PERSIST_SPIN")) P.spin_limit = 1u << 21; // ranks start apart: a longer budget
         // Nothing of an earlier use may look current: a window handed over from another context, or slots of the solve
         // 255 sequence numbers ago, could carry this solve's tags.  Every rank clears the extent of ITS inbox this solve
         // will use (rank 0 the shared host window) before the line-up all-reduce: nobody stores into an inbox before
@@ -1531,7 +1529,7 @@ int cg_phase_persist(mag_ctx *ctx)
         P.kb_stride = npad;
         magk::edge_blocks_build(P, ctx->B, ctx->kblocks.as<double>(), eb_mode, s);
     }
-    magk::persist_launch(P, ctx->B, grid + P.comm_wg, magk::persist_threads(), eb_mode, s);
+    magk::persist_launch(P, ctx->B, grid + P.comm_wg, eb_mode, s);
     if (stamps) {
         // (several ranks: one file per rank, "<name>.<rank>"; with an exchange workgroup its row follows the compute workgroups')
         const int rows = grid + P.comm_wg;
@@ -1867,7 +1865,6 @@ mag_ctx *mag_create(const mag_options *opt)
     if (!(o.tol >= 0.0)) o.tol = MAG_TARGET_CG_COST;
     ctx->B = o.tile_nodes ? o.tile_nodes : 512;
     ctx->device = o.device;
-    if (const char *e = getenv("MAG_TUNE_WT")) ctx->tune_wt = ctx->tune_wt_fused = atoi(e);
     hipError_t e = hipSetDevice(ctx->device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
     for (int i = 0; e == hipSuccess && i < 10; ++i) e = hipEventCreate(&ctx->ev[i]);
@@ -2035,7 +2032,7 @@ int mag_run(mag_ctx *ctx)
         HIPCHK(ctx->bc_touch.reserve((size_t)N + 16));
         // the ordering phase has written b = 0.0 + f for every node (apply_order); only the rows with a prescribed column need
         // K, and the pattern kernel has flagged them (bc_touch_ready); otherwise the full pass
-        if (ctx->b_from_order && ctx->bc_touch_ready && !getenv("MAG_TUNE_RHS_FULL"))
+        if (ctx->b_from_order && ctx->bc_touch_ready)
             magk::rhs_touched(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->kval.as<double>(),
                               ctx->uknown.as<uint8_t>(), ctx->uin.as<double>(), ctx->fin.as<double>(),
                               ctx->perm.as<uint32_t>(), ctx->bc_touch.as<uint8_t>(), N, ctx->bP.as<double>(), s);

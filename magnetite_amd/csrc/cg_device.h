@@ -89,76 +89,19 @@ __device__ inline void fan_force(const V2 db, const V2 ub, const V2 dc, const V2
     fy = fma(w, fma(ga, sy, ba * tq), fy);
 }
 
-// Ring walk without per-entry tests.  k_ring16 pads every row to the tile's row length with entries that repeat the
-// last neighbour and carry the break bit, so every entry below 2 * nwords is a real LDS slot: the walk is a chain of
-// unconditional gathers, the loop bound is a scalar (tile-uniform) branch, and only the ADDITION of a triangle's force
-// is selected by the break bit (a repeated entry spans no area: its force is NaN/inf and is selected out, never
-// multiplied in).  With two waves per SIMD the exec-mask bookkeeping of the branchy walk is pure issue-slot cost.
-// NU: entries walked as ONE straight-line block when the tile's rows have at least that many (a closed fan of valence 6
-// is 7 entries: the rule on the benchmark meshes).  A scalar test per entry makes every entry its own basic block, and the
-// instruction scheduler works per block: the chain  2A -> v_rcp_f64 -> two Newton steps -> weight -> force  of one
-// entry (~12 dependent fp64 operations) then cannot overlap the next entry's, and in-kernel stamps showed a wave stalled
-// on its own dependencies half of the time even when it wins every arbitration (profiles/r03_persist_phases.json).  In
-// one block the gathers of all NU entries issue up front and the NU - 1 chains interleave.
-// A second block, entries NU .. NU2 - 1, is walked the same way when the rows have at least NU2 entries (ROCm 7.2's
-// iterative-ilp scheduler, the fastest for this kernel, crashes on blocks of more than four triangles).
+// Ring walk of the on-chip CG kernel's triangle-walk instantiations, without per-entry tests.  k_ring16 pads every row to
+// the tile's row length with entries that repeat the last neighbour and carry the break bit, so every entry below
+// 2 * nwords is a real LDS slot: the walk is a chain of unconditional gathers, the loop bound is a scalar (tile-uniform)
+// branch, and only the ADDITION of a triangle's force is selected by the break bit (a repeated entry spans no area: its
+// force is NaN/inf and is selected out, never multiplied in).
+// The triangles' weights c0 / (2A) are held in registers: 2A depends on the coordinates only, so the cross product, the
+// v_rcp_f64, its two Newton steps and the scaling -- 8 of the ~48 instructions of a ring step, the only quarter-rate one
+// among them -- are paid once per solve instead of once per iteration, by ring_weights() below with the very operations
+// fan_force uses (same bits).  The break bit is folded into the weight (0 for an entry that closes no triangle: its
+// bracket is finite, 0 x finite adds nothing), so the per-entry selects go as well.  NC weights per node (a closed fan of
+// valence 6 has 6 triangles); triangles beyond NC are evaluated by fan_force.
 // IDMASK / toff: the on-chip kernel rewrites the entries in its registers to WORKGROUP-wide LDS slots (15 bits); entries of
 // longer rows still come from the table in memory, tile-local, and are moved by the tile's slot offset `toff`.
-template <int NW, int NU = 1, int NU2 = NU, uint32_t IDMASK = 0xfffu>
-__device__ inline void ring_walk_uniform(const uint32_t (&w)[NW], const uint32_t *more, int32_t stride, int32_t nent,
-                                         const double2 *s_xy, const double2 *s_p, const double2 ca, const double2 pa,
-                                         double c0, double nu, double h, double &fx, double &fy, uint32_t toff = 0)
-{
-    double2 pd, pu;
-    auto step = [&](uint32_t e, bool seed) {
-        const uint32_t id = e & IDMASK;
-        const double2 cxy = s_xy[id], cp = s_p[id];
-        const double2 d = make_double2(cxy.x - ca.x, cxy.y - ca.y), u = make_double2(cp.x - pa.x, cp.y - pa.y);
-        if (!seed) {
-            double dfx = 0.0, dfy = 0.0;
-            fan_force<double2, double>(pd, pu, d, u, c0, nu, h, dfx, dfy);
-            const bool closes = !(e & 0x8000u);
-            fx += closes ? dfx : 0.0;
-            fy += closes ? dfy : 0.0;
-        }
-        pd = d;
-        pu = u;
-    };
-    auto entry = [&](int k) { return (k & 1) ? (w[k >> 1] >> 16) : (w[k >> 1] & 0xffffu); };
-    step(w[0] & 0xffffu, true);
-    if (NU > 1 && nent >= NU) { // nent: a scalar
-#pragma unroll
-        for (int k = 1; k < NU; ++k) step(entry(k), false);
-    } else {
-#pragma unroll
-        for (int k = 1; k < NU; ++k)
-            if (k < nent) step(entry(k), false);
-    }
-    if (NU2 > NU && nent >= NU2) {
-#pragma unroll
-        for (int k = NU; k < NU2; ++k) step(entry(k), false);
-    } else {
-#pragma unroll
-        for (int k = NU; k < NU2; ++k)
-            if (k < nent) step(entry(k), false);
-    }
-#pragma unroll
-    for (int k = NU2; k < 2 * NW; ++k)
-        if (k < nent) step(entry(k), false);
-    for (int32_t k = 2 * NW; k < nent; ++k) {
-        const uint32_t ww = more[(int64_t)(k >> 1) * stride];
-        const uint32_t e = (k & 1) ? (ww >> 16) : (ww & 0xffffu);
-        step(((e & 0xfffu) + toff) | (e & 0x8000u), false);
-    }
-}
-
-// The same walk with the triangles' weights c0 / (2A) held in registers (the on-chip CG kernel): 2A depends on the
-// coordinates only, so the cross product, the v_rcp_f64, its two Newton steps and the scaling -- 8 of the ~48
-// instructions of a ring step, the only quarter-rate one among them -- are paid once per solve instead of once per
-// iteration, by ring_weights() below with the very operations ring_walk_uniform uses (same bits).  The break bit is
-// folded into the weight (0 for an entry that closes no triangle: its bracket is finite, 0 x finite adds nothing), so
-// the per-entry selects go as well.  NC weights per node (a closed fan of valence 6 has 6 triangles); triangles beyond
-// NC are evaluated as before.
 template <int NW, int NC, uint32_t IDMASK = 0xfffu>
 __device__ inline void ring_weights(const uint32_t (&w)[NW], int32_t nent, const double2 *s_xy, const double2 ca, double c0,
                                     double (&wgt)[NC])
@@ -348,11 +291,10 @@ __device__ inline void ring_walk_blocks(const uint32_t (&w)[NW], const double2 *
 // have seven neighbours).  The blocks beyond the registers are 32-byte records {k11, k12 | k22, slot} in the workgroup's
 // LDS pool: this lane's node owns records off .. off + cnt - 1; nmax = the most records any lane of this wave has for this
 // node slot (a scalar: the trip count).  No lane sits out: a lane with fewer records reads record 0 of the pool, a zero
-// block on a valid slot, so a step is straight-line code -- two record reads, one gather, six fp64 operations -- and two
-// steps go together (their four record reads issue at once, then the two gathers).  u_first and u_last of an OPEN fan are
-// always register entries (k_edge_blocks_ovf puts an open row's last entry into block NB - 1 and its middle ones into
-// the pool), so the telescoped antisymmetric part needs nothing from the pool.  Same sums as the short rows', block after
-// block.
+// block on a valid slot, so a step is straight-line code -- two record reads, one gather, six fp64 operations.  u_first
+// and u_last of an OPEN fan are always register entries (k_edge_blocks_ovf puts an open row's last entry into block
+// NB - 1 and its middle ones into the pool), so the telescoped antisymmetric part needs nothing from the pool.  Same sums
+// as the short rows', block after block.
 template <int NW, int NB, uint32_t IDMASK = 0xfffu>
 __device__ inline void ring_walk_blocks_ovf(const uint32_t (&w)[NW], const double2 *s_p, const double2 pa, double kappa,
                                             bool folded, const double (&kb)[3 * NB], const double2 *pool, uint32_t off,
@@ -385,48 +327,15 @@ __device__ inline void ring_walk_blocks_ovf(const uint32_t (&w)[NW], const doubl
         fx = fma(a.y, u.y, fma(a.x, u.x, fx));
         fy = fma(b.x, u.y, fma(a.y, u.x, fy));
     };
-    // nmax is a scalar: one record (most waves of a frontal mesh: some lane has a seventh neighbour), two together (some lane
-    // has an eighth), the rare rest one at a time -- not unrolled: an unrolled loop here takes its registers from the blocks
-#ifndef MAG_PERSIST_OVF_PAIR
-#define MAG_PERSIST_OVF_PAIR 0 // 1: the first two records together (four record reads in flight) -- measured slower, 7.51 against 7.10 us per iteration on the 1M frontal mesh: the pair takes six block registers to scratch, and their reload waits for the node slot's granule stores
-#endif
-#if MAG_PERSIST_OVF_PAIR
-    if (nmax == 1) {
-        const uint32_t i0 = rec_of(0);
-        const double2 a0 = pool[i0], b0 = pool[i0 + 1];
-        apply(a0, b0);
-    } else if (nmax >= 2) {
-        const uint32_t i0 = rec_of(0), i1 = rec_of(1);
-        const double2 a0 = pool[i0], b0 = pool[i0 + 1], a1 = pool[i1], b1 = pool[i1 + 1];
-        apply(a0, b0);
-        apply(a1, b1);
+    // nmax is a scalar (most waves of a frontal mesh: some lane has a seventh neighbour), one record at a time -- not
+    // unrolled: an unrolled loop here takes its registers from the blocks (taking the first two together was measured
+    // slower in round 4: the pair's registers went to scratch)
 #pragma clang loop unroll(disable)
-        for (int32_t k = 2; k < nmax; ++k) {
-            const uint32_t i2 = rec_of(k);
-            const double2 a2 = pool[i2], b2 = pool[i2 + 1];
-            apply(a2, b2);
-        }
-    }
-#else
-    // MAG_PERSIST_OVF_UNCOND records are taken by EVERY wave, in the same basic block as the register blocks (their record
-    // reads issue alongside the six gathers; a wave none of whose lanes has that many reads the zero record): on a frontal
-    // mesh nearly every wave has a lane with a seventh neighbour.  The rest in a loop that is not unrolled.
-#ifndef MAG_PERSIST_OVF_UNCOND
-#define MAG_PERSIST_OVF_UNCOND 0
-#endif
-#pragma unroll
-    for (int32_t k = 0; k < MAG_PERSIST_OVF_UNCOND; ++k) {
+    for (int32_t k = 0; k < nmax; ++k) {
         const uint32_t i2 = rec_of(k);
         const double2 a2 = pool[i2], b2 = pool[i2 + 1];
         apply(a2, b2);
     }
-#pragma clang loop unroll(disable)
-    for (int32_t k = MAG_PERSIST_OVF_UNCOND; k < nmax; ++k) {
-        const uint32_t i2 = rec_of(k);
-        const double2 a2 = pool[i2], b2 = pool[i2 + 1];
-        apply(a2, b2);
-    }
-#endif
 }
 
 } // namespace magk

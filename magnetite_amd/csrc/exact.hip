@@ -5,7 +5,6 @@
 // and the stress scalar reproduce the reference's rounding, not just its
 // formulas.  None of these kernels is in the CG loop.
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 
 #include <hip/hip_runtime.h>
@@ -90,49 +89,10 @@ void element_stiffness(const double *xy, const int32_t *conn, int64_t E, double 
     k_element_stiffness<<<blocks_for(E, 256), 256, 0, s>>>((const double2 *)xy, conn, E, nu, youngs, thick, ke);
 }
 
-// solver.rs:290-331 without the dense matrix and without atomics: the sorted
-// (row node, col node) pair list groups every '+=' that lands on one 2x2
-// block; inside a group the stable sort kept ascending element order, which
-// is the reference's summation order (0.0 + first contribution is exact).
-__global__ void __launch_bounds__(256) k_assemble_gather(const uint64_t *keys, const uint32_t *vals,
-                                                         const int32_t *seg_start, int64_t nb, const int32_t *bptr,
-                                                         const double *ke, double *kval)
-{
-    const int64_t blk = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (blk >= nb) return;
-    const int32_t s0 = seg_start[blk], s1 = seg_start[blk + 1];
-    const int32_t i = (int32_t)(keys[s0] >> 32);
-    double k00 = 0.0, k01 = 0.0, k10 = 0.0, k11 = 0.0;
-    for (int32_t k = s0; k < s1; ++k) {
-        const uint32_t v = vals[k];
-        const uint32_t e = v / 9u, ab = v - 9u * e;
-        const uint32_t a = ab / 3u, b = ab - 3u * a;
-        const double *src = ke + 36 * (int64_t)e + 12 * a + 2 * b; // K_e[2a][2b]
-        k00 += src[0];
-        k01 += src[1];
-        k10 += src[6];
-        k11 += src[7];
-    }
-    const int32_t p = bptr[i], cnt = bptr[i + 1] - p, kpos = (int32_t)blk - p;
-    double *r0 = kval + 4 * (int64_t)p + 2 * kpos;
-    double *r1 = kval + 4 * (int64_t)p + 2 * cnt + 2 * kpos;
-    r0[0] = k00;
-    r0[1] = k01;
-    r1[0] = k10;
-    r1[1] = k11;
-}
-
-void assemble_gather(const uint64_t *keys, const uint32_t *vals, const int32_t *seg_start, int64_t nb,
-                     const int32_t *bptr, const double *ke, double *kval, hipStream_t s)
-{
-    k_assemble_gather<<<blocks_for(nb, 256), 256, 0, s>>>(keys, vals, seg_start, nb, bptr, ke, kval);
-}
-
-// solver.rs:263-278 + 290-331 fused and still atomic-free: one thread per (row node i, col node j) block of K walks
-// node i's incident elements in ascending element order (the reference's '+=' order) and, for every element that also
-// holds j, evaluates ONLY the 2x2 block K_e[2a..2a+1][2b..2b+1] -- each entry with exactly the operations
-// nalgebra performs for it ((B^T D) B, ascending-k sums from the first product, then * area * thickness), so the
-// result is bit-identical to scattering full K_e matrices.  No 288-byte-per-element K_e buffer is written or read.
+// solver.rs:263-278 for ONE 2x2 block K_e[2a..2a+1][2b..2b+1] of an element: area and divisions re-derived, each entry
+// with exactly the operations nalgebra performs for it ((B^T D) B, ascending-k sums from the first product, then * area
+// * thickness), so the result is bit-identical to scattering full K_e matrices.  The assembly kernels below finish the
+// rows that do not fit their fast paths with it, one thread per (row node, col node) block.
 __device__ inline void ke_block(const double2 v0, const double2 v1, const double2 v2, int a, int b, const double *D,
                                 double thick, double &k00, double &k01, double &k10, double &k11)
 {
@@ -172,54 +132,6 @@ __device__ inline void ke_block(const double2 v0, const double2 v1, const double
     k11 = dot3(My, By_b) * area * thick;
 }
 
-__global__ void __launch_bounds__(256) k_assemble_rows(const int32_t *brow, const int32_t *bcol, const int32_t *bptr,
-                                                       int64_t nb, const int32_t *inc_off, const uint32_t *inc,
-                                                       const int32_t *iperm, const int32_t *conn, const double2 *xy,
-                                                       double nu, double youngs, double thick, double *kval)
-{
-    const int64_t blk = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (blk >= nb) return;
-    const int32_t i = brow[blk], j = bcol[blk];
-    double D[9];
-    stress_strain(nu, youngs, D);
-    const int32_t g = iperm[i]; // incidence lists are keyed by the Hilbert id
-    double k00 = 0.0, k01 = 0.0, k10 = 0.0, k11 = 0.0;
-    for (int32_t q = inc_off[g]; q < inc_off[g + 1]; ++q) {
-        const uint32_t v = inc[q];
-        const uint32_t e = v / 3u;
-        const int a = (int)(v - 3u * e);
-        const int32_t n0 = conn[3 * (int64_t)e], n1 = conn[3 * (int64_t)e + 1], n2 = conn[3 * (int64_t)e + 2];
-        if (n0 != j && n1 != j && n2 != j) continue;
-        const double2 v0 = xy[n0], v1 = xy[n1], v2 = xy[n2];
-        const int32_t nn[3] = {n0, n1, n2};
-#pragma unroll
-        for (int b = 0; b < 3; ++b) { // ascending local column, as the loops of solver.rs:304-322
-            if (nn[b] != j) continue;
-            double c00, c01, c10, c11;
-            ke_block(v0, v1, v2, a, b, D, thick, c00, c01, c10, c11);
-            k00 += c00;
-            k01 += c01;
-            k10 += c10;
-            k11 += c11;
-        }
-    }
-    const int32_t p = bptr[i], cnt = bptr[i + 1] - p, kpos = (int32_t)blk - p;
-    double *r0 = kval + 4 * (int64_t)p + 2 * kpos;
-    double *r1 = kval + 4 * (int64_t)p + 2 * cnt + 2 * kpos;
-    r0[0] = k00;
-    r0[1] = k01;
-    r1[0] = k10;
-    r1[1] = k11;
-}
-
-void assemble_rows(const int32_t *brow, const int32_t *bcol, const int32_t *bptr, int64_t nb, const int32_t *inc_off,
-                   const uint32_t *inc, const int32_t *iperm, const int32_t *conn, const double *xy, double nu,
-                   double youngs, double thick, double *kval, hipStream_t s)
-{
-    k_assemble_rows<<<blocks_for(nb, 256), 256, 0, s>>>(brow, bcol, bptr, nb, inc_off, inc, iperm, conn,
-                                                        (const double2 *)xy, nu, youngs, thick, kval);
-}
-
 // solver.rs:263-278 + 290-331 per ELEMENT TILE (the shape BASELINE.json's north star names), still atomic-free and
 // bit-exact.  A tile is kAsmNodes consecutive nodes of the Hilbert order -- a compact patch of the mesh -- with every
 // element incident on them; one workgroup (two wavefronts) per tile, one thread per ROW NODE i:
@@ -234,11 +146,10 @@ void assemble_rows(const int32_t *brow, const int32_t *bcol, const int32_t *bptr
 //   * the blocks are added into the row's accumulators, which live in LDS ([slot][thread], 16-byte pieces: conflict-
 //     free), at the position of node n_b among the row's sorted columns; at the end the thread stores its two scalar
 //     CSR rows (two runs of 16 * cnt bytes).
-// Against k_assemble_rows (one thread per block re-deriving area and five divisions per matching element, each row's
-// entries scanned by every block of the row: ~9 evaluations and ~21 entry visits per element) an element is evaluated
-// once per incident node (3) and visited 3 times.  Rows with more than kAsmSlots blocks (valence > 7) do not fit the
-// accumulators: the workgroup finishes them together, one thread per block, with the k_assemble_rows arithmetic --
-// same bits.
+// Against one thread per block (round 1: area and five divisions re-derived per matching element, each row's entries
+// scanned by every block of the row: ~9 evaluations and ~21 entry visits per element) an element is evaluated once per
+// incident node (3) and visited 3 times.  Rows with more than kAsmSlots blocks (valence > 7) do not fit the
+// accumulators: the workgroup finishes them together, one thread per block, with ke_block -- same bits.
 constexpr int kAsmNodes = 128; // row nodes (threads) per tile
 constexpr int kAsmSlots = 8;   // 2x2 blocks a row may hold in its LDS accumulators (valence 6 interior node: 7)
 constexpr int kAsmBatch = 4;   // incidence entries whose gathers a thread issues together (the kernel is latency-bound)
@@ -355,7 +266,7 @@ __global__ void __launch_bounds__(kAsmNodes) k_assemble_tiles(const int32_t *bco
                 r1[2 * k + 1] = bot.y;
             }
     }
-    // rows that did not fit the accumulators: the whole workgroup, one thread per block, k_assemble_rows arithmetic
+    // rows that did not fit the accumulators: the whole workgroup, one thread per block, ke_block arithmetic
     if (!__syncthreads_or(g < N && cnt > kAsmSlots)) return;
     int32_t *s_big = (int32_t *)s_top; // every fast row has been stored: the accumulators are free (5 workgroups of
     s_big[lane] = (g < N && cnt > kAsmSlots) ? (int32_t)i : -1; // exactly 32 KiB fit a CU's 160 KiB)
@@ -450,7 +361,7 @@ void assemble_tiles(const int32_t *bcol, const int32_t *bptr, const int32_t *inc
 // >= 2e-166) and per element by 1e-40 < |2A| < 1e60; otherwise the true divisions run.  Under the same bounds (and
 // |D| < 1e60, |thickness| < 1e30) the terms with a structural zero of B or D are left out (see asm_fan_blocks).
 // Rows the scheme does not cover -- more than 8 triangles, an edge with three or more triangles, an element
-// that lists a node twice -- are finished by the whole workgroup with the k_assemble_rows arithmetic (label order, true
+// that lists a node twice -- are finished by the whole workgroup with the ke_block arithmetic (label order, true
 // divisions), as in k_assemble_tiles.  Tiles whose image does not fit fall back to k_assemble_tiles altogether.
 __device__ inline double div_shared(double x, double d, double r)
 {
@@ -553,28 +464,16 @@ __device__ inline void wave_lds_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-// One 16-byte piece of K.  MAG_ASM_STORE: 0 plain (write-back), 1 non-temporal, 2 write-through (sc1: the bytes go out while
-// the kernel still computes).  Measured in one session, numeric assembly at 1M / 4M triangles: 45.0 / 166.8 us plain,
-// 42.9 / 171.2 non-temporal, 42.8 / 162.4 write-through (scripts/asm_store_ab.py): write-through.
-#ifndef MAG_ASM_STORE
-#define MAG_ASM_STORE 2
-#endif
+// One 16-byte piece of K, write-through (sc1: the bytes go out while the kernel still computes).  Measured in one session,
+// numeric assembly at 1M / 4M triangles: 45.0 / 166.8 us plain, 42.9 / 171.2 non-temporal, 42.8 / 162.4 write-through.
 __device__ inline void k_store(double *dst, double2 v)
 {
-#if MAG_ASM_STORE == 1
-    typedef double v2d __attribute__((ext_vector_type(2)));
-    v2d t = {v.x, v.y};
-    __builtin_nontemporal_store(t, (v2d *)dst);
-#elif MAG_ASM_STORE == 2
     typedef unsigned int u4 __attribute__((ext_vector_type(4)));
     u4 t;
     __builtin_memcpy(&t, &v, 16);
     // (s_nop: the registers of a store of more than 8 bytes must not be rewritten in the next two cycles; the compiler
     // keeps that distance for its own stores and cannot see into this one)
     asm volatile("global_store_dwordx4 %0, %1, off sc1" MAG_WS_DATA : : "v"(dst), "v"(t) : "memory");
-#else
-    *(double2 *)dst = v;
-#endif
 }
 
 constexpr int kFanThreads = 256; // 32 nodes x 8 lanes per pass
@@ -772,7 +671,7 @@ __global__ void __launch_bounds__(kFanThreads) k_assemble_fan(const int32_t *bco
             }
         }
     }
-    // rows the fan scheme did not take: the whole workgroup, one thread per block, k_assemble_rows arithmetic
+    // rows the fan scheme did not take: the whole workgroup, one thread per block, ke_block arithmetic
     if (!__syncthreads_or(any_big ? 1 : 0)) return;
     for (int m = lfirst; m < lend; ++m) {
         const int32_t ib = s_big[m];
@@ -831,9 +730,7 @@ bool assemble_ctiles(const int32_t *bcol, const int32_t *bptr, const uint32_t *p
     // 3911 tiles 1: 152, 2: 165)
     int32_t segs = 1;
     while ((int64_t)T * segs < 768 && B / (2 * segs) >= kFanThreads / kFanLanes) segs *= 2;
-    const char *e6 = getenv("MAG_TUNE_ASM_LANES"); // 8: never six lanes per node
-    const int32_t six = e6 && atoi(e6) == 8 ? 0 : 1;
-    if (const char *e = getenv("MAG_TUNE_ASM_SEGS")) segs = std::max(1, std::min(atoi(e), B / (kFanThreads / kFanLanes)));
+    const int32_t six = 1; // six lanes per node where the rows allow it (0: eight for every row)
     if (B == 256)
         k_assemble_fan<256><<<T * segs, kFanThreads, lds, s>>>(
             bcol, bptr, perm, (const double2 *)xyP, (const double2 *)halo_xy, tile_hoff, tile_deg, tile_off, ell_asm,

@@ -121,16 +121,9 @@ void reduce_fill(const int32_t *bptr, const int32_t *bcol, const double *kval, c
 // solver.rs:263-278 per element, ke[36e + 6i + j]
 void element_stiffness(const double *xy, const int32_t *conn, int64_t E, double nu, double youngs, double thick,
                        double *ke, hipStream_t s);
-// solver.rs:290-331 as an atomic-free gather: one thread per (row node, col node) block sums its segment of
-// sorted pairs in ascending element order into the four scalar CSR slots.
-void assemble_gather(const uint64_t *keys, const uint32_t *vals, const int32_t *seg_start, int64_t nb,
-                     const int32_t *bptr, const double *ke, double *kval, hipStream_t s);
-// the same assembly without the K_e buffer: per (row,col) block, only the needed 2x2 blocks of the incident elements
-void assemble_rows(const int32_t *brow, const int32_t *bcol, const int32_t *bptr, int64_t nb, const int32_t *inc_off,
-                   const uint32_t *inc, const int32_t *iperm, const int32_t *conn, const double *xy, double nu,
-                   double youngs, double thick, double *kval, hipStream_t s);
-// the same per element tile (kAsmNodes nodes of the Hilbert order + their incident elements, one workgroup each): element
-// areas and the divided B entries staged once per (node, element) entry in LDS, blocks gathered from LDS (default)
+// solver.rs:290-331, atomic-free, per element tile (kAsmNodes nodes of the Hilbert order + their incident elements, one
+// workgroup each): element areas and the divided B entries staged once per (node, element) entry in LDS, blocks gathered
+// from LDS
 void assemble_tiles(const int32_t *bcol, const int32_t *bptr, const int32_t *inc_off, const uint32_t *inc,
                     const uint32_t *perm, const int32_t *conn, const double *xy, int64_t N, double nu, double youngs,
                     double thick, double *kval, hipStream_t s);
@@ -411,12 +404,12 @@ struct PersistParams {
 void stream_exchange_launch(double *buf, int32_t g_all, int32_t n_iface, int32_t rank, int32_t nranks, int32_t own0,
                             int32_t own1, int32_t fpar, uint32_t spin_limit, const int32_t *iface,
                             const uint8_t *iface_readers, void *const *inboxes, FusedState *st, hipStream_t s);
-int persist_threads(); // workgroup shape of the on-chip kernel: 512 (x 4 nodes per lane) or 768 (x 3); MAG_TUNE_PERSIST_THREADS
-int persist_tiles_per_wg(int32_t B, int threads); // tiles one workgroup keeps on chip (0: tile size not supported)
+// the on-chip kernel's workgroup: 512 threads x 4 nodes per lane
+int persist_tiles_per_wg(int32_t B); // tiles one workgroup keeps on chip (0: tile size not supported)
 // eb_mode: 0 triangle walk, 1 edge blocks (every row a fan of <= 6 blocks), 2 edge blocks with `pool` overflow records in LDS
-size_t persist_lds_bytes(int32_t B, int32_t cap, int32_t maxh, int threads, int eb_mode = 0, int32_t pool = 0, bool mg = false);
+size_t persist_lds_bytes(int32_t B, int32_t cap, int32_t maxh, int eb_mode = 0, int32_t pool = 0, bool mg = false);
 // MG kernel when nranks > 1; eb_mode as above (the host decides from ring16's flags and the overflow limits)
-void persist_launch(const PersistParams &P, int32_t B, int32_t grid, int threads, int eb_mode, hipStream_t s);
+void persist_launch(const PersistParams &P, int32_t B, int32_t grid, int eb_mode, hipStream_t s);
 int persist_block_entries(); // block entries per node of that instantiation
 // ... and its blocks: 3 * persist_block_entries() doubles per node of the T * B padded nodes, into P.kblocks (host sets
 // kblocks / kb_stride before the call; eb_mode 2: row_info / ovf_off / ovf_rec as well)

@@ -1,6 +1,5 @@
 // On-chip conjugate gradients: the whole solve in one launch (see the comment below).  Its own translation unit because
 // it is compiled with a different instruction scheduler than the streaming kernels of cg.hip (Makefile).
-#include <cstdlib>
 #include <cstring>
 
 #include <hip/hip_runtime.h>
@@ -22,18 +21,10 @@ namespace magk {
 // Same recurrences and state machine as k_cg_fused (alpha, beta from the four exact sums of the previous iterate).
 // MG instantiation: several GPUs, each running its tile range, exchanging through per-rank inboxes (further down).
 typedef __attribute__((address_space(1))) unsigned int gu32;
-// Two shapes of the workgroup, both keeping four 512-node tiles (2048 nodes) per CU:
-//   512 threads x 4 nodes per lane: 8 waves = 2 per SIMD, up to 256 VGPRs per lane (round 1-2);
-//   768 threads x 3 nodes per lane: 12 waves = 3 per SIMD, 168 VGPRs per lane -- a third wave per SIMD to cover LDS
-//       gather latency (round 2's counters: waves parked 0.52 of the time, vector pipe busy 0.49); local node n of the
-//       workgroup sits in lane n % 768, slot n / 768, so waves 0-7 carry three nodes per lane and waves 8-11 two, and
-//       every SIMD (waves w, w + 4, w + 8) still gets eight node-slots.  Built and measured in round 3 (-DMAG_PERSIST_768,
-//       MAG_TUNE_PERSIST_THREADS=768; profiles/r03_persist_phases.json): 11.55 against 11.07 us per iteration at 1M
-//       triangles, 6.41 against 5.46 at 100k -- the ring walks are bound by fp64 issue, not by latency (the stamps show
-//       the walks of a workgroup taking 7.7 against 7.3 us), and a 12-wave workgroup pays more at every barrier.  Not
-//       instantiated in the product.
+// The workgroup: 512 threads x 4 nodes per lane (four 512-node tiles, 2048 nodes per CU), 8 waves = 2 per SIMD, up to 256
+// VGPRs per lane.  (A 768 x 3 shape, a third wave per SIMD, measured 4 % slower in round 3: profiles/r03_persist_phases.json.)
 // Local node n = slot * THREADS + lane belongs to local tile n / B: uniform over a wave (64 | B, 64 | THREADS).
-constexpr int kPersistThreadsDefault = 512;
+constexpr int kPersistThreads = 512, kPersistNpt = 4;
 
 // Inter-workgroup exchange by self-validating granules (CDNA4 guide, Guideline 16 R2: "the data IS the flag"): every
 // handed-off 32-bit half travels in its own naturally aligned 8-byte word {value, tag = epoch}; two of them are written
@@ -118,15 +109,6 @@ __device__ inline double wave_sum_dpp(double v)
 // 0-6 the phases, 7 sweeps taken; detail (round 4): 8 wave trees of the sums, 9 the sums' barrier (waiting for the workgroup's
 // slowest wave), 10 cross-wave chain + record store, 11 the deferred x update, 12 after this wave's sweeps: waiting for the
 // workgroup's other waves, 13 record reduction + its barrier
-#ifndef MAG_PERSIST_OPAQUE
-#define MAG_PERSIST_OPAQUE 1 // the thread index behind an empty asm: 0 nowhere, 1 in the overflow instantiation, 2 everywhere
-#endif
-#ifndef MAG_PERSIST_OPAQUE_XCHG
-#define MAG_PERSIST_OPAQUE_XCHG 1
-#endif
-#ifndef MAG_PERSIST_OPAQUE_SUM
-#define MAG_PERSIST_OPAQUE_SUM 1
-#endif
 constexpr int kStampPhases = 14;
 
 // a lane's double moved by a DPP control (lanes without a source read 0)
@@ -138,17 +120,22 @@ __device__ inline double dpp_move_f64(double v)
     return __hiloint2double(hi, lo);
 }
 
+// The two s_sleep of the exchange's first wait, swept per instantiation in rounds 2-4 (the edge-block one arrives ~1.5 us
+// earlier and settled on the same pair; profiles/r03_persist_ab.txt, the rest in git history).
+constexpr int kPersistSleep1 = 6, kPersistSleep2 = 4;
+constexpr int kPersistSleepMg = 20; // the multi-GPU exchange's first wait: two s_sleep of this length
+
 // Wait for epoch `epoch`: every workgroup's partial record (two 16-byte pieces each, one per thread) and the q of this
 // thread's halo nodes, swept together until every tag matches; then the records are summed in one fixed two-level
 // order (chunks of eight workgroups, then the chunks) so that all workgroups hold the same bits.  grid <= 256.
 // Returns false when the spin budget runs out (some workgroup is not running): the timeout word is set for the host.
-template <int NH, bool EB = false, bool OPQ = false>
+template <int NH, bool OPQ = false>
 __device__ inline bool persist_exchange(const PersistParams &P, int par, unsigned epoch, const int32_t (&hg)[NH],
                                         double2 (&hq)[NH], double *s_S, double2 *s_rec, double *s_chunk, double *s_part,
                                         double (&Sx)[4], unsigned long long *stamp = nullptr)
 {
     int tid = threadIdx.x;
-    if (OPQ && MAG_PERSIST_OPAQUE_XCHG) asm volatile("" : "+v"(tid)); // (recomputed LDS addresses instead of hoisted and spilled ones: see persist_block_sum)
+    if (OPQ) asm volatile("" : "+v"(tid)); // (recomputed LDS addresses instead of hoisted and spilled ones: see persist_block_sum)
     const int grid = gridDim.x;
     gu32 *tmo = (gu32 *)P.sync + 9;
     // One sweep fetches what is still missing of both: a 16-byte piece of the records per thread and the q of this
@@ -162,34 +149,13 @@ __device__ inline bool persist_exchange(const PersistParams &P, int par, unsigne
         hq[s] = make_double2(0.0, 0.0);
     }
     bool done = false;
-    // ~0.85 us in all: the other workgroups' records are still on their way, and a sweep that comes too early costs a
-    // full round trip.  Two fixed s_sleep instructions, re-tuned in round 2 on one box (us per iteration at 1M triangles):
-    // 10+10 10.89, 12+12 10.85, 14+14 10.79, 16+8 10.85, 16+16 10.62, 18+14 10.58, 20+20 10.67, 24+24 10.86; one
-    // s_sleep(32) 10.74, one s_sleep(40) 10.79; the same 40 units as a run-time loop of ten s_sleep(4) 10.87.  Round 3, with the
-    // shorter walks and half the halo fetched (profiles/r03_persist_ab.txt): 10+6 8.91, 12+10 8.70, 14+8 8.70, 14+10 8.70,
-    // 14+12 8.73, 16+10 8.72, 18+14 8.80, 22+16 8.95, 26+20 9.19, one s_sleep(24) 8.72.  With x += alpha p moved into this
-    // wait (it takes about half of it): 2 8.34, 4+2 8.20, 6+4 8.23 (4.44 at 100k, where 4+2 gives 4.60), 8+6 8.30, 10+8 8.36.
-#ifndef MAG_PERSIST_SLEEP1
-#define MAG_PERSIST_SLEEP1 6
-#define MAG_PERSIST_SLEEP2 4
-#endif
-    // The edge-block instantiation reaches this point ~1.5 us earlier in the iteration; re-swept for it (us per iteration at
-    // 1M / 100k triangles, one box): 4+2 6.79, 6+4 6.69 / 4.50, 8+6 6.63 / 4.37, 10+8 6.66 / 4.32, 12+10 6.73 / 4.39, 14+12 6.81.
-    // After the workgroup's final sums became a cross-lane chain (persist_block_sum: the record leaves ~0.4 us earlier):
-    // 2+0 6.40 / 4.28, 4+2 6.11 / 4.26, 4+4 6.09 / 4.12, 6+4 6.09 / 4.05, 8+6 6.15 / 4.09, 10+8 6.23 / 4.14, 12+10 6.32 / 4.26.
-#ifndef MAG_PERSIST_SLEEP1_EB
-#define MAG_PERSIST_SLEEP1_EB 6
-#define MAG_PERSIST_SLEEP2_EB 4
-#endif
-    __builtin_amdgcn_s_sleep(EB ? MAG_PERSIST_SLEEP1_EB : MAG_PERSIST_SLEEP1);
-    if ((EB ? MAG_PERSIST_SLEEP2_EB : MAG_PERSIST_SLEEP2) > 0) __builtin_amdgcn_s_sleep(EB ? MAG_PERSIST_SLEEP2_EB : MAG_PERSIST_SLEEP2);
+    // ~0.85 us in all: the other workgroups' records are still on their way, and a sweep that comes too early costs a full
+    // round trip.  x += alpha p runs in this wait (the loop of k_cg_persist) and takes about half of it.
+    __builtin_amdgcn_s_sleep(kPersistSleep1);
+    __builtin_amdgcn_s_sleep(kPersistSleep2);
 #ifdef MAG_PERSIST_STAMPS
     if (stamp) stamp[0] = __builtin_amdgcn_s_memrealtime();
 #endif
-#ifndef MAG_PERSIST_POLL
-#define MAG_PERSIST_POLL 1
-#endif
-#if MAG_PERSIST_POLL
     // Every WAVE polls for what its own lanes still miss and the workgroup meets once, when every wave has everything:
     // a workgroup barrier per sweep (round 1-2) made every sweep as slow as the slowest wave's loads and started the next
     // one only after all of them.
@@ -225,7 +191,7 @@ __device__ inline bool persist_exchange(const PersistParams &P, int par, unsigne
     // every wave has everything?  One flag word per wave, ONE barrier (also: s_rec complete), one 32-byte read: the
     // library's __syncthreads_and is three barriers around an LDS atomic.
     {
-        constexpr int NWV = 8; // (512 threads; the 768-thread shape takes the library call)
+        constexpr int NWV = 8; // (512 threads; any other shape would take the library call)
         if (blockDim.x == 64 * NWV) {
             uint32_t *s_flag = (uint32_t *)(s_chunk + 4); // words 4 .. 7 of s_chunk: free (0, 1: best_param; 16 ..: stamps)
             if ((tid & 63) == 0) s_flag[tid >> 6] = wave_ok ? 1u : 0u;
@@ -244,40 +210,6 @@ __device__ inline bool persist_exchange(const PersistParams &P, int par, unsigne
         stamp[1] = __builtin_amdgcn_s_memrealtime();
         stamp[2] = spins + 1;
     }
-#endif
-#else
-    for (unsigned spins = 0; spins < P.spin_limit; ++spins) {
-        bool ok = true;
-        if (!have_rec) {
-            double2 v;
-            have_rec = get_granules(recb, 64u * (uint32_t)grid, 32u * (uint32_t)tid, epoch, v);
-            if (have_rec) s_rec[tid] = v;
-            ok = have_rec;
-        }
-#pragma unroll
-        for (int s = 0; s < NH; ++s)
-            if (!have_h[s]) {
-                have_h[s] = get_granules(qbase, 32u * (uint32_t)P.N, 32u * (uint32_t)hg[s], epoch, hq[s]);
-                ok &= have_h[s];
-            }
-        if (__syncthreads_and(ok ? 1 : 0)) {
-            done = true;
-#ifdef MAG_PERSIST_STAMPS
-            if (stamp) {
-                stamp[1] = __builtin_amdgcn_s_memrealtime();
-                stamp[2] = spins + 1;
-            }
-#endif
-            break;
-        }
-        if ((spins & 255u) == 255u) { // somebody else gave up: do not wait for a grid that will never be complete
-            const int dead =
-                tid == 0 && __hip_atomic_load(tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u ? 1 : 0;
-            if (__syncthreads_or(dead)) break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
-    __syncthreads(); // s_rec complete
 #endif
     if (!done) {
         if (tid == 0) __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -448,11 +380,8 @@ __device__ inline bool persist_exchange_mg(const PersistParams &P, int par, unsi
         }
         return false;
     };
-#ifndef MAG_PERSIST_SLEEP_MG
-#define MAG_PERSIST_SLEEP_MG 20
-#endif
-    __builtin_amdgcn_s_sleep(MAG_PERSIST_SLEEP_MG);
-    __builtin_amdgcn_s_sleep(MAG_PERSIST_SLEEP_MG);
+    __builtin_amdgcn_s_sleep(kPersistSleepMg);
+    __builtin_amdgcn_s_sleep(kPersistSleepMg);
 #ifdef MAG_PERSIST_STAMPS
     if (stamp) stamp[0] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -714,7 +643,7 @@ __device__ inline void persist_comm_loop(const PersistParams &P, double *s_S, do
     }
 }
 
-// Workgroup totals of four partial sums for the two publishing threads (0 and 1).
+// Workgroup totals of four partial sums (512 threads: eight waves) for the two publishing threads (0 and 1).
 // Round 4 (512 threads): the in-kernel stamps put 0.37 us into four full DPP wave trees and 0.49 us into the seven-step
 // cross-wave chain + the record's store -- a microsecond between the last walk and the record leaving, every iteration.
 // Now ONE tree serves the four sums: level 1 (lane pairs) halves the values a lane carries from four to two -- even lanes
@@ -723,124 +652,54 @@ __device__ inline void persist_comm_loop(const PersistParams &P, double *s_S, do
 // adds them with one 16-byte read and a four-step tree per row -- 7 + 5 additions on the critical path where there were
 // 24 + 7, a fixed order of additions as before (so every run gives the same bits; they are not round 3's bits).
 constexpr int kPersistPartDoubles = 128; // s_part: four sums x (8 waves x 4 rows)
-template <int THREADS, bool OPQ = false>
-__device__ inline void persist_block_sum(double (&acc)[4], double *s_red, double *s_part,
-                                         [[maybe_unused]] unsigned long long *sub = nullptr)
+template <bool OPQ = false>
+__device__ inline void persist_block_sum(double (&acc)[4], double *s_part, [[maybe_unused]] unsigned long long *sub = nullptr)
 {
-    constexpr int kPersistThreads = THREADS;
-    constexpr int NWV = kPersistThreads / 64;
-    if (NWV == 8) {
-        // (tx: the thread index behind an empty asm -- the LDS addresses below are then recomputed in every iteration, three
-        // instructions each.  Taken from threadIdx.x directly they are loop-invariant: the compiler hoisted them out of the CG
-        // loop, had no registers to keep them in -- the edge-block kernel sits at 256 of 256 -- and spilled them: nine
-        // scratch reloads per iteration, each behind an s_waitcnt vmcnt(0), i.e. behind the granule stores in flight.)
-        int tx = threadIdx.x;
-        if (OPQ && MAG_PERSIST_OPAQUE_SUM) asm volatile("" : "+v"(tx));
-        const int l = tx & 63;
-        const bool odd = (l & 1) != 0, two = (l & 2) != 0;
-        // level 1, lanes l and l ^ 1 (quad_perm [1, 0, 3, 2]): an even lane keeps sums 0, 1 and hands over 2, 3; an odd lane the reverse
-        const double ka = odd ? acc[2] : acc[0], kb = odd ? acc[3] : acc[1];
-        const double sa = odd ? acc[0] : acc[2], sb = odd ? acc[1] : acc[3];
-        const double a = ka + dpp_move_f64<0xB1>(sa), b = kb + dpp_move_f64<0xB1>(sb);
-        // level 2, lanes l and l ^ 2 (quad_perm [2, 3, 0, 1]): lanes 0, 1 of a quad keep a, lanes 2, 3 keep b
-        const double k2 = two ? b : a, s2 = two ? a : b;
-        double v = k2 + dpp_move_f64<0x4E>(s2); // lane l of a quad now holds the quad's total of sum {0, 2, 1, 3}[l & 3]
-        v += dpp_move_f64<0x114>(v);            // row_shr:4
-        v += dpp_move_f64<0x118>(v);            // row_shr:8: lanes 12-15 of every row hold the row's totals
-        if ((l & 15) >= 12) s_part[(((l & 1) << 1) | ((l >> 1) & 1)) * 32 + (tx >> 6) * 4 + (l >> 4)] = v;
+    // (tx: the thread index behind an empty asm -- the LDS addresses below are then recomputed in every iteration, three
+    // instructions each.  Taken from threadIdx.x directly they are loop-invariant: the compiler hoisted them out of the CG
+    // loop, had no registers to keep them in -- the edge-block kernel sits at 256 of 256 -- and spilled them: nine
+    // scratch reloads per iteration, each behind an s_waitcnt vmcnt(0), i.e. behind the granule stores in flight.)
+    int tx = threadIdx.x;
+    if (OPQ) asm volatile("" : "+v"(tx));
+    const int l = tx & 63;
+    const bool odd = (l & 1) != 0, two = (l & 2) != 0;
+    // level 1, lanes l and l ^ 1 (quad_perm [1, 0, 3, 2]): an even lane keeps sums 0, 1 and hands over 2, 3; an odd lane the reverse
+    const double ka = odd ? acc[2] : acc[0], kb = odd ? acc[3] : acc[1];
+    const double sa = odd ? acc[0] : acc[2], sb = odd ? acc[1] : acc[3];
+    const double a = ka + dpp_move_f64<0xB1>(sa), b = kb + dpp_move_f64<0xB1>(sb);
+    // level 2, lanes l and l ^ 2 (quad_perm [2, 3, 0, 1]): lanes 0, 1 of a quad keep a, lanes 2, 3 keep b
+    const double k2 = two ? b : a, s2 = two ? a : b;
+    double v = k2 + dpp_move_f64<0x4E>(s2); // lane l of a quad now holds the quad's total of sum {0, 2, 1, 3}[l & 3]
+    v += dpp_move_f64<0x114>(v);            // row_shr:4
+    v += dpp_move_f64<0x118>(v);            // row_shr:8: lanes 12-15 of every row hold the row's totals
+    if ((l & 15) >= 12) s_part[(((l & 1) << 1) | ((l >> 1) & 1)) * 32 + (tx >> 6) * 4 + (l >> 4)] = v;
 #ifdef MAG_PERSIST_STAMPS
-        if (sub) sub[0] = __builtin_amdgcn_s_memrealtime(); // wave trees done, at the barrier
+    if (sub) sub[0] = __builtin_amdgcn_s_memrealtime(); // wave trees done, at the barrier
 #endif
-        __syncthreads();
-#ifdef MAG_PERSIST_STAMPS
-        if (sub) sub[1] = __builtin_amdgcn_s_memrealtime(); // every wave has arrived
-#endif
-        if (tx < 64) { // row c of wave 0 adds sum c's 32 partials: two per lane, then a tree over the row
-            const double2 pr = ((const double2 *)(s_part + (l >> 4) * 32))[l & 15];
-            double t = pr.x + pr.y;
-            t += dpp_move_f64<0x111>(t);
-            t += dpp_move_f64<0x112>(t);
-            t += dpp_move_f64<0x114>(t);
-            t += dpp_move_f64<0x118>(t);
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                acc[c] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(t), 16 * c + 15),
-                                          __builtin_amdgcn_readlane(__double2loint(t), 16 * c + 15));
-        }
-        return;
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[c] = wave_sum_dpp(acc[c]);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) s_red[c * NWV + (threadIdx.x >> 6)] = acc[c];
-    }
     __syncthreads();
-    if (threadIdx.x < 2) {
+#ifdef MAG_PERSIST_STAMPS
+    if (sub) sub[1] = __builtin_amdgcn_s_memrealtime(); // every wave has arrived
+#endif
+    if (tx < 64) { // row c of wave 0 adds sum c's 32 partials: two per lane, then a tree over the row
+        const double2 pr = ((const double2 *)(s_part + (l >> 4) * 32))[l & 15];
+        double t = pr.x + pr.y;
+        t += dpp_move_f64<0x111>(t);
+        t += dpp_move_f64<0x112>(t);
+        t += dpp_move_f64<0x114>(t);
+        t += dpp_move_f64<0x118>(t);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            double t = 0.0;
-#pragma unroll
-            for (int i = 0; i < NWV; ++i) t += s_red[c * NWV + i];
-            acc[c] = t;
-        }
+        for (int c = 0; c < 4; ++c)
+            acc[c] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(t), 16 * c + 15),
+                                      __builtin_amdgcn_readlane(__double2loint(t), 16 * c + 15));
     }
 }
 
 constexpr int kPersistRegs = 5; // ring words in registers per node: 10 entries, a closed fan of valence <= 9
-#ifndef MAG_PERSIST_BLOCK
-#define MAG_PERSIST_BLOCK 1 // (uncached walks only, i.e. the multi-GPU instantiation) measured in round 3, us per iteration at 1M
-#endif                      // triangles: no block 11.06-11.10, 5: 11.02, 4+3: 11.19-11.21, 5+2: 11.14; one block of 7 only compiles
-                            // without iterative-ilp: 11.41-11.71 (profiles/r03_persist_ab.txt).  Back to 1: with the
-                            // tile-relative slots below ROCm 7.2's iterative-ilp scheduler crashes on any block.
-#ifndef MAG_PERSIST_BLOCK2
-#define MAG_PERSIST_BLOCK2 MAG_PERSIST_BLOCK
-#endif
-// ring entries walked as straight-line blocks: 1 .. BLOCK - 1 and BLOCK .. BLOCK2 - 1 (cg_device.h, ring_walk_uniform)
-constexpr int kPersistBlock = MAG_PERSIST_BLOCK, kPersistBlock2 = MAG_PERSIST_BLOCK2;
-#ifndef MAG_PERSIST_WEIGHTS
-#define MAG_PERSIST_WEIGHTS 6
-#endif
-#ifndef MAG_PERSIST_SIBLINGS
-#define MAG_PERSIST_SIBLINGS 1
-#endif
-constexpr bool kPersistSiblings = MAG_PERSIST_SIBLINGS != 0; // sibling tiles of a workgroup read each other's LDS slots
-#ifndef MAG_PERSIST_DEFER_X
-#define MAG_PERSIST_DEFER_X 1
-#endif
-constexpr bool kPersistDeferX = MAG_PERSIST_DEFER_X != 0; // x += alpha p in the exchange's first wait (see the loop)
-#ifndef MAG_PERSIST_PRIO
-#define MAG_PERSIST_PRIO 3 // waves 4-7 (the arbitration losers of their SIMDs) take priority for their last two node slots: 9.55 -> 9.21 us
-#endif
-// triangle weights c0 / (2A) kept in registers per node (cg_device.h, ring_walk_cached); 0: recomputed every iteration.
-// The multi-GPU instantiation has no registers to spare for them (237 VGPRs without).
-constexpr int kPersistWeights = MAG_PERSIST_WEIGHTS;
-#ifndef MAG_PERSIST_EDGE_BLOCKS
-#define MAG_PERSIST_EDGE_BLOCKS 1
-#endif
-constexpr bool kPersistEdgeBlocks = MAG_PERSIST_EDGE_BLOCKS != 0; // edge blocks in registers instead of triangle weights
-#ifndef MAG_PERSIST_NB
-#define MAG_PERSIST_NB 6
-#endif
-#ifndef MAG_PERSIST_SADDR
-#define MAG_PERSIST_SADDR 1
-#endif
-#ifndef MAG_PERSIST_ENT_SCALAR
-#define MAG_PERSIST_ENT_SCALAR 1
-#endif
-#ifndef MAG_PERSIST_PACK_MG
-#define MAG_PERSIST_PACK_MG 1
-#endif
-#ifndef MAG_PERSIST_EB_PACK
-#define MAG_PERSIST_EB_PACK 1
-#endif
-constexpr int kPersistBlockEntries = MAG_PERSIST_NB; // block entries per node: a closed fan of valence 6 is exactly six blocks
+// triangle weights c0 / (2A) kept in registers per node by the triangle-walk instantiations, single- and multi-GPU alike
+// (cg_device.h, ring_walk_cached; round 3: profiles/r03_persist_ab.txt)
+constexpr int kPersistWeights = 6;
+constexpr int kPersistBlockEntries = 6; // block entries per node: a closed fan of valence 6 is exactly six blocks
 constexpr int kPersistNh = 2;   // halo entries per thread: a workgroup's tiles may carry 2 * THREADS halo nodes in all
-#ifndef MAG_PERSIST_ONE_TILE
-#define MAG_PERSIST_ONE_TILE 1
-#endif
-constexpr bool kPersistOneTile = MAG_PERSIST_ONE_TILE != 0;
-constexpr int persist_npt(int threads) { return threads == 768 ? 3 : 4; } // nodes per lane
 
 // Phase stamps (diagnostic build only: -DMAG_PERSIST_STAMPS, scripts/persist_phases.sh): lane 0 of every workgroup reads
 // the 100 MHz constant clock at the phase boundaries of iterations [kStampFrom, kStampTo) and adds the differences up
@@ -856,10 +715,6 @@ constexpr int persist_npt(int threads) { return threads == 768 ? 3 : 4; } // nod
 #else
 #define MAG_STAMP(k)
 #endif
-#ifndef MAG_PERSIST_STAMP_TID
-#define MAG_PERSIST_STAMP_TID 0 // the lane that stamps (0: wave 0, the older wave of its SIMD; 256: wave 4, its partner)
-#endif
-
 
 // the per-slot flag bytes of a lane's nodes in ONE register (the on-chip kernel has none to spare)
 template <int N>
@@ -904,10 +759,9 @@ __device__ inline void persist_single_workgroup(double *s_S, double (&Sx)[4], do
 template <int B, bool MG, int THREADS, int EBM, bool ONE = false, int NPTX = 0>
 __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
 {
-    constexpr int kPersistThreads = THREADS;
-    constexpr int NPT = NPTX ? NPTX : persist_npt(THREADS);
+    constexpr int NPT = NPTX ? NPTX : kPersistNpt;
     constexpr bool EB = EBM != 0, OV = EBM == 2;
-    constexpr bool OPQ = MAG_PERSIST_OPAQUE == 2 || (MAG_PERSIST_OPAQUE == 1 && OV); // see persist_block_sum
+    constexpr bool OPQ = OV; // the thread index behind an empty asm in the overflow instantiation: see persist_block_sum
     constexpr int SB = NPT * THREADS / B - 1; // bias of the workgroup-relative ring entries, in tile images (see the remap below)
     extern __shared__ __attribute__((aligned(16))) double2 smem[];
     const int tid = threadIdx.x;
@@ -920,7 +774,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
     const int tile_words = capx + cap + maxh + B;
     double2 *s_rec = smem + (size_t)(NPT * THREADS / B) * tile_words; // 2 * grid pieces of the partial records
     double *s_red = (double *)(s_rec + 2 * 256);
-    double *s_S = s_red + 4 * (kPersistThreads / 64);
+    double *s_S = s_red + 4 * (THREADS / 64);
     double *s_chunk = s_S + 4;
     double *s_part = s_chunk + 4 * 32; // persist_block_sum: the rows' partials of the four sums
     // overflow records (OV): two double2 each; several ranks: behind the interface words (s_opk, below)
@@ -982,7 +836,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
             flags.set(s, flags[s] | 16u | (mk & 7u));
             // bit 3 of the mask (k_mark_external): read through memory by a tile of ANOTHER workgroup, or by a sibling tile
             // that keeps its halo copies; a node only its siblings read through their LDS slots publishes nothing
-            if (kPersistSiblings && !(mk & 8u)) flags.set(s, flags[s] & ~4u);
+            if (!(mk & 8u)) flags.set(s, flags[s] & ~4u);
             acc[0] = fma(b.y, b.y, fma(b.x, b.x, acc[0]));
         } else {
             xy[lt] = make_double2(0.0, 0.0);
@@ -991,11 +845,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
         pim[lt] = make_double2(0.0, 0.0);
         xs[lt] = make_double2(0.0, 0.0);
         deg[s] = tm.deg;
-#if MAG_PERSIST_ENT_SCALAR
         ent[s] = __builtin_amdgcn_readfirstlane(tm.ent); // one tile per wave and slot
-#else
-        ent[s] = tm.ent;
-#endif
         ell_off[s] = tm.ell_off + lt;
 #pragma unroll
         for (int k = 0; k < kPersistRegs; ++k)
@@ -1015,7 +865,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
             // (several ranks: siblings are tiles of the same workgroup, hence of the same rank; rehearsed with two ranks
             // sharing one GPU at four tiles per workgroup, scripts/mg_share_ab.sh)
             // (OV: every entry, the pool's included, is rewritten here at start-up -- rows of any length)
-            const bool short_rows = kPersistSiblings && (OV || tm.ent <= 2 * kPersistRegs);
+            const bool short_rows = OV || tm.ent <= 2 * kPersistRegs;
             auto remap = [&](uint32_t e) -> uint32_t {
                 if (e == 0xffffu) return e;
                 const uint32_t lid = e & 0xfffu;
@@ -1097,7 +947,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
         }
     }
     // halo entries of the workgroup's tiles, in tile order, dealt out round-robin: thread t takes entries t, t + 512
-    if (kPersistSiblings) {
+    {
         // About half of the entries are owned by sibling tiles and need no halo copy.  The ones that do are
         // COMPACTED before they are dealt out (same order): ~250 of them fill the first round of four waves, where the
         // uncompacted list left a few live lanes in both rounds of all eight -- every one of those wave-rounds pays the LDS
@@ -1108,7 +958,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
         for (int e = 0; e < NH; ++e) {
             cg[e] = -1;
             cl[e] = 0;
-            int32_t rem = tid + kPersistThreads * e;
+            int32_t rem = tid + THREADS * e;
             for (int l = 0; l < P.tiles_per_wg && t_first + l < t_end; ++l) {
                 const TileMeta tm = P.meta[t_first + l];
                 if (rem < tm.nh) {
@@ -1127,7 +977,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
         }
         int32_t *s_cnt = (int32_t *)s_red; // live entries per (round, wave), then their exclusive prefix
         int2 *s_list = (int2 *)s_rec;      // 2 * THREADS entries at most: 8 KB, the record staging area (free until the exchange)
-        constexpr int NW8 = kPersistThreads / 64;
+        constexpr int NW8 = THREADS / 64;
         int32_t pos[NH];
 #pragma unroll
         for (int e = 0; e < NH; ++e) {
@@ -1149,7 +999,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
         for (int e = 0; e < NH; ++e) {
             hg[e] = -1;
             hloc[e] = 0;
-            const int32_t c = tid + kPersistThreads * e;
+            const int32_t c = tid + THREADS * e;
             if (c < total) {
                 const int2 ent2 = s_list[c];
                 hg[e] = ent2.x;
@@ -1168,35 +1018,9 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
             }
         }
         __syncthreads(); // s_red and s_rec go back to their day jobs
-    } else {
-        const int32_t t_first = (MG ? P.t0 : 0) + blockIdx.x * P.tiles_per_wg, t_end = MG ? P.t1 : P.T;
-#pragma unroll
-        for (int e = 0; e < NH; ++e) {
-            hg[e] = -1;
-            hloc[e] = 0;
-            int32_t rem = tid + kPersistThreads * e;
-            for (int l = 0; l < P.tiles_per_wg && t_first + l < t_end; ++l) {
-                const TileMeta tm = P.meta[t_first + l];
-                if (rem < tm.nh) {
-                    double2 *xy = smem + (size_t)l * tile_words;
-                    hg[e] = P.halo_g[tm.hoff + rem];
-                    hloc[e] = l * tile_words + rem;
-                    if (!EB) xy[B + rem] = P.halo_xy[tm.hoff + rem];
-                    const double2 hb = P.bP[hg[e]];
-                    xy[capx + cap + rem] = make_double2(-hb.x, -hb.y);   // halo r
-                    xy[capx + B + rem] = make_double2(0.0, 0.0);         // halo p: its slot in the p image
-                    if (MG) { // a node another rank owns: its q comes through the window (slot s encoded as -2 - s)
-                        const int32_t hs = P.halo_qslot[tm.hoff + rem];
-                        if (hs >= 0) hg[e] = -2 - hs;
-                    }
-                    break;
-                }
-                rem -= tm.nh;
-            }
-        }
     }
     if (blockIdx.x == 0 && tid == 0) acc[1] = 1.0; // "p.q" > 0: alpha finite, multiplies q = 0
-    persist_block_sum<THREADS, OPQ>(acc, s_red, s_part);
+    persist_block_sum<OPQ>(acc, s_part);
     int par = 0;
     unsigned epoch = tag0; // the tags of successive exchanges
     constexpr bool single_wg = ONE && !MG; // the whole mesh in this workgroup: no exchange at all
@@ -1209,17 +1033,13 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
     if (single_wg)
         persist_single_workgroup<NH>(s_S, Sx, hq);
     else if (MG ? !persist_exchange_mg<NH>(P, par, epoch, hg, hq, s_S, s_rec)
-                : !persist_exchange<NH, EB, OPQ>(P, par, epoch, hg, hq, s_S, s_rec, s_chunk, s_part, Sx))
+                : !persist_exchange<NH, OPQ>(P, par, epoch, hg, hq, s_S, s_rec, s_chunk, s_part, Sx))
         return;
 
     const double c0 = P.c0, nu = P.nu, h = P.h;
     // iteration-invariant part of the ring walks: the triangles' weights c0 / (2A), once per solve (the exchange above
     // ended with a workgroup barrier: the coordinates are staged)
-#ifndef MAG_PERSIST_WEIGHTS_MG
-#define MAG_PERSIST_WEIGHTS_MG 6
-#endif
-    constexpr int kW = MG ? MAG_PERSIST_WEIGHTS_MG : kPersistWeights;
-    constexpr int NCW = kW > 0 ? kW : 1;
+    constexpr int NCW = kPersistWeights;
     // Edge blocks (EB instantiation; cg_device.h, ring_blocks): every node's triangles folded into NB symmetric 2 x 2 blocks,
     // once per solve; a ring step is then one gather of p and six fp64 operations, and the coordinates are not read again.
     // Only for meshes whose rows are ALL one fan of at most NB entries, or NB + 1 with the last one closing onto the first
@@ -1227,7 +1047,6 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
     // launches the triangle-walk instantiation for any other mesh.
     constexpr int NB = kPersistBlockEntries;
     constexpr bool BLOCKS = EB;
-    constexpr bool CACHED = !BLOCKS && kW > 0;
     constexpr int NKB = BLOCKS ? 3 * NB : NCW;
     double wgt[NPT][NKB];
     const double kappa = uniform_f64(0.5 * (h - nu) * c0);
@@ -1245,7 +1064,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
         for (int s = 0; s < NPT; ++s)
 #pragma unroll
             for (int c = 0; c < NKB; ++c) asm volatile("" : "+v"(wgt[s][c]));
-    } else if (CACHED) {
+    } else {
 #pragma unroll
         for (int s = 0; s < NPT; ++s) {
 #pragma unroll
@@ -1283,12 +1102,12 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
     // for them, and a spilled register in the loop would be measured along with the phases
     unsigned long long *stamp_sum = (unsigned long long *)(s_chunk + 16); // [kStampPhases], then `last`, then the count, then scratch
     unsigned long long &stamp_last = stamp_sum[kStampPhases], &stamp_iters = stamp_sum[kStampPhases + 1];
-    if (tid == MAG_PERSIST_STAMP_TID)
+    if (tid == 0)
         for (int k = 0; k < kStampPhases + 2; ++k) stamp_sum[k] = 0;
 #endif
     for (;;) {
 #ifdef MAG_PERSIST_STAMPS
-        const bool stamping = tid == MAG_PERSIST_STAMP_TID && j >= kStampFrom && j < kStampTo;
+        const bool stamping = tid == 0 && j >= kStampFrom && j < kStampTo;
         if (stamping) {
             stamp_last = __builtin_amdgcn_s_memrealtime();
             ++stamp_iters;
@@ -1329,7 +1148,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
         // a few ulps per step.  beta = 0 (an exactly zero residual) cannot be divided by: then, and only then, here.
         const bool xnow = !(beta != 0.0) || !(fabs(beta) <= 1.79769313486231570e308);
         // ---- vector updates: r in registers, p and x in LDS, halo copies in LDS (their q from the publishers)
-        if (!kPersistDeferX || xnow) { // x += alpha p here, on the critical path, only when it cannot be rebuilt later
+        if (xnow) { // x += alpha p here, on the critical path, only when it cannot be rebuilt later
 #pragma unroll
             for (int s = 0; s < NPT; ++s) {
                 if (!(flags[s] & 8)) continue;
@@ -1386,9 +1205,9 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
 #pragma unroll
         for (int c = 0; c < 4; ++c) acc[c] = 0.0;
         // the ring words stay packed: unpacked once and for all (loop-invariant) they take a register per entry -- 24 in the
-        // edge-block instantiation, 40 in the others (where MAG_PERSIST_PACK_MG does the same for the multi-GPU instantiation:
-        // the registers go to the cached triangle weights)
-        if ((EB && MAG_PERSIST_EB_PACK) || (MG && !EB && MAG_PERSIST_PACK_MG)) {
+        // edge-block instantiations, 40 in the others (the multi-GPU triangle walk keeps them packed too: its registers go to
+        // the cached triangle weights)
+        if (EB || MG) {
 #pragma unroll
             for (int s = 0; s < NPT; ++s)
 #pragma unroll
@@ -1400,7 +1219,6 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
         }
 #pragma unroll
         for (int s = 0; s < NPT; ++s) {
-#if MAG_PERSIST_PRIO == 3
             // The two waves of a SIMD run the same program, and at equal priority the older one (waves 0-3) wins every
             // arbitration: the stamps showed it through its walks 2 us before its partner, which then ran alone, at
             // single-wave efficiency.  Waves 4-7 take priority 1 for their LAST TWO node slots (back to 0 before the sums):
@@ -1408,16 +1226,11 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
             // slot or pair, one or three slots, three levels, priority during the vector updates) were measured and are in
             // profiles/r03_persist_ab.txt (q0-q16): none better.
             if (((tid >> 8) & 1) && s >= NPT / 2) __builtin_amdgcn_s_setprio(1);
-#endif
-#ifndef MAG_PERSIST_OVF_PRIO
-#define MAG_PERSIST_OVF_PRIO 2 // frontal1m: 6.39 (off), 6.31 (1), 6.30 (2) us per iteration
-#endif
-#if MAG_PERSIST_OVF_PRIO
             // (OV) a wave that carries this slot's long rows -- the valence partition gives every wave one such slot --
-            // takes priority for it: it is the one the workgroup's sums will wait for
-            if (OV && ovmax[s] > 0) __builtin_amdgcn_s_setprio(MAG_PERSIST_OVF_PRIO);
+            // takes priority 2 for it: it is the one the workgroup's sums will wait for (frontal1m: 6.39 without, 6.31 at
+            // priority 1, 6.30 at 2 us per iteration)
+            if (OV && ovmax[s] > 0) __builtin_amdgcn_s_setprio(2);
             else if (OV && !(((tid >> 8) & 1) && s >= NPT / 2)) __builtin_amdgcn_s_setprio(0);
-#endif
             if (!(flags[s] & 8)) continue;
             const int lt = t_lt(s);
             const double2 *xy = t_xy(s), *pim = xy + capx;
@@ -1435,14 +1248,10 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
                     } else if (BLOCKS)
                         ring_walk_blocks<kPersistRegs, NB, 0x7fffu>(w[s], pim - SB * tile_words, pa, kappa, (flags[s] & 32u) != 0,
                                                                     *reinterpret_cast<const double(*)[3 * NB]>(&wgt[s][0]), fx, fy);
-                    else if (CACHED)
+                    else
                         ring_walk_cached<kPersistRegs, NCW, 0x7fffu>(w[s], P.ell16 + ell_off[s], B, nent, xy - SB * tile_words, pim - SB * tile_words,
                                                                      ca, pa, c0, nu, h, *reinterpret_cast<const double(*)[NCW]>(&wgt[s][0]),
                                                                      fx, fy, toff);
-                    else
-                        ring_walk_uniform<kPersistRegs, kPersistBlock, kPersistBlock2, 0x7fffu>(
-                            w[s], P.ell16 + ell_off[s], B, nent, xy - SB * tile_words, pim - SB * tile_words, ca, pa, c0, nu, h, fx, fy,
-                            toff);
                 }
             }
             if ((flags[s] & 1) || !(flags[s] & 16)) fx = 0.0;
@@ -1450,12 +1259,8 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
             const double2 qn = make_double2(fx, fy);
             if (QL) t_xy(s)[lt] = qn;
             else q[s] = qn;
-#if MAG_PERSIST_SADDR
             if ((flags[s] & 20) == 20) // (2 x 32 N bytes of granules: below 4 GB for every mesh the chip can hold)
                 put_granules_at(P.qg, 32u * ((uint32_t)(par ^ 1) * (uint32_t)P.N + (uint32_t)node_of(s)), epoch + 1, qn);
-#else
-            if ((flags[s] & 20) == 20) put_granules(P.qg + 4 * ((int64_t)(par ^ 1) * P.N + node_of(s)), epoch + 1, qn);
-#endif
             if (MG && (flags[s] & 64u)) {
                 const uint32_t opk = s_opk[s * THREADS + tid];
                 publish_q(P, par ^ 1, (int32_t)(opk & 0xffffffu), opk >> 24, epoch + 1, qn);
@@ -1465,15 +1270,13 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
             acc[2] = fma(r[s].y, fy, fma(r[s].x, fx, acc[2]));
             acc[3] = fma(fy, fy, fma(fx, fx, acc[3]));
         }
-#if MAG_PERSIST_PRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
         MAG_STAMP(2) // ring walks of this wave's nodes, q published
 #ifdef MAG_PERSIST_STAMPS
         unsigned long long *sub_ = stamp_sum + kStampPhases + 8;
-        persist_block_sum<THREADS, OPQ>(acc, s_red, s_part, stamping ? sub_ : nullptr);
+        persist_block_sum<OPQ>(acc, s_part, stamping ? sub_ : nullptr);
 #else
-        persist_block_sum<THREADS, OPQ>(acc, s_red, s_part);
+        persist_block_sum<OPQ>(acc, s_part);
 #endif
         par ^= 1;
         ++epoch;
@@ -1491,7 +1294,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
             sub_[2] = now_;
         }
 #endif
-        if (kPersistDeferX && !xnow) { // the deferred x += alpha p_{j-1}, in the shadow of the exchange's first wait
+        if (!xnow) { // the deferred x += alpha p_{j-1}, in the shadow of the exchange's first wait
             const double ab = uniform_f64(alpha / beta);
             auto x_slot = [&](int s) {
                 const int lt = t_lt(s);
@@ -1521,7 +1324,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
         if (single_wg)
             persist_single_workgroup<NH>(s_S, Sx, hq);
         else if (MG ? !persist_exchange_mg<NH>(P, par, epoch, hg, hq, s_S, s_rec, stamping ? xs_ : nullptr)
-                    : !persist_exchange<NH, EB, OPQ>(P, par, epoch, hg, hq, s_S, s_rec, s_chunk, s_part, Sx, stamping ? xs_ : nullptr))
+                    : !persist_exchange<NH, OPQ>(P, par, epoch, hg, hq, s_S, s_rec, s_chunk, s_part, Sx, stamping ? xs_ : nullptr))
             return;
         if (stamping) { // inside the exchange: wait before the first sweep / sweeps until complete / record reduction
             stamp_sum[4] += xs_[0] - stamp_last;
@@ -1536,12 +1339,12 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
         if (single_wg)
             persist_single_workgroup<NH>(s_S, Sx, hq);
         else if (MG ? !persist_exchange_mg<NH>(P, par, epoch, hg, hq, s_S, s_rec)
-                    : !persist_exchange<NH, EB, OPQ>(P, par, epoch, hg, hq, s_S, s_rec, s_chunk, s_part, Sx))
+                    : !persist_exchange<NH, OPQ>(P, par, epoch, hg, hq, s_S, s_rec, s_chunk, s_part, Sx))
             return;
 #endif
     }
 #ifdef MAG_PERSIST_STAMPS
-    if (tid == MAG_PERSIST_STAMP_TID && P.stamps) {
+    if (tid == 0 && P.stamps) {
         unsigned long long *o = P.stamps + (size_t)blockIdx.x * (kStampPhases + 1);
         for (int k = 0; k < kStampPhases; ++k) o[k] = stamp_sum[k];
         o[kStampPhases] = stamp_iters;
@@ -1570,7 +1373,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
 // against 5.52 us per iteration at 1M triangles in one session, while every other instantiation is FASTER under iterative-ilp
 // (one / two / three node slots 3.48 / 4.08 / 4.65 against 3.53 / 4.16 / 4.83; the overflow instantiation indifferent).  The
 // scheduler is a per-translation-unit option, hence the second object.  Builds without -DMAG_PERSIST_SPLIT_K4 (the stamped
-// build, scripts/build_variant.sh) keep the instantiation in this unit.
+// build) keep the instantiation in this unit.
 #ifndef MAG_PERSIST_SPLIT_K4
 #define MAG_PERSIST_SPLIT_K4 0
 #endif
@@ -1741,87 +1544,72 @@ void stream_exchange_launch(double *buf, int32_t g_all, int32_t n_iface, int32_t
     k_stream_exchange<<<blocks, 256, 0, s>>>(P);
 }
 
-int persist_threads()
+int persist_tiles_per_wg(int32_t B)
 {
-    const char *e = getenv("MAG_TUNE_PERSIST_THREADS");
-    const int t = e ? atoi(e) : kPersistThreadsDefault;
-#ifdef MAG_PERSIST_768 // the 768 x 3 shape is only instantiated on request: measured 4 % slower (see the top of this file)
-    return t == 768 ? 768 : 512;
-#else
-    (void)t;
-    return 512;
-#endif
-}
-
-int persist_tiles_per_wg(int32_t B, int threads)
-{
-    return B == 256 || B == 512 ? persist_npt(threads) * threads / B : 0; // whole tiles: 768 x 3 / 512 = 4
+    return B == 256 || B == 512 ? kPersistNpt * kPersistThreads / B : 0;
 }
 
 // dynamic LDS of a launch; every instantiation also carries 256 bytes of static LDS (the library's __syncthreads_and / _or),
 // which the host's fit test adds (kPersistStaticLds)
-size_t persist_lds_bytes(int32_t B, int32_t cap, int32_t maxh, int threads, int eb_mode, int32_t pool, bool mg)
+size_t persist_lds_bytes(int32_t B, int32_t cap, int32_t maxh, int eb_mode, int32_t pool, bool mg)
 {
-    const size_t tiles = (size_t)persist_tiles_per_wg(B, threads);
+    const size_t tiles = (size_t)persist_tiles_per_wg(B);
     const size_t capx = eb_mode == 2 ? (size_t)B : (size_t)cap; // with overflow blocks the first area holds q of the owned nodes only
     return tiles * (capx + (size_t)cap + (size_t)maxh + (size_t)B) * 16 + 2 * 256 * 16 +
-           (4 * ((size_t)threads / 64) + 4 + 4 * 32 + kPersistPartDoubles) * 8 + 16 + (eb_mode == 2 ? 32 * (size_t)pool : 0) +
-           (mg ? 4 * (size_t)persist_npt(threads) * (size_t)threads : 0); // several ranks: the interface words (s_opk)
+           (4 * (size_t)(kPersistThreads / 64) + 4 + 4 * 32 + kPersistPartDoubles) * 8 + 16 + (eb_mode == 2 ? 32 * (size_t)pool : 0) +
+           (mg ? 4 * (size_t)(kPersistNpt * kPersistThreads) : 0); // several ranks: the interface words (s_opk)
 }
 
-template <int THREADS>
-static void persist_launch_t(const PersistParams &P, int32_t B, int32_t grid, size_t lds, int eb_mode, hipStream_t s)
+static void persist_launch_general(const PersistParams &P, int32_t B, int32_t grid, size_t lds, int eb_mode, hipStream_t s)
 {
     if (P.nranks > 1) {
         if (eb_mode == 2) {
             if (B == 256)
-                k_cg_persist<256, true, THREADS, 2><<<grid, THREADS, lds, s>>>(P);
+                k_cg_persist<256, true, 512, 2><<<grid, 512, lds, s>>>(P);
             else
-                k_cg_persist<512, true, THREADS, 2><<<grid, THREADS, lds, s>>>(P);
+                k_cg_persist<512, true, 512, 2><<<grid, 512, lds, s>>>(P);
         } else if (eb_mode == 1) {
             if (B == 256)
-                k_cg_persist<256, true, THREADS, 1><<<grid, THREADS, lds, s>>>(P);
+                k_cg_persist<256, true, 512, 1><<<grid, 512, lds, s>>>(P);
             else
-                k_cg_persist<512, true, THREADS, 1><<<grid, THREADS, lds, s>>>(P);
+                k_cg_persist<512, true, 512, 1><<<grid, 512, lds, s>>>(P);
         } else if (B == 256)
-            k_cg_persist<256, true, THREADS, 0><<<grid, THREADS, lds, s>>>(P);
+            k_cg_persist<256, true, 512, 0><<<grid, 512, lds, s>>>(P);
         else
-            k_cg_persist<512, true, THREADS, 0><<<grid, THREADS, lds, s>>>(P);
+            k_cg_persist<512, true, 512, 0><<<grid, 512, lds, s>>>(P);
     } else if (eb_mode == 2) {
         if (B == 256)
-            k_cg_persist<256, false, THREADS, 2><<<grid, THREADS, lds, s>>>(P);
+            k_cg_persist<256, false, 512, 2><<<grid, 512, lds, s>>>(P);
         else
-            k_cg_persist<512, false, THREADS, 2><<<grid, THREADS, lds, s>>>(P);
+            k_cg_persist<512, false, 512, 2><<<grid, 512, lds, s>>>(P);
     } else if (eb_mode == 1) {
         if (B == 256)
-            k_cg_persist<256, false, THREADS, 1><<<grid, THREADS, lds, s>>>(P);
-        else if constexpr (MAG_PERSIST_SPLIT_K4 && THREADS == 512)
-            persist_launch_eb1_k4(P, grid, lds, s); // (persist_k4.o: the same instantiation under another scheduler)
+            k_cg_persist<256, false, 512, 1><<<grid, 512, lds, s>>>(P);
         else
-            k_cg_persist<512, false, THREADS, 1><<<grid, THREADS, lds, s>>>(P);
+#if MAG_PERSIST_SPLIT_K4
+            persist_launch_eb1_k4(P, grid, lds, s); // (persist_k4.o: the same instantiation under another scheduler)
+#else
+            k_cg_persist<512, false, 512, 1><<<grid, 512, lds, s>>>(P);
+#endif
     } else if (B == 256)
-        k_cg_persist<256, false, THREADS, 0><<<grid, THREADS, lds, s>>>(P);
+        k_cg_persist<256, false, 512, 0><<<grid, 512, lds, s>>>(P);
     else
-        k_cg_persist<512, false, THREADS, 0><<<grid, THREADS, lds, s>>>(P);
+        k_cg_persist<512, false, 512, 0><<<grid, 512, lds, s>>>(P);
 }
 
 // eb_mode: 1 every row of the mesh qualifies for the edge-block instantiation (ring16's flag), 2 with overflow records in LDS
 // (the host has checked the pool against the LDS), 0 the triangle walk
-void persist_launch(const PersistParams &P, int32_t B, int32_t grid, int threads, int eb_mode, hipStream_t s)
+void persist_launch(const PersistParams &P, int32_t B, int32_t grid, int eb_mode, hipStream_t s)
 {
-    if (!kPersistEdgeBlocks) eb_mode = 0;
-    const size_t lds = persist_lds_bytes(B, P.cap, P.maxh, threads, eb_mode, P.pool_cap, P.nranks > 1);
-#ifdef MAG_PERSIST_768
-    if (threads == 768) return persist_launch_t<768>(P, B, grid, lds, 0, s);
-#endif
+    const size_t lds = persist_lds_bytes(B, P.cap, P.maxh, eb_mode, P.pool_cap, P.nranks > 1);
     // The whole mesh in one workgroup: the instantiation without an exchange -- for the edge-block instantiations, whose tiles read
     // every sibling's node through LDS.  (The triangle walk keeps halo COPIES of sibling nodes in tiles whose rows do not fit its
     // registers, and advances them with q fetched from the granules: it goes through the exchange even alone on the grid.)
     // Fewer than four tiles per workgroup (meshes below 769 tiles, 393k nodes): the instantiation with as many node slots per
     // lane (NPTX) -- 0.45 us per iteration less than four slots of which some are dead, at two and three tiles as well.
-    if (P.nranks == 1 && B == 512 && eb_mode != 0 && (grid == 1 || (kPersistOneTile && P.tiles_per_wg < 4))) {
+    if (P.nranks == 1 && B == 512 && eb_mode != 0 && (grid == 1 || P.tiles_per_wg < 4)) {
         const bool one = grid == 1;
-        const int npt = kPersistOneTile && P.tiles_per_wg >= 1 && P.tiles_per_wg < 4 ? P.tiles_per_wg : 0;
+        const int npt = P.tiles_per_wg >= 1 && P.tiles_per_wg < 4 ? P.tiles_per_wg : 0;
 #define MAG_PERSIST_CASE(EBM_, ONE_, NPTX_)                                                                                       \
     if (eb_mode == EBM_ && one == ONE_ && npt == NPTX_) k_cg_persist<512, false, 512, EBM_, ONE_, NPTX_><<<grid, 512, lds, s>>>(P)
 #define MAG_PERSIST_CASES(EBM_, ONE_)                                                                                             \
@@ -1839,7 +1627,7 @@ void persist_launch(const PersistParams &P, int32_t B, int32_t grid, int threads
         return;
     }
     // ... and across ranks (a 1M-triangle mesh over four or eight GPUs is one tile per workgroup)
-    if (kPersistOneTile && P.nranks > 1 && B == 512 && eb_mode != 0 && P.tiles_per_wg >= 1 && P.tiles_per_wg < 4) {
+    if (P.nranks > 1 && B == 512 && eb_mode != 0 && P.tiles_per_wg >= 1 && P.tiles_per_wg < 4) {
         const int npt = P.tiles_per_wg;
 #define MAG_PERSIST_CASE(EBM_, NPTX_)                                                                                             \
     if (eb_mode == EBM_ && npt == NPTX_) k_cg_persist<512, true, 512, EBM_, false, NPTX_><<<grid, 512, lds, s>>>(P)
@@ -1852,7 +1640,7 @@ void persist_launch(const PersistParams &P, int32_t B, int32_t grid, int threads
 #undef MAG_PERSIST_CASE
         return;
     }
-    persist_launch_t<512>(P, B, grid, lds, eb_mode, s);
+    persist_launch_general(P, B, grid, lds, eb_mode, s);
 }
 
 int persist_block_entries() { return kPersistBlockEntries; }
