@@ -1,5 +1,7 @@
 """CPU: the committed BASELINE-size fixtures (tests/golden/fullsize_*.npz) belong to the meshes the generators build
-today -- same sizes, same checksums -- and carry what tests/test_fullsize_parity_gpu.py reads.  (The 16M-triangle mesh
+today -- same sizes, same checksums -- and carry what tests/test_fullsize_parity_gpu.py reads; likewise the round-off
+fixtures (tests/golden/roundoff_*.npz) of tests/test_roundoff_parity_gpu.py, whose figures
+tests/test_fullsize_checks_cpu.py checks against each other.  (The 16M-triangle mesh
 takes ~10 s to build here; its identity is checked on the GPU side only.)"""
 import os
 
@@ -34,3 +36,30 @@ def test_fixture_is_complete_and_matches_its_mesh(name):
     # prescribed displacements come back untouched in the oracle's sample too
     k = p.u_known[fx["dof_idx"]] == 1
     assert np.array_equal(fx["u_at"][k], p.u_in[fx["dof_idx"]][k])
+
+
+@pytest.mark.parametrize("name", ["hole1m", "frontal1m"])
+def test_roundoff_fixture_is_complete_and_matches_its_mesh(name):
+    fx = np.load(os.path.join(GOLDEN, f"roundoff_{name}.npz"), allow_pickle=False)
+    full = np.load(os.path.join(GOLDEN, f"fullsize_{name}.npz"), allow_pickle=False)
+    keys = ["workload", "num_nodes", "num_elements", "n_free", "nnz_ff", "b_norm", "target_cost", "dof_idx", "elem_idx",
+            "xy_checksum", "conn_checksum", "direct_solver", "direct_rel_residual", "direct_last_step"]
+    for who in ("direct", "rnorm", "rnorm_sq"):
+        keys += [f"{who}_{k}" for k in ("u_norm", "u_absmax", "f_known_norm", "stress_norm", "u_at", "f_at", "stress_at")]
+    for rule in ("rnorm", "rnorm_sq"):
+        keys += [f"{rule}_{k}" for k in ("solver", "iterations", "final_cost", "true_rel_residual", "true_abs_residual",
+                                         "rel_l2_to_direct")]
+    assert sorted(set(keys) - set(fx.files)) == []
+    assert str(fx["workload"]) == name and float(fx["target_cost"]) == 1e-4
+    # the same mesh and the same sampled positions as the full-size fixture (whose checksums the test above rebuilds)
+    for key in ("num_nodes", "num_elements", "xy_checksum", "conn_checksum", "dof_idx", "elem_idx"):
+        assert np.array_equal(fx[key], full[key]), key
+    for who in ("direct", "rnorm", "rnorm_sq"):
+        for key in ("u_at", "f_at", "stress_at"):
+            assert fx[f"{who}_{key}"].shape == (4096,) and np.all(np.isfinite(fx[f"{who}_{key}"]))
+    p = meshgen.baseline_problem(name)
+    assert int(fx["n_free"]) == int((p.u_known == 0).sum())
+    k = p.u_known[fx["dof_idx"]] == 1
+    for who in ("direct", "rnorm", "rnorm_sq"):
+        assert np.array_equal(fx[f"{who}_u_at"][k], p.u_in[fx["dof_idx"]][k])
+        assert np.array_equal(fx[f"{who}_f_at"][~k], p.f_in[fx["dof_idx"]][~k])

@@ -55,6 +55,7 @@ def test_sampled_oracle_solution_at_baseline_size(built, name, variant):
     slack = 0 if "1 thread" in str(fx["solver"]) else max(2, int(fx["iterations"]) // 1000)
     if name == "frontal1m":  # the kernels add a node's triangles in another order than the oracle's rows (edge blocks; ring
         slack = max(2, int(fx["iterations"]) // 100)  # order): the count wobbles at the threshold (the residual is not monotone)
+        # (profiles/roundoff_parity.json: 61 here, 90 at most over this workload's stop rules; twice that would be wider, so this stays)
     assert abs(int(out["iterations"]) - int(fx["iterations"])) <= slack, (out["iterations"], int(fx["iterations"]))
     iu, ie = fx["dof_idx"], fx["elem_idx"]
     assert rel(out["u"][iu], fx["u_at"]) <= TOL_U
