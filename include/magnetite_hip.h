@@ -38,7 +38,9 @@ extern "C" {
 #endif
 
 #define MAG_ABI_VERSION 4 /* 3: mag_stats gained exchange_timeout, best_param_mismatch; 4: edge_blocks (and, in the
-                             reserved word behind it, tiles_per_workgroup) */
+                             reserved word behind it, tiles_per_workgroup).  Load cases (mag_set_load_cases ...
+                             mag_get_cases_info) came later as new entry points only: no struct changed, the version
+                             stays 4, and a caller detects the feature by the presence of those symbols (dlsym) */
 
 /* solver.rs:17-19 */
 #define MAG_DOF 2
@@ -223,6 +225,43 @@ int mag_download(mag_ctx *ctx, mag_result *result);
 int mag_get_stats(const mag_ctx *ctx, mag_stats *stats);
 /* cost of CG iterations 1..n (n <= options.history_len, <= iterations) */
 int mag_get_history(mag_ctx *ctx, double *history, int64_t n);
+
+/* ---- load cases: several sets of prescribed values on ONE uploaded mesh ---- */
+/* What a 2-D FEA user does with a part: solve it under several load sets.  Mesh, material and the u_known mask stay those
+ * of mag_upload; only the VALUES change -- u_in where u_known == 1, f_in where u_known == 0.
+ *   shared, done once per mag_run_cases: Hilbert order, tile tables, CSR pattern, K, the on-chip kernel's edge blocks;
+ *   per case: right-hand side, CG, scatter-back, reactions, stress (solver.rs:365-533 per case).
+ * When the mesh runs the on-chip CG (cg_variant 2, one GPU) and at least two cases fit the chip, the cases' CG solves run
+ * side by side in one launch: G = the workgroups one case needs, floor(CUs / G) cases per launch, each case with its own
+ * alpha, beta, stop test and iteration count.  Otherwise (a mesh of more than CUs / 2 workgroups, the fp32 leg, the CSR
+ * operator, a preconditioner, cg_variant 0 / 1, a context backing off after an on-chip time-out) the cases' CG solves run one
+ * after another through the single-case phases; the shared work is still done once.  Either way every case's u, f, stress
+ * and CG statistics are BIT FOR BIT those of mag_upload + mag_run with that case's values.
+ *
+ * mag_set_load_cases: after mag_upload (whose own u_in / f_in mag_run_cases does not use).  u_in, f_in: [num_cases][2N],
+ *   caller's DOF numbering, read as in mag_problem; copied into context-owned device buffers.  memory: enum mag_memory.
+ *   A new mag_upload drops the cases.
+ * mag_run_cases: MAG_OK when every case ended as mag_run's MAG_OK (the iteration cap included); otherwise the status of the
+ *   first failing case (MAG_ERR_NOT_CONVERGED: a non-finite residual) -- the other cases are complete and can be downloaded.
+ *   A case whose group of workgroups timed out at its barrier, or that stopped at the iteration cap with an earlier best
+ *   iterate, is redone ONCE on its own through the single-case path (its time-out fall-back, its best_param repeat).
+ *   options.history_len and options.verbose apply to case 0 only (mag_get_history then returns case 0's costs).
+ *   mag_download / mag_get_stats of the single-case path hold nothing afterwards (mag_get_stats: case 0's statistics).
+ * mag_get_case_stats: iterations, final_cost, rhs_norm, converged, breakdown, termination, best_iteration, cg_kernel,
+ *   edge_blocks, tiles_per_workgroup, n_free, persist_timeout are the case's own; ms_cg is the time of the launch the case
+ *   ran in (or of its own solve); ms_order, ms_csr_symbolic, ms_assemble (the shared work) and ms_bc, ms_post, ms_total (all
+ *   cases together) are the same in every case.
+ * mag_get_cases_info: info[0] cases, info[1] cases per on-chip launch (0: the cases ran one after another through the
+ *   single-case CG phases), info[2] on-chip launches, info[3] cases redone on their own.
+ * Errors, before any HIP call: MAG_ERR_BAD_ARGS for num_cases < 1, a null pointer, a case index out of range, a context
+ *   whose communicator has more than one rank (load cases across GPUs are not supported); MAG_ERR_STATE for
+ *   mag_set_load_cases before mag_upload, mag_run_cases before mag_set_load_cases, mag_download_case / mag_get_case_stats /
+ *   mag_get_cases_info before a completed mag_run_cases. */
+int mag_set_load_cases(mag_ctx *ctx, int32_t num_cases, const double *u_in, const double *f_in, int32_t memory);
+int mag_run_cases(mag_ctx *ctx);
+int mag_download_case(mag_ctx *ctx, int32_t case_index, mag_result *result);
+int mag_get_case_stats(const mag_ctx *ctx, int32_t case_index, mag_stats *stats);
+int mag_get_cases_info(const mag_ctx *ctx, int32_t info[4]);
 
 /* ---- pieces of the path, exposed for parity tests -------------------- */
 /* solver.rs:187-193 compute_element_area (pub; the mesher imports it, mesher.rs:9,523). Host-side. */

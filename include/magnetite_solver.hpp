@@ -67,37 +67,66 @@ inline double compute_element_area(const Element &element, const std::vector<Nod
     return mag_compute_element_area(xy, tri);
 }
 
-// solver.rs:543-586.  `options` == nullptr keeps the reference's constants (absolute cost 1e-4, 1e7 iterations).
-inline Result run(std::vector<Node> &nodes, std::vector<Element> &elements, const ModelMetadata &model_metadata,
-                  const mag_options *options = nullptr, mag_stats *stats_out = nullptr)
+namespace detail {
+
+inline Result solver_error(std::string m) { return Result(MagnetiteError{MagnetiteError::Solver, std::move(m)}); }
+
+// Vec<Node> -> the C ABI's arrays (what the Rust shim does before the extern "C" call); with `mask_of`, the mask of another
+// node list this one must agree with (load cases: one mask for all)
+inline Result flatten_nodes(const std::vector<Node> &nodes, std::vector<double> &xy, std::vector<std::uint8_t> &u_known,
+                            double *u_in, double *f_in, const std::vector<std::uint8_t> *mask_of = nullptr)
 {
-    auto err = [](std::string m) { return Result(MagnetiteError{MagnetiteError::Solver, std::move(m)}); };
-    const std::size_t N = nodes.size(), E = elements.size();
-    std::vector<double> xy(2 * N), u_in(2 * N, 0.0), f_in(2 * N, 0.0), u(2 * N), f(2 * N), stress(E);
-    std::vector<std::uint8_t> u_known(2 * N, 0);
-    std::vector<std::int32_t> conn(3 * E);
+    const std::size_t N = nodes.size();
+    xy.assign(2 * N, 0.0);
+    u_known.assign(2 * N, 0);
     for (std::size_t i = 0; i < N; ++i) {
         xy[2 * i] = nodes[i].vertex.x;
         xy[2 * i + 1] = nodes[i].vertex.y;
         const std::optional<double> *uu[2] = {&nodes[i].ux, &nodes[i].uy}, *ff[2] = {&nodes[i].fx, &nodes[i].fy};
         for (int a = 0; a < 2; ++a) {
+            u_in[2 * i + a] = f_in[2 * i + a] = 0.0;
             // exactly one of (u, f) per DOF; the reference panics otherwise (solver.rs:431,453,472)
             if (uu[a]->has_value() == ff[a]->has_value())
-                return err("node " + std::to_string(i) + ": exactly one of displacement/force must be prescribed per axis");
+                return solver_error("node " + std::to_string(i) + ": exactly one of displacement/force must be prescribed per axis");
             if (uu[a]->has_value()) {
                 u_known[2 * i + a] = 1;
                 u_in[2 * i + a] = **uu[a];
             } else {
                 f_in[2 * i + a] = **ff[a];
             }
+            if (mask_of && (*mask_of)[2 * i + a] != u_known[2 * i + a])
+                return solver_error("node " + std::to_string(i) + ": load cases must prescribe the same quantity per axis");
         }
     }
+    return std::nullopt;
+}
+
+inline Result flatten_elements(const std::vector<Element> &elements, std::size_t N, std::vector<std::int32_t> &conn)
+{
+    const std::size_t E = elements.size();
+    conn.assign(3 * E, 0);
     for (std::size_t e = 0; e < E; ++e)
         for (int c = 0; c < 3; ++c) {
             if (elements[e].nodes[c] >= N || elements[e].nodes[c] > 0x7fffffffu)
-                return err("element " + std::to_string(e) + " references a node outside the mesh");
+                return solver_error("element " + std::to_string(e) + " references a node outside the mesh");
             conn[3 * e + c] = (std::int32_t)elements[e].nodes[c];
         }
+    return std::nullopt;
+}
+
+}  // namespace detail
+
+// solver.rs:543-586.  `options` == nullptr keeps the reference's constants (absolute cost 1e-4, 1e7 iterations).
+inline Result run(std::vector<Node> &nodes, std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                  const mag_options *options = nullptr, mag_stats *stats_out = nullptr)
+{
+    auto err = detail::solver_error;
+    const std::size_t N = nodes.size(), E = elements.size();
+    std::vector<double> xy, u_in(2 * N, 0.0), f_in(2 * N, 0.0), u(2 * N), f(2 * N), stress(E);
+    std::vector<std::uint8_t> u_known;
+    std::vector<std::int32_t> conn;
+    if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
+    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
     mag_ctx *ctx = mag_create(options);
     if (!ctx) return err("mag_create failed");
     mag_problem p{};
@@ -132,6 +161,77 @@ inline Result run(std::vector<Node> &nodes, std::vector<Element> &elements, cons
         nodes[i].fy = f[2 * i + 1];
     }
     for (std::size_t e = 0; e < E; ++e) elements[e].stress = stress[e];  // solver.rs:532-533
+    return std::nullopt;
+}
+
+// Load cases (mag_set_load_cases / mag_run_cases): the same part under several sets of prescribed values.  cases[c] is the
+// node list of case c -- the vertices of cases[0] and the same choice of prescribed quantity per axis, other values.  Order,
+// symbolic work and K are done once, the CG solves run side by side on the chip where they fit; every case gets bit for bit
+// what run() gives for it.  Afterwards every cases[c][i].ux/uy/fx/fy holds a value and stress[c][e] is element e's stress in
+// case c (`elements` is shared by the cases and stays untouched).  info_out: mag_get_cases_info's four words.
+inline Result run_cases(std::vector<std::vector<Node>> &cases, const std::vector<Element> &elements,
+                        const ModelMetadata &model_metadata, std::vector<std::vector<double>> &stress,
+                        const mag_options *options = nullptr, std::vector<mag_stats> *stats_out = nullptr,
+                        std::int32_t *info_out = nullptr)
+{
+    auto err = detail::solver_error;
+    if (cases.empty()) return err("no load case");
+    const std::size_t L = cases.size(), N = cases[0].size(), E = elements.size();
+    std::vector<double> xy, xy_c, u_in(L * 2 * N), f_in(L * 2 * N), u(2 * N), f(2 * N);
+    std::vector<std::uint8_t> u_known, mask_c;
+    std::vector<std::int32_t> conn;
+    if (Result e = detail::flatten_nodes(cases[0], xy, u_known, u_in.data(), f_in.data())) return e;
+    for (std::size_t c = 1; c < L; ++c) {
+        if (cases[c].size() != N) return err("load case " + std::to_string(c) + " has another number of nodes");
+        if (Result e = detail::flatten_nodes(cases[c], xy_c, mask_c, u_in.data() + c * 2 * N, f_in.data() + c * 2 * N, &u_known))
+            return e;
+        if (xy_c != xy) return err("load case " + std::to_string(c) + " has other vertices");
+    }
+    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
+    mag_ctx *ctx = mag_create(options);
+    if (!ctx) return err("mag_create failed");
+    auto fail = [&]() {
+        Result e = err(mag_last_error(ctx));
+        mag_destroy(ctx);
+        return e;
+    };
+    mag_problem p{};
+    p.num_nodes = (std::int64_t)N;
+    p.num_elements = (std::int64_t)E;
+    p.xy = xy.data();
+    p.conn = conn.data();
+    p.u_known = u_known.data();
+    p.u_in = u_in.data();
+    p.f_in = f_in.data();
+    p.youngs_modulus = model_metadata.youngs_modulus;
+    p.poisson_ratio = model_metadata.poisson_ratio;
+    p.part_thickness = model_metadata.part_thickness;
+    p.memory = MAG_MEM_HOST;
+    if (mag_upload(ctx, &p) != MAG_OK) return fail();
+    if (mag_set_load_cases(ctx, (std::int32_t)L, u_in.data(), f_in.data(), MAG_MEM_HOST) != MAG_OK) return fail();
+    const int rc = mag_run_cases(ctx);
+    if (rc != MAG_OK && rc != MAG_ERR_NOT_CONVERGED) return fail();
+    const std::string run_message = mag_last_error(ctx);
+    if (stats_out) stats_out->assign(L, mag_stats{});
+    if (info_out) mag_get_cases_info(ctx, info_out);
+    stress.assign(L, std::vector<double>(E));
+    for (std::size_t c = 0; c < L; ++c) {
+        mag_result r{};
+        r.u_out = u.data();
+        r.f_out = f.data();
+        r.stress_out = stress[c].data();
+        r.memory = MAG_MEM_HOST;
+        if (mag_download_case(ctx, (std::int32_t)c, &r) != MAG_OK) return fail();
+        if (stats_out) mag_get_case_stats(ctx, (std::int32_t)c, &(*stats_out)[c]);
+        for (std::size_t i = 0; i < N; ++i) {
+            cases[c][i].ux = u[2 * i];
+            cases[c][i].uy = u[2 * i + 1];
+            cases[c][i].fx = f[2 * i];
+            cases[c][i].fy = f[2 * i + 1];
+        }
+    }
+    mag_destroy(ctx);
+    if (rc != MAG_OK) return err(run_message); // a case broke down: the others hold their results
     return std::nullopt;
 }
 

@@ -198,6 +198,15 @@ struct mag_ctx {
     DevBuf u, f, stress;
     mag_stats stats = {};
 
+    // load cases (mag_set_load_cases / mag_run_cases): num_cases sets of prescribed values on the uploaded mesh, case after
+    // case in every buffer -- inputs, right-hand sides (Hilbert numbering), solutions, results; the on-chip kernel's granules,
+    // records, timeout words and states for the cases of ONE launch
+    int32_t num_cases = 0;
+    bool have_cases = false, have_cases_run = false;
+    DevBuf c_uin, c_fin, c_keep, c_bP, c_x, c_u, c_f, c_stress, c_qx, c_part, c_sync, c_state;
+    std::vector<mag_stats> case_stats;
+    int32_t cases_info[4] = {};
+
     magc::Comm comm;
 };
 
@@ -1420,6 +1429,71 @@ int choose_edge_blocks(mag_ctx *ctx, bool mg, magk::PersistParams &P, int &mode)
     return MAG_OK;
 }
 
+// what every launch of the on-chip kernel is told about the mesh, the stop rule and the context's single-case buffers
+void persist_common_params(mag_ctx *ctx, bool mg, magk::PersistParams &P)
+{
+    P.N = ctx->N;
+    P.T = ctx->T;
+    P.tiles_per_wg = ctx->persist_k;
+    P.cap = ctx->cap;
+    P.maxh = ctx->persist_maxh;
+    P.hist_len = ctx->opt.history_len;
+    P.stop_mode = ctx->opt.stop_mode;
+    // ~0.3 s of polling (each poll is a memory round trip) before a workgroup concludes that the grid is not resident;
+    // several ranks start apart: a longer budget
+    P.spin_limit = (uint32_t)env_int("MAG_TUNE_PERSIST_SPIN", mg ? 1 << 21 : 1 << 19);
+    P.max_iter = (long long)ctx->opt.max_iter;
+    P.tol = ctx->opt.tol;
+    set_material(ctx, P);
+    P.xyP = ctx->xyP.as<double2>();
+    P.maskP = ctx->maskP.as<uint8_t>();
+    P.meta = ctx->tmeta.as<magk::TileMeta>();
+    P.ell16 = ctx->ell.as<uint32_t>();
+    P.halo_g = ctx->halo_g.as<int32_t>();
+    P.halo_xy = ctx->halo_xy.as<double2>();
+    P.bP = ctx->bP.as<double2>();
+    P.x = ctx->x.as<double2>();
+    P.qg = ctx->qx.as<unsigned long long>();
+    P.recg = ctx->wg_part.as<unsigned long long>();
+    P.sync = ctx->psync.as<uint32_t>();
+    P.st = ctx->fstate.as<magk::FusedState>();
+    P.hist = ctx->hist.as<double>();
+}
+
+// the instantiation for this mesh (mag_stats.edge_blocks), the nodes read through memory, the nodes' blocks: once per solve --
+// or once for all load cases: none of it depends on the prescribed values
+int persist_prepare_blocks(mag_ctx *ctx, bool mg, magk::PersistParams &P, int &eb_mode)
+{
+    hipStream_t s = ctx->stream;
+    eb_mode = 0;
+    if (int rc = choose_edge_blocks(ctx, mg, P, eb_mode)) return rc;
+    ctx->edge_blocks = eb_mode;
+    // which nodes are read through memory at all by this rank's tiles, with persist_k tiles per workgroup (the others publish
+    // nothing on this GPU; what other ranks read goes through the inboxes)
+    magk::mark_external(ctx->halo_g.as<int32_t>(), ctx->tmeta.as<magk::TileMeta>(), ctx->t0, ctx->t1, ctx->B, ctx->persist_k,
+                        ctx->maskP.as<uint8_t>(), eb_mode == 2, s);
+    if (eb_mode) { // the nodes' blocks, once per solve (18 doubles per node of the padded order, value-major)
+        const int64_t npad = (int64_t)ctx->T * ctx->B;
+        HIPCHK(ctx->kblocks.reserve(8 * (size_t)(3 * magk::persist_block_entries()) * (size_t)npad));
+        P.kblocks = ctx->kblocks.as<double>();
+        P.kb_stride = npad;
+        magk::edge_blocks_build(P, ctx->B, ctx->kblocks.as<double>(), eb_mode, s);
+    }
+    return MAG_OK;
+}
+
+// a workgroup gave up waiting at the grid barrier (not every workgroup resident: the GPU is shared with another process, or
+// fewer CUs are usable than reported): use the streaming kernels from now on
+void persist_back_off(mag_ctx *ctx)
+{
+    ctx->persist_failed = true;
+    ctx->persist_timed_out = true;
+    ctx->persist_backoff = ctx->persist_backoff ? std::min(2 * ctx->persist_backoff, 1024) : 8;
+    ctx->persist_retry_in = ctx->persist_backoff;
+    ctx->persist = false;
+    if (ctx->opt.verbose) printf("info: on-chip CG not co-resident, falling back to the streaming iteration\n");
+}
+
 int cg_phase_persist(mag_ctx *ctx)
 {
     using magk::FusedState;
@@ -1467,32 +1541,7 @@ int cg_phase_persist(mag_ctx *ctx)
         const int32_t grid_max = (most_rank_tiles(ctx->T, R) + ctx->persist_k - 1) / ctx->persist_k;
         P.comm_wg = (ctx->inbox_ready && grid_max + 1 <= cus) ? 1 : 0;
     }
-    P.N = ctx->N;
-    P.T = ctx->T;
-    P.tiles_per_wg = ctx->persist_k;
-    P.cap = ctx->cap;
-    P.maxh = ctx->persist_maxh;
-    P.hist_len = ctx->opt.history_len;
-    P.stop_mode = ctx->opt.stop_mode;
-    // ~0.3 s of polling (each poll is a memory round trip) before a workgroup concludes that the grid is not resident;
-    // several ranks start apart: a longer budget
-    P.spin_limit = (uint32_t)env_int("MAG_TUNE_PERSIST_SPIN", mg ? 1 << 21 : 1 << 19);
-    P.max_iter = (long long)ctx->opt.max_iter;
-    P.tol = ctx->opt.tol;
-    set_material(ctx, P);
-    P.xyP = ctx->xyP.as<double2>();
-    P.maskP = ctx->maskP.as<uint8_t>();
-    P.meta = ctx->tmeta.as<magk::TileMeta>();
-    P.ell16 = ctx->ell.as<uint32_t>();
-    P.halo_g = ctx->halo_g.as<int32_t>();
-    P.halo_xy = ctx->halo_xy.as<double2>();
-    P.bP = ctx->bP.as<double2>();
-    P.x = ctx->x.as<double2>();
-    P.qg = ctx->qx.as<unsigned long long>();
-    P.recg = ctx->wg_part.as<unsigned long long>();
-    P.sync = ctx->psync.as<uint32_t>();
-    P.st = ctx->fstate.as<FusedState>();
-    P.hist = ctx->hist.as<double>();
+    persist_common_params(ctx, mg, P);
     if (mg) {
         // every rank's kernel must be running before anybody's spin budget runs out: line the streams up first
         // Nothing of an earlier use may look current: a window handed over from another context, or slots of the solve
@@ -1516,19 +1565,7 @@ int cg_phase_persist(mag_ctx *ctx)
         P.stamps = ctx->pstamps.as<unsigned long long>();
     }
     int eb_mode = 0;
-    if (int rc = choose_edge_blocks(ctx, mg, P, eb_mode)) return rc;
-    ctx->edge_blocks = eb_mode;
-    // which nodes are read through memory at all by this rank's tiles, with persist_k tiles per workgroup (the others publish
-    // nothing on this GPU; what other ranks read goes through the inboxes)
-    magk::mark_external(ctx->halo_g.as<int32_t>(), ctx->tmeta.as<magk::TileMeta>(), ctx->t0, ctx->t1, ctx->B, ctx->persist_k,
-                        ctx->maskP.as<uint8_t>(), eb_mode == 2, s);
-    if (eb_mode) { // the nodes' blocks, once per solve (18 doubles per node of the padded order, value-major)
-        const int64_t npad = (int64_t)ctx->T * ctx->B;
-        HIPCHK(ctx->kblocks.reserve(8 * (size_t)(3 * magk::persist_block_entries()) * (size_t)npad));
-        P.kblocks = ctx->kblocks.as<double>();
-        P.kb_stride = npad;
-        magk::edge_blocks_build(P, ctx->B, ctx->kblocks.as<double>(), eb_mode, s);
-    }
+    if (int rc = persist_prepare_blocks(ctx, mg, P, eb_mode)) return rc;
     magk::persist_launch(P, ctx->B, grid + P.comm_wg, eb_mode, s);
     if (stamps) {
         // (several ranks: one file per rank, "<name>.<rank>"; with an exchange workgroup its row follows the compute workgroups')
@@ -1564,14 +1601,7 @@ int cg_phase_persist(mag_ctx *ctx)
         }
     }
     if (failed) {
-        // a workgroup gave up waiting at the grid barrier (not every workgroup resident: the GPU is shared with
-        // another process, or fewer CUs are usable than reported): use the streaming kernels from now on
-        ctx->persist_failed = true;
-        ctx->persist_timed_out = true;
-        ctx->persist_backoff = ctx->persist_backoff ? std::min(2 * ctx->persist_backoff, 1024) : 8;
-        ctx->persist_retry_in = ctx->persist_backoff;
-        ctx->persist = false;
-        if (ctx->opt.verbose) printf("info: on-chip CG not co-resident, falling back to the streaming iteration\n");
+        persist_back_off(ctx);
         ctx->cg_kernel = 1;
         return cg_phase_fused(ctx);
     }
@@ -1960,103 +1990,40 @@ void mag_compute_stress_strain_matrix(double poisson_ratio, double youngs_modulu
     for (int i = 0; i < 9; ++i) D[i] = m[i] * s;
 }
 
-int mag_upload(mag_ctx *ctx, const mag_problem *p)
+namespace {
+
+// solver.rs:365-404,427-432: the right-hand side of one set of prescribed values, Hilbert numbering.  from_order: the ordering
+// phase has written b = 0.0 + f for every node from THIS f_in (apply_order); a load case's f was not there then and gets the
+// same values from rhs_untouched.  Then only the rows with a prescribed column need K, and the pattern kernel has flagged them
+// (bc_touch_ready); otherwise the full pass
+int rhs_phase(mag_ctx *ctx, const double *u_in, const double *f_in, double *bP, bool from_order)
 {
-    if (int rc = enter(ctx)) return rc;
-    if (!p || !p->xy || !p->conn || !p->u_known || !p->u_in || !p->f_in)
-        return fail(ctx, MAG_ERR_BAD_ARGS, "null problem pointer");
-    const int64_t N = p->num_nodes, E = p->num_elements;
-    if (N < 1 || E < 1)
-        return fail(ctx, MAG_ERR_BAD_ARGS, "empty mesh (nodes=%lld elements=%lld)", (long long)N, (long long)E);
-    if (N >= (int64_t(1) << 30) || 9 * E >= (int64_t(1) << 31))
-        return fail(ctx, MAG_ERR_TOO_LARGE, "mesh too large for int32 indexing (nodes=%lld elements=%lld)", (long long)N,
-                    (long long)E);
-    if (!(p->poisson_ratio * p->poisson_ratio != 1.0))
-        return fail(ctx, MAG_ERR_BAD_ARGS, "poisson_ratio^2 == 1");
-    const hipMemcpyKind kind = p->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     hipStream_t s = ctx->stream;
-    HIPCHK(ctx->xy.reserve(16 * (size_t)N));
-    HIPCHK(ctx->conn.reserve(12 * (size_t)E));
-    HIPCHK(ctx->uknown.reserve(2 * (size_t)N));
-    HIPCHK(ctx->uin.reserve(16 * (size_t)N));
-    HIPCHK(ctx->fin.reserve(16 * (size_t)N));
-    HIPCHK(hipMemcpyAsync(ctx->xy.p, p->xy, 16 * (size_t)N, kind, s));
-    HIPCHK(hipMemcpyAsync(ctx->conn.p, p->conn, 12 * (size_t)E, kind, s));
-    HIPCHK(hipMemcpyAsync(ctx->uknown.p, p->u_known, 2 * (size_t)N, kind, s));
-    HIPCHK(hipMemcpyAsync(ctx->uin.p, p->u_in, 16 * (size_t)N, kind, s));
-    HIPCHK(hipMemcpyAsync(ctx->fin.p, p->f_in, 16 * (size_t)N, kind, s));
-    HIPCHK(hipStreamSynchronize(s));
-    ctx->N = N;
-    ctx->E = E;
-    ctx->youngs = p->youngs_modulus;
-    ctx->nu = p->poisson_ratio;
-    ctx->thick = p->part_thickness;
-    ctx->have_problem = true;
-    ctx->have_order = ctx->have_csr = ctx->have_run = false;
+    const int64_t N = ctx->N;
+    if (ctx->opt.assemble_csr != 0 || ctx->opt.cg_operator == MAG_OP_CSR) {
+        HIPCHK(ctx->bc_touch.reserve((size_t)N + 16));
+        if (ctx->bc_touch_ready) {
+            if (!from_order) magk::rhs_untouched(ctx->uknown.as<uint8_t>(), f_in, ctx->perm.as<uint32_t>(), N, bP, s);
+            magk::rhs_touched(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->kval.as<double>(),
+                              ctx->uknown.as<uint8_t>(), u_in, f_in, ctx->perm.as<uint32_t>(), ctx->bc_touch.as<uint8_t>(), N, bP, s);
+        } else {
+            magk::rhs_from_csr(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->kval.as<double>(),
+                               ctx->uknown.as<uint8_t>(), u_in, f_in, ctx->perm.as<uint32_t>(), ctx->bc_touch.as<uint8_t>(),
+                               ctx->bc_touch_ready, N, bP, s);
+        }
+    } else {
+        magk::known_to_hilbert(u_in, ctx->uknown.as<uint8_t>(), ctx->iperm.as<int32_t>(), N, ctx->tmpP.as<double>(), s);
+        if (int rc = apply_plain(ctx, ctx->tmpP.as<double>(), ctx->q.as<double>(), 0)) return rc;
+        magk::rhs_from_apply(ctx->q.as<double>(), f_in, ctx->uknown.as<uint8_t>(), ctx->perm.as<uint32_t>(), N, bP, s);
+    }
     return MAG_OK;
 }
 
-int mag_run(mag_ctx *ctx)
+// solver.rs:435-441 for the right-hand side in ctx->bP: the CG phase the options and the mesh select, and argmin's best_param
+// at the iteration cap.  Fills the solve's part of ctx->stats; the solution is in ctx->x (ctx->u with the CSR operator).
+int cg_solve(mag_ctx *ctx)
 {
-    if (int rc = enter(ctx)) return rc;
-    if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "mag_run before mag_upload");
-    hipStream_t s = ctx->stream;
-    const int64_t N = ctx->N, E = ctx->E;
     mag_stats &st = ctx->stats;
-    st = {};
-    // every run redoes the whole path: nothing of a previous run is reused except allocations
-    ctx->have_order = ctx->have_csr = ctx->have_run = false;
-    // a context whose on-chip kernel once found the GPU shared is not condemned to stream for ever: after a number of
-    // streamed solves (8, doubling per failure) it tries again -- at worst one more spin budget (~0.3 s).  Across ranks
-    // the failures are agreed on collectively, so every rank counts the same and retries in the same solve.
-    if (ctx->persist_failed && --ctx->persist_retry_in <= 0) ctx->persist_failed = false;
-    if (ctx->opt.verbose) printf("info: building element stiffness matrices...\n");
-
-    HIPCHK(hipEventRecord(ctx->ev[0], s));
-    ctx->order_allow_shard = true; // (every rank of the communicator is in mag_run: the sharded phase's all-reduces are safe)
-    const int rc_order = ensure_order(ctx);
-    ctx->order_allow_shard = false;
-    if (rc_order) return rc_order;
-    HIPCHK(hipEventRecord(ctx->ev[1], s));
-    if (int rc = reserve_cg(ctx)) return rc;
-    const bool csr = ctx->opt.assemble_csr != 0 || ctx->opt.cg_operator == MAG_OP_CSR;
-    if (csr) {
-        if (int rc = csr_symbolic(ctx)) return rc;
-        HIPCHK(hipEventRecord(ctx->ev[2], s)); // (K_e is evaluated inside the row assembly: ms_element is 0 and no event pair is
-                                               // spent on it -- an empty pair still costs ~5 us of stream time)
-        if (ctx->opt.verbose) printf("info: building total stiffness matrix...\n");
-        if (int rc = gather_phase(ctx)) return rc;
-        ctx->have_csr = true;
-        HIPCHK(hipEventRecord(ctx->ev[4], s));
-        if (ctx->opt.verbose) printf("info: setting up system...\n");
-        HIPCHK(ctx->bc_touch.reserve((size_t)N + 16));
-        // the ordering phase has written b = 0.0 + f for every node (apply_order); only the rows with a prescribed column need
-        // K, and the pattern kernel has flagged them (bc_touch_ready); otherwise the full pass
-        if (ctx->b_from_order && ctx->bc_touch_ready)
-            magk::rhs_touched(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->kval.as<double>(),
-                              ctx->uknown.as<uint8_t>(), ctx->uin.as<double>(), ctx->fin.as<double>(),
-                              ctx->perm.as<uint32_t>(), ctx->bc_touch.as<uint8_t>(), N, ctx->bP.as<double>(), s);
-        else
-        magk::rhs_from_csr(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->kval.as<double>(),
-                           ctx->uknown.as<uint8_t>(), ctx->uin.as<double>(), ctx->fin.as<double>(),
-                           ctx->perm.as<uint32_t>(), ctx->bc_touch.as<uint8_t>(), ctx->bc_touch_ready, N,
-                           ctx->bP.as<double>(), s);
-    } else {
-        HIPCHK(hipEventRecord(ctx->ev[2], s));
-        HIPCHK(hipEventRecord(ctx->ev[4], s));
-        magk::known_to_hilbert(ctx->uin.as<double>(), ctx->uknown.as<uint8_t>(), ctx->iperm.as<int32_t>(), N,
-                               ctx->tmpP.as<double>(), s);
-        if (int rc = apply_plain(ctx, ctx->tmpP.as<double>(), ctx->q.as<double>(), 0)) return rc;
-        magk::rhs_from_apply(ctx->q.as<double>(), ctx->fin.as<double>(), ctx->uknown.as<uint8_t>(),
-                             ctx->perm.as<uint32_t>(), N, ctx->bP.as<double>(), s);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->ev[5], s));
-
-    if (ctx->opt.verbose) printf("info: solving...\n");
-    HIPCHK(ctx->u.reserve(16 * (size_t)N));
-    HIPCHK(ctx->f.reserve(16 * (size_t)N));
-    HIPCHK(ctx->stress.reserve(8 * (size_t)E));
     const bool csr_op = ctx->opt.cg_operator == MAG_OP_CSR;
     const bool f32 = ctx->opt.precision == 1;
     if (ctx->opt.preconditioner != 0 && (csr_op || f32 || !ctx->fused))
@@ -2102,26 +2069,121 @@ int mag_run(mag_ctx *ctx)
         st.final_cost = same ? best_cost : cost2;
         st.best_param_mismatch = same ? 0 : 1;
     }
+    return MAG_OK;
+}
+
+// solver.rs:443-535 for one solution: scatter-back, reactions, stress (caller numbering)
+int post_phase(mag_ctx *ctx, const double *xP, const double *u_in, const double *f_in, double *u, double *f, double *stress)
+{
+    hipStream_t s = ctx->stream;
+    const int64_t N = ctx->N;
+    if (ctx->opt.cg_operator != MAG_OP_CSR) // (the CSR operator's phase has expanded its solution into u itself)
+        magk::scatter_back(xP, ctx->perm.as<uint32_t>(), ctx->uknown.as<uint8_t>(), u_in, N, u, s);
+    if (ctx->opt.assemble_csr != 0 || ctx->opt.cg_operator == MAG_OP_CSR) {
+        magk::reactions_from_csr(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->kval.as<double>(),
+                                 ctx->uknown.as<uint8_t>(), u, f_in, N, f, s);
+    } else {
+        magk::to_hilbert(u, ctx->iperm.as<int32_t>(), ctx->uknown.as<uint8_t>(), 0, N, ctx->tmpP.as<double>(), s);
+        if (int rc = apply_plain(ctx, ctx->tmpP.as<double>(), ctx->q.as<double>(), 0)) return rc;
+        magk::reactions_from_apply(ctx->q.as<double>(), ctx->iperm.as<int32_t>(), ctx->uknown.as<uint8_t>(), f_in, N, f, s);
+    }
+    magk::element_stress(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), u, ctx->E, ctx->nu, ctx->youngs, stress, s);
+    return MAG_OK;
+}
+
+} // namespace
+
+int mag_upload(mag_ctx *ctx, const mag_problem *p)
+{
+    if (int rc = enter(ctx)) return rc;
+    if (!p || !p->xy || !p->conn || !p->u_known || !p->u_in || !p->f_in)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "null problem pointer");
+    const int64_t N = p->num_nodes, E = p->num_elements;
+    if (N < 1 || E < 1)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "empty mesh (nodes=%lld elements=%lld)", (long long)N, (long long)E);
+    if (N >= (int64_t(1) << 30) || 9 * E >= (int64_t(1) << 31))
+        return fail(ctx, MAG_ERR_TOO_LARGE, "mesh too large for int32 indexing (nodes=%lld elements=%lld)", (long long)N,
+                    (long long)E);
+    if (!(p->poisson_ratio * p->poisson_ratio != 1.0))
+        return fail(ctx, MAG_ERR_BAD_ARGS, "poisson_ratio^2 == 1");
+    const hipMemcpyKind kind = p->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    hipStream_t s = ctx->stream;
+    HIPCHK(ctx->xy.reserve(16 * (size_t)N));
+    HIPCHK(ctx->conn.reserve(12 * (size_t)E));
+    HIPCHK(ctx->uknown.reserve(2 * (size_t)N));
+    HIPCHK(ctx->uin.reserve(16 * (size_t)N));
+    HIPCHK(ctx->fin.reserve(16 * (size_t)N));
+    HIPCHK(hipMemcpyAsync(ctx->xy.p, p->xy, 16 * (size_t)N, kind, s));
+    HIPCHK(hipMemcpyAsync(ctx->conn.p, p->conn, 12 * (size_t)E, kind, s));
+    HIPCHK(hipMemcpyAsync(ctx->uknown.p, p->u_known, 2 * (size_t)N, kind, s));
+    HIPCHK(hipMemcpyAsync(ctx->uin.p, p->u_in, 16 * (size_t)N, kind, s));
+    HIPCHK(hipMemcpyAsync(ctx->fin.p, p->f_in, 16 * (size_t)N, kind, s));
+    HIPCHK(hipStreamSynchronize(s));
+    ctx->N = N;
+    ctx->E = E;
+    ctx->youngs = p->youngs_modulus;
+    ctx->nu = p->poisson_ratio;
+    ctx->thick = p->part_thickness;
+    ctx->have_problem = true;
+    ctx->have_order = ctx->have_csr = ctx->have_run = false;
+    ctx->have_cases = ctx->have_cases_run = false; // load cases belong to the mesh and mask they were set for
+    ctx->num_cases = 0;
+    return MAG_OK;
+}
+
+int mag_run(mag_ctx *ctx)
+{
+    if (int rc = enter(ctx)) return rc;
+    if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "mag_run before mag_upload");
+    hipStream_t s = ctx->stream;
+    const int64_t N = ctx->N, E = ctx->E;
+    mag_stats &st = ctx->stats;
+    st = {};
+    // every run redoes the whole path: nothing of a previous run is reused except allocations
+    ctx->have_order = ctx->have_csr = ctx->have_run = false;
+    // a context whose on-chip kernel once found the GPU shared is not condemned to stream for ever: after a number of
+    // streamed solves (8, doubling per failure) it tries again -- at worst one more spin budget (~0.3 s).  Across ranks
+    // the failures are agreed on collectively, so every rank counts the same and retries in the same solve.
+    if (ctx->persist_failed && --ctx->persist_retry_in <= 0) ctx->persist_failed = false;
+    if (ctx->opt.verbose) printf("info: building element stiffness matrices...\n");
+
+    HIPCHK(hipEventRecord(ctx->ev[0], s));
+    ctx->order_allow_shard = true; // (every rank of the communicator is in mag_run: the sharded phase's all-reduces are safe)
+    const int rc_order = ensure_order(ctx);
+    ctx->order_allow_shard = false;
+    if (rc_order) return rc_order;
+    HIPCHK(hipEventRecord(ctx->ev[1], s));
+    if (int rc = reserve_cg(ctx)) return rc;
+    const bool csr = ctx->opt.assemble_csr != 0 || ctx->opt.cg_operator == MAG_OP_CSR;
+    if (csr) {
+        if (int rc = csr_symbolic(ctx)) return rc;
+        HIPCHK(hipEventRecord(ctx->ev[2], s)); // (K_e is evaluated inside the row assembly: ms_element is 0 and no event pair is
+                                               // spent on it -- an empty pair still costs ~5 us of stream time)
+        if (ctx->opt.verbose) printf("info: building total stiffness matrix...\n");
+        if (int rc = gather_phase(ctx)) return rc;
+        ctx->have_csr = true;
+        HIPCHK(hipEventRecord(ctx->ev[4], s));
+        if (ctx->opt.verbose) printf("info: setting up system...\n");
+    } else {
+        HIPCHK(hipEventRecord(ctx->ev[2], s));
+        HIPCHK(hipEventRecord(ctx->ev[4], s));
+    }
+    if (int rc = rhs_phase(ctx, ctx->uin.as<double>(), ctx->fin.as<double>(), ctx->bP.as<double>(), ctx->b_from_order)) return rc;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ctx->ev[5], s));
+
+    if (ctx->opt.verbose) printf("info: solving...\n");
+    HIPCHK(ctx->u.reserve(16 * (size_t)N));
+    HIPCHK(ctx->f.reserve(16 * (size_t)N));
+    HIPCHK(ctx->stress.reserve(8 * (size_t)E));
+    if (int rc = cg_solve(ctx)) return rc;
     HIPCHK(hipEventRecord(ctx->ev[6], s));
     if (ctx->opt.verbose)
         printf("info: finished conjugate gradient approximation in %lld iterations\n", (long long)st.iterations);
 
-    if (!csr_op)
-        magk::scatter_back(ctx->x.as<double>(), ctx->perm.as<uint32_t>(), ctx->uknown.as<uint8_t>(),
-                           ctx->uin.as<double>(), N, ctx->u.as<double>(), s);
-    if (csr) {
-        magk::reactions_from_csr(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->kval.as<double>(),
-                                 ctx->uknown.as<uint8_t>(), ctx->u.as<double>(), ctx->fin.as<double>(), N,
-                                 ctx->f.as<double>(), s);
-    } else {
-        magk::to_hilbert(ctx->u.as<double>(), ctx->iperm.as<int32_t>(), ctx->uknown.as<uint8_t>(), 0, N,
-                         ctx->tmpP.as<double>(), s);
-        if (int rc = apply_plain(ctx, ctx->tmpP.as<double>(), ctx->q.as<double>(), 0)) return rc;
-        magk::reactions_from_apply(ctx->q.as<double>(), ctx->iperm.as<int32_t>(), ctx->uknown.as<uint8_t>(),
-                                   ctx->fin.as<double>(), N, ctx->f.as<double>(), s);
-    }
-    magk::element_stress(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), ctx->u.as<double>(), E, ctx->nu, ctx->youngs,
-                         ctx->stress.as<double>(), s);
+    if (int rc = post_phase(ctx, ctx->x.as<double>(), ctx->uin.as<double>(), ctx->fin.as<double>(), ctx->u.as<double>(),
+                            ctx->f.as<double>(), ctx->stress.as<double>()))
+        return rc;
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ctx->ev[7], s));
     HIPCHK(hipStreamSynchronize(s));
@@ -2174,6 +2236,307 @@ int mag_download(mag_ctx *ctx, mag_result *r)
     return MAG_OK;
 }
 
+// ---- load cases: num_cases sets of prescribed values on the uploaded mesh (same mesh, material and u_known mask) ----
+int mag_set_load_cases(mag_ctx *ctx, int32_t num_cases, const double *u_in, const double *f_in, int32_t memory)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (num_cases < 1) return fail(ctx, MAG_ERR_BAD_ARGS, "num_cases = %d: at least one load case", (int)num_cases);
+    if (!u_in || !f_in) return fail(ctx, MAG_ERR_BAD_ARGS, "null load-case pointer");
+    if (ctx->comm.nranks > 1)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "load cases run on one GPU: this context has a communicator of %d ranks", ctx->comm.nranks);
+    if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "mag_set_load_cases before mag_upload");
+    if (int rc = enter(ctx)) return rc;
+    ctx->have_cases = ctx->have_cases_run = false;
+    const size_t bytes = 16 * (size_t)ctx->N * (size_t)num_cases;
+    const hipMemcpyKind kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    hipStream_t s = ctx->stream;
+    HIPCHK(ctx->c_uin.reserve(bytes));
+    HIPCHK(ctx->c_fin.reserve(bytes));
+    HIPCHK(hipMemcpyAsync(ctx->c_uin.p, u_in, bytes, kind, s));
+    HIPCHK(hipMemcpyAsync(ctx->c_fin.p, f_in, bytes, kind, s));
+    HIPCHK(hipStreamSynchronize(s));
+    ctx->num_cases = num_cases;
+    ctx->have_cases = true;
+    return MAG_OK;
+}
+
+namespace {
+
+// the context's own u_in / f_in (mag_upload's) are lent to a case that runs through the single-case phases, and come back
+struct KeepLoads {
+    mag_ctx *ctx;
+    size_t bytes;
+    bool armed = false;
+    ~KeepLoads()
+    {
+        if (!armed) return;
+        (void)hipMemcpyAsync(ctx->uin.p, ctx->c_keep.p, bytes, hipMemcpyDeviceToDevice, ctx->stream);
+        (void)hipMemcpyAsync(ctx->fin.p, ctx->c_keep.as<char>() + bytes, bytes, hipMemcpyDeviceToDevice, ctx->stream);
+        (void)hipStreamSynchronize(ctx->stream);
+    }
+};
+
+// one case through the single-case CG phases (cg_solve: the phase the options select, its time-out fall-back, best_param):
+// its loads and right-hand side into the context's buffers, its solution out of them.  history_len and verbose are case 0's.
+int solve_case_alone(mag_ctx *ctx, int32_t c, mag_stats &out, bool timed_out_before)
+{
+    hipStream_t s = ctx->stream;
+    const size_t vb = 16 * (size_t)ctx->N;
+    HIPCHK(hipMemcpyAsync(ctx->uin.p, ctx->c_uin.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->fin.p, ctx->c_fin.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->bP.p, ctx->c_bP.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
+    const int32_t hist_len = ctx->opt.history_len, verbose = ctx->opt.verbose;
+    if (c != 0) ctx->opt.history_len = ctx->opt.verbose = 0;
+    ctx->stats = {};
+    HIPCHK(hipEventRecord(ctx->ev[8], s));
+    const int rc = cg_solve(ctx);
+    ctx->opt.history_len = hist_len;
+    ctx->opt.verbose = verbose;
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(ctx->ev[9], s));
+    if (ctx->opt.cg_operator == MAG_OP_CSR)
+        HIPCHK(hipMemcpyAsync(ctx->c_u.as<char>() + vb * c, ctx->u.p, vb, hipMemcpyDeviceToDevice, s));
+    else
+        HIPCHK(hipMemcpyAsync(ctx->c_x.as<char>() + vb * c, ctx->x.p, vb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    out = ctx->stats;
+    out.ms_cg = ev_ms(ctx->ev[8], ctx->ev[9]);
+    out.cg_kernel = ctx->cg_kernel;
+    out.exchange = ctx->exchange_kind;
+    out.persist_timeout = (timed_out_before || ctx->persist_timed_out) ? 1 : 0;
+    out.edge_blocks = ctx->cg_kernel == 2 ? ctx->edge_blocks : 0;
+    out.tiles_per_workgroup = ctx->cg_kernel == 2 ? ctx->persist_k : 0;
+    return MAG_OK;
+}
+
+} // namespace
+
+int mag_run_cases(mag_ctx *ctx)
+{
+    using magk::FusedState;
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (ctx->comm.nranks > 1)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "load cases run on one GPU: this context has a communicator of %d ranks", ctx->comm.nranks);
+    if (!ctx->have_problem || !ctx->have_cases) return fail(ctx, MAG_ERR_STATE, "mag_run_cases before mag_set_load_cases");
+    if (int rc = enter(ctx)) return rc;
+    hipStream_t s = ctx->stream;
+    const int64_t N = ctx->N, E = ctx->E;
+    const int32_t L = ctx->num_cases;
+    const size_t vb = 16 * (size_t)N, eb = 8 * (size_t)E;
+    ctx->stats = {};
+    // as in mag_run: the whole path is redone, only allocations are reused; the single-case results of the context are gone
+    ctx->have_order = ctx->have_csr = ctx->have_run = ctx->have_cases_run = false;
+    if (ctx->persist_failed && --ctx->persist_retry_in <= 0) ctx->persist_failed = false;
+    ctx->case_stats.assign((size_t)L, mag_stats{});
+    int32_t *info = ctx->cases_info;
+    info[0] = L;
+    info[1] = info[2] = info[3] = 0;
+    if (ctx->opt.verbose) printf("info: building element stiffness matrices...\n");
+
+    // ---- once for all cases: order, symbolic, K (nothing here reads a prescribed VALUE; apply_order's b = 0.0 + f of the
+    // context's own f_in is simply not used)
+    HIPCHK(hipEventRecord(ctx->ev[0], s));
+    if (int rc = ensure_order(ctx)) return rc;
+    HIPCHK(hipEventRecord(ctx->ev[1], s));
+    if (int rc = reserve_cg(ctx)) return rc;
+    const bool csr = ctx->opt.assemble_csr != 0 || ctx->opt.cg_operator == MAG_OP_CSR;
+    if (csr) {
+        if (int rc = csr_symbolic(ctx)) return rc;
+        HIPCHK(hipEventRecord(ctx->ev[2], s));
+        if (ctx->opt.verbose) printf("info: building total stiffness matrix...\n");
+        if (int rc = gather_phase(ctx)) return rc;
+        ctx->have_csr = true;
+    } else {
+        HIPCHK(hipEventRecord(ctx->ev[2], s));
+    }
+    HIPCHK(hipEventRecord(ctx->ev[4], s));
+    if (ctx->opt.verbose) printf("info: setting up system...\n");
+    HIPCHK(ctx->c_bP.reserve(vb * L));
+    HIPCHK(ctx->c_x.reserve(vb * L));
+    HIPCHK(ctx->c_u.reserve(vb * L));
+    HIPCHK(ctx->c_f.reserve(vb * L));
+    HIPCHK(ctx->c_stress.reserve(eb * L));
+    HIPCHK(ctx->u.reserve(vb)); // (the CSR operator's phase expands into the context's u)
+    auto at = [](const DevBuf &b, size_t stride, int32_t c) { return (double *)(b.as<char>() + stride * (size_t)c); };
+    // ---- per case: the right-hand side, the single-case arithmetic in the single-case order
+    for (int32_t c = 0; c < L; ++c)
+        if (int rc = rhs_phase(ctx, at(ctx->c_uin, vb, c), at(ctx->c_fin, vb, c), at(ctx->c_bP, vb, c), false)) return rc;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ctx->ev[5], s));
+    if (ctx->opt.verbose) printf("info: solving...\n");
+
+    // ---- CG.  On-chip and at least two cases fit the chip: chunks of floor(CUs / G) cases per launch of the load-case kernel,
+    // G = the workgroups one case needs, persist_k as the single-case path chose it (more tiles per workgroup would change the
+    // summation order).  Anything else: one case after another through the single-case phases.
+    int cus = 0;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+    const int32_t G = ctx->persist_grid;
+    int32_t per_launch = 0;
+    magk::PersistParams P = {};
+    int eb_mode = 0;
+    // (ctx->persist: cg_variant 2, fp64, matrix-free, no preconditioner, not in back-off, the mesh fits -- ensure_order)
+    if (ctx->persist && ctx->opt.cg_operator != MAG_OP_CSR && ctx->opt.precision == 0 && G >= 1 && cus / G >= 2) {
+        P.nranks = 1;
+        persist_common_params(ctx, false, P);
+        if (int rc = persist_prepare_blocks(ctx, false, P, eb_mode)) return rc;
+        if (magk::persist_cases_shape(ctx->B, G, ctx->persist_k, eb_mode)) per_launch = cus / G;
+    }
+    info[1] = per_launch;
+    KeepLoads keep{ctx, vb};
+    auto lend_loads = [&]() -> int { // before the first case that runs alone
+        if (keep.armed) return MAG_OK;
+        HIPCHK(ctx->c_keep.reserve(2 * vb));
+        HIPCHK(hipMemcpyAsync(ctx->c_keep.p, ctx->uin.p, vb, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(ctx->c_keep.as<char>() + vb, ctx->fin.p, vb, hipMemcpyDeviceToDevice, s));
+        keep.armed = true;
+        return MAG_OK;
+    };
+    std::vector<uint8_t> alone((size_t)L, per_launch ? 0 : 1), timed_out((size_t)L, 0);
+    if (per_launch) {
+        const size_t qg_bytes = 2 * 32 * (size_t)N, rec_bytes = 2 * 64 * (size_t)G;
+        const int32_t nmax = std::min(per_launch, L);
+        HIPCHK(ctx->c_qx.reserve(qg_bytes * nmax));
+        HIPCHK(ctx->c_part.reserve(rec_bytes * nmax));
+        HIPCHK(ctx->c_sync.reserve(64 * (size_t)nmax));
+        HIPCHK(ctx->c_state.reserve(sizeof(FusedState) * (size_t)nmax));
+        std::vector<FusedState> h_st((size_t)nmax);
+        std::vector<uint32_t> h_sync(16 * (size_t)nmax);
+        for (int32_t c0 = 0; c0 < L; c0 += per_launch) {
+            const int32_t n = std::min(per_launch, L - c0);
+            // tags of a previous launch must not look current: zeroed before EVERY launch, as cg_phase_persist does
+            HIPCHK(hipMemsetAsync(ctx->c_qx.p, 0, qg_bytes * n, s));
+            HIPCHK(hipMemsetAsync(ctx->c_part.p, 0, rec_bytes * n, s));
+            HIPCHK(hipMemsetAsync(ctx->c_sync.p, 0, 64 * (size_t)n, s));
+            HIPCHK(hipMemsetAsync(ctx->c_state.p, 0, sizeof(FusedState) * (size_t)n, s));
+            P.bP = (const double2 *)at(ctx->c_bP, vb, c0);
+            P.x = (double2 *)at(ctx->c_x, vb, c0);
+            P.qg = ctx->c_qx.as<unsigned long long>();
+            P.recg = ctx->c_part.as<unsigned long long>();
+            P.sync = ctx->c_sync.as<uint32_t>();
+            P.st = ctx->c_state.as<FusedState>();
+            P.hist_len = c0 == 0 ? ctx->opt.history_len : 0; // (case 0's alone: the kernel keeps it from the launch's other cases)
+            HIPCHK(hipEventRecord(ctx->ev[8], s));
+            magk::persist_launch_cases(P, ctx->B, G, n, eb_mode, s);
+            HIPCHK(hipEventRecord(ctx->ev[9], s));
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(h_st.data(), ctx->c_state.p, sizeof(FusedState) * (size_t)n, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(h_sync.data(), ctx->c_sync.p, 64 * (size_t)n, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            ++info[2];
+            const double ms = ev_ms(ctx->ev[8], ctx->ev[9]);
+            for (int32_t k = 0; k < n; ++k) {
+                const FusedState &st = h_st[(size_t)k];
+                mag_stats &cs = ctx->case_stats[(size_t)(c0 + k)];
+                cs.ms_cg = ms;
+                if (h_sync[16 * (size_t)k + 9] != 0 || !st.done) { // this case's group gave up at its barrier
+                    alone[(size_t)(c0 + k)] = timed_out[(size_t)(c0 + k)] = 1;
+                    continue;
+                }
+                cs.iterations = st.iterations;
+                cs.final_cost = st.final_cost;
+                cs.rhs_norm = std::sqrt(st.bb);
+                cs.converged = st.converged;
+                cs.breakdown = st.breakdown;
+                cs.best_iteration = st.iterations;
+                cs.termination = st.breakdown ? MAG_TERM_BREAKDOWN : (st.converged ? MAG_TERM_TARGET_COST : MAG_TERM_MAX_ITERS);
+                cs.cg_kernel = 2;
+                cs.edge_blocks = eb_mode;
+                cs.tiles_per_workgroup = ctx->persist_k;
+                // the iteration cap with an earlier best iterate: best_param is recovered by the single-case path's repeat
+                if (cs.termination == MAG_TERM_MAX_ITERS && st.best_iter >= 1 && st.best_iter < st.iterations)
+                    alone[(size_t)(c0 + k)] = 1;
+            }
+        }
+        ctx->cg_kernel = 2;
+    }
+    bool backed_off = false;
+    for (int32_t c = 0; c < L; ++c) {
+        if (!alone[(size_t)c]) continue;
+        if (timed_out[(size_t)c] && !backed_off) { // the single-case path's bookkeeping: the context streams from here on
+            persist_back_off(ctx);
+            backed_off = true;
+        }
+        if (int rc = lend_loads()) return rc;
+        if (int rc = solve_case_alone(ctx, c, ctx->case_stats[(size_t)c], timed_out[(size_t)c] != 0)) return rc;
+        if (per_launch) ++info[3];
+    }
+    if (per_launch && !backed_off) ctx->persist_backoff = 0; // co-resident: the next failure starts from the short wait
+    HIPCHK(hipEventRecord(ctx->ev[6], s));
+    if (ctx->opt.verbose)
+        printf("info: finished conjugate gradient approximation in %lld iterations\n", (long long)ctx->case_stats[0].iterations);
+
+    // ---- per case: scatter-back, reactions, stress
+    for (int32_t c = 0; c < L; ++c)
+        if (int rc = post_phase(ctx, at(ctx->c_x, vb, c), at(ctx->c_uin, vb, c), at(ctx->c_fin, vb, c), at(ctx->c_u, vb, c),
+                                at(ctx->c_f, vb, c), at(ctx->c_stress, eb, c)))
+            return rc;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ctx->ev[7], s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (ctx->opt.verbose) printf("info: solve complete\n");
+
+    int status = MAG_OK;
+    for (int32_t c = 0; c < L; ++c) {
+        mag_stats &cs = ctx->case_stats[(size_t)c];
+        cs.ms_order = ev_ms(ctx->ev[0], ctx->ev[1]); // the shared phases: the same in every case
+        cs.ms_csr_symbolic = ev_ms(ctx->ev[1], ctx->ev[2]);
+        cs.ms_element = 0.0;
+        cs.ms_assemble = ev_ms(ctx->ev[2], ctx->ev[4]);
+        cs.ms_bc = ev_ms(ctx->ev[4], ctx->ev[5]); // all cases' right-hand sides / post-processing / the whole run
+        cs.ms_post = ev_ms(ctx->ev[6], ctx->ev[7]);
+        cs.ms_total = ev_ms(ctx->ev[0], ctx->ev[7]);
+        cs.nnz = csr ? 4 * ctx->nb : 0;
+        cs.num_tiles = ctx->T;
+        cs.ell_entries = ctx->ell_total;
+        cs.halo_nodes = ctx->halo_total;
+        cs.max_tile_halo = ctx->max_halo;
+        cs.lds_operator = ctx->use_lds ? 1 : 0;
+        cs.n_free = ctx->nf;
+        if (cs.breakdown && status == MAG_OK)
+            status = fail(ctx, MAG_ERR_NOT_CONVERGED, "load case %d: Conjugate Gradient error: non-finite residual after %lld iterations",
+                          (int)c, (long long)cs.iterations);
+    }
+    ctx->stats = ctx->case_stats[0];
+    ctx->have_cases_run = true;
+    return status;
+}
+
+int mag_download_case(mag_ctx *ctx, int32_t case_index, mag_result *r)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!r) return fail(ctx, MAG_ERR_BAD_ARGS, "null result");
+    if (case_index < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "load case %d out of range", (int)case_index);
+    if (!ctx->have_cases_run) return fail(ctx, MAG_ERR_STATE, "mag_download_case before a completed mag_run_cases");
+    if (case_index >= ctx->num_cases)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "load case %d out of range [0, %d)", (int)case_index, (int)ctx->num_cases);
+    if (int rc = enter(ctx)) return rc;
+    const hipMemcpyKind kind = r->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    hipStream_t s = ctx->stream;
+    const size_t vb = 16 * (size_t)ctx->N, eb = 8 * (size_t)ctx->E, c = (size_t)case_index;
+    if (r->u_out) HIPCHK(hipMemcpyAsync(r->u_out, ctx->c_u.as<char>() + vb * c, vb, kind, s));
+    if (r->f_out) HIPCHK(hipMemcpyAsync(r->f_out, ctx->c_f.as<char>() + vb * c, vb, kind, s));
+    if (r->stress_out) HIPCHK(hipMemcpyAsync(r->stress_out, ctx->c_stress.as<char>() + eb * c, eb, kind, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
+int mag_get_case_stats(const mag_ctx *ctx, int32_t case_index, mag_stats *st)
+{
+    if (!ctx || !st || case_index < 0) return MAG_ERR_BAD_ARGS;
+    if (!ctx->have_cases_run) return MAG_ERR_STATE;
+    if (case_index >= ctx->num_cases) return MAG_ERR_BAD_ARGS;
+    *st = ctx->case_stats[(size_t)case_index];
+    return MAG_OK;
+}
+
+int mag_get_cases_info(const mag_ctx *ctx, int32_t info[4])
+{
+    if (!ctx || !info) return MAG_ERR_BAD_ARGS;
+    if (!ctx->have_cases_run) return MAG_ERR_STATE;
+    for (int k = 0; k < 4; ++k) info[k] = ctx->cases_info[k];
+    return MAG_OK;
+}
+
 int mag_solve(mag_ctx *ctx, const mag_problem *p, mag_result *r)
 {
     if (int rc = mag_upload(ctx, p)) return rc;
@@ -2197,7 +2560,7 @@ int mag_get_stats(const mag_ctx *ctx, mag_stats *st)
 int mag_get_history(mag_ctx *ctx, double *history, int64_t n)
 {
     if (int rc = enter(ctx)) return rc;
-    if (!ctx->have_run) return fail(ctx, MAG_ERR_STATE, "no completed run");
+    if (!ctx->have_run && !ctx->have_cases_run) return fail(ctx, MAG_ERR_STATE, "no completed run");
     if (n < 0 || n > ctx->opt.history_len || n > ctx->stats.iterations || (n > 0 && !history))
         return fail(ctx, MAG_ERR_BAD_ARGS, "history length %lld not available", (long long)n);
     if (n > 0) HIPCHK(hipMemcpy(history, ctx->hist.p, 8 * (size_t)n, hipMemcpyDeviceToHost));

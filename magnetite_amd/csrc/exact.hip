@@ -889,6 +889,23 @@ __global__ void __launch_bounds__(256) k_rhs_touched(const int32_t *bptr, const 
     bP[g] = make_double2((own & 0xffu) ? 0.0 : s0 + f.x, (own >> 8) ? 0.0 : s1 + f.y);
 }
 
+// b of a row without a prescribed column, as k_apply_order writes it (the same expression: the same bits), for a load case
+// whose f was not there when the ordering phase ran
+__global__ void __launch_bounds__(256) k_rhs_untouched(const uint8_t *u_known, const double2 *f_in, const uint32_t *perm,
+                                                       int64_t N, double2 *bP)
+{
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= N) return;
+    const int64_t o = perm[g];
+    const double2 f = f_in[o];
+    bP[g] = make_double2(u_known[2 * o] ? 0.0 : 0.0 + f.x, u_known[2 * o + 1] ? 0.0 : 0.0 + f.y);
+}
+
+void rhs_untouched(const uint8_t *u_known, const double *f_in, const uint32_t *perm, int64_t N, double *bP, hipStream_t s)
+{
+    k_rhs_untouched<<<blocks_for(N, 256), 256, 0, s>>>(u_known, (const double2 *)f_in, perm, N, (double2 *)bP);
+}
+
 void rhs_touched(const int32_t *bptr, const int32_t *bcol, const double *kval, const uint8_t *u_known, const double *u_in,
                  const double *f_in, const uint32_t *perm, const uint8_t *touch, int64_t N, double *bP, hipStream_t s)
 {

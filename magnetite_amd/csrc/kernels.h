@@ -140,6 +140,9 @@ bool assemble_ctiles(const int32_t *bcol, const int32_t *bptr, const uint32_t *p
 // (touch: the pattern kernel's flags, Hilbert order)
 void rhs_touched(const int32_t *bptr, const int32_t *bcol, const double *kval, const uint8_t *u_known, const double *u_in,
                  const double *f_in, const uint32_t *perm, const uint8_t *touch, int64_t N, double *bP, hipStream_t s);
+// what apply_order writes, on its own (load cases: the ordering phase runs once, every case has its own f): bP = 0.0 + f, 0 on
+// a prescribed DOF
+void rhs_untouched(const uint8_t *u_known, const double *f_in, const uint32_t *perm, int64_t N, double *bP, hipStream_t s);
 // solver.rs:365-404,427-432: b[row] = sum_{known cols, ascending} -(K*u) + f  (0 on prescribed rows),
 // written in Hilbert order: bP[2*iperm[node]+a]
 void rhs_from_csr(const int32_t *bptr, const int32_t *bcol, const double *kval, const uint8_t *u_known,
@@ -410,6 +413,11 @@ int persist_tiles_per_wg(int32_t B); // tiles one workgroup keeps on chip (0: ti
 size_t persist_lds_bytes(int32_t B, int32_t cap, int32_t maxh, int eb_mode = 0, int32_t pool = 0, bool mg = false);
 // MG kernel when nranks > 1; eb_mode as above (the host decides from ring16's flags and the overflow limits)
 void persist_launch(const PersistParams &P, int32_t B, int32_t grid, int eb_mode, hipStream_t s);
+// Load cases: `cases` right-hand sides of one mesh side by side in ONE launch, `grid` workgroups each (grid * cases <= CUs: all
+// co-resident).  P points at case 0; case c's bP, x, qg, recg, sync, st follow at c times their single-case extent
+// (persist.hip, persist_case_params).  persist_cases_shape: the shape has a load-case instantiation (else: one case at a time).
+bool persist_cases_shape(int32_t B, int32_t grid, int32_t tiles_per_wg, int eb_mode);
+void persist_launch_cases(const PersistParams &P, int32_t B, int32_t grid, int32_t cases, int eb_mode, hipStream_t s);
 int persist_block_entries(); // block entries per node of that instantiation
 // ... and its blocks: 3 * persist_block_entries() doubles per node of the T * B padded nodes, into P.kblocks (host sets
 // kblocks / kb_stride before the call; eb_mode 2: row_info / ovf_off / ovf_rec as well)

@@ -748,6 +748,22 @@ __device__ inline void persist_single_workgroup(double *s_S, double (&Sx)[4], do
     __syncthreads(); // (s_S is rewritten by the next iteration's sums)
 }
 
+// Load cases (k_cg_persist<..., LC = true>): the parameters of case blockIdx.y.  Per case, in this order behind each pointer:
+// bP and x N nodes, qg 2 * 4 N granules, recg 2 * 8 gridDim.x granules, sync 16 words, st one FusedState.  The cost history is
+// case 0's alone.  blockIdx.y is a scalar: the offsets are scalar arithmetic, once per launch.
+__device__ inline PersistParams persist_case_params(PersistParams P)
+{
+    const int64_t c = (int64_t)blockIdx.y;
+    P.bP += c * P.N;
+    P.x += c * P.N;
+    P.qg += 8 * c * P.N;
+    P.recg += 16 * c * (int64_t)gridDim.x;
+    P.sync += 16 * c;
+    P.st += c;
+    if (c != 0) P.hist_len = 0;
+    return P;
+}
+
 // EBM: 0 the triangle walk, 1 edge blocks in registers (every row of the mesh a fan of at most six blocks: structured meshes),
 // 2 edge blocks with OVERFLOW (round 4: rows that are one fan of any length -- what gmsh's frontal meshes look like, a quarter
 // of their nodes with seven neighbours: blocks beyond the six in registers sit in an LDS pool of 32-byte records).
@@ -756,9 +772,21 @@ __device__ inline void persist_single_workgroup(double *s_S, double (&Sx)[4], do
 // NPTX: nodes per lane when not the shape's four -- 1: ONE TILE PER WORKGROUP, what a mesh of at most 256 tiles runs as (config 2:
 // 99 tiles).  The general instantiation carries three dead node slots through every loop there, and their registers (the
 // blocks alone are 36 per slot) are what puts it at the 256-register limit.
-template <int B, bool MG, int THREADS, int EBM, bool ONE = false, int NPTX = 0>
-__global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams P)
+// LC: the LOAD-CASE form (one GPU): a 2-D grid, blockIdx.y = the case within the launch, gridDim.x = the workgroups ONE case
+// needs.  The cases share mesh, blocks, mask and tables; each has its own right-hand side, solution, granules, records, timeout
+// word and state, laid out case after case behind the pointers of PersistParams (persist_case_params).  Nothing else differs:
+// tile addressing, exchange and record layout use blockIdx.x / gridDim.x as ever, so a case computes bit for bit what a launch
+// of its own computes, takes its own stop decision and leaves when it is done -- no case waits for another.  A template flag
+// with instantiations of its own for the same reason as ONE: the single-case instantiations keep their code, instruction for
+// instruction (only their mangled names gain the defaulted flag; with the body moved into a function that two kernels inline,
+// which would have kept the names, the compiler allocated the existing kernels' registers differently).
+template <int B, bool MG, int THREADS, int EBM, bool ONE = false, int NPTX = 0, bool LC = false>
+__global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
 {
+    static_assert(!(LC && MG), "load cases run on one GPU");
+    PersistParams Pc; // (LC only)
+    if constexpr (LC) Pc = persist_case_params(Pk);
+    const PersistParams &P = LC ? Pc : Pk;
     constexpr int NPT = NPTX ? NPTX : kPersistNpt;
     constexpr bool EB = EBM != 0, OV = EBM == 2;
     constexpr bool OPQ = OV; // the thread index behind an empty asm in the overflow instantiation: see persist_block_sum
@@ -1382,6 +1410,45 @@ void persist_launch_eb1_k4(const PersistParams &P, int32_t grid, size_t lds, hip
 void persist_launch_eb1_k4(const PersistParams &P, int32_t grid, size_t lds, hipStream_t s)
 {
     k_cg_persist<512, false, 512, 1><<<grid, 512, lds, s>>>(P);
+}
+} // namespace magk
+#elif defined(MAG_PERSIST_TU_CASES)
+// The load-case instantiations (LC), in a translation unit of their own as well (persist_cases.o: this file with
+// -DMAG_PERSIST_TU_CASES, under persist.o's scheduler): persist.o and persist_k4.o are compiled from exactly what they were
+// compiled from before load cases existed.  One instantiation per shape the single-case path runs for a mesh of which at least
+// two cases fit the chip -- the SAME shape, so that a case gets the bits of a launch of its own:
+//   triangle walk: the general four-slot kernel (what persist_launch takes for it whatever the grid);
+//   edge blocks, with and without overflow: the single-workgroup kernel with one to four tiles, and one tile per workgroup.
+bool persist_cases_shape(int32_t B, int32_t grid, int32_t tiles_per_wg, int eb_mode)
+{
+    if (B != 512 || grid < 1) return false;
+    if (eb_mode == 0) return tiles_per_wg >= 1 && tiles_per_wg <= kPersistNpt;
+    return grid == 1 ? tiles_per_wg >= 1 && tiles_per_wg <= kPersistNpt : tiles_per_wg == 1;
+}
+
+void persist_launch_cases(const PersistParams &P, int32_t B, int32_t grid, int32_t cases, int eb_mode, hipStream_t s)
+{
+    if (!persist_cases_shape(B, grid, P.tiles_per_wg, eb_mode) || P.nranks != 1 || cases < 1) return; // (the host has asked)
+    const size_t lds = persist_lds_bytes(B, P.cap, P.maxh, eb_mode, P.pool_cap, false);
+    const dim3 g((unsigned)grid, (unsigned)cases);
+    if (eb_mode == 0) {
+        k_cg_persist<512, false, 512, 0, false, 0, true><<<g, 512, lds, s>>>(P);
+        return;
+    }
+    const bool one = grid == 1;
+    const int npt = P.tiles_per_wg < 4 ? P.tiles_per_wg : 0;
+#define MAG_PERSIST_CASE(EBM_, ONE_, NPTX_)                                                                                       \
+    if (eb_mode == EBM_ && one == ONE_ && npt == NPTX_) k_cg_persist<512, false, 512, EBM_, ONE_, NPTX_, true><<<g, 512, lds, s>>>(P)
+#define MAG_PERSIST_CASES(EBM_)                                                                                                   \
+    MAG_PERSIST_CASE(EBM_, false, 1);                                                                                             \
+    MAG_PERSIST_CASE(EBM_, true, 1);                                                                                              \
+    MAG_PERSIST_CASE(EBM_, true, 2);                                                                                              \
+    MAG_PERSIST_CASE(EBM_, true, 3);                                                                                              \
+    MAG_PERSIST_CASE(EBM_, true, 0)
+    MAG_PERSIST_CASES(1);
+    MAG_PERSIST_CASES(2);
+#undef MAG_PERSIST_CASES
+#undef MAG_PERSIST_CASE
 }
 } // namespace magk
 #else

@@ -230,6 +230,53 @@ class Context:
         out.update(self.stats())
         return out
 
+    # -- load cases: several sets of prescribed values on the uploaded mesh ------
+    def set_load_cases(self, u_in, f_in):
+        """mag_set_load_cases: u_in, f_in of shape (L, 2N) -- prescribed displacements / forces per case, read where the
+        uploaded u_known mask says so."""
+        u_in = np.ascontiguousarray(u_in, dtype=np.float64)
+        f_in = np.ascontiguousarray(f_in, dtype=np.float64)
+        if u_in.ndim != 2 or u_in.shape != f_in.shape or u_in.shape[1] != 2 * self.N:
+            raise MagnetiteError("Solver", "load cases: u_in and f_in must both have shape (num_cases, 2 * num_nodes)")
+        self._check(self._L.mag_set_load_cases(self._h, u_in.shape[0], _p(u_in, C.c_double), _p(f_in, C.c_double),
+                                               MAG_MEM_HOST))
+        self.num_cases = u_in.shape[0]
+
+    def run_cases(self, allow_not_converged=False):
+        """mag_run_cases: order, symbolic work and K once, the cases' CG solves side by side on the chip where they fit."""
+        allow = (MAG_ERR_NOT_CONVERGED,) if allow_not_converged else ()
+        return self._check(self._L.mag_run_cases(self._h), allow)
+
+    def download_case(self, i):
+        u, f, s = np.empty(2 * self.N), np.empty(2 * self.N), np.empty(self.E)
+        r = _lib.Result(u.ctypes.data, f.ctypes.data, s.ctypes.data, MAG_MEM_HOST, 0)
+        self._check(self._L.mag_download_case(self._h, i, C.byref(r)))
+        return u, f, s
+
+    def case_stats(self, i):
+        st = _lib.Stats()
+        self._check(self._L.mag_get_case_stats(self._h, i, C.byref(st)))
+        return st.as_dict()
+
+    def cases_info(self):
+        """dict(cases, cases_per_launch (0: one after another through the single-case CG phases), launches, redone)."""
+        info = (C.c_int32 * 4)()
+        self._check(self._L.mag_get_cases_info(self._h, info))
+        return dict(cases=info[0], cases_per_launch=info[1], launches=info[2], redone=info[3])
+
+    def solve_cases(self, prob, u_in, f_in, allow_not_converged=False):
+        """Upload prob's mesh, material and mask, solve the (L, 2N) load sets: a list of dicts shaped like solve()'s."""
+        self.upload_problem(prob)
+        self.set_load_cases(u_in, f_in)
+        self.run_cases(allow_not_converged)
+        outs = []
+        for i in range(self.num_cases):
+            u, f, s = self.download_case(i)
+            out = dict(u=u, f=f, stress=s)
+            out.update(self.case_stats(i))
+            outs.append(out)
+        return outs
+
     # -- pieces, for parity tests ----------------------------------------------
     def element_stiffness(self):
         ke = np.empty(36 * self.E)
