@@ -40,7 +40,8 @@ extern "C" {
 #define MAG_ABI_VERSION 4 /* 3: mag_stats gained exchange_timeout, best_param_mismatch; 4: edge_blocks (and, in the
                              reserved word behind it, tiles_per_workgroup).  Load cases (mag_set_load_cases ...
                              mag_get_cases_info) came later as new entry points only: no struct changed, the version
-                             stays 4, and a caller detects the feature by the presence of those symbols (dlsym) */
+                             stays 4, and a caller detects the feature by the presence of those symbols (dlsym); design
+                             variants (mag_set_variants ... mag_get_variants_info) likewise */
 
 /* solver.rs:17-19 */
 #define MAG_DOF 2
@@ -263,6 +264,39 @@ int mag_download_case(mag_ctx *ctx, int32_t case_index, mag_result *result);
 int mag_get_case_stats(const mag_ctx *ctx, int32_t case_index, mag_stats *stats);
 int mag_get_cases_info(const mag_ctx *ctx, int32_t info[4]);
 
+/* ---- design variants: several SHAPES and MATERIALS of one uploaded mesh (same connectivity, same u_known mask) ---- */
+/* What shape optimisation, mesh morphing, tolerance / Monte-Carlo studies and sweeps of E, nu, thickness do: the topology stays,
+ * node coordinates, the material and (optionally) the prescribed values change per variant.
+ *   shared, done once per mag_run_variants: the Hilbert order OF THE UPLOADED COORDINATES, incidence, tile, ELL, ring and halo
+ *     tables, masks, the CSR pattern, the on-chip kernel's instantiation (edge_blocks 0 / 1 / 2), overflow-pool layout and grid;
+ *   per variant: permuted coordinates, K values in the shared pattern (bit for bit the reference's assembly for that geometry),
+ *     right-hand side, edge blocks, CG, scatter-back, reactions (that variant's K), stress (its geometry, E, nu).
+ * The variants' CG solves run side by side in the on-chip kernel by the load cases' rule -- floor(CUs / G) per launch, one
+ * launch PER PHASE per chunk (permute, assemble, right-hand sides, blocks, CG, post), device memory bounded by one chunk's K --
+ * when load cases would (and K is assembled: options.assemble_csr); otherwise one variant after another through the
+ * single-case phases, the shared tables kept, the variant's coordinates and material swapped into the context.  Either way a
+ * variant computes bit for bit what it computes as the only variant of a call of its own; a variant with the uploaded
+ * coordinates computes bit for bit what mag_upload + mag_run compute with its material and values.
+ *
+ * mag_set_variants: after mag_upload.  xy [V][2N] or NULL (every variant keeps the uploaded coordinates); material [V][3] =
+ *   E, nu, thickness or NULL (the uploaded material); u_in, f_in [V][2N] each or both NULL (the uploaded values).  At least one
+ *   of the three must be given.  MAG_ERR_BAD_ARGS, with the first offender in mag_last_error: a material mag_upload would
+ *   refuse; a variant in which an element's signed area differs in sign from the uploaded mesh's or is zero (the shared ring
+ *   tables assume the uploaded orientation).  A new mag_upload drops the variants.  Load cases and variants are independent
+ *   sets of one context: setting or running one does not drop the other.
+ * mag_run_variants, mag_download_variant, mag_get_variant_stats, mag_get_variants_info: as mag_run_cases ... mag_get_cases_info
+ *   (status, the one redo of a variant whose group timed out or that stopped at the iteration cap with an earlier best iterate,
+ *   history_len / verbose for variant 0 only, single-case results gone afterwards, info[0..3] = variants, per on-chip launch
+ *   (0: one after another), launches, redone).  In a side-by-side run ms_element is the coordinate permutation, ms_assemble,
+ *   ms_bc (right-hand sides and edge blocks) and ms_post the phases of all chunks together, ms_cg the variant's own launch.
+ * Errors before any HIP call as for load cases; a context with more than one rank is refused. */
+int mag_set_variants(mag_ctx *ctx, int32_t num_variants, const double *xy, const double *material, const double *u_in,
+                     const double *f_in, int32_t memory);
+int mag_run_variants(mag_ctx *ctx);
+int mag_download_variant(mag_ctx *ctx, int32_t v, mag_result *result);
+int mag_get_variant_stats(const mag_ctx *ctx, int32_t v, mag_stats *stats);
+int mag_get_variants_info(const mag_ctx *ctx, int32_t info[4]);
+
 /* ---- pieces of the path, exposed for parity tests -------------------- */
 /* solver.rs:187-193 compute_element_area (pub; the mesher imports it, mesher.rs:9,523). Host-side. */
 double mag_compute_element_area(const double *xy, const int32_t *tri);
@@ -275,6 +309,9 @@ int mag_element_stiffness(mag_ctx *ctx, double *ke_out);
 /* solver.rs:290-331: K (2N x 2N) in CSR, ascending columns, structural pattern.
  * Call once with all outputs NULL to get nnz, then with host buffers rowptr[2N+1], col[nnz], val[nnz]. */
 int mag_assemble_csr(mag_ctx *ctx, int64_t *nnz, int32_t *rowptr, int32_t *col, double *val);
+/* The same for variant v of mag_set_variants (test only): K of that variant's coordinates and material in the pattern of the
+ * uploaded mesh, assembled by the kernels mag_run_variants runs for a chunk. */
+int mag_assemble_csr_variant(mag_ctx *ctx, int32_t v, int64_t *nnz, int32_t *rowptr, int32_t *col, double *val);
 /* solver.rs:365-404,427-432,123-137: K_ff with exact zeros dropped + b, compact unknown numbering.
  * Same two-call pattern: rowptr[n_free+1], col[nnz_ff], val[nnz_ff], b[n_free]. */
 int mag_reduce_system(mag_ctx *ctx, int64_t *n_free, int64_t *nnz_ff, int32_t *rowptr, int32_t *col,

@@ -235,5 +235,90 @@ inline Result run_cases(std::vector<std::vector<Node>> &cases, const std::vector
     return std::nullopt;
 }
 
+// Design variants (mag_set_variants / mag_run_variants): the same part -- `nodes` and `elements`, which give the ordering every
+// variant shares and stay untouched -- in several shapes and materials.  shapes: empty (every variant keeps the vertices of
+// `nodes`) or one vertex list per variant; materials: empty (model_metadata for every variant) or one ModelMetadata per variant;
+// at least one of the two is given, and both agree on the number of variants.  The prescribed values are those of `nodes`.
+// Afterwards results[v][i].ux/uy/fx/fy hold variant v's values (vertex: the variant's) and stress[v][e] element e's stress.
+// info_out: mag_get_variants_info's four words.
+inline Result run_variants(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                           const std::vector<std::vector<Vertex>> &shapes, const std::vector<ModelMetadata> &materials,
+                           std::vector<std::vector<Node>> &results, std::vector<std::vector<double>> &stress,
+                           const mag_options *options = nullptr, std::vector<mag_stats> *stats_out = nullptr,
+                           std::int32_t *info_out = nullptr)
+{
+    auto err = detail::solver_error;
+    const std::size_t V = shapes.empty() ? materials.size() : shapes.size(), N = nodes.size(), E = elements.size();
+    if (V == 0) return err("no variant: give shapes, materials or both");
+    if (!shapes.empty() && !materials.empty() && shapes.size() != materials.size())
+        return err("shapes and materials disagree on the number of variants");
+    std::vector<double> xy, u_in(2 * N), f_in(2 * N), u(2 * N), f(2 * N), vxy, vmat;
+    std::vector<std::uint8_t> u_known;
+    std::vector<std::int32_t> conn;
+    if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
+    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
+    for (std::size_t v = 0; v < shapes.size(); ++v) {
+        if (shapes[v].size() != N) return err("variant " + std::to_string(v) + " has another number of vertices");
+        for (const Vertex &p : shapes[v]) {
+            vxy.push_back(p.x);
+            vxy.push_back(p.y);
+        }
+    }
+    for (const ModelMetadata &m : materials) {
+        vmat.push_back(m.youngs_modulus);
+        vmat.push_back(m.poisson_ratio);
+        vmat.push_back(m.part_thickness);
+    }
+    mag_ctx *ctx = mag_create(options);
+    if (!ctx) return err("mag_create failed");
+    auto fail = [&]() {
+        Result e = err(mag_last_error(ctx));
+        mag_destroy(ctx);
+        return e;
+    };
+    mag_problem p{};
+    p.num_nodes = (std::int64_t)N;
+    p.num_elements = (std::int64_t)E;
+    p.xy = xy.data();
+    p.conn = conn.data();
+    p.u_known = u_known.data();
+    p.u_in = u_in.data();
+    p.f_in = f_in.data();
+    p.youngs_modulus = model_metadata.youngs_modulus;
+    p.poisson_ratio = model_metadata.poisson_ratio;
+    p.part_thickness = model_metadata.part_thickness;
+    p.memory = MAG_MEM_HOST;
+    if (mag_upload(ctx, &p) != MAG_OK) return fail();
+    if (mag_set_variants(ctx, (std::int32_t)V, shapes.empty() ? nullptr : vxy.data(), materials.empty() ? nullptr : vmat.data(),
+                         nullptr, nullptr, MAG_MEM_HOST) != MAG_OK)
+        return fail();
+    const int rc = mag_run_variants(ctx);
+    if (rc != MAG_OK && rc != MAG_ERR_NOT_CONVERGED) return fail();
+    const std::string run_message = mag_last_error(ctx);
+    if (stats_out) stats_out->assign(V, mag_stats{});
+    if (info_out) mag_get_variants_info(ctx, info_out);
+    stress.assign(V, std::vector<double>(E));
+    results.assign(V, nodes);
+    for (std::size_t v = 0; v < V; ++v) {
+        mag_result r{};
+        r.u_out = u.data();
+        r.f_out = f.data();
+        r.stress_out = stress[v].data();
+        r.memory = MAG_MEM_HOST;
+        if (mag_download_variant(ctx, (std::int32_t)v, &r) != MAG_OK) return fail();
+        if (stats_out) mag_get_variant_stats(ctx, (std::int32_t)v, &(*stats_out)[v]);
+        for (std::size_t i = 0; i < N; ++i) {
+            if (!shapes.empty()) results[v][i].vertex = shapes[v][i];
+            results[v][i].ux = u[2 * i];
+            results[v][i].uy = u[2 * i + 1];
+            results[v][i].fx = f[2 * i];
+            results[v][i].fy = f[2 * i + 1];
+        }
+    }
+    mag_destroy(ctx);
+    if (rc != MAG_OK) return err(run_message); // a variant broke down: the others hold their results
+    return std::nullopt;
+}
+
 }  // namespace solver
 }  // namespace magnetite

@@ -29,6 +29,8 @@ SYMBOLS = [
     "mag_compute_strain_displacement_matrix", "mag_compute_stress_strain_matrix",
     "mag_element_stiffness", "mag_assemble_csr", "mag_reduce_system", "mag_apply_operator", "mag_time_operator", "mag_time_spmv",
     "mag_set_load_cases", "mag_run_cases", "mag_download_case", "mag_get_case_stats", "mag_get_cases_info",
+    "mag_set_variants", "mag_run_variants", "mag_download_variant", "mag_get_variant_stats", "mag_get_variants_info",
+    "mag_assemble_csr_variant",
     "mag_comm_get_unique_id", "mag_comm_init_rccl", "mag_comm_query", "mag_comm_init_callback", "mag_comm_set_window", "mag_comm_inbox_create", "mag_comm_inbox_open",
 ]
 
@@ -136,6 +138,12 @@ def lib():
     L.mag_download_case.argtypes = [vp, C.c_int32, C.POINTER(Result)]
     L.mag_get_case_stats.argtypes = [vp, C.c_int32, C.POINTER(Stats)]
     L.mag_get_cases_info.argtypes = [vp, ip]
+    L.mag_set_variants.argtypes = [vp, C.c_int32, dp, dp, dp, dp, C.c_int32]
+    L.mag_run_variants.argtypes = [vp]
+    L.mag_download_variant.argtypes = [vp, C.c_int32, C.POINTER(Result)]
+    L.mag_get_variant_stats.argtypes = [vp, C.c_int32, C.POINTER(Stats)]
+    L.mag_get_variants_info.argtypes = [vp, ip]
+    L.mag_assemble_csr_variant.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), ip, ip, dp]
     L.mag_compute_element_area.argtypes = [dp, ip]
     L.mag_compute_element_area.restype = C.c_double
     L.mag_compute_strain_displacement_matrix.argtypes = [dp, ip, C.c_double, dp]

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <array>
 #include <cstring>
+#include <functional>
 #include <initializer_list>
 #include <map>
 #include <mutex>
@@ -206,6 +207,21 @@ struct mag_ctx {
     DevBuf c_uin, c_fin, c_keep, c_bP, c_x, c_u, c_f, c_stress, c_qx, c_part, c_sync, c_state;
     std::vector<mag_stats> case_stats;
     int32_t cases_info[4] = {};
+
+    // design variants (mag_set_variants / mag_run_variants): num_variants shapes / materials / value sets of the uploaded mesh.
+    // Inputs and results variant after variant (v_xy, v_uin / v_fin only when given; v_mat: E, nu, thickness; v_cmat: the CG
+    // kernels' c0, nu, h); the per-variant OPERATOR data -- permuted coordinates, K values, edge blocks, overflow records --
+    // for the variants of ONE chunk only
+    int32_t num_variants = 0;
+    bool have_variants = false, have_variants_run = false, v_have_xy = false, v_have_loads = false;
+    DevBuf v_xy, v_uin, v_fin, v_mat, v_cmat, v_bad, v_keep;
+    DevBuf v_xyP, v_halo, v_kval, v_kblocks, v_ovf;
+    DevBuf v_bP, v_x, v_u, v_f, v_stress;
+    std::vector<double> v_mat_h; // [num_variants][3] = E, nu, thickness
+    std::vector<mag_stats> variant_stats;
+    int32_t variants_info[4] = {};
+    int32_t ovf_total = 0; // overflow records of the whole mesh (choose_edge_blocks)
+    hipEvent_t evV[7] = {}; // phase boundaries of a chunk (created by the first mag_run_variants)
 
     magc::Comm comm;
 };
@@ -1422,6 +1438,7 @@ int choose_edge_blocks(mag_ctx *ctx, bool mg, magk::PersistParams &P, int &mode)
     }
     mode = 2;
     P.pool_cap = pool;
+    ctx->ovf_total = lim[2];
     HIPCHK(ctx->ovf_rec.reserve(32 * (size_t)std::max(lim[2], 1)));
     P.row_info = ctx->row_info.as<uint8_t>();
     P.ovf_off = ctx->ovf_off.as<int32_t>();
@@ -1461,8 +1478,9 @@ void persist_common_params(mag_ctx *ctx, bool mg, magk::PersistParams &P)
 }
 
 // the instantiation for this mesh (mag_stats.edge_blocks), the nodes read through memory, the nodes' blocks: once per solve --
-// or once for all load cases: none of it depends on the prescribed values
-int persist_prepare_blocks(mag_ctx *ctx, bool mg, magk::PersistParams &P, int &eb_mode)
+// or once for all load cases: none of it depends on the prescribed values.  build = false (design variants): the instantiation and
+// the marks only -- they follow from the ring tables --, the caller builds every variant's blocks from its own coordinates
+int persist_prepare_blocks(mag_ctx *ctx, bool mg, magk::PersistParams &P, int &eb_mode, bool build = true)
 {
     hipStream_t s = ctx->stream;
     eb_mode = 0;
@@ -1472,7 +1490,7 @@ int persist_prepare_blocks(mag_ctx *ctx, bool mg, magk::PersistParams &P, int &e
     // nothing on this GPU; what other ranks read goes through the inboxes)
     magk::mark_external(ctx->halo_g.as<int32_t>(), ctx->tmeta.as<magk::TileMeta>(), ctx->t0, ctx->t1, ctx->B, ctx->persist_k,
                         ctx->maskP.as<uint8_t>(), eb_mode == 2, s);
-    if (eb_mode) { // the nodes' blocks, once per solve (18 doubles per node of the padded order, value-major)
+    if (eb_mode && build) { // the nodes' blocks, once per solve (18 doubles per node of the padded order, value-major)
         const int64_t npad = (int64_t)ctx->T * ctx->B;
         HIPCHK(ctx->kblocks.reserve(8 * (size_t)(3 * magk::persist_block_entries()) * (size_t)npad));
         P.kblocks = ctx->kblocks.as<double>();
@@ -1950,6 +1968,8 @@ void mag_destroy(mag_ctx *ctx)
         if (ctx->h_fstate) (void)hipHostFree(ctx->h_fstate);
         for (int i = 0; i < 10; ++i)
             if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
+        for (int i = 0; i < 7; ++i)
+            if (ctx->evV[i]) (void)hipEventDestroy(ctx->evV[i]);
         for (int i = 0; i < 2; ++i)
             if (ctx->evPoll[i]) (void)hipEventDestroy(ctx->evPoll[i]);
         if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -2128,6 +2148,8 @@ int mag_upload(mag_ctx *ctx, const mag_problem *p)
     ctx->have_order = ctx->have_csr = ctx->have_run = false;
     ctx->have_cases = ctx->have_cases_run = false; // load cases belong to the mesh and mask they were set for
     ctx->num_cases = 0;
+    ctx->have_variants = ctx->have_variants_run = false; // ... and so do design variants
+    ctx->num_variants = 0;
     return MAG_OK;
 }
 
@@ -2276,15 +2298,11 @@ struct KeepLoads {
     }
 };
 
-// one case through the single-case CG phases (cg_solve: the phase the options select, its time-out fall-back, best_param):
-// its loads and right-hand side into the context's buffers, its solution out of them.  history_len and verbose are case 0's.
-int solve_case_alone(mag_ctx *ctx, int32_t c, mag_stats &out, bool timed_out_before)
+// cg_solve for the right-hand side in ctx->bP as member c of a set (a load case, a design variant): history_len and verbose are
+// member 0's; `out` gets the solve's statistics (the stream is idle afterwards)
+int cg_solve_member(mag_ctx *ctx, int32_t c, mag_stats &out, bool timed_out_before)
 {
     hipStream_t s = ctx->stream;
-    const size_t vb = 16 * (size_t)ctx->N;
-    HIPCHK(hipMemcpyAsync(ctx->uin.p, ctx->c_uin.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(ctx->fin.p, ctx->c_fin.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(ctx->bP.p, ctx->c_bP.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
     const int32_t hist_len = ctx->opt.history_len, verbose = ctx->opt.verbose;
     if (c != 0) ctx->opt.history_len = ctx->opt.verbose = 0;
     ctx->stats = {};
@@ -2294,10 +2312,6 @@ int solve_case_alone(mag_ctx *ctx, int32_t c, mag_stats &out, bool timed_out_bef
     ctx->opt.verbose = verbose;
     if (rc) return rc;
     HIPCHK(hipEventRecord(ctx->ev[9], s));
-    if (ctx->opt.cg_operator == MAG_OP_CSR)
-        HIPCHK(hipMemcpyAsync(ctx->c_u.as<char>() + vb * c, ctx->u.p, vb, hipMemcpyDeviceToDevice, s));
-    else
-        HIPCHK(hipMemcpyAsync(ctx->c_x.as<char>() + vb * c, ctx->x.p, vb, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
     out = ctx->stats;
     out.ms_cg = ev_ms(ctx->ev[8], ctx->ev[9]);
@@ -2307,6 +2321,106 @@ int solve_case_alone(mag_ctx *ctx, int32_t c, mag_stats &out, bool timed_out_bef
     out.edge_blocks = ctx->cg_kernel == 2 ? ctx->edge_blocks : 0;
     out.tiles_per_workgroup = ctx->cg_kernel == 2 ? ctx->persist_k : 0;
     return MAG_OK;
+}
+
+// one case through the single-case CG phases (cg_solve: the phase the options select, its time-out fall-back, best_param):
+// its loads and right-hand side into the context's buffers, its solution out of them.
+int solve_case_alone(mag_ctx *ctx, int32_t c, mag_stats &out, bool timed_out_before)
+{
+    hipStream_t s = ctx->stream;
+    const size_t vb = 16 * (size_t)ctx->N;
+    HIPCHK(hipMemcpyAsync(ctx->uin.p, ctx->c_uin.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->fin.p, ctx->c_fin.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->bP.p, ctx->c_bP.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
+    if (int rc = cg_solve_member(ctx, c, out, timed_out_before)) return rc;
+    if (ctx->opt.cg_operator == MAG_OP_CSR)
+        HIPCHK(hipMemcpyAsync(ctx->c_u.as<char>() + vb * c, ctx->u.p, vb, hipMemcpyDeviceToDevice, s));
+    else
+        HIPCHK(hipMemcpyAsync(ctx->c_x.as<char>() + vb * c, ctx->x.p, vb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
+// ONE launch of the load-case kernel (or of its design-variant form) for members [c0, c0 + n) of a set: P carries the members'
+// bP and x and what they share; their granules, records, timeout words and states are the context's launch buffers.  Afterwards
+// every member's CG statistics are in stats[c0 + k]; a member whose group gave up at its barrier (timed_out) or that stopped at
+// the iteration cap with an earlier best iterate is marked `alone`: the caller redoes it through the single-case phases.
+int launch_members(mag_ctx *ctx, magk::PersistParams &P, int32_t G, int32_t c0, int32_t n, int eb_mode, std::vector<mag_stats> &stats,
+                   std::vector<uint8_t> &alone, std::vector<uint8_t> &timed_out, const std::function<void()> &launch)
+{
+    using magk::FusedState;
+    hipStream_t s = ctx->stream;
+    const size_t qg_bytes = 2 * 32 * (size_t)ctx->N, rec_bytes = 2 * 64 * (size_t)G;
+    HIPCHK(ctx->c_qx.reserve(qg_bytes * n));
+    HIPCHK(ctx->c_part.reserve(rec_bytes * n));
+    HIPCHK(ctx->c_sync.reserve(64 * (size_t)n));
+    HIPCHK(ctx->c_state.reserve(sizeof(FusedState) * (size_t)n));
+    std::vector<FusedState> h_st((size_t)n);
+    std::vector<uint32_t> h_sync(16 * (size_t)n);
+    // tags of a previous launch must not look current: zeroed before EVERY launch, as cg_phase_persist does
+    HIPCHK(hipMemsetAsync(ctx->c_qx.p, 0, qg_bytes * n, s));
+    HIPCHK(hipMemsetAsync(ctx->c_part.p, 0, rec_bytes * n, s));
+    HIPCHK(hipMemsetAsync(ctx->c_sync.p, 0, 64 * (size_t)n, s));
+    HIPCHK(hipMemsetAsync(ctx->c_state.p, 0, sizeof(FusedState) * (size_t)n, s));
+    P.qg = ctx->c_qx.as<unsigned long long>();
+    P.recg = ctx->c_part.as<unsigned long long>();
+    P.sync = ctx->c_sync.as<uint32_t>();
+    P.st = ctx->c_state.as<FusedState>();
+    P.hist_len = c0 == 0 ? ctx->opt.history_len : 0; // (member 0's alone: the kernel keeps it from the launch's other members)
+    HIPCHK(hipEventRecord(ctx->ev[8], s));
+    launch();
+    HIPCHK(hipEventRecord(ctx->ev[9], s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_st.data(), ctx->c_state.p, sizeof(FusedState) * (size_t)n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_sync.data(), ctx->c_sync.p, 64 * (size_t)n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const double ms = ev_ms(ctx->ev[8], ctx->ev[9]);
+    for (int32_t k = 0; k < n; ++k) {
+        const FusedState &st = h_st[(size_t)k];
+        mag_stats &cs = stats[(size_t)(c0 + k)];
+        cs.ms_cg = ms;
+        if (h_sync[16 * (size_t)k + 9] != 0 || !st.done) { // this member's group gave up at its barrier
+            alone[(size_t)(c0 + k)] = timed_out[(size_t)(c0 + k)] = 1;
+            continue;
+        }
+        cs.iterations = st.iterations;
+        cs.final_cost = st.final_cost;
+        cs.rhs_norm = std::sqrt(st.bb);
+        cs.converged = st.converged;
+        cs.breakdown = st.breakdown;
+        cs.best_iteration = st.iterations;
+        cs.termination = st.breakdown ? MAG_TERM_BREAKDOWN : (st.converged ? MAG_TERM_TARGET_COST : MAG_TERM_MAX_ITERS);
+        cs.cg_kernel = 2;
+        cs.edge_blocks = eb_mode;
+        cs.tiles_per_workgroup = ctx->persist_k;
+        // the iteration cap with an earlier best iterate: best_param is recovered by the single-case path's repeat
+        if (cs.termination == MAG_TERM_MAX_ITERS && st.best_iter >= 1 && st.best_iter < st.iterations) alone[(size_t)(c0 + k)] = 1;
+    }
+    return MAG_OK;
+}
+
+// what every member of a set reports alike: the shared phases' times, the mesh's figures; the status of the first member that
+// broke down (`what`: "load case" / "variant")
+int finish_member_stats(mag_ctx *ctx, std::vector<mag_stats> &stats, bool csr, const char *what)
+{
+    int status = MAG_OK;
+    for (size_t c = 0; c < stats.size(); ++c) {
+        mag_stats &cs = stats[c];
+        cs.ms_order = ev_ms(ctx->ev[0], ctx->ev[1]); // the shared phases: the same in every member
+        cs.ms_csr_symbolic = ev_ms(ctx->ev[1], ctx->ev[2]);
+        cs.ms_total = ev_ms(ctx->ev[0], ctx->ev[7]);
+        cs.nnz = csr ? 4 * ctx->nb : 0;
+        cs.num_tiles = ctx->T;
+        cs.ell_entries = ctx->ell_total;
+        cs.halo_nodes = ctx->halo_total;
+        cs.max_tile_halo = ctx->max_halo;
+        cs.lds_operator = ctx->use_lds ? 1 : 0;
+        cs.n_free = ctx->nf;
+        if (cs.breakdown && status == MAG_OK)
+            status = fail(ctx, MAG_ERR_NOT_CONVERGED, "%s %d: Conjugate Gradient error: non-finite residual after %lld iterations",
+                          what, (int)c, (long long)cs.iterations);
+    }
+    return status;
 }
 
 } // namespace
@@ -2393,59 +2507,14 @@ int mag_run_cases(mag_ctx *ctx)
     };
     std::vector<uint8_t> alone((size_t)L, per_launch ? 0 : 1), timed_out((size_t)L, 0);
     if (per_launch) {
-        const size_t qg_bytes = 2 * 32 * (size_t)N, rec_bytes = 2 * 64 * (size_t)G;
-        const int32_t nmax = std::min(per_launch, L);
-        HIPCHK(ctx->c_qx.reserve(qg_bytes * nmax));
-        HIPCHK(ctx->c_part.reserve(rec_bytes * nmax));
-        HIPCHK(ctx->c_sync.reserve(64 * (size_t)nmax));
-        HIPCHK(ctx->c_state.reserve(sizeof(FusedState) * (size_t)nmax));
-        std::vector<FusedState> h_st((size_t)nmax);
-        std::vector<uint32_t> h_sync(16 * (size_t)nmax);
         for (int32_t c0 = 0; c0 < L; c0 += per_launch) {
             const int32_t n = std::min(per_launch, L - c0);
-            // tags of a previous launch must not look current: zeroed before EVERY launch, as cg_phase_persist does
-            HIPCHK(hipMemsetAsync(ctx->c_qx.p, 0, qg_bytes * n, s));
-            HIPCHK(hipMemsetAsync(ctx->c_part.p, 0, rec_bytes * n, s));
-            HIPCHK(hipMemsetAsync(ctx->c_sync.p, 0, 64 * (size_t)n, s));
-            HIPCHK(hipMemsetAsync(ctx->c_state.p, 0, sizeof(FusedState) * (size_t)n, s));
             P.bP = (const double2 *)at(ctx->c_bP, vb, c0);
             P.x = (double2 *)at(ctx->c_x, vb, c0);
-            P.qg = ctx->c_qx.as<unsigned long long>();
-            P.recg = ctx->c_part.as<unsigned long long>();
-            P.sync = ctx->c_sync.as<uint32_t>();
-            P.st = ctx->c_state.as<FusedState>();
-            P.hist_len = c0 == 0 ? ctx->opt.history_len : 0; // (case 0's alone: the kernel keeps it from the launch's other cases)
-            HIPCHK(hipEventRecord(ctx->ev[8], s));
-            magk::persist_launch_cases(P, ctx->B, G, n, eb_mode, s);
-            HIPCHK(hipEventRecord(ctx->ev[9], s));
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(h_st.data(), ctx->c_state.p, sizeof(FusedState) * (size_t)n, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(h_sync.data(), ctx->c_sync.p, 64 * (size_t)n, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
+            if (int rc = launch_members(ctx, P, G, c0, n, eb_mode, ctx->case_stats, alone, timed_out,
+                                        [&] { magk::persist_launch_cases(P, ctx->B, G, n, eb_mode, s); }))
+                return rc;
             ++info[2];
-            const double ms = ev_ms(ctx->ev[8], ctx->ev[9]);
-            for (int32_t k = 0; k < n; ++k) {
-                const FusedState &st = h_st[(size_t)k];
-                mag_stats &cs = ctx->case_stats[(size_t)(c0 + k)];
-                cs.ms_cg = ms;
-                if (h_sync[16 * (size_t)k + 9] != 0 || !st.done) { // this case's group gave up at its barrier
-                    alone[(size_t)(c0 + k)] = timed_out[(size_t)(c0 + k)] = 1;
-                    continue;
-                }
-                cs.iterations = st.iterations;
-                cs.final_cost = st.final_cost;
-                cs.rhs_norm = std::sqrt(st.bb);
-                cs.converged = st.converged;
-                cs.breakdown = st.breakdown;
-                cs.best_iteration = st.iterations;
-                cs.termination = st.breakdown ? MAG_TERM_BREAKDOWN : (st.converged ? MAG_TERM_TARGET_COST : MAG_TERM_MAX_ITERS);
-                cs.cg_kernel = 2;
-                cs.edge_blocks = eb_mode;
-                cs.tiles_per_workgroup = ctx->persist_k;
-                // the iteration cap with an earlier best iterate: best_param is recovered by the single-case path's repeat
-                if (cs.termination == MAG_TERM_MAX_ITERS && st.best_iter >= 1 && st.best_iter < st.iterations)
-                    alone[(size_t)(c0 + k)] = 1;
-            }
         }
         ctx->cg_kernel = 2;
     }
@@ -2475,27 +2544,13 @@ int mag_run_cases(mag_ctx *ctx)
     HIPCHK(hipStreamSynchronize(s));
     if (ctx->opt.verbose) printf("info: solve complete\n");
 
-    int status = MAG_OK;
-    for (int32_t c = 0; c < L; ++c) {
-        mag_stats &cs = ctx->case_stats[(size_t)c];
-        cs.ms_order = ev_ms(ctx->ev[0], ctx->ev[1]); // the shared phases: the same in every case
-        cs.ms_csr_symbolic = ev_ms(ctx->ev[1], ctx->ev[2]);
+    for (mag_stats &cs : ctx->case_stats) {
         cs.ms_element = 0.0;
         cs.ms_assemble = ev_ms(ctx->ev[2], ctx->ev[4]);
-        cs.ms_bc = ev_ms(ctx->ev[4], ctx->ev[5]); // all cases' right-hand sides / post-processing / the whole run
+        cs.ms_bc = ev_ms(ctx->ev[4], ctx->ev[5]); // all cases' right-hand sides / post-processing
         cs.ms_post = ev_ms(ctx->ev[6], ctx->ev[7]);
-        cs.ms_total = ev_ms(ctx->ev[0], ctx->ev[7]);
-        cs.nnz = csr ? 4 * ctx->nb : 0;
-        cs.num_tiles = ctx->T;
-        cs.ell_entries = ctx->ell_total;
-        cs.halo_nodes = ctx->halo_total;
-        cs.max_tile_halo = ctx->max_halo;
-        cs.lds_operator = ctx->use_lds ? 1 : 0;
-        cs.n_free = ctx->nf;
-        if (cs.breakdown && status == MAG_OK)
-            status = fail(ctx, MAG_ERR_NOT_CONVERGED, "load case %d: Conjugate Gradient error: non-finite residual after %lld iterations",
-                          (int)c, (long long)cs.iterations);
     }
+    const int status = finish_member_stats(ctx, ctx->case_stats, csr, "load case");
     ctx->stats = ctx->case_stats[0];
     ctx->have_cases_run = true;
     return status;
@@ -2537,6 +2592,454 @@ int mag_get_cases_info(const mag_ctx *ctx, int32_t info[4])
     return MAG_OK;
 }
 
+// ---- design variants: num_variants shapes / materials / value sets of the uploaded mesh (same connectivity and u_known mask) ----
+namespace {
+
+const char *material_error(const double *m) // E, nu, thickness: mag_upload's check
+{
+    return !(m[1] * m[1] != 1.0) ? "poisson_ratio^2 == 1" : nullptr;
+}
+
+int variants_refused(mag_ctx *ctx)
+{
+    if (ctx->comm.nranks > 1)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "variants run on one GPU: this context has a communicator of %d ranks", ctx->comm.nranks);
+    return MAG_OK;
+}
+
+} // namespace
+
+int mag_set_variants(mag_ctx *ctx, int32_t num_variants, const double *xy, const double *material, const double *u_in,
+                     const double *f_in, int32_t memory)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (num_variants < 1) return fail(ctx, MAG_ERR_BAD_ARGS, "num_variants = %d: at least one variant", (int)num_variants);
+    if ((u_in == nullptr) != (f_in == nullptr)) return fail(ctx, MAG_ERR_BAD_ARGS, "variants: u_in and f_in come together, or both null");
+    if (!xy && !material && !u_in)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "variants: at least one of xy, material and the value pair must be given");
+    if (int rc = variants_refused(ctx)) return rc;
+    const int32_t V = num_variants;
+    std::vector<double> mat(3 * (size_t)V);
+    auto check_materials = [&]() -> int {
+        for (int32_t v = 0; v < V; ++v)
+            if (const char *why = material_error(&mat[3 * (size_t)v]))
+                return fail(ctx, MAG_ERR_BAD_ARGS, "variant %d: %s", (int)v, why);
+        return MAG_OK;
+    };
+    if (material && memory != MAG_MEM_DEVICE) { // host values: checked before anything else is looked at
+        memcpy(mat.data(), material, 8 * mat.size());
+        if (int rc = check_materials()) return rc;
+    }
+    if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "mag_set_variants before mag_upload");
+    if (int rc = enter(ctx)) return rc;
+    ctx->have_variants = ctx->have_variants_run = false;
+    const int64_t N = ctx->N, E = ctx->E;
+    const size_t bytes = 16 * (size_t)N * (size_t)V;
+    const hipMemcpyKind kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    hipStream_t s = ctx->stream;
+    if (material && memory == MAG_MEM_DEVICE) {
+        HIPCHK(hipMemcpyAsync(mat.data(), material, 8 * mat.size(), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (int rc = check_materials()) return rc;
+    }
+    if (!material)
+        for (int32_t v = 0; v < V; ++v) {
+            mat[3 * (size_t)v + 0] = ctx->youngs;
+            mat[3 * (size_t)v + 1] = ctx->nu;
+            mat[3 * (size_t)v + 2] = ctx->thick;
+        }
+    // the CG kernels' constants, by set_material's expressions (the same bits as a solve with that material)
+    std::vector<double> cmat(3 * (size_t)V);
+    for (int32_t v = 0; v < V; ++v) {
+        const double youngs = mat[3 * (size_t)v], nu = mat[3 * (size_t)v + 1], thick = mat[3 * (size_t)v + 2];
+        cmat[3 * (size_t)v + 0] = youngs * thick / (2.0 * (1.0 - nu * nu));
+        cmat[3 * (size_t)v + 1] = nu;
+        cmat[3 * (size_t)v + 2] = (1.0 - nu) / 2.0;
+    }
+    HIPCHK(ctx->v_mat.reserve(8 * mat.size()));
+    HIPCHK(ctx->v_cmat.reserve(8 * cmat.size()));
+    HIPCHK(hipMemcpyAsync(ctx->v_mat.p, mat.data(), 8 * mat.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->v_cmat.p, cmat.data(), 8 * cmat.size(), hipMemcpyHostToDevice, s));
+    if (xy) {
+        HIPCHK(ctx->v_xy.reserve(bytes));
+        HIPCHK(hipMemcpyAsync(ctx->v_xy.p, xy, bytes, kind, s));
+    }
+    if (u_in) {
+        HIPCHK(ctx->v_uin.reserve(bytes));
+        HIPCHK(ctx->v_fin.reserve(bytes));
+        HIPCHK(hipMemcpyAsync(ctx->v_uin.p, u_in, bytes, kind, s));
+        HIPCHK(hipMemcpyAsync(ctx->v_fin.p, f_in, bytes, kind, s));
+    }
+    HIPCHK(hipStreamSynchronize(s)); // (the host vectors and the caller's buffers are done with)
+    if (xy) {
+        // the shared ring tables walk every node's triangles in the uploaded orientation: one reduction over (variant, element)
+        HIPCHK(ctx->v_bad.reserve(8));
+        for (int32_t v0 = 0; v0 < V; v0 += 32768) { // (grid.y holds 65535)
+            const int32_t n = std::min<int32_t>(32768, V - v0);
+            unsigned long long bad = ~0ull;
+            magk::variant_orientation(ctx->xy.as<double>(), ctx->v_xy.as<double>() + 2 * (size_t)N * (size_t)v0,
+                                      ctx->conn.as<int32_t>(), N, E, n, ctx->v_bad.as<unsigned long long>(), s);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(&bad, ctx->v_bad.p, 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            if (bad != ~0ull)
+                return fail(ctx, MAG_ERR_BAD_ARGS,
+                            "variant %lld, element %lld: the signed area differs in sign from the uploaded mesh's or is zero "
+                            "(variants keep the orientation of every element)",
+                            (long long)(v0 + (int64_t)(bad / (unsigned long long)E)), (long long)(bad % (unsigned long long)E));
+        }
+    }
+    ctx->v_mat_h = mat;
+    ctx->v_have_xy = xy != nullptr;
+    ctx->v_have_loads = u_in != nullptr;
+    ctx->num_variants = V;
+    ctx->have_variants = true;
+    return MAG_OK;
+}
+
+namespace {
+
+// the uploaded problem is lent to a variant that runs through the single-case phases (its coordinates, material and values go
+// into the context) and comes back
+struct KeepProblem {
+    mag_ctx *ctx;
+    size_t bytes;
+    double youngs, nu, thick;
+    bool armed = false;
+    ~KeepProblem()
+    {
+        if (!armed) return;
+        hipStream_t s = ctx->stream;
+        (void)hipMemcpyAsync(ctx->xy.p, ctx->v_keep.p, bytes, hipMemcpyDeviceToDevice, s);
+        (void)hipMemcpyAsync(ctx->uin.p, ctx->v_keep.as<char>() + bytes, bytes, hipMemcpyDeviceToDevice, s);
+        (void)hipMemcpyAsync(ctx->fin.p, ctx->v_keep.as<char>() + 2 * bytes, bytes, hipMemcpyDeviceToDevice, s);
+        (void)hipStreamSynchronize(s);
+        ctx->youngs = youngs;
+        ctx->nu = nu;
+        ctx->thick = thick;
+    }
+};
+
+// where variant v's coordinates and values are: its own, or the uploaded ones
+const double *variant_xy(const mag_ctx *ctx, const KeepProblem &keep, int32_t v)
+{
+    if (ctx->v_have_xy) return ctx->v_xy.as<double>() + 2 * (size_t)ctx->N * (size_t)v;
+    return keep.armed ? ctx->v_keep.as<double>() : ctx->xy.as<double>();
+}
+const double *variant_loads(const mag_ctx *ctx, const KeepProblem &keep, int32_t v, bool forces)
+{
+    if (ctx->v_have_loads) return (forces ? ctx->v_fin : ctx->v_uin).as<double>() + 2 * (size_t)ctx->N * (size_t)v;
+    if (keep.armed) return ctx->v_keep.as<double>() + 2 * (size_t)ctx->N * (forces ? 2 : 1);
+    return (forces ? ctx->fin : ctx->uin).as<double>();
+}
+
+// one variant through the single-case phases, the shared tables kept: its coordinates (permuted into xyP and the tiles' halo
+// copies), material and values into the context, then K, right-hand side, cg_solve (its time-out fall-back, its best_param
+// repeat) and post as mag_run runs them.  The caller has armed `keep`.
+int solve_variant_alone(mag_ctx *ctx, const KeepProblem &keep, int32_t v, mag_stats &out, bool timed_out_before)
+{
+    hipStream_t s = ctx->stream;
+    const int64_t N = ctx->N, E = ctx->E;
+    const size_t vb = 16 * (size_t)N, eb = 8 * (size_t)E;
+    const bool csr = ctx->opt.assemble_csr != 0 || ctx->opt.cg_operator == MAG_OP_CSR;
+    HIPCHK(hipMemcpyAsync(ctx->xy.p, variant_xy(ctx, keep, v), vb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->uin.p, variant_loads(ctx, keep, v, false), vb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->fin.p, variant_loads(ctx, keep, v, true), vb, hipMemcpyDeviceToDevice, s));
+    ctx->youngs = ctx->v_mat_h[3 * (size_t)v + 0];
+    ctx->nu = ctx->v_mat_h[3 * (size_t)v + 1];
+    ctx->thick = ctx->v_mat_h[3 * (size_t)v + 2];
+    magk::VariantBatch one = {};
+    one.count = 1;
+    one.halo = ctx->halo_total;
+    magk::variant_coords(ctx->xy.as<double>(), ctx->perm.as<uint32_t>(), ctx->halo_g.as<int32_t>(), N,
+                         ctx->use_lds ? ctx->halo_total : 0, one, ctx->xyP.as<double>(), ctx->halo_xy.as<double>(), s);
+    if (csr) {
+        if (int rc = gather_phase(ctx)) return rc;
+        ctx->have_csr = true;
+    }
+    if (int rc = rhs_phase(ctx, ctx->uin.as<double>(), ctx->fin.as<double>(), ctx->bP.as<double>(), false)) return rc;
+    HIPCHK(hipGetLastError());
+    if (int rc = cg_solve_member(ctx, v, out, timed_out_before)) return rc;
+    if (ctx->opt.cg_operator == MAG_OP_CSR) // (that operator's phase has expanded its solution into the context's u)
+        HIPCHK(hipMemcpyAsync(ctx->v_u.as<char>() + vb * (size_t)v, ctx->u.p, vb, hipMemcpyDeviceToDevice, s));
+    if (int rc = post_phase(ctx, ctx->x.as<double>(), ctx->uin.as<double>(), ctx->fin.as<double>(), ctx->v_u.as<double>() + 2 * (size_t)N * v,
+                            ctx->v_f.as<double>() + 2 * (size_t)N * v, (double *)(ctx->v_stress.as<char>() + eb * (size_t)v)))
+        return rc;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
+} // namespace
+
+int mag_run_variants(mag_ctx *ctx)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (int rc = variants_refused(ctx)) return rc;
+    if (!ctx->have_problem || !ctx->have_variants) return fail(ctx, MAG_ERR_STATE, "mag_run_variants before mag_set_variants");
+    if (int rc = enter(ctx)) return rc;
+    hipStream_t s = ctx->stream;
+    const int64_t N = ctx->N, E = ctx->E;
+    const int32_t V = ctx->num_variants;
+    const size_t vb = 16 * (size_t)N, eb = 8 * (size_t)E;
+    ctx->stats = {};
+    // as in mag_run: the whole path is redone, only allocations are reused; the single-case results of the context are gone
+    ctx->have_order = ctx->have_csr = ctx->have_run = ctx->have_variants_run = false;
+    if (ctx->persist_failed && --ctx->persist_retry_in <= 0) ctx->persist_failed = false;
+    ctx->variant_stats.assign((size_t)V, mag_stats{});
+    int32_t *info = ctx->variants_info;
+    info[0] = V;
+    info[1] = info[2] = info[3] = 0;
+    for (hipEvent_t &e : ctx->evV)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    if (ctx->opt.verbose) printf("info: building element stiffness matrices...\n");
+
+    // ---- once for all variants: the Hilbert order OF THE UPLOADED COORDINATES, incidence, tile, ring and halo tables, masks, the
+    // CSR pattern, the fan classification -- connectivity, mask and that one ordering only ("Design variants")
+    HIPCHK(hipEventRecord(ctx->ev[0], s));
+    if (int rc = ensure_order(ctx)) return rc;
+    HIPCHK(hipEventRecord(ctx->ev[1], s));
+    if (int rc = reserve_cg(ctx)) return rc;
+    const bool csr = ctx->opt.assemble_csr != 0 || ctx->opt.cg_operator == MAG_OP_CSR;
+    if (csr)
+        if (int rc = csr_symbolic(ctx)) return rc;
+    HIPCHK(hipEventRecord(ctx->ev[2], s));
+    HIPCHK(ctx->v_bP.reserve(vb * V));
+    HIPCHK(ctx->v_x.reserve(vb * V));
+    HIPCHK(ctx->v_u.reserve(vb * V));
+    HIPCHK(ctx->v_f.reserve(vb * V));
+    HIPCHK(ctx->v_stress.reserve(eb * V));
+    HIPCHK(ctx->u.reserve(vb));
+    HIPCHK(ctx->f.reserve(vb));
+    HIPCHK(ctx->stress.reserve(eb));
+    if (ctx->opt.verbose) printf("info: solving...\n");
+
+    // ---- side by side: on-chip, K assembled (right-hand side and reactions come from its rows), at least two variants fit the
+    // chip -- the load cases' rule, the load cases' shapes.  Anything else: one variant after another.
+    int cus = 0;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+    const int32_t G = ctx->persist_grid;
+    int32_t per_launch = 0;
+    magk::PersistParams P = {};
+    int eb_mode = 0;
+    if (ctx->persist && csr && ctx->opt.cg_operator != MAG_OP_CSR && ctx->opt.precision == 0 && G >= 1 && cus / G >= 2) {
+        P.nranks = 1;
+        persist_common_params(ctx, false, P);
+        if (int rc = persist_prepare_blocks(ctx, false, P, eb_mode, false)) return rc;
+        if (magk::persist_cases_shape(ctx->B, G, ctx->persist_k, eb_mode)) per_launch = cus / G;
+    }
+    info[1] = per_launch;
+    KeepProblem keep{ctx, vb, ctx->youngs, ctx->nu, ctx->thick};
+    auto lend_problem = [&]() -> int { // before the first variant that runs alone
+        if (keep.armed) return MAG_OK;
+        HIPCHK(ctx->v_keep.reserve(3 * vb));
+        HIPCHK(hipMemcpyAsync(ctx->v_keep.p, ctx->xy.p, vb, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(ctx->v_keep.as<char>() + vb, ctx->uin.p, vb, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(ctx->v_keep.as<char>() + 2 * vb, ctx->fin.p, vb, hipMemcpyDeviceToDevice, s));
+        keep.armed = true;
+        return MAG_OK;
+    };
+    std::vector<uint8_t> alone((size_t)V, per_launch ? 0 : 1), timed_out((size_t)V, 0);
+    double ms_phase[6] = {0, 0, 0, 0, 0, 0}; // permute, assemble, right-hand sides, blocks, launches, post: all chunks
+    if (per_launch) {
+        const int32_t nmax = std::min(per_launch, V);
+        const int64_t npad = (int64_t)ctx->T * ctx->B, halo = std::max<int64_t>(ctx->halo_total, 1);
+        const int64_t kb_words = 3 * (int64_t)magk::persist_block_entries() * npad, ovf_words = 4 * (int64_t)std::max(ctx->ovf_total, 1);
+        HIPCHK(ctx->v_xyP.reserve(vb * nmax));
+        HIPCHK(ctx->v_halo.reserve(16 * (size_t)halo * nmax));
+        HIPCHK(ctx->v_kval.reserve(8 * 4 * (size_t)ctx->nb * nmax));
+        if (eb_mode) HIPCHK(ctx->v_kblocks.reserve(8 * (size_t)kb_words * nmax));
+        if (eb_mode == 2) HIPCHK(ctx->v_ovf.reserve(8 * (size_t)ovf_words * nmax));
+        const char *how = getenv("MAG_TUNE_ASSEMBLY");
+        for (int32_t c0 = 0; c0 < V; c0 += per_launch) {
+            const int32_t n = std::min(per_launch, V - c0);
+            magk::VariantBatch vbat = {};
+            vbat.count = n;
+            vbat.mat = ctx->v_mat.as<double>() + 3 * (size_t)c0;
+            vbat.xy = ctx->v_have_xy ? 2 * N : 0;
+            vbat.loads = ctx->v_have_loads ? 2 * N : 0;
+            vbat.halo = halo;
+            vbat.kval = 4 * ctx->nb;
+            const double *xy = variant_xy(ctx, keep, c0), *uin = variant_loads(ctx, keep, c0, false),
+                         *fin = variant_loads(ctx, keep, c0, true);
+            double *bP = ctx->v_bP.as<double>() + 2 * (size_t)N * c0, *xP = ctx->v_x.as<double>() + 2 * (size_t)N * c0;
+            HIPCHK(hipEventRecord(ctx->evV[0], s));
+            magk::variant_coords(xy, ctx->perm.as<uint32_t>(), ctx->halo_g.as<int32_t>(), N, ctx->halo_total, vbat,
+                                 ctx->v_xyP.as<double>(), ctx->v_halo.as<double>(), s);
+            HIPCHK(hipEventRecord(ctx->evV[1], s));
+            // K values of every variant in the shared pattern: gather_phase's choice of kernel
+            if (!(ctx->asm_ctile && ctx->use_lds && !(how && !strcmp(how, "tiles")) &&
+                  magk::assemble_ctiles_variants(ctx->bcol.as<int32_t>(), ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(),
+                                                 ctx->v_xyP.as<double>(), ctx->v_halo.as<double>(), ctx->tile_hoff.as<int32_t>(),
+                                                 ctx->tile_deg.as<int32_t>(), ctx->tile_off.as<int64_t>(), ctx->ell_asm.as<uint32_t>(),
+                                                 ctx->ell_pos.as<uint16_t>(), ctx->inc_off.as<int32_t>(), ctx->inc.as<uint32_t>(),
+                                                 ctx->conn.as<int32_t>(), xy, N, ctx->B, ctx->T, ctx->cap, vbat,
+                                                 ctx->v_kval.as<double>(), s)))
+                magk::assemble_tiles_variants(ctx->bcol.as<int32_t>(), ctx->bptr.as<int32_t>(), ctx->inc_off.as<int32_t>(),
+                                              ctx->inc.as<uint32_t>(), ctx->perm.as<uint32_t>(), ctx->conn.as<int32_t>(), xy, N, vbat,
+                                              ctx->v_kval.as<double>(), s);
+            HIPCHK(hipEventRecord(ctx->evV[2], s));
+            HIPCHK(ctx->bc_touch.reserve((size_t)N + 16));
+            magk::rhs_variants(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->v_kval.as<double>(), ctx->uknown.as<uint8_t>(), uin,
+                               fin, ctx->perm.as<uint32_t>(), ctx->bc_touch.as<uint8_t>(), ctx->bc_touch_ready, N, vbat, bP, s);
+            HIPCHK(hipEventRecord(ctx->evV[3], s));
+            P.xyP = ctx->v_xyP.as<double2>();
+            P.halo_xy = ctx->v_halo.as<double2>();
+            P.var_mat = ctx->v_cmat.as<double>() + 3 * (size_t)c0;
+            P.var_halo_stride = halo;
+            P.var_kb_stride = kb_words;
+            P.var_ovf_stride = ovf_words;
+            if (eb_mode) {
+                P.kblocks = ctx->v_kblocks.as<double>();
+                P.kb_stride = npad;
+                if (eb_mode == 2) P.ovf_rec = ctx->v_ovf.as<double>();
+                magk::edge_blocks_build_variants(P, ctx->B, eb_mode, n, s);
+            }
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(ctx->evV[4], s));
+            P.bP = (const double2 *)bP;
+            P.x = (double2 *)xP;
+            if (int rc = launch_members(ctx, P, G, c0, n, eb_mode, ctx->variant_stats, alone, timed_out,
+                                        [&] { magk::persist_launch_variants(P, ctx->B, G, n, eb_mode, s); }))
+                return rc;
+            ++info[2];
+            // scatter-back, reactions (this chunk's K) and stress (the variant's geometry and material); a variant that is
+            // redone below gets all three again from its own solve
+            HIPCHK(hipEventRecord(ctx->evV[5], s));
+            magk::post_variants(xP, ctx->perm.as<uint32_t>(), ctx->uknown.as<uint8_t>(), uin, fin, ctx->bptr.as<int32_t>(),
+                                ctx->bcol.as<int32_t>(), ctx->v_kval.as<double>(), xy, ctx->conn.as<int32_t>(), N, E, vbat,
+                                ctx->v_u.as<double>() + 2 * (size_t)N * c0, ctx->v_f.as<double>() + 2 * (size_t)N * c0,
+                                (double *)(ctx->v_stress.as<char>() + eb * (size_t)c0), s);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(ctx->evV[6], s));
+            HIPCHK(hipStreamSynchronize(s));
+            const int pairs[6][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {4, 5}, {5, 6}};
+            for (int k = 0; k < 6; ++k) ms_phase[k] += ev_ms(ctx->evV[pairs[k][0]], ctx->evV[pairs[k][1]]);
+        }
+        ctx->cg_kernel = 2;
+    }
+    bool backed_off = false;
+    for (int32_t v = 0; v < V; ++v) {
+        if (!alone[(size_t)v]) continue;
+        if (timed_out[(size_t)v] && !backed_off) { // the single-case path's bookkeeping: the context streams from here on
+            persist_back_off(ctx);
+            backed_off = true;
+        }
+        if (int rc = lend_problem()) return rc;
+        if (int rc = solve_variant_alone(ctx, keep, v, ctx->variant_stats[(size_t)v], timed_out[(size_t)v] != 0)) return rc;
+        if (per_launch) ++info[3];
+    }
+    if (per_launch && !backed_off) ctx->persist_backoff = 0; // co-resident: the next failure starts from the short wait
+    HIPCHK(hipEventRecord(ctx->ev[7], s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (ctx->opt.verbose) {
+        printf("info: finished conjugate gradient approximation in %lld iterations\n", (long long)ctx->variant_stats[0].iterations);
+        printf("info: solve complete\n");
+    }
+    // side by side: the phases' times summed over the chunks, the same in every variant (ms_element: the coordinate permutation;
+    // ms_cg stays the variant's own launch, the block build is counted with ms_bc) -- one after another: each variant's cg time
+    for (mag_stats &cs : ctx->variant_stats) {
+        cs.ms_element = ms_phase[0];
+        cs.ms_assemble = ms_phase[1];
+        cs.ms_bc = ms_phase[2] + ms_phase[3];
+        cs.ms_post = ms_phase[5];
+    }
+    const int status = finish_member_stats(ctx, ctx->variant_stats, csr, "variant");
+    ctx->stats = ctx->variant_stats[0];
+    // xyP, the halo copies and K may be a variant's: nothing of this run is reused by the entry points that would
+    ctx->have_order = ctx->have_csr = false;
+    ctx->have_variants_run = true;
+    return status;
+}
+
+int mag_download_variant(mag_ctx *ctx, int32_t v, mag_result *r)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!r) return fail(ctx, MAG_ERR_BAD_ARGS, "null result");
+    if (v < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "variant %d out of range", (int)v);
+    if (!ctx->have_variants_run) return fail(ctx, MAG_ERR_STATE, "mag_download_variant before a completed mag_run_variants");
+    if (v >= ctx->num_variants) return fail(ctx, MAG_ERR_BAD_ARGS, "variant %d out of range [0, %d)", (int)v, (int)ctx->num_variants);
+    if (int rc = enter(ctx)) return rc;
+    const hipMemcpyKind kind = r->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    hipStream_t s = ctx->stream;
+    const size_t vb = 16 * (size_t)ctx->N, eb = 8 * (size_t)ctx->E, c = (size_t)v;
+    if (r->u_out) HIPCHK(hipMemcpyAsync(r->u_out, ctx->v_u.as<char>() + vb * c, vb, kind, s));
+    if (r->f_out) HIPCHK(hipMemcpyAsync(r->f_out, ctx->v_f.as<char>() + vb * c, vb, kind, s));
+    if (r->stress_out) HIPCHK(hipMemcpyAsync(r->stress_out, ctx->v_stress.as<char>() + eb * c, eb, kind, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
+int mag_get_variant_stats(const mag_ctx *ctx, int32_t v, mag_stats *st)
+{
+    if (!ctx || !st || v < 0) return MAG_ERR_BAD_ARGS;
+    if (!ctx->have_variants_run) return MAG_ERR_STATE;
+    if (v >= ctx->num_variants) return MAG_ERR_BAD_ARGS;
+    *st = ctx->variant_stats[(size_t)v];
+    return MAG_OK;
+}
+
+int mag_get_variants_info(const mag_ctx *ctx, int32_t info[4])
+{
+    if (!ctx || !info) return MAG_ERR_BAD_ARGS;
+    if (!ctx->have_variants_run) return MAG_ERR_STATE;
+    for (int k = 0; k < 4; ++k) info[k] = ctx->variants_info[k];
+    return MAG_OK;
+}
+
+int mag_assemble_csr_variant(mag_ctx *ctx, int32_t v, int64_t *nnz, int32_t *rowptr, int32_t *col, double *val)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (int rc = variants_refused(ctx)) return rc;
+    if (!ctx->have_problem || !ctx->have_variants) return fail(ctx, MAG_ERR_STATE, "mag_assemble_csr_variant before mag_set_variants");
+    if (v < 0 || v >= ctx->num_variants) return fail(ctx, MAG_ERR_BAD_ARGS, "variant %d out of range [0, %d)", (int)v, (int)ctx->num_variants);
+    if (int rc = enter(ctx)) return rc;
+    hipStream_t s = ctx->stream;
+    // the shared tables and pattern of the uploaded mesh, then the variants' batched assembly for this one variant
+    ctx->have_order = ctx->have_csr = false;
+    if (int rc = ensure_order(ctx)) return rc;
+    if (int rc = csr_symbolic(ctx)) return rc;
+    const int64_t N = ctx->N, nz = 4 * ctx->nb;
+    if (nnz) *nnz = nz;
+    if (rowptr || col) {
+        HIPCHK(ctx->rp_full.reserve(4 * (2 * (size_t)N + 1)));
+        HIPCHK(ctx->col_full.reserve(4 * (size_t)nz));
+        magk::csr_export(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), N, ctx->rp_full.as<int32_t>(), ctx->col_full.as<int32_t>(), s);
+        HIPCHK(hipGetLastError());
+        if (rowptr) HIPCHK(hipMemcpyAsync(rowptr, ctx->rp_full.p, 4 * (2 * (size_t)N + 1), hipMemcpyDeviceToHost, s));
+        if (col) HIPCHK(hipMemcpyAsync(col, ctx->col_full.p, 4 * (size_t)nz, hipMemcpyDeviceToHost, s));
+    }
+    if (val) {
+        const int64_t halo = std::max<int64_t>(ctx->halo_total, 1);
+        magk::VariantBatch vbat = {};
+        vbat.count = 1;
+        vbat.mat = ctx->v_mat.as<double>() + 3 * (size_t)v;
+        vbat.halo = halo;
+        vbat.kval = nz;
+        const double *xy = ctx->v_have_xy ? ctx->v_xy.as<double>() + 2 * (size_t)N * (size_t)v : ctx->xy.as<double>();
+        HIPCHK(ctx->v_xyP.reserve(16 * (size_t)N));
+        HIPCHK(ctx->v_halo.reserve(16 * (size_t)halo));
+        HIPCHK(ctx->v_kval.reserve(8 * (size_t)nz));
+        magk::variant_coords(xy, ctx->perm.as<uint32_t>(), ctx->halo_g.as<int32_t>(), N, ctx->use_lds ? ctx->halo_total : 0, vbat,
+                             ctx->v_xyP.as<double>(), ctx->v_halo.as<double>(), s);
+        const char *how = getenv("MAG_TUNE_ASSEMBLY");
+        if (!(ctx->asm_ctile && ctx->use_lds && !(how && !strcmp(how, "tiles")) &&
+              magk::assemble_ctiles_variants(ctx->bcol.as<int32_t>(), ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(),
+                                             ctx->v_xyP.as<double>(), ctx->v_halo.as<double>(), ctx->tile_hoff.as<int32_t>(),
+                                             ctx->tile_deg.as<int32_t>(), ctx->tile_off.as<int64_t>(), ctx->ell_asm.as<uint32_t>(),
+                                             ctx->ell_pos.as<uint16_t>(), ctx->inc_off.as<int32_t>(), ctx->inc.as<uint32_t>(),
+                                             ctx->conn.as<int32_t>(), xy, N, ctx->B, ctx->T, ctx->cap, vbat, ctx->v_kval.as<double>(), s)))
+            magk::assemble_tiles_variants(ctx->bcol.as<int32_t>(), ctx->bptr.as<int32_t>(), ctx->inc_off.as<int32_t>(),
+                                          ctx->inc.as<uint32_t>(), ctx->perm.as<uint32_t>(), ctx->conn.as<int32_t>(), xy, N, vbat,
+                                          ctx->v_kval.as<double>(), s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(val, ctx->v_kval.p, 8 * (size_t)nz, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    ctx->have_csr = false; // (no K of the uploaded problem was assembled)
+    return MAG_OK;
+}
+
 int mag_solve(mag_ctx *ctx, const mag_problem *p, mag_result *r)
 {
     if (int rc = mag_upload(ctx, p)) return rc;
@@ -2560,7 +3063,7 @@ int mag_get_stats(const mag_ctx *ctx, mag_stats *st)
 int mag_get_history(mag_ctx *ctx, double *history, int64_t n)
 {
     if (int rc = enter(ctx)) return rc;
-    if (!ctx->have_run && !ctx->have_cases_run) return fail(ctx, MAG_ERR_STATE, "no completed run");
+    if (!ctx->have_run && !ctx->have_cases_run && !ctx->have_variants_run) return fail(ctx, MAG_ERR_STATE, "no completed run");
     if (n < 0 || n > ctx->opt.history_len || n > ctx->stats.iterations || (n > 0 && !history))
         return fail(ctx, MAG_ERR_BAD_ARGS, "history length %lld not available", (long long)n);
     if (n > 0) HIPCHK(hipMemcpy(history, ctx->hist.p, 8 * (size_t)n, hipMemcpyDeviceToHost));

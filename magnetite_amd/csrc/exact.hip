@@ -199,7 +199,8 @@ __device__ inline void asm_entry(const int32_t (&nn)[3], int a, const double2 v0
     }
 }
 
-__global__ void __launch_bounds__(kAsmNodes) k_assemble_tiles(const int32_t *bcol, const int32_t *bptr,
+__global__ void __launch_bounds__(kAsmNodes) k_assemble_tiles(const int32_t *bcol, const int32_t *bptr, const int32_t *inc_off, const uint32_t *inc, const uint32_t *perm, const int32_t *conn, const double2 *xy, int64_t N, double nu, double youngs, double thick, double *kval); // (end of the file: d_assemble_tiles on the single-case arrays)
+__device__ __forceinline__ void d_assemble_tiles(const int32_t *bcol, const int32_t *bptr,
                                                                const int32_t *inc_off, const uint32_t *inc,
                                                                const uint32_t *perm, const int32_t *conn,
                                                                const double2 *xy, int64_t N, double nu, double youngs,
@@ -481,7 +482,9 @@ constexpr int kFanLanes = 8;     // lanes (triangles, columns) per node
 constexpr int kFanStage = 20;    // 16-byte pieces of staging per node: two rows of at most ten blocks
 
 template <int B>
-__global__ void __launch_bounds__(kFanThreads) k_assemble_fan(const int32_t *bcol, const int32_t *bptr, const uint32_t *perm,
+__global__ void __launch_bounds__(kFanThreads) k_assemble_fan(const int32_t *bcol, const int32_t *bptr, const uint32_t *perm, const double2 *xyP, const double2 *halo_xy, const int32_t *tile_hoff, const int32_t *tile_deg, const int64_t *tile_off, const uint32_t *ell_asm, const uint16_t *ell_pos, const int32_t *inc_off, const uint32_t *inc, const int32_t *conn, const double2 *xy, int64_t N, int32_t cap, int32_t img_pieces, int32_t segs, int32_t six, double nu, double youngs, double thick, double *kval); // (end of the file: d_assemble_fan on the single-case arrays)
+template <int B>
+__device__ __forceinline__ void d_assemble_fan(const int32_t *bcol, const int32_t *bptr, const uint32_t *perm,
                                                               const double2 *xyP, const double2 *halo_xy,
                                                               const int32_t *tile_hoff, const int32_t *tile_deg,
                                                               const int64_t *tile_off, const uint32_t *ell_asm,
@@ -822,7 +825,8 @@ __global__ void __launch_bounds__(256) k_mark_bc_rows(const int32_t *bptr, const
 
 // One thread per node of the HILBERT order (b is written in that order: one coalesced 16-byte store per node; the caller-order
 // inputs are gathered -- scattered 8-byte stores through the permutation cost more than the whole row sums).
-__global__ void __launch_bounds__(256) k_rhs_from_csr(const int32_t *bptr, const int32_t *bcol, const double *kval,
+__global__ void __launch_bounds__(256) k_rhs_from_csr(const int32_t *bptr, const int32_t *bcol, const double *kval, const uint8_t *u_known, const double *u_in, const double *f_in, const uint32_t *perm, const uint8_t *touch, bool hilbert_flags, int64_t N, double2 *bP); // (end of the file: d_rhs_from_csr on the single-case arrays)
+__device__ __forceinline__ void d_rhs_from_csr(const int32_t *bptr, const int32_t *bcol, const double *kval,
                                                       const uint8_t *u_known, const double *u_in, const double *f_in,
                                                       const uint32_t *perm, const uint8_t *touch, bool hilbert_flags,
                                                       int64_t N, double2 *bP)
@@ -843,7 +847,8 @@ __global__ void __launch_bounds__(256) k_rhs_from_csr(const int32_t *bptr, const
 // permutation (symbolic.hip, k_apply_order).  Only the rows that have a prescribed column need K: the pattern kernel flags
 // them in Hilbert order (one coalesced byte per thread here; O(sqrt N) rows do the work, the others leave at once).  Round 3's
 // kernel gathered flag, mask and forces of EVERY node by caller id: 17.6 us at 1M triangles, three times the row sums.
-__global__ void __launch_bounds__(256) k_rhs_touched(const int32_t *bptr, const int32_t *bcol, const double *kval,
+__global__ void __launch_bounds__(256) k_rhs_touched(const int32_t *bptr, const int32_t *bcol, const double *kval, const uint8_t *u_known, const double *u_in, const double *f_in, const uint32_t *perm, const uint8_t *touch, int64_t N, double2 *bP); // (end of the file: d_rhs_touched on the single-case arrays)
+__device__ __forceinline__ void d_rhs_touched(const int32_t *bptr, const int32_t *bcol, const double *kval,
                                                      const uint8_t *u_known, const double *u_in, const double *f_in,
                                                      const uint32_t *perm, const uint8_t *touch, int64_t N, double2 *bP)
 {
@@ -891,7 +896,8 @@ __global__ void __launch_bounds__(256) k_rhs_touched(const int32_t *bptr, const 
 
 // b of a row without a prescribed column, as k_apply_order writes it (the same expression: the same bits), for a load case
 // whose f was not there when the ordering phase ran
-__global__ void __launch_bounds__(256) k_rhs_untouched(const uint8_t *u_known, const double2 *f_in, const uint32_t *perm,
+__global__ void __launch_bounds__(256) k_rhs_untouched(const uint8_t *u_known, const double2 *f_in, const uint32_t *perm, int64_t N, double2 *bP); // (end of the file: d_rhs_untouched on the single-case arrays)
+__device__ __forceinline__ void d_rhs_untouched(const uint8_t *u_known, const double2 *f_in, const uint32_t *perm,
                                                        int64_t N, double2 *bP)
 {
     const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -942,7 +948,8 @@ void rhs_compact(const int32_t *bptr, const int32_t *bcol, const double *kval, c
 }
 
 // solver.rs:443-454
-__global__ void __launch_bounds__(256) k_scatter_back(const double2 *xP, const uint32_t *perm, const uint8_t *u_known,
+__global__ void __launch_bounds__(256) k_scatter_back(const double2 *xP, const uint32_t *perm, const uint8_t *u_known, const double *u_in, int64_t N, double *u); // (end of the file: d_scatter_back on the single-case arrays)
+__device__ __forceinline__ void d_scatter_back(const double2 *xP, const uint32_t *perm, const uint8_t *u_known,
                                                       const double *u_in, int64_t N, double *u)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -960,7 +967,8 @@ void scatter_back(const double *xP, const uint32_t *perm, const uint8_t *u_known
 }
 
 // solver.rs:456-469: full row . u in ascending column order (structural zeros of the dense row add +-0)
-__global__ void __launch_bounds__(256) k_reactions_from_csr(const int32_t *bptr, const int32_t *bcol,
+__global__ void __launch_bounds__(256) k_reactions_from_csr(const int32_t *bptr, const int32_t *bcol, const double *kval, const uint8_t *u_known, const double *u, const double *f_in, int64_t N, double *f); // (end of the file: d_reactions_from_csr on the single-case arrays)
+__device__ __forceinline__ void d_reactions_from_csr(const int32_t *bptr, const int32_t *bcol,
                                                             const double *kval, const uint8_t *u_known,
                                                             const double *u, const double *f_in, int64_t N, double *f)
 {
@@ -1005,7 +1013,8 @@ void reactions_from_apply(const double *yP, const int32_t *iperm, const uint8_t 
 }
 
 // solver.rs:496-535: sigma = (D*B)*u_e; scalar = sqrt(sx^2+sy^2) * (sx+sy < 1.0 ? -1 : 1) -- quirk kept.
-__global__ void __launch_bounds__(256) k_element_stress(const double2 *xy, const int32_t *conn, const double2 *u,
+__global__ void __launch_bounds__(256) k_element_stress(const double2 *xy, const int32_t *conn, const double2 *u, int64_t E, double nu, double youngs, double *stress); // (end of the file: d_element_stress on the single-case arrays)
+__device__ __forceinline__ void d_element_stress(const double2 *xy, const int32_t *conn, const double2 *u,
                                                         int64_t E, double nu, double youngs, double *stress)
 {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1028,6 +1037,220 @@ void element_stress(const double *xy, const int32_t *conn, const double *u, int6
 {
     k_element_stress<<<blocks_for(E, 256), 256, 0, s>>>((const double2 *)xy, conn, (const double2 *)u, E, nu, youngs,
                                                         stress);
+}
+
+
+// ---- the kernels' entry points: the bodies above (d_*) on the single-case arrays ...
+__global__ void __launch_bounds__(kAsmNodes) k_assemble_tiles(const int32_t *bcol, const int32_t *bptr, const int32_t *inc_off, const uint32_t *inc, const uint32_t *perm, const int32_t *conn, const double2 *xy, int64_t N, double nu, double youngs, double thick, double *kval)
+{
+    d_assemble_tiles(bcol, bptr, inc_off, inc, perm, conn, xy, N, nu, youngs, thick, kval);
+}
+template <int B>
+__global__ void __launch_bounds__(kFanThreads) k_assemble_fan(const int32_t *bcol, const int32_t *bptr, const uint32_t *perm, const double2 *xyP, const double2 *halo_xy, const int32_t *tile_hoff, const int32_t *tile_deg, const int64_t *tile_off, const uint32_t *ell_asm, const uint16_t *ell_pos, const int32_t *inc_off, const uint32_t *inc, const int32_t *conn, const double2 *xy, int64_t N, int32_t cap, int32_t img_pieces, int32_t segs, int32_t six, double nu, double youngs, double thick, double *kval)
+{
+    d_assemble_fan<B>(bcol, bptr, perm, xyP, halo_xy, tile_hoff, tile_deg, tile_off, ell_asm, ell_pos, inc_off, inc, conn, xy, N, cap, img_pieces, segs, six, nu, youngs, thick, kval);
+}
+__global__ void __launch_bounds__(256) k_rhs_from_csr(const int32_t *bptr, const int32_t *bcol, const double *kval, const uint8_t *u_known, const double *u_in, const double *f_in, const uint32_t *perm, const uint8_t *touch, bool hilbert_flags, int64_t N, double2 *bP)
+{
+    d_rhs_from_csr(bptr, bcol, kval, u_known, u_in, f_in, perm, touch, hilbert_flags, N, bP);
+}
+__global__ void __launch_bounds__(256) k_rhs_touched(const int32_t *bptr, const int32_t *bcol, const double *kval, const uint8_t *u_known, const double *u_in, const double *f_in, const uint32_t *perm, const uint8_t *touch, int64_t N, double2 *bP)
+{
+    d_rhs_touched(bptr, bcol, kval, u_known, u_in, f_in, perm, touch, N, bP);
+}
+__global__ void __launch_bounds__(256) k_rhs_untouched(const uint8_t *u_known, const double2 *f_in, const uint32_t *perm, int64_t N, double2 *bP)
+{
+    d_rhs_untouched(u_known, f_in, perm, N, bP);
+}
+__global__ void __launch_bounds__(256) k_scatter_back(const double2 *xP, const uint32_t *perm, const uint8_t *u_known, const double *u_in, int64_t N, double *u)
+{
+    d_scatter_back(xP, perm, u_known, u_in, N, u);
+}
+__global__ void __launch_bounds__(256) k_reactions_from_csr(const int32_t *bptr, const int32_t *bcol, const double *kval, const uint8_t *u_known, const double *u, const double *f_in, int64_t N, double *f)
+{
+    d_reactions_from_csr(bptr, bcol, kval, u_known, u, f_in, N, f);
+}
+__global__ void __launch_bounds__(256) k_element_stress(const double2 *xy, const int32_t *conn, const double2 *u, int64_t E, double nu, double youngs, double *stress)
+{
+    d_element_stress(xy, conn, u, E, nu, youngs, stress);
+}
+
+// ---- ... and on the arrays of design variant blockIdx.y (mag_run_variants): the same bodies, hence the same bits as a launch
+// of the variant's own; one launch per phase for all the variants of a chunk
+__device__ inline double var_youngs(const VariantBatch &vb) { return vb.mat[3 * (int64_t)blockIdx.y + 0]; }
+__device__ inline double var_nu(const VariantBatch &vb) { return vb.mat[3 * (int64_t)blockIdx.y + 1]; }
+__device__ inline double var_thick(const VariantBatch &vb) { return vb.mat[3 * (int64_t)blockIdx.y + 2]; }
+
+__global__ void __launch_bounds__(256) k_variant_coords(const double2 *xy, const uint32_t *perm, const int32_t *halo_g, int64_t N,
+                                                        int64_t halo_total, VariantBatch vb, double2 *xyP, double2 *halo_xy)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, v = blockIdx.y;
+    const double2 *src = xy + v * (vb.xy / 2);
+    if (i < N)
+        xyP[v * N + i] = src[perm[i]];
+    else if (i - N < halo_total)
+        halo_xy[v * vb.halo + (i - N)] = src[perm[halo_g[i - N]]];
+}
+
+void variant_coords(const double *xy, const uint32_t *perm, const int32_t *halo_g, int64_t N, int64_t halo_total,
+                    const VariantBatch &vb, double *xyP, double *halo_xy, hipStream_t s)
+{
+    const dim3 g((unsigned)blocks_for(N + halo_total, 256), (unsigned)vb.count);
+    k_variant_coords<<<g, 256, 0, s>>>((const double2 *)xy, perm, halo_g, N, halo_total, vb, (double2 *)xyP, (double2 *)halo_xy);
+}
+
+// the ring tables walk every node's triangles in the orientation of the uploaded mesh: a variant must keep every element's
+// area sign (and no element may collapse).  The first offender, as v * E + e, by an atomic minimum -- offenders only
+__global__ void __launch_bounds__(256) k_variant_orientation(const double2 *xy0, const double2 *xyv, const int32_t *conn, int64_t N,
+                                                             int64_t E, unsigned long long *bad)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x, v = blockIdx.y;
+    if (e >= E) return;
+    const int32_t n0 = conn[3 * e], n1 = conn[3 * e + 1], n2 = conn[3 * e + 2];
+    if ((uint32_t)n0 >= (uint64_t)N || (uint32_t)n1 >= (uint64_t)N || (uint32_t)n2 >= (uint64_t)N) return; // (the ordering phase reports it)
+    const double2 *c = xyv + v * N;
+    const double a0 = signed_area(xy0[n0].x, xy0[n0].y, xy0[n1].x, xy0[n1].y, xy0[n2].x, xy0[n2].y);
+    const double av = signed_area(c[n0].x, c[n0].y, c[n1].x, c[n1].y, c[n2].x, c[n2].y);
+    if (!(av == av) || av == 0.0 || (av > 0.0) != (a0 > 0.0)) atomicMin(bad, (unsigned long long)(v * E + e));
+}
+
+void variant_orientation(const double *xy0, const double *xyv, const int32_t *conn, int64_t N, int64_t E, int32_t count,
+                         unsigned long long *bad, hipStream_t s)
+{
+    (void)hipMemsetAsync(bad, 0xff, 8, s);
+    const dim3 g((unsigned)blocks_for(E, 256), (unsigned)count);
+    k_variant_orientation<<<g, 256, 0, s>>>((const double2 *)xy0, (const double2 *)xyv, conn, N, E, bad);
+}
+
+__global__ void __launch_bounds__(kAsmNodes) k_assemble_tiles_v(const int32_t *bcol, const int32_t *bptr, const int32_t *inc_off,
+                                                                 const uint32_t *inc, const uint32_t *perm, const int32_t *conn,
+                                                                 const double2 *xy, int64_t N, VariantBatch vb, double *kval)
+{
+    const int64_t v = blockIdx.y;
+    d_assemble_tiles(bcol, bptr, inc_off, inc, perm, conn, xy + v * (vb.xy / 2), N, var_nu(vb), var_youngs(vb), var_thick(vb),
+                     kval + v * vb.kval);
+}
+
+void assemble_tiles_variants(const int32_t *bcol, const int32_t *bptr, const int32_t *inc_off, const uint32_t *inc,
+                             const uint32_t *perm, const int32_t *conn, const double *xy, int64_t N, const VariantBatch &vb,
+                             double *kval, hipStream_t s)
+{
+    const dim3 g((unsigned)((N + kAsmNodes - 1) / kAsmNodes), (unsigned)vb.count);
+    k_assemble_tiles_v<<<g, kAsmNodes, 0, s>>>(bcol, bptr, inc_off, inc, perm, conn, (const double2 *)xy, N, vb, kval);
+}
+
+template <int B>
+__global__ void __launch_bounds__(kFanThreads) k_assemble_fan_v(const int32_t *bcol, const int32_t *bptr, const uint32_t *perm,
+                                                                const double2 *xyP, const double2 *halo_xy,
+                                                                const int32_t *tile_hoff, const int32_t *tile_deg,
+                                                                const int64_t *tile_off, const uint32_t *ell_asm,
+                                                                const uint16_t *ell_pos, const int32_t *inc_off,
+                                                                const uint32_t *inc, const int32_t *conn, const double2 *xy,
+                                                                int64_t N, int32_t cap, int32_t img_pieces, int32_t segs,
+                                                                int32_t six, VariantBatch vb, double *kval)
+{
+    const int64_t v = blockIdx.y;
+    d_assemble_fan<B>(bcol, bptr, perm, xyP + v * N, halo_xy + v * vb.halo, tile_hoff, tile_deg, tile_off, ell_asm, ell_pos, inc_off,
+                      inc, conn, xy + v * (vb.xy / 2), N, cap, img_pieces, segs, six, var_nu(vb), var_youngs(vb), var_thick(vb),
+                      kval + v * vb.kval);
+}
+
+bool assemble_ctiles_variants(const int32_t *bcol, const int32_t *bptr, const uint32_t *perm, const double *xyP,
+                              const double *halo_xy, const int32_t *tile_hoff, const int32_t *tile_deg, const int64_t *tile_off,
+                              const uint32_t *ell_asm, const uint16_t *ell_pos, const int32_t *inc_off, const uint32_t *inc,
+                              const int32_t *conn, const double *xy, int64_t N, int32_t B, int32_t T, int32_t cap,
+                              const VariantBatch &vb, double *kval, hipStream_t s)
+{
+    const size_t lds = assemble_ctiles_lds(B, cap);
+    if ((B != 256 && B != 512) || cap > 4096 || lds > 64 * 1024) return false; // as assemble_ctiles
+    const int32_t img = asm_img_pieces(cap, B);
+    int32_t segs = 1; // (the single-case rule: which workgroup takes a row changes no bit, the rule is kept all the same)
+    while ((int64_t)T * segs < 768 && B / (2 * segs) >= kFanThreads / kFanLanes) segs *= 2;
+    const int32_t six = 1;
+    const dim3 g((unsigned)(T * segs), (unsigned)vb.count);
+    if (B == 256)
+        k_assemble_fan_v<256><<<g, kFanThreads, lds, s>>>(bcol, bptr, perm, (const double2 *)xyP, (const double2 *)halo_xy, tile_hoff,
+                                                          tile_deg, tile_off, ell_asm, ell_pos, inc_off, inc, conn,
+                                                          (const double2 *)xy, N, cap, img, segs, six, vb, kval);
+    else
+        k_assemble_fan_v<512><<<g, kFanThreads, lds, s>>>(bcol, bptr, perm, (const double2 *)xyP, (const double2 *)halo_xy, tile_hoff,
+                                                          tile_deg, tile_off, ell_asm, ell_pos, inc_off, inc, conn,
+                                                          (const double2 *)xy, N, cap, img, segs, six, vb, kval);
+    return true;
+}
+
+__global__ void __launch_bounds__(256) k_rhs_untouched_v(const uint8_t *u_known, const double2 *f_in, const uint32_t *perm,
+                                                         int64_t N, VariantBatch vb, double2 *bP)
+{
+    const int64_t v = blockIdx.y;
+    d_rhs_untouched(u_known, f_in + v * (vb.loads / 2), perm, N, bP + v * N);
+}
+
+__global__ void __launch_bounds__(256) k_rhs_touched_v(const int32_t *bptr, const int32_t *bcol, const double *kval,
+                                                       const uint8_t *u_known, const double *u_in, const double *f_in,
+                                                       const uint32_t *perm, const uint8_t *touch, int64_t N, VariantBatch vb,
+                                                       double2 *bP)
+{
+    const int64_t v = blockIdx.y;
+    d_rhs_touched(bptr, bcol, kval + v * vb.kval, u_known, u_in + v * vb.loads, f_in + v * vb.loads, perm, touch, N, bP + v * N);
+}
+
+__global__ void __launch_bounds__(256) k_rhs_from_csr_v(const int32_t *bptr, const int32_t *bcol, const double *kval,
+                                                        const uint8_t *u_known, const double *u_in, const double *f_in,
+                                                        const uint32_t *perm, const uint8_t *touch, bool hilbert_flags, int64_t N,
+                                                        VariantBatch vb, double2 *bP)
+{
+    const int64_t v = blockIdx.y;
+    d_rhs_from_csr(bptr, bcol, kval + v * vb.kval, u_known, u_in + v * vb.loads, f_in + v * vb.loads, perm, touch, hilbert_flags, N,
+                   bP + v * N);
+}
+
+void rhs_variants(const int32_t *bptr, const int32_t *bcol, const double *kval, const uint8_t *u_known, const double *u_in,
+                  const double *f_in, const uint32_t *perm, uint8_t *touch, bool touch_ready, int64_t N,
+                  const VariantBatch &vb, double *bP, hipStream_t s)
+{
+    const dim3 g((unsigned)blocks_for(N, 256), (unsigned)vb.count);
+    if (touch_ready) {
+        k_rhs_untouched_v<<<g, 256, 0, s>>>(u_known, (const double2 *)f_in, perm, N, vb, (double2 *)bP);
+        k_rhs_touched_v<<<g, 256, 0, s>>>(bptr, bcol, kval, u_known, u_in, f_in, perm, touch, N, vb, (double2 *)bP);
+        return;
+    }
+    (void)hipMemsetAsync(touch, 0, (size_t)N, s); // (the flags hang on the pattern and the mask: one marking serves every variant)
+    k_mark_bc_rows<<<blocks_for(N, 256), 256, 0, s>>>(bptr, bcol, u_known, N, touch);
+    k_rhs_from_csr_v<<<g, 256, 0, s>>>(bptr, bcol, kval, u_known, u_in, f_in, perm, touch, false, N, vb, (double2 *)bP);
+}
+
+__global__ void __launch_bounds__(256) k_scatter_back_v(const double2 *xP, const uint32_t *perm, const uint8_t *u_known,
+                                                        const double *u_in, int64_t N, VariantBatch vb, double *u)
+{
+    const int64_t v = blockIdx.y;
+    d_scatter_back(xP + v * N, perm, u_known, u_in + v * vb.loads, N, u + v * 2 * N);
+}
+
+__global__ void __launch_bounds__(256) k_reactions_from_csr_v(const int32_t *bptr, const int32_t *bcol, const double *kval,
+                                                              const uint8_t *u_known, const double *u, const double *f_in,
+                                                              int64_t N, VariantBatch vb, double *f)
+{
+    const int64_t v = blockIdx.y;
+    d_reactions_from_csr(bptr, bcol, kval + v * vb.kval, u_known, u + v * 2 * N, f_in + v * vb.loads, N, f + v * 2 * N);
+}
+
+__global__ void __launch_bounds__(256) k_element_stress_v(const double2 *xy, const int32_t *conn, const double2 *u, int64_t N,
+                                                          int64_t E, VariantBatch vb, double *stress)
+{
+    const int64_t v = blockIdx.y;
+    d_element_stress(xy + v * (vb.xy / 2), conn, u + v * N, E, var_nu(vb), var_youngs(vb), stress + v * E);
+}
+
+void post_variants(const double *xP, const uint32_t *perm, const uint8_t *u_known, const double *u_in, const double *f_in,
+                   const int32_t *bptr, const int32_t *bcol, const double *kval, const double *xy, const int32_t *conn,
+                   int64_t N, int64_t E, const VariantBatch &vb, double *u, double *f, double *stress, hipStream_t s)
+{
+    const unsigned V = (unsigned)vb.count;
+    k_scatter_back_v<<<dim3((unsigned)blocks_for(N, 256), V), 256, 0, s>>>((const double2 *)xP, perm, u_known, u_in, N, vb, u);
+    k_reactions_from_csr_v<<<dim3((unsigned)blocks_for(2 * N, 256), V), 256, 0, s>>>(bptr, bcol, kval, u_known, u, f_in, N, vb, f);
+    k_element_stress_v<<<dim3((unsigned)blocks_for(E, 256), V), 256, 0, s>>>((const double2 *)xy, conn, (const double2 *)u, N, E, vb,
+                                                                             stress);
 }
 
 } // namespace magk

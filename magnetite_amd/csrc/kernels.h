@@ -164,6 +164,42 @@ void reactions_from_apply(const double *yP, const int32_t *iperm, const uint8_t 
 void element_stress(const double *xy, const int32_t *conn, const double *u, int64_t E, double nu, double youngs,
                     double *stress, hipStream_t s);
 
+// ---- design variants (mag_set_variants / mag_run_variants): the phases above for `count` variants in ONE launch each,
+// grid.y = the variant.  Every kernel runs the single-case kernel's body on the variant's arrays, so a variant gets the bits a
+// launch of its own gives.  The extents are in elements of the pointer's type; 0: every variant reads the same array.
+struct VariantBatch {
+    int32_t count;    // variants of this launch
+    int32_t pad;
+    const double *mat; // [count][3] = E, nu, thickness
+    int64_t xy;        // caller-order coordinates (doubles): 2N, or 0 when the variants keep the uploaded shape
+    int64_t loads;     // u_in / f_in (doubles): 2N, or 0 when the variants keep the uploaded values
+    int64_t halo;      // halo_xy (double2)
+    int64_t kval;      // K values in the shared pattern (doubles)
+};
+// xyP[v][g] = xy[v][perm[g]], halo_xy[v][i] = xy[v][perm[halo_g[i]]]: what apply_order and halo_coords write, per variant
+void variant_coords(const double *xy, const uint32_t *perm, const int32_t *halo_g, int64_t N, int64_t halo_total,
+                    const VariantBatch &vb, double *xyP, double *halo_xy, hipStream_t s);
+// bad[0] = the smallest v * E + e whose signed area in variant v differs in sign from the uploaded mesh's or is zero
+// (caller zero-fills nothing: the launcher sets it to ~0 first); xyv: [count][2N]
+void variant_orientation(const double *xy0, const double *xyv, const int32_t *conn, int64_t N, int64_t E, int32_t count,
+                         unsigned long long *bad, hipStream_t s);
+bool assemble_ctiles_variants(const int32_t *bcol, const int32_t *bptr, const uint32_t *perm, const double *xyP,
+                              const double *halo_xy, const int32_t *tile_hoff, const int32_t *tile_deg, const int64_t *tile_off,
+                              const uint32_t *ell_asm, const uint16_t *ell_pos, const int32_t *inc_off, const uint32_t *inc,
+                              const int32_t *conn, const double *xy, int64_t N, int32_t B, int32_t T, int32_t cap,
+                              const VariantBatch &vb, double *kval, hipStream_t s);
+void assemble_tiles_variants(const int32_t *bcol, const int32_t *bptr, const int32_t *inc_off, const uint32_t *inc,
+                             const uint32_t *perm, const int32_t *conn, const double *xy, int64_t N, const VariantBatch &vb,
+                             double *kval, hipStream_t s);
+// rhs_untouched + rhs_touched (touch_ready) or rhs_from_csr's full pass, per variant: bP[v] at v * 2N
+void rhs_variants(const int32_t *bptr, const int32_t *bcol, const double *kval, const uint8_t *u_known, const double *u_in,
+                  const double *f_in, const uint32_t *perm, uint8_t *touch, bool touch_ready, int64_t N,
+                  const VariantBatch &vb, double *bP, hipStream_t s);
+// scatter_back, reactions_from_csr, element_stress per variant: xP, u, f at v * 2N, stress at v * E
+void post_variants(const double *xP, const uint32_t *perm, const uint8_t *u_known, const double *u_in, const double *f_in,
+                   const int32_t *bptr, const int32_t *bcol, const double *kval, const double *xy, const int32_t *conn,
+                   int64_t N, int64_t E, const VariantBatch &vb, double *u, double *f, double *stress, hipStream_t s);
+
 // ------------------------------------------------------------------ cg.hip
 struct CgState {
     double rr_hist[2]; // r.r of iterations k (slot k&1) and k-1
@@ -398,6 +434,14 @@ struct PersistParams {
     double *ovf_rec;
     int32_t pool_cap; // records the LDS pool of a workgroup holds (the host checked every workgroup's run against it)
     int32_t pad3;
+    // design variants (the VAR form of the load-case kernel and of k_edge_blocks; persist.hip, persist_variant_params): variant
+    // blockIdx.y has its own coordinates, block values, overflow records and material constants.  xyP advances by N per
+    // variant, the others by the extents below; var_mat: [variants][3] = c0, nu, h, read once per launch.  Appended: no
+    // field of the single-case and load-case forms moved, and none of their instantiations reads these.
+    const double *var_mat;
+    int64_t var_halo_stride; // double2 entries of halo_xy per variant
+    int64_t var_kb_stride;   // doubles of kblocks per variant
+    int64_t var_ovf_stride;  // doubles of ovf_rec per variant
 };
 // multi-GPU, streaming kernels: the per-iteration exchange [dot partials | interface q] through the ranks' device
 // inboxes instead of an all-reduce, in place on `buf` (persist.hip, k_stream_exchange)
@@ -418,10 +462,16 @@ void persist_launch(const PersistParams &P, int32_t B, int32_t grid, int eb_mode
 // (persist.hip, persist_case_params).  persist_cases_shape: the shape has a load-case instantiation (else: one case at a time).
 bool persist_cases_shape(int32_t B, int32_t grid, int32_t tiles_per_wg, int eb_mode);
 void persist_launch_cases(const PersistParams &P, int32_t B, int32_t grid, int32_t cases, int eb_mode, hipStream_t s);
+// Design variants: `variants` shapes / materials of one mesh side by side in ONE launch, laid out as the load cases are, plus the
+// per-variant operator data of PersistParams' var_* fields (persist.hip, persist_variant_params; persist_variants.o).  The
+// shapes are the load-case ones (persist_cases_shape).
+void persist_launch_variants(const PersistParams &P, int32_t B, int32_t grid, int32_t variants, int eb_mode, hipStream_t s);
 int persist_block_entries(); // block entries per node of that instantiation
 // ... and its blocks: 3 * persist_block_entries() doubles per node of the T * B padded nodes, into P.kblocks (host sets
 // kblocks / kb_stride before the call; eb_mode 2: row_info / ovf_off / ovf_rec as well)
 void edge_blocks_build(const PersistParams &P, int32_t B, double *kblocks, int eb_mode, hipStream_t s);
+// ... of `variants` variants in one launch (grid.y = variant): into P.kblocks (+ P.ovf_rec) at the var_* extents
+void edge_blocks_build_variants(const PersistParams &P, int32_t B, int eb_mode, int32_t variants, hipStream_t s);
 int persist_stamp_words();   // words per workgroup in PersistParams::stamps
 bool persist_stamps_built(); // the library was compiled with -DMAG_PERSIST_STAMPS
 void mark_published(const int32_t *halo_g, int64_t halo_total, uint8_t *maskP, hipStream_t s);

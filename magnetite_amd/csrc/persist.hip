@@ -764,6 +764,23 @@ __device__ inline PersistParams persist_case_params(PersistParams P)
     return P;
 }
 
+// Design variants (the VAR form of k_cg_persist<..., LC> and of the edge-block builders): what variant blockIdx.y has of its own
+// on top of a load case's vectors -- its coordinates (triangle walk), its block values and overflow-record values (edge blocks)
+// and its material constants, read once per launch from a device table.  Mesh, mask, ring tables, row_info and ovf_off (the
+// records' LAYOUT) are shared: none of them reads a coordinate or a material constant.
+__device__ inline PersistParams persist_variant_operator(PersistParams P)
+{
+    const int64_t c = (int64_t)blockIdx.y;
+    P.xyP += c * P.N;
+    P.halo_xy += c * P.var_halo_stride;
+    P.kblocks += c * P.var_kb_stride;
+    P.ovf_rec += c * P.var_ovf_stride;
+    P.c0 = P.var_mat[3 * c + 0];
+    P.nu = P.var_mat[3 * c + 1];
+    P.h = P.var_mat[3 * c + 2];
+    return P;
+}
+
 // EBM: 0 the triangle walk, 1 edge blocks in registers (every row of the mesh a fan of at most six blocks: structured meshes),
 // 2 edge blocks with OVERFLOW (round 4: rows that are one fan of any length -- what gmsh's frontal meshes look like, a quarter
 // of their nodes with seven neighbours: blocks beyond the six in registers sit in an LDS pool of 32-byte records).
@@ -780,12 +797,18 @@ __device__ inline PersistParams persist_case_params(PersistParams P)
 // with instantiations of its own for the same reason as ONE: the single-case instantiations keep their code, instruction for
 // instruction (only their mangled names gain the defaulted flag; with the body moved into a function that two kernels inline,
 // which would have kept the names, the compiler allocated the existing kernels' registers differently).
-template <int B, bool MG, int THREADS, int EBM, bool ONE = false, int NPTX = 0, bool LC = false>
+// VAR (with LC): the DESIGN-VARIANT form -- a load-case launch whose cases also differ in the operator: per-variant coordinates,
+// block values, overflow-record values and material constants behind the same pointers (persist_variant_operator).  The flag
+// sits in front of LC, so that the load-case instantiations keep LC as their last template argument; instantiations of their
+// own again (persist_variants.o), for the reason given above.
+template <int B, bool MG, int THREADS, int EBM, bool ONE = false, int NPTX = 0, bool VAR = false, bool LC = false>
 __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
 {
     static_assert(!(LC && MG), "load cases run on one GPU");
+    static_assert(LC || !VAR, "variants are laid out as load cases");
     PersistParams Pc; // (LC only)
     if constexpr (LC) Pc = persist_case_params(Pk);
+    if constexpr (VAR) Pc = persist_variant_operator(Pc);
     const PersistParams &P = LC ? Pc : Pk;
     constexpr int NPT = NPTX ? NPTX : kPersistNpt;
     constexpr bool EB = EBM != 0, OV = EBM == 2;
@@ -1432,13 +1455,41 @@ void persist_launch_cases(const PersistParams &P, int32_t B, int32_t grid, int32
     const size_t lds = persist_lds_bytes(B, P.cap, P.maxh, eb_mode, P.pool_cap, false);
     const dim3 g((unsigned)grid, (unsigned)cases);
     if (eb_mode == 0) {
-        k_cg_persist<512, false, 512, 0, false, 0, true><<<g, 512, lds, s>>>(P);
+        k_cg_persist<512, false, 512, 0, false, 0, false, true><<<g, 512, lds, s>>>(P);
         return;
     }
     const bool one = grid == 1;
     const int npt = P.tiles_per_wg < 4 ? P.tiles_per_wg : 0;
 #define MAG_PERSIST_CASE(EBM_, ONE_, NPTX_)                                                                                       \
-    if (eb_mode == EBM_ && one == ONE_ && npt == NPTX_) k_cg_persist<512, false, 512, EBM_, ONE_, NPTX_, true><<<g, 512, lds, s>>>(P)
+    if (eb_mode == EBM_ && one == ONE_ && npt == NPTX_) k_cg_persist<512, false, 512, EBM_, ONE_, NPTX_, false, true><<<g, 512, lds, s>>>(P)
+#define MAG_PERSIST_CASES(EBM_)                                                                                                   \
+    MAG_PERSIST_CASE(EBM_, false, 1);                                                                                             \
+    MAG_PERSIST_CASE(EBM_, true, 1);                                                                                              \
+    MAG_PERSIST_CASE(EBM_, true, 2);                                                                                              \
+    MAG_PERSIST_CASE(EBM_, true, 3);                                                                                              \
+    MAG_PERSIST_CASE(EBM_, true, 0)
+    MAG_PERSIST_CASES(1);
+    MAG_PERSIST_CASES(2);
+#undef MAG_PERSIST_CASES
+#undef MAG_PERSIST_CASE
+}
+} // namespace magk
+#elif defined(MAG_PERSIST_TU_VARIANTS)
+// The design-variant instantiations (VAR, LC), in a translation unit of their own (persist_variants.o: this file with
+// -DMAG_PERSIST_TU_VARIANTS, under persist.o's scheduler): the load-case shapes, one for one.
+void persist_launch_variants(const PersistParams &P, int32_t B, int32_t grid, int32_t variants, int eb_mode, hipStream_t s)
+{
+    if (!persist_cases_shape(B, grid, P.tiles_per_wg, eb_mode) || P.nranks != 1 || variants < 1) return; // (the host has asked)
+    const size_t lds = persist_lds_bytes(B, P.cap, P.maxh, eb_mode, P.pool_cap, false);
+    const dim3 g((unsigned)grid, (unsigned)variants);
+    if (eb_mode == 0) {
+        k_cg_persist<512, false, 512, 0, false, 0, true, true><<<g, 512, lds, s>>>(P);
+        return;
+    }
+    const bool one = grid == 1;
+    const int npt = P.tiles_per_wg < 4 ? P.tiles_per_wg : 0;
+#define MAG_PERSIST_CASE(EBM_, ONE_, NPTX_)                                                                                       \
+    if (eb_mode == EBM_ && one == ONE_ && npt == NPTX_) k_cg_persist<512, false, 512, EBM_, ONE_, NPTX_, true, true><<<g, 512, lds, s>>>(P)
 #define MAG_PERSIST_CASES(EBM_)                                                                                                   \
     MAG_PERSIST_CASE(EBM_, false, 1);                                                                                             \
     MAG_PERSIST_CASE(EBM_, true, 1);                                                                                              \
@@ -1717,9 +1768,14 @@ int persist_block_entries() { return kPersistBlockEntries; }
 // from xyP, halo nodes from the tile's contiguous halo copy -- and writes the 3 NB numbers, value-major (the on-chip kernel's
 // loads are coalesced).  Only launched for meshes k_ring16 found to qualify (every row one fan of at most NB entries, or
 // NB + 1 closing onto the first).
-template <int B>
-__global__ void __launch_bounds__(256) k_edge_blocks(const PersistParams P, double *kbg)
+// VAR: the blocks of variant blockIdx.y, from its coordinates and material constants into its extent of P.kblocks
+template <int B, bool VAR = false>
+__global__ void __launch_bounds__(256) k_edge_blocks(const PersistParams Pk, double *kbg_)
 {
+    PersistParams Pv; // (VAR only)
+    if constexpr (VAR) Pv = persist_variant_operator(Pk);
+    const PersistParams &P = VAR ? Pv : Pk;
+    double *kbg = VAR ? const_cast<double *>(P.kblocks) : kbg_;
     constexpr int NB = kPersistBlockEntries, NW = (NB + 2) / 2;
     // (several ranks: the blocks of this rank's own tiles only -- the launcher's grid covers [t0, t1))
     const int64_t nd = (P.nranks > 1 ? (int64_t)P.t0 * B : 0) + (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1753,9 +1809,13 @@ __global__ void __launch_bounds__(256) k_edge_blocks(const PersistParams P, doub
 // the value-major arrays the registers are loaded from, block j >= NB to the node's overflow records, at ovf_off[node] +
 // j - NB, with the ring entry (tile-local id) it multiplies.  Per block the same two-term sums in the same order as
 // ring_blocks: a structured mesh gets the same bits from either kernel.
-template <int B>
-__global__ void __launch_bounds__(256) k_edge_blocks_ovf(const PersistParams P, double *kbg)
+template <int B, bool VAR = false>
+__global__ void __launch_bounds__(256) k_edge_blocks_ovf(const PersistParams Pk, double *kbg_)
 {
+    PersistParams Pv; // (VAR only)
+    if constexpr (VAR) Pv = persist_variant_operator(Pk);
+    const PersistParams &P = VAR ? Pv : Pk;
+    double *kbg = VAR ? const_cast<double *>(P.kblocks) : kbg_;
     constexpr int NB = kPersistBlockEntries;
     const int64_t nd = (P.nranks > 1 ? (int64_t)P.t0 * B : 0) + (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int32_t t = (int32_t)(nd / B), lt = (int32_t)(nd % B);
@@ -1857,6 +1917,22 @@ void edge_blocks_build(const PersistParams &P, int32_t B, double *kblocks, int e
         k_edge_blocks<256><<<blocks, 256, 0, s>>>(P, kblocks);
     else
         k_edge_blocks<512><<<blocks, 256, 0, s>>>(P, kblocks);
+}
+
+void edge_blocks_build_variants(const PersistParams &P, int32_t B, int eb_mode, int32_t variants, hipStream_t s)
+{
+    if (P.nranks > 1 || variants < 1) return; // (variants run on one GPU)
+    const int64_t npad = (int64_t)P.T * B;
+    const dim3 g((unsigned)((npad + 255) / 256), (unsigned)variants);
+    if (eb_mode == 2) {
+        if (B == 256)
+            k_edge_blocks_ovf<256, true><<<g, 256, 0, s>>>(P, nullptr);
+        else
+            k_edge_blocks_ovf<512, true><<<g, 256, 0, s>>>(P, nullptr);
+    } else if (B == 256)
+        k_edge_blocks<256, true><<<g, 256, 0, s>>>(P, nullptr);
+    else
+        k_edge_blocks<512, true><<<g, 256, 0, s>>>(P, nullptr);
 }
 
 int persist_stamp_words() { return kStampPhases + 1; }

@@ -277,6 +277,82 @@ class Context:
             outs.append(out)
         return outs
 
+    # -- design variants: several shapes / materials / value sets of the uploaded mesh ------
+    def set_variants(self, xy=None, material=None, u_in=None, f_in=None):
+        """mag_set_variants: xy (V, 2N) or (V, N, 2), material (V, 3) = E, nu, thickness, u_in / f_in (V, 2N) -- each optional
+        (None: every variant keeps what was uploaded), at least one given, all with the same V."""
+        N = self.N
+
+        def arr(a, width, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.ndim == 3 and what == "xy":
+                a = a.reshape(a.shape[0], -1)
+            if a.ndim != 2 or a.shape[1] != width:
+                raise MagnetiteError("Solver", f"variants: {what} must have shape (num_variants, {width})")
+            return a
+
+        xy, material = arr(xy, 2 * N, "xy"), arr(material, 3, "material")
+        u_in, f_in = arr(u_in, 2 * N, "u_in"), arr(f_in, 2 * N, "f_in")
+        if (u_in is None) != (f_in is None):
+            raise MagnetiteError("Solver", "variants: u_in and f_in come together")
+        given = [a for a in (xy, material, u_in, f_in) if a is not None]
+        if len({a.shape[0] for a in given}) > 1:
+            raise MagnetiteError("Solver", "variants: xy, material, u_in and f_in must agree on num_variants")
+        V = given[0].shape[0] if given else 1  # (nothing given: the library answers)
+        ptr = lambda a: None if a is None else _p(a, C.c_double)
+        self._check(self._L.mag_set_variants(self._h, V, ptr(xy), ptr(material), ptr(u_in), ptr(f_in), MAG_MEM_HOST))
+        self.num_variants = V
+
+    def run_variants(self, allow_not_converged=False):
+        """mag_run_variants: order, tables and CSR pattern once; per variant coordinates, K, right-hand side, blocks, CG, post --
+        the CG solves side by side on the chip where they fit."""
+        allow = (MAG_ERR_NOT_CONVERGED,) if allow_not_converged else ()
+        return self._check(self._L.mag_run_variants(self._h), allow)
+
+    def download_variant(self, i):
+        u, f, s = np.empty(2 * self.N), np.empty(2 * self.N), np.empty(self.E)
+        r = _lib.Result(u.ctypes.data, f.ctypes.data, s.ctypes.data, MAG_MEM_HOST, 0)
+        self._check(self._L.mag_download_variant(self._h, i, C.byref(r)))
+        return u, f, s
+
+    def variant_stats(self, i):
+        st = _lib.Stats()
+        self._check(self._L.mag_get_variant_stats(self._h, i, C.byref(st)))
+        return st.as_dict()
+
+    def variants_info(self):
+        """dict(variants, variants_per_launch (0: one after another through the single-case phases), launches, redone)."""
+        info = (C.c_int32 * 4)()
+        self._check(self._L.mag_get_variants_info(self._h, info))
+        return dict(variants=info[0], variants_per_launch=info[1], launches=info[2], redone=info[3])
+
+    def solve_variants(self, prob, xy=None, material=None, u_in=None, f_in=None, allow_not_converged=False):
+        """Upload prob (its coordinates give the ordering every variant shares), solve the variants: a list of dicts shaped
+        like solve()'s."""
+        self.upload_problem(prob)
+        self.set_variants(xy, material, u_in, f_in)
+        self.run_variants(allow_not_converged)
+        outs = []
+        for i in range(self.num_variants):
+            u, f, s = self.download_variant(i)
+            out = dict(u=u, f=f, stress=s)
+            out.update(self.variant_stats(i))
+            outs.append(out)
+        return outs
+
+    def assemble_csr_variant(self, i):
+        """K of variant i in the uploaded mesh's pattern (test entry point mag_assemble_csr_variant)."""
+        nnz = C.c_int64(0)
+        self._check(self._L.mag_assemble_csr_variant(self._h, i, C.byref(nnz), None, None, None))
+        rowptr = np.empty(2 * self.N + 1, dtype=np.int32)
+        col = np.empty(nnz.value, dtype=np.int32)
+        val = np.empty(nnz.value)
+        self._check(self._L.mag_assemble_csr_variant(self._h, i, C.byref(nnz), _p(rowptr, C.c_int32), _p(col, C.c_int32),
+                                                     _p(val, C.c_double)))
+        return rowptr, col, val
+
     # -- pieces, for parity tests ----------------------------------------------
     def element_stiffness(self):
         ke = np.empty(36 * self.E)
