@@ -114,6 +114,73 @@ inline Result flatten_elements(const std::vector<Element> &elements, std::size_t
     return std::nullopt;
 }
 
+// the flattened arrays as the C ABI's problem (host memory)
+inline mag_problem host_problem(const std::vector<double> &xy, const std::vector<std::int32_t> &conn,
+                                const std::vector<std::uint8_t> &u_known, const double *u_in, const double *f_in,
+                                const ModelMetadata &model_metadata)
+{
+    mag_problem p{};
+    p.num_nodes = (std::int64_t)(xy.size() / 2);
+    p.num_elements = (std::int64_t)(conn.size() / 3);
+    p.xy = xy.data();
+    p.conn = conn.data();
+    p.u_known = u_known.data();
+    p.u_in = u_in;
+    p.f_in = f_in;
+    p.youngs_modulus = model_metadata.youngs_modulus;
+    p.poisson_ratio = model_metadata.poisson_ratio;
+    p.part_thickness = model_metadata.part_thickness;
+    p.memory = MAG_MEM_HOST;
+    return p;
+}
+
+// the error path: the context's message, the context gone
+inline Result fail_and_destroy(mag_ctx *ctx)
+{
+    Result e = solver_error(mag_last_error(ctx));
+    mag_destroy(ctx);
+    return e;
+}
+
+inline void store_values(std::vector<Node> &nodes, const std::vector<double> &u, const std::vector<double> &f)
+{
+    for (std::size_t i = 0; i < nodes.size(); ++i) {  // solver.rs:476-482
+        nodes[i].ux = u[2 * i];
+        nodes[i].uy = u[2 * i + 1];
+        nodes[i].fx = f[2 * i];
+        nodes[i].fy = f[2 * i + 1];
+    }
+}
+
+// After a set's run (load cases, design variants) returned rc: the info words, every member's values into members[m], its
+// stress and statistics; the context goes.  A member that broke down is an error, the others hold their results.
+inline Result collect_members(mag_ctx *ctx, int rc, std::vector<std::vector<Node>> &members, std::size_t E,
+                              std::vector<std::vector<double>> &stress, std::vector<mag_stats> *stats_out, std::int32_t *info_out,
+                              int (*get_info)(const mag_ctx *, std::int32_t *), int (*download)(mag_ctx *, std::int32_t, mag_result *),
+                              int (*get_stats)(const mag_ctx *, std::int32_t, mag_stats *))
+{
+    if (rc != MAG_OK && rc != MAG_ERR_NOT_CONVERGED) return fail_and_destroy(ctx);
+    const std::string run_message = mag_last_error(ctx);
+    const std::size_t M = members.size(), N = M ? members[0].size() : 0;
+    std::vector<double> u(2 * N), f(2 * N);
+    if (stats_out) stats_out->assign(M, mag_stats{});
+    if (info_out) get_info(ctx, info_out);
+    stress.assign(M, std::vector<double>(E));
+    for (std::size_t m = 0; m < M; ++m) {
+        mag_result r{};
+        r.u_out = u.data();
+        r.f_out = f.data();
+        r.stress_out = stress[m].data();
+        r.memory = MAG_MEM_HOST;
+        if (download(ctx, (std::int32_t)m, &r) != MAG_OK) return fail_and_destroy(ctx);
+        if (stats_out) get_stats(ctx, (std::int32_t)m, &(*stats_out)[m]);
+        store_values(members[m], u, f);
+    }
+    mag_destroy(ctx);
+    if (rc != MAG_OK) return solver_error(run_message);
+    return std::nullopt;
+}
+
 }  // namespace detail
 
 // solver.rs:543-586.  `options` == nullptr keeps the reference's constants (absolute cost 1e-4, 1e7 iterations).
@@ -129,18 +196,7 @@ inline Result run(std::vector<Node> &nodes, std::vector<Element> &elements, cons
     if (Result e = detail::flatten_elements(elements, N, conn)) return e;
     mag_ctx *ctx = mag_create(options);
     if (!ctx) return err("mag_create failed");
-    mag_problem p{};
-    p.num_nodes = (std::int64_t)N;
-    p.num_elements = (std::int64_t)E;
-    p.xy = xy.data();
-    p.conn = conn.data();
-    p.u_known = u_known.data();
-    p.u_in = u_in.data();
-    p.f_in = f_in.data();
-    p.youngs_modulus = model_metadata.youngs_modulus;
-    p.poisson_ratio = model_metadata.poisson_ratio;
-    p.part_thickness = model_metadata.part_thickness;
-    p.memory = MAG_MEM_HOST;
+    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
     mag_result r{};
     r.u_out = u.data();
     r.f_out = f.data();
@@ -148,18 +204,9 @@ inline Result run(std::vector<Node> &nodes, std::vector<Element> &elements, cons
     r.memory = MAG_MEM_HOST;
     const int rc = mag_solve(ctx, &p, &r);
     if (stats_out) mag_get_stats(ctx, stats_out);
-    if (rc != MAG_OK) {
-        Result e = err(mag_last_error(ctx));
-        mag_destroy(ctx);
-        return e;
-    }
+    if (rc != MAG_OK) return detail::fail_and_destroy(ctx);
     mag_destroy(ctx);
-    for (std::size_t i = 0; i < N; ++i) {  // solver.rs:476-482
-        nodes[i].ux = u[2 * i];
-        nodes[i].uy = u[2 * i + 1];
-        nodes[i].fx = f[2 * i];
-        nodes[i].fy = f[2 * i + 1];
-    }
+    detail::store_values(nodes, u, f);
     for (std::size_t e = 0; e < E; ++e) elements[e].stress = stress[e];  // solver.rs:532-533
     return std::nullopt;
 }
@@ -177,7 +224,7 @@ inline Result run_cases(std::vector<std::vector<Node>> &cases, const std::vector
     auto err = detail::solver_error;
     if (cases.empty()) return err("no load case");
     const std::size_t L = cases.size(), N = cases[0].size(), E = elements.size();
-    std::vector<double> xy, xy_c, u_in(L * 2 * N), f_in(L * 2 * N), u(2 * N), f(2 * N);
+    std::vector<double> xy, xy_c, u_in(L * 2 * N), f_in(L * 2 * N);
     std::vector<std::uint8_t> u_known, mask_c;
     std::vector<std::int32_t> conn;
     if (Result e = detail::flatten_nodes(cases[0], xy, u_known, u_in.data(), f_in.data())) return e;
@@ -190,49 +237,11 @@ inline Result run_cases(std::vector<std::vector<Node>> &cases, const std::vector
     if (Result e = detail::flatten_elements(elements, N, conn)) return e;
     mag_ctx *ctx = mag_create(options);
     if (!ctx) return err("mag_create failed");
-    auto fail = [&]() {
-        Result e = err(mag_last_error(ctx));
-        mag_destroy(ctx);
-        return e;
-    };
-    mag_problem p{};
-    p.num_nodes = (std::int64_t)N;
-    p.num_elements = (std::int64_t)E;
-    p.xy = xy.data();
-    p.conn = conn.data();
-    p.u_known = u_known.data();
-    p.u_in = u_in.data();
-    p.f_in = f_in.data();
-    p.youngs_modulus = model_metadata.youngs_modulus;
-    p.poisson_ratio = model_metadata.poisson_ratio;
-    p.part_thickness = model_metadata.part_thickness;
-    p.memory = MAG_MEM_HOST;
-    if (mag_upload(ctx, &p) != MAG_OK) return fail();
-    if (mag_set_load_cases(ctx, (std::int32_t)L, u_in.data(), f_in.data(), MAG_MEM_HOST) != MAG_OK) return fail();
-    const int rc = mag_run_cases(ctx);
-    if (rc != MAG_OK && rc != MAG_ERR_NOT_CONVERGED) return fail();
-    const std::string run_message = mag_last_error(ctx);
-    if (stats_out) stats_out->assign(L, mag_stats{});
-    if (info_out) mag_get_cases_info(ctx, info_out);
-    stress.assign(L, std::vector<double>(E));
-    for (std::size_t c = 0; c < L; ++c) {
-        mag_result r{};
-        r.u_out = u.data();
-        r.f_out = f.data();
-        r.stress_out = stress[c].data();
-        r.memory = MAG_MEM_HOST;
-        if (mag_download_case(ctx, (std::int32_t)c, &r) != MAG_OK) return fail();
-        if (stats_out) mag_get_case_stats(ctx, (std::int32_t)c, &(*stats_out)[c]);
-        for (std::size_t i = 0; i < N; ++i) {
-            cases[c][i].ux = u[2 * i];
-            cases[c][i].uy = u[2 * i + 1];
-            cases[c][i].fx = f[2 * i];
-            cases[c][i].fy = f[2 * i + 1];
-        }
-    }
-    mag_destroy(ctx);
-    if (rc != MAG_OK) return err(run_message); // a case broke down: the others hold their results
-    return std::nullopt;
+    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
+    if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    if (mag_set_load_cases(ctx, (std::int32_t)L, u_in.data(), f_in.data(), MAG_MEM_HOST) != MAG_OK) return detail::fail_and_destroy(ctx);
+    return detail::collect_members(ctx, mag_run_cases(ctx), cases, E, stress, stats_out, info_out, mag_get_cases_info, mag_download_case,
+                                   mag_get_case_stats);  // (a case broke down: the others hold their results)
 }
 
 // Design variants (mag_set_variants / mag_run_variants): the same part -- `nodes` and `elements`, which give the ordering every
@@ -252,7 +261,7 @@ inline Result run_variants(const std::vector<Node> &nodes, const std::vector<Ele
     if (V == 0) return err("no variant: give shapes, materials or both");
     if (!shapes.empty() && !materials.empty() && shapes.size() != materials.size())
         return err("shapes and materials disagree on the number of variants");
-    std::vector<double> xy, u_in(2 * N), f_in(2 * N), u(2 * N), f(2 * N), vxy, vmat;
+    std::vector<double> xy, u_in(2 * N), f_in(2 * N), vxy, vmat;
     std::vector<std::uint8_t> u_known;
     std::vector<std::int32_t> conn;
     if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
@@ -271,53 +280,19 @@ inline Result run_variants(const std::vector<Node> &nodes, const std::vector<Ele
     }
     mag_ctx *ctx = mag_create(options);
     if (!ctx) return err("mag_create failed");
-    auto fail = [&]() {
-        Result e = err(mag_last_error(ctx));
-        mag_destroy(ctx);
-        return e;
-    };
-    mag_problem p{};
-    p.num_nodes = (std::int64_t)N;
-    p.num_elements = (std::int64_t)E;
-    p.xy = xy.data();
-    p.conn = conn.data();
-    p.u_known = u_known.data();
-    p.u_in = u_in.data();
-    p.f_in = f_in.data();
-    p.youngs_modulus = model_metadata.youngs_modulus;
-    p.poisson_ratio = model_metadata.poisson_ratio;
-    p.part_thickness = model_metadata.part_thickness;
-    p.memory = MAG_MEM_HOST;
-    if (mag_upload(ctx, &p) != MAG_OK) return fail();
+    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
+    if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
     if (mag_set_variants(ctx, (std::int32_t)V, shapes.empty() ? nullptr : vxy.data(), materials.empty() ? nullptr : vmat.data(),
                          nullptr, nullptr, MAG_MEM_HOST) != MAG_OK)
-        return fail();
+        return detail::fail_and_destroy(ctx);
     const int rc = mag_run_variants(ctx);
-    if (rc != MAG_OK && rc != MAG_ERR_NOT_CONVERGED) return fail();
-    const std::string run_message = mag_last_error(ctx);
-    if (stats_out) stats_out->assign(V, mag_stats{});
-    if (info_out) mag_get_variants_info(ctx, info_out);
-    stress.assign(V, std::vector<double>(E));
-    results.assign(V, nodes);
-    for (std::size_t v = 0; v < V; ++v) {
-        mag_result r{};
-        r.u_out = u.data();
-        r.f_out = f.data();
-        r.stress_out = stress[v].data();
-        r.memory = MAG_MEM_HOST;
-        if (mag_download_variant(ctx, (std::int32_t)v, &r) != MAG_OK) return fail();
-        if (stats_out) mag_get_variant_stats(ctx, (std::int32_t)v, &(*stats_out)[v]);
-        for (std::size_t i = 0; i < N; ++i) {
-            if (!shapes.empty()) results[v][i].vertex = shapes[v][i];
-            results[v][i].ux = u[2 * i];
-            results[v][i].uy = u[2 * i + 1];
-            results[v][i].fx = f[2 * i];
-            results[v][i].fy = f[2 * i + 1];
-        }
+    if (rc == MAG_OK || rc == MAG_ERR_NOT_CONVERGED) {
+        results.assign(V, nodes);
+        for (std::size_t v = 0; v < shapes.size(); ++v)
+            for (std::size_t i = 0; i < N; ++i) results[v][i].vertex = shapes[v][i];
     }
-    mag_destroy(ctx);
-    if (rc != MAG_OK) return err(run_message); // a variant broke down: the others hold their results
-    return std::nullopt;
+    return detail::collect_members(ctx, rc, results, E, stress, stats_out, info_out, mag_get_variants_info, mag_download_variant,
+                                   mag_get_variant_stats);  // (a variant broke down: the others hold their results)
 }
 
 }  // namespace solver

@@ -56,6 +56,24 @@ struct DevBuf {
     T *as() const { return (T *)p; }
 };
 
+// What a set of solves on ONE uploaded mesh owns (load cases, design variants): `count` members, member after member in every
+// buffer -- inputs, the uploaded problem while it is lent to a member that runs alone (keep), right-hand sides and solutions
+// (Hilbert numbering), results (caller numbering) --, every member's statistics and the four words of mag_get_*_info
+struct MemberSet {
+    const char *noun;   // in messages: "load case" / "variant"
+    const char *run_fn; // the entry point that solves the set
+    int32_t count = 0;
+    bool have = false, have_run = false;
+    DevBuf uin, fin, keep, bP, x, u, f, stress;
+    std::vector<mag_stats> stats;
+    int32_t info[4] = {};
+    void reset() // the set belongs to the mesh and mask it was given for
+    {
+        have = have_run = false;
+        count = 0;
+    }
+};
+
 // Run-time knobs (environment, read at every call: tests switch them between calls in one process).  None is needed in
 // production; each one either is set by a test or forces a path the library can take on its own.
 //   MAG_TUNE_FORCE_DIST=1                one rank runs the distributed protocol (tests/dist_worker.py: rccl1 rehearsal)
@@ -199,27 +217,20 @@ struct mag_ctx {
     DevBuf u, f, stress;
     mag_stats stats = {};
 
-    // load cases (mag_set_load_cases / mag_run_cases): num_cases sets of prescribed values on the uploaded mesh, case after
-    // case in every buffer -- inputs, right-hand sides (Hilbert numbering), solutions, results; the on-chip kernel's granules,
-    // records, timeout words and states for the cases of ONE launch
-    int32_t num_cases = 0;
-    bool have_cases = false, have_cases_run = false;
-    DevBuf c_uin, c_fin, c_keep, c_bP, c_x, c_u, c_f, c_stress, c_qx, c_part, c_sync, c_state;
-    std::vector<mag_stats> case_stats;
-    int32_t cases_info[4] = {};
+    // load cases (mag_set_load_cases / mag_run_cases): sets of prescribed values on the uploaded mesh; design variants
+    // (mag_set_variants / mag_run_variants): shapes / materials / value sets of it (variants.uin / fin only when given).  Two
+    // sets: load cases survive a variants run
+    MemberSet cases{"load case", "mag_run_cases"}, variants{"variant", "mag_run_variants"};
+    // the on-chip kernel's granules, records, timeout words and states for the members of ONE launch, of either set
+    DevBuf launch_qx, launch_part, launch_sync, launch_state;
 
-    // design variants (mag_set_variants / mag_run_variants): num_variants shapes / materials / value sets of the uploaded mesh.
-    // Inputs and results variant after variant (v_xy, v_uin / v_fin only when given; v_mat: E, nu, thickness; v_cmat: the CG
+    // what only variants have.  Inputs variant after variant (v_xy only when given; v_mat: E, nu, thickness; v_cmat: the CG
     // kernels' c0, nu, h); the per-variant OPERATOR data -- permuted coordinates, K values, edge blocks, overflow records --
     // for the variants of ONE chunk only
-    int32_t num_variants = 0;
-    bool have_variants = false, have_variants_run = false, v_have_xy = false, v_have_loads = false;
-    DevBuf v_xy, v_uin, v_fin, v_mat, v_cmat, v_bad, v_keep;
+    bool v_have_xy = false, v_have_loads = false;
+    DevBuf v_xy, v_mat, v_cmat, v_bad;
     DevBuf v_xyP, v_halo, v_kval, v_kblocks, v_ovf;
-    DevBuf v_bP, v_x, v_u, v_f, v_stress;
-    std::vector<double> v_mat_h; // [num_variants][3] = E, nu, thickness
-    std::vector<mag_stats> variant_stats;
-    int32_t variants_info[4] = {};
+    std::vector<double> v_mat_h; // [variants.count][3] = E, nu, thickness
     int32_t ovf_total = 0; // overflow records of the whole mesh (choose_edge_blocks)
     hipEvent_t evV[7] = {}; // phase boundaries of a chunk (created by the first mag_run_variants)
 
@@ -254,6 +265,9 @@ int enter(mag_ctx *ctx)
     HIPCHK(hipSetDevice(ctx->device));
     return MAG_OK;
 }
+
+// K is assembled: asked for, or the CG operator is its CSR
+inline bool wants_csr(const mag_ctx *ctx) { return ctx->opt.assemble_csr != 0 || ctx->opt.cg_operator == MAG_OP_CSR; }
 
 int scratch_for(mag_ctx *ctx, size_t bytes)
 {
@@ -446,7 +460,7 @@ int ensure_order(mag_ctx *ctx)
     // Several ranks, inside mag_run (every rank is here: the phase then ends with two small all-reduces), K assembled from the
     // rows a rank keeps: the tables below are built for the tiles this rank needs only (symbolic.hip, need_tiles).  Any other
     // entry point -- and MAG_TUNE_SHARD_ORDER=0 -- builds them for the whole mesh, as every rank did until round 4.
-    const bool csr_rows = ctx->opt.assemble_csr != 0 || ctx->opt.cg_operator == MAG_OP_CSR;
+    const bool csr_rows = wants_csr(ctx);
     const bool sh = R > 1 && ctx->order_allow_shard && csr_rows && !ctx->want_full_csr &&
                     env_int("MAG_TUNE_SHARD_ORDER", 1) != 0 && getenv("MAG_TUNE_FORCE_DIST") == nullptr;
     ctx->order_sharded = sh;
@@ -620,7 +634,7 @@ int ensure_order(mag_ctx *ctx)
         HIPCHK(ctx->ell.reserve(4 * (size_t)(h_total > 0 ? h_total : 1)));
         // the assembly's copy of the corner words (k_assemble_fan): only when K is assembled and the tile image (256 B of
         // accumulators per row node + 20 B per staged node) fits a CU's LDS
-        const bool csr_wanted = ctx->opt.assemble_csr != 0 || ctx->opt.cg_operator == MAG_OP_CSR;
+        const bool csr_wanted = wants_csr(ctx);
         const char *how_asm = getenv("MAG_TUNE_ASSEMBLY");
         ctx->asm_ctile = csr_wanted && !(how_asm && strcmp(how_asm, "ctile") != 0) && (B == 256 || B == 512) &&
                          ctx->cap <= 4096 && magk::assemble_ctiles_lds(B, ctx->cap) <= 64 * 1024;
@@ -815,10 +829,15 @@ int element_phase(mag_ctx *ctx)
 
 // numeric assembly, atomic-free, K_e evaluated on the fly (no 288-byte-per-element buffer): from the CG tiles
 // (k_assemble_fan) where their image fits, otherwise per element tile with LDS staging (k_assemble_tiles).  Bit-identical.
-int gather_phase(mag_ctx *ctx)
+bool assemble_from_ctiles(const mag_ctx *ctx)
 {
     const char *how = getenv("MAG_TUNE_ASSEMBLY");
-    if (ctx->asm_ctile && ctx->use_lds && !(how && !strcmp(how, "tiles")) &&
+    return ctx->asm_ctile && ctx->use_lds && !(how && !strcmp(how, "tiles"));
+}
+
+int gather_phase(mag_ctx *ctx)
+{
+    if (assemble_from_ctiles(ctx) &&
                magk::assemble_ctiles(ctx->bcol.as<int32_t>(), ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(),
                                      ctx->xyP.as<double>(), ctx->halo_xy.as<double>(),
                                      ctx->tile_hoff.as<int32_t>(), ctx->tile_deg.as<int32_t>(), ctx->tile_off.as<int64_t>(),
@@ -835,6 +854,21 @@ int gather_phase(mag_ctx *ctx)
     }
     HIPCHK(hipGetLastError());
     return MAG_OK;
+}
+
+// K values of the variants of `vbat` (coordinates `xy`, permuted in v_xyP / v_halo) in the shared pattern, into v_kval:
+// gather_phase's choice of kernel
+void assemble_variant_values(mag_ctx *ctx, const double *xy, const magk::VariantBatch &vbat, hipStream_t s)
+{
+    if (assemble_from_ctiles(ctx) &&
+        magk::assemble_ctiles_variants(ctx->bcol.as<int32_t>(), ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(),
+                                       ctx->v_xyP.as<double>(), ctx->v_halo.as<double>(), ctx->tile_hoff.as<int32_t>(),
+                                       ctx->tile_deg.as<int32_t>(), ctx->tile_off.as<int64_t>(), ctx->ell_asm.as<uint32_t>(),
+                                       ctx->ell_pos.as<uint16_t>(), ctx->inc_off.as<int32_t>(), ctx->inc.as<uint32_t>(),
+                                       ctx->conn.as<int32_t>(), xy, ctx->N, ctx->B, ctx->T, ctx->cap, vbat, ctx->v_kval.as<double>(), s))
+        return;
+    magk::assemble_tiles_variants(ctx->bcol.as<int32_t>(), ctx->bptr.as<int32_t>(), ctx->inc_off.as<int32_t>(), ctx->inc.as<uint32_t>(),
+                                  ctx->perm.as<uint32_t>(), ctx->conn.as<int32_t>(), xy, ctx->N, vbat, ctx->v_kval.as<double>(), s);
 }
 
 // the whole mesh's tables: a run across ranks has left those of the tiles this rank needs only (order_sharded); the entry
@@ -2020,7 +2054,7 @@ int rhs_phase(mag_ctx *ctx, const double *u_in, const double *f_in, double *bP, 
 {
     hipStream_t s = ctx->stream;
     const int64_t N = ctx->N;
-    if (ctx->opt.assemble_csr != 0 || ctx->opt.cg_operator == MAG_OP_CSR) {
+    if (wants_csr(ctx)) {
         HIPCHK(ctx->bc_touch.reserve((size_t)N + 16));
         if (ctx->bc_touch_ready) {
             if (!from_order) magk::rhs_untouched(ctx->uknown.as<uint8_t>(), f_in, ctx->perm.as<uint32_t>(), N, bP, s);
@@ -2099,7 +2133,7 @@ int post_phase(mag_ctx *ctx, const double *xP, const double *u_in, const double 
     const int64_t N = ctx->N;
     if (ctx->opt.cg_operator != MAG_OP_CSR) // (the CSR operator's phase has expanded its solution into u itself)
         magk::scatter_back(xP, ctx->perm.as<uint32_t>(), ctx->uknown.as<uint8_t>(), u_in, N, u, s);
-    if (ctx->opt.assemble_csr != 0 || ctx->opt.cg_operator == MAG_OP_CSR) {
+    if (wants_csr(ctx)) {
         magk::reactions_from_csr(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->kval.as<double>(),
                                  ctx->uknown.as<uint8_t>(), u, f_in, N, f, s);
     } else {
@@ -2109,6 +2143,19 @@ int post_phase(mag_ctx *ctx, const double *xP, const double *u_in, const double 
     }
     magk::element_stress(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), u, ctx->E, ctx->nu, ctx->youngs, stress, s);
     return MAG_OK;
+}
+
+// what every run starts with (mag_run, and a set's run): it redoes the whole path -- nothing of a previous run is reused except
+// allocations, the single-case results of the context are gone
+void begin_run(mag_ctx *ctx)
+{
+    ctx->stats = {};
+    ctx->have_order = ctx->have_csr = ctx->have_run = false;
+    // a context whose on-chip kernel once found the GPU shared is not condemned to stream for ever: after a number of
+    // streamed solves (8, doubling per failure) it tries again -- at worst one more spin budget (~0.3 s).  Across ranks
+    // the failures are agreed on collectively, so every rank counts the same and retries in the same solve.
+    if (ctx->persist_failed && --ctx->persist_retry_in <= 0) ctx->persist_failed = false;
+    if (ctx->opt.verbose) printf("info: building element stiffness matrices...\n");
 }
 
 } // namespace
@@ -2146,10 +2193,8 @@ int mag_upload(mag_ctx *ctx, const mag_problem *p)
     ctx->thick = p->part_thickness;
     ctx->have_problem = true;
     ctx->have_order = ctx->have_csr = ctx->have_run = false;
-    ctx->have_cases = ctx->have_cases_run = false; // load cases belong to the mesh and mask they were set for
-    ctx->num_cases = 0;
-    ctx->have_variants = ctx->have_variants_run = false; // ... and so do design variants
-    ctx->num_variants = 0;
+    ctx->cases.reset();
+    ctx->variants.reset();
     return MAG_OK;
 }
 
@@ -2160,14 +2205,7 @@ int mag_run(mag_ctx *ctx)
     hipStream_t s = ctx->stream;
     const int64_t N = ctx->N, E = ctx->E;
     mag_stats &st = ctx->stats;
-    st = {};
-    // every run redoes the whole path: nothing of a previous run is reused except allocations
-    ctx->have_order = ctx->have_csr = ctx->have_run = false;
-    // a context whose on-chip kernel once found the GPU shared is not condemned to stream for ever: after a number of
-    // streamed solves (8, doubling per failure) it tries again -- at worst one more spin budget (~0.3 s).  Across ranks
-    // the failures are agreed on collectively, so every rank counts the same and retries in the same solve.
-    if (ctx->persist_failed && --ctx->persist_retry_in <= 0) ctx->persist_failed = false;
-    if (ctx->opt.verbose) printf("info: building element stiffness matrices...\n");
+    begin_run(ctx);
 
     HIPCHK(hipEventRecord(ctx->ev[0], s));
     ctx->order_allow_shard = true; // (every rank of the communicator is in mag_run: the sharded phase's all-reduces are safe)
@@ -2176,7 +2214,7 @@ int mag_run(mag_ctx *ctx)
     if (rc_order) return rc_order;
     HIPCHK(hipEventRecord(ctx->ev[1], s));
     if (int rc = reserve_cg(ctx)) return rc;
-    const bool csr = ctx->opt.assemble_csr != 0 || ctx->opt.cg_operator == MAG_OP_CSR;
+    const bool csr = wants_csr(ctx);
     if (csr) {
         if (int rc = csr_symbolic(ctx)) return rc;
         HIPCHK(hipEventRecord(ctx->ev[2], s)); // (K_e is evaluated inside the row assembly: ms_element is 0 and no event pair is
@@ -2268,33 +2306,63 @@ int mag_set_load_cases(mag_ctx *ctx, int32_t num_cases, const double *u_in, cons
         return fail(ctx, MAG_ERR_BAD_ARGS, "load cases run on one GPU: this context has a communicator of %d ranks", ctx->comm.nranks);
     if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "mag_set_load_cases before mag_upload");
     if (int rc = enter(ctx)) return rc;
-    ctx->have_cases = ctx->have_cases_run = false;
+    ctx->cases.have = ctx->cases.have_run = false;
     const size_t bytes = 16 * (size_t)ctx->N * (size_t)num_cases;
     const hipMemcpyKind kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     hipStream_t s = ctx->stream;
-    HIPCHK(ctx->c_uin.reserve(bytes));
-    HIPCHK(ctx->c_fin.reserve(bytes));
-    HIPCHK(hipMemcpyAsync(ctx->c_uin.p, u_in, bytes, kind, s));
-    HIPCHK(hipMemcpyAsync(ctx->c_fin.p, f_in, bytes, kind, s));
+    HIPCHK(ctx->cases.uin.reserve(bytes));
+    HIPCHK(ctx->cases.fin.reserve(bytes));
+    HIPCHK(hipMemcpyAsync(ctx->cases.uin.p, u_in, bytes, kind, s));
+    HIPCHK(hipMemcpyAsync(ctx->cases.fin.p, f_in, bytes, kind, s));
     HIPCHK(hipStreamSynchronize(s));
-    ctx->num_cases = num_cases;
-    ctx->have_cases = true;
+    ctx->cases.count = num_cases;
+    ctx->cases.have = true;
     return MAG_OK;
 }
 
 namespace {
 
-// the context's own u_in / f_in (mag_upload's) are lent to a case that runs through the single-case phases, and come back
-struct KeepLoads {
+// The uploaded problem is lent to a member that runs through the single-case phases and comes back: the context's u_in / f_in
+// (mag_upload's) take the member's values; with `whole` (design variants) its coordinates and material go into the context too.
+// keep = the uploaded u_in, f_in and -- whole -- xy
+struct LentProblem {
     mag_ctx *ctx;
-    size_t bytes;
+    DevBuf &keep;
+    const bool whole;
+    const size_t bytes; // of one of the vectors
+    const double youngs, nu, thick;
     bool armed = false;
-    ~KeepLoads()
+    LentProblem(mag_ctx *c, DevBuf &k, bool w)
+        : ctx(c), keep(k), whole(w), bytes(16 * (size_t)c->N), youngs(c->youngs), nu(c->nu), thick(c->thick)
+    {
+    }
+    int lend() // before the first member that runs alone
+    {
+        if (armed) return MAG_OK;
+        hipStream_t s = ctx->stream;
+        HIPCHK(keep.reserve((whole ? 3 : 2) * bytes));
+        if (whole) HIPCHK(hipMemcpyAsync(keep.as<char>() + 2 * bytes, ctx->xy.p, bytes, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(keep.p, ctx->uin.p, bytes, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(keep.as<char>() + bytes, ctx->fin.p, bytes, hipMemcpyDeviceToDevice, s));
+        armed = true;
+        return MAG_OK;
+    }
+    // the uploaded vectors while they are lent (nullptr: they are still in the context)
+    const double *uin() const { return armed ? keep.as<double>() : nullptr; }
+    const double *fin() const { return armed ? (const double *)(keep.as<char>() + bytes) : nullptr; }
+    const double *xy() const { return armed && whole ? (const double *)(keep.as<char>() + 2 * bytes) : nullptr; }
+    ~LentProblem()
     {
         if (!armed) return;
-        (void)hipMemcpyAsync(ctx->uin.p, ctx->c_keep.p, bytes, hipMemcpyDeviceToDevice, ctx->stream);
-        (void)hipMemcpyAsync(ctx->fin.p, ctx->c_keep.as<char>() + bytes, bytes, hipMemcpyDeviceToDevice, ctx->stream);
-        (void)hipStreamSynchronize(ctx->stream);
+        hipStream_t s = ctx->stream;
+        if (whole) (void)hipMemcpyAsync(ctx->xy.p, keep.as<char>() + 2 * bytes, bytes, hipMemcpyDeviceToDevice, s);
+        (void)hipMemcpyAsync(ctx->uin.p, keep.p, bytes, hipMemcpyDeviceToDevice, s);
+        (void)hipMemcpyAsync(ctx->fin.p, keep.as<char>() + bytes, bytes, hipMemcpyDeviceToDevice, s);
+        (void)hipStreamSynchronize(s);
+        if (!whole) return;
+        ctx->youngs = youngs;
+        ctx->nu = nu;
+        ctx->thick = thick;
     }
 };
 
@@ -2329,14 +2397,14 @@ int solve_case_alone(mag_ctx *ctx, int32_t c, mag_stats &out, bool timed_out_bef
 {
     hipStream_t s = ctx->stream;
     const size_t vb = 16 * (size_t)ctx->N;
-    HIPCHK(hipMemcpyAsync(ctx->uin.p, ctx->c_uin.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(ctx->fin.p, ctx->c_fin.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(ctx->bP.p, ctx->c_bP.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->uin.p, ctx->cases.uin.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->fin.p, ctx->cases.fin.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->bP.p, ctx->cases.bP.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
     if (int rc = cg_solve_member(ctx, c, out, timed_out_before)) return rc;
     if (ctx->opt.cg_operator == MAG_OP_CSR)
-        HIPCHK(hipMemcpyAsync(ctx->c_u.as<char>() + vb * c, ctx->u.p, vb, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(ctx->cases.u.as<char>() + vb * c, ctx->u.p, vb, hipMemcpyDeviceToDevice, s));
     else
-        HIPCHK(hipMemcpyAsync(ctx->c_x.as<char>() + vb * c, ctx->x.p, vb, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(ctx->cases.x.as<char>() + vb * c, ctx->x.p, vb, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
     return MAG_OK;
 }
@@ -2351,28 +2419,28 @@ int launch_members(mag_ctx *ctx, magk::PersistParams &P, int32_t G, int32_t c0, 
     using magk::FusedState;
     hipStream_t s = ctx->stream;
     const size_t qg_bytes = 2 * 32 * (size_t)ctx->N, rec_bytes = 2 * 64 * (size_t)G;
-    HIPCHK(ctx->c_qx.reserve(qg_bytes * n));
-    HIPCHK(ctx->c_part.reserve(rec_bytes * n));
-    HIPCHK(ctx->c_sync.reserve(64 * (size_t)n));
-    HIPCHK(ctx->c_state.reserve(sizeof(FusedState) * (size_t)n));
+    HIPCHK(ctx->launch_qx.reserve(qg_bytes * n));
+    HIPCHK(ctx->launch_part.reserve(rec_bytes * n));
+    HIPCHK(ctx->launch_sync.reserve(64 * (size_t)n));
+    HIPCHK(ctx->launch_state.reserve(sizeof(FusedState) * (size_t)n));
     std::vector<FusedState> h_st((size_t)n);
     std::vector<uint32_t> h_sync(16 * (size_t)n);
     // tags of a previous launch must not look current: zeroed before EVERY launch, as cg_phase_persist does
-    HIPCHK(hipMemsetAsync(ctx->c_qx.p, 0, qg_bytes * n, s));
-    HIPCHK(hipMemsetAsync(ctx->c_part.p, 0, rec_bytes * n, s));
-    HIPCHK(hipMemsetAsync(ctx->c_sync.p, 0, 64 * (size_t)n, s));
-    HIPCHK(hipMemsetAsync(ctx->c_state.p, 0, sizeof(FusedState) * (size_t)n, s));
-    P.qg = ctx->c_qx.as<unsigned long long>();
-    P.recg = ctx->c_part.as<unsigned long long>();
-    P.sync = ctx->c_sync.as<uint32_t>();
-    P.st = ctx->c_state.as<FusedState>();
+    HIPCHK(hipMemsetAsync(ctx->launch_qx.p, 0, qg_bytes * n, s));
+    HIPCHK(hipMemsetAsync(ctx->launch_part.p, 0, rec_bytes * n, s));
+    HIPCHK(hipMemsetAsync(ctx->launch_sync.p, 0, 64 * (size_t)n, s));
+    HIPCHK(hipMemsetAsync(ctx->launch_state.p, 0, sizeof(FusedState) * (size_t)n, s));
+    P.qg = ctx->launch_qx.as<unsigned long long>();
+    P.recg = ctx->launch_part.as<unsigned long long>();
+    P.sync = ctx->launch_sync.as<uint32_t>();
+    P.st = ctx->launch_state.as<FusedState>();
     P.hist_len = c0 == 0 ? ctx->opt.history_len : 0; // (member 0's alone: the kernel keeps it from the launch's other members)
     HIPCHK(hipEventRecord(ctx->ev[8], s));
     launch();
     HIPCHK(hipEventRecord(ctx->ev[9], s));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h_st.data(), ctx->c_state.p, sizeof(FusedState) * (size_t)n, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(h_sync.data(), ctx->c_sync.p, 64 * (size_t)n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_st.data(), ctx->launch_state.p, sizeof(FusedState) * (size_t)n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_sync.data(), ctx->launch_sync.p, 64 * (size_t)n, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     const double ms = ev_ms(ctx->ev[8], ctx->ev[9]);
     for (int32_t k = 0; k < n; ++k) {
@@ -2423,98 +2491,81 @@ int finish_member_stats(mag_ctx *ctx, std::vector<mag_stats> &stats, bool csr, c
     return status;
 }
 
-} // namespace
+// What differs between the sets when run_members solves them.  after_launch and post may be empty.
+struct MemberHooks {
+    // after the shared phases (order, tables, CSR pattern; ev[2] is recorded): the set's buffers -- and, for load cases, K and
+    // every case's right-hand side
+    std::function<int()> prepare;
+    // side by side, around ONE launch for members [c0, c0 + n): what the launch reads (P.bP and P.x at the least), the launch
+    // itself, what follows it
+    std::function<int(magk::PersistParams &P, int32_t c0, int32_t n, int eb_mode)> before_launch;
+    std::function<void(magk::PersistParams &P, int32_t n, int eb_mode)> launch;
+    std::function<int(int32_t c0, int32_t n)> after_launch;
+    // member c through the single-case phases, the uploaded problem lent to it
+    std::function<int(int32_t c, mag_stats &out, bool timed_out_before)> solve_alone;
+    // after the last solve, before ev[7]
+    std::function<int()> post;
+    // the set's phase times into a member's statistics (the stream is idle)
+    std::function<void(mag_stats &cs)> times;
+};
 
-int mag_run_cases(mag_ctx *ctx)
+// Solve the members of `set` (its state checks are the caller's): the shared phases once, then the CG solves side by side in
+// chunks of floor(CUs / G) members per launch where the on-chip kernel takes them, anything else -- and every member a launch
+// could not finish -- alone through the single-case phases with the uploaded problem lent to it (`keep`; keep.whole: every
+// member is a problem of its own, so side by side needs its K assembled and the hooks build its blocks).
+int run_members(mag_ctx *ctx, MemberSet &set, LentProblem &keep, const MemberHooks &hooks)
 {
-    using magk::FusedState;
-    if (!ctx) return MAG_ERR_BAD_ARGS;
-    if (ctx->comm.nranks > 1)
-        return fail(ctx, MAG_ERR_BAD_ARGS, "load cases run on one GPU: this context has a communicator of %d ranks", ctx->comm.nranks);
-    if (!ctx->have_problem || !ctx->have_cases) return fail(ctx, MAG_ERR_STATE, "mag_run_cases before mag_set_load_cases");
     if (int rc = enter(ctx)) return rc;
     hipStream_t s = ctx->stream;
-    const int64_t N = ctx->N, E = ctx->E;
-    const int32_t L = ctx->num_cases;
-    const size_t vb = 16 * (size_t)N, eb = 8 * (size_t)E;
-    ctx->stats = {};
-    // as in mag_run: the whole path is redone, only allocations are reused; the single-case results of the context are gone
-    ctx->have_order = ctx->have_csr = ctx->have_run = ctx->have_cases_run = false;
-    if (ctx->persist_failed && --ctx->persist_retry_in <= 0) ctx->persist_failed = false;
-    ctx->case_stats.assign((size_t)L, mag_stats{});
-    int32_t *info = ctx->cases_info;
+    const int32_t L = set.count;
+    set.have_run = false;
+    begin_run(ctx);
+    set.stats.assign((size_t)L, mag_stats{});
+    int32_t *info = set.info;
     info[0] = L;
     info[1] = info[2] = info[3] = 0;
-    if (ctx->opt.verbose) printf("info: building element stiffness matrices...\n");
 
-    // ---- once for all cases: order, symbolic, K (nothing here reads a prescribed VALUE; apply_order's b = 0.0 + f of the
-    // context's own f_in is simply not used)
+    // ---- once for all members: the Hilbert order OF THE UPLOADED COORDINATES, incidence, tile, ring and halo tables, masks, the
+    // CSR pattern, the fan classification -- nothing here reads a prescribed VALUE (apply_order's b = 0.0 + f of the context's
+    // own f_in is simply not used)
     HIPCHK(hipEventRecord(ctx->ev[0], s));
     if (int rc = ensure_order(ctx)) return rc;
     HIPCHK(hipEventRecord(ctx->ev[1], s));
     if (int rc = reserve_cg(ctx)) return rc;
-    const bool csr = ctx->opt.assemble_csr != 0 || ctx->opt.cg_operator == MAG_OP_CSR;
-    if (csr) {
+    const bool csr = wants_csr(ctx);
+    if (csr)
         if (int rc = csr_symbolic(ctx)) return rc;
-        HIPCHK(hipEventRecord(ctx->ev[2], s));
-        if (ctx->opt.verbose) printf("info: building total stiffness matrix...\n");
-        if (int rc = gather_phase(ctx)) return rc;
-        ctx->have_csr = true;
-    } else {
-        HIPCHK(hipEventRecord(ctx->ev[2], s));
-    }
-    HIPCHK(hipEventRecord(ctx->ev[4], s));
-    if (ctx->opt.verbose) printf("info: setting up system...\n");
-    HIPCHK(ctx->c_bP.reserve(vb * L));
-    HIPCHK(ctx->c_x.reserve(vb * L));
-    HIPCHK(ctx->c_u.reserve(vb * L));
-    HIPCHK(ctx->c_f.reserve(vb * L));
-    HIPCHK(ctx->c_stress.reserve(eb * L));
-    HIPCHK(ctx->u.reserve(vb)); // (the CSR operator's phase expands into the context's u)
-    auto at = [](const DevBuf &b, size_t stride, int32_t c) { return (double *)(b.as<char>() + stride * (size_t)c); };
-    // ---- per case: the right-hand side, the single-case arithmetic in the single-case order
-    for (int32_t c = 0; c < L; ++c)
-        if (int rc = rhs_phase(ctx, at(ctx->c_uin, vb, c), at(ctx->c_fin, vb, c), at(ctx->c_bP, vb, c), false)) return rc;
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->ev[5], s));
+    HIPCHK(hipEventRecord(ctx->ev[2], s));
+    if (int rc = hooks.prepare()) return rc;
     if (ctx->opt.verbose) printf("info: solving...\n");
 
-    // ---- CG.  On-chip and at least two cases fit the chip: chunks of floor(CUs / G) cases per launch of the load-case kernel,
-    // G = the workgroups one case needs, persist_k as the single-case path chose it (more tiles per workgroup would change the
-    // summation order).  Anything else: one case after another through the single-case phases.
+    // ---- CG.  On-chip and at least two members fit the chip: chunks of floor(CUs / G) members per launch, G = the workgroups
+    // one member needs, persist_k as the single-case path chose it (more tiles per workgroup would change the summation order).
+    // Anything else: one member after another through the single-case phases.
     int cus = 0;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-    const int32_t G = ctx->persist_grid;
+    const int32_t G = ctx->persist_grid, fit = G >= 1 ? cus / G : 0;
     int32_t per_launch = 0;
     magk::PersistParams P = {};
     int eb_mode = 0;
     // (ctx->persist: cg_variant 2, fp64, matrix-free, no preconditioner, not in back-off, the mesh fits -- ensure_order)
-    if (ctx->persist && ctx->opt.cg_operator != MAG_OP_CSR && ctx->opt.precision == 0 && G >= 1 && cus / G >= 2) {
+    if (ctx->persist && (csr || !keep.whole) && ctx->opt.cg_operator != MAG_OP_CSR && ctx->opt.precision == 0 && fit >= 2) {
         P.nranks = 1;
         persist_common_params(ctx, false, P);
-        if (int rc = persist_prepare_blocks(ctx, false, P, eb_mode)) return rc;
-        if (magk::persist_cases_shape(ctx->B, G, ctx->persist_k, eb_mode)) per_launch = cus / G;
+        if (int rc = persist_prepare_blocks(ctx, false, P, eb_mode, !keep.whole)) return rc;
+        if (magk::persist_cases_shape(ctx->B, G, ctx->persist_k, eb_mode)) per_launch = fit;
     }
     info[1] = per_launch;
-    KeepLoads keep{ctx, vb};
-    auto lend_loads = [&]() -> int { // before the first case that runs alone
-        if (keep.armed) return MAG_OK;
-        HIPCHK(ctx->c_keep.reserve(2 * vb));
-        HIPCHK(hipMemcpyAsync(ctx->c_keep.p, ctx->uin.p, vb, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(ctx->c_keep.as<char>() + vb, ctx->fin.p, vb, hipMemcpyDeviceToDevice, s));
-        keep.armed = true;
-        return MAG_OK;
-    };
     std::vector<uint8_t> alone((size_t)L, per_launch ? 0 : 1), timed_out((size_t)L, 0);
     if (per_launch) {
         for (int32_t c0 = 0; c0 < L; c0 += per_launch) {
             const int32_t n = std::min(per_launch, L - c0);
-            P.bP = (const double2 *)at(ctx->c_bP, vb, c0);
-            P.x = (double2 *)at(ctx->c_x, vb, c0);
-            if (int rc = launch_members(ctx, P, G, c0, n, eb_mode, ctx->case_stats, alone, timed_out,
-                                        [&] { magk::persist_launch_cases(P, ctx->B, G, n, eb_mode, s); }))
+            if (int rc = hooks.before_launch(P, c0, n, eb_mode)) return rc;
+            if (int rc = launch_members(ctx, P, G, c0, n, eb_mode, set.stats, alone, timed_out, [&] { hooks.launch(P, n, eb_mode); }))
                 return rc;
             ++info[2];
+            if (hooks.after_launch)
+                if (int rc = hooks.after_launch(c0, n)) return rc;
         }
         ctx->cg_kernel = 2;
     }
@@ -2525,72 +2576,134 @@ int mag_run_cases(mag_ctx *ctx)
             persist_back_off(ctx);
             backed_off = true;
         }
-        if (int rc = lend_loads()) return rc;
-        if (int rc = solve_case_alone(ctx, c, ctx->case_stats[(size_t)c], timed_out[(size_t)c] != 0)) return rc;
+        if (int rc = keep.lend()) return rc;
+        if (int rc = hooks.solve_alone(c, set.stats[(size_t)c], timed_out[(size_t)c] != 0)) return rc;
         if (per_launch) ++info[3];
     }
     if (per_launch && !backed_off) ctx->persist_backoff = 0; // co-resident: the next failure starts from the short wait
-    HIPCHK(hipEventRecord(ctx->ev[6], s));
     if (ctx->opt.verbose)
-        printf("info: finished conjugate gradient approximation in %lld iterations\n", (long long)ctx->case_stats[0].iterations);
-
-    // ---- per case: scatter-back, reactions, stress
-    for (int32_t c = 0; c < L; ++c)
-        if (int rc = post_phase(ctx, at(ctx->c_x, vb, c), at(ctx->c_uin, vb, c), at(ctx->c_fin, vb, c), at(ctx->c_u, vb, c),
-                                at(ctx->c_f, vb, c), at(ctx->c_stress, eb, c)))
-            return rc;
-    HIPCHK(hipGetLastError());
+        printf("info: finished conjugate gradient approximation in %lld iterations\n", (long long)set.stats[0].iterations);
+    if (hooks.post)
+        if (int rc = hooks.post()) return rc;
     HIPCHK(hipEventRecord(ctx->ev[7], s));
     HIPCHK(hipStreamSynchronize(s));
     if (ctx->opt.verbose) printf("info: solve complete\n");
 
-    for (mag_stats &cs : ctx->case_stats) {
-        cs.ms_element = 0.0;
-        cs.ms_assemble = ev_ms(ctx->ev[2], ctx->ev[4]);
-        cs.ms_bc = ev_ms(ctx->ev[4], ctx->ev[5]); // all cases' right-hand sides / post-processing
-        cs.ms_post = ev_ms(ctx->ev[6], ctx->ev[7]);
-    }
-    const int status = finish_member_stats(ctx, ctx->case_stats, csr, "load case");
-    ctx->stats = ctx->case_stats[0];
-    ctx->have_cases_run = true;
+    for (mag_stats &cs : set.stats) hooks.times(cs);
+    const int status = finish_member_stats(ctx, set.stats, csr, set.noun);
+    ctx->stats = set.stats[0];
+    set.have_run = true;
     return status;
 }
 
-int mag_download_case(mag_ctx *ctx, int32_t case_index, mag_result *r)
+// mag_download_case / mag_download_variant (`fn_name`), and the sets' other getters
+int download_member(mag_ctx *ctx, const MemberSet &set, int32_t i, mag_result *r, const char *fn_name)
 {
-    if (!ctx) return MAG_ERR_BAD_ARGS;
     if (!r) return fail(ctx, MAG_ERR_BAD_ARGS, "null result");
-    if (case_index < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "load case %d out of range", (int)case_index);
-    if (!ctx->have_cases_run) return fail(ctx, MAG_ERR_STATE, "mag_download_case before a completed mag_run_cases");
-    if (case_index >= ctx->num_cases)
-        return fail(ctx, MAG_ERR_BAD_ARGS, "load case %d out of range [0, %d)", (int)case_index, (int)ctx->num_cases);
+    if (i < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s %d out of range", set.noun, (int)i);
+    if (!set.have_run) return fail(ctx, MAG_ERR_STATE, "%s before a completed %s", fn_name, set.run_fn);
+    if (i >= set.count) return fail(ctx, MAG_ERR_BAD_ARGS, "%s %d out of range [0, %d)", set.noun, (int)i, (int)set.count);
     if (int rc = enter(ctx)) return rc;
     const hipMemcpyKind kind = r->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     hipStream_t s = ctx->stream;
-    const size_t vb = 16 * (size_t)ctx->N, eb = 8 * (size_t)ctx->E, c = (size_t)case_index;
-    if (r->u_out) HIPCHK(hipMemcpyAsync(r->u_out, ctx->c_u.as<char>() + vb * c, vb, kind, s));
-    if (r->f_out) HIPCHK(hipMemcpyAsync(r->f_out, ctx->c_f.as<char>() + vb * c, vb, kind, s));
-    if (r->stress_out) HIPCHK(hipMemcpyAsync(r->stress_out, ctx->c_stress.as<char>() + eb * c, eb, kind, s));
+    const size_t vb = 16 * (size_t)ctx->N, eb = 8 * (size_t)ctx->E, c = (size_t)i;
+    if (r->u_out) HIPCHK(hipMemcpyAsync(r->u_out, set.u.as<char>() + vb * c, vb, kind, s));
+    if (r->f_out) HIPCHK(hipMemcpyAsync(r->f_out, set.f.as<char>() + vb * c, vb, kind, s));
+    if (r->stress_out) HIPCHK(hipMemcpyAsync(r->stress_out, set.stress.as<char>() + eb * c, eb, kind, s));
     HIPCHK(hipStreamSynchronize(s));
     return MAG_OK;
 }
 
-int mag_get_case_stats(const mag_ctx *ctx, int32_t case_index, mag_stats *st)
+int member_stats(const MemberSet &set, int32_t i, mag_stats *st)
 {
-    if (!ctx || !st || case_index < 0) return MAG_ERR_BAD_ARGS;
-    if (!ctx->have_cases_run) return MAG_ERR_STATE;
-    if (case_index >= ctx->num_cases) return MAG_ERR_BAD_ARGS;
-    *st = ctx->case_stats[(size_t)case_index];
+    if (!st || i < 0) return MAG_ERR_BAD_ARGS;
+    if (!set.have_run) return MAG_ERR_STATE;
+    if (i >= set.count) return MAG_ERR_BAD_ARGS;
+    *st = set.stats[(size_t)i];
     return MAG_OK;
 }
 
-int mag_get_cases_info(const mag_ctx *ctx, int32_t info[4])
+int set_info(const MemberSet &set, int32_t info[4])
 {
-    if (!ctx || !info) return MAG_ERR_BAD_ARGS;
-    if (!ctx->have_cases_run) return MAG_ERR_STATE;
-    for (int k = 0; k < 4; ++k) info[k] = ctx->cases_info[k];
+    if (!info) return MAG_ERR_BAD_ARGS;
+    if (!set.have_run) return MAG_ERR_STATE;
+    for (int k = 0; k < 4; ++k) info[k] = set.info[k];
     return MAG_OK;
 }
+
+} // namespace
+
+int mag_run_cases(mag_ctx *ctx)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (ctx->comm.nranks > 1)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "load cases run on one GPU: this context has a communicator of %d ranks", ctx->comm.nranks);
+    if (!ctx->have_problem || !ctx->cases.have) return fail(ctx, MAG_ERR_STATE, "mag_run_cases before mag_set_load_cases");
+    hipStream_t s = ctx->stream;
+    MemberSet &set = ctx->cases;
+    const int32_t L = set.count;
+    const size_t vb = 16 * (size_t)ctx->N, eb = 8 * (size_t)ctx->E;
+    auto at = [](const DevBuf &b, size_t stride, int32_t c) { return (double *)(b.as<char>() + stride * (size_t)c); };
+    LentProblem keep(ctx, set.keep, false);
+    MemberHooks h;
+    h.prepare = [&]() -> int { // K once, then per case the right-hand side: the single-case arithmetic in the single-case order
+        if (wants_csr(ctx)) {
+            if (ctx->opt.verbose) printf("info: building total stiffness matrix...\n");
+            if (int rc = gather_phase(ctx)) return rc;
+            ctx->have_csr = true;
+        }
+        HIPCHK(hipEventRecord(ctx->ev[4], s));
+        if (ctx->opt.verbose) printf("info: setting up system...\n");
+        HIPCHK(set.bP.reserve(vb * L));
+        HIPCHK(set.x.reserve(vb * L));
+        HIPCHK(set.u.reserve(vb * L));
+        HIPCHK(set.f.reserve(vb * L));
+        HIPCHK(set.stress.reserve(eb * L));
+        HIPCHK(ctx->u.reserve(vb)); // (the CSR operator's phase expands into the context's u)
+        for (int32_t c = 0; c < L; ++c)
+            if (int rc = rhs_phase(ctx, at(set.uin, vb, c), at(set.fin, vb, c), at(set.bP, vb, c), false)) return rc;
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ctx->ev[5], s));
+        return MAG_OK;
+    };
+    h.before_launch = [&](magk::PersistParams &P, int32_t c0, int32_t, int) -> int {
+        P.bP = (const double2 *)at(set.bP, vb, c0);
+        P.x = (double2 *)at(set.x, vb, c0);
+        return MAG_OK;
+    };
+    h.launch = [&](magk::PersistParams &P, int32_t n, int eb_mode) {
+        magk::persist_launch_cases(P, ctx->B, ctx->persist_grid, n, eb_mode, s);
+    };
+    h.solve_alone = [&](int32_t c, mag_stats &out, bool timed_out_before) { return solve_case_alone(ctx, c, out, timed_out_before); };
+    h.post = [&]() -> int { // per case: scatter-back, reactions, stress
+        HIPCHK(hipEventRecord(ctx->ev[6], s));
+        for (int32_t c = 0; c < L; ++c)
+            if (int rc = post_phase(ctx, at(set.x, vb, c), at(set.uin, vb, c), at(set.fin, vb, c), at(set.u, vb, c), at(set.f, vb, c),
+                                    at(set.stress, eb, c)))
+                return rc;
+        HIPCHK(hipGetLastError());
+        return MAG_OK;
+    };
+    h.times = [&](mag_stats &cs) {
+        cs.ms_element = 0.0;
+        cs.ms_assemble = ev_ms(ctx->ev[2], ctx->ev[4]);
+        cs.ms_bc = ev_ms(ctx->ev[4], ctx->ev[5]); // all cases' right-hand sides / post-processing
+        cs.ms_post = ev_ms(ctx->ev[6], ctx->ev[7]);
+    };
+    return run_members(ctx, set, keep, h);
+}
+
+int mag_download_case(mag_ctx *ctx, int32_t case_index, mag_result *r)
+{
+    return ctx ? download_member(ctx, ctx->cases, case_index, r, "mag_download_case") : MAG_ERR_BAD_ARGS;
+}
+
+int mag_get_case_stats(const mag_ctx *ctx, int32_t case_index, mag_stats *st)
+{
+    return ctx ? member_stats(ctx->cases, case_index, st) : MAG_ERR_BAD_ARGS;
+}
+
+int mag_get_cases_info(const mag_ctx *ctx, int32_t info[4]) { return ctx ? set_info(ctx->cases, info) : MAG_ERR_BAD_ARGS; }
 
 // ---- design variants: num_variants shapes / materials / value sets of the uploaded mesh (same connectivity and u_known mask) ----
 namespace {
@@ -2632,7 +2745,7 @@ int mag_set_variants(mag_ctx *ctx, int32_t num_variants, const double *xy, const
     }
     if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "mag_set_variants before mag_upload");
     if (int rc = enter(ctx)) return rc;
-    ctx->have_variants = ctx->have_variants_run = false;
+    ctx->variants.have = ctx->variants.have_run = false;
     const int64_t N = ctx->N, E = ctx->E;
     const size_t bytes = 16 * (size_t)N * (size_t)V;
     const hipMemcpyKind kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -2665,10 +2778,10 @@ int mag_set_variants(mag_ctx *ctx, int32_t num_variants, const double *xy, const
         HIPCHK(hipMemcpyAsync(ctx->v_xy.p, xy, bytes, kind, s));
     }
     if (u_in) {
-        HIPCHK(ctx->v_uin.reserve(bytes));
-        HIPCHK(ctx->v_fin.reserve(bytes));
-        HIPCHK(hipMemcpyAsync(ctx->v_uin.p, u_in, bytes, kind, s));
-        HIPCHK(hipMemcpyAsync(ctx->v_fin.p, f_in, bytes, kind, s));
+        HIPCHK(ctx->variants.uin.reserve(bytes));
+        HIPCHK(ctx->variants.fin.reserve(bytes));
+        HIPCHK(hipMemcpyAsync(ctx->variants.uin.p, u_in, bytes, kind, s));
+        HIPCHK(hipMemcpyAsync(ctx->variants.fin.p, f_in, bytes, kind, s));
     }
     HIPCHK(hipStreamSynchronize(s)); // (the host vectors and the caller's buffers are done with)
     if (xy) {
@@ -2692,56 +2805,34 @@ int mag_set_variants(mag_ctx *ctx, int32_t num_variants, const double *xy, const
     ctx->v_mat_h = mat;
     ctx->v_have_xy = xy != nullptr;
     ctx->v_have_loads = u_in != nullptr;
-    ctx->num_variants = V;
-    ctx->have_variants = true;
+    ctx->variants.count = V;
+    ctx->variants.have = true;
     return MAG_OK;
 }
 
 namespace {
 
-// the uploaded problem is lent to a variant that runs through the single-case phases (its coordinates, material and values go
-// into the context) and comes back
-struct KeepProblem {
-    mag_ctx *ctx;
-    size_t bytes;
-    double youngs, nu, thick;
-    bool armed = false;
-    ~KeepProblem()
-    {
-        if (!armed) return;
-        hipStream_t s = ctx->stream;
-        (void)hipMemcpyAsync(ctx->xy.p, ctx->v_keep.p, bytes, hipMemcpyDeviceToDevice, s);
-        (void)hipMemcpyAsync(ctx->uin.p, ctx->v_keep.as<char>() + bytes, bytes, hipMemcpyDeviceToDevice, s);
-        (void)hipMemcpyAsync(ctx->fin.p, ctx->v_keep.as<char>() + 2 * bytes, bytes, hipMemcpyDeviceToDevice, s);
-        (void)hipStreamSynchronize(s);
-        ctx->youngs = youngs;
-        ctx->nu = nu;
-        ctx->thick = thick;
-    }
-};
-
-// where variant v's coordinates and values are: its own, or the uploaded ones
-const double *variant_xy(const mag_ctx *ctx, const KeepProblem &keep, int32_t v)
+// where variant v's coordinates and values are: its own, or the uploaded ones (kept aside while they are lent)
+const double *variant_xy(const mag_ctx *ctx, const LentProblem &keep, int32_t v)
 {
     if (ctx->v_have_xy) return ctx->v_xy.as<double>() + 2 * (size_t)ctx->N * (size_t)v;
-    return keep.armed ? ctx->v_keep.as<double>() : ctx->xy.as<double>();
+    return keep.armed ? keep.xy() : ctx->xy.as<double>();
 }
-const double *variant_loads(const mag_ctx *ctx, const KeepProblem &keep, int32_t v, bool forces)
+const double *variant_loads(const mag_ctx *ctx, const LentProblem &keep, int32_t v, bool forces)
 {
-    if (ctx->v_have_loads) return (forces ? ctx->v_fin : ctx->v_uin).as<double>() + 2 * (size_t)ctx->N * (size_t)v;
-    if (keep.armed) return ctx->v_keep.as<double>() + 2 * (size_t)ctx->N * (forces ? 2 : 1);
+    if (ctx->v_have_loads) return (forces ? ctx->variants.fin : ctx->variants.uin).as<double>() + 2 * (size_t)ctx->N * (size_t)v;
+    if (keep.armed) return forces ? keep.fin() : keep.uin();
     return (forces ? ctx->fin : ctx->uin).as<double>();
 }
 
 // one variant through the single-case phases, the shared tables kept: its coordinates (permuted into xyP and the tiles' halo
 // copies), material and values into the context, then K, right-hand side, cg_solve (its time-out fall-back, its best_param
 // repeat) and post as mag_run runs them.  The caller has armed `keep`.
-int solve_variant_alone(mag_ctx *ctx, const KeepProblem &keep, int32_t v, mag_stats &out, bool timed_out_before)
+int solve_variant_alone(mag_ctx *ctx, const LentProblem &keep, int32_t v, mag_stats &out, bool timed_out_before)
 {
     hipStream_t s = ctx->stream;
     const int64_t N = ctx->N, E = ctx->E;
     const size_t vb = 16 * (size_t)N, eb = 8 * (size_t)E;
-    const bool csr = ctx->opt.assemble_csr != 0 || ctx->opt.cg_operator == MAG_OP_CSR;
     HIPCHK(hipMemcpyAsync(ctx->xy.p, variant_xy(ctx, keep, v), vb, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(ctx->uin.p, variant_loads(ctx, keep, v, false), vb, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(ctx->fin.p, variant_loads(ctx, keep, v, true), vb, hipMemcpyDeviceToDevice, s));
@@ -2753,17 +2844,18 @@ int solve_variant_alone(mag_ctx *ctx, const KeepProblem &keep, int32_t v, mag_st
     one.halo = ctx->halo_total;
     magk::variant_coords(ctx->xy.as<double>(), ctx->perm.as<uint32_t>(), ctx->halo_g.as<int32_t>(), N,
                          ctx->use_lds ? ctx->halo_total : 0, one, ctx->xyP.as<double>(), ctx->halo_xy.as<double>(), s);
-    if (csr) {
+    if (wants_csr(ctx)) {
         if (int rc = gather_phase(ctx)) return rc;
         ctx->have_csr = true;
     }
     if (int rc = rhs_phase(ctx, ctx->uin.as<double>(), ctx->fin.as<double>(), ctx->bP.as<double>(), false)) return rc;
     HIPCHK(hipGetLastError());
     if (int rc = cg_solve_member(ctx, v, out, timed_out_before)) return rc;
+    MemberSet &set = ctx->variants;
     if (ctx->opt.cg_operator == MAG_OP_CSR) // (that operator's phase has expanded its solution into the context's u)
-        HIPCHK(hipMemcpyAsync(ctx->v_u.as<char>() + vb * (size_t)v, ctx->u.p, vb, hipMemcpyDeviceToDevice, s));
-    if (int rc = post_phase(ctx, ctx->x.as<double>(), ctx->uin.as<double>(), ctx->fin.as<double>(), ctx->v_u.as<double>() + 2 * (size_t)N * v,
-                            ctx->v_f.as<double>() + 2 * (size_t)N * v, (double *)(ctx->v_stress.as<char>() + eb * (size_t)v)))
+        HIPCHK(hipMemcpyAsync(set.u.as<char>() + vb * (size_t)v, ctx->u.p, vb, hipMemcpyDeviceToDevice, s));
+    if (int rc = post_phase(ctx, ctx->x.as<double>(), ctx->uin.as<double>(), ctx->fin.as<double>(), set.u.as<double>() + 2 * (size_t)N * v,
+                            set.f.as<double>() + 2 * (size_t)N * v, (double *)(set.stress.as<char>() + eb * (size_t)v)))
         return rc;
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
@@ -2776,223 +2868,133 @@ int mag_run_variants(mag_ctx *ctx)
 {
     if (!ctx) return MAG_ERR_BAD_ARGS;
     if (int rc = variants_refused(ctx)) return rc;
-    if (!ctx->have_problem || !ctx->have_variants) return fail(ctx, MAG_ERR_STATE, "mag_run_variants before mag_set_variants");
-    if (int rc = enter(ctx)) return rc;
+    if (!ctx->have_problem || !ctx->variants.have) return fail(ctx, MAG_ERR_STATE, "mag_run_variants before mag_set_variants");
     hipStream_t s = ctx->stream;
+    MemberSet &set = ctx->variants;
     const int64_t N = ctx->N, E = ctx->E;
-    const int32_t V = ctx->num_variants;
+    const int32_t V = set.count;
     const size_t vb = 16 * (size_t)N, eb = 8 * (size_t)E;
-    ctx->stats = {};
-    // as in mag_run: the whole path is redone, only allocations are reused; the single-case results of the context are gone
-    ctx->have_order = ctx->have_csr = ctx->have_run = ctx->have_variants_run = false;
-    if (ctx->persist_failed && --ctx->persist_retry_in <= 0) ctx->persist_failed = false;
-    ctx->variant_stats.assign((size_t)V, mag_stats{});
-    int32_t *info = ctx->variants_info;
-    info[0] = V;
-    info[1] = info[2] = info[3] = 0;
-    for (hipEvent_t &e : ctx->evV)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    if (ctx->opt.verbose) printf("info: building element stiffness matrices...\n");
-
-    // ---- once for all variants: the Hilbert order OF THE UPLOADED COORDINATES, incidence, tile, ring and halo tables, masks, the
-    // CSR pattern, the fan classification -- connectivity, mask and that one ordering only ("Design variants")
-    HIPCHK(hipEventRecord(ctx->ev[0], s));
-    if (int rc = ensure_order(ctx)) return rc;
-    HIPCHK(hipEventRecord(ctx->ev[1], s));
-    if (int rc = reserve_cg(ctx)) return rc;
-    const bool csr = ctx->opt.assemble_csr != 0 || ctx->opt.cg_operator == MAG_OP_CSR;
-    if (csr)
-        if (int rc = csr_symbolic(ctx)) return rc;
-    HIPCHK(hipEventRecord(ctx->ev[2], s));
-    HIPCHK(ctx->v_bP.reserve(vb * V));
-    HIPCHK(ctx->v_x.reserve(vb * V));
-    HIPCHK(ctx->v_u.reserve(vb * V));
-    HIPCHK(ctx->v_f.reserve(vb * V));
-    HIPCHK(ctx->v_stress.reserve(eb * V));
-    HIPCHK(ctx->u.reserve(vb));
-    HIPCHK(ctx->f.reserve(vb));
-    HIPCHK(ctx->stress.reserve(eb));
-    if (ctx->opt.verbose) printf("info: solving...\n");
-
-    // ---- side by side: on-chip, K assembled (right-hand side and reactions come from its rows), at least two variants fit the
-    // chip -- the load cases' rule, the load cases' shapes.  Anything else: one variant after another.
-    int cus = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-    const int32_t G = ctx->persist_grid;
-    int32_t per_launch = 0;
-    magk::PersistParams P = {};
-    int eb_mode = 0;
-    if (ctx->persist && csr && ctx->opt.cg_operator != MAG_OP_CSR && ctx->opt.precision == 0 && G >= 1 && cus / G >= 2) {
-        P.nranks = 1;
-        persist_common_params(ctx, false, P);
-        if (int rc = persist_prepare_blocks(ctx, false, P, eb_mode, false)) return rc;
-        if (magk::persist_cases_shape(ctx->B, G, ctx->persist_k, eb_mode)) per_launch = cus / G;
-    }
-    info[1] = per_launch;
-    KeepProblem keep{ctx, vb, ctx->youngs, ctx->nu, ctx->thick};
-    auto lend_problem = [&]() -> int { // before the first variant that runs alone
-        if (keep.armed) return MAG_OK;
-        HIPCHK(ctx->v_keep.reserve(3 * vb));
-        HIPCHK(hipMemcpyAsync(ctx->v_keep.p, ctx->xy.p, vb, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(ctx->v_keep.as<char>() + vb, ctx->uin.p, vb, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(ctx->v_keep.as<char>() + 2 * vb, ctx->fin.p, vb, hipMemcpyDeviceToDevice, s));
-        keep.armed = true;
+    LentProblem keep(ctx, set.keep, true);
+    // one chunk's members, from before_launch to after_launch
+    magk::VariantBatch vbat = {};
+    const double *xy = nullptr, *uin = nullptr, *fin = nullptr;
+    double *xP = nullptr;
+    double ms_phase[6] = {0, 0, 0, 0, 0, 0}; // permute, assemble, right-hand sides, blocks, launches, post: all chunks
+    MemberHooks h;
+    h.prepare = [&]() -> int {
+        for (hipEvent_t &e : ctx->evV)
+            if (!e) HIPCHK(hipEventCreate(&e));
+        HIPCHK(set.bP.reserve(vb * V));
+        HIPCHK(set.x.reserve(vb * V));
+        HIPCHK(set.u.reserve(vb * V));
+        HIPCHK(set.f.reserve(vb * V));
+        HIPCHK(set.stress.reserve(eb * V));
+        HIPCHK(ctx->u.reserve(vb));
+        HIPCHK(ctx->f.reserve(vb));
+        HIPCHK(ctx->stress.reserve(eb));
         return MAG_OK;
     };
-    std::vector<uint8_t> alone((size_t)V, per_launch ? 0 : 1), timed_out((size_t)V, 0);
-    double ms_phase[6] = {0, 0, 0, 0, 0, 0}; // permute, assemble, right-hand sides, blocks, launches, post: all chunks
-    if (per_launch) {
-        const int32_t nmax = std::min(per_launch, V);
+    // a chunk's coordinates, K, right-hand sides and blocks (the first chunk is the largest: its reservations hold for all)
+    h.before_launch = [&](magk::PersistParams &P, int32_t c0, int32_t n, int eb_mode) -> int {
         const int64_t npad = (int64_t)ctx->T * ctx->B, halo = std::max<int64_t>(ctx->halo_total, 1);
         const int64_t kb_words = 3 * (int64_t)magk::persist_block_entries() * npad, ovf_words = 4 * (int64_t)std::max(ctx->ovf_total, 1);
-        HIPCHK(ctx->v_xyP.reserve(vb * nmax));
-        HIPCHK(ctx->v_halo.reserve(16 * (size_t)halo * nmax));
-        HIPCHK(ctx->v_kval.reserve(8 * 4 * (size_t)ctx->nb * nmax));
-        if (eb_mode) HIPCHK(ctx->v_kblocks.reserve(8 * (size_t)kb_words * nmax));
-        if (eb_mode == 2) HIPCHK(ctx->v_ovf.reserve(8 * (size_t)ovf_words * nmax));
-        const char *how = getenv("MAG_TUNE_ASSEMBLY");
-        for (int32_t c0 = 0; c0 < V; c0 += per_launch) {
-            const int32_t n = std::min(per_launch, V - c0);
-            magk::VariantBatch vbat = {};
-            vbat.count = n;
-            vbat.mat = ctx->v_mat.as<double>() + 3 * (size_t)c0;
-            vbat.xy = ctx->v_have_xy ? 2 * N : 0;
-            vbat.loads = ctx->v_have_loads ? 2 * N : 0;
-            vbat.halo = halo;
-            vbat.kval = 4 * ctx->nb;
-            const double *xy = variant_xy(ctx, keep, c0), *uin = variant_loads(ctx, keep, c0, false),
-                         *fin = variant_loads(ctx, keep, c0, true);
-            double *bP = ctx->v_bP.as<double>() + 2 * (size_t)N * c0, *xP = ctx->v_x.as<double>() + 2 * (size_t)N * c0;
-            HIPCHK(hipEventRecord(ctx->evV[0], s));
-            magk::variant_coords(xy, ctx->perm.as<uint32_t>(), ctx->halo_g.as<int32_t>(), N, ctx->halo_total, vbat,
-                                 ctx->v_xyP.as<double>(), ctx->v_halo.as<double>(), s);
-            HIPCHK(hipEventRecord(ctx->evV[1], s));
-            // K values of every variant in the shared pattern: gather_phase's choice of kernel
-            if (!(ctx->asm_ctile && ctx->use_lds && !(how && !strcmp(how, "tiles")) &&
-                  magk::assemble_ctiles_variants(ctx->bcol.as<int32_t>(), ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(),
-                                                 ctx->v_xyP.as<double>(), ctx->v_halo.as<double>(), ctx->tile_hoff.as<int32_t>(),
-                                                 ctx->tile_deg.as<int32_t>(), ctx->tile_off.as<int64_t>(), ctx->ell_asm.as<uint32_t>(),
-                                                 ctx->ell_pos.as<uint16_t>(), ctx->inc_off.as<int32_t>(), ctx->inc.as<uint32_t>(),
-                                                 ctx->conn.as<int32_t>(), xy, N, ctx->B, ctx->T, ctx->cap, vbat,
-                                                 ctx->v_kval.as<double>(), s)))
-                magk::assemble_tiles_variants(ctx->bcol.as<int32_t>(), ctx->bptr.as<int32_t>(), ctx->inc_off.as<int32_t>(),
-                                              ctx->inc.as<uint32_t>(), ctx->perm.as<uint32_t>(), ctx->conn.as<int32_t>(), xy, N, vbat,
-                                              ctx->v_kval.as<double>(), s);
-            HIPCHK(hipEventRecord(ctx->evV[2], s));
-            HIPCHK(ctx->bc_touch.reserve((size_t)N + 16));
-            magk::rhs_variants(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->v_kval.as<double>(), ctx->uknown.as<uint8_t>(), uin,
-                               fin, ctx->perm.as<uint32_t>(), ctx->bc_touch.as<uint8_t>(), ctx->bc_touch_ready, N, vbat, bP, s);
-            HIPCHK(hipEventRecord(ctx->evV[3], s));
-            P.xyP = ctx->v_xyP.as<double2>();
-            P.halo_xy = ctx->v_halo.as<double2>();
-            P.var_mat = ctx->v_cmat.as<double>() + 3 * (size_t)c0;
-            P.var_halo_stride = halo;
-            P.var_kb_stride = kb_words;
-            P.var_ovf_stride = ovf_words;
-            if (eb_mode) {
-                P.kblocks = ctx->v_kblocks.as<double>();
-                P.kb_stride = npad;
-                if (eb_mode == 2) P.ovf_rec = ctx->v_ovf.as<double>();
-                magk::edge_blocks_build_variants(P, ctx->B, eb_mode, n, s);
-            }
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(ctx->evV[4], s));
-            P.bP = (const double2 *)bP;
-            P.x = (double2 *)xP;
-            if (int rc = launch_members(ctx, P, G, c0, n, eb_mode, ctx->variant_stats, alone, timed_out,
-                                        [&] { magk::persist_launch_variants(P, ctx->B, G, n, eb_mode, s); }))
-                return rc;
-            ++info[2];
-            // scatter-back, reactions (this chunk's K) and stress (the variant's geometry and material); a variant that is
-            // redone below gets all three again from its own solve
-            HIPCHK(hipEventRecord(ctx->evV[5], s));
-            magk::post_variants(xP, ctx->perm.as<uint32_t>(), ctx->uknown.as<uint8_t>(), uin, fin, ctx->bptr.as<int32_t>(),
-                                ctx->bcol.as<int32_t>(), ctx->v_kval.as<double>(), xy, ctx->conn.as<int32_t>(), N, E, vbat,
-                                ctx->v_u.as<double>() + 2 * (size_t)N * c0, ctx->v_f.as<double>() + 2 * (size_t)N * c0,
-                                (double *)(ctx->v_stress.as<char>() + eb * (size_t)c0), s);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(ctx->evV[6], s));
-            HIPCHK(hipStreamSynchronize(s));
-            const int pairs[6][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {4, 5}, {5, 6}};
-            for (int k = 0; k < 6; ++k) ms_phase[k] += ev_ms(ctx->evV[pairs[k][0]], ctx->evV[pairs[k][1]]);
+        HIPCHK(ctx->v_xyP.reserve(vb * n));
+        HIPCHK(ctx->v_halo.reserve(16 * (size_t)halo * n));
+        HIPCHK(ctx->v_kval.reserve(8 * 4 * (size_t)ctx->nb * n));
+        if (eb_mode) HIPCHK(ctx->v_kblocks.reserve(8 * (size_t)kb_words * n));
+        if (eb_mode == 2) HIPCHK(ctx->v_ovf.reserve(8 * (size_t)ovf_words * n));
+        vbat = {};
+        vbat.count = n;
+        vbat.mat = ctx->v_mat.as<double>() + 3 * (size_t)c0;
+        vbat.xy = ctx->v_have_xy ? 2 * N : 0;
+        vbat.loads = ctx->v_have_loads ? 2 * N : 0;
+        vbat.halo = halo;
+        vbat.kval = 4 * ctx->nb;
+        xy = variant_xy(ctx, keep, c0);
+        uin = variant_loads(ctx, keep, c0, false);
+        fin = variant_loads(ctx, keep, c0, true);
+        double *bP = set.bP.as<double>() + 2 * (size_t)N * c0;
+        xP = set.x.as<double>() + 2 * (size_t)N * c0;
+        HIPCHK(hipEventRecord(ctx->evV[0], s));
+        magk::variant_coords(xy, ctx->perm.as<uint32_t>(), ctx->halo_g.as<int32_t>(), N, ctx->halo_total, vbat, ctx->v_xyP.as<double>(),
+                             ctx->v_halo.as<double>(), s);
+        HIPCHK(hipEventRecord(ctx->evV[1], s));
+        assemble_variant_values(ctx, xy, vbat, s);
+        HIPCHK(hipEventRecord(ctx->evV[2], s));
+        HIPCHK(ctx->bc_touch.reserve((size_t)N + 16));
+        magk::rhs_variants(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->v_kval.as<double>(), ctx->uknown.as<uint8_t>(), uin,
+                           fin, ctx->perm.as<uint32_t>(), ctx->bc_touch.as<uint8_t>(), ctx->bc_touch_ready, N, vbat, bP, s);
+        HIPCHK(hipEventRecord(ctx->evV[3], s));
+        P.xyP = ctx->v_xyP.as<double2>();
+        P.halo_xy = ctx->v_halo.as<double2>();
+        P.var_mat = ctx->v_cmat.as<double>() + 3 * (size_t)c0;
+        P.var_halo_stride = halo;
+        P.var_kb_stride = kb_words;
+        P.var_ovf_stride = ovf_words;
+        if (eb_mode) {
+            P.kblocks = ctx->v_kblocks.as<double>();
+            P.kb_stride = npad;
+            if (eb_mode == 2) P.ovf_rec = ctx->v_ovf.as<double>();
+            magk::edge_blocks_build_variants(P, ctx->B, eb_mode, n, s);
         }
-        ctx->cg_kernel = 2;
-    }
-    bool backed_off = false;
-    for (int32_t v = 0; v < V; ++v) {
-        if (!alone[(size_t)v]) continue;
-        if (timed_out[(size_t)v] && !backed_off) { // the single-case path's bookkeeping: the context streams from here on
-            persist_back_off(ctx);
-            backed_off = true;
-        }
-        if (int rc = lend_problem()) return rc;
-        if (int rc = solve_variant_alone(ctx, keep, v, ctx->variant_stats[(size_t)v], timed_out[(size_t)v] != 0)) return rc;
-        if (per_launch) ++info[3];
-    }
-    if (per_launch && !backed_off) ctx->persist_backoff = 0; // co-resident: the next failure starts from the short wait
-    HIPCHK(hipEventRecord(ctx->ev[7], s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (ctx->opt.verbose) {
-        printf("info: finished conjugate gradient approximation in %lld iterations\n", (long long)ctx->variant_stats[0].iterations);
-        printf("info: solve complete\n");
-    }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ctx->evV[4], s));
+        P.bP = (const double2 *)bP;
+        P.x = (double2 *)xP;
+        return MAG_OK;
+    };
+    h.launch = [&](magk::PersistParams &P, int32_t n, int eb_mode) {
+        magk::persist_launch_variants(P, ctx->B, ctx->persist_grid, n, eb_mode, s);
+    };
+    // scatter-back, reactions (this chunk's K) and stress (the variant's geometry and material); a variant that is redone
+    // afterwards gets all three again from its own solve
+    h.after_launch = [&](int32_t c0, int32_t) -> int {
+        HIPCHK(hipEventRecord(ctx->evV[5], s));
+        magk::post_variants(xP, ctx->perm.as<uint32_t>(), ctx->uknown.as<uint8_t>(), uin, fin, ctx->bptr.as<int32_t>(),
+                            ctx->bcol.as<int32_t>(), ctx->v_kval.as<double>(), xy, ctx->conn.as<int32_t>(), N, E, vbat,
+                            set.u.as<double>() + 2 * (size_t)N * c0, set.f.as<double>() + 2 * (size_t)N * c0,
+                            (double *)(set.stress.as<char>() + eb * (size_t)c0), s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ctx->evV[6], s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (int k = 0; k < 6; ++k) ms_phase[k] += ev_ms(ctx->evV[k], ctx->evV[k + 1]);
+        return MAG_OK;
+    };
+    h.solve_alone = [&](int32_t v, mag_stats &out, bool timed_out_before) {
+        return solve_variant_alone(ctx, keep, v, out, timed_out_before);
+    };
     // side by side: the phases' times summed over the chunks, the same in every variant (ms_element: the coordinate permutation;
     // ms_cg stays the variant's own launch, the block build is counted with ms_bc) -- one after another: each variant's cg time
-    for (mag_stats &cs : ctx->variant_stats) {
+    h.times = [&](mag_stats &cs) {
         cs.ms_element = ms_phase[0];
         cs.ms_assemble = ms_phase[1];
         cs.ms_bc = ms_phase[2] + ms_phase[3];
         cs.ms_post = ms_phase[5];
-    }
-    const int status = finish_member_stats(ctx, ctx->variant_stats, csr, "variant");
-    ctx->stats = ctx->variant_stats[0];
+    };
+    const int status = run_members(ctx, set, keep, h);
     // xyP, the halo copies and K may be a variant's: nothing of this run is reused by the entry points that would
     ctx->have_order = ctx->have_csr = false;
-    ctx->have_variants_run = true;
     return status;
 }
 
 int mag_download_variant(mag_ctx *ctx, int32_t v, mag_result *r)
 {
-    if (!ctx) return MAG_ERR_BAD_ARGS;
-    if (!r) return fail(ctx, MAG_ERR_BAD_ARGS, "null result");
-    if (v < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "variant %d out of range", (int)v);
-    if (!ctx->have_variants_run) return fail(ctx, MAG_ERR_STATE, "mag_download_variant before a completed mag_run_variants");
-    if (v >= ctx->num_variants) return fail(ctx, MAG_ERR_BAD_ARGS, "variant %d out of range [0, %d)", (int)v, (int)ctx->num_variants);
-    if (int rc = enter(ctx)) return rc;
-    const hipMemcpyKind kind = r->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    hipStream_t s = ctx->stream;
-    const size_t vb = 16 * (size_t)ctx->N, eb = 8 * (size_t)ctx->E, c = (size_t)v;
-    if (r->u_out) HIPCHK(hipMemcpyAsync(r->u_out, ctx->v_u.as<char>() + vb * c, vb, kind, s));
-    if (r->f_out) HIPCHK(hipMemcpyAsync(r->f_out, ctx->v_f.as<char>() + vb * c, vb, kind, s));
-    if (r->stress_out) HIPCHK(hipMemcpyAsync(r->stress_out, ctx->v_stress.as<char>() + eb * c, eb, kind, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return MAG_OK;
+    return ctx ? download_member(ctx, ctx->variants, v, r, "mag_download_variant") : MAG_ERR_BAD_ARGS;
 }
 
 int mag_get_variant_stats(const mag_ctx *ctx, int32_t v, mag_stats *st)
 {
-    if (!ctx || !st || v < 0) return MAG_ERR_BAD_ARGS;
-    if (!ctx->have_variants_run) return MAG_ERR_STATE;
-    if (v >= ctx->num_variants) return MAG_ERR_BAD_ARGS;
-    *st = ctx->variant_stats[(size_t)v];
-    return MAG_OK;
+    return ctx ? member_stats(ctx->variants, v, st) : MAG_ERR_BAD_ARGS;
 }
 
-int mag_get_variants_info(const mag_ctx *ctx, int32_t info[4])
-{
-    if (!ctx || !info) return MAG_ERR_BAD_ARGS;
-    if (!ctx->have_variants_run) return MAG_ERR_STATE;
-    for (int k = 0; k < 4; ++k) info[k] = ctx->variants_info[k];
-    return MAG_OK;
-}
+int mag_get_variants_info(const mag_ctx *ctx, int32_t info[4]) { return ctx ? set_info(ctx->variants, info) : MAG_ERR_BAD_ARGS; }
 
 int mag_assemble_csr_variant(mag_ctx *ctx, int32_t v, int64_t *nnz, int32_t *rowptr, int32_t *col, double *val)
 {
     if (!ctx) return MAG_ERR_BAD_ARGS;
     if (int rc = variants_refused(ctx)) return rc;
-    if (!ctx->have_problem || !ctx->have_variants) return fail(ctx, MAG_ERR_STATE, "mag_assemble_csr_variant before mag_set_variants");
-    if (v < 0 || v >= ctx->num_variants) return fail(ctx, MAG_ERR_BAD_ARGS, "variant %d out of range [0, %d)", (int)v, (int)ctx->num_variants);
+    if (!ctx->have_problem || !ctx->variants.have) return fail(ctx, MAG_ERR_STATE, "mag_assemble_csr_variant before mag_set_variants");
+    if (v < 0 || v >= ctx->variants.count) return fail(ctx, MAG_ERR_BAD_ARGS, "variant %d out of range [0, %d)", (int)v, (int)ctx->variants.count);
     if (int rc = enter(ctx)) return rc;
     hipStream_t s = ctx->stream;
     // the shared tables and pattern of the uploaded mesh, then the variants' batched assembly for this one variant
@@ -3022,16 +3024,7 @@ int mag_assemble_csr_variant(mag_ctx *ctx, int32_t v, int64_t *nnz, int32_t *row
         HIPCHK(ctx->v_kval.reserve(8 * (size_t)nz));
         magk::variant_coords(xy, ctx->perm.as<uint32_t>(), ctx->halo_g.as<int32_t>(), N, ctx->use_lds ? ctx->halo_total : 0, vbat,
                              ctx->v_xyP.as<double>(), ctx->v_halo.as<double>(), s);
-        const char *how = getenv("MAG_TUNE_ASSEMBLY");
-        if (!(ctx->asm_ctile && ctx->use_lds && !(how && !strcmp(how, "tiles")) &&
-              magk::assemble_ctiles_variants(ctx->bcol.as<int32_t>(), ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(),
-                                             ctx->v_xyP.as<double>(), ctx->v_halo.as<double>(), ctx->tile_hoff.as<int32_t>(),
-                                             ctx->tile_deg.as<int32_t>(), ctx->tile_off.as<int64_t>(), ctx->ell_asm.as<uint32_t>(),
-                                             ctx->ell_pos.as<uint16_t>(), ctx->inc_off.as<int32_t>(), ctx->inc.as<uint32_t>(),
-                                             ctx->conn.as<int32_t>(), xy, N, ctx->B, ctx->T, ctx->cap, vbat, ctx->v_kval.as<double>(), s)))
-            magk::assemble_tiles_variants(ctx->bcol.as<int32_t>(), ctx->bptr.as<int32_t>(), ctx->inc_off.as<int32_t>(),
-                                          ctx->inc.as<uint32_t>(), ctx->perm.as<uint32_t>(), ctx->conn.as<int32_t>(), xy, N, vbat,
-                                          ctx->v_kval.as<double>(), s);
+        assemble_variant_values(ctx, xy, vbat, s);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(val, ctx->v_kval.p, 8 * (size_t)nz, hipMemcpyDeviceToHost, s));
     }
@@ -3063,7 +3056,7 @@ int mag_get_stats(const mag_ctx *ctx, mag_stats *st)
 int mag_get_history(mag_ctx *ctx, double *history, int64_t n)
 {
     if (int rc = enter(ctx)) return rc;
-    if (!ctx->have_run && !ctx->have_cases_run && !ctx->have_variants_run) return fail(ctx, MAG_ERR_STATE, "no completed run");
+    if (!ctx->have_run && !ctx->cases.have_run && !ctx->variants.have_run) return fail(ctx, MAG_ERR_STATE, "no completed run");
     if (n < 0 || n > ctx->opt.history_len || n > ctx->stats.iterations || (n > 0 && !history))
         return fail(ctx, MAG_ERR_BAD_ARGS, "history length %lld not available", (long long)n);
     if (n > 0) HIPCHK(hipMemcpy(history, ctx->hist.p, 8 * (size_t)n, hipMemcpyDeviceToHost));

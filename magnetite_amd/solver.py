@@ -230,6 +230,31 @@ class Context:
         out.update(self.stats())
         return out
 
+    # -- member sets (load cases, design variants): what their getters share ------
+    def _download_at(self, fn, i):
+        u, f, s = np.empty(2 * self.N), np.empty(2 * self.N), np.empty(self.E)
+        r = _lib.Result(u.ctypes.data, f.ctypes.data, s.ctypes.data, MAG_MEM_HOST, 0)
+        self._check(fn(self._h, i, C.byref(r)))
+        return u, f, s
+
+    def _stats_at(self, fn, i):
+        st = _lib.Stats()
+        self._check(fn(self._h, i, C.byref(st)))
+        return st.as_dict()
+
+    def _info(self, fn, keys):
+        info = (C.c_int32 * 4)()
+        self._check(fn(self._h, info))
+        return dict(zip(keys, info))
+
+    def _collect(self, n, download, stats):
+        """A list of dicts shaped like solve()'s, one per member."""
+        outs = []
+        for i in range(n):
+            u, f, s = download(i)
+            outs.append(dict(u=u, f=f, stress=s, **stats(i)))
+        return outs
+
     # -- load cases: several sets of prescribed values on the uploaded mesh ------
     def set_load_cases(self, u_in, f_in):
         """mag_set_load_cases: u_in, f_in of shape (L, 2N) -- prescribed displacements / forces per case, read where the
@@ -248,34 +273,21 @@ class Context:
         return self._check(self._L.mag_run_cases(self._h), allow)
 
     def download_case(self, i):
-        u, f, s = np.empty(2 * self.N), np.empty(2 * self.N), np.empty(self.E)
-        r = _lib.Result(u.ctypes.data, f.ctypes.data, s.ctypes.data, MAG_MEM_HOST, 0)
-        self._check(self._L.mag_download_case(self._h, i, C.byref(r)))
-        return u, f, s
+        return self._download_at(self._L.mag_download_case, i)
 
     def case_stats(self, i):
-        st = _lib.Stats()
-        self._check(self._L.mag_get_case_stats(self._h, i, C.byref(st)))
-        return st.as_dict()
+        return self._stats_at(self._L.mag_get_case_stats, i)
 
     def cases_info(self):
         """dict(cases, cases_per_launch (0: one after another through the single-case CG phases), launches, redone)."""
-        info = (C.c_int32 * 4)()
-        self._check(self._L.mag_get_cases_info(self._h, info))
-        return dict(cases=info[0], cases_per_launch=info[1], launches=info[2], redone=info[3])
+        return self._info(self._L.mag_get_cases_info, ("cases", "cases_per_launch", "launches", "redone"))
 
     def solve_cases(self, prob, u_in, f_in, allow_not_converged=False):
         """Upload prob's mesh, material and mask, solve the (L, 2N) load sets: a list of dicts shaped like solve()'s."""
         self.upload_problem(prob)
         self.set_load_cases(u_in, f_in)
         self.run_cases(allow_not_converged)
-        outs = []
-        for i in range(self.num_cases):
-            u, f, s = self.download_case(i)
-            out = dict(u=u, f=f, stress=s)
-            out.update(self.case_stats(i))
-            outs.append(out)
-        return outs
+        return self._collect(self.num_cases, self.download_case, self.case_stats)
 
     # -- design variants: several shapes / materials / value sets of the uploaded mesh ------
     def set_variants(self, xy=None, material=None, u_in=None, f_in=None):
@@ -312,21 +324,14 @@ class Context:
         return self._check(self._L.mag_run_variants(self._h), allow)
 
     def download_variant(self, i):
-        u, f, s = np.empty(2 * self.N), np.empty(2 * self.N), np.empty(self.E)
-        r = _lib.Result(u.ctypes.data, f.ctypes.data, s.ctypes.data, MAG_MEM_HOST, 0)
-        self._check(self._L.mag_download_variant(self._h, i, C.byref(r)))
-        return u, f, s
+        return self._download_at(self._L.mag_download_variant, i)
 
     def variant_stats(self, i):
-        st = _lib.Stats()
-        self._check(self._L.mag_get_variant_stats(self._h, i, C.byref(st)))
-        return st.as_dict()
+        return self._stats_at(self._L.mag_get_variant_stats, i)
 
     def variants_info(self):
         """dict(variants, variants_per_launch (0: one after another through the single-case phases), launches, redone)."""
-        info = (C.c_int32 * 4)()
-        self._check(self._L.mag_get_variants_info(self._h, info))
-        return dict(variants=info[0], variants_per_launch=info[1], launches=info[2], redone=info[3])
+        return self._info(self._L.mag_get_variants_info, ("variants", "variants_per_launch", "launches", "redone"))
 
     def solve_variants(self, prob, xy=None, material=None, u_in=None, f_in=None, allow_not_converged=False):
         """Upload prob (its coordinates give the ordering every variant shares), solve the variants: a list of dicts shaped
@@ -334,13 +339,7 @@ class Context:
         self.upload_problem(prob)
         self.set_variants(xy, material, u_in, f_in)
         self.run_variants(allow_not_converged)
-        outs = []
-        for i in range(self.num_variants):
-            u, f, s = self.download_variant(i)
-            out = dict(u=u, f=f, stress=s)
-            out.update(self.variant_stats(i))
-            outs.append(out)
-        return outs
+        return self._collect(self.num_variants, self.download_variant, self.variant_stats)
 
     def assemble_csr_variant(self, i):
         """K of variant i in the uploaded mesh's pattern (test entry point mag_assemble_csr_variant)."""
