@@ -41,7 +41,8 @@ extern "C" {
                              reserved word behind it, tiles_per_workgroup).  Load cases (mag_set_load_cases ...
                              mag_get_cases_info) came later as new entry points only: no struct changed, the version
                              stays 4, and a caller detects the feature by the presence of those symbols (dlsym); design
-                             variants (mag_set_variants ... mag_get_variants_info) likewise */
+                             variants (mag_set_variants ... mag_get_variants_info) and sensitivities (mag_run_sensitivities,
+                             mag_download_sensitivity) likewise */
 
 /* solver.rs:17-19 */
 #define MAG_DOF 2
@@ -296,6 +297,47 @@ int mag_run_variants(mag_ctx *ctx);
 int mag_download_variant(mag_ctx *ctx, int32_t v, mag_result *result);
 int mag_get_variant_stats(const mag_ctx *ctx, int32_t v, mag_stats *stats);
 int mag_get_variants_info(const mag_ctx *ctx, int32_t info[4]);
+
+/* ---- energy and design sensitivities of solved runs, load cases and variants ---- */
+/* What shape optimisation and material sweeps need next to the solution: the objective -- strain energy, total potential energy
+ * -- and its gradient with respect to the design, i.e. every node coordinate, E, nu and the thickness.  The problem is
+ * self-adjoint: with prescribed displacements on the u_known DOFs and prescribed forces f on the others the potential is
+ * Pi = 1/2 u^T K u - f_F^T u_F, at the solution dPi/du_F = 0, hence dPi/dtheta = 1/2 u^T (dK/dtheta) u -- no second solve.
+ *   shared: the Hilbert order, the incidence lists and the tiles' halo lists of the uploaded mesh, as the set's run left them;
+ *   per solved member: one pass over the elements, one over the nodes, one fixed-shape two-stage reduction -- launches of
+ *     several members each (grid.y), chunked by a device-memory bound.
+ * Everything follows the reference's K_e = (B^T D) B A t (solver.rs:263-278) with the SIGNED area A: a clockwise element gets
+ * the sign that K_e gives it.
+ *   energy[e]   = 1/2 u_e^T K_e u_e                                                                      (E values)
+ *   dxy[2i + d] = sum over the triangles e of node i of 1/2 u_e^T (dK_e / dx_{i,d}) u_e, u held fixed      (2N values, caller
+ *                 numbering; nodes with prescribed displacements included)
+ *   scalars[0]  W = sum of energy[e]                         scalars[4]  dPi/dE  = W / E
+ *   scalars[1]  Pi = W - scalars[2]                          scalars[5]  dPi/dnu = sum over e of 1/2 u_e^T (dK_e / dnu) u_e
+ *   scalars[2]  external work: sum of f_in u over u_known == 0      scalars[6]  dPi/dt  = W / thickness
+ *   scalars[3]  reaction work: sum of f_out u_in over u_known == 1  scalars[7]  0
+ * dxy and scalars[4..6] are the TOTAL derivatives of Pi with respect to the design at fixed prescribed values.  For the
+ * compliance C = f^T u over all DOFs that means: prescribed forces only (every prescribed displacement zero) C = -2 Pi, so
+ * dC/dtheta = -2 dPi/dtheta -- stiffening the part lowers C --; prescribed displacements only (every prescribed force zero)
+ * C = 2 Pi, so dC/dtheta = +2 dPi/dtheta.
+ *
+ * mag_run_sensitivities: set = enum mag_set.  Works on the results of the last completed mag_run / mag_run_cases /
+ *   mag_run_variants, solves nothing and alters none of those results, whether the members ran side by side or one after
+ *   another.  Every sum has a fixed order (no floating-point atomics): a repeat gives the same bits, and a member the same bits
+ *   whatever launch it shares.  A new mag_upload, a new mag_set_* or a new run of the set drops the set's sensitivities.
+ * mag_download_sensitivity: member `index` of the set (0 for MAG_SET_RUN); NULL arrays are skipped, scalars are always filled.
+ * Errors, before any HIP call: MAG_ERR_BAD_ARGS for a set that is none of enum mag_set, a negative or too large index, a null
+ *   `out`, a context whose communicator has more than one rank; MAG_ERR_STATE for no completed run of the set and for
+ *   mag_download_sensitivity before mag_run_sensitivities of it. */
+enum mag_set { MAG_SET_RUN = 0, MAG_SET_CASES = 1, MAG_SET_VARIANTS = 2 };
+typedef struct mag_sensitivity {
+    double *energy_out; /* E,  NULL: skipped */
+    double *dxy_out;    /* 2N, NULL: skipped */
+    double scalars[8];
+    int32_t memory;     /* enum mag_memory */
+    int32_t reserved;
+} mag_sensitivity;      /* 88 bytes */
+int mag_run_sensitivities(mag_ctx *ctx, int32_t set);
+int mag_download_sensitivity(mag_ctx *ctx, int32_t set, int32_t index, mag_sensitivity *out);
 
 /* ---- pieces of the path, exposed for parity tests -------------------- */
 /* solver.rs:187-193 compute_element_area (pub; the mesher imports it, mesher.rs:9,523). Host-side. */

@@ -52,6 +52,12 @@ struct MagnetiteError {  // error.rs:3-22
     }
 };
 
+// What solver::sensitivities returns per solved member: the outputs of mag_download_sensitivity, the scalars by name.
+struct Sensitivity {
+    std::vector<double> energy, dxy;
+    double strain_energy = 0, potential_energy = 0, external_work = 0, reaction_work = 0, dPi_dE = 0, dPi_dnu = 0, dPi_dt = 0;
+};
+
 // Result<(), MagnetiteError>
 using Result = std::optional<MagnetiteError>;  // nullopt == Ok(())
 
@@ -293,6 +299,72 @@ inline Result run_variants(const std::vector<Node> &nodes, const std::vector<Ele
     }
     return detail::collect_members(ctx, rc, results, E, stress, stats_out, info_out, mag_get_variants_info, mag_download_variant,
                                    mag_get_variant_stats);  // (a variant broke down: the others hold their results)
+}
+
+// Energy and design sensitivities (mag_run_sensitivities) of the part as it is -- shapes and materials both empty: one member --
+// or of its design variants, as run_variants takes them: the problem(s) are solved, then every member's element energies
+// (energy, E values), the gradient of the potential energy with respect to every node coordinate (dxy, 2N values in the order of
+// `nodes`; the problem is self-adjoint, no second solve) and the scalars of include/magnetite_hip.h by name.
+inline Result sensitivities(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                            const std::vector<std::vector<Vertex>> &shapes, const std::vector<ModelMetadata> &materials,
+                            std::vector<Sensitivity> &out, const mag_options *options = nullptr)
+{
+    auto err = detail::solver_error;
+    const bool plain = shapes.empty() && materials.empty();
+    const std::size_t V = plain ? 1 : (shapes.empty() ? materials.size() : shapes.size()), N = nodes.size(), E = elements.size();
+    if (!shapes.empty() && !materials.empty() && shapes.size() != materials.size())
+        return err("shapes and materials disagree on the number of variants");
+    std::vector<double> xy, u_in(2 * N), f_in(2 * N), vxy, vmat;
+    std::vector<std::uint8_t> u_known;
+    std::vector<std::int32_t> conn;
+    if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
+    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
+    for (std::size_t v = 0; v < shapes.size(); ++v) {
+        if (shapes[v].size() != N) return err("variant " + std::to_string(v) + " has another number of vertices");
+        for (const Vertex &p : shapes[v]) {
+            vxy.push_back(p.x);
+            vxy.push_back(p.y);
+        }
+    }
+    for (const ModelMetadata &m : materials) {
+        vmat.push_back(m.youngs_modulus);
+        vmat.push_back(m.poisson_ratio);
+        vmat.push_back(m.part_thickness);
+    }
+    mag_ctx *ctx = mag_create(options);
+    if (!ctx) return err("mag_create failed");
+    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
+    if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    const std::int32_t set = plain ? MAG_SET_RUN : MAG_SET_VARIANTS;
+    if (plain) {
+        if (mag_run(ctx) != MAG_OK) return detail::fail_and_destroy(ctx);
+    } else {
+        if (mag_set_variants(ctx, (std::int32_t)V, shapes.empty() ? nullptr : vxy.data(), materials.empty() ? nullptr : vmat.data(),
+                             nullptr, nullptr, MAG_MEM_HOST) != MAG_OK)
+            return detail::fail_and_destroy(ctx);
+        if (mag_run_variants(ctx) != MAG_OK) return detail::fail_and_destroy(ctx);
+    }
+    if (mag_run_sensitivities(ctx, set) != MAG_OK) return detail::fail_and_destroy(ctx);
+    out.assign(V, Sensitivity{});
+    for (std::size_t v = 0; v < V; ++v) {
+        Sensitivity &s = out[v];
+        s.energy.resize(E);
+        s.dxy.resize(2 * N);
+        mag_sensitivity d{};
+        d.energy_out = s.energy.data();
+        d.dxy_out = s.dxy.data();
+        d.memory = MAG_MEM_HOST;
+        if (mag_download_sensitivity(ctx, set, (std::int32_t)v, &d) != MAG_OK) return detail::fail_and_destroy(ctx);
+        s.strain_energy = d.scalars[0];
+        s.potential_energy = d.scalars[1];
+        s.external_work = d.scalars[2];
+        s.reaction_work = d.scalars[3];
+        s.dPi_dE = d.scalars[4];
+        s.dPi_dnu = d.scalars[5];
+        s.dPi_dt = d.scalars[6];
+    }
+    mag_destroy(ctx);
+    return std::nullopt;
 }
 
 }  // namespace solver

@@ -19,6 +19,7 @@ MAG_STOP_RNORM, MAG_STOP_RNORM_SQ, MAG_STOP_REL = 0, 1, 2
 MAG_OP_MATRIX_FREE, MAG_OP_CSR = 0, 1
 MAG_TERM_NONE, MAG_TERM_TARGET_COST, MAG_TERM_MAX_ITERS, MAG_TERM_BREAKDOWN = 0, 1, 2, 3
 MAG_MEM_HOST, MAG_MEM_DEVICE = 0, 1
+MAG_SET_RUN, MAG_SET_CASES, MAG_SET_VARIANTS = 0, 1, 2
 MAG_UNIQUE_ID_BYTES = 128
 MAG_IPC_HANDLE_BYTES = 64
 
@@ -31,6 +32,7 @@ SYMBOLS = [
     "mag_set_load_cases", "mag_run_cases", "mag_download_case", "mag_get_case_stats", "mag_get_cases_info",
     "mag_set_variants", "mag_run_variants", "mag_download_variant", "mag_get_variant_stats", "mag_get_variants_info",
     "mag_assemble_csr_variant",
+    "mag_run_sensitivities", "mag_download_sensitivity",
     "mag_comm_get_unique_id", "mag_comm_init_rccl", "mag_comm_query", "mag_comm_init_callback", "mag_comm_set_window", "mag_comm_inbox_create", "mag_comm_inbox_open",
 ]
 
@@ -69,6 +71,11 @@ class Stats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Sensitivity(C.Structure):
+    _fields_ = [("energy_out", C.c_void_p), ("dxy_out", C.c_void_p), ("scalars", C.c_double * 8),
+                ("memory", C.c_int32), ("reserved", C.c_int32)]
 
 
 HASHED_SOURCES = ("persist.hip", "cg.hip", "cg_device.h", "exact.hip", "symbolic.hip", "kernels.h")
@@ -144,6 +151,8 @@ def lib():
     L.mag_get_variant_stats.argtypes = [vp, C.c_int32, C.POINTER(Stats)]
     L.mag_get_variants_info.argtypes = [vp, ip]
     L.mag_assemble_csr_variant.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), ip, ip, dp]
+    L.mag_run_sensitivities.argtypes = [vp, C.c_int32]
+    L.mag_download_sensitivity.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(Sensitivity)]
     L.mag_compute_element_area.argtypes = [dp, ip]
     L.mag_compute_element_area.restype = C.c_double
     L.mag_compute_strain_displacement_matrix.argtypes = [dp, ip, C.c_double, dp]

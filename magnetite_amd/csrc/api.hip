@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "magnetite_hip.h"
 #include "primitives.h"
+#include "sens.h"
 
 using magk::CgState;
 
@@ -74,6 +75,15 @@ struct MemberSet {
     }
 };
 
+// What mag_run_sensitivities leaves for one set of solved members (enum mag_set): element energies and node gradients member
+// after member on the device, the scalars on the host.  Dropped by a new mag_upload and by a new run of the set.
+struct SensSet {
+    bool have = false;
+    int32_t count = 0;
+    DevBuf energy, dxy, scalars;
+    std::vector<double> scalars_h; // [count][8]
+};
+
 // Run-time knobs (environment, read at every call: tests switch them between calls in one process).  None is needed in
 // production; each one either is set by a test or forces a path the library can take on its own.
 //   MAG_TUNE_FORCE_DIST=1                one rank runs the distributed protocol (tests/dist_worker.py: rccl1 rehearsal)
@@ -92,6 +102,8 @@ struct MemberSet {
 //   MAG_TUNE_ASSEMBLY=tiles|ctile        numeric assembly: k_assemble_tiles / k_assemble_fan where it fits (tests)
 //   MAG_TUNE_PATTERN_SORT=1              the sort-based CSR pattern, the fall-back for rows of valence >= 16 (tests)
 //   MAG_TUNE_GRID, MAG_TUNE_DMA          streaming kernels: grid cap, LDS-DMA staging off (cg.hip; tests)
+//   MAG_TUNE_SENS_CHUNK=n                members per launch of the sensitivity kernels (tests; default: a device-memory bound)
+//   MAG_TUNE_SENS_STAGE=0                the node kernel gathers from memory as on tiles too large for the LDS (tests)
 //   MAG_LIB_PATH                         Python binding: load another build of this library (magnetite_amd/_lib.py)
 int env_int(const char *name, int dflt)
 {
@@ -122,6 +134,8 @@ struct mag_ctx {
     int64_t N = 0, E = 0;
     double youngs = 0, nu = 0, thick = 0;
     bool have_problem = false, have_order = false, have_csr = false, have_run = false;
+    // (perm, the incidence lists, the tiles and their halo lists hang on the connectivity and the uploaded coordinates only: they
+    // outlive have_order, which a variants run drops because xyP and K may be a variant's)
     DevBuf xy, conn, uknown, uin, fin;
 
     // ordering / tiles
@@ -233,6 +247,12 @@ struct mag_ctx {
     std::vector<double> v_mat_h; // [variants.count][3] = E, nu, thickness
     int32_t ovf_total = 0; // overflow records of the whole mesh (choose_edge_blocks)
     hipEvent_t evV[7] = {}; // phase boundaries of a chunk (created by the first mag_run_variants)
+
+    // energy and design sensitivities (mag_run_sensitivities) of the last mag_run, mag_run_cases, mag_run_variants; the
+    // materials, per-element nu terms and partial sums of ONE chunk of members
+    SensSet sens[3];
+    DevBuf sens_mat, sens_nuterm, sens_part, sens_tab; // sens_tab: the node kernel's tile-local corner table, of this ordering
+    bool sens_tab_ready = false;
 
     magc::Comm comm;
 };
@@ -380,6 +400,7 @@ void set_material(const mag_ctx *ctx, Params &P)
 int ensure_order(mag_ctx *ctx)
 {
     if (ctx->have_order) return MAG_OK;
+    ctx->sens_tab_ready = false;
     const int64_t N = ctx->N, E = ctx->E;
     // automatic tile size: 512-node tiles once the mesh has at least as many of them as the fused kernel keeps
     // resident (2 per CU x 256 CUs); smaller meshes are latency-bound and run faster on twice as many 256-node tiles
@@ -2151,6 +2172,7 @@ void begin_run(mag_ctx *ctx)
 {
     ctx->stats = {};
     ctx->have_order = ctx->have_csr = ctx->have_run = false;
+    ctx->sens[MAG_SET_RUN].have = false; // (the single-case results go with every run, a set's included)
     // a context whose on-chip kernel once found the GPU shared is not condemned to stream for ever: after a number of
     // streamed solves (8, doubling per failure) it tries again -- at worst one more spin budget (~0.3 s).  Across ranks
     // the failures are agreed on collectively, so every rank counts the same and retries in the same solve.
@@ -2193,8 +2215,10 @@ int mag_upload(mag_ctx *ctx, const mag_problem *p)
     ctx->thick = p->part_thickness;
     ctx->have_problem = true;
     ctx->have_order = ctx->have_csr = ctx->have_run = false;
+    ctx->sens_tab_ready = false;
     ctx->cases.reset();
     ctx->variants.reset();
+    for (SensSet &ss : ctx->sens) ss.have = false;
     return MAG_OK;
 }
 
@@ -2307,6 +2331,7 @@ int mag_set_load_cases(mag_ctx *ctx, int32_t num_cases, const double *u_in, cons
     if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "mag_set_load_cases before mag_upload");
     if (int rc = enter(ctx)) return rc;
     ctx->cases.have = ctx->cases.have_run = false;
+    ctx->sens[MAG_SET_CASES].have = false;
     const size_t bytes = 16 * (size_t)ctx->N * (size_t)num_cases;
     const hipMemcpyKind kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     hipStream_t s = ctx->stream;
@@ -2519,6 +2544,7 @@ int run_members(mag_ctx *ctx, MemberSet &set, LentProblem &keep, const MemberHoo
     hipStream_t s = ctx->stream;
     const int32_t L = set.count;
     set.have_run = false;
+    ctx->sens[&set == &ctx->cases ? MAG_SET_CASES : MAG_SET_VARIANTS].have = false;
     begin_run(ctx);
     set.stats.assign((size_t)L, mag_stats{});
     int32_t *info = set.info;
@@ -2746,6 +2772,7 @@ int mag_set_variants(mag_ctx *ctx, int32_t num_variants, const double *xy, const
     if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "mag_set_variants before mag_upload");
     if (int rc = enter(ctx)) return rc;
     ctx->variants.have = ctx->variants.have_run = false;
+    ctx->sens[MAG_SET_VARIANTS].have = false;
     const int64_t N = ctx->N, E = ctx->E;
     const size_t bytes = 16 * (size_t)N * (size_t)V;
     const hipMemcpyKind kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -3030,6 +3057,142 @@ int mag_assemble_csr_variant(mag_ctx *ctx, int32_t v, int64_t *nnz, int32_t *row
     }
     HIPCHK(hipStreamSynchronize(s));
     ctx->have_csr = false; // (no K of the uploaded problem was assembled)
+    return MAG_OK;
+}
+
+// ---- energy and design sensitivities of the solved members of a set (sens.hip) ----
+namespace {
+
+const char *const kSetRun[3] = {"mag_run", "mag_run_cases", "mag_run_variants"};
+
+// the checks mag_run_sensitivities and mag_download_sensitivity share, all before any HIP call; *count: the set's members
+int sens_refused(mag_ctx *ctx, int32_t set, const char *fn, int32_t *count)
+{
+    if (set < MAG_SET_RUN || set > MAG_SET_VARIANTS) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: set %d is none of enum mag_set", fn, (int)set);
+    if (ctx->comm.nranks > 1)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "sensitivities run on one GPU: this context has a communicator of %d ranks", ctx->comm.nranks);
+    const bool ran = set == MAG_SET_RUN ? ctx->have_run : (set == MAG_SET_CASES ? ctx->cases.have_run : ctx->variants.have_run);
+    if (!ctx->have_problem || !ran) return fail(ctx, MAG_ERR_STATE, "%s before a completed %s", fn, kSetRun[set]);
+    *count = set == MAG_SET_RUN ? 1 : (set == MAG_SET_CASES ? ctx->cases.count : ctx->variants.count);
+    return MAG_OK;
+}
+
+} // namespace
+
+int mag_run_sensitivities(mag_ctx *ctx, int32_t set)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    int32_t M = 0;
+    if (int rc = sens_refused(ctx, set, "mag_run_sensitivities", &M)) return rc;
+    if (int rc = enter(ctx)) return rc;
+    hipStream_t s = ctx->stream;
+    const int64_t N = ctx->N, E = ctx->E;
+    SensSet &out = ctx->sens[set];
+    out.have = false;
+    // The ordering phase's tables of the uploaded mesh are there: every completed run of one rank has built them whole, and
+    // they hang on the connectivity and the uploaded coordinates only (a variants run leaves them as they are).  The node
+    // kernel's tile-local corner table is built from them once per ordering, where a tile's image fits the LDS.
+    const bool staged = ctx->cap <= magk::kMaxLdsNodes && env_int("MAG_TUNE_SENS_STAGE", 1) != 0;
+    if (staged && !ctx->sens_tab_ready) {
+        HIPCHK(ctx->sens_tab.reserve(4 * (size_t)std::max<int64_t>(ctx->ell_total, 1)));
+        magk::fill_ell16(ctx->inc_off.as<int32_t>(), ctx->inc.as<uint32_t>(), ctx->conn.as<int32_t>(), ctx->iperm.as<int32_t>(),
+                         ctx->tile_deg.as<int32_t>(), ctx->tile_off.as<int64_t>(), ctx->tile_hoff.as<int32_t>(),
+                         ctx->halo_g.as<int32_t>(), N, ctx->B, ctx->T, ctx->sens_tab.as<uint32_t>(), nullptr, nullptr, s);
+        HIPCHK(hipGetLastError());
+        ctx->sens_tab_ready = true;
+    }
+    magk::SensMesh mesh = {};
+    mesh.N = N;
+    mesh.E = E;
+    mesh.conn = ctx->conn.as<int32_t>();
+    mesh.u_known = ctx->uknown.as<uint8_t>();
+    mesh.perm = ctx->perm.as<uint32_t>();
+    mesh.inc_off = ctx->inc_off.as<int32_t>();
+    mesh.inc = ctx->inc.as<uint32_t>();
+    mesh.B = ctx->B;
+    mesh.T = ctx->T;
+    mesh.cap = ctx->cap;
+    mesh.halo_g = ctx->halo_g.as<int32_t>();
+    mesh.tile_hoff = ctx->tile_hoff.as<int32_t>();
+    mesh.tile_deg = ctx->tile_deg.as<int32_t>();
+    mesh.tile_off = ctx->tile_off.as<int64_t>();
+    mesh.tab = staged ? ctx->sens_tab.as<uint32_t>() : nullptr;
+    // the members' arrays: where the set's run left them
+    const MemberSet *ms = set == MAG_SET_CASES ? &ctx->cases : (set == MAG_SET_VARIANTS ? &ctx->variants : nullptr);
+    const bool own_xy = set == MAG_SET_VARIANTS && ctx->v_have_xy;
+    const bool own_loads = set == MAG_SET_CASES || (set == MAG_SET_VARIANTS && ctx->v_have_loads);
+    const double *xy = own_xy ? ctx->v_xy.as<double>() : ctx->xy.as<double>();
+    const double *u = ms ? ms->u.as<double>() : ctx->u.as<double>(), *f = ms ? ms->f.as<double>() : ctx->f.as<double>();
+    const double *uin = own_loads ? ms->uin.as<double>() : ctx->uin.as<double>();
+    const double *fin = own_loads ? ms->fin.as<double>() : ctx->fin.as<double>();
+    // the material: a variant's own (v_mat, on the device since mag_set_variants), otherwise the uploaded one for every member
+    const bool own_mat = set == MAG_SET_VARIANTS;
+    if (!own_mat) {
+        const double mat[3] = {ctx->youngs, ctx->nu, ctx->thick};
+        HIPCHK(ctx->sens_mat.reserve(sizeof mat));
+        HIPCHK(hipMemcpy(ctx->sens_mat.p, mat, sizeof mat, hipMemcpyHostToDevice));
+    }
+    // members per launch: the scratch of one chunk (a nu term per element, the partial sums) may take a quarter of the device
+    // memory that is free now; and what grid.y holds
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const size_t per_member = 8 * (size_t)E + 8 * 4 * (size_t)magk::kSensBlocks;
+    int64_t chunk = std::max<int64_t>(1, (int64_t)(free_b / 4 / per_member));
+    chunk = std::min<int64_t>(chunk, 32768);
+    const int tuned = env_int("MAG_TUNE_SENS_CHUNK", 0);
+    if (tuned >= 1) chunk = std::min<int64_t>(tuned, 32768);
+    chunk = std::min<int64_t>(chunk, M);
+    HIPCHK(out.energy.reserve(8 * (size_t)E * M));
+    HIPCHK(out.dxy.reserve(16 * (size_t)N * M));
+    HIPCHK(out.scalars.reserve(64 * (size_t)M));
+    HIPCHK(ctx->sens_nuterm.reserve(8 * (size_t)E * chunk));
+    HIPCHK(ctx->sens_part.reserve(8 * 4 * (size_t)magk::kSensBlocks * chunk));
+    for (int32_t c0 = 0; c0 < M; c0 += (int32_t)chunk) {
+        magk::SensBatch sb = {};
+        sb.count = (int32_t)std::min<int64_t>(chunk, M - c0);
+        sb.mat_stride = own_mat ? 3 : 0;
+        sb.mat = own_mat ? ctx->v_mat.as<double>() + 3 * (size_t)c0 : ctx->sens_mat.as<double>();
+        sb.xy_stride = own_xy ? 2 * N : 0;
+        sb.xy = xy + (size_t)sb.xy_stride * c0;
+        sb.u = u + 2 * (size_t)N * c0;
+        sb.f_out = f + 2 * (size_t)N * c0;
+        sb.loads_stride = own_loads ? 2 * N : 0;
+        sb.u_in = uin + (size_t)sb.loads_stride * c0;
+        sb.f_in = fin + (size_t)sb.loads_stride * c0;
+        sb.energy = out.energy.as<double>() + (size_t)E * c0;
+        sb.dxy = out.dxy.as<double>() + 2 * (size_t)N * c0;
+        sb.scalars = out.scalars.as<double>() + 8 * (size_t)c0;
+        sb.nuterm = ctx->sens_nuterm.as<double>();
+        sb.partials = ctx->sens_part.as<double>();
+        magk::sensitivities(mesh, sb, s);
+        HIPCHK(hipGetLastError());
+    }
+    out.scalars_h.assign(8 * (size_t)M, 0.0);
+    HIPCHK(hipMemcpyAsync(out.scalars_h.data(), out.scalars.p, 64 * (size_t)M, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    out.count = M;
+    out.have = true;
+    return MAG_OK;
+}
+
+int mag_download_sensitivity(mag_ctx *ctx, int32_t set, int32_t index, mag_sensitivity *o)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "null sensitivity");
+    if (index < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "member %d out of range", (int)index);
+    int32_t M = 0;
+    if (int rc = sens_refused(ctx, set, "mag_download_sensitivity", &M)) return rc;
+    const SensSet &have = ctx->sens[set];
+    if (!have.have) return fail(ctx, MAG_ERR_STATE, "mag_download_sensitivity before mag_run_sensitivities of this set");
+    if (index >= have.count) return fail(ctx, MAG_ERR_BAD_ARGS, "member %d out of range [0, %d)", (int)index, (int)have.count);
+    if (int rc = enter(ctx)) return rc;
+    const hipMemcpyKind kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    hipStream_t s = ctx->stream;
+    const size_t eb = 8 * (size_t)ctx->E, vb = 16 * (size_t)ctx->N, i = (size_t)index;
+    if (o->energy_out) HIPCHK(hipMemcpyAsync(o->energy_out, have.energy.as<char>() + eb * i, eb, kind, s));
+    if (o->dxy_out) HIPCHK(hipMemcpyAsync(o->dxy_out, have.dxy.as<char>() + vb * i, vb, kind, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int k = 0; k < 8; ++k) o->scalars[k] = have.scalars_h[8 * i + k];
     return MAG_OK;
 }
 

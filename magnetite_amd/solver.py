@@ -352,6 +352,37 @@ class Context:
                                                      _p(val, C.c_double)))
         return rowptr, col, val
 
+    # -- energy and design sensitivities of the solved members of a set ------------
+    SENSITIVITY_SETS = {"run": _lib.MAG_SET_RUN, "cases": _lib.MAG_SET_CASES, "variants": _lib.MAG_SET_VARIANTS}
+    SENSITIVITY_SCALARS = ("strain_energy", "potential_energy", "external_work", "reaction_work", "dPi_dE", "dPi_dnu",
+                           "dPi_dt")
+
+    def _sensitivity_set(self, set):
+        if set not in self.SENSITIVITY_SETS:
+            raise MagnetiteError("Solver", f"sensitivities: set must be one of {sorted(self.SENSITIVITY_SETS)}")
+        return self.SENSITIVITY_SETS[set]
+
+    def run_sensitivities(self, set="run"):
+        """mag_run_sensitivities on the last completed run() / run_cases() / run_variants(): solves nothing."""
+        self._check(self._L.mag_run_sensitivities(self._h, self._sensitivity_set(set)))
+
+    def download_sensitivity(self, set, i):
+        """dict(energy (E), dxy (2N), strain_energy, potential_energy, external_work, reaction_work, dPi_dE, dPi_dnu, dPi_dt)
+        of member i of the set."""
+        which = self._sensitivity_set(set)
+        energy, dxy = np.empty(self.E), np.empty(2 * self.N)
+        o = _lib.Sensitivity(energy.ctypes.data, dxy.ctypes.data, (C.c_double * 8)(), MAG_MEM_HOST, 0)
+        self._check(self._L.mag_download_sensitivity(self._h, which, i, C.byref(o)))
+        return dict(energy=energy, dxy=dxy, **dict(zip(self.SENSITIVITY_SCALARS, o.scalars)))
+
+    def sensitivities(self, set="run"):
+        """Energy and design gradient of every solved member of the set ("run": the one of run(); "cases"; "variants"): a list
+        of dicts as download_sensitivity returns them.  dxy, dPi_dE, dPi_dnu, dPi_dt are the total derivatives of the potential
+        energy with respect to the node coordinates and the material (include/magnetite_hip.h)."""
+        self.run_sensitivities(set)
+        n = 1 if set == "run" else (self.num_cases if set == "cases" else self.num_variants)
+        return [self.download_sensitivity(set, i) for i in range(n)]
+
     # -- pieces, for parity tests ----------------------------------------------
     def element_stiffness(self):
         ke = np.empty(36 * self.E)
