@@ -41,8 +41,9 @@ extern "C" {
                              reserved word behind it, tiles_per_workgroup).  Load cases (mag_set_load_cases ...
                              mag_get_cases_info) came later as new entry points only: no struct changed, the version
                              stays 4, and a caller detects the feature by the presence of those symbols (dlsym); design
-                             variants (mag_set_variants ... mag_get_variants_info) and sensitivities (mag_run_sensitivities,
-                             mag_download_sensitivity) likewise */
+                             variants (mag_set_variants ... mag_get_variants_info), sensitivities (mag_run_sensitivities,
+                             mag_download_sensitivity) and adjoint sensitivities (mag_run_adjoint ... mag_get_adjoint_info)
+                             likewise */
 
 /* solver.rs:17-19 */
 #define MAG_DOF 2
@@ -338,6 +339,64 @@ typedef struct mag_sensitivity {
 } mag_sensitivity;      /* 88 bytes */
 int mag_run_sensitivities(mag_ctx *ctx, int32_t set);
 int mag_download_sensitivity(mag_ctx *ctx, int32_t set, int32_t index, mag_sensitivity *out);
+
+/* ---- adjoint sensitivities: the gradient of ANY objective of solved runs, load cases and variants ---- */
+/* The potential energy above is the one self-adjoint objective.  Any other J(u) -- a displacement at a point, a target-shape
+ * mismatch |u - u*|^2, a stress aggregate, a displacement constraint -- needs one more solve per member, with the member's own K:
+ * member i of a solved set has u (all DOFs, prescribed values included) and K (its coordinates, E, nu, thickness); the caller
+ * gives g = dJ/du (2N, caller numbering) evaluated at that u.  Split the DOFs into F (u_known == 0) and P (u_known == 1).  With
+ * the prescribed values held fixed, K_FF u_F = f_F - K_FP u_P gives du_F/dtheta = -K_FF^-1 (dK/dtheta u)_F, hence with the adjoint
+ *   K_FF lambda_F = g_F,   lambda_P = 0:        dJ/dtheta = g_F^T du_F/dtheta = -lambda^T (dK/dtheta) u.
+ * Explicit partials (dJ/dtheta at fixed u) are the caller's to add.  Likewise dJ/df_F = K_FF^-1 g_F = lambda_F, and
+ * dJ/du_P = g_P - K_PF lambda_F = g_P - (K lambda)_P, the second term being the reactions of the adjoint solve.
+ * The bilinear form follows the reference's K_e with the SIGNED area, in the notation of the sensitivities: for a vector v
+ *   p_v = sum b_i vx_i,  q_v = sum g_i vy_i,  r_v = sum (g_i vx_i + b_i vy_i),   A2 = 2A,  om = 1 - nu^2,
+ *   Qb = p_l p_u + q_l q_u + nu (p_l q_u + q_l p_u) + (1 - nu) / 2 r_l r_u,      lambda_e^T K_e u_e = E t Qb / (2 A2 om),
+ * and the coordinate and nu derivatives are its closed-form derivatives.  Per member:
+ *   lambda      the adjoint solution, 0 on the prescribed DOFs                                          (2N values)
+ *   dloads[i]   dJ/df_in[i] = lambda[i] where u_known == 0; dJ/du_in[i] = g[i] - (K lambda)[i] where u_known == 1  (2N values)
+ *   delem[e]    -lambda_e^T K_e u_e: dJ with respect to a relative stiffness scale of element e -- what a density or
+ *               thickness-field method consumes                                                        (E values)
+ *   dxy[2i + d] -(sum over the triangles e of node i of lambda_e^T (dK_e / dx_{i,d}) u_e), nodes with prescribed
+ *               displacements included                                                                  (2N values)
+ *   scalars[0]  a = sum over e of lambda_e^T K_e u_e          scalars[2]  dJ/dnu = -(sum over e of lambda_e^T (dK_e / dnu) u_e)
+ *   scalars[1]  dJ/dE = -a / E                                scalars[3]  dJ/dt  = -a / thickness;   scalars[4..7] = 0
+ *
+ * mag_run_adjoint: set = enum mag_set, after a completed run of that set; dJ_du [members][2N] (one row for MAG_SET_RUN), memory:
+ *   enum mag_memory.  One objective per member per call: a second objective is a second call, which replaces the first's results.
+ *   The adjoint systems are load sets (u_in = 0, f_in = g; entries of g on prescribed DOFs do not enter the solve) and run through
+ *   the driver of the sets: for MAG_SET_RUN and MAG_SET_CASES as load cases -- K once, all members side by side, floor(CUs / G)
+ *   per on-chip launch --, for MAG_SET_VARIANTS as variants with the set's coordinates and materials -- one launch per phase and
+ *   chunk, device memory bounded by one chunk's K.  The fall-backs are the sets' (a mesh of more than CUs / 2 workgroups, the fp32
+ *   leg, the CSR operator, a preconditioner, cg_variant 0 / 1, back-off): one member after another.  lambda of member i is BIT FOR
+ *   BIT the u that mag_run_cases returns for the case (0, g_i) on the same upload, respectively mag_run_variants for that variant
+ *   with the loads (0, g_i); mag_get_adjoint_stats / mag_get_adjoint_info (as mag_get_case_stats / mag_get_cases_info) report those
+ *   solves.  The status follows mag_run_cases: the first failing member's, the others complete.
+ *   STOP RULE: the adjoint solve stops by the context's rule like any case.  Under the two absolute rules (MAG_STOP_RNORM,
+ *   MAG_STOP_RNORM_SQ) the accuracy of lambda therefore depends on the SCALE of g: a g of norm 1e-6 "converges" at once under an
+ *   absolute 1e-4.  Scale the objective so that |g_F| is of the size of the primal right-hand side (mag_stats.rhs_norm), or use
+ *   MAG_STOP_REL.
+ *   Nothing else changes: the set's primal results, statistics and info words, its sensitivities, the other sets and -- although
+ *   a set's run otherwise drops them -- mag_download, mag_get_stats, mag_get_history and the sensitivities of MAG_SET_RUN are bit for
+ *   bit what they were.  The bilinear pass has no floating-point atomics: a repeat gives the same bits, a member the same bits
+ *   whatever launch it shares.  A new mag_upload, a new mag_set_* of the set or a new run of the set drops the set's adjoint results
+ *   (any set's run drops those of MAG_SET_RUN with the single-case results).
+ * mag_download_adjoint: member `index` of the set (0 for MAG_SET_RUN); NULL arrays are skipped, scalars are always filled.
+ * Errors, before any HIP call: MAG_ERR_BAD_ARGS for a set that is none of enum mag_set, a null dJ_du / out / stats / info, an index
+ *   out of range, a context whose communicator has more than one rank; MAG_ERR_STATE for no completed run of the set, and for
+ *   download, stats or info before mag_run_adjoint of that set. */
+typedef struct mag_adjoint {
+    double *lambda_out; /* 2N, NULL: skipped */
+    double *dloads_out; /* 2N */
+    double *delem_out;  /* E  */
+    double *dxy_out;    /* 2N */
+    double scalars[8];
+    int32_t memory, reserved;
+} mag_adjoint;          /* 104 bytes */
+int mag_run_adjoint(mag_ctx *ctx, int32_t set, const double *dJ_du /* [members][2N] */, int32_t memory);
+int mag_download_adjoint(mag_ctx *ctx, int32_t set, int32_t index, mag_adjoint *out);
+int mag_get_adjoint_stats(const mag_ctx *ctx, int32_t set, int32_t index, mag_stats *stats);
+int mag_get_adjoint_info(const mag_ctx *ctx, int32_t set, int32_t info[4]); /* as mag_get_cases_info */
 
 /* ---- pieces of the path, exposed for parity tests -------------------- */
 /* solver.rs:187-193 compute_element_area (pub; the mesher imports it, mesher.rs:9,523). Host-side. */

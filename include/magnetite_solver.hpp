@@ -11,8 +11,10 @@
 //                       afterwards every node.ux/uy/fx/fy and element.stress holds a value (solver.rs:476-482,532-533)
 // The Rust shim a Magnetite maintainer would add instead is shown in INTEGRATION.md.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
+#include <functional>
 #include <optional>
 #include <string>
 #include <variant>
@@ -57,6 +59,16 @@ struct Sensitivity {
     std::vector<double> energy, dxy;
     double strain_energy = 0, potential_energy = 0, external_work = 0, reaction_work = 0, dPi_dE = 0, dPi_dnu = 0, dPi_dt = 0;
 };
+
+// What solver::adjoint returns per solved member: the outputs of mag_download_adjoint, the scalars by name.
+struct Adjoint {
+    std::vector<double> lambda, dloads, delem, dxy;
+    double a = 0, dJ_dE = 0, dJ_dnu = 0, dJ_dt = 0;
+};
+
+// The objective of solver::adjoint: dJ/du (2N, already sized and zeroed, in the order of `nodes`) of member `member` at its
+// solved displacements u (2N, prescribed values included).
+using ObjectiveGradient = std::function<void(std::size_t member, const std::vector<double> &u, std::vector<double> &dJ_du)>;
 
 // Result<(), MagnetiteError>
 using Result = std::optional<MagnetiteError>;  // nullopt == Ok(())
@@ -362,6 +374,90 @@ inline Result sensitivities(const std::vector<Node> &nodes, const std::vector<El
         s.dPi_dE = d.scalars[4];
         s.dPi_dnu = d.scalars[5];
         s.dPi_dt = d.scalars[6];
+    }
+    mag_destroy(ctx);
+    return std::nullopt;
+}
+
+// Adjoint sensitivities (mag_run_adjoint) of any objective J of the part as it is -- shapes and materials both empty: one member
+// -- or of its design variants, as sensitivities() takes them: the problem(s) are solved, `objective` gives dJ/du at every
+// member's u, one adjoint solve per member with the member's own K follows (side by side on the chip where the sets' solves
+// are), then per member lambda, dJ/d(loads) (dloads), dJ/d(relative stiffness of an element) (delem), dJ/d(node coordinates)
+// (dxy) and dJ/dE, dJ/dnu, dJ/dt -- total derivatives at fixed prescribed values; J's explicit dependence on the design is the
+// caller's to add (include/magnetite_hip.h).  Under an absolute stop rule scale J so that |dJ/du| is of the size of the loads.
+inline Result adjoint(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                      const std::vector<std::vector<Vertex>> &shapes, const std::vector<ModelMetadata> &materials,
+                      const ObjectiveGradient &objective, std::vector<Adjoint> &out, const mag_options *options = nullptr)
+{
+    auto err = detail::solver_error;
+    const bool plain = shapes.empty() && materials.empty();
+    const std::size_t V = plain ? 1 : (shapes.empty() ? materials.size() : shapes.size()), N = nodes.size(), E = elements.size();
+    if (!shapes.empty() && !materials.empty() && shapes.size() != materials.size())
+        return err("shapes and materials disagree on the number of variants");
+    if (!objective) return err("no objective");
+    std::vector<double> xy, u_in(2 * N), f_in(2 * N), vxy, vmat;
+    std::vector<std::uint8_t> u_known;
+    std::vector<std::int32_t> conn;
+    if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
+    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
+    for (std::size_t v = 0; v < shapes.size(); ++v) {
+        if (shapes[v].size() != N) return err("variant " + std::to_string(v) + " has another number of vertices");
+        for (const Vertex &p : shapes[v]) {
+            vxy.push_back(p.x);
+            vxy.push_back(p.y);
+        }
+    }
+    for (const ModelMetadata &m : materials) {
+        vmat.push_back(m.youngs_modulus);
+        vmat.push_back(m.poisson_ratio);
+        vmat.push_back(m.part_thickness);
+    }
+    mag_ctx *ctx = mag_create(options);
+    if (!ctx) return err("mag_create failed");
+    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
+    if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    const std::int32_t set = plain ? MAG_SET_RUN : MAG_SET_VARIANTS;
+    if (plain) {
+        if (mag_run(ctx) != MAG_OK) return detail::fail_and_destroy(ctx);
+    } else {
+        if (mag_set_variants(ctx, (std::int32_t)V, shapes.empty() ? nullptr : vxy.data(), materials.empty() ? nullptr : vmat.data(),
+                             nullptr, nullptr, MAG_MEM_HOST) != MAG_OK)
+            return detail::fail_and_destroy(ctx);
+        if (mag_run_variants(ctx) != MAG_OK) return detail::fail_and_destroy(ctx);
+    }
+    std::vector<double> u(2 * N), g(V * 2 * N, 0.0), g_v;
+    for (std::size_t v = 0; v < V; ++v) {
+        mag_result r{};
+        r.u_out = u.data();
+        r.memory = MAG_MEM_HOST;
+        if ((plain ? mag_download(ctx, &r) : mag_download_variant(ctx, (std::int32_t)v, &r)) != MAG_OK) return detail::fail_and_destroy(ctx);
+        g_v.assign(2 * N, 0.0);
+        objective(v, u, g_v);
+        if (g_v.size() != 2 * N) {
+            mag_destroy(ctx);
+            return err("the objective resized dJ/du");
+        }
+        std::copy(g_v.begin(), g_v.end(), g.begin() + v * 2 * N);
+    }
+    if (mag_run_adjoint(ctx, set, g.data(), MAG_MEM_HOST) != MAG_OK) return detail::fail_and_destroy(ctx);
+    out.assign(V, Adjoint{});
+    for (std::size_t v = 0; v < V; ++v) {
+        Adjoint &s = out[v];
+        s.lambda.resize(2 * N);
+        s.dloads.resize(2 * N);
+        s.delem.resize(E);
+        s.dxy.resize(2 * N);
+        mag_adjoint d{};
+        d.lambda_out = s.lambda.data();
+        d.dloads_out = s.dloads.data();
+        d.delem_out = s.delem.data();
+        d.dxy_out = s.dxy.data();
+        d.memory = MAG_MEM_HOST;
+        if (mag_download_adjoint(ctx, set, (std::int32_t)v, &d) != MAG_OK) return detail::fail_and_destroy(ctx);
+        s.a = d.scalars[0];
+        s.dJ_dE = d.scalars[1];
+        s.dJ_dnu = d.scalars[2];
+        s.dJ_dt = d.scalars[3];
     }
     mag_destroy(ctx);
     return std::nullopt;

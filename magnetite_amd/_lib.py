@@ -33,6 +33,7 @@ SYMBOLS = [
     "mag_set_variants", "mag_run_variants", "mag_download_variant", "mag_get_variant_stats", "mag_get_variants_info",
     "mag_assemble_csr_variant",
     "mag_run_sensitivities", "mag_download_sensitivity",
+    "mag_run_adjoint", "mag_download_adjoint", "mag_get_adjoint_stats", "mag_get_adjoint_info",
     "mag_comm_get_unique_id", "mag_comm_init_rccl", "mag_comm_query", "mag_comm_init_callback", "mag_comm_set_window", "mag_comm_inbox_create", "mag_comm_inbox_open",
 ]
 
@@ -76,6 +77,11 @@ class Stats(C.Structure):
 class Sensitivity(C.Structure):
     _fields_ = [("energy_out", C.c_void_p), ("dxy_out", C.c_void_p), ("scalars", C.c_double * 8),
                 ("memory", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Adjoint(C.Structure):
+    _fields_ = [("lambda_out", C.c_void_p), ("dloads_out", C.c_void_p), ("delem_out", C.c_void_p), ("dxy_out", C.c_void_p),
+                ("scalars", C.c_double * 8), ("memory", C.c_int32), ("reserved", C.c_int32)]
 
 
 HASHED_SOURCES = ("persist.hip", "cg.hip", "cg_device.h", "exact.hip", "symbolic.hip", "kernels.h")
@@ -153,6 +159,11 @@ def lib():
     L.mag_assemble_csr_variant.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), ip, ip, dp]
     L.mag_run_sensitivities.argtypes = [vp, C.c_int32]
     L.mag_download_sensitivity.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(Sensitivity)]
+    if hasattr(L, "mag_run_adjoint"):  # (an earlier build loaded through MAG_LIB_PATH has none: scripts/adjoint_probe.py)
+        L.mag_run_adjoint.argtypes = [vp, C.c_int32, dp, C.c_int32]
+        L.mag_download_adjoint.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(Adjoint)]
+        L.mag_get_adjoint_stats.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(Stats)]
+        L.mag_get_adjoint_info.argtypes = [vp, C.c_int32, ip]
     L.mag_compute_element_area.argtypes = [dp, ip]
     L.mag_compute_element_area.restype = C.c_double
     L.mag_compute_strain_displacement_matrix.argtypes = [dp, ip, C.c_double, dp]
@@ -173,8 +184,8 @@ def lib():
     L.mag_comm_inbox_create.argtypes = [vp, C.c_uint64, vp]
     L.mag_comm_inbox_open.argtypes = [vp, vp]
     for name in SYMBOLS:
-        fn = getattr(L, name)
-        if fn.restype is C.c_int and name not in ("mag_version",):
+        fn = getattr(L, name, None)
+        if fn is not None and fn.restype is C.c_int and name not in ("mag_version",):
             fn.restype = C.c_int
     _lib = L
     return L

@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "magnetite_hip.h"
 #include "primitives.h"
+#include "adjoint.h"
 #include "sens.h"
 
 using magk::CgState;
@@ -59,10 +60,14 @@ struct DevBuf {
 
 // What a set of solves on ONE uploaded mesh owns (load cases, design variants): `count` members, member after member in every
 // buffer -- inputs, the uploaded problem while it is lent to a member that runs alone (keep), right-hand sides and solutions
-// (Hilbert numbering), results (caller numbering) --, every member's statistics and the four words of mag_get_*_info
+// (Hilbert numbering), results (caller numbering) --, every member's statistics and the four words of mag_get_*_info.  An
+// adjoint set (mag_run_adjoint) is one more of them per enum mag_set value: u_in = 0, f_in = dJ/du, solved by the hooks of
+// the set whose members it differentiates.
 struct MemberSet {
     const char *noun;   // in messages: "load case" / "variant"
     const char *run_fn; // the entry point that solves the set
+    int32_t slot;       // enum mag_set: whose sensitivities and adjoint results a run of this set drops
+    bool adjoint = false;
     int32_t count = 0;
     bool have = false, have_run = false;
     DevBuf uin, fin, keep, bP, x, u, f, stress;
@@ -81,6 +86,15 @@ struct SensSet {
     bool have = false;
     int32_t count = 0;
     DevBuf energy, dxy, scalars;
+    std::vector<double> scalars_h; // [count][8]
+};
+
+// What mag_run_adjoint leaves for one set next to its adjoint MemberSet (lambda = that set's u, the adjoint reactions its f, dJ/du
+// its f_in): the derivatives member after member on the device, the scalars on the host.  Dropped as SensSet is.
+struct AdjointSet {
+    bool have = false;
+    int32_t count = 0;
+    DevBuf dloads, delem, dxy, scalars;
     std::vector<double> scalars_h; // [count][8]
 };
 
@@ -234,7 +248,7 @@ struct mag_ctx {
     // load cases (mag_set_load_cases / mag_run_cases): sets of prescribed values on the uploaded mesh; design variants
     // (mag_set_variants / mag_run_variants): shapes / materials / value sets of it (variants.uin / fin only when given).  Two
     // sets: load cases survive a variants run
-    MemberSet cases{"load case", "mag_run_cases"}, variants{"variant", "mag_run_variants"};
+    MemberSet cases{"load case", "mag_run_cases", MAG_SET_CASES}, variants{"variant", "mag_run_variants", MAG_SET_VARIANTS};
     // the on-chip kernel's granules, records, timeout words and states for the members of ONE launch, of either set
     DevBuf launch_qx, launch_part, launch_sync, launch_state;
 
@@ -253,6 +267,14 @@ struct mag_ctx {
     SensSet sens[3];
     DevBuf sens_mat, sens_nuterm, sens_part, sens_tab; // sens_tab: the node kernel's tile-local corner table, of this ordering
     bool sens_tab_ready = false;
+
+    // adjoint sensitivities (mag_run_adjoint) of the same three sets: the adjoint systems as member sets of their own, what the
+    // bilinear pass made of them, and the single-case results kept aside while the adjoint systems run
+    MemberSet adj[3] = {{"adjoint", "mag_run_adjoint", MAG_SET_RUN, true},
+                        {"adjoint", "mag_run_adjoint", MAG_SET_CASES, true},
+                        {"adjoint", "mag_run_adjoint", MAG_SET_VARIANTS, true}};
+    AdjointSet adjres[3];
+    DevBuf adj_keep;
 
     magc::Comm comm;
 };
@@ -2173,6 +2195,7 @@ void begin_run(mag_ctx *ctx)
     ctx->stats = {};
     ctx->have_order = ctx->have_csr = ctx->have_run = false;
     ctx->sens[MAG_SET_RUN].have = false; // (the single-case results go with every run, a set's included)
+    ctx->adjres[MAG_SET_RUN].have = false;
     // a context whose on-chip kernel once found the GPU shared is not condemned to stream for ever: after a number of
     // streamed solves (8, doubling per failure) it tries again -- at worst one more spin budget (~0.3 s).  Across ranks
     // the failures are agreed on collectively, so every rank counts the same and retries in the same solve.
@@ -2219,6 +2242,7 @@ int mag_upload(mag_ctx *ctx, const mag_problem *p)
     ctx->cases.reset();
     ctx->variants.reset();
     for (SensSet &ss : ctx->sens) ss.have = false;
+    for (AdjointSet &as : ctx->adjres) as.have = false;
     return MAG_OK;
 }
 
@@ -2332,6 +2356,7 @@ int mag_set_load_cases(mag_ctx *ctx, int32_t num_cases, const double *u_in, cons
     if (int rc = enter(ctx)) return rc;
     ctx->cases.have = ctx->cases.have_run = false;
     ctx->sens[MAG_SET_CASES].have = false;
+    ctx->adjres[MAG_SET_CASES].have = false;
     const size_t bytes = 16 * (size_t)ctx->N * (size_t)num_cases;
     const hipMemcpyKind kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     hipStream_t s = ctx->stream;
@@ -2418,18 +2443,18 @@ int cg_solve_member(mag_ctx *ctx, int32_t c, mag_stats &out, bool timed_out_befo
 
 // one case through the single-case CG phases (cg_solve: the phase the options select, its time-out fall-back, best_param):
 // its loads and right-hand side into the context's buffers, its solution out of them.
-int solve_case_alone(mag_ctx *ctx, int32_t c, mag_stats &out, bool timed_out_before)
+int solve_case_alone(mag_ctx *ctx, MemberSet &set, int32_t c, mag_stats &out, bool timed_out_before)
 {
     hipStream_t s = ctx->stream;
     const size_t vb = 16 * (size_t)ctx->N;
-    HIPCHK(hipMemcpyAsync(ctx->uin.p, ctx->cases.uin.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(ctx->fin.p, ctx->cases.fin.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(ctx->bP.p, ctx->cases.bP.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->uin.p, set.uin.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->fin.p, set.fin.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->bP.p, set.bP.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
     if (int rc = cg_solve_member(ctx, c, out, timed_out_before)) return rc;
     if (ctx->opt.cg_operator == MAG_OP_CSR)
-        HIPCHK(hipMemcpyAsync(ctx->cases.u.as<char>() + vb * c, ctx->u.p, vb, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(set.u.as<char>() + vb * c, ctx->u.p, vb, hipMemcpyDeviceToDevice, s));
     else
-        HIPCHK(hipMemcpyAsync(ctx->cases.x.as<char>() + vb * c, ctx->x.p, vb, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(set.x.as<char>() + vb * c, ctx->x.p, vb, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
     return MAG_OK;
 }
@@ -2544,7 +2569,10 @@ int run_members(mag_ctx *ctx, MemberSet &set, LentProblem &keep, const MemberHoo
     hipStream_t s = ctx->stream;
     const int32_t L = set.count;
     set.have_run = false;
-    ctx->sens[&set == &ctx->cases ? MAG_SET_CASES : MAG_SET_VARIANTS].have = false;
+    if (!set.adjoint) { // (an adjoint set's run leaves the results of the set it differentiates as they are)
+        ctx->sens[set.slot].have = false;
+        ctx->adjres[set.slot].have = false;
+    }
     begin_run(ctx);
     set.stats.assign((size_t)L, mag_stats{});
     int32_t *info = set.info;
@@ -2657,16 +2685,10 @@ int set_info(const MemberSet &set, int32_t info[4])
     return MAG_OK;
 }
 
-} // namespace
-
-int mag_run_cases(mag_ctx *ctx)
+// the members of `set` as load cases of the uploaded mesh (mag_run_cases; the adjoint systems of a run or of load cases)
+int run_case_set(mag_ctx *ctx, MemberSet &set)
 {
-    if (!ctx) return MAG_ERR_BAD_ARGS;
-    if (ctx->comm.nranks > 1)
-        return fail(ctx, MAG_ERR_BAD_ARGS, "load cases run on one GPU: this context has a communicator of %d ranks", ctx->comm.nranks);
-    if (!ctx->have_problem || !ctx->cases.have) return fail(ctx, MAG_ERR_STATE, "mag_run_cases before mag_set_load_cases");
     hipStream_t s = ctx->stream;
-    MemberSet &set = ctx->cases;
     const int32_t L = set.count;
     const size_t vb = 16 * (size_t)ctx->N, eb = 8 * (size_t)ctx->E;
     auto at = [](const DevBuf &b, size_t stride, int32_t c) { return (double *)(b.as<char>() + stride * (size_t)c); };
@@ -2700,7 +2722,7 @@ int mag_run_cases(mag_ctx *ctx)
     h.launch = [&](magk::PersistParams &P, int32_t n, int eb_mode) {
         magk::persist_launch_cases(P, ctx->B, ctx->persist_grid, n, eb_mode, s);
     };
-    h.solve_alone = [&](int32_t c, mag_stats &out, bool timed_out_before) { return solve_case_alone(ctx, c, out, timed_out_before); };
+    h.solve_alone = [&](int32_t c, mag_stats &out, bool timed_out_before) { return solve_case_alone(ctx, set, c, out, timed_out_before); };
     h.post = [&]() -> int { // per case: scatter-back, reactions, stress
         HIPCHK(hipEventRecord(ctx->ev[6], s));
         for (int32_t c = 0; c < L; ++c)
@@ -2717,6 +2739,17 @@ int mag_run_cases(mag_ctx *ctx)
         cs.ms_post = ev_ms(ctx->ev[6], ctx->ev[7]);
     };
     return run_members(ctx, set, keep, h);
+}
+
+} // namespace
+
+int mag_run_cases(mag_ctx *ctx)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (ctx->comm.nranks > 1)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "load cases run on one GPU: this context has a communicator of %d ranks", ctx->comm.nranks);
+    if (!ctx->have_problem || !ctx->cases.have) return fail(ctx, MAG_ERR_STATE, "mag_run_cases before mag_set_load_cases");
+    return run_case_set(ctx, ctx->cases);
 }
 
 int mag_download_case(mag_ctx *ctx, int32_t case_index, mag_result *r)
@@ -2773,6 +2806,7 @@ int mag_set_variants(mag_ctx *ctx, int32_t num_variants, const double *xy, const
     if (int rc = enter(ctx)) return rc;
     ctx->variants.have = ctx->variants.have_run = false;
     ctx->sens[MAG_SET_VARIANTS].have = false;
+    ctx->adjres[MAG_SET_VARIANTS].have = false;
     const int64_t N = ctx->N, E = ctx->E;
     const size_t bytes = 16 * (size_t)N * (size_t)V;
     const hipMemcpyKind kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -2845,9 +2879,10 @@ const double *variant_xy(const mag_ctx *ctx, const LentProblem &keep, int32_t v)
     if (ctx->v_have_xy) return ctx->v_xy.as<double>() + 2 * (size_t)ctx->N * (size_t)v;
     return keep.armed ? keep.xy() : ctx->xy.as<double>();
 }
-const double *variant_loads(const mag_ctx *ctx, const LentProblem &keep, int32_t v, bool forces)
+// (`set`: the variants, or their adjoint systems, which always bring loads of their own)
+const double *variant_loads(const mag_ctx *ctx, const MemberSet &set, const LentProblem &keep, int32_t v, bool forces)
 {
-    if (ctx->v_have_loads) return (forces ? ctx->variants.fin : ctx->variants.uin).as<double>() + 2 * (size_t)ctx->N * (size_t)v;
+    if (set.adjoint || ctx->v_have_loads) return (forces ? set.fin : set.uin).as<double>() + 2 * (size_t)ctx->N * (size_t)v;
     if (keep.armed) return forces ? keep.fin() : keep.uin();
     return (forces ? ctx->fin : ctx->uin).as<double>();
 }
@@ -2855,14 +2890,14 @@ const double *variant_loads(const mag_ctx *ctx, const LentProblem &keep, int32_t
 // one variant through the single-case phases, the shared tables kept: its coordinates (permuted into xyP and the tiles' halo
 // copies), material and values into the context, then K, right-hand side, cg_solve (its time-out fall-back, its best_param
 // repeat) and post as mag_run runs them.  The caller has armed `keep`.
-int solve_variant_alone(mag_ctx *ctx, const LentProblem &keep, int32_t v, mag_stats &out, bool timed_out_before)
+int solve_variant_alone(mag_ctx *ctx, MemberSet &set, const LentProblem &keep, int32_t v, mag_stats &out, bool timed_out_before)
 {
     hipStream_t s = ctx->stream;
     const int64_t N = ctx->N, E = ctx->E;
     const size_t vb = 16 * (size_t)N, eb = 8 * (size_t)E;
     HIPCHK(hipMemcpyAsync(ctx->xy.p, variant_xy(ctx, keep, v), vb, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(ctx->uin.p, variant_loads(ctx, keep, v, false), vb, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(ctx->fin.p, variant_loads(ctx, keep, v, true), vb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->uin.p, variant_loads(ctx, set, keep, v, false), vb, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->fin.p, variant_loads(ctx, set, keep, v, true), vb, hipMemcpyDeviceToDevice, s));
     ctx->youngs = ctx->v_mat_h[3 * (size_t)v + 0];
     ctx->nu = ctx->v_mat_h[3 * (size_t)v + 1];
     ctx->thick = ctx->v_mat_h[3 * (size_t)v + 2];
@@ -2878,7 +2913,6 @@ int solve_variant_alone(mag_ctx *ctx, const LentProblem &keep, int32_t v, mag_st
     if (int rc = rhs_phase(ctx, ctx->uin.as<double>(), ctx->fin.as<double>(), ctx->bP.as<double>(), false)) return rc;
     HIPCHK(hipGetLastError());
     if (int rc = cg_solve_member(ctx, v, out, timed_out_before)) return rc;
-    MemberSet &set = ctx->variants;
     if (ctx->opt.cg_operator == MAG_OP_CSR) // (that operator's phase has expanded its solution into the context's u)
         HIPCHK(hipMemcpyAsync(set.u.as<char>() + vb * (size_t)v, ctx->u.p, vb, hipMemcpyDeviceToDevice, s));
     if (int rc = post_phase(ctx, ctx->x.as<double>(), ctx->uin.as<double>(), ctx->fin.as<double>(), set.u.as<double>() + 2 * (size_t)N * v,
@@ -2889,15 +2923,11 @@ int solve_variant_alone(mag_ctx *ctx, const LentProblem &keep, int32_t v, mag_st
     return MAG_OK;
 }
 
-} // namespace
-
-int mag_run_variants(mag_ctx *ctx)
+// the members of `set` as design variants of the uploaded mesh: the coordinates and materials of mag_set_variants, the loads
+// of `set` (mag_run_variants; the variants' adjoint systems)
+int run_variant_set(mag_ctx *ctx, MemberSet &set)
 {
-    if (!ctx) return MAG_ERR_BAD_ARGS;
-    if (int rc = variants_refused(ctx)) return rc;
-    if (!ctx->have_problem || !ctx->variants.have) return fail(ctx, MAG_ERR_STATE, "mag_run_variants before mag_set_variants");
     hipStream_t s = ctx->stream;
-    MemberSet &set = ctx->variants;
     const int64_t N = ctx->N, E = ctx->E;
     const int32_t V = set.count;
     const size_t vb = 16 * (size_t)N, eb = 8 * (size_t)E;
@@ -2934,12 +2964,12 @@ int mag_run_variants(mag_ctx *ctx)
         vbat.count = n;
         vbat.mat = ctx->v_mat.as<double>() + 3 * (size_t)c0;
         vbat.xy = ctx->v_have_xy ? 2 * N : 0;
-        vbat.loads = ctx->v_have_loads ? 2 * N : 0;
+        vbat.loads = set.adjoint || ctx->v_have_loads ? 2 * N : 0;
         vbat.halo = halo;
         vbat.kval = 4 * ctx->nb;
         xy = variant_xy(ctx, keep, c0);
-        uin = variant_loads(ctx, keep, c0, false);
-        fin = variant_loads(ctx, keep, c0, true);
+        uin = variant_loads(ctx, set, keep, c0, false);
+        fin = variant_loads(ctx, set, keep, c0, true);
         double *bP = set.bP.as<double>() + 2 * (size_t)N * c0;
         xP = set.x.as<double>() + 2 * (size_t)N * c0;
         HIPCHK(hipEventRecord(ctx->evV[0], s));
@@ -2988,7 +3018,7 @@ int mag_run_variants(mag_ctx *ctx)
         return MAG_OK;
     };
     h.solve_alone = [&](int32_t v, mag_stats &out, bool timed_out_before) {
-        return solve_variant_alone(ctx, keep, v, out, timed_out_before);
+        return solve_variant_alone(ctx, set, keep, v, out, timed_out_before);
     };
     // side by side: the phases' times summed over the chunks, the same in every variant (ms_element: the coordinate permutation;
     // ms_cg stays the variant's own launch, the block build is counted with ms_bc) -- one after another: each variant's cg time
@@ -3002,6 +3032,16 @@ int mag_run_variants(mag_ctx *ctx)
     // xyP, the halo copies and K may be a variant's: nothing of this run is reused by the entry points that would
     ctx->have_order = ctx->have_csr = false;
     return status;
+}
+
+} // namespace
+
+int mag_run_variants(mag_ctx *ctx)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (int rc = variants_refused(ctx)) return rc;
+    if (!ctx->have_problem || !ctx->variants.have) return fail(ctx, MAG_ERR_STATE, "mag_run_variants before mag_set_variants");
+    return run_variant_set(ctx, ctx->variants);
 }
 
 int mag_download_variant(mag_ctx *ctx, int32_t v, mag_result *r)
@@ -3077,21 +3117,14 @@ int sens_refused(mag_ctx *ctx, int32_t set, const char *fn, int32_t *count)
     return MAG_OK;
 }
 
-} // namespace
-
-int mag_run_sensitivities(mag_ctx *ctx, int32_t set)
+// The uploaded mesh and its ordering tables as the sensitivity kernels take them (mag_run_sensitivities, mag_run_adjoint).
+// The ordering phase's tables of the uploaded mesh are there: every completed run of one rank has built them whole, and they
+// hang on the connectivity and the uploaded coordinates only (a variants run leaves them as they are).  The node kernels'
+// tile-local corner table is built from them once per ordering, where a tile's image fits the LDS.
+int sens_mesh(mag_ctx *ctx, magk::SensMesh &mesh)
 {
-    if (!ctx) return MAG_ERR_BAD_ARGS;
-    int32_t M = 0;
-    if (int rc = sens_refused(ctx, set, "mag_run_sensitivities", &M)) return rc;
-    if (int rc = enter(ctx)) return rc;
     hipStream_t s = ctx->stream;
-    const int64_t N = ctx->N, E = ctx->E;
-    SensSet &out = ctx->sens[set];
-    out.have = false;
-    // The ordering phase's tables of the uploaded mesh are there: every completed run of one rank has built them whole, and
-    // they hang on the connectivity and the uploaded coordinates only (a variants run leaves them as they are).  The node
-    // kernel's tile-local corner table is built from them once per ordering, where a tile's image fits the LDS.
+    const int64_t N = ctx->N;
     const bool staged = ctx->cap <= magk::kMaxLdsNodes && env_int("MAG_TUNE_SENS_STAGE", 1) != 0;
     if (staged && !ctx->sens_tab_ready) {
         HIPCHK(ctx->sens_tab.reserve(4 * (size_t)std::max<int64_t>(ctx->ell_total, 1)));
@@ -3101,9 +3134,9 @@ int mag_run_sensitivities(mag_ctx *ctx, int32_t set)
         HIPCHK(hipGetLastError());
         ctx->sens_tab_ready = true;
     }
-    magk::SensMesh mesh = {};
+    mesh = {};
     mesh.N = N;
-    mesh.E = E;
+    mesh.E = ctx->E;
     mesh.conn = ctx->conn.as<int32_t>();
     mesh.u_known = ctx->uknown.as<uint8_t>();
     mesh.perm = ctx->perm.as<uint32_t>();
@@ -3117,6 +3150,46 @@ int mag_run_sensitivities(mag_ctx *ctx, int32_t set)
     mesh.tile_deg = ctx->tile_deg.as<int32_t>();
     mesh.tile_off = ctx->tile_off.as<int64_t>();
     mesh.tab = staged ? ctx->sens_tab.as<uint32_t>() : nullptr;
+    return MAG_OK;
+}
+
+// members per launch of those kernels: the scratch of one chunk (per_member bytes each) may take a quarter of the device memory
+// that is free now; and what grid.y holds
+int sens_chunk(mag_ctx *ctx, size_t per_member, int32_t M, int64_t &chunk)
+{
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    chunk = std::max<int64_t>(1, (int64_t)(free_b / 4 / per_member));
+    chunk = std::min<int64_t>(chunk, 32768);
+    const int tuned = env_int("MAG_TUNE_SENS_CHUNK", 0);
+    if (tuned >= 1) chunk = std::min<int64_t>(tuned, 32768);
+    chunk = std::min<int64_t>(chunk, M);
+    return MAG_OK;
+}
+
+// the uploaded material for every member of a set that has none of its own
+int sens_uploaded_material(mag_ctx *ctx)
+{
+    const double mat[3] = {ctx->youngs, ctx->nu, ctx->thick};
+    HIPCHK(ctx->sens_mat.reserve(sizeof mat));
+    HIPCHK(hipMemcpy(ctx->sens_mat.p, mat, sizeof mat, hipMemcpyHostToDevice));
+    return MAG_OK;
+}
+
+} // namespace
+
+int mag_run_sensitivities(mag_ctx *ctx, int32_t set)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    int32_t M = 0;
+    if (int rc = sens_refused(ctx, set, "mag_run_sensitivities", &M)) return rc;
+    if (int rc = enter(ctx)) return rc;
+    hipStream_t s = ctx->stream;
+    const int64_t N = ctx->N, E = ctx->E;
+    SensSet &out = ctx->sens[set];
+    out.have = false;
+    magk::SensMesh mesh;
+    if (int rc = sens_mesh(ctx, mesh)) return rc;
     // the members' arrays: where the set's run left them
     const MemberSet *ms = set == MAG_SET_CASES ? &ctx->cases : (set == MAG_SET_VARIANTS ? &ctx->variants : nullptr);
     const bool own_xy = set == MAG_SET_VARIANTS && ctx->v_have_xy;
@@ -3127,21 +3200,11 @@ int mag_run_sensitivities(mag_ctx *ctx, int32_t set)
     const double *fin = own_loads ? ms->fin.as<double>() : ctx->fin.as<double>();
     // the material: a variant's own (v_mat, on the device since mag_set_variants), otherwise the uploaded one for every member
     const bool own_mat = set == MAG_SET_VARIANTS;
-    if (!own_mat) {
-        const double mat[3] = {ctx->youngs, ctx->nu, ctx->thick};
-        HIPCHK(ctx->sens_mat.reserve(sizeof mat));
-        HIPCHK(hipMemcpy(ctx->sens_mat.p, mat, sizeof mat, hipMemcpyHostToDevice));
-    }
-    // members per launch: the scratch of one chunk (a nu term per element, the partial sums) may take a quarter of the device
-    // memory that is free now; and what grid.y holds
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    const size_t per_member = 8 * (size_t)E + 8 * 4 * (size_t)magk::kSensBlocks;
-    int64_t chunk = std::max<int64_t>(1, (int64_t)(free_b / 4 / per_member));
-    chunk = std::min<int64_t>(chunk, 32768);
-    const int tuned = env_int("MAG_TUNE_SENS_CHUNK", 0);
-    if (tuned >= 1) chunk = std::min<int64_t>(tuned, 32768);
-    chunk = std::min<int64_t>(chunk, M);
+    if (!own_mat)
+        if (int rc = sens_uploaded_material(ctx)) return rc;
+    // members per launch, by the scratch of one chunk: a nu term per element, the partial sums
+    int64_t chunk = 1;
+    if (int rc = sens_chunk(ctx, 8 * (size_t)E + 8 * 4 * (size_t)magk::kSensBlocks, M, chunk)) return rc;
     HIPCHK(out.energy.reserve(8 * (size_t)E * M));
     HIPCHK(out.dxy.reserve(16 * (size_t)N * M));
     HIPCHK(out.scalars.reserve(64 * (size_t)M));
@@ -3194,6 +3257,174 @@ int mag_download_sensitivity(mag_ctx *ctx, int32_t set, int32_t index, mag_sensi
     HIPCHK(hipStreamSynchronize(s));
     for (int k = 0; k < 8; ++k) o->scalars[k] = have.scalars_h[8 * i + k];
     return MAG_OK;
+}
+
+// ---- adjoint sensitivities of the solved members of a set: the adjoint systems through the member-set driver, then the
+// bilinear pass (adjoint.hip) ----
+namespace {
+
+// What a set's run drops of the single-case path (begin_run) and overwrites in its buffers: kept aside around the run of an
+// adjoint set, which must leave all of it as it was.
+struct KeptRun {
+    mag_ctx *ctx;
+    const size_t vb, eb;
+    const mag_stats stats;
+    const bool have_run, have_sens, have_adjoint;
+    const int32_t history_len;
+    bool armed = false;
+    explicit KeptRun(mag_ctx *c)
+        : ctx(c), vb(16 * (size_t)c->N), eb(8 * (size_t)c->E), stats(c->stats), have_run(c->have_run), have_sens(c->sens[MAG_SET_RUN].have),
+          have_adjoint(c->adjres[MAG_SET_RUN].have), history_len(c->opt.history_len)
+    {
+    }
+    int keep() // (u, f, stress: the CSR operator's phase expands into the context's u, a lent problem runs through all three)
+    {
+        ctx->opt.history_len = 0; // the recorded costs stay those of the run that recorded them
+        if (!have_run) return MAG_OK;
+        hipStream_t s = ctx->stream;
+        HIPCHK(ctx->adj_keep.reserve(2 * vb + eb));
+        HIPCHK(hipMemcpyAsync(ctx->adj_keep.p, ctx->u.p, vb, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(ctx->adj_keep.as<char>() + vb, ctx->f.p, vb, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(ctx->adj_keep.as<char>() + 2 * vb, ctx->stress.p, eb, hipMemcpyDeviceToDevice, s));
+        armed = true;
+        return MAG_OK;
+    }
+    ~KeptRun()
+    {
+        ctx->opt.history_len = history_len;
+        ctx->stats = stats;
+        ctx->have_run = have_run;
+        ctx->sens[MAG_SET_RUN].have = have_sens;
+        ctx->adjres[MAG_SET_RUN].have = have_adjoint;
+        if (!armed) return;
+        hipStream_t s = ctx->stream;
+        (void)hipMemcpyAsync(ctx->u.p, ctx->adj_keep.p, vb, hipMemcpyDeviceToDevice, s);
+        (void)hipMemcpyAsync(ctx->f.p, ctx->adj_keep.as<char>() + vb, vb, hipMemcpyDeviceToDevice, s);
+        (void)hipMemcpyAsync(ctx->stress.p, ctx->adj_keep.as<char>() + 2 * vb, eb, hipMemcpyDeviceToDevice, s);
+        (void)hipStreamSynchronize(s);
+    }
+};
+
+// the checks of the adjoint getters, all before any HIP call
+int adjoint_refused(mag_ctx *ctx, int32_t set, const char *fn, int32_t *count)
+{
+    if (int rc = sens_refused(ctx, set, fn, count)) return rc;
+    if (!ctx->adjres[set].have) return fail(ctx, MAG_ERR_STATE, "%s before mag_run_adjoint of this set", fn);
+    return MAG_OK;
+}
+
+} // namespace
+
+int mag_run_adjoint(mag_ctx *ctx, int32_t set, const double *dJ_du, int32_t memory)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    int32_t M = 0;
+    if (set >= MAG_SET_RUN && set <= MAG_SET_VARIANTS && !dJ_du) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_adjoint: null dJ_du");
+    if (int rc = sens_refused(ctx, set, "mag_run_adjoint", &M)) return rc;
+    if (int rc = enter(ctx)) return rc;
+    hipStream_t s = ctx->stream;
+    const int64_t N = ctx->N, E = ctx->E;
+    const size_t vb = 16 * (size_t)N;
+    AdjointSet &out = ctx->adjres[set];
+    MemberSet &adj = ctx->adj[set];
+    out.have = false;
+    adj.have = adj.have_run = false;
+    // the adjoint systems: load sets (0, dJ/du) on the set's own K
+    HIPCHK(adj.uin.reserve(vb * M));
+    HIPCHK(adj.fin.reserve(vb * M));
+    HIPCHK(hipMemsetAsync(adj.uin.p, 0, vb * M, s));
+    HIPCHK(hipMemcpyAsync(adj.fin.p, dJ_du, vb * M, memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    adj.count = M;
+    adj.have = true;
+    int status = MAG_OK;
+    {
+        KeptRun kept(ctx);
+        if (int rc = kept.keep()) return rc;
+        status = set == MAG_SET_VARIANTS ? run_variant_set(ctx, adj) : run_case_set(ctx, adj);
+    }
+    if (status != MAG_OK && status != MAG_ERR_NOT_CONVERGED) return status;
+    const std::string run_message = ctx->err;
+
+    // ---- the bilinear pass over (u of the set, lambda = u of its adjoint set), chunked as mag_run_sensitivities is
+    magk::SensMesh mesh;
+    if (int rc = sens_mesh(ctx, mesh)) return rc;
+    const bool own_xy = set == MAG_SET_VARIANTS && ctx->v_have_xy, own_mat = set == MAG_SET_VARIANTS;
+    const double *xy = own_xy ? ctx->v_xy.as<double>() : ctx->xy.as<double>();
+    const double *u = set == MAG_SET_RUN ? ctx->u.as<double>() : (set == MAG_SET_CASES ? ctx->cases : ctx->variants).u.as<double>();
+    if (!own_mat)
+        if (int rc = sens_uploaded_material(ctx)) return rc;
+    int64_t chunk = 1;
+    if (int rc = sens_chunk(ctx, 8 * (size_t)E + 8 * 2 * (size_t)magk::kSensBlocks, M, chunk)) return rc;
+    HIPCHK(out.dloads.reserve(vb * M));
+    HIPCHK(out.delem.reserve(8 * (size_t)E * M));
+    HIPCHK(out.dxy.reserve(vb * M));
+    HIPCHK(out.scalars.reserve(64 * (size_t)M));
+    HIPCHK(ctx->sens_nuterm.reserve(8 * (size_t)E * chunk));
+    HIPCHK(ctx->sens_part.reserve(8 * 2 * (size_t)magk::kSensBlocks * chunk));
+    for (int32_t c0 = 0; c0 < M; c0 += (int32_t)chunk) {
+        magk::AdjointBatch ab = {};
+        ab.count = (int32_t)std::min<int64_t>(chunk, M - c0);
+        ab.mat_stride = own_mat ? 3 : 0;
+        ab.mat = own_mat ? ctx->v_mat.as<double>() + 3 * (size_t)c0 : ctx->sens_mat.as<double>();
+        ab.xy_stride = own_xy ? 2 * N : 0;
+        ab.xy = xy + (size_t)ab.xy_stride * c0;
+        ab.u = u + 2 * (size_t)N * c0;
+        ab.lam = adj.u.as<double>() + 2 * (size_t)N * c0;
+        ab.g = adj.fin.as<double>() + 2 * (size_t)N * c0;
+        ab.f_adj = adj.f.as<double>() + 2 * (size_t)N * c0;
+        ab.dloads = out.dloads.as<double>() + 2 * (size_t)N * c0;
+        ab.delem = out.delem.as<double>() + (size_t)E * c0;
+        ab.dxy = out.dxy.as<double>() + 2 * (size_t)N * c0;
+        ab.scalars = out.scalars.as<double>() + 8 * (size_t)c0;
+        ab.nuterm = ctx->sens_nuterm.as<double>();
+        ab.partials = ctx->sens_part.as<double>();
+        HIPCHK(magk::adjoint_bilinear(mesh, ab, s));
+        HIPCHK(hipGetLastError());
+    }
+    out.scalars_h.assign(8 * (size_t)M, 0.0);
+    HIPCHK(hipMemcpyAsync(out.scalars_h.data(), out.scalars.p, 64 * (size_t)M, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    out.count = M;
+    out.have = true;
+    if (status != MAG_OK) ctx->err = run_message;
+    return status;
+}
+
+int mag_download_adjoint(mag_ctx *ctx, int32_t set, int32_t index, mag_adjoint *o)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "null adjoint");
+    if (index < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "member %d out of range", (int)index);
+    int32_t M = 0;
+    if (int rc = adjoint_refused(ctx, set, "mag_download_adjoint", &M)) return rc;
+    const AdjointSet &have = ctx->adjres[set];
+    if (index >= have.count) return fail(ctx, MAG_ERR_BAD_ARGS, "member %d out of range [0, %d)", (int)index, (int)have.count);
+    if (int rc = enter(ctx)) return rc;
+    const hipMemcpyKind kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    hipStream_t s = ctx->stream;
+    const size_t eb = 8 * (size_t)ctx->E, vb = 16 * (size_t)ctx->N, i = (size_t)index;
+    if (o->lambda_out) HIPCHK(hipMemcpyAsync(o->lambda_out, ctx->adj[set].u.as<char>() + vb * i, vb, kind, s));
+    if (o->dloads_out) HIPCHK(hipMemcpyAsync(o->dloads_out, have.dloads.as<char>() + vb * i, vb, kind, s));
+    if (o->delem_out) HIPCHK(hipMemcpyAsync(o->delem_out, have.delem.as<char>() + eb * i, eb, kind, s));
+    if (o->dxy_out) HIPCHK(hipMemcpyAsync(o->dxy_out, have.dxy.as<char>() + vb * i, vb, kind, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int k = 0; k < 8; ++k) o->scalars[k] = have.scalars_h[8 * i + k];
+    return MAG_OK;
+}
+
+int mag_get_adjoint_stats(const mag_ctx *ctx, int32_t set, int32_t index, mag_stats *st)
+{
+    if (!ctx || !st || index < 0 || set < MAG_SET_RUN || set > MAG_SET_VARIANTS || ctx->comm.nranks > 1) return MAG_ERR_BAD_ARGS;
+    if (!ctx->adjres[set].have) return MAG_ERR_STATE;
+    return member_stats(ctx->adj[set], index, st);
+}
+
+int mag_get_adjoint_info(const mag_ctx *ctx, int32_t set, int32_t info[4])
+{
+    if (!ctx || !info || set < MAG_SET_RUN || set > MAG_SET_VARIANTS || ctx->comm.nranks > 1) return MAG_ERR_BAD_ARGS;
+    if (!ctx->adjres[set].have) return MAG_ERR_STATE;
+    return set_info(ctx->adj[set], info);
 }
 
 int mag_solve(mag_ctx *ctx, const mag_problem *p, mag_result *r)

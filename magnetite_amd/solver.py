@@ -383,6 +383,55 @@ class Context:
         n = 1 if set == "run" else (self.num_cases if set == "cases" else self.num_variants)
         return [self.download_sensitivity(set, i) for i in range(n)]
 
+    # -- adjoint sensitivities: the gradient of any objective of the solved members of a set ------------
+    ADJOINT_SCALARS = ("a", "dJ_dE", "dJ_dnu", "dJ_dt")
+
+    def _members(self, set):
+        """Members of the set; 0 where none was given yet (the library then answers with its state error)."""
+        return 1 if set == "run" else getattr(self, "num_cases" if set == "cases" else "num_variants", 0)
+
+    def run_adjoint(self, dJ_du, set="run", allow_not_converged=False):
+        """mag_run_adjoint on the last completed run() / run_cases() / run_variants(): dJ_du of shape (members, 2N), or (2N,)
+        for "run" -- one adjoint solve per member with its own K, then the bilinear pass."""
+        which = self._sensitivity_set(set)
+        g = np.ascontiguousarray(dJ_du, dtype=np.float64)
+        if set == "run" and g.ndim == 1:
+            g = g.reshape(1, -1)
+        members = self._members(set)
+        if g.ndim != 2 or (self.N and g.shape[1] != 2 * self.N) or (members and g.shape[0] != members):
+            raise MagnetiteError("Solver", "adjoint: dJ_du must have shape (members of the set, 2 * num_nodes)")
+        allow = (MAG_ERR_NOT_CONVERGED,) if allow_not_converged else ()
+        return self._check(self._L.mag_run_adjoint(self._h, which, _p(g, C.c_double), MAG_MEM_HOST), allow)
+
+    def download_adjoint(self, set, i):
+        """dict(lambda (2N), dloads (2N), delem (E), dxy (2N), a, dJ_dE, dJ_dnu, dJ_dt) of member i of the set."""
+        which = self._sensitivity_set(set)
+        lam, dloads, delem, dxy = np.empty(2 * self.N), np.empty(2 * self.N), np.empty(self.E), np.empty(2 * self.N)
+        o = _lib.Adjoint(lam.ctypes.data, dloads.ctypes.data, delem.ctypes.data, dxy.ctypes.data, (C.c_double * 8)(), MAG_MEM_HOST, 0)
+        self._check(self._L.mag_download_adjoint(self._h, which, i, C.byref(o)))
+        out = {"lambda": lam, "dloads": dloads, "delem": delem, "dxy": dxy}
+        out.update(zip(self.ADJOINT_SCALARS, o.scalars))
+        return out
+
+    def adjoint_stats(self, set, i):
+        """The statistics of member i's adjoint solve (mag_get_adjoint_stats)."""
+        st = _lib.Stats()
+        self._check(self._L.mag_get_adjoint_stats(self._h, self._sensitivity_set(set), i, C.byref(st)))
+        return st.as_dict()
+
+    def adjoint_info(self, set):
+        """mag_get_adjoint_info: the four words of cases_info() for the adjoint solves of the set, as a list."""
+        info = (C.c_int32 * 4)()
+        self._check(self._L.mag_get_adjoint_info(self._h, self._sensitivity_set(set), info))
+        return list(info)
+
+    def adjoint(self, dJ_du, set="run", allow_not_converged=False):
+        """The gradient of an objective J of every solved member of the set, given dJ/du at the member's u: a list of dicts as
+        download_adjoint returns them.  dxy, dJ_dE, dJ_dnu, dJ_dt, delem and dloads are total derivatives at fixed prescribed
+        values, without J's explicit dependence on the design (include/magnetite_hip.h)."""
+        self.run_adjoint(dJ_du, set, allow_not_converged)
+        return [self.download_adjoint(set, i) for i in range(self._members(set))]
+
     # -- pieces, for parity tests ----------------------------------------------
     def element_stiffness(self):
         ke = np.empty(36 * self.E)
