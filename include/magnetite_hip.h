@@ -398,6 +398,70 @@ int mag_download_adjoint(mag_ctx *ctx, int32_t set, int32_t index, mag_adjoint *
 int mag_get_adjoint_stats(const mag_ctx *ctx, int32_t set, int32_t index, mag_stats *stats);
 int mag_get_adjoint_info(const mag_ctx *ctx, int32_t set, int32_t info[4]); /* as mag_get_cases_info */
 
+/* ---- objectives on the device: J, dJ/du and the explicit partials of solved runs, load cases and variants ---- */
+/* mag_run_adjoint takes g = dJ/du from the caller and leaves J's explicit partials (dJ/dtheta at fixed u) to the caller.  For the
+ * two objectives below the device forms both per solved member, where u lies, hands g to the adjoint pass without a copy to the
+ * host, and adds explicit and adjoint parts to the total design gradient.  In the notation of the sensitivities (b, g, A2 = 2A
+ * with the SIGNED area, p_u, q_u, r_u):
+ * MAG_OBJ_STRESS_PNORM   the p-norm aggregate of the plane-stress von Mises stress.  sigma_e = D B u_e = (sx, sy, txy) with the
+ *   reference's D (solver.rs:240-250) and B (solver.rs:204-230):  (sx, sy, txy) = E / ((1 - nu^2) A2) (P, Q, R),
+ *   P = p_u + nu q_u, Q = nu p_u + q_u, R = (1 - nu) / 2 r_u;  vm_e = sqrt(sx^2 - sx sy + sy^2 + 3 txy^2).  (NOT the reference's
+ *   scalar stress[e]: its sign factor (sx + sy < 1) is discontinuous.)
+ *       S = sum_e w_e (vm_e / scale)^p,        J = scale S^(1/p),
+ *   weights: E values >= 0, NULL for all ones; p >= 1 and scale > 0, both finite.  `scale` only keeps vm^p inside the range of
+ *   a double: pass a typical stress of the part (the yield stress, the expected maximum); J does not depend on it but through
+ *   round-off.  dJ/dz = S^(1/p - 1) / (2 scale) sum_e w_e (vm_e / scale)^(p - 2) d(vm_e^2)/dz; the explicit partials at fixed u:
+ *   dJ/dxy is non-zero (B and A depend on the coordinates), dJ/dE = J / E, dJ/dnu in closed form from D, dJ/dt = 0.  An element
+ *   with vm_e = 0 contributes 0 to S, to g and to the partials (for p < 2 its derivative does not exist); S = 0 gives J = 0,
+ *   g = 0 and partials 0.
+ * MAG_OBJ_DISP_LSQ       J = sum_i w_i (u_i - target_i)^2 over all 2N DOFs: weights 2N values >= 0 (required), target 2N values or
+ *   NULL for zeros.  g = 2 w (u - target); every explicit partial is 0.  One non-zero weight is a displacement at a point, a
+ *   target field a shape mismatch.
+ * mag_objective: kind; per_member = 0: weights and target are ONE row for all members of the set, != 0: a row per member,
+ *   [members][2N] (MAG_OBJ_DISP_LSQ) or [members][E] (MAG_OBJ_STRESS_PNORM); p and scale (MAG_OBJ_STRESS_PNORM only); memory: enum
+ *   mag_memory of weights and target (rows on the device are read where they are).
+ * mag_run_objective: set = enum mag_set, after a completed run of that set.
+ *   with_adjoint = 0: nothing is solved; no other result of the context is touched.
+ *   with_adjoint != 0: the device-resident g of all members goes through mag_run_adjoint's path -- its results for the set are
+ *   those of mag_run_adjoint(set, g), bit for bit, readable through mag_download_adjoint, mag_get_adjoint_stats and
+ *   mag_get_adjoint_info, and they REPLACE the results of an earlier adjoint call for the set; its status is returned (the first
+ *   failing member's, the others complete).  Then total = explicit + adjoint, one addition per entry: dxy = pxy + the adjoint's dxy,
+ *   dJ/dE, dJ/dnu, dJ/dt likewise.  The adjoint's STOP RULE caveat applies: under the absolute rules the accuracy of lambda depends
+ *   on the scale of g, so scale the weights until |g_F| is of the size of mag_stats.rhs_norm (MAG_OBJ_DISP_LSQ: J and g are linear in w;
+ *   MAG_OBJ_STRESS_PNORM: they grow with w^(1/p), so a factor c on g is a factor c^p on every weight), or
+ *   use MAG_STOP_REL.
+ *   Nothing else changes, as for mag_run_adjoint.  No floating-point atomics: a repeat gives the same bits, a member the same
+ *   bits whatever launch it shares.  Objective results are dropped where the set's sensitivities are: a new mag_upload, a new
+ *   mag_set_* of the set, a new run of the set (any set's run drops those of MAG_SET_RUN).
+ * mag_download_objective: member `index` (0 for MAG_SET_RUN); NULL arrays are skipped, scalars are always filled:
+ *   g_out        dJ/du                                                    (2N values, caller numbering)
+ *   pxy_out      explicit dJ/dxy at fixed u                                (2N values)
+ *   dxy_out      total dJ/dxy = pxy + adjoint dxy; with_adjoint only       (2N values)
+ *   scalars[0]   J                      scalars[1..3]  explicit dJ/dE, dJ/dnu, dJ/dt
+ *   scalars[4..6]  total dJ/dE, dJ/dnu, dJ/dt (0 without the adjoint)      scalars[7]  1 if the totals are present, else 0
+ * Errors, before any HIP call: MAG_ERR_BAD_ARGS for a set that is none of enum mag_set, an unknown kind, a null objective / out,
+ *   a p or scale that is not finite or out of range, null weights for MAG_OBJ_DISP_LSQ, an index out of range, a context whose
+ *   communicator has more than one rank; MAG_ERR_STATE for no completed run of the set, download before mag_run_objective of
+ *   the set, and dxy_out when the objective ran with with_adjoint = 0. */
+enum mag_objective_kind { MAG_OBJ_DISP_LSQ = 0, MAG_OBJ_STRESS_PNORM = 1 };
+typedef struct mag_objective {
+    int32_t kind;          /* enum mag_objective_kind */
+    int32_t per_member;
+    double p, scale;
+    const double *weights;
+    const double *target;
+    int32_t memory, reserved;
+} mag_objective;           /* 48 bytes */
+typedef struct mag_objective_result {
+    double *g_out;   /* 2N, NULL: skipped */
+    double *pxy_out; /* 2N, explicit */
+    double *dxy_out; /* 2N, total */
+    double scalars[8];
+    int32_t memory, reserved;
+} mag_objective_result;    /* 96 bytes */
+int mag_run_objective(mag_ctx *ctx, int32_t set, const mag_objective *objective, int32_t with_adjoint);
+int mag_download_objective(mag_ctx *ctx, int32_t set, int32_t index, mag_objective_result *out);
+
 /* ---- pieces of the path, exposed for parity tests -------------------- */
 /* solver.rs:187-193 compute_element_area (pub; the mesher imports it, mesher.rs:9,523). Host-side. */
 double mag_compute_element_area(const double *xy, const int32_t *tri);

@@ -66,6 +66,22 @@ struct Adjoint {
     double a = 0, dJ_dE = 0, dJ_dnu = 0, dJ_dt = 0;
 };
 
+// What solver::objective returns per solved member: the outputs of mag_download_objective, the scalars by name (pJ_*: explicit
+// partials at fixed u; dxy and dJ_*: totals, filled when the adjoint ran).
+struct Objective {
+    std::vector<double> g, pxy, dxy;
+    double J = 0, pJ_pE = 0, pJ_pnu = 0, pJ_pt = 0, dJ_dE = 0, dJ_dnu = 0, dJ_dt = 0;
+    bool totals = false;
+};
+
+// The objective of solver::objective (include/magnetite_hip.h, mag_objective): one row of weights (and of the target) for all
+// members -- 2N values for MAG_OBJ_DISP_LSQ, E values or none for MAG_OBJ_STRESS_PNORM.
+struct ObjectiveSpec {
+    std::int32_t kind = MAG_OBJ_STRESS_PNORM;
+    std::vector<double> weights, target;
+    double p = 8.0, scale = 1.0;
+};
+
 // The objective of solver::adjoint: dJ/du (2N, already sized and zeroed, in the order of `nodes`) of member `member` at its
 // solved displacements u (2N, prescribed values included).
 using ObjectiveGradient = std::function<void(std::size_t member, const std::vector<double> &u, std::vector<double> &dJ_du)>;
@@ -458,6 +474,86 @@ inline Result adjoint(const std::vector<Node> &nodes, const std::vector<Element>
         s.dJ_dE = d.scalars[1];
         s.dJ_dnu = d.scalars[2];
         s.dJ_dt = d.scalars[3];
+    }
+    mag_destroy(ctx);
+    return std::nullopt;
+}
+
+// An objective of the part as it is -- shapes and materials both empty: one member -- or of its design variants, as adjoint()
+// takes them, evaluated on the device (mag_run_objective): the problem(s) are solved, then per member J, dJ/du (g) and J's explicit
+// partials at fixed u (pxy, pJ_pE, pJ_pnu, pJ_pt); with_adjoint, dJ/du goes through the adjoint pass where it lies and the total
+// derivatives dxy, dJ_dE, dJ_dnu, dJ_dt follow.  Under an absolute stop rule scale the weights so that |dJ/du| is of the size of
+// the loads.
+inline Result objective(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                        const std::vector<std::vector<Vertex>> &shapes, const std::vector<ModelMetadata> &materials,
+                        const ObjectiveSpec &spec, bool with_adjoint, std::vector<Objective> &out, const mag_options *options = nullptr)
+{
+    auto err = detail::solver_error;
+    const bool plain = shapes.empty() && materials.empty();
+    const std::size_t V = plain ? 1 : (shapes.empty() ? materials.size() : shapes.size()), N = nodes.size(), E = elements.size();
+    if (!shapes.empty() && !materials.empty() && shapes.size() != materials.size())
+        return err("shapes and materials disagree on the number of variants");
+    const std::size_t row = spec.kind == MAG_OBJ_DISP_LSQ ? 2 * N : E;
+    if (!spec.weights.empty() && spec.weights.size() != row) return err("the objective's weights have another length than its sum");
+    if (!spec.target.empty() && spec.target.size() != 2 * N) return err("the objective's target has another length than 2 N");
+    std::vector<double> xy, u_in(2 * N), f_in(2 * N), vxy, vmat;
+    std::vector<std::uint8_t> u_known;
+    std::vector<std::int32_t> conn;
+    if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
+    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
+    for (std::size_t v = 0; v < shapes.size(); ++v) {
+        if (shapes[v].size() != N) return err("variant " + std::to_string(v) + " has another number of vertices");
+        for (const Vertex &p : shapes[v]) {
+            vxy.push_back(p.x);
+            vxy.push_back(p.y);
+        }
+    }
+    for (const ModelMetadata &m : materials) {
+        vmat.push_back(m.youngs_modulus);
+        vmat.push_back(m.poisson_ratio);
+        vmat.push_back(m.part_thickness);
+    }
+    mag_ctx *ctx = mag_create(options);
+    if (!ctx) return err("mag_create failed");
+    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
+    if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    const std::int32_t set = plain ? MAG_SET_RUN : MAG_SET_VARIANTS;
+    if (plain) {
+        if (mag_run(ctx) != MAG_OK) return detail::fail_and_destroy(ctx);
+    } else {
+        if (mag_set_variants(ctx, (std::int32_t)V, shapes.empty() ? nullptr : vxy.data(), materials.empty() ? nullptr : vmat.data(),
+                             nullptr, nullptr, MAG_MEM_HOST) != MAG_OK)
+            return detail::fail_and_destroy(ctx);
+        if (mag_run_variants(ctx) != MAG_OK) return detail::fail_and_destroy(ctx);
+    }
+    mag_objective o{};
+    o.kind = spec.kind;
+    o.p = spec.p;
+    o.scale = spec.scale;
+    o.weights = spec.weights.empty() ? nullptr : spec.weights.data();
+    o.target = spec.target.empty() ? nullptr : spec.target.data();
+    o.memory = MAG_MEM_HOST;
+    if (mag_run_objective(ctx, set, &o, with_adjoint ? 1 : 0) != MAG_OK) return detail::fail_and_destroy(ctx);
+    out.assign(V, Objective{});
+    for (std::size_t v = 0; v < V; ++v) {
+        Objective &s = out[v];
+        s.g.resize(2 * N);
+        s.pxy.resize(2 * N);
+        if (with_adjoint) s.dxy.resize(2 * N);
+        mag_objective_result d{};
+        d.g_out = s.g.data();
+        d.pxy_out = s.pxy.data();
+        d.dxy_out = with_adjoint ? s.dxy.data() : nullptr;
+        d.memory = MAG_MEM_HOST;
+        if (mag_download_objective(ctx, set, (std::int32_t)v, &d) != MAG_OK) return detail::fail_and_destroy(ctx);
+        s.J = d.scalars[0];
+        s.pJ_pE = d.scalars[1];
+        s.pJ_pnu = d.scalars[2];
+        s.pJ_pt = d.scalars[3];
+        s.dJ_dE = d.scalars[4];
+        s.dJ_dnu = d.scalars[5];
+        s.dJ_dt = d.scalars[6];
+        s.totals = d.scalars[7] != 0.0;
     }
     mag_destroy(ctx);
     return std::nullopt;

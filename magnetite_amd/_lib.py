@@ -20,6 +20,7 @@ MAG_OP_MATRIX_FREE, MAG_OP_CSR = 0, 1
 MAG_TERM_NONE, MAG_TERM_TARGET_COST, MAG_TERM_MAX_ITERS, MAG_TERM_BREAKDOWN = 0, 1, 2, 3
 MAG_MEM_HOST, MAG_MEM_DEVICE = 0, 1
 MAG_SET_RUN, MAG_SET_CASES, MAG_SET_VARIANTS = 0, 1, 2
+MAG_OBJ_DISP_LSQ, MAG_OBJ_STRESS_PNORM = 0, 1
 MAG_UNIQUE_ID_BYTES = 128
 MAG_IPC_HANDLE_BYTES = 64
 
@@ -34,6 +35,7 @@ SYMBOLS = [
     "mag_assemble_csr_variant",
     "mag_run_sensitivities", "mag_download_sensitivity",
     "mag_run_adjoint", "mag_download_adjoint", "mag_get_adjoint_stats", "mag_get_adjoint_info",
+    "mag_run_objective", "mag_download_objective",
     "mag_comm_get_unique_id", "mag_comm_init_rccl", "mag_comm_query", "mag_comm_init_callback", "mag_comm_set_window", "mag_comm_inbox_create", "mag_comm_inbox_open",
 ]
 
@@ -82,6 +84,16 @@ class Sensitivity(C.Structure):
 class Adjoint(C.Structure):
     _fields_ = [("lambda_out", C.c_void_p), ("dloads_out", C.c_void_p), ("delem_out", C.c_void_p), ("dxy_out", C.c_void_p),
                 ("scalars", C.c_double * 8), ("memory", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Objective(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("per_member", C.c_int32), ("p", C.c_double), ("scale", C.c_double),
+                ("weights", C.c_void_p), ("target", C.c_void_p), ("memory", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ObjectiveResult(C.Structure):
+    _fields_ = [("g_out", C.c_void_p), ("pxy_out", C.c_void_p), ("dxy_out", C.c_void_p), ("scalars", C.c_double * 8),
+                ("memory", C.c_int32), ("reserved", C.c_int32)]
 
 
 HASHED_SOURCES = ("persist.hip", "cg.hip", "cg_device.h", "exact.hip", "symbolic.hip", "kernels.h")
@@ -164,6 +176,9 @@ def lib():
         L.mag_download_adjoint.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(Adjoint)]
         L.mag_get_adjoint_stats.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(Stats)]
         L.mag_get_adjoint_info.argtypes = [vp, C.c_int32, ip]
+    if hasattr(L, "mag_run_objective"):  # (likewise: scripts/objective_probe.py)
+        L.mag_run_objective.argtypes = [vp, C.c_int32, C.POINTER(Objective), C.c_int32]
+        L.mag_download_objective.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(ObjectiveResult)]
     L.mag_compute_element_area.argtypes = [dp, ip]
     L.mag_compute_element_area.restype = C.c_double
     L.mag_compute_strain_displacement_matrix.argtypes = [dp, ip, C.c_double, dp]

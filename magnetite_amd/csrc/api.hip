@@ -24,6 +24,7 @@
 #include "magnetite_hip.h"
 #include "primitives.h"
 #include "adjoint.h"
+#include "objective.h"
 #include "sens.h"
 
 using magk::CgState;
@@ -95,6 +96,15 @@ struct AdjointSet {
     bool have = false;
     int32_t count = 0;
     DevBuf dloads, delem, dxy, scalars;
+    std::vector<double> scalars_h; // [count][8]
+};
+
+// What mag_run_objective leaves for one set: dJ/du, the explicit dJ/dxy and -- with_adjoint -- the total dJ/dxy member after
+// member on the device, the scalars on the host.  Dropped as SensSet is.
+struct ObjectiveSet {
+    bool have = false, totals = false;
+    int32_t count = 0;
+    DevBuf g, pxy, dxy, scalars;
     std::vector<double> scalars_h; // [count][8]
 };
 
@@ -275,6 +285,11 @@ struct mag_ctx {
                         {"adjoint", "mag_run_adjoint", MAG_SET_VARIANTS, true}};
     AdjointSet adjres[3];
     DevBuf adj_keep;
+
+    // objectives of the same three sets (mag_run_objective); the caller's weights and targets, and the summands, per-element
+    // factors and member factors of ONE chunk of members (the nu terms and partial sums are the sensitivities')
+    ObjectiveSet objres[3];
+    DevBuf obj_w, obj_target, obj_terms, obj_helem, obj_factor;
 
     magc::Comm comm;
 };
@@ -2196,6 +2211,7 @@ void begin_run(mag_ctx *ctx)
     ctx->have_order = ctx->have_csr = ctx->have_run = false;
     ctx->sens[MAG_SET_RUN].have = false; // (the single-case results go with every run, a set's included)
     ctx->adjres[MAG_SET_RUN].have = false;
+    ctx->objres[MAG_SET_RUN].have = false;
     // a context whose on-chip kernel once found the GPU shared is not condemned to stream for ever: after a number of
     // streamed solves (8, doubling per failure) it tries again -- at worst one more spin budget (~0.3 s).  Across ranks
     // the failures are agreed on collectively, so every rank counts the same and retries in the same solve.
@@ -2243,6 +2259,7 @@ int mag_upload(mag_ctx *ctx, const mag_problem *p)
     ctx->variants.reset();
     for (SensSet &ss : ctx->sens) ss.have = false;
     for (AdjointSet &as : ctx->adjres) as.have = false;
+    for (ObjectiveSet &os : ctx->objres) os.have = false;
     return MAG_OK;
 }
 
@@ -2357,6 +2374,7 @@ int mag_set_load_cases(mag_ctx *ctx, int32_t num_cases, const double *u_in, cons
     ctx->cases.have = ctx->cases.have_run = false;
     ctx->sens[MAG_SET_CASES].have = false;
     ctx->adjres[MAG_SET_CASES].have = false;
+    ctx->objres[MAG_SET_CASES].have = false;
     const size_t bytes = 16 * (size_t)ctx->N * (size_t)num_cases;
     const hipMemcpyKind kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     hipStream_t s = ctx->stream;
@@ -2572,6 +2590,7 @@ int run_members(mag_ctx *ctx, MemberSet &set, LentProblem &keep, const MemberHoo
     if (!set.adjoint) { // (an adjoint set's run leaves the results of the set it differentiates as they are)
         ctx->sens[set.slot].have = false;
         ctx->adjres[set.slot].have = false;
+        ctx->objres[set.slot].have = false;
     }
     begin_run(ctx);
     set.stats.assign((size_t)L, mag_stats{});
@@ -2807,6 +2826,7 @@ int mag_set_variants(mag_ctx *ctx, int32_t num_variants, const double *xy, const
     ctx->variants.have = ctx->variants.have_run = false;
     ctx->sens[MAG_SET_VARIANTS].have = false;
     ctx->adjres[MAG_SET_VARIANTS].have = false;
+    ctx->objres[MAG_SET_VARIANTS].have = false;
     const int64_t N = ctx->N, E = ctx->E;
     const size_t bytes = 16 * (size_t)N * (size_t)V;
     const hipMemcpyKind kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -3269,12 +3289,12 @@ struct KeptRun {
     mag_ctx *ctx;
     const size_t vb, eb;
     const mag_stats stats;
-    const bool have_run, have_sens, have_adjoint;
+    const bool have_run, have_sens, have_adjoint, have_objective;
     const int32_t history_len;
     bool armed = false;
     explicit KeptRun(mag_ctx *c)
         : ctx(c), vb(16 * (size_t)c->N), eb(8 * (size_t)c->E), stats(c->stats), have_run(c->have_run), have_sens(c->sens[MAG_SET_RUN].have),
-          have_adjoint(c->adjres[MAG_SET_RUN].have), history_len(c->opt.history_len)
+          have_adjoint(c->adjres[MAG_SET_RUN].have), have_objective(c->objres[MAG_SET_RUN].have), history_len(c->opt.history_len)
     {
     }
     int keep() // (u, f, stress: the CSR operator's phase expands into the context's u, a lent problem runs through all three)
@@ -3296,6 +3316,7 @@ struct KeptRun {
         ctx->have_run = have_run;
         ctx->sens[MAG_SET_RUN].have = have_sens;
         ctx->adjres[MAG_SET_RUN].have = have_adjoint;
+        ctx->objres[MAG_SET_RUN].have = have_objective;
         if (!armed) return;
         hipStream_t s = ctx->stream;
         (void)hipMemcpyAsync(ctx->u.p, ctx->adj_keep.p, vb, hipMemcpyDeviceToDevice, s);
@@ -3313,15 +3334,9 @@ int adjoint_refused(mag_ctx *ctx, int32_t set, const char *fn, int32_t *count)
     return MAG_OK;
 }
 
-} // namespace
-
-int mag_run_adjoint(mag_ctx *ctx, int32_t set, const double *dJ_du, int32_t memory)
+// mag_run_adjoint past its checks: dJ_du [M][2N] on the host or -- mag_run_objective's -- already on the device
+int run_adjoint(mag_ctx *ctx, int32_t set, int32_t M, const double *dJ_du, int32_t memory)
 {
-    if (!ctx) return MAG_ERR_BAD_ARGS;
-    int32_t M = 0;
-    if (set >= MAG_SET_RUN && set <= MAG_SET_VARIANTS && !dJ_du) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_adjoint: null dJ_du");
-    if (int rc = sens_refused(ctx, set, "mag_run_adjoint", &M)) return rc;
-    if (int rc = enter(ctx)) return rc;
     hipStream_t s = ctx->stream;
     const int64_t N = ctx->N, E = ctx->E;
     const size_t vb = 16 * (size_t)N;
@@ -3391,6 +3406,18 @@ int mag_run_adjoint(mag_ctx *ctx, int32_t set, const double *dJ_du, int32_t memo
     return status;
 }
 
+} // namespace
+
+int mag_run_adjoint(mag_ctx *ctx, int32_t set, const double *dJ_du, int32_t memory)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    int32_t M = 0;
+    if (set >= MAG_SET_RUN && set <= MAG_SET_VARIANTS && !dJ_du) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_adjoint: null dJ_du");
+    if (int rc = sens_refused(ctx, set, "mag_run_adjoint", &M)) return rc;
+    if (int rc = enter(ctx)) return rc;
+    return run_adjoint(ctx, set, M, dJ_du, memory);
+}
+
 int mag_download_adjoint(mag_ctx *ctx, int32_t set, int32_t index, mag_adjoint *o)
 {
     if (!ctx) return MAG_ERR_BAD_ARGS;
@@ -3425,6 +3452,137 @@ int mag_get_adjoint_info(const mag_ctx *ctx, int32_t set, int32_t info[4])
     if (!ctx || !info || set < MAG_SET_RUN || set > MAG_SET_VARIANTS || ctx->comm.nranks > 1) return MAG_ERR_BAD_ARGS;
     if (!ctx->adjres[set].have) return MAG_ERR_STATE;
     return set_info(ctx->adj[set], info);
+}
+
+// ---- objectives of the solved members of a set on the device (objective.hip): J, dJ/du, the explicit partials; with_adjoint,
+// dJ/du goes on to the adjoint pass where it lies and the totals are formed ----
+int mag_run_objective(mag_ctx *ctx, int32_t set, const mag_objective *obj, int32_t with_adjoint)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (set < MAG_SET_RUN || set > MAG_SET_VARIANTS)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_objective: set %d is none of enum mag_set", (int)set);
+    if (!obj) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_objective: null objective");
+    if (obj->kind != MAG_OBJ_DISP_LSQ && obj->kind != MAG_OBJ_STRESS_PNORM)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_objective: kind %d is none of enum mag_objective_kind", (int)obj->kind);
+    const bool lsq = obj->kind == MAG_OBJ_DISP_LSQ;
+    if (lsq && !obj->weights) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_objective: MAG_OBJ_DISP_LSQ needs weights");
+    if (!lsq && !(std::isfinite(obj->p) && obj->p >= 1.0))
+        return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_objective: p = %g is not a finite exponent >= 1", obj->p);
+    if (!lsq && !(std::isfinite(obj->scale) && obj->scale > 0.0))
+        return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_objective: scale = %g is not a finite stress > 0", obj->scale);
+    int32_t M = 0;
+    if (int rc = sens_refused(ctx, set, "mag_run_objective", &M)) return rc;
+    if (int rc = enter(ctx)) return rc;
+    hipStream_t s = ctx->stream;
+    const int64_t N = ctx->N, E = ctx->E;
+    const size_t vb = 16 * (size_t)N;
+    ObjectiveSet &out = ctx->objres[set];
+    out.have = out.totals = false;
+    magk::SensMesh mesh;
+    if (int rc = sens_mesh(ctx, mesh)) return rc;
+    const bool own_xy = set == MAG_SET_VARIANTS && ctx->v_have_xy, own_mat = set == MAG_SET_VARIANTS;
+    const double *xy = own_xy ? ctx->v_xy.as<double>() : ctx->xy.as<double>();
+    const double *u = set == MAG_SET_RUN ? ctx->u.as<double>() : (set == MAG_SET_CASES ? ctx->cases : ctx->variants).u.as<double>();
+    if (!own_mat)
+        if (int rc = sens_uploaded_material(ctx)) return rc;
+    // the caller's rows: one for all members or one per member, on the device as they are
+    const int64_t row = lsq ? 2 * N : E, stride = obj->per_member ? row : 0;
+    const size_t rows_b = 8 * (size_t)row * (obj->per_member ? (size_t)M : 1);
+    const double *w = obj->weights, *target = lsq ? obj->target : nullptr;
+    if (obj->memory != MAG_MEM_DEVICE) {
+        if (w) {
+            HIPCHK(ctx->obj_w.reserve(rows_b));
+            HIPCHK(hipMemcpyAsync(ctx->obj_w.p, w, rows_b, hipMemcpyHostToDevice, s));
+            w = ctx->obj_w.as<double>();
+        }
+        if (target) {
+            HIPCHK(ctx->obj_target.reserve(rows_b));
+            HIPCHK(hipMemcpyAsync(ctx->obj_target.p, target, rows_b, hipMemcpyHostToDevice, s));
+            target = ctx->obj_target.as<double>();
+        }
+    }
+    // members per launch, by the scratch of one chunk: summands, nu terms and factors per element, the partial sums
+    int64_t chunk = 1;
+    if (int rc = sens_chunk(ctx, 8 * (size_t)row + 16 * (size_t)E + 8 * 2 * (size_t)magk::kSensBlocks + 8, M, chunk)) return rc;
+    HIPCHK(out.g.reserve(vb * M));
+    HIPCHK(out.pxy.reserve(vb * M));
+    HIPCHK(out.scalars.reserve(64 * (size_t)M));
+    HIPCHK(ctx->obj_terms.reserve(8 * (size_t)row * chunk));
+    HIPCHK(ctx->sens_nuterm.reserve(8 * (size_t)E * chunk));
+    HIPCHK(ctx->obj_helem.reserve(8 * (size_t)E * chunk));
+    HIPCHK(ctx->sens_part.reserve(8 * 2 * (size_t)magk::kSensBlocks * chunk));
+    HIPCHK(ctx->obj_factor.reserve(8 * (size_t)chunk));
+    for (int32_t c0 = 0; c0 < M; c0 += (int32_t)chunk) {
+        magk::ObjectiveBatch ob = {};
+        ob.count = (int32_t)std::min<int64_t>(chunk, M - c0);
+        ob.kind = obj->kind;
+        ob.mat_stride = own_mat ? 3 : 0;
+        ob.mat = own_mat ? ctx->v_mat.as<double>() + 3 * (size_t)c0 : ctx->sens_mat.as<double>();
+        ob.xy_stride = own_xy ? 2 * N : 0;
+        ob.xy = xy + (size_t)ob.xy_stride * c0;
+        ob.u = u + 2 * (size_t)N * c0;
+        ob.w_stride = stride;
+        ob.w = w ? w + (size_t)stride * c0 : nullptr;
+        ob.target_stride = stride;
+        ob.target = target ? target + (size_t)stride * c0 : nullptr;
+        ob.p = obj->p;
+        ob.scale = obj->scale;
+        ob.g = out.g.as<double>() + 2 * (size_t)N * c0;
+        ob.pxy = out.pxy.as<double>() + 2 * (size_t)N * c0;
+        ob.scalars = out.scalars.as<double>() + 8 * (size_t)c0;
+        ob.terms = ctx->obj_terms.as<double>();
+        ob.nuterm = ctx->sens_nuterm.as<double>();
+        ob.helem = ctx->obj_helem.as<double>();
+        ob.partials = ctx->sens_part.as<double>();
+        ob.factor = ctx->obj_factor.as<double>();
+        magk::objective(mesh, ob, s);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(s)); // (the caller's rows are read, the results stand)
+    out.count = M;
+    out.have = true;
+    int status = MAG_OK;
+    std::string run_message;
+    if (with_adjoint) {
+        status = run_adjoint(ctx, set, M, out.g.as<double>(), MAG_MEM_DEVICE);
+        if (status != MAG_OK && status != MAG_ERR_NOT_CONVERGED) return status;
+        run_message = ctx->err;
+        const AdjointSet &adj = ctx->adjres[set];
+        HIPCHK(out.dxy.reserve(vb * M));
+        magk::objective_totals(N, M, out.pxy.as<double>(), adj.dxy.as<double>(), adj.scalars.as<double>(), out.dxy.as<double>(),
+                               out.scalars.as<double>(), s);
+        HIPCHK(hipGetLastError());
+    }
+    out.scalars_h.assign(8 * (size_t)M, 0.0);
+    HIPCHK(hipMemcpyAsync(out.scalars_h.data(), out.scalars.p, 64 * (size_t)M, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    out.totals = with_adjoint != 0;
+    if (status != MAG_OK) ctx->err = run_message;
+    return status;
+}
+
+int mag_download_objective(mag_ctx *ctx, int32_t set, int32_t index, mag_objective_result *o)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "null objective result");
+    if (index < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "member %d out of range", (int)index);
+    int32_t M = 0;
+    if (int rc = sens_refused(ctx, set, "mag_download_objective", &M)) return rc;
+    const ObjectiveSet &have = ctx->objres[set];
+    if (!have.have) return fail(ctx, MAG_ERR_STATE, "mag_download_objective before mag_run_objective of this set");
+    if (index >= have.count) return fail(ctx, MAG_ERR_BAD_ARGS, "member %d out of range [0, %d)", (int)index, (int)have.count);
+    if (o->dxy_out && !have.totals)
+        return fail(ctx, MAG_ERR_STATE, "mag_download_objective: dxy_out needs mag_run_objective with with_adjoint != 0");
+    if (int rc = enter(ctx)) return rc;
+    const hipMemcpyKind kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    hipStream_t s = ctx->stream;
+    const size_t vb = 16 * (size_t)ctx->N, i = (size_t)index;
+    if (o->g_out) HIPCHK(hipMemcpyAsync(o->g_out, have.g.as<char>() + vb * i, vb, kind, s));
+    if (o->pxy_out) HIPCHK(hipMemcpyAsync(o->pxy_out, have.pxy.as<char>() + vb * i, vb, kind, s));
+    if (o->dxy_out) HIPCHK(hipMemcpyAsync(o->dxy_out, have.dxy.as<char>() + vb * i, vb, kind, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int k = 0; k < 8; ++k) o->scalars[k] = have.scalars_h[8 * i + k];
+    return MAG_OK;
 }
 
 int mag_solve(mag_ctx *ctx, const mag_problem *p, mag_result *r)

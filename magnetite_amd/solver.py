@@ -432,6 +432,58 @@ class Context:
         self.run_adjoint(dJ_du, set, allow_not_converged)
         return [self.download_adjoint(set, i) for i in range(self._members(set))]
 
+    # -- objectives on the device: J, dJ/du, explicit partials and, through the adjoint, the total design gradient ------------
+    OBJECTIVE_KINDS = {"disp_lsq": _lib.MAG_OBJ_DISP_LSQ, "stress_pnorm": _lib.MAG_OBJ_STRESS_PNORM}
+    OBJECTIVE_SCALARS = ("J", "pJ_pE", "pJ_pnu", "pJ_pt", "dJ_dE", "dJ_dnu", "dJ_dt")
+
+    def run_objective(self, kind, set="run", weights=None, target=None, p=8.0, scale=1.0, adjoint=False, allow_not_converged=False):
+        """mag_run_objective on the last completed run() / run_cases() / run_variants().  kind: "disp_lsq" (weights (2N,) or
+        (members, 2N), target likewise or None) or "stress_pnorm" (weights (E,) or (members, E) or None, p, scale)."""
+        which = self._sensitivity_set(set)
+        if kind not in self.OBJECTIVE_KINDS:
+            raise MagnetiteError("Solver", f"objective: kind must be one of {sorted(self.OBJECTIVE_KINDS)}")
+        width = 2 * self.N if kind == "disp_lsq" else self.E
+        members = self._members(set)
+
+        def rows(a, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.ndim not in (1, 2) or (width and a.shape[-1] != width) or (a.ndim == 2 and members and a.shape[0] != members):
+                raise MagnetiteError("Solver", f"objective: {what} must have shape ({width},) or (members of the set, {width})")
+            return a
+
+        w, tg = rows(weights, "weights"), rows(target if kind == "disp_lsq" else None, "target")
+        given = [a for a in (w, tg) if a is not None]
+        if len({a.ndim for a in given}) > 1:
+            raise MagnetiteError("Solver", "objective: weights and target are both one row or both a row per member")
+        per_member = 1 if given and given[0].ndim == 2 else 0
+        ptr = lambda a: None if a is None else a.ctypes.data
+        o = _lib.Objective(self.OBJECTIVE_KINDS[kind], per_member, float(p), float(scale), ptr(w), ptr(tg), MAG_MEM_HOST, 0)
+        allow = (MAG_ERR_NOT_CONVERGED,) if allow_not_converged else ()
+        return self._check(self._L.mag_run_objective(self._h, which, C.byref(o), 1 if adjoint else 0), allow)
+
+    def download_objective(self, set, i, total=False):
+        """dict(J, g (2N), pxy (2N), pJ_pE, pJ_pnu, pJ_pt: the explicit partials) of member i of the set; with total (the
+        objective ran with adjoint=True) also dxy (2N), dJ_dE, dJ_dnu, dJ_dt: the total derivatives."""
+        which = self._sensitivity_set(set)
+        g, pxy, dxy = np.empty(2 * self.N), np.empty(2 * self.N), np.empty(2 * self.N) if total else None
+        o = _lib.ObjectiveResult(g.ctypes.data, pxy.ctypes.data, dxy.ctypes.data if total else None, (C.c_double * 8)(), MAG_MEM_HOST, 0)
+        self._check(self._L.mag_download_objective(self._h, which, i, C.byref(o)))
+        out = dict(g=g, pxy=pxy)
+        out.update(zip(self.OBJECTIVE_SCALARS[:4], o.scalars))
+        if total:
+            out["dxy"] = dxy
+            out.update(zip(self.OBJECTIVE_SCALARS[4:], o.scalars[4:7]))
+        return out
+
+    def objective(self, kind, set="run", weights=None, target=None, p=8.0, scale=1.0, adjoint=False, allow_not_converged=False):
+        """An objective of every solved member of the set, evaluated on the device: a list of dicts as download_objective
+        returns them.  adjoint=True also runs the adjoint pass on the device-resident dJ/du (its results are then those of
+        adjoint(g, set)) and returns the total derivatives (include/magnetite_hip.h)."""
+        self.run_objective(kind, set, weights, target, p, scale, adjoint, allow_not_converged)
+        return [self.download_objective(set, i, total=adjoint) for i in range(self._members(set))]
+
     # -- pieces, for parity tests ----------------------------------------------
     def element_stiffness(self):
         ke = np.empty(36 * self.E)
