@@ -215,6 +215,72 @@ inline Result collect_members(mag_ctx *ctx, int rc, std::vector<std::vector<Node
     return std::nullopt;
 }
 
+// the variants' shapes and materials as mag_set_variants takes them: [V][2N] coordinates, [V][3] = E, nu, thickness
+inline Result flatten_variants(const std::vector<std::vector<Vertex>> &shapes, const std::vector<ModelMetadata> &materials, std::size_t N,
+                               std::vector<double> &vxy, std::vector<double> &vmat)
+{
+    for (std::size_t v = 0; v < shapes.size(); ++v) {
+        if (shapes[v].size() != N) return solver_error("variant " + std::to_string(v) + " has another number of vertices");
+        for (const Vertex &p : shapes[v]) {
+            vxy.push_back(p.x);
+            vxy.push_back(p.y);
+        }
+    }
+    for (const ModelMetadata &m : materials) {
+        vmat.push_back(m.youngs_modulus);
+        vmat.push_back(m.poisson_ratio);
+        vmat.push_back(m.part_thickness);
+    }
+    return std::nullopt;
+}
+
+// The solved members that sensitivities(), adjoint() and objective() differentiate: the part as it is -- shapes and materials
+// both empty: one member, MAG_SET_RUN -- or its design variants as run_variants takes them (MAG_SET_VARIANTS).  Owns the context:
+// it goes with this object on every path.
+struct SolvedMembers {
+    mag_ctx *ctx = nullptr;
+    std::int32_t set = MAG_SET_RUN;
+    std::size_t V = 0, N = 0, E = 0;
+    SolvedMembers() = default;
+    SolvedMembers(const SolvedMembers &) = delete;
+    SolvedMembers &operator=(const SolvedMembers &) = delete;
+    ~SolvedMembers()
+    {
+        if (ctx) mag_destroy(ctx);
+    }
+    // the error path: the context's message
+    Result fail() const { return solver_error(mag_last_error(ctx)); }
+    // The number of members before anything else is looked at, then `precheck` -- the caller's checks of its own arguments, which
+    // sees V, N and E -- then flatten, create, upload, solve.
+    template <class Precheck>
+    Result solve(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                 const std::vector<std::vector<Vertex>> &shapes, const std::vector<ModelMetadata> &materials, const mag_options *options,
+                 Precheck precheck)
+    {
+        const bool plain = shapes.empty() && materials.empty();
+        set = plain ? MAG_SET_RUN : MAG_SET_VARIANTS;
+        V = plain ? 1 : (shapes.empty() ? materials.size() : shapes.size()), N = nodes.size(), E = elements.size();
+        if (!shapes.empty() && !materials.empty() && shapes.size() != materials.size())
+            return solver_error("shapes and materials disagree on the number of variants");
+        if (Result e = precheck()) return e;
+        std::vector<double> xy, u_in(2 * N), f_in(2 * N), vxy, vmat;
+        std::vector<std::uint8_t> u_known;
+        std::vector<std::int32_t> conn;
+        if (Result e = flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
+        if (Result e = flatten_elements(elements, N, conn)) return e;
+        if (Result e = flatten_variants(shapes, materials, N, vxy, vmat)) return e;
+        ctx = mag_create(options);
+        if (!ctx) return solver_error("mag_create failed");
+        const mag_problem p = host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
+        if (mag_upload(ctx, &p) != MAG_OK) return fail();
+        if (set == MAG_SET_RUN) return mag_run(ctx) != MAG_OK ? fail() : std::nullopt;
+        if (mag_set_variants(ctx, (std::int32_t)V, shapes.empty() ? nullptr : vxy.data(), materials.empty() ? nullptr : vmat.data(), nullptr,
+                             nullptr, MAG_MEM_HOST) != MAG_OK)
+            return fail();
+        return mag_run_variants(ctx) != MAG_OK ? fail() : std::nullopt;
+    }
+};
+
 }  // namespace detail
 
 // solver.rs:543-586.  `options` == nullptr keeps the reference's constants (absolute cost 1e-4, 1e7 iterations).
@@ -300,18 +366,7 @@ inline Result run_variants(const std::vector<Node> &nodes, const std::vector<Ele
     std::vector<std::int32_t> conn;
     if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
     if (Result e = detail::flatten_elements(elements, N, conn)) return e;
-    for (std::size_t v = 0; v < shapes.size(); ++v) {
-        if (shapes[v].size() != N) return err("variant " + std::to_string(v) + " has another number of vertices");
-        for (const Vertex &p : shapes[v]) {
-            vxy.push_back(p.x);
-            vxy.push_back(p.y);
-        }
-    }
-    for (const ModelMetadata &m : materials) {
-        vmat.push_back(m.youngs_modulus);
-        vmat.push_back(m.poisson_ratio);
-        vmat.push_back(m.part_thickness);
-    }
+    if (Result e = detail::flatten_variants(shapes, materials, N, vxy, vmat)) return e;
     mag_ctx *ctx = mag_create(options);
     if (!ctx) return err("mag_create failed");
     const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
@@ -337,42 +392,12 @@ inline Result sensitivities(const std::vector<Node> &nodes, const std::vector<El
                             const std::vector<std::vector<Vertex>> &shapes, const std::vector<ModelMetadata> &materials,
                             std::vector<Sensitivity> &out, const mag_options *options = nullptr)
 {
-    auto err = detail::solver_error;
-    const bool plain = shapes.empty() && materials.empty();
-    const std::size_t V = plain ? 1 : (shapes.empty() ? materials.size() : shapes.size()), N = nodes.size(), E = elements.size();
-    if (!shapes.empty() && !materials.empty() && shapes.size() != materials.size())
-        return err("shapes and materials disagree on the number of variants");
-    std::vector<double> xy, u_in(2 * N), f_in(2 * N), vxy, vmat;
-    std::vector<std::uint8_t> u_known;
-    std::vector<std::int32_t> conn;
-    if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
-    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
-    for (std::size_t v = 0; v < shapes.size(); ++v) {
-        if (shapes[v].size() != N) return err("variant " + std::to_string(v) + " has another number of vertices");
-        for (const Vertex &p : shapes[v]) {
-            vxy.push_back(p.x);
-            vxy.push_back(p.y);
-        }
-    }
-    for (const ModelMetadata &m : materials) {
-        vmat.push_back(m.youngs_modulus);
-        vmat.push_back(m.poisson_ratio);
-        vmat.push_back(m.part_thickness);
-    }
-    mag_ctx *ctx = mag_create(options);
-    if (!ctx) return err("mag_create failed");
-    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
-    if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
-    const std::int32_t set = plain ? MAG_SET_RUN : MAG_SET_VARIANTS;
-    if (plain) {
-        if (mag_run(ctx) != MAG_OK) return detail::fail_and_destroy(ctx);
-    } else {
-        if (mag_set_variants(ctx, (std::int32_t)V, shapes.empty() ? nullptr : vxy.data(), materials.empty() ? nullptr : vmat.data(),
-                             nullptr, nullptr, MAG_MEM_HOST) != MAG_OK)
-            return detail::fail_and_destroy(ctx);
-        if (mag_run_variants(ctx) != MAG_OK) return detail::fail_and_destroy(ctx);
-    }
-    if (mag_run_sensitivities(ctx, set) != MAG_OK) return detail::fail_and_destroy(ctx);
+    detail::SolvedMembers sm;
+    if (Result e = sm.solve(nodes, elements, model_metadata, shapes, materials, options, []() -> Result { return std::nullopt; })) return e;
+    mag_ctx *ctx = sm.ctx;
+    const std::int32_t set = sm.set;
+    const std::size_t V = sm.V, N = sm.N, E = sm.E;
+    if (mag_run_sensitivities(ctx, set) != MAG_OK) return sm.fail();
     out.assign(V, Sensitivity{});
     for (std::size_t v = 0; v < V; ++v) {
         Sensitivity &s = out[v];
@@ -382,7 +407,7 @@ inline Result sensitivities(const std::vector<Node> &nodes, const std::vector<El
         d.energy_out = s.energy.data();
         d.dxy_out = s.dxy.data();
         d.memory = MAG_MEM_HOST;
-        if (mag_download_sensitivity(ctx, set, (std::int32_t)v, &d) != MAG_OK) return detail::fail_and_destroy(ctx);
+        if (mag_download_sensitivity(ctx, set, (std::int32_t)v, &d) != MAG_OK) return sm.fail();
         s.strain_energy = d.scalars[0];
         s.potential_energy = d.scalars[1];
         s.external_work = d.scalars[2];
@@ -391,7 +416,6 @@ inline Result sensitivities(const std::vector<Node> &nodes, const std::vector<El
         s.dPi_dnu = d.scalars[5];
         s.dPi_dt = d.scalars[6];
     }
-    mag_destroy(ctx);
     return std::nullopt;
 }
 
@@ -406,56 +430,25 @@ inline Result adjoint(const std::vector<Node> &nodes, const std::vector<Element>
                       const ObjectiveGradient &objective, std::vector<Adjoint> &out, const mag_options *options = nullptr)
 {
     auto err = detail::solver_error;
-    const bool plain = shapes.empty() && materials.empty();
-    const std::size_t V = plain ? 1 : (shapes.empty() ? materials.size() : shapes.size()), N = nodes.size(), E = elements.size();
-    if (!shapes.empty() && !materials.empty() && shapes.size() != materials.size())
-        return err("shapes and materials disagree on the number of variants");
-    if (!objective) return err("no objective");
-    std::vector<double> xy, u_in(2 * N), f_in(2 * N), vxy, vmat;
-    std::vector<std::uint8_t> u_known;
-    std::vector<std::int32_t> conn;
-    if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
-    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
-    for (std::size_t v = 0; v < shapes.size(); ++v) {
-        if (shapes[v].size() != N) return err("variant " + std::to_string(v) + " has another number of vertices");
-        for (const Vertex &p : shapes[v]) {
-            vxy.push_back(p.x);
-            vxy.push_back(p.y);
-        }
-    }
-    for (const ModelMetadata &m : materials) {
-        vmat.push_back(m.youngs_modulus);
-        vmat.push_back(m.poisson_ratio);
-        vmat.push_back(m.part_thickness);
-    }
-    mag_ctx *ctx = mag_create(options);
-    if (!ctx) return err("mag_create failed");
-    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
-    if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
-    const std::int32_t set = plain ? MAG_SET_RUN : MAG_SET_VARIANTS;
-    if (plain) {
-        if (mag_run(ctx) != MAG_OK) return detail::fail_and_destroy(ctx);
-    } else {
-        if (mag_set_variants(ctx, (std::int32_t)V, shapes.empty() ? nullptr : vxy.data(), materials.empty() ? nullptr : vmat.data(),
-                             nullptr, nullptr, MAG_MEM_HOST) != MAG_OK)
-            return detail::fail_and_destroy(ctx);
-        if (mag_run_variants(ctx) != MAG_OK) return detail::fail_and_destroy(ctx);
-    }
+    detail::SolvedMembers sm;
+    const auto precheck = [&]() -> Result { return objective ? std::nullopt : err("no objective"); };
+    if (Result e = sm.solve(nodes, elements, model_metadata, shapes, materials, options, precheck)) return e;
+    mag_ctx *ctx = sm.ctx;
+    const std::int32_t set = sm.set;
+    const std::size_t V = sm.V, N = sm.N, E = sm.E;
+    const bool plain = set == MAG_SET_RUN;
     std::vector<double> u(2 * N), g(V * 2 * N, 0.0), g_v;
     for (std::size_t v = 0; v < V; ++v) {
         mag_result r{};
         r.u_out = u.data();
         r.memory = MAG_MEM_HOST;
-        if ((plain ? mag_download(ctx, &r) : mag_download_variant(ctx, (std::int32_t)v, &r)) != MAG_OK) return detail::fail_and_destroy(ctx);
+        if ((plain ? mag_download(ctx, &r) : mag_download_variant(ctx, (std::int32_t)v, &r)) != MAG_OK) return sm.fail();
         g_v.assign(2 * N, 0.0);
         objective(v, u, g_v);
-        if (g_v.size() != 2 * N) {
-            mag_destroy(ctx);
-            return err("the objective resized dJ/du");
-        }
+        if (g_v.size() != 2 * N) return err("the objective resized dJ/du");
         std::copy(g_v.begin(), g_v.end(), g.begin() + v * 2 * N);
     }
-    if (mag_run_adjoint(ctx, set, g.data(), MAG_MEM_HOST) != MAG_OK) return detail::fail_and_destroy(ctx);
+    if (mag_run_adjoint(ctx, set, g.data(), MAG_MEM_HOST) != MAG_OK) return sm.fail();
     out.assign(V, Adjoint{});
     for (std::size_t v = 0; v < V; ++v) {
         Adjoint &s = out[v];
@@ -469,13 +462,12 @@ inline Result adjoint(const std::vector<Node> &nodes, const std::vector<Element>
         d.delem_out = s.delem.data();
         d.dxy_out = s.dxy.data();
         d.memory = MAG_MEM_HOST;
-        if (mag_download_adjoint(ctx, set, (std::int32_t)v, &d) != MAG_OK) return detail::fail_and_destroy(ctx);
+        if (mag_download_adjoint(ctx, set, (std::int32_t)v, &d) != MAG_OK) return sm.fail();
         s.a = d.scalars[0];
         s.dJ_dE = d.scalars[1];
         s.dJ_dnu = d.scalars[2];
         s.dJ_dt = d.scalars[3];
     }
-    mag_destroy(ctx);
     return std::nullopt;
 }
 
@@ -489,43 +481,17 @@ inline Result objective(const std::vector<Node> &nodes, const std::vector<Elemen
                         const ObjectiveSpec &spec, bool with_adjoint, std::vector<Objective> &out, const mag_options *options = nullptr)
 {
     auto err = detail::solver_error;
-    const bool plain = shapes.empty() && materials.empty();
-    const std::size_t V = plain ? 1 : (shapes.empty() ? materials.size() : shapes.size()), N = nodes.size(), E = elements.size();
-    if (!shapes.empty() && !materials.empty() && shapes.size() != materials.size())
-        return err("shapes and materials disagree on the number of variants");
-    const std::size_t row = spec.kind == MAG_OBJ_DISP_LSQ ? 2 * N : E;
-    if (!spec.weights.empty() && spec.weights.size() != row) return err("the objective's weights have another length than its sum");
-    if (!spec.target.empty() && spec.target.size() != 2 * N) return err("the objective's target has another length than 2 N");
-    std::vector<double> xy, u_in(2 * N), f_in(2 * N), vxy, vmat;
-    std::vector<std::uint8_t> u_known;
-    std::vector<std::int32_t> conn;
-    if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
-    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
-    for (std::size_t v = 0; v < shapes.size(); ++v) {
-        if (shapes[v].size() != N) return err("variant " + std::to_string(v) + " has another number of vertices");
-        for (const Vertex &p : shapes[v]) {
-            vxy.push_back(p.x);
-            vxy.push_back(p.y);
-        }
-    }
-    for (const ModelMetadata &m : materials) {
-        vmat.push_back(m.youngs_modulus);
-        vmat.push_back(m.poisson_ratio);
-        vmat.push_back(m.part_thickness);
-    }
-    mag_ctx *ctx = mag_create(options);
-    if (!ctx) return err("mag_create failed");
-    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
-    if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
-    const std::int32_t set = plain ? MAG_SET_RUN : MAG_SET_VARIANTS;
-    if (plain) {
-        if (mag_run(ctx) != MAG_OK) return detail::fail_and_destroy(ctx);
-    } else {
-        if (mag_set_variants(ctx, (std::int32_t)V, shapes.empty() ? nullptr : vxy.data(), materials.empty() ? nullptr : vmat.data(),
-                             nullptr, nullptr, MAG_MEM_HOST) != MAG_OK)
-            return detail::fail_and_destroy(ctx);
-        if (mag_run_variants(ctx) != MAG_OK) return detail::fail_and_destroy(ctx);
-    }
+    detail::SolvedMembers sm;
+    const auto precheck = [&]() -> Result {
+        const std::size_t row = spec.kind == MAG_OBJ_DISP_LSQ ? 2 * sm.N : sm.E;
+        if (!spec.weights.empty() && spec.weights.size() != row) return err("the objective's weights have another length than its sum");
+        if (!spec.target.empty() && spec.target.size() != 2 * sm.N) return err("the objective's target has another length than 2 N");
+        return std::nullopt;
+    };
+    if (Result e = sm.solve(nodes, elements, model_metadata, shapes, materials, options, precheck)) return e;
+    mag_ctx *ctx = sm.ctx;
+    const std::int32_t set = sm.set;
+    const std::size_t V = sm.V, N = sm.N;
     mag_objective o{};
     o.kind = spec.kind;
     o.p = spec.p;
@@ -533,7 +499,7 @@ inline Result objective(const std::vector<Node> &nodes, const std::vector<Elemen
     o.weights = spec.weights.empty() ? nullptr : spec.weights.data();
     o.target = spec.target.empty() ? nullptr : spec.target.data();
     o.memory = MAG_MEM_HOST;
-    if (mag_run_objective(ctx, set, &o, with_adjoint ? 1 : 0) != MAG_OK) return detail::fail_and_destroy(ctx);
+    if (mag_run_objective(ctx, set, &o, with_adjoint ? 1 : 0) != MAG_OK) return sm.fail();
     out.assign(V, Objective{});
     for (std::size_t v = 0; v < V; ++v) {
         Objective &s = out[v];
@@ -545,7 +511,7 @@ inline Result objective(const std::vector<Node> &nodes, const std::vector<Elemen
         d.pxy_out = s.pxy.data();
         d.dxy_out = with_adjoint ? s.dxy.data() : nullptr;
         d.memory = MAG_MEM_HOST;
-        if (mag_download_objective(ctx, set, (std::int32_t)v, &d) != MAG_OK) return detail::fail_and_destroy(ctx);
+        if (mag_download_objective(ctx, set, (std::int32_t)v, &d) != MAG_OK) return sm.fail();
         s.J = d.scalars[0];
         s.pJ_pE = d.scalars[1];
         s.pJ_pnu = d.scalars[2];
@@ -555,7 +521,6 @@ inline Result objective(const std::vector<Node> &nodes, const std::vector<Elemen
         s.dJ_dt = d.scalars[6];
         s.totals = d.scalars[7] != 0.0;
     }
-    mag_destroy(ctx);
     return std::nullopt;
 }
 

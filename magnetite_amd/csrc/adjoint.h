@@ -8,16 +8,8 @@
 
 namespace magk {
 
-// `count` members of one launch, grid.y = the member, as SensBatch: every pointer is the FIRST member's; a stride of 0: every
-// member reads the same array.
-struct AdjointBatch {
-    int32_t count;
-    int32_t pad;
-    const double *mat;   // E, nu, thickness
-    int64_t mat_stride;  // doubles: 3 (a material per member) or 0
-    const double *xy;    // caller-order coordinates
-    int64_t xy_stride;   // doubles: 2N or 0
-    const double *u;     // [count][2N] the members' solved displacements, caller numbering
+// The members of one launch (MemberBatch, sens.h) with their adjoint solutions.
+struct AdjointBatch : MemberBatch {
     const double *lam;   // [count][2N] the adjoint solutions (0 on the prescribed DOFs)
     const double *g;     // [count][2N] dJ/du as the caller gave it
     const double *f_adj; // [count][2N] the adjoint solves' forces: (K lambda) on the prescribed DOFs

@@ -81,32 +81,21 @@ struct MemberSet {
     }
 };
 
-// What mag_run_sensitivities leaves for one set of solved members (enum mag_set): element energies and node gradients member
+// What a pass over the solved members of one set (enum mag_set) leaves -- mag_run_sensitivities, mag_run_adjoint (next to its
+// adjoint MemberSet: lambda = that set's u, the adjoint reactions its f, dJ/du its f_in), mag_run_objective: its rows member
 // after member on the device, the scalars on the host.  Dropped by a new mag_upload and by a new run of the set.
-struct SensSet {
+struct DerivedSet {
     bool have = false;
+    bool totals = false; // mag_run_objective with_adjoint: dxy and scalars 4..7 hold the total derivatives
     int32_t count = 0;
-    DevBuf energy, dxy, scalars;
-    std::vector<double> scalars_h; // [count][8]
+    DevBuf energy;        // sensitivities [count][E]
+    DevBuf dloads, delem; // adjoint [count][2N], [count][E]
+    DevBuf g, pxy;        // objective [count][2N] each
+    DevBuf dxy;           // every pass [count][2N]
+    DevBuf scalars;       // every pass [count][8]
+    std::vector<double> scalars_h;
 };
-
-// What mag_run_adjoint leaves for one set next to its adjoint MemberSet (lambda = that set's u, the adjoint reactions its f, dJ/du
-// its f_in): the derivatives member after member on the device, the scalars on the host.  Dropped as SensSet is.
-struct AdjointSet {
-    bool have = false;
-    int32_t count = 0;
-    DevBuf dloads, delem, dxy, scalars;
-    std::vector<double> scalars_h; // [count][8]
-};
-
-// What mag_run_objective leaves for one set: dJ/du, the explicit dJ/dxy and -- with_adjoint -- the total dJ/dxy member after
-// member on the device, the scalars on the host.  Dropped as SensSet is.
-struct ObjectiveSet {
-    bool have = false, totals = false;
-    int32_t count = 0;
-    DevBuf g, pxy, dxy, scalars;
-    std::vector<double> scalars_h; // [count][8]
-};
+enum Pass { PASS_SENS, PASS_ADJOINT, PASS_OBJECTIVE, PASS_COUNT }; // the passes that leave a DerivedSet per set
 
 // Run-time knobs (environment, read at every call: tests switch them between calls in one process).  None is needed in
 // production; each one either is set by a test or forces a path the library can take on its own.
@@ -272,23 +261,23 @@ struct mag_ctx {
     int32_t ovf_total = 0; // overflow records of the whole mesh (choose_edge_blocks)
     hipEvent_t evV[7] = {}; // phase boundaries of a chunk (created by the first mag_run_variants)
 
-    // energy and design sensitivities (mag_run_sensitivities) of the last mag_run, mag_run_cases, mag_run_variants; the
-    // materials, per-element nu terms and partial sums of ONE chunk of members
-    SensSet sens[3];
+    // what the passes over solved members left of the last mag_run, mag_run_cases, mag_run_variants: [enum Pass][enum mag_set]
+    DerivedSet derived[PASS_COUNT][3];
+
+    // energy and design sensitivities (mag_run_sensitivities): the materials, per-element nu terms and partial sums of ONE chunk
+    // of members
     DevBuf sens_mat, sens_nuterm, sens_part, sens_tab; // sens_tab: the node kernel's tile-local corner table, of this ordering
     bool sens_tab_ready = false;
 
-    // adjoint sensitivities (mag_run_adjoint) of the same three sets: the adjoint systems as member sets of their own, what the
-    // bilinear pass made of them, and the single-case results kept aside while the adjoint systems run
+    // adjoint sensitivities (mag_run_adjoint) of the same three sets: the adjoint systems as member sets of their own (what the
+    // bilinear pass made of them is derived[PASS_ADJOINT]), and the single-case results kept aside while the adjoint systems run
     MemberSet adj[3] = {{"adjoint", "mag_run_adjoint", MAG_SET_RUN, true},
                         {"adjoint", "mag_run_adjoint", MAG_SET_CASES, true},
                         {"adjoint", "mag_run_adjoint", MAG_SET_VARIANTS, true}};
-    AdjointSet adjres[3];
     DevBuf adj_keep;
 
     // objectives of the same three sets (mag_run_objective); the caller's weights and targets, and the summands, per-element
     // factors and member factors of ONE chunk of members (the nu terms and partial sums are the sensitivities')
-    ObjectiveSet objres[3];
     DevBuf obj_w, obj_target, obj_terms, obj_helem, obj_factor;
 
     magc::Comm comm;
@@ -2203,15 +2192,19 @@ int post_phase(mag_ctx *ctx, const double *xP, const double *u_in, const double 
     return MAG_OK;
 }
 
+// the derived results of set `slot` -- sensitivities, adjoint, objective -- go with the solutions they were derived from
+void drop_derived(mag_ctx *ctx, int32_t slot)
+{
+    for (DerivedSet (&pass)[3] : ctx->derived) pass[slot].have = false;
+}
+
 // what every run starts with (mag_run, and a set's run): it redoes the whole path -- nothing of a previous run is reused except
 // allocations, the single-case results of the context are gone
 void begin_run(mag_ctx *ctx)
 {
     ctx->stats = {};
     ctx->have_order = ctx->have_csr = ctx->have_run = false;
-    ctx->sens[MAG_SET_RUN].have = false; // (the single-case results go with every run, a set's included)
-    ctx->adjres[MAG_SET_RUN].have = false;
-    ctx->objres[MAG_SET_RUN].have = false;
+    drop_derived(ctx, MAG_SET_RUN); // (the single-case results go with every run, a set's included)
     // a context whose on-chip kernel once found the GPU shared is not condemned to stream for ever: after a number of
     // streamed solves (8, doubling per failure) it tries again -- at worst one more spin budget (~0.3 s).  Across ranks
     // the failures are agreed on collectively, so every rank counts the same and retries in the same solve.
@@ -2257,9 +2250,7 @@ int mag_upload(mag_ctx *ctx, const mag_problem *p)
     ctx->sens_tab_ready = false;
     ctx->cases.reset();
     ctx->variants.reset();
-    for (SensSet &ss : ctx->sens) ss.have = false;
-    for (AdjointSet &as : ctx->adjres) as.have = false;
-    for (ObjectiveSet &os : ctx->objres) os.have = false;
+    for (int32_t slot = MAG_SET_RUN; slot <= MAG_SET_VARIANTS; ++slot) drop_derived(ctx, slot);
     return MAG_OK;
 }
 
@@ -2372,9 +2363,7 @@ int mag_set_load_cases(mag_ctx *ctx, int32_t num_cases, const double *u_in, cons
     if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "mag_set_load_cases before mag_upload");
     if (int rc = enter(ctx)) return rc;
     ctx->cases.have = ctx->cases.have_run = false;
-    ctx->sens[MAG_SET_CASES].have = false;
-    ctx->adjres[MAG_SET_CASES].have = false;
-    ctx->objres[MAG_SET_CASES].have = false;
+    drop_derived(ctx, MAG_SET_CASES);
     const size_t bytes = 16 * (size_t)ctx->N * (size_t)num_cases;
     const hipMemcpyKind kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     hipStream_t s = ctx->stream;
@@ -2587,11 +2576,7 @@ int run_members(mag_ctx *ctx, MemberSet &set, LentProblem &keep, const MemberHoo
     hipStream_t s = ctx->stream;
     const int32_t L = set.count;
     set.have_run = false;
-    if (!set.adjoint) { // (an adjoint set's run leaves the results of the set it differentiates as they are)
-        ctx->sens[set.slot].have = false;
-        ctx->adjres[set.slot].have = false;
-        ctx->objres[set.slot].have = false;
-    }
+    if (!set.adjoint) drop_derived(ctx, set.slot); // (an adjoint set's run leaves the results of the set it differentiates)
     begin_run(ctx);
     set.stats.assign((size_t)L, mag_stats{});
     int32_t *info = set.info;
@@ -2824,9 +2809,7 @@ int mag_set_variants(mag_ctx *ctx, int32_t num_variants, const double *xy, const
     if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "mag_set_variants before mag_upload");
     if (int rc = enter(ctx)) return rc;
     ctx->variants.have = ctx->variants.have_run = false;
-    ctx->sens[MAG_SET_VARIANTS].have = false;
-    ctx->adjres[MAG_SET_VARIANTS].have = false;
-    ctx->objres[MAG_SET_VARIANTS].have = false;
+    drop_derived(ctx, MAG_SET_VARIANTS);
     const int64_t N = ctx->N, E = ctx->E;
     const size_t bytes = 16 * (size_t)N * (size_t)V;
     const hipMemcpyKind kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -3187,12 +3170,128 @@ int sens_chunk(mag_ctx *ctx, size_t per_member, int32_t M, int64_t &chunk)
     return MAG_OK;
 }
 
-// the uploaded material for every member of a set that has none of its own
-int sens_uploaded_material(mag_ctx *ctx)
+// The solved members of a set as a pass reads them: where the set's run left their arrays, member after member (a stride of
+// 0: every member reads the same array).
+struct MemberView {
+    int64_t N = 0;
+    const double *xy = nullptr, *mat = nullptr, *u = nullptr, *f = nullptr, *u_in = nullptr, *f_in = nullptr;
+    int64_t xy_stride = 0, mat_stride = 0, loads_stride = 0; // doubles
+    // the head of the batch of members c0 .. c0 + count - 1
+    void head(magk::MemberBatch &mb, int32_t c0, int32_t count) const
+    {
+        mb.count = count;
+        mb.mat_stride = mat_stride;
+        mb.mat = mat + (size_t)mat_stride * c0;
+        mb.xy_stride = xy_stride;
+        mb.xy = xy + (size_t)xy_stride * c0;
+        mb.u = u + 2 * (size_t)N * c0;
+    }
+};
+
+// The material: a variant's own (v_mat, on the device since mag_set_variants), otherwise the uploaded one for every member,
+// which goes to the device here.
+int member_view(mag_ctx *ctx, int32_t set, MemberView &mv)
 {
-    const double mat[3] = {ctx->youngs, ctx->nu, ctx->thick};
-    HIPCHK(ctx->sens_mat.reserve(sizeof mat));
-    HIPCHK(hipMemcpy(ctx->sens_mat.p, mat, sizeof mat, hipMemcpyHostToDevice));
+    const MemberSet *ms = set == MAG_SET_CASES ? &ctx->cases : (set == MAG_SET_VARIANTS ? &ctx->variants : nullptr);
+    const bool own_xy = set == MAG_SET_VARIANTS && ctx->v_have_xy, own_mat = set == MAG_SET_VARIANTS;
+    const bool own_loads = set == MAG_SET_CASES || (set == MAG_SET_VARIANTS && ctx->v_have_loads);
+    mv.N = ctx->N;
+    mv.xy = own_xy ? ctx->v_xy.as<double>() : ctx->xy.as<double>();
+    mv.xy_stride = own_xy ? 2 * ctx->N : 0;
+    mv.u = ms ? ms->u.as<double>() : ctx->u.as<double>();
+    mv.f = ms ? ms->f.as<double>() : ctx->f.as<double>();
+    mv.u_in = own_loads ? ms->uin.as<double>() : ctx->uin.as<double>();
+    mv.f_in = own_loads ? ms->fin.as<double>() : ctx->fin.as<double>();
+    mv.loads_stride = own_loads ? 2 * ctx->N : 0;
+    if (!own_mat) {
+        const double mat[3] = {ctx->youngs, ctx->nu, ctx->thick};
+        HIPCHK(ctx->sens_mat.reserve(sizeof mat));
+        HIPCHK(hipMemcpy(ctx->sens_mat.p, mat, sizeof mat, hipMemcpyHostToDevice));
+    }
+    mv.mat = own_mat ? ctx->v_mat.as<double>() : ctx->sens_mat.as<double>();
+    mv.mat_stride = own_mat ? 3 : 0;
+    return MAG_OK;
+}
+
+struct Rows {
+    DevBuf *buf;
+    size_t bytes;     // per member
+    const char *name; // in the message of a failed reservation
+};
+#define ROWS(buf, bytes) Rows{&(buf), (bytes), #buf}
+
+int reserve_rows(mag_ctx *ctx, std::initializer_list<Rows> rows, size_t members)
+{
+    for (const Rows &r : rows) {
+        const hipError_t e = r.buf->reserve(r.bytes * members);
+        if (e != hipSuccess)
+            return fail(ctx, MAG_ERR_HIP, "%s.reserve(%zu) failed: %s", r.name, r.bytes * members, hipGetErrorString(e));
+    }
+    return MAG_OK;
+}
+
+// The members of a pass in chunks: per_member = the scratch bytes one member needs; `results` hold all M members, `scratch`
+// ONE chunk of them; launch(c0, count) fills a batch for the members from c0 and launches the pass on it.
+int run_chunks(mag_ctx *ctx, DerivedSet &out, int32_t M, size_t per_member, std::initializer_list<Rows> results,
+               std::initializer_list<Rows> scratch, const std::function<int(int32_t, int32_t)> &launch)
+{
+    int64_t chunk = 1;
+    if (int rc = sens_chunk(ctx, per_member, M, chunk)) return rc;
+    if (int rc = reserve_rows(ctx, results, (size_t)M)) return rc;
+    HIPCHK(out.scalars.reserve(64 * (size_t)M));
+    if (int rc = reserve_rows(ctx, scratch, (size_t)chunk)) return rc;
+    for (int32_t c0 = 0; c0 < M; c0 += (int32_t)chunk) {
+        if (int rc = launch(c0, (int32_t)std::min<int64_t>(chunk, M - c0))) return rc;
+        HIPCHK(hipGetLastError());
+    }
+    return MAG_OK;
+}
+
+// the end of a pass: its scalars on the host, the set held
+int hold_derived(mag_ctx *ctx, DerivedSet &out, int32_t M)
+{
+    hipStream_t s = ctx->stream;
+    out.scalars_h.assign(8 * (size_t)M, 0.0);
+    HIPCHK(hipMemcpyAsync(out.scalars_h.data(), out.scalars.p, 64 * (size_t)M, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    out.count = M;
+    out.have = true;
+    return MAG_OK;
+}
+
+// The checks of a pass's mag_download_* (fn; `sets`: the pass's results, which the entry point run_fn leaves; what: the caller's
+// struct in messages), all before any HIP call; *have: the results of the set
+int download_refused(mag_ctx *ctx, Pass pass, int32_t set, int32_t index, const void *o, const char *what,
+                     const char *fn, const char *run_fn, const DerivedSet **have)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "null %s", what);
+    if (index < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "member %d out of range", (int)index);
+    int32_t M = 0;
+    if (int rc = sens_refused(ctx, set, fn, &M)) return rc;
+    *have = &ctx->derived[pass][set];
+    if (!(*have)->have) return fail(ctx, MAG_ERR_STATE, "%s before %s of this set", fn, run_fn);
+    if (index >= (*have)->count) return fail(ctx, MAG_ERR_BAD_ARGS, "member %d out of range [0, %d)", (int)index, (int)(*have)->count);
+    return MAG_OK;
+}
+
+struct Download {
+    void *dst; // the caller's, or null: not wanted
+    const DevBuf &src;
+    size_t bytes; // per member
+};
+
+// ... and past them: the rows of member `index` to the caller's memory, the eight scalars
+int download_rows(mag_ctx *ctx, const DerivedSet &have, int32_t index, int32_t memory, std::initializer_list<Download> rows, double *scalars)
+{
+    if (int rc = enter(ctx)) return rc;
+    const hipMemcpyKind kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    hipStream_t s = ctx->stream;
+    const size_t i = (size_t)index;
+    for (const Download &r : rows)
+        if (r.dst) HIPCHK(hipMemcpyAsync(r.dst, r.src.as<char>() + r.bytes * i, r.bytes, kind, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int k = 0; k < 8; ++k) scalars[k] = have.scalars_h[8 * i + k];
     return MAG_OK;
 }
 
@@ -3204,79 +3303,42 @@ int mag_run_sensitivities(mag_ctx *ctx, int32_t set)
     int32_t M = 0;
     if (int rc = sens_refused(ctx, set, "mag_run_sensitivities", &M)) return rc;
     if (int rc = enter(ctx)) return rc;
-    hipStream_t s = ctx->stream;
     const int64_t N = ctx->N, E = ctx->E;
-    SensSet &out = ctx->sens[set];
+    const size_t vb = 16 * (size_t)N, eb = 8 * (size_t)E, pb = 8 * 4 * (size_t)magk::kSensBlocks;
+    DerivedSet &out = ctx->derived[PASS_SENS][set];
     out.have = false;
     magk::SensMesh mesh;
     if (int rc = sens_mesh(ctx, mesh)) return rc;
-    // the members' arrays: where the set's run left them
-    const MemberSet *ms = set == MAG_SET_CASES ? &ctx->cases : (set == MAG_SET_VARIANTS ? &ctx->variants : nullptr);
-    const bool own_xy = set == MAG_SET_VARIANTS && ctx->v_have_xy;
-    const bool own_loads = set == MAG_SET_CASES || (set == MAG_SET_VARIANTS && ctx->v_have_loads);
-    const double *xy = own_xy ? ctx->v_xy.as<double>() : ctx->xy.as<double>();
-    const double *u = ms ? ms->u.as<double>() : ctx->u.as<double>(), *f = ms ? ms->f.as<double>() : ctx->f.as<double>();
-    const double *uin = own_loads ? ms->uin.as<double>() : ctx->uin.as<double>();
-    const double *fin = own_loads ? ms->fin.as<double>() : ctx->fin.as<double>();
-    // the material: a variant's own (v_mat, on the device since mag_set_variants), otherwise the uploaded one for every member
-    const bool own_mat = set == MAG_SET_VARIANTS;
-    if (!own_mat)
-        if (int rc = sens_uploaded_material(ctx)) return rc;
-    // members per launch, by the scratch of one chunk: a nu term per element, the partial sums
-    int64_t chunk = 1;
-    if (int rc = sens_chunk(ctx, 8 * (size_t)E + 8 * 4 * (size_t)magk::kSensBlocks, M, chunk)) return rc;
-    HIPCHK(out.energy.reserve(8 * (size_t)E * M));
-    HIPCHK(out.dxy.reserve(16 * (size_t)N * M));
-    HIPCHK(out.scalars.reserve(64 * (size_t)M));
-    HIPCHK(ctx->sens_nuterm.reserve(8 * (size_t)E * chunk));
-    HIPCHK(ctx->sens_part.reserve(8 * 4 * (size_t)magk::kSensBlocks * chunk));
-    for (int32_t c0 = 0; c0 < M; c0 += (int32_t)chunk) {
+    MemberView mv;
+    if (int rc = member_view(ctx, set, mv)) return rc;
+    const auto launch = [&](int32_t c0, int32_t count) {
         magk::SensBatch sb = {};
-        sb.count = (int32_t)std::min<int64_t>(chunk, M - c0);
-        sb.mat_stride = own_mat ? 3 : 0;
-        sb.mat = own_mat ? ctx->v_mat.as<double>() + 3 * (size_t)c0 : ctx->sens_mat.as<double>();
-        sb.xy_stride = own_xy ? 2 * N : 0;
-        sb.xy = xy + (size_t)sb.xy_stride * c0;
-        sb.u = u + 2 * (size_t)N * c0;
-        sb.f_out = f + 2 * (size_t)N * c0;
-        sb.loads_stride = own_loads ? 2 * N : 0;
-        sb.u_in = uin + (size_t)sb.loads_stride * c0;
-        sb.f_in = fin + (size_t)sb.loads_stride * c0;
+        mv.head(sb, c0, count);
+        sb.f_out = mv.f + 2 * (size_t)N * c0;
+        sb.loads_stride = mv.loads_stride;
+        sb.u_in = mv.u_in + (size_t)mv.loads_stride * c0;
+        sb.f_in = mv.f_in + (size_t)mv.loads_stride * c0;
         sb.energy = out.energy.as<double>() + (size_t)E * c0;
         sb.dxy = out.dxy.as<double>() + 2 * (size_t)N * c0;
         sb.scalars = out.scalars.as<double>() + 8 * (size_t)c0;
         sb.nuterm = ctx->sens_nuterm.as<double>();
         sb.partials = ctx->sens_part.as<double>();
-        magk::sensitivities(mesh, sb, s);
-        HIPCHK(hipGetLastError());
-    }
-    out.scalars_h.assign(8 * (size_t)M, 0.0);
-    HIPCHK(hipMemcpyAsync(out.scalars_h.data(), out.scalars.p, 64 * (size_t)M, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    out.count = M;
-    out.have = true;
-    return MAG_OK;
+        magk::sensitivities(mesh, sb, ctx->stream);
+        return (int)MAG_OK;
+    };
+    // (the scratch of one member: a nu term per element, the partial sums)
+    if (int rc = run_chunks(ctx, out, M, eb + pb, {ROWS(out.energy, eb), ROWS(out.dxy, vb)}, {ROWS(ctx->sens_nuterm, eb), ROWS(ctx->sens_part, pb)}, launch))
+        return rc;
+    return hold_derived(ctx, out, M);
 }
 
 int mag_download_sensitivity(mag_ctx *ctx, int32_t set, int32_t index, mag_sensitivity *o)
 {
-    if (!ctx) return MAG_ERR_BAD_ARGS;
-    if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "null sensitivity");
-    if (index < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "member %d out of range", (int)index);
-    int32_t M = 0;
-    if (int rc = sens_refused(ctx, set, "mag_download_sensitivity", &M)) return rc;
-    const SensSet &have = ctx->sens[set];
-    if (!have.have) return fail(ctx, MAG_ERR_STATE, "mag_download_sensitivity before mag_run_sensitivities of this set");
-    if (index >= have.count) return fail(ctx, MAG_ERR_BAD_ARGS, "member %d out of range [0, %d)", (int)index, (int)have.count);
-    if (int rc = enter(ctx)) return rc;
-    const hipMemcpyKind kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    hipStream_t s = ctx->stream;
-    const size_t eb = 8 * (size_t)ctx->E, vb = 16 * (size_t)ctx->N, i = (size_t)index;
-    if (o->energy_out) HIPCHK(hipMemcpyAsync(o->energy_out, have.energy.as<char>() + eb * i, eb, kind, s));
-    if (o->dxy_out) HIPCHK(hipMemcpyAsync(o->dxy_out, have.dxy.as<char>() + vb * i, vb, kind, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (int k = 0; k < 8; ++k) o->scalars[k] = have.scalars_h[8 * i + k];
-    return MAG_OK;
+    const DerivedSet *have = nullptr;
+    if (int rc = download_refused(ctx, PASS_SENS, set, index, o, "sensitivity", "mag_download_sensitivity", "mag_run_sensitivities", &have))
+        return rc;
+    const size_t eb = 8 * (size_t)ctx->E, vb = 16 * (size_t)ctx->N;
+    return download_rows(ctx, *have, index, o->memory, {{o->energy_out, have->energy, eb}, {o->dxy_out, have->dxy, vb}}, o->scalars);
 }
 
 // ---- adjoint sensitivities of the solved members of a set: the adjoint systems through the member-set driver, then the
@@ -3289,13 +3351,14 @@ struct KeptRun {
     mag_ctx *ctx;
     const size_t vb, eb;
     const mag_stats stats;
-    const bool have_run, have_sens, have_adjoint, have_objective;
+    const bool have_run;
+    bool have_derived[PASS_COUNT]; // (of the single case)
     const int32_t history_len;
     bool armed = false;
     explicit KeptRun(mag_ctx *c)
-        : ctx(c), vb(16 * (size_t)c->N), eb(8 * (size_t)c->E), stats(c->stats), have_run(c->have_run), have_sens(c->sens[MAG_SET_RUN].have),
-          have_adjoint(c->adjres[MAG_SET_RUN].have), have_objective(c->objres[MAG_SET_RUN].have), history_len(c->opt.history_len)
+        : ctx(c), vb(16 * (size_t)c->N), eb(8 * (size_t)c->E), stats(c->stats), have_run(c->have_run), history_len(c->opt.history_len)
     {
+        for (int k = 0; k < PASS_COUNT; ++k) have_derived[k] = ctx->derived[k][MAG_SET_RUN].have;
     }
     int keep() // (u, f, stress: the CSR operator's phase expands into the context's u, a lent problem runs through all three)
     {
@@ -3314,9 +3377,7 @@ struct KeptRun {
         ctx->opt.history_len = history_len;
         ctx->stats = stats;
         ctx->have_run = have_run;
-        ctx->sens[MAG_SET_RUN].have = have_sens;
-        ctx->adjres[MAG_SET_RUN].have = have_adjoint;
-        ctx->objres[MAG_SET_RUN].have = have_objective;
+        for (int k = 0; k < PASS_COUNT; ++k) ctx->derived[k][MAG_SET_RUN].have = have_derived[k];
         if (!armed) return;
         hipStream_t s = ctx->stream;
         (void)hipMemcpyAsync(ctx->u.p, ctx->adj_keep.p, vb, hipMemcpyDeviceToDevice, s);
@@ -3326,21 +3387,13 @@ struct KeptRun {
     }
 };
 
-// the checks of the adjoint getters, all before any HIP call
-int adjoint_refused(mag_ctx *ctx, int32_t set, const char *fn, int32_t *count)
-{
-    if (int rc = sens_refused(ctx, set, fn, count)) return rc;
-    if (!ctx->adjres[set].have) return fail(ctx, MAG_ERR_STATE, "%s before mag_run_adjoint of this set", fn);
-    return MAG_OK;
-}
-
 // mag_run_adjoint past its checks: dJ_du [M][2N] on the host or -- mag_run_objective's -- already on the device
 int run_adjoint(mag_ctx *ctx, int32_t set, int32_t M, const double *dJ_du, int32_t memory)
 {
     hipStream_t s = ctx->stream;
     const int64_t N = ctx->N, E = ctx->E;
     const size_t vb = 16 * (size_t)N;
-    AdjointSet &out = ctx->adjres[set];
+    DerivedSet &out = ctx->derived[PASS_ADJOINT][set];
     MemberSet &adj = ctx->adj[set];
     out.have = false;
     adj.have = adj.have_run = false;
@@ -3362,29 +3415,14 @@ int run_adjoint(mag_ctx *ctx, int32_t set, int32_t M, const double *dJ_du, int32
     const std::string run_message = ctx->err;
 
     // ---- the bilinear pass over (u of the set, lambda = u of its adjoint set), chunked as mag_run_sensitivities is
+    const size_t eb = 8 * (size_t)E, pb = 8 * 2 * (size_t)magk::kSensBlocks;
     magk::SensMesh mesh;
     if (int rc = sens_mesh(ctx, mesh)) return rc;
-    const bool own_xy = set == MAG_SET_VARIANTS && ctx->v_have_xy, own_mat = set == MAG_SET_VARIANTS;
-    const double *xy = own_xy ? ctx->v_xy.as<double>() : ctx->xy.as<double>();
-    const double *u = set == MAG_SET_RUN ? ctx->u.as<double>() : (set == MAG_SET_CASES ? ctx->cases : ctx->variants).u.as<double>();
-    if (!own_mat)
-        if (int rc = sens_uploaded_material(ctx)) return rc;
-    int64_t chunk = 1;
-    if (int rc = sens_chunk(ctx, 8 * (size_t)E + 8 * 2 * (size_t)magk::kSensBlocks, M, chunk)) return rc;
-    HIPCHK(out.dloads.reserve(vb * M));
-    HIPCHK(out.delem.reserve(8 * (size_t)E * M));
-    HIPCHK(out.dxy.reserve(vb * M));
-    HIPCHK(out.scalars.reserve(64 * (size_t)M));
-    HIPCHK(ctx->sens_nuterm.reserve(8 * (size_t)E * chunk));
-    HIPCHK(ctx->sens_part.reserve(8 * 2 * (size_t)magk::kSensBlocks * chunk));
-    for (int32_t c0 = 0; c0 < M; c0 += (int32_t)chunk) {
+    MemberView mv;
+    if (int rc = member_view(ctx, set, mv)) return rc;
+    const auto launch = [&](int32_t c0, int32_t count) {
         magk::AdjointBatch ab = {};
-        ab.count = (int32_t)std::min<int64_t>(chunk, M - c0);
-        ab.mat_stride = own_mat ? 3 : 0;
-        ab.mat = own_mat ? ctx->v_mat.as<double>() + 3 * (size_t)c0 : ctx->sens_mat.as<double>();
-        ab.xy_stride = own_xy ? 2 * N : 0;
-        ab.xy = xy + (size_t)ab.xy_stride * c0;
-        ab.u = u + 2 * (size_t)N * c0;
+        mv.head(ab, c0, count);
         ab.lam = adj.u.as<double>() + 2 * (size_t)N * c0;
         ab.g = adj.fin.as<double>() + 2 * (size_t)N * c0;
         ab.f_adj = adj.f.as<double>() + 2 * (size_t)N * c0;
@@ -3395,13 +3433,12 @@ int run_adjoint(mag_ctx *ctx, int32_t set, int32_t M, const double *dJ_du, int32
         ab.nuterm = ctx->sens_nuterm.as<double>();
         ab.partials = ctx->sens_part.as<double>();
         HIPCHK(magk::adjoint_bilinear(mesh, ab, s));
-        HIPCHK(hipGetLastError());
-    }
-    out.scalars_h.assign(8 * (size_t)M, 0.0);
-    HIPCHK(hipMemcpyAsync(out.scalars_h.data(), out.scalars.p, 64 * (size_t)M, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    out.count = M;
-    out.have = true;
+        return (int)MAG_OK;
+    };
+    if (int rc = run_chunks(ctx, out, M, eb + pb, {ROWS(out.dloads, vb), ROWS(out.delem, eb), ROWS(out.dxy, vb)},
+                            {ROWS(ctx->sens_nuterm, eb), ROWS(ctx->sens_part, pb)}, launch))
+        return rc;
+    if (int rc = hold_derived(ctx, out, M)) return rc;
     if (status != MAG_OK) ctx->err = run_message;
     return status;
 }
@@ -3420,37 +3457,26 @@ int mag_run_adjoint(mag_ctx *ctx, int32_t set, const double *dJ_du, int32_t memo
 
 int mag_download_adjoint(mag_ctx *ctx, int32_t set, int32_t index, mag_adjoint *o)
 {
-    if (!ctx) return MAG_ERR_BAD_ARGS;
-    if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "null adjoint");
-    if (index < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "member %d out of range", (int)index);
-    int32_t M = 0;
-    if (int rc = adjoint_refused(ctx, set, "mag_download_adjoint", &M)) return rc;
-    const AdjointSet &have = ctx->adjres[set];
-    if (index >= have.count) return fail(ctx, MAG_ERR_BAD_ARGS, "member %d out of range [0, %d)", (int)index, (int)have.count);
-    if (int rc = enter(ctx)) return rc;
-    const hipMemcpyKind kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    hipStream_t s = ctx->stream;
-    const size_t eb = 8 * (size_t)ctx->E, vb = 16 * (size_t)ctx->N, i = (size_t)index;
-    if (o->lambda_out) HIPCHK(hipMemcpyAsync(o->lambda_out, ctx->adj[set].u.as<char>() + vb * i, vb, kind, s));
-    if (o->dloads_out) HIPCHK(hipMemcpyAsync(o->dloads_out, have.dloads.as<char>() + vb * i, vb, kind, s));
-    if (o->delem_out) HIPCHK(hipMemcpyAsync(o->delem_out, have.delem.as<char>() + eb * i, eb, kind, s));
-    if (o->dxy_out) HIPCHK(hipMemcpyAsync(o->dxy_out, have.dxy.as<char>() + vb * i, vb, kind, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (int k = 0; k < 8; ++k) o->scalars[k] = have.scalars_h[8 * i + k];
-    return MAG_OK;
+    const DerivedSet *have = nullptr;
+    if (int rc = download_refused(ctx, PASS_ADJOINT, set, index, o, "adjoint", "mag_download_adjoint", "mag_run_adjoint", &have)) return rc;
+    const size_t eb = 8 * (size_t)ctx->E, vb = 16 * (size_t)ctx->N;
+    return download_rows(ctx, *have, index, o->memory,
+                         {{o->lambda_out, ctx->adj[set].u, vb}, {o->dloads_out, have->dloads, vb}, {o->delem_out, have->delem, eb},
+                          {o->dxy_out, have->dxy, vb}},
+                         o->scalars);
 }
 
 int mag_get_adjoint_stats(const mag_ctx *ctx, int32_t set, int32_t index, mag_stats *st)
 {
     if (!ctx || !st || index < 0 || set < MAG_SET_RUN || set > MAG_SET_VARIANTS || ctx->comm.nranks > 1) return MAG_ERR_BAD_ARGS;
-    if (!ctx->adjres[set].have) return MAG_ERR_STATE;
+    if (!ctx->derived[PASS_ADJOINT][set].have) return MAG_ERR_STATE;
     return member_stats(ctx->adj[set], index, st);
 }
 
 int mag_get_adjoint_info(const mag_ctx *ctx, int32_t set, int32_t info[4])
 {
     if (!ctx || !info || set < MAG_SET_RUN || set > MAG_SET_VARIANTS || ctx->comm.nranks > 1) return MAG_ERR_BAD_ARGS;
-    if (!ctx->adjres[set].have) return MAG_ERR_STATE;
+    if (!ctx->derived[PASS_ADJOINT][set].have) return MAG_ERR_STATE;
     return set_info(ctx->adj[set], info);
 }
 
@@ -3476,15 +3502,12 @@ int mag_run_objective(mag_ctx *ctx, int32_t set, const mag_objective *obj, int32
     hipStream_t s = ctx->stream;
     const int64_t N = ctx->N, E = ctx->E;
     const size_t vb = 16 * (size_t)N;
-    ObjectiveSet &out = ctx->objres[set];
+    DerivedSet &out = ctx->derived[PASS_OBJECTIVE][set];
     out.have = out.totals = false;
     magk::SensMesh mesh;
     if (int rc = sens_mesh(ctx, mesh)) return rc;
-    const bool own_xy = set == MAG_SET_VARIANTS && ctx->v_have_xy, own_mat = set == MAG_SET_VARIANTS;
-    const double *xy = own_xy ? ctx->v_xy.as<double>() : ctx->xy.as<double>();
-    const double *u = set == MAG_SET_RUN ? ctx->u.as<double>() : (set == MAG_SET_CASES ? ctx->cases : ctx->variants).u.as<double>();
-    if (!own_mat)
-        if (int rc = sens_uploaded_material(ctx)) return rc;
+    MemberView mv;
+    if (int rc = member_view(ctx, set, mv)) return rc;
     // the caller's rows: one for all members or one per member, on the device as they are
     const int64_t row = lsq ? 2 * N : E, stride = obj->per_member ? row : 0;
     const size_t rows_b = 8 * (size_t)row * (obj->per_member ? (size_t)M : 1);
@@ -3501,26 +3524,10 @@ int mag_run_objective(mag_ctx *ctx, int32_t set, const mag_objective *obj, int32
             target = ctx->obj_target.as<double>();
         }
     }
-    // members per launch, by the scratch of one chunk: summands, nu terms and factors per element, the partial sums
-    int64_t chunk = 1;
-    if (int rc = sens_chunk(ctx, 8 * (size_t)row + 16 * (size_t)E + 8 * 2 * (size_t)magk::kSensBlocks + 8, M, chunk)) return rc;
-    HIPCHK(out.g.reserve(vb * M));
-    HIPCHK(out.pxy.reserve(vb * M));
-    HIPCHK(out.scalars.reserve(64 * (size_t)M));
-    HIPCHK(ctx->obj_terms.reserve(8 * (size_t)row * chunk));
-    HIPCHK(ctx->sens_nuterm.reserve(8 * (size_t)E * chunk));
-    HIPCHK(ctx->obj_helem.reserve(8 * (size_t)E * chunk));
-    HIPCHK(ctx->sens_part.reserve(8 * 2 * (size_t)magk::kSensBlocks * chunk));
-    HIPCHK(ctx->obj_factor.reserve(8 * (size_t)chunk));
-    for (int32_t c0 = 0; c0 < M; c0 += (int32_t)chunk) {
+    const auto launch = [&](int32_t c0, int32_t count) {
         magk::ObjectiveBatch ob = {};
-        ob.count = (int32_t)std::min<int64_t>(chunk, M - c0);
+        mv.head(ob, c0, count);
         ob.kind = obj->kind;
-        ob.mat_stride = own_mat ? 3 : 0;
-        ob.mat = own_mat ? ctx->v_mat.as<double>() + 3 * (size_t)c0 : ctx->sens_mat.as<double>();
-        ob.xy_stride = own_xy ? 2 * N : 0;
-        ob.xy = xy + (size_t)ob.xy_stride * c0;
-        ob.u = u + 2 * (size_t)N * c0;
         ob.w_stride = stride;
         ob.w = w ? w + (size_t)stride * c0 : nullptr;
         ob.target_stride = stride;
@@ -3536,8 +3543,14 @@ int mag_run_objective(mag_ctx *ctx, int32_t set, const mag_objective *obj, int32
         ob.partials = ctx->sens_part.as<double>();
         ob.factor = ctx->obj_factor.as<double>();
         magk::objective(mesh, ob, s);
-        HIPCHK(hipGetLastError());
-    }
+        return (int)MAG_OK;
+    };
+    // (the scratch of one member: summands, nu terms and factors per element, the partial sums, the member's factor)
+    const size_t eb = 8 * (size_t)E, tb = 8 * (size_t)row, pb = 8 * 2 * (size_t)magk::kSensBlocks;
+    if (int rc = run_chunks(ctx, out, M, tb + 2 * eb + pb + 8, {ROWS(out.g, vb), ROWS(out.pxy, vb)},
+                            {ROWS(ctx->obj_terms, tb), ROWS(ctx->sens_nuterm, eb), ROWS(ctx->obj_helem, eb), ROWS(ctx->sens_part, pb), ROWS(ctx->obj_factor, 8)},
+                            launch))
+        return rc;
     HIPCHK(hipStreamSynchronize(s)); // (the caller's rows are read, the results stand)
     out.count = M;
     out.have = true;
@@ -3547,15 +3560,13 @@ int mag_run_objective(mag_ctx *ctx, int32_t set, const mag_objective *obj, int32
         status = run_adjoint(ctx, set, M, out.g.as<double>(), MAG_MEM_DEVICE);
         if (status != MAG_OK && status != MAG_ERR_NOT_CONVERGED) return status;
         run_message = ctx->err;
-        const AdjointSet &adj = ctx->adjres[set];
+        const DerivedSet &adj = ctx->derived[PASS_ADJOINT][set];
         HIPCHK(out.dxy.reserve(vb * M));
         magk::objective_totals(N, M, out.pxy.as<double>(), adj.dxy.as<double>(), adj.scalars.as<double>(), out.dxy.as<double>(),
                                out.scalars.as<double>(), s);
         HIPCHK(hipGetLastError());
     }
-    out.scalars_h.assign(8 * (size_t)M, 0.0);
-    HIPCHK(hipMemcpyAsync(out.scalars_h.data(), out.scalars.p, 64 * (size_t)M, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    if (int rc = hold_derived(ctx, out, M)) return rc;
     out.totals = with_adjoint != 0;
     if (status != MAG_OK) ctx->err = run_message;
     return status;
@@ -3563,26 +3574,14 @@ int mag_run_objective(mag_ctx *ctx, int32_t set, const mag_objective *obj, int32
 
 int mag_download_objective(mag_ctx *ctx, int32_t set, int32_t index, mag_objective_result *o)
 {
-    if (!ctx) return MAG_ERR_BAD_ARGS;
-    if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "null objective result");
-    if (index < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "member %d out of range", (int)index);
-    int32_t M = 0;
-    if (int rc = sens_refused(ctx, set, "mag_download_objective", &M)) return rc;
-    const ObjectiveSet &have = ctx->objres[set];
-    if (!have.have) return fail(ctx, MAG_ERR_STATE, "mag_download_objective before mag_run_objective of this set");
-    if (index >= have.count) return fail(ctx, MAG_ERR_BAD_ARGS, "member %d out of range [0, %d)", (int)index, (int)have.count);
-    if (o->dxy_out && !have.totals)
+    const DerivedSet *have = nullptr;
+    if (int rc = download_refused(ctx, PASS_OBJECTIVE, set, index, o, "objective result", "mag_download_objective", "mag_run_objective", &have))
+        return rc;
+    if (o->dxy_out && !have->totals)
         return fail(ctx, MAG_ERR_STATE, "mag_download_objective: dxy_out needs mag_run_objective with with_adjoint != 0");
-    if (int rc = enter(ctx)) return rc;
-    const hipMemcpyKind kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    hipStream_t s = ctx->stream;
-    const size_t vb = 16 * (size_t)ctx->N, i = (size_t)index;
-    if (o->g_out) HIPCHK(hipMemcpyAsync(o->g_out, have.g.as<char>() + vb * i, vb, kind, s));
-    if (o->pxy_out) HIPCHK(hipMemcpyAsync(o->pxy_out, have.pxy.as<char>() + vb * i, vb, kind, s));
-    if (o->dxy_out) HIPCHK(hipMemcpyAsync(o->dxy_out, have.dxy.as<char>() + vb * i, vb, kind, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (int k = 0; k < 8; ++k) o->scalars[k] = have.scalars_h[8 * i + k];
-    return MAG_OK;
+    const size_t vb = 16 * (size_t)ctx->N;
+    return download_rows(ctx, *have, index, o->memory, {{o->g_out, have->g, vb}, {o->pxy_out, have->pxy, vb}, {o->dxy_out, have->dxy, vb}},
+                         o->scalars);
 }
 
 int mag_solve(mag_ctx *ctx, const mag_problem *p, mag_result *r)

@@ -9,16 +9,9 @@
 
 namespace magk {
 
-// `count` members of one launch, grid.y = the member, as SensBatch: every pointer is the FIRST member's; a stride of 0: every
-// member reads the same array.
-struct ObjectiveBatch {
-    int32_t count;
+// The members of one launch (MemberBatch, sens.h) with the objective.
+struct ObjectiveBatch : MemberBatch {
     int32_t kind;          // enum mag_objective_kind
-    const double *mat;     // E, nu, thickness
-    int64_t mat_stride;    // doubles: 3 (a material per member) or 0
-    const double *xy;      // caller-order coordinates
-    int64_t xy_stride;     // doubles: 2N or 0
-    const double *u;       // [count][2N] the members' solved displacements, caller numbering
     const double *w;       // weights: 2N per row (MAG_OBJ_DISP_LSQ), E per row or null = ones (MAG_OBJ_STRESS_PNORM)
     int64_t w_stride;      // doubles: the row's length (a row per member) or 0
     const double *target;  // MAG_OBJ_DISP_LSQ: 2N per row, or null = zeros

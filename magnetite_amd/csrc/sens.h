@@ -8,16 +8,20 @@ namespace magk {
 
 constexpr int kSensBlocks = 256; // workgroups per member of the scalars' first stage: a fixed shape, whatever the mesh
 
-// `count` solved members of one launch, grid.y = the member.  Every pointer is the FIRST member's; a stride of 0: every member
-// reads the same array (the uploaded coordinates, the uploaded values).
-struct SensBatch {
+// The head of every pass's batch (SensBatch, AdjointBatch, ObjectiveBatch): `count` solved members of one launch, grid.y = the
+// member.  Every pointer of a batch is the FIRST member's; a stride of 0: every member reads the same array (the uploaded
+// coordinates, the uploaded values).  member_of (member_pass.h) unpacks it on the device.
+struct MemberBatch {
     int32_t count;
     int32_t pad;
-    const double *mat;    // E, nu, thickness
-    int64_t mat_stride;   // doubles: 3 (a material per member) or 0
-    const double *xy;     // caller-order coordinates
-    int64_t xy_stride;    // doubles: 2N or 0
-    const double *u;      // [count][2N] solved displacements, caller numbering
+    const double *mat;  // E, nu, thickness
+    int64_t mat_stride; // doubles: 3 (a material per member) or 0
+    const double *xy;   // caller-order coordinates
+    int64_t xy_stride;  // doubles: 2N or 0
+    const double *u;    // [count][2N] solved displacements, caller numbering
+};
+
+struct SensBatch : MemberBatch {
     const double *f_out;  // [count][2N] forces with the reactions
     const double *u_in;   // prescribed values
     const double *f_in;
