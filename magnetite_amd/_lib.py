@@ -96,7 +96,7 @@ class ObjectiveResult(C.Structure):
                 ("memory", C.c_int32), ("reserved", C.c_int32)]
 
 
-HASHED_SOURCES = ("persist.hip", "cg.hip", "cg_device.h", "exact.hip", "symbolic.hip", "kernels.h")
+HASHED_SOURCES = ("persist.hip", "persist_kernel.h", "persist_shapes.h", "persist_inst.hip", "cg.hip", "cg_device.h", "exact.hip", "symbolic.hip", "kernels.h")
 
 
 def kernel_source_hash():

@@ -198,7 +198,7 @@ struct mag_ctx {
     int32_t g_all = 1; // ... of the rank with the most tiles: dot-partial slots of the exchange buffer (multi-GPU)
     size_t cwords = 0; // doubles per exchange buffer: nsums * g_all + 2 * n_iface
     bool pre = false;  // mag_options.preconditioner != 0
-    // on-chip CG (persist.hip, k_cg_persist): the whole solve in one launch when every tile fits registers + LDS
+    // on-chip CG (persist_kernel.h, k_cg_persist): the whole solve in one launch when every tile fits registers + LDS
     bool persist = false, persist_failed = false;
     // after a grid-barrier timeout the context streams for `persist_retry_in` solves, then tries the on-chip kernel again;
     // the wait doubles with every further failure (8 .. 1024 solves) and starts over after a success
@@ -1457,7 +1457,7 @@ int cg_phase_fused(mag_ctx *ctx)
     return MAG_OK;
 }
 
-// ---- on-chip variant: ONE launch for the whole solve (persist.hip, k_cg_persist) ----
+// ---- on-chip variant: ONE launch for the whole solve (persist_kernel.h, k_cg_persist) ----
 // Which instantiation (mode): edge blocks in registers when every row of the mesh is one short fan (1; k_ring16 left the
 // answer behind tile_rdeg's two arrays), the triangle walk with cached weights otherwise (0).  One 4-byte read per solve.
 // Round 4: a mesh whose rows are single fans of ANY length (flag word 1: gmsh-type meshes, a quarter of their nodes with
@@ -1576,7 +1576,7 @@ int persist_prepare_blocks(mag_ctx *ctx, bool mg, magk::PersistParams &P, int &e
         HIPCHK(ctx->kblocks.reserve(8 * (size_t)(3 * magk::persist_block_entries()) * (size_t)npad));
         P.kblocks = ctx->kblocks.as<double>();
         P.kb_stride = npad;
-        magk::edge_blocks_build(P, ctx->B, ctx->kblocks.as<double>(), eb_mode, s);
+        magk::edge_blocks_build(P, ctx->B, ctx->kblocks.as<double>(), eb_mode, 0, s);
     }
     return MAG_OK;
 }
@@ -1665,7 +1665,8 @@ int cg_phase_persist(mag_ctx *ctx)
     }
     int eb_mode = 0;
     if (int rc = persist_prepare_blocks(ctx, mg, P, eb_mode)) return rc;
-    magk::persist_launch(P, ctx->B, grid + P.comm_wg, eb_mode, s);
+    if (!magk::persist_launch(P, ctx->B, grid + P.comm_wg, 1, magk::PERSIST_SINGLE, eb_mode, s))
+        return fail(ctx, MAG_ERR_STATE, "on-chip CG: no kernel for this shape");
     if (stamps) {
         // (several ranks: one file per rank, "<name>.<rank>"; with an exchange workgroup its row follows the compute workgroups')
         const int rows = grid + P.comm_wg;
@@ -2471,7 +2472,7 @@ int solve_case_alone(mag_ctx *ctx, MemberSet &set, int32_t c, mag_stats &out, bo
 // every member's CG statistics are in stats[c0 + k]; a member whose group gave up at its barrier (timed_out) or that stopped at
 // the iteration cap with an earlier best iterate is marked `alone`: the caller redoes it through the single-case phases.
 int launch_members(mag_ctx *ctx, magk::PersistParams &P, int32_t G, int32_t c0, int32_t n, int eb_mode, std::vector<mag_stats> &stats,
-                   std::vector<uint8_t> &alone, std::vector<uint8_t> &timed_out, const std::function<void()> &launch)
+                   std::vector<uint8_t> &alone, std::vector<uint8_t> &timed_out, magk::PersistMembers members)
 {
     using magk::FusedState;
     hipStream_t s = ctx->stream;
@@ -2493,7 +2494,8 @@ int launch_members(mag_ctx *ctx, magk::PersistParams &P, int32_t G, int32_t c0, 
     P.st = ctx->launch_state.as<FusedState>();
     P.hist_len = c0 == 0 ? ctx->opt.history_len : 0; // (member 0's alone: the kernel keeps it from the launch's other members)
     HIPCHK(hipEventRecord(ctx->ev[8], s));
-    launch();
+    if (!magk::persist_launch(P, ctx->B, G, n, members, eb_mode, s)) // (unreachable: run_members has asked persist_shape)
+        return fail(ctx, MAG_ERR_STATE, "on-chip CG: no kernel for this shape");
     HIPCHK(hipEventRecord(ctx->ev[9], s));
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h_st.data(), ctx->launch_state.p, sizeof(FusedState) * (size_t)n, hipMemcpyDeviceToHost, s));
@@ -2553,10 +2555,8 @@ struct MemberHooks {
     // after the shared phases (order, tables, CSR pattern; ev[2] is recorded): the set's buffers -- and, for load cases, K and
     // every case's right-hand side
     std::function<int()> prepare;
-    // side by side, around ONE launch for members [c0, c0 + n): what the launch reads (P.bP and P.x at the least), the launch
-    // itself, what follows it
+    // side by side, around ONE launch for members [c0, c0 + n): what the launch reads (P.bP and P.x at the least), what follows it
     std::function<int(magk::PersistParams &P, int32_t c0, int32_t n, int eb_mode)> before_launch;
-    std::function<void(magk::PersistParams &P, int32_t n, int eb_mode)> launch;
     std::function<int(int32_t c0, int32_t n)> after_launch;
     // member c through the single-case phases, the uploaded problem lent to it
     std::function<int(int32_t c, mag_stats &out, bool timed_out_before)> solve_alone;
@@ -2604,6 +2604,9 @@ int run_members(mag_ctx *ctx, MemberSet &set, LentProblem &keep, const MemberHoo
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
     const int32_t G = ctx->persist_grid, fit = G >= 1 ? cus / G : 0;
     int32_t per_launch = 0;
+    // (an adjoint set is solved as the set it differentiates is: the variants' by the variant kernels, the others as load cases)
+    const magk::PersistMembers members = set.slot == MAG_SET_VARIANTS ? magk::PERSIST_VARIANTS : magk::PERSIST_CASES;
+    magk::PersistShape shape;
     magk::PersistParams P = {};
     int eb_mode = 0;
     // (ctx->persist: cg_variant 2, fp64, matrix-free, no preconditioner, not in back-off, the mesh fits -- ensure_order)
@@ -2611,7 +2614,7 @@ int run_members(mag_ctx *ctx, MemberSet &set, LentProblem &keep, const MemberHoo
         P.nranks = 1;
         persist_common_params(ctx, false, P);
         if (int rc = persist_prepare_blocks(ctx, false, P, eb_mode, !keep.whole)) return rc;
-        if (magk::persist_cases_shape(ctx->B, G, ctx->persist_k, eb_mode)) per_launch = fit;
+        if (magk::persist_shape(ctx->B, 1, G, ctx->persist_k, eb_mode, members, shape)) per_launch = fit;
     }
     info[1] = per_launch;
     std::vector<uint8_t> alone((size_t)L, per_launch ? 0 : 1), timed_out((size_t)L, 0);
@@ -2619,8 +2622,7 @@ int run_members(mag_ctx *ctx, MemberSet &set, LentProblem &keep, const MemberHoo
         for (int32_t c0 = 0; c0 < L; c0 += per_launch) {
             const int32_t n = std::min(per_launch, L - c0);
             if (int rc = hooks.before_launch(P, c0, n, eb_mode)) return rc;
-            if (int rc = launch_members(ctx, P, G, c0, n, eb_mode, set.stats, alone, timed_out, [&] { hooks.launch(P, n, eb_mode); }))
-                return rc;
+            if (int rc = launch_members(ctx, P, G, c0, n, eb_mode, set.stats, alone, timed_out, members)) return rc;
             ++info[2];
             if (hooks.after_launch)
                 if (int rc = hooks.after_launch(c0, n)) return rc;
@@ -2722,9 +2724,6 @@ int run_case_set(mag_ctx *ctx, MemberSet &set)
         P.bP = (const double2 *)at(set.bP, vb, c0);
         P.x = (double2 *)at(set.x, vb, c0);
         return MAG_OK;
-    };
-    h.launch = [&](magk::PersistParams &P, int32_t n, int eb_mode) {
-        magk::persist_launch_cases(P, ctx->B, ctx->persist_grid, n, eb_mode, s);
     };
     h.solve_alone = [&](int32_t c, mag_stats &out, bool timed_out_before) { return solve_case_alone(ctx, set, c, out, timed_out_before); };
     h.post = [&]() -> int { // per case: scatter-back, reactions, stress
@@ -2995,16 +2994,13 @@ int run_variant_set(mag_ctx *ctx, MemberSet &set)
             P.kblocks = ctx->v_kblocks.as<double>();
             P.kb_stride = npad;
             if (eb_mode == 2) P.ovf_rec = ctx->v_ovf.as<double>();
-            magk::edge_blocks_build_variants(P, ctx->B, eb_mode, n, s);
+            magk::edge_blocks_build(P, ctx->B, nullptr, eb_mode, n, s);
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ctx->evV[4], s));
         P.bP = (const double2 *)bP;
         P.x = (double2 *)xP;
         return MAG_OK;
-    };
-    h.launch = [&](magk::PersistParams &P, int32_t n, int eb_mode) {
-        magk::persist_launch_variants(P, ctx->B, ctx->persist_grid, n, eb_mode, s);
     };
     // scatter-back, reactions (this chunk's K) and stress (the variant's geometry and material); a variant that is redone
     // afterwards gets all three again from its own solve

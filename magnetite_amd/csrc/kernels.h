@@ -7,6 +7,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "persist_shapes.h"
+
 // Wait states of the hand-written VMEM stores (persist.hip, exact.hip).  The compiler's hazard recognizer does not look at the
 // uses inside an inline-asm statement, nor at what the asm's last instruction needs from the code behind it, so the asm
 // strings carry them: five wait states before a store addressed through an SGPR base (a VALU write of that SGPR -- a spill
@@ -434,7 +436,7 @@ struct PersistParams {
     double *ovf_rec;
     int32_t pool_cap; // records the LDS pool of a workgroup holds (the host checked every workgroup's run against it)
     int32_t pad3;
-    // design variants (the VAR form of the load-case kernel and of k_edge_blocks; persist.hip, persist_variant_params): variant
+    // design variants (the VAR form of the load-case kernel and of k_edge_blocks; persist_kernel.h, persist_variant_operator): variant
     // blockIdx.y has its own coordinates, block values, overflow records and material constants.  xyP advances by N per
     // variant, the others by the extents below; var_mat: [variants][3] = c0, nu, h, read once per launch.  Appended: no
     // field of the single-case and load-case forms moved, and none of their instantiations reads these.
@@ -455,23 +457,19 @@ void stream_exchange_launch(double *buf, int32_t g_all, int32_t n_iface, int32_t
 int persist_tiles_per_wg(int32_t B); // tiles one workgroup keeps on chip (0: tile size not supported)
 // eb_mode: 0 triangle walk, 1 edge blocks (every row a fan of <= 6 blocks), 2 edge blocks with `pool` overflow records in LDS
 size_t persist_lds_bytes(int32_t B, int32_t cap, int32_t maxh, int eb_mode = 0, int32_t pool = 0, bool mg = false);
-// MG kernel when nranks > 1; eb_mode as above (the host decides from ring16's flags and the overflow limits)
-void persist_launch(const PersistParams &P, int32_t B, int32_t grid, int eb_mode, hipStream_t s);
-// Load cases: `cases` right-hand sides of one mesh side by side in ONE launch, `grid` workgroups each (grid * cases <= CUs: all
-// co-resident).  P points at case 0; case c's bP, x, qg, recg, sync, st follow at c times their single-case extent
-// (persist.hip, persist_case_params).  persist_cases_shape: the shape has a load-case instantiation (else: one case at a time).
-bool persist_cases_shape(int32_t B, int32_t grid, int32_t tiles_per_wg, int eb_mode);
-void persist_launch_cases(const PersistParams &P, int32_t B, int32_t grid, int32_t cases, int eb_mode, hipStream_t s);
-// Design variants: `variants` shapes / materials of one mesh side by side in ONE launch, laid out as the load cases are, plus the
-// per-variant operator data of PersistParams' var_* fields (persist.hip, persist_variant_params; persist_variants.o).  The
-// shapes are the load-case ones (persist_cases_shape).
-void persist_launch_variants(const PersistParams &P, int32_t B, int32_t grid, int32_t variants, int eb_mode, hipStream_t s);
+// Every launch of the on-chip kernel: `members` problems side by side (grid.y), `grid` workgroups each.  PERSIST_SINGLE: one
+// problem (members = 1), the MG kernel when nranks > 1; eb_mode as above (the host decides from ring16's flags and the overflow
+// limits).  PERSIST_CASES: right-hand sides of one mesh (grid * members <= CUs: all co-resident); P points at case 0, case c's
+// bP, x, qg, recg, sync, st follow at c times their single-case extent (persist_kernel.h, persist_case_params).
+// PERSIST_VARIANTS: shapes / materials of one mesh, laid out as the load cases are, plus the per-variant operator data of
+// PersistParams' var_* fields (persist_variant_operator).  The instantiation is persist_shape's (persist_shapes.h); false: that
+// shape has none and nothing was launched (the host asks persist_shape first: else one member at a time).
+bool persist_launch(const PersistParams &P, int32_t B, int32_t grid, int32_t members, PersistMembers m, int eb_mode, hipStream_t s);
 int persist_block_entries(); // block entries per node of that instantiation
 // ... and its blocks: 3 * persist_block_entries() doubles per node of the T * B padded nodes, into P.kblocks (host sets
 // kblocks / kb_stride before the call; eb_mode 2: row_info / ovf_off / ovf_rec as well)
-void edge_blocks_build(const PersistParams &P, int32_t B, double *kblocks, int eb_mode, hipStream_t s);
-// ... of `variants` variants in one launch (grid.y = variant): into P.kblocks (+ P.ovf_rec) at the var_* extents
-void edge_blocks_build_variants(const PersistParams &P, int32_t B, int eb_mode, int32_t variants, hipStream_t s);
+// variants >= 1: of so many variants in one launch (grid.y = variant), into P.kblocks (+ P.ovf_rec) at the var_* extents
+void edge_blocks_build(const PersistParams &P, int32_t B, double *kblocks, int eb_mode, int32_t variants, hipStream_t s);
 int persist_stamp_words();   // words per workgroup in PersistParams::stamps
 bool persist_stamps_built(); // the library was compiled with -DMAG_PERSIST_STAMPS
 void mark_published(const int32_t *halo_g, int64_t halo_total, uint8_t *maskP, hipStream_t s);
