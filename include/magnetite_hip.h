@@ -462,6 +462,48 @@ typedef struct mag_objective_result {
 int mag_run_objective(mag_ctx *ctx, int32_t set, const mag_objective *objective, int32_t with_adjoint);
 int mag_download_objective(mag_ctx *ctx, int32_t set, int32_t index, mag_objective_result *out);
 
+/* ---- stress recovery: the tensor per element, the nodal field and the ZZ error estimate of solved runs, cases and variants ---- */
+/* What a post-processor reads a part by, next to the reference-compatible scalar stress_out (which stays as it is): per solved
+ * member the stress tensor of every element, a continuous nodal field for plots and read-outs at a point, and the
+ * Zienkiewicz-Zhu estimate of the discretisation error -- whether the mesh that produced the stress can be trusted, and which
+ * elements to refine.  In the notation of the sensitivities (b, g, A2 = 2A with the SIGNED area, p_u, q_u, r_u):
+ *   (sx, sy, txy) = E / ((1 - nu^2) A2) (p_u + nu q_u, nu p_u + q_u, (1 - nu) / 2 r_u): sigma_e = D B u_e with the reference's D
+ *                 and B; B carries 1 / A2, so the tensor is the physical one for either orientation of an element;
+ *   vm            = sqrt(sx^2 - sx sy + sy^2 + 3 txy^2), MAG_OBJ_STRESS_PNORM's vm_e;
+ *   elem[e]       = (sx, sy, txy, vm)                                                                  ([E][4] values)
+ *   node[i]       = (sx*, sy*, txy*, vm(sigma*_i)) with the area-weighted average of the node's triangles
+ *                   sigma*_i = (sum_{e of i} |A_e| sigma_e) / (sum_{e of i} |A_e|), the sums in the order of the node's
+ *                   incidence list; caller numbering, nodes with prescribed displacements included, four zeros for a node
+ *                   that no element touches                                                            ([N][4] values)
+ *   eta2[e]       = |A_e| t / 12 (sum_k d_k^T C d_k + (sum_k d_k)^T C (sum_k d_k)),  d_k = sigma*_{n_k} - sigma_e for the three
+ *                   corners, C = D^-1: s^T C s = (sx^2 - 2 nu sx sy + sy^2 + 2 (1 + nu) txy^2) / E -- the exact integral over the
+ *                   triangle of (sigma* - sigma_e)^T C (sigma* - sigma_e) t with sigma* interpolated linearly and sigma_e
+ *                   constant: what an adaptive mesher consumes                                          (E values)
+ *   scalars[0]  eta^2 = sum of eta2[e]                        scalars[3]  the largest vm of the elements
+ *   scalars[1]  U^2 = sum of |A_e| t sigma_e^T C sigma_e      scalars[4]  the largest vm(sigma*_i) of the nodes
+ *               (= 2 |W| of the sensitivities)                 scalars[5..7]  0
+ *   scalars[2]  eta_rel = sqrt(eta^2 / (U^2 + eta^2)), 0 where both are 0
+ *
+ * mag_run_stress: set = enum mag_set.  Works on the results of the last completed mag_run / mag_run_cases / mag_run_variants,
+ *   solves nothing and alters no other result of the context -- primal results, statistics, sensitivities, adjoint and objective
+ *   results of every set stay bit for bit --, whether the members ran side by side or one after another.  Every sum has a fixed
+ *   order (no floating-point atomics): a repeat gives the same bits, and a member the same bits whatever launch it shares.  The
+ *   recovery is dropped where the set's sensitivities are: a new mag_upload, a new mag_set_* of the set, a new run of the set (any
+ *   set's run drops that of MAG_SET_RUN).
+ * mag_download_stress: member `index` of the set (0 for MAG_SET_RUN); NULL arrays are skipped, scalars are always filled.
+ * Errors, before any HIP call: MAG_ERR_BAD_ARGS for a set that is none of enum mag_set, a negative or too large index, a null
+ *   `out`, a context whose communicator has more than one rank; MAG_ERR_STATE for no completed run of the set and for
+ *   mag_download_stress before mag_run_stress of it. */
+typedef struct mag_stress_field {
+    double *elem_out;  /* [E][4], NULL: skipped */
+    double *node_out;  /* [N][4] */
+    double *eta2_out;  /* [E]    */
+    double scalars[8];
+    int32_t memory, reserved;
+} mag_stress_field;     /* 96 bytes */
+int mag_run_stress(mag_ctx *ctx, int32_t set);
+int mag_download_stress(mag_ctx *ctx, int32_t set, int32_t index, mag_stress_field *out);
+
 /* ---- pieces of the path, exposed for parity tests -------------------- */
 /* solver.rs:187-193 compute_element_area (pub; the mesher imports it, mesher.rs:9,523). Host-side. */
 double mag_compute_element_area(const double *xy, const int32_t *tri);

@@ -13,6 +13,7 @@
 #pragma once
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <functional>
 #include <optional>
@@ -72,6 +73,14 @@ struct Objective {
     std::vector<double> g, pxy, dxy;
     double J = 0, pJ_pE = 0, pJ_pnu = 0, pJ_pt = 0, dJ_dE = 0, dJ_dnu = 0, dJ_dt = 0;
     bool totals = false;
+};
+
+// What solver::stress_recovery returns per solved member: the outputs of mag_download_stress -- elem (E rows of sx, sy, txy, vm),
+// node (N rows of the averaged tensor and its vm, in the order of `nodes`), eta2 (E) -- and the scalars by name: eta and
+// energy_norm are the square roots of the library's eta^2 and U^2.
+struct StressField {
+    std::vector<double> elem, node, eta2;
+    double eta = 0, energy_norm = 0, eta_rel = 0, vm_max = 0, vm_node_max = 0;
 };
 
 // The objective of solver::objective (include/magnetite_hip.h, mag_objective): one row of weights (and of the target) for all
@@ -520,6 +529,41 @@ inline Result objective(const std::vector<Node> &nodes, const std::vector<Elemen
         s.dJ_dnu = d.scalars[5];
         s.dJ_dt = d.scalars[6];
         s.totals = d.scalars[7] != 0.0;
+    }
+    return std::nullopt;
+}
+
+// Stress recovery (mag_run_stress) of the part as it is -- shapes and materials both empty: one member -- or of its design
+// variants, as sensitivities() takes them: the problem(s) are solved, then per member the stress tensor and von Mises value of
+// every element, the area-weighted nodal field, the ZZ error indicator per element and the scalars of include/magnetite_hip.h by
+// name.
+inline Result stress_recovery(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                              const std::vector<std::vector<Vertex>> &shapes, const std::vector<ModelMetadata> &materials,
+                              std::vector<StressField> &out, const mag_options *options = nullptr)
+{
+    detail::SolvedMembers sm;
+    if (Result e = sm.solve(nodes, elements, model_metadata, shapes, materials, options, []() -> Result { return std::nullopt; })) return e;
+    mag_ctx *ctx = sm.ctx;
+    const std::int32_t set = sm.set;
+    const std::size_t V = sm.V, N = sm.N, E = sm.E;
+    if (mag_run_stress(ctx, set) != MAG_OK) return sm.fail();
+    out.assign(V, StressField{});
+    for (std::size_t v = 0; v < V; ++v) {
+        StressField &s = out[v];
+        s.elem.resize(4 * E);
+        s.node.resize(4 * N);
+        s.eta2.resize(E);
+        mag_stress_field d{};
+        d.elem_out = s.elem.data();
+        d.node_out = s.node.data();
+        d.eta2_out = s.eta2.data();
+        d.memory = MAG_MEM_HOST;
+        if (mag_download_stress(ctx, set, (std::int32_t)v, &d) != MAG_OK) return sm.fail();
+        s.eta = std::sqrt(d.scalars[0]);
+        s.energy_norm = std::sqrt(d.scalars[1]);
+        s.eta_rel = d.scalars[2];
+        s.vm_max = d.scalars[3];
+        s.vm_node_max = d.scalars[4];
     }
     return std::nullopt;
 }

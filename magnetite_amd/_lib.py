@@ -36,6 +36,7 @@ SYMBOLS = [
     "mag_run_sensitivities", "mag_download_sensitivity",
     "mag_run_adjoint", "mag_download_adjoint", "mag_get_adjoint_stats", "mag_get_adjoint_info",
     "mag_run_objective", "mag_download_objective",
+    "mag_run_stress", "mag_download_stress",
     "mag_comm_get_unique_id", "mag_comm_init_rccl", "mag_comm_query", "mag_comm_init_callback", "mag_comm_set_window", "mag_comm_inbox_create", "mag_comm_inbox_open",
 ]
 
@@ -93,6 +94,11 @@ class Objective(C.Structure):
 
 class ObjectiveResult(C.Structure):
     _fields_ = [("g_out", C.c_void_p), ("pxy_out", C.c_void_p), ("dxy_out", C.c_void_p), ("scalars", C.c_double * 8),
+                ("memory", C.c_int32), ("reserved", C.c_int32)]
+
+
+class StressField(C.Structure):
+    _fields_ = [("elem_out", C.c_void_p), ("node_out", C.c_void_p), ("eta2_out", C.c_void_p), ("scalars", C.c_double * 8),
                 ("memory", C.c_int32), ("reserved", C.c_int32)]
 
 
@@ -179,6 +185,9 @@ def lib():
     if hasattr(L, "mag_run_objective"):  # (likewise: scripts/objective_probe.py)
         L.mag_run_objective.argtypes = [vp, C.c_int32, C.POINTER(Objective), C.c_int32]
         L.mag_download_objective.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(ObjectiveResult)]
+    if hasattr(L, "mag_run_stress"):  # (likewise: scripts/stress_recovery_probe.py)
+        L.mag_run_stress.argtypes = [vp, C.c_int32]
+        L.mag_download_stress.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(StressField)]
     L.mag_compute_element_area.argtypes = [dp, ip]
     L.mag_compute_element_area.restype = C.c_double
     L.mag_compute_strain_displacement_matrix.argtypes = [dp, ip, C.c_double, dp]

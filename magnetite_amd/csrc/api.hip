@@ -25,6 +25,7 @@
 #include "primitives.h"
 #include "adjoint.h"
 #include "objective.h"
+#include "recover.h"
 #include "sens.h"
 
 using magk::CgState;
@@ -82,8 +83,8 @@ struct MemberSet {
 };
 
 // What a pass over the solved members of one set (enum mag_set) leaves -- mag_run_sensitivities, mag_run_adjoint (next to its
-// adjoint MemberSet: lambda = that set's u, the adjoint reactions its f, dJ/du its f_in), mag_run_objective: its rows member
-// after member on the device, the scalars on the host.  Dropped by a new mag_upload and by a new run of the set.
+// adjoint MemberSet: lambda = that set's u, the adjoint reactions its f, dJ/du its f_in), mag_run_objective, mag_run_stress: its
+// rows member after member on the device, the scalars on the host.  Dropped by a new mag_upload and by a new run of the set.
 struct DerivedSet {
     bool have = false;
     bool totals = false; // mag_run_objective with_adjoint: dxy and scalars 4..7 hold the total derivatives
@@ -91,11 +92,12 @@ struct DerivedSet {
     DevBuf energy;        // sensitivities [count][E]
     DevBuf dloads, delem; // adjoint [count][2N], [count][E]
     DevBuf g, pxy;        // objective [count][2N] each
-    DevBuf dxy;           // every pass [count][2N]
+    DevBuf selem, snode, seta2; // stress recovery [count][E][4], [count][N][4], [count][E]
+    DevBuf dxy;           // the three design passes [count][2N]
     DevBuf scalars;       // every pass [count][8]
     std::vector<double> scalars_h;
 };
-enum Pass { PASS_SENS, PASS_ADJOINT, PASS_OBJECTIVE, PASS_COUNT }; // the passes that leave a DerivedSet per set
+enum Pass { PASS_SENS, PASS_ADJOINT, PASS_OBJECTIVE, PASS_STRESS, PASS_COUNT }; // the passes that leave a DerivedSet per set
 
 // Run-time knobs (environment, read at every call: tests switch them between calls in one process).  None is needed in
 // production; each one either is set by a test or forces a path the library can take on its own.
@@ -3577,6 +3579,49 @@ int mag_download_objective(mag_ctx *ctx, int32_t set, int32_t index, mag_objecti
         return fail(ctx, MAG_ERR_STATE, "mag_download_objective: dxy_out needs mag_run_objective with with_adjoint != 0");
     const size_t vb = 16 * (size_t)ctx->N;
     return download_rows(ctx, *have, index, o->memory, {{o->g_out, have->g, vb}, {o->pxy_out, have->pxy, vb}, {o->dxy_out, have->dxy, vb}},
+                         o->scalars);
+}
+
+// ---- stress recovery of the solved members of a set (recover.hip): the fourth pass, chunked as mag_run_sensitivities is ----
+int mag_run_stress(mag_ctx *ctx, int32_t set)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    int32_t M = 0;
+    if (int rc = sens_refused(ctx, set, "mag_run_stress", &M)) return rc;
+    if (int rc = enter(ctx)) return rc;
+    const int64_t N = ctx->N, E = ctx->E;
+    const size_t nb = 32 * (size_t)N, rb = 32 * (size_t)E, eb = 8 * (size_t)E, pb = 8 * 4 * (size_t)magk::kSensBlocks;
+    DerivedSet &out = ctx->derived[PASS_STRESS][set];
+    out.have = false;
+    magk::SensMesh mesh;
+    if (int rc = sens_mesh(ctx, mesh)) return rc;
+    MemberView mv;
+    if (int rc = member_view(ctx, set, mv)) return rc;
+    const auto launch = [&](int32_t c0, int32_t count) {
+        magk::StressBatch sb = {};
+        mv.head(sb, c0, count);
+        sb.elem = out.selem.as<double>() + 4 * (size_t)E * c0;
+        sb.node = out.snode.as<double>() + 4 * (size_t)N * c0;
+        sb.eta2 = out.seta2.as<double>() + (size_t)E * c0;
+        sb.scalars = out.scalars.as<double>() + 8 * (size_t)c0;
+        sb.uterm = ctx->sens_nuterm.as<double>();
+        sb.partials = ctx->sens_part.as<double>();
+        magk::stress_recovery(mesh, sb, ctx->stream);
+        return (int)MAG_OK;
+    };
+    // (the scratch of one member: an energy term per element, the partial sums and maxima -- the sensitivities' buffers)
+    if (int rc = run_chunks(ctx, out, M, eb + pb, {ROWS(out.selem, rb), ROWS(out.snode, nb), ROWS(out.seta2, eb)},
+                            {ROWS(ctx->sens_nuterm, eb), ROWS(ctx->sens_part, pb)}, launch))
+        return rc;
+    return hold_derived(ctx, out, M);
+}
+
+int mag_download_stress(mag_ctx *ctx, int32_t set, int32_t index, mag_stress_field *o)
+{
+    const DerivedSet *have = nullptr;
+    if (int rc = download_refused(ctx, PASS_STRESS, set, index, o, "stress field", "mag_download_stress", "mag_run_stress", &have)) return rc;
+    const size_t rb = 32 * (size_t)ctx->E, nb = 32 * (size_t)ctx->N, eb = 8 * (size_t)ctx->E;
+    return download_rows(ctx, *have, index, o->memory, {{o->elem_out, have->selem, rb}, {o->node_out, have->snode, nb}, {o->eta2_out, have->seta2, eb}},
                          o->scalars);
 }
 

@@ -484,6 +484,31 @@ class Context:
         self.run_objective(kind, set, weights, target, p, scale, adjoint, allow_not_converged)
         return [self.download_objective(set, i, total=adjoint) for i in range(self._members(set))]
 
+    # -- stress recovery: the tensor per element, the nodal field and the ZZ error estimate of the solved members of a set ---
+    STRESS_SCALARS = ("eta", "energy_norm", "eta_rel", "vm_max", "vm_node_max")
+
+    def run_stress(self, set="run"):
+        """mag_run_stress on the last completed run() / run_cases() / run_variants(): solves nothing."""
+        self._check(self._L.mag_run_stress(self._h, self._sensitivity_set(set)))
+
+    def download_stress(self, set, i):
+        """dict(elem (E, 4): sx, sy, txy, vm; node (N, 4): the averaged tensor and its vm; eta2 (E); eta, energy_norm: the
+        square roots of the library's eta^2 and U^2; eta_rel, vm_max, vm_node_max) of member i of the set."""
+        which = self._sensitivity_set(set)
+        elem, node, eta2 = np.empty((self.E, 4)), np.empty((self.N, 4)), np.empty(self.E)
+        o = _lib.StressField(elem.ctypes.data, node.ctypes.data, eta2.ctypes.data, (C.c_double * 8)(), MAG_MEM_HOST, 0)
+        self._check(self._L.mag_download_stress(self._h, which, i, C.byref(o)))
+        sc = list(o.scalars)
+        return dict(elem=elem, node=node, eta2=eta2, **dict(zip(self.STRESS_SCALARS, [np.sqrt(sc[0]), np.sqrt(sc[1])] + sc[2:5])))
+
+    def stress_recovery(self, set="run"):
+        """The stress field of every solved member of the set ("run": the one of run(); "cases"; "variants"): a list of dicts
+        as download_stress returns them -- the tensor and von Mises value per element, the area-weighted nodal field, the ZZ
+        error indicator eta2 per element with its norm eta, the energy norm of the solution and their ratio eta_rel
+        (include/magnetite_hip.h)."""
+        self.run_stress(set)
+        return [self.download_stress(set, i) for i in range(self._members(set))]
+
     # -- pieces, for parity tests ----------------------------------------------
     def element_stiffness(self):
         ke = np.empty(36 * self.E)

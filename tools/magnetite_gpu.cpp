@@ -7,8 +7,12 @@
 //   * MSH-4 ASCII           mesher.rs:536-704   + check_ccw with its `< 1.0` quirk (mesher.rs:522-526)
 //   * nodes.csv/elements.csv post_processor.rs:18-83, floats as Rust's `{}` prints them
 // Usage: magnetite_gpu <input.json> <mesh.msh> [--nodes nodes.csv] [--elements elements.csv] [--dry-run] [--rel TOL]
+//                      [--stress-recovery]
 //   --dry-run  stop before the solver and print what was parsed (no GPU needed)
 //   --rel TOL  stop CG on relative residual TOL instead of the reference's absolute 1e-4
+//   --stress-recovery  also write nodes_stress.csv (id,sx,sy,txy,vm) and elements_stress.csv (id,sx,sy,txy,vm,eta2) next to the
+//              two files -- solver::stress_recovery: the tensor per element, the nodal field, the ZZ error indicator -- and
+//              print eta_rel; without it nothing changes
 #include <charconv>
 #include <cstdio>
 #include <cstdlib>
@@ -316,16 +320,45 @@ void csv_output(const std::vector<Element> &elements, const std::vector<Node> &n
     std::printf("info: wrote output to %s and %s\n", nodes_output.c_str(), elements_output.c_str());
 }
 
+// "dir/nodes.csv" -> "dir/nodes_stress.csv"
+std::string stress_name(const std::string &path)
+{
+    const size_t slash = path.find_last_of('/'), dot = path.find_last_of('.');
+    const bool ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
+    return ext ? path.substr(0, dot) + "_stress" + path.substr(dot) : path + "_stress";
+}
+
+// the rows of solver::stress_recovery, floats as csv_output prints them
+void stress_output(const StressField &s, const std::string &nodes_output, const std::string &elements_output)
+{
+    std::FILE *nf = std::fopen(nodes_output.c_str(), "w");
+    if (!nf) die({MagnetiteError::Solver, "Failed to create nodes_stress.csv: " + nodes_output});
+    std::FILE *ef = std::fopen(elements_output.c_str(), "w");
+    if (!ef) die({MagnetiteError::Solver, "Failed to create elements_stress.csv: " + elements_output});
+    std::fputs("id,sx,sy,txy,vm\n", nf);
+    for (size_t i = 0; 4 * i < s.node.size(); ++i)
+        std::fprintf(nf, "%zu,%s,%s,%s,%s\n", i, rust_display(s.node[4 * i]).c_str(), rust_display(s.node[4 * i + 1]).c_str(),
+                     rust_display(s.node[4 * i + 2]).c_str(), rust_display(s.node[4 * i + 3]).c_str());
+    std::fputs("id,sx,sy,txy,vm,eta2\n", ef);
+    for (size_t e = 0; e < s.eta2.size(); ++e)
+        std::fprintf(ef, "%zu,%s,%s,%s,%s,%s\n", e, rust_display(s.elem[4 * e]).c_str(), rust_display(s.elem[4 * e + 1]).c_str(),
+                     rust_display(s.elem[4 * e + 2]).c_str(), rust_display(s.elem[4 * e + 3]).c_str(), rust_display(s.eta2[e]).c_str());
+    std::fclose(nf);
+    std::fclose(ef);
+    std::printf("info: wrote stress recovery to %s and %s\n", nodes_output.c_str(), elements_output.c_str());
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
 {
     std::string input, mesh, nodes_out = "nodes.csv", elements_out = "elements.csv";
-    bool dry = false;
+    bool dry = false, recover = false;
     double rel = 0.0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--dry-run") dry = true;
+        else if (a == "--stress-recovery") recover = true;
         else if (a == "--nodes" && i + 1 < argc) nodes_out = argv[++i];
         else if (a == "--elements" && i + 1 < argc) elements_out = argv[++i];
         else if (a == "--rel" && i + 1 < argc) rel = std::atof(argv[++i]);
@@ -334,7 +367,7 @@ int main(int argc, char **argv)
         else die({MagnetiteError::Input, "Unrecognized argument " + a});
     }
     if (input.empty() || mesh.empty()) {
-        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL]\n");
+        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery]\n");
         return 2;
     }
     // mesher::run (mesher.rs:939-974) minus geometry parsing and the gmsh subprocess
@@ -378,8 +411,18 @@ int main(int argc, char **argv)
         opt.stop_mode = MAG_STOP_REL;
         opt.tol = rel;
     }
+    const std::vector<Node> posed = recover ? nodes : std::vector<Node>();  // (run() fills every value in)
     if (Result err = solver::run(nodes, elements, meta, &opt)) die(*err);
     // post_processor::csv_output (main.rs:69); the matplotlib plot (main.rs:72) is not part of this tool
     csv_output(elements, nodes, nodes_out, elements_out);
+    if (recover) {
+        opt.verbose = 0;
+        std::vector<StressField> fields;
+        if (Result err = solver::stress_recovery(posed, elements, meta, {}, {}, fields, &opt)) die(*err);
+        stress_output(fields[0], stress_name(nodes_out), stress_name(elements_out));
+        std::printf("info: stress recovery eta_rel %s (eta %s, energy norm %s), largest von Mises stress %s in an element, %s at a node\n",
+                    rust_display(fields[0].eta_rel).c_str(), rust_display(fields[0].eta).c_str(), rust_display(fields[0].energy_norm).c_str(),
+                    rust_display(fields[0].vm_max).c_str(), rust_display(fields[0].vm_node_max).c_str());
+    }
     return 0;
 }
