@@ -504,6 +504,65 @@ typedef struct mag_stress_field {
 int mag_run_stress(mag_ctx *ctx, int32_t set);
 int mag_download_stress(mag_ctx *ctx, int32_t set, int32_t index, mag_stress_field *out);
 
+/* ---- modal analysis: the lowest natural frequencies and mode shapes of the uploaded part -------------------
+ * mag_run_modal: the `modes` lowest pairs of  K_FF phi_F = lambda M_FF phi_F,  phi_P = 0,  by subspace iteration on the device.
+ *   Stiffness and supports.  K is the reference's stiffness of the uploaded mesh and material (solver.rs:263-331).  F is the set
+ *     of DOFs with u_known == 0, P those with u_known == 1; prescribed DOFs are SUPPORTS: the uploaded u_in / f_in values play no
+ *     role.
+ *   Mass.  With density rho, m_e = rho * thickness * |A_e|.  Consistent (default): per direction M_e = m_e / 12 [[2,1,1],[1,2,1],
+ *     [1,1,2]] on the element's three nodes; lumped (lumped != 0): m_e / 3 on each corner's diagonal.
+ *   Orientation.  The reference's mesher guarantees counter-clockwise elements (check_ccw) and its K_e carries the signed area: a
+ *     clockwise element makes K indefinite and inverse iteration meaningless.  A mesh with an element of signed area <= 0 is
+ *     refused with MAG_ERR_BAD_ARGS, the first such element named in mag_last_error.
+ *   Results, for modes = p:  lambda[k] ascending in (rad/s)^2;  frequency[k] = sqrt(lambda[k]) / (2 pi);  shape[k] (2N, caller
+ *     numbering, 0 on P) normalised so that phi_k^T M phi_l = delta_kl, its entry of largest magnitude positive (on a tie the first
+ *     in caller order);  residual[k] = |K_FF phi - lambda M_FF phi| / |lambda M_FF phi| from the pass's own quantities (below).
+ *   A supported part is required: where too few supports leave a rigid-body motion free K_FF is singular, the inner CG breaks
+ *     down or stalls and the call returns that status (MAG_ERR_NOT_CONVERGED).  There is no shift.
+ * Algorithm: subspace iteration with q vectors, q = subspace or min(2p, p + 8) when 0;  p >= 1, p <= q <= 32, q <= n_free.
+ *   1. q deterministic start vectors: vector j is the (j / 2)-th monomial xi^a eta^b (by total degree) of the coordinates
+ *      normalised to the bounding box and shifted by 1/2, in direction x (j even) or y (j odd), zero on P.  Y = M X.
+ *   2. Each outer step: K_FF Z_j = Y_j for all q columns as ONE member set (u_in = 0, f_in = Y_j) through the driver of the load
+ *      cases -- side by side on the chip, floor(CUs / G) per launch, where load cases run so, otherwise one after another;
+ *      W = M Z;  A = Z^T Y (= Z^T K Z) and B = Z^T W, symmetrised;  on the host the pairs of (A, B), ascending, Q^T B Q = I;
+ *      X = Z Q, Y = W Q (K X = Y_old Q to the accuracy of the inner solves: no further operator application);
+ *      residual[k] from Y_old Q e_k - lambda_k Y_new e_k.
+ *   3. Stop when the largest relative change of the first p eigenvalues is <= tol, or after max_outer steps: reaching the cap is
+ *      no error (converged = 0, the last iterate is returned, as with the CG's iteration cap).
+ *   The inner solves run under MAG_STOP_REL with cg_tol whatever the context's stop rule is (its absolute rules mean nothing for
+ *   right-hand sides of the size of a mass); the context's options are as they were afterwards.
+ * mag_run_modal needs an uploaded problem, no run.  It alters no other result of the context: mag_download, mag_get_stats,
+ *   mag_get_history, every set's results and every derived pass stay bit for bit.  Every sum has a fixed order: a repeat gives
+ *   the same bits.  The modal results depend on the upload only: a new mag_upload drops them, a new mag_run_modal replaces them.
+ * Errors, before any HIP call: MAG_ERR_BAD_ARGS for a null pointer, modes < 1, subspace not 0 and outside [modes, 32] (or the
+ *   default above 32), max_outer < 0, a density that is not positive and finite, a tol or cg_tol that is negative or not finite,
+ *   an index out of range, a communicator of more than one rank; MAG_ERR_STATE for no upload and for mag_download_modal /
+ *   mag_get_modal_info / mag_get_modal_stats before a completed mag_run_modal.  subspace > n_free: MAG_ERR_BAD_ARGS once the
+ *   ordering phase has counted the free DOFs. */
+typedef struct mag_modal_options {
+    int32_t modes;      /* p >= 1 */
+    int32_t subspace;   /* q, 0: min(2p, p + 8); p <= q <= 32 */
+    int32_t max_outer;  /* 0: 50 */
+    int32_t lumped;     /* 0 consistent mass, != 0 lumped */
+    double density;     /* > 0, finite */
+    double tol;         /* relative change of the first p eigenvalues; 0: 1e-10 */
+    double cg_tol;      /* MAG_STOP_REL tolerance of the inner solves; 0: 1e-10 */
+} mag_modal_options;    /* 40 bytes */
+typedef struct mag_modal_result {
+    double *lambda_out;    /* p, NULL: skipped */
+    double *frequency_out; /* p */
+    double *residual_out;  /* p */
+    double *shapes_out;    /* [p][2N] */
+    int32_t memory, reserved;
+} mag_modal_result;        /* 40 bytes */
+int mag_run_modal(mag_ctx *ctx, const mag_modal_options *opt);
+int mag_download_modal(mag_ctx *ctx, mag_modal_result *out);
+/* info[0] modes, [1] subspace, [2] outer steps, [3] converged, [4] vectors per on-chip launch (0: one after another),
+ * [5] on-chip launches of all steps, [6] vectors redone alone, [7] 0 */
+int mag_get_modal_info(const mag_ctx *ctx, int32_t info[8]);
+/* statistics of inner solve j of the LAST outer step, as mag_get_case_stats */
+int mag_get_modal_stats(const mag_ctx *ctx, int32_t j, mag_stats *stats);
+
 /* ---- pieces of the path, exposed for parity tests -------------------- */
 /* solver.rs:187-193 compute_element_area (pub; the mesher imports it, mesher.rs:9,523). Host-side. */
 double mag_compute_element_area(const double *xy, const int32_t *tri);
@@ -527,6 +586,10 @@ int mag_reduce_system(mag_ctx *ctx, int64_t *n_free, int64_t *nnz_ff, int32_t *r
  * (x, y: host, 2N, caller's DOF numbering).  masked != 0 applies M K M with M
  * zeroing prescribed-displacement DOFs (that is K_ff embedded in full length). */
 int mag_apply_operator(mag_ctx *ctx, const double *x, double *y, int32_t masked);
+/* y = M x with the mass operator of mag_run_modal (density, lumped as there) on the uploaded mesh (x, y: host, 2N, caller's
+ * DOF numbering); masked != 0 applies P M P with P zeroing prescribed-displacement DOFs, as mag_apply_operator does (M_FF
+ * embedded in full length).  Alters no result of the context. */
+int mag_apply_mass(mag_ctx *ctx, double density, int32_t lumped, const double *x, double *y, int32_t masked);
 /* Bench helper: `reps` back-to-back launches of the CG iteration kernel (cg_variant 1: the fused
  * iteration kernel; 0: the operator kernel of the two-launch iteration) on the context's stream
  * between two HIP events; *ms_per_launch = elapsed / reps.  Needs an uploaded problem, not a solve: straight after

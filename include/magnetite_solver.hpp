@@ -83,6 +83,20 @@ struct StressField {
     double eta = 0, energy_norm = 0, eta_rel = 0, vm_max = 0, vm_node_max = 0;
 };
 
+// What solver::modal returns: the outputs of mag_download_modal -- lambda ((rad/s)^2, ascending), frequency (Hz), residual, shapes
+// (modes rows of 2N values in the order of `nodes`, mass-normalised, 0 on prescribed DOFs) -- and mag_get_modal_info's words by name.
+struct Modes {
+    std::vector<double> lambda, frequency, residual, shapes;
+    std::int32_t modes = 0, subspace = 0, outer = 0, converged = 0, vectors_per_launch = 0, launches = 0, redone = 0;
+};
+
+// The options of solver::modal (include/magnetite_hip.h, mag_modal_options); 0: the library's default.
+struct ModalSpec {
+    std::int32_t modes = 6, subspace = 0, max_outer = 0;
+    bool lumped = false;
+    double density = 0.0, tol = 0.0, cg_tol = 0.0;
+};
+
 // The objective of solver::objective (include/magnetite_hip.h, mag_objective): one row of weights (and of the target) for all
 // members -- 2N values for MAG_OBJ_DISP_LSQ, E values or none for MAG_OBJ_STRESS_PNORM.
 struct ObjectiveSpec {
@@ -565,6 +579,57 @@ inline Result stress_recovery(const std::vector<Node> &nodes, const std::vector<
         s.vm_max = d.scalars[3];
         s.vm_node_max = d.scalars[4];
     }
+    return std::nullopt;
+}
+
+// Modal analysis (mag_run_modal) of the part: the spec.modes lowest natural frequencies and mode shapes of K_FF phi = lambda M_FF phi
+// with the density of spec (the model has none).  The DOFs of `nodes` with a displacement are supports whatever its value, the
+// forces play no role; nothing is solved for them.  Reaching the cap of outer steps is no error: out.converged == 0.
+inline Result modal(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                    const ModalSpec &spec, Modes &out, const mag_options *options = nullptr)
+{
+    const std::size_t N = nodes.size();
+    std::vector<double> xy, u_in(2 * N), f_in(2 * N);
+    std::vector<std::uint8_t> u_known;
+    std::vector<std::int32_t> conn;
+    if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
+    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
+    mag_ctx *ctx = mag_create(options);
+    if (!ctx) return detail::solver_error("mag_create failed");
+    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
+    if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    mag_modal_options o{};
+    o.modes = spec.modes;
+    o.subspace = spec.subspace;
+    o.max_outer = spec.max_outer;
+    o.lumped = spec.lumped ? 1 : 0;
+    o.density = spec.density;
+    o.tol = spec.tol;
+    o.cg_tol = spec.cg_tol;
+    if (mag_run_modal(ctx, &o) != MAG_OK) return detail::fail_and_destroy(ctx);
+    std::int32_t info[8] = {};
+    if (mag_get_modal_info(ctx, info) != MAG_OK) return detail::fail_and_destroy(ctx);
+    const std::size_t P = (std::size_t)info[0];
+    out = Modes{};
+    out.lambda.resize(P);
+    out.frequency.resize(P);
+    out.residual.resize(P);
+    out.shapes.resize(P * 2 * N);
+    mag_modal_result d{};
+    d.lambda_out = out.lambda.data();
+    d.frequency_out = out.frequency.data();
+    d.residual_out = out.residual.data();
+    d.shapes_out = out.shapes.data();
+    d.memory = MAG_MEM_HOST;
+    if (mag_download_modal(ctx, &d) != MAG_OK) return detail::fail_and_destroy(ctx);
+    out.modes = info[0];
+    out.subspace = info[1];
+    out.outer = info[2];
+    out.converged = info[3];
+    out.vectors_per_launch = info[4];
+    out.launches = info[5];
+    out.redone = info[6];
+    mag_destroy(ctx);
     return std::nullopt;
 }
 

@@ -37,6 +37,7 @@ SYMBOLS = [
     "mag_run_adjoint", "mag_download_adjoint", "mag_get_adjoint_stats", "mag_get_adjoint_info",
     "mag_run_objective", "mag_download_objective",
     "mag_run_stress", "mag_download_stress",
+    "mag_run_modal", "mag_download_modal", "mag_get_modal_info", "mag_get_modal_stats", "mag_apply_mass",
     "mag_comm_get_unique_id", "mag_comm_init_rccl", "mag_comm_query", "mag_comm_init_callback", "mag_comm_set_window", "mag_comm_inbox_create", "mag_comm_inbox_open",
 ]
 
@@ -99,6 +100,16 @@ class ObjectiveResult(C.Structure):
 
 class StressField(C.Structure):
     _fields_ = [("elem_out", C.c_void_p), ("node_out", C.c_void_p), ("eta2_out", C.c_void_p), ("scalars", C.c_double * 8),
+                ("memory", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ModalOptions(C.Structure):
+    _fields_ = [("modes", C.c_int32), ("subspace", C.c_int32), ("max_outer", C.c_int32), ("lumped", C.c_int32),
+                ("density", C.c_double), ("tol", C.c_double), ("cg_tol", C.c_double)]
+
+
+class ModalResult(C.Structure):
+    _fields_ = [("lambda_out", C.c_void_p), ("frequency_out", C.c_void_p), ("residual_out", C.c_void_p), ("shapes_out", C.c_void_p),
                 ("memory", C.c_int32), ("reserved", C.c_int32)]
 
 
@@ -188,6 +199,12 @@ def lib():
     if hasattr(L, "mag_run_stress"):  # (likewise: scripts/stress_recovery_probe.py)
         L.mag_run_stress.argtypes = [vp, C.c_int32]
         L.mag_download_stress.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(StressField)]
+    if hasattr(L, "mag_run_modal"):  # (likewise: scripts/modal_probe.py)
+        L.mag_run_modal.argtypes = [vp, C.POINTER(ModalOptions)]
+        L.mag_download_modal.argtypes = [vp, C.POINTER(ModalResult)]
+        L.mag_get_modal_info.argtypes = [vp, ip]
+        L.mag_get_modal_stats.argtypes = [vp, C.c_int32, C.POINTER(Stats)]
+        L.mag_apply_mass.argtypes = [vp, C.c_double, C.c_int32, dp, dp, C.c_int32]
     L.mag_compute_element_area.argtypes = [dp, ip]
     L.mag_compute_element_area.restype = C.c_double
     L.mag_compute_strain_displacement_matrix.argtypes = [dp, ip, C.c_double, dp]

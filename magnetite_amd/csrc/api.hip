@@ -24,6 +24,8 @@
 #include "magnetite_hip.h"
 #include "primitives.h"
 #include "adjoint.h"
+#include "modal.h"
+#include "modal_host.h"
 #include "objective.h"
 #include "recover.h"
 #include "sens.h"
@@ -281,6 +283,16 @@ struct mag_ctx {
     // objectives of the same three sets (mag_run_objective); the caller's weights and targets, and the summands, per-element
     // factors and member factors of ONE chunk of members (the nu terms and partial sums are the sensitivities')
     DevBuf obj_w, obj_target, obj_terms, obj_helem, obj_factor;
+
+    // modal analysis (mag_run_modal): the q vectors of the subspace as one more member set -- u_in = 0, f_in = Y = M X, solved as
+    // load cases are and, like an adjoint set, dropping nothing; the rotated vectors X (the modes, at the end), W = M Z, the
+    // rotation's second Y, the residual vectors, the Gram partials, and Q, lambda, the Gram matrices and norms in modal_small.
+    // The results hang on the upload only: a new mag_upload drops them, a new mag_run_modal replaces them
+    MemberSet modal{"mode vector", "mag_run_modal", MAG_SET_CASES, true};
+    DevBuf modal_x, modal_w, modal_y2, modal_r, modal_part, modal_small, modal_bad;
+    bool modal_have = false;
+    int32_t modal_info[8] = {};
+    std::vector<double> modal_lambda, modal_residual;
 
     magc::Comm comm;
 };
@@ -2253,6 +2265,8 @@ int mag_upload(mag_ctx *ctx, const mag_problem *p)
     ctx->sens_tab_ready = false;
     ctx->cases.reset();
     ctx->variants.reset();
+    ctx->modal.reset();
+    ctx->modal_have = false;
     for (int32_t slot = MAG_SET_RUN; slot <= MAG_SET_VARIANTS; ++slot) drop_derived(ctx, slot);
     return MAG_OK;
 }
@@ -3623,6 +3637,273 @@ int mag_download_stress(mag_ctx *ctx, int32_t set, int32_t index, mag_stress_fie
     const size_t rb = 32 * (size_t)ctx->E, nb = 32 * (size_t)ctx->N, eb = 8 * (size_t)ctx->E;
     return download_rows(ctx, *have, index, o->memory, {{o->elem_out, have->selem, rb}, {o->node_out, have->snode, nb}, {o->eta2_out, have->seta2, eb}},
                          o->scalars);
+}
+
+// ---- modal analysis (modal.hip, modal_host.h): subspace iteration for the lowest pairs of K_FF phi = lambda M_FF phi, the inner
+// solves through the member-set driver as one more set, the Rayleigh-Ritz step on the host ----
+namespace {
+
+// The inner solves of mag_run_modal run under MAG_STOP_REL with cg_tol, silently: the context's stop rule, tolerance and
+// verbosity (read at every solve) are swapped here and come back on every exit path; the history is KeptRun's.
+struct ModalStopRule {
+    mag_ctx *ctx;
+    const int32_t stop_mode, verbose;
+    const double tol;
+    ModalStopRule(mag_ctx *c, double cg_tol) : ctx(c), stop_mode(c->opt.stop_mode), verbose(c->opt.verbose), tol(c->opt.tol)
+    {
+        ctx->opt.stop_mode = MAG_STOP_REL;
+        ctx->opt.tol = cg_tol;
+        ctx->opt.verbose = 0;
+    }
+    ~ModalStopRule()
+    {
+        ctx->opt.stop_mode = stop_mode;
+        ctx->opt.tol = tol;
+        ctx->opt.verbose = verbose;
+    }
+};
+
+// the checks of the mass operator's arguments (mag_run_modal, mag_apply_mass), before any HIP call
+int mass_refused(mag_ctx *ctx, const char *fn, double density)
+{
+    if (!(density > 0.0) || !std::isfinite(density)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: density %g is not positive and finite", fn, density);
+    if (ctx->comm.nranks > 1)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "modal analysis runs on one GPU: this context has a communicator of %d ranks", ctx->comm.nranks);
+    if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "%s before mag_upload", fn);
+    return MAG_OK;
+}
+
+// `count` vectors x on the uploaded mesh as the mass pass takes them (one mesh, one material, many vectors)
+int mass_batch(mag_ctx *ctx, double density, int32_t lumped, int32_t masked, int32_t count, const double *x, double *y, magk::MassBatch &mb)
+{
+    MemberView mv;
+    if (int rc = member_view(ctx, MAG_SET_RUN, mv)) return rc; // (the uploaded material, on the device)
+    mb = {};
+    mb.count = count;
+    mb.mat = mv.mat;
+    mb.mat_stride = 0;
+    mb.xy = ctx->xy.as<double>();
+    mb.xy_stride = 0;
+    mb.u = x;
+    mb.y = y;
+    mb.density = density;
+    mb.lumped = lumped ? 1 : 0;
+    mb.masked = masked ? 1 : 0;
+    return MAG_OK;
+}
+
+} // namespace
+
+int mag_run_modal(mag_ctx *ctx, const mag_modal_options *mo)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!mo) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_modal: null options");
+    const int32_t p = mo->modes;
+    if (p < 1) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_modal: modes = %d: at least one mode", (int)p);
+    const int32_t q = mo->subspace != 0 ? mo->subspace : std::min(2 * p, p + 8);
+    if (q < p || q > magk::kModalMaxQ)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_modal: subspace = %d outside [modes = %d, %d]", (int)q, (int)p, magk::kModalMaxQ);
+    if (mo->max_outer < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_modal: max_outer = %d is negative", (int)mo->max_outer);
+    if (!(mo->tol >= 0.0) || !std::isfinite(mo->tol) || !(mo->cg_tol >= 0.0) || !std::isfinite(mo->cg_tol))
+        return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_modal: tol %g / cg_tol %g is negative or not finite", mo->tol, mo->cg_tol);
+    if (int rc = mass_refused(ctx, "mag_run_modal", mo->density)) return rc;
+    if (int rc = enter(ctx)) return rc;
+    const int32_t max_outer = mo->max_outer != 0 ? mo->max_outer : 50;
+    const double tol = mo->tol != 0.0 ? mo->tol : 1e-10, cg_tol = mo->cg_tol != 0.0 ? mo->cg_tol : 1e-10;
+    hipStream_t s = ctx->stream;
+    const int64_t N = ctx->N;
+    const size_t vb = 16 * (size_t)N;
+    constexpr int MQ = magk::kModalMaxQ;
+    ctx->modal_have = false;
+    MemberSet &set = ctx->modal;
+    set.have = set.have_run = false;
+
+    if (int rc = ensure_full_order(ctx)) return rc; // (validates conn, counts the free DOFs, leaves the bounding box)
+    if (q > ctx->nf)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_modal: subspace = %d exceeds the %lld free DOFs", (int)q, (long long)ctx->nf);
+    HIPCHK(ctx->modal_bad.reserve(8));
+    unsigned long long bad = ~0ull;
+    magk::orientation(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), N, ctx->E, ctx->modal_bad.as<unsigned long long>(), s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&bad, ctx->modal_bad.p, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (bad != ~0ull)
+        return fail(ctx, MAG_ERR_BAD_ARGS,
+                    "mag_run_modal: element %lld has a signed area <= 0 (the stiffness carries the signed area: modal analysis needs "
+                    "counter-clockwise elements)",
+                    (long long)bad);
+
+    // Q [MQ][MQ], lambda [MQ], then A and B [q][q] each, then the norms [p][2]
+    const size_t small_doubles = MQ * MQ + MQ + 2 * (size_t)MQ * MQ + 2 * MQ;
+    HIPCHK(set.uin.reserve(vb * q));
+    HIPCHK(set.fin.reserve(vb * q));
+    HIPCHK(ctx->modal_x.reserve(vb * q));
+    HIPCHK(ctx->modal_w.reserve(vb * q));
+    HIPCHK(ctx->modal_y2.reserve(vb * q));
+    HIPCHK(ctx->modal_r.reserve(vb * p));
+    HIPCHK(ctx->modal_part.reserve(8 * 2 * magk::kModalGramCols * (size_t)magk::kSensBlocks * (size_t)magk::gram_rows(q)));
+    HIPCHK(ctx->modal_small.reserve(8 * small_doubles));
+    double *d_qs = ctx->modal_small.as<double>(), *d_gram = d_qs + MQ * MQ + MQ, *d_norms = d_gram + 2 * MQ * MQ;
+    double *X = ctx->modal_x.as<double>(), *Y = set.fin.as<double>(), *W = ctx->modal_w.as<double>(), *Y2 = ctx->modal_y2.as<double>();
+
+    // ---- 1. the start vectors and Y = M X
+    magk::SensMesh mesh;
+    magk::MassBatch mb;
+    if (int rc = sens_mesh(ctx, mesh)) return rc;
+    HIPCHK(hipMemsetAsync(set.uin.p, 0, vb * q, s));
+    magk::start_vectors(ctx->xy.as<double>(), ctx->uknown.as<uint8_t>(), ctx->small.as<double>() + 4 * 256, N, q, X, s);
+    if (int rc = mass_batch(ctx, mo->density, mo->lumped, 1, q, X, Y, mb)) return rc;
+    magk::mass_apply(mesh, mb, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    set.count = q;
+    set.have = true;
+
+    // ---- 2. the outer steps
+    int32_t *info = ctx->modal_info;
+    for (int k = 0; k < 8; ++k) info[k] = 0;
+    info[0] = p;
+    info[1] = q;
+    std::vector<double> lambda((size_t)q, 0.0), prev, h_gram(2 * (size_t)q * q), A((size_t)q * q), B((size_t)q * q), Qm((size_t)q * q), h_qs(MQ * MQ + MQ);
+    bool converged = false;
+    for (int32_t step = 0; step < max_outer; ++step) {
+        int status = MAG_OK;
+        {
+            KeptRun kept(ctx);
+            if (int rc = kept.keep()) return rc;
+            ModalStopRule rule(ctx, cg_tol);
+            status = run_case_set(ctx, set);
+        }
+        info[2] = step + 1;
+        info[4] = set.info[1];
+        info[5] += set.info[2];
+        info[6] += set.info[3];
+        if (status != MAG_OK) return status;
+        for (int32_t j = 0; j < q; ++j)
+            if (!set.stats[(size_t)j].converged)
+                return fail(ctx, MAG_ERR_NOT_CONVERGED,
+                            "mag_run_modal: outer step %d, vector %d: the inner solve stopped at the iteration cap after %lld iterations "
+                            "(a part without enough supports has a singular K_FF)",
+                            (int)step + 1, (int)j, (long long)set.stats[(size_t)j].iterations);
+        const double *Z = set.u.as<double>();
+        if (int rc = sens_mesh(ctx, mesh)) return rc; // (the run has redone the ordering: the tile-local table with it)
+        if (int rc = mass_batch(ctx, mo->density, mo->lumped, 1, q, Z, W, mb)) return rc;
+        magk::mass_apply(mesh, mb, s);
+        magk::gram(Z, Y, W, N, q, ctx->modal_part.as<double>(), d_gram, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h_gram.data(), d_gram, 8 * h_gram.size(), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (int32_t i = 0; i < q; ++i)
+            for (int32_t j = 0; j < q; ++j) {
+                A[(size_t)i * q + j] = 0.5 * (h_gram[(size_t)i * q + j] + h_gram[(size_t)j * q + i]);
+                B[(size_t)i * q + j] = 0.5 * (h_gram[(size_t)q * q + (size_t)i * q + j] + h_gram[(size_t)q * q + (size_t)j * q + i]);
+            }
+        int pivot = -1;
+        const int eig = magh::sym_def_eig(q, A.data(), B.data(), lambda.data(), Qm.data(), &pivot);
+        if (eig == magh::EIG_DEPENDENT)
+            return fail(ctx, MAG_ERR_NOT_CONVERGED, "mag_run_modal: outer step %d: the vectors of the subspace are linearly dependent (pivot %d of Z^T M Z)",
+                        (int)step + 1, pivot);
+        if (eig != magh::EIG_OK) return fail(ctx, MAG_ERR_NOT_CONVERGED, "mag_run_modal: outer step %d: the Rayleigh-Ritz step did not converge", (int)step + 1);
+        if (!prev.empty()) {
+            double change = 0.0;
+            for (int32_t k = 0; k < p; ++k) change = std::max(change, std::fabs(lambda[(size_t)k] - prev[(size_t)k]) / std::fabs(lambda[(size_t)k]));
+            converged = change <= tol; // (a NaN is no convergence)
+        }
+        prev = lambda;
+        const bool last = converged || step + 1 == max_outer;
+        std::fill(h_qs.begin(), h_qs.end(), 0.0);
+        for (int32_t i = 0; i < q; ++i)
+            for (int32_t j = 0; j < q; ++j) h_qs[(size_t)i * MQ + j] = Qm[(size_t)i * q + j];
+        for (int32_t k = 0; k < q; ++k) h_qs[(size_t)MQ * MQ + k] = lambda[(size_t)k];
+        HIPCHK(hipMemcpyAsync(d_qs, h_qs.data(), 8 * h_qs.size(), hipMemcpyHostToDevice, s));
+        magk::rotate(Z, W, Y, d_qs, N, q, p, X, Y2, last ? ctx->modal_r.as<double>() : nullptr, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(Y, Y2, vb * q, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipStreamSynchronize(s)); // (h_qs is done with)
+        if (last) break;
+    }
+
+    // ---- 3. the residuals from the pass's own quantities, the modes' signs
+    std::vector<double> norms(2 * (size_t)p);
+    magk::residual_norms(ctx->modal_r.as<double>(), Y, N, p, ctx->modal_part.as<double>(), d_norms, s);
+    magk::fix_signs(X, N, p, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(norms.data(), d_norms, 8 * norms.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    ctx->modal_lambda.assign(lambda.begin(), lambda.begin() + p);
+    ctx->modal_residual.assign((size_t)p, 0.0);
+    for (int32_t k = 0; k < p; ++k) {
+        const double den = std::fabs(lambda[(size_t)k]) * std::sqrt(norms[2 * (size_t)k + 1]);
+        ctx->modal_residual[(size_t)k] = den > 0.0 ? std::sqrt(norms[2 * (size_t)k]) / den : 0.0;
+    }
+    info[3] = converged ? 1 : 0;
+    ctx->modal_have = true;
+    if (!converged)
+        ctx->err = "mag_run_modal stopped at the cap of " + std::to_string((int)max_outer) + " outer steps above the tolerance: last iterate returned";
+    return MAG_OK;
+}
+
+int mag_download_modal(mag_ctx *ctx, mag_modal_result *o)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "null modal result");
+    if (ctx->comm.nranks > 1)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "modal analysis runs on one GPU: this context has a communicator of %d ranks", ctx->comm.nranks);
+    if (!ctx->have_problem || !ctx->modal_have) return fail(ctx, MAG_ERR_STATE, "mag_download_modal before a completed mag_run_modal");
+    if (int rc = enter(ctx)) return rc;
+    const int32_t p = ctx->modal_info[0];
+    const hipMemcpyKind kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const hipMemcpyKind hkind = o->memory == MAG_MEM_DEVICE ? hipMemcpyHostToDevice : hipMemcpyHostToHost;
+    hipStream_t s = ctx->stream;
+    std::vector<double> freq((size_t)p);
+    for (int32_t k = 0; k < p; ++k) freq[(size_t)k] = std::sqrt(ctx->modal_lambda[(size_t)k]) / (2.0 * M_PI);
+    if (o->lambda_out) HIPCHK(hipMemcpyAsync(o->lambda_out, ctx->modal_lambda.data(), 8 * (size_t)p, hkind, s));
+    if (o->frequency_out) HIPCHK(hipMemcpyAsync(o->frequency_out, freq.data(), 8 * (size_t)p, hkind, s));
+    if (o->residual_out) HIPCHK(hipMemcpyAsync(o->residual_out, ctx->modal_residual.data(), 8 * (size_t)p, hkind, s));
+    if (o->shapes_out) HIPCHK(hipMemcpyAsync(o->shapes_out, ctx->modal_x.p, 16 * (size_t)ctx->N * (size_t)p, kind, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
+int mag_get_modal_info(const mag_ctx *ctx, int32_t info[8])
+{
+    if (!ctx || !info || ctx->comm.nranks > 1) return MAG_ERR_BAD_ARGS;
+    if (!ctx->have_problem || !ctx->modal_have) return MAG_ERR_STATE;
+    for (int k = 0; k < 8; ++k) info[k] = ctx->modal_info[k];
+    return MAG_OK;
+}
+
+int mag_get_modal_stats(const mag_ctx *ctx, int32_t j, mag_stats *st)
+{
+    if (!ctx || !st || j < 0 || ctx->comm.nranks > 1) return MAG_ERR_BAD_ARGS;
+    if (!ctx->have_problem || !ctx->modal_have) return MAG_ERR_STATE;
+    return member_stats(ctx->modal, j, st);
+}
+
+int mag_apply_mass(mag_ctx *ctx, double density, int32_t lumped, const double *x, double *y, int32_t masked)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!x || !y) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_apply_mass: null vector");
+    if (int rc = mass_refused(ctx, "mag_apply_mass", density)) return rc;
+    if (int rc = enter(ctx)) return rc;
+    if (int rc = ensure_full_order(ctx)) return rc;
+    const int64_t N = ctx->N;
+    const size_t vb = 16 * (size_t)N;
+    hipStream_t s = ctx->stream;
+    // (staged in the iteration's scratch vectors: the modes, like every other result, stay as they are)
+    HIPCHK(ctx->modal_w.reserve(vb));
+    HIPCHK(ctx->modal_y2.reserve(vb));
+    magk::SensMesh mesh;
+    magk::MassBatch mb;
+    if (int rc = sens_mesh(ctx, mesh)) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->modal_w.p, x, vb, hipMemcpyHostToDevice, s));
+    if (masked) magk::mask_vectors(ctx->uknown.as<uint8_t>(), N, 1, ctx->modal_w.as<double>(), s);
+    if (int rc = mass_batch(ctx, density, lumped, masked, 1, ctx->modal_w.as<double>(), ctx->modal_y2.as<double>(), mb)) return rc;
+    magk::mass_apply(mesh, mb, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(y, ctx->modal_y2.p, vb, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
 }
 
 int mag_solve(mag_ctx *ctx, const mag_problem *p, mag_result *r)

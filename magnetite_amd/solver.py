@@ -509,6 +509,55 @@ class Context:
         self.run_stress(set)
         return [self.download_stress(set, i) for i in range(self._members(set))]
 
+    # -- modal analysis: the lowest natural frequencies and mode shapes of the uploaded part ------------
+    MODAL_INFO = ("modes", "subspace", "outer", "converged", "vectors_per_launch", "launches", "redone")
+
+    def run_modal(self, modes=6, density=None, subspace=0, tol=0.0, cg_tol=0.0, max_outer=0, lumped=False, allow_not_converged=False):
+        """mag_run_modal on the uploaded problem (no run needed): subspace iteration for the `modes` lowest pairs of
+        K_FF phi = lambda M_FF phi, prescribed DOFs as supports.  Reaching max_outer is no error (modal_info()["converged"] == 0)."""
+        if density is None:
+            raise MagnetiteError("Solver", "modal: a density is needed (the model has none)")
+        o = _lib.ModalOptions(int(modes), int(subspace), int(max_outer), 1 if lumped else 0, float(density), float(tol), float(cg_tol))
+        allow = (MAG_ERR_NOT_CONVERGED,) if allow_not_converged else ()
+        return self._check(self._L.mag_run_modal(self._h, C.byref(o)), allow)
+
+    def modal_info(self):
+        """dict(modes, subspace, outer, converged, vectors_per_launch (0: one after another), launches, redone)."""
+        info = (C.c_int32 * 8)()
+        self._check(self._L.mag_get_modal_info(self._h, info))
+        return dict(zip(self.MODAL_INFO, info))
+
+    def modal_stats(self, j):
+        """The statistics of inner solve j of the last outer step (mag_get_modal_stats)."""
+        return self._stats_at(self._L.mag_get_modal_stats, j)
+
+    def download_modal(self):
+        """dict(lambda (p), frequency (p), residual (p), shapes (p, 2N)) of the last run_modal()."""
+        p = self.modal_info()["modes"]
+        lam, freq, res, shapes = np.empty(p), np.empty(p), np.empty(p), np.empty((p, 2 * self.N))
+        o = _lib.ModalResult(lam.ctypes.data, freq.ctypes.data, res.ctypes.data, shapes.ctypes.data, MAG_MEM_HOST, 0)
+        self._check(self._L.mag_download_modal(self._h, C.byref(o)))
+        return {"lambda": lam, "frequency": freq, "residual": res, "shapes": shapes}
+
+    def modal(self, prob=None, modes=6, density=None, subspace=0, tol=0.0, cg_tol=0.0, max_outer=0, lumped=False):
+        """The `modes` lowest natural frequencies (Hz) and mode shapes of prob (uploaded when given; otherwise of what is
+        uploaded): dict(lambda, frequency, residual, shapes (modes, 2N), and the words of modal_info() by name).  shapes are
+        mass-normalised, phi_k^T M phi_l = delta_kl, and 0 on prescribed DOFs, which act as supports (include/magnetite_hip.h)."""
+        if prob is not None:
+            self.upload_problem(prob)
+        self.run_modal(modes, density, subspace, tol, cg_tol, max_outer, lumped)
+        out = self.download_modal()
+        out.update(self.modal_info())
+        return out
+
+    def apply_mass(self, x, density, lumped=False, masked=False):
+        """y = M x with the mass operator of run_modal (test entry point mag_apply_mass)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.empty(2 * self.N)
+        self._check(self._L.mag_apply_mass(self._h, float(density), 1 if lumped else 0, _p(x, C.c_double), _p(y, C.c_double),
+                                           1 if masked else 0))
+        return y
+
     # -- pieces, for parity tests ----------------------------------------------
     def element_stiffness(self):
         ke = np.empty(36 * self.E)

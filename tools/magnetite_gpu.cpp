@@ -7,9 +7,11 @@
 //   * MSH-4 ASCII           mesher.rs:536-704   + check_ccw with its `< 1.0` quirk (mesher.rs:522-526)
 //   * nodes.csv/elements.csv post_processor.rs:18-83, floats as Rust's `{}` prints them
 // Usage: magnetite_gpu <input.json> <mesh.msh> [--nodes nodes.csv] [--elements elements.csv] [--dry-run] [--rel TOL]
-//                      [--stress-recovery]
+//                      [--stress-recovery] [--modal P --density RHO]
 //   --dry-run  stop before the solver and print what was parsed (no GPU needed)
 //   --rel TOL  stop CG on relative residual TOL instead of the reference's absolute 1e-4
+//   --modal P --density RHO  also print "info: mode k frequency F Hz residual R" for the P lowest modes and write modes.csv
+//              (id,ux1,uy1,...,uxP,uyP) next to nodes.csv -- solver::modal; the input JSON has no density, hence the flag
 //   --stress-recovery  also write nodes_stress.csv (id,sx,sy,txy,vm) and elements_stress.csv (id,sx,sy,txy,vm,eta2) next to the
 //              two files -- solver::stress_recovery: the tensor per element, the nodal field, the ZZ error indicator -- and
 //              print eta_rel; without it nothing changes
@@ -348,17 +350,47 @@ void stress_output(const StressField &s, const std::string &nodes_output, const 
     std::printf("info: wrote stress recovery to %s and %s\n", nodes_output.c_str(), elements_output.c_str());
 }
 
+// "dir/nodes.csv" -> "dir/modes.csv"
+std::string modes_name(const std::string &nodes_output)
+{
+    const size_t slash = nodes_output.find_last_of('/');
+    return (slash == std::string::npos ? std::string() : nodes_output.substr(0, slash + 1)) + "modes.csv";
+}
+
+// the shapes of solver::modal, a row per node, floats as csv_output prints them
+void modes_output(const Modes &m, size_t num_nodes, const std::string &path)
+{
+    std::FILE *mf = std::fopen(path.c_str(), "w");
+    if (!mf) die({MagnetiteError::Solver, "Failed to create modes.csv: " + path});
+    const size_t P = m.lambda.size();
+    std::fputs("id", mf);
+    for (size_t k = 1; k <= P; ++k) std::fprintf(mf, ",ux%zu,uy%zu", k, k);
+    std::fputs("\n", mf);
+    for (size_t i = 0; i < num_nodes; ++i) {
+        std::fprintf(mf, "%zu", i);
+        for (size_t k = 0; k < P; ++k)
+            std::fprintf(mf, ",%s,%s", rust_display(m.shapes[k * 2 * num_nodes + 2 * i]).c_str(),
+                         rust_display(m.shapes[k * 2 * num_nodes + 2 * i + 1]).c_str());
+        std::fputs("\n", mf);
+    }
+    std::fclose(mf);
+    std::printf("info: wrote mode shapes to %s\n", path.c_str());
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
 {
     std::string input, mesh, nodes_out = "nodes.csv", elements_out = "elements.csv";
     bool dry = false, recover = false;
-    double rel = 0.0;
+    int modal_modes = 0;
+    double rel = 0.0, density = 0.0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--dry-run") dry = true;
         else if (a == "--stress-recovery") recover = true;
+        else if (a == "--modal" && i + 1 < argc) modal_modes = std::atoi(argv[++i]);
+        else if (a == "--density" && i + 1 < argc) density = std::atof(argv[++i]);
         else if (a == "--nodes" && i + 1 < argc) nodes_out = argv[++i];
         else if (a == "--elements" && i + 1 < argc) elements_out = argv[++i];
         else if (a == "--rel" && i + 1 < argc) rel = std::atof(argv[++i]);
@@ -367,9 +399,10 @@ int main(int argc, char **argv)
         else die({MagnetiteError::Input, "Unrecognized argument " + a});
     }
     if (input.empty() || mesh.empty()) {
-        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery]\n");
+        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery] [--modal P --density RHO]\n");
         return 2;
     }
+    if (modal_modes < 0 || (modal_modes > 0 && !(density > 0.0))) die({MagnetiteError::Input, "--modal P needs P >= 1 and --density RHO > 0"});
     // mesher::run (mesher.rs:939-974) minus geometry parsing and the gmsh subprocess
     const std::string text = slurp(input, MagnetiteError::Input, "Unable to open input file " + input);
     JsonParser jp(text);
@@ -411,7 +444,7 @@ int main(int argc, char **argv)
         opt.stop_mode = MAG_STOP_REL;
         opt.tol = rel;
     }
-    const std::vector<Node> posed = recover ? nodes : std::vector<Node>();  // (run() fills every value in)
+    const std::vector<Node> posed = recover || modal_modes > 0 ? nodes : std::vector<Node>();  // (run() fills every value in)
     if (Result err = solver::run(nodes, elements, meta, &opt)) die(*err);
     // post_processor::csv_output (main.rs:69); the matplotlib plot (main.rs:72) is not part of this tool
     csv_output(elements, nodes, nodes_out, elements_out);
@@ -423,6 +456,23 @@ int main(int argc, char **argv)
         std::printf("info: stress recovery eta_rel %s (eta %s, energy norm %s), largest von Mises stress %s in an element, %s at a node\n",
                     rust_display(fields[0].eta_rel).c_str(), rust_display(fields[0].eta).c_str(), rust_display(fields[0].energy_norm).c_str(),
                     rust_display(fields[0].vm_max).c_str(), rust_display(fields[0].vm_node_max).c_str());
+    }
+    if (modal_modes > 0) {
+        // The modal analysis needs every element counter-clockwise (the stiffness carries the signed area).  check_ccw compares
+        // the area with 1.0 (parse_mesh), which leaves a part of small elements clockwise: the elements go in by their true sign.
+        std::vector<Element> ccw = elements;
+        for (Element &e : ccw)
+            if (solver::compute_element_area(e, posed) < 0.0) std::swap(e.nodes[0], e.nodes[2]);
+        opt.verbose = 0;
+        ModalSpec spec;
+        spec.modes = modal_modes;
+        spec.density = density;
+        Modes modes;
+        if (Result err = solver::modal(posed, ccw, meta, spec, modes, &opt)) die(*err);
+        for (size_t k = 0; k < modes.lambda.size(); ++k)
+            std::printf("info: mode %zu frequency %s Hz residual %s\n", k + 1, rust_display(modes.frequency[k]).c_str(),
+                        rust_display(modes.residual[k]).c_str());
+        modes_output(modes, posed.size(), modes_name(nodes_out));
     }
     return 0;
 }
