@@ -42,8 +42,8 @@ extern "C" {
                              mag_get_cases_info) came later as new entry points only: no struct changed, the version
                              stays 4, and a caller detects the feature by the presence of those symbols (dlsym); design
                              variants (mag_set_variants ... mag_get_variants_info), sensitivities (mag_run_sensitivities,
-                             mag_download_sensitivity) and adjoint sensitivities (mag_run_adjoint ... mag_get_adjoint_info)
-                             likewise */
+                             mag_download_sensitivity), adjoint sensitivities (mag_run_adjoint ... mag_get_adjoint_info) and
+                             mesh refinement (mag_run_refine ... mag_upload_refined) likewise */
 
 /* solver.rs:17-19 */
 #define MAG_DOF 2
@@ -562,6 +562,78 @@ int mag_download_modal(mag_ctx *ctx, mag_modal_result *out);
 int mag_get_modal_info(const mag_ctx *ctx, int32_t info[8]);
 /* statistics of inner solve j of the LAST outer step, as mag_get_case_stats */
 int mag_get_modal_stats(const mag_ctx *ctx, int32_t j, mag_stats *stats);
+
+/* ---- adaptive mesh refinement: longest-edge bisection with conformity closure (Rivara) of the uploaded mesh, on the device ----
+ * What acts on the ZZ indicator of mag_run_stress: solve -> mag_run_stress -> mag_run_refine -> mag_upload_refined -> solve, the
+ * mesh never leaving the device.  The reference (gmsh meshing, no adaptivity) has no counterpart.  The result is a pure function
+ * of the inputs -- a repeat gives the same bits -- because the numbering is fixed:
+ *   edges      local edge k of element e is (conn[3e + k], conn[3e + (k + 1) % 3]), identified by (lo, hi) = (smaller, larger
+ *              node); its id is the rank of (lo, hi) in lexicographic order among the unique edges of the mesh;
+ *   length     len2 = dx * dx + dy * dy with (dx, dy) = xy[hi] - xy[lo], two products and one addition, never fused: both
+ *              elements of an edge see the same bits;
+ *   longest    of an element: the local edge of largest len2, on a tie the smaller edge id -- a total order on the edges, which
+ *              makes the closure terminate and the result conforming when lengths tie exactly;
+ *   marked elements, by `rule`:
+ *     MAG_REFINE_MARKS         marks[E], nonzero: marked;
+ *     MAG_REFINE_MAX_FRACTION  ind[e] >= theta * max(ind), the product rounded once; nothing is marked when the maximum is 0;
+ *     MAG_REFINE_TOP_FRACTION  the k = clamp(ceil(theta * E), 1, E) elements of largest indicator, ties to the lower element
+ *                              index (a stable sort on the bits of ind[e] + 0.0);
+ *     indicator: E values in `memory`, every one finite and >= 0 (otherwise MAG_ERR_BAD_ARGS, the first offender named in
+ *     mag_last_error); NULL: the device-resident eta2 of the last mag_run_stress(MAG_SET_RUN), read where it lies.  theta in
+ *     (0, 1].  No floating-point sum enters the marking;
+ *   marked edges   split = 1: the longest edge of every marked element; split = 3: all three of its edges (Rivara's
+ *              four-triangle variant: h halves where marked);
+ *   closure    every element with a marked edge gets its longest edge marked, swept until a sweep marks nothing.  The marked set
+ *              is the least fixed point: it does not depend on the order of a sweep, the number of sweeps does;
+ *   new nodes  marked edge number r in edge-id order becomes node N + r at 0.5 * (x[lo] + x[hi]), 0.5 * (y[lo] + y[hi]).  Old
+ *              nodes keep index, coordinates and boundary data.  Per DOF d of a new node: where u_known[2 lo + d] and
+ *              u_known[2 hi + d] are both set, u_known = 1, u_in = 0.5 * (u_in[2 lo + d] + u_in[2 hi + d]); otherwise u_known = 0,
+ *              u_in = 0; f_in = 0 always.  Point loads stay on their nodes, so the total load is preserved, and the constraint
+ *              of the fine mesh interpolates the coarse one.  Re-stamping region rules (which put a force on EVERY node of a
+ *              region, so the total would grow with the mesh) is the caller's: node_parents is there for that;
+ *   new elements   an element without a marked edge is copied verbatim.  Otherwise, rotated so that its longest edge comes
+ *              first, (p, q, r) with the new nodes M, A, B of pq, qr, rp: (p, M, B), (B, M, r) when rp is marked, else (p, M, r);
+ *              then (M, q, A), (M, A, r) when qr is marked, else (M, q, r) -- 2, 3 or 4 children of the parent's orientation (a
+ *              clockwise mesh stays clockwise).  The children of e occupy off[e] .. off[e + 1], off the exclusive scan of the
+ *              child counts; elem_parent[E'] names each child's parent.
+ * mag_run_refine: works on the uploaded mesh; MAG_REFINE_MARKS or a caller's indicator needs no run.  Solves nothing and alters
+ *   no result of the context.  N' >= 2^30 or 9 E' >= 2^31: MAG_ERR_TOO_LARGE (mag_upload's limits).
+ * mag_get_refine_info: info[0] N', [1] E', [2] elements marked before the closure, [3] marked edges (N' - N), [4] closure
+ *   sweeps (the last, which marked nothing, included), [5] [6] [7] elements split in two, three, four.
+ * mag_download_refine: NULL members are skipped.
+ * mag_upload_refined: the refined mesh becomes the uploaded problem with the same material, copied device to device: bit for bit
+ *   mag_download_refine followed by mag_upload, and like mag_upload it drops runs, sets and modes.  The refinement's arrays stay
+ *   readable afterwards (the parents relate the new mesh to the old one) until a caller's mag_upload drops them or the next
+ *   mag_run_refine replaces them.
+ * Errors, before any HIP call: MAG_ERR_BAD_ARGS for null options / info / out, an unknown rule, split not 1 or 3, a theta that is
+ *   not finite or outside (0, 1] (rules 1 and 2), null marks under rule 0, a communicator of more than one rank; MAG_ERR_STATE
+ *   before mag_upload, for a NULL indicator (rules 1 and 2) without a completed mag_run_stress(MAG_SET_RUN), and for info,
+ *   download or mag_upload_refined before mag_run_refine.
+ * Out of scope: refinement across ranks; of load-case or variant sets (the uploaded mesh and MAG_SET_RUN's indicator only);
+ *   coarsening; snapping new boundary nodes to curved geometry (the model carries none); prolonging u as a starting guess (the
+ *   solver takes none); per-element material fields. */
+enum mag_refine_rule { MAG_REFINE_MARKS = 0, MAG_REFINE_MAX_FRACTION = 1, MAG_REFINE_TOP_FRACTION = 2 };
+typedef struct mag_refine_options {
+    int32_t rule;            /* enum mag_refine_rule */
+    int32_t split;           /* 1 | 3 */
+    double theta;            /* rules 1, 2: in (0, 1] */
+    const uint8_t *marks;    /* rule 0: E */
+    const double *indicator; /* rules 1, 2: E, NULL: eta2 of mag_run_stress(MAG_SET_RUN) */
+    int32_t memory, reserved; /* enum mag_memory of marks and indicator */
+} mag_refine_options;        /* 40 bytes */
+typedef struct mag_refined {
+    double *xy;            /* 2N', NULL: skipped */
+    int32_t *conn;         /* 3E' */
+    uint8_t *u_known;      /* 2N' */
+    double *u_in, *f_in;   /* 2N' */
+    int32_t *node_parents; /* [N' - N][2]: lo, hi of the edge a new node halves */
+    int32_t *elem_parent;  /* [E'] */
+    int32_t memory, reserved;
+} mag_refined;             /* 64 bytes */
+int mag_run_refine(mag_ctx *ctx, const mag_refine_options *opt);
+int mag_get_refine_info(const mag_ctx *ctx, int64_t info[8]);
+int mag_download_refine(mag_ctx *ctx, mag_refined *out);
+int mag_upload_refined(mag_ctx *ctx);
 
 /* ---- pieces of the path, exposed for parity tests -------------------- */
 /* solver.rs:187-193 compute_element_area (pub; the mesher imports it, mesher.rs:9,523). Host-side. */

@@ -90,6 +90,34 @@ struct Modes {
     std::int32_t modes = 0, subspace = 0, outer = 0, converged = 0, vectors_per_launch = 0, launches = 0, redone = 0;
 };
 
+// The options of solver::refine and solver::upload_refined (include/magnetite_hip.h, mag_refine_options).  marks (E values) given:
+// MAG_REFINE_MARKS whatever `rule` says; otherwise `rule` of `indicator` (E values), or, when that is empty, of the ZZ indicator
+// eta2 of the solved part, read on the device.
+struct RefineSpec {
+    std::int32_t rule = MAG_REFINE_TOP_FRACTION, split = 1;
+    double theta = 0.2;
+    std::vector<std::uint8_t> marks;
+    std::vector<double> indicator;
+};
+
+// What solver::refine returns: the refined mesh as a part to solve -- nodes with their boundary data as posed (exactly one of
+// displacement / force per axis), elements without stress --, the parents (node_parents: lo, hi of the edge that new node
+// nodes.size() - node_parents.size() / 2 + i halves; elem_parent: the coarse element of every element) and mag_get_refine_info's
+// words by name.
+struct Refined {
+    std::vector<Node> nodes;
+    std::vector<Element> elements;
+    std::vector<std::int32_t> node_parents, elem_parent;
+    std::int64_t marked = 0, marked_edges = 0, sweeps = 0, split2 = 0, split3 = 0, split4 = 0;
+};
+
+// One solve of solver::upload_refined's loop: the mesh it ran on, the ZZ estimate of its solution, its CG iterations.
+struct AdaptRound {
+    std::size_t nodes = 0, elements = 0;
+    double eta = 0, eta_rel = 0;
+    std::int64_t iterations = 0;
+};
+
 // The options of solver::modal (include/magnetite_hip.h, mag_modal_options); 0: the library's default.
 struct ModalSpec {
     std::int32_t modes = 6, subspace = 0, max_outer = 0;
@@ -630,6 +658,153 @@ inline Result modal(const std::vector<Node> &nodes, const std::vector<Element> &
     out.launches = info[5];
     out.redone = info[6];
     mag_destroy(ctx);
+    return std::nullopt;
+}
+
+namespace detail {
+
+// mag_run_refine with spec on the uploaded (and, for the device's own indicator, solved and recovered) problem of ctx
+inline int run_refine(mag_ctx *ctx, const RefineSpec &spec)
+{
+    mag_refine_options o{};
+    o.rule = spec.marks.empty() ? spec.rule : (std::int32_t)MAG_REFINE_MARKS;
+    o.split = spec.split;
+    o.theta = spec.theta;
+    o.marks = spec.marks.empty() ? nullptr : spec.marks.data();
+    o.indicator = spec.indicator.empty() ? nullptr : spec.indicator.data();
+    o.memory = MAG_MEM_HOST;
+    return mag_run_refine(ctx, &o);
+}
+
+// mag_download_refine into a part as posed: the mask decides which of displacement / force a node's axis carries
+inline int download_refined(mag_ctx *ctx, Refined &out)
+{
+    std::int64_t info[8] = {};
+    if (int rc = mag_get_refine_info(ctx, info)) return rc;
+    const std::size_t N = (std::size_t)info[0], E = (std::size_t)info[1], added = (std::size_t)info[3];
+    std::vector<double> xy(2 * N), u_in(2 * N), f_in(2 * N);
+    std::vector<std::uint8_t> known(2 * N);
+    std::vector<std::int32_t> conn(3 * E);
+    out = Refined{};
+    out.node_parents.resize(2 * added);
+    out.elem_parent.resize(E);
+    mag_refined d{};
+    d.xy = xy.data();
+    d.conn = conn.data();
+    d.u_known = known.data();
+    d.u_in = u_in.data();
+    d.f_in = f_in.data();
+    d.node_parents = added ? out.node_parents.data() : nullptr;
+    d.elem_parent = out.elem_parent.data();
+    d.memory = MAG_MEM_HOST;
+    if (int rc = mag_download_refine(ctx, &d)) return rc;
+    out.nodes.resize(N);
+    for (std::size_t i = 0; i < N; ++i) {
+        Node &n = out.nodes[i];
+        n.vertex = {xy[2 * i], xy[2 * i + 1]};
+        if (known[2 * i]) n.ux = u_in[2 * i]; else n.fx = f_in[2 * i];
+        if (known[2 * i + 1]) n.uy = u_in[2 * i + 1]; else n.fy = f_in[2 * i + 1];
+    }
+    out.elements.resize(E);
+    for (std::size_t e = 0; e < E; ++e)
+        out.elements[e].nodes = {(std::size_t)conn[3 * e], (std::size_t)conn[3 * e + 1], (std::size_t)conn[3 * e + 2]};
+    out.marked = info[2];
+    out.marked_edges = info[3];
+    out.sweeps = info[4];
+    out.split2 = info[5];
+    out.split3 = info[6];
+    out.split4 = info[7];
+    return MAG_OK;
+}
+
+}  // namespace detail
+
+// Mesh refinement (mag_run_refine): longest-edge bisection with conformity closure of the part's mesh, on the device.  With
+// marks or an indicator in spec nothing is solved; otherwise the part is solved, its stress recovered, and the elements are
+// marked by the ZZ indicator eta2 where it lies.  `nodes` carry the boundary data as posed; out.nodes carry the refined mesh's:
+// old nodes keep theirs, a new node interpolates a constraint both of its parents carry and is free and unloaded otherwise.
+inline Result refine(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                     const RefineSpec &spec, Refined &out, const mag_options *options = nullptr)
+{
+    const std::size_t N = nodes.size(), E = elements.size();
+    if (!spec.marks.empty() && spec.marks.size() != E) return detail::solver_error("refine: marks must have one entry per element");
+    if (!spec.indicator.empty() && spec.indicator.size() != E) return detail::solver_error("refine: indicator must have one entry per element");
+    std::vector<double> xy, u_in(2 * N), f_in(2 * N);
+    std::vector<std::uint8_t> u_known;
+    std::vector<std::int32_t> conn;
+    if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
+    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
+    mag_ctx *ctx = mag_create(options);
+    if (!ctx) return detail::solver_error("mag_create failed");
+    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
+    if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    if (spec.marks.empty() && spec.indicator.empty())
+        if (mag_run(ctx) != MAG_OK || mag_run_stress(ctx, MAG_SET_RUN) != MAG_OK) return detail::fail_and_destroy(ctx);
+    if (detail::run_refine(ctx, spec) != MAG_OK || detail::download_refined(ctx, out) != MAG_OK) return detail::fail_and_destroy(ctx);
+    mag_destroy(ctx);
+    return std::nullopt;
+}
+
+// The adaptive loop on mag_upload_refined, the mesh never leaving the device: per round solve -> mag_run_stress -> record ->
+// mag_run_refine by the ZZ indicator (spec.rule, theta, split; marks and indicator are not used) -> mag_upload_refined; after
+// the last refinement one more solve and recovery.  Afterwards `nodes` and
+// `elements` are the final mesh as run() leaves a part -- every ux / uy / fx / fy and stress set --, history holds one entry
+// per solve (rounds + 1) and *posed_out, when asked for, the final mesh's nodes with their boundary data
+// as posed.
+inline Result upload_refined(std::vector<Node> &nodes, std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                             const RefineSpec &spec, int rounds, std::vector<AdaptRound> &history, const mag_options *options = nullptr,
+                             std::vector<Node> *posed_out = nullptr)
+{
+    std::size_t N = nodes.size(), E = elements.size();
+    std::vector<double> xy, u_in(2 * N), f_in(2 * N);
+    std::vector<std::uint8_t> u_known;
+    std::vector<std::int32_t> conn;
+    if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
+    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
+    mag_ctx *ctx = mag_create(options);
+    if (!ctx) return detail::solver_error("mag_create failed");
+    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
+    if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    RefineSpec by_eta2 = spec;
+    by_eta2.marks.clear();
+    by_eta2.indicator.clear();
+    history.clear();
+    bool refined = false;
+    for (int r = 0;; ++r) {
+        if (mag_run(ctx) != MAG_OK || mag_run_stress(ctx, MAG_SET_RUN) != MAG_OK) return detail::fail_and_destroy(ctx);
+        mag_stress_field f{};
+        f.memory = MAG_MEM_HOST;
+        mag_stats st{};
+        if (mag_download_stress(ctx, MAG_SET_RUN, 0, &f) != MAG_OK || mag_get_stats(ctx, &st) != MAG_OK) return detail::fail_and_destroy(ctx);
+        history.push_back({N, E, std::sqrt(f.scalars[0]), f.scalars[2], st.iterations});
+        if (r >= rounds) break;
+        std::int64_t info[8] = {};
+        if (detail::run_refine(ctx, by_eta2) != MAG_OK || mag_upload_refined(ctx) != MAG_OK || mag_get_refine_info(ctx, info) != MAG_OK)
+            return detail::fail_and_destroy(ctx);
+        N = (std::size_t)info[0];
+        E = (std::size_t)info[1];
+        refined = true;
+    }
+    Refined mesh;
+    if (refined) {
+        if (detail::download_refined(ctx, mesh) != MAG_OK) return detail::fail_and_destroy(ctx);
+    } else {
+        mesh.nodes = nodes;
+        mesh.elements = elements;
+    }
+    std::vector<double> u(2 * N), f(2 * N), stress(E);
+    mag_result res{};
+    res.u_out = u.data();
+    res.f_out = f.data();
+    res.stress_out = stress.data();
+    res.memory = MAG_MEM_HOST;
+    if (mag_download(ctx, &res) != MAG_OK) return detail::fail_and_destroy(ctx);
+    mag_destroy(ctx);
+    if (posed_out) *posed_out = mesh.nodes;
+    nodes = std::move(mesh.nodes);
+    elements = std::move(mesh.elements);
+    detail::store_values(nodes, u, f);
+    for (std::size_t e = 0; e < E; ++e) elements[e].stress = stress[e];
     return std::nullopt;
 }
 

@@ -21,6 +21,7 @@ MAG_TERM_NONE, MAG_TERM_TARGET_COST, MAG_TERM_MAX_ITERS, MAG_TERM_BREAKDOWN = 0,
 MAG_MEM_HOST, MAG_MEM_DEVICE = 0, 1
 MAG_SET_RUN, MAG_SET_CASES, MAG_SET_VARIANTS = 0, 1, 2
 MAG_OBJ_DISP_LSQ, MAG_OBJ_STRESS_PNORM = 0, 1
+MAG_REFINE_MARKS, MAG_REFINE_MAX_FRACTION, MAG_REFINE_TOP_FRACTION = 0, 1, 2
 MAG_UNIQUE_ID_BYTES = 128
 MAG_IPC_HANDLE_BYTES = 64
 
@@ -38,6 +39,7 @@ SYMBOLS = [
     "mag_run_objective", "mag_download_objective",
     "mag_run_stress", "mag_download_stress",
     "mag_run_modal", "mag_download_modal", "mag_get_modal_info", "mag_get_modal_stats", "mag_apply_mass",
+    "mag_run_refine", "mag_get_refine_info", "mag_download_refine", "mag_upload_refined",
     "mag_comm_get_unique_id", "mag_comm_init_rccl", "mag_comm_query", "mag_comm_init_callback", "mag_comm_set_window", "mag_comm_inbox_create", "mag_comm_inbox_open",
 ]
 
@@ -111,6 +113,16 @@ class ModalOptions(C.Structure):
 class ModalResult(C.Structure):
     _fields_ = [("lambda_out", C.c_void_p), ("frequency_out", C.c_void_p), ("residual_out", C.c_void_p), ("shapes_out", C.c_void_p),
                 ("memory", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RefineOptions(C.Structure):
+    _fields_ = [("rule", C.c_int32), ("split", C.c_int32), ("theta", C.c_double), ("marks", C.c_void_p), ("indicator", C.c_void_p),
+                ("memory", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Refined(C.Structure):
+    _fields_ = [("xy", C.c_void_p), ("conn", C.c_void_p), ("u_known", C.c_void_p), ("u_in", C.c_void_p), ("f_in", C.c_void_p),
+                ("node_parents", C.c_void_p), ("elem_parent", C.c_void_p), ("memory", C.c_int32), ("reserved", C.c_int32)]
 
 
 HASHED_SOURCES = ("persist.hip", "persist_kernel.h", "persist_shapes.h", "persist_inst.hip", "cg.hip", "cg_device.h", "exact.hip", "symbolic.hip", "kernels.h")
@@ -205,6 +217,11 @@ def lib():
         L.mag_get_modal_info.argtypes = [vp, ip]
         L.mag_get_modal_stats.argtypes = [vp, C.c_int32, C.POINTER(Stats)]
         L.mag_apply_mass.argtypes = [vp, C.c_double, C.c_int32, dp, dp, C.c_int32]
+    if hasattr(L, "mag_run_refine"):  # (likewise: scripts/refine_probe.py)
+        L.mag_run_refine.argtypes = [vp, C.POINTER(RefineOptions)]
+        L.mag_get_refine_info.argtypes = [vp, C.POINTER(C.c_int64)]
+        L.mag_download_refine.argtypes = [vp, C.POINTER(Refined)]
+        L.mag_upload_refined.argtypes = [vp]
     L.mag_compute_element_area.argtypes = [dp, ip]
     L.mag_compute_element_area.restype = C.c_double
     L.mag_compute_strain_displacement_matrix.argtypes = [dp, ip, C.c_double, dp]

@@ -28,6 +28,7 @@
 #include "modal_host.h"
 #include "objective.h"
 #include "recover.h"
+#include "refine.h"
 #include "sens.h"
 
 using magk::CgState;
@@ -293,6 +294,13 @@ struct mag_ctx {
     bool modal_have = false;
     int32_t modal_info[8] = {};
     std::vector<double> modal_lambda, modal_residual;
+
+    // mesh refinement (mag_run_refine): the tables of the pass (rf_tab: one allocation, carved up per call), the caller's marks
+    // or indicator while they are read, rocPRIM's temporary of its sorts and scans (its own: the ordering phase's stays as it is),
+    // and the refined mesh with its parents, which outlives mag_upload_refined.  A caller's mag_upload drops it
+    DevBuf rf_tab, rf_in, rf_tmp, rf_xy, rf_conn, rf_uknown, rf_uin, rf_fin, rf_nparents, rf_eparent;
+    bool rf_have = false;
+    int64_t rf_info[8] = {};
 
     magc::Comm comm;
 };
@@ -2267,6 +2275,7 @@ int mag_upload(mag_ctx *ctx, const mag_problem *p)
     ctx->variants.reset();
     ctx->modal.reset();
     ctx->modal_have = false;
+    ctx->rf_have = false;
     for (int32_t slot = MAG_SET_RUN; slot <= MAG_SET_VARIANTS; ++slot) drop_derived(ctx, slot);
     return MAG_OK;
 }
@@ -3903,6 +3912,259 @@ int mag_apply_mass(mag_ctx *ctx, double density, int32_t lumped, const double *x
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(y, ctx->modal_y2.p, vb, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
+// ---- mesh refinement (refine.hip): longest-edge bisection with conformity closure of the uploaded mesh.  The driver owns the
+// buffers, runs the sorts and scans between the kernels' stages and reads back three times: the indicator's check (rules 1, 2),
+// the sweeps' "changed" words once per batch, the sizes N' and E' to allocate ----
+namespace {
+
+// the checks mag_get_refine_info, mag_download_refine and mag_upload_refined share, before any HIP call
+int refined_refused(const mag_ctx *ctx, const void *o, const char *what, const char *fn)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    mag_ctx *c = const_cast<mag_ctx *>(ctx); // (the message only)
+    if (!o) return fail(c, MAG_ERR_BAD_ARGS, "%s: null %s", fn, what);
+    if (!ctx->have_problem || !ctx->rf_have) return fail(c, MAG_ERR_STATE, "%s before a completed mag_run_refine", fn);
+    return MAG_OK;
+}
+
+} // namespace
+
+int mag_run_refine(mag_ctx *ctx, const mag_refine_options *ro)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!ro) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_refine: null options");
+    const int32_t rule = ro->rule, split = ro->split;
+    if (rule < MAG_REFINE_MARKS || rule > MAG_REFINE_TOP_FRACTION)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_refine: rule %d is none of enum mag_refine_rule", (int)rule);
+    if (split != 1 && split != 3) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_refine: split = %d is neither 1 nor 3", (int)split);
+    const bool by_indicator = rule != MAG_REFINE_MARKS;
+    if (by_indicator && !(std::isfinite(ro->theta) && ro->theta > 0.0 && ro->theta <= 1.0))
+        return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_refine: theta = %g outside (0, 1]", ro->theta);
+    if (!by_indicator && !ro->marks) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_refine: null marks under MAG_REFINE_MARKS");
+    if (ctx->comm.nranks > 1)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "refinement runs on one GPU: this context has a communicator of %d ranks", ctx->comm.nranks);
+    if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "mag_run_refine before mag_upload");
+    const DerivedSet &recovery = ctx->derived[PASS_STRESS][MAG_SET_RUN];
+    if (by_indicator && !ro->indicator && !(ctx->have_run && recovery.have))
+        return fail(ctx, MAG_ERR_STATE, "mag_run_refine: no indicator given and none held: before a completed mag_run_stress(MAG_SET_RUN)");
+    if (int rc = enter(ctx)) return rc;
+
+    hipStream_t s = ctx->stream;
+    const int64_t N = ctx->N, E = ctx->E;
+    const size_t n3 = 3 * (size_t)E;
+    ctx->rf_have = false;
+
+    // the tables: one allocation, every part on a 256-byte boundary
+    magk::RefineTables t = {};
+    size_t bytes = 0;
+    const auto part = [&bytes](size_t b) {
+        const size_t at = bytes;
+        bytes += (b + 255) & ~(size_t)255;
+        return at;
+    };
+    const size_t o_key0 = part(8 * n3), o_key1 = part(8 * n3), o_val0 = part(4 * n3), o_val1 = part(4 * n3), o_head = part(4 * n3),
+                 o_hscan = part(4 * n3), o_eid = part(4 * n3), o_ekey = part(8 * n3), o_flag = part(4 * (n3 + 1)),
+                 o_mid = part(4 * (n3 + 1)), o_lng = part((size_t)E), o_marks = part((size_t)E), o_cnt = part(4 * ((size_t)E + 1)),
+                 o_off = part(4 * ((size_t)E + 1)), o_counters = part(4 * magk::RF_COUNTERS), o_check = part(16);
+    HIPCHK(ctx->rf_tab.reserve(bytes));
+    char *base = ctx->rf_tab.as<char>();
+    t.N = N;
+    t.E = E;
+    t.xy = ctx->xy.as<double>();
+    t.conn = ctx->conn.as<int32_t>();
+    t.u_known = ctx->uknown.as<uint8_t>();
+    t.u_in = ctx->uin.as<double>();
+    t.f_in = ctx->fin.as<double>();
+    t.key0 = (uint64_t *)(base + o_key0);
+    t.key1 = (uint64_t *)(base + o_key1);
+    t.val0 = (uint32_t *)(base + o_val0);
+    t.val1 = (uint32_t *)(base + o_val1);
+    t.head = (int32_t *)(base + o_head);
+    t.hscan = (int32_t *)(base + o_hscan);
+    t.eid = (int32_t *)(base + o_eid);
+    t.ekey = (uint64_t *)(base + o_ekey);
+    t.flag = (uint32_t *)(base + o_flag);
+    t.mid = (int32_t *)(base + o_mid);
+    t.lng = (uint8_t *)(base + o_lng);
+    t.marks = (uint8_t *)(base + o_marks);
+    t.cnt = (int32_t *)(base + o_cnt);
+    t.off = (int32_t *)(base + o_off);
+    t.counters = (uint32_t *)(base + o_counters);
+    t.check = (uint64_t *)(base + o_check);
+
+    // (the sorts and scans with a temporary of the pass's own)
+    const auto sort64 = [&](const uint64_t *kin, uint64_t *kout, const uint32_t *vin, uint32_t *vout, size_t n, int end_bit) -> int {
+        size_t tb = 0;
+        HIPCHK(magp::sort_pairs_u64(nullptr, &tb, kin, kout, vin, vout, n, 0, end_bit, s));
+        HIPCHK(ctx->rf_tmp.reserve(tb));
+        HIPCHK(magp::sort_pairs_u64(ctx->rf_tmp.p, &tb, kin, kout, vin, vout, n, 0, end_bit, s));
+        return MAG_OK;
+    };
+    const auto scan32 = [&](const int32_t *in, int32_t *out, size_t n) -> int {
+        size_t tb = 0;
+        HIPCHK(magp::exclusive_scan_i32(nullptr, &tb, in, out, n, s));
+        HIPCHK(ctx->rf_tmp.reserve(tb));
+        HIPCHK(magp::exclusive_scan_i32(ctx->rf_tmp.p, &tb, in, out, n, s));
+        return MAG_OK;
+    };
+
+    // 1. edges: keys, sort, run heads, ids, the longest edge of every element
+    HIPCHK(hipMemsetAsync(t.flag, 0, 4 * (n3 + 1), s));
+    HIPCHK(hipMemsetAsync(t.counters, 0, 4 * magk::RF_COUNTERS, s));
+    magk::refine_edge_keys(t, s);
+    if (int rc = sort64(t.key0, t.key1, t.val0, t.val1, n3, 32 + ceil_log2(N))) return rc;
+    magk::refine_heads(t, s);
+    if (int rc = scan32(t.head, t.hscan, n3)) return rc;
+    magk::refine_edge_table(t, s);
+    HIPCHK(hipGetLastError());
+
+    // 2. marked elements
+    const hipMemcpyKind kind = ro->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (!by_indicator) {
+        HIPCHK(hipMemcpyAsync(t.marks, ro->marks, (size_t)E, kind, s));
+    } else {
+        const double *ind = recovery.seta2.as<double>(); // (member 0 of MAG_SET_RUN's recovery, where it lies)
+        if (ro->indicator) {
+            ind = ro->indicator;
+            if (ro->memory != MAG_MEM_DEVICE) {
+                HIPCHK(ctx->rf_in.reserve(8 * (size_t)E));
+                HIPCHK(hipMemcpyAsync(ctx->rf_in.p, ro->indicator, 8 * (size_t)E, hipMemcpyHostToDevice, s));
+                ind = ctx->rf_in.as<double>();
+            }
+        }
+        const uint64_t check0[2] = {0, ~uint64_t(0)};
+        uint64_t check[2] = {};
+        HIPCHK(hipMemcpyAsync(t.check, check0, sizeof check0, hipMemcpyHostToDevice, s));
+        magk::refine_check_indicator(t, ind, s);
+        HIPCHK(hipMemcpyAsync(check, t.check, sizeof check, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (check[1] != ~uint64_t(0)) {
+            double bad = 0.0;
+            HIPCHK(hipMemcpy(&bad, ind + check[1], 8, hipMemcpyDeviceToHost));
+            return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_refine: indicator[%lld] = %g is not finite and >= 0", (long long)check[1], bad);
+        }
+        if (rule == MAG_REFINE_MAX_FRACTION) {
+            double vmax;
+            memcpy(&vmax, &check[0], 8);
+            if (vmax > 0.0) {
+                const double threshold = ro->theta * vmax; // rounded once
+                magk::refine_mark_max(t, ind, threshold, s);
+            } else {
+                HIPCHK(hipMemsetAsync(t.marks, 0, (size_t)E, s));
+            }
+        } else {
+            const int64_t k = std::min<int64_t>(std::max<int64_t>((int64_t)std::ceil(ro->theta * (double)E), 1), E);
+            HIPCHK(hipMemsetAsync(t.marks, 0, (size_t)E, s));
+            magk::refine_top_keys(t, ind, s);
+            if (int rc = sort64(t.key0, t.key1, t.val0, t.val1, (size_t)E, 64)) return rc;
+            magk::refine_mark_top(t, k, s);
+        }
+    }
+    magk::refine_mark_edges(t, split, s);
+    HIPCHK(hipGetLastError());
+
+    // 3. closure: batches of sweeps, their "changed" words read back once per batch; at most E + 1 sweeps
+    int64_t sweeps = 0;
+    for (bool done = false; !done;) {
+        const int batch = (int)std::min<int64_t>(magk::kRefineSweepBatch, E + 1 - sweeps);
+        if (batch < 1) return fail(ctx, MAG_ERR_STATE, "mag_run_refine: the closure did not end within %lld sweeps", (long long)(E + 1));
+        uint32_t changed[magk::kRefineSweepBatch] = {};
+        HIPCHK(hipMemsetAsync(t.counters + magk::RF_CHANGED, 0, sizeof changed, s));
+        magk::refine_sweeps(t, batch, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(changed, t.counters + magk::RF_CHANGED, sizeof changed, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (int j = 0; j < batch && !done; ++j) {
+            ++sweeps;
+            done = changed[j] == 0;
+        }
+    }
+
+    // 4. counts, numbering, sizes
+    magk::refine_child_counts(t, s);
+    if (int rc = scan32((const int32_t *)t.flag, t.mid, n3 + 1)) return rc;
+    if (int rc = scan32(t.cnt, t.off, (size_t)E + 1)) return rc;
+    magk::refine_sizes(t, s);
+    HIPCHK(hipGetLastError());
+    uint32_t counters[magk::RF_COUNTERS] = {};
+    HIPCHK(hipMemcpyAsync(counters, t.counters, sizeof counters, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const int64_t Nn = N + (int64_t)counters[magk::RF_NEW_NODES], En = (int64_t)counters[magk::RF_NEW_ELEMS];
+    if (Nn >= (int64_t(1) << 30) || 9 * En >= (int64_t(1) << 31))
+        return fail(ctx, MAG_ERR_TOO_LARGE, "refined mesh too large for int32 indexing (nodes=%lld elements=%lld)", (long long)Nn, (long long)En);
+
+    // 5. the refined mesh: the old nodes verbatim, the new nodes, the elements
+    HIPCHK(ctx->rf_xy.reserve(16 * (size_t)Nn));
+    HIPCHK(ctx->rf_conn.reserve(12 * (size_t)En));
+    HIPCHK(ctx->rf_uknown.reserve(2 * (size_t)Nn));
+    HIPCHK(ctx->rf_uin.reserve(16 * (size_t)Nn));
+    HIPCHK(ctx->rf_fin.reserve(16 * (size_t)Nn));
+    HIPCHK(ctx->rf_nparents.reserve(8 * (size_t)(Nn - N)));
+    HIPCHK(ctx->rf_eparent.reserve(4 * (size_t)En));
+    HIPCHK(hipMemcpyAsync(ctx->rf_xy.p, ctx->xy.p, 16 * (size_t)N, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->rf_uknown.p, ctx->uknown.p, 2 * (size_t)N, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->rf_uin.p, ctx->uin.p, 16 * (size_t)N, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->rf_fin.p, ctx->fin.p, 16 * (size_t)N, hipMemcpyDeviceToDevice, s));
+    magk::RefinedMesh out = {ctx->rf_xy.as<double>(), ctx->rf_conn.as<int32_t>(), ctx->rf_uknown.as<uint8_t>(), ctx->rf_uin.as<double>(),
+                             ctx->rf_fin.as<double>(), ctx->rf_nparents.as<int32_t>(), ctx->rf_eparent.as<int32_t>()};
+    magk::refine_emit(t, out, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    const int64_t info[8] = {Nn, En, (int64_t)counters[magk::RF_MARKED], Nn - N, sweeps, (int64_t)counters[magk::RF_SPLIT2],
+                             (int64_t)counters[magk::RF_SPLIT3], (int64_t)counters[magk::RF_SPLIT4]};
+    memcpy(ctx->rf_info, info, sizeof info);
+    ctx->rf_have = true;
+    return MAG_OK;
+}
+
+int mag_get_refine_info(const mag_ctx *ctx, int64_t info[8])
+{
+    if (int rc = refined_refused(ctx, info, "info", "mag_get_refine_info")) return rc;
+    memcpy(info, ctx->rf_info, sizeof ctx->rf_info);
+    return MAG_OK;
+}
+
+int mag_download_refine(mag_ctx *ctx, mag_refined *o)
+{
+    if (int rc = refined_refused(ctx, o, "refined mesh", "mag_download_refine")) return rc;
+    if (int rc = enter(ctx)) return rc;
+    const hipMemcpyKind kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    hipStream_t s = ctx->stream;
+    const size_t Nn = (size_t)ctx->rf_info[0], En = (size_t)ctx->rf_info[1], added = (size_t)ctx->rf_info[3];
+    if (o->xy) HIPCHK(hipMemcpyAsync(o->xy, ctx->rf_xy.p, 16 * Nn, kind, s));
+    if (o->conn) HIPCHK(hipMemcpyAsync(o->conn, ctx->rf_conn.p, 12 * En, kind, s));
+    if (o->u_known) HIPCHK(hipMemcpyAsync(o->u_known, ctx->rf_uknown.p, 2 * Nn, kind, s));
+    if (o->u_in) HIPCHK(hipMemcpyAsync(o->u_in, ctx->rf_uin.p, 16 * Nn, kind, s));
+    if (o->f_in) HIPCHK(hipMemcpyAsync(o->f_in, ctx->rf_fin.p, 16 * Nn, kind, s));
+    if (o->node_parents && added) HIPCHK(hipMemcpyAsync(o->node_parents, ctx->rf_nparents.p, 8 * added, kind, s));
+    if (o->elem_parent) HIPCHK(hipMemcpyAsync(o->elem_parent, ctx->rf_eparent.p, 4 * En, kind, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
+// The refined mesh through mag_upload itself, its arrays read where they lie: what mag_upload does to the context is done, and
+// only the refinement's arrays, which it drops, are held again
+int mag_upload_refined(mag_ctx *ctx)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!ctx->have_problem || !ctx->rf_have) return fail(ctx, MAG_ERR_STATE, "mag_upload_refined before a completed mag_run_refine");
+    mag_problem p = {};
+    p.num_nodes = ctx->rf_info[0];
+    p.num_elements = ctx->rf_info[1];
+    p.xy = ctx->rf_xy.as<double>();
+    p.conn = ctx->rf_conn.as<int32_t>();
+    p.u_known = ctx->rf_uknown.as<uint8_t>();
+    p.u_in = ctx->rf_uin.as<double>();
+    p.f_in = ctx->rf_fin.as<double>();
+    p.youngs_modulus = ctx->youngs;
+    p.poisson_ratio = ctx->nu;
+    p.part_thickness = ctx->thick;
+    p.memory = MAG_MEM_DEVICE;
+    if (int rc = mag_upload(ctx, &p)) return rc;
+    ctx->rf_have = true;
     return MAG_OK;
 }
 

@@ -509,8 +509,95 @@ class Context:
         self.run_stress(set)
         return [self.download_stress(set, i) for i in range(self._members(set))]
 
+    # -- adaptive mesh refinement: longest-edge bisection with conformity closure of the uploaded mesh -----------------
+    REFINE_RULES = {"marks": _lib.MAG_REFINE_MARKS, "max_fraction": _lib.MAG_REFINE_MAX_FRACTION, "top_fraction": _lib.MAG_REFINE_TOP_FRACTION}
+    REFINE_INFO = ("nodes", "elements", "marked", "marked_edges", "sweeps", "split2", "split3", "split4")
+
+    def run_refine(self, marks=None, indicator=None, rule="top_fraction", theta=0.2, split=1):
+        """mag_run_refine on the uploaded mesh: solves nothing.  marks (E, nonzero: marked) selects rule "marks" whatever
+        `rule` says; otherwise `rule` is "top_fraction" or "max_fraction" of `indicator` (E values, finite and >= 0), or of the
+        device-resident eta2 of the last run_stress("run") when indicator is None."""
+        if marks is not None:
+            rule = "marks"
+        if rule not in self.REFINE_RULES:
+            raise MagnetiteError("Solver", f"refine: rule must be one of {sorted(self.REFINE_RULES)}")
+        keep = []
+        o = _lib.RefineOptions(self.REFINE_RULES[rule], int(split), float(theta), None, None, MAG_MEM_HOST, 0)
+        for name, a, dtype in (("marks", marks, np.uint8), ("indicator", indicator, np.float64)):
+            if a is None:
+                continue
+            a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+            if a.size != self.E:
+                raise MagnetiteError("Solver", f"refine: {name} must have num_elements entries")
+            keep.append(a)
+            setattr(o, name, a.ctypes.data)
+        self._check(self._L.mag_run_refine(self._h, C.byref(o)))
+
+    def refine_info(self):
+        """dict(nodes, elements: N', E' of the refined mesh; marked: elements marked before the closure; marked_edges = N' - N;
+        sweeps of the closure; split2, split3, split4: elements split in two, three, four)."""
+        info = (C.c_int64 * 8)()
+        self._check(self._L.mag_get_refine_info(self._h, info))
+        return dict(zip(self.REFINE_INFO, info))
+
+    def download_refine(self):
+        """dict(xy (N', 2), conn (E', 3), u_known, u_in, f_in (2N'), node_parents (N' - N, 2): lo, hi of the edge a new node
+        halves; elem_parent (E')) of the last run_refine()."""
+        info = self.refine_info()
+        Nn, En, added = info["nodes"], info["elements"], info["marked_edges"]
+        xy, conn = np.empty((Nn, 2)), np.empty((En, 3), dtype=np.int32)
+        known, u_in, f_in = np.empty(2 * Nn, dtype=np.uint8), np.empty(2 * Nn), np.empty(2 * Nn)
+        nparents, eparent = np.empty((added, 2), dtype=np.int32), np.empty(En, dtype=np.int32)
+        o = _lib.Refined(xy.ctypes.data, conn.ctypes.data, known.ctypes.data, u_in.ctypes.data, f_in.ctypes.data,
+                         nparents.ctypes.data if added else None, eparent.ctypes.data, MAG_MEM_HOST, 0)
+        self._check(self._L.mag_download_refine(self._h, C.byref(o)))
+        return dict(xy=xy, conn=conn, u_known=known, u_in=u_in, f_in=f_in, node_parents=nparents, elem_parent=eparent)
+
+    def upload_refined(self):
+        """mag_upload_refined: the refined mesh becomes the uploaded problem, device to device, with the same material -- bit
+        for bit download_refine() followed by upload().  Runs, sets and modes are dropped as upload() drops them."""
+        info = self.refine_info()
+        self._check(self._L.mag_upload_refined(self._h))
+        self.N, self.E = info["nodes"], info["elements"]
+
+    def refine(self, marks=None, indicator=None, rule="top_fraction", theta=0.2, split=1):
+        """run_refine + download_refine: the arrays of the refined mesh and the words of refine_info() by name."""
+        self.run_refine(marks, indicator, rule, theta, split)
+        out = self.download_refine()
+        out.update(self.refine_info())
+        return out
+
+    def adapt(self, prob, rounds=3, theta=0.2, rule="top_fraction", split=1, target_eta_rel=None):
+        """The adaptive loop on a meshgen.Problem with the mesh staying on the device: per round solve -> stress_recovery("run")
+        -> record -> run_refine on the device's eta2 -> upload_refined; after the last refinement a final solve and recovery.
+        Stops early once eta_rel <= target_eta_rel.  Returns dict(history: per solve dict(nodes, elements, eta, eta_rel,
+        iterations), rounds + 1 entries unless stopped early; problem: the final mesh and boundary data as a meshgen.Problem;
+        result: solve()'s dict for it; recovery: its stress_recovery("run")[0])."""
+        from .meshgen import Mesh, Problem
+        self.upload_problem(prob)
+        history = []
+        for r in range(int(rounds) + 1):
+            self.run()
+            field = self.stress_recovery("run")[0]
+            history.append(dict(nodes=self.N, elements=self.E, eta=field["eta"], eta_rel=field["eta_rel"], iterations=self.stats()["iterations"]))
+            if r == rounds or (target_eta_rel is not None and field["eta_rel"] <= target_eta_rel):
+                break
+            self.run_refine(rule=rule, theta=theta, split=split)
+            self.upload_refined()
+        u, f, s = self.download()
+        result = dict(u=u, f=f, stress=s)
+        result.update(self.stats())
+        if len(history) > 1:
+            m = self.download_refine()
+            name = getattr(prob.mesh, "name", "mesh") + "_adapted"
+            final = Problem(Mesh(m["xy"], m["conn"], name), m["u_known"], m["u_in"], m["f_in"], prob.youngs_modulus,
+                            prob.poisson_ratio, prob.part_thickness)
+        else:
+            final = prob
+        return dict(history=history, problem=final, result=result, recovery=field)
+
     # -- modal analysis: the lowest natural frequencies and mode shapes of the uploaded part ------------
-    MODAL_INFO = ("modes", "subspace", "outer", "converged", "vectors_per_launch", "launches", "redone")
+    MODAL_INFO =("modes", "subspace", "outer", "converged", "vectors_per_launch", "launches", "redone")
 
     def run_modal(self, modes=6, density=None, subspace=0, tol=0.0, cg_tol=0.0, max_outer=0, lumped=False, allow_not_converged=False):
         """mag_run_modal on the uploaded problem (no run needed): subspace iteration for the `modes` lowest pairs of

@@ -7,7 +7,7 @@
 //   * MSH-4 ASCII           mesher.rs:536-704   + check_ccw with its `< 1.0` quirk (mesher.rs:522-526)
 //   * nodes.csv/elements.csv post_processor.rs:18-83, floats as Rust's `{}` prints them
 // Usage: magnetite_gpu <input.json> <mesh.msh> [--nodes nodes.csv] [--elements elements.csv] [--dry-run] [--rel TOL]
-//                      [--stress-recovery] [--modal P --density RHO]
+//                      [--stress-recovery] [--modal P --density RHO] [--adapt R [--refine-fraction T] [--refine-split 1|3]]
 //   --dry-run  stop before the solver and print what was parsed (no GPU needed)
 //   --rel TOL  stop CG on relative residual TOL instead of the reference's absolute 1e-4
 //   --modal P --density RHO  also print "info: mode k frequency F Hz residual R" for the P lowest modes and write modes.csv
@@ -15,6 +15,11 @@
 //   --stress-recovery  also write nodes_stress.csv (id,sx,sy,txy,vm) and elements_stress.csv (id,sx,sy,txy,vm,eta2) next to the
 //              two files -- solver::stress_recovery: the tensor per element, the nodal field, the ZZ error indicator -- and
 //              print eta_rel; without it nothing changes
+//   --adapt R  the adaptive loop of solver::upload_refined instead of the one solve: R times solve -> stress recovery -> refine
+//              the T (default 0.2) of the elements with the largest ZZ indicator by longest-edge bisection (--refine-split 3:
+//              all three edges of a marked element) -> upload, on the device, then the final solve; prints "info: adapt round r:
+//              N nodes, E elements, eta_rel X" per solve, and the two files (and what the other flags write) are the FINAL
+//              mesh's; without it nothing changes
 #include <charconv>
 #include <cstdio>
 #include <cstdlib>
@@ -383,14 +388,17 @@ int main(int argc, char **argv)
 {
     std::string input, mesh, nodes_out = "nodes.csv", elements_out = "elements.csv";
     bool dry = false, recover = false;
-    int modal_modes = 0;
-    double rel = 0.0, density = 0.0;
+    int modal_modes = 0, adapt = 0, refine_split = 1;
+    double rel = 0.0, density = 0.0, refine_fraction = 0.2;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--dry-run") dry = true;
         else if (a == "--stress-recovery") recover = true;
         else if (a == "--modal" && i + 1 < argc) modal_modes = std::atoi(argv[++i]);
         else if (a == "--density" && i + 1 < argc) density = std::atof(argv[++i]);
+        else if (a == "--adapt" && i + 1 < argc) adapt = std::atoi(argv[++i]);
+        else if (a == "--refine-fraction" && i + 1 < argc) refine_fraction = std::atof(argv[++i]);
+        else if (a == "--refine-split" && i + 1 < argc) refine_split = std::atoi(argv[++i]);
         else if (a == "--nodes" && i + 1 < argc) nodes_out = argv[++i];
         else if (a == "--elements" && i + 1 < argc) elements_out = argv[++i];
         else if (a == "--rel" && i + 1 < argc) rel = std::atof(argv[++i]);
@@ -399,10 +407,12 @@ int main(int argc, char **argv)
         else die({MagnetiteError::Input, "Unrecognized argument " + a});
     }
     if (input.empty() || mesh.empty()) {
-        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery] [--modal P --density RHO]\n");
+        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery] [--modal P --density RHO] [--adapt R [--refine-fraction T] [--refine-split 1|3]]\n");
         return 2;
     }
     if (modal_modes < 0 || (modal_modes > 0 && !(density > 0.0))) die({MagnetiteError::Input, "--modal P needs P >= 1 and --density RHO > 0"});
+    if (adapt < 0 || !(refine_fraction > 0.0 && refine_fraction <= 1.0) || (refine_split != 1 && refine_split != 3))
+        die({MagnetiteError::Input, "--adapt R needs R >= 0, --refine-fraction T in (0, 1] and --refine-split 1 or 3"});
     // mesher::run (mesher.rs:939-974) minus geometry parsing and the gmsh subprocess
     const std::string text = slurp(input, MagnetiteError::Input, "Unable to open input file " + input);
     JsonParser jp(text);
@@ -444,8 +454,19 @@ int main(int argc, char **argv)
         opt.stop_mode = MAG_STOP_REL;
         opt.tol = rel;
     }
-    const std::vector<Node> posed = recover || modal_modes > 0 ? nodes : std::vector<Node>();  // (run() fills every value in)
-    if (Result err = solver::run(nodes, elements, meta, &opt)) die(*err);
+    std::vector<Node> posed = recover || modal_modes > 0 ? nodes : std::vector<Node>();  // (run() fills every value in)
+    if (adapt > 0) {
+        RefineSpec spec;
+        spec.theta = refine_fraction;
+        spec.split = refine_split;
+        std::vector<AdaptRound> history;
+        if (Result err = solver::upload_refined(nodes, elements, meta, spec, adapt, history, &opt, &posed)) die(*err);
+        for (size_t r = 0; r < history.size(); ++r)
+            std::printf("info: adapt round %zu: %zu nodes, %zu elements, eta_rel %s\n", r, history[r].nodes, history[r].elements,
+                        rust_display(history[r].eta_rel).c_str());
+    } else if (Result err = solver::run(nodes, elements, meta, &opt)) {
+        die(*err);
+    }
     // post_processor::csv_output (main.rs:69); the matplotlib plot (main.rs:72) is not part of this tool
     csv_output(elements, nodes, nodes_out, elements_out);
     if (recover) {
