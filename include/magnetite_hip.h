@@ -43,7 +43,9 @@ extern "C" {
                              stays 4, and a caller detects the feature by the presence of those symbols (dlsym); design
                              variants (mag_set_variants ... mag_get_variants_info), sensitivities (mag_run_sensitivities,
                              mag_download_sensitivity), adjoint sensitivities (mag_run_adjoint ... mag_get_adjoint_info) and
-                             mesh refinement (mag_run_refine ... mag_upload_refined) likewise */
+                             mesh refinement (mag_run_refine ... mag_upload_refined), the element stiffness field
+                             (mag_set_element_scale) and the density design update (mag_design_init ... mag_download_design)
+                             likewise */
 
 /* solver.rs:17-19 */
 #define MAG_DOF 2
@@ -611,7 +613,7 @@ int mag_get_modal_stats(const mag_ctx *ctx, int32_t j, mag_stats *stats);
  *   download or mag_upload_refined before mag_run_refine.
  * Out of scope: refinement across ranks; of load-case or variant sets (the uploaded mesh and MAG_SET_RUN's indicator only);
  *   coarsening; snapping new boundary nodes to curved geometry (the model carries none); prolonging u as a starting guess (the
- *   solver takes none); per-element material fields. */
+ *   solver takes none); carrying an element stiffness field over to the refined mesh (mag_upload_refined clears it). */
 enum mag_refine_rule { MAG_REFINE_MARKS = 0, MAG_REFINE_MAX_FRACTION = 1, MAG_REFINE_TOP_FRACTION = 2 };
 typedef struct mag_refine_options {
     int32_t rule;            /* enum mag_refine_rule */
@@ -635,6 +637,94 @@ int mag_get_refine_info(const mag_ctx *ctx, int64_t info[8]);
 int mag_download_refine(mag_ctx *ctx, mag_refined *out);
 int mag_upload_refined(mag_ctx *ctx);
 
+/* ---- element stiffness field: a relative stiffness scale per element of the uploaded mesh ----
+ * What a thickness field, a damaged region and a density (topology) method need: K = sum_e s_e K_e with K_e the reference's
+ * element matrix (solver.rs:263-278) of the uploaded E, nu and thickness.  It is what mag_adjoint.delem differentiates.
+ * mag_set_element_scale: after mag_upload.  scale: E values in `memory`, every one finite and > 0 (checked on the device:
+ *   MAG_ERR_BAD_ARGS with the first offender named in mag_last_error, the field as it was); NULL clears the field, and the context
+ *   computes bit for bit what it computed without one.
+ *   Assembly: every contribution of element e to K is the value computed without a field, multiplied once by s_e, then added in
+ *   the order it is added without a field (both assembly kernels carry the field as a template flag; without a field the
+ *   kernels of a context without one run).  A field of all ones gives K bit for bit.
+ *   What follows K follows the field: the right-hand side and the reactions (K's rows), mag_assemble_csr and mag_reduce_system
+ *   (the scaled K).  mag_element_stiffness returns the UNSCALED K_e.
+ *   Stress: stress_out[e] and MAG_OBJ_STRESS_PNORM stay functions of u, E and nu alone, sigma = D B u_e -- the stress of the
+ *   unscaled material, which is the thickness-field and SIMP reading (a scale stands for less material carrying the same stress).
+ *   CG: while a field is set the CG runs the CSR operator's phase whatever mag_options.cg_operator says (mag_stats.cg_kernel == 3):
+ *   the on-chip kernel's edge blocks assume one material and the matrix-free operators carry no element id.
+ *   Load cases: mag_run_cases works under a field, K assembled once, the cases one after another (mag_get_cases_info: info[1] == 0);
+ *   every case bit for bit mag_upload + mag_set_element_scale + mag_run of it.
+ *   Passes: mag_run_sensitivities, mag_run_adjoint and mag_run_objective work for MAG_SET_RUN and MAG_SET_CASES; every element's term
+ *   carries s_e:  energy[e] = s_e (1/2 u_e^T K_e u_e), hence dPi/ds_e = energy[e] / s_e;  delem[e] = -lambda_e^T (s_e K_e) u_e stays
+ *   the derivative with respect to a RELATIVE scale, hence dJ/ds_e = delem[e] / s_e;  dxy and the scalars are sums of the scaled
+ *   terms (dPi/dE, dPi/dt, dJ/dE, dJ/dt remain W / E ... of the scaled sums).
+ *   Lifetime: mag_upload and mag_upload_refined clear the field.  Setting or clearing it drops the results of mag_run and
+ *   mag_run_cases and everything derived from them; the Hilbert order, the tables and the CSR pattern of the first run under a
+ *   field are kept by the runs that follow (mag_stats.ms_order == ms_csr_symbolic == 0 for them).
+ * Refused with MAG_ERR_STATE before any HIP call, the message naming the field: while a field is set mag_set_variants,
+ *   mag_run_variants, mag_run_modal, mag_run_stress, mag_run_refine, mag_apply_operator, mag_time_operator, mag_time_spmv, and the
+ *   passes and their downloads for MAG_SET_VARIANTS (variants solved before the field was set carry none: their results stay and
+ *   are readable again once the field is cleared); a field on a context
+ *   with a communicator of more than one rank, assemble_csr = 0, precision = 1 or a preconditioner; mag_set_element_scale before
+ *   mag_upload.  MAG_ERR_BAD_ARGS for a `memory` that is none of enum mag_memory (here and in mag_design_init, mag_design_step,
+ *   mag_download_design). */
+int mag_set_element_scale(mag_ctx *ctx, const double *scale /* E, or NULL: clear */, int32_t memory);
+
+/* ---- density design update on the device: SIMP interpolation, a mesh-based density filter, the optimality-criteria update ----
+ * mag_run -> mag_run_sensitivities -> mag_design_step -> mag_run ... iterates with the design never leaving the device; the order,
+ * the tables and the CSR pattern are built once.  a_e is the signed area of element e (an element of area <= 0 is refused with
+ * MAG_ERR_BAD_ARGS and named, as mag_run_modal does), P = filter_passes, p = penal.  Every sum has a fixed order (no floating-point
+ * atomics): a repeat gives the same bits.
+ *   filter F      n_i = (sum_{e in i} a_e x_e) / A_i,  A_i = sum_{e in i} a_e, both in the order of node i's incidence list;
+ *                 (F x)_e = ((n_a + n_b) + n_c) / 3 with a, b, c in conn order: a one-ring radius on the tables stress recovery
+ *                 averages over, no neighbour search;
+ *   transpose     m_i = sum_{e in i} y_e / 3;  (F^T y)_e = a_e ((m_a / A_a + m_b / A_b) + m_c / A_c);
+ *   interpolation rho~ = F^P rho,  s = scale_min + (1 - scale_min) rho~^p (repeated multiplication, no pow());
+ *   chain rule    dJ/drho~_e = dJ/ds_e (1 - scale_min) p rho~_e^(p - 1),  dJ/drho = (F^T)^P dJ/drho~;
+ *   volume        w = (F^T)^P a, once at init: the filtered volume sum_e a_e rho~_e is sum_e w_e rho_e, so the bisection filters
+ *                 nothing;  target V* = volume_fraction sum_e a_e;
+ *   OC update     Bq_e = max(-dJ/drho_e, 0) / w_e,
+ *                 rho_new(L) = min(min(1, rho + move), max(max(rho_min, rho - move), rho sqrt(Bq / L)))  (fmin / fmax: where Bq / L
+ *                 is 0 / 0 the lower limit stands),   V(L) = sum_e w_e rho_new_e(L);
+ *   bisection     lo = 0, hi = max_e Bq_e / rho_min^2; exactly 100 times mid = 0.5 (lo + hi), lo = mid if V(mid) > V* else hi = mid;
+ *                 the result is rho_new(0.5 (lo + hi)).  The bracket lives on the device: no read-back between the steps.
+ * mag_design_init: after mag_upload.  rho0: E values in (0, 1] in `memory`, NULL: volume_fraction everywhere.  Stores rho, computes
+ *   rho~ and s and installs s as the context's element scale, device to device, with mag_set_element_scale's effect on the
+ *   context's results.  The scale is installed once everything is checked: a refused init (an element of area <= 0, a rho0
+ *   outside (0, 1]) leaves a field of the caller's and the results under it as they were; a design in progress is ended.
+ * mag_design_step: needs a completed mag_run under the installed scale.  dJ_ds: E values dJ/ds_e in `memory` for any objective (for
+ *   instance delem / s of mag_run_adjoint), or NULL: the stiffest design, J = -2 Pi -- under prescribed forces C = -2 Pi, under
+ *   prescribed displacements C = 2 Pi, so minimising J stiffens the part in both -- with dJ/ds_e = -2 energy[e] / s_e read from the
+ *   device-resident energies of mag_run_sensitivities(MAG_SET_RUN), which it then needs.  Installs the new scale (the run is gone).
+ * mag_get_design_info: info[0] volume fraction reached (sum_e w_e rho_e / sum_e a_e), [1] L, [2] max |rho_new - rho|, [3] greyness
+ *   mean(4 rho~ (1 - rho~)), [4] 1 if V(lo0) >= V* >= V(hi0) (the target was reachable within the move limits), else 0 -- the step
+ *   still returns MAG_OK with the nearest reachable design --, [5] steps since init, [6] J of the step (0 with a caller's gradient),
+ *   [7] 0.  After mag_design_init: [0] and [3] of the start, the rest 0.
+ * mag_download_design: NULL members are skipped; dJ_drho of the last step (zeros before the first).
+ * mag_upload ends the design, and so does a mag_set_element_scale of the caller's.
+ * Errors, before any HIP call: MAG_ERR_BAD_ARGS for null options / info / design and options outside their ranges; MAG_ERR_STATE
+ *   for mag_design_init before mag_upload or on a context a field is refused on, mag_design_step before mag_design_init, before a
+ *   completed mag_run, or with a NULL gradient before mag_run_sensitivities, and for info or download before mag_design_init.
+ * Out of scope: the on-chip and fused CG under a field; fields for variants, modal analysis, stress recovery and refinement; more
+ *   than one rank; non-integer penal, continuation schedules, MMA; passing delem to mag_design_step without a host round trip. */
+typedef struct mag_design_options {
+    double volume_fraction;   /* (0, 1] */
+    double scale_min;         /* (0, 1), e.g. 1e-3 */
+    double rho_min;           /* (0, 1) */
+    double move;              /* (0, 1] */
+    int32_t penal;            /* 1..8: rho^p by repeated multiplication, no pow() */
+    int32_t filter_passes;    /* 0..8 */
+    int32_t reserved[2];
+} mag_design_options;         /* 48 bytes */
+typedef struct mag_design {
+    double *rho_out, *rho_filtered_out, *scale_out, *dJ_drho_out; /* E each, NULL: skipped */
+    int32_t memory, reserved;
+} mag_design;                 /* 40 bytes */
+int mag_design_init(mag_ctx *ctx, const mag_design_options *opt, const double *rho0 /* NULL: volume_fraction everywhere */, int32_t memory);
+int mag_design_step(mag_ctx *ctx, const double *dJ_ds /* E, or NULL: stiffness */, int32_t memory);
+int mag_get_design_info(const mag_ctx *ctx, double info[8]);
+int mag_download_design(mag_ctx *ctx, const mag_design *out);
+
 /* ---- pieces of the path, exposed for parity tests -------------------- */
 /* solver.rs:187-193 compute_element_area (pub; the mesher imports it, mesher.rs:9,523). Host-side. */
 double mag_compute_element_area(const double *xy, const int32_t *tri);
@@ -642,9 +732,11 @@ double mag_compute_element_area(const double *xy, const int32_t *tri);
 void mag_compute_strain_displacement_matrix(const double *xy, const int32_t *tri, double element_area, double *B);
 /* solver.rs:240-250 compute_stress_strain_matrix (pub): D[9], 3x3 row major, plane stress. */
 void mag_compute_stress_strain_matrix(double poisson_ratio, double youngs_modulus, double *D);
-/* solver.rs:263-278 for every element of the uploaded problem: ke_out[36E] host, row-major 6x6. */
+/* solver.rs:263-278 for every element of the uploaded problem: ke_out[36E] host, row-major 6x6.  Under an element stiffness field:
+ * the UNSCALED K_e. */
 int mag_element_stiffness(mag_ctx *ctx, double *ke_out);
-/* solver.rs:290-331: K (2N x 2N) in CSR, ascending columns, structural pattern.
+/* solver.rs:290-331: K (2N x 2N) in CSR, ascending columns, structural pattern (under an element stiffness field: the scaled K,
+ * here and in mag_reduce_system).
  * Call once with all outputs NULL to get nnz, then with host buffers rowptr[2N+1], col[nnz], val[nnz]. */
 int mag_assemble_csr(mag_ctx *ctx, int64_t *nnz, int32_t *rowptr, int32_t *col, double *val);
 /* The same for variant v of mag_set_variants (test only): K of that variant's coordinates and material in the pattern of the

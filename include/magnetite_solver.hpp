@@ -118,6 +118,40 @@ struct AdaptRound {
     std::int64_t iterations = 0;
 };
 
+// The options of solver::design_init (include/magnetite_hip.h, mag_design_options); rho0: E start densities in (0, 1], or empty:
+// volume_fraction everywhere.
+struct DesignSpec {
+    double volume_fraction = 0.5, scale_min = 1e-3, rho_min = 1e-3, move = 0.2;
+    std::int32_t penal = 3, filter_passes = 1;
+    std::vector<double> rho0;
+};
+
+// mag_get_design_info's words by name.
+struct DesignInfo {
+    double volume_fraction = 0, lagrange = 0, change = 0, greyness = 0, J = 0;
+    bool reachable = false;
+    std::int64_t steps = 0;
+};
+
+// What solver::download_design returns: the outputs of mag_download_design, E values each.
+struct Design {
+    std::vector<double> rho, rho_filtered, scale, dJ_drho;
+};
+
+// A part kept on the device under an element stiffness field, between the calls of solver::set_element_scale, design_init,
+// design_step, design_info and download_design.  Owns the context: it goes with this object on every path.
+struct FieldSession {
+    mag_ctx *ctx = nullptr;
+    std::size_t N = 0, E = 0;
+    FieldSession() = default;
+    FieldSession(const FieldSession &) = delete;
+    FieldSession &operator=(const FieldSession &) = delete;
+    ~FieldSession()
+    {
+        if (ctx) mag_destroy(ctx);
+    }
+};
+
 // The options of solver::modal (include/magnetite_hip.h, mag_modal_options); 0: the library's default.
 struct ModalSpec {
     std::int32_t modes = 6, subspace = 0, max_outer = 0;
@@ -806,6 +840,133 @@ inline Result upload_refined(std::vector<Node> &nodes, std::vector<Element> &ele
     detail::store_values(nodes, u, f);
     for (std::size_t e = 0; e < E; ++e) elements[e].stress = stress[e];
     return std::nullopt;
+}
+
+namespace detail {
+
+// the part of `nodes` and `elements` uploaded into a fresh context of the session
+inline Result open_session(FieldSession &session, const std::vector<Node> &nodes, const std::vector<Element> &elements,
+                           const ModelMetadata &model_metadata, const mag_options *options)
+{
+    const std::size_t N = nodes.size();
+    std::vector<double> xy, u_in(2 * N), f_in(2 * N);
+    std::vector<std::uint8_t> u_known;
+    std::vector<std::int32_t> conn;
+    if (Result e = flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
+    if (Result e = flatten_elements(elements, N, conn)) return e;
+    if (session.ctx) mag_destroy(session.ctx);
+    session.ctx = mag_create(options);
+    if (!session.ctx) return solver_error("mag_create failed");
+    session.N = N;
+    session.E = elements.size();
+    const mag_problem p = host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
+    return mag_upload(session.ctx, &p) != MAG_OK ? solver_error(mag_last_error(session.ctx)) : std::nullopt;
+}
+
+}  // namespace detail
+
+// NOTE on names: like the other functions of this namespace, the five below are whole workflows on a part, not the C entry points
+// of the same name one to one -- and not what the Python methods of the same name do, which ARE the entry points alone:
+// set_element_scale uploads, sets the field AND solves; design_init uploads and starts the design; design_step is one ITERATION
+// (mag_run, mag_run_sensitivities, then mag_design_step).  A caller who wants the single calls has them on session.ctx.
+//
+// Element stiffness field (mag_set_element_scale): the part solved with K = sum_e scale[e] K_e.  The part is uploaded into the
+// session, the field set (E values, finite and > 0) and the part solved; afterwards every node.ux/uy/fx/fy and element.stress
+// holds a value as after run() -- the stress is that of the unscaled material (include/magnetite_hip.h) -- and the session keeps
+// the solved part for what follows (mag_run_sensitivities ... on session.ctx).
+inline Result set_element_scale(FieldSession &session, std::vector<Node> &nodes, std::vector<Element> &elements,
+                                const ModelMetadata &model_metadata, const std::vector<double> &scale, const mag_options *options = nullptr,
+                                mag_stats *stats_out = nullptr)
+{
+    if (scale.size() != elements.size()) return detail::solver_error("element scale: one entry per element is needed");
+    if (Result e = detail::open_session(session, nodes, elements, model_metadata, options)) return e;
+    mag_ctx *ctx = session.ctx;
+    const auto fail = [&]() { return detail::solver_error(mag_last_error(ctx)); };
+    if (mag_set_element_scale(ctx, scale.data(), MAG_MEM_HOST) != MAG_OK || mag_run(ctx) != MAG_OK) return fail();
+    std::vector<double> u(2 * session.N), f(2 * session.N), stress(session.E);
+    mag_result r{};
+    r.u_out = u.data();
+    r.f_out = f.data();
+    r.stress_out = stress.data();
+    r.memory = MAG_MEM_HOST;
+    if (mag_download(ctx, &r) != MAG_OK) return fail();
+    if (stats_out) mag_get_stats(ctx, stats_out);
+    detail::store_values(nodes, u, f);
+    for (std::size_t e = 0; e < session.E; ++e) elements[e].stress = stress[e];
+    return std::nullopt;
+}
+
+// Density design (mag_design_init): the part uploaded into the session and a design started on it -- the densities of spec, their
+// filtered field and its SIMP scale, installed as the part's element scale.
+inline Result design_init(FieldSession &session, const std::vector<Node> &nodes, const std::vector<Element> &elements,
+                          const ModelMetadata &model_metadata, const DesignSpec &spec, const mag_options *options = nullptr)
+{
+    if (!spec.rho0.empty() && spec.rho0.size() != elements.size()) return detail::solver_error("design: rho0 needs one entry per element");
+    if (Result e = detail::open_session(session, nodes, elements, model_metadata, options)) return e;
+    mag_design_options o{};
+    o.volume_fraction = spec.volume_fraction;
+    o.scale_min = spec.scale_min;
+    o.rho_min = spec.rho_min;
+    o.move = spec.move;
+    o.penal = spec.penal;
+    o.filter_passes = spec.filter_passes;
+    if (mag_design_init(session.ctx, &o, spec.rho0.empty() ? nullptr : spec.rho0.data(), MAG_MEM_HOST) != MAG_OK)
+        return detail::solver_error(mag_last_error(session.ctx));
+    return std::nullopt;
+}
+
+// mag_get_design_info by name
+inline Result design_info(const FieldSession &session, DesignInfo &out)
+{
+    double info[8] = {};
+    if (!session.ctx || mag_get_design_info(session.ctx, info) != MAG_OK) return detail::solver_error("design_info before design_init");
+    out.volume_fraction = info[0];
+    out.lagrange = info[1];
+    out.change = info[2];
+    out.greyness = info[3];
+    out.reachable = info[4] != 0.0;
+    out.steps = (std::int64_t)info[5];
+    out.J = info[6];
+    return std::nullopt;
+}
+
+// One iteration of the design loop (mag_run, mag_run_sensitivities, mag_design_step): the part is solved under the design's scale,
+// then the densities take one optimality-criteria step under the volume constraint -- towards the stiffest design (J = -2 Pi) when
+// dJ_ds is null, otherwise along the caller's dJ/ds_e (E values; the caller reads what it needs of the solved part from
+// session.ctx in `objective`, which is called between the solve and the step).  info_out: the step's words; stats_out: the solve's.
+inline Result design_step(FieldSession &session, DesignInfo *info_out = nullptr, mag_stats *stats_out = nullptr,
+                          const std::function<Result(mag_ctx *, std::vector<double> &dJ_ds)> &objective = nullptr)
+{
+    mag_ctx *ctx = session.ctx;
+    if (!ctx) return detail::solver_error("design_step before design_init");
+    const auto fail = [&]() { return detail::solver_error(mag_last_error(ctx)); };
+    if (mag_run(ctx) != MAG_OK) return fail();
+    if (stats_out) mag_get_stats(ctx, stats_out);
+    if (objective) {
+        std::vector<double> dJ_ds(session.E, 0.0);
+        if (Result e = objective(ctx, dJ_ds)) return e;
+        if (mag_design_step(ctx, dJ_ds.data(), MAG_MEM_HOST) != MAG_OK) return fail();
+    } else if (mag_run_sensitivities(ctx, MAG_SET_RUN) != MAG_OK || mag_design_step(ctx, nullptr, MAG_MEM_HOST) != MAG_OK) {
+        return fail();
+    }
+    return info_out ? design_info(session, *info_out) : std::nullopt;
+}
+
+// mag_download_design: the design as it stands
+inline Result download_design(FieldSession &session, Design &out)
+{
+    if (!session.ctx) return detail::solver_error("download_design before design_init");
+    out.rho.assign(session.E, 0.0);
+    out.rho_filtered.assign(session.E, 0.0);
+    out.scale.assign(session.E, 0.0);
+    out.dJ_drho.assign(session.E, 0.0);
+    mag_design d{};
+    d.rho_out = out.rho.data();
+    d.rho_filtered_out = out.rho_filtered.data();
+    d.scale_out = out.scale.data();
+    d.dJ_drho_out = out.dJ_drho.data();
+    d.memory = MAG_MEM_HOST;
+    return mag_download_design(session.ctx, &d) != MAG_OK ? detail::solver_error(mag_last_error(session.ctx)) : std::nullopt;
 }
 
 }  // namespace solver

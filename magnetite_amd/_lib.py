@@ -40,6 +40,7 @@ SYMBOLS = [
     "mag_run_stress", "mag_download_stress",
     "mag_run_modal", "mag_download_modal", "mag_get_modal_info", "mag_get_modal_stats", "mag_apply_mass",
     "mag_run_refine", "mag_get_refine_info", "mag_download_refine", "mag_upload_refined",
+    "mag_set_element_scale", "mag_design_init", "mag_design_step", "mag_get_design_info", "mag_download_design",
     "mag_comm_get_unique_id", "mag_comm_init_rccl", "mag_comm_query", "mag_comm_init_callback", "mag_comm_set_window", "mag_comm_inbox_create", "mag_comm_inbox_open",
 ]
 
@@ -123,6 +124,16 @@ class RefineOptions(C.Structure):
 class Refined(C.Structure):
     _fields_ = [("xy", C.c_void_p), ("conn", C.c_void_p), ("u_known", C.c_void_p), ("u_in", C.c_void_p), ("f_in", C.c_void_p),
                 ("node_parents", C.c_void_p), ("elem_parent", C.c_void_p), ("memory", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DesignOptions(C.Structure):
+    _fields_ = [("volume_fraction", C.c_double), ("scale_min", C.c_double), ("rho_min", C.c_double), ("move", C.c_double),
+                ("penal", C.c_int32), ("filter_passes", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class Design(C.Structure):
+    _fields_ = [("rho_out", C.c_void_p), ("rho_filtered_out", C.c_void_p), ("scale_out", C.c_void_p), ("dJ_drho_out", C.c_void_p),
+                ("memory", C.c_int32), ("reserved", C.c_int32)]
 
 
 HASHED_SOURCES = ("persist.hip", "persist_kernel.h", "persist_shapes.h", "persist_inst.hip", "cg.hip", "cg_device.h", "exact.hip", "symbolic.hip", "kernels.h")
@@ -222,6 +233,12 @@ def lib():
         L.mag_get_refine_info.argtypes = [vp, C.POINTER(C.c_int64)]
         L.mag_download_refine.argtypes = [vp, C.POINTER(Refined)]
         L.mag_upload_refined.argtypes = [vp]
+    if hasattr(L, "mag_set_element_scale"):  # (likewise: scripts/design_probe.py)
+        L.mag_set_element_scale.argtypes = [vp, dp, C.c_int32]
+        L.mag_design_init.argtypes = [vp, C.POINTER(DesignOptions), dp, C.c_int32]
+        L.mag_design_step.argtypes = [vp, dp, C.c_int32]
+        L.mag_get_design_info.argtypes = [vp, dp]
+        L.mag_download_design.argtypes = [vp, C.POINTER(Design)]
     L.mag_compute_element_area.argtypes = [dp, ip]
     L.mag_compute_element_area.restype = C.c_double
     L.mag_compute_strain_displacement_matrix.argtypes = [dp, ip, C.c_double, dp]

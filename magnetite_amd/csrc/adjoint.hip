@@ -51,18 +51,17 @@ __device__ inline const double2 *lambda_of(const AdjointBatch &ab, int64_t v, in
 
 // The node pass: dxy[2i + d] = -(sum over the node's incident triangles, in the order of its incidence list, of the derivative
 // of l_e^T K_e u_e with respect to coordinate d of the node).  Fields: coordinates, u, lambda.
-struct Bilinear {
+struct Bilinear : ScaledCorners {
     double nu, cm;
     double2 *dxy;
-    struct Node {
-        double gx, gy;
-    };
-    __device__ Bilinear(const Member &m, const AdjointBatch &ab)
-        : nu(m.nu), cm(m.youngs * m.thick / (2.0 * (1.0 - m.nu * m.nu))), dxy((double2 *)ab.dxy)
+    __device__ Bilinear(const Member &m, const AdjointBatch &ab, const SensMesh &mesh)
+        : ScaledCorners(m, mesh), nu(m.nu), cm(m.youngs * m.thick / (2.0 * (1.0 - m.nu * m.nu))), dxy((double2 *)ab.dxy)
     {
     }
-    __device__ Node node(int64_t) const { return {0.0, 0.0}; }
-    __device__ void corner(Node &n, const double2 (&f)[3][3], int32_t) const { corner_bilinear(f[0], f[1], f[2], nu, cm, n.gx, n.gy); }
+    __device__ void corner(Node &n, const double2 (&f)[3][3], int32_t k) const
+    {
+        corner_bilinear(f[0], f[1], f[2], nu, factor(n, k, cm), n.gx, n.gy);
+    }
     __device__ void store(const Node &n, int64_t at) const { dxy[at] = make_double2(-n.gx, -n.gy); }
 };
 
@@ -79,7 +78,8 @@ __global__ void __launch_bounds__(256) k_adjoint_elements(const int32_t *conn, i
     load_corners(src, conn, e, 0, f);
     const BilinearState s = bilinear_state(f[0], f[1], f[2]);
     const double Qb = bilinear_Q(s, m.nu), om = 1.0 - m.nu * m.nu;
-    const double k = m.youngs * m.thick / (2.0 * s.A2);
+    double k = m.youngs * m.thick / (2.0 * s.A2);
+    if (m.scale) k *= m.scale[e];
     ab.delem[v * E + e] = -(k * Qb / om);
     // d/dnu of Qb / (1 - nu^2)
     ab.nuterm[v * E + e] = k * (((s.pl * s.qu + s.ql * s.pu) - 0.5 * s.rl * s.ru) / om + 2.0 * m.nu * Qb / (om * om));
@@ -92,7 +92,7 @@ __global__ void __launch_bounds__(256) k_adjoint_nodes_tile(SensMesh mesh, Adjoi
     extern __shared__ __attribute__((aligned(16))) double2 s_img[];
     const Member m = member_of(ab, blockIdx.y, mesh.N);
     const double2 *const src[3] = {m.xy, m.u, lambda_of(ab, blockIdx.y, mesh.N)};
-    tile_walk(mesh, src, s_img, Bilinear(m, ab));
+    tile_walk(mesh, src, s_img, Bilinear(m, ab, mesh));
 }
 
 // ---- ... or gathered from memory
@@ -100,7 +100,7 @@ __global__ void __launch_bounds__(256) k_adjoint_nodes(SensMesh mesh, AdjointBat
 {
     const Member m = member_of(ab, blockIdx.y, mesh.N);
     const double2 *const src[3] = {m.xy, m.u, lambda_of(ab, blockIdx.y, mesh.N)};
-    gather_walk(mesh, src, Bilinear(m, ab));
+    gather_walk(mesh, src, Bilinear(m, ab, mesh));
 }
 
 // ---- 3. per DOF: dJ/df_in = lambda on a free DOF, dJ/du_in = g - (K lambda) on a prescribed one

@@ -27,6 +27,7 @@
 #include "modal.h"
 #include "modal_host.h"
 #include "objective.h"
+#include "design.h"
 #include "recover.h"
 #include "refine.h"
 #include "sens.h"
@@ -302,6 +303,19 @@ struct mag_ctx {
     bool rf_have = false;
     int64_t rf_info[8] = {};
 
+    // element stiffness field (mag_set_element_scale): E relative scales on the device while field_on.  field_sym: the order, the
+    // tables and the CSR pattern held now were built under this field (with the CSR operator's choices) and a run keeps them
+    DevBuf escale;
+    bool field_on = false, field_sym = false;
+
+    // density design (mag_design_init / mag_design_step): the densities, the filter's tables and the update's scratch; the
+    // bracket, the sums and the info words live on the device between the launches of a step
+    bool design_on = false;
+    mag_design_options design_opt = {};
+    int64_t design_steps = 0;
+    double design_info[8] = {};
+    DevBuf ds_rho, ds_rhof, ds_w, ds_area, ds_node_area, ds_node, ds_tmp, ds_dJ, ds_dJdrho, ds_bq, ds_rho_new, ds_part, ds_small;
+
     magc::Comm comm;
 };
 
@@ -336,6 +350,39 @@ int enter(mag_ctx *ctx)
 
 // K is assembled: asked for, or the CG operator is its CSR
 inline bool wants_csr(const mag_ctx *ctx) { return ctx->opt.assemble_csr != 0 || ctx->opt.cg_operator == MAG_OP_CSR; }
+
+// ---- the element stiffness field (mag_set_element_scale)
+// what does not honour a field refuses it by name, before any HIP call
+int field_refuses(mag_ctx *ctx, const char *fn)
+{
+    return fail(ctx, MAG_ERR_STATE, "%s: not available while an element stiffness field is set (mag_set_element_scale; NULL clears it)", fn);
+}
+
+// the contexts a field cannot be set on, or run under: again before any HIP call
+int field_context_refused(mag_ctx *ctx, const char *fn)
+{
+    const char *why = ctx->comm.nranks > 1            ? "a communicator of more than one rank"
+                      : ctx->opt.assemble_csr == 0    ? "assemble_csr = 0 (the field lives in the assembled K)"
+                      : ctx->opt.precision == 1       ? "precision = 1 (the fp32 leg is matrix-free)"
+                      : ctx->opt.preconditioner != 0  ? "a preconditioner (it needs the fused matrix-free iteration)"
+                                                      : nullptr;
+    return why ? fail(ctx, MAG_ERR_STATE, "%s: an element stiffness field does not work with %s", fn, why) : MAG_OK;
+}
+
+// While a field is set the CG runs the CSR operator's phase whatever mag_options.cg_operator says (the on-chip kernel's edge
+// blocks and the matrix-free operators assume one material): the option reads MAG_OP_CSR for the length of a call.
+struct FieldOperator {
+    mag_ctx *ctx;
+    const int32_t cg_operator;
+    // (force: mag_design_init builds the order of the field it is about to install)
+    explicit FieldOperator(mag_ctx *c, bool force = false) : ctx(c), cg_operator(c->opt.cg_operator)
+    {
+        if (ctx->field_on || force) ctx->opt.cg_operator = MAG_OP_CSR;
+    }
+    ~FieldOperator() { ctx->opt.cg_operator = cg_operator; }
+};
+inline const double *field_of(const mag_ctx *ctx) { return ctx->field_on ? ctx->escale.as<double>() : nullptr; }
+inline bool memory_known(int32_t memory) { return memory == MAG_MEM_HOST || memory == MAG_MEM_DEVICE; }
 
 int scratch_for(mag_ctx *ctx, size_t bytes)
 {
@@ -913,13 +960,13 @@ int gather_phase(mag_ctx *ctx)
                                      ctx->ell_asm.as<uint32_t>(), ctx->ell_pos.as<uint16_t>(),
                                      ctx->inc_off.as<int32_t>(), ctx->inc.as<uint32_t>(),
                                      ctx->conn.as<int32_t>(), ctx->xy.as<double>(), ctx->N, ctx->B, ctx->T, ctx->cap,
-                                     ctx->nu, ctx->youngs, ctx->thick, ctx->kval.as<double>(), ctx->stream)) {
+                                     ctx->nu, ctx->youngs, ctx->thick, ctx->kval.as<double>(), field_of(ctx), ctx->stream)) {
         // assembled from the CG tiles (coordinates and caller ids staged in LDS)
     } else {
         magk::assemble_tiles(ctx->bcol.as<int32_t>(), ctx->bptr.as<int32_t>(), ctx->inc_off.as<int32_t>(),
                              ctx->inc.as<uint32_t>(), ctx->perm.as<uint32_t>(), ctx->conn.as<int32_t>(),
                              ctx->xy.as<double>(), ctx->N, ctx->nu, ctx->youngs, ctx->thick, ctx->kval.as<double>(),
-                             ctx->stream);
+                             field_of(ctx), ctx->stream);
     }
     HIPCHK(hipGetLastError());
     return MAG_OK;
@@ -954,11 +1001,16 @@ int ensure_full_order(mag_ctx *ctx)
 int ensure_csr(mag_ctx *ctx)
 {
     if (ctx->have_csr && ctx->csr_full) return MAG_OK;
+    FieldOperator op(ctx);
     if (int rc = ensure_full_order(ctx)) return rc; // validates conn
-    ctx->want_full_csr = true;
-    int rc = csr_symbolic(ctx);
-    ctx->want_full_csr = false;
-    if (rc) return rc;
+    int rc = MAG_OK;
+    if (!(ctx->field_on && ctx->field_sym)) { // (under a field the pattern of its first run stays)
+        ctx->want_full_csr = true;
+        rc = csr_symbolic(ctx);
+        ctx->want_full_csr = false;
+        if (rc) return rc;
+        ctx->field_sym = ctx->field_on;
+    }
     if ((rc = gather_phase(ctx))) return rc;
     ctx->have_csr = true;
     return MAG_OK;
@@ -2226,7 +2278,11 @@ void drop_derived(mag_ctx *ctx, int32_t slot)
 void begin_run(mag_ctx *ctx)
 {
     ctx->stats = {};
-    ctx->have_order = ctx->have_csr = ctx->have_run = false;
+    // (under an element stiffness field the order, the tables and the pattern of the field's first run are kept: a design
+    // iteration changes the values of K only)
+    ctx->have_order = ctx->field_on && ctx->field_sym && ctx->have_order;
+    ctx->field_sym = ctx->have_order;
+    ctx->have_csr = ctx->have_run = false;
     drop_derived(ctx, MAG_SET_RUN); // (the single-case results go with every run, a set's included)
     // a context whose on-chip kernel once found the GPU shared is not condemned to stream for ever: after a number of
     // streamed solves (8, doubling per failure) it tries again -- at worst one more spin budget (~0.3 s).  Across ranks
@@ -2270,6 +2326,7 @@ int mag_upload(mag_ctx *ctx, const mag_problem *p)
     ctx->thick = p->part_thickness;
     ctx->have_problem = true;
     ctx->have_order = ctx->have_csr = ctx->have_run = false;
+    ctx->field_on = ctx->field_sym = ctx->design_on = false; // the field and the design belong to the mesh they were given for
     ctx->sens_tab_ready = false;
     ctx->cases.reset();
     ctx->variants.reset();
@@ -2284,10 +2341,14 @@ int mag_run(mag_ctx *ctx)
 {
     if (int rc = enter(ctx)) return rc;
     if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "mag_run before mag_upload");
+    if (ctx->field_on)
+        if (int rc = field_context_refused(ctx, "mag_run")) return rc;
+    FieldOperator field_op(ctx);
     hipStream_t s = ctx->stream;
     const int64_t N = ctx->N, E = ctx->E;
     mag_stats &st = ctx->stats;
     begin_run(ctx);
+    const bool kept_sym = ctx->field_sym; // the order and the pattern are those of an earlier run under this field
 
     HIPCHK(hipEventRecord(ctx->ev[0], s));
     ctx->order_allow_shard = true; // (every rank of the communicator is in mag_run: the sharded phase's all-reduces are safe)
@@ -2298,7 +2359,9 @@ int mag_run(mag_ctx *ctx)
     if (int rc = reserve_cg(ctx)) return rc;
     const bool csr = wants_csr(ctx);
     if (csr) {
-        if (int rc = csr_symbolic(ctx)) return rc;
+        if (!kept_sym)
+            if (int rc = csr_symbolic(ctx)) return rc;
+        ctx->field_sym = ctx->field_on;
         HIPCHK(hipEventRecord(ctx->ev[2], s)); // (K_e is evaluated inside the row assembly: ms_element is 0 and no event pair is
                                                // spent on it -- an empty pair still costs ~5 us of stream time)
         if (ctx->opt.verbose) printf("info: building total stiffness matrix...\n");
@@ -2310,7 +2373,8 @@ int mag_run(mag_ctx *ctx)
         HIPCHK(hipEventRecord(ctx->ev[2], s));
         HIPCHK(hipEventRecord(ctx->ev[4], s));
     }
-    if (int rc = rhs_phase(ctx, ctx->uin.as<double>(), ctx->fin.as<double>(), ctx->bP.as<double>(), ctx->b_from_order)) return rc;
+    // (a kept order has not written b = 0.0 + f in this run: rhs_untouched writes the same values)
+    if (int rc = rhs_phase(ctx, ctx->uin.as<double>(), ctx->fin.as<double>(), ctx->bP.as<double>(), ctx->b_from_order && !kept_sym)) return rc;
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ctx->ev[5], s));
 
@@ -2331,8 +2395,8 @@ int mag_run(mag_ctx *ctx)
     HIPCHK(hipStreamSynchronize(s));
     if (ctx->opt.verbose) printf("info: solve complete\n");
 
-    st.ms_order = ev_ms(ctx->ev[0], ctx->ev[1]);
-    st.ms_csr_symbolic = ev_ms(ctx->ev[1], ctx->ev[2]);
+    st.ms_order = kept_sym ? 0.0 : ev_ms(ctx->ev[0], ctx->ev[1]); // (kept: neither phase ran)
+    st.ms_csr_symbolic = kept_sym ? 0.0 : ev_ms(ctx->ev[1], ctx->ev[2]);
     st.ms_element = 0.0; // part of ms_assemble (the assembly kernels evaluate the elements on the fly)
     st.ms_assemble = ev_ms(ctx->ev[2], ctx->ev[4]);
     st.ms_bc = ev_ms(ctx->ev[4], ctx->ev[5]);
@@ -2597,7 +2661,10 @@ struct MemberHooks {
 // member is a problem of its own, so side by side needs its K assembled and the hooks build its blocks).
 int run_members(mag_ctx *ctx, MemberSet &set, LentProblem &keep, const MemberHooks &hooks)
 {
+    if (ctx->field_on)
+        if (int rc = field_context_refused(ctx, set.run_fn)) return rc;
     if (int rc = enter(ctx)) return rc;
+    FieldOperator field_op(ctx); // (under a field: the CSR operator's phase, hence one member after another)
     hipStream_t s = ctx->stream;
     const int32_t L = set.count;
     set.have_run = false;
@@ -2616,8 +2683,10 @@ int run_members(mag_ctx *ctx, MemberSet &set, LentProblem &keep, const MemberHoo
     HIPCHK(hipEventRecord(ctx->ev[1], s));
     if (int rc = reserve_cg(ctx)) return rc;
     const bool csr = wants_csr(ctx);
-    if (csr)
+    const bool kept_sym = ctx->field_sym; // (begin_run: the order and the pattern of an earlier run under this field)
+    if (csr && !kept_sym)
         if (int rc = csr_symbolic(ctx)) return rc;
+    ctx->field_sym = ctx->field_on && csr;
     HIPCHK(hipEventRecord(ctx->ev[2], s));
     if (int rc = hooks.prepare()) return rc;
     if (ctx->opt.verbose) printf("info: solving...\n");
@@ -2813,6 +2882,7 @@ int mag_set_variants(mag_ctx *ctx, int32_t num_variants, const double *xy, const
                      const double *f_in, int32_t memory)
 {
     if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (ctx->field_on) return field_refuses(ctx, "mag_set_variants");
     if (num_variants < 1) return fail(ctx, MAG_ERR_BAD_ARGS, "num_variants = %d: at least one variant", (int)num_variants);
     if ((u_in == nullptr) != (f_in == nullptr)) return fail(ctx, MAG_ERR_BAD_ARGS, "variants: u_in and f_in come together, or both null");
     if (!xy && !material && !u_in)
@@ -3063,6 +3133,7 @@ int run_variant_set(mag_ctx *ctx, MemberSet &set)
 int mag_run_variants(mag_ctx *ctx)
 {
     if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (ctx->field_on) return field_refuses(ctx, "mag_run_variants");
     if (int rc = variants_refused(ctx)) return rc;
     if (!ctx->have_problem || !ctx->variants.have) return fail(ctx, MAG_ERR_STATE, "mag_run_variants before mag_set_variants");
     return run_variant_set(ctx, ctx->variants);
@@ -3083,6 +3154,7 @@ int mag_get_variants_info(const mag_ctx *ctx, int32_t info[4]) { return ctx ? se
 int mag_assemble_csr_variant(mag_ctx *ctx, int32_t v, int64_t *nnz, int32_t *rowptr, int32_t *col, double *val)
 {
     if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (ctx->field_on) return field_refuses(ctx, "mag_assemble_csr_variant");
     if (int rc = variants_refused(ctx)) return rc;
     if (!ctx->have_problem || !ctx->variants.have) return fail(ctx, MAG_ERR_STATE, "mag_assemble_csr_variant before mag_set_variants");
     if (v < 0 || v >= ctx->variants.count) return fail(ctx, MAG_ERR_BAD_ARGS, "variant %d out of range [0, %d)", (int)v, (int)ctx->variants.count);
@@ -3135,6 +3207,8 @@ int sens_refused(mag_ctx *ctx, int32_t set, const char *fn, int32_t *count)
     if (set < MAG_SET_RUN || set > MAG_SET_VARIANTS) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: set %d is none of enum mag_set", fn, (int)set);
     if (ctx->comm.nranks > 1)
         return fail(ctx, MAG_ERR_BAD_ARGS, "sensitivities run on one GPU: this context has a communicator of %d ranks", ctx->comm.nranks);
+    // (variants were solved without a field and carry none: their passes wait until it is cleared)
+    if (set == MAG_SET_VARIANTS && ctx->field_on) return field_refuses(ctx, fn);
     const bool ran = set == MAG_SET_RUN ? ctx->have_run : (set == MAG_SET_CASES ? ctx->cases.have_run : ctx->variants.have_run);
     if (!ctx->have_problem || !ran) return fail(ctx, MAG_ERR_STATE, "%s before a completed %s", fn, kSetRun[set]);
     *count = set == MAG_SET_RUN ? 1 : (set == MAG_SET_CASES ? ctx->cases.count : ctx->variants.count);
@@ -3196,6 +3270,7 @@ int sens_chunk(mag_ctx *ctx, size_t per_member, int32_t M, int64_t &chunk)
 struct MemberView {
     int64_t N = 0;
     const double *xy = nullptr, *mat = nullptr, *u = nullptr, *f = nullptr, *u_in = nullptr, *f_in = nullptr;
+    const double *scale = nullptr; // the element stiffness field, shared by the members (variants have none)
     int64_t xy_stride = 0, mat_stride = 0, loads_stride = 0; // doubles
     // the head of the batch of members c0 .. c0 + count - 1
     void head(magk::MemberBatch &mb, int32_t c0, int32_t count) const
@@ -3206,6 +3281,7 @@ struct MemberView {
         mb.xy_stride = xy_stride;
         mb.xy = xy + (size_t)xy_stride * c0;
         mb.u = u + 2 * (size_t)N * c0;
+        mb.scale = scale;
     }
 };
 
@@ -3217,6 +3293,7 @@ int member_view(mag_ctx *ctx, int32_t set, MemberView &mv)
     const bool own_xy = set == MAG_SET_VARIANTS && ctx->v_have_xy, own_mat = set == MAG_SET_VARIANTS;
     const bool own_loads = set == MAG_SET_CASES || (set == MAG_SET_VARIANTS && ctx->v_have_loads);
     mv.N = ctx->N;
+    mv.scale = set == MAG_SET_VARIANTS ? nullptr : field_of(ctx);
     mv.xy = own_xy ? ctx->v_xy.as<double>() : ctx->xy.as<double>();
     mv.xy_stride = own_xy ? 2 * ctx->N : 0;
     mv.u = ms ? ms->u.as<double>() : ctx->u.as<double>();
@@ -3609,6 +3686,7 @@ int mag_download_objective(mag_ctx *ctx, int32_t set, int32_t index, mag_objecti
 int mag_run_stress(mag_ctx *ctx, int32_t set)
 {
     if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (ctx->field_on) return field_refuses(ctx, "mag_run_stress");
     int32_t M = 0;
     if (int rc = sens_refused(ctx, set, "mag_run_stress", &M)) return rc;
     if (int rc = enter(ctx)) return rc;
@@ -3706,6 +3784,7 @@ int mass_batch(mag_ctx *ctx, double density, int32_t lumped, int32_t masked, int
 int mag_run_modal(mag_ctx *ctx, const mag_modal_options *mo)
 {
     if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (ctx->field_on) return field_refuses(ctx, "mag_run_modal");
     if (!mo) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_modal: null options");
     const int32_t p = mo->modes;
     if (p < 1) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_modal: modes = %d: at least one mode", (int)p);
@@ -3935,6 +4014,7 @@ int refined_refused(const mag_ctx *ctx, const void *o, const char *what, const c
 int mag_run_refine(mag_ctx *ctx, const mag_refine_options *ro)
 {
     if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (ctx->field_on) return field_refuses(ctx, "mag_run_refine");
     if (!ro) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_refine: null options");
     const int32_t rule = ro->rule, split = ro->split;
     if (rule < MAG_REFINE_MARKS || rule > MAG_REFINE_TOP_FRACTION)
@@ -4168,6 +4248,269 @@ int mag_upload_refined(mag_ctx *ctx)
     return MAG_OK;
 }
 
+// ---- the element stiffness field and the density design update on it ----
+namespace {
+
+// A new field (or none) is in place: the single run's and the load cases' results and what was derived from them go; the order,
+// the tables and the pattern stay when the context already ran under a field (they were built with the CSR operator's choices)
+void field_installed(mag_ctx *ctx, bool on)
+{
+    if (on != ctx->field_on) ctx->have_order = ctx->field_sym = false;
+    ctx->field_on = on;
+    ctx->have_csr = ctx->have_run = false;
+    ctx->cases.have_run = false;
+    for (int32_t slot = MAG_SET_RUN; slot <= MAG_SET_CASES; ++slot) {
+        drop_derived(ctx, slot);
+        ctx->adj[slot].have = ctx->adj[slot].have_run = false;
+    }
+}
+
+// the first entry of x[0 .. n) that is not finite, <= 0 or > upper: -1 when there is none
+int first_bad_entry(mag_ctx *ctx, const double *x, int64_t n, double upper, int32_t &first)
+{
+    hipStream_t s = ctx->stream;
+    HIPCHK(ctx->ds_small.reserve(8 * magk::DW_COUNT + 16));
+    int32_t *flag = (int32_t *)(ctx->ds_small.as<double>() + magk::DW_COUNT);
+    first = INT32_MAX;
+    HIPCHK(hipMemcpyAsync(flag, &first, 4, hipMemcpyHostToDevice, s));
+    magk::first_out_of_range(x, n, upper, flag, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&first, flag, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (first == INT32_MAX) first = -1;
+    return MAG_OK;
+}
+
+magk::DesignParams design_params(const mag_ctx *ctx)
+{
+    const mag_design_options &o = ctx->design_opt;
+    return {o.scale_min, o.rho_min, o.move, o.volume_fraction, o.penal, o.filter_passes};
+}
+
+// out = F^passes x (forward) or (F^T)^passes x; out may not be x; ds_tmp: two rows of E, ds_node: N
+int design_filter_passes(mag_ctx *ctx, const magk::SensMesh &mesh, bool transpose, const double *x, double *out)
+{
+    hipStream_t s = ctx->stream;
+    const size_t eb = 8 * (size_t)ctx->E;
+    const int32_t P = ctx->design_opt.filter_passes;
+    if (P == 0) {
+        HIPCHK(hipMemcpyAsync(out, x, eb, hipMemcpyDeviceToDevice, s));
+        return MAG_OK;
+    }
+    double *tmp[2] = {ctx->ds_tmp.as<double>(), ctx->ds_tmp.as<double>() + ctx->E};
+    const double *cur = x;
+    for (int32_t k = 0; k < P; ++k) {
+        double *nxt = k == P - 1 ? out : tmp[k & 1];
+        if (transpose)
+            magk::design_filter_t(mesh, ctx->xy.as<double>(), ctx->ds_area.as<double>(), ctx->ds_node_area.as<double>(), cur,
+                                  ctx->ds_node.as<double>(), nxt, s);
+        else
+            magk::design_filter(mesh, ctx->xy.as<double>(), ctx->ds_area.as<double>(), ctx->ds_node_area.as<double>(), cur,
+                                ctx->ds_node.as<double>(), nxt, s);
+        cur = nxt;
+    }
+    HIPCHK(hipGetLastError());
+    return MAG_OK;
+}
+
+// rho~ = F^P rho, s = scale_min + (1 - scale_min) rho~^p into the context's field, the greyness word
+int design_interpolate_field(mag_ctx *ctx, const magk::SensMesh &mesh)
+{
+    hipStream_t s = ctx->stream;
+    if (int rc = design_filter_passes(ctx, mesh, false, ctx->ds_rho.as<double>(), ctx->ds_rhof.as<double>())) return rc;
+    magk::design_interpolate(ctx->ds_rhof.as<double>(), ctx->E, design_params(ctx), ctx->escale.as<double>(), s);
+    magk::design_greyness(ctx->ds_rhof.as<double>(), ctx->E, ctx->ds_part.as<double>(), ctx->ds_small.as<double>(), s);
+    HIPCHK(hipGetLastError());
+    return MAG_OK;
+}
+
+int design_read_info(mag_ctx *ctx)
+{
+    hipStream_t s = ctx->stream;
+    HIPCHK(hipMemcpyAsync(ctx->design_info, ctx->ds_small.as<double>() + magk::DW_INFO, 64, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
+} // namespace
+
+int mag_set_element_scale(mag_ctx *ctx, const double *scale, int32_t memory)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (scale && !memory_known(memory)) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_set_element_scale: memory = %d is none of enum mag_memory", (int)memory);
+    if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "mag_set_element_scale before mag_upload");
+    if (scale)
+        if (int rc = field_context_refused(ctx, "mag_set_element_scale")) return rc;
+    if (int rc = enter(ctx)) return rc;
+    if (!scale) { // clear: the context computes what it computed before the field
+        ctx->design_on = false;
+        if (ctx->field_on) field_installed(ctx, false);
+        return MAG_OK;
+    }
+    hipStream_t s = ctx->stream;
+    const int64_t E = ctx->E;
+    HIPCHK(ctx->ds_tmp.reserve(2 * 8 * (size_t)E));
+    HIPCHK(hipMemcpyAsync(ctx->ds_tmp.p, scale, 8 * (size_t)E, memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    int32_t bad = -1;
+    if (int rc = first_bad_entry(ctx, ctx->ds_tmp.as<double>(), E, HUGE_VAL, bad)) return rc;
+    if (bad >= 0)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "mag_set_element_scale: scale[%d] is not finite and > 0 (the field is as it was)", (int)bad);
+    HIPCHK(ctx->escale.reserve(8 * (size_t)E));
+    HIPCHK(hipMemcpyAsync(ctx->escale.p, ctx->ds_tmp.p, 8 * (size_t)E, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    ctx->design_on = false; // (a field of the caller's ends a design)
+    field_installed(ctx, true);
+    return MAG_OK;
+}
+
+int mag_design_init(mag_ctx *ctx, const mag_design_options *o, const double *rho0, int32_t memory)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_design_init: null options");
+    const auto inside = [](double v, bool closed_above) { return std::isfinite(v) && v > 0.0 && (closed_above ? v <= 1.0 : v < 1.0); };
+    if (!inside(o->volume_fraction, true))
+        return fail(ctx, MAG_ERR_BAD_ARGS, "mag_design_init: volume_fraction = %g outside (0, 1]", o->volume_fraction);
+    if (!inside(o->scale_min, false)) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_design_init: scale_min = %g outside (0, 1)", o->scale_min);
+    if (!inside(o->rho_min, false)) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_design_init: rho_min = %g outside (0, 1)", o->rho_min);
+    if (!inside(o->move, true)) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_design_init: move = %g outside (0, 1]", o->move);
+    if (o->penal < 1 || o->penal > 8) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_design_init: penal = %d outside 1..8", (int)o->penal);
+    if (o->filter_passes < 0 || o->filter_passes > 8)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "mag_design_init: filter_passes = %d outside 0..8", (int)o->filter_passes);
+    if (rho0 && !memory_known(memory)) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_design_init: memory = %d is none of enum mag_memory", (int)memory);
+    if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "mag_design_init before mag_upload");
+    if (int rc = field_context_refused(ctx, "mag_design_init")) return rc;
+    if (int rc = enter(ctx)) return rc;
+    hipStream_t s = ctx->stream;
+    const int64_t N = ctx->N, E = ctx->E;
+    const size_t eb = 8 * (size_t)E;
+    ctx->design_on = false;
+    ctx->design_opt = *o;
+    // The filter walks the incidence lists: the order and the tables are built here, with the CSR operator's choices as every
+    // context under a field has them.  The design's scale becomes the context's field at the END, once everything is checked:
+    // a refused init leaves a field of the caller's, and the results under it, as they were (a design in progress is ended).
+    struct Undo { // ... and an order built here does not outlive a refused init on a context without a field
+        mag_ctx *ctx;
+        bool armed;
+        ~Undo()
+        {
+            if (armed) ctx->have_order = false;
+        }
+    } undo{ctx, !ctx->field_on};
+    if (!ctx->field_on) ctx->have_order = false;
+    {
+        FieldOperator op(ctx, true);
+        if (int rc = ensure_order(ctx)) return rc;
+    }
+    magk::SensMesh mesh;
+    if (int rc = sens_mesh(ctx, mesh)) return rc;
+    if (int rc = reserve_rows(ctx, {ROWS(ctx->ds_rho, eb), ROWS(ctx->ds_rhof, eb), ROWS(ctx->ds_w, eb), ROWS(ctx->ds_area, eb),
+                                    ROWS(ctx->ds_tmp, 2 * eb), ROWS(ctx->ds_dJ, eb), ROWS(ctx->ds_dJdrho, eb), ROWS(ctx->ds_bq, eb),
+                                    ROWS(ctx->ds_rho_new, eb), ROWS(ctx->escale, eb), ROWS(ctx->ds_node_area, 8 * (size_t)N),
+                                    ROWS(ctx->ds_node, 8 * (size_t)N), ROWS(ctx->ds_part, 8 * magk::kDesignPartials),
+                                    ROWS(ctx->ds_small, 8 * magk::DW_COUNT + 16)}, 1))
+        return rc;
+    double *small = ctx->ds_small.as<double>(), *part = ctx->ds_part.as<double>();
+    int32_t *flag = (int32_t *)(small + magk::DW_COUNT);
+    HIPCHK(hipMemsetAsync(small, 0, 8 * magk::DW_COUNT, s));
+    HIPCHK(hipMemsetAsync(ctx->ds_dJdrho.p, 0, eb, s));
+    int32_t bad = INT32_MAX;
+    HIPCHK(hipMemcpyAsync(flag, &bad, 4, hipMemcpyHostToDevice, s));
+    magk::design_areas(mesh, ctx->xy.as<double>(), ctx->ds_area.as<double>(), flag, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (bad != INT32_MAX)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "mag_design_init: element %d has a signed area <= 0 (counter-clockwise elements are required)", (int)bad);
+    if (rho0) {
+        HIPCHK(hipMemcpyAsync(ctx->ds_rho.p, rho0, eb, memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+        if (int rc = first_bad_entry(ctx, ctx->ds_rho.as<double>(), E, 1.0, bad)) return rc;
+        if (bad >= 0) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_design_init: rho0[%d] is outside (0, 1]", (int)bad);
+    } else {
+        const std::vector<double> uniform((size_t)E, o->volume_fraction);
+        HIPCHK(hipMemcpyAsync(ctx->ds_rho.p, uniform.data(), eb, hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    magk::design_node_areas(mesh, ctx->xy.as<double>(), ctx->ds_area.as<double>(), ctx->ds_node_area.as<double>(), s);
+    magk::design_total_area(ctx->ds_area.as<double>(), E, o->volume_fraction, part, small, s);
+    HIPCHK(hipGetLastError());
+    // w = (F^T)^P a: the filtered volume is sum_e w_e rho_e exactly, no filter inside the bisection
+    if (int rc = design_filter_passes(ctx, mesh, true, ctx->ds_area.as<double>(), ctx->ds_w.as<double>())) return rc;
+    magk::design_volume(ctx->ds_rho.as<double>(), ctx->ds_w.as<double>(), E, part, small, s);
+    if (int rc = design_interpolate_field(ctx, mesh)) return rc;
+    if (int rc = design_read_info(ctx)) return rc;
+    undo.armed = false;
+    const bool order_kept = ctx->have_order;
+    field_installed(ctx, true);
+    ctx->have_order = order_kept; // (built above under the field's choices)
+    ctx->design_steps = 0;
+    ctx->design_on = true;
+    return MAG_OK;
+}
+
+int mag_design_step(mag_ctx *ctx, const double *dJ_ds, int32_t memory)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (dJ_ds && !memory_known(memory)) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_design_step: memory = %d is none of enum mag_memory", (int)memory);
+    if (!ctx->design_on) return fail(ctx, MAG_ERR_STATE, "mag_design_step before mag_design_init");
+    if (!ctx->have_run) return fail(ctx, MAG_ERR_STATE, "mag_design_step before a completed mag_run under the design's scale");
+    const DerivedSet &sens = ctx->derived[PASS_SENS][MAG_SET_RUN];
+    if (!dJ_ds && !sens.have)
+        return fail(ctx, MAG_ERR_STATE, "mag_design_step with a NULL gradient before mag_run_sensitivities(MAG_SET_RUN) of this run");
+    if (int rc = enter(ctx)) return rc;
+    hipStream_t s = ctx->stream;
+    const int64_t E = ctx->E;
+    const size_t eb = 8 * (size_t)E;
+    const magk::DesignParams dp = design_params(ctx);
+    magk::SensMesh mesh;
+    if (int rc = sens_mesh(ctx, mesh)) return rc;
+    const double J = dJ_ds ? 0.0 : -2.0 * sens.scalars_h[1];
+    const double *given = nullptr;
+    if (dJ_ds) {
+        given = ctx->ds_dJ.as<double>();
+        HIPCHK(hipMemcpyAsync(ctx->ds_dJ.p, dJ_ds, eb, memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    }
+    // dJ/drho~ (into ds_bq, free until the update), then dJ/drho = (F^T)^P of it
+    magk::design_chain(given, sens.energy.as<double>(), ctx->escale.as<double>(), ctx->ds_rhof.as<double>(), E, dp, ctx->ds_bq.as<double>(), s);
+    if (int rc = design_filter_passes(ctx, mesh, true, ctx->ds_bq.as<double>(), ctx->ds_dJdrho.as<double>())) return rc;
+    magk::design_oc(ctx->ds_rho.as<double>(), ctx->ds_dJdrho.as<double>(), ctx->ds_w.as<double>(), E, dp, ctx->ds_bq.as<double>(),
+                    ctx->ds_rho_new.as<double>(), ctx->ds_part.as<double>(), ctx->ds_small.as<double>(), s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ctx->ds_rho.p, ctx->ds_rho_new.p, eb, hipMemcpyDeviceToDevice, s));
+    if (int rc = design_interpolate_field(ctx, mesh)) return rc;
+    if (int rc = design_read_info(ctx)) return rc;
+    ctx->design_info[5] = (double)++ctx->design_steps;
+    ctx->design_info[6] = J;
+    ctx->design_info[7] = 0.0;
+    field_installed(ctx, true); // the new scale: the run it was derived from is gone
+    return MAG_OK;
+}
+
+int mag_get_design_info(const mag_ctx *ctx, double info[8])
+{
+    if (!ctx || !info) return MAG_ERR_BAD_ARGS;
+    if (!ctx->design_on) return MAG_ERR_STATE;
+    for (int k = 0; k < 8; ++k) info[k] = ctx->design_info[k];
+    return MAG_OK;
+}
+
+int mag_download_design(mag_ctx *ctx, const mag_design *o)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "null design");
+    if (!memory_known(o->memory)) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_download_design: memory = %d is none of enum mag_memory", (int)o->memory);
+    if (!ctx->design_on) return fail(ctx, MAG_ERR_STATE, "mag_download_design before mag_design_init");
+    if (int rc = enter(ctx)) return rc;
+    const hipMemcpyKind kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    hipStream_t s = ctx->stream;
+    const size_t eb = 8 * (size_t)ctx->E;
+    if (o->rho_out) HIPCHK(hipMemcpyAsync(o->rho_out, ctx->ds_rho.p, eb, kind, s));
+    if (o->rho_filtered_out) HIPCHK(hipMemcpyAsync(o->rho_filtered_out, ctx->ds_rhof.p, eb, kind, s));
+    if (o->scale_out) HIPCHK(hipMemcpyAsync(o->scale_out, ctx->escale.p, eb, kind, s));
+    if (o->dJ_drho_out) HIPCHK(hipMemcpyAsync(o->dJ_drho_out, ctx->ds_dJdrho.p, eb, kind, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
 int mag_solve(mag_ctx *ctx, const mag_problem *p, mag_result *r)
 {
     if (int rc = mag_upload(ctx, p)) return rc;
@@ -4258,6 +4601,7 @@ int mag_reduce_system(mag_ctx *ctx, int64_t *n_free, int64_t *nnz_ff, int32_t *r
 
 int mag_apply_operator(mag_ctx *ctx, const double *x, double *y, int32_t masked)
 {
+    if (ctx && ctx->field_on) return field_refuses(ctx, "mag_apply_operator");
     if (int rc = enter(ctx)) return rc;
     if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "no problem uploaded");
     if (!x || !y) return fail(ctx, MAG_ERR_BAD_ARGS, "null vector");
@@ -4280,6 +4624,7 @@ int mag_apply_operator(mag_ctx *ctx, const double *x, double *y, int32_t masked)
 
 int mag_time_operator(mag_ctx *ctx, int32_t reps, double *ms_per_launch)
 {
+    if (ctx && ctx->field_on) return field_refuses(ctx, "mag_time_operator");
     if (int rc = enter(ctx)) return rc;
     if (reps < 1 || !ms_per_launch) return fail(ctx, MAG_ERR_BAD_ARGS, "reps < 1 or null output");
     if (int rc = prepare_timing(ctx)) return rc;
@@ -4324,6 +4669,7 @@ int mag_time_operator(mag_ctx *ctx, int32_t reps, double *ms_per_launch)
 
 int mag_time_spmv(mag_ctx *ctx, int32_t reps, double *ms_per_launch)
 {
+    if (ctx && ctx->field_on) return field_refuses(ctx, "mag_time_spmv");
     if (int rc = enter(ctx)) return rc;
     if (reps < 1 || !ms_per_launch) return fail(ctx, MAG_ERR_BAD_ARGS, "reps < 1 or null output");
     if (int rc = prepare_timing(ctx)) return rc;

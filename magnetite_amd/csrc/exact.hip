@@ -154,10 +154,12 @@ constexpr int kAsmNodes = 128; // row nodes (threads) per tile
 constexpr int kAsmSlots = 8;   // 2x2 blocks a row may hold in its LDS accumulators (valence 6 interior node: 7)
 constexpr int kAsmBatch = 4;   // incidence entries whose gathers a thread issues together (the kernel is latency-bound)
 
-template <int STRIDE = kAsmNodes>
+// FIELD (mag_set_element_scale): every contribution is today's value multiplied once by the element's scale se, then added
+// in today's order; without it no multiply exists
+template <int STRIDE = kAsmNodes, bool FIELD = false>
 __device__ inline void asm_entry(const int32_t (&nn)[3], int a, const double2 v0, const double2 v1, const double2 v2,
                                  const double *D, double thick, const int32_t (&col)[kAsmSlots], double2 *s_top,
-                                 double2 *s_bot, int lane)
+                                 double2 *s_bot, int lane, double se = 1.0)
 {
     const double area = signed_area(v0.x, v0.y, v1.x, v1.y, v2.x, v2.y);
     const double d = 2.0 * area;
@@ -186,6 +188,7 @@ __device__ inline void asm_entry(const int32_t (&nn)[3], int a, const double2 v0
         t = Mx[0] * z;  t = t + Mx[1] * gb; t = t + Mx[2] * bb; c01 = t * area * thick;
         t = My[0] * bb; t = t + My[1] * z;  t = t + My[2] * gb; c10 = t * area * thick;
         t = My[0] * z;  t = t + My[1] * gb; t = t + My[2] * bb; c11 = t * area * thick;
+        if constexpr (FIELD) c00 *= se, c01 *= se, c10 *= se, c11 *= se;
         int kpos = 0; // position of n_b among the row's ascending columns (it is one of them)
 #pragma unroll
         for (int k = 0; k < kAsmSlots; ++k) kpos += col[k] < nn[b] ? 1 : 0;
@@ -200,11 +203,12 @@ __device__ inline void asm_entry(const int32_t (&nn)[3], int a, const double2 v0
 }
 
 __global__ void __launch_bounds__(kAsmNodes) k_assemble_tiles(const int32_t *bcol, const int32_t *bptr, const int32_t *inc_off, const uint32_t *inc, const uint32_t *perm, const int32_t *conn, const double2 *xy, int64_t N, double nu, double youngs, double thick, double *kval); // (end of the file: d_assemble_tiles on the single-case arrays)
+template <bool FIELD = false>
 __device__ __forceinline__ void d_assemble_tiles(const int32_t *bcol, const int32_t *bptr,
                                                                const int32_t *inc_off, const uint32_t *inc,
                                                                const uint32_t *perm, const int32_t *conn,
                                                                const double2 *xy, int64_t N, double nu, double youngs,
-                                                               double thick, double *kval)
+                                                               double thick, double *kval, const double *scale = nullptr)
 {
     __shared__ double2 s_top[kAsmSlots * kAsmNodes]; // (k00, k01) of block `slot` of the thread's row
     __shared__ double2 s_bot[kAsmSlots * kAsmNodes]; // (k10, k11)
@@ -253,8 +257,13 @@ __device__ __forceinline__ void d_assemble_tiles(const int32_t *bcol, const int3
                 }
 #pragma unroll
             for (int u = 0; u < kAsmBatch; ++u)
-                if (v[u] != 0xffffffffu)
-                    asm_entry(nn[u], (int)(v[u] % 3u), c[u][0], c[u][1], c[u][2], D, thick, col, s_top, s_bot, lane);
+                if (v[u] != 0xffffffffu) {
+                    if constexpr (FIELD)
+                        asm_entry<kAsmNodes, true>(nn[u], (int)(v[u] % 3u), c[u][0], c[u][1], c[u][2], D, thick, col, s_top, s_bot,
+                                                   lane, scale[v[u] / 3u]);
+                    else
+                        asm_entry(nn[u], (int)(v[u] % 3u), c[u][0], c[u][1], c[u][2], D, thick, col, s_top, s_bot, lane);
+                }
         }
         double *r0 = kval + 4 * (int64_t)p, *r1 = r0 + 2 * cnt;
 #pragma unroll
@@ -293,6 +302,10 @@ __device__ __forceinline__ void d_assemble_tiles(const int32_t *bcol, const int3
                     if (nn[b] != j) continue;
                     double c00, c01, c10, c11;
                     ke_block(v0, v1, v2, a, b, D, thick, c00, c01, c10, c11);
+                    if constexpr (FIELD) {
+                        const double se = scale[e];
+                        c00 *= se, c01 *= se, c10 *= se, c11 *= se;
+                    }
                     k00 += c00;
                     k01 += c01;
                     k10 += c10;
@@ -309,11 +322,17 @@ __device__ __forceinline__ void d_assemble_tiles(const int32_t *bcol, const int3
     }
 }
 
+__global__ void __launch_bounds__(kAsmNodes) k_assemble_tiles_s(const int32_t *bcol, const int32_t *bptr, const int32_t *inc_off, const uint32_t *inc, const uint32_t *perm, const int32_t *conn, const double2 *xy, int64_t N, double nu, double youngs, double thick, double *kval, const double *scale); // (end of the file)
 void assemble_tiles(const int32_t *bcol, const int32_t *bptr, const int32_t *inc_off, const uint32_t *inc,
                     const uint32_t *perm, const int32_t *conn, const double *xy, int64_t N, double nu, double youngs,
-                    double thick, double *kval, hipStream_t s)
+                    double thick, double *kval, const double *scale, hipStream_t s)
 {
     const int64_t tiles = (N + kAsmNodes - 1) / kAsmNodes;
+    if (scale) {
+        k_assemble_tiles_s<<<(unsigned)tiles, kAsmNodes, 0, s>>>(bcol, bptr, inc_off, inc, perm, conn, (const double2 *)xy, N,
+                                                                 nu, youngs, thick, kval, scale);
+        return;
+    }
     k_assemble_tiles<<<(unsigned)tiles, kAsmNodes, 0, s>>>(bcol, bptr, inc_off, inc, perm, conn, (const double2 *)xy, N,
                                                            nu, youngs, thick, kval);
 }
@@ -483,7 +502,7 @@ constexpr int kFanStage = 20;    // 16-byte pieces of staging per node: two rows
 
 template <int B>
 __global__ void __launch_bounds__(kFanThreads) k_assemble_fan(const int32_t *bcol, const int32_t *bptr, const uint32_t *perm, const double2 *xyP, const double2 *halo_xy, const int32_t *tile_hoff, const int32_t *tile_deg, const int64_t *tile_off, const uint32_t *ell_asm, const uint16_t *ell_pos, const int32_t *inc_off, const uint32_t *inc, const int32_t *conn, const double2 *xy, int64_t N, int32_t cap, int32_t img_pieces, int32_t segs, int32_t six, double nu, double youngs, double thick, double *kval); // (end of the file: d_assemble_fan on the single-case arrays)
-template <int B>
+template <int B, bool FIELD = false>
 __device__ __forceinline__ void d_assemble_fan(const int32_t *bcol, const int32_t *bptr, const uint32_t *perm,
                                                               const double2 *xyP, const double2 *halo_xy,
                                                               const int32_t *tile_hoff, const int32_t *tile_deg,
@@ -491,7 +510,8 @@ __device__ __forceinline__ void d_assemble_fan(const int32_t *bcol, const int32_
                                                               const uint16_t *ell_pos, const int32_t *inc_off,
                                                               const uint32_t *inc, const int32_t *conn, const double2 *xy,
                                                               int64_t N, int32_t cap, int32_t img_pieces, int32_t segs,
-                                                              int32_t six, double nu, double youngs, double thick, double *kval)
+                                                              int32_t six, double nu, double youngs, double thick, double *kval,
+                                                              const double *scale = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) double2 s_asm[];
     double2 *s_xy = s_asm;                                   // [cap] coordinates of the tile's owned + halo nodes
@@ -583,6 +603,12 @@ __device__ __forceinline__ void d_assemble_fan(const int32_t *bcol, const int32_
             double dgc[4] = {0.0, 0.0, 0.0, 0.0}, kbv[4] = {0.0, 0.0, 0.0, 0.0}, kcv[4] = {0.0, 0.0, 0.0, 0.0};
             if (fanrow) {
                 asm_fan_blocks((int)((w >> 12) & 3u), s_xy[l], s_xy[lb], s_xy[lc], D, thick, sane, dgc, kbv, kcv);
+                if constexpr (FIELD) {
+                    // slot k of the node's table words is entry k of its incidence list: the lane's element
+                    const double se = scale[inc[inc_off[(int64_t)t * B + l] + k] / 3u];
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) dgc[m] *= se, kbv[m] *= se, kcv[m] *= se;
+                }
                 wreg[wl] = make_double2(kcv[0], kcv[1]); // the c-side block: top piece, bottom piece
                 wreg[64 + wl] = make_double2(kcv[2], kcv[3]);
             }
@@ -697,6 +723,10 @@ __device__ __forceinline__ void d_assemble_fan(const int32_t *bcol, const int32_
                     if (nn[b] != j) continue;
                     double c00, c01, c10, c11;
                     ke_block(v0, v1, v2, a, b, D, thick, c00, c01, c10, c11);
+                    if constexpr (FIELD) {
+                        const double se = scale[e];
+                        c00 *= se, c01 *= se, c10 *= se, c11 *= se;
+                    }
                     k00 += c00;
                     k01 += c01;
                     k10 += c10;
@@ -720,11 +750,13 @@ size_t assemble_ctiles_lds(int32_t B, int32_t cap)
     return (size_t)asm_img_pieces(cap, B) * 16 + (size_t)kFanThreads * 64 + (size_t)B * 4;
 }
 
+template <int B>
+__global__ void __launch_bounds__(kFanThreads) k_assemble_fan_s(const int32_t *bcol, const int32_t *bptr, const uint32_t *perm, const double2 *xyP, const double2 *halo_xy, const int32_t *tile_hoff, const int32_t *tile_deg, const int64_t *tile_off, const uint32_t *ell_asm, const uint16_t *ell_pos, const int32_t *inc_off, const uint32_t *inc, const int32_t *conn, const double2 *xy, int64_t N, int32_t cap, int32_t img_pieces, int32_t segs, int32_t six, double nu, double youngs, double thick, double *kval, const double *scale); // (end of the file)
 bool assemble_ctiles(const int32_t *bcol, const int32_t *bptr, const uint32_t *perm, const double *xyP,
                      const double *halo_xy, const int32_t *tile_hoff, const int32_t *tile_deg, const int64_t *tile_off,
                      const uint32_t *ell_asm, const uint16_t *ell_pos, const int32_t *inc_off, const uint32_t *inc,
                      const int32_t *conn, const double *xy, int64_t N, int32_t B, int32_t T, int32_t cap, double nu,
-                     double youngs, double thick, double *kval, hipStream_t s)
+                     double youngs, double thick, double *kval, const double *scale, hipStream_t s)
 {
     const size_t lds = assemble_ctiles_lds(B, cap);
     if ((B != 256 && B != 512) || cap > 4096 || lds > 64 * 1024) return false; // 12-bit local ids; the image fits the LDS
@@ -734,6 +766,17 @@ bool assemble_ctiles(const int32_t *bcol, const int32_t *bptr, const uint32_t *p
     int32_t segs = 1;
     while ((int64_t)T * segs < 768 && B / (2 * segs) >= kFanThreads / kFanLanes) segs *= 2;
     const int32_t six = 1; // six lanes per node where the rows allow it (0: eight for every row)
+    if (scale) {
+        if (B == 256)
+            k_assemble_fan_s<256><<<T * segs, kFanThreads, lds, s>>>(
+                bcol, bptr, perm, (const double2 *)xyP, (const double2 *)halo_xy, tile_hoff, tile_deg, tile_off, ell_asm,
+                ell_pos, inc_off, inc, conn, (const double2 *)xy, N, cap, img, segs, six, nu, youngs, thick, kval, scale);
+        else
+            k_assemble_fan_s<512><<<T * segs, kFanThreads, lds, s>>>(
+                bcol, bptr, perm, (const double2 *)xyP, (const double2 *)halo_xy, tile_hoff, tile_deg, tile_off, ell_asm,
+                ell_pos, inc_off, inc, conn, (const double2 *)xy, N, cap, img, segs, six, nu, youngs, thick, kval, scale);
+        return true;
+    }
     if (B == 256)
         k_assemble_fan<256><<<T * segs, kFanThreads, lds, s>>>(
             bcol, bptr, perm, (const double2 *)xyP, (const double2 *)halo_xy, tile_hoff, tile_deg, tile_off, ell_asm,
@@ -1049,6 +1092,17 @@ template <int B>
 __global__ void __launch_bounds__(kFanThreads) k_assemble_fan(const int32_t *bcol, const int32_t *bptr, const uint32_t *perm, const double2 *xyP, const double2 *halo_xy, const int32_t *tile_hoff, const int32_t *tile_deg, const int64_t *tile_off, const uint32_t *ell_asm, const uint16_t *ell_pos, const int32_t *inc_off, const uint32_t *inc, const int32_t *conn, const double2 *xy, int64_t N, int32_t cap, int32_t img_pieces, int32_t segs, int32_t six, double nu, double youngs, double thick, double *kval)
 {
     d_assemble_fan<B>(bcol, bptr, perm, xyP, halo_xy, tile_hoff, tile_deg, tile_off, ell_asm, ell_pos, inc_off, inc, conn, xy, N, cap, img_pieces, segs, six, nu, youngs, thick, kval);
+}
+// ... and under an element stiffness field (mag_set_element_scale): the FIELD instantiations of the same bodies, kernels of their
+// own, so that the ones above stay what they are
+__global__ void __launch_bounds__(kAsmNodes) k_assemble_tiles_s(const int32_t *bcol, const int32_t *bptr, const int32_t *inc_off, const uint32_t *inc, const uint32_t *perm, const int32_t *conn, const double2 *xy, int64_t N, double nu, double youngs, double thick, double *kval, const double *scale)
+{
+    d_assemble_tiles<true>(bcol, bptr, inc_off, inc, perm, conn, xy, N, nu, youngs, thick, kval, scale);
+}
+template <int B>
+__global__ void __launch_bounds__(kFanThreads) k_assemble_fan_s(const int32_t *bcol, const int32_t *bptr, const uint32_t *perm, const double2 *xyP, const double2 *halo_xy, const int32_t *tile_hoff, const int32_t *tile_deg, const int64_t *tile_off, const uint32_t *ell_asm, const uint16_t *ell_pos, const int32_t *inc_off, const uint32_t *inc, const int32_t *conn, const double2 *xy, int64_t N, int32_t cap, int32_t img_pieces, int32_t segs, int32_t six, double nu, double youngs, double thick, double *kval, const double *scale)
+{
+    d_assemble_fan<B, true>(bcol, bptr, perm, xyP, halo_xy, tile_hoff, tile_deg, tile_off, ell_asm, ell_pos, inc_off, inc, conn, xy, N, cap, img_pieces, segs, six, nu, youngs, thick, kval, scale);
 }
 __global__ void __launch_bounds__(256) k_rhs_from_csr(const int32_t *bptr, const int32_t *bcol, const double *kval, const uint8_t *u_known, const double *u_in, const double *f_in, const uint32_t *perm, const uint8_t *touch, bool hilbert_flags, int64_t N, double2 *bP)
 {

@@ -128,7 +128,9 @@ void element_stiffness(const double *xy, const int32_t *conn, int64_t E, double 
 // from LDS
 void assemble_tiles(const int32_t *bcol, const int32_t *bptr, const int32_t *inc_off, const uint32_t *inc,
                     const uint32_t *perm, const int32_t *conn, const double *xy, int64_t N, double nu, double youngs,
-                    double thick, double *kval, hipStream_t s);
+                    double thick, double *kval, const double *scale, hipStream_t s);
+// (scale, here and in assemble_ctiles: the element stiffness field of mag_set_element_scale, E values, or null -- with it the
+// FIELD instantiation of the kernel runs: every contribution of element e is today's value times scale[e], added in today's order)
 // the same assembly fed from the CG tiles (exact.hip, k_assemble_fan): coordinates and caller ids staged in LDS, the
 // per-node corner words of fill_ell16 (ell_asm) instead of the incidence -> connectivity -> coordinate gathers; false
 // when a tile's image does not fit one CU's LDS (the caller then uses assemble_tiles)
@@ -137,7 +139,7 @@ bool assemble_ctiles(const int32_t *bcol, const int32_t *bptr, const uint32_t *p
                      const double *halo_xy, const int32_t *tile_hoff, const int32_t *tile_deg, const int64_t *tile_off,
                      const uint32_t *ell_asm, const uint16_t *ell_pos, const int32_t *inc_off, const uint32_t *inc,
                      const int32_t *conn, const double *xy, int64_t N, int32_t B, int32_t T, int32_t cap, double nu,
-                     double youngs, double thick, double *kval, hipStream_t s);
+                     double youngs, double thick, double *kval, const double *scale, hipStream_t s);
 // apply_order has written b = 0.0 + f (0 on prescribed DOFs) for every node; this redoes the rows with a prescribed column
 // (touch: the pattern kernel's flags, Hilbert order)
 void rhs_touched(const int32_t *bptr, const int32_t *bcol, const double *kval, const uint8_t *u_known, const double *u_in,

@@ -12,6 +12,7 @@ namespace magk {
 struct Member {
     const double2 *xy, *u;
     double youngs, nu, thick;
+    const double *scale; // per element, or null
 };
 
 __device__ inline Member member_of(const MemberBatch &mb, int64_t v, int64_t N)
@@ -22,6 +23,7 @@ __device__ inline Member member_of(const MemberBatch &mb, int64_t v, int64_t N)
     m.youngs = mb.mat[mb.mat_stride * v];
     m.nu = mb.mat[mb.mat_stride * v + 1];
     m.thick = mb.mat[mb.mat_stride * v + 2];
+    m.scale = mb.scale;
     return m;
 }
 
@@ -76,7 +78,22 @@ __device__ inline void load_corners(const double2 *const (&src)[P], const int32_
 //   corner(n, f, k)    what the node's k-th incident triangle adds: f[j] = field j of its corners in cyclic order, corner 0 the
 //                      node; the triangle's id, where the pass wants it, is inc[inc_off[pos] + k] / 3,
 //   store(n, at)       what is written for the node, at = (member) * N + (caller id).
+// ScaledCorners is what a pass whose terms carry the element stiffness field derives from: node(pos) keeps the node's incidence
+// list, factor(n, k, cm) is cm times the scale of the node's k-th triangle -- cm itself where there is no field.
 // Sums run in the order of the node's incidence list in both walks, with the same arithmetic: the same bits.
+
+struct ScaledCorners {
+    const double *scale;
+    const uint32_t *inc;
+    const int32_t *inc_off;
+    struct Node {
+        double gx, gy;
+        const uint32_t *list;
+    };
+    __device__ ScaledCorners(const Member &m, const SensMesh &mesh) : scale(m.scale), inc(mesh.inc), inc_off(mesh.inc_off) {}
+    __device__ Node node(int64_t pos) const { return {0.0, 0.0, scale ? inc + inc_off[pos] : nullptr}; }
+    __device__ double factor(const Node &n, int32_t k, double cm) const { return scale ? cm * scale[n.list[k] / 3u] : cm; }
+};
 
 // One workgroup per tile of the Hilbert order and member (grid: T x count, 256 threads).  The tile's image -- P fields of its
 // owned and halo nodes, each fetched once from the member's caller-order arrays through perm -- is staged in s_img as P planes
@@ -163,6 +180,23 @@ __device__ inline void block_sum256(double (&v)[NS], double *s_red)
     if (threadIdx.x == 0)
 #pragma unroll
         for (int c = 0; c < NS; ++c) v[c] = (s_red[c] + s_red[NS + c]) + (s_red[2 * NS + c] + s_red[3 * NS + c]);
+}
+
+// maximum over the 256 threads of a workgroup of NS values each, in block_sum256's shape; valid in thread 0
+template <int NS>
+__device__ inline void block_max256(double (&v)[NS], double *s_red)
+{
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int c = 0; c < NS; ++c) v[c] = fmax(v[c], __shfl_down(v[c], off));
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0)
+#pragma unroll
+        for (int c = 0; c < NS; ++c) s_red[NS * w + c] = v[c];
+    __syncthreads();
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int c = 0; c < NS; ++c) v[c] = fmax(fmax(s_red[c], s_red[NS + c]), fmax(s_red[2 * NS + c], s_red[3 * NS + c]));
 }
 
 // Stage one (grid: kSensBlocks x count, 256 threads): every thread adds the pass's summands add(i, acc) of its fixed share of

@@ -87,23 +87,6 @@ struct Average {
     }
 };
 
-// maximum over the 256 threads of a workgroup of NS values each, in block_sum256's shape; valid in thread 0
-template <int NS>
-__device__ inline void block_max256(double (&v)[NS], double *s_red)
-{
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int c = 0; c < NS; ++c) v[c] = fmax(v[c], __shfl_down(v[c], off));
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0)
-#pragma unroll
-        for (int c = 0; c < NS; ++c) s_red[NS * w + c] = v[c];
-    __syncthreads();
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int c = 0; c < NS; ++c) v[c] = fmax(fmax(s_red[c], s_red[NS + c]), fmax(s_red[2 * NS + c], s_red[3 * NS + c]));
-}
-
 } // namespace
 
 // ---- 1. per element: elem[e] = (sx, sy, txy, vm)

@@ -19,6 +19,8 @@ struct MemberBatch {
     const double *xy;   // caller-order coordinates
     int64_t xy_stride;  // doubles: 2N or 0
     const double *u;    // [count][2N] solved displacements, caller numbering
+    const double *scale; // the element stiffness field (mag_set_element_scale): E values every member shares, or null -- then no
+                         // term is multiplied by anything
 };
 
 struct SensBatch : MemberBatch {

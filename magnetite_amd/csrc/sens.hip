@@ -44,18 +44,17 @@ __device__ inline void corner_gradient(const double2 (&c)[3], const double2 (&d)
 
 // The node pass: dxy[2i + d] = sum over the node's incident triangles, in the order of its incidence list, of the triangle's
 // energy derivative with respect to coordinate d of the node (u held fixed).  Fields: coordinates, u.
-struct Gradient {
+struct Gradient : ScaledCorners {
     double nu, cm;
     double2 *dxy;
-    struct Node {
-        double gx, gy;
-    };
-    __device__ Gradient(const Member &m, const SensBatch &sb)
-        : nu(m.nu), cm(m.youngs * m.thick / (4.0 * (1.0 - m.nu * m.nu))), dxy((double2 *)sb.dxy)
+    __device__ Gradient(const Member &m, const SensBatch &sb, const SensMesh &mesh)
+        : ScaledCorners(m, mesh), nu(m.nu), cm(m.youngs * m.thick / (4.0 * (1.0 - m.nu * m.nu))), dxy((double2 *)sb.dxy)
     {
     }
-    __device__ Node node(int64_t) const { return {0.0, 0.0}; }
-    __device__ void corner(Node &n, const double2 (&f)[2][3], int32_t) const { corner_gradient(f[0], f[1], nu, cm, n.gx, n.gy); }
+    __device__ void corner(Node &n, const double2 (&f)[2][3], int32_t k) const
+    {
+        corner_gradient(f[0], f[1], nu, factor(n, k, cm), n.gx, n.gy);
+    }
     __device__ void store(const Node &n, int64_t at) const { dxy[at] = make_double2(n.gx, n.gy); }
 };
 
@@ -72,7 +71,8 @@ __global__ void __launch_bounds__(256) k_sens_energy(const int32_t *conn, int64_
     load_corners(src, conn, e, 0, f);
     const ElemState s = elem_state(f[0], f[1]);
     const double Q = elem_Q(s, m.nu), om = 1.0 - m.nu * m.nu;
-    const double k = m.youngs * m.thick / (4.0 * s.A2);
+    double k = m.youngs * m.thick / (4.0 * s.A2);
+    if (m.scale) k *= m.scale[e];
     sb.energy[v * E + e] = k * Q / om;
     // d/dnu of Q / (1 - nu^2)
     sb.nuterm[v * E + e] = k * ((2.0 * s.p * s.q - 0.5 * s.r * s.r) / om + 2.0 * m.nu * Q / (om * om));
@@ -84,7 +84,7 @@ __global__ void __launch_bounds__(256) k_sens_nodes_tile(SensMesh mesh, SensBatc
     extern __shared__ __attribute__((aligned(16))) double2 s_img[];
     const Member m = member_of(sb, blockIdx.y, mesh.N);
     const double2 *const src[2] = {m.xy, m.u};
-    tile_walk(mesh, src, s_img, Gradient(m, sb));
+    tile_walk(mesh, src, s_img, Gradient(m, sb, mesh));
 }
 
 // ---- ... or gathered from memory
@@ -92,7 +92,7 @@ __global__ void __launch_bounds__(256) k_sens_nodes(SensMesh mesh, SensBatch sb)
 {
     const Member m = member_of(sb, blockIdx.y, mesh.N);
     const double2 *const src[2] = {m.xy, m.u};
-    gather_walk(mesh, src, Gradient(m, sb));
+    gather_walk(mesh, src, Gradient(m, sb, mesh));
 }
 
 // ---- 3. scalars, stage one: W, dW/dnu over the elements; external work, reaction work over the DOFs

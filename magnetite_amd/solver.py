@@ -596,6 +596,75 @@ class Context:
             final = prob
         return dict(history=history, problem=final, result=result, recovery=field)
 
+    # -- element stiffness field and the density design update on it --------------------------------------------------
+    DESIGN_INFO = ("volume_fraction", "lagrange", "change", "greyness", "reachable", "steps", "J")
+
+    def set_element_scale(self, scale):
+        """mag_set_element_scale: a relative stiffness scale per element (E values, finite and > 0), K = sum_e s_e K_e; None
+        clears the field.  Drops the results of run() and run_cases(); ends a design."""
+        if scale is None:
+            return self._check(self._L.mag_set_element_scale(self._h, None, MAG_MEM_HOST))
+        scale = np.ascontiguousarray(scale, dtype=np.float64).reshape(-1)
+        if self.E and scale.size != self.E:
+            raise MagnetiteError("Solver", "element scale: num_elements entries are needed")
+        return self._check(self._L.mag_set_element_scale(self._h, _p(scale, C.c_double), MAG_MEM_HOST))
+
+    def design_init(self, volume_fraction=0.5, penal=3, scale_min=1e-3, rho_min=1e-3, move=0.2, filter_passes=1, rho0=None):
+        """mag_design_init on the uploaded problem: the densities rho0 (E values in (0, 1]; None: volume_fraction everywhere),
+        their filtered field and its SIMP scale, installed as the element scale."""
+        o = _lib.DesignOptions(float(volume_fraction), float(scale_min), float(rho_min), float(move), int(penal), int(filter_passes))
+        if rho0 is not None:
+            rho0 = np.ascontiguousarray(rho0, dtype=np.float64).reshape(-1)
+            if self.E and rho0.size != self.E:
+                raise MagnetiteError("Solver", "design: rho0 needs num_elements entries")
+        return self._check(self._L.mag_design_init(self._h, C.byref(o), None if rho0 is None else _p(rho0, C.c_double), MAG_MEM_HOST))
+
+    def design_step(self, dJ_ds=None):
+        """mag_design_step after run(): the optimality-criteria update under the volume constraint.  dJ_ds None: the stiffest
+        design (J = -2 Pi) from the device-resident energies of run_sensitivities("run"); otherwise E values dJ/ds_e of any
+        objective, e.g. adjoint delem / scale.  Installs the new scale: the next run() solves the updated design."""
+        if dJ_ds is not None:
+            dJ_ds = np.ascontiguousarray(dJ_ds, dtype=np.float64).reshape(-1)
+            if self.E and dJ_ds.size != self.E:
+                raise MagnetiteError("Solver", "design: dJ_ds needs num_elements entries")
+        return self._check(self._L.mag_design_step(self._h, None if dJ_ds is None else _p(dJ_ds, C.c_double), MAG_MEM_HOST))
+
+    def design_info(self):
+        """dict(volume_fraction reached, lagrange: the multiplier L, change: max |rho_new - rho|, greyness: mean(4 rho~ (1 - rho~)),
+        reachable: 1 if the volume target lay within the move limits, steps since design_init, J of the step)."""
+        info = (C.c_double * 8)()
+        self._check(self._L.mag_get_design_info(self._h, info))
+        out = dict(zip(self.DESIGN_INFO, info))
+        out["reachable"], out["steps"] = int(out["reachable"]), int(out["steps"])
+        return out
+
+    def download_design(self):
+        """dict(rho, rho_filtered, scale, dJ_drho: E values each) of the design as it stands."""
+        rho, rhof, scale, g = (np.empty(self.E) for _ in range(4))
+        o = _lib.Design(rho.ctypes.data, rhof.ctypes.data, scale.ctypes.data, g.ctypes.data, MAG_MEM_HOST, 0)
+        self._check(self._L.mag_download_design(self._h, C.byref(o)))
+        return dict(rho=rho, rho_filtered=rhof, scale=scale, dJ_drho=g)
+
+    def topopt(self, prob, iters=30, volume_fraction=0.5, penal=3, scale_min=1e-3, rho_min=1e-3, move=0.2, filter_passes=1, rho0=None):
+        """Density topology optimisation of the stiffest design (J = -2 Pi) on a meshgen.Problem, the design staying on the
+        device: upload, design_init, then `iters` times run + run_sensitivities + design_step.  Returns dict(history: per
+        iteration dict(J, volume_fraction, change, greyness, reachable, lagrange, iterations, cg_kernel, ms_order,
+        ms_csr_symbolic), J being that of the design the iteration SOLVED and the rest of the update that followed; rho,
+        rho_filtered, scale: the final design, which no run has solved yet)."""
+        self.upload_problem(prob)
+        self.design_init(volume_fraction, penal, scale_min, rho_min, move, filter_passes, rho0)
+        history = []
+        for _ in range(int(iters)):
+            self.run()
+            st = self.stats()
+            self.run_sensitivities("run")
+            self.design_step()
+            info = self.design_info()
+            info.pop("steps")
+            history.append(dict(info, **{k: st[k] for k in ("iterations", "cg_kernel", "ms_order", "ms_csr_symbolic")}))
+        final = self.download_design()
+        return dict(history=history, rho=final["rho"], rho_filtered=final["rho_filtered"], scale=final["scale"])
+
     # -- modal analysis: the lowest natural frequencies and mode shapes of the uploaded part ------------
     MODAL_INFO =("modes", "subspace", "outer", "converged", "vectors_per_launch", "launches", "redone")
 

@@ -382,14 +382,34 @@ void modes_output(const Modes &m, size_t num_nodes, const std::string &path)
     std::printf("info: wrote mode shapes to %s\n", path.c_str());
 }
 
+// "dir/elements.csv" -> "dir/density.csv"
+std::string density_name(const std::string &elements_output)
+{
+    const size_t slash = elements_output.find_last_of('/');
+    return (slash == std::string::npos ? std::string() : elements_output.substr(0, slash + 1)) + "density.csv";
+}
+
+// the design of solver::download_design, a row per element, floats as csv_output prints them
+void density_output(const Design &d, const std::string &path)
+{
+    std::FILE *df = std::fopen(path.c_str(), "w");
+    if (!df) die({MagnetiteError::Solver, "Failed to create density.csv: " + path});
+    std::fputs("element,rho,rho_filtered,scale\n", df);
+    for (size_t e = 0; e < d.rho.size(); ++e)
+        std::fprintf(df, "%zu,%s,%s,%s\n", e, rust_display(d.rho[e]).c_str(), rust_display(d.rho_filtered[e]).c_str(),
+                     rust_display(d.scale[e]).c_str());
+    std::fclose(df);
+    std::printf("info: wrote the design to %s\n", path.c_str());
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
 {
     std::string input, mesh, nodes_out = "nodes.csv", elements_out = "elements.csv";
     bool dry = false, recover = false;
-    int modal_modes = 0, adapt = 0, refine_split = 1;
-    double rel = 0.0, density = 0.0, refine_fraction = 0.2;
+    int modal_modes = 0, adapt = 0, refine_split = 1, topopt = 0, penal = 3, filter_passes = 1;
+    double rel = 0.0, density = 0.0, refine_fraction = 0.2, volume_fraction = 0.5;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--dry-run") dry = true;
@@ -399,6 +419,10 @@ int main(int argc, char **argv)
         else if (a == "--adapt" && i + 1 < argc) adapt = std::atoi(argv[++i]);
         else if (a == "--refine-fraction" && i + 1 < argc) refine_fraction = std::atof(argv[++i]);
         else if (a == "--refine-split" && i + 1 < argc) refine_split = std::atoi(argv[++i]);
+        else if (a == "--topopt" && i + 1 < argc) topopt = std::atoi(argv[++i]);
+        else if (a == "--volume-fraction" && i + 1 < argc) volume_fraction = std::atof(argv[++i]);
+        else if (a == "--penal" && i + 1 < argc) penal = std::atoi(argv[++i]);
+        else if (a == "--filter-passes" && i + 1 < argc) filter_passes = std::atoi(argv[++i]);
         else if (a == "--nodes" && i + 1 < argc) nodes_out = argv[++i];
         else if (a == "--elements" && i + 1 < argc) elements_out = argv[++i];
         else if (a == "--rel" && i + 1 < argc) rel = std::atof(argv[++i]);
@@ -407,12 +431,15 @@ int main(int argc, char **argv)
         else die({MagnetiteError::Input, "Unrecognized argument " + a});
     }
     if (input.empty() || mesh.empty()) {
-        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery] [--modal P --density RHO] [--adapt R [--refine-fraction T] [--refine-split 1|3]]\n");
+        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery] [--modal P --density RHO] [--adapt R [--refine-fraction T] [--refine-split 1|3]] [--topopt ITERS [--volume-fraction F] [--penal P] [--filter-passes K]]\n");
         return 2;
     }
     if (modal_modes < 0 || (modal_modes > 0 && !(density > 0.0))) die({MagnetiteError::Input, "--modal P needs P >= 1 and --density RHO > 0"});
     if (adapt < 0 || !(refine_fraction > 0.0 && refine_fraction <= 1.0) || (refine_split != 1 && refine_split != 3))
         die({MagnetiteError::Input, "--adapt R needs R >= 0, --refine-fraction T in (0, 1] and --refine-split 1 or 3"});
+    if (topopt < 0 || !(volume_fraction > 0.0 && volume_fraction <= 1.0) || penal < 1 || penal > 8 || filter_passes < 0 || filter_passes > 8)
+        die({MagnetiteError::Input, "--topopt ITERS needs ITERS >= 0, --volume-fraction F in (0, 1], --penal 1..8 and --filter-passes 0..8"});
+    if (topopt > 0 && adapt > 0) die({MagnetiteError::Input, "--topopt designs on the mesh as given: not together with --adapt"});
     // mesher::run (mesher.rs:939-974) minus geometry parsing and the gmsh subprocess
     const std::string text = slurp(input, MagnetiteError::Input, "Unable to open input file " + input);
     JsonParser jp(text);
@@ -454,7 +481,7 @@ int main(int argc, char **argv)
         opt.stop_mode = MAG_STOP_REL;
         opt.tol = rel;
     }
-    std::vector<Node> posed = recover || modal_modes > 0 ? nodes : std::vector<Node>();  // (run() fills every value in)
+    std::vector<Node> posed = recover || modal_modes > 0 || topopt > 0 ? nodes : std::vector<Node>();  // (run() fills every value in)
     if (adapt > 0) {
         RefineSpec spec;
         spec.theta = refine_fraction;
@@ -494,6 +521,28 @@ int main(int argc, char **argv)
             std::printf("info: mode %zu frequency %s Hz residual %s\n", k + 1, rust_display(modes.frequency[k]).c_str(),
                         rust_display(modes.residual[k]).c_str());
         modes_output(modes, posed.size(), modes_name(nodes_out));
+    }
+    if (topopt > 0) {
+        // The density design needs every element counter-clockwise, as the modal analysis does: the elements go in by their true sign.
+        std::vector<Element> ccw = elements;
+        for (Element &e : ccw)
+            if (solver::compute_element_area(e, posed) < 0.0) std::swap(e.nodes[0], e.nodes[2]);
+        opt.verbose = 0;
+        DesignSpec spec;
+        spec.volume_fraction = volume_fraction;
+        spec.penal = penal;
+        spec.filter_passes = filter_passes;
+        FieldSession session;
+        if (Result err = solver::design_init(session, posed, ccw, meta, spec, &opt)) die(*err);
+        for (int k = 0; k < topopt; ++k) {
+            DesignInfo info;
+            if (Result err = solver::design_step(session, &info)) die(*err);
+            std::printf("info: topopt iteration %d: J %s, volume %s, change %s\n", k, rust_display(info.J).c_str(),
+                        rust_display(info.volume_fraction).c_str(), rust_display(info.change).c_str());
+        }
+        Design design;
+        if (Result err = solver::download_design(session, design)) die(*err);
+        density_output(design, density_name(elements_out));
     }
     return 0;
 }
