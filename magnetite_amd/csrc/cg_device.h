@@ -259,28 +259,36 @@ __device__ inline void ring_pad_entries(uint32_t (&w)[NW], int32_t nent)
     }
 }
 
-// The walk over a node's NB blocks: all NB gathers of p in one straight-line block (ring_pad_entries made every entry a
-// valid slot; a zero block adds nothing), one FMA per term.  folded: the fan closes inside the blocks (nothing to telescope).
-template <int NW, int NB, uint32_t IDMASK = 0xfffu>
+// The walk over a node's NB blocks: the gathers of p go out in groups of G, each group in one piece before the FMAs that use it
+// (ring_pad_entries made every entry a valid slot; a zero block adds nothing), one FMA per term.  G = 0 leaves the placement
+// to the scheduler -- which, at the register ceiling of the four-slot kernels, turned "all NB in one block" into one gather,
+// one full lgkmcnt(0), four FMAs, six times per node slot.  G > 0 pins it: a scheduling barrier behind each group's loads, so
+// that the waits become counted ones (lgkmcnt(G - 1) ... 0) over G loads in flight.  The FMAs into fx, fy keep their order
+// whatever G is: the same bits.  folded: the fan closes inside the blocks (nothing to telescope).
+template <int NW, int NB, uint32_t IDMASK = 0xfffu, int G = 0>
 __device__ inline void ring_walk_blocks(const uint32_t (&w)[NW], const double2 *s_p, const double2 pa, double kappa,
                                         bool folded, const double (&kb)[3 * NB], double &fx, double &fy)
 {
+    constexpr int GG = G ? G : 1; // (G = 0: gather, FMAs, gather, FMAs ... in program order, and no barrier)
+    static_assert(NB % GG == 0, "whole groups");
     auto entry = [&](int k) { return (k & 1) ? (w[k >> 1] >> 16) : (w[k >> 1] & 0xffffu); };
     double2 u0, ul;
-    {
-        const double2 cp = s_p[entry(0) & IDMASK];
-        u0 = make_double2(cp.x - pa.x, cp.y - pa.y);
-        fx = fma(kb[1], u0.y, fma(kb[0], u0.x, fx)); // one FMA per term (a sum of two products first costs a third operation)
-        fy = fma(kb[2], u0.y, fma(kb[1], u0.x, fy));
-        ul = u0;
-    }
 #pragma unroll
-    for (int k = 1; k < NB; ++k) {
-        const double2 cp = s_p[entry(k) & IDMASK];
-        const double2 u = make_double2(cp.x - pa.x, cp.y - pa.y);
-        fx = fma(kb[3 * k + 1], u.y, fma(kb[3 * k], u.x, fx));
-        fy = fma(kb[3 * k + 2], u.y, fma(kb[3 * k + 1], u.x, fy));
-        ul = u;
+    for (int g = 0; g < NB; g += GG) {
+        double2 cp[GG];
+#pragma unroll
+        for (int i = 0; i < GG; ++i) cp[i] = s_p[entry(g + i) & IDMASK];
+        if (G) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < GG; ++i) {
+            const int k = g + i;
+            const double2 u = make_double2(cp[i].x - pa.x, cp[i].y - pa.y);
+            // one FMA per term (a sum of two products first costs a third operation)
+            fx = fma(kb[3 * k + 1], u.y, fma(kb[3 * k], u.x, fx));
+            fy = fma(kb[3 * k + 2], u.y, fma(kb[3 * k + 1], u.x, fy));
+            if (k == 0) u0 = u;
+            ul = u;
+        }
     }
     const double kap = folded ? 0.0 : kappa; // a fan closed inside the blocks: its antisymmetric parts cancel
     fx = fma(kap, ul.y - u0.y, fx);          // otherwise they telescope to kappa J (u_last - u_first)
@@ -294,32 +302,13 @@ __device__ inline void ring_walk_blocks(const uint32_t (&w)[NW], const double2 *
 // block on a valid slot, so a step is straight-line code -- two record reads, one gather, six fp64 operations.  u_first
 // and u_last of an OPEN fan are always register entries (k_edge_blocks_ovf puts an open row's last entry into block
 // NB - 1 and its middle ones into the pool), so the telescoped antisymmetric part needs nothing from the pool.  Same sums
-// as the short rows', block after block.
-template <int NW, int NB, uint32_t IDMASK = 0xfffu>
+// as the short rows', block after block: the register part IS the short rows' walk.
+template <int NW, int NB, uint32_t IDMASK = 0xfffu, int G = 0>
 __device__ inline void ring_walk_blocks_ovf(const uint32_t (&w)[NW], const double2 *s_p, const double2 pa, double kappa,
                                             bool folded, const double (&kb)[3 * NB], const double2 *pool, uint32_t off,
                                             uint32_t cnt, int32_t nmax, double &fx, double &fy)
 {
-    auto entry = [&](int k) { return (k & 1) ? (w[k >> 1] >> 16) : (w[k >> 1] & 0xffffu); };
-    double2 u0, ul;
-    {
-        const double2 cp = s_p[entry(0) & IDMASK];
-        u0 = make_double2(cp.x - pa.x, cp.y - pa.y);
-        fx = fma(kb[1], u0.y, fma(kb[0], u0.x, fx));
-        fy = fma(kb[2], u0.y, fma(kb[1], u0.x, fy));
-        ul = u0;
-    }
-#pragma unroll
-    for (int k = 1; k < NB; ++k) {
-        const double2 cp = s_p[entry(k) & IDMASK];
-        const double2 u = make_double2(cp.x - pa.x, cp.y - pa.y);
-        fx = fma(kb[3 * k + 1], u.y, fma(kb[3 * k], u.x, fx));
-        fy = fma(kb[3 * k + 2], u.y, fma(kb[3 * k + 1], u.x, fy));
-        ul = u;
-    }
-    const double kap = folded ? 0.0 : kappa;
-    fx = fma(kap, ul.y - u0.y, fx);
-    fy = fma(-kap, ul.x - u0.x, fy);
+    ring_walk_blocks<NW, NB, IDMASK, G>(w, s_p, pa, kappa, folded, kb, fx, fy);
     auto rec_of = [&](int32_t k) { return 2u * ((uint32_t)k < cnt ? off + (uint32_t)k : 0u); };
     auto apply = [&](const double2 a, const double2 b) {
         const double2 cp = s_p[(uint32_t)__double2loint(b.y)];

@@ -783,6 +783,20 @@ __device__ inline PersistParams persist_variant_operator(PersistParams P)
     return P;
 }
 
+// Gathers per group in the ring walks of an instantiation (cg_device.h, ring_walk_blocks; 0: the scheduler's placement).
+// Pinned where the scheduler, at the register ceiling, serialises them -- one gather, a full lgkmcnt(0), four FMAs, six LDS
+// round trips per node slot: the four-slot edge-block kernels of one GPU on a grid.  Two groups of three in the structured
+// kernels (six at once are 24 registers: they went to scratch inside the walk), three groups of two in the overflow kernel of
+// the 512-node tiles (measured: 6.15 / 6.05 / 5.98 us per iteration unpinned / G = 3 / G = 2 at 1M triangles).  Everything else
+// keeps the scheduler's placement, which has three to four gathers in flight in most walks there: one to three node slots
+// LOSE with all six pinned up front (3.48 -> 3.51, 4.11 -> 4.15, 4.67 -> 4.75 us; overflow 4.53 -> 4.71 at two slots), the
+// single-workgroup kernels are pipelined as they are, the multi-GPU kernels are not this function's business.
+constexpr int persist_walk_group(int B, bool MG, int EBM, bool ONE, int NPT)
+{
+    if (EBM == 0 || MG || ONE || NPT != 4) return 0;
+    return EBM == 2 && B == 512 ? 2 : 3;
+}
+
 // EBM: 0 the triangle walk, 1 edge blocks in registers (every row of the mesh a fan of at most six blocks: structured meshes),
 // 2 edge blocks with OVERFLOW (round 4: rows that are one fan of any length -- what gmsh's frontal meshes look like, a quarter
 // of their nodes with seven neighbours: blocks beyond the six in registers sit in an LDS pool of 32-byte records).
@@ -814,7 +828,9 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
     const PersistParams &P = LC ? Pc : Pk;
     constexpr int NPT = NPTX ? NPTX : kPersistNpt;
     constexpr bool EB = EBM != 0, OV = EBM == 2;
-    constexpr bool OPQ = OV; // the thread index behind an empty asm in the overflow instantiation: see persist_block_sum
+    // the thread index behind an empty asm in the overflow instantiations, and in the structured kernel of the 256-node tiles
+    // (25 spills without, two of them reloaded inside the first slot's walk): see persist_block_sum
+    constexpr bool OPQ = OV || (EB && !MG && B == 256);
     constexpr int SB = NPT * THREADS / B - 1; // bias of the workgroup-relative ring entries, in tile images (see the remap below)
     extern __shared__ __attribute__((aligned(16))) double2 smem[];
     const int tid = threadIdx.x;
@@ -1100,6 +1116,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
     // launches the triangle-walk instantiation for any other mesh.
     constexpr int NB = kPersistBlockEntries;
     constexpr bool BLOCKS = EB;
+    constexpr int WG = persist_walk_group(B, MG, EBM, ONE, NPT); // gathers per group in the walks
     constexpr int NKB = BLOCKS ? 3 * NB : NCW;
     double wgt[NPT][NKB];
     const double kappa = uniform_f64(0.5 * (h - nu) * c0);
@@ -1295,12 +1312,12 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
                     const uint32_t toff = (uint32_t)(SB * tile_words);
                     if (OV) {
                         const uint32_t oc = (ovpk[s >> 1] >> (16 * (s & 1))) & 0xffffu;
-                        ring_walk_blocks_ovf<kPersistRegs, NB, 0x7fffu>(w[s], pim - SB * tile_words, pa, kappa, (flags[s] & 32u) != 0,
-                                                                        *reinterpret_cast<const double(*)[3 * NB]>(&wgt[s][0]), s_pool,
-                                                                        oc & 0xfffu, oc >> 12, ovmax[s], fx, fy);
+                        ring_walk_blocks_ovf<kPersistRegs, NB, 0x7fffu, WG>(
+                            w[s], pim - SB * tile_words, pa, kappa, (flags[s] & 32u) != 0,
+                            *reinterpret_cast<const double(*)[3 * NB]>(&wgt[s][0]), s_pool, oc & 0xfffu, oc >> 12, ovmax[s], fx, fy);
                     } else if (BLOCKS)
-                        ring_walk_blocks<kPersistRegs, NB, 0x7fffu>(w[s], pim - SB * tile_words, pa, kappa, (flags[s] & 32u) != 0,
-                                                                    *reinterpret_cast<const double(*)[3 * NB]>(&wgt[s][0]), fx, fy);
+                        ring_walk_blocks<kPersistRegs, NB, 0x7fffu, WG>(w[s], pim - SB * tile_words, pa, kappa, (flags[s] & 32u) != 0,
+                                                                        *reinterpret_cast<const double(*)[3 * NB]>(&wgt[s][0]), fx, fy);
                     else
                         ring_walk_cached<kPersistRegs, NCW, 0x7fffu>(w[s], P.ell16 + ell_off[s], B, nent, xy - SB * tile_words, pim - SB * tile_words,
                                                                      ca, pa, c0, nu, h, *reinterpret_cast<const double(*)[NCW]>(&wgt[s][0]),
@@ -1404,9 +1421,13 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
     }
 #endif
     // x of iterate j-1 is in LDS; the verdict is the same in every workgroup
+    // (four slots with pinned walks: the node ids behind an empty asm -- as the start-up's 64-bit indices, which the compiler
+    // would otherwise keep for this line, they are six registers spilled across the whole loop)
+    int tid_x = tid;
+    if (WG) asm volatile("" : "+v"(tid_x));
 #pragma unroll
     for (int s = 0; s < NPT; ++s)
-        if ((flags[s] & 24) == 24) P.x[node_of(s)] = (t_xy(s) + capx + cap + maxh)[t_lt(s)];
+        if ((flags[s] & 24) == 24) P.x[node_base + s * THREADS + tid_x] = (t_xy(s) + capx + cap + maxh)[t_lt(s)];
     if (blockIdx.x == 0 && tid == 0) {
         FusedState *st = P.st;
         st->bb = bb;
