@@ -586,7 +586,8 @@ int mag_get_modal_stats(const mag_ctx *ctx, int32_t j, mag_stats *stats);
  *   marked edges   split = 1: the longest edge of every marked element; split = 3: all three of its edges (Rivara's
  *              four-triangle variant: h halves where marked);
  *   closure    every element with a marked edge gets its longest edge marked, swept until a sweep marks nothing.  The marked set
- *              is the least fixed point: it does not depend on the order of a sweep, the number of sweeps does;
+ *              is the least fixed point.  A sweep reads the flags as they were before it, so the number of sweeps is the same in
+ *              every run as well;
  *   new nodes  marked edge number r in edge-id order becomes node N + r at 0.5 * (x[lo] + x[hi]), 0.5 * (y[lo] + y[hi]).  Old
  *              nodes keep index, coordinates and boundary data.  Per DOF d of a new node: where u_known[2 lo + d] and
  *              u_known[2 hi + d] are both set, u_known = 1, u_in = 0.5 * (u_in[2 lo + d] + u_in[2 hi + d]); otherwise u_known = 0,

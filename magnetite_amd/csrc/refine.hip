@@ -7,7 +7,8 @@
 //   longest     the local edge of largest len2, on a tie the smaller edge id: a total order on the edges;
 //   closure     an element with a marked edge gets its longest edge marked, swept until nothing changes.  The marked set is the
 //               least fixed point of a monotone rule on a finite set, so it does not depend on which of a sweep's own writes a
-//               sweep sees; flags are one 32-bit word per edge, written and read with relaxed device-scope atomics;
+//               sweep sees; the NUMBER of sweeps would, so a sweep reads a copy of the flags made before it (Jacobi); flags are
+//               one 32-bit word per edge, written with relaxed device-scope atomic stores;
 //   new nodes   marked edge number r in edge-id order becomes node N + r, the midpoint 0.5 * (x[lo] + x[hi]);
 //   children    of element e at off[e] .. off[e + 1], the element rotated so that its longest edge comes first.
 // No floating-point sum and no floating-point atomic anywhere.
@@ -21,7 +22,6 @@ constexpr int kBlock = 256;
 
 inline dim3 blocks_for(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
 
-__device__ inline uint32_t flag_load(const uint32_t *f) { return __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ inline void flag_set(uint32_t *f) { __hip_atomic_store(f, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __device__ inline double len2_of(const double2 *xy, int32_t a, int32_t b)
@@ -156,14 +156,15 @@ __global__ void __launch_bounds__(kBlock) k_rf_mark_edges(const uint8_t *marks, 
     }
 }
 
-// ---- one closure sweep: an element with a marked edge gets its longest edge marked
-__global__ void __launch_bounds__(kBlock) k_rf_sweep(const int32_t *eid, const uint8_t *lng, int64_t E, uint32_t *flag,
-                                                     uint32_t *changed)
+// ---- one closure sweep: an element with a marked edge gets its longest edge marked.  `seen`: the flags as they were before the
+// sweep (a copy: no write of this launch), so that what a sweep marks, and with it the number of sweeps, is the same in every run
+__global__ void __launch_bounds__(kBlock) k_rf_sweep(const int32_t *eid, const uint8_t *lng, int64_t E, const uint32_t *seen,
+                                                     uint32_t *flag, uint32_t *changed)
 {
     const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (e >= E) return;
     const int32_t id[3] = {eid[3 * e], eid[3 * e + 1], eid[3 * e + 2]};
-    const uint32_t f[3] = {flag_load(&flag[id[0]]), flag_load(&flag[id[1]]), flag_load(&flag[id[2]])};
+    const uint32_t f[3] = {seen[id[0]], seen[id[1]], seen[id[2]]};
     const int L = lng[e];
     if ((f[0] | f[1] | f[2]) && !f[L]) {
         flag_set(&flag[id[L]]);
@@ -298,8 +299,11 @@ void refine_mark_edges(const RefineTables &t, int split, hipStream_t s)
 
 void refine_sweeps(const RefineTables &t, int sweeps, hipStream_t s)
 {
-    for (int j = 0; j < sweeps && j < kRefineSweepBatch; ++j)
-        k_rf_sweep<<<blocks_for(t.E), kBlock, 0, s>>>(t.eid, t.lng, t.E, t.flag, t.counters + RF_CHANGED + j);
+    // (mid is free until the scan after the closure: it holds the flags a sweep reads)
+    for (int j = 0; j < sweeps && j < kRefineSweepBatch; ++j) {
+        (void)hipMemcpyAsync(t.mid, t.flag, 4 * (3 * (size_t)t.E + 1), hipMemcpyDeviceToDevice, s);
+        k_rf_sweep<<<blocks_for(t.E), kBlock, 0, s>>>(t.eid, t.lng, t.E, (const uint32_t *)t.mid, t.flag, t.counters + RF_CHANGED + j);
+    }
 }
 
 void refine_child_counts(const RefineTables &t, hipStream_t s)

@@ -4,12 +4,11 @@ that reaches every row; here the answers are held against a transcription of the
 header existed -- persist_launch's two ladders, persist_launch_general, persist_cases_shape, persist_launch_cases and
 persist_launch_variants -- written from those functions, not from the header."""
 import itertools
-import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from persist_shapes_util import compile_and_parse
+
 SINGLE, CASES, VARIANTS = 0, 1, 2
 NPT = 4  # kPersistNpt
 
@@ -72,27 +71,7 @@ def domain():
 
 @pytest.fixture(scope="module")
 def printed(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("persist_shapes") / "persist_shapes")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "magnetite_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "cpp", "persist_shapes.cpp"), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60, check=True).stdout.splitlines()
-    rows = {"main": [], "k4": [], "cases": [], "variants": []}
-    shapes = {}
-    for ln in out:
-        w = ln.split()
-        if w[0] == "row":
-            v = [int(x) for x in w[2:]]
-            rows[w[1]].append((v[0], bool(v[1]), v[2], bool(v[3]), v[4]))
-        else:
-            assert w[0] == "shape" and w[7] == ":"
-            key = tuple(int(x) for x in w[1:7])
-            assert key not in shapes
-            if w[8] == "none":
-                shapes[key] = None
-            else:
-                v = [int(x) for x in w[8:]]
-                shapes[key] = ((v[0], bool(v[1]), v[2], bool(v[3]), v[4]), v[5])
-    return rows, shapes
+    return compile_and_parse(tmp_path_factory.mktemp("persist_shapes"))
 
 
 def test_the_lists_have_31_1_11_and_11_distinct_rows(printed):
