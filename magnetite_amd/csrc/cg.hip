@@ -1761,6 +1761,8 @@ int fused32_grid(int32_t B, int32_t cap, int32_t tiles)
     if (e != hipSuccess || per_cu < 1) per_cu = 1;
     long g = (long)per_cu * cus;
     if (g > kMaxGrid) g = kMaxGrid;
+    if (const char *cap_env = getenv("MAG_TUNE_GRID")) // tests: few workgroups, so each walks several tiles (as fused_grid)
+        if (atoi(cap_env) > 0 && g > atoi(cap_env)) g = atoi(cap_env);
     if (g > tiles) g = tiles;
     return g < 1 ? 1 : (int)g;
 }

@@ -56,15 +56,15 @@ class HostAllReduce:
         self.barrier.wait()
 
 
-def run_ranks(prob, inboxes, solves=1, inbox_bytes=1 << 20, **opts):
-    comm = HostAllReduce(R)
-    sync = threading.Barrier(R, timeout=180)
-    handles, results, errors = [None] * R, [None] * R, []
+def run_ranks(prob, inboxes, solves=1, inbox_bytes=1 << 20, ranks=R, **opts):
+    comm = HostAllReduce(ranks)
+    sync = threading.Barrier(ranks, timeout=180)
+    handles, results, errors = [None] * ranks, [None] * ranks, []
 
     def worker(rank):
         try:
             with Context(device=0, **opts) as c:
-                c.init_callback(lambda a, r=rank: comm(r, a), rank, R)
+                c.init_callback(lambda a, r=rank: comm(r, a), rank, ranks)
                 if inboxes:
                     handles[rank] = c.create_inbox(inbox_bytes)
                     sync.wait()
@@ -81,7 +81,7 @@ def run_ranks(prob, inboxes, solves=1, inbox_bytes=1 << 20, **opts):
             comm.barrier.abort()
             sync.abort()
 
-    threads = [threading.Thread(target=worker, args=(r,)) for r in range(R)]
+    threads = [threading.Thread(target=worker, args=(r,)) for r in range(ranks)]
     for t in threads:
         t.start()
     for t in threads:
@@ -247,6 +247,37 @@ def test_eight_ranks_fp32_leg_of_config5(case):
         assert 1e-9 < rel(out["u"], ref["u"]) < 5e-4     # fp32 accuracy, as on one GPU
         assert 0 < out["nnz"] < 0.3 * one["nnz"]
         assert np.array_equal(out["u"], results[0][0]["u"])
+
+
+@pytest.mark.parametrize("grid", [None, "2"])
+@pytest.mark.parametrize("tile", [256, 512])
+def test_two_ranks_fp32_operator_probe(built, tile, grid, monkeypatch):
+    """k_cg_fused32<.., COMM = true> against the float32 twin (tests/fp32_twin.py, test_fp32_leg_gpu.py): the operator probe
+    of the one-rank tests on two ranks over the callback transport -- interface q through the exchange buffer, the records
+    of interface nodes the other rank owns advanced locally -- with the one-rank bars, and once more with two workgroups per
+    rank (MAG_TUNE_GRID=2), so that every workgroup walks several tiles and the ghost loop runs on a grid smaller than the
+    rank's tile count.  Every rank returns the same bits."""
+    import fp32_cases as fc
+    if grid:
+        monkeypatch.setenv("MAG_TUNE_GRID", grid)
+    name = "holes56_grid3"  # 3064 nodes: 12 tiles of 256, 6 of 512
+    p = fc.problem(name)
+    assert all(f[2] == 2 for f in fc.family_probe(name))
+    bar, alpha_bar = fc.bars(name)
+    opts = dict(precision=1, tile_nodes=tile)
+    one = run_ranks(p, inboxes=False, ranks=2, max_iter=1, **opts)
+    two = run_ranks(p, inboxes=False, ranks=2, max_iter=2, **opts)
+    for rank in range(2):
+        a, b = one[rank][0], two[rank][0]
+        assert a["cg_kernel"] == b["cg_kernel"] == 4 and a["comm_info"]["ranks"] == 2 and b["comm_info"]["rank"] == rank
+        assert a["iterations"] == 1 and b["iterations"] == 2 and b["best_iteration"] == 2 and b["best_param_mismatch"] == 0
+        assert b["num_tiles"] >= (6 if grid else 2)
+        assert np.array_equal(a["u"], one[0][0]["u"]) and np.array_equal(b["u"], two[0][0]["u"])
+    ratio, alpha_dev = fc.probe(name, one[0][0]["u"], two[0][0]["u"])
+    print(f"[fp32 probe, 2 ranks] {name} tile {tile} grid {grid}: ratio {ratio:.2f} (family max {bar / 4:.2f}), alpha1 deviation "
+          f"{alpha_dev:.2e} (family max {alpha_bar / 4:.2e})")
+    assert ratio <= bar, (ratio, bar)
+    assert alpha_dev <= alpha_bar, (alpha_dev, alpha_bar)
 
 
 @pytest.mark.parametrize("inboxes,variant,exchange", [(False, 1, 1), (True, 1, 3), (True, 2, 2)])

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle
+from fp32_cases import zoo_mesh
 from magnetite_amd import Context, MagnetiteError, _lib, meshgen
 from magnetite_amd._lib import (MAG_ERR_BAD_ARGS, MAG_ERR_BC_MISMATCH, MAG_OP_CSR, MAG_STOP_REL,
                                 MAG_STOP_RNORM_SQ)
@@ -703,32 +704,7 @@ def test_ring_table_on_irregular_node_stars(built):
     node (bow-tie), an edge shared by three triangles (non-manifold), mixed CCW / CW orientation, shuffled element
     order, and a 40-fan (ring longer than the register-resident words, built by the > 32 fallback)."""
     rng = np.random.default_rng(5)
-    base = meshgen.plate(6, 5)
-    xy = [tuple(v) for v in base.xy]
-    tri = [list(t) for t in base.conn]
-
-    def add(pt):
-        xy.append(pt)
-        return len(xy) - 1
-
-    # bow-tie: a second, separate fan hanging off node 0 (corner of the plate), not edge-connected to the first
-    a, b = add((-0.3, -0.1)), add((-0.1, -0.3))
-    tri.append([0, a, b])
-    # non-manifold edge: a third triangle on an interior edge of the plate
-    e0, e1 = tri[7][0], tri[7][1]
-    c = add((0.5 * (xy[e0][0] + xy[e1][0]) + 0.01, 0.5 * (xy[e0][1] + xy[e1][1]) + 0.013))
-    tri.append([e0, e1, c])
-    # 40-fan around a new hub, attached to the plate through one node
-    hub = add((2.0, 2.0))
-    ring = [add((2.0 + 0.4 * np.cos(t), 2.0 + 0.4 * np.sin(t))) for t in np.linspace(0, 2 * np.pi, 40, endpoint=False)]
-    for k in range(40):
-        tri.append([hub, ring[k], ring[(k + 1) % 40]])
-    tri.append([base.num_nodes - 1, ring[25], ring[24]])
-    tri = np.array(tri, dtype=np.int32)
-    flip = rng.random(len(tri)) < 0.3                      # mixed orientation: CW elements get negative stiffness
-    tri[flip] = tri[flip][:, ::-1]
-    tri = tri[rng.permutation(len(tri))]
-    m = meshgen.Mesh(np.array(xy, dtype=np.float64), np.ascontiguousarray(tri), "zoo")
+    m = zoo_mesh(rng)  # (shared with the fp32 leg's tests)
     p = meshgen.apply_boundary_rules(m, [meshgen.BoundaryRule("hold", x_max=1e-9, ux=0.0, uy=0.0)])
     K = oracle.assemble_sparse(p.xy_flat, p.conn_flat, p.poisson_ratio, p.youngs_modulus, p.part_thickness)
     x = rng.standard_normal(2 * m.num_nodes)
