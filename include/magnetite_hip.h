@@ -128,8 +128,17 @@ typedef struct mag_options {
                              diagonal blocks of K_ff (inverse blocks kept in fp32).  Same stop rule on the true
                              residual norm, same solution within the tolerance, fewer iterations on graded meshes.
                              Needs the fused LDS iteration (cg_variant 1, fp64, matrix-free operator).           */
-    int32_t reserved;
+    int32_t field_cg;     /* enum mag_field_cg: the CG under an element stiffness field (mag_set_element_scale); no effect
+                             without one.  0 (default): the CSR operator's phase (mag_stats.cg_kernel 3).  OPT-IN: one fused
+                             launch per iteration over the assembled K's block rows (cg_kernel 5) -- 1 plain CG, 2 Jacobi,
+                             3 block-Jacobi on the 2x2 node-diagonal blocks of the scaled K_ff (inverse blocks in fp32).
+                             `preconditioner` still refuses a field: the field's preconditioner is chosen here alone.
+                             Falls back to the CSR operator's phase where the context has no tile-local tables
+                             (mag_stats.lds_operator 0: op_variant 1, or a tile beyond LDS).  Other values read 0.
+                             (this word was `reserved`: same offset, same size, zero means what it meant)           */
 } mag_options;
+
+enum mag_field_cg { MAG_FIELD_CG_CSR = 0, MAG_FIELD_CG_PLAIN = 1, MAG_FIELD_CG_JACOBI = 2, MAG_FIELD_CG_BLOCK_JACOBI = 3 };
 
 /* Borrowed view of the caller's flattened Vec<Node>/Vec<Element>/ModelMetadata
  * (solver.rs:543-547 arguments). */
@@ -172,7 +181,8 @@ typedef struct mag_stats {
     int32_t max_tile_halo;
     int32_t lds_operator; /* 1: LDS-halo operator ran, 0: global-gather fallback */
     int32_t cg_kernel;    /* what ran the CG: 0 two launches per iteration, 1 one fused launch per iteration,
-                             2 on-chip single launch, 3 CSR operator, 4 fp32 leg */
+                             2 on-chip single launch, 3 CSR operator, 4 fp32 leg, 5 one fused launch per iteration over
+                             the assembled K's block rows (mag_options.field_cg, under an element stiffness field) */
     int32_t exchange;     /* several ranks, how they traded per iteration: 0 one rank, 1 one all-reduce (RCCL or the test
                              transport), 2 on-chip kernels through the inboxes, 3 streaming kernels through the inboxes */
     /* per-phase device time, HIP events on the context's stream, milliseconds */
@@ -653,6 +663,10 @@ int mag_upload_refined(mag_ctx *ctx);
  *   unscaled material, which is the thickness-field and SIMP reading (a scale stands for less material carrying the same stress).
  *   CG: while a field is set the CG runs the CSR operator's phase whatever mag_options.cg_operator says (mag_stats.cg_kernel == 3):
  *   the on-chip kernel's edge blocks assume one material and the matrix-free operators carry no element id.
+ *   Opt-in, mag_options.field_cg = 1 | 2 | 3: the CG runs one fused launch per iteration over the block rows of the assembled,
+ *   scaled K instead (cg_kernel == 5; plain, Jacobi, 2x2 block-Jacobi), the rows' values gathered tile by tile after every
+ *   assembly with the Dirichlet mask applied; where the context has no tile-local tables (lds_operator == 0) the CSR operator's
+ *   phase runs as before (cg_kernel == 3).  The table of the rows is built in the first run and kept like the pattern.
  *   Load cases: mag_run_cases works under a field, K assembled once, the cases one after another (mag_get_cases_info: info[1] == 0);
  *   every case bit for bit mag_upload + mag_set_element_scale + mag_run of it.
  *   Passes: mag_run_sensitivities, mag_run_adjoint and mag_run_objective work for MAG_SET_RUN and MAG_SET_CASES; every element's term

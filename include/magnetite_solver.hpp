@@ -871,7 +871,8 @@ inline Result open_session(FieldSession &session, const std::vector<Node> &nodes
 // (mag_run, mag_run_sensitivities, then mag_design_step).  A caller who wants the single calls has them on session.ctx.
 //
 // Element stiffness field (mag_set_element_scale): the part solved with K = sum_e scale[e] K_e.  The part is uploaded into the
-// session, the field set (E values, finite and > 0) and the part solved; afterwards every node.ux/uy/fx/fy and element.stress
+// session, the field set (E values, finite and > 0) and the part solved (options->field_cg chooses the CG under the field:
+// 0 the CSR operator's phase, 1 | 2 | 3 the fused block-row kernel, plain | Jacobi | block-Jacobi); afterwards every node.ux/uy/fx/fy and element.stress
 // holds a value as after run() -- the stress is that of the unscaled material (include/magnetite_hip.h) -- and the session keeps
 // the solved part for what follows (mag_run_sensitivities ... on session.ctx).
 inline Result set_element_scale(FieldSession &session, std::vector<Node> &nodes, std::vector<Element> &elements,

@@ -17,6 +17,7 @@ MAG_OK, MAG_ERR_BAD_ARGS, MAG_ERR_BC_MISMATCH, MAG_ERR_NOT_CONVERGED = 0, 1, 2, 
 MAG_ERR_HIP, MAG_ERR_RCCL, MAG_ERR_TOO_LARGE, MAG_ERR_STATE = 4, 5, 6, 7
 MAG_STOP_RNORM, MAG_STOP_RNORM_SQ, MAG_STOP_REL = 0, 1, 2
 MAG_OP_MATRIX_FREE, MAG_OP_CSR = 0, 1
+MAG_FIELD_CG_PLAIN, MAG_FIELD_CG_JACOBI, MAG_FIELD_CG_BLOCK_JACOBI = 1, 2, 3
 MAG_TERM_NONE, MAG_TERM_TARGET_COST, MAG_TERM_MAX_ITERS, MAG_TERM_BREAKDOWN = 0, 1, 2, 3
 MAG_MEM_HOST, MAG_MEM_DEVICE = 0, 1
 MAG_SET_RUN, MAG_SET_CASES, MAG_SET_VARIANTS = 0, 1, 2
@@ -50,7 +51,7 @@ class Options(C.Structure):
                 ("cg_operator", C.c_int32), ("assemble_csr", C.c_int32), ("check_every", C.c_int32),
                 ("use_graph", C.c_int32), ("tile_nodes", C.c_int32), ("history_len", C.c_int32),
                 ("verbose", C.c_int32), ("op_variant", C.c_int32), ("cg_variant", C.c_int32), ("precision", C.c_int32),
-                ("preconditioner", C.c_int32), ("reserved", C.c_int32)]
+                ("preconditioner", C.c_int32), ("field_cg", C.c_int32)]
 
 
 class Problem(C.Structure):

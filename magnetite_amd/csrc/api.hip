@@ -3,6 +3,7 @@
 // No CPU fallback exists: without a HIP device every compute entry point
 // returns MAG_ERR_HIP with the runtime's message.
 #include <cassert>
+#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -307,6 +308,13 @@ struct mag_ctx {
     // tables and the CSR pattern held now were built under this field (with the CSR operator's choices) and a run keeps them
     DevBuf escale;
     bool field_on = false, field_sym = false;
+    // mag_options.field_cg: the tile-local block-row table of K (k_field_rows: per tile meta, slots, sources -- of this order and
+    // this pattern, dropped with either), the values gathered from kval after every assembly, the workgroups of k_cg_field
+    DevBuf fc_width, fc_meta, fc_slot, fc_src, fc_val;
+    bool fc_ready = false;
+    int64_t fc_total = 0;
+    int32_t fc_grid = 1;
+    double fc_build_ms = 0.0; // the table was built in this run: its time (mag_stats.ms_csr_symbolic)
 
     // density design (mag_design_init / mag_design_step): the densities, the filter's tables and the update's scratch; the
     // bracket, the sums and the info words live on the device between the launches of a step
@@ -382,6 +390,12 @@ struct FieldOperator {
     ~FieldOperator() { ctx->opt.cg_operator = cg_operator; }
 };
 inline const double *field_of(const mag_ctx *ctx) { return ctx->field_on ? ctx->escale.as<double>() : nullptr; }
+// mag_options.field_cg: under a field the CG runs the fused block-row phase (cg_phase_field) where the context has the
+// tile-local tables; without them (op_variant 1, a tile beyond LDS) the CSR operator's phase runs as before.  Valid once the
+// order is there.
+inline bool field_cg_selected(const mag_ctx *ctx) { return ctx->field_on && ctx->opt.field_cg != 0 && ctx->use_lds; }
+// the CG phase of this context leaves its solution expanded in ctx->u (the CSR operator's), not in ctx->x in Hilbert numbering
+inline bool solution_expanded(const mag_ctx *ctx) { return ctx->opt.cg_operator == MAG_OP_CSR && !field_cg_selected(ctx); }
 inline bool memory_known(int32_t memory) { return memory == MAG_MEM_HOST || memory == MAG_MEM_DEVICE; }
 
 int scratch_for(mag_ctx *ctx, size_t bytes)
@@ -496,6 +510,7 @@ int ensure_order(mag_ctx *ctx)
 {
     if (ctx->have_order) return MAG_OK;
     ctx->sens_tab_ready = false;
+    ctx->fc_ready = false; // (the block-row table is of this order's tiles and halo lists)
     const int64_t N = ctx->N, E = ctx->E;
     // automatic tile size: 512-node tiles once the mesh has at least as many of them as the fused kernel keeps
     // resident (2 per CU x 256 CUs); smaller meshes are latency-bound and run faster on twice as many 256-node tiles
@@ -831,6 +846,7 @@ int ensure_order(mag_ctx *ctx)
 int csr_symbolic(mag_ctx *ctx)
 {
     ctx->bc_touch_ready = false;
+    ctx->fc_ready = false; // (... and of this pattern's block numbering)
     const int64_t N = ctx->N, E = ctx->E;
     int64_t n9 = 9 * E;
     hipStream_t s = ctx->stream;
@@ -951,7 +967,71 @@ bool assemble_from_ctiles(const mag_ctx *ctx)
     return ctx->asm_ctile && ctx->use_lds && !(how && !strcmp(how, "tiles"));
 }
 
-int gather_phase(mag_ctx *ctx)
+// ---- mag_options.field_cg: the block-row table of K, once per order and pattern; the gathered values, once per assembly ----
+int ensure_field_table(mag_ctx *ctx)
+{
+    if (ctx->fc_ready || !field_cg_selected(ctx)) return MAG_OK;
+    using magk::FieldTileMeta;
+    hipStream_t s = ctx->stream;
+    const auto t_start = std::chrono::steady_clock::now();
+    const int32_t T = ctx->T, B = ctx->B;
+    HIPCHK(ctx->fc_width.reserve(4 * (size_t)T + 64));
+    magk::field_widths(ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(), ctx->N, B, T, ctx->fc_width.as<int32_t>(), s);
+    std::vector<int32_t> width((size_t)T), hoff((size_t)T + 1);
+    HIPCHK(hipMemcpyAsync(width.data(), ctx->fc_width.p, 4 * (size_t)T, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hoff.data(), ctx->tile_hoff.p, 4 * ((size_t)T + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    std::vector<FieldTileMeta> meta((size_t)T);
+    int64_t total = 0;
+    for (int32_t t = 0; t < T; ++t) {
+        meta[(size_t)t] = FieldTileMeta{total, width[(size_t)t], hoff[(size_t)t], hoff[(size_t)t + 1] - hoff[(size_t)t], 0, 0};
+        total += (int64_t)width[(size_t)t] * B;
+    }
+    ctx->fc_total = total;
+    HIPCHK(ctx->fc_meta.reserve(sizeof(FieldTileMeta) * (size_t)T));
+    HIPCHK(ctx->fc_slot.reserve(2 * (size_t)total + 64));
+    HIPCHK(ctx->fc_src.reserve(4 * (size_t)total + 64));
+    HIPCHK(ctx->fc_val.reserve(2 * 16 * (size_t)total));
+    HIPCHK(hipMemcpyAsync(ctx->fc_meta.p, meta.data(), sizeof(FieldTileMeta) * (size_t)T, hipMemcpyHostToDevice, s));
+    int32_t *err = ctx->fc_width.as<int32_t>() + T; // (the spare words behind the widths)
+    HIPCHK(hipMemsetAsync(err, 0, 4, s));
+    magk::field_rows(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->perm.as<uint32_t>(), ctx->iperm.as<int32_t>(),
+                     ctx->halo_g.as<int32_t>(), ctx->fc_meta.as<FieldTileMeta>(), ctx->N, B, T, ctx->fc_slot.as<uint16_t>(),
+                     ctx->fc_src.as<int32_t>(), err, s);
+    int32_t h_err = 0;
+    HIPCHK(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s)); // (the host vectors must outlive the copies)
+    if (h_err) return fail(ctx, MAG_ERR_STATE, "field_cg: a column of K is in neither its tile nor the tile's halo list");
+    ctx->fc_grid = magk::field_cg_grid(B, ctx->cap, T, ctx->opt.field_cg >= 2);
+    ctx->fc_ready = true;
+    ctx->fc_build_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    return MAG_OK;
+}
+
+// after kval is written: the gathered copy with the Dirichlet mask applied, and the preconditioner's inverse node blocks
+int field_numeric(mag_ctx *ctx)
+{
+    if (!field_cg_selected(ctx)) return MAG_OK;
+    if (int rc = ensure_field_table(ctx)) return rc;
+    using magk::FieldTileMeta;
+    hipStream_t s = ctx->stream;
+    magk::field_gather(ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(), ctx->kval.as<double>(), ctx->maskP.as<uint8_t>(),
+                       ctx->halo_g.as<int32_t>(), ctx->fc_meta.as<FieldTileMeta>(), ctx->fc_slot.as<uint16_t>(),
+                       ctx->fc_src.as<int32_t>(), ctx->N, ctx->B, ctx->T, ctx->fc_total, ctx->fc_val.as<double2>(), s);
+    if (ctx->opt.field_cg >= 2) {
+        HIPCHK(ctx->minvP.reserve(16 * (size_t)ctx->N));
+        HIPCHK(ctx->halo_minv.reserve(16 * (size_t)std::max<int64_t>(ctx->halo_total, 1)));
+        magk::field_minv(ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(), ctx->kval.as<double>(), ctx->maskP.as<uint8_t>(),
+                         ctx->fc_meta.as<FieldTileMeta>(), ctx->fc_src.as<int32_t>(), ctx->N, ctx->B,
+                         ctx->opt.field_cg == 3 ? 2 : 1, ctx->minvP.as<float4>(), s);
+        magk::halo_minv(ctx->halo_g.as<int32_t>(), ctx->minvP.as<float4>(), ctx->halo_total, ctx->halo_minv.as<float4>(), s);
+    }
+    HIPCHK(hipGetLastError());
+    return MAG_OK;
+}
+
+int assemble_values(mag_ctx *ctx)
 {
     if (assemble_from_ctiles(ctx) &&
                magk::assemble_ctiles(ctx->bcol.as<int32_t>(), ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(),
@@ -970,6 +1050,12 @@ int gather_phase(mag_ctx *ctx)
     }
     HIPCHK(hipGetLastError());
     return MAG_OK;
+}
+
+int gather_phase(mag_ctx *ctx)
+{
+    if (int rc = assemble_values(ctx)) return rc;
+    return field_numeric(ctx);
 }
 
 // K values of the variants of `vbat` (coordinates `xy`, permuted in v_xyP / v_halo) in the shared pattern, into v_kval:
@@ -1883,6 +1969,86 @@ int cg_phase_csr(mag_ctx *ctx)
     return MAG_OK;
 }
 
+// ---- mag_options.field_cg: one fused launch per iteration over the assembled K's block rows (cg.hip, k_cg_field) ----
+// cg_phase_fused's protocol on one GPU: the right-hand side in bP is in Hilbert numbering already, the solution stays in
+// ctx->x; the reduced system (build_reduced) is not needed and not built.
+magk::FieldCgParams field_cg_params(mag_ctx *ctx, int par)
+{
+    magk::FieldCgParams P = {};
+    const int32_t stride = magk::kMaxGrid;
+    P.N = ctx->N;
+    P.total = ctx->fc_total;
+    P.T = ctx->T;
+    P.nPart = ctx->fc_grid;
+    P.cap = ctx->cap;
+    P.par = par;
+    P.hist_len = ctx->opt.history_len;
+    P.part_stride = stride;
+    P.maskP = ctx->maskP.as<uint8_t>();
+    P.meta = ctx->fc_meta.as<magk::FieldTileMeta>();
+    P.slot = ctx->fc_slot.as<uint16_t>();
+    P.fval = ctx->fc_val.as<double2>();
+    P.halo_g = ctx->halo_g.as<int32_t>();
+    P.in = (par ? ctx->rqp1 : ctx->rqp0).as<magk::Rqp>();
+    P.out = (par ? ctx->rqp0 : ctx->rqp1).as<magk::Rqp>();
+    P.x = ctx->x.as<double2>();
+    double *part = ctx->fpart.as<double>();
+    P.part_in = part + (size_t)par * 5 * stride;
+    P.part_out = part + (size_t)(par ^ 1) * 5 * stride;
+    P.st = ctx->fstate.as<magk::FusedState>();
+    P.hist = ctx->hist.as<double>();
+    if (ctx->opt.field_cg >= 2) {
+        P.minvP = ctx->minvP.as<float4>();
+        P.halo_minv = ctx->halo_minv.as<float4>();
+    }
+    return P;
+}
+
+int field_cg_block(mag_ctx *ctx, int G)
+{
+    for (int i = 0; i < G; ++i) magk::field_cg_launch(field_cg_params(ctx, i & 1), ctx->B, ctx->fc_grid, ctx->stream);
+    HIPCHK(hipGetLastError());
+    return MAG_OK;
+}
+
+int cg_phase_field(mag_ctx *ctx)
+{
+    using magk::FusedState;
+    hipStream_t s = ctx->stream;
+    if (!ctx->fc_ready) return fail(ctx, MAG_ERR_STATE, "field_cg: no block-row table (K has not been assembled under this field)");
+    const bool pre = ctx->opt.field_cg >= 2;
+    HIPCHK(ctx->rqp0.reserve(sizeof(magk::Rqp) * (size_t)ctx->N));
+    HIPCHK(ctx->rqp1.reserve(sizeof(magk::Rqp) * (size_t)ctx->N));
+    HIPCHK(ctx->fpart.reserve(8 * 2 * 5 * (size_t)magk::kMaxGrid));
+    HIPCHK(ctx->fstate.reserve(sizeof(FusedState)));
+    HIPCHK(hipMemsetAsync(ctx->x.p, 0, 16 * (size_t)ctx->N, s));
+    double *part = ctx->fpart.as<double>();
+    const int32_t stride = magk::kMaxGrid, grid = ctx->fc_grid;
+    HIPCHK(hipMemsetAsync(part, 0, 8 * 2 * 5 * (size_t)stride, s));
+    magk::fused_init(ctx->bP.as<double2>(), pre ? ctx->minvP.as<float4>() : nullptr, ctx->rqp0.as<magk::Rqp>(),
+                     ctx->rqp1.as<magk::Rqp>(), ctx->N, ctx->B, ctx->T, 0, ctx->T, part, stride, grid, s);
+    magk::fused_setup(part, grid, stride, ctx->opt.stop_mode, ctx->opt.tol, (long long)ctx->opt.max_iter,
+                      ctx->fstate.as<FusedState>(), s);
+    HIPCHK(hipGetLastError());
+
+    const int G = ctx->opt.check_every;
+    const bool graph = ctx->opt.use_graph != 0;
+    if (graph) {
+        const mag_ctx::GraphKey k =
+            graph_key(ctx, G, {ctx->x.p, ctx->rqp0.p, ctx->rqp1.p, ctx->fpart.p, ctx->fstate.p, ctx->hist.p, ctx->maskP.p,
+                               ctx->fc_meta.p, ctx->fc_slot.p, ctx->fc_val.p, ctx->halo_g.p, (void *)(intptr_t)ctx->cap,
+                               (void *)(intptr_t)(0x10000 + ctx->fc_grid) /* block rows */, (void *)(intptr_t)ctx->fc_total,
+                               pre ? ctx->minvP.p : nullptr, pre ? ctx->halo_minv.p : nullptr});
+        if (int rc = capture_graph(ctx, k, [&] { return field_cg_block(ctx, G); })) return rc;
+    }
+    if (int rc = run_blocks(ctx, ctx->fstate, ctx->h_fstate, [&] { return graph ? launch_graph(ctx) : field_cg_block(ctx, G); }))
+        return rc;
+    HIPCHK(hipMemcpyAsync(&ctx->h_fstate[2], ctx->fstate.p, sizeof(FusedState), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    take_stats(ctx, ctx->h_fstate[2]);
+    return MAG_OK;
+}
+
 // ---- fp32 leg of BASELINE config 5: same fused iteration, CG state and operator arithmetic in fp32 (cg.hip, k_cg_fused32) ----
 magk::Fused32Params fused32_params(mag_ctx *ctx, int par, int grid)
 {
@@ -2048,6 +2214,7 @@ void mag_default_options(mag_options *o)
     o->cg_variant = 2;
     o->precision = 0;
     o->preconditioner = 0;
+    o->field_cg = 0;
 }
 
 mag_ctx *mag_create(const mag_options *opt)
@@ -2061,6 +2228,7 @@ mag_ctx *mag_create(const mag_options *opt)
     mag_options &o = ctx->opt;
     if (o.tile_nodes != 256 && o.tile_nodes != 512 && o.tile_nodes != 1024) o.tile_nodes = 0; // 0 = automatic
     if (o.preconditioner < 0 || o.preconditioner > 2) o.preconditioner = 0;
+    if (o.field_cg < 0 || o.field_cg > 3) o.field_cg = 0;
     if (o.check_every < 2) o.check_every = 2;
     if (o.check_every & 1) ++o.check_every; // p ping-pong parity must restart at 0 every block
     if (o.check_every > 4096) o.check_every = 4096;
@@ -2206,12 +2374,14 @@ int cg_solve(mag_ctx *ctx)
         return fail(ctx, MAG_ERR_BAD_ARGS,
                     "preconditioner needs the fused LDS iteration: cg_variant 1, precision fp64, matrix-free operator, "
                     "every tile within LDS");
-    ctx->cg_kernel = csr_op ? 3 : (f32 ? 4 : (ctx->fused ? 1 : 0));
+    const bool field_rows = csr_op && field_cg_selected(ctx); // (mag_options.field_cg: K's block rows, fused)
+    ctx->cg_kernel = field_rows ? 5 : (csr_op ? 3 : (f32 ? 4 : (ctx->fused ? 1 : 0)));
     ctx->exchange_kind = ctx->dist ? 1 : 0; // the phases that trade through the inboxes say so themselves
     ctx->persist_timed_out = false;
     ctx->exchange_timed_out = false;
     auto cg_dispatch = [&]() {
-        return csr_op ? cg_phase_csr(ctx)
+        return field_rows ? cg_phase_field(ctx)
+               : csr_op   ? cg_phase_csr(ctx)
                       : (f32 ? cg_phase_fused32(ctx)
                              : (ctx->persist ? cg_phase_persist(ctx) : (ctx->fused ? cg_phase_fused(ctx) : cg_phase(ctx))));
     };
@@ -2253,7 +2423,7 @@ int post_phase(mag_ctx *ctx, const double *xP, const double *u_in, const double 
 {
     hipStream_t s = ctx->stream;
     const int64_t N = ctx->N;
-    if (ctx->opt.cg_operator != MAG_OP_CSR) // (the CSR operator's phase has expanded its solution into u itself)
+    if (!solution_expanded(ctx)) // (the CSR operator's phase has expanded its solution into u itself)
         magk::scatter_back(xP, ctx->perm.as<uint32_t>(), ctx->uknown.as<uint8_t>(), u_in, N, u, s);
     if (wants_csr(ctx)) {
         magk::reactions_from_csr(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->kval.as<double>(),
@@ -2283,6 +2453,7 @@ void begin_run(mag_ctx *ctx)
     ctx->have_order = ctx->field_on && ctx->field_sym && ctx->have_order;
     ctx->field_sym = ctx->have_order;
     ctx->have_csr = ctx->have_run = false;
+    ctx->fc_build_ms = 0.0;
     drop_derived(ctx, MAG_SET_RUN); // (the single-case results go with every run, a set's included)
     // a context whose on-chip kernel once found the GPU shared is not condemned to stream for ever: after a number of
     // streamed solves (8, doubling per failure) it tries again -- at worst one more spin budget (~0.3 s).  Across ranks
@@ -2362,6 +2533,7 @@ int mag_run(mag_ctx *ctx)
         if (!kept_sym)
             if (int rc = csr_symbolic(ctx)) return rc;
         ctx->field_sym = ctx->field_on;
+        if (int rc = ensure_field_table(ctx)) return rc; // (mag_options.field_cg: built once, kept like the pattern)
         HIPCHK(hipEventRecord(ctx->ev[2], s)); // (K_e is evaluated inside the row assembly: ms_element is 0 and no event pair is
                                                // spent on it -- an empty pair still costs ~5 us of stream time)
         if (ctx->opt.verbose) printf("info: building total stiffness matrix...\n");
@@ -2396,7 +2568,7 @@ int mag_run(mag_ctx *ctx)
     if (ctx->opt.verbose) printf("info: solve complete\n");
 
     st.ms_order = kept_sym ? 0.0 : ev_ms(ctx->ev[0], ctx->ev[1]); // (kept: neither phase ran)
-    st.ms_csr_symbolic = kept_sym ? 0.0 : ev_ms(ctx->ev[1], ctx->ev[2]);
+    st.ms_csr_symbolic = kept_sym ? ctx->fc_build_ms : ev_ms(ctx->ev[1], ctx->ev[2]); // (kept: at most the block-row table)
     st.ms_element = 0.0; // part of ms_assemble (the assembly kernels evaluate the elements on the fly)
     st.ms_assemble = ev_ms(ctx->ev[2], ctx->ev[4]);
     st.ms_bc = ev_ms(ctx->ev[4], ctx->ev[5]);
@@ -2548,7 +2720,7 @@ int solve_case_alone(mag_ctx *ctx, MemberSet &set, int32_t c, mag_stats &out, bo
     HIPCHK(hipMemcpyAsync(ctx->fin.p, set.fin.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(ctx->bP.p, set.bP.as<char>() + vb * c, vb, hipMemcpyDeviceToDevice, s));
     if (int rc = cg_solve_member(ctx, c, out, timed_out_before)) return rc;
-    if (ctx->opt.cg_operator == MAG_OP_CSR)
+    if (solution_expanded(ctx))
         HIPCHK(hipMemcpyAsync(set.u.as<char>() + vb * c, ctx->u.p, vb, hipMemcpyDeviceToDevice, s));
     else
         HIPCHK(hipMemcpyAsync(set.x.as<char>() + vb * c, ctx->x.p, vb, hipMemcpyDeviceToDevice, s));
@@ -2687,6 +2859,8 @@ int run_members(mag_ctx *ctx, MemberSet &set, LentProblem &keep, const MemberHoo
     if (csr && !kept_sym)
         if (int rc = csr_symbolic(ctx)) return rc;
     ctx->field_sym = ctx->field_on && csr;
+    if (csr)
+        if (int rc = ensure_field_table(ctx)) return rc;
     HIPCHK(hipEventRecord(ctx->ev[2], s));
     if (int rc = hooks.prepare()) return rc;
     if (ctx->opt.verbose) printf("info: solving...\n");
@@ -3010,7 +3184,7 @@ int solve_variant_alone(mag_ctx *ctx, MemberSet &set, const LentProblem &keep, i
     if (int rc = rhs_phase(ctx, ctx->uin.as<double>(), ctx->fin.as<double>(), ctx->bP.as<double>(), false)) return rc;
     HIPCHK(hipGetLastError());
     if (int rc = cg_solve_member(ctx, v, out, timed_out_before)) return rc;
-    if (ctx->opt.cg_operator == MAG_OP_CSR) // (that operator's phase has expanded its solution into the context's u)
+    if (solution_expanded(ctx)) // (that operator's phase has expanded its solution into the context's u)
         HIPCHK(hipMemcpyAsync(set.u.as<char>() + vb * (size_t)v, ctx->u.p, vb, hipMemcpyDeviceToDevice, s));
     if (int rc = post_phase(ctx, ctx->x.as<double>(), ctx->uin.as<double>(), ctx->fin.as<double>(), set.u.as<double>() + 2 * (size_t)N * v,
                             set.f.as<double>() + 2 * (size_t)N * v, (double *)(set.stress.as<char>() + eb * (size_t)v)))

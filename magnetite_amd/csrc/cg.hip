@@ -1919,5 +1919,307 @@ void rhs_from_apply(const double *yP, const double *f_in, const uint8_t *u_known
     k_rhs_from_apply<<<blocks_for(2 * N, 256), 256, 0, s>>>(yP, f_in, u_known, perm, N, bP);
 }
 
+// ==================================== fused CG on the assembled K's block rows ===
+// mag_options.field_cg: under an element stiffness field K is assembled anyway, in the shared pattern, every design
+// iteration.  The tile-local block-row table (symbolic.hip, k_field_rows) says where each block of a row sits in kval and
+// which slot of the tile's p image its column is; the two kernels below run once per assembly, k_cg_field once per iteration.
+
+// block `src` of the pattern, of the row of caller node c: kval keeps a node's two DOF rows one after the other
+__device__ inline void field_block(const int32_t *bptr, const double *kval, int32_t c, int32_t src, double2 &row0, double2 &row1)
+{
+    const int32_t p = bptr[c], nb = bptr[c + 1] - p;
+    const double *base = kval + 4 * (int64_t)p + 2 * (int64_t)(src - p);
+    row0 = make_double2(base[0], base[1]);
+    row1 = make_double2(base[2 * (int64_t)nb], base[2 * (int64_t)nb + 1]);
+}
+
+// fval[off + k * B + tid] = kval[source], rows and columns of prescribed DOFs zeroed HERE: the iteration kernel needs no
+// per-entry mask (it forces q of a prescribed DOF to zero as k_cg_fused does).  kval stays as it is -- the right-hand side and
+// the reactions keep reading it.
+__global__ void __launch_bounds__(256) k_field_gather(const int32_t *bptr, const uint32_t *perm, const double *kval,
+                                                      const uint8_t *maskP, const int32_t *halo_g, const FieldTileMeta *meta,
+                                                      const uint16_t *slot, const int32_t *src, int64_t N, int32_t B,
+                                                      int64_t total, double2 *fval)
+{
+    const int32_t t = blockIdx.x;
+    const FieldTileMeta tm = meta[t];
+    const int32_t n = tm.width * B;
+    for (int32_t e = threadIdx.x; e < n; e += 256) {
+        const int32_t tid = e % B;
+        const int64_t g = (int64_t)t * B + tid;
+        const int32_t sj = src[tm.off + e];
+        double2 r0 = make_double2(0.0, 0.0), r1 = r0;
+        if (sj >= 0 && g < N) {
+            field_block(bptr, kval, (int32_t)perm[g], sj, r0, r1);
+            const int32_t sl = slot[tm.off + e];
+            const uint8_t mr = maskP[g];
+            const uint8_t mc = sl < B ? maskP[(int64_t)t * B + sl] : maskP[halo_g[tm.hoff + sl - B]];
+            if (mr & 1) r0 = make_double2(0.0, 0.0);
+            if (mr & 2) r1 = make_double2(0.0, 0.0);
+            if (mc & 1) r0.x = r1.x = 0.0;
+            if (mc & 2) r0.y = r1.y = 0.0;
+        }
+        fval[tm.off + e] = r0;
+        fval[total + tm.off + e] = r1;
+    }
+}
+
+void field_gather(const int32_t *bptr, const uint32_t *perm, const double *kval, const uint8_t *maskP, const int32_t *halo_g,
+                  const FieldTileMeta *meta, const uint16_t *slot, const int32_t *src, int64_t N, int32_t B, int32_t T,
+                  int64_t total, double2 *fval, hipStream_t s)
+{
+    k_field_gather<<<T, 256, 0, s>>>(bptr, perm, kval, maskP, halo_g, meta, slot, src, N, B, total, fval);
+}
+
+// the operations of k_precond_blocks (exact.hip) on the diagonal block of the scaled K: entry 0 of the node's row
+__global__ void __launch_bounds__(256) k_field_minv(const int32_t *bptr, const uint32_t *perm, const double *kval,
+                                                    const uint8_t *maskP, const FieldTileMeta *meta, const int32_t *src,
+                                                    int64_t N, int32_t B, int kind, float4 *minvP)
+{
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= N) return;
+    const int32_t t = (int32_t)(g / B);
+    const int32_t sj = src[meta[t].off + (g - (int64_t)t * B)];
+    double i00 = 0.0, i01 = 0.0, i11 = 0.0;
+    if (sj >= 0) {
+        double2 r0, r1;
+        field_block(bptr, kval, (int32_t)perm[g], sj, r0, r1);
+        const double k00 = r0.x, k01 = r0.y, k11 = r1.y;
+        const uint8_t m = maskP[g];
+        const bool fx = !(m & 1), fy = !(m & 2);
+        if (fx && fy && kind == 2) {
+            const double det = k00 * k11 - k01 * k01;
+            i00 = k11 / det;
+            i01 = (k01 / det) * -1.0;
+            i11 = k00 / det;
+        } else {
+            if (fx) i00 = 1.0 / k00;
+            if (fy) i11 = 1.0 / k11;
+        }
+    }
+    minvP[g] = make_float4((float)i00, (float)i01, (float)i11, 0.f);
+}
+
+void field_minv(const int32_t *bptr, const uint32_t *perm, const double *kval, const uint8_t *maskP, const FieldTileMeta *meta,
+                const int32_t *src, int64_t N, int32_t B, int kind, float4 *minvP, hipStream_t s)
+{
+    k_field_minv<<<blocks_for(N, 256), 256, 0, s>>>(bptr, perm, kval, maskP, meta, src, N, B, kind, minvP);
+}
+
+// k_cg_fused<B, false, false, PRE> with the operator replaced and the coordinates gone: persistent over tiles, one lane per
+// owned node, q = sum_k fval_k * s_p[slot_k] over the row in table order.  No floating-point atomics, no grid barrier, a
+// fixed summation order: a repeat gives the same bits.  LDS: cap * 16 bytes + the reduction scratch.
+// slots of the first entries of a row, loaded with the records (ahead of the values): eight, four where 1024 lanes leave
+// 128 registers each (eight spill there)
+template <int B>
+constexpr int kFieldSlotRegs = B == 1024 ? 4 : 8;
+// block_sumN with the per-wave partials combined by a butterfly over B / 64 lanes instead of B / 64 loads per sum and lane (with
+// 1024 lanes those loads, hoisted, cost more registers than the kernel has): every lane ends with the same totals, in a fixed order
+template <int B, int NS>
+__device__ inline void field_block_sum(double (&v)[NS], double *s_red)
+{
+    constexpr int W = B / 64;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int c = 0; c < NS; ++c) v[c] += __shfl_down(v[c], off);
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < NS; ++c) s_red[c * W + (threadIdx.x >> 6)] = v[c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < NS; ++c) {
+        double t = s_red[c * W + (threadIdx.x & (W - 1))];
+#pragma unroll
+        for (int off = W / 2; off > 0; off >>= 1) t += __shfl_xor(t, off);
+        v[c] = t;
+    }
+}
+
+template <int B, bool PRE>
+__global__ void __launch_bounds__(B) k_cg_field(const FieldCgParams P)
+{
+    constexpr int NS = PRE ? 5 : 4;
+    extern __shared__ __attribute__((aligned(16))) double2 smem[];
+    double2 *s_p = smem;
+    double *s_red = (double *)(smem + P.cap);
+    const int tid = threadIdx.x;
+
+    FusedState *st = P.st;
+    const long long j = st->jslot[P.par];
+    const int was_done = st->done;
+    const double target = st->target;
+    const long long max_iter = st->max_iter;
+    const int stop_mode = st->stop_mode;
+
+    int64_t node = 0;
+    bool valid = false, hvalid = false;
+    double2 ar, aq, ap, xo, hr, hq, hp;
+    uint8_t m = 3;
+    int32_t width = 0, nh = 0, hoff = 0;
+    float4 mi = make_float4(0.f, 0.f, 0.f, 0.f), hmi = mi;
+    constexpr int SR = kFieldSlotRegs<B>;
+    uint32_t w[SR];
+    const uint16_t *sl = nullptr;
+    const double2 *v0 = nullptr, *v1 = nullptr;
+    auto load_tile = [&](int32_t t) {
+        const FieldTileMeta tm = P.meta[t];
+        node = (int64_t)t * B + tid;
+        valid = node < P.N;
+        ar = aq = ap = xo = make_double2(0.0, 0.0);
+        m = 3;
+        if (valid) {
+            const Rqp rec = P.in[node];
+            ar = rec.r;
+            aq = rec.q;
+            ap = rec.p;
+            xo = P.x[node];
+            m = P.maskP[node];
+            if (PRE) mi = P.minvP[node];
+        }
+        width = tm.width;
+        sl = P.slot + tm.off + tid;
+        v0 = P.fval + tm.off + tid;
+        v1 = v0 + P.total;
+#pragma unroll
+        for (int k = 0; k < SR; ++k) w[k] = k < width ? sl[(int64_t)k * B] : (uint32_t)tid;
+        hoff = tm.hoff;
+        nh = tm.nh;
+        hvalid = tid < nh;
+        hr = hq = hp = make_double2(0.0, 0.0);
+        if (hvalid) {
+            const int32_t hg = P.halo_g[hoff + tid];
+            if (PRE) hmi = P.halo_minv[hoff + tid];
+            const Rqp rec = P.in[hg];
+            hr = rec.r;
+            hq = rec.q;
+            hp = rec.p;
+        }
+    };
+    load_tile(blockIdx.x);
+
+    // ---- dots of iterate j-1
+    double S[NS] = {};
+    for (int i = tid; i < P.nPart; i += B) {
+#pragma unroll
+        for (int c = 0; c < NS; ++c) S[c] += P.part_in[c * P.part_stride + i];
+    }
+    field_block_sum<B, NS>(S, s_red);
+    if (was_done) return;
+    double alpha = 0.0, beta = 0.0;
+    if (!fused_step<NS>(st, P.par, j, target, max_iter, stop_mode, S, P.hist, P.hist_len, alpha, beta)) return;
+
+    double acc[NS] = {};
+    int32_t t = blockIdx.x;
+    for (;;) {
+        double2 rn, pn;
+        rn.x = fma(alpha, aq.x, ar.x);
+        rn.y = fma(alpha, aq.y, ar.y);
+        const double2 zn = PRE ? apply_minv(mi, rn) : rn;
+        pn.x = fma(beta, ap.x, -zn.x);
+        pn.y = fma(beta, ap.y, -zn.y);
+        xo.x = fma(alpha, ap.x, xo.x);
+        xo.y = fma(alpha, ap.y, xo.y);
+        __syncthreads(); // previous tile's readers are done with the LDS image
+        s_p[tid] = pn;
+        if (hvalid) {
+            double2 hrn, hpn;
+            hrn.x = fma(alpha, hq.x, hr.x);
+            hrn.y = fma(alpha, hq.y, hr.y);
+            const double2 hzn = PRE ? apply_minv(hmi, hrn) : hrn;
+            hpn.x = fma(beta, hp.x, -hzn.x);
+            hpn.y = fma(beta, hp.y, -hzn.y);
+            s_p[B + tid] = hpn;
+        }
+        for (int32_t hh = tid + B; hh < nh; hh += B) { // more halo nodes than threads (rare)
+            const Rqp rec = P.in[P.halo_g[hoff + hh]];
+            double2 hrn, hpn;
+            hrn.x = fma(alpha, rec.q.x, rec.r.x);
+            hrn.y = fma(alpha, rec.q.y, rec.r.y);
+            const double2 hzn = PRE ? apply_minv(P.halo_minv[hoff + hh], hrn) : hrn;
+            hpn.x = fma(beta, rec.p.x, -hzn.x);
+            hpn.y = fma(beta, rec.p.y, -hzn.y);
+            s_p[B + hh] = hpn;
+        }
+        __syncthreads();
+
+        double fx = 0.0, fy = 0.0;
+        auto entry = [&](const uint32_t s, const int64_t k) {
+            const double2 a0 = v0[k * B], a1 = v1[k * B];
+            const double2 pv = s_p[s];
+            fx = fma(a0.y, pv.y, fma(a0.x, pv.x, fx));
+            fy = fma(a1.y, pv.y, fma(a1.x, pv.x, fy));
+        };
+#pragma unroll
+        for (int k = 0; k < SR; ++k)
+            if (k < width) entry(w[k], k);
+#pragma unroll 2
+        for (int32_t k = SR; k < width; ++k) entry(sl[(int64_t)k * B], k);
+        if (valid) {
+            if (m & 1) fx = 0.0;
+            if (m & 2) fy = 0.0;
+            P.out[node].r = rn;
+            P.out[node].q = make_double2(fx, fy);
+            P.out[node].p = pn;
+            P.x[node] = xo;
+            acc[0] = fma(rn.y, rn.y, fma(rn.x, rn.x, acc[0]));
+            acc[1] = fma(pn.y, fy, fma(pn.x, fx, acc[1]));
+            if (PRE) {
+                const double2 zq = apply_minv(mi, make_double2(fx, fy));
+                acc[2] = fma(rn.y, zn.y, fma(rn.x, zn.x, acc[2]));
+                acc[NS - 2] = fma(fy, zn.y, fma(fx, zn.x, acc[NS - 2]));
+                acc[NS - 1] = fma(fy, zq.y, fma(fx, zq.x, acc[NS - 1]));
+            } else {
+                acc[2] = fma(rn.y, fy, fma(rn.x, fx, acc[2]));
+                acc[3] = fma(fy, fy, fma(fx, fx, acc[3]));
+            }
+        }
+        t += gridDim.x;
+        if (t >= P.T) break;
+        load_tile(t);
+    }
+    field_block_sum<B, NS>(acc, s_red);
+    if (tid == 0) {
+#pragma unroll
+        for (int c = 0; c < NS; ++c) P.part_out[c * P.part_stride + blockIdx.x] = acc[c];
+    }
+}
+
+static size_t field_cg_lds(int32_t cap, int32_t B, bool pre) { return (size_t)cap * 16 + (size_t)(B / 64) * (pre ? 40 : 32) + 16; }
+
+typedef void (*field_fn)(const FieldCgParams);
+static field_fn field_pick(int32_t B, bool pre)
+{
+    if (B == 256) return pre ? k_cg_field<256, true> : k_cg_field<256, false>;
+    if (B == 1024) return pre ? k_cg_field<1024, true> : k_cg_field<1024, false>;
+    return pre ? k_cg_field<512, true> : k_cg_field<512, false>;
+}
+
+// as fused_grid: all workgroups co-resident (occupancy query x CUs), capped by MAG_TUNE_GRID and by the tile count
+int field_cg_grid(int32_t B, int32_t cap, int32_t tiles, bool pre)
+{
+    int dev = 0, cus = 256, per_cu = 1;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, field_pick(B, pre), B == 256 || B == 1024 ? B : 512,
+                                                                      field_cg_lds(cap, B, pre));
+    if (e != hipSuccess || per_cu < 1) per_cu = 1;
+    long g = (long)per_cu * cus;
+    if (g > kMaxGrid) g = kMaxGrid;
+    if (const char *cap_env = getenv("MAG_TUNE_GRID"))
+        if (atoi(cap_env) > 0 && g > atoi(cap_env)) g = atoi(cap_env);
+    if (g > tiles) g = tiles;
+    return g < 1 ? 1 : (int)g;
+}
+
+void field_cg_launch(const FieldCgParams &P, int32_t B, int32_t grid, hipStream_t s)
+{
+    const bool pre = P.minvP != nullptr;
+    field_pick(B, pre)<<<grid, B == 256 || B == 1024 ? B : 512, field_cg_lds(P.cap, B, pre), s>>>(P);
+}
+
 
 } // namespace magk

@@ -386,6 +386,52 @@ void fused_setup(const double *part, int32_t nPart, int32_t stride, int stop_mod
 void comm_slots(const int32_t *iface, int32_t n_iface, int32_t own0, int32_t own1, const int32_t *halo_g,
                 int64_t halo_total, int64_t N, int32_t *own_qslot, int32_t *halo_qslot, hipStream_t s);
 
+// ---- fused CG on the assembled K's block rows (mag_options.field_cg, under an element stiffness field) ----
+// Tile-local block-row table of K from the block-CSR pattern (symbolic.hip): for every owned node of a tile its row as entries
+// (slot, source), column-major per tile like ell16 -- entry k of lane tid at off + k * B + tid.  slot: tile-local index of the
+// column node (0..B-1 owned, B + h halo entry h: the indexing of s_p in k_cg_fused); source: index of the 2x2 block in the
+// pattern (bptr/bcol numbering), -1 for padding.  Row order: the diagonal block, then ascending Hilbert index of the column.
+struct FieldTileMeta { // one 32-byte scalar load per tile
+    int64_t off;
+    int32_t width, hoff, nh, pad0; // width: blocks of the tile's longest row
+    int64_t pad1;
+};
+// width[t] = longest row of tile t (at least 1)
+void field_widths(const int32_t *bptr, const uint32_t *perm, int64_t N, int32_t B, int32_t T, int32_t *width, hipStream_t s);
+// fills slot / src of every tile; *err is set when a column is neither owned nor in the tile's halo list
+void field_rows(const int32_t *bptr, const int32_t *bcol, const uint32_t *perm, const int32_t *iperm, const int32_t *halo_g,
+                const FieldTileMeta *meta, int64_t N, int32_t B, int32_t T, uint16_t *slot, int32_t *src, int32_t *err,
+                hipStream_t s);
+// numeric part, once per assembly: the gathered values as two double2 planes (row 0, row 1 of every block; `total` entries
+// each), rows and columns of prescribed DOFs zeroed, zero blocks on the padding; kval itself is untouched
+void field_gather(const int32_t *bptr, const uint32_t *perm, const double *kval, const uint8_t *maskP, const int32_t *halo_g,
+                  const FieldTileMeta *meta, const uint16_t *slot, const int32_t *src, int64_t N, int32_t B, int32_t T,
+                  int64_t total, double2 *fval, hipStream_t s);
+// inverse node-diagonal blocks of the scaled K (kind 1: diagonal only, 2: 2x2 blocks), k_precond_blocks' treatment of the
+// prescribed DOFs and its fp32 rounding, Hilbert order
+void field_minv(const int32_t *bptr, const uint32_t *perm, const double *kval, const uint8_t *maskP, const FieldTileMeta *meta,
+                const int32_t *src, int64_t N, int32_t B, int kind, float4 *minvP, hipStream_t s);
+struct FieldCgParams {
+    int64_t N, total;
+    int32_t T, nPart, cap, par, hist_len, part_stride;
+    const uint8_t *maskP;
+    const FieldTileMeta *meta;
+    const uint16_t *slot;
+    const double2 *fval; // plane 0 at fval, plane 1 at fval + total
+    const int32_t *halo_g;
+    const Rqp *in;
+    Rqp *out;
+    double2 *x;
+    const double *part_in;
+    double *part_out;
+    FusedState *st;
+    double *hist;
+    const float4 *minvP; // null: plain CG
+    const float4 *halo_minv;
+};
+int field_cg_grid(int32_t B, int32_t cap, int32_t tiles, bool pre);
+void field_cg_launch(const FieldCgParams &P, int32_t B, int32_t grid, hipStream_t s);
+
 // ---- on-chip (persistent) CG: the whole solve in one launch when every tile fits registers + LDS (persist.hip) ----
 struct PersistParams {
     int64_t N;

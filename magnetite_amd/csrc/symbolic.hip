@@ -1242,4 +1242,90 @@ void reduce_fill(const int32_t *bptr, const int32_t *bcol, const double *kval, c
                                                         col_ff, val_ff);
 }
 
+// ---- tile-local block rows of the assembled K (mag_options.field_cg; the kernel is cg.hip's k_cg_field) ----
+// Built from the block-CSR pattern, not from the ring table: the pattern holds every neighbour block of any node star
+// (bow-ties, non-manifold edges, hubs), the ring words encode triangles.
+__global__ void __launch_bounds__(256) k_field_widths(const int32_t *bptr, const uint32_t *perm, int64_t N, int32_t B,
+                                                      int32_t *width)
+{
+    __shared__ int32_t s_w[4];
+    const int32_t t = blockIdx.x;
+    int32_t w = 1;
+    for (int32_t tid = threadIdx.x; tid < B; tid += 256) {
+        const int64_t g = (int64_t)t * B + tid;
+        if (g < N) {
+            const int64_t c = perm[g];
+            w = max(w, bptr[c + 1] - bptr[c]);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) w = max(w, __shfl_down(w, off));
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = w;
+    __syncthreads();
+    if (threadIdx.x == 0) width[t] = max(max(s_w[0], s_w[1]), max(s_w[2], s_w[3]));
+}
+
+void field_widths(const int32_t *bptr, const uint32_t *perm, int64_t N, int32_t B, int32_t T, int32_t *width, hipStream_t s)
+{
+    k_field_widths<<<T, 256, 0, s>>>(bptr, perm, N, B, width);
+}
+
+// One lane per owned node.  The row order is fixed -- the diagonal block, then ascending Hilbert index of the column -- so the
+// row sum is a function of the mesh alone; the ascending pass is a selection (rows are short, and this runs once per mesh).
+// A halo column's slot is resolved here, by bisection of the tile's sorted halo list, never per iteration.
+__global__ void __launch_bounds__(256) k_field_rows(const int32_t *bptr, const int32_t *bcol, const uint32_t *perm,
+                                                    const int32_t *iperm, const int32_t *halo_g, const FieldTileMeta *meta,
+                                                    int64_t N, int32_t B, uint16_t *slot, int32_t *src, int32_t *err)
+{
+    const int32_t t = blockIdx.x;
+    const FieldTileMeta tm = meta[t];
+    const int32_t base = t * B;
+    const int32_t *hl = halo_g + tm.hoff;
+    for (int32_t tid = threadIdx.x; tid < B; tid += 256) {
+        uint16_t *sl = slot + tm.off + tid;
+        int32_t *sr = src + tm.off + tid;
+        const int64_t g = (int64_t)base + tid;
+        int32_t k = 0;
+        if (g < N) {
+            const int32_t c = (int32_t)perm[g];
+            const int32_t p0 = bptr[c], p1 = bptr[c + 1];
+            for (int32_t j = p0; j < p1; ++j)
+                if (bcol[j] == c) {
+                    sl[0] = (uint16_t)tid;
+                    sr[0] = j;
+                    k = 1;
+                }
+            int32_t last = -1;
+            for (;;) {
+                int32_t best = 0x7fffffff, bj = -1;
+                for (int32_t j = p0; j < p1; ++j) {
+                    const int32_t h = iperm[bcol[j]];
+                    if (h > last && h < best && h != (int32_t)g) {
+                        best = h;
+                        bj = j;
+                    }
+                }
+                if (bj < 0 || k >= tm.width) break;
+                const uint32_t l = local_id(best, base, B, hl, tm.nh);
+                if (l >= (uint32_t)B && (tm.nh == 0 || hl[l - B] != best)) *err = 1;
+                sl[(int64_t)k * B] = (uint16_t)(l < (uint32_t)(B + max(tm.nh, 1)) ? l : tid);
+                sr[(int64_t)k * B] = bj;
+                last = best;
+                ++k;
+            }
+        }
+        for (; k < tm.width; ++k) { // short rows: a zero block on the lane's own slot
+            sl[(int64_t)k * B] = (uint16_t)tid;
+            sr[(int64_t)k * B] = -1;
+        }
+    }
+}
+
+void field_rows(const int32_t *bptr, const int32_t *bcol, const uint32_t *perm, const int32_t *iperm, const int32_t *halo_g,
+                const FieldTileMeta *meta, int64_t N, int32_t B, int32_t T, uint16_t *slot, int32_t *src, int32_t *err,
+                hipStream_t s)
+{
+    k_field_rows<<<T, 256, 0, s>>>(bptr, bcol, perm, iperm, halo_g, meta, N, B, slot, src, err);
+}
+
 } // namespace magk

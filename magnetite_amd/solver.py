@@ -84,8 +84,9 @@ class Context:
         L = _lib.lib()
         o = _lib.Options()
         L.mag_default_options(C.byref(o))
+        known = {name for name, _ in _lib.Options._fields_}
         for k, v in opts.items():
-            if not hasattr(o, k):
+            if k not in known:  # (setattr on a ctypes structure takes any name: only mag_options' own fields are options)
                 raise TypeError(f"unknown option {k}")
             setattr(o, k, v)
         self.options = o

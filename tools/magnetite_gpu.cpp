@@ -408,7 +408,7 @@ int main(int argc, char **argv)
 {
     std::string input, mesh, nodes_out = "nodes.csv", elements_out = "elements.csv";
     bool dry = false, recover = false;
-    int modal_modes = 0, adapt = 0, refine_split = 1, topopt = 0, penal = 3, filter_passes = 1;
+    int modal_modes = 0, adapt = 0, refine_split = 1, topopt = 0, penal = 3, filter_passes = 1, field_cg = 0;
     double rel = 0.0, density = 0.0, refine_fraction = 0.2, volume_fraction = 0.5;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -423,6 +423,7 @@ int main(int argc, char **argv)
         else if (a == "--volume-fraction" && i + 1 < argc) volume_fraction = std::atof(argv[++i]);
         else if (a == "--penal" && i + 1 < argc) penal = std::atoi(argv[++i]);
         else if (a == "--filter-passes" && i + 1 < argc) filter_passes = std::atoi(argv[++i]);
+        else if (a == "--field-cg" && i + 1 < argc) field_cg = std::atoi(argv[++i]);
         else if (a == "--nodes" && i + 1 < argc) nodes_out = argv[++i];
         else if (a == "--elements" && i + 1 < argc) elements_out = argv[++i];
         else if (a == "--rel" && i + 1 < argc) rel = std::atof(argv[++i]);
@@ -431,7 +432,7 @@ int main(int argc, char **argv)
         else die({MagnetiteError::Input, "Unrecognized argument " + a});
     }
     if (input.empty() || mesh.empty()) {
-        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery] [--modal P --density RHO] [--adapt R [--refine-fraction T] [--refine-split 1|3]] [--topopt ITERS [--volume-fraction F] [--penal P] [--filter-passes K]]\n");
+        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery] [--modal P --density RHO] [--adapt R [--refine-fraction T] [--refine-split 1|3]] [--topopt ITERS [--volume-fraction F] [--penal P] [--filter-passes K] [--field-cg 0..3]]\n");
         return 2;
     }
     if (modal_modes < 0 || (modal_modes > 0 && !(density > 0.0))) die({MagnetiteError::Input, "--modal P needs P >= 1 and --density RHO > 0"});
@@ -439,6 +440,8 @@ int main(int argc, char **argv)
         die({MagnetiteError::Input, "--adapt R needs R >= 0, --refine-fraction T in (0, 1] and --refine-split 1 or 3"});
     if (topopt < 0 || !(volume_fraction > 0.0 && volume_fraction <= 1.0) || penal < 1 || penal > 8 || filter_passes < 0 || filter_passes > 8)
         die({MagnetiteError::Input, "--topopt ITERS needs ITERS >= 0, --volume-fraction F in (0, 1], --penal 1..8 and --filter-passes 0..8"});
+    if (field_cg < 0 || field_cg > 3 || (field_cg != 0 && topopt == 0))
+        die({MagnetiteError::Input, "--field-cg K needs K in 0..3 (0 CSR phase, 1 plain, 2 Jacobi, 3 block-Jacobi on K's block rows) and --topopt"});
     if (topopt > 0 && adapt > 0) die({MagnetiteError::Input, "--topopt designs on the mesh as given: not together with --adapt"});
     // mesher::run (mesher.rs:939-974) minus geometry parsing and the gmsh subprocess
     const std::string text = slurp(input, MagnetiteError::Input, "Unable to open input file " + input);
@@ -528,6 +531,7 @@ int main(int argc, char **argv)
         for (Element &e : ccw)
             if (solver::compute_element_area(e, posed) < 0.0) std::swap(e.nodes[0], e.nodes[2]);
         opt.verbose = 0;
+        opt.field_cg = field_cg; // (the CG of every design iteration: mag_options.field_cg)
         DesignSpec spec;
         spec.volume_fraction = volume_fraction;
         spec.penal = penal;
