@@ -91,6 +91,11 @@ enum mag_operator {
     MAG_OP_CSR = 1          /* reference-faithful: K_ff in CSR, solver.rs:31-36     */
 };
 
+/* Where a caller's arrays live.  One rule for every entry point and struct that carries a `memory`: a value that is none of
+ * enum mag_memory is refused with MAG_ERR_BAD_ARGS, mag_last_error naming the function and mag_memory, among the argument checks
+ * that precede any HIP call (so ahead of the MAG_ERR_STATE of a missing upload or run); where the pointers it describes are all
+ * optional and NULL, so that nothing would be read or written through them, it is not looked at (an input that may be NULL:
+ * mag_set_element_scale(NULL) clears, mag_run_refine's NULL indicator; output structs are always checked). */
 enum mag_memory { MAG_MEM_HOST = 0, MAG_MEM_DEVICE = 1 };
 
 typedef struct mag_options {
@@ -296,7 +301,9 @@ int mag_get_cases_info(const mag_ctx *ctx, int32_t info[4]);
  *   E, nu, thickness or NULL (the uploaded material); u_in, f_in [V][2N] each or both NULL (the uploaded values).  At least one
  *   of the three must be given.  MAG_ERR_BAD_ARGS, with the first offender in mag_last_error: a material mag_upload would
  *   refuse; a variant in which an element's signed area differs in sign from the uploaded mesh's or is zero (the shared ring
- *   tables assume the uploaded orientation).  A new mag_upload drops the variants.  Load cases and variants are independent
+ *   tables assume the uploaded orientation).  A refused material leaves the variants, their results and what was derived from
+ *   them as they were, in either memory (values on the device are read back and checked before the set is touched); a refused
+ *   shape has already replaced the set's coordinates, and the variants are gone.  A new mag_upload drops the variants.  Load cases and variants are independent
  *   sets of one context: setting or running one does not drop the other.
  * mag_run_variants, mag_download_variant, mag_get_variant_stats, mag_get_variants_info: as mag_run_cases ... mag_get_cases_info
  *   (status, the one redo of a variant whose group timed out or that stopped at the iteration cap with an earlier best iterate,

@@ -397,6 +397,13 @@ inline bool field_cg_selected(const mag_ctx *ctx) { return ctx->field_on && ctx-
 // the CG phase of this context leaves its solution expanded in ctx->u (the CSR operator's), not in ctx->x in Hilbert numbering
 inline bool solution_expanded(const mag_ctx *ctx) { return ctx->opt.cg_operator == MAG_OP_CSR && !field_cg_selected(ctx); }
 inline bool memory_known(int32_t memory) { return memory == MAG_MEM_HOST || memory == MAG_MEM_DEVICE; }
+// The one rule of the ABI: a `memory` that is none of enum mag_memory is refused where a pointer it describes would be read or
+// written, among the argument checks that precede any HIP call (fn: the entry point, named in the message)
+int memory_refused(mag_ctx *ctx, int32_t memory, const char *fn)
+{
+    if (memory_known(memory)) return MAG_OK;
+    return fail(ctx, MAG_ERR_BAD_ARGS, "%s: memory = %d is none of enum mag_memory", fn, (int)memory);
+}
 
 int scratch_for(mag_ctx *ctx, size_t bytes)
 {
@@ -2466,6 +2473,8 @@ void begin_run(mag_ctx *ctx)
 
 int mag_upload(mag_ctx *ctx, const mag_problem *p)
 {
+    if (ctx && p)
+        if (int rc = memory_refused(ctx, p->memory, "mag_upload")) return rc;
     if (int rc = enter(ctx)) return rc;
     if (!p || !p->xy || !p->conn || !p->u_known || !p->u_in || !p->f_in)
         return fail(ctx, MAG_ERR_BAD_ARGS, "null problem pointer");
@@ -2602,6 +2611,8 @@ int mag_run(mag_ctx *ctx)
 
 int mag_download(mag_ctx *ctx, mag_result *r)
 {
+    if (ctx && r)
+        if (int rc = memory_refused(ctx, r->memory, "mag_download")) return rc;
     if (int rc = enter(ctx)) return rc;
     if (!r) return fail(ctx, MAG_ERR_BAD_ARGS, "null result");
     if (!ctx->have_run) return fail(ctx, MAG_ERR_STATE, "mag_download before a completed mag_run");
@@ -2620,6 +2631,7 @@ int mag_set_load_cases(mag_ctx *ctx, int32_t num_cases, const double *u_in, cons
     if (!ctx) return MAG_ERR_BAD_ARGS;
     if (num_cases < 1) return fail(ctx, MAG_ERR_BAD_ARGS, "num_cases = %d: at least one load case", (int)num_cases);
     if (!u_in || !f_in) return fail(ctx, MAG_ERR_BAD_ARGS, "null load-case pointer");
+    if (int rc = memory_refused(ctx, memory, "mag_set_load_cases")) return rc;
     if (ctx->comm.nranks > 1)
         return fail(ctx, MAG_ERR_BAD_ARGS, "load cases run on one GPU: this context has a communicator of %d ranks", ctx->comm.nranks);
     if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "mag_set_load_cases before mag_upload");
@@ -2928,6 +2940,7 @@ int run_members(mag_ctx *ctx, MemberSet &set, LentProblem &keep, const MemberHoo
 int download_member(mag_ctx *ctx, const MemberSet &set, int32_t i, mag_result *r, const char *fn_name)
 {
     if (!r) return fail(ctx, MAG_ERR_BAD_ARGS, "null result");
+    if (int rc = memory_refused(ctx, r->memory, fn_name)) return rc;
     if (i < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s %d out of range", set.noun, (int)i);
     if (!set.have_run) return fail(ctx, MAG_ERR_STATE, "%s before a completed %s", fn_name, set.run_fn);
     if (i >= set.count) return fail(ctx, MAG_ERR_BAD_ARGS, "%s %d out of range [0, %d)", set.noun, (int)i, (int)set.count);
@@ -3061,6 +3074,7 @@ int mag_set_variants(mag_ctx *ctx, int32_t num_variants, const double *xy, const
     if ((u_in == nullptr) != (f_in == nullptr)) return fail(ctx, MAG_ERR_BAD_ARGS, "variants: u_in and f_in come together, or both null");
     if (!xy && !material && !u_in)
         return fail(ctx, MAG_ERR_BAD_ARGS, "variants: at least one of xy, material and the value pair must be given");
+    if (int rc = memory_refused(ctx, memory, "mag_set_variants")) return rc;
     if (int rc = variants_refused(ctx)) return rc;
     const int32_t V = num_variants;
     std::vector<double> mat(3 * (size_t)V);
@@ -3076,17 +3090,18 @@ int mag_set_variants(mag_ctx *ctx, int32_t num_variants, const double *xy, const
     }
     if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "mag_set_variants before mag_upload");
     if (int rc = enter(ctx)) return rc;
-    ctx->variants.have = ctx->variants.have_run = false;
-    drop_derived(ctx, MAG_SET_VARIANTS);
     const int64_t N = ctx->N, E = ctx->E;
     const size_t bytes = 16 * (size_t)N * (size_t)V;
     const hipMemcpyKind kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     hipStream_t s = ctx->stream;
-    if (material && memory == MAG_MEM_DEVICE) {
+    if (material && memory == MAG_MEM_DEVICE) { // device values: read back and checked before the set is touched, so that a
+                                                // refused material leaves the variants as they were, as a host one does
         HIPCHK(hipMemcpyAsync(mat.data(), material, 8 * mat.size(), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         if (int rc = check_materials()) return rc;
     }
+    ctx->variants.have = ctx->variants.have_run = false;
+    drop_derived(ctx, MAG_SET_VARIANTS);
     if (!material)
         for (int32_t v = 0; v < V; ++v) {
             mat[3 * (size_t)v + 0] = ctx->youngs;
@@ -3607,6 +3622,8 @@ int mag_run_sensitivities(mag_ctx *ctx, int32_t set)
 int mag_download_sensitivity(mag_ctx *ctx, int32_t set, int32_t index, mag_sensitivity *o)
 {
     const DerivedSet *have = nullptr;
+    if (ctx && o)
+        if (int rc = memory_refused(ctx, o->memory, "mag_download_sensitivity")) return rc;
     if (int rc = download_refused(ctx, PASS_SENS, set, index, o, "sensitivity", "mag_download_sensitivity", "mag_run_sensitivities", &have))
         return rc;
     const size_t eb = 8 * (size_t)ctx->E, vb = 16 * (size_t)ctx->N;
@@ -3722,6 +3739,8 @@ int mag_run_adjoint(mag_ctx *ctx, int32_t set, const double *dJ_du, int32_t memo
     if (!ctx) return MAG_ERR_BAD_ARGS;
     int32_t M = 0;
     if (set >= MAG_SET_RUN && set <= MAG_SET_VARIANTS && !dJ_du) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_adjoint: null dJ_du");
+    if (dJ_du)
+        if (int rc = memory_refused(ctx, memory, "mag_run_adjoint")) return rc;
     if (int rc = sens_refused(ctx, set, "mag_run_adjoint", &M)) return rc;
     if (int rc = enter(ctx)) return rc;
     return run_adjoint(ctx, set, M, dJ_du, memory);
@@ -3730,6 +3749,8 @@ int mag_run_adjoint(mag_ctx *ctx, int32_t set, const double *dJ_du, int32_t memo
 int mag_download_adjoint(mag_ctx *ctx, int32_t set, int32_t index, mag_adjoint *o)
 {
     const DerivedSet *have = nullptr;
+    if (ctx && o)
+        if (int rc = memory_refused(ctx, o->memory, "mag_download_adjoint")) return rc;
     if (int rc = download_refused(ctx, PASS_ADJOINT, set, index, o, "adjoint", "mag_download_adjoint", "mag_run_adjoint", &have)) return rc;
     const size_t eb = 8 * (size_t)ctx->E, vb = 16 * (size_t)ctx->N;
     return download_rows(ctx, *have, index, o->memory,
@@ -3763,6 +3784,8 @@ int mag_run_objective(mag_ctx *ctx, int32_t set, const mag_objective *obj, int32
     if (obj->kind != MAG_OBJ_DISP_LSQ && obj->kind != MAG_OBJ_STRESS_PNORM)
         return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_objective: kind %d is none of enum mag_objective_kind", (int)obj->kind);
     const bool lsq = obj->kind == MAG_OBJ_DISP_LSQ;
+    if (obj->weights || (lsq && obj->target)) // (the rows that would be read)
+        if (int rc = memory_refused(ctx, obj->memory, "mag_run_objective")) return rc;
     if (lsq && !obj->weights) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_objective: MAG_OBJ_DISP_LSQ needs weights");
     if (!lsq && !(std::isfinite(obj->p) && obj->p >= 1.0))
         return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_objective: p = %g is not a finite exponent >= 1", obj->p);
@@ -3847,6 +3870,8 @@ int mag_run_objective(mag_ctx *ctx, int32_t set, const mag_objective *obj, int32
 int mag_download_objective(mag_ctx *ctx, int32_t set, int32_t index, mag_objective_result *o)
 {
     const DerivedSet *have = nullptr;
+    if (ctx && o)
+        if (int rc = memory_refused(ctx, o->memory, "mag_download_objective")) return rc;
     if (int rc = download_refused(ctx, PASS_OBJECTIVE, set, index, o, "objective result", "mag_download_objective", "mag_run_objective", &have))
         return rc;
     if (o->dxy_out && !have->totals)
@@ -3894,6 +3919,8 @@ int mag_run_stress(mag_ctx *ctx, int32_t set)
 int mag_download_stress(mag_ctx *ctx, int32_t set, int32_t index, mag_stress_field *o)
 {
     const DerivedSet *have = nullptr;
+    if (ctx && o)
+        if (int rc = memory_refused(ctx, o->memory, "mag_download_stress")) return rc;
     if (int rc = download_refused(ctx, PASS_STRESS, set, index, o, "stress field", "mag_download_stress", "mag_run_stress", &have)) return rc;
     const size_t rb = 32 * (size_t)ctx->E, nb = 32 * (size_t)ctx->N, eb = 8 * (size_t)ctx->E;
     return download_rows(ctx, *have, index, o->memory, {{o->elem_out, have->selem, rb}, {o->node_out, have->snode, nb}, {o->eta2_out, have->seta2, eb}},
@@ -4109,6 +4136,7 @@ int mag_download_modal(mag_ctx *ctx, mag_modal_result *o)
 {
     if (!ctx) return MAG_ERR_BAD_ARGS;
     if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "null modal result");
+    if (int rc = memory_refused(ctx, o->memory, "mag_download_modal")) return rc;
     if (ctx->comm.nranks > 1)
         return fail(ctx, MAG_ERR_BAD_ARGS, "modal analysis runs on one GPU: this context has a communicator of %d ranks", ctx->comm.nranks);
     if (!ctx->have_problem || !ctx->modal_have) return fail(ctx, MAG_ERR_STATE, "mag_download_modal before a completed mag_run_modal");
@@ -4198,6 +4226,8 @@ int mag_run_refine(mag_ctx *ctx, const mag_refine_options *ro)
     if (by_indicator && !(std::isfinite(ro->theta) && ro->theta > 0.0 && ro->theta <= 1.0))
         return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_refine: theta = %g outside (0, 1]", ro->theta);
     if (!by_indicator && !ro->marks) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_refine: null marks under MAG_REFINE_MARKS");
+    if (!by_indicator || ro->indicator) // (the array the rule reads; a NULL indicator is the device's own eta2)
+        if (int rc = memory_refused(ctx, ro->memory, "mag_run_refine")) return rc;
     if (ctx->comm.nranks > 1)
         return fail(ctx, MAG_ERR_BAD_ARGS, "refinement runs on one GPU: this context has a communicator of %d ranks", ctx->comm.nranks);
     if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "mag_run_refine before mag_upload");
@@ -4383,6 +4413,8 @@ int mag_get_refine_info(const mag_ctx *ctx, int64_t info[8])
 
 int mag_download_refine(mag_ctx *ctx, mag_refined *o)
 {
+    if (ctx && o)
+        if (int rc = memory_refused(ctx, o->memory, "mag_download_refine")) return rc;
     if (int rc = refined_refused(ctx, o, "refined mesh", "mag_download_refine")) return rc;
     if (int rc = enter(ctx)) return rc;
     const hipMemcpyKind kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
@@ -4687,6 +4719,10 @@ int mag_download_design(mag_ctx *ctx, const mag_design *o)
 
 int mag_solve(mag_ctx *ctx, const mag_problem *p, mag_result *r)
 {
+    if (ctx && p) // (both structs before the upload: a refused result leaves the context as it was)
+        if (int rc = memory_refused(ctx, p->memory, "mag_solve")) return rc;
+    if (ctx && r)
+        if (int rc = memory_refused(ctx, r->memory, "mag_solve")) return rc;
     if (int rc = mag_upload(ctx, p)) return rc;
     const int rc_run = mag_run(ctx);
     if (rc_run != MAG_OK && rc_run != MAG_ERR_NOT_CONVERGED) return rc_run; // a breakdown still hands back what it has

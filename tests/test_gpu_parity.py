@@ -523,6 +523,11 @@ def test_device_resident_inputs_and_outputs(built):
     k = p.u_known == 1
     assert np.array_equal(f[~k], p.f_in[~k])
     assert np.isfinite(s).all()
+    # the device path adds copies, never arithmetic: bit for bit the solve of the same problem from and into host memory
+    with Context(device=0) as c:
+        host = c.solve(p)
+    for name, got in (("u", u), ("f", f), ("stress", s)):
+        assert got.tobytes() == host[name].tobytes(), name
 
 
 def _random_delaunay_problem(seed):
