@@ -539,11 +539,15 @@ int mag_download_stress(mag_ctx *ctx, int32_t set, int32_t index, mag_stress_fie
  *   A supported part is required: where too few supports leave a rigid-body motion free K_FF is singular, the inner CG breaks
  *     down or stalls and the call returns that status (MAG_ERR_NOT_CONVERGED).  There is no shift.
  * Algorithm: subspace iteration with q vectors, q = subspace or min(2p, p + 8) when 0;  p >= 1, p <= q <= 32, q <= n_free.
- *   1. q deterministic start vectors: vector j is the (j / 2)-th monomial xi^a eta^b (by total degree) of the coordinates
- *      normalised to the bounding box and shifted by 1/2, in direction x (j even) or y (j odd), zero on P.  Y = M X.
+ *   1. q deterministic start vectors: DOF d of a node in vector j is a fixed integer hash of the bits of the node's coordinates
+ *      and of 2 j + d, in [-1, 1), zero on P -- a function of the coordinates and j only, not of the numbering; independent on
+ *      any mesh (a strip one element thick, where polynomials of the coordinates are exactly dependent, solves like any other
+ *      part).  Y = M X.
  *   2. Each outer step: K_FF Z_j = Y_j for all q columns as ONE member set (u_in = 0, f_in = Y_j) through the driver of the load
  *      cases -- side by side on the chip, floor(CUs / G) per launch, where load cases run so, otherwise one after another;
- *      W = M Z;  A = Z^T Y (= Z^T K Z) and B = Z^T W, symmetrised;  on the host the pairs of (A, B), ascending, Q^T B Q = I;
+ *      W = M Z;  A = Z^T Y (= Z^T K Z) and B = Z^T W, symmetrised;  on the host the pairs of (A, B), ascending, Q^T B Q = I,
+ *      through the Cholesky factor of A scaled to a unit diagonal (A carries lambda_q / lambda_1 where B carries its square:
+ *      slender parts and 32 vectors are within reach);
  *      X = Z Q, Y = W Q (K X = Y_old Q to the accuracy of the inner solves: no further operator application);
  *      residual[k] from Y_old Q e_k - lambda_k Y_new e_k.
  *   3. Stop when the largest relative change of the first p eigenvalues is <= tol, or after max_outer steps: reaching the cap is
@@ -557,7 +561,13 @@ int mag_download_stress(mag_ctx *ctx, int32_t set, int32_t index, mag_stress_fie
  *   default above 32), max_outer < 0, a density that is not positive and finite, a tol or cg_tol that is negative or not finite,
  *   an index out of range, a communicator of more than one rank; MAG_ERR_STATE for no upload and for mag_download_modal /
  *   mag_get_modal_info / mag_get_modal_stats before a completed mag_run_modal.  subspace > n_free: MAG_ERR_BAD_ARGS once the
- *   ordering phase has counted the free DOFs. */
+ *   ordering phase has counted the free DOFs.
+ * Errors of the iteration, all MAG_ERR_NOT_CONVERGED with mag_last_error naming mag_run_modal and the outer step; the earlier
+ *   modal results are gone (MAG_ERR_STATE from mag_download_modal) and the context is usable as before: an inner solve that
+ *   breaks down or stops at the iteration cap (its own words follow); a subspace whose vectors are linearly dependent -- a
+ *   Cholesky pivot of the unit-diagonal A, or the ratio of the smallest to the largest eigenvalue of the reduced pencil, at or
+ *   below 1e-13 --, the column and the figure named.  The hashed start vectors cannot be exactly dependent for a legal input;
+ *   the tests' smallest figure is 1.4e-5 (an 8:1 cantilever, q = 20). */
 typedef struct mag_modal_options {
     int32_t modes;      /* p >= 1 */
     int32_t subspace;   /* q, 0: min(2p, p + 8); p <= q <= 32 */

@@ -4040,7 +4040,7 @@ int mag_run_modal(mag_ctx *ctx, const mag_modal_options *mo)
     magk::MassBatch mb;
     if (int rc = sens_mesh(ctx, mesh)) return rc;
     HIPCHK(hipMemsetAsync(set.uin.p, 0, vb * q, s));
-    magk::start_vectors(ctx->xy.as<double>(), ctx->uknown.as<uint8_t>(), ctx->small.as<double>() + 4 * 256, N, q, X, s);
+    magk::start_vectors(ctx->xy.as<double>(), ctx->uknown.as<uint8_t>(), N, q, X, s);
     if (int rc = mass_batch(ctx, mo->density, mo->lumped, 1, q, X, Y, mb)) return rc;
     magk::mass_apply(mesh, mb, s);
     HIPCHK(hipGetLastError());
@@ -4067,7 +4067,10 @@ int mag_run_modal(mag_ctx *ctx, const mag_modal_options *mo)
         info[4] = set.info[1];
         info[5] += set.info[2];
         info[6] += set.info[3];
-        if (status != MAG_OK) return status;
+        if (status != MAG_OK) { // (the inner solve's own status and words, under this entry point's name)
+            const std::string why = ctx->err;
+            return fail(ctx, status, "mag_run_modal: outer step %d: %s", (int)step + 1, why.c_str());
+        }
         for (int32_t j = 0; j < q; ++j)
             if (!set.stats[(size_t)j].converged)
                 return fail(ctx, MAG_ERR_NOT_CONVERGED,
@@ -4088,10 +4091,13 @@ int mag_run_modal(mag_ctx *ctx, const mag_modal_options *mo)
                 B[(size_t)i * q + j] = 0.5 * (h_gram[(size_t)q * q + (size_t)i * q + j] + h_gram[(size_t)q * q + (size_t)j * q + i]);
             }
         int pivot = -1;
-        const int eig = magh::sym_def_eig(q, A.data(), B.data(), lambda.data(), Qm.data(), &pivot);
+        double least = 0.0;
+        const int eig = magh::sym_def_eig(q, A.data(), B.data(), lambda.data(), Qm.data(), &pivot, &least);
         if (eig == magh::EIG_DEPENDENT)
-            return fail(ctx, MAG_ERR_NOT_CONVERGED, "mag_run_modal: outer step %d: the vectors of the subspace are linearly dependent (pivot %d of Z^T M Z)",
-                        (int)step + 1, pivot);
+            return fail(ctx, MAG_ERR_NOT_CONVERGED,
+                        "mag_run_modal: outer step %d: the vectors of the subspace are linearly dependent (pivot %d of the Gram matrices: %.3g against a "
+                        "unit diagonal, refused at or below %.3g)",
+                        (int)step + 1, pivot, least, magh::kEigPivotTol);
         if (eig != magh::EIG_OK) return fail(ctx, MAG_ERR_NOT_CONVERGED, "mag_run_modal: outer step %d: the Rayleigh-Ritz step did not converge", (int)step + 1);
         if (!prev.empty()) {
             double change = 0.0;

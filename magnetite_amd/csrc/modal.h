@@ -43,9 +43,9 @@ void rotate(const double *Z, const double *W, const double *Yold, const double *
 // out[2 k] = |R_k|^2, out[2 k + 1] = |Y_k|^2 for k < modes; partials: scratch [modes][kSensBlocks][2].  Two launches.
 void residual_norms(const double *R, const double *Y, int64_t N, int32_t modes, double *partials, double *out, hipStream_t s);
 
-// the q start vectors: vector j = monomial j / 2 (by total degree) of the bounding-box-normalised coordinates shifted by 1/2,
-// in direction j % 2, 0 on prescribed DOFs.  bbox4: xlo, ylo, xhi, yhi on the device.
-void start_vectors(const double *xy, const uint8_t *u_known, const double *bbox4, int64_t N, int32_t q, double *X, hipStream_t s);
+// the q start vectors: DOF d of node i in vector j = a fixed integer hash of the bits of the node's coordinates and of 2 j + d,
+// in [-1, 1), 0 on prescribed DOFs (tests/modal_ref.py hash_unit is its twin)
+void start_vectors(const double *xy, const uint8_t *u_known, int64_t N, int32_t q, double *X, hipStream_t s);
 
 // *bad = the first element whose signed area is not positive (all ones: none) -- an integer minimum, by offenders only
 void orientation(const double *xy, const int32_t *conn, int64_t N, int64_t E, unsigned long long *bad, hipStream_t s);

@@ -52,13 +52,19 @@ struct Mass {
     }
 };
 
-// the exponents of the m-th monomial xi^a eta^b, by total degree: 1, xi, eta, xi^2, xi eta, eta^2, ...
-__device__ inline void monomial(int32_t m, int32_t &a, int32_t &b)
+// the finaliser of splitmix64
+__device__ inline uint64_t mix64(uint64_t z)
 {
-    int32_t d = 0;
-    while ((d + 1) * (d + 2) / 2 <= m) ++d;
-    b = m - d * (d + 1) / 2;
-    a = d - b;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+// in [-1, 1): stream c of the node whose coordinates hashed to `node` (53 bits of the hash: the conversion is exact)
+__device__ inline double hash_unit(uint64_t node, uint32_t c)
+{
+    const uint64_t k = mix64(node + (uint64_t)(c + 1) * 0x9e3779b97f4a7c15ull);
+    return (double)(k >> 11) / 4503599627370496.0 - 1.0;
 }
 
 } // namespace
@@ -239,28 +245,22 @@ void residual_norms(const double *R, const double *Y, int64_t N, int32_t modes, 
     k_modal_norm_sum<<<dim3(1, (unsigned)modes), 256, 0, s>>>(partials, out);
 }
 
-// ---- the start vectors: a function of the uploaded coordinates and the vector's index only
-__global__ void __launch_bounds__(256) k_modal_start(const double2 *xy, const uint8_t *known, const double *bbox4, int64_t N, double2 *X)
+// ---- the start vectors: a function of the uploaded coordinates and the vector's index only -- a fixed integer hash of the
+// bits of the node's coordinates (+ 0.0: a -0 counts as 0) and of 2 j + direction, mapped to [-1, 1).  No polynomial of the
+// coordinates: nothing degenerates on a mesh one element thick, and the q vectors are as good as orthogonal
+__global__ void __launch_bounds__(256) k_modal_start(const double2 *xy, const uint8_t *known, int64_t N, double2 *X)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int32_t j = blockIdx.y;
+    const uint32_t j = blockIdx.y;
     if (i >= N) return;
-    const double xlo = bbox4[0], ylo = bbox4[1], xhi = bbox4[2], yhi = bbox4[3];
-    const double sx = xhi > xlo ? xhi - xlo : 1.0, sy = yhi > ylo ? yhi - ylo : 1.0;
     const double2 c = xy[i];
-    const double xi = (c.x - xlo) / sx + 0.5, eta = (c.y - ylo) / sy + 0.5;
-    int32_t a, b;
-    monomial(j >> 1, a, b);
-    double v = 1.0;
-    for (int32_t k = 0; k < a; ++k) v *= xi;
-    for (int32_t k = 0; k < b; ++k) v *= eta;
-    const bool y_dir = (j & 1) != 0;
-    X[(int64_t)j * N + i] = make_double2(y_dir || known[2 * i] ? 0.0 : v, !y_dir || known[2 * i + 1] ? 0.0 : v);
+    const uint64_t node = mix64(mix64((uint64_t)__double_as_longlong(c.x + 0.0) + 0x9e3779b97f4a7c15ull) ^ (uint64_t)__double_as_longlong(c.y + 0.0));
+    X[(int64_t)j * N + i] = make_double2(known[2 * i] ? 0.0 : hash_unit(node, 2 * j), known[2 * i + 1] ? 0.0 : hash_unit(node, 2 * j + 1));
 }
 
-void start_vectors(const double *xy, const uint8_t *u_known, const double *bbox4, int64_t N, int32_t q, double *X, hipStream_t s)
+void start_vectors(const double *xy, const uint8_t *u_known, int64_t N, int32_t q, double *X, hipStream_t s)
 {
-    k_modal_start<<<dim3((unsigned)((N + 255) / 256), (unsigned)q), 256, 0, s>>>((const double2 *)xy, u_known, bbox4, N, (double2 *)X);
+    k_modal_start<<<dim3((unsigned)((N + 255) / 256), (unsigned)q), 256, 0, s>>>((const double2 *)xy, u_known, N, (double2 *)X);
 }
 
 // ---- the reference's K_e carries the SIGNED area: an element of area <= 0 makes K indefinite.  The first offender by an atomic

@@ -1,46 +1,92 @@
 // Internal, host only (no HIP include: a host compiler alone builds it; tests/cpp/modal_eig.cpp does): the Rayleigh-Ritz step of
-// mag_run_modal -- the symmetric-definite generalised eigenproblem A q = lambda B q for n <= 32.
-//   B = L L^T (Cholesky),  C = L^-1 A L^-T,  C = V diag(lambda) V^T by cyclic Jacobi to convergence,  Q = L^-T V,
-// the pairs sorted ascending (equal values in the order Jacobi left them), so that Q^T B Q = I and Q^T A Q = diag(lambda), and
-// every column of Q with its entry of largest magnitude positive (the first on a tie): the same input gives the same bits.
+// mag_run_modal -- the generalised eigenproblem A q = lambda B q of two symmetric positive definite matrices for n <= 32.
+//   A and B scaled to A's unit diagonal (S = diag(A)^-1/2: A_s = S A S, B_s = S B S),  A_s = L L^T (Cholesky),
+//   C = L^-1 B_s L^-T,  C = V diag(mu) V^T by cyclic Jacobi to convergence,  lambda = 1 / mu,  Q = S L^-T V diag(mu)^-1/2,
+// the pairs sorted ascending in lambda (equal values in the order Jacobi left them), so that Q^T B Q = I and
+// Q^T A Q = diag(lambda), and every column of Q with its entry of largest magnitude positive (the first on a tie): the same
+// input gives the same bits.
+// Why A is the matrix factored: with Z = K^-1 Y, A = Z^T K Z carries the spread lambda_q / lambda_1 of the subspace where
+// B = Z^T M Z carries its square -- at the first outer step, where the columns of Z are no Ritz vectors yet, a slender part's B
+// has a condition beyond 1e13 and no Cholesky of it is to be trusted, while A's stays at its square root.  The large mu
+// (the lowest modes) come out of Jacobi to round-off; a small mu (a guard vector) to round-off of the largest.
+// What is refused (EIG_DEPENDENT): a Cholesky pivot of A_s at or below kEigPivotTol (each pivot stands against its own column:
+// the diagonal is 1), and a mu at or below kEigPivotTol times the largest (B deficient where A is not).
 #pragma once
 #include <cmath>
 
 namespace magh {
 
 constexpr int kEigMaxN = 32;
-constexpr double kEigPivotTol = 1e-13; // a Cholesky pivot <= this times the largest diagonal entry of B: dependent vectors
+constexpr double kEigPivotTol = 1e-13; // a pivot of the unit-diagonal A, or mu_min / mu_max, at or below this: dependent vectors
 
 enum { EIG_OK = 0, EIG_BAD_ARGS = 1, EIG_DEPENDENT = 2, EIG_NO_CONVERGENCE = 3 };
 
-// A, B: n x n row major, symmetric (the lower triangles are read).  lambda: n.  Q: n x n row major, column k = vector k.
-// *pivot: with EIG_DEPENDENT, the column whose pivot failed.
-inline int sym_def_eig(int n, const double *A, const double *B, double *lambda, double *Q, int *pivot)
+// the column with the smallest Cholesky pivot of the n x n matrix M (row major, the lower triangle is read) scaled to a unit
+// diagonal, a pivot that is not positive ending the search: names the dependent column where EIG_DEPENDENT comes from B
+inline int weakest_column(int n, const double *M)
 {
-    if (n < 1 || n > kEigMaxN || !A || !B || !lambda || !Q) return EIG_BAD_ARGS;
     constexpr int S = kEigMaxN;
-    double L[S][S] = {}, C[S][S] = {}, V[S][S] = {};
-    double top = 0.0;
-    for (int i = 0; i < n; ++i) top = std::fmax(top, B[i * n + i]);
-    // ---- B = L L^T
+    double L[S][S] = {}, d[S];
+    for (int i = 0; i < n; ++i) {
+        if (!(M[i * n + i] > 0.0)) return i;
+        d[i] = 1.0 / std::sqrt(M[i * n + i]);
+    }
+    int at = 0;
+    double least = 2.0;
     for (int j = 0; j < n; ++j) {
-        double s = B[j * n + j];
+        double s = 1.0;
         for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
-        if (!(s > kEigPivotTol * top) || !std::isfinite(s)) {
-            if (pivot) *pivot = j;
-            return EIG_DEPENDENT;
+        if (s < least) {
+            least = s;
+            at = j;
         }
+        if (!(s > 0.0)) return j;
         L[j][j] = std::sqrt(s);
         for (int i = j + 1; i < n; ++i) {
-            double t = B[i * n + j];
+            double t = d[i] * M[i * n + j] * d[j];
             for (int k = 0; k < j; ++k) t -= L[i][k] * L[j][k];
             L[i][j] = t / L[j][j];
         }
     }
-    // ---- C = L^-1 A L^-T: T = L^-1 A column by column, then C^T = L^-1 T^T row by row; the mean of both triangles
+    return at;
+}
+
+// A, B: n x n row major, symmetric (the lower triangles are read), positive definite.  lambda: n.  Q: n x n row major, column k
+// = vector k.  *pivot: with EIG_DEPENDENT, the column whose pivot failed.  *least (may be null): the smallest figure that was
+// tested against kEigPivotTol (on EIG_DEPENDENT the failing one).
+inline int sym_def_eig(int n, const double *A, const double *B, double *lambda, double *Q, int *pivot, double *least = nullptr)
+{
+    if (n < 1 || n > kEigMaxN || !A || !B || !lambda || !Q) return EIG_BAD_ARGS;
+    constexpr int S = kEigMaxN;
+    double L[S][S] = {}, C[S][S] = {}, V[S][S] = {}, d[S];
+    double low = 1.0;
+    const auto dependent = [&](int column, double figure) {
+        if (pivot) *pivot = column;
+        if (least) *least = figure;
+        return (int)EIG_DEPENDENT;
+    };
+    for (int i = 0; i < n; ++i) {
+        const double a = A[i * n + i];
+        if (!(a > 0.0) || !std::isfinite(a)) return dependent(i, a);
+        d[i] = 1.0 / std::sqrt(a);
+    }
+    // ---- A_s = L L^T
+    for (int j = 0; j < n; ++j) {
+        double s = 1.0;
+        for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
+        if (!(s > kEigPivotTol) || !std::isfinite(s)) return dependent(j, s);
+        low = std::fmin(low, s);
+        L[j][j] = std::sqrt(s);
+        for (int i = j + 1; i < n; ++i) {
+            double t = d[i] * A[i * n + j] * d[j];
+            for (int k = 0; k < j; ++k) t -= L[i][k] * L[j][k];
+            L[i][j] = t / L[j][j];
+        }
+    }
+    // ---- C = L^-1 B_s L^-T: T = L^-1 B_s column by column, then C^T = L^-1 T^T row by row; the mean of both triangles
     for (int c = 0; c < n; ++c)
         for (int i = 0; i < n; ++i) {
-            double t = i >= c ? A[i * n + c] : A[c * n + i];
+            double t = d[i] * (i >= c ? B[i * n + c] : B[c * n + i]) * d[c];
             for (int k = 0; k < i; ++k) t -= L[i][k] * C[k][c];
             C[i][c] = t / L[i][i];
         }
@@ -96,25 +142,31 @@ inline int sym_def_eig(int n, const double *A, const double *B, double *lambda, 
             }
     }
     if (!done) return EIG_NO_CONVERGENCE;
-    // ---- ascending (insertion sort: stable), Q = L^-T V, signs
+    // ---- mu descending = lambda ascending (insertion sort: stable), Q = S L^-T V diag(mu)^-1/2, signs
     int order[S];
     for (int k = 0; k < n; ++k) {
         int at = k;
-        while (at > 0 && C[order[at - 1]][order[at - 1]] > C[k][k]) {
+        while (at > 0 && C[order[at - 1]][order[at - 1]] < C[k][k]) {
             order[at] = order[at - 1];
             --at;
         }
         order[at] = k;
     }
+    const double mu_top = C[order[0]][order[0]], mu_low = C[order[n - 1]][order[n - 1]];
+    if (!(mu_low > kEigPivotTol * mu_top) || !std::isfinite(mu_top)) return dependent(weakest_column(n, B), mu_low / mu_top);
+    low = std::fmin(low, mu_low / mu_top);
+    if (least) *least = low;
     for (int k = 0; k < n; ++k) {
         const int src = order[k];
-        lambda[k] = C[src][src];
+        const double mu = C[src][src], scale = 1.0 / std::sqrt(mu);
+        lambda[k] = 1.0 / mu;
         double col[S];
         for (int i = n - 1; i >= 0; --i) {
             double t = V[i][src];
             for (int m = i + 1; m < n; ++m) t -= L[m][i] * col[m];
             col[i] = t / L[i][i];
         }
+        for (int i = 0; i < n; ++i) col[i] = d[i] * col[i] * scale;
         int big = 0;
         for (int i = 1; i < n; ++i)
             if (std::fabs(col[i]) > std::fabs(col[big])) big = i;

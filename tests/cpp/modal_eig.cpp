@@ -1,7 +1,9 @@
 // Host-only check of csrc/modal_host.h (the Rayleigh-Ritz step of mag_run_modal): for seeded symmetric positive definite pairs
 // (A, B) it prints n, A, B, the eigenvalues and Q in hex (tests/test_modal.py does the arithmetic), then a rank-deficient B,
-// which must be reported and not factored.  Built by g++ alone, with the address and undefined-behaviour sanitizers where
-// they link.
+// which must be reported and not factored, then graded pairs as the first outer step of a slender part hands them over:
+// A = G^T D G and B = G^T D^2 G with G orthogonal and B of condition 1e10 and 1e12, n = 12 and 32, their eigenvalues 1 / D
+// printed as "exact".  Built by g++ alone, with the address and undefined-behaviour sanitizers where they link.
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <vector>
@@ -31,6 +33,38 @@ std::vector<double> spd(int n, double shift)
             for (int k = 0; k < n; ++k) s += g[(size_t)k * n + i] * g[(size_t)k * n + j];
             m[(size_t)i * n + j] = s;
         }
+    return m;
+}
+
+// an orthogonal n x n G: the rows of a random matrix by Gram-Schmidt, twice
+std::vector<double> orthogonal(int n)
+{
+    std::vector<double> g((size_t)n * n);
+    for (double &v : g) v = uniform();
+    for (int pass = 0; pass < 2; ++pass)
+        for (int i = 0; i < n; ++i) {
+            double *gi = &g[(size_t)i * n];
+            for (int k = 0; k < i; ++k) {
+                const double *gk = &g[(size_t)k * n];
+                double dot = 0.0;
+                for (int c = 0; c < n; ++c) dot += gi[c] * gk[c];
+                for (int c = 0; c < n; ++c) gi[c] -= dot * gk[c];
+            }
+            double norm = 0.0;
+            for (int c = 0; c < n; ++c) norm += gi[c] * gi[c];
+            norm = std::sqrt(norm);
+            for (int c = 0; c < n; ++c) gi[c] /= norm;
+        }
+    return g;
+}
+
+// G^T diag(d) G
+std::vector<double> congruence(int n, const std::vector<double> &g, const std::vector<double> &d)
+{
+    std::vector<double> m((size_t)n * n, 0.0);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j)
+            for (int k = 0; k < n; ++k) m[(size_t)i * n + j] += g[(size_t)k * n + i] * d[(size_t)k] * g[(size_t)k * n + j];
     return m;
 }
 
@@ -88,5 +122,17 @@ int main()
                 for (int k = 0; k < 3; ++k) B[(size_t)i * n + j] += v[i][k] * v[j][k];
         if (solve_and_print(n, A, B) != magh::EIG_DEPENDENT) return 1;
     }
+    for (double cond : {1e10, 1e12})
+        for (int n : {12, 32}) { // graded: D_k^2 from 1 down to 1 / cond, every column of G in every entry
+            const std::vector<double> g = orthogonal(n);
+            std::vector<double> d((size_t)n), d2((size_t)n), exact((size_t)n);
+            for (int k = 0; k < n; ++k) {
+                d[(size_t)k] = std::pow(cond, -0.5 * k / (n - 1));
+                d2[(size_t)k] = d[(size_t)k] * d[(size_t)k];
+                exact[(size_t)k] = 1.0 / d[(size_t)k];
+            }
+            if (solve_and_print(n, congruence(n, g, d), congruence(n, g, d2)) != magh::EIG_OK) return 1;
+            print("exact", exact);
+        }
     return 0;
 }

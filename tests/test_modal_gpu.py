@@ -33,9 +33,11 @@ def assert_same_bits(a, b, what):
         assert a[k] == b[k], (what, k, a[k], b[k])
 
 
-def check_modes(name, out, lumped=False, max_outer=40):
-    """every bar of the issue for one result of modal() on mesh `name`; returns the figures it printed"""
-    prob, K, M, free, lam, Phi = ref.cached(name, RHO, lumped)
+def check_modes(name, out, lumped=False, max_outer=40, pairs=8):
+    """every bar of the issue for one result of modal() on part `name` of modal_ref.PARTS, against `pairs` (more than the modes
+    of out) reference pairs; returns the figures it printed"""
+    prob, K, M, free, lam, Phi = ref.cached(name, RHO, lumped, pairs)
+    assert len(out["lambda"]) < pairs
     p = len(out["lambda"])
     shapes = out["shapes"]
     err = float(np.max(np.abs(out["lambda"] - lam[:p]) / lam[:p]))
