@@ -592,6 +592,67 @@ int mag_get_modal_info(const mag_ctx *ctx, int32_t info[8]);
 /* statistics of inner solve j of the LAST outer step, as mag_get_case_stats */
 int mag_get_modal_stats(const mag_ctx *ctx, int32_t j, mag_stats *stats);
 
+/* ---- transient dynamics: Newmark time stepping of the uploaded part, on the device ------------------------------
+ * mag_run_transient: Newmark's method in acceleration form on the uploaded mesh and material, with density rho.
+ *   Mass.  M is the consistent mass, or the lumped one (lumped != 0), as in mag_run_modal.  Damping: C = alpha M + eta K
+ *     (rayleigh_mass, rayleigh_stiffness).
+ *   Supports.  DOFs with u_known == 1 are supports held at the uploaded u_in for all time: u_P = u_in, v_P = a_P = 0.
+ *   Loads.  The load on the free DOFs is amplitude[n] * f_in; amplitude is [steps + 1], NULL: all ones (a step load at t = 0).
+ *   Start.  u_0, v_0 are given on F (2N vectors, their entries on P ignored), or zero.  M_FF a_0 = (amplitude[0] f - C v_0 - K u_0)_F.
+ *   Step n -> n+1:   ut = u + dt v + dt^2 (1/2 - beta) a,   vt = v + dt (1 - gamma) a;
+ *     A_FF a' = (amplitude[n+1] f - alpha M vt - K (ut + eta vt))_F,   A = (1 + gamma dt alpha) M + (beta dt^2 + gamma dt eta) K,   a'_P = 0;
+ *     u' = ut + beta dt^2 a',   v' = vt + gamma dt a'.
+ *     Prescribed displacements enter through K ut (ut_P = u_in): no elimination pass.
+ *   beta and gamma are taken literally.  2 beta >= gamma >= 1/2 is unconditionally stable; anything else is the caller's to judge.
+ *   The solves.  The initial solve and every step's are the same code with other coefficients ((c_M, c_K) = (1, 0) for a_0).  Each
+ *     starts from zero and runs under MAG_STOP_REL with cg_tol whatever the context's stop rule is; the context's options are as
+ *     they were afterwards.  An exactly zero right-hand side gives a' = 0 in 0 iterations.  cg: 0 fused block rows of A with
+ *     block-Jacobi where the context has tile-local tables, else the CSR operator's phase; 1 | 2 | 3 fused plain / Jacobi /
+ *     block-Jacobi; 4 the CSR operator's phase on A_FF.
+ *   Reactions.  f_out is K (u + eta v) + M (a + alpha v) on P (the support reaction including inertia and damping) and
+ *     amplitude[n] f_in on F.
+ *   Records.  probes: DOF indices in caller numbering; their u, v, a at every step, row 0 = the start.  energies != 0: T = 1/2 v.Mv,
+ *     W = 1/2 u.Ku, P = amplitude[n] f.u_F per step.  snapshot_every = k > 0: u at steps 0, k, 2k, ...
+ *   resume != 0: starts from the final u, v, a, t of the previous completed run of this pass: no a_0 solve, u0 / v0 must be NULL,
+ *     amplitude[0] is ignored.  Its records cover its own steps, row 0 the resumed state.  n1 steps followed by a resumed n2 steps
+ *     give, bit for bit, the rows of one run of n1 + n2 steps.
+ * mag_assemble_effective: c_K K + c_M M in the layout of mag_assemble_csr (values_out: 4 * blocks doubles in `memory`).
+ * The pass needs an upload and no run.  It changes no other result of the context; a repeat gives the same bits (every sum has a
+ *   fixed order, no floating-point atomics); a new mag_upload drops its results.
+ * Errors, before any HIP call: MAG_ERR_BAD_ARGS (mag_last_error naming the function and the argument) for a null struct, steps < 1,
+ *   dt or density not positive and finite, beta, gamma, a Rayleigh coefficient or cg_tol negative or not finite, cg outside 0..4,
+ *   snapshot_every < 0, num_probes < 0 or > 0 with NULL probes, a `memory` outside enum mag_memory, more than one rank;
+ *   MAG_ERR_STATE for no upload, resume without a completed run or with u0 / v0, download or info before a completed run, a context
+ *   with an element stiffness field (the message names the field), assemble_csr = 0 or precision = 1.
+ * Errors after the first device work: a probe outside [0, 2N) and an element of signed area <= 0 (MAG_ERR_BAD_ARGS, the offender
+ *   named, as mag_run_modal); records that would not fit device memory (MAG_ERR_TOO_LARGE); a solve that breaks down
+ *   (MAG_ERR_NOT_CONVERGED naming the step: the pass's earlier results are gone, the context is usable as before).  The iteration
+ *   cap is no error (info[7] = 0).
+ * Out of scope: time-varying supports; a warm start of the step's CG; the on-chip CG on A; fields, variants and ranks; modal
+ *   superposition; explicit stepping without a solve for lumped mass. */
+typedef struct mag_transient_options {
+    int32_t steps, resume, lumped, cg, energies, snapshot_every, num_probes, memory;
+    double dt, beta, gamma, density, rayleigh_mass, rayleigh_stiffness, cg_tol; /* cg_tol 0: 1e-10 */
+    const double *amplitude, *u0, *v0;                                           /* NULL: ones, zero, zero */
+    const int32_t *probes;                                                       /* NULL: none */
+} mag_transient_options;                                                         /* 120 bytes */
+void mag_default_transient_options(mag_transient_options *opt); /* beta 0.25, gamma 0.5, everything else 0 / NULL */
+typedef struct mag_transient_result {
+    double *u_out, *v_out, *a_out, *f_out;  /* 2N, the final state; NULL members are skipped */
+    double *probe_u, *probe_v, *probe_a;    /* [steps + 1][num_probes], row 0 = the start */
+    double *energies;                       /* [steps + 1][3] = T, W, P */
+    double *snapshots;                      /* [steps / snapshot_every + 1][2N] of u, row 0 = the start */
+    int32_t *iterations;                    /* [steps + 1], entry 0 = the a_0 solve (0 in a resumed run) */
+    double scalars[4];                      /* t_start, t_end, 0, 0 (written by the call, on the host) */
+    int32_t memory, reserved;
+} mag_transient_result;                     /* 120 bytes */
+int mag_run_transient(mag_ctx *ctx, const mag_transient_options *opt);
+int mag_download_transient(mag_ctx *ctx, mag_transient_result *out);
+/* info[0] steps done, [1] cg_kernel (3 or 5), [2] preconditioner (0 / 1 / 2), [3] CG iterations of all solves, [4] the largest of
+ * a step, [5] snapshots kept, [6] resumed, [7] 1 when every solve converged */
+int mag_get_transient_info(const mag_ctx *ctx, int32_t info[8]);
+int mag_assemble_effective(mag_ctx *ctx, double c_K, double c_M, double density, int32_t lumped, double *values_out, int32_t memory);
+
 /* ---- adaptive mesh refinement: longest-edge bisection with conformity closure (Rivara) of the uploaded mesh, on the device ----
  * What acts on the ZZ indicator of mag_run_stress: solve -> mag_run_stress -> mag_run_refine -> mag_upload_refined -> solve, the
  * mesh never leaving the device.  The reference (gmsh meshing, no adaptivity) has no counterpart.  The result is a pure function

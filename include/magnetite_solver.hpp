@@ -159,6 +159,27 @@ struct ModalSpec {
     double density = 0.0, tol = 0.0, cg_tol = 0.0;
 };
 
+// The options of solver::transient (include/magnetite_hip.h, mag_transient_options); 0: the library's default.  amplitude: steps + 1
+// values or empty (ones); u0, v0: 2N values in the order of `nodes` or empty (zero); probes: DOF indices 2 * node + axis.
+struct TransientSpec {
+    std::int32_t steps = 0, cg = 0, snapshot_every = 0;
+    bool lumped = false, energies = false;
+    double dt = 0.0, beta = 0.25, gamma = 0.5, density = 0.0, rayleigh_mass = 0.0, rayleigh_stiffness = 0.0, cg_tol = 0.0;
+    std::vector<double> amplitude, u0, v0;
+    std::vector<std::int32_t> probes;
+};
+
+// What solver::transient returns: the outputs of mag_download_transient -- the final state u, v, a and its reactions f (2N each,
+// in the order of `nodes`), the probes' rows (steps + 1 rows of probes.size() values), the energies (steps + 1 rows of T, W, P),
+// the snapshots of u, the iterations per solve -- and mag_get_transient_info's words by name.
+struct Transient {
+    std::vector<double> u, v, a, f, probe_u, probe_v, probe_a, energies, snapshots;
+    std::vector<std::int32_t> iterations;
+    double t_start = 0, t_end = 0;
+    std::int32_t steps = 0, cg_kernel = 0, preconditioner = 0, cg_iterations = 0, max_step_iterations = 0, snapshots_kept = 0, resumed = 0,
+                 converged = 0;
+};
+
 // The objective of solver::objective (include/magnetite_hip.h, mag_objective): one row of weights (and of the target) for all
 // members -- 2N values for MAG_OBJ_DISP_LSQ, E values or none for MAG_OBJ_STRESS_PNORM.
 struct ObjectiveSpec {
@@ -691,6 +712,86 @@ inline Result modal(const std::vector<Node> &nodes, const std::vector<Element> &
     out.vectors_per_launch = info[4];
     out.launches = info[5];
     out.redone = info[6];
+    mag_destroy(ctx);
+    return std::nullopt;
+}
+
+// Transient dynamics (mag_run_transient) of the part: spec.steps steps of Newmark's method with the density of spec (the model has
+// none).  The DOFs of `nodes` with a displacement are supports held at that value for all time; the forces are the load, scaled
+// by spec.amplitude step by step.  Nothing static is solved.  A solve that stops at the iteration cap is no error: out.converged == 0.
+inline Result transient(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                        const TransientSpec &spec, Transient &out, const mag_options *options = nullptr)
+{
+    const std::size_t N = nodes.size();
+    std::vector<double> xy, u_in(2 * N), f_in(2 * N);
+    std::vector<std::uint8_t> u_known;
+    std::vector<std::int32_t> conn;
+    if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
+    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
+    if (!spec.amplitude.empty() && spec.amplitude.size() != (std::size_t)std::max(spec.steps, 0) + 1)
+        return detail::solver_error("the amplitude has another length than steps + 1");
+    if ((!spec.u0.empty() && spec.u0.size() != 2 * N) || (!spec.v0.empty() && spec.v0.size() != 2 * N))
+        return detail::solver_error("u0 / v0 have another length than 2 N");
+    mag_ctx *ctx = mag_create(options);
+    if (!ctx) return detail::solver_error("mag_create failed");
+    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
+    if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    mag_transient_options o;
+    mag_default_transient_options(&o);
+    o.steps = spec.steps;
+    o.lumped = spec.lumped ? 1 : 0;
+    o.cg = spec.cg;
+    o.energies = spec.energies ? 1 : 0;
+    o.snapshot_every = spec.snapshot_every;
+    o.num_probes = (std::int32_t)spec.probes.size();
+    o.memory = MAG_MEM_HOST;
+    o.dt = spec.dt;
+    o.beta = spec.beta;
+    o.gamma = spec.gamma;
+    o.density = spec.density;
+    o.rayleigh_mass = spec.rayleigh_mass;
+    o.rayleigh_stiffness = spec.rayleigh_stiffness;
+    o.cg_tol = spec.cg_tol;
+    o.amplitude = spec.amplitude.empty() ? nullptr : spec.amplitude.data();
+    o.u0 = spec.u0.empty() ? nullptr : spec.u0.data();
+    o.v0 = spec.v0.empty() ? nullptr : spec.v0.data();
+    o.probes = spec.probes.empty() ? nullptr : spec.probes.data();
+    if (mag_run_transient(ctx, &o) != MAG_OK) return detail::fail_and_destroy(ctx);
+    std::int32_t info[8] = {};
+    if (mag_get_transient_info(ctx, info) != MAG_OK) return detail::fail_and_destroy(ctx);
+    const std::size_t rows = (std::size_t)info[0] + 1, P = spec.probes.size();
+    out = Transient{};
+    out.u.resize(2 * N);
+    out.v.resize(2 * N);
+    out.a.resize(2 * N);
+    out.f.resize(2 * N);
+    out.probe_u.resize(rows * P);
+    out.probe_v.resize(rows * P);
+    out.probe_a.resize(rows * P);
+    if (spec.energies) out.energies.resize(3 * rows);
+    out.snapshots.resize((std::size_t)info[5] * 2 * N);
+    out.iterations.resize(rows);
+    mag_transient_result d{};
+    d.u_out = out.u.data();
+    d.v_out = out.v.data();
+    d.a_out = out.a.data();
+    d.f_out = out.f.data();
+    if (P) d.probe_u = out.probe_u.data(), d.probe_v = out.probe_v.data(), d.probe_a = out.probe_a.data();
+    if (spec.energies) d.energies = out.energies.data();
+    if (info[5]) d.snapshots = out.snapshots.data();
+    d.iterations = out.iterations.data();
+    d.memory = MAG_MEM_HOST;
+    if (mag_download_transient(ctx, &d) != MAG_OK) return detail::fail_and_destroy(ctx);
+    out.t_start = d.scalars[0];
+    out.t_end = d.scalars[1];
+    out.steps = info[0];
+    out.cg_kernel = info[1];
+    out.preconditioner = info[2];
+    out.cg_iterations = info[3];
+    out.max_step_iterations = info[4];
+    out.snapshots_kept = info[5];
+    out.resumed = info[6];
+    out.converged = info[7];
     mag_destroy(ctx);
     return std::nullopt;
 }

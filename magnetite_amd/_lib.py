@@ -40,6 +40,7 @@ SYMBOLS = [
     "mag_run_objective", "mag_download_objective",
     "mag_run_stress", "mag_download_stress",
     "mag_run_modal", "mag_download_modal", "mag_get_modal_info", "mag_get_modal_stats", "mag_apply_mass",
+    "mag_default_transient_options", "mag_run_transient", "mag_download_transient", "mag_get_transient_info", "mag_assemble_effective",
     "mag_run_refine", "mag_get_refine_info", "mag_download_refine", "mag_upload_refined",
     "mag_set_element_scale", "mag_design_init", "mag_design_step", "mag_get_design_info", "mag_download_design",
     "mag_comm_get_unique_id", "mag_comm_init_rccl", "mag_comm_query", "mag_comm_init_callback", "mag_comm_set_window", "mag_comm_inbox_create", "mag_comm_inbox_open",
@@ -114,6 +115,21 @@ class ModalOptions(C.Structure):
 
 class ModalResult(C.Structure):
     _fields_ = [("lambda_out", C.c_void_p), ("frequency_out", C.c_void_p), ("residual_out", C.c_void_p), ("shapes_out", C.c_void_p),
+                ("memory", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TransientOptions(C.Structure):
+    _fields_ = [("steps", C.c_int32), ("resume", C.c_int32), ("lumped", C.c_int32), ("cg", C.c_int32), ("energies", C.c_int32),
+                ("snapshot_every", C.c_int32), ("num_probes", C.c_int32), ("memory", C.c_int32),
+                ("dt", C.c_double), ("beta", C.c_double), ("gamma", C.c_double), ("density", C.c_double),
+                ("rayleigh_mass", C.c_double), ("rayleigh_stiffness", C.c_double), ("cg_tol", C.c_double),
+                ("amplitude", C.c_void_p), ("u0", C.c_void_p), ("v0", C.c_void_p), ("probes", C.c_void_p)]
+
+
+class TransientResult(C.Structure):
+    _fields_ = [("u_out", C.c_void_p), ("v_out", C.c_void_p), ("a_out", C.c_void_p), ("f_out", C.c_void_p),
+                ("probe_u", C.c_void_p), ("probe_v", C.c_void_p), ("probe_a", C.c_void_p), ("energies", C.c_void_p),
+                ("snapshots", C.c_void_p), ("iterations", C.c_void_p), ("scalars", C.c_double * 4),
                 ("memory", C.c_int32), ("reserved", C.c_int32)]
 
 
@@ -229,6 +245,13 @@ def lib():
         L.mag_get_modal_info.argtypes = [vp, ip]
         L.mag_get_modal_stats.argtypes = [vp, C.c_int32, C.POINTER(Stats)]
         L.mag_apply_mass.argtypes = [vp, C.c_double, C.c_int32, dp, dp, C.c_int32]
+    if hasattr(L, "mag_run_transient"):  # (likewise: scripts/transient_probe.py)
+        L.mag_default_transient_options.argtypes = [C.POINTER(TransientOptions)]
+        L.mag_default_transient_options.restype = None
+        L.mag_run_transient.argtypes = [vp, C.POINTER(TransientOptions)]
+        L.mag_download_transient.argtypes = [vp, C.POINTER(TransientResult)]
+        L.mag_get_transient_info.argtypes = [vp, ip]
+        L.mag_assemble_effective.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_int32, dp, C.c_int32]
     if hasattr(L, "mag_run_refine"):  # (likewise: scripts/refine_probe.py)
         L.mag_run_refine.argtypes = [vp, C.POINTER(RefineOptions)]
         L.mag_get_refine_info.argtypes = [vp, C.POINTER(C.c_int64)]

@@ -32,6 +32,7 @@
 #include "recover.h"
 #include "refine.h"
 #include "sens.h"
+#include "transient.h"
 
 using magk::CgState;
 
@@ -323,6 +324,22 @@ struct mag_ctx {
     int64_t design_steps = 0;
     double design_info[8] = {};
     DevBuf ds_rho, ds_rhof, ds_w, ds_area, ds_node_area, ds_node, ds_tmp, ds_dJ, ds_dJdrho, ds_bq, ds_rho_new, ds_part, ds_small;
+
+    // transient dynamics (mag_run_transient): the mass and the effective matrix in K's pattern (tr_aval in kval's layout), the
+    // block-row table and the gathered values of A in buffers of the pass's own (fc_* are a field's), the state, the predictors,
+    // the right-hand side, a zero vector, the records of the last run, and the words of mag_get_transient_info.  The results hang
+    // on the upload only: a new mag_upload drops them, a new run replaces them
+    DevBuf tr_mval, tr_aval, tr_width, tr_meta, tr_slot, tr_src, tr_val, tr_minv, tr_hminv;
+    DevBuf tr_u, tr_v, tr_a, tr_ut, tr_vt, tr_rhs, tr_zero, tr_f, tr_ku, tr_mv, tr_amp, tr_in, tr_probes, tr_bad;
+    DevBuf tr_probe, tr_energy, tr_snap, tr_part;
+    bool tr_have = false;
+    int32_t tr_info[8] = {}, tr_steps = 0, tr_num_probes = 0, tr_snaps = 0;
+    bool tr_energies = false;
+    double tr_t0 = 0.0, tr_t1 = 0.0, tr_amp_last = 1.0;
+    std::vector<int32_t> tr_iterations;
+    // the length of the FIRST poll block of the pass's next solve (0: check_every, as for every other caller): the pass expects
+    // the iteration count of its previous solve and polls in short blocks behind it
+    int32_t tr_first_block = 0;
 
     magc::Comm comm;
 };
@@ -975,17 +992,22 @@ bool assemble_from_ctiles(const mag_ctx *ctx)
 }
 
 // ---- mag_options.field_cg: the block-row table of K, once per order and pattern; the gathered values, once per assembly ----
-int ensure_field_table(mag_ctx *ctx)
+// The table of the order and the pattern held now, in the buffers of its owner: a field's (fc_*, ensure_field_table) or the
+// transient pass's (tr_*).  val: room for the gathered values
+struct FieldTable {
+    DevBuf &width, &meta, &slot, &src, &val;
+    int64_t total = 0;
+};
+
+int build_field_table(mag_ctx *ctx, FieldTable &tab)
 {
-    if (ctx->fc_ready || !field_cg_selected(ctx)) return MAG_OK;
     using magk::FieldTileMeta;
     hipStream_t s = ctx->stream;
-    const auto t_start = std::chrono::steady_clock::now();
     const int32_t T = ctx->T, B = ctx->B;
-    HIPCHK(ctx->fc_width.reserve(4 * (size_t)T + 64));
-    magk::field_widths(ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(), ctx->N, B, T, ctx->fc_width.as<int32_t>(), s);
+    HIPCHK(tab.width.reserve(4 * (size_t)T + 64));
+    magk::field_widths(ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(), ctx->N, B, T, tab.width.as<int32_t>(), s);
     std::vector<int32_t> width((size_t)T), hoff((size_t)T + 1);
-    HIPCHK(hipMemcpyAsync(width.data(), ctx->fc_width.p, 4 * (size_t)T, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(width.data(), tab.width.p, 4 * (size_t)T, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(hoff.data(), ctx->tile_hoff.p, 4 * ((size_t)T + 1), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     std::vector<FieldTileMeta> meta((size_t)T);
@@ -994,23 +1016,53 @@ int ensure_field_table(mag_ctx *ctx)
         meta[(size_t)t] = FieldTileMeta{total, width[(size_t)t], hoff[(size_t)t], hoff[(size_t)t + 1] - hoff[(size_t)t], 0, 0};
         total += (int64_t)width[(size_t)t] * B;
     }
-    ctx->fc_total = total;
-    HIPCHK(ctx->fc_meta.reserve(sizeof(FieldTileMeta) * (size_t)T));
-    HIPCHK(ctx->fc_slot.reserve(2 * (size_t)total + 64));
-    HIPCHK(ctx->fc_src.reserve(4 * (size_t)total + 64));
-    HIPCHK(ctx->fc_val.reserve(2 * 16 * (size_t)total));
-    HIPCHK(hipMemcpyAsync(ctx->fc_meta.p, meta.data(), sizeof(FieldTileMeta) * (size_t)T, hipMemcpyHostToDevice, s));
-    int32_t *err = ctx->fc_width.as<int32_t>() + T; // (the spare words behind the widths)
+    tab.total = total;
+    HIPCHK(tab.meta.reserve(sizeof(FieldTileMeta) * (size_t)T));
+    HIPCHK(tab.slot.reserve(2 * (size_t)total + 64));
+    HIPCHK(tab.src.reserve(4 * (size_t)total + 64));
+    HIPCHK(tab.val.reserve(2 * 16 * (size_t)total));
+    HIPCHK(hipMemcpyAsync(tab.meta.p, meta.data(), sizeof(FieldTileMeta) * (size_t)T, hipMemcpyHostToDevice, s));
+    int32_t *err = tab.width.as<int32_t>() + T; // (the spare words behind the widths)
     HIPCHK(hipMemsetAsync(err, 0, 4, s));
     magk::field_rows(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->perm.as<uint32_t>(), ctx->iperm.as<int32_t>(),
-                     ctx->halo_g.as<int32_t>(), ctx->fc_meta.as<FieldTileMeta>(), ctx->N, B, T, ctx->fc_slot.as<uint16_t>(),
-                     ctx->fc_src.as<int32_t>(), err, s);
+                     ctx->halo_g.as<int32_t>(), tab.meta.as<FieldTileMeta>(), ctx->N, B, T, tab.slot.as<uint16_t>(),
+                     tab.src.as<int32_t>(), err, s);
     int32_t h_err = 0;
     HIPCHK(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s)); // (the host vectors must outlive the copies)
     if (h_err) return fail(ctx, MAG_ERR_STATE, "field_cg: a column of K is in neither its tile nor the tile's halo list");
-    ctx->fc_grid = magk::field_cg_grid(B, ctx->cap, T, ctx->opt.field_cg >= 2);
+    return MAG_OK;
+}
+
+// The numeric part for the matrix values `val` (kval's layout) on a table: the gathered copy with the Dirichlet mask applied
+// and, for kind 1 | 2, the preconditioner's inverse node blocks (diagonal | 2 x 2) with their halo copies
+int field_values(mag_ctx *ctx, const FieldTable &tab, const double *val, int kind, DevBuf &minv, DevBuf &hminv)
+{
+    using magk::FieldTileMeta;
+    hipStream_t s = ctx->stream;
+    magk::field_gather(ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(), val, ctx->maskP.as<uint8_t>(),
+                       ctx->halo_g.as<int32_t>(), tab.meta.as<FieldTileMeta>(), tab.slot.as<uint16_t>(),
+                       tab.src.as<int32_t>(), ctx->N, ctx->B, ctx->T, tab.total, tab.val.as<double2>(), s);
+    if (kind) {
+        HIPCHK(minv.reserve(16 * (size_t)ctx->N));
+        HIPCHK(hminv.reserve(16 * (size_t)std::max<int64_t>(ctx->halo_total, 1)));
+        magk::field_minv(ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(), val, ctx->maskP.as<uint8_t>(),
+                         tab.meta.as<FieldTileMeta>(), tab.src.as<int32_t>(), ctx->N, ctx->B, kind, minv.as<float4>(), s);
+        magk::halo_minv(ctx->halo_g.as<int32_t>(), minv.as<float4>(), ctx->halo_total, hminv.as<float4>(), s);
+    }
+    HIPCHK(hipGetLastError());
+    return MAG_OK;
+}
+
+int ensure_field_table(mag_ctx *ctx)
+{
+    if (ctx->fc_ready || !field_cg_selected(ctx)) return MAG_OK;
+    const auto t_start = std::chrono::steady_clock::now();
+    FieldTable tab{ctx->fc_width, ctx->fc_meta, ctx->fc_slot, ctx->fc_src, ctx->fc_val};
+    if (int rc = build_field_table(ctx, tab)) return rc;
+    ctx->fc_total = tab.total;
+    ctx->fc_grid = magk::field_cg_grid(ctx->B, ctx->cap, ctx->T, ctx->opt.field_cg >= 2);
     ctx->fc_ready = true;
     ctx->fc_build_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     return MAG_OK;
@@ -1021,21 +1073,9 @@ int field_numeric(mag_ctx *ctx)
 {
     if (!field_cg_selected(ctx)) return MAG_OK;
     if (int rc = ensure_field_table(ctx)) return rc;
-    using magk::FieldTileMeta;
-    hipStream_t s = ctx->stream;
-    magk::field_gather(ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(), ctx->kval.as<double>(), ctx->maskP.as<uint8_t>(),
-                       ctx->halo_g.as<int32_t>(), ctx->fc_meta.as<FieldTileMeta>(), ctx->fc_slot.as<uint16_t>(),
-                       ctx->fc_src.as<int32_t>(), ctx->N, ctx->B, ctx->T, ctx->fc_total, ctx->fc_val.as<double2>(), s);
-    if (ctx->opt.field_cg >= 2) {
-        HIPCHK(ctx->minvP.reserve(16 * (size_t)ctx->N));
-        HIPCHK(ctx->halo_minv.reserve(16 * (size_t)std::max<int64_t>(ctx->halo_total, 1)));
-        magk::field_minv(ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(), ctx->kval.as<double>(), ctx->maskP.as<uint8_t>(),
-                         ctx->fc_meta.as<FieldTileMeta>(), ctx->fc_src.as<int32_t>(), ctx->N, ctx->B,
-                         ctx->opt.field_cg == 3 ? 2 : 1, ctx->minvP.as<float4>(), s);
-        magk::halo_minv(ctx->halo_g.as<int32_t>(), ctx->minvP.as<float4>(), ctx->halo_total, ctx->halo_minv.as<float4>(), s);
-    }
-    HIPCHK(hipGetLastError());
-    return MAG_OK;
+    FieldTable tab{ctx->fc_width, ctx->fc_meta, ctx->fc_slot, ctx->fc_src, ctx->fc_val, ctx->fc_total};
+    const int kind = ctx->opt.field_cg >= 2 ? (ctx->opt.field_cg == 3 ? 2 : 1) : 0;
+    return field_values(ctx, tab, ctx->kval.as<double>(), kind, ctx->minvP, ctx->halo_minv);
 }
 
 int assemble_values(mag_ctx *ctx)
@@ -1884,8 +1924,10 @@ int cg_phase_persist(mag_ctx *ctx)
 }
 
 // solver.rs:365-404,427-432,123-137 on the device: K_ff (exact zeros dropped) + b in compact unknown numbering
-int build_reduced(mag_ctx *ctx, bool fill)
+// (kval: the matrix in K's pattern -- ctx->kval, or the transient pass's A; rhs: b = f_in - K u_in of the uploaded problem too)
+int build_reduced(mag_ctx *ctx, bool fill, const double *kval = nullptr, bool rhs = true)
 {
+    if (!kval) kval = ctx->kval.as<double>();
     const int64_t N = ctx->N, n = 2 * N;
     hipStream_t s = ctx->stream;
     HIPCHK(ctx->isfree.reserve(4 * ((size_t)n + 1)));
@@ -1894,7 +1936,7 @@ int build_reduced(mag_ctx *ctx, bool fill)
     HIPCHK(ctx->rowoff.reserve(4 * ((size_t)n + 1)));
     magk::free_flags(ctx->uknown.as<uint8_t>(), n, ctx->isfree.as<int32_t>(), s);
     if (int rc = scan_i32(ctx, ctx->isfree.as<int32_t>(), ctx->fidx.as<int32_t>(), (size_t)n + 1)) return rc;
-    magk::reduce_count(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->kval.as<double>(),
+    magk::reduce_count(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), kval,
                        ctx->uknown.as<uint8_t>(), N, ctx->rcnt.as<int32_t>(), s);
     if (int rc = scan_i32(ctx, ctx->rcnt.as<int32_t>(), ctx->rowoff.as<int32_t>(), (size_t)n + 1)) return rc;
     int32_t h[2] = {0, 0};
@@ -1911,22 +1953,26 @@ int build_reduced(mag_ctx *ctx, bool fill)
     HIPCHK(ctx->col_ff.reserve(4 * (size_t)(nz > 0 ? nz : 1)));
     HIPCHK(ctx->val_ff.reserve(8 * (size_t)(nz > 0 ? nz : 1)));
     HIPCHK(ctx->b_ff.reserve(8 * (size_t)nf));
-    magk::reduce_fill(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->kval.as<double>(),
+    magk::reduce_fill(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), kval,
                       ctx->uknown.as<uint8_t>(), ctx->fidx.as<int32_t>(), ctx->rowoff.as<int32_t>(), N,
                       ctx->rp_ff.as<int32_t>(), ctx->col_ff.as<int32_t>(), ctx->val_ff.as<double>(), s);
-    magk::rhs_compact(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->kval.as<double>(),
-                      ctx->uknown.as<uint8_t>(), ctx->uin.as<double>(), ctx->fin.as<double>(),
-                      ctx->fidx.as<int32_t>(), N, ctx->b_ff.as<double>(), s);
+    if (rhs)
+        magk::rhs_compact(ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), kval,
+                          ctx->uknown.as<uint8_t>(), ctx->uin.as<double>(), ctx->fin.as<double>(),
+                          ctx->fidx.as<int32_t>(), N, ctx->b_ff.as<double>(), s);
     HIPCHK(hipGetLastError());
     return MAG_OK;
 }
 
 // MAG_OP_CSR: the reference's own iteration (CSR SpMV on K_ff + argmin recurrences), three launches per iteration
-int cg_phase_csr(mag_ctx *ctx)
+// (reduced: the reduced system and its right-hand side are in place -- the transient pass's, built once per run of the pass;
+// known / u_out: the values of the prescribed DOFs and where the expanded solution goes)
+int cg_phase_csr(mag_ctx *ctx, bool reduced = false, const double *known = nullptr, double *u_out = nullptr)
 {
     hipStream_t s = ctx->stream;
     if (ctx->comm.distributed()) return fail(ctx, MAG_ERR_BAD_ARGS, "cg_operator MAG_OP_CSR is single-GPU only");
-    if (int rc = build_reduced(ctx, true)) return rc;
+    if (!reduced)
+        if (int rc = build_reduced(ctx, true)) return rc;
     const int64_t nf = ctx->nf;
     const size_t vb = 8 * (size_t)nf;
     double *x = ctx->x.as<double>(), *r = ctx->r.as<double>(), *q = ctx->q.as<double>();
@@ -1938,9 +1984,11 @@ int cg_phase_csr(mag_ctx *ctx)
     magk::cg_setup(ctx->partRR.as<double>(), grid, ctx->opt.stop_mode, ctx->opt.tol, (long long)ctx->opt.max_iter,
                    ctx->state.as<CgState>(), s);
     HIPCHK(hipGetLastError());
-    const int G = ctx->opt.check_every;
+    int G = ctx->tr_first_block > 0 ? ctx->tr_first_block : ctx->opt.check_every;
     auto block = [&]() -> int {
-        for (int i = 0; i < G; ++i) {
+        const int len = G;
+        G = ctx->opt.check_every;
+        for (int i = 0; i < len; ++i) {
             magk::CsrCgParams P = {};
             P.n = nf;
             P.nPart = grid;
@@ -1968,8 +2016,8 @@ int cg_phase_csr(mag_ctx *ctx)
     if (int rc = run_blocks(ctx, ctx->state, ctx->h_state, block)) return rc;
     HIPCHK(hipMemcpyAsync(&ctx->h_state[2], ctx->state.p, sizeof(CgState), hipMemcpyDeviceToHost, s));
     // solver.rs:443-454: the solution goes back into the unknown slots in ascending DOF order
-    magk::expand_free(x, ctx->fidx.as<int32_t>(), ctx->uknown.as<uint8_t>(), ctx->uin.as<double>(), 2 * ctx->N,
-                      ctx->u.as<double>(), s);
+    magk::expand_free(x, ctx->fidx.as<int32_t>(), ctx->uknown.as<uint8_t>(), known ? known : ctx->uin.as<double>(), 2 * ctx->N,
+                      u_out ? u_out : ctx->u.as<double>(), s);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
     take_stats(ctx, ctx->h_state[2]);
@@ -1979,22 +2027,40 @@ int cg_phase_csr(mag_ctx *ctx)
 // ---- mag_options.field_cg: one fused launch per iteration over the assembled K's block rows (cg.hip, k_cg_field) ----
 // cg_phase_fused's protocol on one GPU: the right-hand side in bP is in Hilbert numbering already, the solution stays in
 // ctx->x; the reduced system (build_reduced) is not needed and not built.
-magk::FieldCgParams field_cg_params(mag_ctx *ctx, int par)
+// the matrix of a solve: the block-row table, the gathered values and the inverse blocks -- a field's K (field_system), or the
+// transient pass's A
+struct FieldSystem {
+    const magk::FieldTileMeta *meta;
+    const uint16_t *slot;
+    const double2 *fval;
+    const float4 *minvP, *halo_minv; // null: plain CG
+    int64_t total;
+    int32_t grid;
+};
+
+FieldSystem field_system(const mag_ctx *ctx)
+{
+    const bool pre = ctx->opt.field_cg >= 2;
+    return {ctx->fc_meta.as<magk::FieldTileMeta>(), ctx->fc_slot.as<uint16_t>(), ctx->fc_val.as<double2>(),
+            pre ? ctx->minvP.as<float4>() : nullptr, pre ? ctx->halo_minv.as<float4>() : nullptr, ctx->fc_total, ctx->fc_grid};
+}
+
+magk::FieldCgParams field_cg_params(mag_ctx *ctx, int par, const FieldSystem &sys)
 {
     magk::FieldCgParams P = {};
     const int32_t stride = magk::kMaxGrid;
     P.N = ctx->N;
-    P.total = ctx->fc_total;
+    P.total = sys.total;
     P.T = ctx->T;
-    P.nPart = ctx->fc_grid;
+    P.nPart = sys.grid;
     P.cap = ctx->cap;
     P.par = par;
     P.hist_len = ctx->opt.history_len;
     P.part_stride = stride;
     P.maskP = ctx->maskP.as<uint8_t>();
-    P.meta = ctx->fc_meta.as<magk::FieldTileMeta>();
-    P.slot = ctx->fc_slot.as<uint16_t>();
-    P.fval = ctx->fc_val.as<double2>();
+    P.meta = sys.meta;
+    P.slot = sys.slot;
+    P.fval = sys.fval;
     P.halo_g = ctx->halo_g.as<int32_t>();
     P.in = (par ? ctx->rqp1 : ctx->rqp0).as<magk::Rqp>();
     P.out = (par ? ctx->rqp0 : ctx->rqp1).as<magk::Rqp>();
@@ -2004,35 +2070,31 @@ magk::FieldCgParams field_cg_params(mag_ctx *ctx, int par)
     P.part_out = part + (size_t)(par ^ 1) * 5 * stride;
     P.st = ctx->fstate.as<magk::FusedState>();
     P.hist = ctx->hist.as<double>();
-    if (ctx->opt.field_cg >= 2) {
-        P.minvP = ctx->minvP.as<float4>();
-        P.halo_minv = ctx->halo_minv.as<float4>();
-    }
+    P.minvP = sys.minvP;
+    P.halo_minv = sys.halo_minv;
     return P;
 }
 
-int field_cg_block(mag_ctx *ctx, int G)
+int field_cg_block(mag_ctx *ctx, int G, const FieldSystem &sys)
 {
-    for (int i = 0; i < G; ++i) magk::field_cg_launch(field_cg_params(ctx, i & 1), ctx->B, ctx->fc_grid, ctx->stream);
+    for (int i = 0; i < G; ++i) magk::field_cg_launch(field_cg_params(ctx, i & 1, sys), ctx->B, sys.grid, ctx->stream);
     HIPCHK(hipGetLastError());
     return MAG_OK;
 }
 
-int cg_phase_field(mag_ctx *ctx)
+int cg_phase_field(mag_ctx *ctx, const FieldSystem &sys)
 {
     using magk::FusedState;
     hipStream_t s = ctx->stream;
-    if (!ctx->fc_ready) return fail(ctx, MAG_ERR_STATE, "field_cg: no block-row table (K has not been assembled under this field)");
-    const bool pre = ctx->opt.field_cg >= 2;
     HIPCHK(ctx->rqp0.reserve(sizeof(magk::Rqp) * (size_t)ctx->N));
     HIPCHK(ctx->rqp1.reserve(sizeof(magk::Rqp) * (size_t)ctx->N));
     HIPCHK(ctx->fpart.reserve(8 * 2 * 5 * (size_t)magk::kMaxGrid));
     HIPCHK(ctx->fstate.reserve(sizeof(FusedState)));
     HIPCHK(hipMemsetAsync(ctx->x.p, 0, 16 * (size_t)ctx->N, s));
     double *part = ctx->fpart.as<double>();
-    const int32_t stride = magk::kMaxGrid, grid = ctx->fc_grid;
+    const int32_t stride = magk::kMaxGrid, grid = sys.grid;
     HIPCHK(hipMemsetAsync(part, 0, 8 * 2 * 5 * (size_t)stride, s));
-    magk::fused_init(ctx->bP.as<double2>(), pre ? ctx->minvP.as<float4>() : nullptr, ctx->rqp0.as<magk::Rqp>(),
+    magk::fused_init(ctx->bP.as<double2>(), sys.minvP, ctx->rqp0.as<magk::Rqp>(),
                      ctx->rqp1.as<magk::Rqp>(), ctx->N, ctx->B, ctx->T, 0, ctx->T, part, stride, grid, s);
     magk::fused_setup(part, grid, stride, ctx->opt.stop_mode, ctx->opt.tol, (long long)ctx->opt.max_iter,
                       ctx->fstate.as<FusedState>(), s);
@@ -2043,13 +2105,18 @@ int cg_phase_field(mag_ctx *ctx)
     if (graph) {
         const mag_ctx::GraphKey k =
             graph_key(ctx, G, {ctx->x.p, ctx->rqp0.p, ctx->rqp1.p, ctx->fpart.p, ctx->fstate.p, ctx->hist.p, ctx->maskP.p,
-                               ctx->fc_meta.p, ctx->fc_slot.p, ctx->fc_val.p, ctx->halo_g.p, (void *)(intptr_t)ctx->cap,
-                               (void *)(intptr_t)(0x10000 + ctx->fc_grid) /* block rows */, (void *)(intptr_t)ctx->fc_total,
-                               pre ? ctx->minvP.p : nullptr, pre ? ctx->halo_minv.p : nullptr});
-        if (int rc = capture_graph(ctx, k, [&] { return field_cg_block(ctx, G); })) return rc;
+                               (void *)sys.meta, (void *)sys.slot, (void *)sys.fval, ctx->halo_g.p, (void *)(intptr_t)ctx->cap,
+                               (void *)(intptr_t)(0x10000 + sys.grid) /* block rows */, (void *)(intptr_t)sys.total,
+                               (void *)sys.minvP, (void *)sys.halo_minv});
+        if (int rc = capture_graph(ctx, k, [&] { return field_cg_block(ctx, G, sys); })) return rc;
     }
-    if (int rc = run_blocks(ctx, ctx->fstate, ctx->h_fstate, [&] { return graph ? launch_graph(ctx) : field_cg_block(ctx, G); }))
-        return rc;
+    int first = ctx->tr_first_block; // (the transient pass's, launched one by one: no graph)
+    auto eager = [&] {
+        const int len = first > 0 ? first : G;
+        first = 0;
+        return field_cg_block(ctx, len, sys);
+    };
+    if (int rc = run_blocks(ctx, ctx->fstate, ctx->h_fstate, [&] { return graph ? launch_graph(ctx) : eager(); })) return rc;
     HIPCHK(hipMemcpyAsync(&ctx->h_fstate[2], ctx->fstate.p, sizeof(FusedState), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     take_stats(ctx, ctx->h_fstate[2]);
@@ -2387,7 +2454,8 @@ int cg_solve(mag_ctx *ctx)
     ctx->persist_timed_out = false;
     ctx->exchange_timed_out = false;
     auto cg_dispatch = [&]() {
-        return field_rows ? cg_phase_field(ctx)
+        if (field_rows && !ctx->fc_ready) return fail(ctx, MAG_ERR_STATE, "field_cg: no block-row table (K has not been assembled under this field)");
+        return field_rows ? cg_phase_field(ctx, field_system(ctx))
                : csr_op   ? cg_phase_csr(ctx)
                       : (f32 ? cg_phase_fused32(ctx)
                              : (ctx->persist ? cg_phase_persist(ctx) : (ctx->fused ? cg_phase_fused(ctx) : cg_phase(ctx))));
@@ -2512,6 +2580,7 @@ int mag_upload(mag_ctx *ctx, const mag_problem *p)
     ctx->variants.reset();
     ctx->modal.reset();
     ctx->modal_have = false;
+    ctx->tr_have = false;
     ctx->rf_have = false;
     for (int32_t slot = MAG_SET_RUN; slot <= MAG_SET_VARIANTS; ++slot) drop_derived(ctx, slot);
     return MAG_OK;
@@ -4199,6 +4268,405 @@ int mag_apply_mass(mag_ctx *ctx, double density, int32_t lumped, const double *x
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(y, ctx->modal_y2.p, vb, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
+// ---- transient dynamics (transient.hip): Newmark time stepping of the uploaded part.  The driver owns the buffers, builds the
+// mass and the effective matrix in K's pattern, prepares the solver's copy of it once per system (the a_0 system, then the
+// step's) and enqueues every step on the context's stream: the host reads the CG's convergence polls and nothing else ----
+namespace {
+
+// The solves of the pass run under MAG_STOP_REL with cg_tol, silently, launched one by one (the pass chooses the poll's block
+// length per solve) and without a cost history; the context's options, statistics and the CSR phase's counts are as they were
+// afterwards, on every exit path.
+struct TransientSolves {
+    mag_ctx *ctx;
+    const mag_options opt;
+    const mag_stats stats;
+    const double best_cost;
+    const long long best_iter;
+    const int64_t nf, nz_ff;
+    const int32_t cg_kernel;
+    TransientSolves(mag_ctx *c, double cg_tol)
+        : ctx(c), opt(c->opt), stats(c->stats), best_cost(c->best_cost), best_iter(c->best_iter), nf(c->nf), nz_ff(c->nz_ff), cg_kernel(c->cg_kernel)
+    {
+        ctx->opt.stop_mode = MAG_STOP_REL;
+        ctx->opt.tol = cg_tol;
+        ctx->opt.verbose = 0;
+        ctx->opt.use_graph = 0;
+        ctx->opt.history_len = 0;
+    }
+    ~TransientSolves()
+    {
+        ctx->opt = opt;
+        ctx->stats = stats;
+        ctx->best_cost = best_cost;
+        ctx->best_iter = best_iter;
+        ctx->nf = nf;
+        ctx->nz_ff = nz_ff;
+        ctx->cg_kernel = cg_kernel;
+        ctx->tr_first_block = 0;
+    }
+};
+
+constexpr int kTransientPoll = 8; // launches per poll block behind a solve's first block (even: the parity restarts per block)
+
+inline bool nonneg_finite(double x) { return x >= 0.0 && std::isfinite(x); }
+inline bool pos_finite(double x) { return x > 0.0 && std::isfinite(x); }
+
+// the contexts the pass does not run on, before any HIP call
+int transient_refused(mag_ctx *ctx, const char *fn)
+{
+    if (ctx->comm.nranks > 1)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: transient dynamics run on one GPU: this context has a communicator of %d ranks", fn, ctx->comm.nranks);
+    if (ctx->opt.assemble_csr == 0) return fail(ctx, MAG_ERR_STATE, "%s: needs the assembled K: this context has assemble_csr = 0", fn);
+    if (ctx->opt.precision == 1) return fail(ctx, MAG_ERR_STATE, "%s: not available with precision = 1 (the fp32 leg is matrix-free)", fn);
+    if (ctx->field_on) return field_refuses(ctx, fn);
+    if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "%s before mag_upload", fn);
+    return MAG_OK;
+}
+
+magk::Pattern transient_pattern(const mag_ctx *ctx) { return {ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->N, ctx->nb}; }
+
+// K assembled, and M in its pattern (tr_mval); room for A (tr_aval)
+int transient_matrices(mag_ctx *ctx, double density, int32_t lumped)
+{
+    if (int rc = ensure_csr(ctx)) return rc;
+    HIPCHK(ctx->tr_mval.reserve(8 * (size_t)ctx->nb));
+    HIPCHK(ctx->tr_aval.reserve(32 * (size_t)ctx->nb));
+    magk::mass_pattern(transient_pattern(ctx), ctx->perm.as<uint32_t>(), ctx->inc_off.as<int32_t>(), ctx->inc.as<uint32_t>(),
+                       ctx->conn.as<int32_t>(), ctx->xy.as<double>(), density * ctx->thick, lumped ? 1 : 0, ctx->tr_mval.as<double>(),
+                       ctx->stream);
+    HIPCHK(hipGetLastError());
+    return MAG_OK;
+}
+
+} // namespace
+
+void mag_default_transient_options(mag_transient_options *o)
+{
+    if (!o) return;
+    *o = {};
+    o->beta = 0.25;
+    o->gamma = 0.5;
+}
+
+int mag_assemble_effective(mag_ctx *ctx, double c_K, double c_M, double density, int32_t lumped, double *values_out, int32_t memory)
+{
+    const char *fn = "mag_assemble_effective";
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!values_out) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null values_out", fn);
+    if (!std::isfinite(c_K) || !std::isfinite(c_M)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: c_K %g / c_M %g is not finite", fn, c_K, c_M);
+    if (!pos_finite(density)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: density %g is not positive and finite", fn, density);
+    if (int rc = memory_refused(ctx, memory, fn)) return rc;
+    if (int rc = transient_refused(ctx, fn)) return rc;
+    if (int rc = enter(ctx)) return rc;
+    if (int rc = transient_matrices(ctx, density, lumped)) return rc;
+    hipStream_t s = ctx->stream;
+    magk::effective_values(transient_pattern(ctx), ctx->kval.as<double>(), ctx->tr_mval.as<double>(), c_K, c_M, ctx->tr_aval.as<double>(), s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(values_out, ctx->tr_aval.p, 32 * (size_t)ctx->nb, memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
+int mag_run_transient(mag_ctx *ctx, const mag_transient_options *o)
+{
+    const char *fn = "mag_run_transient";
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null options", fn);
+    if (o->steps < 1) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: steps = %d: at least one step", fn, (int)o->steps);
+    if (!pos_finite(o->dt)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: dt %g is not positive and finite", fn, o->dt);
+    if (!pos_finite(o->density)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: density %g is not positive and finite", fn, o->density);
+    if (!nonneg_finite(o->beta)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: beta %g is negative or not finite", fn, o->beta);
+    if (!nonneg_finite(o->gamma)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: gamma %g is negative or not finite", fn, o->gamma);
+    if (!nonneg_finite(o->rayleigh_mass)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: rayleigh_mass %g is negative or not finite", fn, o->rayleigh_mass);
+    if (!nonneg_finite(o->rayleigh_stiffness))
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: rayleigh_stiffness %g is negative or not finite", fn, o->rayleigh_stiffness);
+    if (!nonneg_finite(o->cg_tol)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: cg_tol %g is negative or not finite", fn, o->cg_tol);
+    if (o->cg < 0 || o->cg > 4) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: cg = %d outside 0..4", fn, (int)o->cg);
+    if (o->snapshot_every < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: snapshot_every = %d is negative", fn, (int)o->snapshot_every);
+    if (o->num_probes < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: num_probes = %d is negative", fn, (int)o->num_probes);
+    if (o->num_probes > 0 && !o->probes) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: num_probes = %d with null probes", fn, (int)o->num_probes);
+    if (int rc = memory_refused(ctx, o->memory, fn)) return rc;
+    if (ctx->comm.nranks > 1)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: transient dynamics run on one GPU: this context has a communicator of %d ranks", fn, ctx->comm.nranks);
+    if (o->resume && (o->u0 || o->v0)) return fail(ctx, MAG_ERR_STATE, "%s: resume starts from the previous run's state: u0 / v0 must be NULL", fn);
+    if (o->resume && !(ctx->have_problem && ctx->tr_have)) return fail(ctx, MAG_ERR_STATE, "%s: resume without a completed run of the pass", fn);
+    if (int rc = transient_refused(ctx, fn)) return rc;
+    if (int rc = enter(ctx)) return rc;
+
+    const bool resume = o->resume != 0, energies = o->energies != 0;
+    const int32_t steps = o->steps, np = o->num_probes, se = o->snapshot_every;
+    const double dt = o->dt, beta = o->beta, gamma = o->gamma, alpha = o->rayleigh_mass, eta = o->rayleigh_stiffness;
+    const double cg_tol = o->cg_tol != 0.0 ? o->cg_tol : 1e-10;
+    const double t_start = resume ? ctx->tr_t1 : 0.0;
+    const double amp_first = ctx->tr_amp_last; // (a resumed run's row 0 carries the load of the state it resumes)
+    ctx->tr_have = false; // (a failure leaves no results of the pass)
+    hipStream_t s = ctx->stream;
+    const hipMemcpyKind in_kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+
+    if (int rc = transient_matrices(ctx, o->density, o->lumped)) return rc;
+    if (int rc = reserve_cg(ctx)) return rc;
+    const int64_t N = ctx->N, n2 = 2 * N;
+    const size_t vb = 16 * (size_t)N;
+    const magk::Pattern pat = transient_pattern(ctx);
+
+    // ---- the checks that need the device: the elements' orientation, the probes
+    HIPCHK(ctx->tr_bad.reserve(16));
+    HIPCHK(ctx->tr_probes.reserve(4 * (size_t)std::max(np, 1)));
+    unsigned long long bad[2] = {~0ull, ~0ull};
+    unsigned long long *d_bad = ctx->tr_bad.as<unsigned long long>();
+    if (np > 0) HIPCHK(hipMemcpyAsync(ctx->tr_probes.p, o->probes, 4 * (size_t)np, in_kind, s));
+    magk::orientation(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), N, ctx->E, d_bad, s);
+    magk::check_probes(ctx->tr_probes.as<int32_t>(), np, n2, d_bad + 1, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(bad, d_bad, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (bad[0] != ~0ull)
+        return fail(ctx, MAG_ERR_BAD_ARGS,
+                    "%s: element %lld has a signed area <= 0 (the stiffness carries the signed area: the pass needs counter-clockwise elements)", fn,
+                    (long long)bad[0]);
+    if (bad[1] != ~0ull)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: probes[%lld] is outside [0, %lld)", fn, (long long)bad[1], (long long)n2);
+
+    // ---- the solver
+    const bool fused = o->cg == 0 ? ctx->use_lds : o->cg <= 3;
+    if (fused && !ctx->use_lds)
+        return fail(ctx, MAG_ERR_STATE, "%s: cg = %d needs the tile-local tables, which this context does not build (op_variant, or a tile beyond the LDS)", fn,
+                    (int)o->cg);
+    const int kind = !fused ? 0 : (o->cg == 0 ? 2 : o->cg - 1);
+
+    // ---- the buffers: the records first, against the memory that is free now
+    const size_t rows = (size_t)steps + 1, snaps = se > 0 ? (size_t)(steps / se) + 1 : 0;
+    const size_t probe_b = 3 * 8 * rows * (size_t)std::max(np, 1), energy_b = 3 * 8 * rows, snap_b = snaps * vb;
+    {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        auto more = [](const DevBuf &b, size_t want) { return want > b.cap ? want + (want >> 4) + 256 : (size_t)0; };
+        const size_t need = more(ctx->tr_probe, probe_b) + more(ctx->tr_energy, energy_b) + more(ctx->tr_snap, snap_b) + more(ctx->tr_amp, 8 * rows);
+        if (need > free_b)
+            return fail(ctx, MAG_ERR_TOO_LARGE, "%s: the records of %d steps need %zu bytes of device memory, %zu are free", fn, (int)steps, need, free_b);
+    }
+    HIPCHK(ctx->tr_probe.reserve(probe_b));
+    HIPCHK(ctx->tr_energy.reserve(energy_b));
+    HIPCHK(ctx->tr_snap.reserve(std::max<size_t>(snap_b, 8)));
+    HIPCHK(ctx->tr_amp.reserve(8 * rows));
+    HIPCHK(ctx->tr_part.reserve(8 * 3 * (size_t)magk::kSensBlocks));
+    for (DevBuf *b : {&ctx->tr_u, &ctx->tr_v, &ctx->tr_a}) {
+        if (resume && b->cap < vb) return fail(ctx, MAG_ERR_STATE, "%s: resume without the state of a completed run", fn);
+        HIPCHK(b->reserve(vb));
+    }
+    for (DevBuf *b : {&ctx->tr_ut, &ctx->tr_vt, &ctx->tr_rhs, &ctx->tr_zero, &ctx->tr_f, &ctx->tr_ku, &ctx->tr_mv}) HIPCHK(b->reserve(vb));
+    HIPCHK(hipMemsetAsync(ctx->tr_zero.p, 0, vb, s));
+
+    // ---- the inputs: amplitude (ones where none is given), u0, v0
+    std::vector<double> ones;
+    double *d_amp = ctx->tr_amp.as<double>();
+    if (o->amplitude) {
+        HIPCHK(hipMemcpyAsync(d_amp, o->amplitude, 8 * rows, in_kind, s));
+    } else {
+        ones.assign(rows, 1.0);
+        HIPCHK(hipMemcpyAsync(d_amp, ones.data(), 8 * rows, hipMemcpyHostToDevice, s));
+    }
+    if (resume) HIPCHK(hipMemcpyAsync(d_amp, &amp_first, 8, hipMemcpyHostToDevice, s));
+    double amp_last = 1.0;
+    HIPCHK(hipMemcpyAsync(&amp_last, d_amp + steps, 8, hipMemcpyDeviceToHost, s));
+    const double *d_u0 = nullptr, *d_v0 = nullptr;
+    if (o->u0 || o->v0) {
+        HIPCHK(ctx->tr_in.reserve(2 * vb));
+        if (o->u0) {
+            HIPCHK(hipMemcpyAsync(ctx->tr_in.p, o->u0, vb, in_kind, s));
+            d_u0 = ctx->tr_in.as<double>();
+        }
+        if (o->v0) {
+            HIPCHK(hipMemcpyAsync(ctx->tr_in.as<char>() + vb, o->v0, vb, in_kind, s));
+            d_v0 = ctx->tr_in.as<double>() + n2;
+        }
+    }
+    HIPCHK(hipStreamSynchronize(s)); // (the host's copies are done with)
+
+    magk::NewmarkState st = {};
+    st.n2 = n2;
+    st.u = ctx->tr_u.as<double>();
+    st.v = ctx->tr_v.as<double>();
+    st.a = ctx->tr_a.as<double>();
+    st.ut = ctx->tr_ut.as<double>();
+    st.vt = ctx->tr_vt.as<double>();
+    st.known = ctx->uknown.as<uint8_t>();
+    st.u_in = ctx->uin.as<double>();
+    st.num_probes = np;
+    st.probes = ctx->tr_probes.as<int32_t>();
+    st.probe_u = ctx->tr_probe.as<double>();
+    st.probe_v = st.probe_u + rows * (size_t)np;
+    st.probe_a = st.probe_v + rows * (size_t)np;
+    double *d_rhs = ctx->tr_rhs.as<double>(), *d_energy = ctx->tr_energy.as<double>(), *d_snap = ctx->tr_snap.as<double>();
+    const double *d_f = ctx->fin.as<double>(), *d_k = ctx->kval.as<double>(), *d_m = ctx->tr_mval.as<double>();
+
+    TransientSolves solves(ctx, cg_tol);
+    const int G0 = solves.opt.check_every;
+    FieldTable tab{ctx->tr_width, ctx->tr_meta, ctx->tr_slot, ctx->tr_src, ctx->tr_val};
+    FieldSystem sys = {};
+    if (fused) {
+        if (int rc = build_field_table(ctx, tab)) return rc;
+        sys = {tab.meta.as<magk::FieldTileMeta>(), tab.slot.as<uint16_t>(), tab.val.as<double2>(), nullptr, nullptr, tab.total,
+               magk::field_cg_grid(ctx->B, ctx->cap, ctx->T, kind != 0)};
+    }
+    // A = c_M M + c_K K and the solver's copy of it: the gathered block rows and the inverse blocks, or the reduced system
+    auto system = [&](double c_M, double c_K) -> int {
+        magk::effective_values(pat, d_k, d_m, c_K, c_M, ctx->tr_aval.as<double>(), s);
+        HIPCHK(hipGetLastError());
+        if (!fused) return build_reduced(ctx, true, ctx->tr_aval.as<double>(), false);
+        if (int rc = field_values(ctx, tab, ctx->tr_aval.as<double>(), kind, ctx->tr_minv, ctx->tr_hminv)) return rc;
+        sys.minvP = kind ? ctx->tr_minv.as<float4>() : nullptr;
+        sys.halo_minv = kind ? ctx->tr_hminv.as<float4>() : nullptr;
+        return MAG_OK;
+    };
+    // A_FF a = rhs_F from zero, a_P = 0.  The poll's first block: the previous solve's iteration count + 2 (a launch judges the
+    // iterate of the one before), rounded up to even -- the context's check_every for the first solve --, then blocks of
+    // kTransientPoll.  Launches behind convergence are no-ops: the results do not depend on it.
+    std::vector<int32_t> iterations(rows, 0);
+    long long all_iterations = 0, most = 0, prev = -1;
+    bool all_converged = true;
+    auto solve = [&](int32_t row) -> int {
+        long long G = prev < 0 ? G0 : std::min<long long>(prev + 2, 4096);
+        G += G & 1;
+        ctx->tr_first_block = (int32_t)std::max<long long>(G, 2);
+        ctx->opt.check_every = kTransientPoll;
+        if (fused) {
+            magk::to_hilbert(d_rhs, ctx->iperm.as<int32_t>(), st.known, 0, N, ctx->bP.as<double>(), s);
+            if (int rc = cg_phase_field(ctx, sys)) return rc;
+            magk::scatter_back(ctx->x.as<double>(), ctx->perm.as<uint32_t>(), st.known, ctx->tr_zero.as<double>(), N, st.a, s);
+        } else {
+            magk::compact_free(d_rhs, ctx->fidx.as<int32_t>(), st.known, n2, ctx->b_ff.as<double>(), s);
+            if (int rc = cg_phase_csr(ctx, true, ctx->tr_zero.as<double>(), st.a)) return rc;
+        }
+        HIPCHK(hipGetLastError());
+        const mag_stats &cs = ctx->stats;
+        if (cs.breakdown)
+            return fail(ctx, MAG_ERR_NOT_CONVERGED, "%s: step %d: the solve broke down (non-finite residual after %lld iterations)", fn, (int)row,
+                        (long long)cs.iterations);
+        iterations[(size_t)row] = (int32_t)cs.iterations;
+        all_iterations += cs.iterations;
+        most = std::max<long long>(most, cs.iterations);
+        all_converged = all_converged && cs.converged != 0;
+        prev = cs.iterations;
+        return MAG_OK;
+    };
+    auto record_energies = [&](int64_t row) -> int {
+        magk::PatternApply e = {};
+        e.kval = d_k, e.mval = d_m, e.xa = st.u, e.ca = 1.0, e.xc = st.v, e.cc = 1.0, e.y = d_rhs;
+        e.ku = ctx->tr_ku.as<double>(), e.mv = ctx->tr_mv.as<double>();
+        magk::pattern_apply(pat, e, s);
+        magk::newmark_energies(st, e.ku, e.mv, d_f, d_amp, row, ctx->tr_part.as<double>(), d_energy + 3 * row, s);
+        HIPCHK(hipGetLastError());
+        return MAG_OK;
+    };
+
+    // ---- the start
+    if (!resume) {
+        magk::newmark_start(st, d_u0, d_v0, s);
+        if (int rc = system(1.0, 0.0)) return rc;
+        magk::PatternApply r = {};
+        r.kval = d_k, r.mval = d_m, r.xa = st.u, r.ca = 1.0, r.xb = eta != 0.0 ? st.v : nullptr, r.cb = eta;
+        r.xc = alpha != 0.0 ? st.v : nullptr, r.cc = alpha;
+        r.kind = 1, r.known = st.known, r.f = d_f, r.amplitude = d_amp, r.amp_at = 0, r.y = d_rhs;
+        magk::pattern_apply(pat, r, s);
+        if (int rc = solve(0)) return rc;
+    }
+    magk::newmark_record(st, 0, se > 0 ? d_snap : nullptr, s);
+    if (energies)
+        if (int rc = record_energies(0)) return rc;
+    if (int rc = system(1.0 + gamma * dt * alpha, beta * dt * dt + gamma * dt * eta)) return rc;
+
+    // ---- the steps
+    for (int32_t n = 0; n < steps; ++n) {
+        magk::newmark_predict(st, dt, beta, gamma, s);
+        magk::PatternApply r = {};
+        r.kval = d_k, r.mval = d_m, r.xa = st.ut, r.ca = 1.0, r.xb = eta != 0.0 ? st.vt : nullptr, r.cb = eta;
+        r.xc = alpha != 0.0 ? st.vt : nullptr, r.cc = alpha;
+        r.kind = 1, r.known = st.known, r.f = d_f, r.amplitude = d_amp, r.amp_at = n + 1, r.y = d_rhs;
+        magk::pattern_apply(pat, r, s);
+        if (int rc = solve(n + 1)) return rc;
+        const bool snap = se > 0 && (n + 1) % se == 0;
+        magk::newmark_correct(st, dt, beta, gamma, n + 1, snap ? d_snap + (size_t)((n + 1) / se) * (size_t)n2 : nullptr, s);
+        if (energies)
+            if (int rc = record_energies(n + 1)) return rc;
+    }
+
+    // ---- the reactions of the final state
+    {
+        magk::PatternApply r = {};
+        r.kval = d_k, r.mval = d_m, r.xa = st.u, r.ca = 1.0, r.xb = eta != 0.0 ? st.v : nullptr, r.cb = eta;
+        r.xc = st.a, r.cc = 1.0, r.xd = alpha != 0.0 ? st.v : nullptr, r.cd = alpha;
+        r.kind = 2, r.known = st.known, r.f = d_f, r.amplitude = d_amp, r.amp_at = steps, r.y = ctx->tr_f.as<double>();
+        magk::pattern_apply(pat, r, s);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+
+    int32_t *info = ctx->tr_info;
+    info[0] = steps;
+    info[1] = fused ? 5 : 3;
+    info[2] = kind;
+    info[3] = (int32_t)std::min<long long>(all_iterations, INT32_MAX);
+    info[4] = (int32_t)most;
+    info[5] = (int32_t)snaps;
+    info[6] = resume ? 1 : 0;
+    info[7] = all_converged ? 1 : 0;
+    ctx->tr_steps = steps;
+    ctx->tr_num_probes = np;
+    ctx->tr_snaps = (int32_t)snaps;
+    ctx->tr_energies = energies;
+    ctx->tr_t0 = t_start;
+    ctx->tr_t1 = t_start + (double)steps * dt;
+    ctx->tr_amp_last = amp_last;
+    ctx->tr_iterations = iterations;
+    ctx->tr_have = true;
+    if (!all_converged) ctx->err = std::string(fn) + ": a solve stopped at the iteration cap above the tolerance: its last iterate was used";
+    return MAG_OK;
+}
+
+int mag_download_transient(mag_ctx *ctx, mag_transient_result *o)
+{
+    const char *fn = "mag_download_transient";
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null result", fn);
+    if (int rc = memory_refused(ctx, o->memory, fn)) return rc;
+    if (ctx->comm.nranks > 1)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: transient dynamics run on one GPU: this context has a communicator of %d ranks", fn, ctx->comm.nranks);
+    if (!ctx->have_problem || !ctx->tr_have) return fail(ctx, MAG_ERR_STATE, "%s before a completed mag_run_transient", fn);
+    if (o->probe_u || o->probe_v || o->probe_a)
+        if (ctx->tr_num_probes == 0) return fail(ctx, MAG_ERR_STATE, "%s: the run recorded no probes", fn);
+    if (o->energies && !ctx->tr_energies) return fail(ctx, MAG_ERR_STATE, "%s: the run recorded no energies", fn);
+    if (o->snapshots && ctx->tr_snaps == 0) return fail(ctx, MAG_ERR_STATE, "%s: the run kept no snapshots", fn);
+    if (int rc = enter(ctx)) return rc;
+    const hipMemcpyKind kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const hipMemcpyKind hkind = o->memory == MAG_MEM_DEVICE ? hipMemcpyHostToDevice : hipMemcpyHostToHost;
+    hipStream_t s = ctx->stream;
+    const size_t vb = 16 * (size_t)ctx->N, rows = (size_t)ctx->tr_steps + 1, pb = 8 * rows * (size_t)ctx->tr_num_probes;
+    if (o->u_out) HIPCHK(hipMemcpyAsync(o->u_out, ctx->tr_u.p, vb, kind, s));
+    if (o->v_out) HIPCHK(hipMemcpyAsync(o->v_out, ctx->tr_v.p, vb, kind, s));
+    if (o->a_out) HIPCHK(hipMemcpyAsync(o->a_out, ctx->tr_a.p, vb, kind, s));
+    if (o->f_out) HIPCHK(hipMemcpyAsync(o->f_out, ctx->tr_f.p, vb, kind, s));
+    if (o->probe_u) HIPCHK(hipMemcpyAsync(o->probe_u, ctx->tr_probe.p, pb, kind, s));
+    if (o->probe_v) HIPCHK(hipMemcpyAsync(o->probe_v, ctx->tr_probe.as<char>() + pb, pb, kind, s));
+    if (o->probe_a) HIPCHK(hipMemcpyAsync(o->probe_a, ctx->tr_probe.as<char>() + 2 * pb, pb, kind, s));
+    if (o->energies) HIPCHK(hipMemcpyAsync(o->energies, ctx->tr_energy.p, 3 * 8 * rows, kind, s));
+    if (o->snapshots) HIPCHK(hipMemcpyAsync(o->snapshots, ctx->tr_snap.p, (size_t)ctx->tr_snaps * vb, kind, s));
+    if (o->iterations) HIPCHK(hipMemcpyAsync(o->iterations, ctx->tr_iterations.data(), 4 * rows, hkind, s));
+    HIPCHK(hipStreamSynchronize(s));
+    o->scalars[0] = ctx->tr_t0;
+    o->scalars[1] = ctx->tr_t1;
+    o->scalars[2] = o->scalars[3] = 0.0;
+    return MAG_OK;
+}
+
+int mag_get_transient_info(const mag_ctx *ctx, int32_t info[8])
+{
+    if (!ctx || !info || ctx->comm.nranks > 1) return MAG_ERR_BAD_ARGS;
+    if (!ctx->have_problem || !ctx->tr_have) return MAG_ERR_STATE;
+    for (int k = 0; k < 8; ++k) info[k] = ctx->tr_info[k];
     return MAG_OK;
 }
 

@@ -715,6 +715,98 @@ class Context:
                                            1 if masked else 0))
         return y
 
+    # -- transient dynamics: Newmark time stepping of the uploaded part ----------------------------------
+    TRANSIENT_INFO = ("steps", "cg_kernel", "preconditioner", "cg_iterations", "max_step_iterations", "snapshots_kept", "resumed", "converged")
+
+    def run_transient(self, steps, dt, density=None, beta=0.25, gamma=0.5, rayleigh=(0.0, 0.0), amplitude=None, u0=None, v0=None,
+                      probes=(), energies=False, snapshot_every=0, cg=0, cg_tol=0.0, lumped=False, resume=False):
+        """mag_run_transient on the uploaded problem (no run needed): `steps` steps of Newmark's method (include/magnetite_hip.h)."""
+        if density is None:
+            raise MagnetiteError("Solver", "transient: a density is needed (the model has none)")
+        o = _lib.TransientOptions()
+        self._L.mag_default_transient_options(C.byref(o))
+        keep = []  # (the arrays the options point to, until the call returns)
+
+        def vec(x, n, dtype=np.float64):
+            if x is None:
+                return None
+            a = np.ascontiguousarray(x, dtype=dtype).reshape(-1)
+            if a.size != n:
+                raise MagnetiteError("Solver", f"transient: an array of {a.size} entries where {n} are expected")
+            keep.append(a)
+            return a.ctypes.data
+
+        probes = np.ascontiguousarray(probes, dtype=np.int32).reshape(-1)
+        o.steps, o.resume, o.lumped, o.cg = int(steps), 1 if resume else 0, 1 if lumped else 0, int(cg)
+        o.energies, o.snapshot_every, o.num_probes, o.memory = 1 if energies else 0, int(snapshot_every), int(probes.size), MAG_MEM_HOST
+        o.dt, o.beta, o.gamma, o.density = float(dt), float(beta), float(gamma), float(density)
+        o.rayleigh_mass, o.rayleigh_stiffness, o.cg_tol = float(rayleigh[0]), float(rayleigh[1]), float(cg_tol)
+        o.amplitude = vec(amplitude, max(int(steps), 0) + 1)
+        o.u0, o.v0 = vec(u0, 2 * self.N), vec(v0, 2 * self.N)
+        o.probes = probes.ctypes.data if probes.size else None
+        rc = self._check(self._L.mag_run_transient(self._h, C.byref(o)))
+        self._transient_probes, self._transient_energies = int(probes.size), bool(energies)  # (what download_transient sizes)
+        return rc
+
+    def transient_info(self):
+        """The words of mag_get_transient_info by name (TRANSIENT_INFO)."""
+        info = (C.c_int32 * 8)()
+        self._check(self._L.mag_get_transient_info(self._h, info))
+        return dict(zip(self.TRANSIENT_INFO, (int(v) for v in info)))
+
+    def download_transient(self, num_probes=None, energies=None):
+        """dict(u, v, a, f (2N: the final state and its reactions), iterations (steps + 1), t_start, t_end, and what the run
+        recorded: probe_u / probe_v / probe_a (steps + 1, probes), energies (steps + 1, 3 = T, W, P), snapshots (rows, 2N))."""
+        info = self.transient_info()
+        rows, n2 = info["steps"] + 1, 2 * self.N
+        num_probes = self._transient_probes if num_probes is None else num_probes
+        energies = self._transient_energies if energies is None else energies
+        out = {k: np.empty(n2) for k in ("u", "v", "a", "f")}
+        out["iterations"] = np.empty(rows, dtype=np.int32)
+        if num_probes:
+            for k in ("probe_u", "probe_v", "probe_a"):
+                out[k] = np.empty((rows, num_probes))
+        if energies:
+            out["energies"] = np.empty((rows, 3))
+        if info["snapshots_kept"]:
+            out["snapshots"] = np.empty((info["snapshots_kept"], n2))
+        o = _lib.TransientResult()
+        o.u_out, o.v_out, o.a_out, o.f_out = (out[k].ctypes.data for k in ("u", "v", "a", "f"))
+        o.iterations = out["iterations"].ctypes.data
+        for k in ("probe_u", "probe_v", "probe_a", "energies", "snapshots"):
+            if k in out:
+                setattr(o, k, out[k].ctypes.data)
+        o.memory = MAG_MEM_HOST
+        self._check(self._L.mag_download_transient(self._h, C.byref(o)))
+        out["t_start"], out["t_end"] = float(o.scalars[0]), float(o.scalars[1])
+        return out
+
+    _transient_probes = 0
+    _transient_energies = False
+
+    def transient(self, prob=None, steps=None, dt=None, density=None, beta=0.25, gamma=0.5, rayleigh=(0.0, 0.0), amplitude=None,
+                  u0=None, v0=None, probes=(), energies=False, snapshot_every=0, cg=0, cg_tol=0.0, lumped=False, resume=False):
+        """The response of prob (uploaded when given; otherwise of what is uploaded) over `steps` steps of dt: the arrays of
+        download_transient() and the words of transient_info() by name."""
+        if prob is not None:
+            self.upload_problem(prob)
+        if steps is None or dt is None:
+            raise MagnetiteError("Solver", "transient: steps and dt are needed")
+        self.run_transient(steps, dt, density, beta, gamma, rayleigh, amplitude, u0, v0, probes, energies, snapshot_every, cg, cg_tol,
+                           lumped, resume)
+        out = self.download_transient()
+        out.update(self.transient_info())
+        return out
+
+    def assemble_effective(self, c_K, c_M, density, lumped=False):
+        """The values of c_K K + c_M M in the layout of assemble_csr() (mag_assemble_effective)."""
+        nnz = C.c_int64(0)
+        self._check(self._L.mag_assemble_csr(self._h, C.byref(nnz), None, None, None))
+        val = np.empty(nnz.value)
+        self._check(self._L.mag_assemble_effective(self._h, float(c_K), float(c_M), float(density), 1 if lumped else 0,
+                                                   _p(val, C.c_double), MAG_MEM_HOST))
+        return val
+
     # -- pieces, for parity tests ----------------------------------------------
     def element_stiffness(self):
         ke = np.empty(36 * self.E)

@@ -8,10 +8,14 @@
 //   * nodes.csv/elements.csv post_processor.rs:18-83, floats as Rust's `{}` prints them
 // Usage: magnetite_gpu <input.json> <mesh.msh> [--nodes nodes.csv] [--elements elements.csv] [--dry-run] [--rel TOL]
 //                      [--stress-recovery] [--modal P --density RHO] [--adapt R [--refine-fraction T] [--refine-split 1|3]]
+//                      [--transient STEPS --dt DT --density RHO [--rayleigh A,E] [--probe DOF]...]
 //   --dry-run  stop before the solver and print what was parsed (no GPU needed)
 //   --rel TOL  stop CG on relative residual TOL instead of the reference's absolute 1e-4
 //   --modal P --density RHO  also print "info: mode k frequency F Hz residual R" for the P lowest modes and write modes.csv
 //              (id,ux1,uy1,...,uxP,uyP) next to nodes.csv -- solver::modal; the input JSON has no density, hence the flag
+//   --transient STEPS --dt DT --density RHO  also run STEPS steps of Newmark's method from rest under the loads applied at t = 0
+//              (solver::transient; --rayleigh A,E: C = A M + E K), print "info: step n t T iterations I" per step and write
+//              history.csv (step,t, then u,v,a per --probe DOF, DOF = 2 * node + axis) next to nodes.csv
 //   --stress-recovery  also write nodes_stress.csv (id,sx,sy,txy,vm) and elements_stress.csv (id,sx,sy,txy,vm,eta2) next to the
 //              two files -- solver::stress_recovery: the tensor per element, the nodal field, the ZZ error indicator -- and
 //              print eta_rel; without it nothing changes
@@ -382,6 +386,33 @@ void modes_output(const Modes &m, size_t num_nodes, const std::string &path)
     std::printf("info: wrote mode shapes to %s\n", path.c_str());
 }
 
+// "dir/nodes.csv" -> "dir/history.csv"
+std::string history_name(const std::string &nodes_output)
+{
+    const size_t slash = nodes_output.find_last_of('/');
+    return (slash == std::string::npos ? std::string() : nodes_output.substr(0, slash + 1)) + "history.csv";
+}
+
+// the probes' rows of solver::transient, a row per step, floats as csv_output prints them
+void history_output(const Transient &tr, const std::vector<std::int32_t> &probes, double dt, const std::string &path)
+{
+    std::FILE *hf = std::fopen(path.c_str(), "w");
+    if (!hf) die({MagnetiteError::Solver, "Failed to create history.csv: " + path});
+    std::fputs("step,t", hf);
+    for (std::int32_t d : probes) std::fprintf(hf, ",u%d,v%d,a%d", (int)d, (int)d, (int)d);
+    std::fputs("\n", hf);
+    const size_t P = probes.size();
+    for (size_t n = 0; n < tr.iterations.size(); ++n) {
+        std::fprintf(hf, "%zu,%s", n, rust_display((double)n * dt).c_str());
+        for (size_t k = 0; k < P; ++k)
+            std::fprintf(hf, ",%s,%s,%s", rust_display(tr.probe_u[n * P + k]).c_str(), rust_display(tr.probe_v[n * P + k]).c_str(),
+                         rust_display(tr.probe_a[n * P + k]).c_str());
+        std::fputs("\n", hf);
+    }
+    std::fclose(hf);
+    std::printf("info: wrote the probes' history to %s\n", path.c_str());
+}
+
 // "dir/elements.csv" -> "dir/density.csv"
 std::string density_name(const std::string &elements_output)
 {
@@ -408,14 +439,26 @@ int main(int argc, char **argv)
 {
     std::string input, mesh, nodes_out = "nodes.csv", elements_out = "elements.csv";
     bool dry = false, recover = false;
-    int modal_modes = 0, adapt = 0, refine_split = 1, topopt = 0, penal = 3, filter_passes = 1, field_cg = 0;
-    double rel = 0.0, density = 0.0, refine_fraction = 0.2, volume_fraction = 0.5;
+    int modal_modes = 0, adapt = 0, refine_split = 1, topopt = 0, penal = 3, filter_passes = 1, field_cg = 0, transient_steps = 0;
+    double rel = 0.0, density = 0.0, refine_fraction = 0.2, volume_fraction = 0.5, dt = 0.0, rayleigh_mass = 0.0, rayleigh_stiffness = 0.0;
+    bool transient = false;
+    std::vector<std::int32_t> probes;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--dry-run") dry = true;
         else if (a == "--stress-recovery") recover = true;
         else if (a == "--modal" && i + 1 < argc) modal_modes = std::atoi(argv[++i]);
         else if (a == "--density" && i + 1 < argc) density = std::atof(argv[++i]);
+        else if (a == "--transient" && i + 1 < argc) transient = true, transient_steps = std::atoi(argv[++i]);
+        else if (a == "--dt" && i + 1 < argc) dt = std::atof(argv[++i]);
+        else if (a == "--probe" && i + 1 < argc) probes.push_back((std::int32_t)std::atoi(argv[++i]));
+        else if (a == "--rayleigh" && i + 1 < argc) {
+            const std::string pair = argv[++i];
+            const size_t comma = pair.find(',');
+            if (comma == std::string::npos) die({MagnetiteError::Input, "--rayleigh A,E needs two values"});
+            rayleigh_mass = std::atof(pair.substr(0, comma).c_str());
+            rayleigh_stiffness = std::atof(pair.substr(comma + 1).c_str());
+        }
         else if (a == "--adapt" && i + 1 < argc) adapt = std::atoi(argv[++i]);
         else if (a == "--refine-fraction" && i + 1 < argc) refine_fraction = std::atof(argv[++i]);
         else if (a == "--refine-split" && i + 1 < argc) refine_split = std::atoi(argv[++i]);
@@ -432,16 +475,21 @@ int main(int argc, char **argv)
         else die({MagnetiteError::Input, "Unrecognized argument " + a});
     }
     if (input.empty() || mesh.empty()) {
-        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery] [--modal P --density RHO] [--adapt R [--refine-fraction T] [--refine-split 1|3]] [--topopt ITERS [--volume-fraction F] [--penal P] [--filter-passes K] [--field-cg 0..3]]\n");
+        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery] [--modal P --density RHO] [--transient STEPS --dt DT --density RHO [--rayleigh A,E] [--probe DOF]...] [--adapt R [--refine-fraction T] [--refine-split 1|3]] [--topopt ITERS [--volume-fraction F] [--penal P] [--filter-passes K] [--field-cg 0..3]]\n");
         return 2;
     }
     if (modal_modes < 0 || (modal_modes > 0 && !(density > 0.0))) die({MagnetiteError::Input, "--modal P needs P >= 1 and --density RHO > 0"});
+    if (transient && (transient_steps < 1 || !(dt > 0.0) || !(density > 0.0) || rayleigh_mass < 0.0 || rayleigh_stiffness < 0.0))
+        die({MagnetiteError::Input, "--transient STEPS needs STEPS >= 1, --dt DT > 0, --density RHO > 0 and --rayleigh A,E >= 0"});
+    if (!transient && (dt != 0.0 || !probes.empty() || rayleigh_mass != 0.0 || rayleigh_stiffness != 0.0))
+        die({MagnetiteError::Input, "--dt, --rayleigh and --probe need --transient STEPS"});
     if (adapt < 0 || !(refine_fraction > 0.0 && refine_fraction <= 1.0) || (refine_split != 1 && refine_split != 3))
         die({MagnetiteError::Input, "--adapt R needs R >= 0, --refine-fraction T in (0, 1] and --refine-split 1 or 3"});
     if (topopt < 0 || !(volume_fraction > 0.0 && volume_fraction <= 1.0) || penal < 1 || penal > 8 || filter_passes < 0 || filter_passes > 8)
         die({MagnetiteError::Input, "--topopt ITERS needs ITERS >= 0, --volume-fraction F in (0, 1], --penal 1..8 and --filter-passes 0..8"});
     if (field_cg < 0 || field_cg > 3 || (field_cg != 0 && topopt == 0))
         die({MagnetiteError::Input, "--field-cg K needs K in 0..3 (0 CSR phase, 1 plain, 2 Jacobi, 3 block-Jacobi on K's block rows) and --topopt"});
+    if (transient && adapt > 0) die({MagnetiteError::Input, "--transient steps the mesh as given: not together with --adapt"});
     if (topopt > 0 && adapt > 0) die({MagnetiteError::Input, "--topopt designs on the mesh as given: not together with --adapt"});
     // mesher::run (mesher.rs:939-974) minus geometry parsing and the gmsh subprocess
     const std::string text = slurp(input, MagnetiteError::Input, "Unable to open input file " + input);
@@ -474,6 +522,9 @@ int main(int argc, char **argv)
                     rust_display(meta.youngs_modulus).c_str(), rust_display(meta.poisson_ratio).c_str(),
                     rust_display(meta.part_thickness).c_str(), elements.empty() ? 0 : elements[0].nodes[0],
                     elements.empty() ? 0 : elements[0].nodes[1], elements.empty() ? 0 : elements[0].nodes[2]);
+        if (transient)
+            std::printf("dry-run: transient steps %d dt %s density %s rayleigh %s,%s probes %zu\n", transient_steps, rust_display(dt).c_str(),
+                        rust_display(density).c_str(), rust_display(rayleigh_mass).c_str(), rust_display(rayleigh_stiffness).c_str(), probes.size());
         return 0;
     }
     // solver::run (main.rs:64)
@@ -484,7 +535,7 @@ int main(int argc, char **argv)
         opt.stop_mode = MAG_STOP_REL;
         opt.tol = rel;
     }
-    std::vector<Node> posed = recover || modal_modes > 0 || topopt > 0 ? nodes : std::vector<Node>();  // (run() fills every value in)
+    std::vector<Node> posed = recover || modal_modes > 0 || topopt > 0 || transient ? nodes : std::vector<Node>();  // (run() fills every value in)
     if (adapt > 0) {
         RefineSpec spec;
         spec.theta = refine_fraction;
@@ -524,6 +575,25 @@ int main(int argc, char **argv)
             std::printf("info: mode %zu frequency %s Hz residual %s\n", k + 1, rust_display(modes.frequency[k]).c_str(),
                         rust_display(modes.residual[k]).c_str());
         modes_output(modes, posed.size(), modes_name(nodes_out));
+    }
+    if (transient) {
+        // The pass needs every element counter-clockwise, as the modal analysis does: the elements go in by their true sign.
+        std::vector<Element> ccw = elements;
+        for (Element &e : ccw)
+            if (solver::compute_element_area(e, posed) < 0.0) std::swap(e.nodes[0], e.nodes[2]);
+        opt.verbose = 0;
+        TransientSpec spec;
+        spec.steps = transient_steps;
+        spec.dt = dt;
+        spec.density = density;
+        spec.rayleigh_mass = rayleigh_mass;
+        spec.rayleigh_stiffness = rayleigh_stiffness;
+        spec.probes = probes;
+        Transient tr;
+        if (Result err = solver::transient(posed, ccw, meta, spec, tr, &opt)) die(*err);
+        for (size_t n = 0; n < tr.iterations.size(); ++n)
+            std::printf("info: step %zu t %s iterations %d\n", n, rust_display((double)n * dt).c_str(), (int)tr.iterations[n]);
+        history_output(tr, probes, dt, history_name(nodes_out));
     }
     if (topopt > 0) {
         // The density design needs every element counter-clockwise, as the modal analysis does: the elements go in by their true sign.
