@@ -157,11 +157,11 @@ class Leg:
         a = np.ascontiguousarray(a, dtype=dtype)
         return self.arena.put(a, self.offset) if self.device else HostBuffer(a)
 
-    def _out(self, shape, dtype=np.float64):
+    def _out(self, shape, dtype=np.float64, offset=None):
         if shape is None:
             return None
         if self.device:
-            return self.arena.empty(shape, dtype, self.offset)
+            return self.arena.empty(shape, dtype, self.offset if offset is None else offset)
         n = int(np.prod(shape)) * np.dtype(dtype).itemsize
         return HostBuffer(np.full(n, UNWRITTEN[MAG_MEM_HOST], dtype=np.uint8).view(dtype).reshape(shape))
 
@@ -307,6 +307,66 @@ class Leg:
         outs = [self._out(p), self._out(p), self._out(p), self._out((p, 2 * self.ctx.N))]
         self._ok(self.L.mag_download_modal(self.h, C.byref(_lib.ModalResult(*[b.ptr for b in outs], self.memory, 0))))
         return dict(zip(("lambda", "frequency", "residual", "shapes"), self._called(outputs=outs)))
+
+    # -- transient dynamics
+    TRANSIENT = (("u", "u_out"), ("v", "v_out"), ("a", "a_out"), ("f", "f_out"), ("probe_u", "probe_u"), ("probe_v", "probe_v"),
+                 ("probe_a", "probe_a"), ("energies", "energies"), ("snapshots", "snapshots"), ("iterations", "iterations"))
+
+    def run_transient(self, steps, dt, density, amplitude=None, u0=None, v0=None, probes=None, scribble=True, **options):
+        """amplitude, u0, v0 and the int32 probes in `memory` (the probes on a 4-byte boundary that is no 8-byte one where the
+        doubles lie at an offset); `options`: the other fields of mag_transient_options by name.  The inputs stay allocated,
+        scribbled over: a resumed run that read them again would step with NaNs, and every later check() sees them as 0xFF."""
+        ins = [self._in(amplitude), self._in(u0), self._in(v0)]
+        p = None
+        if probes is not None:
+            p = np.ascontiguousarray(probes, dtype=np.int32)
+            p = self.arena.put(p, 4 if self.offset else 0) if self.device else HostBuffer(p)
+        o = _lib.TransientOptions()
+        self.L.mag_default_transient_options(C.byref(o))
+        o.steps, o.dt, o.density, o.memory = int(steps), float(dt), float(density), self.memory
+        o.amplitude, o.u0, o.v0, o.probes = (self._ptr(b) for b in ins + [p])
+        o.num_probes = 0 if probes is None else len(probes)
+        for k, v in options.items():
+            assert hasattr(o, k), k
+            setattr(o, k, v)
+        rc = self.L.mag_run_transient(self.h, C.byref(o))
+        self._called(ins + [p], scribble=scribble, keep=True)
+        self._transient = (o.num_probes, bool(o.energies))  # (what download_transient sizes)
+        return rc
+
+    def download_transient(self, want=None, slack=3):
+        """Every array of the result struct (`want` names the members asked for, the others are passed as NULL), iterations as
+        int32, t_start and t_end.  Every buffer has room for `slack` entries more than the header documents: they must come
+        back UNWRITTEN."""
+        info = self.ctx.transient_info()
+        rows, n2, (num_probes, energies) = info["steps"] + 1, 2 * self.ctx.N, self._transient
+        shapes = dict(u=(n2,), v=(n2,), a=(n2,), f=(n2,), probe_u=(rows, num_probes), probe_v=(rows, num_probes), probe_a=(rows, num_probes),
+                      energies=(rows, 3), snapshots=(info["snapshots_kept"], n2), iterations=(rows,))
+        want = tuple(k for k, _ in self.TRANSIENT if int(np.prod(shapes[k])) > 0 and (energies or k != "energies")) if want is None else want
+        outs = {k: self._out(int(np.prod(shapes[k])) + slack if k in want else None) for k, _ in self.TRANSIENT if k != "iterations"}
+        # (the int32 buffer on a 4-byte boundary, like the probes)
+        outs["iterations"] = self._out(rows + slack if "iterations" in want else None, np.int32, 4 if self.offset else 0)
+        o = _lib.TransientResult(memory=self.memory, scalars=(C.c_double * 4)(*([np.nan] * 4)))
+        for k, member in self.TRANSIENT:
+            setattr(o, member, self._ptr(outs[k]))
+        self._ok(self.L.mag_download_transient(self.h, C.byref(o)))
+        got = self._called(outputs=list(outs.values()))
+        out = {}
+        for k, flat in zip([k for k, _ in self.TRANSIENT if k in want], got):
+            n = int(np.prod(shapes[k]))
+            assert (flat[n:].view(np.uint8) == UNWRITTEN[self.memory]).all(), ("written beyond its documented size", k)
+            out[k] = flat[:n].reshape(shapes[k])
+        out["t_start"], out["t_end"] = float(o.scalars[0]), float(o.scalars[1])
+        return out
+
+    def assemble_effective(self, c_K, c_M, density, lumped=False, slack=3):
+        """c_K K + c_M M in the layout of assemble_csr(), into `memory`; `slack` entries behind it stay UNWRITTEN"""
+        n = self.ctx.assemble_csr()[2].size
+        out = self._out(n + slack)
+        self._ok(self.L.mag_assemble_effective(self.h, float(c_K), float(c_M), float(density), 1 if lumped else 0, _dp(out.ptr), self.memory))
+        flat, = self._called(outputs=[out])
+        assert (flat[n:].view(np.uint8) == UNWRITTEN[self.memory]).all(), "written beyond its documented size"
+        return flat[:n]
 
     # -- the element stiffness field and the design
     def set_element_scale(self, scale):

@@ -10,11 +10,14 @@ import numpy as np
 import pytest
 
 import design_ref as dref
+import modal_ref
 import refine_ref
+import transient_ref
 from device_buffers import UNWRITTEN, DeviceArena, Leg
 from load_cases_util import make_cases
 from magnetite_amd import Context
 from magnetite_amd._lib import MAG_ERR_BAD_ARGS, MAG_MEM_DEVICE, MAG_MEM_HOST, MAG_OK
+from magnetite_amd.solver import MagnetiteError
 from test_load_cases_gpu import MESHES
 from variants_util import make_variants
 
@@ -448,3 +451,67 @@ def test_a_bad_indicator_on_the_device_is_refused_with_the_offender_and_its_valu
         twin = refine_ref.of_problem(prob, indicator=ind, rule="top_fraction", theta=0.2)
         for k in REFINED:
             assert got[k].tobytes() == twin[k].tobytes(), k
+
+
+# ---- transient dynamics ------------------------------------------------------------------------------------------------------------
+def test_the_transient_pass_reads_and_writes_device_memory(built):
+    """mag_run_transient (amplitude, u0, v0, probes), mag_download_transient (nine arrays and the int32 iterations, which come from
+    the host) and mag_assemble_effective: the doubles on an 8-byte boundary that is no 16-byte one, the int32 arrays on a 4-byte
+    boundary that is no 8-byte one"""
+    import test_transient_gpu as tg
+    from test_transient_paths_gpu import some_probes
+    prob, K, M, free, w1, T1 = tg.setup("plate16", "load")
+    n2 = 2 * prob.mesh.num_nodes
+    beta, gamma, alpha, eta = tg.parameters("damped", w1)
+    dt = T1 / 200.0
+    u0, v0 = transient_ref.moving_start(K, M, free, prob.u_in, prob.f_in, modal_ref.eigenpairs(K, M, free, 4)[1], alpha, eta)
+    amp = tg.amplitude_of("load", dt, T1, 15)
+    resumed_amp = amp[10:].copy()
+    resumed_amp[0] = np.nan  # (ignored)
+    probes = some_probes(prob)
+    assert len(probes) == 300 and probes.max() == n2 - 1
+    opts = dict(beta=beta, gamma=gamma, rayleigh_mass=alpha, rayleigh_stiffness=eta, energies=1, snapshot_every=3, cg_tol=tg.CG_TOL)
+    with two_legs(offset=8) as legs:
+        def run(leg):
+            c = leg.ctx
+            c.upload_problem(prob)
+            out = {}
+            assert leg.run_transient(10, dt, RHO, amp[:11], u0, v0, probes, **opts) == MAG_OK, leg.error()
+            out["first"] = written(leg.download_transient(), "first")
+            out["first, three members"] = leg.download_transient(want=("v", "probe_a", "iterations"))
+            out["first, to the host"] = c.download_transient(num_probes=len(probes), energies=True)
+            assert leg.run_transient(5, dt, RHO, resumed_amp, probes=probes[:7], resume=1, **opts) == MAG_OK, leg.error()
+            out["resumed"] = written(leg.download_transient(), "resumed")
+            out["effective"] = written(dict(values=leg.assemble_effective(0.37, 2.5e4, RHO)), "effective")
+            out["resumed, afterwards"] = leg.download_transient()  # (mag_assemble_effective overwrites A, not the results)
+            return out
+        want, got = in_all_legs(legs, run)
+        for key in want:
+            assert_same_bits(got[key], want[key], key)
+        assert list(got["first, three members"]) == ["v", "probe_a", "iterations", "t_start", "t_end"]
+        assert got["first"]["iterations"].dtype == np.int32 and got["first"]["iterations"].min() > 0
+        assert got["first"]["probe_u"].shape == (11, 300) and got["first"]["snapshots"].shape == (4, n2) and got["first"]["energies"].shape == (11, 3)
+        assert got["resumed"]["probe_u"].shape == (6, 7) and got["resumed"]["snapshots"].shape == (2, n2)
+        assert_same_bits(got["resumed, afterwards"], got["resumed"], "after mag_assemble_effective")
+        for k in got["first, three members"]:
+            assert np.array_equal(got["first, three members"][k], got["first"][k]), k
+        for k, a in got["first, to the host"].items():
+            assert np.array_equal(a, got["first"][k]), k
+        # the binding's own path, host memory throughout, on a third context
+        with Context(device=0) as c:
+            kw = dict(dt=dt, density=RHO, beta=beta, gamma=gamma, rayleigh=(alpha, eta), energies=True, snapshot_every=3, cg_tol=tg.CG_TOL)
+            first = c.transient(prob, steps=10, amplitude=amp[:11], u0=u0, v0=v0, probes=probes, **kw)
+            resumed = c.transient(steps=5, amplitude=resumed_amp, probes=probes[:7], resume=True, **kw)
+            effective = c.assemble_effective(0.37, 2.5e4, RHO)
+        for key, ref in (("first", first), ("resumed", resumed)):
+            for k, a in got[key].items():
+                assert np.array_equal(a, ref[k]), (key, k)
+        assert np.array_equal(got["effective"]["values"], effective)
+        # a probe outside [0, 2N) that lives on the device: refused like its host twin, and the earlier results are gone
+        bad = probes[:9].copy()
+        bad[5] = n2
+        refused_alike(legs, lambda leg: leg.run_transient(4, dt, RHO, probes=bad, **opts), "probes[5]")
+        for leg in legs:
+            with pytest.raises(MagnetiteError) as e:
+                leg.ctx.download_transient()
+            assert e.value.code == 7  # MAG_ERR_STATE

@@ -67,8 +67,9 @@ def twin(name, config, which, lumped=False):
     return ref.newmark(K, M, free, prob.u_in, prob.f_in, STEPS, dt, beta, gamma, alpha, eta, amplitude_of(config, dt, T1))
 
 
-def every_step(c, prob, steps, dt, amplitude=None, **kw):
-    """u, v, a (steps + 1, 2N) and f (steps + 1, 2N, row 0 not available: NaN) of `steps` steps run one at a time"""
+def every_step(c, prob, steps, dt, amplitude=None, u0=None, v0=None, **kw):
+    """u, v, a (steps + 1, 2N) and f (steps + 1, 2N, row 0 not available: NaN) of `steps` steps run one at a time (u0, v0: the
+    start of the first)"""
     n2 = 2 * prob.mesh.num_nodes
     amp = np.ones(steps + 1) if amplitude is None else amplitude
     out = {k: np.full((steps + 1, n2), np.nan) for k in ("u", "v", "a", "f")}
@@ -76,7 +77,7 @@ def every_step(c, prob, steps, dt, amplitude=None, **kw):
     for n in range(steps):
         first = n == 0
         r = c.transient(prob if first else None, steps=1, dt=dt, density=RHO, amplitude=amp[n:n + 2], resume=not first,
-                        probes=np.arange(n2) if first else (), cg_tol=CG_TOL, **kw)
+                        probes=np.arange(n2) if first else (), cg_tol=CG_TOL, u0=u0 if first else None, v0=v0 if first else None, **kw)
         if first:
             out["u"][0], out["v"][0], out["a"][0] = r["probe_u"][0], r["probe_v"][0], r["probe_a"][0]
             iterations.append(int(r["iterations"][0]))

@@ -55,6 +55,62 @@ def newmark(K, M, free, u_in, f_in, steps, dt, beta=0.25, gamma=0.5, alpha=0.0, 
     return out
 
 
+class _NodeBlocks:
+    """the entries field_cg_ref.inverse_blocks reads of a matrix -- K[2g, 2g], K[2g, 2g + 1], K[2g + 1, 2g + 1] -- of a sparse one"""
+
+    def __init__(self, A):
+        self.diagonal, self.above = A.diagonal(), A.diagonal(1)
+
+    def __getitem__(self, ij):
+        i, j = ij
+        return self.diagonal[i] if i == j else self.above[i]
+
+
+def cg_solver(known, kind, tol, max_iter=10 ** 7, log=None):
+    """A `solver` for newmark(): the pass's own solve, launch by launch -- field_cg_ref.fused_cg (k_cg_field's recurrence) under
+    MAG_STOP_REL with `tol`, from zero, on A_FF scattered into the masked 2N x 2N matrix, with the fp32 inverse node blocks of
+    kind 2 (Jacobi) / 3 (2x2 blocks); kind 1: plain.  Device `preconditioner` 0 / 1 / 2 is kind 1 / 2 / 3; the CSR phase (cg = 4)
+    is plain CG: kind 1.  At the cap the solve hands on its last iterate, x_{max_iter}.  (iterations, converged) of every solve
+    is appended to `log`; newmark() does not call the solver for a right-hand side that is exactly zero (0 iterations)."""
+    import scipy.sparse as sp
+
+    import field_cg_ref as fc
+    known = np.asarray(known) != 0
+    n = len(known)
+    free = np.flatnonzero(~known)
+
+    def make(A_FF):
+        A = A_FF.tocoo()
+        Am = sp.csr_matrix((A.data, (free[A.row], free[A.col])), shape=(n, n))
+        minv = fc.inverse_blocks(_NodeBlocks(Am), known, kind) if kind >= 2 else None
+
+        def solve(b):
+            full = np.zeros(n)
+            full[free] = b
+            out = fc.fused_cg(Am, full, tol, kind, minv, max_iter=max_iter)
+            if log is not None:
+                log.append((int(out["iterations"]), int(out["converged"])))
+            return out["x"][free]
+        return solve
+    return make
+
+
+def moving_start(K, M, free, u_in, f_in, Phi, alpha, eta, amp0=1.0, modes=(1, 2), share=0.5):
+    """(u0, v0): a start that every term of M_FF a_0 = (amp[0] f - C v_0 - K u_0)_F feels.  u0 is mode shape Phi[modes[0]] scaled
+    so that |(K u0)_F| is `share` of |(amp[0] f - K u_P)_F| (the right-hand side of the start at rest), v0 is Phi[modes[1]] scaled
+    so that |(C v0)_F| is the same share of it, C = alpha M + eta K (pass the damped set's coefficients for an undamped run too).
+    Every prescribed DOF holds NaN: the header says those entries are ignored."""
+    n = K.shape[0]
+    known = np.ones(n, dtype=bool)
+    known[free] = False
+    at_rest = (amp0 * np.where(known, 0.0, f_in) - K @ np.where(known, u_in, 0.0))[free]
+    size = share * np.linalg.norm(at_rest)
+    u0 = Phi[modes[0]] * (size / np.linalg.norm((K @ Phi[modes[0]])[free]))
+    v0 = Phi[modes[1]] * (size / np.linalg.norm((alpha * (M @ Phi[modes[1]]) + eta * (K @ Phi[modes[1]]))[free]))
+    u0[known] = v0[known] = np.nan
+    return u0, v0
+
+
 def mode_closed_form(lam, phi, steps, dt):
     """u_n of the undamped average-acceleration scheme (beta 1/4, gamma 1/2) started at rest in mode phi of eigenvalue lam:
     cos(n theta) phi with cos(theta) = (1 - Omega^2 / 4) / (1 + Omega^2 / 4), Omega = sqrt(lam) dt."""
