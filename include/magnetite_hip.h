@@ -629,7 +629,7 @@ int mag_get_modal_stats(const mag_ctx *ctx, int32_t j, mag_stats *stats);
  *   (MAG_ERR_NOT_CONVERGED naming the step: the pass's earlier results are gone, the context is usable as before).  The iteration
  *   cap is no error (info[7] = 0).
  * Out of scope: time-varying supports; a warm start of the step's CG; the on-chip CG on A; fields, variants and ranks; modal
- *   superposition; explicit stepping without a solve for lumped mass. */
+ *   superposition. */
 typedef struct mag_transient_options {
     int32_t steps, resume, lumped, cg, energies, snapshot_every, num_probes, memory;
     double dt, beta, gamma, density, rayleigh_mass, rayleigh_stiffness, cg_tol; /* cg_tol 0: 1e-10 */
@@ -643,7 +643,8 @@ typedef struct mag_transient_result {
     double *energies;                       /* [steps + 1][3] = T, W, P */
     double *snapshots;                      /* [steps / snapshot_every + 1][2N] of u, row 0 = the start */
     int32_t *iterations;                    /* [steps + 1], entry 0 = the a_0 solve (0 in a resumed run) */
-    double scalars[4];                      /* t_start, t_end, 0, 0 (written by the call, on the host) */
+    double scalars[4];                      /* t_start, t_end, 0, 0; after mag_run_explicit: t_start, t_end, the dt used, dt_bound
+                                               (written by the call, on the host) */
     int32_t memory, reserved;
 } mag_transient_result;                     /* 120 bytes */
 int mag_run_transient(mag_ctx *ctx, const mag_transient_options *opt);
@@ -652,6 +653,57 @@ int mag_download_transient(mag_ctx *ctx, mag_transient_result *out);
  * a step, [5] snapshots kept, [6] resumed, [7] 1 when every solve converged */
 int mag_get_transient_info(const mag_ctx *ctx, int32_t info[8]);
 int mag_assemble_effective(mag_ctx *ctx, double c_K, double c_M, double density, int32_t lumped, double *values_out, int32_t memory);
+
+/* ---- explicit dynamics: central-difference time stepping of the uploaded part, one fused launch a step -----------
+ * mag_run_explicit: Newmark's method with beta = 0, gamma = 1/2 on the LUMPED mass m (mag_run_transient's lumped = 1), so that no
+ *   system is solved: the method for impact, wave propagation and short shocks, where the step is bounded by the mesh's fastest
+ *   mode anyway.  C = alpha M + eta K (rayleigh_mass, rayleigh_stiffness), the eta term taken at the half-step velocity.
+ *   Supports, loads and the start are mag_run_transient's: u_P = u_in, v_P = a_P = 0; the load on F is amplitude[n] * f_in;
+ *   u_0, v_0 given on F or zero.
+ *   Start:  a_0 = (amplitude[0] f - alpha m v_0 - K (u_0 + eta v_0))_F / m   (the step below with dt = 0: one code).
+ *   Step n -> n+1:   ut = u + dt v + dt^2/2 a,   vt = v + dt/2 a   (on P: ut = u_in, vt = 0);
+ *     a' = (amplitude[n+1] f - alpha m vt - K (ut + eta vt))_F / ((1 + dt alpha / 2) m),   a'_P = 0;
+ *     u' = ut,   v' = vt + dt/2 a'.
+ *     With eta = 0 this is mag_run_transient(beta = 0, gamma = 0.5, lumped = 1) with its solve replaced by a division.
+ *   The stable step.  lambda_bound = max over free DOFs i of (sum over free j of |K_ij|) / m_i (Gershgorin on M_FF^-1 K_FF),
+ *     omega_bound = sqrt(lambda_bound), xi = eta omega_bound / 2, dt_bound = (2 / omega_bound) (sqrt(1 + xi^2) - xi): never above
+ *     the true limit 2 / omega_max (and 0.69 - 0.94 of it on the test meshes).  The mass-proportional damping is centred in time
+ *     and does not shrink the limit; the lagged stiffness-proportional part does.  dt = 0 asks for dt_scale * dt_bound (dt_scale 0:
+ *     0.9).  A dt above dt_bound is NOT refused (the bound is conservative); a final state that is not finite is
+ *     MAG_ERR_NOT_CONVERGED naming dt and dt_bound: the pass's results are gone, the context is usable as before.
+ *   A step is ONE launch where the context has tile-local tables (info[2] = 1): the kernel reads K's tile-local block rows once,
+ *     the state lives in Hilbert order in two buffers (a launch reads one and writes the other), amplitude[n + 1] is read on the
+ *     device, and the host reads nothing between the launches.  The row order is a function of the mesh alone: the results are the
+ *     same bits for every tile_nodes and every grid.  Without the tables (op_variant = 1, a tile beyond the LDS) a step is four
+ *     launches in caller numbering (info[2] = 0), to the same accuracy.
+ *   Records.  Probe and energy rows are written at steps 0, record_every, 2 record_every, ... (record_every 0: 1): steps /
+ *     record_every + 1 rows; snapshots at steps 0, snapshot_every, ...  At such a step the state is moved to caller numbering and
+ *     mag_run_transient's record kernels run; any other step is the one launch.
+ *   Results.  The final u, v, a, t, the last amplitude and the reactions go into mag_run_transient's slots: mag_download_transient
+ *     and mag_get_transient_info serve an explicit run (`iterations`: steps / record_every + 1 zeros), and either pass may resume
+ *     the other's state.  n1 steps followed by a resumed n2 steps give, bit for bit, one run of n1 + n2 steps.
+ * mag_explicit_dt: out[0] lambda_bound, [1] dt_bound with eta = 0, [2] dt_bound with rayleigh_stiffness, [3] the smallest node
+ *   mass; needs an upload only.
+ * Errors: mag_run_transient's rules, order and wording.  Before any HIP call: MAG_ERR_BAD_ARGS for a null struct, steps < 1, a dt,
+ *   dt_scale or Rayleigh coefficient negative or not finite, a density not positive and finite, a negative record_every,
+ *   snapshot_every or num_probes, num_probes > 0 with NULL probes, a `memory` outside enum mag_memory, more than one rank;
+ *   MAG_ERR_STATE for resume with u0 / v0 or without a completed run, no upload, an element stiffness field, assemble_csr = 0 or
+ *   precision = 1.  After the first device work: a probe outside [0, 2N), an element of signed area <= 0, records beyond device
+ *   memory, the final state not finite.
+ * Out of scope: several steps in one launch; a graph replay of the steps; time-varying supports; fields, variants and ranks; a
+ *   sharper step estimate; element-wise step control, mass scaling, contact. */
+typedef struct mag_explicit_options {
+    int32_t steps, resume, energies, record_every, snapshot_every, num_probes, memory, reserved; /* record_every 0: 1 */
+    double dt, dt_scale, density, rayleigh_mass, rayleigh_stiffness;  /* dt 0: dt_scale * dt_bound; dt_scale 0: 0.9 */
+    const double *amplitude, *u0, *v0;                                /* [steps + 1], 2N, 2N; NULL: ones, zero, zero */
+    const int32_t *probes;                                            /* NULL: none */
+} mag_explicit_options;                                               /* 104 bytes */
+void mag_default_explicit_options(mag_explicit_options *opt); /* record_every 1, dt_scale 0.9, everything else 0 / NULL */
+int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *opt);
+/* after mag_run_explicit, mag_get_transient_info gives: info[0] steps done, [1] 6 (explicit), [2] 1 fused / 0 unfused, [3] step
+ * launches (fused: steps + 1 with the start, steps in a resumed run; unfused: four per step), [4] record_every, [5] snapshots
+ * kept, [6] resumed, [7] 1 */
+int mag_explicit_dt(mag_ctx *ctx, double density, double rayleigh_stiffness, double out[4]);
 
 /* ---- adaptive mesh refinement: longest-edge bisection with conformity closure (Rivara) of the uploaded mesh, on the device ----
  * What acts on the ZZ indicator of mag_run_stress: solve -> mag_run_stress -> mag_run_refine -> mag_upload_refined -> solve, the

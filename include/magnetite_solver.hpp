@@ -180,6 +180,30 @@ struct Transient {
                  converged = 0;
 };
 
+// The options of solver::run_explicit (include/magnetite_hip.h, mag_explicit_options); dt 0: dt_scale times the device's bound.
+// amplitude: steps + 1 values or empty (ones); u0, v0: 2N values in the order of `nodes` or empty (zero); probes: 2 * node + axis.
+struct ExplicitSpec {
+    std::int32_t steps = 0, record_every = 1, snapshot_every = 0;
+    bool energies = false;
+    double dt = 0.0, dt_scale = 0.9, density = 0.0, rayleigh_mass = 0.0, rayleigh_stiffness = 0.0;
+    std::vector<double> amplitude, u0, v0;
+    std::vector<std::int32_t> probes;
+};
+
+// What solver::run_explicit returns: the outputs of mag_download_transient after an explicit run -- the final state and its
+// reactions, the rows of steps 0, record_every, ... (probes, energies, `time`), the snapshots -- the step used, its bound and
+// mag_get_transient_info's words by name.
+struct Explicit {
+    std::vector<double> u, v, a, f, probe_u, probe_v, probe_a, energies, snapshots, time;
+    double t_start = 0, t_end = 0, dt = 0, dt_bound = 0;
+    std::int32_t steps = 0, fused = 0, step_launches = 0, record_every = 0, snapshots_kept = 0, resumed = 0;
+};
+
+// What solver::explicit_dt returns (mag_explicit_dt)
+struct ExplicitBound {
+    double lambda_bound = 0, dt_bound_undamped = 0, dt_bound = 0, min_mass = 0;
+};
+
 // The objective of solver::objective (include/magnetite_hip.h, mag_objective): one row of weights (and of the target) for all
 // members -- 2N values for MAG_OBJ_DISP_LSQ, E values or none for MAG_OBJ_STRESS_PNORM.
 struct ObjectiveSpec {
@@ -792,6 +816,103 @@ inline Result transient(const std::vector<Node> &nodes, const std::vector<Elemen
     out.snapshots_kept = info[5];
     out.resumed = info[6];
     out.converged = info[7];
+    mag_destroy(ctx);
+    return std::nullopt;
+}
+
+// Explicit dynamics (mag_run_explicit) of the part: spec.steps central-difference steps on the lumped mass, one fused launch a
+// step; supports, loads and the start as solver::transient.  (`explicit` is a keyword: hence the names.)
+inline Result run_explicit(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                           const ExplicitSpec &spec, Explicit &out, const mag_options *options = nullptr)
+{
+    const std::size_t N = nodes.size();
+    std::vector<double> xy, u_in(2 * N), f_in(2 * N);
+    std::vector<std::uint8_t> u_known;
+    std::vector<std::int32_t> conn;
+    if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
+    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
+    if (!spec.amplitude.empty() && spec.amplitude.size() != (std::size_t)std::max(spec.steps, 0) + 1)
+        return detail::solver_error("the amplitude has another length than steps + 1");
+    if ((!spec.u0.empty() && spec.u0.size() != 2 * N) || (!spec.v0.empty() && spec.v0.size() != 2 * N))
+        return detail::solver_error("u0 / v0 have another length than 2 N");
+    mag_ctx *ctx = mag_create(options);
+    if (!ctx) return detail::solver_error("mag_create failed");
+    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
+    if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    mag_explicit_options o;
+    mag_default_explicit_options(&o);
+    o.steps = spec.steps;
+    o.energies = spec.energies ? 1 : 0;
+    o.record_every = spec.record_every;
+    o.snapshot_every = spec.snapshot_every;
+    o.num_probes = (std::int32_t)spec.probes.size();
+    o.memory = MAG_MEM_HOST;
+    o.dt = spec.dt;
+    o.dt_scale = spec.dt_scale;
+    o.density = spec.density;
+    o.rayleigh_mass = spec.rayleigh_mass;
+    o.rayleigh_stiffness = spec.rayleigh_stiffness;
+    o.amplitude = spec.amplitude.empty() ? nullptr : spec.amplitude.data();
+    o.u0 = spec.u0.empty() ? nullptr : spec.u0.data();
+    o.v0 = spec.v0.empty() ? nullptr : spec.v0.data();
+    o.probes = spec.probes.empty() ? nullptr : spec.probes.data();
+    if (mag_run_explicit(ctx, &o) != MAG_OK) return detail::fail_and_destroy(ctx);
+    std::int32_t info[8] = {};
+    if (mag_get_transient_info(ctx, info) != MAG_OK) return detail::fail_and_destroy(ctx);
+    const std::size_t rows = (std::size_t)(info[0] / info[4]) + 1, P = spec.probes.size();
+    out = Explicit{};
+    out.u.resize(2 * N);
+    out.v.resize(2 * N);
+    out.a.resize(2 * N);
+    out.f.resize(2 * N);
+    out.probe_u.resize(rows * P);
+    out.probe_v.resize(rows * P);
+    out.probe_a.resize(rows * P);
+    if (spec.energies) out.energies.resize(3 * rows);
+    out.snapshots.resize((std::size_t)info[5] * 2 * N);
+    mag_transient_result d{};
+    d.u_out = out.u.data();
+    d.v_out = out.v.data();
+    d.a_out = out.a.data();
+    d.f_out = out.f.data();
+    if (P) d.probe_u = out.probe_u.data(), d.probe_v = out.probe_v.data(), d.probe_a = out.probe_a.data();
+    if (spec.energies) d.energies = out.energies.data();
+    if (info[5]) d.snapshots = out.snapshots.data();
+    d.memory = MAG_MEM_HOST;
+    if (mag_download_transient(ctx, &d) != MAG_OK) return detail::fail_and_destroy(ctx);
+    out.t_start = d.scalars[0];
+    out.t_end = d.scalars[1];
+    out.dt = d.scalars[2];
+    out.dt_bound = d.scalars[3];
+    out.steps = info[0];
+    out.fused = info[2];
+    out.step_launches = info[3];
+    out.record_every = info[4];
+    out.snapshots_kept = info[5];
+    out.resumed = info[6];
+    out.time.resize(rows);
+    for (std::size_t k = 0; k < rows; ++k) out.time[k] = out.t_start + out.dt * (double)((std::size_t)out.record_every * k);
+    mag_destroy(ctx);
+    return std::nullopt;
+}
+
+// The bound of the stable explicit step of the part (mag_explicit_dt): Gershgorin on M_FF^-1 K_FF with the lumped mass.
+inline Result explicit_dt(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                          double density, double rayleigh_stiffness, ExplicitBound &out, const mag_options *options = nullptr)
+{
+    const std::size_t N = nodes.size();
+    std::vector<double> xy, u_in(2 * N), f_in(2 * N);
+    std::vector<std::uint8_t> u_known;
+    std::vector<std::int32_t> conn;
+    if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
+    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
+    mag_ctx *ctx = mag_create(options);
+    if (!ctx) return detail::solver_error("mag_create failed");
+    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
+    if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    double b[4] = {};
+    if (mag_explicit_dt(ctx, density, rayleigh_stiffness, b) != MAG_OK) return detail::fail_and_destroy(ctx);
+    out = ExplicitBound{b[0], b[1], b[2], b[3]};
     mag_destroy(ctx);
     return std::nullopt;
 }

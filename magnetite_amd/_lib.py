@@ -41,6 +41,7 @@ SYMBOLS = [
     "mag_run_stress", "mag_download_stress",
     "mag_run_modal", "mag_download_modal", "mag_get_modal_info", "mag_get_modal_stats", "mag_apply_mass",
     "mag_default_transient_options", "mag_run_transient", "mag_download_transient", "mag_get_transient_info", "mag_assemble_effective",
+    "mag_default_explicit_options", "mag_run_explicit", "mag_explicit_dt",
     "mag_run_refine", "mag_get_refine_info", "mag_download_refine", "mag_upload_refined",
     "mag_set_element_scale", "mag_design_init", "mag_design_step", "mag_get_design_info", "mag_download_design",
     "mag_comm_get_unique_id", "mag_comm_init_rccl", "mag_comm_query", "mag_comm_init_callback", "mag_comm_set_window", "mag_comm_inbox_create", "mag_comm_inbox_open",
@@ -123,6 +124,14 @@ class TransientOptions(C.Structure):
                 ("snapshot_every", C.c_int32), ("num_probes", C.c_int32), ("memory", C.c_int32),
                 ("dt", C.c_double), ("beta", C.c_double), ("gamma", C.c_double), ("density", C.c_double),
                 ("rayleigh_mass", C.c_double), ("rayleigh_stiffness", C.c_double), ("cg_tol", C.c_double),
+                ("amplitude", C.c_void_p), ("u0", C.c_void_p), ("v0", C.c_void_p), ("probes", C.c_void_p)]
+
+
+class ExplicitOptions(C.Structure):
+    _fields_ = [("steps", C.c_int32), ("resume", C.c_int32), ("energies", C.c_int32), ("record_every", C.c_int32),
+                ("snapshot_every", C.c_int32), ("num_probes", C.c_int32), ("memory", C.c_int32), ("reserved", C.c_int32),
+                ("dt", C.c_double), ("dt_scale", C.c_double), ("density", C.c_double), ("rayleigh_mass", C.c_double),
+                ("rayleigh_stiffness", C.c_double),
                 ("amplitude", C.c_void_p), ("u0", C.c_void_p), ("v0", C.c_void_p), ("probes", C.c_void_p)]
 
 
@@ -252,6 +261,11 @@ def lib():
         L.mag_download_transient.argtypes = [vp, C.POINTER(TransientResult)]
         L.mag_get_transient_info.argtypes = [vp, ip]
         L.mag_assemble_effective.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_int32, dp, C.c_int32]
+    if hasattr(L, "mag_run_explicit"):  # (likewise: scripts/explicit_probe.py)
+        L.mag_default_explicit_options.argtypes = [C.POINTER(ExplicitOptions)]
+        L.mag_default_explicit_options.restype = None
+        L.mag_run_explicit.argtypes = [vp, C.POINTER(ExplicitOptions)]
+        L.mag_explicit_dt.argtypes = [vp, C.c_double, C.c_double, dp]
     if hasattr(L, "mag_run_refine"):  # (likewise: scripts/refine_probe.py)
         L.mag_run_refine.argtypes = [vp, C.POINTER(RefineOptions)]
         L.mag_get_refine_info.argtypes = [vp, C.POINTER(C.c_int64)]

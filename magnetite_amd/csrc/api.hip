@@ -33,6 +33,7 @@
 #include "refine.h"
 #include "sens.h"
 #include "transient.h"
+#include "explicit.h"
 
 using magk::CgState;
 
@@ -340,6 +341,14 @@ struct mag_ctx {
     // the length of the FIRST poll block of the pass's next solve (0: check_every, as for every other caller): the pass expects
     // the iteration count of its previous solve and polls in short blocks behind it
     int32_t tr_first_block = 0;
+    // explicit dynamics (mag_run_explicit) leaves its final state and its records in the transient pass's slots (either pass
+    // resumes the other's state; mag_download_transient serves both).  tr_rows: the record rows of the last run of either pass;
+    // tr_dt, tr_dt_bound: scalars[2..3] (0 after the implicit pass).  Its own buffers: the state records in Hilbert order (two:
+    // a step reads one and writes the other), the node masses, u_in and f_in in Hilbert order, the bound's partials and result,
+    // the finite flag
+    DevBuf ex_rec[2], ex_mass, ex_uin, ex_f, ex_part, ex_out;
+    int64_t tr_rows = 0;
+    double tr_dt = 0.0, tr_dt_bound = 0.0;
 
     magc::Comm comm;
 };
@@ -4622,6 +4631,8 @@ int mag_run_transient(mag_ctx *ctx, const mag_transient_options *o)
     ctx->tr_t1 = t_start + (double)steps * dt;
     ctx->tr_amp_last = amp_last;
     ctx->tr_iterations = iterations;
+    ctx->tr_rows = (int64_t)rows;
+    ctx->tr_dt = ctx->tr_dt_bound = 0.0;
     ctx->tr_have = true;
     if (!all_converged) ctx->err = std::string(fn) + ": a solve stopped at the iteration cap above the tolerance: its last iterate was used";
     return MAG_OK;
@@ -4644,7 +4655,7 @@ int mag_download_transient(mag_ctx *ctx, mag_transient_result *o)
     const hipMemcpyKind kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     const hipMemcpyKind hkind = o->memory == MAG_MEM_DEVICE ? hipMemcpyHostToDevice : hipMemcpyHostToHost;
     hipStream_t s = ctx->stream;
-    const size_t vb = 16 * (size_t)ctx->N, rows = (size_t)ctx->tr_steps + 1, pb = 8 * rows * (size_t)ctx->tr_num_probes;
+    const size_t vb = 16 * (size_t)ctx->N, rows = (size_t)ctx->tr_rows, pb = 8 * rows * (size_t)ctx->tr_num_probes;
     if (o->u_out) HIPCHK(hipMemcpyAsync(o->u_out, ctx->tr_u.p, vb, kind, s));
     if (o->v_out) HIPCHK(hipMemcpyAsync(o->v_out, ctx->tr_v.p, vb, kind, s));
     if (o->a_out) HIPCHK(hipMemcpyAsync(o->a_out, ctx->tr_a.p, vb, kind, s));
@@ -4658,7 +4669,8 @@ int mag_download_transient(mag_ctx *ctx, mag_transient_result *o)
     HIPCHK(hipStreamSynchronize(s));
     o->scalars[0] = ctx->tr_t0;
     o->scalars[1] = ctx->tr_t1;
-    o->scalars[2] = o->scalars[3] = 0.0;
+    o->scalars[2] = ctx->tr_dt;
+    o->scalars[3] = ctx->tr_dt_bound;
     return MAG_OK;
 }
 
@@ -4667,6 +4679,323 @@ int mag_get_transient_info(const mag_ctx *ctx, int32_t info[8])
     if (!ctx || !info || ctx->comm.nranks > 1) return MAG_ERR_BAD_ARGS;
     if (!ctx->have_problem || !ctx->tr_have) return MAG_ERR_STATE;
     for (int k = 0; k < 8; ++k) info[k] = ctx->tr_info[k];
+    return MAG_OK;
+}
+
+// ---- explicit dynamics (explicit.hip): central differences on the lumped mass.  The driver shares the transient pass's
+// matrices, table buffers, records and result slots; a step that records nothing is one launch, enqueued on the context's
+// stream, and the host reads nothing between the launches ----
+namespace {
+
+// the stable step from lambda_bound: (2 / omega) (sqrt(1 + xi^2) - xi), xi = eta omega / 2, with the difference written as
+// 1 / (sqrt(1 + xi^2) + xi) (no cancellation at a large xi)
+double explicit_dt_bound(double lambda, double eta)
+{
+    const double omega = std::sqrt(lambda), xi = eta * omega / 2.0;
+    return (2.0 / omega) / (std::sqrt(1.0 + xi * xi) + xi);
+}
+
+// out[0] lambda_bound, [1] dt_bound with eta = 0, [2] with eta, [3] the smallest node mass, of K and the lumped mass in place
+// (transient_matrices); synchronises
+int explicit_bounds(mag_ctx *ctx, double eta, double out[4])
+{
+    hipStream_t s = ctx->stream;
+    HIPCHK(ctx->ex_part.reserve(8 * 2 * (size_t)magk::kSensBlocks));
+    HIPCHK(ctx->ex_out.reserve(32));
+    magk::explicit_bound(transient_pattern(ctx), ctx->kval.as<double>(), ctx->tr_mval.as<double>(), ctx->uknown.as<uint8_t>(),
+                         ctx->ex_part.as<double>(), ctx->ex_out.as<double>(), s);
+    HIPCHK(hipGetLastError());
+    double h[2] = {0.0, 0.0};
+    HIPCHK(hipMemcpyAsync(h, ctx->ex_out.p, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    out[0] = h[0];
+    out[1] = explicit_dt_bound(h[0], 0.0);
+    out[2] = explicit_dt_bound(h[0], eta);
+    out[3] = h[1];
+    return MAG_OK;
+}
+
+} // namespace
+
+void mag_default_explicit_options(mag_explicit_options *o)
+{
+    if (!o) return;
+    *o = {};
+    o->record_every = 1;
+    o->dt_scale = 0.9;
+}
+
+int mag_explicit_dt(mag_ctx *ctx, double density, double rayleigh_stiffness, double out[4])
+{
+    const char *fn = "mag_explicit_dt";
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!out) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null out", fn);
+    if (!pos_finite(density)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: density %g is not positive and finite", fn, density);
+    if (!nonneg_finite(rayleigh_stiffness))
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: rayleigh_stiffness %g is negative or not finite", fn, rayleigh_stiffness);
+    if (int rc = transient_refused(ctx, fn)) return rc;
+    if (int rc = enter(ctx)) return rc;
+    if (int rc = transient_matrices(ctx, density, 1)) return rc;
+    return explicit_bounds(ctx, rayleigh_stiffness, out);
+}
+
+int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
+{
+    const char *fn = "mag_run_explicit";
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null options", fn);
+    if (o->steps < 1) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: steps = %d: at least one step", fn, (int)o->steps);
+    if (!nonneg_finite(o->dt)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: dt %g is negative or not finite", fn, o->dt);
+    if (!nonneg_finite(o->dt_scale)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: dt_scale %g is negative or not finite", fn, o->dt_scale);
+    if (!pos_finite(o->density)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: density %g is not positive and finite", fn, o->density);
+    if (!nonneg_finite(o->rayleigh_mass)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: rayleigh_mass %g is negative or not finite", fn, o->rayleigh_mass);
+    if (!nonneg_finite(o->rayleigh_stiffness))
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: rayleigh_stiffness %g is negative or not finite", fn, o->rayleigh_stiffness);
+    if (o->record_every < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: record_every = %d is negative", fn, (int)o->record_every);
+    if (o->snapshot_every < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: snapshot_every = %d is negative", fn, (int)o->snapshot_every);
+    if (o->num_probes < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: num_probes = %d is negative", fn, (int)o->num_probes);
+    if (o->num_probes > 0 && !o->probes) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: num_probes = %d with null probes", fn, (int)o->num_probes);
+    if (int rc = memory_refused(ctx, o->memory, fn)) return rc;
+    if (ctx->comm.nranks > 1)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: transient dynamics run on one GPU: this context has a communicator of %d ranks", fn, ctx->comm.nranks);
+    if (o->resume && (o->u0 || o->v0)) return fail(ctx, MAG_ERR_STATE, "%s: resume starts from the previous run's state: u0 / v0 must be NULL", fn);
+    if (o->resume && !(ctx->have_problem && ctx->tr_have)) return fail(ctx, MAG_ERR_STATE, "%s: resume without a completed run of the pass", fn);
+    if (int rc = transient_refused(ctx, fn)) return rc;
+    if (int rc = enter(ctx)) return rc;
+
+    const bool resume = o->resume != 0, energies = o->energies != 0;
+    const int32_t steps = o->steps, np = o->num_probes, se = o->snapshot_every, re = o->record_every > 0 ? o->record_every : 1;
+    const double alpha = o->rayleigh_mass, eta = o->rayleigh_stiffness;
+    const double t_start = resume ? ctx->tr_t1 : 0.0;
+    const double amp_first = ctx->tr_amp_last; // (a resumed run's row 0 carries the load of the state it resumes)
+    ctx->tr_have = false; // (a failure leaves no results of the pass)
+    hipStream_t s = ctx->stream;
+    const hipMemcpyKind in_kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+
+    if (int rc = transient_matrices(ctx, o->density, 1)) return rc;
+    const bool fused = ctx->use_lds; // (known once the order is built: the tile-local tables, or a step of four launches)
+    const int64_t N = ctx->N, n2 = 2 * N;
+    const size_t vb = 16 * (size_t)N;
+    const magk::Pattern pat = transient_pattern(ctx);
+
+    // ---- the checks that need the device: the elements' orientation, the probes; the step
+    HIPCHK(ctx->tr_bad.reserve(16));
+    HIPCHK(ctx->tr_probes.reserve(4 * (size_t)std::max(np, 1)));
+    unsigned long long bad[2] = {~0ull, ~0ull};
+    unsigned long long *d_bad = ctx->tr_bad.as<unsigned long long>();
+    if (np > 0) HIPCHK(hipMemcpyAsync(ctx->tr_probes.p, o->probes, 4 * (size_t)np, in_kind, s));
+    magk::orientation(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), N, ctx->E, d_bad, s);
+    magk::check_probes(ctx->tr_probes.as<int32_t>(), np, n2, d_bad + 1, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(bad, d_bad, 16, hipMemcpyDeviceToHost, s));
+    double bounds[4];
+    if (int rc = explicit_bounds(ctx, eta, bounds)) return rc; // (synchronises)
+    if (bad[0] != ~0ull)
+        return fail(ctx, MAG_ERR_BAD_ARGS,
+                    "%s: element %lld has a signed area <= 0 (the stiffness carries the signed area: the pass needs counter-clockwise elements)", fn,
+                    (long long)bad[0]);
+    if (bad[1] != ~0ull)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: probes[%lld] is outside [0, %lld)", fn, (long long)bad[1], (long long)n2);
+    const double dt_bound = bounds[2];
+    const double dt = o->dt != 0.0 ? o->dt : (o->dt_scale != 0.0 ? o->dt_scale : 0.9) * dt_bound;
+    if (!pos_finite(dt)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: dt = 0 asks for dt_scale * dt_bound, and dt_bound is %g (no free DOF carries stiffness)", fn, dt_bound);
+
+    // ---- the buffers: the records first, against the memory that is free now
+    const size_t rows = (size_t)(steps / re) + 1, amp_n = (size_t)steps + 1, snaps = se > 0 ? (size_t)(steps / se) + 1 : 0;
+    const size_t probe_b = 3 * 8 * rows * (size_t)std::max(np, 1), energy_b = 3 * 8 * rows, snap_b = snaps * vb;
+    {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        auto more = [](const DevBuf &b, size_t want) { return want > b.cap ? want + (want >> 4) + 256 : (size_t)0; };
+        const size_t need = more(ctx->tr_probe, probe_b) + more(ctx->tr_energy, energy_b) + more(ctx->tr_snap, snap_b) + more(ctx->tr_amp, 8 * amp_n);
+        if (need > free_b)
+            return fail(ctx, MAG_ERR_TOO_LARGE, "%s: the records of %d steps need %zu bytes of device memory, %zu are free", fn, (int)steps, need, free_b);
+    }
+    HIPCHK(ctx->tr_probe.reserve(probe_b));
+    HIPCHK(ctx->tr_energy.reserve(energy_b));
+    HIPCHK(ctx->tr_snap.reserve(std::max<size_t>(snap_b, 8)));
+    HIPCHK(ctx->tr_amp.reserve(8 * amp_n));
+    HIPCHK(ctx->tr_part.reserve(8 * 3 * (size_t)magk::kSensBlocks));
+    for (DevBuf *b : {&ctx->tr_u, &ctx->tr_v, &ctx->tr_a}) {
+        if (resume && b->cap < vb) return fail(ctx, MAG_ERR_STATE, "%s: resume without the state of a completed run", fn);
+        HIPCHK(b->reserve(vb));
+    }
+    for (DevBuf *b : {&ctx->tr_ut, &ctx->tr_vt, &ctx->tr_rhs, &ctx->tr_zero, &ctx->tr_f, &ctx->tr_ku, &ctx->tr_mv}) HIPCHK(b->reserve(vb));
+    HIPCHK(hipMemsetAsync(ctx->tr_zero.p, 0, vb, s));
+
+    // ---- the inputs: amplitude (ones where none is given), u0, v0
+    std::vector<double> ones;
+    double *d_amp = ctx->tr_amp.as<double>();
+    if (o->amplitude) {
+        HIPCHK(hipMemcpyAsync(d_amp, o->amplitude, 8 * amp_n, in_kind, s));
+    } else {
+        ones.assign(amp_n, 1.0);
+        HIPCHK(hipMemcpyAsync(d_amp, ones.data(), 8 * amp_n, hipMemcpyHostToDevice, s));
+    }
+    if (resume) HIPCHK(hipMemcpyAsync(d_amp, &amp_first, 8, hipMemcpyHostToDevice, s));
+    double amp_last = 1.0;
+    HIPCHK(hipMemcpyAsync(&amp_last, d_amp + steps, 8, hipMemcpyDeviceToHost, s));
+    const double *d_u0 = nullptr, *d_v0 = nullptr;
+    if (o->u0 || o->v0) {
+        HIPCHK(ctx->tr_in.reserve(2 * vb));
+        if (o->u0) {
+            HIPCHK(hipMemcpyAsync(ctx->tr_in.p, o->u0, vb, in_kind, s));
+            d_u0 = ctx->tr_in.as<double>();
+        }
+        if (o->v0) {
+            HIPCHK(hipMemcpyAsync(ctx->tr_in.as<char>() + vb, o->v0, vb, in_kind, s));
+            d_v0 = ctx->tr_in.as<double>() + n2;
+        }
+    }
+    HIPCHK(hipStreamSynchronize(s)); // (the host's copies are done with)
+
+    magk::NewmarkState st = {};
+    st.n2 = n2;
+    st.u = ctx->tr_u.as<double>();
+    st.v = ctx->tr_v.as<double>();
+    st.a = ctx->tr_a.as<double>();
+    st.ut = ctx->tr_ut.as<double>();
+    st.vt = ctx->tr_vt.as<double>();
+    st.known = ctx->uknown.as<uint8_t>();
+    st.u_in = ctx->uin.as<double>();
+    st.num_probes = np;
+    st.probes = ctx->tr_probes.as<int32_t>();
+    st.probe_u = ctx->tr_probe.as<double>();
+    st.probe_v = st.probe_u + rows * (size_t)np;
+    st.probe_a = st.probe_v + rows * (size_t)np;
+    magk::NewmarkState st_quiet = st; // (the state without the probes: a snapshot alone, the unfused step's corrector)
+    st_quiet.num_probes = 0;
+    double *d_rhs = ctx->tr_rhs.as<double>(), *d_energy = ctx->tr_energy.as<double>(), *d_snap = ctx->tr_snap.as<double>();
+    const double *d_f = ctx->fin.as<double>(), *d_k = ctx->kval.as<double>(), *d_m = ctx->tr_mval.as<double>();
+
+    // ---- the fused step's table, values (unmasked: prescribed displacements enter through K ut) and inputs in Hilbert order
+    magk::ExplicitParams P = {};
+    int32_t grid = 1;
+    int cur = 0;
+    magk::ExRec *rec[2] = {nullptr, nullptr};
+    if (fused) {
+        FieldTable tab{ctx->tr_width, ctx->tr_meta, ctx->tr_slot, ctx->tr_src, ctx->tr_val};
+        if (int rc = build_field_table(ctx, tab)) return rc;
+        magk::field_gather(ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(), d_k, ctx->tr_zero.as<uint8_t>(), ctx->halo_g.as<int32_t>(),
+                           tab.meta.as<magk::FieldTileMeta>(), tab.slot.as<uint16_t>(), tab.src.as<int32_t>(), N, ctx->B, ctx->T, tab.total,
+                           tab.val.as<double2>(), s);
+        for (DevBuf &b : ctx->ex_rec) HIPCHK(b.reserve(sizeof(magk::ExRec) * (size_t)N));
+        HIPCHK(ctx->ex_mass.reserve(8 * (size_t)N));
+        HIPCHK(ctx->ex_uin.reserve(vb));
+        HIPCHK(ctx->ex_f.reserve(vb));
+        magk::explicit_inputs(pat, ctx->perm.as<uint32_t>(), d_m, st.u_in, d_f, ctx->ex_mass.as<double>(), ctx->ex_uin.as<double2>(),
+                              ctx->ex_f.as<double2>(), s);
+        HIPCHK(hipGetLastError());
+        rec[0] = ctx->ex_rec[0].as<magk::ExRec>();
+        rec[1] = ctx->ex_rec[1].as<magk::ExRec>();
+        P.N = N, P.total = tab.total, P.T = ctx->T, P.cap = ctx->cap;
+        P.maskP = ctx->maskP.as<uint8_t>();
+        P.meta = tab.meta.as<magk::FieldTileMeta>(), P.slot = tab.slot.as<uint16_t>(), P.fval = tab.val.as<double2>();
+        P.halo_g = ctx->halo_g.as<int32_t>();
+        P.uinP = ctx->ex_uin.as<double2>(), P.fP = ctx->ex_f.as<double2>(), P.massP = ctx->ex_mass.as<double>();
+        P.amplitude = d_amp, P.alpha = alpha, P.eta = eta;
+        grid = magk::explicit_grid(ctx->B, ctx->cap, ctx->T);
+    }
+    long long launches = 0;
+    bool expanded = true; // (tr_u, tr_v, tr_a hold the current state)
+    // one step of h (the start: h = 0) under amplitude[amp_at]
+    auto step = [&](double h, int64_t amp_at) {
+        if (fused) {
+            P.in = rec[cur], P.out = rec[cur ^ 1], P.dt = h, P.amp_at = amp_at;
+            magk::explicit_step(P, ctx->B, grid, s);
+            cur ^= 1;
+            expanded = false;
+            launches += 1;
+            return;
+        }
+        magk::newmark_predict(st, h, 0.0, 0.5, s);
+        magk::PatternApply r = {};
+        r.kval = d_k, r.mval = d_m, r.xa = st.ut, r.ca = 1.0, r.xb = eta != 0.0 ? st.vt : nullptr, r.cb = eta;
+        r.xc = alpha != 0.0 ? st.vt : nullptr, r.cc = alpha;
+        r.kind = 1, r.known = st.known, r.f = d_f, r.amplitude = d_amp, r.amp_at = amp_at, r.y = d_rhs;
+        magk::pattern_apply(pat, r, s);
+        magk::explicit_divide(pat, d_m, st.known, d_rhs, 1.0 + 0.5 * h * alpha, st.a, s);
+        magk::newmark_correct(st_quiet, h, 0.0, 0.5, 0, nullptr, s);
+        launches += 4;
+    };
+    auto expand = [&]() {
+        if (expanded) return;
+        magk::explicit_scatter(ctx->perm.as<uint32_t>(), N, rec[cur], st.u, st.v, st.a, s);
+        expanded = true;
+    };
+    // the records of step n: probe and energy row n / re when re divides n, the snapshot when se does
+    auto record = [&](int32_t n) {
+        // (a row without probes and energies holds nothing: such a step stays the one launch)
+        const bool row_due = n % re == 0 && (np > 0 || energies), snap_due = se > 0 && n % se == 0;
+        if (!row_due && !snap_due) return;
+        expand();
+        double *snap = snap_due ? d_snap + (size_t)(n / se) * (size_t)n2 : nullptr;
+        const int64_t row = n / re;
+        magk::newmark_record(row_due ? st : st_quiet, row, snap, s);
+        if (row_due && energies) {
+            magk::PatternApply e = {};
+            e.kval = d_k, e.mval = d_m, e.xa = st.u, e.ca = 1.0, e.xc = st.v, e.cc = 1.0, e.y = d_rhs;
+            e.ku = ctx->tr_ku.as<double>(), e.mv = ctx->tr_mv.as<double>();
+            magk::pattern_apply(pat, e, s);
+            magk::newmark_energies(st, e.ku, e.mv, d_f, d_amp, n, ctx->tr_part.as<double>(), d_energy + 3 * row, s);
+        }
+    };
+
+    // ---- the start: a_0 by the step with dt = 0
+    if (!resume) magk::newmark_start(st, d_u0, d_v0, s);
+    if (fused) magk::explicit_gather(ctx->perm.as<uint32_t>(), N, st.u, st.v, st.a, rec[cur], s);
+    if (!resume) step(0.0, 0);
+    record(0);
+    HIPCHK(hipGetLastError());
+
+    // ---- the steps
+    for (int32_t n = 0; n < steps; ++n) {
+        step(dt, n + 1);
+        record(n + 1);
+    }
+    HIPCHK(hipGetLastError());
+
+    // ---- the final state, its finite check and its reactions
+    expand();
+    int32_t *d_flag = (int32_t *)(d_bad); // (the checks' words are done with)
+    HIPCHK(hipMemsetAsync(d_flag, 0, 4, s));
+    magk::explicit_finite(st.u, st.v, st.a, n2, d_flag, s);
+    {
+        magk::PatternApply r = {};
+        r.kval = d_k, r.mval = d_m, r.xa = st.u, r.ca = 1.0, r.xb = eta != 0.0 ? st.v : nullptr, r.cb = eta;
+        r.xc = st.a, r.cc = 1.0, r.xd = alpha != 0.0 ? st.v : nullptr, r.cd = alpha;
+        r.kind = 2, r.known = st.known, r.f = d_f, r.amplitude = d_amp, r.amp_at = steps, r.y = ctx->tr_f.as<double>();
+        magk::pattern_apply(pat, r, s);
+    }
+    int32_t not_finite = 0;
+    HIPCHK(hipMemcpyAsync(&not_finite, d_flag, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    if (not_finite)
+        return fail(ctx, MAG_ERR_NOT_CONVERGED, "%s: the state after %d steps is not finite: dt = %g against dt_bound = %g (the step is unstable)", fn,
+                    (int)steps, dt, dt_bound);
+
+    int32_t *info = ctx->tr_info;
+    info[0] = steps;
+    info[1] = 6;
+    info[2] = fused ? 1 : 0;
+    info[3] = (int32_t)std::min<long long>(launches, INT32_MAX);
+    info[4] = re;
+    info[5] = (int32_t)snaps;
+    info[6] = resume ? 1 : 0;
+    info[7] = 1;
+    ctx->tr_steps = steps;
+    ctx->tr_num_probes = np;
+    ctx->tr_snaps = (int32_t)snaps;
+    ctx->tr_energies = energies;
+    ctx->tr_t0 = t_start;
+    ctx->tr_t1 = t_start + (double)steps * dt;
+    ctx->tr_amp_last = amp_last;
+    ctx->tr_iterations.assign(rows, 0);
+    ctx->tr_rows = (int64_t)rows;
+    ctx->tr_dt = dt;
+    ctx->tr_dt_bound = dt_bound;
+    ctx->tr_have = true;
     return MAG_OK;
 }
 

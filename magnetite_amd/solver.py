@@ -758,7 +758,8 @@ class Context:
         """dict(u, v, a, f (2N: the final state and its reactions), iterations (steps + 1), t_start, t_end, and what the run
         recorded: probe_u / probe_v / probe_a (steps + 1, probes), energies (steps + 1, 3 = T, W, P), snapshots (rows, 2N))."""
         info = self.transient_info()
-        rows, n2 = info["steps"] + 1, 2 * self.N
+        # (after an explicit run -- cg_kernel 6 -- the rows are those of steps 0, record_every, ...: word 4)
+        rows, n2 = (info["steps"] // info["max_step_iterations"] if info["cg_kernel"] == 6 else info["steps"]) + 1, 2 * self.N
         num_probes = self._transient_probes if num_probes is None else num_probes
         energies = self._transient_energies if energies is None else energies
         out = {k: np.empty(n2) for k in ("u", "v", "a", "f")}
@@ -779,6 +780,8 @@ class Context:
         o.memory = MAG_MEM_HOST
         self._check(self._L.mag_download_transient(self._h, C.byref(o)))
         out["t_start"], out["t_end"] = float(o.scalars[0]), float(o.scalars[1])
+        if info["cg_kernel"] == 6:
+            out["dt"], out["dt_bound"] = float(o.scalars[2]), float(o.scalars[3])
         return out
 
     _transient_probes = 0
@@ -796,6 +799,63 @@ class Context:
                            lumped, resume)
         out = self.download_transient()
         out.update(self.transient_info())
+        return out
+
+    # -- explicit dynamics: central differences on the lumped mass, one fused launch a step --------------
+    EXPLICIT_INFO = ("steps", "method", "fused", "step_launches", "record_every", "snapshots_kept", "resumed", "finite")
+
+    def explicit_dt(self, density, rayleigh_stiffness=0.0):
+        """mag_explicit_dt on the uploaded problem: dict(lambda_bound, dt_bound_undamped, dt_bound, min_mass)."""
+        out = np.empty(4)
+        self._check(self._L.mag_explicit_dt(self._h, float(density), float(rayleigh_stiffness), _p(out, C.c_double)))
+        return dict(zip(("lambda_bound", "dt_bound_undamped", "dt_bound", "min_mass"), (float(v) for v in out)))
+
+    def run_explicit(self, steps, dt=None, dt_scale=0.9, density=None, rayleigh=(0.0, 0.0), amplitude=None, u0=None, v0=None, probes=(),
+                     energies=False, record_every=1, snapshot_every=0, resume=False):
+        """mag_run_explicit on the uploaded problem (no run needed): `steps` central-difference steps (include/magnetite_hip.h);
+        dt None: dt_scale times the device's bound."""
+        if density is None:
+            raise MagnetiteError("Solver", "explicit: a density is needed (the model has none)")
+        o = _lib.ExplicitOptions()
+        self._L.mag_default_explicit_options(C.byref(o))
+        keep = []  # (the arrays the options point to, until the call returns)
+
+        def vec(x, n):
+            if x is None:
+                return None
+            a = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+            if a.size != n:
+                raise MagnetiteError("Solver", f"explicit: an array of {a.size} entries where {n} are expected")
+            keep.append(a)
+            return a.ctypes.data
+
+        probes = np.ascontiguousarray(probes, dtype=np.int32).reshape(-1)
+        o.steps, o.resume, o.energies, o.record_every = int(steps), 1 if resume else 0, 1 if energies else 0, int(record_every)
+        o.snapshot_every, o.num_probes, o.memory = int(snapshot_every), int(probes.size), MAG_MEM_HOST
+        o.dt, o.dt_scale, o.density = 0.0 if dt is None else float(dt), float(dt_scale), float(density)
+        o.rayleigh_mass, o.rayleigh_stiffness = float(rayleigh[0]), float(rayleigh[1])
+        o.amplitude = vec(amplitude, max(int(steps), 0) + 1)
+        o.u0, o.v0 = vec(u0, 2 * self.N), vec(v0, 2 * self.N)
+        o.probes = probes.ctypes.data if probes.size else None
+        rc = self._check(self._L.mag_run_explicit(self._h, C.byref(o)))
+        self._transient_probes, self._transient_energies = int(probes.size), bool(energies)  # (what download_transient sizes)
+        return rc
+
+    def explicit(self, prob=None, steps=None, dt=None, dt_scale=0.9, density=None, rayleigh=(0.0, 0.0), amplitude=None, u0=None, v0=None,
+                 probes=(), energies=False, record_every=1, snapshot_every=0, resume=False):
+        """The response of prob (uploaded when given; otherwise of what is uploaded) over `steps` explicit steps: the arrays of
+        download_transient() (rows at steps 0, record_every, ...), the words of mag_get_transient_info by name (EXPLICIT_INFO),
+        dt (the step used), dt_bound and time (the rows' times)."""
+        if prob is not None:
+            self.upload_problem(prob)
+        if steps is None:
+            raise MagnetiteError("Solver", "explicit: steps are needed")
+        self.run_explicit(steps, dt, dt_scale, density, rayleigh, amplitude, u0, v0, probes, energies, record_every, snapshot_every, resume)
+        out = self.download_transient()
+        info = (C.c_int32 * 8)()
+        self._check(self._L.mag_get_transient_info(self._h, info))
+        out.update(zip(self.EXPLICIT_INFO, (int(v) for v in info)))
+        out["time"] = out["t_start"] + out["dt"] * (out["record_every"] * np.arange(len(out["iterations"])))
         return out
 
     def assemble_effective(self, c_K, c_M, density, lumped=False):

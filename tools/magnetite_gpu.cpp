@@ -9,6 +9,7 @@
 // Usage: magnetite_gpu <input.json> <mesh.msh> [--nodes nodes.csv] [--elements elements.csv] [--dry-run] [--rel TOL]
 //                      [--stress-recovery] [--modal P --density RHO] [--adapt R [--refine-fraction T] [--refine-split 1|3]]
 //                      [--transient STEPS --dt DT --density RHO [--rayleigh A,E] [--probe DOF]...]
+//                      [--explicit STEPS --density RHO [--dt DT | --dt-scale S] [--rayleigh A,E] [--probe DOF]... [--record-every K]]
 //   --dry-run  stop before the solver and print what was parsed (no GPU needed)
 //   --rel TOL  stop CG on relative residual TOL instead of the reference's absolute 1e-4
 //   --modal P --density RHO  also print "info: mode k frequency F Hz residual R" for the P lowest modes and write modes.csv
@@ -16,6 +17,10 @@
 //   --transient STEPS --dt DT --density RHO  also run STEPS steps of Newmark's method from rest under the loads applied at t = 0
 //              (solver::transient; --rayleigh A,E: C = A M + E K), print "info: step n t T iterations I" per step and write
 //              history.csv (step,t, then u,v,a per --probe DOF, DOF = 2 * node + axis) next to nodes.csv
+//   --explicit STEPS --density RHO  also run STEPS central-difference steps on the lumped mass from rest under the loads applied at
+//              t = 0 (solver::run_explicit: one fused launch a step; --dt DT, or --dt-scale S times the device's bound of the
+//              stable step, 0.9 by default), print "info: explicit dt D (bound B)" and "info: step n t T" per recorded row
+//              (--record-every K: steps 0, K, 2K, ...) and write history.csv as --transient does
 //   --stress-recovery  also write nodes_stress.csv (id,sx,sy,txy,vm) and elements_stress.csv (id,sx,sy,txy,vm,eta2) next to the
 //              two files -- solver::stress_recovery: the tensor per element, the nodal field, the ZZ error indicator -- and
 //              print eta_rel; without it nothing changes
@@ -394,7 +399,21 @@ std::string history_name(const std::string &nodes_output)
 }
 
 // the probes' rows of solver::transient, a row per step, floats as csv_output prints them
+void history_output(const std::vector<double> &time, const std::vector<std::size_t> &step, const std::vector<double> &probe_u,
+                    const std::vector<double> &probe_v, const std::vector<double> &probe_a, const std::vector<std::int32_t> &probes,
+                    const std::string &path);
 void history_output(const Transient &tr, const std::vector<std::int32_t> &probes, double dt, const std::string &path)
+{
+    std::vector<double> time;
+    std::vector<std::size_t> step;
+    for (size_t n = 0; n < tr.iterations.size(); ++n) time.push_back((double)n * dt), step.push_back(n);
+    history_output(time, step, tr.probe_u, tr.probe_v, tr.probe_a, probes, path);
+}
+
+// a row per recorded step (solver::transient: every step; solver::run_explicit: steps 0, record_every, ...)
+void history_output(const std::vector<double> &time, const std::vector<std::size_t> &step, const std::vector<double> &probe_u,
+                    const std::vector<double> &probe_v, const std::vector<double> &probe_a, const std::vector<std::int32_t> &probes,
+                    const std::string &path)
 {
     std::FILE *hf = std::fopen(path.c_str(), "w");
     if (!hf) die({MagnetiteError::Solver, "Failed to create history.csv: " + path});
@@ -402,11 +421,11 @@ void history_output(const Transient &tr, const std::vector<std::int32_t> &probes
     for (std::int32_t d : probes) std::fprintf(hf, ",u%d,v%d,a%d", (int)d, (int)d, (int)d);
     std::fputs("\n", hf);
     const size_t P = probes.size();
-    for (size_t n = 0; n < tr.iterations.size(); ++n) {
-        std::fprintf(hf, "%zu,%s", n, rust_display((double)n * dt).c_str());
+    for (size_t n = 0; n < time.size(); ++n) {
+        std::fprintf(hf, "%zu,%s", step[n], rust_display(time[n]).c_str());
         for (size_t k = 0; k < P; ++k)
-            std::fprintf(hf, ",%s,%s,%s", rust_display(tr.probe_u[n * P + k]).c_str(), rust_display(tr.probe_v[n * P + k]).c_str(),
-                         rust_display(tr.probe_a[n * P + k]).c_str());
+            std::fprintf(hf, ",%s,%s,%s", rust_display(probe_u[n * P + k]).c_str(), rust_display(probe_v[n * P + k]).c_str(),
+                         rust_display(probe_a[n * P + k]).c_str());
         std::fputs("\n", hf);
     }
     std::fclose(hf);
@@ -441,7 +460,9 @@ int main(int argc, char **argv)
     bool dry = false, recover = false;
     int modal_modes = 0, adapt = 0, refine_split = 1, topopt = 0, penal = 3, filter_passes = 1, field_cg = 0, transient_steps = 0;
     double rel = 0.0, density = 0.0, refine_fraction = 0.2, volume_fraction = 0.5, dt = 0.0, rayleigh_mass = 0.0, rayleigh_stiffness = 0.0;
-    bool transient = false;
+    bool transient = false, explicit_run = false;
+    int explicit_steps = 0, record_every = 1;
+    double dt_scale = 0.0;
     std::vector<std::int32_t> probes;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -451,6 +472,9 @@ int main(int argc, char **argv)
         else if (a == "--density" && i + 1 < argc) density = std::atof(argv[++i]);
         else if (a == "--transient" && i + 1 < argc) transient = true, transient_steps = std::atoi(argv[++i]);
         else if (a == "--dt" && i + 1 < argc) dt = std::atof(argv[++i]);
+        else if (a == "--explicit" && i + 1 < argc) explicit_run = true, explicit_steps = std::atoi(argv[++i]);
+        else if (a == "--dt-scale" && i + 1 < argc) dt_scale = std::atof(argv[++i]);
+        else if (a == "--record-every" && i + 1 < argc) record_every = std::atoi(argv[++i]);
         else if (a == "--probe" && i + 1 < argc) probes.push_back((std::int32_t)std::atoi(argv[++i]));
         else if (a == "--rayleigh" && i + 1 < argc) {
             const std::string pair = argv[++i];
@@ -475,13 +499,18 @@ int main(int argc, char **argv)
         else die({MagnetiteError::Input, "Unrecognized argument " + a});
     }
     if (input.empty() || mesh.empty()) {
-        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery] [--modal P --density RHO] [--transient STEPS --dt DT --density RHO [--rayleigh A,E] [--probe DOF]...] [--adapt R [--refine-fraction T] [--refine-split 1|3]] [--topopt ITERS [--volume-fraction F] [--penal P] [--filter-passes K] [--field-cg 0..3]]\n");
+        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery] [--modal P --density RHO] [--transient STEPS --dt DT --density RHO [--rayleigh A,E] [--probe DOF]...] [--explicit STEPS --density RHO [--dt DT | --dt-scale S] [--rayleigh A,E] [--probe DOF]... [--record-every K]] [--adapt R [--refine-fraction T] [--refine-split 1|3]] [--topopt ITERS [--volume-fraction F] [--penal P] [--filter-passes K] [--field-cg 0..3]]\n");
         return 2;
     }
     if (modal_modes < 0 || (modal_modes > 0 && !(density > 0.0))) die({MagnetiteError::Input, "--modal P needs P >= 1 and --density RHO > 0"});
     if (transient && (transient_steps < 1 || !(dt > 0.0) || !(density > 0.0) || rayleigh_mass < 0.0 || rayleigh_stiffness < 0.0))
         die({MagnetiteError::Input, "--transient STEPS needs STEPS >= 1, --dt DT > 0, --density RHO > 0 and --rayleigh A,E >= 0"});
-    if (!transient && (dt != 0.0 || !probes.empty() || rayleigh_mass != 0.0 || rayleigh_stiffness != 0.0))
+    if (explicit_run && (explicit_steps < 1 || dt < 0.0 || dt_scale < 0.0 || (dt > 0.0 && dt_scale > 0.0) || !(density > 0.0) || rayleigh_mass < 0.0 ||
+                         rayleigh_stiffness < 0.0 || record_every < 1))
+        die({MagnetiteError::Input, "--explicit STEPS needs STEPS >= 1, --density RHO > 0, --dt DT > 0 or --dt-scale S > 0 (not both), --rayleigh A,E >= 0 and --record-every K >= 1"});
+    if (explicit_run && transient) die({MagnetiteError::Input, "--explicit and --transient share --dt, --rayleigh and --probe: one of them at a time"});
+    if (!explicit_run && (dt_scale != 0.0 || record_every != 1)) die({MagnetiteError::Input, "--dt-scale and --record-every need --explicit STEPS"});
+    if (!transient && !explicit_run && (dt != 0.0 || !probes.empty() || rayleigh_mass != 0.0 || rayleigh_stiffness != 0.0))
         die({MagnetiteError::Input, "--dt, --rayleigh and --probe need --transient STEPS"});
     if (adapt < 0 || !(refine_fraction > 0.0 && refine_fraction <= 1.0) || (refine_split != 1 && refine_split != 3))
         die({MagnetiteError::Input, "--adapt R needs R >= 0, --refine-fraction T in (0, 1] and --refine-split 1 or 3"});
@@ -489,6 +518,7 @@ int main(int argc, char **argv)
         die({MagnetiteError::Input, "--topopt ITERS needs ITERS >= 0, --volume-fraction F in (0, 1], --penal 1..8 and --filter-passes 0..8"});
     if (field_cg < 0 || field_cg > 3 || (field_cg != 0 && topopt == 0))
         die({MagnetiteError::Input, "--field-cg K needs K in 0..3 (0 CSR phase, 1 plain, 2 Jacobi, 3 block-Jacobi on K's block rows) and --topopt"});
+    if (explicit_run && adapt > 0) die({MagnetiteError::Input, "--explicit steps the mesh as given: not together with --adapt"});
     if (transient && adapt > 0) die({MagnetiteError::Input, "--transient steps the mesh as given: not together with --adapt"});
     if (topopt > 0 && adapt > 0) die({MagnetiteError::Input, "--topopt designs on the mesh as given: not together with --adapt"});
     // mesher::run (mesher.rs:939-974) minus geometry parsing and the gmsh subprocess
@@ -525,6 +555,10 @@ int main(int argc, char **argv)
         if (transient)
             std::printf("dry-run: transient steps %d dt %s density %s rayleigh %s,%s probes %zu\n", transient_steps, rust_display(dt).c_str(),
                         rust_display(density).c_str(), rust_display(rayleigh_mass).c_str(), rust_display(rayleigh_stiffness).c_str(), probes.size());
+        if (explicit_run)
+            std::printf("dry-run: explicit steps %d dt %s dt_scale %s density %s rayleigh %s,%s probes %zu record_every %d\n", explicit_steps,
+                        rust_display(dt).c_str(), rust_display(dt_scale).c_str(), rust_display(density).c_str(), rust_display(rayleigh_mass).c_str(),
+                        rust_display(rayleigh_stiffness).c_str(), probes.size(), record_every);
         return 0;
     }
     // solver::run (main.rs:64)
@@ -535,7 +569,7 @@ int main(int argc, char **argv)
         opt.stop_mode = MAG_STOP_REL;
         opt.tol = rel;
     }
-    std::vector<Node> posed = recover || modal_modes > 0 || topopt > 0 || transient ? nodes : std::vector<Node>();  // (run() fills every value in)
+    std::vector<Node> posed = recover || modal_modes > 0 || topopt > 0 || transient || explicit_run ? nodes : std::vector<Node>();  // (run() fills every value in)
     if (adapt > 0) {
         RefineSpec spec;
         spec.theta = refine_fraction;
@@ -594,6 +628,31 @@ int main(int argc, char **argv)
         for (size_t n = 0; n < tr.iterations.size(); ++n)
             std::printf("info: step %zu t %s iterations %d\n", n, rust_display((double)n * dt).c_str(), (int)tr.iterations[n]);
         history_output(tr, probes, dt, history_name(nodes_out));
+    }
+    if (explicit_run) {
+        // The pass needs every element counter-clockwise, as the modal analysis does: the elements go in by their true sign.
+        std::vector<Element> ccw = elements;
+        for (Element &e : ccw)
+            if (solver::compute_element_area(e, posed) < 0.0) std::swap(e.nodes[0], e.nodes[2]);
+        opt.verbose = 0;
+        ExplicitSpec spec;
+        spec.steps = explicit_steps;
+        spec.dt = dt;
+        if (dt_scale > 0.0) spec.dt_scale = dt_scale;
+        spec.density = density;
+        spec.rayleigh_mass = rayleigh_mass;
+        spec.rayleigh_stiffness = rayleigh_stiffness;
+        spec.probes = probes;
+        spec.record_every = record_every;
+        Explicit ex;
+        if (Result err = solver::run_explicit(posed, ccw, meta, spec, ex, &opt)) die(*err);
+        std::printf("info: explicit dt %s (bound %s)\n", rust_display(ex.dt).c_str(), rust_display(ex.dt_bound).c_str());
+        std::vector<std::size_t> step;
+        for (size_t n = 0; n < ex.time.size(); ++n) {
+            step.push_back(n * (size_t)ex.record_every);
+            std::printf("info: step %zu t %s\n", step[n], rust_display(ex.time[n]).c_str());
+        }
+        history_output(ex.time, step, ex.probe_u, ex.probe_v, ex.probe_a, probes, history_name(nodes_out));
     }
     if (topopt > 0) {
         // The density design needs every element counter-clockwise, as the modal analysis does: the elements go in by their true sign.
