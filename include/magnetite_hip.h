@@ -691,9 +691,39 @@ int mag_assemble_effective(mag_ctx *ctx, double c_K, double c_M, double density,
  *   precision = 1.  After the first device work: a probe outside [0, 2N), an element of signed area <= 0, records beyond device
  *   memory, the final state not finite.
  * Out of scope: several steps in one launch; a graph replay of the steps; time-varying supports; fields, variants and ranks; a
- *   sharper step estimate; element-wise step control, mass scaling, contact. */
+ *   sharper step estimate; element-wise step control, mass scaling, contact.
+ *
+ * kinematics = MAG_KIN_TOTAL_LAGRANGIAN: large rotations.  MAG_KIN_LINEAR (0, the default) is everything above, bit for bit.  With
+ *   MAG_KIN_TOTAL_LAGRANGIAN the step is the one above with K (ut + eta vt) replaced by the internal force f_int(ut) of a
+ *   St. Venant-Kirchhoff plane-stress material in the reference configuration.  For a triangle (a, b, c) with the reference edges
+ *   db = X_b - X_a, dc = X_c - X_a and the relative displacements ub = u_b - u_a, uc = u_c - u_a:
+ *     2A = db x dc;   H = grad u:   H11 = (dc.y ub.x - db.y uc.x) / 2A,   H12 = (db.x uc.x - dc.x ub.x) / 2A,
+ *                                   H21 = (dc.y ub.y - db.y uc.y) / 2A,   H22 = (db.x uc.y - dc.x ub.y) / 2A;   F = I + H;
+ *     Green-Lagrange strain  Exx = H11 + (H11^2 + H21^2) / 2,  Eyy = H22 + (H12^2 + H22^2) / 2,  Gxy = H12 + H21 + H11 H12 + H21 H22;
+ *     second Piola-Kirchhoff stress, c = E / (1 - nu^2):  Sxx = c (Exx + nu Eyy),  Syy = c (Eyy + nu Exx),  Sxy = c (1 - nu) / 2 Gxy;
+ *     first Piola-Kirchhoff stress P = F S;  the force on corner a is (t / 2) P (db.y - dc.y, dc.x - db.x)^T;
+ *     the element's strain energy is W_e = A t (Sxx Exx + Syy Eyy + Sxy Gxy) / 2.
+ *   Its linearisation at u = 0 is K, and a rigid motion u = (R - I)(X - X_c) + d gives zero force: a part may swing and whip.
+ *     a' = (amplitude[n+1] f - alpha m vt - f_int(ut))_F / ((1 + dt alpha / 2) m).  Reactions: f_int(u) on P, amplitude[n] f on F.
+ *     Energies: T = 1/2 v.mv, W = the sum of W_e, P = amplitude[n] f.u_F.  Supports, loads, the start (the step with dt = 0),
+ *     records, resume and results are those above; either kinematics may resume the other's state, and a resumed run uses the
+ *     kinematics it is given.
+ *   rayleigh_stiffness must be 0 (MAG_ERR_BAD_ARGS otherwise): initial-stiffness damping is not objective.
+ *   dt_bound stays the linear bound at the reference configuration, and dt = 0 asks for dt_scale times it.  Tension stiffens the
+ *     part and shrinks the true limit: the caller lowers dt_scale for it.  The finite check on the final state is the safety net.
+ *   An element with det F <= 0 is inverted.  It is no error: the run completes, info[7] is 0 and mag_last_error is unchanged.
+ *   A step is ONE launch where the context has tile-local tables, and reads no matrix: the ring walk of the matrix-free operator
+ *     with the force above per triangle.  A node's sum runs in its ring's order, which depends on tile_nodes: the same bits for
+ *     every grid, a repeat and a resumed run, not across tile sizes.  Without the tables a step is four launches (info[2] = 0).
+ *   Out of scope: other materials (neo-Hooke, plasticity); stiffness-proportional damping; an updated step bound during the run;
+ *     follower loads; contact; the implicit pass with a tangent; fields, variants and ranks; several steps per launch.
+ * mag_internal_force: f_out = f_int(u) for all 2N DOFs in caller numbering (u, f_out: 2N doubles in `memory`), scalars_out[0] =
+ *   W(u), scalars_out[1] = 1 if some element has det F <= 0, else 0 (written on the host).  The residual of a caller's own
+ *   dynamic relaxation or Newton loop.  Needs an upload only and changes no result of the context; mag_run_explicit's refusals
+ *   and wording (null u, f_out or scalars_out: MAG_ERR_BAD_ARGS). */
+enum { MAG_KIN_LINEAR = 0, MAG_KIN_TOTAL_LAGRANGIAN = 1 };
 typedef struct mag_explicit_options {
-    int32_t steps, resume, energies, record_every, snapshot_every, num_probes, memory, reserved; /* record_every 0: 1 */
+    int32_t steps, resume, energies, record_every, snapshot_every, num_probes, memory, kinematics; /* record_every 0: 1 */
     double dt, dt_scale, density, rayleigh_mass, rayleigh_stiffness;  /* dt 0: dt_scale * dt_bound; dt_scale 0: 0.9 */
     const double *amplitude, *u0, *v0;                                /* [steps + 1], 2N, 2N; NULL: ones, zero, zero */
     const int32_t *probes;                                            /* NULL: none */
@@ -702,8 +732,10 @@ void mag_default_explicit_options(mag_explicit_options *opt); /* record_every 1,
 int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *opt);
 /* after mag_run_explicit, mag_get_transient_info gives: info[0] steps done, [1] 6 (explicit), [2] 1 fused / 0 unfused, [3] step
  * launches (fused: steps + 1 with the start, steps in a resumed run; unfused: four per step), [4] record_every, [5] snapshots
- * kept, [6] resumed, [7] 1 */
+ * kept, [6] resumed, [7] 1.  With MAG_KIN_TOTAL_LAGRANGIAN: [1] 7, [7] 0 when an element was inverted (det F <= 0) in some
+ * evaluation of the force, 1 otherwise */
 int mag_explicit_dt(mag_ctx *ctx, double density, double rayleigh_stiffness, double out[4]);
+int mag_internal_force(mag_ctx *ctx, const double *u, double *f_out, double scalars_out[2], int32_t memory);
 
 /* ---- adaptive mesh refinement: longest-edge bisection with conformity closure (Rivara) of the uploaded mesh, on the device ----
  * What acts on the ZZ indicator of mag_run_stress: solve -> mag_run_stress -> mag_run_refine -> mag_upload_refined -> solve, the

@@ -182,8 +182,9 @@ struct Transient {
 
 // The options of solver::run_explicit (include/magnetite_hip.h, mag_explicit_options); dt 0: dt_scale times the device's bound.
 // amplitude: steps + 1 values or empty (ones); u0, v0: 2N values in the order of `nodes` or empty (zero); probes: 2 * node + axis.
+// kinematics: MAG_KIN_LINEAR, or MAG_KIN_TOTAL_LAGRANGIAN for large rotations (rayleigh_stiffness must then be 0).
 struct ExplicitSpec {
-    std::int32_t steps = 0, record_every = 1, snapshot_every = 0;
+    std::int32_t steps = 0, record_every = 1, snapshot_every = 0, kinematics = MAG_KIN_LINEAR;
     bool energies = false;
     double dt = 0.0, dt_scale = 0.9, density = 0.0, rayleigh_mass = 0.0, rayleigh_stiffness = 0.0;
     std::vector<double> amplitude, u0, v0;
@@ -192,11 +193,20 @@ struct ExplicitSpec {
 
 // What solver::run_explicit returns: the outputs of mag_download_transient after an explicit run -- the final state and its
 // reactions, the rows of steps 0, record_every, ... (probes, energies, `time`), the snapshots -- the step used, its bound and
-// mag_get_transient_info's words by name.
+// mag_get_transient_info's words by name.  inverted: an element had det F <= 0 in a total-Lagrangian run (no error).
 struct Explicit {
     std::vector<double> u, v, a, f, probe_u, probe_v, probe_a, energies, snapshots, time;
     double t_start = 0, t_end = 0, dt = 0, dt_bound = 0;
-    std::int32_t steps = 0, fused = 0, step_launches = 0, record_every = 0, snapshots_kept = 0, resumed = 0;
+    std::int32_t steps = 0, method = 0, fused = 0, step_launches = 0, record_every = 0, snapshots_kept = 0, resumed = 0;
+    bool inverted = false;
+};
+
+// What solver::internal_force returns (mag_internal_force): f_int(u) in the order of `nodes`, the strain energy W(u), and whether
+// some element has det F <= 0.
+struct InternalForce {
+    std::vector<double> f;
+    double energy = 0;
+    bool inverted = false;
 };
 
 // What solver::explicit_dt returns (mag_explicit_dt)
@@ -847,6 +857,7 @@ inline Result run_explicit(const std::vector<Node> &nodes, const std::vector<Ele
     o.snapshot_every = spec.snapshot_every;
     o.num_probes = (std::int32_t)spec.probes.size();
     o.memory = MAG_MEM_HOST;
+    o.kinematics = spec.kinematics;
     o.dt = spec.dt;
     o.dt_scale = spec.dt_scale;
     o.density = spec.density;
@@ -885,6 +896,8 @@ inline Result run_explicit(const std::vector<Node> &nodes, const std::vector<Ele
     out.dt = d.scalars[2];
     out.dt_bound = d.scalars[3];
     out.steps = info[0];
+    out.method = info[1];
+    out.inverted = info[1] == 7 && info[7] == 0;
     out.fused = info[2];
     out.step_launches = info[3];
     out.record_every = info[4];
@@ -892,6 +905,32 @@ inline Result run_explicit(const std::vector<Node> &nodes, const std::vector<Ele
     out.resumed = info[6];
     out.time.resize(rows);
     for (std::size_t k = 0; k < rows; ++k) out.time[k] = out.t_start + out.dt * (double)((std::size_t)out.record_every * k);
+    mag_destroy(ctx);
+    return std::nullopt;
+}
+
+// The total-Lagrangian internal force of the part at the displacement u (2N values in the order of `nodes`): the residual of a
+// caller's own dynamic relaxation or Newton loop (mag_internal_force).
+inline Result internal_force(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                             const std::vector<double> &u, InternalForce &out, const mag_options *options = nullptr)
+{
+    const std::size_t N = nodes.size();
+    std::vector<double> xy, u_in(2 * N), f_in(2 * N);
+    std::vector<std::uint8_t> u_known;
+    std::vector<std::int32_t> conn;
+    if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
+    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
+    if (u.size() != 2 * N) return detail::solver_error("u has another length than 2 N");
+    mag_ctx *ctx = mag_create(options);
+    if (!ctx) return detail::solver_error("mag_create failed");
+    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
+    if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    out = InternalForce{};
+    out.f.resize(2 * N);
+    double scalars[2] = {};
+    if (mag_internal_force(ctx, u.data(), out.f.data(), scalars, MAG_MEM_HOST) != MAG_OK) return detail::fail_and_destroy(ctx);
+    out.energy = scalars[0];
+    out.inverted = scalars[1] != 0.0;
     mag_destroy(ctx);
     return std::nullopt;
 }

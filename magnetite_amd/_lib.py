@@ -20,6 +20,7 @@ MAG_OP_MATRIX_FREE, MAG_OP_CSR = 0, 1
 MAG_FIELD_CG_PLAIN, MAG_FIELD_CG_JACOBI, MAG_FIELD_CG_BLOCK_JACOBI = 1, 2, 3
 MAG_TERM_NONE, MAG_TERM_TARGET_COST, MAG_TERM_MAX_ITERS, MAG_TERM_BREAKDOWN = 0, 1, 2, 3
 MAG_MEM_HOST, MAG_MEM_DEVICE = 0, 1
+MAG_KIN_LINEAR, MAG_KIN_TOTAL_LAGRANGIAN = 0, 1
 MAG_SET_RUN, MAG_SET_CASES, MAG_SET_VARIANTS = 0, 1, 2
 MAG_OBJ_DISP_LSQ, MAG_OBJ_STRESS_PNORM = 0, 1
 MAG_REFINE_MARKS, MAG_REFINE_MAX_FRACTION, MAG_REFINE_TOP_FRACTION = 0, 1, 2
@@ -41,7 +42,7 @@ SYMBOLS = [
     "mag_run_stress", "mag_download_stress",
     "mag_run_modal", "mag_download_modal", "mag_get_modal_info", "mag_get_modal_stats", "mag_apply_mass",
     "mag_default_transient_options", "mag_run_transient", "mag_download_transient", "mag_get_transient_info", "mag_assemble_effective",
-    "mag_default_explicit_options", "mag_run_explicit", "mag_explicit_dt",
+    "mag_default_explicit_options", "mag_run_explicit", "mag_explicit_dt", "mag_internal_force",
     "mag_run_refine", "mag_get_refine_info", "mag_download_refine", "mag_upload_refined",
     "mag_set_element_scale", "mag_design_init", "mag_design_step", "mag_get_design_info", "mag_download_design",
     "mag_comm_get_unique_id", "mag_comm_init_rccl", "mag_comm_query", "mag_comm_init_callback", "mag_comm_set_window", "mag_comm_inbox_create", "mag_comm_inbox_open",
@@ -129,7 +130,7 @@ class TransientOptions(C.Structure):
 
 class ExplicitOptions(C.Structure):
     _fields_ = [("steps", C.c_int32), ("resume", C.c_int32), ("energies", C.c_int32), ("record_every", C.c_int32),
-                ("snapshot_every", C.c_int32), ("num_probes", C.c_int32), ("memory", C.c_int32), ("reserved", C.c_int32),
+                ("snapshot_every", C.c_int32), ("num_probes", C.c_int32), ("memory", C.c_int32), ("kinematics", C.c_int32),
                 ("dt", C.c_double), ("dt_scale", C.c_double), ("density", C.c_double), ("rayleigh_mass", C.c_double),
                 ("rayleigh_stiffness", C.c_double),
                 ("amplitude", C.c_void_p), ("u0", C.c_void_p), ("v0", C.c_void_p), ("probes", C.c_void_p)]
@@ -266,6 +267,8 @@ def lib():
         L.mag_default_explicit_options.restype = None
         L.mag_run_explicit.argtypes = [vp, C.POINTER(ExplicitOptions)]
         L.mag_explicit_dt.argtypes = [vp, C.c_double, C.c_double, dp]
+    if hasattr(L, "mag_internal_force"):  # (likewise: scripts/explicit_tl_probe.py)
+        L.mag_internal_force.argtypes = [vp, dp, dp, dp, C.c_int32]
     if hasattr(L, "mag_run_refine"):  # (likewise: scripts/refine_probe.py)
         L.mag_run_refine.argtypes = [vp, C.POINTER(RefineOptions)]
         L.mag_get_refine_info.argtypes = [vp, C.POINTER(C.c_int64)]

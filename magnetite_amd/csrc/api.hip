@@ -34,6 +34,7 @@
 #include "sens.h"
 #include "transient.h"
 #include "explicit.h"
+#include "explicit_tl.h"
 
 using magk::CgState;
 
@@ -347,6 +348,8 @@ struct mag_ctx {
     // a step reads one and writes the other), the node masses, u_in and f_in in Hilbert order, the bound's partials and result,
     // the finite flag
     DevBuf ex_rec[2], ex_mass, ex_uin, ex_f, ex_part, ex_out;
+    // mag_internal_force's own buffers (it changes no result of the context): u, f_int(u), the energy's partials, W
+    DevBuf tl_u, tl_f, tl_part, tl_out;
     int64_t tr_rows = 0;
     double tr_dt = 0.0, tr_dt_bound = 0.0;
 
@@ -4751,6 +4754,12 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
     if (!nonneg_finite(o->rayleigh_mass)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: rayleigh_mass %g is negative or not finite", fn, o->rayleigh_mass);
     if (!nonneg_finite(o->rayleigh_stiffness))
         return fail(ctx, MAG_ERR_BAD_ARGS, "%s: rayleigh_stiffness %g is negative or not finite", fn, o->rayleigh_stiffness);
+    if (o->kinematics != MAG_KIN_LINEAR && o->kinematics != MAG_KIN_TOTAL_LAGRANGIAN)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: kinematics = %d is neither MAG_KIN_LINEAR nor MAG_KIN_TOTAL_LAGRANGIAN", fn, (int)o->kinematics);
+    if (o->kinematics == MAG_KIN_TOTAL_LAGRANGIAN && o->rayleigh_stiffness != 0.0)
+        return fail(ctx, MAG_ERR_BAD_ARGS,
+                    "%s: rayleigh_stiffness %g must be 0 with kinematics = MAG_KIN_TOTAL_LAGRANGIAN (initial-stiffness damping is not objective)", fn,
+                    o->rayleigh_stiffness);
     if (o->record_every < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: record_every = %d is negative", fn, (int)o->record_every);
     if (o->snapshot_every < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: snapshot_every = %d is negative", fn, (int)o->snapshot_every);
     if (o->num_probes < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: num_probes = %d is negative", fn, (int)o->num_probes);
@@ -4763,7 +4772,7 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
     if (int rc = transient_refused(ctx, fn)) return rc;
     if (int rc = enter(ctx)) return rc;
 
-    const bool resume = o->resume != 0, energies = o->energies != 0;
+    const bool resume = o->resume != 0, energies = o->energies != 0, tl = o->kinematics == MAG_KIN_TOTAL_LAGRANGIAN;
     const int32_t steps = o->steps, np = o->num_probes, se = o->snapshot_every, re = o->record_every > 0 ? o->record_every : 1;
     const double alpha = o->rayleigh_mass, eta = o->rayleigh_stiffness;
     const double t_start = resume ? ctx->tr_t1 : 0.0;
@@ -4868,12 +4877,45 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
     double *d_rhs = ctx->tr_rhs.as<double>(), *d_energy = ctx->tr_energy.as<double>(), *d_snap = ctx->tr_snap.as<double>();
     const double *d_f = ctx->fin.as<double>(), *d_k = ctx->kval.as<double>(), *d_m = ctx->tr_mval.as<double>();
 
+    // ---- total-Lagrangian kinematics (explicit_tl.hip): the mesh as the force kernel reads it, the inverted-element flag (the
+    // probes' word is done with), the fused step's inputs in Hilbert order; no table and no values: the step reads no matrix
+    magk::TlMesh tlm = {};
+    magk::ExplicitTlParams Q = {};
+    int32_t *d_inverted = (int32_t *)(d_bad + 1);
+    if (tl) {
+        tlm.N = N, tlm.E = ctx->E;
+        tlm.perm = ctx->perm.as<uint32_t>(), tlm.inc_off = ctx->inc_off.as<int32_t>(), tlm.inc = ctx->inc.as<uint32_t>();
+        tlm.conn = ctx->conn.as<int32_t>(), tlm.xy = ctx->xy.as<double2>();
+        set_material(ctx, tlm);
+        HIPCHK(hipMemsetAsync(d_inverted, 0, 4, s));
+    }
+
     // ---- the fused step's table, values (unmasked: prescribed displacements enter through K ut) and inputs in Hilbert order
     magk::ExplicitParams P = {};
     int32_t grid = 1;
     int cur = 0;
     magk::ExRec *rec[2] = {nullptr, nullptr};
-    if (fused) {
+    if (fused && tl) {
+        for (DevBuf &b : ctx->ex_rec) HIPCHK(b.reserve(sizeof(magk::ExRec) * (size_t)N));
+        HIPCHK(ctx->ex_mass.reserve(8 * (size_t)N));
+        HIPCHK(ctx->ex_uin.reserve(vb));
+        HIPCHK(ctx->ex_f.reserve(vb));
+        magk::explicit_inputs(pat, ctx->perm.as<uint32_t>(), d_m, st.u_in, d_f, ctx->ex_mass.as<double>(), ctx->ex_uin.as<double2>(),
+                              ctx->ex_f.as<double2>(), s);
+        HIPCHK(hipGetLastError());
+        rec[0] = ctx->ex_rec[0].as<magk::ExRec>();
+        rec[1] = ctx->ex_rec[1].as<magk::ExRec>();
+        Q.N = N, Q.T = ctx->T, Q.cap = ctx->cap;
+        Q.maskP = ctx->maskP.as<uint8_t>();
+        Q.xyP = ctx->xyP.as<double2>(), Q.halo_xy = ctx->halo_xy.as<double2>();
+        Q.tile_deg = ctx->tile_rdeg.as<int32_t>(), Q.tile_off = ctx->tile_off.as<int64_t>(), Q.ell16 = ctx->ell.as<uint32_t>();
+        Q.tile_hoff = ctx->tile_hoff.as<int32_t>(), Q.halo_g = ctx->halo_g.as<int32_t>();
+        Q.uinP = ctx->ex_uin.as<double2>(), Q.fP = ctx->ex_f.as<double2>(), Q.massP = ctx->ex_mass.as<double>();
+        Q.amplitude = d_amp, Q.alpha = alpha;
+        set_material(ctx, Q);
+        Q.inverted = d_inverted;
+        grid = magk::explicit_tl_grid(ctx->B, ctx->cap, ctx->T);
+    } else if (fused) {
         FieldTable tab{ctx->tr_width, ctx->tr_meta, ctx->tr_slot, ctx->tr_src, ctx->tr_val};
         if (int rc = build_field_table(ctx, tab)) return rc;
         magk::field_gather(ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(), d_k, ctx->tr_zero.as<uint8_t>(), ctx->halo_g.as<int32_t>(),
@@ -4900,6 +4942,22 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
     bool expanded = true; // (tr_u, tr_v, tr_a hold the current state)
     // one step of h (the start: h = 0) under amplitude[amp_at]
     auto step = [&](double h, int64_t amp_at) {
+        if (fused && tl) {
+            Q.in = rec[cur], Q.out = rec[cur ^ 1], Q.dt = h, Q.amp_at = amp_at;
+            magk::explicit_tl_step(Q, ctx->B, grid, s);
+            cur ^= 1;
+            expanded = false;
+            launches += 1;
+            return;
+        }
+        if (tl) {
+            magk::newmark_predict(st, h, 0.0, 0.5, s);
+            magk::tl_force(tlm, st.ut, d_rhs, d_inverted, nullptr, nullptr, s);
+            magk::tl_divide(pat, d_m, st.known, d_f, d_amp, amp_at, d_rhs, st.vt, alpha, 1.0 + 0.5 * h * alpha, st.a, s);
+            magk::newmark_correct(st_quiet, h, 0.0, 0.5, 0, nullptr, s);
+            launches += 4;
+            return;
+        }
         if (fused) {
             P.in = rec[cur], P.out = rec[cur ^ 1], P.dt = h, P.amp_at = amp_at;
             magk::explicit_step(P, ctx->B, grid, s);
@@ -4932,7 +4990,9 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
         double *snap = snap_due ? d_snap + (size_t)(n / se) * (size_t)n2 : nullptr;
         const int64_t row = n / re;
         magk::newmark_record(row_due ? st : st_quiet, row, snap, s);
-        if (row_due && energies) {
+        if (row_due && energies && tl) {
+            magk::tl_energies(tlm, pat, d_m, st.known, st.u, st.v, d_f, d_amp, n, d_inverted, ctx->tr_part.as<double>(), d_energy + 3 * row, s);
+        } else if (row_due && energies) {
             magk::PatternApply e = {};
             e.kval = d_k, e.mval = d_m, e.xa = st.u, e.ca = 1.0, e.xc = st.v, e.cc = 1.0, e.y = d_rhs;
             e.ku = ctx->tr_ku.as<double>(), e.mv = ctx->tr_mv.as<double>();
@@ -4960,30 +5020,34 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
     int32_t *d_flag = (int32_t *)(d_bad); // (the checks' words are done with)
     HIPCHK(hipMemsetAsync(d_flag, 0, 4, s));
     magk::explicit_finite(st.u, st.v, st.a, n2, d_flag, s);
-    {
+    if (tl) {
+        magk::tl_force(tlm, st.u, d_rhs, d_inverted, nullptr, nullptr, s);
+        magk::tl_reactions(st.known, d_f, d_amp, steps, d_rhs, n2, ctx->tr_f.as<double>(), s);
+    } else {
         magk::PatternApply r = {};
         r.kval = d_k, r.mval = d_m, r.xa = st.u, r.ca = 1.0, r.xb = eta != 0.0 ? st.v : nullptr, r.cb = eta;
         r.xc = st.a, r.cc = 1.0, r.xd = alpha != 0.0 ? st.v : nullptr, r.cd = alpha;
         r.kind = 2, r.known = st.known, r.f = d_f, r.amplitude = d_amp, r.amp_at = steps, r.y = ctx->tr_f.as<double>();
         magk::pattern_apply(pat, r, s);
     }
-    int32_t not_finite = 0;
-    HIPCHK(hipMemcpyAsync(&not_finite, d_flag, 4, hipMemcpyDeviceToHost, s));
+    int32_t flags[3] = {0, 0, 0}; // (the finite flag, the rest of its word, the inverted-element flag)
+    HIPCHK(hipMemcpyAsync(flags, d_flag, tl ? 12 : 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
+    const int32_t not_finite = flags[0], inverted = tl ? flags[2] : 0;
     if (not_finite)
         return fail(ctx, MAG_ERR_NOT_CONVERGED, "%s: the state after %d steps is not finite: dt = %g against dt_bound = %g (the step is unstable)", fn,
                     (int)steps, dt, dt_bound);
 
     int32_t *info = ctx->tr_info;
     info[0] = steps;
-    info[1] = 6;
+    info[1] = tl ? 7 : 6;
     info[2] = fused ? 1 : 0;
     info[3] = (int32_t)std::min<long long>(launches, INT32_MAX);
     info[4] = re;
     info[5] = (int32_t)snaps;
     info[6] = resume ? 1 : 0;
-    info[7] = 1;
+    info[7] = inverted ? 0 : 1;
     ctx->tr_steps = steps;
     ctx->tr_num_probes = np;
     ctx->tr_snaps = (int32_t)snaps;
@@ -4996,6 +5060,55 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
     ctx->tr_dt = dt;
     ctx->tr_dt_bound = dt_bound;
     ctx->tr_have = true;
+    return MAG_OK;
+}
+
+int mag_internal_force(mag_ctx *ctx, const double *u, double *f_out, double scalars_out[2], int32_t memory)
+{
+    const char *fn = "mag_internal_force";
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!u) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null u", fn);
+    if (!f_out) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null f_out", fn);
+    if (!scalars_out) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null scalars_out", fn);
+    if (int rc = memory_refused(ctx, memory, fn)) return rc;
+    if (int rc = transient_refused(ctx, fn)) return rc;
+    if (int rc = enter(ctx)) return rc;
+    if (int rc = ensure_order(ctx)) return rc;
+    hipStream_t s = ctx->stream;
+    const int64_t N = ctx->N;
+    const size_t vb = 16 * (size_t)N;
+    HIPCHK(ctx->tl_u.reserve(vb));
+    HIPCHK(ctx->tl_f.reserve(vb));
+    HIPCHK(ctx->tl_part.reserve(8 * (size_t)magk::kSensBlocks));
+    HIPCHK(ctx->tl_out.reserve(32)); // W, the first element of signed area <= 0, the inverted flag
+    double *d_w = ctx->tl_out.as<double>();
+    unsigned long long *d_bad = (unsigned long long *)(d_w + 1);
+    int32_t *d_inverted = (int32_t *)(d_w + 2);
+    HIPCHK(hipMemsetAsync(d_inverted, 0, 4, s));
+    HIPCHK(hipMemcpyAsync(ctx->tl_u.p, u, vb, memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    magk::orientation(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), N, ctx->E, d_bad, s);
+    magk::TlMesh m = {};
+    m.N = N, m.E = ctx->E;
+    m.perm = ctx->perm.as<uint32_t>(), m.inc_off = ctx->inc_off.as<int32_t>(), m.inc = ctx->inc.as<uint32_t>();
+    m.conn = ctx->conn.as<int32_t>(), m.xy = ctx->xy.as<double2>();
+    set_material(ctx, m);
+    magk::tl_force(m, ctx->tl_u.as<double>(), ctx->tl_f.as<double>(), d_inverted, ctx->tl_part.as<double>(), d_w, s);
+    HIPCHK(hipGetLastError());
+    struct {
+        double w;
+        unsigned long long bad;
+        int32_t inverted, pad;
+    } h = {0.0, ~0ull, 0, 0};
+    HIPCHK(hipMemcpyAsync(&h, d_w, 24, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (h.bad != ~0ull)
+        return fail(ctx, MAG_ERR_BAD_ARGS,
+                    "%s: element %lld has a signed area <= 0 (the stiffness carries the signed area: the pass needs counter-clockwise elements)", fn,
+                    (long long)h.bad);
+    HIPCHK(hipMemcpyAsync(f_out, ctx->tl_f.p, vb, memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    scalars_out[0] = h.w;
+    scalars_out[1] = h.inverted ? 1.0 : 0.0;
     return MAG_OK;
 }
 

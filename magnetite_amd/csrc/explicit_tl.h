@@ -1,0 +1,132 @@
+// Internal: launch wrappers of explicit_tl.hip (explicit dynamics with large rotations, mag_run_explicit with kinematics =
+// MAG_KIN_TOTAL_LAGRANGIAN, and mag_internal_force): the total-Lagrangian internal force of a St. Venant-Kirchhoff plane-stress
+// material in the reference configuration, as a fused central-difference step on the tile-local ring tables and as a kernel in
+// caller numbering over the incidence lists.
+//
+// The method.  The step is explicit.h's with K (ut + eta vt) replaced by f_int(ut) (eta must be 0: initial-stiffness damping is
+// not objective).  For a triangle (a, b, c) with the reference edges db = X_b - X_a, dc = X_c - X_a and the relative displacements
+// ub = u_b - u_a, uc = u_c - u_a:
+//   2A = db x dc
+//   H = grad u:   H11 = (dc.y ub.x - db.y uc.x) / 2A    H12 = (db.x uc.x - dc.x ub.x) / 2A
+//                 H21 = (dc.y ub.y - db.y uc.y) / 2A    H22 = (db.x uc.y - dc.x ub.y) / 2A
+//   F = I + H
+//   Green-Lagrange strain:   Exx = H11 + (H11^2 + H21^2) / 2,   Eyy = H22 + (H12^2 + H22^2) / 2,
+//                            Gxy = H12 + H21 + H11 H12 + H21 H22
+//   second Piola-Kirchhoff stress, c = E / (1 - nu^2):   Sxx = c (Exx + nu Eyy),   Syy = c (Eyy + nu Exx),   Sxy = c (1 - nu) / 2 Gxy
+//     (the constants c0 = c t / 2, nu, h = (1 - nu) / 2 that fan_force takes)
+//   first Piola-Kirchhoff stress P = F S;   the force on corner a is (t / 2) P (db.y - dc.y, dc.x - db.x)^T
+//   the element's strain energy is A t (Sxx Exx + Syy Eyy + Sxy Gxy) / 2
+// Without the quadratic terms of E and with F = I this is fan_force: the linearisation at u = 0 is the project's K, and a rigid
+// motion u = (R - I)(X - X_c) + d gives zero force.
+//   step:       a' = (amplitude[n+1] f - alpha m vt - f_int(ut))_F / ((1 + dt alpha / 2) m),   a'_P = 0
+//   reactions:  f_int(u) on P (a = v = 0 there), amplitude[n] f on F
+//   energies:   T = 1/2 v.mv,   W = sum over the elements of W_e,   P = amplitude[n] f.u_F
+// An element with det F <= 0 is inverted: the kernels raise an integer flag (one atomicOr behind the test) and go on.
+#pragma once
+#include <cstdint>
+
+#include <hip/hip_runtime.h>
+
+#include "cg_device.h"
+#include "explicit.h"
+
+namespace magk {
+
+// Green-Lagrange strain and the scaled stress of one triangle given relative to its corner a; s = S / c
+struct TlStrain {
+    double twoA, H11, H12, H21, H22, Exx, Eyy, Gxy, sx, sy, tq;
+};
+
+// (every multiply-add is written as the fma() it is: the unit is compiled -ffp-contract=off)
+__device__ inline TlStrain tl_strain(const double2 db, const double2 ub, const double2 dc, const double2 uc, double nu, double h, int32_t *inverted)
+{
+    TlStrain s;
+    s.twoA = fma(db.x, dc.y, -(dc.x * db.y));
+    const double r = ring_rcp<double>(s.twoA);
+    s.H11 = fma(dc.y, ub.x, -(db.y * uc.x)) * r;
+    s.H12 = fma(db.x, uc.x, -(dc.x * ub.x)) * r;
+    s.H21 = fma(dc.y, ub.y, -(db.y * uc.y)) * r;
+    s.H22 = fma(db.x, uc.y, -(dc.x * ub.y)) * r;
+    s.Exx = fma(0.5, fma(s.H11, s.H11, s.H21 * s.H21), s.H11);
+    s.Eyy = fma(0.5, fma(s.H12, s.H12, s.H22 * s.H22), s.H22);
+    s.Gxy = (s.H12 + s.H21) + fma(s.H11, s.H12, s.H21 * s.H22);
+    s.sx = fma(nu, s.Eyy, s.Exx);
+    s.sy = fma(nu, s.Exx, s.Eyy);
+    s.tq = h * s.Gxy;
+    const double det = fma(1.0 + s.H11, 1.0 + s.H22, -(s.H12 * s.H21));
+    if (det <= 0.0) atomicOr(inverted, 1);
+    return s;
+}
+
+// fan_force with the total-Lagrangian internal force: adds the force of the triangle (a, b, c) on corner a to (fx, fy)
+__device__ inline void fan_force_tl(const double2 db, const double2 ub, const double2 dc, const double2 uc, double c0, double nu, double h,
+                                    double &fx, double &fy, int32_t *inverted)
+{
+    const TlStrain s = tl_strain(db, ub, dc, uc, nu, h, inverted);
+    const double ba = db.y - dc.y, ga = dc.x - db.x;
+    const double qx = fma(ba, s.sx, ga * s.tq), qy = fma(ga, s.sy, ba * s.tq); // (S / c) (ba, ga)^T
+    const double px = qx + fma(s.H11, qx, s.H12 * qy), py = qy + fma(s.H21, qx, s.H22 * qy); // F times it
+    fx = fma(c0, px, fx);
+    fy = fma(c0, py, fy);
+}
+
+// W_e = A t S:E / 2 = (2A) c0 (sx Exx + sy Eyy + tq Gxy) / 2
+__device__ inline double tl_energy(const TlStrain &s, double c0)
+{
+    return (0.5 * s.twoA) * (c0 * fma(s.sx, s.Exx, fma(s.sy, s.Eyy, s.tq * s.Gxy)));
+}
+
+struct ExplicitTlParams {
+    int64_t N;
+    int32_t T, cap;
+    const uint8_t *maskP; // bit 0 / 1: prescribed ux / uy
+    const double2 *xyP, *halo_xy;
+    const int32_t *tile_deg; // ring words per row of the tile
+    const int64_t *tile_off;
+    const uint32_t *ell16; // the ring table (symbolic.hip, k_ring16)
+    const int32_t *tile_hoff, *halo_g;
+    const ExRec *in;
+    ExRec *out;
+    const double2 *uinP, *fP; // u_in and f_in, Hilbert order
+    const double *massP;      // the node masses, Hilbert order
+    const double *amplitude;
+    int64_t amp_at; // the step's load is amplitude[amp_at] f
+    double dt, alpha;
+    double c0, nu, h;
+    int32_t *inverted;
+};
+
+// workgroups of a step: all co-resident, capped by MAG_TUNE_GRID and by the tile count (as explicit_grid)
+int explicit_tl_grid(int32_t B, int32_t cap, int32_t tiles);
+// one time step, one launch: reads P.in, writes P.out.  The order of a node's sum is its ring's (a function of the mesh and the
+// tile size): the same bits for every grid, not across tile sizes
+void explicit_tl_step(const ExplicitTlParams &P, int32_t B, int32_t grid, hipStream_t s);
+
+// the mesh in caller numbering: the incidence lists by Hilbert position (mass_pattern's), the material
+struct TlMesh {
+    int64_t N, E;
+    const uint32_t *perm;
+    const int32_t *inc_off;
+    const uint32_t *inc;
+    const int32_t *conn;
+    const double2 *xy;
+    double c0, nu, h;
+};
+
+// f[2N] = f_int(u), one lane per node, the triangles in the order of its incidence list; *inverted |= 1 for det F <= 0.
+// energy != nullptr: also *energy = W(u), the elements' energies by a two-stage sum of a fixed shape (partials: scratch
+// [kSensBlocks]).  One launch, or three
+void tl_force(const TlMesh &m, const double *u, double *f, int32_t *inverted, double *partials, double *energy, hipStream_t s);
+
+// the unfused step's acceleration: a = (amplitude[amp_at] f - (fint + m (alpha vt))) / (c m) on F, 0 on P (m the diagonal of mval)
+void tl_divide(const Pattern &pat, const double *mval, const uint8_t *known, const double *f, const double *amplitude, int64_t amp_at,
+               const double *fint, const double *vt, double alpha, double c, double *a, hipStream_t s);
+// the reactions: out = fint on P, amplitude[amp_at] f on F
+void tl_reactions(const uint8_t *known, const double *f, const double *amplitude, int64_t amp_at, const double *fint, int64_t n2, double *out,
+                  hipStream_t s);
+// an energy row: out[0] = 1/2 v.mv, out[1] = W(u), out[2] = amplitude[amp_at] f.u_F; partials: scratch [kSensBlocks][3].
+// Two launches; *inverted as tl_force
+void tl_energies(const TlMesh &m, const Pattern &pat, const double *mval, const uint8_t *known, const double *u, const double *v, const double *f,
+                 const double *amplitude, int64_t amp_at, int32_t *inverted, double *partials, double *out, hipStream_t s);
+
+} // namespace magk

@@ -1,0 +1,248 @@
+// Explicit dynamics with large rotations (mag_run_explicit with kinematics = MAG_KIN_TOTAL_LAGRANGIAN, mag_internal_force): the
+// total-Lagrangian internal force f_int(u) of explicit_tl.h in place of K u.  A whole time step is one launch of
+// k_explicit_tl_step, which reads no matrix: k_explicit_step's skeleton (explicit.hip) around k_operator_lds's ring walk (cg.hip)
+// with fan_force_tl as the triangle's function.  Compiled -ffp-contract=off: the rounding is the source's; no floating-point
+// atomics, every sum in a fixed order (a node's in its ring's, or its incidence list's): a repeat gives the same bits, every grid
+// gives the same bits, and a resumed run the bits of the run it continues.  The ring's order depends on the tile size, so the bits
+// may differ across tile_nodes (the linear step's do not: its row order is the table's).
+#include "explicit_tl.h"
+#include "member_pass.h"
+
+#include <cstdlib>
+
+namespace magk {
+
+constexpr int kTlSlotRegs = 5; // ring words kept in registers, as cg.hip's kSlotRegs: 10 entries, a closed fan of valence <= 9
+
+// the predicted displacement of one node (explicit.hip's explicit_predict without the velocity); on P: ut = u_in
+__device__ __forceinline__ double2 tl_predict_u(const ExRec &r, const uint8_t m, const double2 uin, const double c_uv, const double c_ua)
+{
+    double2 ut;
+    ut.x = (m & 1) ? uin.x : (r.u.x + c_uv * r.v.x) + c_ua * r.a.x;
+    ut.y = (m & 2) ? uin.y : (r.u.y + c_uv * r.v.y) + c_ua * r.a.y;
+    return ut;
+}
+
+// Persistent over tiles, one lane per owned node.  A launch reads P.in and writes P.out, so a tile never sees a neighbour's new
+// state; a halo node's predictor is recomputed from the same inputs as its owner's: the same bits.  LDS: cap * 32 bytes (the
+// images of the reference coordinates and of ut).
+template <int B>
+__global__ void __launch_bounds__(B) k_explicit_tl_step(const ExplicitTlParams P)
+{
+    extern __shared__ __attribute__((aligned(16))) double2 s_tl[];
+    double2 *s_xy = s_tl, *s_u = s_tl + P.cap;
+    const int tid = threadIdx.x;
+    const double dt = P.dt, alpha = P.alpha;
+    const double c_ua = dt * dt * 0.5, c_va = dt * 0.5, c_den = 1.0 + c_va * alpha;
+    const double amp = P.amplitude[P.amp_at];
+    const double c0 = P.c0, nu = P.nu, h = P.h;
+    int32_t *inverted = P.inverted;
+
+    for (int32_t t = blockIdx.x; t < P.T; t += gridDim.x) {
+        const int64_t node = (int64_t)t * B + tid;
+        const bool valid = node < P.N;
+        const int32_t deg = P.tile_deg[t], hoff = P.tile_hoff[t], nh = P.tile_hoff[t + 1] - hoff;
+        const uint32_t *ell = P.ell16 + P.tile_off[t] + tid;
+        uint32_t w[kTlSlotRegs];
+#pragma unroll
+        for (int k = 0; k < kTlSlotRegs; ++k) w[k] = k < deg ? ell[(int64_t)k * B] : 0xffffffffu;
+
+        uint8_t m = 3;
+        double2 ca = make_double2(0.0, 0.0), ut = ca, vt = ca, fl = ca;
+        double mass = 1.0;
+        if (valid) {
+            const ExRec r = P.in[node];
+            m = P.maskP[node];
+            ut = tl_predict_u(r, m, P.uinP[node], dt, c_ua);
+            vt.x = (m & 1) ? 0.0 : r.v.x + c_va * r.a.x;
+            vt.y = (m & 2) ? 0.0 : r.v.y + c_va * r.a.y;
+            fl = P.fP[node];
+            mass = P.massP[node];
+            ca = P.xyP[node];
+        }
+        __syncthreads(); // the previous tile's readers are done with the images
+        s_xy[tid] = ca;
+        s_u[tid] = ut;
+        for (int32_t hh = tid; hh < nh; hh += B) { // (more halo nodes than threads: rare)
+            const int32_t hg = P.halo_g[hoff + hh];
+            s_xy[B + hh] = P.halo_xy[hoff + hh]; // the static per-tile copy: coalesced, independent of the index load
+            s_u[B + hh] = tl_predict_u(P.in[hg], P.maskP[hg], P.uinP[hg], dt, c_ua);
+        }
+        __syncthreads();
+
+        double fx = 0.0, fy = 0.0;
+        {
+            double2 rd = ca, ru = ut; // the previous ring entry, relative to this node; every fan starts with the break bit
+            auto tri = [&](const double2 db, const double2 ub, const double2 dc, const double2 uc) {
+                fan_force_tl(db, ub, dc, uc, c0, nu, h, fx, fy, inverted);
+            };
+#pragma unroll
+            for (int k = 0; k < kTlSlotRegs; ++k) ring_word(w[k], s_xy, s_u, ca, ut, rd, ru, tri);
+            for (int32_t k = kTlSlotRegs; k < deg; ++k) ring_word(ell[(int64_t)k * B], s_xy, s_u, ca, ut, rd, ru, tri);
+        }
+
+        if (valid) {
+            const double den = c_den * mass;
+            double2 an, vn;
+            an.x = (m & 1) ? 0.0 : (amp * fl.x - (fx + mass * (alpha * vt.x))) / den;
+            an.y = (m & 2) ? 0.0 : (amp * fl.y - (fy + mass * (alpha * vt.y))) / den;
+            vn.x = vt.x + c_va * an.x;
+            vn.y = vt.y + c_va * an.y;
+            ExRec o;
+            o.u = ut;
+            o.v = vn;
+            o.a = an;
+            P.out[node] = o;
+        }
+    }
+}
+
+static size_t explicit_tl_lds(int32_t cap) { return (size_t)cap * 32; }
+
+typedef void (*explicit_tl_fn)(const ExplicitTlParams);
+static explicit_tl_fn explicit_tl_pick(int32_t B)
+{
+    return B == 256 ? k_explicit_tl_step<256> : (B == 1024 ? k_explicit_tl_step<1024> : k_explicit_tl_step<512>);
+}
+static int explicit_tl_threads(int32_t B) { return B == 256 || B == 1024 ? B : 512; }
+
+int explicit_tl_grid(int32_t B, int32_t cap, int32_t tiles)
+{
+    int dev = 0, cus = 256, per_cu = 1;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, explicit_tl_pick(B), explicit_tl_threads(B), explicit_tl_lds(cap));
+    if (e != hipSuccess || per_cu < 1) per_cu = 1;
+    long g = (long)per_cu * cus;
+    if (const char *cap_env = getenv("MAG_TUNE_GRID"))
+        if (atoi(cap_env) > 0 && g > atoi(cap_env)) g = atoi(cap_env);
+    if (g > tiles) g = tiles;
+    return g < 1 ? 1 : (int)g;
+}
+
+void explicit_tl_step(const ExplicitTlParams &P, int32_t B, int32_t grid, hipStream_t s)
+{
+    explicit_tl_pick(B)<<<grid, explicit_tl_threads(B), explicit_tl_lds(P.cap), s>>>(P);
+}
+
+// ---- f_int(u) in caller numbering: lane g takes the node at Hilbert position g and fetches every corner through conn.
+// inc[k] = 3e + (the corner of e that is this node); the triangle is taken from that corner on, counter-clockwise
+__global__ void __launch_bounds__(256) k_tl_force(TlMesh m, const double2 *u, double2 *f, int32_t *inverted)
+{
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= m.N) return;
+    const int64_t i = m.perm[g];
+    const double2 ca = m.xy[i], ua = u[i];
+    double fx = 0.0, fy = 0.0;
+    const int32_t q1 = m.inc_off[g + 1];
+    for (int32_t q = m.inc_off[g]; q < q1; ++q) {
+        const uint32_t w = m.inc[q];
+        const int64_t e = w / 3u;
+        const int a = (int)(w - 3u * (uint32_t)e);
+        const int64_t b = m.conn[3 * e + (a + 1) % 3], c = m.conn[3 * e + (a + 2) % 3];
+        const double2 cb = m.xy[b], cc = m.xy[c], pb = u[b], pc = u[c];
+        fan_force_tl(make_double2(cb.x - ca.x, cb.y - ca.y), make_double2(pb.x - ua.x, pb.y - ua.y), make_double2(cc.x - ca.x, cc.y - ca.y),
+                     make_double2(pc.x - ua.x, pc.y - ua.y), m.c0, m.nu, m.h, fx, fy, inverted);
+    }
+    f[i] = make_double2(fx, fy);
+}
+
+// the strain energy of element e, from its first corner
+__device__ inline double tl_element_energy(const TlMesh &m, const double2 *u, int64_t e, int32_t *inverted)
+{
+    const int64_t a = m.conn[3 * e], b = m.conn[3 * e + 1], c = m.conn[3 * e + 2];
+    const double2 ca = m.xy[a], cb = m.xy[b], cc = m.xy[c], ua = u[a], pb = u[b], pc = u[c];
+    const TlStrain s = tl_strain(make_double2(cb.x - ca.x, cb.y - ca.y), make_double2(pb.x - ua.x, pb.y - ua.y),
+                                 make_double2(cc.x - ca.x, cc.y - ca.y), make_double2(pc.x - ua.x, pc.y - ua.y), m.nu, m.h, inverted);
+    return tl_energy(s, m.c0);
+}
+
+// ---- W(u): stage one over the elements, stage two over the kSensBlocks partial records
+__global__ void __launch_bounds__(256) k_tl_energy_partials(TlMesh m, const double2 *u, int32_t *inverted, double *partials)
+{
+    double acc[1] = {0.0};
+    share_sum(m.E, acc, [&](int64_t e, double (&a)[1]) { a[0] += tl_element_energy(m, u, e, inverted); });
+    store_partials(acc, partials);
+}
+
+__global__ void __launch_bounds__(256) k_tl_energy_sum(const double *partials, double *out)
+{
+    sum_partials<1>(partials, [&](int64_t, const double (&acc)[1]) { out[0] = acc[0]; });
+}
+
+void tl_force(const TlMesh &m, const double *u, double *f, int32_t *inverted, double *partials, double *energy, hipStream_t s)
+{
+    k_tl_force<<<dim3((unsigned)((m.N + 255) / 256)), 256, 0, s>>>(m, (const double2 *)u, (double2 *)f, inverted);
+    if (!energy) return;
+    k_tl_energy_partials<<<dim3(kSensBlocks, 1), 256, 0, s>>>(m, (const double2 *)u, inverted, partials);
+    k_tl_energy_sum<<<dim3(1, 1), 256, 0, s>>>(partials, energy);
+}
+
+// ---- the unfused step's subtraction and division by the mass: one thread per DOF
+__global__ void __launch_bounds__(256) k_tl_divide(Pattern pat, const double *mval, const uint8_t *known, const double *f, const double *amplitude,
+                                                   int64_t amp_at, const double *fint, const double *vt, double alpha, double c, double *a)
+{
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= 2 * pat.N) return;
+    const int64_t i = r >> 1;
+    double m = 0.0;
+    for (int32_t p = pat.bptr[i]; p < pat.bptr[i + 1]; ++p)
+        if (pat.bcol[p] == i) m = mval[p];
+    a[r] = known[r] ? 0.0 : (amplitude[amp_at] * f[r] - (fint[r] + m * (alpha * vt[r]))) / (c * m);
+}
+
+void tl_divide(const Pattern &pat, const double *mval, const uint8_t *known, const double *f, const double *amplitude, int64_t amp_at,
+               const double *fint, const double *vt, double alpha, double c, double *a, hipStream_t s)
+{
+    k_tl_divide<<<dim3((unsigned)((2 * pat.N + 255) / 256)), 256, 0, s>>>(pat, mval, known, f, amplitude, amp_at, fint, vt, alpha, c, a);
+}
+
+__global__ void __launch_bounds__(256) k_tl_reactions(const uint8_t *known, const double *f, const double *amplitude, int64_t amp_at,
+                                                      const double *fint, int64_t n2, double *out)
+{
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= n2) return;
+    out[r] = known[r] ? fint[r] : amplitude[amp_at] * f[r];
+}
+
+void tl_reactions(const uint8_t *known, const double *f, const double *amplitude, int64_t amp_at, const double *fint, int64_t n2, double *out,
+                  hipStream_t s)
+{
+    k_tl_reactions<<<dim3((unsigned)((n2 + 255) / 256)), 256, 0, s>>>(known, f, amplitude, amp_at, fint, n2, out);
+}
+
+// ---- an energy row: the kinetic energy and the load's work over the 2N DOFs, the strain energy over the elements, each thread
+// its fixed share of either
+__global__ void __launch_bounds__(256) k_tl_row_partials(TlMesh m, Pattern pat, const double *mval, const uint8_t *known, const double *u,
+                                                         const double *v, const double *f, int32_t *inverted, double *partials)
+{
+    double acc[3] = {0.0, 0.0, 0.0};
+    share_sum(2 * m.N, acc, [&](int64_t r, double (&a)[3]) {
+        const int64_t i = r >> 1;
+        double mm = 0.0;
+        for (int32_t p = pat.bptr[i]; p < pat.bptr[i + 1]; ++p)
+            if (pat.bcol[p] == i) mm = mval[p];
+        a[0] += v[r] * (mm * v[r]);
+        a[2] += known[r] ? 0.0 : f[r] * u[r];
+    });
+    share_sum(m.E, acc, [&](int64_t e, double (&a)[3]) { a[1] += tl_element_energy(m, (const double2 *)u, e, inverted); });
+    store_partials(acc, partials);
+}
+
+__global__ void __launch_bounds__(256) k_tl_row_sum(const double *partials, const double *amplitude, int64_t amp_at, double *out)
+{
+    sum_partials<3>(partials, [&](int64_t, const double (&acc)[3]) {
+        out[0] = 0.5 * acc[0];
+        out[1] = acc[1];
+        out[2] = amplitude[amp_at] * acc[2];
+    });
+}
+
+void tl_energies(const TlMesh &m, const Pattern &pat, const double *mval, const uint8_t *known, const double *u, const double *v, const double *f,
+                 const double *amplitude, int64_t amp_at, int32_t *inverted, double *partials, double *out, hipStream_t s)
+{
+    k_tl_row_partials<<<dim3(kSensBlocks, 1), 256, 0, s>>>(m, pat, mval, known, u, v, f, inverted, partials);
+    k_tl_row_sum<<<dim3(1, 1), 256, 0, s>>>(partials, amplitude, amp_at, out);
+}
+
+} // namespace magk

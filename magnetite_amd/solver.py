@@ -758,8 +758,10 @@ class Context:
         """dict(u, v, a, f (2N: the final state and its reactions), iterations (steps + 1), t_start, t_end, and what the run
         recorded: probe_u / probe_v / probe_a (steps + 1, probes), energies (steps + 1, 3 = T, W, P), snapshots (rows, 2N))."""
         info = self.transient_info()
-        # (after an explicit run -- cg_kernel 6 -- the rows are those of steps 0, record_every, ...: word 4)
-        rows, n2 = (info["steps"] // info["max_step_iterations"] if info["cg_kernel"] == 6 else info["steps"]) + 1, 2 * self.N
+        # (after an explicit run -- cg_kernel 6, or 7 with total-Lagrangian kinematics -- the rows are those of steps 0,
+        # record_every, ...: word 4)
+        explicit = info["cg_kernel"] in (6, 7)
+        rows, n2 = (info["steps"] // info["max_step_iterations"] if explicit else info["steps"]) + 1, 2 * self.N
         num_probes = self._transient_probes if num_probes is None else num_probes
         energies = self._transient_energies if energies is None else energies
         out = {k: np.empty(n2) for k in ("u", "v", "a", "f")}
@@ -780,7 +782,7 @@ class Context:
         o.memory = MAG_MEM_HOST
         self._check(self._L.mag_download_transient(self._h, C.byref(o)))
         out["t_start"], out["t_end"] = float(o.scalars[0]), float(o.scalars[1])
-        if info["cg_kernel"] == 6:
+        if explicit:
             out["dt"], out["dt_bound"] = float(o.scalars[2]), float(o.scalars[3])
         return out
 
@@ -810,10 +812,15 @@ class Context:
         self._check(self._L.mag_explicit_dt(self._h, float(density), float(rayleigh_stiffness), _p(out, C.c_double)))
         return dict(zip(("lambda_bound", "dt_bound_undamped", "dt_bound", "min_mass"), (float(v) for v in out)))
 
+    KINEMATICS = {"linear": _lib.MAG_KIN_LINEAR, "tl": _lib.MAG_KIN_TOTAL_LAGRANGIAN}
+
     def run_explicit(self, steps, dt=None, dt_scale=0.9, density=None, rayleigh=(0.0, 0.0), amplitude=None, u0=None, v0=None, probes=(),
-                     energies=False, record_every=1, snapshot_every=0, resume=False):
+                     energies=False, record_every=1, snapshot_every=0, resume=False, kinematics="linear"):
         """mag_run_explicit on the uploaded problem (no run needed): `steps` central-difference steps (include/magnetite_hip.h);
-        dt None: dt_scale times the device's bound."""
+        dt None: dt_scale times the device's bound.  kinematics: "linear", or "tl" for the total-Lagrangian internal force (large
+        rotations)."""
+        if kinematics not in self.KINEMATICS:
+            raise ValueError(f"explicit: kinematics {kinematics!r} is none of {sorted(self.KINEMATICS)}")
         if density is None:
             raise MagnetiteError("Solver", "explicit: a density is needed (the model has none)")
         o = _lib.ExplicitOptions()
@@ -832,6 +839,7 @@ class Context:
         probes = np.ascontiguousarray(probes, dtype=np.int32).reshape(-1)
         o.steps, o.resume, o.energies, o.record_every = int(steps), 1 if resume else 0, 1 if energies else 0, int(record_every)
         o.snapshot_every, o.num_probes, o.memory = int(snapshot_every), int(probes.size), MAG_MEM_HOST
+        o.kinematics = self.KINEMATICS[kinematics]
         o.dt, o.dt_scale, o.density = 0.0 if dt is None else float(dt), float(dt_scale), float(density)
         o.rayleigh_mass, o.rayleigh_stiffness = float(rayleigh[0]), float(rayleigh[1])
         o.amplitude = vec(amplitude, max(int(steps), 0) + 1)
@@ -842,21 +850,37 @@ class Context:
         return rc
 
     def explicit(self, prob=None, steps=None, dt=None, dt_scale=0.9, density=None, rayleigh=(0.0, 0.0), amplitude=None, u0=None, v0=None,
-                 probes=(), energies=False, record_every=1, snapshot_every=0, resume=False):
+                 probes=(), energies=False, record_every=1, snapshot_every=0, resume=False, kinematics="linear"):
         """The response of prob (uploaded when given; otherwise of what is uploaded) over `steps` explicit steps: the arrays of
         download_transient() (rows at steps 0, record_every, ...), the words of mag_get_transient_info by name (EXPLICIT_INFO),
-        dt (the step used), dt_bound and time (the rows' times)."""
+        dt (the step used), dt_bound and time (the rows' times).  kinematics="tl": method is 7, and the dict gains inverted
+        (True when an element had det F <= 0 in some evaluation of the force; `finite` is then 0)."""
+        if kinematics not in self.KINEMATICS:
+            raise ValueError(f"explicit: kinematics {kinematics!r} is none of {sorted(self.KINEMATICS)}")
         if prob is not None:
             self.upload_problem(prob)
         if steps is None:
             raise MagnetiteError("Solver", "explicit: steps are needed")
-        self.run_explicit(steps, dt, dt_scale, density, rayleigh, amplitude, u0, v0, probes, energies, record_every, snapshot_every, resume)
+        self.run_explicit(steps, dt, dt_scale, density, rayleigh, amplitude, u0, v0, probes, energies, record_every, snapshot_every, resume,
+                          kinematics)
         out = self.download_transient()
         info = (C.c_int32 * 8)()
         self._check(self._L.mag_get_transient_info(self._h, info))
         out.update(zip(self.EXPLICIT_INFO, (int(v) for v in info)))
+        if kinematics == "tl":
+            out["inverted"] = info[7] == 0
         out["time"] = out["t_start"] + out["dt"] * (out["record_every"] * np.arange(len(out["iterations"])))
         return out
+
+    def internal_force(self, u):
+        """(f, W, inverted) of mag_internal_force: the total-Lagrangian internal force f_int(u) (2N, caller numbering), the strain
+        energy W(u), and whether some element has det F <= 0."""
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+        if u.size != 2 * self.N:
+            raise MagnetiteError("Solver", f"internal_force: an array of {u.size} entries where {2 * self.N} are expected")
+        f, scalars = np.empty(2 * self.N), np.empty(2)
+        self._check(self._L.mag_internal_force(self._h, _p(u, C.c_double), _p(f, C.c_double), _p(scalars, C.c_double), MAG_MEM_HOST))
+        return f, float(scalars[0]), bool(scalars[1] != 0.0)
 
     def assemble_effective(self, c_K, c_M, density, lumped=False):
         """The values of c_K K + c_M M in the layout of assemble_csr() (mag_assemble_effective)."""

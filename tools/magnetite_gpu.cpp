@@ -9,7 +9,8 @@
 // Usage: magnetite_gpu <input.json> <mesh.msh> [--nodes nodes.csv] [--elements elements.csv] [--dry-run] [--rel TOL]
 //                      [--stress-recovery] [--modal P --density RHO] [--adapt R [--refine-fraction T] [--refine-split 1|3]]
 //                      [--transient STEPS --dt DT --density RHO [--rayleigh A,E] [--probe DOF]...]
-//                      [--explicit STEPS --density RHO [--dt DT | --dt-scale S] [--rayleigh A,E] [--probe DOF]... [--record-every K]]
+//                      [--explicit STEPS --density RHO [--dt DT | --dt-scale S] [--rayleigh A,E] [--probe DOF]... [--record-every K]
+//                       [--kinematics linear|tl]]
 //   --dry-run  stop before the solver and print what was parsed (no GPU needed)
 //   --rel TOL  stop CG on relative residual TOL instead of the reference's absolute 1e-4
 //   --modal P --density RHO  also print "info: mode k frequency F Hz residual R" for the P lowest modes and write modes.csv
@@ -20,7 +21,9 @@
 //   --explicit STEPS --density RHO  also run STEPS central-difference steps on the lumped mass from rest under the loads applied at
 //              t = 0 (solver::run_explicit: one fused launch a step; --dt DT, or --dt-scale S times the device's bound of the
 //              stable step, 0.9 by default), print "info: explicit dt D (bound B)" and "info: step n t T" per recorded row
-//              (--record-every K: steps 0, K, 2K, ...) and write history.csv as --transient does
+//              (--record-every K: steps 0, K, 2K, ...) and write history.csv as --transient does; --kinematics tl: the
+//              total-Lagrangian internal force in place of K u (large rotations; --rayleigh A,0 only), prints "info: explicit
+//              kinematics total-lagrangian" and "warning: explicit: an element was inverted (det F <= 0)" when one was
 //   --stress-recovery  also write nodes_stress.csv (id,sx,sy,txy,vm) and elements_stress.csv (id,sx,sy,txy,vm,eta2) next to the
 //              two files -- solver::stress_recovery: the tensor per element, the nodal field, the ZZ error indicator -- and
 //              print eta_rel; without it nothing changes
@@ -463,6 +466,7 @@ int main(int argc, char **argv)
     bool transient = false, explicit_run = false;
     int explicit_steps = 0, record_every = 1;
     double dt_scale = 0.0;
+    std::string kinematics;
     std::vector<std::int32_t> probes;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -475,6 +479,7 @@ int main(int argc, char **argv)
         else if (a == "--explicit" && i + 1 < argc) explicit_run = true, explicit_steps = std::atoi(argv[++i]);
         else if (a == "--dt-scale" && i + 1 < argc) dt_scale = std::atof(argv[++i]);
         else if (a == "--record-every" && i + 1 < argc) record_every = std::atoi(argv[++i]);
+        else if (a == "--kinematics" && i + 1 < argc) kinematics = argv[++i];
         else if (a == "--probe" && i + 1 < argc) probes.push_back((std::int32_t)std::atoi(argv[++i]));
         else if (a == "--rayleigh" && i + 1 < argc) {
             const std::string pair = argv[++i];
@@ -499,7 +504,7 @@ int main(int argc, char **argv)
         else die({MagnetiteError::Input, "Unrecognized argument " + a});
     }
     if (input.empty() || mesh.empty()) {
-        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery] [--modal P --density RHO] [--transient STEPS --dt DT --density RHO [--rayleigh A,E] [--probe DOF]...] [--explicit STEPS --density RHO [--dt DT | --dt-scale S] [--rayleigh A,E] [--probe DOF]... [--record-every K]] [--adapt R [--refine-fraction T] [--refine-split 1|3]] [--topopt ITERS [--volume-fraction F] [--penal P] [--filter-passes K] [--field-cg 0..3]]\n");
+        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery] [--modal P --density RHO] [--transient STEPS --dt DT --density RHO [--rayleigh A,E] [--probe DOF]...] [--explicit STEPS --density RHO [--dt DT | --dt-scale S] [--rayleigh A,E] [--probe DOF]... [--record-every K] [--kinematics linear|tl]] [--adapt R [--refine-fraction T] [--refine-split 1|3]] [--topopt ITERS [--volume-fraction F] [--penal P] [--filter-passes K] [--field-cg 0..3]]\n");
         return 2;
     }
     if (modal_modes < 0 || (modal_modes > 0 && !(density > 0.0))) die({MagnetiteError::Input, "--modal P needs P >= 1 and --density RHO > 0"});
@@ -510,6 +515,12 @@ int main(int argc, char **argv)
         die({MagnetiteError::Input, "--explicit STEPS needs STEPS >= 1, --density RHO > 0, --dt DT > 0 or --dt-scale S > 0 (not both), --rayleigh A,E >= 0 and --record-every K >= 1"});
     if (explicit_run && transient) die({MagnetiteError::Input, "--explicit and --transient share --dt, --rayleigh and --probe: one of them at a time"});
     if (!explicit_run && (dt_scale != 0.0 || record_every != 1)) die({MagnetiteError::Input, "--dt-scale and --record-every need --explicit STEPS"});
+    if (!kinematics.empty() && !explicit_run) die({MagnetiteError::Input, "--kinematics needs --explicit STEPS"});
+    if (!kinematics.empty() && kinematics != "linear" && kinematics != "tl")
+        die({MagnetiteError::Input, "--kinematics " + kinematics + ": linear or tl (with --explicit STEPS)"});
+    const bool total_lagrangian = kinematics == "tl";
+    if (total_lagrangian && rayleigh_stiffness != 0.0)
+        die({MagnetiteError::Input, "--explicit with --kinematics tl takes --rayleigh A,0: stiffness-proportional damping is not objective"});
     if (!transient && !explicit_run && (dt != 0.0 || !probes.empty() || rayleigh_mass != 0.0 || rayleigh_stiffness != 0.0))
         die({MagnetiteError::Input, "--dt, --rayleigh and --probe need --transient STEPS"});
     if (adapt < 0 || !(refine_fraction > 0.0 && refine_fraction <= 1.0) || (refine_split != 1 && refine_split != 3))
@@ -559,6 +570,8 @@ int main(int argc, char **argv)
             std::printf("dry-run: explicit steps %d dt %s dt_scale %s density %s rayleigh %s,%s probes %zu record_every %d\n", explicit_steps,
                         rust_display(dt).c_str(), rust_display(dt_scale).c_str(), rust_display(density).c_str(), rust_display(rayleigh_mass).c_str(),
                         rust_display(rayleigh_stiffness).c_str(), probes.size(), record_every);
+        if (explicit_run && !kinematics.empty())
+            std::printf("dry-run: explicit kinematics %s\n", total_lagrangian ? "total-lagrangian" : "linear");
         return 0;
     }
     // solver::run (main.rs:64)
@@ -644,8 +657,11 @@ int main(int argc, char **argv)
         spec.rayleigh_stiffness = rayleigh_stiffness;
         spec.probes = probes;
         spec.record_every = record_every;
+        spec.kinematics = total_lagrangian ? MAG_KIN_TOTAL_LAGRANGIAN : MAG_KIN_LINEAR;
         Explicit ex;
         if (Result err = solver::run_explicit(posed, ccw, meta, spec, ex, &opt)) die(*err);
+        if (total_lagrangian) std::printf("info: explicit kinematics total-lagrangian\n");
+        if (ex.inverted) std::printf("warning: explicit: an element was inverted (det F <= 0)\n");
         std::printf("info: explicit dt %s (bound %s)\n", rust_display(ex.dt).c_str(), rust_display(ex.dt_bound).c_str());
         std::vector<std::size_t> step;
         for (size_t n = 0; n < ex.time.size(); ++n) {
