@@ -4353,6 +4353,235 @@ int transient_matrices(mag_ctx *ctx, double density, int32_t lumped)
     return MAG_OK;
 }
 
+// ---- what mag_run_transient and mag_run_explicit share: the set-up of a stepping pass on the host
+
+// the option fields both passes have
+struct StepOptions {
+    int32_t steps, snapshot_every, num_probes;
+    const int32_t *probes;
+    int32_t memory, resume;
+    const double *amplitude, *u0, *v0;
+};
+inline hipMemcpyKind step_in_kind(const StepOptions &o) { return o.memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice; }
+
+// the tail of the argument checks, behind the pass's own: the records, the context, the resume rule; enters the context
+int step_args_tail(mag_ctx *ctx, const char *fn, const StepOptions &o)
+{
+    if (o.snapshot_every < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: snapshot_every = %d is negative", fn, (int)o.snapshot_every);
+    if (o.num_probes < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: num_probes = %d is negative", fn, (int)o.num_probes);
+    if (o.num_probes > 0 && !o.probes) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: num_probes = %d with null probes", fn, (int)o.num_probes);
+    if (int rc = memory_refused(ctx, o.memory, fn)) return rc;
+    if (ctx->comm.nranks > 1)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: transient dynamics run on one GPU: this context has a communicator of %d ranks", fn, ctx->comm.nranks);
+    if (o.resume && (o.u0 || o.v0)) return fail(ctx, MAG_ERR_STATE, "%s: resume starts from the previous run's state: u0 / v0 must be NULL", fn);
+    if (o.resume && !(ctx->have_problem && ctx->tr_have)) return fail(ctx, MAG_ERR_STATE, "%s: resume without a completed run of the pass", fn);
+    if (int rc = transient_refused(ctx, fn)) return rc;
+    return enter(ctx);
+}
+
+// The 16 bytes of tr_bad.  The device checks write two words (all ones: nothing found); once those are read back, the explicit
+// pass keeps its flags in the same bytes: the finite flag at byte 0, the inverted-element flag at byte 8
+struct StepWords {
+    union {
+        unsigned long long clockwise; // the first element of signed area <= 0
+        int32_t not_finite;
+    };
+    union {
+        unsigned long long bad_probe; // the first probe outside [0, 2N)
+        int32_t inverted;
+    };
+};
+static_assert(sizeof(StepWords) == 16 && offsetof(StepWords, bad_probe) == 8 && offsetof(StepWords, inverted) == 8, "tr_bad's layout");
+
+// the checks that need the device, enqueued: the elements' orientation, the probes (uploaded into tr_probes); *h receives the
+// words once the stream is synchronised
+int step_checks_enqueue(mag_ctx *ctx, const StepOptions &o, StepWords *h)
+{
+    hipStream_t s = ctx->stream;
+    const int32_t np = o.num_probes;
+    HIPCHK(ctx->tr_bad.reserve(sizeof(StepWords)));
+    HIPCHK(ctx->tr_probes.reserve(4 * (size_t)std::max(np, 1)));
+    h->clockwise = h->bad_probe = ~0ull;
+    StepWords *d = ctx->tr_bad.as<StepWords>();
+    if (np > 0) HIPCHK(hipMemcpyAsync(ctx->tr_probes.p, o.probes, 4 * (size_t)np, step_in_kind(o), s));
+    magk::orientation(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), ctx->N, ctx->E, &d->clockwise, s);
+    magk::check_probes(ctx->tr_probes.as<int32_t>(), np, 2 * ctx->N, &d->bad_probe, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h, d, sizeof(StepWords), hipMemcpyDeviceToHost, s));
+    return MAG_OK;
+}
+
+// ... and reported, behind the synchronise
+int step_checks_report(mag_ctx *ctx, const char *fn, const StepWords &h)
+{
+    if (h.clockwise != ~0ull)
+        return fail(ctx, MAG_ERR_BAD_ARGS,
+                    "%s: element %lld has a signed area <= 0 (the stiffness carries the signed area: the pass needs counter-clockwise elements)", fn,
+                    (long long)h.clockwise);
+    if (h.bad_probe != ~0ull)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: probes[%lld] is outside [0, %lld)", fn, (long long)h.bad_probe, (long long)(2 * ctx->N));
+    return MAG_OK;
+}
+
+// the buffers of a run of `rows` record rows, `amp_n` amplitudes and `snaps` snapshots: the records first, against the memory
+// that is free now; the state (a resumed run finds it there), the work vectors, tr_zero zeroed
+int step_buffers(mag_ctx *ctx, const char *fn, int32_t steps, size_t rows, size_t amp_n, size_t snaps, int32_t np, bool resume)
+{
+    const size_t vb = 16 * (size_t)ctx->N;
+    const size_t probe_b = 3 * 8 * rows * (size_t)std::max(np, 1), energy_b = 3 * 8 * rows, snap_b = snaps * vb;
+    {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        auto more = [](const DevBuf &b, size_t want) { return want > b.cap ? want + (want >> 4) + 256 : (size_t)0; };
+        const size_t need = more(ctx->tr_probe, probe_b) + more(ctx->tr_energy, energy_b) + more(ctx->tr_snap, snap_b) + more(ctx->tr_amp, 8 * amp_n);
+        if (need > free_b)
+            return fail(ctx, MAG_ERR_TOO_LARGE, "%s: the records of %d steps need %zu bytes of device memory, %zu are free", fn, (int)steps, need, free_b);
+    }
+    HIPCHK(ctx->tr_probe.reserve(probe_b));
+    HIPCHK(ctx->tr_energy.reserve(energy_b));
+    HIPCHK(ctx->tr_snap.reserve(std::max<size_t>(snap_b, 8)));
+    HIPCHK(ctx->tr_amp.reserve(8 * amp_n));
+    HIPCHK(ctx->tr_part.reserve(8 * 3 * (size_t)magk::kSensBlocks));
+    for (DevBuf *b : {&ctx->tr_u, &ctx->tr_v, &ctx->tr_a}) {
+        if (resume && b->cap < vb) return fail(ctx, MAG_ERR_STATE, "%s: resume without the state of a completed run", fn);
+        HIPCHK(b->reserve(vb));
+    }
+    for (DevBuf *b : {&ctx->tr_ut, &ctx->tr_vt, &ctx->tr_rhs, &ctx->tr_zero, &ctx->tr_f, &ctx->tr_ku, &ctx->tr_mv}) HIPCHK(b->reserve(vb));
+    HIPCHK(hipMemsetAsync(ctx->tr_zero.p, 0, vb, ctx->stream));
+    return MAG_OK;
+}
+
+// the inputs on the device: the amplitude in tr_amp (ones where none is given; a resumed run's row 0 carries amp_first, the load
+// of the state it resumes), u0 / v0 in tr_in (null where none is given); synchronises (the host's copies are done with)
+struct StepInputs {
+    const double *d_u0, *d_v0;
+    double amp_last; // amplitude[steps]
+};
+int step_inputs(mag_ctx *ctx, const StepOptions &o, size_t amp_n, double amp_first, StepInputs *in)
+{
+    hipStream_t s = ctx->stream;
+    const hipMemcpyKind in_kind = step_in_kind(o);
+    const size_t vb = 16 * (size_t)ctx->N;
+    std::vector<double> ones;
+    double *d_amp = ctx->tr_amp.as<double>();
+    if (o.amplitude) {
+        HIPCHK(hipMemcpyAsync(d_amp, o.amplitude, 8 * amp_n, in_kind, s));
+    } else {
+        ones.assign(amp_n, 1.0);
+        HIPCHK(hipMemcpyAsync(d_amp, ones.data(), 8 * amp_n, hipMemcpyHostToDevice, s));
+    }
+    if (o.resume) HIPCHK(hipMemcpyAsync(d_amp, &amp_first, 8, hipMemcpyHostToDevice, s));
+    *in = {nullptr, nullptr, 1.0};
+    HIPCHK(hipMemcpyAsync(&in->amp_last, d_amp + o.steps, 8, hipMemcpyDeviceToHost, s));
+    if (o.u0 || o.v0) {
+        HIPCHK(ctx->tr_in.reserve(2 * vb));
+        if (o.u0) {
+            HIPCHK(hipMemcpyAsync(ctx->tr_in.p, o.u0, vb, in_kind, s));
+            in->d_u0 = ctx->tr_in.as<double>();
+        }
+        if (o.v0) {
+            HIPCHK(hipMemcpyAsync(ctx->tr_in.as<char>() + vb, o.v0, vb, in_kind, s));
+            in->d_v0 = ctx->tr_in.as<double>() + 2 * ctx->N;
+        }
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
+// the state and the probe records of a run of `rows` rows, in the context's buffers
+magk::NewmarkState newmark_state(const mag_ctx *ctx, size_t rows, int32_t np)
+{
+    magk::NewmarkState st = {};
+    st.n2 = 2 * ctx->N;
+    st.u = ctx->tr_u.as<double>();
+    st.v = ctx->tr_v.as<double>();
+    st.a = ctx->tr_a.as<double>();
+    st.ut = ctx->tr_ut.as<double>();
+    st.vt = ctx->tr_vt.as<double>();
+    st.known = ctx->uknown.as<uint8_t>();
+    st.u_in = ctx->uin.as<double>();
+    st.num_probes = np;
+    st.probes = ctx->tr_probes.as<int32_t>();
+    st.probe_u = ctx->tr_probe.as<double>();
+    st.probe_v = st.probe_u + rows * (size_t)np;
+    st.probe_a = st.probe_v + rows * (size_t)np;
+    return st;
+}
+
+// tr_rhs = (amplitude[amp_at] f - alpha M xv - K (x + eta xv))_F, 0 on P: the right-hand side of a_0 (x, xv = u, v) and of a step
+// (ut, vt)
+void damped_rhs(mag_ctx *ctx, const magk::NewmarkState &st, const double *x, const double *xv, double alpha, double eta, int64_t amp_at)
+{
+    magk::PatternApply r = {};
+    r.kval = ctx->kval.as<double>(), r.mval = ctx->tr_mval.as<double>(), r.xa = x, r.ca = 1.0, r.xb = eta != 0.0 ? xv : nullptr, r.cb = eta;
+    r.xc = alpha != 0.0 ? xv : nullptr, r.cc = alpha;
+    r.kind = 1, r.known = st.known, r.f = ctx->fin.as<double>(), r.amplitude = ctx->tr_amp.as<double>(), r.amp_at = amp_at;
+    r.y = ctx->tr_rhs.as<double>();
+    magk::pattern_apply(transient_pattern(ctx), r, ctx->stream);
+}
+
+// tr_f = the reactions of the final state: K (u + eta v) + M (a + alpha v) on P, amplitude[steps] f on F
+void linear_reactions(mag_ctx *ctx, const magk::NewmarkState &st, double alpha, double eta, int64_t steps)
+{
+    magk::PatternApply r = {};
+    r.kval = ctx->kval.as<double>(), r.mval = ctx->tr_mval.as<double>(), r.xa = st.u, r.ca = 1.0, r.xb = eta != 0.0 ? st.v : nullptr, r.cb = eta;
+    r.xc = st.a, r.cc = 1.0, r.xd = alpha != 0.0 ? st.v : nullptr, r.cd = alpha;
+    r.kind = 2, r.known = st.known, r.f = ctx->fin.as<double>(), r.amplitude = ctx->tr_amp.as<double>(), r.amp_at = steps;
+    r.y = ctx->tr_f.as<double>();
+    magk::pattern_apply(transient_pattern(ctx), r, ctx->stream);
+}
+
+// energy row `row` of the state under amplitude[amp_at]: T = 1/2 v.Mv, W = 1/2 u.Ku, P = amplitude[amp_at] f.u_F
+void linear_energy_row(mag_ctx *ctx, const magk::NewmarkState &st, int64_t row, int64_t amp_at)
+{
+    magk::PatternApply e = {};
+    e.kval = ctx->kval.as<double>(), e.mval = ctx->tr_mval.as<double>(), e.xa = st.u, e.ca = 1.0, e.xc = st.v, e.cc = 1.0;
+    e.y = ctx->tr_rhs.as<double>(), e.ku = ctx->tr_ku.as<double>(), e.mv = ctx->tr_mv.as<double>();
+    magk::pattern_apply(transient_pattern(ctx), e, ctx->stream);
+    magk::newmark_energies(st, e.ku, e.mv, ctx->fin.as<double>(), ctx->tr_amp.as<double>(), amp_at, ctx->tr_part.as<double>(),
+                           ctx->tr_energy.as<double>() + 3 * row, ctx->stream);
+}
+
+// the mesh as the total-Lagrangian kernels read it in caller numbering
+magk::TlMesh tl_mesh(const mag_ctx *ctx)
+{
+    magk::TlMesh m = {};
+    m.N = ctx->N, m.E = ctx->E;
+    m.perm = ctx->perm.as<uint32_t>(), m.inc_off = ctx->inc_off.as<int32_t>(), m.inc = ctx->inc.as<uint32_t>();
+    m.conn = ctx->conn.as<int32_t>(), m.xy = ctx->xy.as<double2>();
+    set_material(ctx, m);
+    return m;
+}
+
+// what the two fused step kernels share, but the step itself (in, out, dt, amp_at)
+magk::StepFrame step_frame(const mag_ctx *ctx, double alpha)
+{
+    magk::StepFrame F = {};
+    F.N = ctx->N, F.T = ctx->T, F.cap = ctx->cap;
+    F.maskP = ctx->maskP.as<uint8_t>();
+    F.halo_g = ctx->halo_g.as<int32_t>();
+    F.uinP = ctx->ex_uin.as<double2>(), F.fP = ctx->ex_f.as<double2>(), F.massP = ctx->ex_mass.as<double>();
+    F.amplitude = ctx->tr_amp.as<double>(), F.alpha = alpha;
+    return F;
+}
+
+// the results of a completed run, but the pass's own info words and tr_iterations
+void publish_steps(mag_ctx *ctx, const StepOptions &o, bool energies, size_t rows, size_t snaps, double t_start, double dt, double amp_last,
+                   double dt_recorded, double dt_bound)
+{
+    ctx->tr_steps = o.steps;
+    ctx->tr_num_probes = o.num_probes;
+    ctx->tr_snaps = (int32_t)snaps;
+    ctx->tr_energies = energies;
+    ctx->tr_t0 = t_start;
+    ctx->tr_t1 = t_start + (double)o.steps * dt;
+    ctx->tr_amp_last = amp_last;
+    ctx->tr_rows = (int64_t)rows;
+    ctx->tr_dt = dt_recorded;
+    ctx->tr_dt_bound = dt_bound;
+    ctx->tr_have = true;
+}
+
 } // namespace
 
 void mag_default_transient_options(mag_transient_options *o)
@@ -4397,16 +4626,8 @@ int mag_run_transient(mag_ctx *ctx, const mag_transient_options *o)
         return fail(ctx, MAG_ERR_BAD_ARGS, "%s: rayleigh_stiffness %g is negative or not finite", fn, o->rayleigh_stiffness);
     if (!nonneg_finite(o->cg_tol)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: cg_tol %g is negative or not finite", fn, o->cg_tol);
     if (o->cg < 0 || o->cg > 4) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: cg = %d outside 0..4", fn, (int)o->cg);
-    if (o->snapshot_every < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: snapshot_every = %d is negative", fn, (int)o->snapshot_every);
-    if (o->num_probes < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: num_probes = %d is negative", fn, (int)o->num_probes);
-    if (o->num_probes > 0 && !o->probes) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: num_probes = %d with null probes", fn, (int)o->num_probes);
-    if (int rc = memory_refused(ctx, o->memory, fn)) return rc;
-    if (ctx->comm.nranks > 1)
-        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: transient dynamics run on one GPU: this context has a communicator of %d ranks", fn, ctx->comm.nranks);
-    if (o->resume && (o->u0 || o->v0)) return fail(ctx, MAG_ERR_STATE, "%s: resume starts from the previous run's state: u0 / v0 must be NULL", fn);
-    if (o->resume && !(ctx->have_problem && ctx->tr_have)) return fail(ctx, MAG_ERR_STATE, "%s: resume without a completed run of the pass", fn);
-    if (int rc = transient_refused(ctx, fn)) return rc;
-    if (int rc = enter(ctx)) return rc;
+    const StepOptions so = {o->steps, o->snapshot_every, o->num_probes, o->probes, o->memory, o->resume, o->amplitude, o->u0, o->v0};
+    if (int rc = step_args_tail(ctx, fn, so)) return rc;
 
     const bool resume = o->resume != 0, energies = o->energies != 0;
     const int32_t steps = o->steps, np = o->num_probes, se = o->snapshot_every;
@@ -4416,31 +4637,17 @@ int mag_run_transient(mag_ctx *ctx, const mag_transient_options *o)
     const double amp_first = ctx->tr_amp_last; // (a resumed run's row 0 carries the load of the state it resumes)
     ctx->tr_have = false; // (a failure leaves no results of the pass)
     hipStream_t s = ctx->stream;
-    const hipMemcpyKind in_kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
 
     if (int rc = transient_matrices(ctx, o->density, o->lumped)) return rc;
     if (int rc = reserve_cg(ctx)) return rc;
     const int64_t N = ctx->N, n2 = 2 * N;
-    const size_t vb = 16 * (size_t)N;
     const magk::Pattern pat = transient_pattern(ctx);
 
     // ---- the checks that need the device: the elements' orientation, the probes
-    HIPCHK(ctx->tr_bad.reserve(16));
-    HIPCHK(ctx->tr_probes.reserve(4 * (size_t)std::max(np, 1)));
-    unsigned long long bad[2] = {~0ull, ~0ull};
-    unsigned long long *d_bad = ctx->tr_bad.as<unsigned long long>();
-    if (np > 0) HIPCHK(hipMemcpyAsync(ctx->tr_probes.p, o->probes, 4 * (size_t)np, in_kind, s));
-    magk::orientation(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), N, ctx->E, d_bad, s);
-    magk::check_probes(ctx->tr_probes.as<int32_t>(), np, n2, d_bad + 1, s);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(bad, d_bad, 16, hipMemcpyDeviceToHost, s));
+    StepWords words;
+    if (int rc = step_checks_enqueue(ctx, so, &words)) return rc;
     HIPCHK(hipStreamSynchronize(s));
-    if (bad[0] != ~0ull)
-        return fail(ctx, MAG_ERR_BAD_ARGS,
-                    "%s: element %lld has a signed area <= 0 (the stiffness carries the signed area: the pass needs counter-clockwise elements)", fn,
-                    (long long)bad[0]);
-    if (bad[1] != ~0ull)
-        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: probes[%lld] is outside [0, %lld)", fn, (long long)bad[1], (long long)n2);
+    if (int rc = step_checks_report(ctx, fn, words)) return rc;
 
     // ---- the solver
     const bool fused = o->cg == 0 ? ctx->use_lds : o->cg <= 3;
@@ -4449,71 +4656,14 @@ int mag_run_transient(mag_ctx *ctx, const mag_transient_options *o)
                     (int)o->cg);
     const int kind = !fused ? 0 : (o->cg == 0 ? 2 : o->cg - 1);
 
-    // ---- the buffers: the records first, against the memory that is free now
+    // ---- the buffers, the inputs
     const size_t rows = (size_t)steps + 1, snaps = se > 0 ? (size_t)(steps / se) + 1 : 0;
-    const size_t probe_b = 3 * 8 * rows * (size_t)std::max(np, 1), energy_b = 3 * 8 * rows, snap_b = snaps * vb;
-    {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        auto more = [](const DevBuf &b, size_t want) { return want > b.cap ? want + (want >> 4) + 256 : (size_t)0; };
-        const size_t need = more(ctx->tr_probe, probe_b) + more(ctx->tr_energy, energy_b) + more(ctx->tr_snap, snap_b) + more(ctx->tr_amp, 8 * rows);
-        if (need > free_b)
-            return fail(ctx, MAG_ERR_TOO_LARGE, "%s: the records of %d steps need %zu bytes of device memory, %zu are free", fn, (int)steps, need, free_b);
-    }
-    HIPCHK(ctx->tr_probe.reserve(probe_b));
-    HIPCHK(ctx->tr_energy.reserve(energy_b));
-    HIPCHK(ctx->tr_snap.reserve(std::max<size_t>(snap_b, 8)));
-    HIPCHK(ctx->tr_amp.reserve(8 * rows));
-    HIPCHK(ctx->tr_part.reserve(8 * 3 * (size_t)magk::kSensBlocks));
-    for (DevBuf *b : {&ctx->tr_u, &ctx->tr_v, &ctx->tr_a}) {
-        if (resume && b->cap < vb) return fail(ctx, MAG_ERR_STATE, "%s: resume without the state of a completed run", fn);
-        HIPCHK(b->reserve(vb));
-    }
-    for (DevBuf *b : {&ctx->tr_ut, &ctx->tr_vt, &ctx->tr_rhs, &ctx->tr_zero, &ctx->tr_f, &ctx->tr_ku, &ctx->tr_mv}) HIPCHK(b->reserve(vb));
-    HIPCHK(hipMemsetAsync(ctx->tr_zero.p, 0, vb, s));
-
-    // ---- the inputs: amplitude (ones where none is given), u0, v0
-    std::vector<double> ones;
-    double *d_amp = ctx->tr_amp.as<double>();
-    if (o->amplitude) {
-        HIPCHK(hipMemcpyAsync(d_amp, o->amplitude, 8 * rows, in_kind, s));
-    } else {
-        ones.assign(rows, 1.0);
-        HIPCHK(hipMemcpyAsync(d_amp, ones.data(), 8 * rows, hipMemcpyHostToDevice, s));
-    }
-    if (resume) HIPCHK(hipMemcpyAsync(d_amp, &amp_first, 8, hipMemcpyHostToDevice, s));
-    double amp_last = 1.0;
-    HIPCHK(hipMemcpyAsync(&amp_last, d_amp + steps, 8, hipMemcpyDeviceToHost, s));
-    const double *d_u0 = nullptr, *d_v0 = nullptr;
-    if (o->u0 || o->v0) {
-        HIPCHK(ctx->tr_in.reserve(2 * vb));
-        if (o->u0) {
-            HIPCHK(hipMemcpyAsync(ctx->tr_in.p, o->u0, vb, in_kind, s));
-            d_u0 = ctx->tr_in.as<double>();
-        }
-        if (o->v0) {
-            HIPCHK(hipMemcpyAsync(ctx->tr_in.as<char>() + vb, o->v0, vb, in_kind, s));
-            d_v0 = ctx->tr_in.as<double>() + n2;
-        }
-    }
-    HIPCHK(hipStreamSynchronize(s)); // (the host's copies are done with)
-
-    magk::NewmarkState st = {};
-    st.n2 = n2;
-    st.u = ctx->tr_u.as<double>();
-    st.v = ctx->tr_v.as<double>();
-    st.a = ctx->tr_a.as<double>();
-    st.ut = ctx->tr_ut.as<double>();
-    st.vt = ctx->tr_vt.as<double>();
-    st.known = ctx->uknown.as<uint8_t>();
-    st.u_in = ctx->uin.as<double>();
-    st.num_probes = np;
-    st.probes = ctx->tr_probes.as<int32_t>();
-    st.probe_u = ctx->tr_probe.as<double>();
-    st.probe_v = st.probe_u + rows * (size_t)np;
-    st.probe_a = st.probe_v + rows * (size_t)np;
-    double *d_rhs = ctx->tr_rhs.as<double>(), *d_energy = ctx->tr_energy.as<double>(), *d_snap = ctx->tr_snap.as<double>();
-    const double *d_f = ctx->fin.as<double>(), *d_k = ctx->kval.as<double>(), *d_m = ctx->tr_mval.as<double>();
+    if (int rc = step_buffers(ctx, fn, steps, rows, rows, snaps, np, resume)) return rc;
+    StepInputs in;
+    if (int rc = step_inputs(ctx, so, rows, amp_first, &in)) return rc;
+    const magk::NewmarkState st = newmark_state(ctx, rows, np);
+    double *d_rhs = ctx->tr_rhs.as<double>(), *d_snap = ctx->tr_snap.as<double>();
+    const double *d_k = ctx->kval.as<double>(), *d_m = ctx->tr_mval.as<double>();
 
     TransientSolves solves(ctx, cg_tol);
     const int G0 = solves.opt.check_every;
@@ -4566,24 +4716,16 @@ int mag_run_transient(mag_ctx *ctx, const mag_transient_options *o)
         return MAG_OK;
     };
     auto record_energies = [&](int64_t row) -> int {
-        magk::PatternApply e = {};
-        e.kval = d_k, e.mval = d_m, e.xa = st.u, e.ca = 1.0, e.xc = st.v, e.cc = 1.0, e.y = d_rhs;
-        e.ku = ctx->tr_ku.as<double>(), e.mv = ctx->tr_mv.as<double>();
-        magk::pattern_apply(pat, e, s);
-        magk::newmark_energies(st, e.ku, e.mv, d_f, d_amp, row, ctx->tr_part.as<double>(), d_energy + 3 * row, s);
+        linear_energy_row(ctx, st, row, row);
         HIPCHK(hipGetLastError());
         return MAG_OK;
     };
 
     // ---- the start
     if (!resume) {
-        magk::newmark_start(st, d_u0, d_v0, s);
+        magk::newmark_start(st, in.d_u0, in.d_v0, s);
         if (int rc = system(1.0, 0.0)) return rc;
-        magk::PatternApply r = {};
-        r.kval = d_k, r.mval = d_m, r.xa = st.u, r.ca = 1.0, r.xb = eta != 0.0 ? st.v : nullptr, r.cb = eta;
-        r.xc = alpha != 0.0 ? st.v : nullptr, r.cc = alpha;
-        r.kind = 1, r.known = st.known, r.f = d_f, r.amplitude = d_amp, r.amp_at = 0, r.y = d_rhs;
-        magk::pattern_apply(pat, r, s);
+        damped_rhs(ctx, st, st.u, st.v, alpha, eta, 0);
         if (int rc = solve(0)) return rc;
     }
     magk::newmark_record(st, 0, se > 0 ? d_snap : nullptr, s);
@@ -4594,11 +4736,7 @@ int mag_run_transient(mag_ctx *ctx, const mag_transient_options *o)
     // ---- the steps
     for (int32_t n = 0; n < steps; ++n) {
         magk::newmark_predict(st, dt, beta, gamma, s);
-        magk::PatternApply r = {};
-        r.kval = d_k, r.mval = d_m, r.xa = st.ut, r.ca = 1.0, r.xb = eta != 0.0 ? st.vt : nullptr, r.cb = eta;
-        r.xc = alpha != 0.0 ? st.vt : nullptr, r.cc = alpha;
-        r.kind = 1, r.known = st.known, r.f = d_f, r.amplitude = d_amp, r.amp_at = n + 1, r.y = d_rhs;
-        magk::pattern_apply(pat, r, s);
+        damped_rhs(ctx, st, st.ut, st.vt, alpha, eta, n + 1);
         if (int rc = solve(n + 1)) return rc;
         const bool snap = se > 0 && (n + 1) % se == 0;
         magk::newmark_correct(st, dt, beta, gamma, n + 1, snap ? d_snap + (size_t)((n + 1) / se) * (size_t)n2 : nullptr, s);
@@ -4607,13 +4745,7 @@ int mag_run_transient(mag_ctx *ctx, const mag_transient_options *o)
     }
 
     // ---- the reactions of the final state
-    {
-        magk::PatternApply r = {};
-        r.kval = d_k, r.mval = d_m, r.xa = st.u, r.ca = 1.0, r.xb = eta != 0.0 ? st.v : nullptr, r.cb = eta;
-        r.xc = st.a, r.cc = 1.0, r.xd = alpha != 0.0 ? st.v : nullptr, r.cd = alpha;
-        r.kind = 2, r.known = st.known, r.f = d_f, r.amplitude = d_amp, r.amp_at = steps, r.y = ctx->tr_f.as<double>();
-        magk::pattern_apply(pat, r, s);
-    }
+    linear_reactions(ctx, st, alpha, eta, steps);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
 
@@ -4626,17 +4758,8 @@ int mag_run_transient(mag_ctx *ctx, const mag_transient_options *o)
     info[5] = (int32_t)snaps;
     info[6] = resume ? 1 : 0;
     info[7] = all_converged ? 1 : 0;
-    ctx->tr_steps = steps;
-    ctx->tr_num_probes = np;
-    ctx->tr_snaps = (int32_t)snaps;
-    ctx->tr_energies = energies;
-    ctx->tr_t0 = t_start;
-    ctx->tr_t1 = t_start + (double)steps * dt;
-    ctx->tr_amp_last = amp_last;
     ctx->tr_iterations = iterations;
-    ctx->tr_rows = (int64_t)rows;
-    ctx->tr_dt = ctx->tr_dt_bound = 0.0;
-    ctx->tr_have = true;
+    publish_steps(ctx, so, energies, rows, snaps, t_start, dt, in.amp_last, 0.0, 0.0);
     if (!all_converged) ctx->err = std::string(fn) + ": a solve stopped at the iteration cap above the tolerance: its last iterate was used";
     return MAG_OK;
 }
@@ -4761,16 +4884,8 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
                     "%s: rayleigh_stiffness %g must be 0 with kinematics = MAG_KIN_TOTAL_LAGRANGIAN (initial-stiffness damping is not objective)", fn,
                     o->rayleigh_stiffness);
     if (o->record_every < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: record_every = %d is negative", fn, (int)o->record_every);
-    if (o->snapshot_every < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: snapshot_every = %d is negative", fn, (int)o->snapshot_every);
-    if (o->num_probes < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: num_probes = %d is negative", fn, (int)o->num_probes);
-    if (o->num_probes > 0 && !o->probes) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: num_probes = %d with null probes", fn, (int)o->num_probes);
-    if (int rc = memory_refused(ctx, o->memory, fn)) return rc;
-    if (ctx->comm.nranks > 1)
-        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: transient dynamics run on one GPU: this context has a communicator of %d ranks", fn, ctx->comm.nranks);
-    if (o->resume && (o->u0 || o->v0)) return fail(ctx, MAG_ERR_STATE, "%s: resume starts from the previous run's state: u0 / v0 must be NULL", fn);
-    if (o->resume && !(ctx->have_problem && ctx->tr_have)) return fail(ctx, MAG_ERR_STATE, "%s: resume without a completed run of the pass", fn);
-    if (int rc = transient_refused(ctx, fn)) return rc;
-    if (int rc = enter(ctx)) return rc;
+    const StepOptions so = {o->steps, o->snapshot_every, o->num_probes, o->probes, o->memory, o->resume, o->amplitude, o->u0, o->v0};
+    if (int rc = step_args_tail(ctx, fn, so)) return rc;
 
     const bool resume = o->resume != 0, energies = o->energies != 0, tl = o->kinematics == MAG_KIN_TOTAL_LAGRANGIAN;
     const int32_t steps = o->steps, np = o->num_probes, se = o->snapshot_every, re = o->record_every > 0 ? o->record_every : 1;
@@ -4779,7 +4894,6 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
     const double amp_first = ctx->tr_amp_last; // (a resumed run's row 0 carries the load of the state it resumes)
     ctx->tr_have = false; // (a failure leaves no results of the pass)
     hipStream_t s = ctx->stream;
-    const hipMemcpyKind in_kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
 
     if (int rc = transient_matrices(ctx, o->density, 1)) return rc;
     const bool fused = ctx->use_lds; // (known once the order is built: the tile-local tables, or a step of four launches)
@@ -4788,139 +4902,53 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
     const magk::Pattern pat = transient_pattern(ctx);
 
     // ---- the checks that need the device: the elements' orientation, the probes; the step
-    HIPCHK(ctx->tr_bad.reserve(16));
-    HIPCHK(ctx->tr_probes.reserve(4 * (size_t)std::max(np, 1)));
-    unsigned long long bad[2] = {~0ull, ~0ull};
-    unsigned long long *d_bad = ctx->tr_bad.as<unsigned long long>();
-    if (np > 0) HIPCHK(hipMemcpyAsync(ctx->tr_probes.p, o->probes, 4 * (size_t)np, in_kind, s));
-    magk::orientation(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), N, ctx->E, d_bad, s);
-    magk::check_probes(ctx->tr_probes.as<int32_t>(), np, n2, d_bad + 1, s);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(bad, d_bad, 16, hipMemcpyDeviceToHost, s));
+    StepWords words;
+    if (int rc = step_checks_enqueue(ctx, so, &words)) return rc;
     double bounds[4];
     if (int rc = explicit_bounds(ctx, eta, bounds)) return rc; // (synchronises)
-    if (bad[0] != ~0ull)
-        return fail(ctx, MAG_ERR_BAD_ARGS,
-                    "%s: element %lld has a signed area <= 0 (the stiffness carries the signed area: the pass needs counter-clockwise elements)", fn,
-                    (long long)bad[0]);
-    if (bad[1] != ~0ull)
-        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: probes[%lld] is outside [0, %lld)", fn, (long long)bad[1], (long long)n2);
+    if (int rc = step_checks_report(ctx, fn, words)) return rc;
     const double dt_bound = bounds[2];
     const double dt = o->dt != 0.0 ? o->dt : (o->dt_scale != 0.0 ? o->dt_scale : 0.9) * dt_bound;
     if (!pos_finite(dt)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: dt = 0 asks for dt_scale * dt_bound, and dt_bound is %g (no free DOF carries stiffness)", fn, dt_bound);
 
-    // ---- the buffers: the records first, against the memory that is free now
+    // ---- the buffers, the inputs
     const size_t rows = (size_t)(steps / re) + 1, amp_n = (size_t)steps + 1, snaps = se > 0 ? (size_t)(steps / se) + 1 : 0;
-    const size_t probe_b = 3 * 8 * rows * (size_t)std::max(np, 1), energy_b = 3 * 8 * rows, snap_b = snaps * vb;
-    {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        auto more = [](const DevBuf &b, size_t want) { return want > b.cap ? want + (want >> 4) + 256 : (size_t)0; };
-        const size_t need = more(ctx->tr_probe, probe_b) + more(ctx->tr_energy, energy_b) + more(ctx->tr_snap, snap_b) + more(ctx->tr_amp, 8 * amp_n);
-        if (need > free_b)
-            return fail(ctx, MAG_ERR_TOO_LARGE, "%s: the records of %d steps need %zu bytes of device memory, %zu are free", fn, (int)steps, need, free_b);
-    }
-    HIPCHK(ctx->tr_probe.reserve(probe_b));
-    HIPCHK(ctx->tr_energy.reserve(energy_b));
-    HIPCHK(ctx->tr_snap.reserve(std::max<size_t>(snap_b, 8)));
-    HIPCHK(ctx->tr_amp.reserve(8 * amp_n));
-    HIPCHK(ctx->tr_part.reserve(8 * 3 * (size_t)magk::kSensBlocks));
-    for (DevBuf *b : {&ctx->tr_u, &ctx->tr_v, &ctx->tr_a}) {
-        if (resume && b->cap < vb) return fail(ctx, MAG_ERR_STATE, "%s: resume without the state of a completed run", fn);
-        HIPCHK(b->reserve(vb));
-    }
-    for (DevBuf *b : {&ctx->tr_ut, &ctx->tr_vt, &ctx->tr_rhs, &ctx->tr_zero, &ctx->tr_f, &ctx->tr_ku, &ctx->tr_mv}) HIPCHK(b->reserve(vb));
-    HIPCHK(hipMemsetAsync(ctx->tr_zero.p, 0, vb, s));
-
-    // ---- the inputs: amplitude (ones where none is given), u0, v0
-    std::vector<double> ones;
-    double *d_amp = ctx->tr_amp.as<double>();
-    if (o->amplitude) {
-        HIPCHK(hipMemcpyAsync(d_amp, o->amplitude, 8 * amp_n, in_kind, s));
-    } else {
-        ones.assign(amp_n, 1.0);
-        HIPCHK(hipMemcpyAsync(d_amp, ones.data(), 8 * amp_n, hipMemcpyHostToDevice, s));
-    }
-    if (resume) HIPCHK(hipMemcpyAsync(d_amp, &amp_first, 8, hipMemcpyHostToDevice, s));
-    double amp_last = 1.0;
-    HIPCHK(hipMemcpyAsync(&amp_last, d_amp + steps, 8, hipMemcpyDeviceToHost, s));
-    const double *d_u0 = nullptr, *d_v0 = nullptr;
-    if (o->u0 || o->v0) {
-        HIPCHK(ctx->tr_in.reserve(2 * vb));
-        if (o->u0) {
-            HIPCHK(hipMemcpyAsync(ctx->tr_in.p, o->u0, vb, in_kind, s));
-            d_u0 = ctx->tr_in.as<double>();
-        }
-        if (o->v0) {
-            HIPCHK(hipMemcpyAsync(ctx->tr_in.as<char>() + vb, o->v0, vb, in_kind, s));
-            d_v0 = ctx->tr_in.as<double>() + n2;
-        }
-    }
-    HIPCHK(hipStreamSynchronize(s)); // (the host's copies are done with)
-
-    magk::NewmarkState st = {};
-    st.n2 = n2;
-    st.u = ctx->tr_u.as<double>();
-    st.v = ctx->tr_v.as<double>();
-    st.a = ctx->tr_a.as<double>();
-    st.ut = ctx->tr_ut.as<double>();
-    st.vt = ctx->tr_vt.as<double>();
-    st.known = ctx->uknown.as<uint8_t>();
-    st.u_in = ctx->uin.as<double>();
-    st.num_probes = np;
-    st.probes = ctx->tr_probes.as<int32_t>();
-    st.probe_u = ctx->tr_probe.as<double>();
-    st.probe_v = st.probe_u + rows * (size_t)np;
-    st.probe_a = st.probe_v + rows * (size_t)np;
+    if (int rc = step_buffers(ctx, fn, steps, rows, amp_n, snaps, np, resume)) return rc;
+    StepInputs in;
+    if (int rc = step_inputs(ctx, so, amp_n, amp_first, &in)) return rc;
+    const magk::NewmarkState st = newmark_state(ctx, rows, np);
     magk::NewmarkState st_quiet = st; // (the state without the probes: a snapshot alone, the unfused step's corrector)
     st_quiet.num_probes = 0;
     double *d_rhs = ctx->tr_rhs.as<double>(), *d_energy = ctx->tr_energy.as<double>(), *d_snap = ctx->tr_snap.as<double>();
+    double *d_amp = ctx->tr_amp.as<double>();
     const double *d_f = ctx->fin.as<double>(), *d_k = ctx->kval.as<double>(), *d_m = ctx->tr_mval.as<double>();
+    StepWords *d_words = ctx->tr_bad.as<StepWords>();
 
     // ---- total-Lagrangian kinematics (explicit_tl.hip): the mesh as the force kernel reads it, the inverted-element flag (the
-    // probes' word is done with), the fused step's inputs in Hilbert order; no table and no values: the step reads no matrix
-    magk::TlMesh tlm = {};
-    magk::ExplicitTlParams Q = {};
-    int32_t *d_inverted = (int32_t *)(d_bad + 1);
-    if (tl) {
-        tlm.N = N, tlm.E = ctx->E;
-        tlm.perm = ctx->perm.as<uint32_t>(), tlm.inc_off = ctx->inc_off.as<int32_t>(), tlm.inc = ctx->inc.as<uint32_t>();
-        tlm.conn = ctx->conn.as<int32_t>(), tlm.xy = ctx->xy.as<double2>();
-        set_material(ctx, tlm);
-        HIPCHK(hipMemsetAsync(d_inverted, 0, 4, s));
-    }
+    // probes' word is done with)
+    const magk::TlMesh tlm = tl ? tl_mesh(ctx) : magk::TlMesh{};
+    int32_t *d_inverted = &d_words->inverted;
+    if (tl) HIPCHK(hipMemsetAsync(d_inverted, 0, 4, s));
 
-    // ---- the fused step's table, values (unmasked: prescribed displacements enter through K ut) and inputs in Hilbert order
+    // ---- the fused step: the inputs and the records in Hilbert order and the frame of either kernel; the linear step's table and
+    // values (unmasked: prescribed displacements enter through K ut) -- the total-Lagrangian step reads no matrix
     magk::ExplicitParams P = {};
+    magk::ExplicitTlParams Q = {};
+    magk::StepFrame &F = tl ? Q.f : P.f;
     int32_t grid = 1;
     int cur = 0;
     magk::ExRec *rec[2] = {nullptr, nullptr};
-    if (fused && tl) {
-        for (DevBuf &b : ctx->ex_rec) HIPCHK(b.reserve(sizeof(magk::ExRec) * (size_t)N));
-        HIPCHK(ctx->ex_mass.reserve(8 * (size_t)N));
-        HIPCHK(ctx->ex_uin.reserve(vb));
-        HIPCHK(ctx->ex_f.reserve(vb));
-        magk::explicit_inputs(pat, ctx->perm.as<uint32_t>(), d_m, st.u_in, d_f, ctx->ex_mass.as<double>(), ctx->ex_uin.as<double2>(),
-                              ctx->ex_f.as<double2>(), s);
-        HIPCHK(hipGetLastError());
-        rec[0] = ctx->ex_rec[0].as<magk::ExRec>();
-        rec[1] = ctx->ex_rec[1].as<magk::ExRec>();
-        Q.N = N, Q.T = ctx->T, Q.cap = ctx->cap;
-        Q.maskP = ctx->maskP.as<uint8_t>();
-        Q.xyP = ctx->xyP.as<double2>(), Q.halo_xy = ctx->halo_xy.as<double2>();
-        Q.tile_deg = ctx->tile_rdeg.as<int32_t>(), Q.tile_off = ctx->tile_off.as<int64_t>(), Q.ell16 = ctx->ell.as<uint32_t>();
-        Q.tile_hoff = ctx->tile_hoff.as<int32_t>(), Q.halo_g = ctx->halo_g.as<int32_t>();
-        Q.uinP = ctx->ex_uin.as<double2>(), Q.fP = ctx->ex_f.as<double2>(), Q.massP = ctx->ex_mass.as<double>();
-        Q.amplitude = d_amp, Q.alpha = alpha;
-        set_material(ctx, Q);
-        Q.inverted = d_inverted;
-        grid = magk::explicit_tl_grid(ctx->B, ctx->cap, ctx->T);
-    } else if (fused) {
+    if (fused && !tl) {
         FieldTable tab{ctx->tr_width, ctx->tr_meta, ctx->tr_slot, ctx->tr_src, ctx->tr_val};
         if (int rc = build_field_table(ctx, tab)) return rc;
         magk::field_gather(ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(), d_k, ctx->tr_zero.as<uint8_t>(), ctx->halo_g.as<int32_t>(),
                            tab.meta.as<magk::FieldTileMeta>(), tab.slot.as<uint16_t>(), tab.src.as<int32_t>(), N, ctx->B, ctx->T, tab.total,
                            tab.val.as<double2>(), s);
+        P.total = tab.total;
+        P.meta = tab.meta.as<magk::FieldTileMeta>(), P.slot = tab.slot.as<uint16_t>(), P.fval = tab.val.as<double2>();
+        P.eta = eta;
+    }
+    if (fused) {
         for (DevBuf &b : ctx->ex_rec) HIPCHK(b.reserve(sizeof(magk::ExRec) * (size_t)N));
         HIPCHK(ctx->ex_mass.reserve(8 * (size_t)N));
         HIPCHK(ctx->ex_uin.reserve(vb));
@@ -4930,21 +4958,26 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
         HIPCHK(hipGetLastError());
         rec[0] = ctx->ex_rec[0].as<magk::ExRec>();
         rec[1] = ctx->ex_rec[1].as<magk::ExRec>();
-        P.N = N, P.total = tab.total, P.T = ctx->T, P.cap = ctx->cap;
-        P.maskP = ctx->maskP.as<uint8_t>();
-        P.meta = tab.meta.as<magk::FieldTileMeta>(), P.slot = tab.slot.as<uint16_t>(), P.fval = tab.val.as<double2>();
-        P.halo_g = ctx->halo_g.as<int32_t>();
-        P.uinP = ctx->ex_uin.as<double2>(), P.fP = ctx->ex_f.as<double2>(), P.massP = ctx->ex_mass.as<double>();
-        P.amplitude = d_amp, P.alpha = alpha, P.eta = eta;
-        grid = magk::explicit_grid(ctx->B, ctx->cap, ctx->T);
+        F = step_frame(ctx, alpha);
     }
+    if (fused && tl) {
+        Q.xyP = ctx->xyP.as<double2>(), Q.halo_xy = ctx->halo_xy.as<double2>();
+        Q.tile_deg = ctx->tile_rdeg.as<int32_t>(), Q.tile_off = ctx->tile_off.as<int64_t>(), Q.ell16 = ctx->ell.as<uint32_t>();
+        Q.tile_hoff = ctx->tile_hoff.as<int32_t>();
+        set_material(ctx, Q);
+        Q.inverted = d_inverted;
+    }
+    if (fused) grid = tl ? magk::explicit_tl_grid(ctx->B, ctx->cap, ctx->T) : magk::explicit_grid(ctx->B, ctx->cap, ctx->T);
     long long launches = 0;
     bool expanded = true; // (tr_u, tr_v, tr_a hold the current state)
     // one step of h (the start: h = 0) under amplitude[amp_at]
     auto step = [&](double h, int64_t amp_at) {
-        if (fused && tl) {
-            Q.in = rec[cur], Q.out = rec[cur ^ 1], Q.dt = h, Q.amp_at = amp_at;
-            magk::explicit_tl_step(Q, ctx->B, grid, s);
+        if (fused) {
+            F.in = rec[cur], F.out = rec[cur ^ 1], F.dt = h, F.amp_at = amp_at;
+            if (tl)
+                magk::explicit_tl_step(Q, ctx->B, grid, s);
+            else
+                magk::explicit_step(P, ctx->B, grid, s);
             cur ^= 1;
             expanded = false;
             launches += 1;
@@ -4958,20 +4991,8 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
             launches += 4;
             return;
         }
-        if (fused) {
-            P.in = rec[cur], P.out = rec[cur ^ 1], P.dt = h, P.amp_at = amp_at;
-            magk::explicit_step(P, ctx->B, grid, s);
-            cur ^= 1;
-            expanded = false;
-            launches += 1;
-            return;
-        }
         magk::newmark_predict(st, h, 0.0, 0.5, s);
-        magk::PatternApply r = {};
-        r.kval = d_k, r.mval = d_m, r.xa = st.ut, r.ca = 1.0, r.xb = eta != 0.0 ? st.vt : nullptr, r.cb = eta;
-        r.xc = alpha != 0.0 ? st.vt : nullptr, r.cc = alpha;
-        r.kind = 1, r.known = st.known, r.f = d_f, r.amplitude = d_amp, r.amp_at = amp_at, r.y = d_rhs;
-        magk::pattern_apply(pat, r, s);
+        damped_rhs(ctx, st, st.ut, st.vt, alpha, eta, amp_at);
         magk::explicit_divide(pat, d_m, st.known, d_rhs, 1.0 + 0.5 * h * alpha, st.a, s);
         magk::newmark_correct(st_quiet, h, 0.0, 0.5, 0, nullptr, s);
         launches += 4;
@@ -4993,16 +5014,12 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
         if (row_due && energies && tl) {
             magk::tl_energies(tlm, pat, d_m, st.known, st.u, st.v, d_f, d_amp, n, d_inverted, ctx->tr_part.as<double>(), d_energy + 3 * row, s);
         } else if (row_due && energies) {
-            magk::PatternApply e = {};
-            e.kval = d_k, e.mval = d_m, e.xa = st.u, e.ca = 1.0, e.xc = st.v, e.cc = 1.0, e.y = d_rhs;
-            e.ku = ctx->tr_ku.as<double>(), e.mv = ctx->tr_mv.as<double>();
-            magk::pattern_apply(pat, e, s);
-            magk::newmark_energies(st, e.ku, e.mv, d_f, d_amp, n, ctx->tr_part.as<double>(), d_energy + 3 * row, s);
+            linear_energy_row(ctx, st, row, n);
         }
     };
 
     // ---- the start: a_0 by the step with dt = 0
-    if (!resume) magk::newmark_start(st, d_u0, d_v0, s);
+    if (!resume) magk::newmark_start(st, in.d_u0, in.d_v0, s);
     if (fused) magk::explicit_gather(ctx->perm.as<uint32_t>(), N, st.u, st.v, st.a, rec[cur], s);
     if (!resume) step(0.0, 0);
     record(0);
@@ -5017,24 +5034,20 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
 
     // ---- the final state, its finite check and its reactions
     expand();
-    int32_t *d_flag = (int32_t *)(d_bad); // (the checks' words are done with)
+    int32_t *d_flag = &d_words->not_finite; // (the checks' words are done with)
     HIPCHK(hipMemsetAsync(d_flag, 0, 4, s));
     magk::explicit_finite(st.u, st.v, st.a, n2, d_flag, s);
     if (tl) {
         magk::tl_force(tlm, st.u, d_rhs, d_inverted, nullptr, nullptr, s);
         magk::tl_reactions(st.known, d_f, d_amp, steps, d_rhs, n2, ctx->tr_f.as<double>(), s);
     } else {
-        magk::PatternApply r = {};
-        r.kval = d_k, r.mval = d_m, r.xa = st.u, r.ca = 1.0, r.xb = eta != 0.0 ? st.v : nullptr, r.cb = eta;
-        r.xc = st.a, r.cc = 1.0, r.xd = alpha != 0.0 ? st.v : nullptr, r.cd = alpha;
-        r.kind = 2, r.known = st.known, r.f = d_f, r.amplitude = d_amp, r.amp_at = steps, r.y = ctx->tr_f.as<double>();
-        magk::pattern_apply(pat, r, s);
+        linear_reactions(ctx, st, alpha, eta, steps);
     }
-    int32_t flags[3] = {0, 0, 0}; // (the finite flag, the rest of its word, the inverted-element flag)
-    HIPCHK(hipMemcpyAsync(flags, d_flag, tl ? 12 : 4, hipMemcpyDeviceToHost, s));
+    StepWords flags = {}; // (read back up to the inverted-element flag)
+    HIPCHK(hipMemcpyAsync(&flags, d_words, tl ? offsetof(StepWords, inverted) + 4 : 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
-    const int32_t not_finite = flags[0], inverted = tl ? flags[2] : 0;
+    const int32_t not_finite = flags.not_finite, inverted = tl ? flags.inverted : 0;
     if (not_finite)
         return fail(ctx, MAG_ERR_NOT_CONVERGED, "%s: the state after %d steps is not finite: dt = %g against dt_bound = %g (the step is unstable)", fn,
                     (int)steps, dt, dt_bound);
@@ -5048,18 +5061,8 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
     info[5] = (int32_t)snaps;
     info[6] = resume ? 1 : 0;
     info[7] = inverted ? 0 : 1;
-    ctx->tr_steps = steps;
-    ctx->tr_num_probes = np;
-    ctx->tr_snaps = (int32_t)snaps;
-    ctx->tr_energies = energies;
-    ctx->tr_t0 = t_start;
-    ctx->tr_t1 = t_start + (double)steps * dt;
-    ctx->tr_amp_last = amp_last;
     ctx->tr_iterations.assign(rows, 0);
-    ctx->tr_rows = (int64_t)rows;
-    ctx->tr_dt = dt;
-    ctx->tr_dt_bound = dt_bound;
-    ctx->tr_have = true;
+    publish_steps(ctx, so, energies, rows, snaps, t_start, dt, in.amp_last, dt, dt_bound);
     return MAG_OK;
 }
 
@@ -5087,12 +5090,7 @@ int mag_internal_force(mag_ctx *ctx, const double *u, double *f_out, double scal
     HIPCHK(hipMemsetAsync(d_inverted, 0, 4, s));
     HIPCHK(hipMemcpyAsync(ctx->tl_u.p, u, vb, memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
     magk::orientation(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), N, ctx->E, d_bad, s);
-    magk::TlMesh m = {};
-    m.N = N, m.E = ctx->E;
-    m.perm = ctx->perm.as<uint32_t>(), m.inc_off = ctx->inc_off.as<int32_t>(), m.inc = ctx->inc.as<uint32_t>();
-    m.conn = ctx->conn.as<int32_t>(), m.xy = ctx->xy.as<double2>();
-    set_material(ctx, m);
-    magk::tl_force(m, ctx->tl_u.as<double>(), ctx->tl_f.as<double>(), d_inverted, ctx->tl_part.as<double>(), d_w, s);
+    magk::tl_force(tl_mesh(ctx), ctx->tl_u.as<double>(), ctx->tl_f.as<double>(), d_inverted, ctx->tl_part.as<double>(), d_w, s);
     HIPCHK(hipGetLastError());
     struct {
         double w;

@@ -24,13 +24,12 @@ struct ExRec {
     double2 u, v, a;
 };
 
-struct ExplicitParams {
-    int64_t N, total;
+// what the two step kernels (k_explicit_step, explicit_tl.hip's k_explicit_tl_step) share: the tiles, the records, the inputs in
+// Hilbert order and the step
+struct StepFrame {
+    int64_t N;
     int32_t T, cap;
     const uint8_t *maskP; // bit 0 / 1: prescribed ux / uy
-    const FieldTileMeta *meta;
-    const uint16_t *slot;
-    const double2 *fval; // the unmasked block rows: plane 0 at fval, plane 1 at fval + total
     const int32_t *halo_g;
     const ExRec *in;
     ExRec *out;
@@ -38,12 +37,71 @@ struct ExplicitParams {
     const double *massP;      // the node masses, Hilbert order
     const double *amplitude;
     int64_t amp_at; // the step's load is amplitude[amp_at] f
-    double dt, alpha, eta;
+    double dt, alpha;
 };
 
-// workgroups of a step: all co-resident, capped by MAG_TUNE_GRID and by the tile count (as field_cg_grid)
+// (Where the frame stands among a kernel's arguments decides how the compiler batches their scalar loads: here behind the
+// kernel's own, in ExplicitTlParams in front of them, every argument arrives in one batch and the load of amplitude[amp_at], which
+// depends on them, stays in flight until the corrector.  The other way round it is waited for in the prologue: 4 % of a step.)
+struct ExplicitParams {
+    int64_t total;
+    const FieldTileMeta *meta;
+    const uint16_t *slot;
+    const double2 *fval; // the unmasked block rows: plane 0 at fval, plane 1 at fval + total
+    double eta;
+    StepFrame f;
+};
+
+// ---- the frame of a step, used by both kernels (both units are compiled -ffp-contract=off)
+// the step's coefficients
+struct StepCoef {
+    double c_ua, c_va, c_den, amp;
+};
+__device__ __forceinline__ StepCoef step_coef(const StepFrame &F)
+{
+    StepCoef c;
+    c.c_ua = F.dt * F.dt * 0.5;
+    c.c_va = F.dt * 0.5;
+    c.c_den = 1.0 + c.c_va * F.alpha;
+    c.amp = F.amplitude[F.amp_at];
+    return c;
+}
+
+// the predictors of one node; on P: ut = u_in, vt = 0
+__device__ __forceinline__ void explicit_predict(const ExRec &r, const uint8_t m, const double2 uin, const double c_uv, const double c_ua,
+                                                 const double c_va, double2 &ut, double2 &vt)
+{
+    ut.x = (m & 1) ? uin.x : (r.u.x + c_uv * r.v.x) + c_ua * r.a.x;
+    ut.y = (m & 2) ? uin.y : (r.u.y + c_uv * r.v.y) + c_ua * r.a.y;
+    vt.x = (m & 1) ? 0.0 : r.v.x + c_va * r.a.x;
+    vt.y = (m & 2) ? 0.0 : r.v.y + c_va * r.a.y;
+}
+
+// the corrector of one node and its record: (kx, ky) is the internal force on it, K (ut + eta vt) or f_int(ut)
+__device__ __forceinline__ void explicit_correct(const StepFrame &F, const StepCoef &c, const int64_t node, const uint8_t m, const double2 ut,
+                                                 const double2 vt, const double2 fl, const double mass, const double kx, const double ky)
+{
+    const double den = c.c_den * mass;
+    double2 an, vn;
+    an.x = (m & 1) ? 0.0 : (c.amp * fl.x - (kx + mass * (F.alpha * vt.x))) / den;
+    an.y = (m & 2) ? 0.0 : (c.amp * fl.y - (ky + mass * (F.alpha * vt.y))) / den;
+    vn.x = vt.x + c.c_va * an.x;
+    vn.y = vt.y + c.c_va * an.y;
+    ExRec o;
+    o.u = ut;
+    o.v = vn;
+    o.a = an;
+    F.out[node] = o;
+}
+
+// a step kernel's workgroup size for tile size B, and its workgroups: all co-resident (the occupancy of `kernel` at `threads`
+// and `lds` bytes), capped by MAG_TUNE_GRID and by the tile count (as field_cg_grid)
+inline int step_threads(int32_t B) { return B == 256 || B == 1024 ? B : 512; }
+int step_grid(const void *kernel, int threads, size_t lds, int32_t tiles);
+
+// workgroups of a step of k_explicit_step (step_grid)
 int explicit_grid(int32_t B, int32_t cap, int32_t tiles);
-// one time step, one launch: reads P.in, writes P.out.  The row order (the diagonal, then ascending Hilbert index) is the
+// one time step, one launch: reads P.f.in, writes P.f.out.  The row order (the diagonal, then ascending Hilbert index) is the
 // table's and a function of the mesh alone: the same bits for every tile size and grid
 void explicit_step(const ExplicitParams &P, int32_t B, int32_t grid, hipStream_t s);
 

@@ -15,33 +15,23 @@ namespace magk {
 template <int B>
 constexpr int kExplicitSlotRegs = B == 1024 ? 4 : 8;
 
-// the predictors of one node; on P: ut = u_in, vt = 0
-__device__ __forceinline__ void explicit_predict(const ExRec &r, const uint8_t m, const double2 uin, const double c_uv, const double c_ua,
-                                                 const double c_va, double2 &ut, double2 &vt)
-{
-    ut.x = (m & 1) ? uin.x : (r.u.x + c_uv * r.v.x) + c_ua * r.a.x;
-    ut.y = (m & 2) ? uin.y : (r.u.y + c_uv * r.v.y) + c_ua * r.a.y;
-    vt.x = (m & 1) ? 0.0 : r.v.x + c_va * r.a.x;
-    vt.y = (m & 2) ? 0.0 : r.v.y + c_va * r.a.y;
-}
-
 // k_cg_field's skeleton without the dot products, the FusedState and the preconditioner: persistent over tiles, one lane per
-// owned node.  A launch reads P.in and writes P.out, so a tile never sees a neighbour's new state; a halo node's predictors are
+// owned node.  A launch reads P.f.in and writes P.f.out, so a tile never sees a neighbour's new state; a halo node's predictors are
 // recomputed from the same inputs as its owner's: the same bits.  LDS: cap * 16 bytes (the image of w = ut + eta vt).
 template <int B>
 __global__ void __launch_bounds__(B) k_explicit_step(const ExplicitParams P)
 {
     extern __shared__ __attribute__((aligned(16))) double2 s_w[];
     const int tid = threadIdx.x;
-    const double dt = P.dt, alpha = P.alpha, eta = P.eta;
-    const double c_ua = dt * dt * 0.5, c_va = dt * 0.5, c_den = 1.0 + c_va * alpha;
-    const double amp = P.amplitude[P.amp_at];
+    const StepFrame &F = P.f;
+    const double dt = F.dt, eta = P.eta;
+    const StepCoef c = step_coef(F);
     constexpr int SR = kExplicitSlotRegs<B>;
 
-    for (int32_t t = blockIdx.x; t < P.T; t += gridDim.x) {
+    for (int32_t t = blockIdx.x; t < F.T; t += gridDim.x) {
         const FieldTileMeta tm = P.meta[t];
         const int64_t node = (int64_t)t * B + tid;
-        const bool valid = node < P.N;
+        const bool valid = node < F.N;
         const int32_t width = tm.width, nh = tm.nh, hoff = tm.hoff;
         const uint16_t *sl = P.slot + tm.off + tid;
         const double2 *v0 = P.fval + tm.off + tid, *v1 = v0 + P.total;
@@ -53,17 +43,17 @@ __global__ void __launch_bounds__(B) k_explicit_step(const ExplicitParams P)
         double2 ut = make_double2(0.0, 0.0), vt = ut, fl = ut;
         double mass = 1.0;
         if (valid) {
-            m = P.maskP[node];
-            explicit_predict(P.in[node], m, P.uinP[node], dt, c_ua, c_va, ut, vt);
-            fl = P.fP[node];
-            mass = P.massP[node];
+            m = F.maskP[node];
+            explicit_predict(F.in[node], m, F.uinP[node], dt, c.c_ua, c.c_va, ut, vt);
+            fl = F.fP[node];
+            mass = F.massP[node];
         }
         __syncthreads(); // the previous tile's readers are done with the image
         s_w[tid] = make_double2(ut.x + eta * vt.x, ut.y + eta * vt.y);
         for (int32_t hh = tid; hh < nh; hh += B) { // (more halo nodes than threads: rare)
-            const int32_t hg = P.halo_g[hoff + hh];
+            const int32_t hg = F.halo_g[hoff + hh];
             double2 hut, hvt;
-            explicit_predict(P.in[hg], P.maskP[hg], P.uinP[hg], dt, c_ua, c_va, hut, hvt);
+            explicit_predict(F.in[hg], F.maskP[hg], F.uinP[hg], dt, c.c_ua, c.c_va, hut, hvt);
             s_w[B + hh] = make_double2(hut.x + eta * hvt.x, hut.y + eta * hvt.y);
         }
         __syncthreads();
@@ -81,19 +71,7 @@ __global__ void __launch_bounds__(B) k_explicit_step(const ExplicitParams P)
 #pragma unroll 2
         for (int32_t k = SR; k < width; ++k) entry(sl[(int64_t)k * B], k);
 
-        if (valid) {
-            const double den = c_den * mass;
-            double2 an, vn;
-            an.x = (m & 1) ? 0.0 : (amp * fl.x - (kx + mass * (alpha * vt.x))) / den;
-            an.y = (m & 2) ? 0.0 : (amp * fl.y - (ky + mass * (alpha * vt.y))) / den;
-            vn.x = vt.x + c_va * an.x;
-            vn.y = vt.y + c_va * an.y;
-            ExRec o;
-            o.u = ut;
-            o.v = vn;
-            o.a = an;
-            P.out[node] = o;
-        }
+        if (valid) explicit_correct(F, c, node, m, ut, vt, fl, mass, kx, ky);
     }
 }
 
@@ -101,14 +79,13 @@ static size_t explicit_lds(int32_t cap) { return (size_t)cap * 16; }
 
 typedef void (*explicit_fn)(const ExplicitParams);
 static explicit_fn explicit_pick(int32_t B) { return B == 256 ? k_explicit_step<256> : (B == 1024 ? k_explicit_step<1024> : k_explicit_step<512>); }
-static int explicit_threads(int32_t B) { return B == 256 || B == 1024 ? B : 512; }
 
-int explicit_grid(int32_t B, int32_t cap, int32_t tiles)
+int step_grid(const void *kernel, int threads, size_t lds, int32_t tiles)
 {
     int dev = 0, cus = 256, per_cu = 1;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, explicit_pick(B), explicit_threads(B), explicit_lds(cap));
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds);
     if (e != hipSuccess || per_cu < 1) per_cu = 1;
     long g = (long)per_cu * cus;
     if (const char *cap_env = getenv("MAG_TUNE_GRID"))
@@ -117,9 +94,11 @@ int explicit_grid(int32_t B, int32_t cap, int32_t tiles)
     return g < 1 ? 1 : (int)g;
 }
 
+int explicit_grid(int32_t B, int32_t cap, int32_t tiles) { return step_grid((const void *)explicit_pick(B), step_threads(B), explicit_lds(cap), tiles); }
+
 void explicit_step(const ExplicitParams &P, int32_t B, int32_t grid, hipStream_t s)
 {
-    explicit_pick(B)<<<grid, explicit_threads(B), explicit_lds(P.cap), s>>>(P);
+    explicit_pick(B)<<<grid, step_threads(B), explicit_lds(P.f.cap), s>>>(P);
 }
 
 // ---- the inputs in Hilbert order: one thread per node
@@ -129,10 +108,7 @@ __global__ void __launch_bounds__(256) k_ex_inputs(Pattern pat, const uint32_t *
     const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (g >= pat.N) return;
     const int64_t i = perm[g];
-    double m = 0.0;
-    for (int32_t p = pat.bptr[i]; p < pat.bptr[i + 1]; ++p)
-        if (pat.bcol[p] == i) m = mval[p];
-    massP[g] = m;
+    massP[g] = diagonal_mass(pat, mval, i);
     uinP[g] = u_in[i];
     fP[g] = f_in[i];
 }
@@ -229,10 +205,7 @@ __global__ void __launch_bounds__(256) k_ex_divide(Pattern pat, const double *mv
 {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= 2 * pat.N) return;
-    const int64_t i = r >> 1;
-    double m = 0.0;
-    for (int32_t p = pat.bptr[i]; p < pat.bptr[i + 1]; ++p)
-        if (pat.bcol[p] == i) m = mval[p];
+    const double m = diagonal_mass(pat, mval, r >> 1);
     a[r] = known[r] ? 0.0 : rhs[r] / (c * m);
 }
 

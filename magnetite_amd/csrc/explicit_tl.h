@@ -77,28 +77,19 @@ __device__ inline double tl_energy(const TlStrain &s, double c0)
 }
 
 struct ExplicitTlParams {
-    int64_t N;
-    int32_t T, cap;
-    const uint8_t *maskP; // bit 0 / 1: prescribed ux / uy
+    StepFrame f;
     const double2 *xyP, *halo_xy;
     const int32_t *tile_deg; // ring words per row of the tile
     const int64_t *tile_off;
     const uint32_t *ell16; // the ring table (symbolic.hip, k_ring16)
-    const int32_t *tile_hoff, *halo_g;
-    const ExRec *in;
-    ExRec *out;
-    const double2 *uinP, *fP; // u_in and f_in, Hilbert order
-    const double *massP;      // the node masses, Hilbert order
-    const double *amplitude;
-    int64_t amp_at; // the step's load is amplitude[amp_at] f
-    double dt, alpha;
+    const int32_t *tile_hoff;
     double c0, nu, h;
     int32_t *inverted;
 };
 
-// workgroups of a step: all co-resident, capped by MAG_TUNE_GRID and by the tile count (as explicit_grid)
+// workgroups of a step (step_grid)
 int explicit_tl_grid(int32_t B, int32_t cap, int32_t tiles);
-// one time step, one launch: reads P.in, writes P.out.  The order of a node's sum is its ring's (a function of the mesh and the
+// one time step, one launch: reads P.f.in, writes P.f.out.  The order of a node's sum is its ring's (a function of the mesh and the
 // tile size): the same bits for every grid, not across tile sizes
 void explicit_tl_step(const ExplicitTlParams &P, int32_t B, int32_t grid, hipStream_t s);
 

@@ -8,39 +8,28 @@
 #include "explicit_tl.h"
 #include "member_pass.h"
 
-#include <cstdlib>
-
 namespace magk {
 
 constexpr int kTlSlotRegs = 5; // ring words kept in registers, as cg.hip's kSlotRegs: 10 entries, a closed fan of valence <= 9
 
-// the predicted displacement of one node (explicit.hip's explicit_predict without the velocity); on P: ut = u_in
-__device__ __forceinline__ double2 tl_predict_u(const ExRec &r, const uint8_t m, const double2 uin, const double c_uv, const double c_ua)
-{
-    double2 ut;
-    ut.x = (m & 1) ? uin.x : (r.u.x + c_uv * r.v.x) + c_ua * r.a.x;
-    ut.y = (m & 2) ? uin.y : (r.u.y + c_uv * r.v.y) + c_ua * r.a.y;
-    return ut;
-}
-
-// Persistent over tiles, one lane per owned node.  A launch reads P.in and writes P.out, so a tile never sees a neighbour's new
+// Persistent over tiles, one lane per owned node.  A launch reads P.f.in and writes P.f.out, so a tile never sees a neighbour's new
 // state; a halo node's predictor is recomputed from the same inputs as its owner's: the same bits.  LDS: cap * 32 bytes (the
 // images of the reference coordinates and of ut).
 template <int B>
 __global__ void __launch_bounds__(B) k_explicit_tl_step(const ExplicitTlParams P)
 {
     extern __shared__ __attribute__((aligned(16))) double2 s_tl[];
-    double2 *s_xy = s_tl, *s_u = s_tl + P.cap;
+    const StepFrame &F = P.f;
+    double2 *s_xy = s_tl, *s_u = s_tl + F.cap;
     const int tid = threadIdx.x;
-    const double dt = P.dt, alpha = P.alpha;
-    const double c_ua = dt * dt * 0.5, c_va = dt * 0.5, c_den = 1.0 + c_va * alpha;
-    const double amp = P.amplitude[P.amp_at];
+    const double dt = F.dt;
+    const StepCoef c = step_coef(F);
     const double c0 = P.c0, nu = P.nu, h = P.h;
     int32_t *inverted = P.inverted;
 
-    for (int32_t t = blockIdx.x; t < P.T; t += gridDim.x) {
+    for (int32_t t = blockIdx.x; t < F.T; t += gridDim.x) {
         const int64_t node = (int64_t)t * B + tid;
-        const bool valid = node < P.N;
+        const bool valid = node < F.N;
         const int32_t deg = P.tile_deg[t], hoff = P.tile_hoff[t], nh = P.tile_hoff[t + 1] - hoff;
         const uint32_t *ell = P.ell16 + P.tile_off[t] + tid;
         uint32_t w[kTlSlotRegs];
@@ -51,22 +40,22 @@ __global__ void __launch_bounds__(B) k_explicit_tl_step(const ExplicitTlParams P
         double2 ca = make_double2(0.0, 0.0), ut = ca, vt = ca, fl = ca;
         double mass = 1.0;
         if (valid) {
-            const ExRec r = P.in[node];
-            m = P.maskP[node];
-            ut = tl_predict_u(r, m, P.uinP[node], dt, c_ua);
-            vt.x = (m & 1) ? 0.0 : r.v.x + c_va * r.a.x;
-            vt.y = (m & 2) ? 0.0 : r.v.y + c_va * r.a.y;
-            fl = P.fP[node];
-            mass = P.massP[node];
+            const ExRec r = F.in[node];
+            m = F.maskP[node];
+            explicit_predict(r, m, F.uinP[node], dt, c.c_ua, c.c_va, ut, vt);
+            fl = F.fP[node];
+            mass = F.massP[node];
             ca = P.xyP[node];
         }
         __syncthreads(); // the previous tile's readers are done with the images
         s_xy[tid] = ca;
         s_u[tid] = ut;
         for (int32_t hh = tid; hh < nh; hh += B) { // (more halo nodes than threads: rare)
-            const int32_t hg = P.halo_g[hoff + hh];
+            const int32_t hg = F.halo_g[hoff + hh];
             s_xy[B + hh] = P.halo_xy[hoff + hh]; // the static per-tile copy: coalesced, independent of the index load
-            s_u[B + hh] = tl_predict_u(P.in[hg], P.maskP[hg], P.uinP[hg], dt, c_ua);
+            double2 hut, hvt; // (the velocity is not used: the force reads ut alone)
+            explicit_predict(F.in[hg], F.maskP[hg], F.uinP[hg], dt, c.c_ua, c.c_va, hut, hvt);
+            s_u[B + hh] = hut;
         }
         __syncthreads();
 
@@ -81,19 +70,7 @@ __global__ void __launch_bounds__(B) k_explicit_tl_step(const ExplicitTlParams P
             for (int32_t k = kTlSlotRegs; k < deg; ++k) ring_word(ell[(int64_t)k * B], s_xy, s_u, ca, ut, rd, ru, tri);
         }
 
-        if (valid) {
-            const double den = c_den * mass;
-            double2 an, vn;
-            an.x = (m & 1) ? 0.0 : (amp * fl.x - (fx + mass * (alpha * vt.x))) / den;
-            an.y = (m & 2) ? 0.0 : (amp * fl.y - (fy + mass * (alpha * vt.y))) / den;
-            vn.x = vt.x + c_va * an.x;
-            vn.y = vt.y + c_va * an.y;
-            ExRec o;
-            o.u = ut;
-            o.v = vn;
-            o.a = an;
-            P.out[node] = o;
-        }
+        if (valid) explicit_correct(F, c, node, m, ut, vt, fl, mass, fx, fy);
     }
 }
 
@@ -104,25 +81,15 @@ static explicit_tl_fn explicit_tl_pick(int32_t B)
 {
     return B == 256 ? k_explicit_tl_step<256> : (B == 1024 ? k_explicit_tl_step<1024> : k_explicit_tl_step<512>);
 }
-static int explicit_tl_threads(int32_t B) { return B == 256 || B == 1024 ? B : 512; }
 
 int explicit_tl_grid(int32_t B, int32_t cap, int32_t tiles)
 {
-    int dev = 0, cus = 256, per_cu = 1;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, explicit_tl_pick(B), explicit_tl_threads(B), explicit_tl_lds(cap));
-    if (e != hipSuccess || per_cu < 1) per_cu = 1;
-    long g = (long)per_cu * cus;
-    if (const char *cap_env = getenv("MAG_TUNE_GRID"))
-        if (atoi(cap_env) > 0 && g > atoi(cap_env)) g = atoi(cap_env);
-    if (g > tiles) g = tiles;
-    return g < 1 ? 1 : (int)g;
+    return step_grid((const void *)explicit_tl_pick(B), step_threads(B), explicit_tl_lds(cap), tiles);
 }
 
 void explicit_tl_step(const ExplicitTlParams &P, int32_t B, int32_t grid, hipStream_t s)
 {
-    explicit_tl_pick(B)<<<grid, explicit_tl_threads(B), explicit_tl_lds(P.cap), s>>>(P);
+    explicit_tl_pick(B)<<<grid, step_threads(B), explicit_tl_lds(P.f.cap), s>>>(P);
 }
 
 // ---- f_int(u) in caller numbering: lane g takes the node at Hilbert position g and fetches every corner through conn.
@@ -184,10 +151,7 @@ __global__ void __launch_bounds__(256) k_tl_divide(Pattern pat, const double *mv
 {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= 2 * pat.N) return;
-    const int64_t i = r >> 1;
-    double m = 0.0;
-    for (int32_t p = pat.bptr[i]; p < pat.bptr[i + 1]; ++p)
-        if (pat.bcol[p] == i) m = mval[p];
+    const double m = diagonal_mass(pat, mval, r >> 1);
     a[r] = known[r] ? 0.0 : (amplitude[amp_at] * f[r] - (fint[r] + m * (alpha * vt[r]))) / (c * m);
 }
 
@@ -218,10 +182,7 @@ __global__ void __launch_bounds__(256) k_tl_row_partials(TlMesh m, Pattern pat, 
 {
     double acc[3] = {0.0, 0.0, 0.0};
     share_sum(2 * m.N, acc, [&](int64_t r, double (&a)[3]) {
-        const int64_t i = r >> 1;
-        double mm = 0.0;
-        for (int32_t p = pat.bptr[i]; p < pat.bptr[i + 1]; ++p)
-            if (pat.bcol[p] == i) mm = mval[p];
+        const double mm = diagonal_mass(pat, mval, r >> 1);
         a[0] += v[r] * (mm * v[r]);
         a[2] += known[r] ? 0.0 : f[r] * u[r];
     });

@@ -24,6 +24,15 @@ struct Pattern {
     int64_t N, nb;
 };
 
+// the diagonal entry of mval in row node i: the lumped mass of node i
+__device__ inline double diagonal_mass(const Pattern &pat, const double *mval, int64_t i)
+{
+    double m = 0.0;
+    for (int32_t p = pat.bptr[i]; p < pat.bptr[i + 1]; ++p)
+        if (pat.bcol[p] == i) m = mval[p];
+    return m;
+}
+
 // mval[block (i, j)] = sum over the triangles that hold i and j, in the order of i's incidence list (inc_off / inc by Hilbert
 // position, inc = 3 e + corner), of m_e / 12 (i != j) or m_e / 6 (i == j), m_e = c |A_e|, c = rho t; lumped: m_e / 3 on the
 // diagonal, 0 elsewhere.  One launch.

@@ -725,26 +725,31 @@ class Context:
             raise MagnetiteError("Solver", "transient: a density is needed (the model has none)")
         o = _lib.TransientOptions()
         self._L.mag_default_transient_options(C.byref(o))
+        o.lumped, o.cg = 1 if lumped else 0, int(cg)
+        o.dt, o.beta, o.gamma, o.density = float(dt), float(beta), float(gamma), float(density)
+        o.rayleigh_mass, o.rayleigh_stiffness, o.cg_tol = float(rayleigh[0]), float(rayleigh[1]), float(cg_tol)
+        return self._run_steps("transient", self._L.mag_run_transient, o, steps, amplitude, u0, v0, probes, energies, snapshot_every, resume)
+
+    def _run_steps(self, name, run, o, steps, amplitude, u0, v0, probes, energies, snapshot_every, resume):
+        """What run_transient and run_explicit share: the options both passes have, the call, what download_transient sizes."""
         keep = []  # (the arrays the options point to, until the call returns)
 
-        def vec(x, n, dtype=np.float64):
+        def vec(x, n):
             if x is None:
                 return None
-            a = np.ascontiguousarray(x, dtype=dtype).reshape(-1)
+            a = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
             if a.size != n:
-                raise MagnetiteError("Solver", f"transient: an array of {a.size} entries where {n} are expected")
+                raise MagnetiteError("Solver", f"{name}: an array of {a.size} entries where {n} are expected")
             keep.append(a)
             return a.ctypes.data
 
         probes = np.ascontiguousarray(probes, dtype=np.int32).reshape(-1)
-        o.steps, o.resume, o.lumped, o.cg = int(steps), 1 if resume else 0, 1 if lumped else 0, int(cg)
-        o.energies, o.snapshot_every, o.num_probes, o.memory = 1 if energies else 0, int(snapshot_every), int(probes.size), MAG_MEM_HOST
-        o.dt, o.beta, o.gamma, o.density = float(dt), float(beta), float(gamma), float(density)
-        o.rayleigh_mass, o.rayleigh_stiffness, o.cg_tol = float(rayleigh[0]), float(rayleigh[1]), float(cg_tol)
+        o.steps, o.resume, o.energies = int(steps), 1 if resume else 0, 1 if energies else 0
+        o.snapshot_every, o.num_probes, o.memory = int(snapshot_every), int(probes.size), MAG_MEM_HOST
         o.amplitude = vec(amplitude, max(int(steps), 0) + 1)
         o.u0, o.v0 = vec(u0, 2 * self.N), vec(v0, 2 * self.N)
         o.probes = probes.ctypes.data if probes.size else None
-        rc = self._check(self._L.mag_run_transient(self._h, C.byref(o)))
+        rc = self._check(run(self._h, C.byref(o)))
         self._transient_probes, self._transient_energies = int(probes.size), bool(energies)  # (what download_transient sizes)
         return rc
 
@@ -825,29 +830,10 @@ class Context:
             raise MagnetiteError("Solver", "explicit: a density is needed (the model has none)")
         o = _lib.ExplicitOptions()
         self._L.mag_default_explicit_options(C.byref(o))
-        keep = []  # (the arrays the options point to, until the call returns)
-
-        def vec(x, n):
-            if x is None:
-                return None
-            a = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
-            if a.size != n:
-                raise MagnetiteError("Solver", f"explicit: an array of {a.size} entries where {n} are expected")
-            keep.append(a)
-            return a.ctypes.data
-
-        probes = np.ascontiguousarray(probes, dtype=np.int32).reshape(-1)
-        o.steps, o.resume, o.energies, o.record_every = int(steps), 1 if resume else 0, 1 if energies else 0, int(record_every)
-        o.snapshot_every, o.num_probes, o.memory = int(snapshot_every), int(probes.size), MAG_MEM_HOST
-        o.kinematics = self.KINEMATICS[kinematics]
+        o.record_every, o.kinematics = int(record_every), self.KINEMATICS[kinematics]
         o.dt, o.dt_scale, o.density = 0.0 if dt is None else float(dt), float(dt_scale), float(density)
         o.rayleigh_mass, o.rayleigh_stiffness = float(rayleigh[0]), float(rayleigh[1])
-        o.amplitude = vec(amplitude, max(int(steps), 0) + 1)
-        o.u0, o.v0 = vec(u0, 2 * self.N), vec(v0, 2 * self.N)
-        o.probes = probes.ctypes.data if probes.size else None
-        rc = self._check(self._L.mag_run_explicit(self._h, C.byref(o)))
-        self._transient_probes, self._transient_energies = int(probes.size), bool(energies)  # (what download_transient sizes)
-        return rc
+        return self._run_steps("explicit", self._L.mag_run_explicit, o, steps, amplitude, u0, v0, probes, energies, snapshot_every, resume)
 
     def explicit(self, prob=None, steps=None, dt=None, dt_scale=0.9, density=None, rayleigh=(0.0, 0.0), amplitude=None, u0=None, v0=None,
                  probes=(), energies=False, record_every=1, snapshot_every=0, resume=False, kinematics="linear"):
