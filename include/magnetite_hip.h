@@ -737,6 +737,75 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *opt);
 int mag_explicit_dt(mag_ctx *ctx, double density, double rayleigh_stiffness, double out[4]);
 int mag_internal_force(mag_ctx *ctx, const double *u, double *f_out, double scalars_out[2], int32_t memory);
 
+/* ---- nonlinear statics: Newton's method on the total-Lagrangian tangent, on the device ---------------------------
+ * mag_run_newton: the large-deflection equilibrium of the uploaded part under the internal force above (MAG_KIN_TOTAL_LAGRANGIAN's
+ *   f_int), in load increments.  Increment k = 1 .. increments has the load factor lambda_k = load_factors[k - 1], or
+ *   k / increments where load_factors is NULL, and solves
+ *     f_int(u)_F = lambda f_F on the free DOFs,   u_P = lambda u_in on the supports
+ *   by Newton-Raphson with the consistent tangent of f_int.  Needs an upload and no run; changes no other result of the context.
+ *   The tangent.  With H, F = I + H and S of the triangle as above, the reference shape gradients
+ *     g_a = (db.y - dc.y, dc.x - db.x) / 2A,  g_b = (dc.y, -dc.x) / 2A,  g_c = (-db.y, db.x) / 2A  (cyclic shifts),
+ *     V = A t,  D = c [[1, nu, 0], [nu, 1, 0], [0, 0, h]],  h = (1 - nu) / 2,
+ *   the 2 x 2 block of corners (k, l) is
+ *     K_T[k, l] = V (B_k^T D B_l + (g_k^T S g_l) I),   B_k (3 x 2) with column d = (F_d1 g_k.x,  F_d2 g_k.y,  F_d1 g_k.y + F_d2 g_k.x).
+ *   K_T(0) = K.  It is assembled into K's pattern: block (i, j) is the sum over the triangles that hold i and j in the order of
+ *   i's incidence list, without floating-point atomics: the same bits for a repeat, every grid and every tile_nodes.
+ *   An iteration.  The first one of an increment moves the supports by its linearisation (the support predictor):
+ *     dU_P = lambda u_in - u on P;   K_T,FF du_F = (lambda f - f_int(u))_F - (K_T dU_P)_F;   u += s (du_F + dU_P);
+ *   the later ones solve K_T,FF du_F = (lambda f - f_int(u))_F with du_P = 0.  Every iteration is one evaluation of f_int, one
+ *   tangent launch, the gather of the tangent into the solver's rows and one CG solve from zero under MAG_STOP_REL with cg_tol
+ *   (0: 1e-10).  cg as mag_run_transient's: 0 block-Jacobi on the fused block-row kernel where the context has tile-local tables
+ *   and the CSR operator's phase elsewhere, 1 | 2 | 3 the fused kernel plain | Jacobi | block-Jacobi, 4 the CSR operator's phase.
+ *   Stop.  After every update: |r_F|_2 <= newton_tol * ref,  r = lambda f - f_int(u),  ref = max(|lambda f_F|_2, |f_int(u)_P|_2).
+ *     newton_tol 0: 1e-10; max_newton 0: 25 iterations per increment.  The host reads one record of scalars per evaluation and
+ *     the CG's convergence polls, nothing else.
+ *   Line search.  line_search = H > 0: the step length s starts at 1 and is halved, at most H times, while the trial state
+ *     u + s du has an inverted element (det F <= 0) or Pi(u + s du) > Pi(u) + 1e-4 s g, with Pi = W - lambda f_F.u_F and the slope
+ *     g = (f_int(u) - lambda f_F).du (this is -r.du where du_P = 0).  The energy test is skipped where g >= 0 (a support predictor
+ *     that works against the part) or |s g| <= 1e-13 max(|Pi|, W) (rounding).  H = 0 is plain Newton: s = 1.
+ *   Not converged within max_newton: no error.  The run ends there; the state and the records stay at the last converged
+ *     increment, info[7] is 0, info[0] the increments converged, and mag_last_error names the increment, the iteration and the
+ *     ratio |r_F| / ref.  A CG that broke down (non-finite): MAG_ERR_NOT_CONVERGED naming increment and iteration, no results.
+ *     An indefinite tangent (buckling, limit points) is out of scope: the CG needs K_T,FF positive definite.
+ *   Start.  u0 (2N) starts from a given state: its P entries are where the supports stand.  NULL: zero.
+ *   Records, row 0 the start and row k increment k: load (the factors, row 0: 0), probe_u (the load-deflection curve), energies
+ *     (W, Pi), newton_iterations, snapshots (snapshots != 0).  residuals (|r_F| / ref after the update), cg_iterations and
+ *     step_lengths have one entry per Newton iteration of the run: info[3] entries, at most increments * max_newton.  Rows of
+ *     increments that did not converge are zero.
+ *   Results: u_out (2N), f_out (2N: f_int on P, lambda f on F), elem (E x 8: Exx, Eyy, Gxy, Sxx, Syy, Sxy, det F, W_e).
+ * mag_get_newton_info: info[0] increments converged, [1] cg_kernel (3 CSR operator's phase | 5 fused block rows), [2] preconditioner
+ *   (0 none, 1 Jacobi, 2 block-Jacobi), [3] Newton iterations of the run, [4] CG iterations of the run, [5] halvings, [6] 1 when an
+ *   element was inverted in an accepted state, [7] 1 when every increment converged.
+ * mag_assemble_tangent: values_out = K_T(u) (u: 2N) in the layout of mag_assemble_csr's val (its rowptr / col apply).  Needs an
+ *   upload only.
+ * Errors: mag_run_transient's rules, order and wording.  Before any HIP call: MAG_ERR_BAD_ARGS for a null struct, increments < 1,
+ *   a negative max_newton, line_search, num_probes, a newton_tol or cg_tol negative or not finite, cg outside 0..4, num_probes > 0
+ *   with NULL probes, a `memory` outside enum mag_memory, more than one rank; MAG_ERR_STATE for no upload, an element stiffness
+ *   field, assemble_csr = 0 or precision = 1.  After the first device work: an element of signed area <= 0, a probe outside [0, 2N).
+ * Out of scope: arc-length and limit points; follower loads; other materials; a warm-started or inexact inner solve; the on-chip
+ *   CG on K_T; a matrix-free tangent operator; fields, variants and ranks; an implicit dynamic pass on the tangent. */
+typedef struct mag_newton_options {
+    int32_t increments, max_newton, line_search, cg, snapshots, num_probes, memory, reserved;
+    double newton_tol, cg_tol;
+    const double *load_factors, *u0; /* [increments], 2N; NULL: k / increments, zero */
+    const int32_t *probes;           /* NULL: none */
+} mag_newton_options;                /* 72 bytes */
+typedef struct mag_newton_result {
+    double *u_out, *f_out, *elem;    /* 2N, 2N, E x 8 */
+    double *probe_u, *snapshots;     /* [increments + 1][num_probes], [increments + 1][2N] */
+    double *load, *energies;         /* [increments + 1], [increments + 1][2] */
+    int32_t *newton_iterations;      /* [increments + 1] */
+    double *residuals;               /* [info[3]] */
+    int32_t *cg_iterations;          /* [info[3]] */
+    double *step_lengths;            /* [info[3]] */
+    int32_t memory, reserved;        /* NULL members are skipped */
+} mag_newton_result;                 /* 96 bytes */
+void mag_default_newton_options(mag_newton_options *opt); /* increments 1, everything else 0 / NULL */
+int mag_run_newton(mag_ctx *ctx, const mag_newton_options *opt);
+int mag_download_newton(mag_ctx *ctx, mag_newton_result *out);
+int mag_get_newton_info(const mag_ctx *ctx, int32_t info[8]);
+int mag_assemble_tangent(mag_ctx *ctx, const double *u, double *values_out, int32_t memory);
+
 /* ---- adaptive mesh refinement: longest-edge bisection with conformity closure (Rivara) of the uploaded mesh, on the device ----
  * What acts on the ZZ indicator of mag_run_stress: solve -> mag_run_stress -> mag_run_refine -> mag_upload_refined -> solve, the
  * mesh never leaving the device.  The reference (gmsh meshing, no adaptivity) has no counterpart.  The result is a pure function

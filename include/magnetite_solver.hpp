@@ -209,6 +209,28 @@ struct InternalForce {
     bool inverted = false;
 };
 
+// The options of solver::run_newton (include/magnetite_hip.h, mag_newton_options).  load_factors: increments values or empty
+// (k / increments); u0: 2N values in the order of `nodes` or empty (zero); probes: 2 * node + axis.
+struct NewtonSpec {
+    std::int32_t increments = 1, max_newton = 0, line_search = 0, cg = 0;
+    bool snapshots = false;
+    double newton_tol = 0.0, cg_tol = 0.0;
+    std::vector<double> load_factors, u0;
+    std::vector<std::int32_t> probes;
+};
+
+// What solver::run_newton returns: the outputs of mag_download_newton -- the last converged state, its reactions and element rows
+// (E x 8: Exx, Eyy, Gxy, Sxx, Syy, Sxy, det F, W_e), the rows of the start and of every increment (load, probe_u, energies = W, Pi,
+// newton_iterations, snapshots), one entry per Newton iteration of the run (residuals, cg_iterations, step_lengths) -- and
+// mag_get_newton_info's words by name.  converged false: an increment ran into max_newton (no error); message says which.
+struct Newton {
+    std::vector<double> u, f, elem, probe_u, snapshots, load, energies, residuals, step_lengths;
+    std::vector<std::int32_t> newton_iterations, cg_iterations;
+    std::int32_t increments_converged = 0, cg_kernel = 0, preconditioner = 0, newton_iterations_total = 0, cg_iterations_total = 0, halvings = 0;
+    bool inverted = false, converged = false;
+    std::string message;
+};
+
 // What solver::explicit_dt returns (mag_explicit_dt)
 struct ExplicitBound {
     double lambda_bound = 0, dt_bound_undamped = 0, dt_bound = 0, min_mass = 0;
@@ -931,6 +953,107 @@ inline Result internal_force(const std::vector<Node> &nodes, const std::vector<E
     if (mag_internal_force(ctx, u.data(), out.f.data(), scalars, MAG_MEM_HOST) != MAG_OK) return detail::fail_and_destroy(ctx);
     out.energy = scalars[0];
     out.inverted = scalars[1] != 0.0;
+    mag_destroy(ctx);
+    return std::nullopt;
+}
+
+// Nonlinear statics (mag_run_newton) of the part: its large-deflection equilibrium under the total-Lagrangian internal force, in
+// spec.increments load increments of Newton's method on the consistent tangent; supports and loads as solver::run.
+inline Result run_newton(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                         const NewtonSpec &spec, Newton &out, const mag_options *options = nullptr)
+{
+    const std::size_t N = nodes.size(), E = elements.size();
+    std::vector<double> xy, u_in(2 * N), f_in(2 * N);
+    std::vector<std::uint8_t> u_known;
+    std::vector<std::int32_t> conn;
+    if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
+    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
+    if (!spec.load_factors.empty() && spec.load_factors.size() != (std::size_t)std::max(spec.increments, 0))
+        return detail::solver_error("the load factors have another length than increments");
+    if (!spec.u0.empty() && spec.u0.size() != 2 * N) return detail::solver_error("u0 has another length than 2 N");
+    mag_ctx *ctx = mag_create(options);
+    if (!ctx) return detail::solver_error("mag_create failed");
+    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
+    if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    mag_newton_options o;
+    mag_default_newton_options(&o);
+    o.increments = spec.increments;
+    o.max_newton = spec.max_newton;
+    o.line_search = spec.line_search;
+    o.cg = spec.cg;
+    o.snapshots = spec.snapshots ? 1 : 0;
+    o.num_probes = (std::int32_t)spec.probes.size();
+    o.memory = MAG_MEM_HOST;
+    o.newton_tol = spec.newton_tol;
+    o.cg_tol = spec.cg_tol;
+    o.load_factors = spec.load_factors.empty() ? nullptr : spec.load_factors.data();
+    o.u0 = spec.u0.empty() ? nullptr : spec.u0.data();
+    o.probes = spec.probes.empty() ? nullptr : spec.probes.data();
+    if (mag_run_newton(ctx, &o) != MAG_OK) return detail::fail_and_destroy(ctx);
+    std::int32_t info[8] = {};
+    if (mag_get_newton_info(ctx, info) != MAG_OK) return detail::fail_and_destroy(ctx);
+    const std::size_t rows = (std::size_t)spec.increments + 1, P = spec.probes.size(), its = (std::size_t)info[3];
+    out = Newton{};
+    out.u.resize(2 * N);
+    out.f.resize(2 * N);
+    out.elem.resize(8 * E);
+    out.probe_u.resize(rows * P);
+    if (spec.snapshots) out.snapshots.resize(rows * 2 * N);
+    out.load.resize(rows);
+    out.energies.resize(2 * rows);
+    out.newton_iterations.resize(rows);
+    out.residuals.resize(its);
+    out.cg_iterations.resize(its);
+    out.step_lengths.resize(its);
+    mag_newton_result d{};
+    d.u_out = out.u.data();
+    d.f_out = out.f.data();
+    d.elem = out.elem.data();
+    if (P) d.probe_u = out.probe_u.data();
+    if (spec.snapshots) d.snapshots = out.snapshots.data();
+    d.load = out.load.data();
+    d.energies = out.energies.data();
+    d.newton_iterations = out.newton_iterations.data();
+    if (its) d.residuals = out.residuals.data(), d.cg_iterations = out.cg_iterations.data(), d.step_lengths = out.step_lengths.data();
+    d.memory = MAG_MEM_HOST;
+    if (mag_download_newton(ctx, &d) != MAG_OK) return detail::fail_and_destroy(ctx);
+    out.increments_converged = info[0];
+    out.cg_kernel = info[1];
+    out.preconditioner = info[2];
+    out.newton_iterations_total = info[3];
+    out.cg_iterations_total = info[4];
+    out.halvings = info[5];
+    out.inverted = info[6] != 0;
+    out.converged = info[7] != 0;
+    if (!out.converged) out.message = mag_last_error(ctx);
+    mag_destroy(ctx);
+    return std::nullopt;
+}
+
+// The consistent tangent K_T(u) of the total-Lagrangian internal force at the displacement u (2N values in the order of `nodes`)
+// as a CSR matrix with mag_assemble_csr's pattern (mag_assemble_tangent).
+inline Result assemble_tangent(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                               const std::vector<double> &u, std::vector<std::int32_t> &rowptr, std::vector<std::int32_t> &col,
+                               std::vector<double> &val, const mag_options *options = nullptr)
+{
+    const std::size_t N = nodes.size();
+    std::vector<double> xy, u_in(2 * N), f_in(2 * N);
+    std::vector<std::uint8_t> u_known;
+    std::vector<std::int32_t> conn;
+    if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
+    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
+    if (u.size() != 2 * N) return detail::solver_error("u has another length than 2 N");
+    mag_ctx *ctx = mag_create(options);
+    if (!ctx) return detail::solver_error("mag_create failed");
+    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
+    if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    std::int64_t nnz = 0;
+    if (mag_assemble_csr(ctx, &nnz, nullptr, nullptr, nullptr) != MAG_OK) return detail::fail_and_destroy(ctx);
+    rowptr.resize(2 * N + 1);
+    col.resize((std::size_t)nnz);
+    val.resize((std::size_t)nnz);
+    if (mag_assemble_csr(ctx, &nnz, rowptr.data(), col.data(), nullptr) != MAG_OK) return detail::fail_and_destroy(ctx);
+    if (mag_assemble_tangent(ctx, u.data(), val.data(), MAG_MEM_HOST) != MAG_OK) return detail::fail_and_destroy(ctx);
     mag_destroy(ctx);
     return std::nullopt;
 }

@@ -35,6 +35,7 @@
 #include "transient.h"
 #include "explicit.h"
 #include "explicit_tl.h"
+#include "newton.h"
 
 using magk::CgState;
 
@@ -127,6 +128,7 @@ enum Pass { PASS_SENS, PASS_ADJOINT, PASS_OBJECTIVE, PASS_STRESS, PASS_COUNT }; 
 //   MAG_TUNE_GRID, MAG_TUNE_DMA          streaming kernels: grid cap, LDS-DMA staging off (cg.hip; tests)
 //   MAG_TUNE_SENS_CHUNK=n                members per launch of the sensitivity kernels (tests; default: a device-memory bound)
 //   MAG_TUNE_SENS_STAGE=0                the node kernel gathers from memory as on tiles too large for the LDS (tests)
+//   MAG_TUNE_NEWTON_TIMES=<file>         mag_run_newton appends the run's phase times to <file> (scripts/newton_probe.py)
 //   MAG_LIB_PATH                         Python binding: load another build of this library (magnetite_amd/_lib.py)
 int env_int(const char *name, int dflt)
 {
@@ -352,6 +354,18 @@ struct mag_ctx {
     DevBuf tl_u, tl_f, tl_part, tl_out;
     int64_t tr_rows = 0;
     double tr_dt = 0.0, tr_dt_bound = 0.0;
+
+    // nonlinear statics (mag_run_newton): the tangent in K's pattern (nt_kval in kval's layout), the block-row table, the gathered
+    // values and the inverse blocks in buffers of the pass's own (tr_* are the transient pass's), the state and its trial, the last
+    // converged state, the step and its support part, a zero vector, f_int, the right-hand side, the results, the device's
+    // records and the scalars of an evaluation; the records the host keeps; the words of mag_get_newton_info.  The results hang on
+    // the upload only: a new mag_upload drops them, a new run replaces them
+    DevBuf nt_kval, nt_width, nt_meta, nt_slot, nt_src, nt_val, nt_minv, nt_hminv;
+    DevBuf nt_u, nt_ut, nt_uc, nt_du, nt_dup, nt_zero, nt_f, nt_rhs, nt_fout, nt_elem, nt_load, nt_probes, nt_bad, nt_probe, nt_snap, nt_part, nt_scal;
+    bool nt_have = false;
+    int32_t nt_info[8] = {}, nt_increments = 0, nt_num_probes = 0, nt_snaps = 0;
+    std::vector<double> nt_loads, nt_energies, nt_residuals, nt_steps;
+    std::vector<int32_t> nt_newton, nt_cg;
 
     magc::Comm comm;
 };
@@ -2593,6 +2607,7 @@ int mag_upload(mag_ctx *ctx, const mag_problem *p)
     ctx->modal.reset();
     ctx->modal_have = false;
     ctx->tr_have = false;
+    ctx->nt_have = false;
     ctx->rf_have = false;
     for (int32_t slot = MAG_SET_RUN; slot <= MAG_SET_VARIANTS; ++slot) drop_derived(ctx, slot);
     return MAG_OK;
@@ -5107,6 +5122,367 @@ int mag_internal_force(mag_ctx *ctx, const double *u, double *f_out, double scal
     HIPCHK(hipStreamSynchronize(s));
     scalars_out[0] = h.w;
     scalars_out[1] = h.inverted ? 1.0 : 0.0;
+    return MAG_OK;
+}
+
+// ---- nonlinear statics (newton.hip): Newton's method on the total-Lagrangian tangent, in load increments.  The driver owns the
+// buffers and enqueues force, tangent, gather and solve of every iteration on the context's stream; between them the host reads
+// one NewtonScalars record per evaluation and the CG's convergence polls, nothing else.  It shares the transient pass's solver
+// set-up (TransientSolves, the poll scheme, build_field_table / field_values / build_reduced) and none of its buffers ----
+void mag_default_newton_options(mag_newton_options *o)
+{
+    if (!o) return;
+    *o = {};
+    o->increments = 1;
+}
+
+int mag_assemble_tangent(mag_ctx *ctx, const double *u, double *values_out, int32_t memory)
+{
+    const char *fn = "mag_assemble_tangent";
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!u) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null u", fn);
+    if (!values_out) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null values_out", fn);
+    if (int rc = memory_refused(ctx, memory, fn)) return rc;
+    if (int rc = transient_refused(ctx, fn)) return rc;
+    if (int rc = enter(ctx)) return rc;
+    if (int rc = ensure_csr(ctx)) return rc;
+    hipStream_t s = ctx->stream;
+    const size_t vb = 16 * (size_t)ctx->N;
+    const hipMemcpyKind in_kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const hipMemcpyKind out_kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    HIPCHK(ctx->nt_ut.reserve(vb));
+    HIPCHK(ctx->nt_kval.reserve(32 * (size_t)ctx->nb));
+    HIPCHK(ctx->nt_bad.reserve(16)); // the first element of signed area <= 0, the inverted flag
+    unsigned long long *d_bad = ctx->nt_bad.as<unsigned long long>();
+    HIPCHK(hipMemsetAsync(d_bad + 1, 0, 8, s));
+    HIPCHK(hipMemcpyAsync(ctx->nt_ut.p, u, vb, in_kind, s));
+    magk::orientation(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), ctx->N, ctx->E, d_bad, s);
+    magk::tl_tangent(tl_mesh(ctx), transient_pattern(ctx), ctx->nt_ut.as<double>(), ctx->nt_kval.as<double>(), (int32_t *)(d_bad + 1), s);
+    HIPCHK(hipGetLastError());
+    unsigned long long bad = ~0ull;
+    HIPCHK(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (bad != ~0ull)
+        return fail(ctx, MAG_ERR_BAD_ARGS,
+                    "%s: element %lld has a signed area <= 0 (the stiffness carries the signed area: the pass needs counter-clockwise elements)", fn,
+                    (long long)bad);
+    HIPCHK(hipMemcpyAsync(values_out, ctx->nt_kval.p, 32 * (size_t)ctx->nb, out_kind, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
+int mag_run_newton(mag_ctx *ctx, const mag_newton_options *o)
+{
+    using magk::NewtonScalars;
+    const char *fn = "mag_run_newton";
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null options", fn);
+    if (o->increments < 1) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: increments = %d: at least one increment", fn, (int)o->increments);
+    if (o->max_newton < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: max_newton = %d is negative", fn, (int)o->max_newton);
+    if (o->line_search < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: line_search = %d is negative", fn, (int)o->line_search);
+    if (!nonneg_finite(o->newton_tol)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: newton_tol %g is negative or not finite", fn, o->newton_tol);
+    if (!nonneg_finite(o->cg_tol)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: cg_tol %g is negative or not finite", fn, o->cg_tol);
+    if (o->cg < 0 || o->cg > 4) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: cg = %d outside 0..4", fn, (int)o->cg);
+    const StepOptions so = {o->increments, 0, o->num_probes, o->probes, o->memory, 0, nullptr, o->u0, nullptr};
+    if (int rc = step_args_tail(ctx, fn, so)) return rc;
+
+    const int32_t incs = o->increments, np = o->num_probes, H = o->line_search;
+    const int32_t cap = o->max_newton > 0 ? o->max_newton : 25;
+    const double tol = o->newton_tol != 0.0 ? o->newton_tol : 1e-10, cg_tol = o->cg_tol != 0.0 ? o->cg_tol : 1e-10;
+    const bool snapshots = o->snapshots != 0;
+    ctx->nt_have = false; // (a failure leaves no results of the pass)
+    hipStream_t s = ctx->stream;
+    const hipMemcpyKind in_kind = step_in_kind(so);
+
+    if (int rc = ensure_csr(ctx)) return rc;
+    if (int rc = reserve_cg(ctx)) return rc;
+    const int64_t N = ctx->N, n2 = 2 * N;
+    const size_t vb = 16 * (size_t)N, rows = (size_t)incs + 1;
+    const magk::Pattern pat = transient_pattern(ctx);
+    const magk::TlMesh mesh = tl_mesh(ctx);
+
+    // ---- the checks that need the device: the elements' orientation, the probes
+    HIPCHK(ctx->nt_bad.reserve(16));
+    HIPCHK(ctx->nt_probes.reserve(4 * (size_t)std::max(np, 1)));
+    unsigned long long words[2] = {~0ull, ~0ull}, *d_words = ctx->nt_bad.as<unsigned long long>();
+    if (np > 0) HIPCHK(hipMemcpyAsync(ctx->nt_probes.p, o->probes, 4 * (size_t)np, in_kind, s));
+    magk::orientation(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), N, ctx->E, d_words, s);
+    magk::check_probes(ctx->nt_probes.as<int32_t>(), np, n2, d_words + 1, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(words, d_words, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (words[0] != ~0ull)
+        return fail(ctx, MAG_ERR_BAD_ARGS,
+                    "%s: element %lld has a signed area <= 0 (the stiffness carries the signed area: the pass needs counter-clockwise elements)", fn,
+                    (long long)words[0]);
+    if (words[1] != ~0ull) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: probes[%lld] is outside [0, %lld)", fn, (long long)words[1], (long long)n2);
+
+    // ---- the solver
+    const bool fused = o->cg == 0 ? ctx->use_lds : o->cg <= 3;
+    if (fused && !ctx->use_lds)
+        return fail(ctx, MAG_ERR_STATE, "%s: cg = %d needs the tile-local tables, which this context does not build (op_variant, or a tile beyond the LDS)", fn,
+                    (int)o->cg);
+    const int kind = !fused ? 0 : (o->cg == 0 ? 2 : o->cg - 1);
+
+    // ---- the buffers, the inputs
+    for (DevBuf *b : {&ctx->nt_u, &ctx->nt_ut, &ctx->nt_uc, &ctx->nt_du, &ctx->nt_dup, &ctx->nt_zero, &ctx->nt_f, &ctx->nt_rhs, &ctx->nt_fout})
+        HIPCHK(b->reserve(vb));
+    HIPCHK(ctx->nt_kval.reserve(32 * (size_t)ctx->nb));
+    HIPCHK(ctx->nt_elem.reserve(64 * (size_t)ctx->E));
+    HIPCHK(ctx->nt_load.reserve(8 * rows));
+    HIPCHK(ctx->nt_probe.reserve(8 * rows * (size_t)std::max(np, 1)));
+    HIPCHK(ctx->nt_snap.reserve(snapshots ? rows * vb : 8));
+    HIPCHK(ctx->nt_part.reserve(8 * 5 * (size_t)magk::kSensBlocks));
+    HIPCHK(ctx->nt_scal.reserve(sizeof(NewtonScalars) + 8)); // (behind the record: the flag of the element rows)
+    HIPCHK(hipMemsetAsync(ctx->nt_zero.p, 0, vb, s));
+    HIPCHK(hipMemsetAsync(ctx->nt_probe.p, 0, 8 * rows * (size_t)std::max(np, 1), s));
+    if (snapshots) HIPCHK(hipMemsetAsync(ctx->nt_snap.p, 0, rows * vb, s));
+    std::vector<double> loads(rows, 0.0);
+    double *d_load = ctx->nt_load.as<double>();
+    if (o->load_factors) {
+        HIPCHK(hipMemsetAsync(d_load, 0, 8, s));
+        HIPCHK(hipMemcpyAsync(d_load + 1, o->load_factors, 8 * (size_t)incs, in_kind, s));
+        HIPCHK(hipMemcpyAsync(loads.data(), d_load, 8 * rows, hipMemcpyDeviceToHost, s));
+    } else {
+        for (int32_t k = 1; k <= incs; ++k) loads[(size_t)k] = (double)k / (double)incs;
+        HIPCHK(hipMemcpyAsync(d_load, loads.data(), 8 * rows, hipMemcpyHostToDevice, s));
+    }
+    if (o->u0)
+        HIPCHK(hipMemcpyAsync(ctx->nt_u.p, o->u0, vb, in_kind, s));
+    else
+        HIPCHK(hipMemsetAsync(ctx->nt_u.p, 0, vb, s));
+    HIPCHK(hipStreamSynchronize(s)); // (the host's copies are done with)
+
+    double *d_u = ctx->nt_u.as<double>(), *d_ut = ctx->nt_ut.as<double>(), *d_uc = ctx->nt_uc.as<double>();
+    double *d_du = ctx->nt_du.as<double>(), *d_dup = ctx->nt_dup.as<double>(), *d_f = ctx->nt_f.as<double>(), *d_rhs = ctx->nt_rhs.as<double>();
+    double *d_kt = ctx->nt_kval.as<double>(), *d_snap = ctx->nt_snap.as<double>(), *d_part = ctx->nt_part.as<double>();
+    const double *d_zero = ctx->nt_zero.as<double>(), *d_fin = ctx->fin.as<double>(), *d_uin = ctx->uin.as<double>();
+    const uint8_t *d_known = ctx->uknown.as<uint8_t>();
+    const int32_t *d_probes = ctx->nt_probes.as<int32_t>();
+    NewtonScalars *d_scal = ctx->nt_scal.as<NewtonScalars>();
+
+    TransientSolves solves(ctx, cg_tol);
+    const int G0 = solves.opt.check_every;
+    FieldTable tab{ctx->nt_width, ctx->nt_meta, ctx->nt_slot, ctx->nt_src, ctx->nt_val};
+    FieldSystem sys = {};
+    if (fused) {
+        if (int rc = build_field_table(ctx, tab)) return rc;
+        sys = {tab.meta.as<magk::FieldTileMeta>(), tab.slot.as<uint16_t>(), tab.val.as<double2>(), nullptr, nullptr, tab.total,
+               magk::field_cg_grid(ctx->B, ctx->cap, ctx->T, kind != 0)};
+    }
+    // the solver's copy of the tangent in nt_kval: the gathered block rows and the inverse blocks, or the reduced system
+    auto system = [&]() -> int {
+        if (!fused) return build_reduced(ctx, true, d_kt, false);
+        if (int rc = field_values(ctx, tab, d_kt, kind, ctx->nt_minv, ctx->nt_hminv)) return rc;
+        sys.minvP = kind ? ctx->nt_minv.as<float4>() : nullptr;
+        sys.halo_minv = kind ? ctx->nt_hminv.as<float4>() : nullptr;
+        return MAG_OK;
+    };
+    // K_T,FF du_F = rhs_F from zero, du_P = dP (the support part of the step, or zero): the transient pass's poll scheme
+    std::vector<int32_t> newton_its(rows, 0), cg_its;
+    std::vector<double> energies(2 * rows, 0.0), residuals, steps;
+    long long all_cg = 0, prev = -1, halvings = 0;
+    auto solve = [&](int32_t inc, int32_t it, const double *dP) -> int {
+        long long G = prev < 0 ? G0 : std::min<long long>(prev + 2, 4096);
+        G += G & 1;
+        ctx->tr_first_block = (int32_t)std::max<long long>(G, 2);
+        ctx->opt.check_every = kTransientPoll;
+        if (fused) {
+            magk::to_hilbert(d_rhs, ctx->iperm.as<int32_t>(), d_known, 0, N, ctx->bP.as<double>(), s);
+            if (int rc = cg_phase_field(ctx, sys)) return rc;
+            magk::scatter_back(ctx->x.as<double>(), ctx->perm.as<uint32_t>(), d_known, dP, N, d_du, s);
+        } else {
+            magk::compact_free(d_rhs, ctx->fidx.as<int32_t>(), d_known, n2, ctx->b_ff.as<double>(), s);
+            if (int rc = cg_phase_csr(ctx, true, dP, d_du)) return rc;
+        }
+        HIPCHK(hipGetLastError());
+        const mag_stats &cs = ctx->stats;
+        if (cs.breakdown)
+            return fail(ctx, MAG_ERR_NOT_CONVERGED, "%s: increment %d, iteration %d: the solve broke down (non-finite residual after %lld iterations)",
+                        fn, (int)inc, (int)it, (long long)cs.iterations);
+        cg_its.push_back((int32_t)cs.iterations);
+        all_cg += cs.iterations;
+        prev = cs.iterations;
+        return MAG_OK;
+    };
+    // f_int, W and the norms of the state w under load[at] (with du: the slope too, of the force that is in nt_f already)
+    auto evaluate = [&](const double *w, int64_t at, NewtonScalars *h) -> int {
+        HIPCHK(hipMemsetAsync(&d_scal->inverted, 0, 4, s));
+        magk::tl_force(mesh, w, d_f, &d_scal->inverted, d_part, &d_scal->W, s);
+        magk::newton_norms(d_known, d_fin, d_load, at, d_f, w, nullptr, n2, d_part, d_scal, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h, d_scal, sizeof(NewtonScalars), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return MAG_OK;
+    };
+    auto record = [&](int64_t row, const NewtonScalars &h) {
+        magk::newton_record(d_uc, d_probes, np, row, ctx->nt_probe.as<double>(), snapshots ? d_snap + (size_t)row * (size_t)n2 : nullptr, n2, s);
+        energies[2 * (size_t)row] = h.W;
+        energies[2 * (size_t)row + 1] = h.W - loads[(size_t)row] * h.fu;
+    };
+
+    // MAG_TUNE_NEWTON_TIMES: the phases of every iteration between events, read behind the evaluation's synchronise
+    const char *times_path = getenv("MAG_TUNE_NEWTON_TIMES");
+    const bool timed = times_path && *times_path;
+    double phase_ms[4] = {0.0, 0.0, 0.0, 0.0}; // tangent + right-hand side, gather, CG, update + force + norms
+    auto stamp = [&](int k) -> int {
+        if (timed) HIPCHK(hipEventRecord(ctx->ev[k], s));
+        return MAG_OK;
+    };
+
+    // ---- the start
+    NewtonScalars cur = {};
+    if (int rc = evaluate(d_u, 0, &cur)) return rc;
+    HIPCHK(hipMemcpyAsync(d_uc, d_u, vb, hipMemcpyDeviceToDevice, s));
+    record(0, cur);
+    bool inverted = false;
+    int32_t done = 0;
+    std::string unconverged;
+
+    // ---- the increments
+    for (int32_t k = 1; k <= incs; ++k) {
+        const double lam = loads[(size_t)k];
+        bool converged = false;
+        double ratio = 0.0;
+        for (int32_t it = 1; it <= cap && !converged; ++it) {
+            const bool first = it == 1;
+            if (int rc = stamp(0)) return rc;
+            magk::tl_tangent(mesh, pat, d_u, d_kt, &d_scal->inverted, s);
+            magk::newton_rhs(pat, d_kt, d_known, d_fin, d_load, k, d_f, d_u, d_uin, first ? 1 : 0, d_rhs, d_dup, s);
+            HIPCHK(hipGetLastError());
+            if (int rc = stamp(1)) return rc;
+            if (int rc = system()) return rc;
+            if (int rc = stamp(2)) return rc;
+            if (int rc = solve(k, it, first ? d_dup : d_zero)) return rc;
+            if (int rc = stamp(3)) return rc;
+            double slope = 0.0;
+            const double Pi0 = cur.W - lam * cur.fu;
+            if (H > 0) { // the slope of Pi along the step, of the force still in nt_f
+                NewtonScalars hs = {};
+                magk::newton_norms(d_known, d_fin, d_load, k, d_f, d_u, d_du, n2, d_part, d_scal, s);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipMemcpyAsync(&hs, d_scal, sizeof(NewtonScalars), hipMemcpyDeviceToHost, s));
+                HIPCHK(hipStreamSynchronize(s));
+                slope = hs.slope;
+            }
+            double sl = 1.0;
+            NewtonScalars trial = {};
+            for (int32_t hv = 0;; ++hv) {
+                magk::newton_update(d_u, d_du, sl, n2, d_ut, s);
+                if (int rc = evaluate(d_ut, k, &trial)) return rc;
+                const double Pi_t = trial.W - lam * trial.fu;
+                const bool energy = slope < 0.0 && std::fabs(sl * slope) > 1e-13 * std::max(std::fabs(Pi0), cur.W) && Pi_t > Pi0 + 1e-4 * sl * slope;
+                if (hv == H || !(trial.inverted || energy)) break;
+                sl *= 0.5;
+                ++halvings;
+            }
+            if (timed) {
+                HIPCHK(hipEventRecord(ctx->ev[4], s));
+                HIPCHK(hipEventSynchronize(ctx->ev[4]));
+                for (int ph = 0; ph < 4; ++ph) {
+                    float ms = 0.0f;
+                    HIPCHK(hipEventElapsedTime(&ms, ctx->ev[ph], ctx->ev[ph + 1]));
+                    phase_ms[ph] += ms;
+                }
+            }
+            std::swap(d_u, d_ut);
+            cur = trial;
+            inverted = inverted || cur.inverted != 0;
+            const double rn = std::sqrt(cur.r2), ref = std::sqrt(std::max(cur.f2, cur.p2));
+            ratio = ref > 0.0 ? rn / ref : (rn == 0.0 ? 0.0 : INFINITY);
+            residuals.push_back(ratio);
+            steps.push_back(sl);
+            converged = rn <= tol * ref;
+            if (converged) newton_its[(size_t)k] = it;
+        }
+        if (!converged) {
+            char buf[256];
+            snprintf(buf, sizeof buf, "%s: increment %d did not converge within %d iterations: |r_F| / ref = %.3e after iteration %d (tolerance %.3e)",
+                     fn, (int)k, (int)cap, ratio, (int)cap, tol);
+            unconverged = buf;
+            break;
+        }
+        HIPCHK(hipMemcpyAsync(d_uc, d_u, vb, hipMemcpyDeviceToDevice, s));
+        record(k, cur);
+        done = k;
+    }
+    for (size_t k = (size_t)done + 1; k < rows; ++k) loads[k] = 0.0;
+
+    // ---- the results of the last converged state: its reactions, its element rows
+    int32_t *d_flag = (int32_t *)(d_scal + 1);
+    magk::tl_force(mesh, d_uc, d_f, d_flag, d_part, nullptr, s);
+    magk::tl_reactions(d_known, d_fin, d_load, done, d_f, n2, ctx->nt_fout.as<double>(), s);
+    magk::newton_elements(mesh, d_uc, ctx->youngs / (1.0 - ctx->nu * ctx->nu), ctx->nt_elem.as<double>(), d_flag, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+
+    int32_t *info = ctx->nt_info;
+    info[0] = done;
+    info[1] = fused ? 5 : 3;
+    info[2] = kind;
+    info[3] = (int32_t)residuals.size();
+    info[4] = (int32_t)std::min<long long>(all_cg, INT32_MAX);
+    info[5] = (int32_t)std::min<long long>(halvings, INT32_MAX);
+    info[6] = inverted ? 1 : 0;
+    info[7] = done == incs ? 1 : 0;
+    ctx->nt_increments = incs;
+    ctx->nt_num_probes = np;
+    ctx->nt_snaps = snapshots ? (int32_t)rows : 0;
+    ctx->nt_loads = loads;
+    ctx->nt_energies = energies;
+    ctx->nt_residuals = residuals;
+    ctx->nt_steps = steps;
+    ctx->nt_newton = newton_its;
+    ctx->nt_cg = cg_its;
+    ctx->nt_have = true;
+    if (timed)
+        if (FILE *tf = fopen(times_path, "a")) {
+            fprintf(tf, "{\"newton_iterations\": %d, \"cg_iterations\": %lld, \"tangent_ms\": %.6f, \"gather_ms\": %.6f, \"cg_ms\": %.6f, \"force_ms\": %.6f}\n",
+                    (int)residuals.size(), all_cg, phase_ms[0], phase_ms[1], phase_ms[2], phase_ms[3]);
+            fclose(tf);
+        }
+    if (!unconverged.empty()) ctx->err = unconverged;
+    return MAG_OK;
+}
+
+int mag_download_newton(mag_ctx *ctx, mag_newton_result *o)
+{
+    const char *fn = "mag_download_newton";
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null result", fn);
+    if (int rc = memory_refused(ctx, o->memory, fn)) return rc;
+    if (ctx->comm.nranks > 1)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: transient dynamics run on one GPU: this context has a communicator of %d ranks", fn, ctx->comm.nranks);
+    if (!ctx->have_problem || !ctx->nt_have) return fail(ctx, MAG_ERR_STATE, "%s before a completed mag_run_newton", fn);
+    if (o->probe_u && ctx->nt_num_probes == 0) return fail(ctx, MAG_ERR_STATE, "%s: the run recorded no probes", fn);
+    if (o->snapshots && ctx->nt_snaps == 0) return fail(ctx, MAG_ERR_STATE, "%s: the run kept no snapshots", fn);
+    if (int rc = enter(ctx)) return rc;
+    const hipMemcpyKind kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const hipMemcpyKind hkind = o->memory == MAG_MEM_DEVICE ? hipMemcpyHostToDevice : hipMemcpyHostToHost;
+    hipStream_t s = ctx->stream;
+    const size_t vb = 16 * (size_t)ctx->N, rows = (size_t)ctx->nt_increments + 1, its = ctx->nt_residuals.size();
+    if (o->u_out) HIPCHK(hipMemcpyAsync(o->u_out, ctx->nt_uc.p, vb, kind, s));
+    if (o->f_out) HIPCHK(hipMemcpyAsync(o->f_out, ctx->nt_fout.p, vb, kind, s));
+    if (o->elem) HIPCHK(hipMemcpyAsync(o->elem, ctx->nt_elem.p, 64 * (size_t)ctx->E, kind, s));
+    if (o->probe_u) HIPCHK(hipMemcpyAsync(o->probe_u, ctx->nt_probe.p, 8 * rows * (size_t)ctx->nt_num_probes, kind, s));
+    if (o->snapshots) HIPCHK(hipMemcpyAsync(o->snapshots, ctx->nt_snap.p, rows * vb, kind, s));
+    if (o->load) HIPCHK(hipMemcpyAsync(o->load, ctx->nt_loads.data(), 8 * rows, hkind, s));
+    if (o->energies) HIPCHK(hipMemcpyAsync(o->energies, ctx->nt_energies.data(), 16 * rows, hkind, s));
+    if (o->newton_iterations) HIPCHK(hipMemcpyAsync(o->newton_iterations, ctx->nt_newton.data(), 4 * rows, hkind, s));
+    if (its > 0) {
+        if (o->residuals) HIPCHK(hipMemcpyAsync(o->residuals, ctx->nt_residuals.data(), 8 * its, hkind, s));
+        if (o->cg_iterations) HIPCHK(hipMemcpyAsync(o->cg_iterations, ctx->nt_cg.data(), 4 * its, hkind, s));
+        if (o->step_lengths) HIPCHK(hipMemcpyAsync(o->step_lengths, ctx->nt_steps.data(), 8 * its, hkind, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
+int mag_get_newton_info(const mag_ctx *ctx, int32_t info[8])
+{
+    if (!ctx || !info || ctx->comm.nranks > 1) return MAG_ERR_BAD_ARGS;
+    if (!ctx->have_problem || !ctx->nt_have) return MAG_ERR_STATE;
+    for (int k = 0; k < 8; ++k) info[k] = ctx->nt_info[k];
     return MAG_OK;
 }
 

@@ -868,6 +868,96 @@ class Context:
         self._check(self._L.mag_internal_force(self._h, _p(u, C.c_double), _p(f, C.c_double), _p(scalars, C.c_double), MAG_MEM_HOST))
         return f, float(scalars[0]), bool(scalars[1] != 0.0)
 
+    # -- nonlinear statics: Newton's method on the total-Lagrangian tangent, in load increments ----------
+    NEWTON_INFO = ("increments_converged", "cg_kernel", "preconditioner", "newton_iterations_total", "cg_iterations_total", "halvings",
+                   "inverted", "converged")
+
+    def run_newton(self, increments=1, load_factors=None, newton_tol=0.0, max_newton=0, line_search=0, cg=0, cg_tol=0.0, u0=None,
+                   probes=(), snapshots=False):
+        """mag_run_newton on the uploaded problem (no run needed): the large-deflection equilibrium in `increments` load increments
+        (include/magnetite_hip.h)."""
+        o = _lib.NewtonOptions()
+        self._L.mag_default_newton_options(C.byref(o))
+        keep = []  # (the arrays the options point to, until the call returns)
+
+        def vec(x, n, what):
+            if x is None:
+                return None
+            a = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+            if a.size != n:
+                raise MagnetiteError("Solver", f"newton: {what} has {a.size} entries where {n} are expected")
+            keep.append(a)
+            return a.ctypes.data
+
+        probes = np.ascontiguousarray(probes, dtype=np.int32).reshape(-1)
+        o.increments, o.max_newton, o.line_search, o.cg = int(increments), int(max_newton), int(line_search), int(cg)
+        o.snapshots, o.num_probes, o.memory = 1 if snapshots else 0, int(probes.size), MAG_MEM_HOST
+        o.newton_tol, o.cg_tol = float(newton_tol), float(cg_tol)
+        o.load_factors = vec(load_factors, max(int(increments), 0), "load_factors")
+        o.u0 = vec(u0, 2 * self.N, "u0")
+        o.probes = probes.ctypes.data if probes.size else None
+        rc = self._check(self._L.mag_run_newton(self._h, C.byref(o)))
+        self._newton_shape = (int(increments), int(probes.size), bool(snapshots))  # (what download_newton sizes)
+        return rc
+
+    def newton_info(self):
+        """The words of mag_get_newton_info by name (NEWTON_INFO)."""
+        info = (C.c_int32 * 8)()
+        self._check(self._L.mag_get_newton_info(self._h, info))
+        return dict(zip(self.NEWTON_INFO, (int(v) for v in info)))
+
+    def download_newton(self):
+        """dict(u, f (2N), elem (E, 8), load, newton_iterations (increments + 1), energies (increments + 1, 2 = W, Pi), residuals,
+        cg_iterations, step_lengths (one entry per Newton iteration of the run), and what the run recorded: probe_u (increments + 1,
+        probes), snapshots (increments + 1, 2N))."""
+        increments, num_probes, snapshots = self._newton_shape
+        rows, n2, its = increments + 1, 2 * self.N, self.newton_info()["newton_iterations_total"]
+        out = dict(u=np.empty(n2), f=np.empty(n2), elem=np.empty((self.E, 8)), load=np.empty(rows), energies=np.empty((rows, 2)),
+                   newton_iterations=np.empty(rows, dtype=np.int32), residuals=np.empty(its), cg_iterations=np.empty(its, dtype=np.int32),
+                   step_lengths=np.empty(its))
+        if num_probes:
+            out["probe_u"] = np.empty((rows, num_probes))
+        if snapshots:
+            out["snapshots"] = np.empty((rows, n2))
+        o = _lib.NewtonResult()
+        o.u_out, o.f_out = out["u"].ctypes.data, out["f"].ctypes.data
+        for k in ("elem", "load", "energies", "newton_iterations", "residuals", "cg_iterations", "step_lengths", "probe_u", "snapshots"):
+            if k in out and out[k].size:
+                setattr(o, k, out[k].ctypes.data)
+        o.memory = MAG_MEM_HOST
+        self._check(self._L.mag_download_newton(self._h, C.byref(o)))
+        return out
+
+    _newton_shape = (0, 0, False)
+
+    def newton(self, prob=None, increments=1, load_factors=None, newton_tol=0.0, max_newton=0, line_search=0, cg=0, cg_tol=0.0, u0=None,
+               probes=(), snapshots=False):
+        """The large-deflection equilibrium of prob (uploaded when given; otherwise of what is uploaded): the arrays of
+        download_newton() and the words of newton_info() by name; `message` is mag_last_error's text when an increment did not
+        converge (converged == 0: the state and the records are the last converged increment's)."""
+        if prob is not None:
+            self.upload_problem(prob)
+        self.run_newton(increments, load_factors, newton_tol, max_newton, line_search, cg, cg_tol, u0, probes, snapshots)
+        out = self.download_newton()
+        info = self.newton_info()
+        out["newton_iterations_total"] = info.pop("newton_iterations_total")
+        out["cg_iterations_total"] = info.pop("cg_iterations_total")
+        out.update(info)
+        if not out["converged"]:
+            out["message"] = self._L.mag_last_error(self._h).decode()
+        return out
+
+    def assemble_tangent(self, u):
+        """The values of the consistent tangent K_T(u) in the layout of assemble_csr() (mag_assemble_tangent)."""
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+        if u.size != 2 * self.N:
+            raise MagnetiteError("Solver", f"assemble_tangent: an array of {u.size} entries where {2 * self.N} are expected")
+        nnz = C.c_int64(0)
+        self._check(self._L.mag_assemble_csr(self._h, C.byref(nnz), None, None, None))
+        val = np.empty(nnz.value)
+        self._check(self._L.mag_assemble_tangent(self._h, _p(u, C.c_double), _p(val, C.c_double), MAG_MEM_HOST))
+        return val
+
     def assemble_effective(self, c_K, c_M, density, lumped=False):
         """The values of c_K K + c_M M in the layout of assemble_csr() (mag_assemble_effective)."""
         nnz = C.c_int64(0)

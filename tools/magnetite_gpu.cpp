@@ -11,6 +11,7 @@
 //                      [--transient STEPS --dt DT --density RHO [--rayleigh A,E] [--probe DOF]...]
 //                      [--explicit STEPS --density RHO [--dt DT | --dt-scale S] [--rayleigh A,E] [--probe DOF]... [--record-every K]
 //                       [--kinematics linear|tl]]
+//                      [--nonlinear INCREMENTS [--newton-tol T] [--line-search H] [--probe DOF]...]
 //   --dry-run  stop before the solver and print what was parsed (no GPU needed)
 //   --rel TOL  stop CG on relative residual TOL instead of the reference's absolute 1e-4
 //   --modal P --density RHO  also print "info: mode k frequency F Hz residual R" for the P lowest modes and write modes.csv
@@ -24,6 +25,11 @@
 //              (--record-every K: steps 0, K, 2K, ...) and write history.csv as --transient does; --kinematics tl: the
 //              total-Lagrangian internal force in place of K u (large rotations; --rayleigh A,0 only), prints "info: explicit
 //              kinematics total-lagrangian" and "warning: explicit: an element was inverted (det F <= 0)" when one was
+//   --nonlinear INCREMENTS  solve the large-deflection equilibrium under the total-Lagrangian internal force in INCREMENTS load
+//              increments of Newton's method (solver::run_newton; --newton-tol T, --line-search H), print "info: increment k load L
+//              newton I cg C residual R" per converged increment, write nodes.csv / elements.csv from the NONLINEAR result (u; the
+//              von Mises value of the second Piola-Kirchhoff stress) and load_path.csv (increment,load,newton,W,Pi, then u per
+//              --probe DOF) next to nodes.csv
 //   --stress-recovery  also write nodes_stress.csv (id,sx,sy,txy,vm) and elements_stress.csv (id,sx,sy,txy,vm,eta2) next to the
 //              two files -- solver::stress_recovery: the tensor per element, the nodal field, the ZZ error indicator -- and
 //              print eta_rel; without it nothing changes
@@ -33,6 +39,7 @@
 //              N nodes, E elements, eta_rel X" per solve, and the two files (and what the other flags write) are the FINAL
 //              mesh's; without it nothing changes
 #include <charconv>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -435,6 +442,32 @@ void history_output(const std::vector<double> &time, const std::vector<std::size
     std::printf("info: wrote the probes' history to %s\n", path.c_str());
 }
 
+// "dir/nodes.csv" -> "dir/load_path.csv"
+std::string load_path_name(const std::string &nodes_output)
+{
+    const size_t slash = nodes_output.find_last_of('/');
+    return (slash == std::string::npos ? std::string() : nodes_output.substr(0, slash + 1)) + "load_path.csv";
+}
+
+// the load-deflection curve of solver::run_newton, a row per converged increment behind the start's, floats as csv_output prints them
+void load_path_output(const Newton &nl, const std::vector<std::int32_t> &probes, const std::string &path)
+{
+    std::FILE *lf = std::fopen(path.c_str(), "w");
+    if (!lf) die({MagnetiteError::Solver, "Failed to create load_path.csv: " + path});
+    std::fputs("increment,load,newton,W,Pi", lf);
+    for (std::int32_t d : probes) std::fprintf(lf, ",u%d", (int)d);
+    std::fputs("\n", lf);
+    const size_t P = probes.size();
+    for (size_t k = 0; k <= (size_t)nl.increments_converged; ++k) {
+        std::fprintf(lf, "%zu,%s,%d,%s,%s", k, rust_display(nl.load[k]).c_str(), (int)nl.newton_iterations[k], rust_display(nl.energies[2 * k]).c_str(),
+                     rust_display(nl.energies[2 * k + 1]).c_str());
+        for (size_t j = 0; j < P; ++j) std::fprintf(lf, ",%s", rust_display(nl.probe_u[k * P + j]).c_str());
+        std::fputs("\n", lf);
+    }
+    std::fclose(lf);
+    std::printf("info: wrote the load path to %s\n", path.c_str());
+}
+
 // "dir/elements.csv" -> "dir/density.csv"
 std::string density_name(const std::string &elements_output)
 {
@@ -464,6 +497,8 @@ int main(int argc, char **argv)
     int modal_modes = 0, adapt = 0, refine_split = 1, topopt = 0, penal = 3, filter_passes = 1, field_cg = 0, transient_steps = 0;
     double rel = 0.0, density = 0.0, refine_fraction = 0.2, volume_fraction = 0.5, dt = 0.0, rayleigh_mass = 0.0, rayleigh_stiffness = 0.0;
     bool transient = false, explicit_run = false;
+    int nonlinear = -1, line_search = 0;
+    double newton_tol = 0.0;
     int explicit_steps = 0, record_every = 1;
     double dt_scale = 0.0;
     std::string kinematics;
@@ -480,6 +515,9 @@ int main(int argc, char **argv)
         else if (a == "--dt-scale" && i + 1 < argc) dt_scale = std::atof(argv[++i]);
         else if (a == "--record-every" && i + 1 < argc) record_every = std::atoi(argv[++i]);
         else if (a == "--kinematics" && i + 1 < argc) kinematics = argv[++i];
+        else if (a == "--nonlinear" && i + 1 < argc) nonlinear = std::atoi(argv[++i]);
+        else if (a == "--newton-tol" && i + 1 < argc) newton_tol = std::atof(argv[++i]);
+        else if (a == "--line-search" && i + 1 < argc) line_search = std::atoi(argv[++i]);
         else if (a == "--probe" && i + 1 < argc) probes.push_back((std::int32_t)std::atoi(argv[++i]));
         else if (a == "--rayleigh" && i + 1 < argc) {
             const std::string pair = argv[++i];
@@ -504,7 +542,7 @@ int main(int argc, char **argv)
         else die({MagnetiteError::Input, "Unrecognized argument " + a});
     }
     if (input.empty() || mesh.empty()) {
-        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery] [--modal P --density RHO] [--transient STEPS --dt DT --density RHO [--rayleigh A,E] [--probe DOF]...] [--explicit STEPS --density RHO [--dt DT | --dt-scale S] [--rayleigh A,E] [--probe DOF]... [--record-every K] [--kinematics linear|tl]] [--adapt R [--refine-fraction T] [--refine-split 1|3]] [--topopt ITERS [--volume-fraction F] [--penal P] [--filter-passes K] [--field-cg 0..3]]\n");
+        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery] [--modal P --density RHO] [--transient STEPS --dt DT --density RHO [--rayleigh A,E] [--probe DOF]...] [--explicit STEPS --density RHO [--dt DT | --dt-scale S] [--rayleigh A,E] [--probe DOF]... [--record-every K] [--kinematics linear|tl]] [--nonlinear INCREMENTS [--newton-tol T] [--line-search H] [--probe DOF]...] [--adapt R [--refine-fraction T] [--refine-split 1|3]] [--topopt ITERS [--volume-fraction F] [--penal P] [--filter-passes K] [--field-cg 0..3]]\n");
         return 2;
     }
     if (modal_modes < 0 || (modal_modes > 0 && !(density > 0.0))) die({MagnetiteError::Input, "--modal P needs P >= 1 and --density RHO > 0"});
@@ -521,7 +559,13 @@ int main(int argc, char **argv)
     const bool total_lagrangian = kinematics == "tl";
     if (total_lagrangian && rayleigh_stiffness != 0.0)
         die({MagnetiteError::Input, "--explicit with --kinematics tl takes --rayleigh A,0: stiffness-proportional damping is not objective"});
-    if (!transient && !explicit_run && (dt != 0.0 || !probes.empty() || rayleigh_mass != 0.0 || rayleigh_stiffness != 0.0))
+    const bool nonlinear_run = nonlinear != -1;
+    if (nonlinear_run && (nonlinear < 1 || newton_tol < 0.0 || line_search < 0))
+        die({MagnetiteError::Input, "--nonlinear INCREMENTS needs INCREMENTS >= 1, --newton-tol T >= 0 and --line-search H >= 0"});
+    if (!nonlinear_run && (newton_tol != 0.0 || line_search != 0)) die({MagnetiteError::Input, "--newton-tol and --line-search need --nonlinear INCREMENTS"});
+    if (nonlinear_run && (transient || explicit_run)) die({MagnetiteError::Input, "--nonlinear shares --probe with --transient and --explicit: one of them at a time"});
+    if (nonlinear_run && adapt > 0) die({MagnetiteError::Input, "--nonlinear solves on the mesh as given: not together with --adapt"});
+    if (!transient && !explicit_run && (dt != 0.0 || (!probes.empty() && !nonlinear_run) || rayleigh_mass != 0.0 || rayleigh_stiffness != 0.0))
         die({MagnetiteError::Input, "--dt, --rayleigh and --probe need --transient STEPS"});
     if (adapt < 0 || !(refine_fraction > 0.0 && refine_fraction <= 1.0) || (refine_split != 1 && refine_split != 3))
         die({MagnetiteError::Input, "--adapt R needs R >= 0, --refine-fraction T in (0, 1] and --refine-split 1 or 3"});
@@ -572,6 +616,9 @@ int main(int argc, char **argv)
                         rust_display(rayleigh_stiffness).c_str(), probes.size(), record_every);
         if (explicit_run && !kinematics.empty())
             std::printf("dry-run: explicit kinematics %s\n", total_lagrangian ? "total-lagrangian" : "linear");
+        if (nonlinear_run)
+            std::printf("dry-run: nonlinear increments %d newton_tol %s line_search %d probes %zu\n", nonlinear, rust_display(newton_tol).c_str(),
+                        line_search, probes.size());
         return 0;
     }
     // solver::run (main.rs:64)
@@ -582,7 +629,7 @@ int main(int argc, char **argv)
         opt.stop_mode = MAG_STOP_REL;
         opt.tol = rel;
     }
-    std::vector<Node> posed = recover || modal_modes > 0 || topopt > 0 || transient || explicit_run ? nodes : std::vector<Node>();  // (run() fills every value in)
+    std::vector<Node> posed = recover || modal_modes > 0 || topopt > 0 || transient || explicit_run || nonlinear_run ? nodes : std::vector<Node>();  // (run() fills every value in)
     if (adapt > 0) {
         RefineSpec spec;
         spec.theta = refine_fraction;
@@ -594,6 +641,37 @@ int main(int argc, char **argv)
                         rust_display(history[r].eta_rel).c_str());
     } else if (Result err = solver::run(nodes, elements, meta, &opt)) {
         die(*err);
+    }
+    if (nonlinear_run) {
+        // The pass needs every element counter-clockwise, as the modal analysis does: the elements go in by their true sign.
+        std::vector<Element> ccw = elements;
+        for (Element &e : ccw)
+            if (solver::compute_element_area(e, posed) < 0.0) std::swap(e.nodes[0], e.nodes[2]);
+        opt.verbose = 0;
+        NewtonSpec spec;
+        spec.increments = nonlinear;
+        spec.newton_tol = newton_tol;
+        spec.line_search = line_search;
+        spec.probes = probes;
+        Newton nl;
+        if (Result err = solver::run_newton(posed, ccw, meta, spec, nl, &opt)) die(*err);
+        size_t at = 0;
+        for (int k = 1; k <= nl.increments_converged; ++k) {
+            int cg = 0;
+            for (int i = 0; i < nl.newton_iterations[(size_t)k]; ++i) cg += nl.cg_iterations[at + (size_t)i];
+            at += (size_t)nl.newton_iterations[(size_t)k];
+            std::printf("info: increment %d load %s newton %d cg %d residual %s\n", k, rust_display(nl.load[(size_t)k]).c_str(),
+                        (int)nl.newton_iterations[(size_t)k], cg, rust_display(nl.residuals[at - 1]).c_str());
+        }
+        if (!nl.converged) std::printf("warning: nonlinear: %s\n", nl.message.c_str());
+        if (nl.inverted) std::printf("warning: nonlinear: an element was inverted (det F <= 0)\n");
+        // nodes.csv / elements.csv carry the nonlinear result: u, and the von Mises value of the second Piola-Kirchhoff stress
+        for (size_t i = 0; i < nodes.size(); ++i) nodes[i].ux = nl.u[2 * i], nodes[i].uy = nl.u[2 * i + 1];
+        for (size_t e = 0; e < elements.size(); ++e) {
+            const double sx = nl.elem[8 * e + 3], sy = nl.elem[8 * e + 4], sxy = nl.elem[8 * e + 5];
+            elements[e].stress = std::sqrt(sx * sx - sx * sy + sy * sy + 3.0 * sxy * sxy);
+        }
+        load_path_output(nl, probes, load_path_name(nodes_out));
     }
     // post_processor::csv_output (main.rs:69); the matplotlib plot (main.rs:72) is not part of this tool
     csv_output(elements, nodes, nodes_out, elements_out);
