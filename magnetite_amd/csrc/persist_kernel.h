@@ -122,9 +122,9 @@ __device__ inline double dpp_move_f64(double v)
     return __hiloint2double(hi, lo);
 }
 
-// The two s_sleep of the exchange's first wait, swept per instantiation in rounds 2-4 (the edge-block one arrives ~1.5 us
-// earlier and settled on the same pair; profiles/r03_persist_ab.txt, the rest in git history).
-constexpr int kPersistSleep1 = 6, kPersistSleep2 = 4;
+// The two s_sleep of the exchange's first wait.  6 + 4 until the exchange issued its halo loads in front of them (rounds 2-4:
+// profiles/r03_persist_ab.txt); re-swept with that placement over 0+0 ... 16+12: 8 + 6 (DESIGN XB, profiles/exchange_batched.json).
+constexpr int kPersistSleep1 = 8, kPersistSleep2 = 6;
 constexpr int kPersistSleepMg = 20; // the multi-GPU exchange's first wait: two s_sleep of this length
 
 // Wait for epoch `epoch`: every workgroup's partial record (two 16-byte pieces each, one per thread) and the q of this
@@ -144,14 +144,63 @@ __device__ inline bool persist_exchange(const PersistParams &P, int par, unsigne
     // thread's halo nodes.
     const unsigned long long *recb = P.recg + 8 * (int64_t)par * grid; // this parity's records: 64 bytes per workgroup
     const unsigned long long *qbase = P.qg + 4 * (int64_t)par * P.N;   // ... and q granules: 32 bytes per node
-    bool have_rec = tid >= 2 * grid, have_h[NH];
+    // The loads of one pass go out TOGETHER, in front of the pass's first wait: one round trip through the memory side per
+    // pass, not one per fetch.  A lane that holds a value already, or has none to fetch, is given the buffer's extent as
+    // its offset: the resources are range-checked (get_granules builds the same ones), such a load returns zeros and moves
+    // nothing.  Values are taken by selects -- around a branch the compiler sinks the load back into it, a basic block with
+    // waits of its own per fetch.
+    const uint32_t rec_bytes = 64u * (uint32_t)grid, q_bytes = 32u * (uint32_t)P.N;
+    const auto rsrc_rec = __builtin_amdgcn_make_buffer_rsrc((void *)recb, (short)0, (int)rec_bytes, 0x00020000);
+    const auto rsrc_q = __builtin_amdgcn_make_buffer_rsrc((void *)qbase, (short)0, (int)q_bytes, 0x00020000);
+    // What a lane still misses IS its offset: the extent once the value is held (or where there is none: tid >= 2 grid lies
+    // beyond the records by itself, hg < 0 is set there) -- no flags beside the offsets in the registers of the loop.  The
+    // offsets are made anew in every exchange (the empty asm hides their sources): hoisted out of the CG loop they cost the
+    // four-slot kernels a register each, all the way round the iteration.
+    int tq = tid;
+    asm volatile("" : "+v"(tq));
+    uint32_t orec = 32u * (uint32_t)tq, oh[NH];
 #pragma unroll
     for (int s = 0; s < NH; ++s) {
-        have_h[s] = hg[s] < 0;
+        int32_t h = hg[s];
+        asm volatile("" : "+v"(h));
+        oh[s] = h < 0 ? q_bytes : 32u * (uint32_t)h;
         hq[s] = make_double2(0.0, 0.0);
     }
+    auto tags_ok = [&](const u32x4 &a, const u32x4 &b) { return a.y == epoch && a.w == epoch && b.y == epoch && b.w == epoch; };
+    auto value_of = [](const u32x4 &a, const u32x4 &b) {
+        const unsigned w[4] = {a.x, a.z, b.x, b.z};
+        double2 v;
+        __builtin_memcpy(&v, w, 16);
+        return v;
+    };
+    // A wave none of whose lanes has a record piece, or an entry s, does not issue those loads at all: loads whose every lane is
+    // out of range are not free (measured: hole1m 0.17 us per iteration for entry 1's, which no lane has; with every wave
+    // issuing all six plate100k is 4 % slower than the parent, with these skips 4 % faster: DESIGN XB).  Wave-uniform and
+    // fixed for the exchange: plain scalar branches, no lane is masked.  The registers are named one by one, not an array:
+    // with arrays behind such branches the compiler merged the entries' blocks and indexed the array in scratch.
+    static_assert(NH == 2, "the halo registers below are written out for two entries");
+    const bool live_rec = __any(orec < rec_bytes ? 1 : 0) != 0, live_h0 = __any(oh[0] != q_bytes ? 1 : 0) != 0,
+               live_h1 = __any(oh[1] != q_bytes ? 1 : 0) != 0;
+    const u32x4 zero4 = {0u, 0u, 0u, 0u};
+    u32x4 h0a = zero4, h0b = zero4, h1a = zero4, h1b = zero4;
+    auto issue_halo = [&]() {
+        if (live_h0) {
+            h0a = __builtin_amdgcn_raw_buffer_load_b128(rsrc_q, (int)oh[0], 0, 16);
+            h0b = __builtin_amdgcn_raw_buffer_load_b128(rsrc_q, (int)oh[0] + 16, 0, 16);
+        }
+        if (live_h1) {
+            h1a = __builtin_amdgcn_raw_buffer_load_b128(rsrc_q, (int)oh[1], 0, 16);
+            h1b = __builtin_amdgcn_raw_buffer_load_b128(rsrc_q, (int)oh[1] + 16, 0, 16);
+        }
+        __builtin_amdgcn_sched_barrier(0); // (pinned where they stand, as ring_walk_blocks pins its gathers)
+    };
     bool done = false;
-    // ~0.85 us in all: the other workgroups' records are still on their way, and a sweep that comes too early costs a full
+    // The halo loads go out BEFORE the wait -- the neighbours published their q during their walks, a microsecond ago -- and
+    // only the record loads behind it; a granule that is not there yet is taken in the next pass.  (With a spin budget of 0,
+    // and after the last pass of an exhausted one, these loads go out and nobody reads them: the registers are dead, the
+    // timeout path is as it was.)
+    issue_halo();
+    // ~0.95 us in all: the other workgroups' records are still on their way, and a sweep that comes too early costs a full
     // round trip.  x += alpha p runs in this wait (the loop of k_cg_persist) and takes about half of it.
     __builtin_amdgcn_s_sleep(kPersistSleep1);
     __builtin_amdgcn_s_sleep(kPersistSleep2);
@@ -164,19 +213,26 @@ __device__ inline bool persist_exchange(const PersistParams &P, int par, unsigne
     bool wave_ok = false;
     unsigned spins = 0;
     for (; spins < P.spin_limit; ++spins) {
-        bool ok = true;
-        if (!have_rec) {
-            double2 v;
-            have_rec = get_granules(recb, 64u * (uint32_t)grid, 32u * (uint32_t)tid, epoch, v);
-            if (have_rec) s_rec[tid] = v;
-            ok = have_rec;
+        u32x4 ra = zero4, rb = zero4;
+        if (live_rec) {
+            ra = __builtin_amdgcn_raw_buffer_load_b128(rsrc_rec, (int)orec, 0, 16);
+            rb = __builtin_amdgcn_raw_buffer_load_b128(rsrc_rec, (int)orec + 16, 0, 16);
         }
+        __builtin_amdgcn_sched_barrier(0); // the pass's loads are all in flight: counted waits from here
+        const bool got_rec = orec < rec_bytes && tags_ok(ra, rb);
+        if (got_rec) s_rec[tid] = value_of(ra, rb);
+        orec = got_rec ? rec_bytes : orec;
+        bool ok = orec >= rec_bytes;
 #pragma unroll
-        for (int s = 0; s < NH; ++s)
-            if (!have_h[s]) {
-                have_h[s] = get_granules(qbase, 32u * (uint32_t)P.N, 32u * (uint32_t)hg[s], epoch, hq[s]);
-                ok &= have_h[s];
-            }
+        for (int s = 0; s < NH; ++s) {
+            const u32x4 &a = s ? h1a : h0a, &b = s ? h1b : h0b;
+            const bool got = oh[s] != q_bytes && tags_ok(a, b);
+            const double2 v = value_of(a, b);
+            hq[s].x = got ? v.x : hq[s].x;
+            hq[s].y = got ? v.y : hq[s].y;
+            oh[s] = got ? q_bytes : oh[s];
+            ok &= oh[s] == q_bytes;
+        }
         if (__all(ok ? 1 : 0)) {
             wave_ok = true;
             break;
@@ -185,6 +241,7 @@ __device__ inline bool persist_exchange(const PersistParams &P, int par, unsigne
             const unsigned dead = (tid & 63) == 0 ? __hip_atomic_load(tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
             if (__any(dead != 0u ? 1 : 0)) break;
         }
+        issue_halo(); // the next pass's, for what is still missing
         __builtin_amdgcn_s_sleep(1);
     }
 #ifdef MAG_PERSIST_STAMPS
