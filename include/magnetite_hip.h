@@ -716,7 +716,7 @@ int mag_assemble_effective(mag_ctx *ctx, double c_K, double c_M, double density,
  *     with the force above per triangle.  A node's sum runs in its ring's order, which depends on tile_nodes: the same bits for
  *     every grid, a repeat and a resumed run, not across tile sizes.  Without the tables a step is four launches (info[2] = 0).
  *   Out of scope: other materials (neo-Hooke, plasticity); stiffness-proportional damping; an updated step bound during the run;
- *     follower loads; contact; the implicit pass with a tangent; fields, variants and ranks; several steps per launch.
+ *     follower loads; contact; fields, variants and ranks; several steps per launch.  (The implicit pass: mag_run_transient_tl.)
  * mag_internal_force: f_out = f_int(u) for all 2N DOFs in caller numbering (u, f_out: 2N doubles in `memory`), scalars_out[0] =
  *   W(u), scalars_out[1] = 1 if some element has det F <= 0, else 0 (written on the host).  The residual of a caller's own
  *   dynamic relaxation or Newton loop.  Needs an upload only and changes no result of the context; mag_run_explicit's refusals
@@ -783,7 +783,8 @@ int mag_internal_force(mag_ctx *ctx, const double *u, double *f_out, double scal
  *   with NULL probes, a `memory` outside enum mag_memory, more than one rank; MAG_ERR_STATE for no upload, an element stiffness
  *   field, assemble_csr = 0 or precision = 1.  After the first device work: an element of signed area <= 0, a probe outside [0, 2N).
  * Out of scope: arc-length and limit points; follower loads; other materials; a warm-started or inexact inner solve; the on-chip
- *   CG on K_T; a matrix-free tangent operator; fields, variants and ranks; an implicit dynamic pass on the tangent. */
+ *   CG on K_T; a matrix-free tangent operator; fields, variants and ranks.  (The implicit dynamic pass on the tangent:
+ *   mag_run_transient_tl below.) */
 typedef struct mag_newton_options {
     int32_t increments, max_newton, line_search, cg, snapshots, num_probes, memory, reserved;
     double newton_tol, cg_tol;
@@ -805,6 +806,81 @@ int mag_run_newton(mag_ctx *ctx, const mag_newton_options *opt);
 int mag_download_newton(mag_ctx *ctx, mag_newton_result *out);
 int mag_get_newton_info(const mag_ctx *ctx, int32_t info[8]);
 int mag_assemble_tangent(mag_ctx *ctx, const double *u, double *values_out, int32_t memory);
+
+/* ---- nonlinear transient dynamics: Newmark steps, Newton's method on the total-Lagrangian tangent, on the device ----
+ * mag_run_transient_tl: implicit dynamics with large rotations -- mag_run_transient's Newmark method in acceleration form with
+ *   K u replaced by the internal force f_int(u) of MAG_KIN_TOTAL_LAGRANGIAN above, every step solved by Newton-Raphson with the
+ *   consistent tangent K_T of mag_run_newton.  The step is not bound by the mesh's fastest mode: what mag_run_explicit with
+ *   kinematics = MAG_KIN_TOTAL_LAGRANGIAN follows in hundreds of steps, this pass follows in one.
+ *   Supports, loads, start, mass and records are mag_run_transient's: u_P = u_in, v_P = a_P = 0; the load on F is
+ *   amplitude[n] f_in; the mass is consistent, or lumped; C = alpha M (rayleigh_mass).  There is no stiffness-proportional term
+ *   (initial-stiffness damping is not objective) and no field for it.
+ *     start   M_FF a_0 = (amplitude[0] f - alpha M v_0 - f_int(u_0))_F
+ *     step    ut = u + dt v + dt^2 (1/2 - beta) a,   vt = v + dt (1 - gamma) a      (on P: ut = u_in, vt = 0)
+ *             unknown a':  u' = ut + beta dt^2 a',   v' = vt + gamma dt a'
+ *             r(a')   = (amplitude[n+1] f - f_int(u') - M (a' + alpha v'))_F
+ *             Newton:  A_T,FF da = r_F,   A_T = (1 + gamma dt alpha) M + beta dt^2 K_T(u'),   a' += da
+ *             first iterate:  a'_F = (u - ut)_F / (beta dt^2), so that u' = u_n (a zero displacement increment)
+ *             stop, judged after every update:  |r_F|_2 <= newton_tol * ref,
+ *                      ref = max(|amplitude[n+1] f_F|, |f_int(u')_F|, |(M (a' + alpha v'))_F|);  newton_tol 0: 1e-10;  max_newton 0: 25
+ *     reactions   f_int(u) + M (a + alpha v) on P,  amplitude[n] f on F
+ *     energies    T = 1/2 v.Mv,  W = the sum of the elements' W_e,  P = amplitude[n] f_F.u_F
+ *   The first iterate is not a free choice.  a' = a_n and a' = 0 move the part by the linear predictor, which rotates it
+ *     linearly and stretches it: at dt = T1 / 20 Newton then diverges or stalls on every case of the tests.  From u' = u_n it
+ *     converges in 3 to 6 iterations a step.
+ *   beta <= 0 is MAG_ERR_BAD_ARGS (beta = 0 leaves no system: that step is mag_run_explicit's); beta and gamma are otherwise taken
+ *     literally.
+ *   An iteration is: the effective tangent A_T in one launch (K_T's row walk, the lane that owns a row finishing it with c_M M; no
+ *     K_T is kept), the gather of A_T into the solver's rows, one CG solve from zero under MAG_STOP_REL with cg_tol (0: 1e-10)
+ *     through mag_run_transient's poll scheme, the state update, f_int, the residual with its norms.  The host reads one record of
+ *     scalars per iteration and the CG's polls, nothing else.  cg = 0..4 selects as in mag_run_transient.
+ *   Not converged within max_newton: no error, as mag_run_newton's increments.  The run ends there; the state and the records
+ *     stay at the last converged step, MAG_OK is returned, mag_get_transient_tl_info's [7] is 0, [0] the steps done, and
+ *     mag_last_error names the step, the iteration count and the ratio |r_F| / ref.  A CG that broke down (non-finite):
+ *     MAG_ERR_NOT_CONVERGED naming step and iteration, no results.  An indefinite A_T is out of scope: the CG needs it positive
+ *     definite (a small enough dt makes it so).
+ *   An inverted element (det F <= 0) in a trial state raises info[6] and is no error.
+ *   Results.  The final state, time, last amplitude, reactions and records go into mag_run_transient's slots:
+ *     mag_download_transient and mag_get_transient_info serve the run (rows: steps done + 1; iterations[n]: the CG iterations of
+ *     step n summed over its Newton iterations, entry 0 the a_0 solve; info[0] the steps done, [3] / [4] the CG iterations of all
+ *     steps / the most of a step, [7] 1 when every step converged).  This pass, mag_run_transient and mag_run_explicit may each
+ *     resume another's state; n1 steps and a resumed n2 give, bit for bit, one run of n1 + n2.
+ * mag_get_transient_tl_info: info[0] steps done, [1] cg_kernel (3 | 5), [2] preconditioner, [3] Newton iterations of all steps,
+ *   [4] the most of one step, [5] CG iterations of all solves (saturating), [6] 1 when an inverted element was seen, [7] 1 when
+ *   every step converged.
+ * mag_download_transient_tl: newton_iterations [steps done + 1] (entry 0 = 0); cg_iterations and residuals (|r_F| / ref after
+ *   the update), one entry per Newton iteration of the run: info[3] entries; elem (E x 8, mag_run_newton's element rows of the
+ *   final state).  NULL members are skipped.  Both need a completed mag_run_transient_tl that no other stepping pass has replaced.
+ * mag_assemble_effective_tangent: values_out = c_K K_T(u) + c_M M in the layout of mag_assemble_csr's val, bit for bit
+ *   mag_assemble_tangent's values combined with mag_assemble_effective's expression.  Needs an upload only.
+ * The pass owns its matrix, table and work buffers: it changes no result of mag_run_newton, of a run, of a set or of
+ *   mag_run_modal.  A repeat gives the same bits (every sum has a fixed order, no floating-point atomics).
+ * Errors: mag_run_transient's rules, order and wording, the pass's own first: MAG_ERR_BAD_ARGS for a null struct, steps < 1, dt or
+ *   density not positive and finite, beta negative, not finite or 0, gamma, rayleigh_mass, cg_tol or newton_tol negative or not
+ *   finite, a negative max_newton, cg outside 0..4; then mag_run_transient's for the records, the context and the resume rule;
+ *   after the first device work an element of signed area <= 0, a probe outside [0, 2N), records beyond device memory.
+ * Out of scope: a line search; modified or quasi-Newton; a warm-started or inexact inner solve; stiffness-proportional damping;
+ *   HHT / generalised-alpha; adaptive dt; time-varying supports; follower loads; other materials; the on-chip CG on A_T; fields,
+ *   variants and ranks. */
+typedef struct mag_transient_tl_options {
+    int32_t steps, resume, lumped, cg, energies, snapshot_every, num_probes, memory, max_newton, reserved;
+    double dt, beta, gamma, density, rayleigh_mass, cg_tol, newton_tol; /* cg_tol, newton_tol 0: 1e-10; max_newton 0: 25 */
+    const double *amplitude, *u0, *v0;                                   /* NULL: ones, zero, zero */
+    const int32_t *probes;                                               /* NULL: none */
+} mag_transient_tl_options;                                              /* 128 bytes */
+typedef struct mag_transient_tl_result {
+    int32_t *newton_iterations; /* [steps done + 1], entry 0 = 0; NULL members are skipped */
+    int32_t *cg_iterations;     /* [info[3]] */
+    double *residuals;          /* [info[3]] */
+    double *elem;               /* E x 8 */
+    int32_t memory, reserved;
+} mag_transient_tl_result;      /* 40 bytes */
+void mag_default_transient_tl_options(mag_transient_tl_options *opt); /* beta 0.25, gamma 0.5, everything else 0 / NULL */
+int mag_run_transient_tl(mag_ctx *ctx, const mag_transient_tl_options *opt);
+int mag_download_transient_tl(mag_ctx *ctx, mag_transient_tl_result *out);
+int mag_get_transient_tl_info(const mag_ctx *ctx, int32_t info[8]);
+int mag_assemble_effective_tangent(mag_ctx *ctx, const double *u, double c_K, double c_M, double density, int32_t lumped, double *values_out,
+                                   int32_t memory);
 
 /* ---- adaptive mesh refinement: longest-edge bisection with conformity closure (Rivara) of the uploaded mesh, on the device ----
  * What acts on the ZZ indicator of mag_run_stress: solve -> mag_run_stress -> mag_run_refine -> mag_upload_refined -> solve, the

@@ -231,6 +231,29 @@ struct Newton {
     std::string message;
 };
 
+// The options of solver::transient_tl (include/magnetite_hip.h, mag_transient_tl_options); 0: the library's default.  amplitude,
+// u0, v0 and probes as TransientSpec's.  There is no stiffness-proportional damping.
+struct TransientTlSpec {
+    std::int32_t steps = 0, cg = 0, snapshot_every = 0, max_newton = 0;
+    bool lumped = false, energies = false;
+    double dt = 0.0, beta = 0.25, gamma = 0.5, density = 0.0, rayleigh_mass = 0.0, cg_tol = 0.0, newton_tol = 0.0;
+    std::vector<double> amplitude, u0, v0;
+    std::vector<std::int32_t> probes;
+};
+
+// What solver::transient_tl returns: solver::transient's outputs (`run`: rows = steps done + 1; run.converged: every step
+// converged) and the outputs of mag_download_transient_tl -- newton_iterations per step (entry 0 = 0), the residual ratio and the CG
+// iterations of every Newton iteration of the run, the final state's element rows (E x 8, as Newton::elem) -- with
+// mag_get_transient_tl_info's words by name.  converged false: a step ran into max_newton (no error); message says which.
+struct TransientTl {
+    Transient run;
+    std::vector<std::int32_t> newton_iterations, newton_cg;
+    std::vector<double> newton_residuals, elements;
+    std::int32_t steps = 0, cg_kernel = 0, preconditioner = 0, newton_iterations_total = 0, max_step_newton = 0, cg_iterations_total = 0;
+    bool inverted = false, converged = false;
+    std::string message;
+};
+
 // What solver::explicit_dt returns (mag_explicit_dt)
 struct ExplicitBound {
     double lambda_bound = 0, dt_bound_undamped = 0, dt_bound = 0, min_mass = 0;
@@ -1054,6 +1077,139 @@ inline Result assemble_tangent(const std::vector<Node> &nodes, const std::vector
     val.resize((std::size_t)nnz);
     if (mag_assemble_csr(ctx, &nnz, rowptr.data(), col.data(), nullptr) != MAG_OK) return detail::fail_and_destroy(ctx);
     if (mag_assemble_tangent(ctx, u.data(), val.data(), MAG_MEM_HOST) != MAG_OK) return detail::fail_and_destroy(ctx);
+    mag_destroy(ctx);
+    return std::nullopt;
+}
+
+// Nonlinear transient dynamics (mag_run_transient_tl) of the part: spec.steps Newmark steps on the total-Lagrangian internal
+// force, every step by Newton's method on the effective tangent; supports, loads and the start as solver::transient.  A step
+// that does not converge within max_newton ends the run and is no error: out.converged is false, the state and the rows are the
+// last converged step's.
+inline Result transient_tl(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                           const TransientTlSpec &spec, TransientTl &out, const mag_options *options = nullptr)
+{
+    const std::size_t N = nodes.size();
+    std::vector<double> xy, u_in(2 * N), f_in(2 * N);
+    std::vector<std::uint8_t> u_known;
+    std::vector<std::int32_t> conn;
+    if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
+    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
+    if (!spec.amplitude.empty() && spec.amplitude.size() != (std::size_t)std::max(spec.steps, 0) + 1)
+        return detail::solver_error("the amplitude has another length than steps + 1");
+    if ((!spec.u0.empty() && spec.u0.size() != 2 * N) || (!spec.v0.empty() && spec.v0.size() != 2 * N))
+        return detail::solver_error("u0 / v0 have another length than 2 N");
+    mag_ctx *ctx = mag_create(options);
+    if (!ctx) return detail::solver_error("mag_create failed");
+    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
+    if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    mag_transient_tl_options o;
+    mag_default_transient_tl_options(&o);
+    o.steps = spec.steps;
+    o.lumped = spec.lumped ? 1 : 0;
+    o.cg = spec.cg;
+    o.energies = spec.energies ? 1 : 0;
+    o.snapshot_every = spec.snapshot_every;
+    o.num_probes = (std::int32_t)spec.probes.size();
+    o.memory = MAG_MEM_HOST;
+    o.max_newton = spec.max_newton;
+    o.dt = spec.dt;
+    o.beta = spec.beta;
+    o.gamma = spec.gamma;
+    o.density = spec.density;
+    o.rayleigh_mass = spec.rayleigh_mass;
+    o.cg_tol = spec.cg_tol;
+    o.newton_tol = spec.newton_tol;
+    o.amplitude = spec.amplitude.empty() ? nullptr : spec.amplitude.data();
+    o.u0 = spec.u0.empty() ? nullptr : spec.u0.data();
+    o.v0 = spec.v0.empty() ? nullptr : spec.v0.data();
+    o.probes = spec.probes.empty() ? nullptr : spec.probes.data();
+    if (mag_run_transient_tl(ctx, &o) != MAG_OK) return detail::fail_and_destroy(ctx);
+    std::int32_t info[8] = {}, ti[8] = {};
+    if (mag_get_transient_info(ctx, info) != MAG_OK) return detail::fail_and_destroy(ctx);
+    if (mag_get_transient_tl_info(ctx, ti) != MAG_OK) return detail::fail_and_destroy(ctx);
+    const std::size_t rows = (std::size_t)info[0] + 1, P = spec.probes.size(), its = (std::size_t)ti[3];
+    out = TransientTl{};
+    Transient &r = out.run;
+    r.u.resize(2 * N);
+    r.v.resize(2 * N);
+    r.a.resize(2 * N);
+    r.f.resize(2 * N);
+    r.probe_u.resize(rows * P);
+    r.probe_v.resize(rows * P);
+    r.probe_a.resize(rows * P);
+    if (spec.energies) r.energies.resize(3 * rows);
+    r.snapshots.resize((std::size_t)info[5] * 2 * N);
+    r.iterations.resize(rows);
+    mag_transient_result d{};
+    d.u_out = r.u.data();
+    d.v_out = r.v.data();
+    d.a_out = r.a.data();
+    d.f_out = r.f.data();
+    if (P) d.probe_u = r.probe_u.data(), d.probe_v = r.probe_v.data(), d.probe_a = r.probe_a.data();
+    if (spec.energies) d.energies = r.energies.data();
+    if (info[5]) d.snapshots = r.snapshots.data();
+    d.iterations = r.iterations.data();
+    d.memory = MAG_MEM_HOST;
+    if (mag_download_transient(ctx, &d) != MAG_OK) return detail::fail_and_destroy(ctx);
+    r.t_start = d.scalars[0];
+    r.t_end = d.scalars[1];
+    r.steps = info[0];
+    r.cg_kernel = info[1];
+    r.preconditioner = info[2];
+    r.cg_iterations = info[3];
+    r.max_step_iterations = info[4];
+    r.snapshots_kept = info[5];
+    r.resumed = info[6];
+    r.converged = info[7];
+    out.newton_iterations.resize(rows);
+    out.newton_cg.resize(its);
+    out.newton_residuals.resize(its);
+    out.elements.resize(8 * elements.size());
+    mag_transient_tl_result t{};
+    t.newton_iterations = out.newton_iterations.data();
+    if (its) t.cg_iterations = out.newton_cg.data(), t.residuals = out.newton_residuals.data();
+    t.elem = out.elements.data();
+    t.memory = MAG_MEM_HOST;
+    if (mag_download_transient_tl(ctx, &t) != MAG_OK) return detail::fail_and_destroy(ctx);
+    out.steps = ti[0];
+    out.cg_kernel = ti[1];
+    out.preconditioner = ti[2];
+    out.newton_iterations_total = ti[3];
+    out.max_step_newton = ti[4];
+    out.cg_iterations_total = ti[5];
+    out.inverted = ti[6] != 0;
+    out.converged = ti[7] != 0;
+    if (!out.converged) out.message = mag_last_error(ctx);
+    mag_destroy(ctx);
+    return std::nullopt;
+}
+
+// c_K K_T(u) + c_M M at the displacement u (2N values in the order of `nodes`) as a CSR matrix with mag_assemble_csr's pattern
+// (mag_assemble_effective_tangent): the matrix of a Newton iteration of solver::transient_tl.
+inline Result assemble_effective_tangent(const std::vector<Node> &nodes, const std::vector<Element> &elements,
+                                         const ModelMetadata &model_metadata, const std::vector<double> &u, double c_K, double c_M,
+                                         double density, bool lumped, std::vector<std::int32_t> &rowptr, std::vector<std::int32_t> &col,
+                                         std::vector<double> &val, const mag_options *options = nullptr)
+{
+    const std::size_t N = nodes.size();
+    std::vector<double> xy, u_in(2 * N), f_in(2 * N);
+    std::vector<std::uint8_t> u_known;
+    std::vector<std::int32_t> conn;
+    if (Result e = detail::flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
+    if (Result e = detail::flatten_elements(elements, N, conn)) return e;
+    if (u.size() != 2 * N) return detail::solver_error("u has another length than 2 N");
+    mag_ctx *ctx = mag_create(options);
+    if (!ctx) return detail::solver_error("mag_create failed");
+    const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
+    if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    std::int64_t nnz = 0;
+    if (mag_assemble_csr(ctx, &nnz, nullptr, nullptr, nullptr) != MAG_OK) return detail::fail_and_destroy(ctx);
+    rowptr.resize(2 * N + 1);
+    col.resize((std::size_t)nnz);
+    val.resize((std::size_t)nnz);
+    if (mag_assemble_csr(ctx, &nnz, rowptr.data(), col.data(), nullptr) != MAG_OK) return detail::fail_and_destroy(ctx);
+    if (mag_assemble_effective_tangent(ctx, u.data(), c_K, c_M, density, lumped ? 1 : 0, val.data(), MAG_MEM_HOST) != MAG_OK)
+        return detail::fail_and_destroy(ctx);
     mag_destroy(ctx);
     return std::nullopt;
 }

@@ -44,6 +44,8 @@ SYMBOLS = [
     "mag_default_transient_options", "mag_run_transient", "mag_download_transient", "mag_get_transient_info", "mag_assemble_effective",
     "mag_default_explicit_options", "mag_run_explicit", "mag_explicit_dt", "mag_internal_force",
     "mag_default_newton_options", "mag_run_newton", "mag_download_newton", "mag_get_newton_info", "mag_assemble_tangent",
+    "mag_default_transient_tl_options", "mag_run_transient_tl", "mag_download_transient_tl", "mag_get_transient_tl_info",
+    "mag_assemble_effective_tangent",
     "mag_run_refine", "mag_get_refine_info", "mag_download_refine", "mag_upload_refined",
     "mag_set_element_scale", "mag_design_init", "mag_design_step", "mag_get_design_info", "mag_download_design",
     "mag_comm_get_unique_id", "mag_comm_init_rccl", "mag_comm_query", "mag_comm_init_callback", "mag_comm_set_window", "mag_comm_inbox_create", "mag_comm_inbox_open",
@@ -155,6 +157,20 @@ class NewtonResult(C.Structure):
     _fields_ = [("u_out", C.c_void_p), ("f_out", C.c_void_p), ("elem", C.c_void_p), ("probe_u", C.c_void_p), ("snapshots", C.c_void_p),
                 ("load", C.c_void_p), ("energies", C.c_void_p), ("newton_iterations", C.c_void_p), ("residuals", C.c_void_p),
                 ("cg_iterations", C.c_void_p), ("step_lengths", C.c_void_p), ("memory", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TransientTlOptions(C.Structure):
+    _fields_ = [("steps", C.c_int32), ("resume", C.c_int32), ("lumped", C.c_int32), ("cg", C.c_int32), ("energies", C.c_int32),
+                ("snapshot_every", C.c_int32), ("num_probes", C.c_int32), ("memory", C.c_int32), ("max_newton", C.c_int32),
+                ("reserved", C.c_int32),
+                ("dt", C.c_double), ("beta", C.c_double), ("gamma", C.c_double), ("density", C.c_double),
+                ("rayleigh_mass", C.c_double), ("cg_tol", C.c_double), ("newton_tol", C.c_double),
+                ("amplitude", C.c_void_p), ("u0", C.c_void_p), ("v0", C.c_void_p), ("probes", C.c_void_p)]
+
+
+class TransientTlResult(C.Structure):
+    _fields_ = [("newton_iterations", C.c_void_p), ("cg_iterations", C.c_void_p), ("residuals", C.c_void_p), ("elem", C.c_void_p),
+                ("memory", C.c_int32), ("reserved", C.c_int32)]
 
 
 class RefineOptions(C.Structure):
@@ -290,6 +306,13 @@ def lib():
         L.mag_download_newton.argtypes = [vp, C.POINTER(NewtonResult)]
         L.mag_get_newton_info.argtypes = [vp, ip]
         L.mag_assemble_tangent.argtypes = [vp, dp, dp, C.c_int32]
+    if hasattr(L, "mag_run_transient_tl"):  # (likewise: scripts/transient_tl_probe.py)
+        L.mag_default_transient_tl_options.argtypes = [C.POINTER(TransientTlOptions)]
+        L.mag_default_transient_tl_options.restype = None
+        L.mag_run_transient_tl.argtypes = [vp, C.POINTER(TransientTlOptions)]
+        L.mag_download_transient_tl.argtypes = [vp, C.POINTER(TransientTlResult)]
+        L.mag_get_transient_tl_info.argtypes = [vp, ip]
+        L.mag_assemble_effective_tangent.argtypes = [vp, dp, C.c_double, C.c_double, C.c_double, C.c_int32, dp, C.c_int32]
     if hasattr(L, "mag_run_refine"):  # (likewise: scripts/refine_probe.py)
         L.mag_run_refine.argtypes = [vp, C.POINTER(RefineOptions)]
         L.mag_get_refine_info.argtypes = [vp, C.POINTER(C.c_int64)]

@@ -36,6 +36,7 @@
 #include "explicit.h"
 #include "explicit_tl.h"
 #include "newton.h"
+#include "transient_tl.h"
 
 using magk::CgState;
 
@@ -129,6 +130,7 @@ enum Pass { PASS_SENS, PASS_ADJOINT, PASS_OBJECTIVE, PASS_STRESS, PASS_COUNT }; 
 //   MAG_TUNE_SENS_CHUNK=n                members per launch of the sensitivity kernels (tests; default: a device-memory bound)
 //   MAG_TUNE_SENS_STAGE=0                the node kernel gathers from memory as on tiles too large for the LDS (tests)
 //   MAG_TUNE_NEWTON_TIMES=<file>         mag_run_newton appends the run's phase times to <file> (scripts/newton_probe.py)
+//   MAG_TUNE_TRANSIENT_TL_TIMES=<file>   mag_run_transient_tl appends the run's phase times to <file> (scripts/transient_tl_probe.py)
 //   MAG_LIB_PATH                         Python binding: load another build of this library (magnetite_amd/_lib.py)
 int env_int(const char *name, int dflt)
 {
@@ -366,6 +368,18 @@ struct mag_ctx {
     int32_t nt_info[8] = {}, nt_increments = 0, nt_num_probes = 0, nt_snaps = 0;
     std::vector<double> nt_loads, nt_energies, nt_residuals, nt_steps;
     std::vector<int32_t> nt_newton, nt_cg;
+
+    // nonlinear transient dynamics (mag_run_transient_tl): the effective tangent in K's pattern (tt_aval in kval's layout), the
+    // block-row table, the gathered values and the inverse blocks in buffers of the pass's own, the trial state (a', u', v'), the
+    // Newton step, f_int, the element rows, the scalars of an iteration, the partials; the records the host keeps; the words of
+    // mag_get_transient_tl_info.  The final state and the step records are in the transient pass's slots (tr_*).  tt_u, tt_bad:
+    // mag_assemble_effective_tangent's state and flags
+    DevBuf tt_aval, tt_width, tt_meta, tt_slot, tt_src, tt_val, tt_minv, tt_hminv;
+    DevBuf tt_an, tt_un, tt_vn, tt_da, tt_fint, tt_elem, tt_scal, tt_part, tt_move, tt_u, tt_bad;
+    bool tt_have = false;
+    int32_t tt_info[8] = {};
+    std::vector<double> tt_residuals;
+    std::vector<int32_t> tt_newton, tt_cg;
 
     magc::Comm comm;
 };
@@ -2608,6 +2622,7 @@ int mag_upload(mag_ctx *ctx, const mag_problem *p)
     ctx->modal_have = false;
     ctx->tr_have = false;
     ctx->nt_have = false;
+    ctx->tt_have = false;
     ctx->rf_have = false;
     for (int32_t slot = MAG_SET_RUN; slot <= MAG_SET_VARIANTS; ++slot) drop_derived(ctx, slot);
     return MAG_OK;
@@ -4338,6 +4353,67 @@ struct TransientSolves {
 
 constexpr int kTransientPoll = 8; // launches per poll block behind a solve's first block (even: the parity restarts per block)
 
+// What the inner solves of the two Newton passes (mag_run_newton, mag_run_transient_tl) share: a matrix in kval's layout, the
+// pass's own block-row table and inverse blocks (or the reduced system of the CSR phase), and the transient pass's poll scheme,
+// in one place.  Used inside a TransientSolves scope.
+struct PatternSolver {
+    mag_ctx *ctx;
+    bool fused;
+    int kind;
+    FieldTable tab;
+    DevBuf &minv, &hminv;
+    int G0; // the context's check_every: the first poll block of the first solve
+    FieldSystem sys = {};
+    long long prev = -1; // the iterations of the previous solve
+
+    int init()
+    {
+        if (!fused) return MAG_OK;
+        if (int rc = build_field_table(ctx, tab)) return rc;
+        sys = {tab.meta.as<magk::FieldTileMeta>(), tab.slot.as<uint16_t>(), tab.val.as<double2>(), nullptr, nullptr, tab.total,
+               magk::field_cg_grid(ctx->B, ctx->cap, ctx->T, kind != 0)};
+        return MAG_OK;
+    }
+    // the solver's copy of the matrix in val: the gathered block rows and the inverse blocks, or the reduced system
+    int system(const double *val)
+    {
+        if (!fused) return build_reduced(ctx, true, val, false);
+        if (int rc = field_values(ctx, tab, val, kind, minv, hminv)) return rc;
+        sys.minvP = kind ? minv.as<float4>() : nullptr;
+        sys.halo_minv = kind ? hminv.as<float4>() : nullptr;
+        return MAG_OK;
+    }
+    // A_FF x_F = rhs_F from zero, x_P = xP.  The poll's first block: the previous solve's iteration count + 2 (a launch judges the
+    // iterate of the one before), rounded up to even -- the context's check_every for the first solve --, then blocks of
+    // kTransientPoll.  before / after: events recorded around the CG itself (behind the move into the solver's numbering, in
+    // front of the move back).  The statistics of the solve are the context's (ctx->stats) on return
+    int solve(const double *rhs, const double *xP, double *x, hipEvent_t before = nullptr, hipEvent_t after = nullptr)
+    {
+        hipStream_t s = ctx->stream;
+        const int64_t N = ctx->N;
+        const uint8_t *known = ctx->uknown.as<uint8_t>();
+        long long G = prev < 0 ? G0 : std::min<long long>(prev + 2, 4096);
+        G += G & 1;
+        ctx->tr_first_block = (int32_t)std::max<long long>(G, 2);
+        ctx->opt.check_every = kTransientPoll;
+        if (fused) {
+            magk::to_hilbert(rhs, ctx->iperm.as<int32_t>(), known, 0, N, ctx->bP.as<double>(), s);
+            if (before) HIPCHK(hipEventRecord(before, s));
+            if (int rc = cg_phase_field(ctx, sys)) return rc;
+            if (after) HIPCHK(hipEventRecord(after, s));
+            magk::scatter_back(ctx->x.as<double>(), ctx->perm.as<uint32_t>(), known, xP, N, x, s);
+        } else {
+            magk::compact_free(rhs, ctx->fidx.as<int32_t>(), known, 2 * N, ctx->b_ff.as<double>(), s);
+            if (before) HIPCHK(hipEventRecord(before, s));
+            if (int rc = cg_phase_csr(ctx, true, xP, x)) return rc;
+            if (after) HIPCHK(hipEventRecord(after, s));
+        }
+        HIPCHK(hipGetLastError());
+        prev = ctx->stats.iterations;
+        return MAG_OK;
+    }
+};
+
 inline bool nonneg_finite(double x) { return x >= 0.0 && std::isfinite(x); }
 inline bool pos_finite(double x) { return x > 0.0 && std::isfinite(x); }
 
@@ -4650,7 +4726,7 @@ int mag_run_transient(mag_ctx *ctx, const mag_transient_options *o)
     const double cg_tol = o->cg_tol != 0.0 ? o->cg_tol : 1e-10;
     const double t_start = resume ? ctx->tr_t1 : 0.0;
     const double amp_first = ctx->tr_amp_last; // (a resumed run's row 0 carries the load of the state it resumes)
-    ctx->tr_have = false; // (a failure leaves no results of the pass)
+    ctx->tr_have = ctx->tt_have = false; // (a failure leaves no results of the pass)
     hipStream_t s = ctx->stream;
 
     if (int rc = transient_matrices(ctx, o->density, o->lumped)) return rc;
@@ -4907,7 +4983,7 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
     const double alpha = o->rayleigh_mass, eta = o->rayleigh_stiffness;
     const double t_start = resume ? ctx->tr_t1 : 0.0;
     const double amp_first = ctx->tr_amp_last; // (a resumed run's row 0 carries the load of the state it resumes)
-    ctx->tr_have = false; // (a failure leaves no results of the pass)
+    ctx->tr_have = ctx->tt_have = false; // (a failure leaves no results of the pass)
     hipStream_t s = ctx->stream;
 
     if (int rc = transient_matrices(ctx, o->density, 1)) return rc;
@@ -5262,47 +5338,23 @@ int mag_run_newton(mag_ctx *ctx, const mag_newton_options *o)
     NewtonScalars *d_scal = ctx->nt_scal.as<NewtonScalars>();
 
     TransientSolves solves(ctx, cg_tol);
-    const int G0 = solves.opt.check_every;
-    FieldTable tab{ctx->nt_width, ctx->nt_meta, ctx->nt_slot, ctx->nt_src, ctx->nt_val};
-    FieldSystem sys = {};
-    if (fused) {
-        if (int rc = build_field_table(ctx, tab)) return rc;
-        sys = {tab.meta.as<magk::FieldTileMeta>(), tab.slot.as<uint16_t>(), tab.val.as<double2>(), nullptr, nullptr, tab.total,
-               magk::field_cg_grid(ctx->B, ctx->cap, ctx->T, kind != 0)};
-    }
-    // the solver's copy of the tangent in nt_kval: the gathered block rows and the inverse blocks, or the reduced system
-    auto system = [&]() -> int {
-        if (!fused) return build_reduced(ctx, true, d_kt, false);
-        if (int rc = field_values(ctx, tab, d_kt, kind, ctx->nt_minv, ctx->nt_hminv)) return rc;
-        sys.minvP = kind ? ctx->nt_minv.as<float4>() : nullptr;
-        sys.halo_minv = kind ? ctx->nt_hminv.as<float4>() : nullptr;
-        return MAG_OK;
-    };
+    PatternSolver ps{ctx, fused, kind, FieldTable{ctx->nt_width, ctx->nt_meta, ctx->nt_slot, ctx->nt_src, ctx->nt_val}, ctx->nt_minv, ctx->nt_hminv,
+                     solves.opt.check_every};
+    if (int rc = ps.init()) return rc;
+    // the solver's copy of the tangent in nt_kval
+    auto system = [&]() -> int { return ps.system(d_kt); };
     // K_T,FF du_F = rhs_F from zero, du_P = dP (the support part of the step, or zero): the transient pass's poll scheme
     std::vector<int32_t> newton_its(rows, 0), cg_its;
     std::vector<double> energies(2 * rows, 0.0), residuals, steps;
-    long long all_cg = 0, prev = -1, halvings = 0;
+    long long all_cg = 0, halvings = 0;
     auto solve = [&](int32_t inc, int32_t it, const double *dP) -> int {
-        long long G = prev < 0 ? G0 : std::min<long long>(prev + 2, 4096);
-        G += G & 1;
-        ctx->tr_first_block = (int32_t)std::max<long long>(G, 2);
-        ctx->opt.check_every = kTransientPoll;
-        if (fused) {
-            magk::to_hilbert(d_rhs, ctx->iperm.as<int32_t>(), d_known, 0, N, ctx->bP.as<double>(), s);
-            if (int rc = cg_phase_field(ctx, sys)) return rc;
-            magk::scatter_back(ctx->x.as<double>(), ctx->perm.as<uint32_t>(), d_known, dP, N, d_du, s);
-        } else {
-            magk::compact_free(d_rhs, ctx->fidx.as<int32_t>(), d_known, n2, ctx->b_ff.as<double>(), s);
-            if (int rc = cg_phase_csr(ctx, true, dP, d_du)) return rc;
-        }
-        HIPCHK(hipGetLastError());
+        if (int rc = ps.solve(d_rhs, dP, d_du)) return rc;
         const mag_stats &cs = ctx->stats;
         if (cs.breakdown)
             return fail(ctx, MAG_ERR_NOT_CONVERGED, "%s: increment %d, iteration %d: the solve broke down (non-finite residual after %lld iterations)",
                         fn, (int)inc, (int)it, (long long)cs.iterations);
         cg_its.push_back((int32_t)cs.iterations);
         all_cg += cs.iterations;
-        prev = cs.iterations;
         return MAG_OK;
     };
     // f_int, W and the norms of the state w under load[at] (with du: the slope too, of the force that is in nt_f already)
@@ -5483,6 +5535,344 @@ int mag_get_newton_info(const mag_ctx *ctx, int32_t info[8])
     if (!ctx || !info || ctx->comm.nranks > 1) return MAG_ERR_BAD_ARGS;
     if (!ctx->have_problem || !ctx->nt_have) return MAG_ERR_STATE;
     for (int k = 0; k < 8; ++k) info[k] = ctx->nt_info[k];
+    return MAG_OK;
+}
+
+// ---- nonlinear transient dynamics (transient_tl.hip): Newmark's method on the total-Lagrangian internal force, every step by
+// Newton's method on the effective tangent.  The driver owns its matrix, table and work buffers, shares the step frame of
+// mag_run_transient / mag_run_explicit (the checks, the inputs, the records, the result slots) and the solver set-up of
+// mag_run_newton (TransientSolves, the poll scheme); between the launches the host reads one TlStepScalars record per Newton
+// iteration and the CG's convergence polls, nothing else ----
+void mag_default_transient_tl_options(mag_transient_tl_options *o)
+{
+    if (!o) return;
+    *o = {};
+    o->beta = 0.25;
+    o->gamma = 0.5;
+}
+
+int mag_assemble_effective_tangent(mag_ctx *ctx, const double *u, double c_K, double c_M, double density, int32_t lumped, double *values_out,
+                                   int32_t memory)
+{
+    const char *fn = "mag_assemble_effective_tangent";
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!u) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null u", fn);
+    if (!values_out) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null values_out", fn);
+    if (!std::isfinite(c_K) || !std::isfinite(c_M)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: c_K %g / c_M %g is not finite", fn, c_K, c_M);
+    if (!pos_finite(density)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: density %g is not positive and finite", fn, density);
+    if (int rc = memory_refused(ctx, memory, fn)) return rc;
+    if (int rc = transient_refused(ctx, fn)) return rc;
+    if (int rc = enter(ctx)) return rc;
+    if (int rc = transient_matrices(ctx, density, lumped)) return rc;
+    hipStream_t s = ctx->stream;
+    const size_t vb = 16 * (size_t)ctx->N;
+    const hipMemcpyKind in_kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const hipMemcpyKind out_kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    HIPCHK(ctx->tt_u.reserve(vb));
+    HIPCHK(ctx->tt_aval.reserve(32 * (size_t)ctx->nb));
+    HIPCHK(ctx->tt_bad.reserve(16)); // the first element of signed area <= 0, the inverted flag
+    unsigned long long *d_bad = ctx->tt_bad.as<unsigned long long>();
+    HIPCHK(hipMemsetAsync(d_bad + 1, 0, 8, s));
+    HIPCHK(hipMemcpyAsync(ctx->tt_u.p, u, vb, in_kind, s));
+    magk::orientation(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), ctx->N, ctx->E, d_bad, s);
+    magk::tl_effective_tangent(tl_mesh(ctx), transient_pattern(ctx), ctx->tt_u.as<double>(), ctx->tr_mval.as<double>(), c_K, c_M,
+                               ctx->tt_aval.as<double>(), (int32_t *)(d_bad + 1), s);
+    HIPCHK(hipGetLastError());
+    unsigned long long bad = ~0ull;
+    HIPCHK(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (bad != ~0ull)
+        return fail(ctx, MAG_ERR_BAD_ARGS,
+                    "%s: element %lld has a signed area <= 0 (the stiffness carries the signed area: the pass needs counter-clockwise elements)", fn,
+                    (long long)bad);
+    HIPCHK(hipMemcpyAsync(values_out, ctx->tt_aval.p, 32 * (size_t)ctx->nb, out_kind, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
+int mag_run_transient_tl(mag_ctx *ctx, const mag_transient_tl_options *o)
+{
+    using magk::TlStepScalars;
+    const char *fn = "mag_run_transient_tl";
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null options", fn);
+    if (o->steps < 1) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: steps = %d: at least one step", fn, (int)o->steps);
+    if (!pos_finite(o->dt)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: dt %g is not positive and finite", fn, o->dt);
+    if (!pos_finite(o->density)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: density %g is not positive and finite", fn, o->density);
+    if (!nonneg_finite(o->beta)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: beta %g is negative or not finite", fn, o->beta);
+    if (o->beta == 0.0)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: beta = 0 leaves no system to solve: the explicit step is mag_run_explicit's (kinematics = MAG_KIN_TOTAL_LAGRANGIAN)",
+                    fn);
+    if (!nonneg_finite(o->gamma)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: gamma %g is negative or not finite", fn, o->gamma);
+    if (!nonneg_finite(o->rayleigh_mass)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: rayleigh_mass %g is negative or not finite", fn, o->rayleigh_mass);
+    if (!nonneg_finite(o->cg_tol)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: cg_tol %g is negative or not finite", fn, o->cg_tol);
+    if (!nonneg_finite(o->newton_tol)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: newton_tol %g is negative or not finite", fn, o->newton_tol);
+    if (o->max_newton < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: max_newton = %d is negative", fn, (int)o->max_newton);
+    if (o->cg < 0 || o->cg > 4) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: cg = %d outside 0..4", fn, (int)o->cg);
+    const StepOptions so = {o->steps, o->snapshot_every, o->num_probes, o->probes, o->memory, o->resume, o->amplitude, o->u0, o->v0};
+    if (int rc = step_args_tail(ctx, fn, so)) return rc;
+
+    const bool resume = o->resume != 0, energies = o->energies != 0;
+    const int32_t steps = o->steps, np = o->num_probes, se = o->snapshot_every;
+    const int32_t cap = o->max_newton > 0 ? o->max_newton : 25;
+    const double dt = o->dt, beta = o->beta, gamma = o->gamma, alpha = o->rayleigh_mass;
+    const double tol = o->newton_tol != 0.0 ? o->newton_tol : 1e-10, cg_tol = o->cg_tol != 0.0 ? o->cg_tol : 1e-10;
+    const double c_u = beta * dt * dt, c_v = gamma * dt, c_M = 1.0 + gamma * dt * alpha;
+    const double t_start = resume ? ctx->tr_t1 : 0.0;
+    const double amp_first = ctx->tr_amp_last; // (a resumed run's row 0 carries the load of the state it resumes)
+    ctx->tr_have = ctx->tt_have = false; // (a failure leaves no results of the pass)
+    hipStream_t s = ctx->stream;
+
+    if (int rc = transient_matrices(ctx, o->density, o->lumped)) return rc;
+    if (int rc = reserve_cg(ctx)) return rc;
+    const int64_t N = ctx->N, n2 = 2 * N;
+    const size_t vb = 16 * (size_t)N;
+    const magk::Pattern pat = transient_pattern(ctx);
+    const magk::TlMesh mesh = tl_mesh(ctx);
+
+    // ---- the checks that need the device: the elements' orientation, the probes
+    StepWords words;
+    if (int rc = step_checks_enqueue(ctx, so, &words)) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    if (int rc = step_checks_report(ctx, fn, words)) return rc;
+
+    // ---- the solver
+    const bool fused = o->cg == 0 ? ctx->use_lds : o->cg <= 3;
+    if (fused && !ctx->use_lds)
+        return fail(ctx, MAG_ERR_STATE, "%s: cg = %d needs the tile-local tables, which this context does not build (op_variant, or a tile beyond the LDS)", fn,
+                    (int)o->cg);
+    const int kind = !fused ? 0 : (o->cg == 0 ? 2 : o->cg - 1);
+
+    // ---- the buffers, the inputs
+    const size_t rows = (size_t)steps + 1, snaps = se > 0 ? (size_t)(steps / se) + 1 : 0;
+    if (int rc = step_buffers(ctx, fn, steps, rows, rows, snaps, np, resume)) return rc;
+    StepInputs in;
+    if (int rc = step_inputs(ctx, so, rows, amp_first, &in)) return rc;
+    const magk::NewmarkState st = newmark_state(ctx, rows, np);
+    for (DevBuf *b : {&ctx->tt_an, &ctx->tt_un, &ctx->tt_vn, &ctx->tt_da, &ctx->tt_fint}) HIPCHK(b->reserve(vb));
+    HIPCHK(ctx->tt_aval.reserve(32 * (size_t)ctx->nb));
+    HIPCHK(ctx->tt_elem.reserve(64 * (size_t)ctx->E));
+    HIPCHK(ctx->tt_part.reserve(8 * 4 * (size_t)magk::kSensBlocks));
+    HIPCHK(ctx->tt_scal.reserve(sizeof(TlStepScalars) + 8)); // (behind the record: the flag of the element rows)
+    double *d_rhs = ctx->tr_rhs.as<double>(), *d_snap = ctx->tr_snap.as<double>(), *d_amp = ctx->tr_amp.as<double>();
+    double *d_an = ctx->tt_an.as<double>(), *d_un = ctx->tt_un.as<double>(), *d_vn = ctx->tt_vn.as<double>(), *d_da = ctx->tt_da.as<double>();
+    double *d_fint = ctx->tt_fint.as<double>(), *d_at = ctx->tt_aval.as<double>(), *d_part = ctx->tt_part.as<double>();
+    const double *d_m = ctx->tr_mval.as<double>(), *d_f = ctx->fin.as<double>(), *d_zero = ctx->tr_zero.as<double>();
+    TlStepScalars *d_scal = ctx->tt_scal.as<TlStepScalars>();
+    HIPCHK(hipMemsetAsync(d_scal, 0, sizeof(TlStepScalars) + 8, s));
+
+    TransientSolves solves(ctx, cg_tol);
+    PatternSolver ps{ctx, fused, kind, FieldTable{ctx->tt_width, ctx->tt_meta, ctx->tt_slot, ctx->tt_src, ctx->tt_val}, ctx->tt_minv, ctx->tt_hminv,
+                     solves.opt.check_every};
+    if (int rc = ps.init()) return rc;
+    // A_T = cm M + ck K_T(w) in tt_aval, one launch
+    auto tangent = [&](double cm, double ck, const double *w) -> int {
+        magk::tl_effective_tangent(mesh, pat, w, d_m, ck, cm, d_at, &d_scal->inverted, s);
+        HIPCHK(hipGetLastError());
+        return MAG_OK;
+    };
+    // MAG_TUNE_TRANSIENT_TL_TIMES: the phases of every iteration between events, read behind the iteration's synchronise
+    const char *times_path = getenv("MAG_TUNE_TRANSIENT_TL_TIMES");
+    const bool timed = times_path && *times_path;
+    double phase_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0}; // tangent; gather; into the solver's numbering; CG; back + state + force + residual
+    auto stamp = [&](int k) -> int {
+        if (timed) HIPCHK(hipEventRecord(ctx->ev[k], s));
+        return MAG_OK;
+    };
+    // A_T,FF x_F = rhs_F from zero, x_P = 0: the transient pass's poll scheme
+    std::vector<int32_t> iterations(rows, 0), newton_its(rows, 0), cg_its;
+    std::vector<double> residuals;
+    long long all_cg = 0;
+    auto solve = [&](int32_t step, int32_t it, double *x) -> int {
+        if (int rc = ps.solve(d_rhs, d_zero, x, timed ? ctx->ev[3] : nullptr, timed ? ctx->ev[4] : nullptr)) return rc;
+        const mag_stats &cs = ctx->stats;
+        if (cs.breakdown)
+            return fail(ctx, MAG_ERR_NOT_CONVERGED, "%s: step %d, iteration %d: the solve broke down (non-finite residual after %lld iterations)", fn,
+                        (int)step, (int)it, (long long)cs.iterations);
+        iterations[(size_t)step] = (int32_t)std::min<long long>((long long)iterations[(size_t)step] + cs.iterations, INT32_MAX);
+        all_cg += cs.iterations;
+        return MAG_OK;
+    };
+    // f_int(w) and the residual of (w, av, vv) under amplitude[at] into tr_rhs, its norms into the record
+    auto residual = [&](const double *w, const double *av, const double *vv, int64_t at) -> int {
+        magk::tl_force(mesh, w, d_fint, &d_scal->inverted, nullptr, nullptr, s);
+        magk::tl_residual(pat, d_m, st.known, d_f, d_amp, at, d_fint, av, vv, alpha, d_rhs, d_part, d_scal, s);
+        HIPCHK(hipGetLastError());
+        return MAG_OK;
+    };
+    auto record_energies = [&](int64_t row) -> int {
+        magk::tl_dynamic_energies(mesh, pat, d_m, st.known, st.u, st.v, d_f, d_amp, row, &d_scal->inverted, ctx->tr_part.as<double>(),
+                                  ctx->tr_energy.as<double>() + 3 * row, s);
+        HIPCHK(hipGetLastError());
+        return MAG_OK;
+    };
+
+    // ---- the start: M_FF a_0 = (amp[0] f - alpha M v_0 - f_int(u_0))_F.  The matrix is M alone, by the linear pass's
+    // effective_values on K with (c_M, c_K) = (1, 0): no tangent is evaluated for a factor of zero
+    if (!resume) {
+        magk::newmark_start(st, in.d_u0, in.d_v0, s);
+        if (int rc = residual(st.u, d_zero, st.v, 0)) return rc;
+        magk::effective_values(pat, ctx->kval.as<double>(), d_m, 0.0, 1.0, d_at, s);
+        HIPCHK(hipGetLastError());
+        if (int rc = ps.system(d_at)) return rc;
+        if (int rc = solve(0, 0, st.a)) return rc;
+    }
+    magk::newmark_record(st, 0, se > 0 ? d_snap : nullptr, s);
+    if (energies)
+        if (int rc = record_energies(0)) return rc;
+
+    // ---- the steps
+    magk::TlTrial trial = {n2, st.known, st.u, st.ut, st.vt, d_an, d_da, d_an, d_un, d_vn};
+    int32_t done = 0, most = 0;
+    bool inverted = false;
+    std::string unconverged;
+    for (int32_t n = 0; n < steps; ++n) {
+        magk::newmark_predict(st, dt, beta, gamma, s);
+        magk::tl_trial_state(trial, 1.0, c_u, c_v, 1, s); // the first iterate: u' = u_n
+        if (int rc = residual(d_un, d_an, d_vn, n + 1)) return rc;
+        bool converged = false;
+        double ratio = 0.0;
+        int32_t it = 0;
+        while (it < cap && !converged) {
+            ++it;
+            if (int rc = stamp(0)) return rc;
+            if (int rc = tangent(c_M, c_u, d_un)) return rc;
+            if (int rc = stamp(1)) return rc;
+            if (int rc = ps.system(d_at)) return rc;
+            if (int rc = stamp(2)) return rc;
+            if (int rc = solve(n + 1, it, d_da)) return rc; // (records events 3 and 4 around the CG)
+            magk::tl_trial_state(trial, 1.0, c_u, c_v, 0, s);
+            if (int rc = residual(d_un, d_an, d_vn, n + 1)) return rc;
+            TlStepScalars h = {};
+            HIPCHK(hipMemcpyAsync(&h, d_scal, sizeof(TlStepScalars), hipMemcpyDeviceToHost, s));
+            if (timed) HIPCHK(hipEventRecord(ctx->ev[5], s));
+            HIPCHK(hipStreamSynchronize(s));
+            if (timed)
+                for (int ph = 0; ph < 5; ++ph) {
+                    float ms = 0.0f;
+                    HIPCHK(hipEventElapsedTime(&ms, ctx->ev[ph], ctx->ev[ph + 1]));
+                    phase_ms[ph] += ms;
+                }
+            inverted = inverted || h.inverted != 0;
+            const double rn = std::sqrt(h.r2), ref = std::sqrt(std::max(h.f2, std::max(h.i2, h.m2)));
+            ratio = ref > 0.0 ? rn / ref : (rn == 0.0 ? 0.0 : INFINITY);
+            residuals.push_back(ratio);
+            cg_its.push_back((int32_t)ps.prev);
+            converged = rn <= tol * ref;
+        }
+        most = std::max(most, it);
+        if (!converged) {
+            char buf[256];
+            snprintf(buf, sizeof buf, "%s: step %d did not converge within %d iterations: |r_F| / ref = %.3e after iteration %d (tolerance %.3e)", fn,
+                     (int)(n + 1), (int)cap, ratio, (int)it, tol);
+            unconverged = buf;
+            break;
+        }
+        newton_its[(size_t)n + 1] = it;
+        HIPCHK(hipMemcpyAsync(st.u, d_un, vb, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(st.v, d_vn, vb, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(st.a, d_an, vb, hipMemcpyDeviceToDevice, s));
+        const bool snap = se > 0 && (n + 1) % se == 0;
+        magk::newmark_record(st, n + 1, snap ? d_snap + (size_t)((n + 1) / se) * (size_t)n2 : nullptr, s);
+        if (energies)
+            if (int rc = record_energies(n + 1)) return rc;
+        done = n + 1;
+    }
+
+    // ---- a run that ended early keeps the rows of its converged steps: the probes' three blocks move together (through a buffer of
+    // the pass's: the blocks may overlap), the last amplitude is the last converged step's
+    const size_t rows_done = (size_t)done + 1;
+    double amp_last = in.amp_last;
+    if (done < steps) {
+        iterations.resize(rows_done);
+        newton_its.resize(rows_done);
+        HIPCHK(hipMemcpyAsync(&amp_last, d_amp + done, 8, hipMemcpyDeviceToHost, s));
+        if (np > 0) {
+            const size_t blk = 8 * rows_done * (size_t)np;
+            HIPCHK(ctx->tt_move.reserve(blk));
+            for (size_t b = 1; b < 3; ++b) {
+                HIPCHK(hipMemcpyAsync(ctx->tt_move.p, st.probe_u + b * rows * (size_t)np, blk, hipMemcpyDeviceToDevice, s));
+                HIPCHK(hipMemcpyAsync(st.probe_u + b * rows_done * (size_t)np, ctx->tt_move.p, blk, hipMemcpyDeviceToDevice, s));
+            }
+        }
+    }
+
+    // ---- the results of the last converged state: its reactions, its element rows
+    int32_t *d_flag = (int32_t *)(d_scal + 1);
+    magk::tl_force(mesh, st.u, d_fint, d_flag, nullptr, nullptr, s);
+    magk::tl_dynamic_reactions(pat, d_m, st.known, d_f, d_amp, done, d_fint, st.a, st.v, alpha, ctx->tr_f.as<double>(), s);
+    magk::newton_elements(mesh, st.u, ctx->youngs / (1.0 - ctx->nu * ctx->nu), ctx->tt_elem.as<double>(), d_flag, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+
+    const size_t snaps_done = se > 0 ? (size_t)(done / se) + 1 : 0;
+    long long step_most = 0, step_all = 0;
+    for (int32_t v : iterations) step_most = std::max<long long>(step_most, v), step_all += v;
+    int32_t *info = ctx->tr_info;
+    info[0] = done;
+    info[1] = fused ? 5 : 3;
+    info[2] = kind;
+    info[3] = (int32_t)std::min<long long>(step_all, INT32_MAX);
+    info[4] = (int32_t)step_most;
+    info[5] = (int32_t)snaps_done;
+    info[6] = resume ? 1 : 0;
+    info[7] = done == steps ? 1 : 0;
+    int32_t *ti = ctx->tt_info;
+    ti[0] = done;
+    ti[1] = fused ? 5 : 3;
+    ti[2] = kind;
+    ti[3] = (int32_t)residuals.size();
+    ti[4] = most;
+    ti[5] = (int32_t)std::min<long long>(all_cg, INT32_MAX);
+    ti[6] = inverted ? 1 : 0;
+    ti[7] = done == steps ? 1 : 0;
+    ctx->tr_iterations = iterations;
+    ctx->tt_newton = newton_its;
+    ctx->tt_cg = cg_its;
+    ctx->tt_residuals = residuals;
+    StepOptions published = so;
+    published.steps = done;
+    publish_steps(ctx, published, energies, rows_done, snaps_done, t_start, dt, amp_last, 0.0, 0.0);
+    ctx->tt_have = true;
+    if (timed)
+        if (FILE *tf = fopen(times_path, "a")) {
+            fprintf(tf, "{\"steps\": %d, \"newton_iterations\": %d, \"cg_iterations\": %lld, \"tangent_ms\": %.6f, \"gather_ms\": %.6f, \"cg_ms\": %.6f, \"state_ms\": %.6f}\n",
+                    (int)done, (int)residuals.size(), all_cg, phase_ms[0], phase_ms[1], phase_ms[3], phase_ms[2] + phase_ms[4]);
+            fclose(tf);
+        }
+    if (!unconverged.empty()) ctx->err = unconverged;
+    return MAG_OK;
+}
+
+int mag_download_transient_tl(mag_ctx *ctx, mag_transient_tl_result *o)
+{
+    const char *fn = "mag_download_transient_tl";
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null result", fn);
+    if (int rc = memory_refused(ctx, o->memory, fn)) return rc;
+    if (ctx->comm.nranks > 1)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: transient dynamics run on one GPU: this context has a communicator of %d ranks", fn, ctx->comm.nranks);
+    if (!ctx->have_problem || !ctx->tr_have || !ctx->tt_have) return fail(ctx, MAG_ERR_STATE, "%s before a completed mag_run_transient_tl", fn);
+    if (int rc = enter(ctx)) return rc;
+    const hipMemcpyKind kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const hipMemcpyKind hkind = o->memory == MAG_MEM_DEVICE ? hipMemcpyHostToDevice : hipMemcpyHostToHost;
+    hipStream_t s = ctx->stream;
+    const size_t its = ctx->tt_residuals.size();
+    if (o->newton_iterations) HIPCHK(hipMemcpyAsync(o->newton_iterations, ctx->tt_newton.data(), 4 * ctx->tt_newton.size(), hkind, s));
+    if (its > 0) {
+        if (o->cg_iterations) HIPCHK(hipMemcpyAsync(o->cg_iterations, ctx->tt_cg.data(), 4 * its, hkind, s));
+        if (o->residuals) HIPCHK(hipMemcpyAsync(o->residuals, ctx->tt_residuals.data(), 8 * its, hkind, s));
+    }
+    if (o->elem) HIPCHK(hipMemcpyAsync(o->elem, ctx->tt_elem.p, 64 * (size_t)ctx->E, kind, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
+int mag_get_transient_tl_info(const mag_ctx *ctx, int32_t info[8])
+{
+    if (!ctx || !info || ctx->comm.nranks > 1) return MAG_ERR_BAD_ARGS;
+    if (!ctx->have_problem || !ctx->tr_have || !ctx->tt_have) return MAG_ERR_STATE;
+    for (int k = 0; k < 8; ++k) info[k] = ctx->tt_info[k];
     return MAG_OK;
 }
 

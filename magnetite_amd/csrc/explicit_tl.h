@@ -104,6 +104,16 @@ struct TlMesh {
     double c0, nu, h;
 };
 
+// the strain energy of element e, from its first corner (explicit_tl.hip, transient_tl.hip)
+__device__ inline double tl_element_energy(const TlMesh &m, const double2 *u, int64_t e, int32_t *inverted)
+{
+    const int64_t a = m.conn[3 * e], b = m.conn[3 * e + 1], c = m.conn[3 * e + 2];
+    const double2 ca = m.xy[a], cb = m.xy[b], cc = m.xy[c], ua = u[a], pb = u[b], pc = u[c];
+    const TlStrain s = tl_strain(make_double2(cb.x - ca.x, cb.y - ca.y), make_double2(pb.x - ua.x, pb.y - ua.y),
+                                 make_double2(cc.x - ca.x, cc.y - ca.y), make_double2(pc.x - ua.x, pc.y - ua.y), m.nu, m.h, inverted);
+    return tl_energy(s, m.c0);
+}
+
 // f[2N] = f_int(u), one lane per node, the triangles in the order of its incidence list; *inverted |= 1 for det F <= 0.
 // energy != nullptr: also *energy = W(u), the elements' energies by a two-stage sum of a fixed shape (partials: scratch
 // [kSensBlocks]).  One launch, or three
@@ -119,5 +129,9 @@ void tl_reactions(const uint8_t *known, const double *f, const double *amplitude
 // Two launches; *inverted as tl_force
 void tl_energies(const TlMesh &m, const Pattern &pat, const double *mval, const uint8_t *known, const double *u, const double *v, const double *f,
                  const double *amplitude, int64_t amp_at, int32_t *inverted, double *partials, double *out, hipStream_t s);
+
+// the second stage of an energy row: out[0] = 1/2 partials' T, out[1] = their W, out[2] = amplitude[amp_at] times their f.u;
+// partials: [kSensBlocks][3] (tl_energies', tl_dynamic_energies')
+void tl_row_sum(const double *partials, const double *amplitude, int64_t amp_at, double *out, hipStream_t s);
 
 } // namespace magk

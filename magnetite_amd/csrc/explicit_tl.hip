@@ -114,16 +114,6 @@ __global__ void __launch_bounds__(256) k_tl_force(TlMesh m, const double2 *u, do
     f[i] = make_double2(fx, fy);
 }
 
-// the strain energy of element e, from its first corner
-__device__ inline double tl_element_energy(const TlMesh &m, const double2 *u, int64_t e, int32_t *inverted)
-{
-    const int64_t a = m.conn[3 * e], b = m.conn[3 * e + 1], c = m.conn[3 * e + 2];
-    const double2 ca = m.xy[a], cb = m.xy[b], cc = m.xy[c], ua = u[a], pb = u[b], pc = u[c];
-    const TlStrain s = tl_strain(make_double2(cb.x - ca.x, cb.y - ca.y), make_double2(pb.x - ua.x, pb.y - ua.y),
-                                 make_double2(cc.x - ca.x, cc.y - ca.y), make_double2(pc.x - ua.x, pc.y - ua.y), m.nu, m.h, inverted);
-    return tl_energy(s, m.c0);
-}
-
 // ---- W(u): stage one over the elements, stage two over the kSensBlocks partial records
 __global__ void __launch_bounds__(256) k_tl_energy_partials(TlMesh m, const double2 *u, int32_t *inverted, double *partials)
 {
@@ -199,11 +189,16 @@ __global__ void __launch_bounds__(256) k_tl_row_sum(const double *partials, cons
     });
 }
 
+void tl_row_sum(const double *partials, const double *amplitude, int64_t amp_at, double *out, hipStream_t s)
+{
+    k_tl_row_sum<<<dim3(1, 1), 256, 0, s>>>(partials, amplitude, amp_at, out);
+}
+
 void tl_energies(const TlMesh &m, const Pattern &pat, const double *mval, const uint8_t *known, const double *u, const double *v, const double *f,
                  const double *amplitude, int64_t amp_at, int32_t *inverted, double *partials, double *out, hipStream_t s)
 {
     k_tl_row_partials<<<dim3(kSensBlocks, 1), 256, 0, s>>>(m, pat, mval, known, u, v, f, inverted, partials);
-    k_tl_row_sum<<<dim3(1, 1), 256, 0, s>>>(partials, amplitude, amp_at, out);
+    tl_row_sum(partials, amplitude, amp_at, out, s);
 }
 
 } // namespace magk

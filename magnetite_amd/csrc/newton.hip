@@ -8,61 +8,13 @@
 
 namespace magk {
 
-// ---- the tangent in the pattern: one thread per row node (Hilbert position g, caller id perm[g]), as k_tr_mass_pattern.  The
-// row's values are zeroed, then every incident triangle adds its three blocks of this node's row, in list order.  The triangle is
-// always taken from its first corner on, so that its three rows see the same H, F and S.
+// ---- the tangent in the pattern: one thread per row node (Hilbert position g, caller id perm[g]), as k_tr_mass_pattern; the
+// row itself is newton.h's tl_tangent_row, which transient_tl.hip finishes as the effective matrix
 __global__ void __launch_bounds__(256) k_tl_tangent(TlMesh m, Pattern pat, const double2 *u, double *kval, int32_t *inverted)
 {
     const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (g >= m.N) return;
-    const int64_t i = m.perm[g];
-    const int32_t p = pat.bptr[i], cnt = pat.bptr[i + 1] - p;
-    double *row0 = kval + 4 * (int64_t)p, *row1 = row0 + 2 * cnt;
-    for (int32_t k = 0; k < 2 * cnt; ++k) row0[k] = 0.0, row1[k] = 0.0;
-    const double nu = m.nu, h = m.h;
-    const int32_t q1 = m.inc_off[g + 1];
-    for (int32_t q = m.inc_off[g]; q < q1; ++q) {
-        const uint32_t w = m.inc[q];
-        const int64_t e = w / 3u;
-        const int a = (int)(w - 3u * (uint32_t)e);
-        const int32_t n0 = m.conn[3 * e], n1 = m.conn[3 * e + 1], n2 = m.conn[3 * e + 2];
-        const double2 x0 = m.xy[n0], x1 = m.xy[n1], x2 = m.xy[n2], u0 = u[n0], u1 = u[n1], u2 = u[n2];
-        const double2 db = make_double2(x1.x - x0.x, x1.y - x0.y), dc = make_double2(x2.x - x0.x, x2.y - x0.y);
-        const TlStrain s = tl_strain(db, make_double2(u1.x - u0.x, u1.y - u0.y), dc, make_double2(u2.x - u0.x, u2.y - u0.y), nu, h, inverted);
-        const double r = ring_rcp<double>(s.twoA);
-        const double2 g0 = make_double2((db.y - dc.y) * r, (dc.x - db.x) * r), g1 = make_double2(dc.y * r, -(dc.x * r)),
-                      g2 = make_double2(-(db.y * r), db.x * r);
-        const double F11 = 1.0 + s.H11, F12 = s.H12, F21 = s.H21, F22 = 1.0 + s.H22;
-        const double wv = s.twoA * m.c0; // V c
-        const double2 gk = a == 0 ? g0 : (a == 1 ? g1 : g2);
-        // (D / c) B_k, column d: (p0 + nu p1, p1 + nu p0, h p2) of p = (F_d1 gk.x, F_d2 gk.y, F_d1 gk.y + F_d2 gk.x)
-        const double pa0 = F11 * gk.x, pa1 = F12 * gk.y, pa2 = fma(F11, gk.y, F12 * gk.x);
-        const double pb0 = F21 * gk.x, pb1 = F22 * gk.y, pb2 = fma(F21, gk.y, F22 * gk.x);
-        const double da0 = fma(nu, pa1, pa0), da1 = fma(nu, pa0, pa1), da2 = h * pa2;
-        const double db0 = fma(nu, pb1, pb0), db1 = fma(nu, pb0, pb1), db2 = h * pb2;
-        // (S / c) g_k
-        const double tx = fma(s.sx, gk.x, s.tq * gk.y), ty = fma(s.tq, gk.x, s.sy * gk.y);
-#pragma unroll
-        for (int l = 0; l < 3; ++l) {
-            const double2 gl = l == 0 ? g0 : (l == 1 ? g1 : g2);
-            const int32_t j = l == 0 ? n0 : (l == 1 ? n1 : n2);
-            const double qa0 = F11 * gl.x, qa1 = F12 * gl.y, qa2 = fma(F11, gl.y, F12 * gl.x);
-            const double qb0 = F21 * gl.x, qb1 = F22 * gl.y, qb2 = fma(F21, gl.y, F22 * gl.x);
-            const double geo = fma(tx, gl.x, ty * gl.y);
-            const double k00 = wv * (fma(da0, qa0, fma(da1, qa1, da2 * qa2)) + geo);
-            const double k01 = wv * fma(da0, qb0, fma(da1, qb1, da2 * qb2));
-            const double k10 = wv * fma(db0, qa0, fma(db1, qa1, db2 * qa2));
-            const double k11 = wv * (fma(db0, qb0, fma(db1, qb1, db2 * qb2)) + geo);
-            for (int32_t k = 0; k < cnt; ++k) // (the column is one of the row's: K couples the same pairs)
-                if (pat.bcol[p + k] == j) {
-                    row0[2 * k] = row0[2 * k] + k00;
-                    row0[2 * k + 1] = row0[2 * k + 1] + k01;
-                    row1[2 * k] = row1[2 * k] + k10;
-                    row1[2 * k + 1] = row1[2 * k + 1] + k11;
-                    break;
-                }
-        }
-    }
+    tl_tangent_row<false>(m, pat, u, g, kval, inverted, nullptr, 0.0, 0.0);
 }
 
 void tl_tangent(const TlMesh &m, const Pattern &pat, const double *u, double *kval, int32_t *inverted, hipStream_t s)

@@ -795,18 +795,89 @@ class Context:
     _transient_energies = False
 
     def transient(self, prob=None, steps=None, dt=None, density=None, beta=0.25, gamma=0.5, rayleigh=(0.0, 0.0), amplitude=None,
-                  u0=None, v0=None, probes=(), energies=False, snapshot_every=0, cg=0, cg_tol=0.0, lumped=False, resume=False):
+                  u0=None, v0=None, probes=(), energies=False, snapshot_every=0, cg=0, cg_tol=0.0, lumped=False, resume=False,
+                  kinematics="linear", newton_tol=0.0, max_newton=0):
         """The response of prob (uploaded when given; otherwise of what is uploaded) over `steps` steps of dt: the arrays of
-        download_transient() and the words of transient_info() by name."""
+        download_transient() and the words of transient_info() by name.  kinematics="tl": mag_run_transient_tl, Newton's method
+        on the total-Lagrangian tangent in every step (rayleigh[1] must be 0) -- the dict gains newton_iterations (steps done + 1),
+        newton_residuals and newton_cg (one entry per Newton iteration of the run), elements (E, 8), inverted, the words of
+        mag_get_transient_tl_info by name (TRANSIENT_TL_INFO; `steps` is the steps done) and, when a step did not converge
+        (converged == 0), `message`."""
+        if kinematics not in self.KINEMATICS:
+            raise ValueError(f"transient: kinematics {kinematics!r} is none of {sorted(self.KINEMATICS)}")
         if prob is not None:
             self.upload_problem(prob)
         if steps is None or dt is None:
             raise MagnetiteError("Solver", "transient: steps and dt are needed")
+        if kinematics == "tl":
+            self.run_transient_tl(steps, dt, density, beta, gamma, rayleigh, amplitude, u0, v0, probes, energies, snapshot_every, cg,
+                                  cg_tol, lumped, resume, newton_tol, max_newton)
+            out = self.download_transient()
+            out.update(self.transient_info())
+            out.update(self.download_transient_tl())
+            out.update(self.transient_tl_info())
+            out["inverted"] = bool(out["inverted"])
+            if not out["converged"]:
+                out["message"] = self._L.mag_last_error(self._h).decode()
+            return out
         self.run_transient(steps, dt, density, beta, gamma, rayleigh, amplitude, u0, v0, probes, energies, snapshot_every, cg, cg_tol,
                            lumped, resume)
         out = self.download_transient()
         out.update(self.transient_info())
         return out
+
+    # -- nonlinear transient dynamics: Newmark steps, Newton's method on the total-Lagrangian tangent ------
+    TRANSIENT_TL_INFO = ("steps", "cg_kernel", "preconditioner", "newton_iterations_total", "max_step_newton", "cg_iterations_total",
+                         "inverted", "converged")
+
+    def run_transient_tl(self, steps, dt, density=None, beta=0.25, gamma=0.5, rayleigh=(0.0, 0.0), amplitude=None, u0=None, v0=None,
+                         probes=(), energies=False, snapshot_every=0, cg=0, cg_tol=0.0, lumped=False, resume=False, newton_tol=0.0,
+                         max_newton=0):
+        """mag_run_transient_tl on the uploaded problem (no run needed): `steps` Newmark steps on the total-Lagrangian internal
+        force, each by Newton's method (include/magnetite_hip.h)."""
+        if density is None:
+            raise MagnetiteError("Solver", "transient: a density is needed (the model has none)")
+        if float(rayleigh[1]) != 0.0:
+            raise MagnetiteError("Solver", "transient: kinematics 'tl' has no stiffness-proportional damping: rayleigh[1] must be 0")
+        o = _lib.TransientTlOptions()
+        self._L.mag_default_transient_tl_options(C.byref(o))
+        o.lumped, o.cg, o.max_newton = 1 if lumped else 0, int(cg), int(max_newton)
+        o.dt, o.beta, o.gamma, o.density = float(dt), float(beta), float(gamma), float(density)
+        o.rayleigh_mass, o.cg_tol, o.newton_tol = float(rayleigh[0]), float(cg_tol), float(newton_tol)
+        return self._run_steps("transient", self._L.mag_run_transient_tl, o, steps, amplitude, u0, v0, probes, energies, snapshot_every, resume)
+
+    def transient_tl_info(self):
+        """The words of mag_get_transient_tl_info by name (TRANSIENT_TL_INFO)."""
+        info = (C.c_int32 * 8)()
+        self._check(self._L.mag_get_transient_tl_info(self._h, info))
+        return dict(zip(self.TRANSIENT_TL_INFO, (int(v) for v in info)))
+
+    def download_transient_tl(self):
+        """dict(newton_iterations (steps done + 1), newton_residuals, newton_cg (one entry per Newton iteration of the run),
+        elements (E, 8: mag_run_newton's element rows of the final state))."""
+        info = self.transient_tl_info()
+        its = info["newton_iterations_total"]
+        out = dict(newton_iterations=np.empty(info["steps"] + 1, dtype=np.int32), newton_residuals=np.empty(its),
+                   newton_cg=np.empty(its, dtype=np.int32), elements=np.empty((self.E, 8)))
+        o = _lib.TransientTlResult()
+        o.newton_iterations, o.elem = out["newton_iterations"].ctypes.data, out["elements"].ctypes.data
+        if its:
+            o.residuals, o.cg_iterations = out["newton_residuals"].ctypes.data, out["newton_cg"].ctypes.data
+        o.memory = MAG_MEM_HOST
+        self._check(self._L.mag_download_transient_tl(self._h, C.byref(o)))
+        return out
+
+    def assemble_effective_tangent(self, u, c_K, c_M, density, lumped=False):
+        """The values of c_K K_T(u) + c_M M in the layout of assemble_csr() (mag_assemble_effective_tangent)."""
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+        if u.size != 2 * self.N:
+            raise MagnetiteError("Solver", f"assemble_effective_tangent: an array of {u.size} entries where {2 * self.N} are expected")
+        nnz = C.c_int64(0)
+        self._check(self._L.mag_assemble_csr(self._h, C.byref(nnz), None, None, None))
+        val = np.empty(nnz.value)
+        self._check(self._L.mag_assemble_effective_tangent(self._h, _p(u, C.c_double), float(c_K), float(c_M), float(density),
+                                                           1 if lumped else 0, _p(val, C.c_double), MAG_MEM_HOST))
+        return val
 
     # -- explicit dynamics: central differences on the lumped mass, one fused launch a step --------------
     EXPLICIT_INFO = ("steps", "method", "fused", "step_launches", "record_every", "snapshots_kept", "resumed", "finite")

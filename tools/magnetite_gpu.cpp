@@ -8,7 +8,7 @@
 //   * nodes.csv/elements.csv post_processor.rs:18-83, floats as Rust's `{}` prints them
 // Usage: magnetite_gpu <input.json> <mesh.msh> [--nodes nodes.csv] [--elements elements.csv] [--dry-run] [--rel TOL]
 //                      [--stress-recovery] [--modal P --density RHO] [--adapt R [--refine-fraction T] [--refine-split 1|3]]
-//                      [--transient STEPS --dt DT --density RHO [--rayleigh A,E] [--probe DOF]...]
+//                      [--transient STEPS --dt DT --density RHO [--rayleigh A,E] [--probe DOF]... [--kinematics linear|tl [--newton-tol T]]]
 //                      [--explicit STEPS --density RHO [--dt DT | --dt-scale S] [--rayleigh A,E] [--probe DOF]... [--record-every K]
 //                       [--kinematics linear|tl]]
 //                      [--nonlinear INCREMENTS [--newton-tol T] [--line-search H] [--probe DOF]...]
@@ -18,7 +18,11 @@
 //              (id,ux1,uy1,...,uxP,uyP) next to nodes.csv -- solver::modal; the input JSON has no density, hence the flag
 //   --transient STEPS --dt DT --density RHO  also run STEPS steps of Newmark's method from rest under the loads applied at t = 0
 //              (solver::transient; --rayleigh A,E: C = A M + E K), print "info: step n t T iterations I" per step and write
-//              history.csv (step,t, then u,v,a per --probe DOF, DOF = 2 * node + axis) next to nodes.csv
+//              history.csv (step,t, then u,v,a per --probe DOF, DOF = 2 * node + axis) next to nodes.csv; --kinematics tl: every step
+//              by Newton's method on the total-Lagrangian tangent (solver::transient_tl: large rotations at an implicit step;
+//              --rayleigh A,0 only; --newton-tol T), prints "info: transient kinematics total-lagrangian", then "info: step n t T
+//              newton I iterations C" per step, "warning: transient: ..." when a step did not converge (the rows end at the last
+//              converged step) or an element was inverted
 //   --explicit STEPS --density RHO  also run STEPS central-difference steps on the lumped mass from rest under the loads applied at
 //              t = 0 (solver::run_explicit: one fused launch a step; --dt DT, or --dt-scale S times the device's bound of the
 //              stable step, 0.9 by default), print "info: explicit dt D (bound B)" and "info: step n t T" per recorded row
@@ -542,7 +546,7 @@ int main(int argc, char **argv)
         else die({MagnetiteError::Input, "Unrecognized argument " + a});
     }
     if (input.empty() || mesh.empty()) {
-        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery] [--modal P --density RHO] [--transient STEPS --dt DT --density RHO [--rayleigh A,E] [--probe DOF]...] [--explicit STEPS --density RHO [--dt DT | --dt-scale S] [--rayleigh A,E] [--probe DOF]... [--record-every K] [--kinematics linear|tl]] [--nonlinear INCREMENTS [--newton-tol T] [--line-search H] [--probe DOF]...] [--adapt R [--refine-fraction T] [--refine-split 1|3]] [--topopt ITERS [--volume-fraction F] [--penal P] [--filter-passes K] [--field-cg 0..3]]\n");
+        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery] [--modal P --density RHO] [--transient STEPS --dt DT --density RHO [--rayleigh A,E] [--probe DOF]... [--kinematics linear|tl [--newton-tol T]]] [--explicit STEPS --density RHO [--dt DT | --dt-scale S] [--rayleigh A,E] [--probe DOF]... [--record-every K] [--kinematics linear|tl]] [--nonlinear INCREMENTS [--newton-tol T] [--line-search H] [--probe DOF]...] [--adapt R [--refine-fraction T] [--refine-split 1|3]] [--topopt ITERS [--volume-fraction F] [--penal P] [--filter-passes K] [--field-cg 0..3]]\n");
         return 2;
     }
     if (modal_modes < 0 || (modal_modes > 0 && !(density > 0.0))) die({MagnetiteError::Input, "--modal P needs P >= 1 and --density RHO > 0"});
@@ -553,16 +557,20 @@ int main(int argc, char **argv)
         die({MagnetiteError::Input, "--explicit STEPS needs STEPS >= 1, --density RHO > 0, --dt DT > 0 or --dt-scale S > 0 (not both), --rayleigh A,E >= 0 and --record-every K >= 1"});
     if (explicit_run && transient) die({MagnetiteError::Input, "--explicit and --transient share --dt, --rayleigh and --probe: one of them at a time"});
     if (!explicit_run && (dt_scale != 0.0 || record_every != 1)) die({MagnetiteError::Input, "--dt-scale and --record-every need --explicit STEPS"});
-    if (!kinematics.empty() && !explicit_run) die({MagnetiteError::Input, "--kinematics needs --explicit STEPS"});
+    if (!kinematics.empty() && !explicit_run && !transient) die({MagnetiteError::Input, "--kinematics needs --explicit STEPS or --transient STEPS"});
     if (!kinematics.empty() && kinematics != "linear" && kinematics != "tl")
-        die({MagnetiteError::Input, "--kinematics " + kinematics + ": linear or tl (with --explicit STEPS)"});
+        die({MagnetiteError::Input, "--kinematics " + kinematics + ": linear or tl (with --explicit STEPS or --transient STEPS)"});
     const bool total_lagrangian = kinematics == "tl";
     if (total_lagrangian && rayleigh_stiffness != 0.0)
-        die({MagnetiteError::Input, "--explicit with --kinematics tl takes --rayleigh A,0: stiffness-proportional damping is not objective"});
+        die({MagnetiteError::Input, std::string(transient ? "--transient" : "--explicit") +
+                                        " with --kinematics tl takes --rayleigh A,0: stiffness-proportional damping is not objective"});
+    const bool transient_tl = transient && total_lagrangian;
     const bool nonlinear_run = nonlinear != -1;
     if (nonlinear_run && (nonlinear < 1 || newton_tol < 0.0 || line_search < 0))
         die({MagnetiteError::Input, "--nonlinear INCREMENTS needs INCREMENTS >= 1, --newton-tol T >= 0 and --line-search H >= 0"});
-    if (!nonlinear_run && (newton_tol != 0.0 || line_search != 0)) die({MagnetiteError::Input, "--newton-tol and --line-search need --nonlinear INCREMENTS"});
+    if (transient_tl && newton_tol < 0.0) die({MagnetiteError::Input, "--transient STEPS --kinematics tl needs --newton-tol T >= 0"});
+    if (!nonlinear_run && ((newton_tol != 0.0 && !transient_tl) || line_search != 0))
+        die({MagnetiteError::Input, "--newton-tol and --line-search need --nonlinear INCREMENTS (--newton-tol also goes with --transient STEPS --kinematics tl)"});
     if (nonlinear_run && (transient || explicit_run)) die({MagnetiteError::Input, "--nonlinear shares --probe with --transient and --explicit: one of them at a time"});
     if (nonlinear_run && adapt > 0) die({MagnetiteError::Input, "--nonlinear solves on the mesh as given: not together with --adapt"});
     if (!transient && !explicit_run && (dt != 0.0 || (!probes.empty() && !nonlinear_run) || rayleigh_mass != 0.0 || rayleigh_stiffness != 0.0))
@@ -616,6 +624,9 @@ int main(int argc, char **argv)
                         rust_display(rayleigh_stiffness).c_str(), probes.size(), record_every);
         if (explicit_run && !kinematics.empty())
             std::printf("dry-run: explicit kinematics %s\n", total_lagrangian ? "total-lagrangian" : "linear");
+        if (transient && !kinematics.empty())
+            std::printf("dry-run: transient kinematics %s newton_tol %s\n", total_lagrangian ? "total-lagrangian" : "linear",
+                        rust_display(newton_tol).c_str());
         if (nonlinear_run)
             std::printf("dry-run: nonlinear increments %d newton_tol %s line_search %d probes %zu\n", nonlinear, rust_display(newton_tol).c_str(),
                         line_search, probes.size());
@@ -701,7 +712,29 @@ int main(int argc, char **argv)
                         rust_display(modes.residual[k]).c_str());
         modes_output(modes, posed.size(), modes_name(nodes_out));
     }
-    if (transient) {
+    if (transient_tl) {
+        // The pass needs every element counter-clockwise, as the modal analysis does: the elements go in by their true sign.
+        std::vector<Element> ccw = elements;
+        for (Element &e : ccw)
+            if (solver::compute_element_area(e, posed) < 0.0) std::swap(e.nodes[0], e.nodes[2]);
+        opt.verbose = 0;
+        TransientTlSpec spec;
+        spec.steps = transient_steps;
+        spec.dt = dt;
+        spec.density = density;
+        spec.rayleigh_mass = rayleigh_mass;
+        spec.newton_tol = newton_tol;
+        spec.probes = probes;
+        TransientTl tt;
+        if (Result err = solver::transient_tl(posed, ccw, meta, spec, tt, &opt)) die(*err);
+        std::printf("info: transient kinematics total-lagrangian\n");
+        for (size_t n = 0; n < tt.run.iterations.size(); ++n)
+            std::printf("info: step %zu t %s newton %d iterations %d\n", n, rust_display((double)n * dt).c_str(), (int)tt.newton_iterations[n],
+                        (int)tt.run.iterations[n]);
+        if (!tt.converged) std::printf("warning: transient: %s\n", tt.message.c_str());
+        if (tt.inverted) std::printf("warning: transient: an element was inverted (det F <= 0)\n");
+        history_output(tt.run, probes, dt, history_name(nodes_out));
+    } else if (transient) {
         // The pass needs every element counter-clockwise, as the modal analysis does: the elements go in by their true sign.
         std::vector<Element> ccw = elements;
         for (Element &e : ccw)
