@@ -854,6 +854,17 @@ constexpr int persist_walk_group(int B, bool MG, int EBM, bool ONE, int NPT)
     return EBM == 2 && B == 512 ? 2 : 3;
 }
 
+// The update phase's LDS loads in flight under the scalars (DESIGN UB): q of the lane's four node slots is read at the TOP of the
+// loop body, in front of the chains of alpha, beta and the cost, p two slots at a time in front of the r updates of two slots,
+// with counted waits -- at most 24 registers of loads in flight; the kernel has no more to give in this phase (all eight loads
+// in front of the scalars, or q and p of two slots with the other two behind them as a group: 8 to 18 spilled dwords, slower).
+// false: the update phase as the scheduler places it, which at the register ceiling is load, load, full wait, four FMAs,
+// store, once per slot, behind the scalars.  On for the four-slot structured kernel of the 512-node tiles on a grid.
+constexpr bool persist_update_loads(int B, bool MG, int EBM, bool ONE, int NPT)
+{
+    return EBM == 1 && !MG && !ONE && NPT == 4 && B == 512;
+}
+
 // EBM: 0 the triangle walk, 1 edge blocks in registers (every row of the mesh a fan of at most six blocks: structured meshes),
 // 2 edge blocks with OVERFLOW (round 4: rows that are one fan of any length -- what gmsh's frontal meshes look like, a quarter
 // of their nodes with seven neighbours: blocks beyond the six in registers sit in an LDS pool of 32-byte records).
@@ -915,6 +926,8 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
         persist_comm_loop(P, s_S, s_rec);
         return;
     }
+    constexpr bool UL = persist_update_loads(B, MG, EBM, ONE, NPT); // the update's LDS loads in flight under the scalars
+    static_assert(!UL || EB, "the update loads in front: q lives in LDS");
     constexpr int NH = kPersistNh; // halo entries per thread: the workgroup's halo nodes are dealt out over ALL threads
     const unsigned tag0 = (MG ? P.tag_base : 0u) + 1u; // tag of epoch e: tag0 + e - 1
     int32_t deg[NPT], ent[NPT];
@@ -949,7 +962,11 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
         r[s] = q[s] = make_double2(0.0, 0.0);
 #pragma unroll
         for (int k = 0; k < kPersistRegs; ++k) w[s][k] = 0xffffffffu;
-        if (!(l < P.tiles_per_wg && t < (MG ? P.t1 : P.T))) continue;
+        if (!(l < P.tiles_per_wg && t < (MG ? P.t1 : P.T))) {
+            // (UL) a dead slot is updated like a live one, without a test: its r, q and p are zeros and stay zeros
+            if constexpr (UL) xy[lt] = pim[lt] = make_double2(0.0, 0.0);
+            continue;
+        }
         const TileMeta tm = P.meta[t];
         const int64_t nd = (int64_t)t * B + lt;
         flags.set(s, 8);
@@ -1240,19 +1257,43 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
             ++stamp_iters;
         }
 #endif
+        // (UL) The update phase's first LDS reads, q of the lane's own nodes, in front of the scalars: they depend on neither
+        // alpha nor beta nor the sums -- q has been final in LDS since the walks -- and are in flight while the chains below run.
+        // A loop that breaks below leaves them unused.  Pinned where they stand, as ring_walk_blocks pins its gathers.
+        [[maybe_unused]] double2 uq[NPT], up[NPT];
+        if constexpr (UL) {
+#pragma unroll
+            for (int s = 0; s < NPT; ++s) uq[s] = t_xy(s)[t_lt(s)];
+            __builtin_amdgcn_sched_barrier(0);
+        }
         // (single GPU: the exchange hands the sums over in scalar registers already)
         const double S0 = MG ? uniform_f64(s_S[0]) : Sx[0], S1 = MG ? uniform_f64(s_S[1]) : Sx[1],
                      S2 = MG ? uniform_f64(s_S[2]) : Sx[2], S3 = MG ? uniform_f64(s_S[3]) : Sx[3];
+        // alpha and beta before the stop test: on the way out they are simply not used.  Their two divisions and the square
+        // root of the cost are some forty dependent fp64 operations in every wave and every iteration.  Behind the j == 0 block
+        // the square root, which that block shares with the cost, is hoisted in front of it, a block of its own, and the
+        // divisions follow in the next; in front of it (UL) the three are one basic block: alpha's division, beta's, the root.
+        // (Measured: no difference on the 1M mesh -- a wave's dependent fp64 operations issue back to back as it is.)
+        double alpha_, beta_;
+        if constexpr (UL) {
+            alpha_ = uniform_f64(S0 / S1);
+            beta_ = uniform_f64(fma(alpha_ * alpha_, S3, fma(2.0 * alpha_, S2, S0)) / S0);
+            cost = uniform_f64(P.stop_mode == 1 ? fabs(S0) : sqrt(S0));
+        }
         if (j == 0) {
-            bb = S0;
+            // (UL: b.b moved to scalar registers -- as a copy of S0 it took two vector registers all the way round the loop,
+            // and the kernel spilled a fifth dword in the exchange)
+            if constexpr (UL) bb = uniform_f64(S0);
+            else bb = S0;
             target = uniform_f64(P.stop_mode == 2 ? P.tol * sqrt(bb) : P.tol);
         }
         const double rr = S0;
-        // alpha and beta before the stop test: their two division chains (~300 cycles, every wave, every iteration) then run
-        // alongside the square root of the cost instead of behind it; on the way out they are simply not used
-        const double alpha = uniform_f64(rr / S1);
-        const double beta = uniform_f64(fma(alpha * alpha, S3, fma(2.0 * alpha, S2, rr)) / rr);
-        cost = uniform_f64(P.stop_mode == 1 ? fabs(rr) : sqrt(rr));
+        if constexpr (!UL) {
+            alpha_ = uniform_f64(rr / S1);
+            beta_ = uniform_f64(fma(alpha_ * alpha_, S3, fma(2.0 * alpha_, S2, rr)) / rr);
+            cost = uniform_f64(P.stop_mode == 1 ? fabs(rr) : sqrt(rr));
+        }
+        const double alpha = alpha_, beta = beta_;
         const long long it_done = j - 1;
         if (reporter && it_done >= 1 && it_done - 1 < P.hist_len) P.hist[it_done - 1] = cost;
         if (j == 0 && bb == 0.0) {
@@ -1301,10 +1342,36 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
             pn.y = fma(beta, po.y, -r[s].y);
             pim[lt] = pn;
         };
-        // A workgroup whose node slots are all live (every one on the 1M mesh but the last) runs them as ONE basic block: the
-        // eight LDS loads of the four slots go out together.  With a test per slot each slot waited for its own two loads
-        // before the next slot's were issued.  (A dead slot's LDS is never read by anybody else: it is skipped, not zeroed.)
-        if (all_live) {
+        // A workgroup whose node slots are all live (every one on the 1M mesh but the last) runs them as ONE basic block, so
+        // that the eight LDS loads of the four slots can go out together; with a test per slot each slot waits for its own two
+        // loads before the next slot's are issued.  (A dead slot's LDS is never read by anybody else: it is skipped, not zeroed.)
+        // What the ISA has at the register ceiling of the four-slot kernels is the second shape in the one block as well: load,
+        // load, lgkmcnt(0), four FMAs, store, once per slot.
+        // UL: one block for every workgroup, no test (a dead slot's zeros stay zeros), on the q loads issued at the top of the
+        // loop body: p of two slots, the r updates of two slots, twice; then the four p updates and stores.  Each pair of loads
+        // is pinned in front of FMAs that do not need it; the waits are counted.  Per value the same fma() on the same operands
+        // as update_slot: the same bits.  r is updated in place (with an all-live path and a tested one the allocator computed
+        // the first one's r into other registers and copied it over at the join).
+        if constexpr (UL) {
+#pragma unroll
+            for (int h = 0; h < NPT; h += 2) {
+#pragma unroll
+                for (int s = h; s < h + 2; ++s) up[s] = t_xy(s)[capx + t_lt(s)];
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int s = h; s < h + 2; ++s) {
+                    r[s].x = fma(alpha, uq[s].x, r[s].x);
+                    r[s].y = fma(alpha, uq[s].y, r[s].y);
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < NPT; ++s) {
+                double2 pn;
+                pn.x = fma(beta, up[s].x, -r[s].x);
+                pn.y = fma(beta, up[s].y, -r[s].y);
+                t_xy(s)[capx + t_lt(s)] = pn;
+            }
+        } else if (all_live) {
 #pragma unroll
             for (int s = 0; s < NPT; ++s) update_slot(s);
         } else {
