@@ -331,12 +331,22 @@ struct mag_ctx {
     double design_info[8] = {};
     DevBuf ds_rho, ds_rhof, ds_w, ds_area, ds_node_area, ds_node, ds_tmp, ds_dJ, ds_dJdrho, ds_bq, ds_rho_new, ds_part, ds_small;
 
+    // What the passes on the assembled pattern share, none of it a result (mag_run_transient, mag_run_explicit, mag_run_newton,
+    // mag_run_transient_tl and the single evaluations).  ptab: the block-row table of K's pattern, the gathered values of the
+    // pass's matrix and the inverse blocks, in buffers of the passes' own (fc_* are a field's, kept between runs): every run
+    // rebuilds the table and regathers the values before its first solve, nothing is carried between runs in it.  chk_words,
+    // chk_probes: the 16 bytes of the device checks (StepWords) and the probe list of the run in flight.  ev_u, ev_words: the state
+    // and the words (EvalWords) of mag_internal_force, mag_assemble_tangent and mag_assemble_effective_tangent
+    struct PassTable {
+        DevBuf width, meta, slot, src, val, minv, hminv;
+    } ptab;
+    DevBuf chk_words, chk_probes, ev_u, ev_words;
+
     // transient dynamics (mag_run_transient): the mass and the effective matrix in K's pattern (tr_aval in kval's layout), the
-    // block-row table and the gathered values of A in buffers of the pass's own (fc_* are a field's), the state, the predictors,
-    // the right-hand side, a zero vector, the records of the last run, and the words of mag_get_transient_info.  The results hang
-    // on the upload only: a new mag_upload drops them, a new run replaces them
-    DevBuf tr_mval, tr_aval, tr_width, tr_meta, tr_slot, tr_src, tr_val, tr_minv, tr_hminv;
-    DevBuf tr_u, tr_v, tr_a, tr_ut, tr_vt, tr_rhs, tr_zero, tr_f, tr_ku, tr_mv, tr_amp, tr_in, tr_probes, tr_bad;
+    // state, the predictors, the right-hand side, a zero vector, the records of the last run, and the words of
+    // mag_get_transient_info.  The results hang on the upload only: a new mag_upload drops them, a new run replaces them
+    DevBuf tr_mval, tr_aval;
+    DevBuf tr_u, tr_v, tr_a, tr_ut, tr_vt, tr_rhs, tr_zero, tr_f, tr_ku, tr_mv, tr_amp, tr_in;
     DevBuf tr_probe, tr_energy, tr_snap, tr_part;
     bool tr_have = false;
     int32_t tr_info[8] = {}, tr_steps = 0, tr_num_probes = 0, tr_snaps = 0;
@@ -349,33 +359,31 @@ struct mag_ctx {
     // explicit dynamics (mag_run_explicit) leaves its final state and its records in the transient pass's slots (either pass
     // resumes the other's state; mag_download_transient serves both).  tr_rows: the record rows of the last run of either pass;
     // tr_dt, tr_dt_bound: scalars[2..3] (0 after the implicit pass).  Its own buffers: the state records in Hilbert order (two:
-    // a step reads one and writes the other), the node masses, u_in and f_in in Hilbert order, the bound's partials and result,
-    // the finite flag
+    // a step reads one and writes the other), the node masses, u_in and f_in in Hilbert order, the bound's partials and result;
+    // its flags are in chk_words once the checks are read back
     DevBuf ex_rec[2], ex_mass, ex_uin, ex_f, ex_part, ex_out;
-    // mag_internal_force's own buffers (it changes no result of the context): u, f_int(u), the energy's partials, W
-    DevBuf tl_u, tl_f, tl_part, tl_out;
+    // mag_internal_force's own buffers (it changes no result of the context): f_int(u), the energy's partials
+    DevBuf tl_f, tl_part;
     int64_t tr_rows = 0;
     double tr_dt = 0.0, tr_dt_bound = 0.0;
 
-    // nonlinear statics (mag_run_newton): the tangent in K's pattern (nt_kval in kval's layout), the block-row table, the gathered
-    // values and the inverse blocks in buffers of the pass's own (tr_* are the transient pass's), the state and its trial, the last
+    // nonlinear statics (mag_run_newton): the tangent in K's pattern (nt_kval in kval's layout), the state and its trial, the last
     // converged state, the step and its support part, a zero vector, f_int, the right-hand side, the results, the device's
     // records and the scalars of an evaluation; the records the host keeps; the words of mag_get_newton_info.  The results hang on
     // the upload only: a new mag_upload drops them, a new run replaces them
-    DevBuf nt_kval, nt_width, nt_meta, nt_slot, nt_src, nt_val, nt_minv, nt_hminv;
-    DevBuf nt_u, nt_ut, nt_uc, nt_du, nt_dup, nt_zero, nt_f, nt_rhs, nt_fout, nt_elem, nt_load, nt_probes, nt_bad, nt_probe, nt_snap, nt_part, nt_scal;
+    DevBuf nt_kval;
+    DevBuf nt_u, nt_ut, nt_uc, nt_du, nt_dup, nt_zero, nt_f, nt_rhs, nt_fout, nt_elem, nt_load, nt_probe, nt_snap, nt_part, nt_scal;
     bool nt_have = false;
     int32_t nt_info[8] = {}, nt_increments = 0, nt_num_probes = 0, nt_snaps = 0;
     std::vector<double> nt_loads, nt_energies, nt_residuals, nt_steps;
     std::vector<int32_t> nt_newton, nt_cg;
 
     // nonlinear transient dynamics (mag_run_transient_tl): the effective tangent in K's pattern (tt_aval in kval's layout), the
-    // block-row table, the gathered values and the inverse blocks in buffers of the pass's own, the trial state (a', u', v'), the
-    // Newton step, f_int, the element rows, the scalars of an iteration, the partials; the records the host keeps; the words of
-    // mag_get_transient_tl_info.  The final state and the step records are in the transient pass's slots (tr_*).  tt_u, tt_bad:
-    // mag_assemble_effective_tangent's state and flags
-    DevBuf tt_aval, tt_width, tt_meta, tt_slot, tt_src, tt_val, tt_minv, tt_hminv;
-    DevBuf tt_an, tt_un, tt_vn, tt_da, tt_fint, tt_elem, tt_scal, tt_part, tt_move, tt_u, tt_bad;
+    // trial state (a', u', v'), the Newton step, f_int, the element rows, the scalars of an iteration, the partials; the records
+    // the host keeps; the words of mag_get_transient_tl_info.  The final state and the step records are in the transient pass's
+    // slots (tr_*)
+    DevBuf tt_aval;
+    DevBuf tt_an, tt_un, tt_vn, tt_da, tt_fint, tt_elem, tt_scal, tt_part, tt_move;
     bool tt_have = false;
     int32_t tt_info[8] = {};
     std::vector<double> tt_residuals;
@@ -460,6 +468,33 @@ int memory_refused(mag_ctx *ctx, int32_t memory, const char *fn)
 {
     if (memory_known(memory)) return MAG_OK;
     return fail(ctx, MAG_ERR_BAD_ARGS, "%s: memory = %d is none of enum mag_memory", fn, (int)memory);
+}
+// the copies into a caller's buffers of kind `memory`: from the device, from the host
+struct OutKinds {
+    hipMemcpyKind dev, host;
+};
+inline OutKinds out_kinds(int32_t memory)
+{
+    const bool d = memory == MAG_MEM_DEVICE;
+    return {d ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, d ? hipMemcpyHostToDevice : hipMemcpyHostToHost};
+}
+inline hipMemcpyKind in_kind_of(int32_t memory) { return memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice; }
+
+// the two rules of the real-valued arguments, among the argument checks (what: the field, named in the message)
+inline bool nonneg_finite(double x) { return x >= 0.0 && std::isfinite(x); }
+inline bool pos_finite(double x) { return x > 0.0 && std::isfinite(x); }
+using NamedValues = std::initializer_list<std::pair<const char *, double>>; // checked in the order given
+int need_nonneg(mag_ctx *ctx, const char *fn, NamedValues fields)
+{
+    for (const auto &[what, x] : fields)
+        if (!nonneg_finite(x)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: %s %g is negative or not finite", fn, what, x);
+    return MAG_OK;
+}
+int need_pos(mag_ctx *ctx, const char *fn, NamedValues fields)
+{
+    for (const auto &[what, x] : fields)
+        if (!pos_finite(x)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: %s %g is not positive and finite", fn, what, x);
+    return MAG_OK;
 }
 
 int scratch_for(mag_ctx *ctx, size_t bytes)
@@ -1033,11 +1068,13 @@ bool assemble_from_ctiles(const mag_ctx *ctx)
 
 // ---- mag_options.field_cg: the block-row table of K, once per order and pattern; the gathered values, once per assembly ----
 // The table of the order and the pattern held now, in the buffers of its owner: a field's (fc_*, ensure_field_table) or the
-// transient pass's (tr_*).  val: room for the gathered values
+// passes' on the assembled pattern (ptab, pass_table).  val: room for the gathered values
 struct FieldTable {
     DevBuf &width, &meta, &slot, &src, &val;
     int64_t total = 0;
 };
+
+inline FieldTable pass_table(mag_ctx *ctx) { return {ctx->ptab.width, ctx->ptab.meta, ctx->ptab.slot, ctx->ptab.src, ctx->ptab.val}; }
 
 int build_field_table(mag_ctx *ctx, FieldTable &tab)
 {
@@ -4259,8 +4296,7 @@ int mag_download_modal(mag_ctx *ctx, mag_modal_result *o)
     if (!ctx->have_problem || !ctx->modal_have) return fail(ctx, MAG_ERR_STATE, "mag_download_modal before a completed mag_run_modal");
     if (int rc = enter(ctx)) return rc;
     const int32_t p = ctx->modal_info[0];
-    const hipMemcpyKind kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const hipMemcpyKind hkind = o->memory == MAG_MEM_DEVICE ? hipMemcpyHostToDevice : hipMemcpyHostToHost;
+    const auto [kind, hkind] = out_kinds(o->memory);
     hipStream_t s = ctx->stream;
     std::vector<double> freq((size_t)p);
     for (int32_t k = 0; k < p; ++k) freq[(size_t)k] = std::sqrt(ctx->modal_lambda[(size_t)k]) / (2.0 * M_PI);
@@ -4315,22 +4351,50 @@ int mag_apply_mass(mag_ctx *ctx, double density, int32_t lumped, const double *x
 
 // ---- transient dynamics (transient.hip): Newmark time stepping of the uploaded part.  The driver owns the buffers, builds the
 // mass and the effective matrix in K's pattern, prepares the solver's copy of it once per system (the a_0 system, then the
-// step's) and enqueues every step on the context's stream: the host reads the CG's convergence polls and nothing else ----
+// step's) and enqueues every step on the context's stream: the host reads the CG's convergence polls and nothing else.  The
+// solver (ImplicitSolver), its table (ptab) and the device checks' scratch (chk_*) are shared with the two Newton passes ----
 namespace {
 
-// The solves of the pass run under MAG_STOP_REL with cg_tol, silently, launched one by one (the pass chooses the poll's block
+constexpr int kTransientPoll = 8; // launches per poll block behind a solve's first block (even: the parity restarts per block)
+
+// The inner solves of the implicit passes (mag_run_transient, mag_run_newton, mag_run_transient_tl): a matrix in kval's layout,
+// the block-row table and the inverse blocks (ptab; or the reduced system of the CSR phase), and the poll scheme, in one
+// place.  The solves run under MAG_STOP_REL with cg_tol, silently, launched one by one (the pass chooses the poll's block
 // length per solve) and without a cost history; the context's options, statistics and the CSR phase's counts are as they were
-// afterwards, on every exit path.
-struct TransientSolves {
+// once the object goes, on every exit path.
+struct ImplicitSolver {
+    // mag_*_options.cg: the fused block-row CG (kind: its preconditioner) or the CSR phase's
+    struct Choice {
+        bool fused;
+        int kind;
+    };
+    static int choose(mag_ctx *ctx, const char *fn, int32_t cg, Choice *c)
+    {
+        c->fused = cg == 0 ? ctx->use_lds : cg <= 3;
+        if (c->fused && !ctx->use_lds)
+            return fail(ctx, MAG_ERR_STATE, "%s: cg = %d needs the tile-local tables, which this context does not build (op_variant, or a tile beyond the LDS)",
+                        fn, (int)cg);
+        c->kind = !c->fused ? 0 : (cg == 0 ? 2 : cg - 1);
+        return MAG_OK;
+    }
+
     mag_ctx *ctx;
+    const char *fn;
+    const bool fused;
+    const int kind;
     const mag_options opt;
     const mag_stats stats;
     const double best_cost;
     const long long best_iter;
     const int64_t nf, nz_ff;
     const int32_t cg_kernel;
-    TransientSolves(mag_ctx *c, double cg_tol)
-        : ctx(c), opt(c->opt), stats(c->stats), best_cost(c->best_cost), best_iter(c->best_iter), nf(c->nf), nz_ff(c->nz_ff), cg_kernel(c->cg_kernel)
+    FieldTable tab;
+    FieldSystem sys = {};
+    long long prev = -1; // the iterations of the previous solve
+
+    ImplicitSolver(mag_ctx *c, const char *fn_, Choice ch, double cg_tol)
+        : ctx(c), fn(fn_), fused(ch.fused), kind(ch.kind), opt(c->opt), stats(c->stats), best_cost(c->best_cost), best_iter(c->best_iter), nf(c->nf),
+          nz_ff(c->nz_ff), cg_kernel(c->cg_kernel), tab(pass_table(c))
     {
         ctx->opt.stop_mode = MAG_STOP_REL;
         ctx->opt.tol = cg_tol;
@@ -4338,7 +4402,8 @@ struct TransientSolves {
         ctx->opt.use_graph = 0;
         ctx->opt.history_len = 0;
     }
-    ~TransientSolves()
+    ImplicitSolver(const ImplicitSolver &) = delete;
+    ~ImplicitSolver()
     {
         ctx->opt = opt;
         ctx->stats = stats;
@@ -4349,23 +4414,7 @@ struct TransientSolves {
         ctx->cg_kernel = cg_kernel;
         ctx->tr_first_block = 0;
     }
-};
-
-constexpr int kTransientPoll = 8; // launches per poll block behind a solve's first block (even: the parity restarts per block)
-
-// What the inner solves of the two Newton passes (mag_run_newton, mag_run_transient_tl) share: a matrix in kval's layout, the
-// pass's own block-row table and inverse blocks (or the reduced system of the CSR phase), and the transient pass's poll scheme,
-// in one place.  Used inside a TransientSolves scope.
-struct PatternSolver {
-    mag_ctx *ctx;
-    bool fused;
-    int kind;
-    FieldTable tab;
-    DevBuf &minv, &hminv;
-    int G0; // the context's check_every: the first poll block of the first solve
-    FieldSystem sys = {};
-    long long prev = -1; // the iterations of the previous solve
-
+    // the table of the order and the pattern held now
     int init()
     {
         if (!fused) return MAG_OK;
@@ -4378,21 +4427,24 @@ struct PatternSolver {
     int system(const double *val)
     {
         if (!fused) return build_reduced(ctx, true, val, false);
-        if (int rc = field_values(ctx, tab, val, kind, minv, hminv)) return rc;
-        sys.minvP = kind ? minv.as<float4>() : nullptr;
-        sys.halo_minv = kind ? hminv.as<float4>() : nullptr;
+        if (int rc = field_values(ctx, tab, val, kind, ctx->ptab.minv, ctx->ptab.hminv)) return rc;
+        sys.minvP = kind ? ctx->ptab.minv.as<float4>() : nullptr;
+        sys.halo_minv = kind ? ctx->ptab.hminv.as<float4>() : nullptr;
         return MAG_OK;
     }
     // A_FF x_F = rhs_F from zero, x_P = xP.  The poll's first block: the previous solve's iteration count + 2 (a launch judges the
     // iterate of the one before), rounded up to even -- the context's check_every for the first solve --, then blocks of
-    // kTransientPoll.  before / after: events recorded around the CG itself (behind the move into the solver's numbering, in
-    // front of the move back).  The statistics of the solve are the context's (ctx->stats) on return
-    int solve(const double *rhs, const double *xP, double *x, hipEvent_t before = nullptr, hipEvent_t after = nullptr)
+    // kTransientPoll.  Launches behind convergence are no-ops: the results do not depend on it.  before / after: events recorded
+    // around the CG itself (behind the move into the solver's numbering, in front of the move back), or null.  The statistics of
+    // the solve are the context's (ctx->stats) on return; a solve that broke down is refused, named by `where` (a format and its
+    // arguments: "step %d")
+    __attribute__((format(printf, 7, 8))) int solve(const double *rhs, const double *xP, double *x, hipEvent_t before, hipEvent_t after,
+                                                    const char *where, ...)
     {
         hipStream_t s = ctx->stream;
         const int64_t N = ctx->N;
         const uint8_t *known = ctx->uknown.as<uint8_t>();
-        long long G = prev < 0 ? G0 : std::min<long long>(prev + 2, 4096);
+        long long G = prev < 0 ? opt.check_every : std::min<long long>(prev + 2, 4096);
         G += G & 1;
         ctx->tr_first_block = (int32_t)std::max<long long>(G, 2);
         ctx->opt.check_every = kTransientPoll;
@@ -4410,12 +4462,17 @@ struct PatternSolver {
         }
         HIPCHK(hipGetLastError());
         prev = ctx->stats.iterations;
+        if (ctx->stats.breakdown) {
+            char at[64];
+            va_list ap;
+            va_start(ap, where);
+            vsnprintf(at, sizeof at, where, ap);
+            va_end(ap);
+            return fail(ctx, MAG_ERR_NOT_CONVERGED, "%s: %s: the solve broke down (non-finite residual after %lld iterations)", fn, at, prev);
+        }
         return MAG_OK;
     }
 };
-
-inline bool nonneg_finite(double x) { return x >= 0.0 && std::isfinite(x); }
-inline bool pos_finite(double x) { return x > 0.0 && std::isfinite(x); }
 
 // the contexts the pass does not run on, before any HIP call
 int transient_refused(mag_ctx *ctx, const char *fn)
@@ -4453,7 +4510,6 @@ struct StepOptions {
     int32_t memory, resume;
     const double *amplitude, *u0, *v0;
 };
-inline hipMemcpyKind step_in_kind(const StepOptions &o) { return o.memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice; }
 
 // the tail of the argument checks, behind the pass's own: the records, the context, the resume rule; enters the context
 int step_args_tail(mag_ctx *ctx, const char *fn, const StepOptions &o)
@@ -4470,7 +4526,46 @@ int step_args_tail(mag_ctx *ctx, const char *fn, const StepOptions &o)
     return enter(ctx);
 }
 
-// The 16 bytes of tr_bad.  The device checks write two words (all ones: nothing found); once those are read back, the explicit
+// the orientation kernel's word (all ones: nothing found), refused
+int clockwise_refused(mag_ctx *ctx, const char *fn, unsigned long long clockwise)
+{
+    if (clockwise == ~0ull) return MAG_OK;
+    return fail(ctx, MAG_ERR_BAD_ARGS,
+                "%s: element %lld has a signed area <= 0 (the stiffness carries the signed area: the pass needs counter-clockwise elements)", fn,
+                (long long)clockwise);
+}
+
+// What mag_internal_force, mag_assemble_tangent and mag_assemble_effective_tangent share: one evaluation at a caller's state u,
+// in scratch that holds no result of the context (ev_u, ev_words).  enqueue(d_u, d_words) launches the kernel, which writes
+// `out`; the elements' orientation is checked in front of it, `bytes` of `out` go to the caller behind it, *h receives the words
+struct EvalWords {
+    unsigned long long clockwise; // the first element of signed area <= 0
+    int32_t inverted, pad;
+    double W;
+};
+int evaluate_at(mag_ctx *ctx, const char *fn, const double *u, int32_t memory, const std::function<void(const double *, EvalWords *)> &enqueue,
+                const DevBuf &out, size_t bytes, void *dst, EvalWords *h)
+{
+    hipStream_t s = ctx->stream;
+    const size_t vb = 16 * (size_t)ctx->N;
+    HIPCHK(ctx->ev_u.reserve(vb));
+    HIPCHK(ctx->ev_words.reserve(sizeof(EvalWords)));
+    EvalWords *d = ctx->ev_words.as<EvalWords>();
+    HIPCHK(hipMemsetAsync(&d->inverted, 0, 8, s));
+    HIPCHK(hipMemcpyAsync(ctx->ev_u.p, u, vb, in_kind_of(memory), s));
+    magk::orientation(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), ctx->N, ctx->E, &d->clockwise, s);
+    enqueue(ctx->ev_u.as<double>(), d);
+    HIPCHK(hipGetLastError());
+    *h = {~0ull, 0, 0, 0.0};
+    HIPCHK(hipMemcpyAsync(h, d, sizeof(EvalWords), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (int rc = clockwise_refused(ctx, fn, h->clockwise)) return rc;
+    HIPCHK(hipMemcpyAsync(dst, out.p, bytes, out_kinds(memory).dev, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
+// The 16 bytes of chk_words.  The device checks write two words (all ones: nothing found); once those are read back, the explicit
 // pass keeps its flags in the same bytes: the finite flag at byte 0, the inverted-element flag at byte 8
 struct StepWords {
     union {
@@ -4482,21 +4577,21 @@ struct StepWords {
         int32_t inverted;
     };
 };
-static_assert(sizeof(StepWords) == 16 && offsetof(StepWords, bad_probe) == 8 && offsetof(StepWords, inverted) == 8, "tr_bad's layout");
+static_assert(sizeof(StepWords) == 16 && offsetof(StepWords, bad_probe) == 8 && offsetof(StepWords, inverted) == 8, "chk_words' layout");
 
-// the checks that need the device, enqueued: the elements' orientation, the probes (uploaded into tr_probes); *h receives the
+// the checks that need the device, enqueued: the elements' orientation, the probes (uploaded into chk_probes); *h receives the
 // words once the stream is synchronised
 int step_checks_enqueue(mag_ctx *ctx, const StepOptions &o, StepWords *h)
 {
     hipStream_t s = ctx->stream;
     const int32_t np = o.num_probes;
-    HIPCHK(ctx->tr_bad.reserve(sizeof(StepWords)));
-    HIPCHK(ctx->tr_probes.reserve(4 * (size_t)std::max(np, 1)));
+    HIPCHK(ctx->chk_words.reserve(sizeof(StepWords)));
+    HIPCHK(ctx->chk_probes.reserve(4 * (size_t)std::max(np, 1)));
     h->clockwise = h->bad_probe = ~0ull;
-    StepWords *d = ctx->tr_bad.as<StepWords>();
-    if (np > 0) HIPCHK(hipMemcpyAsync(ctx->tr_probes.p, o.probes, 4 * (size_t)np, step_in_kind(o), s));
+    StepWords *d = ctx->chk_words.as<StepWords>();
+    if (np > 0) HIPCHK(hipMemcpyAsync(ctx->chk_probes.p, o.probes, 4 * (size_t)np, in_kind_of(o.memory), s));
     magk::orientation(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), ctx->N, ctx->E, &d->clockwise, s);
-    magk::check_probes(ctx->tr_probes.as<int32_t>(), np, 2 * ctx->N, &d->bad_probe, s);
+    magk::check_probes(ctx->chk_probes.as<int32_t>(), np, 2 * ctx->N, &d->bad_probe, s);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h, d, sizeof(StepWords), hipMemcpyDeviceToHost, s));
     return MAG_OK;
@@ -4505,10 +4600,7 @@ int step_checks_enqueue(mag_ctx *ctx, const StepOptions &o, StepWords *h)
 // ... and reported, behind the synchronise
 int step_checks_report(mag_ctx *ctx, const char *fn, const StepWords &h)
 {
-    if (h.clockwise != ~0ull)
-        return fail(ctx, MAG_ERR_BAD_ARGS,
-                    "%s: element %lld has a signed area <= 0 (the stiffness carries the signed area: the pass needs counter-clockwise elements)", fn,
-                    (long long)h.clockwise);
+    if (int rc = clockwise_refused(ctx, fn, h.clockwise)) return rc;
     if (h.bad_probe != ~0ull)
         return fail(ctx, MAG_ERR_BAD_ARGS, "%s: probes[%lld] is outside [0, %lld)", fn, (long long)h.bad_probe, (long long)(2 * ctx->N));
     return MAG_OK;
@@ -4551,7 +4643,7 @@ struct StepInputs {
 int step_inputs(mag_ctx *ctx, const StepOptions &o, size_t amp_n, double amp_first, StepInputs *in)
 {
     hipStream_t s = ctx->stream;
-    const hipMemcpyKind in_kind = step_in_kind(o);
+    const hipMemcpyKind in_kind = in_kind_of(o.memory);
     const size_t vb = 16 * (size_t)ctx->N;
     std::vector<double> ones;
     double *d_amp = ctx->tr_amp.as<double>();
@@ -4592,7 +4684,7 @@ magk::NewmarkState newmark_state(const mag_ctx *ctx, size_t rows, int32_t np)
     st.known = ctx->uknown.as<uint8_t>();
     st.u_in = ctx->uin.as<double>();
     st.num_probes = np;
-    st.probes = ctx->tr_probes.as<int32_t>();
+    st.probes = ctx->chk_probes.as<int32_t>();
     st.probe_u = ctx->tr_probe.as<double>();
     st.probe_v = st.probe_u + rows * (size_t)np;
     st.probe_a = st.probe_v + rows * (size_t)np;
@@ -4673,6 +4765,66 @@ void publish_steps(mag_ctx *ctx, const StepOptions &o, bool energies, size_t row
     ctx->tr_have = true;
 }
 
+// ---- what the Newton loops of mag_run_newton and mag_run_transient_tl share on the host
+
+// MAG_TUNE_*_TIMES (env: the variable): the n phases of every iteration between the events ctx->ev[0..n], summed over the run
+struct PhaseTimer {
+    mag_ctx *ctx;
+    const char *path;
+    const int n;
+    double ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    PhaseTimer(mag_ctx *c, const char *env, int phases) : ctx(c), path(getenv(env)), n(phases) {}
+    bool on() const { return path && *path; }
+    hipEvent_t event(int k) const { return on() ? ctx->ev[k] : nullptr; }
+    int stamp(int k)
+    {
+        if (on()) HIPCHK(hipEventRecord(ctx->ev[k], ctx->stream));
+        return MAG_OK;
+    }
+    // the iteration's phases, once event n has completed (wait: not behind a synchronise of the stream yet)
+    int add(bool wait)
+    {
+        if (!on()) return MAG_OK;
+        if (wait) HIPCHK(hipEventSynchronize(ctx->ev[n]));
+        for (int ph = 0; ph < n; ++ph) {
+            float t = 0.0f;
+            HIPCHK(hipEventElapsedTime(&t, ctx->ev[ph], ctx->ev[ph + 1]));
+            ms[ph] += t;
+        }
+        return MAG_OK;
+    }
+    __attribute__((format(printf, 2, 3))) void append(const char *fmt, ...)
+    {
+        FILE *tf = on() ? fopen(path, "a") : nullptr;
+        if (!tf) return;
+        va_list ap;
+        va_start(ap, fmt);
+        vfprintf(tf, fmt, ap);
+        va_end(ap);
+        fclose(tf);
+    }
+};
+
+// the stop rule: |r_F| <= tol * ref, from the squares of the norms; ratio: what the records keep
+struct NewtonStop {
+    double ratio;
+    bool converged;
+};
+inline NewtonStop newton_stop(double r2, double ref2, double tol)
+{
+    const double rn = std::sqrt(r2), ref = std::sqrt(ref2);
+    return {ref > 0.0 ? rn / ref : (rn == 0.0 ? 0.0 : INFINITY), rn <= tol * ref};
+}
+
+// the warning of a run that stopped at the cap (what: "increment" / "step")
+void newton_unconverged(std::string &msg, const char *fn, const char *what, int index, int cap, double ratio, int it, double tol)
+{
+    char buf[256];
+    snprintf(buf, sizeof buf, "%s: %s %d did not converge within %d iterations: |r_F| / ref = %.3e after iteration %d (tolerance %.3e)", fn, what, index,
+             cap, ratio, it, tol);
+    msg = buf;
+}
+
 } // namespace
 
 void mag_default_transient_options(mag_transient_options *o)
@@ -4689,7 +4841,7 @@ int mag_assemble_effective(mag_ctx *ctx, double c_K, double c_M, double density,
     if (!ctx) return MAG_ERR_BAD_ARGS;
     if (!values_out) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null values_out", fn);
     if (!std::isfinite(c_K) || !std::isfinite(c_M)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: c_K %g / c_M %g is not finite", fn, c_K, c_M);
-    if (!pos_finite(density)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: density %g is not positive and finite", fn, density);
+    if (int rc = need_pos(ctx, fn, {{"density", density}})) return rc;
     if (int rc = memory_refused(ctx, memory, fn)) return rc;
     if (int rc = transient_refused(ctx, fn)) return rc;
     if (int rc = enter(ctx)) return rc;
@@ -4708,14 +4860,10 @@ int mag_run_transient(mag_ctx *ctx, const mag_transient_options *o)
     if (!ctx) return MAG_ERR_BAD_ARGS;
     if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null options", fn);
     if (o->steps < 1) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: steps = %d: at least one step", fn, (int)o->steps);
-    if (!pos_finite(o->dt)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: dt %g is not positive and finite", fn, o->dt);
-    if (!pos_finite(o->density)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: density %g is not positive and finite", fn, o->density);
-    if (!nonneg_finite(o->beta)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: beta %g is negative or not finite", fn, o->beta);
-    if (!nonneg_finite(o->gamma)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: gamma %g is negative or not finite", fn, o->gamma);
-    if (!nonneg_finite(o->rayleigh_mass)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: rayleigh_mass %g is negative or not finite", fn, o->rayleigh_mass);
-    if (!nonneg_finite(o->rayleigh_stiffness))
-        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: rayleigh_stiffness %g is negative or not finite", fn, o->rayleigh_stiffness);
-    if (!nonneg_finite(o->cg_tol)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: cg_tol %g is negative or not finite", fn, o->cg_tol);
+    if (int rc = need_pos(ctx, fn, {{"dt", o->dt}, {"density", o->density}})) return rc;
+    if (int rc = need_nonneg(ctx, fn, {{"beta", o->beta}, {"gamma", o->gamma}, {"rayleigh_mass", o->rayleigh_mass},
+                                       {"rayleigh_stiffness", o->rayleigh_stiffness}, {"cg_tol", o->cg_tol}}))
+        return rc;
     if (o->cg < 0 || o->cg > 4) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: cg = %d outside 0..4", fn, (int)o->cg);
     const StepOptions so = {o->steps, o->snapshot_every, o->num_probes, o->probes, o->memory, o->resume, o->amplitude, o->u0, o->v0};
     if (int rc = step_args_tail(ctx, fn, so)) return rc;
@@ -4740,12 +4888,8 @@ int mag_run_transient(mag_ctx *ctx, const mag_transient_options *o)
     HIPCHK(hipStreamSynchronize(s));
     if (int rc = step_checks_report(ctx, fn, words)) return rc;
 
-    // ---- the solver
-    const bool fused = o->cg == 0 ? ctx->use_lds : o->cg <= 3;
-    if (fused && !ctx->use_lds)
-        return fail(ctx, MAG_ERR_STATE, "%s: cg = %d needs the tile-local tables, which this context does not build (op_variant, or a tile beyond the LDS)", fn,
-                    (int)o->cg);
-    const int kind = !fused ? 0 : (o->cg == 0 ? 2 : o->cg - 1);
+    ImplicitSolver::Choice choice;
+    if (int rc = ImplicitSolver::choose(ctx, fn, o->cg, &choice)) return rc;
 
     // ---- the buffers, the inputs
     const size_t rows = (size_t)steps + 1, snaps = se > 0 ? (size_t)(steps / se) + 1 : 0;
@@ -4756,54 +4900,25 @@ int mag_run_transient(mag_ctx *ctx, const mag_transient_options *o)
     double *d_rhs = ctx->tr_rhs.as<double>(), *d_snap = ctx->tr_snap.as<double>();
     const double *d_k = ctx->kval.as<double>(), *d_m = ctx->tr_mval.as<double>();
 
-    TransientSolves solves(ctx, cg_tol);
-    const int G0 = solves.opt.check_every;
-    FieldTable tab{ctx->tr_width, ctx->tr_meta, ctx->tr_slot, ctx->tr_src, ctx->tr_val};
-    FieldSystem sys = {};
-    if (fused) {
-        if (int rc = build_field_table(ctx, tab)) return rc;
-        sys = {tab.meta.as<magk::FieldTileMeta>(), tab.slot.as<uint16_t>(), tab.val.as<double2>(), nullptr, nullptr, tab.total,
-               magk::field_cg_grid(ctx->B, ctx->cap, ctx->T, kind != 0)};
-    }
-    // A = c_M M + c_K K and the solver's copy of it: the gathered block rows and the inverse blocks, or the reduced system
+    ImplicitSolver solver(ctx, fn, choice, cg_tol);
+    if (int rc = solver.init()) return rc;
+    // A = c_M M + c_K K and the solver's copy of it
     auto system = [&](double c_M, double c_K) -> int {
         magk::effective_values(pat, d_k, d_m, c_K, c_M, ctx->tr_aval.as<double>(), s);
         HIPCHK(hipGetLastError());
-        if (!fused) return build_reduced(ctx, true, ctx->tr_aval.as<double>(), false);
-        if (int rc = field_values(ctx, tab, ctx->tr_aval.as<double>(), kind, ctx->tr_minv, ctx->tr_hminv)) return rc;
-        sys.minvP = kind ? ctx->tr_minv.as<float4>() : nullptr;
-        sys.halo_minv = kind ? ctx->tr_hminv.as<float4>() : nullptr;
-        return MAG_OK;
+        return solver.system(ctx->tr_aval.as<double>());
     };
-    // A_FF a = rhs_F from zero, a_P = 0.  The poll's first block: the previous solve's iteration count + 2 (a launch judges the
-    // iterate of the one before), rounded up to even -- the context's check_every for the first solve --, then blocks of
-    // kTransientPoll.  Launches behind convergence are no-ops: the results do not depend on it.
+    // A_FF a = rhs_F from zero, a_P = 0, and the row's bookkeeping
     std::vector<int32_t> iterations(rows, 0);
-    long long all_iterations = 0, most = 0, prev = -1;
+    long long all_iterations = 0, most = 0;
     bool all_converged = true;
     auto solve = [&](int32_t row) -> int {
-        long long G = prev < 0 ? G0 : std::min<long long>(prev + 2, 4096);
-        G += G & 1;
-        ctx->tr_first_block = (int32_t)std::max<long long>(G, 2);
-        ctx->opt.check_every = kTransientPoll;
-        if (fused) {
-            magk::to_hilbert(d_rhs, ctx->iperm.as<int32_t>(), st.known, 0, N, ctx->bP.as<double>(), s);
-            if (int rc = cg_phase_field(ctx, sys)) return rc;
-            magk::scatter_back(ctx->x.as<double>(), ctx->perm.as<uint32_t>(), st.known, ctx->tr_zero.as<double>(), N, st.a, s);
-        } else {
-            magk::compact_free(d_rhs, ctx->fidx.as<int32_t>(), st.known, n2, ctx->b_ff.as<double>(), s);
-            if (int rc = cg_phase_csr(ctx, true, ctx->tr_zero.as<double>(), st.a)) return rc;
-        }
-        HIPCHK(hipGetLastError());
+        if (int rc = solver.solve(d_rhs, ctx->tr_zero.as<double>(), st.a, nullptr, nullptr, "step %d", (int)row)) return rc;
         const mag_stats &cs = ctx->stats;
-        if (cs.breakdown)
-            return fail(ctx, MAG_ERR_NOT_CONVERGED, "%s: step %d: the solve broke down (non-finite residual after %lld iterations)", fn, (int)row,
-                        (long long)cs.iterations);
         iterations[(size_t)row] = (int32_t)cs.iterations;
         all_iterations += cs.iterations;
         most = std::max<long long>(most, cs.iterations);
         all_converged = all_converged && cs.converged != 0;
-        prev = cs.iterations;
         return MAG_OK;
     };
     auto record_energies = [&](int64_t row) -> int {
@@ -4842,8 +4957,8 @@ int mag_run_transient(mag_ctx *ctx, const mag_transient_options *o)
 
     int32_t *info = ctx->tr_info;
     info[0] = steps;
-    info[1] = fused ? 5 : 3;
-    info[2] = kind;
+    info[1] = choice.fused ? 5 : 3;
+    info[2] = choice.kind;
     info[3] = (int32_t)std::min<long long>(all_iterations, INT32_MAX);
     info[4] = (int32_t)most;
     info[5] = (int32_t)snaps;
@@ -4869,8 +4984,7 @@ int mag_download_transient(mag_ctx *ctx, mag_transient_result *o)
     if (o->energies && !ctx->tr_energies) return fail(ctx, MAG_ERR_STATE, "%s: the run recorded no energies", fn);
     if (o->snapshots && ctx->tr_snaps == 0) return fail(ctx, MAG_ERR_STATE, "%s: the run kept no snapshots", fn);
     if (int rc = enter(ctx)) return rc;
-    const hipMemcpyKind kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const hipMemcpyKind hkind = o->memory == MAG_MEM_DEVICE ? hipMemcpyHostToDevice : hipMemcpyHostToHost;
+    const auto [kind, hkind] = out_kinds(o->memory);
     hipStream_t s = ctx->stream;
     const size_t vb = 16 * (size_t)ctx->N, rows = (size_t)ctx->tr_rows, pb = 8 * rows * (size_t)ctx->tr_num_probes;
     if (o->u_out) HIPCHK(hipMemcpyAsync(o->u_out, ctx->tr_u.p, vb, kind, s));
@@ -4900,8 +5014,8 @@ int mag_get_transient_info(const mag_ctx *ctx, int32_t info[8])
 }
 
 // ---- explicit dynamics (explicit.hip): central differences on the lumped mass.  The driver shares the transient pass's
-// matrices, table buffers, records and result slots; a step that records nothing is one launch, enqueued on the context's
-// stream, and the host reads nothing between the launches ----
+// matrices, records and result slots and the passes' table (ptab: the linear fused step's) and checks (chk_*); a step that
+// records nothing is one launch, enqueued on the context's stream, and the host reads nothing between the launches ----
 namespace {
 
 // the stable step from lambda_bound: (2 / omega) (sqrt(1 + xi^2) - xi), xi = eta omega / 2, with the difference written as
@@ -4947,9 +5061,8 @@ int mag_explicit_dt(mag_ctx *ctx, double density, double rayleigh_stiffness, dou
     const char *fn = "mag_explicit_dt";
     if (!ctx) return MAG_ERR_BAD_ARGS;
     if (!out) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null out", fn);
-    if (!pos_finite(density)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: density %g is not positive and finite", fn, density);
-    if (!nonneg_finite(rayleigh_stiffness))
-        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: rayleigh_stiffness %g is negative or not finite", fn, rayleigh_stiffness);
+    if (int rc = need_pos(ctx, fn, {{"density", density}})) return rc;
+    if (int rc = need_nonneg(ctx, fn, {{"rayleigh_stiffness", rayleigh_stiffness}})) return rc;
     if (int rc = transient_refused(ctx, fn)) return rc;
     if (int rc = enter(ctx)) return rc;
     if (int rc = transient_matrices(ctx, density, 1)) return rc;
@@ -4962,12 +5075,9 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
     if (!ctx) return MAG_ERR_BAD_ARGS;
     if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null options", fn);
     if (o->steps < 1) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: steps = %d: at least one step", fn, (int)o->steps);
-    if (!nonneg_finite(o->dt)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: dt %g is negative or not finite", fn, o->dt);
-    if (!nonneg_finite(o->dt_scale)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: dt_scale %g is negative or not finite", fn, o->dt_scale);
-    if (!pos_finite(o->density)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: density %g is not positive and finite", fn, o->density);
-    if (!nonneg_finite(o->rayleigh_mass)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: rayleigh_mass %g is negative or not finite", fn, o->rayleigh_mass);
-    if (!nonneg_finite(o->rayleigh_stiffness))
-        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: rayleigh_stiffness %g is negative or not finite", fn, o->rayleigh_stiffness);
+    if (int rc = need_nonneg(ctx, fn, {{"dt", o->dt}, {"dt_scale", o->dt_scale}})) return rc;
+    if (int rc = need_pos(ctx, fn, {{"density", o->density}})) return rc;
+    if (int rc = need_nonneg(ctx, fn, {{"rayleigh_mass", o->rayleigh_mass}, {"rayleigh_stiffness", o->rayleigh_stiffness}})) return rc;
     if (o->kinematics != MAG_KIN_LINEAR && o->kinematics != MAG_KIN_TOTAL_LAGRANGIAN)
         return fail(ctx, MAG_ERR_BAD_ARGS, "%s: kinematics = %d is neither MAG_KIN_LINEAR nor MAG_KIN_TOTAL_LAGRANGIAN", fn, (int)o->kinematics);
     if (o->kinematics == MAG_KIN_TOTAL_LAGRANGIAN && o->rayleigh_stiffness != 0.0)
@@ -5013,7 +5123,7 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
     double *d_rhs = ctx->tr_rhs.as<double>(), *d_energy = ctx->tr_energy.as<double>(), *d_snap = ctx->tr_snap.as<double>();
     double *d_amp = ctx->tr_amp.as<double>();
     const double *d_f = ctx->fin.as<double>(), *d_k = ctx->kval.as<double>(), *d_m = ctx->tr_mval.as<double>();
-    StepWords *d_words = ctx->tr_bad.as<StepWords>();
+    StepWords *d_words = ctx->chk_words.as<StepWords>();
 
     // ---- total-Lagrangian kinematics (explicit_tl.hip): the mesh as the force kernel reads it, the inverted-element flag (the
     // probes' word is done with)
@@ -5030,7 +5140,7 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
     int cur = 0;
     magk::ExRec *rec[2] = {nullptr, nullptr};
     if (fused && !tl) {
-        FieldTable tab{ctx->tr_width, ctx->tr_meta, ctx->tr_slot, ctx->tr_src, ctx->tr_val};
+        FieldTable tab = pass_table(ctx);
         if (int rc = build_field_table(ctx, tab)) return rc;
         magk::field_gather(ctx->bptr.as<int32_t>(), ctx->perm.as<uint32_t>(), d_k, ctx->tr_zero.as<uint8_t>(), ctx->halo_g.as<int32_t>(),
                            tab.meta.as<magk::FieldTileMeta>(), tab.slot.as<uint16_t>(), tab.src.as<int32_t>(), N, ctx->B, ctx->T, tab.total,
@@ -5168,35 +5278,15 @@ int mag_internal_force(mag_ctx *ctx, const double *u, double *f_out, double scal
     if (int rc = transient_refused(ctx, fn)) return rc;
     if (int rc = enter(ctx)) return rc;
     if (int rc = ensure_order(ctx)) return rc;
-    hipStream_t s = ctx->stream;
-    const int64_t N = ctx->N;
-    const size_t vb = 16 * (size_t)N;
-    HIPCHK(ctx->tl_u.reserve(vb));
+    const size_t vb = 16 * (size_t)ctx->N;
     HIPCHK(ctx->tl_f.reserve(vb));
     HIPCHK(ctx->tl_part.reserve(8 * (size_t)magk::kSensBlocks));
-    HIPCHK(ctx->tl_out.reserve(32)); // W, the first element of signed area <= 0, the inverted flag
-    double *d_w = ctx->tl_out.as<double>();
-    unsigned long long *d_bad = (unsigned long long *)(d_w + 1);
-    int32_t *d_inverted = (int32_t *)(d_w + 2);
-    HIPCHK(hipMemsetAsync(d_inverted, 0, 4, s));
-    HIPCHK(hipMemcpyAsync(ctx->tl_u.p, u, vb, memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    magk::orientation(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), N, ctx->E, d_bad, s);
-    magk::tl_force(tl_mesh(ctx), ctx->tl_u.as<double>(), ctx->tl_f.as<double>(), d_inverted, ctx->tl_part.as<double>(), d_w, s);
-    HIPCHK(hipGetLastError());
-    struct {
-        double w;
-        unsigned long long bad;
-        int32_t inverted, pad;
-    } h = {0.0, ~0ull, 0, 0};
-    HIPCHK(hipMemcpyAsync(&h, d_w, 24, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (h.bad != ~0ull)
-        return fail(ctx, MAG_ERR_BAD_ARGS,
-                    "%s: element %lld has a signed area <= 0 (the stiffness carries the signed area: the pass needs counter-clockwise elements)", fn,
-                    (long long)h.bad);
-    HIPCHK(hipMemcpyAsync(f_out, ctx->tl_f.p, vb, memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    scalars_out[0] = h.w;
+    EvalWords h;
+    auto force = [&](const double *d_u, EvalWords *d) {
+        magk::tl_force(tl_mesh(ctx), d_u, ctx->tl_f.as<double>(), &d->inverted, ctx->tl_part.as<double>(), &d->W, ctx->stream);
+    };
+    if (int rc = evaluate_at(ctx, fn, u, memory, force, ctx->tl_f, vb, f_out, &h)) return rc;
+    scalars_out[0] = h.W;
     scalars_out[1] = h.inverted ? 1.0 : 0.0;
     return MAG_OK;
 }
@@ -5204,7 +5294,8 @@ int mag_internal_force(mag_ctx *ctx, const double *u, double *f_out, double scal
 // ---- nonlinear statics (newton.hip): Newton's method on the total-Lagrangian tangent, in load increments.  The driver owns the
 // buffers and enqueues force, tangent, gather and solve of every iteration on the context's stream; between them the host reads
 // one NewtonScalars record per evaluation and the CG's convergence polls, nothing else.  It shares the transient pass's solver
-// set-up (TransientSolves, the poll scheme, build_field_table / field_values / build_reduced) and none of its buffers ----
+// (ImplicitSolver on ptab), device checks (step_checks_*, chk_*) and argument tail, and the loop's host logic (PhaseTimer,
+// newton_stop, newton_unconverged) with mag_run_transient_tl; its state, records and results are its own (nt_*) ----
 void mag_default_newton_options(mag_newton_options *o)
 {
     if (!o) return;
@@ -5222,29 +5313,13 @@ int mag_assemble_tangent(mag_ctx *ctx, const double *u, double *values_out, int3
     if (int rc = transient_refused(ctx, fn)) return rc;
     if (int rc = enter(ctx)) return rc;
     if (int rc = ensure_csr(ctx)) return rc;
-    hipStream_t s = ctx->stream;
-    const size_t vb = 16 * (size_t)ctx->N;
-    const hipMemcpyKind in_kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    const hipMemcpyKind out_kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    HIPCHK(ctx->nt_ut.reserve(vb));
-    HIPCHK(ctx->nt_kval.reserve(32 * (size_t)ctx->nb));
-    HIPCHK(ctx->nt_bad.reserve(16)); // the first element of signed area <= 0, the inverted flag
-    unsigned long long *d_bad = ctx->nt_bad.as<unsigned long long>();
-    HIPCHK(hipMemsetAsync(d_bad + 1, 0, 8, s));
-    HIPCHK(hipMemcpyAsync(ctx->nt_ut.p, u, vb, in_kind, s));
-    magk::orientation(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), ctx->N, ctx->E, d_bad, s);
-    magk::tl_tangent(tl_mesh(ctx), transient_pattern(ctx), ctx->nt_ut.as<double>(), ctx->nt_kval.as<double>(), (int32_t *)(d_bad + 1), s);
-    HIPCHK(hipGetLastError());
-    unsigned long long bad = ~0ull;
-    HIPCHK(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (bad != ~0ull)
-        return fail(ctx, MAG_ERR_BAD_ARGS,
-                    "%s: element %lld has a signed area <= 0 (the stiffness carries the signed area: the pass needs counter-clockwise elements)", fn,
-                    (long long)bad);
-    HIPCHK(hipMemcpyAsync(values_out, ctx->nt_kval.p, 32 * (size_t)ctx->nb, out_kind, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return MAG_OK;
+    const size_t ab = 32 * (size_t)ctx->nb;
+    HIPCHK(ctx->nt_kval.reserve(ab));
+    EvalWords h;
+    auto tangent = [&](const double *d_u, EvalWords *d) {
+        magk::tl_tangent(tl_mesh(ctx), transient_pattern(ctx), d_u, ctx->nt_kval.as<double>(), &d->inverted, ctx->stream);
+    };
+    return evaluate_at(ctx, fn, u, memory, tangent, ctx->nt_kval, ab, values_out, &h);
 }
 
 int mag_run_newton(mag_ctx *ctx, const mag_newton_options *o)
@@ -5256,8 +5331,7 @@ int mag_run_newton(mag_ctx *ctx, const mag_newton_options *o)
     if (o->increments < 1) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: increments = %d: at least one increment", fn, (int)o->increments);
     if (o->max_newton < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: max_newton = %d is negative", fn, (int)o->max_newton);
     if (o->line_search < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: line_search = %d is negative", fn, (int)o->line_search);
-    if (!nonneg_finite(o->newton_tol)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: newton_tol %g is negative or not finite", fn, o->newton_tol);
-    if (!nonneg_finite(o->cg_tol)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: cg_tol %g is negative or not finite", fn, o->cg_tol);
+    if (int rc = need_nonneg(ctx, fn, {{"newton_tol", o->newton_tol}, {"cg_tol", o->cg_tol}})) return rc;
     if (o->cg < 0 || o->cg > 4) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: cg = %d outside 0..4", fn, (int)o->cg);
     const StepOptions so = {o->increments, 0, o->num_probes, o->probes, o->memory, 0, nullptr, o->u0, nullptr};
     if (int rc = step_args_tail(ctx, fn, so)) return rc;
@@ -5268,7 +5342,7 @@ int mag_run_newton(mag_ctx *ctx, const mag_newton_options *o)
     const bool snapshots = o->snapshots != 0;
     ctx->nt_have = false; // (a failure leaves no results of the pass)
     hipStream_t s = ctx->stream;
-    const hipMemcpyKind in_kind = step_in_kind(so);
+    const hipMemcpyKind in_kind = in_kind_of(so.memory);
 
     if (int rc = ensure_csr(ctx)) return rc;
     if (int rc = reserve_cg(ctx)) return rc;
@@ -5278,27 +5352,13 @@ int mag_run_newton(mag_ctx *ctx, const mag_newton_options *o)
     const magk::TlMesh mesh = tl_mesh(ctx);
 
     // ---- the checks that need the device: the elements' orientation, the probes
-    HIPCHK(ctx->nt_bad.reserve(16));
-    HIPCHK(ctx->nt_probes.reserve(4 * (size_t)std::max(np, 1)));
-    unsigned long long words[2] = {~0ull, ~0ull}, *d_words = ctx->nt_bad.as<unsigned long long>();
-    if (np > 0) HIPCHK(hipMemcpyAsync(ctx->nt_probes.p, o->probes, 4 * (size_t)np, in_kind, s));
-    magk::orientation(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), N, ctx->E, d_words, s);
-    magk::check_probes(ctx->nt_probes.as<int32_t>(), np, n2, d_words + 1, s);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(words, d_words, 16, hipMemcpyDeviceToHost, s));
+    StepWords words;
+    if (int rc = step_checks_enqueue(ctx, so, &words)) return rc;
     HIPCHK(hipStreamSynchronize(s));
-    if (words[0] != ~0ull)
-        return fail(ctx, MAG_ERR_BAD_ARGS,
-                    "%s: element %lld has a signed area <= 0 (the stiffness carries the signed area: the pass needs counter-clockwise elements)", fn,
-                    (long long)words[0]);
-    if (words[1] != ~0ull) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: probes[%lld] is outside [0, %lld)", fn, (long long)words[1], (long long)n2);
+    if (int rc = step_checks_report(ctx, fn, words)) return rc;
 
-    // ---- the solver
-    const bool fused = o->cg == 0 ? ctx->use_lds : o->cg <= 3;
-    if (fused && !ctx->use_lds)
-        return fail(ctx, MAG_ERR_STATE, "%s: cg = %d needs the tile-local tables, which this context does not build (op_variant, or a tile beyond the LDS)", fn,
-                    (int)o->cg);
-    const int kind = !fused ? 0 : (o->cg == 0 ? 2 : o->cg - 1);
+    ImplicitSolver::Choice choice;
+    if (int rc = ImplicitSolver::choose(ctx, fn, o->cg, &choice)) return rc;
 
     // ---- the buffers, the inputs
     for (DevBuf *b : {&ctx->nt_u, &ctx->nt_ut, &ctx->nt_uc, &ctx->nt_du, &ctx->nt_dup, &ctx->nt_zero, &ctx->nt_f, &ctx->nt_rhs, &ctx->nt_fout})
@@ -5334,27 +5394,19 @@ int mag_run_newton(mag_ctx *ctx, const mag_newton_options *o)
     double *d_kt = ctx->nt_kval.as<double>(), *d_snap = ctx->nt_snap.as<double>(), *d_part = ctx->nt_part.as<double>();
     const double *d_zero = ctx->nt_zero.as<double>(), *d_fin = ctx->fin.as<double>(), *d_uin = ctx->uin.as<double>();
     const uint8_t *d_known = ctx->uknown.as<uint8_t>();
-    const int32_t *d_probes = ctx->nt_probes.as<int32_t>();
+    const int32_t *d_probes = ctx->chk_probes.as<int32_t>();
     NewtonScalars *d_scal = ctx->nt_scal.as<NewtonScalars>();
 
-    TransientSolves solves(ctx, cg_tol);
-    PatternSolver ps{ctx, fused, kind, FieldTable{ctx->nt_width, ctx->nt_meta, ctx->nt_slot, ctx->nt_src, ctx->nt_val}, ctx->nt_minv, ctx->nt_hminv,
-                     solves.opt.check_every};
-    if (int rc = ps.init()) return rc;
-    // the solver's copy of the tangent in nt_kval
-    auto system = [&]() -> int { return ps.system(d_kt); };
-    // K_T,FF du_F = rhs_F from zero, du_P = dP (the support part of the step, or zero): the transient pass's poll scheme
+    ImplicitSolver solver(ctx, fn, choice, cg_tol);
+    if (int rc = solver.init()) return rc;
+    // K_T,FF du_F = rhs_F from zero, du_P = dP (the support part of the step, or zero), on the solver's copy of the tangent in nt_kval
     std::vector<int32_t> newton_its(rows, 0), cg_its;
     std::vector<double> energies(2 * rows, 0.0), residuals, steps;
     long long all_cg = 0, halvings = 0;
     auto solve = [&](int32_t inc, int32_t it, const double *dP) -> int {
-        if (int rc = ps.solve(d_rhs, dP, d_du)) return rc;
-        const mag_stats &cs = ctx->stats;
-        if (cs.breakdown)
-            return fail(ctx, MAG_ERR_NOT_CONVERGED, "%s: increment %d, iteration %d: the solve broke down (non-finite residual after %lld iterations)",
-                        fn, (int)inc, (int)it, (long long)cs.iterations);
-        cg_its.push_back((int32_t)cs.iterations);
-        all_cg += cs.iterations;
+        if (int rc = solver.solve(d_rhs, dP, d_du, nullptr, nullptr, "increment %d, iteration %d", (int)inc, (int)it)) return rc;
+        cg_its.push_back((int32_t)solver.prev);
+        all_cg += solver.prev;
         return MAG_OK;
     };
     // f_int, W and the norms of the state w under load[at] (with du: the slope too, of the force that is in nt_f already)
@@ -5373,14 +5425,8 @@ int mag_run_newton(mag_ctx *ctx, const mag_newton_options *o)
         energies[2 * (size_t)row + 1] = h.W - loads[(size_t)row] * h.fu;
     };
 
-    // MAG_TUNE_NEWTON_TIMES: the phases of every iteration between events, read behind the evaluation's synchronise
-    const char *times_path = getenv("MAG_TUNE_NEWTON_TIMES");
-    const bool timed = times_path && *times_path;
-    double phase_ms[4] = {0.0, 0.0, 0.0, 0.0}; // tangent + right-hand side, gather, CG, update + force + norms
-    auto stamp = [&](int k) -> int {
-        if (timed) HIPCHK(hipEventRecord(ctx->ev[k], s));
-        return MAG_OK;
-    };
+    // the phases of every iteration: tangent + right-hand side, gather, CG, update + force + norms
+    PhaseTimer timer(ctx, "MAG_TUNE_NEWTON_TIMES", 4);
 
     // ---- the start
     NewtonScalars cur = {};
@@ -5398,15 +5444,15 @@ int mag_run_newton(mag_ctx *ctx, const mag_newton_options *o)
         double ratio = 0.0;
         for (int32_t it = 1; it <= cap && !converged; ++it) {
             const bool first = it == 1;
-            if (int rc = stamp(0)) return rc;
+            if (int rc = timer.stamp(0)) return rc;
             magk::tl_tangent(mesh, pat, d_u, d_kt, &d_scal->inverted, s);
             magk::newton_rhs(pat, d_kt, d_known, d_fin, d_load, k, d_f, d_u, d_uin, first ? 1 : 0, d_rhs, d_dup, s);
             HIPCHK(hipGetLastError());
-            if (int rc = stamp(1)) return rc;
-            if (int rc = system()) return rc;
-            if (int rc = stamp(2)) return rc;
+            if (int rc = timer.stamp(1)) return rc;
+            if (int rc = solver.system(d_kt)) return rc;
+            if (int rc = timer.stamp(2)) return rc;
             if (int rc = solve(k, it, first ? d_dup : d_zero)) return rc;
-            if (int rc = stamp(3)) return rc;
+            if (int rc = timer.stamp(3)) return rc;
             double slope = 0.0;
             const double Pi0 = cur.W - lam * cur.fu;
             if (H > 0) { // the slope of Pi along the step, of the force still in nt_f
@@ -5428,30 +5474,19 @@ int mag_run_newton(mag_ctx *ctx, const mag_newton_options *o)
                 sl *= 0.5;
                 ++halvings;
             }
-            if (timed) {
-                HIPCHK(hipEventRecord(ctx->ev[4], s));
-                HIPCHK(hipEventSynchronize(ctx->ev[4]));
-                for (int ph = 0; ph < 4; ++ph) {
-                    float ms = 0.0f;
-                    HIPCHK(hipEventElapsedTime(&ms, ctx->ev[ph], ctx->ev[ph + 1]));
-                    phase_ms[ph] += ms;
-                }
-            }
+            if (int rc = timer.stamp(4)) return rc;
+            if (int rc = timer.add(true)) return rc;
             std::swap(d_u, d_ut);
             cur = trial;
             inverted = inverted || cur.inverted != 0;
-            const double rn = std::sqrt(cur.r2), ref = std::sqrt(std::max(cur.f2, cur.p2));
-            ratio = ref > 0.0 ? rn / ref : (rn == 0.0 ? 0.0 : INFINITY);
+            const NewtonStop stop = newton_stop(cur.r2, std::max(cur.f2, cur.p2), tol);
+            ratio = stop.ratio, converged = stop.converged;
             residuals.push_back(ratio);
             steps.push_back(sl);
-            converged = rn <= tol * ref;
             if (converged) newton_its[(size_t)k] = it;
         }
         if (!converged) {
-            char buf[256];
-            snprintf(buf, sizeof buf, "%s: increment %d did not converge within %d iterations: |r_F| / ref = %.3e after iteration %d (tolerance %.3e)",
-                     fn, (int)k, (int)cap, ratio, (int)cap, tol);
-            unconverged = buf;
+            newton_unconverged(unconverged, fn, "increment", k, cap, ratio, cap, tol);
             break;
         }
         HIPCHK(hipMemcpyAsync(d_uc, d_u, vb, hipMemcpyDeviceToDevice, s));
@@ -5470,8 +5505,8 @@ int mag_run_newton(mag_ctx *ctx, const mag_newton_options *o)
 
     int32_t *info = ctx->nt_info;
     info[0] = done;
-    info[1] = fused ? 5 : 3;
-    info[2] = kind;
+    info[1] = choice.fused ? 5 : 3;
+    info[2] = choice.kind;
     info[3] = (int32_t)residuals.size();
     info[4] = (int32_t)std::min<long long>(all_cg, INT32_MAX);
     info[5] = (int32_t)std::min<long long>(halvings, INT32_MAX);
@@ -5487,12 +5522,8 @@ int mag_run_newton(mag_ctx *ctx, const mag_newton_options *o)
     ctx->nt_newton = newton_its;
     ctx->nt_cg = cg_its;
     ctx->nt_have = true;
-    if (timed)
-        if (FILE *tf = fopen(times_path, "a")) {
-            fprintf(tf, "{\"newton_iterations\": %d, \"cg_iterations\": %lld, \"tangent_ms\": %.6f, \"gather_ms\": %.6f, \"cg_ms\": %.6f, \"force_ms\": %.6f}\n",
-                    (int)residuals.size(), all_cg, phase_ms[0], phase_ms[1], phase_ms[2], phase_ms[3]);
-            fclose(tf);
-        }
+    timer.append("{\"newton_iterations\": %d, \"cg_iterations\": %lld, \"tangent_ms\": %.6f, \"gather_ms\": %.6f, \"cg_ms\": %.6f, \"force_ms\": %.6f}\n",
+                 (int)residuals.size(), all_cg, timer.ms[0], timer.ms[1], timer.ms[2], timer.ms[3]);
     if (!unconverged.empty()) ctx->err = unconverged;
     return MAG_OK;
 }
@@ -5509,8 +5540,7 @@ int mag_download_newton(mag_ctx *ctx, mag_newton_result *o)
     if (o->probe_u && ctx->nt_num_probes == 0) return fail(ctx, MAG_ERR_STATE, "%s: the run recorded no probes", fn);
     if (o->snapshots && ctx->nt_snaps == 0) return fail(ctx, MAG_ERR_STATE, "%s: the run kept no snapshots", fn);
     if (int rc = enter(ctx)) return rc;
-    const hipMemcpyKind kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const hipMemcpyKind hkind = o->memory == MAG_MEM_DEVICE ? hipMemcpyHostToDevice : hipMemcpyHostToHost;
+    const auto [kind, hkind] = out_kinds(o->memory);
     hipStream_t s = ctx->stream;
     const size_t vb = 16 * (size_t)ctx->N, rows = (size_t)ctx->nt_increments + 1, its = ctx->nt_residuals.size();
     if (o->u_out) HIPCHK(hipMemcpyAsync(o->u_out, ctx->nt_uc.p, vb, kind, s));
@@ -5539,9 +5569,9 @@ int mag_get_newton_info(const mag_ctx *ctx, int32_t info[8])
 }
 
 // ---- nonlinear transient dynamics (transient_tl.hip): Newmark's method on the total-Lagrangian internal force, every step by
-// Newton's method on the effective tangent.  The driver owns its matrix, table and work buffers, shares the step frame of
-// mag_run_transient / mag_run_explicit (the checks, the inputs, the records, the result slots) and the solver set-up of
-// mag_run_newton (TransientSolves, the poll scheme); between the launches the host reads one TlStepScalars record per Newton
+// Newton's method on the effective tangent.  The driver owns its matrix and work buffers (tt_*), shares the step frame of
+// mag_run_transient / mag_run_explicit (the checks, the inputs, the records, the result slots), their solver (ImplicitSolver on
+// ptab) and the Newton loop's host logic of mag_run_newton; between the launches the host reads one TlStepScalars record per Newton
 // iteration and the CG's convergence polls, nothing else ----
 void mag_default_transient_tl_options(mag_transient_tl_options *o)
 {
@@ -5559,35 +5589,19 @@ int mag_assemble_effective_tangent(mag_ctx *ctx, const double *u, double c_K, do
     if (!u) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null u", fn);
     if (!values_out) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null values_out", fn);
     if (!std::isfinite(c_K) || !std::isfinite(c_M)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: c_K %g / c_M %g is not finite", fn, c_K, c_M);
-    if (!pos_finite(density)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: density %g is not positive and finite", fn, density);
+    if (int rc = need_pos(ctx, fn, {{"density", density}})) return rc;
     if (int rc = memory_refused(ctx, memory, fn)) return rc;
     if (int rc = transient_refused(ctx, fn)) return rc;
     if (int rc = enter(ctx)) return rc;
     if (int rc = transient_matrices(ctx, density, lumped)) return rc;
-    hipStream_t s = ctx->stream;
-    const size_t vb = 16 * (size_t)ctx->N;
-    const hipMemcpyKind in_kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    const hipMemcpyKind out_kind = memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    HIPCHK(ctx->tt_u.reserve(vb));
-    HIPCHK(ctx->tt_aval.reserve(32 * (size_t)ctx->nb));
-    HIPCHK(ctx->tt_bad.reserve(16)); // the first element of signed area <= 0, the inverted flag
-    unsigned long long *d_bad = ctx->tt_bad.as<unsigned long long>();
-    HIPCHK(hipMemsetAsync(d_bad + 1, 0, 8, s));
-    HIPCHK(hipMemcpyAsync(ctx->tt_u.p, u, vb, in_kind, s));
-    magk::orientation(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), ctx->N, ctx->E, d_bad, s);
-    magk::tl_effective_tangent(tl_mesh(ctx), transient_pattern(ctx), ctx->tt_u.as<double>(), ctx->tr_mval.as<double>(), c_K, c_M,
-                               ctx->tt_aval.as<double>(), (int32_t *)(d_bad + 1), s);
-    HIPCHK(hipGetLastError());
-    unsigned long long bad = ~0ull;
-    HIPCHK(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (bad != ~0ull)
-        return fail(ctx, MAG_ERR_BAD_ARGS,
-                    "%s: element %lld has a signed area <= 0 (the stiffness carries the signed area: the pass needs counter-clockwise elements)", fn,
-                    (long long)bad);
-    HIPCHK(hipMemcpyAsync(values_out, ctx->tt_aval.p, 32 * (size_t)ctx->nb, out_kind, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return MAG_OK;
+    const size_t ab = 32 * (size_t)ctx->nb;
+    HIPCHK(ctx->tt_aval.reserve(ab));
+    EvalWords h;
+    auto tangent = [&](const double *d_u, EvalWords *d) {
+        magk::tl_effective_tangent(tl_mesh(ctx), transient_pattern(ctx), d_u, ctx->tr_mval.as<double>(), c_K, c_M, ctx->tt_aval.as<double>(),
+                                   &d->inverted, ctx->stream);
+    };
+    return evaluate_at(ctx, fn, u, memory, tangent, ctx->tt_aval, ab, values_out, &h);
 }
 
 int mag_run_transient_tl(mag_ctx *ctx, const mag_transient_tl_options *o)
@@ -5597,16 +5611,13 @@ int mag_run_transient_tl(mag_ctx *ctx, const mag_transient_tl_options *o)
     if (!ctx) return MAG_ERR_BAD_ARGS;
     if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null options", fn);
     if (o->steps < 1) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: steps = %d: at least one step", fn, (int)o->steps);
-    if (!pos_finite(o->dt)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: dt %g is not positive and finite", fn, o->dt);
-    if (!pos_finite(o->density)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: density %g is not positive and finite", fn, o->density);
-    if (!nonneg_finite(o->beta)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: beta %g is negative or not finite", fn, o->beta);
+    if (int rc = need_pos(ctx, fn, {{"dt", o->dt}, {"density", o->density}})) return rc;
+    if (int rc = need_nonneg(ctx, fn, {{"beta", o->beta}})) return rc;
     if (o->beta == 0.0)
         return fail(ctx, MAG_ERR_BAD_ARGS, "%s: beta = 0 leaves no system to solve: the explicit step is mag_run_explicit's (kinematics = MAG_KIN_TOTAL_LAGRANGIAN)",
                     fn);
-    if (!nonneg_finite(o->gamma)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: gamma %g is negative or not finite", fn, o->gamma);
-    if (!nonneg_finite(o->rayleigh_mass)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: rayleigh_mass %g is negative or not finite", fn, o->rayleigh_mass);
-    if (!nonneg_finite(o->cg_tol)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: cg_tol %g is negative or not finite", fn, o->cg_tol);
-    if (!nonneg_finite(o->newton_tol)) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: newton_tol %g is negative or not finite", fn, o->newton_tol);
+    if (int rc = need_nonneg(ctx, fn, {{"gamma", o->gamma}, {"rayleigh_mass", o->rayleigh_mass}, {"cg_tol", o->cg_tol}, {"newton_tol", o->newton_tol}}))
+        return rc;
     if (o->max_newton < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: max_newton = %d is negative", fn, (int)o->max_newton);
     if (o->cg < 0 || o->cg > 4) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: cg = %d outside 0..4", fn, (int)o->cg);
     const StepOptions so = {o->steps, o->snapshot_every, o->num_probes, o->probes, o->memory, o->resume, o->amplitude, o->u0, o->v0};
@@ -5636,12 +5647,8 @@ int mag_run_transient_tl(mag_ctx *ctx, const mag_transient_tl_options *o)
     HIPCHK(hipStreamSynchronize(s));
     if (int rc = step_checks_report(ctx, fn, words)) return rc;
 
-    // ---- the solver
-    const bool fused = o->cg == 0 ? ctx->use_lds : o->cg <= 3;
-    if (fused && !ctx->use_lds)
-        return fail(ctx, MAG_ERR_STATE, "%s: cg = %d needs the tile-local tables, which this context does not build (op_variant, or a tile beyond the LDS)", fn,
-                    (int)o->cg);
-    const int kind = !fused ? 0 : (o->cg == 0 ? 2 : o->cg - 1);
+    ImplicitSolver::Choice choice;
+    if (int rc = ImplicitSolver::choose(ctx, fn, o->cg, &choice)) return rc;
 
     // ---- the buffers, the inputs
     const size_t rows = (size_t)steps + 1, snaps = se > 0 ? (size_t)(steps / se) + 1 : 0;
@@ -5661,36 +5668,24 @@ int mag_run_transient_tl(mag_ctx *ctx, const mag_transient_tl_options *o)
     TlStepScalars *d_scal = ctx->tt_scal.as<TlStepScalars>();
     HIPCHK(hipMemsetAsync(d_scal, 0, sizeof(TlStepScalars) + 8, s));
 
-    TransientSolves solves(ctx, cg_tol);
-    PatternSolver ps{ctx, fused, kind, FieldTable{ctx->tt_width, ctx->tt_meta, ctx->tt_slot, ctx->tt_src, ctx->tt_val}, ctx->tt_minv, ctx->tt_hminv,
-                     solves.opt.check_every};
-    if (int rc = ps.init()) return rc;
+    ImplicitSolver solver(ctx, fn, choice, cg_tol);
+    if (int rc = solver.init()) return rc;
     // A_T = cm M + ck K_T(w) in tt_aval, one launch
     auto tangent = [&](double cm, double ck, const double *w) -> int {
         magk::tl_effective_tangent(mesh, pat, w, d_m, ck, cm, d_at, &d_scal->inverted, s);
         HIPCHK(hipGetLastError());
         return MAG_OK;
     };
-    // MAG_TUNE_TRANSIENT_TL_TIMES: the phases of every iteration between events, read behind the iteration's synchronise
-    const char *times_path = getenv("MAG_TUNE_TRANSIENT_TL_TIMES");
-    const bool timed = times_path && *times_path;
-    double phase_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0}; // tangent; gather; into the solver's numbering; CG; back + state + force + residual
-    auto stamp = [&](int k) -> int {
-        if (timed) HIPCHK(hipEventRecord(ctx->ev[k], s));
-        return MAG_OK;
-    };
+    // the phases of every iteration: tangent; gather; into the solver's numbering; CG; back + state + force + residual
+    PhaseTimer timer(ctx, "MAG_TUNE_TRANSIENT_TL_TIMES", 5);
     // A_T,FF x_F = rhs_F from zero, x_P = 0: the transient pass's poll scheme
     std::vector<int32_t> iterations(rows, 0), newton_its(rows, 0), cg_its;
     std::vector<double> residuals;
     long long all_cg = 0;
     auto solve = [&](int32_t step, int32_t it, double *x) -> int {
-        if (int rc = ps.solve(d_rhs, d_zero, x, timed ? ctx->ev[3] : nullptr, timed ? ctx->ev[4] : nullptr)) return rc;
-        const mag_stats &cs = ctx->stats;
-        if (cs.breakdown)
-            return fail(ctx, MAG_ERR_NOT_CONVERGED, "%s: step %d, iteration %d: the solve broke down (non-finite residual after %lld iterations)", fn,
-                        (int)step, (int)it, (long long)cs.iterations);
-        iterations[(size_t)step] = (int32_t)std::min<long long>((long long)iterations[(size_t)step] + cs.iterations, INT32_MAX);
-        all_cg += cs.iterations;
+        if (int rc = solver.solve(d_rhs, d_zero, x, timer.event(3), timer.event(4), "step %d, iteration %d", (int)step, (int)it)) return rc;
+        iterations[(size_t)step] = (int32_t)std::min<long long>((long long)iterations[(size_t)step] + solver.prev, INT32_MAX);
+        all_cg += solver.prev;
         return MAG_OK;
     };
     // f_int(w) and the residual of (w, av, vv) under amplitude[at] into tr_rhs, its norms into the record
@@ -5714,7 +5709,7 @@ int mag_run_transient_tl(mag_ctx *ctx, const mag_transient_tl_options *o)
         if (int rc = residual(st.u, d_zero, st.v, 0)) return rc;
         magk::effective_values(pat, ctx->kval.as<double>(), d_m, 0.0, 1.0, d_at, s);
         HIPCHK(hipGetLastError());
-        if (int rc = ps.system(d_at)) return rc;
+        if (int rc = solver.system(d_at)) return rc;
         if (int rc = solve(0, 0, st.a)) return rc;
     }
     magk::newmark_record(st, 0, se > 0 ? d_snap : nullptr, s);
@@ -5735,37 +5730,28 @@ int mag_run_transient_tl(mag_ctx *ctx, const mag_transient_tl_options *o)
         int32_t it = 0;
         while (it < cap && !converged) {
             ++it;
-            if (int rc = stamp(0)) return rc;
+            if (int rc = timer.stamp(0)) return rc;
             if (int rc = tangent(c_M, c_u, d_un)) return rc;
-            if (int rc = stamp(1)) return rc;
-            if (int rc = ps.system(d_at)) return rc;
-            if (int rc = stamp(2)) return rc;
+            if (int rc = timer.stamp(1)) return rc;
+            if (int rc = solver.system(d_at)) return rc;
+            if (int rc = timer.stamp(2)) return rc;
             if (int rc = solve(n + 1, it, d_da)) return rc; // (records events 3 and 4 around the CG)
             magk::tl_trial_state(trial, 1.0, c_u, c_v, 0, s);
             if (int rc = residual(d_un, d_an, d_vn, n + 1)) return rc;
             TlStepScalars h = {};
             HIPCHK(hipMemcpyAsync(&h, d_scal, sizeof(TlStepScalars), hipMemcpyDeviceToHost, s));
-            if (timed) HIPCHK(hipEventRecord(ctx->ev[5], s));
+            if (int rc = timer.stamp(5)) return rc;
             HIPCHK(hipStreamSynchronize(s));
-            if (timed)
-                for (int ph = 0; ph < 5; ++ph) {
-                    float ms = 0.0f;
-                    HIPCHK(hipEventElapsedTime(&ms, ctx->ev[ph], ctx->ev[ph + 1]));
-                    phase_ms[ph] += ms;
-                }
+            if (int rc = timer.add(false)) return rc;
             inverted = inverted || h.inverted != 0;
-            const double rn = std::sqrt(h.r2), ref = std::sqrt(std::max(h.f2, std::max(h.i2, h.m2)));
-            ratio = ref > 0.0 ? rn / ref : (rn == 0.0 ? 0.0 : INFINITY);
+            const NewtonStop stop = newton_stop(h.r2, std::max(h.f2, std::max(h.i2, h.m2)), tol);
+            ratio = stop.ratio, converged = stop.converged;
             residuals.push_back(ratio);
-            cg_its.push_back((int32_t)ps.prev);
-            converged = rn <= tol * ref;
+            cg_its.push_back((int32_t)solver.prev);
         }
         most = std::max(most, it);
         if (!converged) {
-            char buf[256];
-            snprintf(buf, sizeof buf, "%s: step %d did not converge within %d iterations: |r_F| / ref = %.3e after iteration %d (tolerance %.3e)", fn,
-                     (int)(n + 1), (int)cap, ratio, (int)it, tol);
-            unconverged = buf;
+            newton_unconverged(unconverged, fn, "step", n + 1, cap, ratio, it, tol);
             break;
         }
         newton_its[(size_t)n + 1] = it;
@@ -5810,8 +5796,8 @@ int mag_run_transient_tl(mag_ctx *ctx, const mag_transient_tl_options *o)
     for (int32_t v : iterations) step_most = std::max<long long>(step_most, v), step_all += v;
     int32_t *info = ctx->tr_info;
     info[0] = done;
-    info[1] = fused ? 5 : 3;
-    info[2] = kind;
+    info[1] = choice.fused ? 5 : 3;
+    info[2] = choice.kind;
     info[3] = (int32_t)std::min<long long>(step_all, INT32_MAX);
     info[4] = (int32_t)step_most;
     info[5] = (int32_t)snaps_done;
@@ -5819,8 +5805,8 @@ int mag_run_transient_tl(mag_ctx *ctx, const mag_transient_tl_options *o)
     info[7] = done == steps ? 1 : 0;
     int32_t *ti = ctx->tt_info;
     ti[0] = done;
-    ti[1] = fused ? 5 : 3;
-    ti[2] = kind;
+    ti[1] = choice.fused ? 5 : 3;
+    ti[2] = choice.kind;
     ti[3] = (int32_t)residuals.size();
     ti[4] = most;
     ti[5] = (int32_t)std::min<long long>(all_cg, INT32_MAX);
@@ -5834,12 +5820,8 @@ int mag_run_transient_tl(mag_ctx *ctx, const mag_transient_tl_options *o)
     published.steps = done;
     publish_steps(ctx, published, energies, rows_done, snaps_done, t_start, dt, amp_last, 0.0, 0.0);
     ctx->tt_have = true;
-    if (timed)
-        if (FILE *tf = fopen(times_path, "a")) {
-            fprintf(tf, "{\"steps\": %d, \"newton_iterations\": %d, \"cg_iterations\": %lld, \"tangent_ms\": %.6f, \"gather_ms\": %.6f, \"cg_ms\": %.6f, \"state_ms\": %.6f}\n",
-                    (int)done, (int)residuals.size(), all_cg, phase_ms[0], phase_ms[1], phase_ms[3], phase_ms[2] + phase_ms[4]);
-            fclose(tf);
-        }
+    timer.append("{\"steps\": %d, \"newton_iterations\": %d, \"cg_iterations\": %lld, \"tangent_ms\": %.6f, \"gather_ms\": %.6f, \"cg_ms\": %.6f, \"state_ms\": %.6f}\n",
+                 (int)done, (int)residuals.size(), all_cg, timer.ms[0], timer.ms[1], timer.ms[3], timer.ms[2] + timer.ms[4]);
     if (!unconverged.empty()) ctx->err = unconverged;
     return MAG_OK;
 }
@@ -5854,8 +5836,7 @@ int mag_download_transient_tl(mag_ctx *ctx, mag_transient_tl_result *o)
         return fail(ctx, MAG_ERR_BAD_ARGS, "%s: transient dynamics run on one GPU: this context has a communicator of %d ranks", fn, ctx->comm.nranks);
     if (!ctx->have_problem || !ctx->tr_have || !ctx->tt_have) return fail(ctx, MAG_ERR_STATE, "%s before a completed mag_run_transient_tl", fn);
     if (int rc = enter(ctx)) return rc;
-    const hipMemcpyKind kind = o->memory == MAG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const hipMemcpyKind hkind = o->memory == MAG_MEM_DEVICE ? hipMemcpyHostToDevice : hipMemcpyHostToHost;
+    const auto [kind, hkind] = out_kinds(o->memory);
     hipStream_t s = ctx->stream;
     const size_t its = ctx->tt_residuals.size();
     if (o->newton_iterations) HIPCHK(hipMemcpyAsync(o->newton_iterations, ctx->tt_newton.data(), 4 * ctx->tt_newton.size(), hkind, s));

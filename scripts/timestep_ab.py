@@ -1,15 +1,20 @@
-"""A/B of builds of the library over the three time-stepping passes (mag_run_transient, mag_run_explicit with either kinematics)
-in ONE GPU session: the same bits, and the same speed as far as the session can tell.  Every library is loaded by a child process
+"""A/B of builds of the library over the time-stepping passes (mag_run_transient, mag_run_explicit with either kinematics,
+mag_run_transient_tl) and mag_run_newton in ONE GPU session: the same bits, and the same speed as far as the session can tell.  Every library is loaded by a child process
 of its own through MAG_LIB_PATH; the libraries alternate over the rounds.  The first library named is the parent, the others are
 compared with it.
 
 Bits (--rounds-bits, default 2): on holes3k and two_fans, with the tile-local tables and under op_variant=1, the implicit pass at
 cg = 0 and cg = 4, the linear and the total-Lagrangian explicit pass; every run records three probes, the energies, a snapshot
 every 5 steps and (explicit) a row every 3, and is a 40-step run followed by a resumed 24-step run.  A sha256 of every array of
-download_transient() and the info words are printed; every library must agree with the parent on each.
+download_transient() and the info words are printed; every library must agree with the parent on each.  Likewise mag_run_newton
+(2 increments, line search off and on, cg = 0 and 4: every array of download_newton()), mag_run_transient_tl (a 10-step run and a
+resumed 6-step run, cg = 0 and 4: download_transient() and download_transient_tl()) and the three single evaluations
+(mag_assemble_tangent, mag_assemble_effective_tangent, mag_internal_force) at a non-zero state.
 
 Speed (--rounds, default 7): on plate100k, 4096 explicit steps without records at 0.9 dt_bound for both kinematics and 256
-implicit steps at dt = T1 / 200, cg = 0 (T1 from the host's eigensolver, tests/modal_ref.py).  A child does one run of each to
+implicit steps at dt = T1 / 200, cg = 0 (T1 from the host's eigensolver, tests/modal_ref.py); on the same plate as the cantilever of
+profiles/newton.json and profiles/transient_tl.json, the first of the eight increments of mag_run_newton and 8 steps of
+mag_run_transient_tl at that profile's dt.  A child does one run of each to
 warm up and one timed run of each (the passes synchronise before they return); a figure is the median over the rounds.  The
 control is the parent library once more under another file name: twice the relative difference between the two parent legs is
 what the session cannot resolve, and a library passes a figure when its median exceeds the parent's by no more than that.
@@ -32,7 +37,9 @@ sys.path.insert(0, ROOT)
 RHO = 2700.0
 PROBES = (1, 100, 401)
 EX_STEPS, IM_STEPS = 4096, 256
-FIGURES = ("explicit_linear_4096_steps", "explicit_tl_4096_steps", "implicit_cg0_256_steps")
+TL_STEPS, TOTAL_LOAD = 8, 3e8
+FIGURES = ("explicit_linear_4096_steps", "explicit_tl_4096_steps", "implicit_cg0_256_steps", "newton_cantilever_1_increment",
+           "transient_tl_cantilever_8_steps")
 
 
 def meshes():
@@ -46,6 +53,17 @@ def meshes():
 
 def digest(x):
     return hashlib.sha256(np.ascontiguousarray(x).tobytes()).hexdigest()[:16]
+
+
+def cantilever():
+    """the plate of plate100k clamped on the left, its right edge pulled down by TOTAL_LOAD (scripts/newton_probe.py)"""
+    from magnetite_amd import meshgen
+    mesh = meshgen.plate(224)
+    prob = meshgen.config_fixed_left_point_load(mesh, load=0.0)
+    right = np.flatnonzero(mesh.xy[:, 0] > mesh.xy[:, 0].max() - 1e-9)
+    prob.f_in[:] = 0.0
+    prob.f_in[2 * right + 1] = -TOTAL_LOAD / len(right)
+    return prob
 
 
 def bits_leg():
@@ -70,6 +88,26 @@ def bits_leg():
                         for k in sorted(got):
                             out[f"{key}/{k}"] = digest(np.asarray(got[k]))
                         out[f"{key}/info"] = list(c.transient_info().values())
+                for cg in (0, 4):
+                    for search in (0, 3):
+                        c.run_newton(increments=2, line_search=search, cg=cg, probes=PROBES, snapshots=True)
+                        got, key = c.download_newton(), f"{mesh}/{cname}/newton_cg{cg}_search{search}"
+                        for k in sorted(got):
+                            out[f"{key}/{k}"] = digest(np.asarray(got[k]))
+                        out[f"{key}/info"] = list(c.newton_info().values())
+                    for part, steps, resume in (("first", 10, False), ("resumed", 6, True)):
+                        c.run_transient_tl(steps=steps, dt=dt_im, cg=cg, rayleigh=(5.0, 0.0), resume=resume,
+                                           amplitude=1.0 + 0.5 * np.sin(0.3 * np.arange(steps + 1)), **rec)
+                        got, key = dict(c.download_transient(), **c.download_transient_tl()), f"{mesh}/{cname}/transient_tl_cg{cg}/{part}"
+                        for k in sorted(got):
+                            out[f"{key}/{k}"] = digest(np.asarray(got[k]))
+                        out[f"{key}/info"] = list(c.transient_info().values()) + list(c.transient_tl_info().values())
+                u = 2e-4 * np.sin(np.arange(2.0 * c.N))
+                f, W, inverted = c.internal_force(u)
+                evaluations = dict(tangent=c.assemble_tangent(u), effective_tangent=c.assemble_effective_tangent(u, 0.25 * dt_im ** 2, 1.01, RHO),
+                                   internal_force=f, W=np.float64(W), inverted=np.int32(inverted))
+                for k, v in evaluations.items():
+                    out[f"{mesh}/{cname}/evaluations/{k}"] = digest(np.asarray(v))
     print(json.dumps(out))
 
 
@@ -84,12 +122,29 @@ def speed_leg(dt_im):
                 "explicit_tl_4096_steps": lambda: c.run_explicit(EX_STEPS, dt=dt, density=RHO, kinematics="tl"),
                 "implicit_cg0_256_steps": lambda: c.run_transient(IM_STEPS, dt_im, density=RHO, cg=0)}
         wall = {}
-        for name in FIGURES:
-            runs[name]()
+        for name, run in runs.items():
+            run()
             t0 = time.perf_counter()
-            runs[name]()
+            run()
             wall[name] = 1e3 * (time.perf_counter() - t0)
             wall[name + "/launches_or_iterations"] = c.transient_info()["cg_iterations"]
+    # the cantilever's figures, each on a context of its own: where the buffers of a pass lie then does not depend on the passes
+    # that ran before it
+    with open(os.path.join(ROOT, "profiles", "transient_tl.json")) as fh:
+        dt_tl = json.load(fh)["dt"]
+    prob = cantilever()
+    for name, run, count in (
+            ("newton_cantilever_1_increment", lambda c: c.run_newton(increments=1, load_factors=[0.125], cg=0),
+             lambda c: c.newton_info()["cg_iterations_total"]),
+            ("transient_tl_cantilever_8_steps", lambda c: c.run_transient_tl(TL_STEPS, dt_tl, density=RHO, lumped=True, newton_tol=1e-10, cg_tol=1e-10),
+             lambda c: c.transient_tl_info()["cg_iterations_total"])):
+        with Context(device=0) as c:
+            c.upload_problem(prob)
+            run(c)
+            t0 = time.perf_counter()
+            run(c)
+            wall[name] = 1e3 * (time.perf_counter() - t0)
+            wall[name + "/launches_or_iterations"] = count(c)
     print(json.dumps(wall))
 
 
