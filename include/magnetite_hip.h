@@ -752,7 +752,9 @@ int mag_internal_force(mag_ctx *ctx, const double *u, double *f_out, double scal
  *   i's incidence list, without floating-point atomics: the same bits for a repeat, every grid and every tile_nodes.
  *   An iteration.  The first one of an increment moves the supports by its linearisation (the support predictor):
  *     dU_P = lambda u_in - u on P;   K_T,FF du_F = (lambda f - f_int(u))_F - (K_T dU_P)_F;   u += s (du_F + dU_P);
- *   the later ones solve K_T,FF du_F = (lambda f - f_int(u))_F with du_P = 0.  Every iteration is one evaluation of f_int, one
+ *   the later ones solve K_T,FF du_F = (lambda f - f_int(u))_F with du_P = 0.  An iteration whose step the line search shortened
+ *   (s < 1) leaves the supports short of lambda u_in: the next one is a first iteration again, on the rest of the way, until one
+ *   with s = 1 has put them in place; an increment converges only then.  Every iteration is one evaluation of f_int, one
  *   tangent launch, the gather of the tangent into the solver's rows and one CG solve from zero under MAG_STOP_REL with cg_tol
  *   (0: 1e-10).  cg as mag_run_transient's: 0 block-Jacobi on the fused block-row kernel where the context has tile-local tables
  *   and the CSR operator's phase elsewhere, 1 | 2 | 3 the fused kernel plain | Jacobi | block-Jacobi, 4 the CSR operator's phase.

@@ -5441,9 +5441,9 @@ int mag_run_newton(mag_ctx *ctx, const mag_newton_options *o)
     for (int32_t k = 1; k <= incs; ++k) {
         const double lam = loads[(size_t)k];
         bool converged = false;
+        bool first = true; // the supports are not at lam u_in yet: until an iteration with s = 1 has moved them
         double ratio = 0.0;
         for (int32_t it = 1; it <= cap && !converged; ++it) {
-            const bool first = it == 1;
             if (int rc = timer.stamp(0)) return rc;
             magk::tl_tangent(mesh, pat, d_u, d_kt, &d_scal->inverted, s);
             magk::newton_rhs(pat, d_kt, d_known, d_fin, d_load, k, d_f, d_u, d_uin, first ? 1 : 0, d_rhs, d_dup, s);
@@ -5479,8 +5479,9 @@ int mag_run_newton(mag_ctx *ctx, const mag_newton_options *o)
             std::swap(d_u, d_ut);
             cur = trial;
             inverted = inverted || cur.inverted != 0;
+            first = first && sl != 1.0; // (a shortened step leaves them short: the next iteration predicts the rest)
             const NewtonStop stop = newton_stop(cur.r2, std::max(cur.f2, cur.p2), tol);
-            ratio = stop.ratio, converged = stop.converged;
+            ratio = stop.ratio, converged = stop.converged && !first;
             residuals.push_back(ratio);
             steps.push_back(sl);
             if (converged) newton_its[(size_t)k] = it;

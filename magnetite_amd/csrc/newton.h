@@ -13,7 +13,8 @@
 // The loop (api.hip, mag_run_newton).  Increment k under lambda = load[k]:  f_int(u)_F = lambda f_F,  u_P = lambda u_in.
 //   first iteration    dU_P = lambda u_in - u on P;   K_T,FF du_F = (lambda f - f_int(u))_F - (K_T dU_P)_F;   u += s (du_F + dU_P)
 //   later iterations   K_T,FF du_F = (lambda f - f_int(u))_F;   u += s du_F
-//   stop               |r_F| <= newton_tol ref,   ref = max(|lambda f_F|, |f_int(u)_P|),   judged after every update
+//                      (behind a step with s < 1 the supports are short of lambda u_in: a first iteration again, on the rest)
+//   stop               |r_F| <= newton_tol ref,   ref = max(|lambda f_F|, |f_int(u)_P|),   judged after every update (supports in place)
 //   line search        Pi = W - lambda f_F.u_F;   slope g = (f_int(u) - lambda f_F).du (= -r.du where du_P = 0)
 #pragma once
 #include <cstdint>

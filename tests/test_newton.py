@@ -2,7 +2,8 @@
 symmetry, a central difference of the internal force, a rigid motion, and the convergence of the Newton loop on the cases the GPU
 tests hold the device against.  Figures measured here: tangent(0) - K exactly 0; symmetry 0; the central difference 6e-12
 (plate16), 1.3e-10 (beam); the beam in 8 increments 4 iterations each, smallest det F 0.9575; load300 in 2 increments 4-5 and 4;
-pull5 in 1 increment 4 with the predictor, 6-12 when the supports jump first."""
+pull5 in 1 increment 4 with the predictor, 6-12 when the supports jump first.  At the end: the admission of newton_ref.PATHS, the
+cases of tests/test_newton_paths_gpu.py (every integer the device is asked for is off its threshold; figures beside the cases)."""
 import numpy as np
 import pytest
 
@@ -113,3 +114,71 @@ def test_the_predictor_saves_iterations():
 def test_the_cap_leaves_the_start():
     out = nr.case_run("beam", "beam", 1, max_newton=2)
     assert not out["converged"] and out["converged_increments"] == 0 and not out["u"].any() and len(out["residuals"]) == 2
+
+
+# ---- the admission of the cases of tests/test_newton_paths_gpu.py (newton_ref.PATHS): change the case, not the test
+@pytest.mark.parametrize("key", list(nr.PATHS))
+def test_admission_of_the_path_cases(key):
+    """Every converged increment's last ratio <= newton_tol / 10 and last-but-one >= 10 newton_tol; an increment at the cap stands
+    at >= 100 newton_tol; with a search, every trial has |min det F| >= 1e-3 and, where the energy test is live, is 1e-9 max(|Pi0|,
+    W) from its threshold; every tangent factored is positive definite (eigenvalue ratio > 1e-8).  Then the device's integers
+    are the twin's."""
+    out, opts = nr.path_run(key), nr.path_options(key)
+    its, res = out["newton_iterations"], out["residuals"]
+    end = np.cumsum(its[1:])
+    last = res[end - 1]
+    before = np.array([res[e - 2] if n > 1 else np.inf for n, e in zip(its[1:], end)])
+    past = res[its[1:].sum():]
+    print(f"{key}: newton {its.tolist()} last max {last.max():.2e} last-but-one min {before.min():.2e} past the converged {past} "
+          f"definite {out['definite']:.2e} inverted {out['inverted']} halvings {out['halvings']} steps {out['step_lengths'].tolist()}")
+    assert last.max() <= TOL / 10 and before.min() >= 10 * TOL
+    assert out["definite"] > 1e-8
+    if out["converged"]:
+        assert len(past) == 0
+    else:
+        assert len(past) == opts["max_newton"] and past[-1] >= 100 * TOL
+    if opts.get("line_search", 0) > 0:
+        tr = out["trials"]
+        dets = np.array([abs(t[3]) for t in tr])
+        # (from the unloaded start Pi0 = W = 0: every energy excess but 0 is infinitely far from the threshold on that scale)
+        live = np.array([abs(t[4]) / t[5] if t[5] > 0.0 else (np.inf if t[4] != 0.0 else 0.0)
+                         for t in tr if t[6] < 0.0 and abs(t[2] * t[6]) > 1e-13 * t[5]])
+        print(f"{key}: trials {len(tr)} smallest |min det F| {dets.min():.3e} live energy tests {len(live)} smallest margin {live.min():.2e}")
+        assert dets.min() >= 1e-3
+        assert live.min() >= 1e-9
+
+
+def test_the_path_cases_take_the_paths_they_are_named_for():
+    """what each case is there for, on the twin: the early end after two increments; accepted inverted states that end in a sound
+    one; halvings that only the inverted trial causes, and only the energy rule; a moving support under a search that never halves"""
+    early = nr.path_run("early")
+    assert not early["converged"] and early["converged_increments"] == 2 and early["newton_iterations"].tolist() == [0, 4, 4]
+    assert len(early["residuals"]) == 12 and early["load"].tolist() == [0.0, 0.125, 0.25]
+    through, p = nr.path_run("through"), nr.path_problem("through")
+    assert through["converged"] and through["inverted"] and through["halvings"] == 0
+    assert min(d for _, d in through["iterates"]) < -1.0 and through["iterates"][-1][1] > 0.1
+    assert nr.element_rows(*nr.of_problem(p), through["u"])[:, 6].min() > 0.1
+    for key, steps in (("inversion72", [0.25, 1, 1, 1, 1, 1, 1]), ("inversion320", [0.125, 1, 1, 1, 1, 1, 1, 1])):
+        out = nr.path_run(key)
+        assert out["converged"] and not out["inverted"] and out["step_lengths"].tolist() == steps
+        halved = [t for t in out["trials"] if t[1] == 1][:-1]  # (the trials of iteration 1 that were rejected)
+        assert len(halved) == out["halvings"] and halved[0][3] <= -1e-3  # (s = 1 is inverted; the energy rule rejects it as well)
+    for key, steps in (("energy1", [0.5, 1, 0.5] + [1] * 7), ("energy2", [0.25] + [1] * 9)):
+        out = nr.path_run(key)
+        assert out["converged"] and out["step_lengths"].tolist() == steps and out["halvings"] == 2
+        assert min(t[3] for t in out["trials"]) > 0.9  # (no trial is inverted: the energy rule alone)
+    pull = nr.path_run("pull")
+    assert pull["converged"] and pull["halvings"] == 0 and (pull["step_lengths"] == 1.0).all() and pull["min_det"] > 0.5
+    assert np.abs(nr.path_problem("pull").u_in).max() > 0  # (du_P != 0 in the slope of iteration 1)
+    # pull7: every rejected trial is inverted under a slope g >= 0, where the energy test is skipped -- the inverted trial alone
+    # decides; and the supports, moved by s < 1 three times, stand at u_in in the end
+    pull7, p7 = nr.path_run("pull7"), nr.path_problem("pull7")
+    known = np.asarray(p7.u_known).reshape(-1) != 0
+    assert pull7["converged"] and not pull7["inverted"] and pull7["halvings"] == 7
+    assert pull7["step_lengths"].tolist() == [0.25, 0.125, 0.25, 1, 1, 1, 1]
+    trials = pull7["trials"]
+    rejected = [t for t, after in zip(trials, trials[1:]) if after[1] == t[1]]
+    assert len(rejected) == 7 and all(t[3] <= -1e-3 and t[6] >= 0.0 for t in rejected)
+    gap = np.abs(pull7["u"][known] - np.asarray(p7.u_in)[known]).max() / np.abs(p7.u_in).max()
+    print("pull7: the supports against u_in", gap)
+    assert gap <= 4 * np.finfo(float).eps

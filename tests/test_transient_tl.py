@@ -1,7 +1,8 @@
 """The numpy twin of mag_run_transient_tl (tests/transient_tl_ref.py) against what is known without a device: the linear Newmark
 twin for a small load, the size of the nonlinearity, the order of the scheme, and the admission of the GPU tests' cases
 (tests/transient_tl_cases.py) -- the twin's own round-off floor against the GPU bars, every step's residual ratios away from the
-threshold that decides an iteration count."""
+threshold that decides an iteration count; and the same admission, with the step at the cap and the definiteness of every matrix
+factored, of the cases of tests/test_transient_tl_paths_gpu.py (EARLY, LONG, INVERTED, NEWMARK)."""
 import numpy as np
 import pytest
 
@@ -92,16 +93,67 @@ def test_admission_the_twin_is_at_its_floor(name, kind):
     assert max(err[k] for k in ("v", "a", "f", "energies")) <= 1e-8
 
 
+def off_the_threshold(what, got):
+    """the admission rule on the converged steps of a run; returns the ratios past them (those of a step that hit the cap)"""
+    its, res = got["newton_iterations"], got["residuals"]
+    assert its[0] == 0 and len(its) == got["steps_done"] + 1 and its[1:].sum() <= len(res)
+    end = np.cumsum(its[1:])
+    last = res[end - 1]
+    before = np.array([res[e - 2] if n > 1 else np.inf for n, e in zip(its[1:], end)])
+    print(f"{what}: newton {its.tolist()} last max {last.max():.2e} last-but-one min {before.min():.2e}")
+    assert last.max() <= TOL / 10
+    assert before.min() >= 10 * TOL
+    return res[its[1:].sum():]
+
+
 @pytest.mark.parametrize("name,kind", cases.CASES)
 def test_admission_every_step_is_off_the_threshold(name, kind):
     """every step's last residual ratio is at most newton_tol / 10 and its last-but-one at least 10 newton_tol: the device's
     iteration counts are the twin's.  A case that misses this gets another dt (transient_tl_cases.FACTOR), not another test."""
     got = cases.twin(name, kind)
-    its, res = got["newton_iterations"], got["residuals"]
-    assert got["converged"] and its[0] == 0 and its[1:].sum() == len(res)
-    end = np.cumsum(its[1:])
-    last = res[end - 1]
-    before = np.array([res[e - 2] if n > 1 else np.inf for n, e in zip(its[1:], end)])
-    print(f"{name} {kind}: newton {its.tolist()} last max {last.max():.2e} last-but-one min {before.min():.2e}")
-    assert last.max() <= TOL / 10
-    assert before.min() >= 10 * TOL
+    assert got["converged"]
+    assert len(off_the_threshold(f"{name} {kind}", got)) == 0
+
+
+# ---- the admission of the cases of tests/test_transient_tl_paths_gpu.py: the same rule, change the case and not the test
+def at_the_floor(what, got, floor):
+    rows = len(got["u"])
+    err = {k: max([cases.rel(got[k][n], floor[k][n]) for n in range(1, rows)], default=0.0) for k in ("u", "v", "a", "f", "energies")}
+    print(f"{what}: against the floor run " + " ".join(f"{k} {v:.1e}" for k, v in err.items()))
+    assert err["u"] <= 1e-9
+    assert max(err[k] for k in ("v", "a", "f", "energies")) <= 1e-8
+
+
+@pytest.mark.parametrize("which", ["EARLY", "LONG", "INVERTED"])
+def test_admission_of_the_early_ends(which):
+    """plate16 / load300 under the amplitude jump: the converged steps off the threshold, the step at the cap at least 100
+    newton_tol, every matrix factored positive definite (ratio > 1e-8), the twin at its floor.  Measured: EARLY 3 steps (5, 4, 4),
+    9.0e-6 at the cap; LONG all 8; INVERTED 3 steps, 0.21 at the cap, smallest det F -4.7; definite ratios >= 2.9e-4."""
+    kw = getattr(cases, which)
+    got = cases.twin_with("plate16", "load300", definite=True, **kw)
+    past = off_the_threshold(which, got)
+    print(f"{which}: steps done {got['steps_done']} the ratios of the step at the cap {past} smallest det F {got['min_det']:.3f} "
+          f"definite {got['definite']:.2e}")
+    assert got["definite"] > 1e-8
+    if which == "LONG":
+        assert got["converged"] and len(past) == 0 and not got["inverted"]
+        assert got["newton_iterations"].max() == kw["max_newton"]  # (so that one iteration fewer ends the run early)
+    else:
+        assert not got["converged"] and got["steps_done"] == cases.JUMP_AT - 1 and len(past) == kw["max_newton"]
+        assert past[-1] >= 100 * TOL
+        assert got["inverted"] == (which == "INVERTED") and abs(got["min_det"]) >= 1e-3
+    done = got["steps_done"]
+    at_the_floor(which, got, cases.twin_with("plate16", "load300", extra=3, steps=done, **{**kw, "max_newton": 0}))
+
+
+@pytest.mark.parametrize("name,kind,beta,gamma,lumped", cases.NEWMARK)
+def test_admission_of_the_newmark_parameters(name, kind, beta, gamma, lumped):
+    """other (beta, gamma): off the threshold, at the floor, positive definite, and more than 1e-4 from the (1/4, 1/2) run"""
+    kw = dict(beta=beta, gamma=gamma, lumped=lumped)
+    got = cases.twin_with(name, kind, definite=True, **kw)
+    assert got["converged"] and not got["inverted"]
+    assert len(off_the_threshold(f"{name} {kind} {kw}", got)) == 0
+    at_the_floor(f"{name} {kind} {kw}", got, cases.twin_with(name, kind, extra=3, **kw))
+    apart = cases.rel(got["u"][-1], cases.twin(name, kind, lumped=lumped)["u"][-1])
+    print(f"{name} {kind} {kw}: definite {got['definite']:.2e} rel(u, the (1/4, 1/2) run) {apart:.2e}")
+    assert got["definite"] > 1e-8 and apart > 1e-3

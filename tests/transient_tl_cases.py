@@ -19,6 +19,7 @@ import numpy as np
 
 import explicit_tl_cases as tlc
 import modal_ref
+import newton_ref
 import transient_ref
 import transient_tl_ref as ref
 
@@ -67,6 +68,48 @@ def twin(name, kind, extra=0, lumped=False, steps=None, dt=None, newton_tol=NEWT
     return ref.newmark_tl(*ref.of_problem(p), s["M"], s["free"], p.u_in, p.f_in, s["steps"] if steps is None else steps,
                           s["dt"] if dt is None else dt, alpha=s["alpha"], u0=s["u0"], newton_tol=newton_tol, max_newton=max_newton,
                           extra=extra)
+
+
+# ---- the cases of the paths the first suite only brushed (tests/test_transient_tl_paths_gpu.py), admitted like the ones above
+# in tests/test_transient_tl.py.  The figures: the converged steps' last max and last-but-one min; the ratio at the cap.
+# The jump was scanned like FACTOR.  A single level of 20 (the issue's starting point) is not admitted at the cap of 6: step 4 ends
+# at 3.2e-11 > newton_tol / 10, and under every level from 15 to 19.8 step 5's last-but-one is below 10 newton_tol.  Two levels are.
+JUMP_AT = 4
+EARLY = dict(jump_to=18.0, jump_then=24.0, max_newton=5)  # 3 steps (5, 4, 4), step 4 at 2.1e-6 at the cap; 2.4e-12, 3.4e-9
+LONG = dict(jump_to=18.0, jump_then=24.0, max_newton=6)   # all 8 steps ([0 5 4 4 6 5 4 4 4]); 2.4e-12, 2.9e-9
+INVERTED = dict(jump_to=100.0, max_newton=5)              # 3 steps, step 4 at 0.20 at the cap, a trial's smallest det F -4.6
+NEWMARK = [                                   # (name, kind, beta, gamma, lumped)
+    ("plate16", "pull5d", 0.3025, 0.6, False),   # 1.0e-12, 1.9e-7
+    ("plate16", "pull5d", 0.5, 1.0, False),      # 1.2e-13, 2.4e-8
+    ("plate16", "load300", 0.5, 1.0, False),     # 2.9e-12, 3.6e-9
+    ("plate16", "pull5d", 0.5, 1.0, True),       # 1.3e-13, 2.5e-8
+]
+
+
+def jump(to, then=None, steps=8):
+    """the amplitude of the early-end cases: 1, 1.01, 1.02, 1.03 (no two rows alike: a row taken for its neighbour shows), `to` at
+    row JUMP_AT, `then` (None: `to`) behind it"""
+    amp = 1.0 + 0.01 * np.arange(steps + 1)
+    amp[JUMP_AT] = to
+    amp[JUMP_AT + 1:] = to if then is None else then
+    return amp
+
+
+@functools.lru_cache(maxsize=None)
+def twin_with(name, kind, extra=0, lumped=False, steps=None, max_newton=0, beta=0.25, gamma=0.5, jump_to=None, jump_then=None, definite=False):
+    """the twin's run of a case under other Newmark parameters or the amplitude jump(jump_to, jump_then); definite=True: with
+    out["definite"], the smallest ratio of smallest to largest eigenvalue over the matrices the run factors"""
+    s = setup(name, kind, lumped)
+    p = s["prob"]
+    steps = s["steps"] if steps is None else steps
+    ratios = []
+    out = ref.newmark_tl(*ref.of_problem(p), s["M"], s["free"], p.u_in, p.f_in, steps, s["dt"], beta=beta, gamma=gamma, alpha=s["alpha"],
+                         amplitude=None if jump_to is None else jump(jump_to, jump_then)[:steps + 1], u0=s["u0"], newton_tol=NEWTON_TOL,
+                         max_newton=max_newton, extra=extra,
+                         on_factor=(lambda A: ratios.append(newton_ref.definiteness(A))) if definite else None)
+    if definite:
+        out["definite"] = min(ratios)
+    return out
 
 
 @functools.lru_cache(maxsize=None)

@@ -21,9 +21,11 @@ import newton_ref
 
 
 def newmark_tl(xy, conn, E, nu, t, M, free, u_in, f_in, steps, dt, beta=0.25, gamma=0.5, alpha=0.0, amplitude=None, u0=None, v0=None,
-               newton_tol=0.0, max_newton=0, extra=0, start="u"):
+               newton_tol=0.0, max_newton=0, extra=0, start="u", on_factor=None):
     """dict(u, v, a, f (rows, 2N each), energies (rows, 3 = T, W, P), newton_iterations (rows), residuals (one ratio per Newton
-    iteration of the run), steps_done, converged, min_det); rows = steps_done + 1.  extra = k runs every step k iterations past
+    iteration of the run), steps_done, converged, min_det, inverted); rows = steps_done + 1.  inverted: some trial state of the
+    run, of a step that did not converge included, had det F <= 0 (mag_get_transient_tl_info's [6]).  on_factor(A_FF) is called
+    with every matrix the run factors (M_FF for a_0, then every A_T,FF).  extra = k runs every step k iterations past
     convergence (the round-off floor; newton_iterations and residuals count and hold them).  start: the first iterate of a step --
     "u" (u' = u_n: the pass's), "a" (a' = a_n) or "0" (a' = 0), the two the header warns of."""
     if beta <= 0.0:
@@ -51,7 +53,11 @@ def newmark_tl(xy, conn, E, nu, t, M, free, u_in, f_in, steps, dt, beta=0.25, ga
     def solve_free(A, rhs):
         x = np.zeros(n)
         r = rhs[free]
-        x[free] = spla.splu(A[free][:, free].tocsc()).solve(r) if np.any(r != 0.0) else 0.0
+        if np.any(r != 0.0):
+            Aff = A[free][:, free].tocsc()
+            if on_factor is not None:
+                on_factor(Aff)
+            x[free] = spla.splu(Aff).solve(r)
         return x
 
     def record(row, fi, W):
@@ -97,7 +103,7 @@ def newmark_tl(xy, conn, E, nu, t, M, free, u_in, f_in, steps, dt, beta=0.25, ga
         done += 1
     for k in ("u", "v", "a", "f", "energies", "residuals", "newton_iterations"):
         out[k] = np.array(out[k])
-    out.update(steps_done=done, converged=done == steps)
+    out.update(steps_done=done, converged=done == steps, inverted=bool(out["min_det"] <= 0.0))
     return out
 
 
