@@ -125,13 +125,20 @@ __device__ inline double dpp_move_f64(double v)
 // The two s_sleep of the exchange's first wait.  6 + 4 until the exchange issued its halo loads in front of them (rounds 2-4:
 // profiles/r03_persist_ab.txt); re-swept with that placement over 0+0 ... 16+12: 8 + 6 (DESIGN XB, profiles/exchange_batched.json).
 constexpr int kPersistSleep1 = 8, kPersistSleep2 = 6;
+// ... and of the exchange that reduces on the lane's own piece (XR): its reduction is 0.24 us shorter, the records of the other
+// workgroups are as far away as before -- re-swept over 4+2 ... 12+10 (DESIGN XR, profiles/exchange_reduction.json): 6 + 4.
+constexpr int kPersistSleepXr1 = 6, kPersistSleepXr2 = 4;
 constexpr int kPersistSleepMg = 20; // the multi-GPU exchange's first wait: two s_sleep of this length
 
 // Wait for epoch `epoch`: every workgroup's partial record (two 16-byte pieces each, one per thread) and the q of this
-// thread's halo nodes, swept together until every tag matches; then the records are summed in one fixed two-level
-// order (chunks of eight workgroups, then the chunks) so that all workgroups hold the same bits.  grid <= 256.
+// thread's halo nodes, swept together until every tag matches; then the records are summed in one fixed order (512 threads:
+// the tree of persist_block_sum over the 2 x 256 pieces, every wave finishing it for itself; any other shape: four records
+// per lane in order, then a wave tree per sum) so that all workgroups hold the same bits.  grid <= 256.
 // Returns false when the spin budget runs out (some workgroup is not running): the timeout word is set for the host.
-template <int NH, bool OPQ = false>
+// Barriers of the 512-thread path: the waves' flags (with s_rec complete), then the rows' partials -- two; with XR one.
+// XR (persist_own_piece_reduction, DESIGN XR): the validated piece stays in the lane's registers and the reduction meets at ONE
+// barrier -- see the comment at the sweep's end.
+template <int NH, bool OPQ = false, bool XR = false>
 __device__ inline bool persist_exchange(const PersistParams &P, int par, unsigned epoch, const int32_t (&hg)[NH],
                                         double2 (&hq)[NH], double *s_S, double2 *s_rec, double *s_chunk, double *s_part,
                                         double (&Sx)[4], unsigned long long *stamp = nullptr)
@@ -202,8 +209,8 @@ __device__ inline bool persist_exchange(const PersistParams &P, int par, unsigne
     issue_halo();
     // ~0.95 us in all: the other workgroups' records are still on their way, and a sweep that comes too early costs a full
     // round trip.  x += alpha p runs in this wait (the loop of k_cg_persist) and takes about half of it.
-    __builtin_amdgcn_s_sleep(kPersistSleep1);
-    __builtin_amdgcn_s_sleep(kPersistSleep2);
+    __builtin_amdgcn_s_sleep(XR ? kPersistSleepXr1 : kPersistSleep1);
+    __builtin_amdgcn_s_sleep(XR ? kPersistSleepXr2 : kPersistSleep2);
 #ifdef MAG_PERSIST_STAMPS
     if (stamp) stamp[0] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -212,6 +219,7 @@ __device__ inline bool persist_exchange(const PersistParams &P, int par, unsigne
     // one only after all of them.
     bool wave_ok = false;
     unsigned spins = 0;
+    [[maybe_unused]] double2 pc = make_double2(0.0, 0.0); // XR: this lane's piece of the records (lanes >= 2 grid have none: 0)
     for (; spins < P.spin_limit; ++spins) {
         u32x4 ra = zero4, rb = zero4;
         if (live_rec) {
@@ -220,7 +228,13 @@ __device__ inline bool persist_exchange(const PersistParams &P, int par, unsigne
         }
         __builtin_amdgcn_sched_barrier(0); // the pass's loads are all in flight: counted waits from here
         const bool got_rec = orec < rec_bytes && tags_ok(ra, rb);
-        if (got_rec) s_rec[tid] = value_of(ra, rb);
+        if constexpr (XR) { // taken by selects, as hq[] below: no LDS store in the polling loop
+            const double2 v = value_of(ra, rb);
+            pc.x = got_rec ? v.x : pc.x;
+            pc.y = got_rec ? v.y : pc.y;
+        } else {
+            if (got_rec) s_rec[tid] = value_of(ra, rb);
+        }
         orec = got_rec ? rec_bytes : orec;
         bool ok = orec >= rec_bytes;
 #pragma unroll
@@ -247,6 +261,50 @@ __device__ inline bool persist_exchange(const PersistParams &P, int par, unsigne
 #ifdef MAG_PERSIST_STAMPS
     if (stamp) stamp[4] = __builtin_amdgcn_s_memrealtime(); // this wave has its pieces
 #endif
+    // XR (512 threads): lane `tid` validated piece `tid` -- exactly the piece the tree below would read back for it from
+    // s_rec[2 m + (l & 1)], m = 32 (tid >> 6) + (l >> 1).  So the piece never goes through LDS: a wave whose own sweep has ended
+    // runs the first half of the tree (level 2 and the two row shifts) on its lanes' registers at once -- while the slower waves
+    // still poll -- and leaves its rows' partials and its flag in LDS.  ONE barrier; behind it every wave reads the eight flags
+    // and its row of partials together and finishes the tree.  Same operands, same order of additions as the path below: the
+    // same bits.  The partials go to the record staging area (s_rec, which this path does not use otherwise), NOT to s_part:
+    // wave 0 may still be reading persist_block_sum's partials there when a wave without record pieces ends its sweep, and no
+    // barrier lies in between any more.  A wave that gave up leaves partials nobody reads: the give-up path returns first.
+    if constexpr (XR) {
+        const int l = tid & 63;
+        const bool two = (l & 2) != 0;
+        const double k2 = two ? pc.y : pc.x, s2 = two ? pc.x : pc.y;
+        double v = k2 + dpp_move_f64<0x4E>(s2);
+        v += dpp_move_f64<0x114>(v);
+        v += dpp_move_f64<0x118>(v);
+        double *s_xp = (double *)s_rec;               // [sum][wave * 4 + row], as s_part
+        uint32_t *s_flag = (uint32_t *)(s_chunk + 4); // (words 4 .. 7 of s_chunk, as below)
+        if ((l & 15) >= 12) s_xp[(((l & 1) << 1) | ((l >> 1) & 1)) * 32 + (tid >> 6) * 4 + (l >> 4)] = v;
+        if (l == 0) s_flag[tid >> 6] = wave_ok ? 1u : 0u;
+        __syncthreads();
+        const uint4 f0 = ((const uint4 *)s_flag)[0], f1 = ((const uint4 *)s_flag)[1];
+        const double2 pr = ((const double2 *)(s_xp + (l >> 4) * 32))[l & 15];
+        done = (f0.x & f0.y & f0.z & f0.w & f1.x & f1.y & f1.z & f1.w) != 0u;
+#ifdef MAG_PERSIST_STAMPS
+        if (stamp) {
+            stamp[3] = stamp[1] = __builtin_amdgcn_s_memrealtime(); // every wave of the workgroup has its pieces
+            stamp[2] = spins + 1;
+        }
+#endif
+        if (!done) {
+            if (tid == 0) __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return false;
+        }
+        double t = pr.x + pr.y;
+        t += dpp_move_f64<0x111>(t);
+        t += dpp_move_f64<0x112>(t);
+        t += dpp_move_f64<0x114>(t);
+        t += dpp_move_f64<0x118>(t);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            Sx[c] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(t), 16 * c + 15),
+                                     __builtin_amdgcn_readlane(__double2loint(t), 16 * c + 15));
+        return true;
+    }
     // every wave has everything?  One flag word per wave, ONE barrier (also: s_rec complete), one 32-byte read: the
     // library's __syncthreads_and is three barriers around an LDS atomic.
     {
@@ -711,8 +769,12 @@ __device__ inline void persist_comm_loop(const PersistParams &P, double *s_S, do
 // adds them with one 16-byte read and a four-step tree per row -- 7 + 5 additions on the critical path where there were
 // 24 + 7, a fixed order of additions as before (so every run gives the same bits; they are not round 3's bits).
 constexpr int kPersistPartDoubles = 128; // s_part: four sums x (8 waves x 4 rows)
-template <bool OPQ = false>
-__device__ inline void persist_block_sum(double (&acc)[4], double *s_part, [[maybe_unused]] unsigned long long *sub = nullptr)
+// DIRECT (persist_own_piece_reduction): `rec` is the workgroup's record of the coming epoch.  Lanes 15 / 31 / 47 / 63 of wave 0 hold
+// the totals of sums 0 .. 3 when the row tree ends: each stores its sum's two granules itself, one 16-byte store into the layout
+// put_granules writes, and the four readlane pairs with the two-lane store behind them are gone.  acc is then not written.
+template <bool OPQ = false, bool DIRECT = false>
+__device__ inline void persist_block_sum(double (&acc)[4], double *s_part, [[maybe_unused]] unsigned long long *sub = nullptr,
+                                         [[maybe_unused]] unsigned long long *rec = nullptr, [[maybe_unused]] unsigned epoch = 0u)
 {
     // (tx: the thread index behind an empty asm -- the LDS addresses below are then recomputed in every iteration, three
     // instructions each.  Taken from threadIdx.x directly they are loop-invariant: the compiler hoisted them out of the CG
@@ -746,10 +808,17 @@ __device__ inline void persist_block_sum(double (&acc)[4], double *s_part, [[may
         t += dpp_move_f64<0x112>(t);
         t += dpp_move_f64<0x114>(t);
         t += dpp_move_f64<0x118>(t);
+        if constexpr (DIRECT) {
+            if ((l & 15) == 15) {
+                const u32x4 g = {(unsigned)__double2loint(t), epoch, (unsigned)__double2hiint(t), epoch};
+                asm volatile("global_store_dwordx4 %0, %1, off sc1" MAG_WS_DATA : : "v"(rec + 2 * (l >> 4)), "v"(g) : "memory");
+            }
+        } else {
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
-            acc[c] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(t), 16 * c + 15),
-                                      __builtin_amdgcn_readlane(__double2loint(t), 16 * c + 15));
+            for (int c = 0; c < 4; ++c)
+                acc[c] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(t), 16 * c + 15),
+                                          __builtin_amdgcn_readlane(__double2loint(t), 16 * c + 15));
+        }
     }
 }
 
@@ -865,6 +934,14 @@ constexpr bool persist_update_loads(int B, bool MG, int EBM, bool ONE, int NPT)
     return EBM == 1 && !MG && !ONE && NPT == 4 && B == 512;
 }
 
+// The exchange's reduction on the lane's own record piece, one workgroup barrier (DESIGN XR; persist_exchange<.., XR>).  On for
+// the four-slot structured kernel of the 512-node tiles on a single-GPU grid -- the single-case launch: load cases and variants
+// (LC) keep the exchange they have, instruction for instruction, like every other instantiation.
+constexpr bool persist_own_piece_reduction(int B, bool MG, int EBM, bool ONE, int NPT, bool LC)
+{
+    return persist_update_loads(B, MG, EBM, ONE, NPT) && !LC;
+}
+
 // EBM: 0 the triangle walk, 1 edge blocks in registers (every row of the mesh a fan of at most six blocks: structured meshes),
 // 2 edge blocks with OVERFLOW (round 4: rows that are one fan of any length -- what gmsh's frontal meshes look like, a quarter
 // of their nodes with seven neighbours: blocks beyond the six in registers sit in an LDS pool of 32-byte records).
@@ -927,6 +1004,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
         return;
     }
     constexpr bool UL = persist_update_loads(B, MG, EBM, ONE, NPT); // the update's LDS loads in flight under the scalars
+    constexpr bool XR = persist_own_piece_reduction(B, MG, EBM, ONE, NPT, LC); // the exchange's reduction on the lane's own piece
     static_assert(!UL || EB, "the update loads in front: q lives in LDS");
     constexpr int NH = kPersistNh; // halo entries per thread: the workgroup's halo nodes are dealt out over ALL threads
     const unsigned tag0 = (MG ? P.tag_base : 0u) + 1u; // tag of epoch e: tag0 + e - 1
@@ -1176,7 +1254,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
     if (single_wg)
         persist_single_workgroup<NH>(s_S, Sx, hq);
     else if (MG ? !persist_exchange_mg<NH>(P, par, epoch, hg, hq, s_S, s_rec)
-                : !persist_exchange<NH, OPQ>(P, par, epoch, hg, hq, s_S, s_rec, s_chunk, s_part, Sx))
+                : !persist_exchange<NH, OPQ, XR>(P, par, epoch, hg, hq, s_S, s_rec, s_chunk, s_part, Sx))
         return;
 
     const double c0 = P.c0, nu = P.nu, h = P.h;
@@ -1468,14 +1546,14 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
         MAG_STAMP(2) // ring walks of this wave's nodes, q published
 #ifdef MAG_PERSIST_STAMPS
         unsigned long long *sub_ = stamp_sum + kStampPhases + 8;
-        persist_block_sum<OPQ>(acc, s_part, stamping ? sub_ : nullptr);
+        persist_block_sum<OPQ, XR>(acc, s_part, stamping ? sub_ : nullptr, P.recg + 8 * ((int64_t)(par ^ 1) * cgrid + blockIdx.x), epoch + 1);
 #else
-        persist_block_sum<OPQ>(acc, s_part);
+        persist_block_sum<OPQ, XR>(acc, s_part, nullptr, P.recg + 8 * ((int64_t)(par ^ 1) * cgrid + blockIdx.x), epoch + 1);
 #endif
         par ^= 1;
         ++epoch;
         ++j;
-        if (tid < 2)
+        if (!XR && tid < 2)
             put_granules(P.recg + 4 * (2 * ((int64_t)par * cgrid + blockIdx.x) + tid), epoch,
                          tid == 0 ? make_double2(acc[0], acc[1]) : make_double2(acc[2], acc[3]));
         if (single_wg && tid < 2) ((double2 *)s_S)[tid] = tid == 0 ? make_double2(acc[0], acc[1]) : make_double2(acc[2], acc[3]);
@@ -1518,7 +1596,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
         if (single_wg)
             persist_single_workgroup<NH>(s_S, Sx, hq);
         else if (MG ? !persist_exchange_mg<NH>(P, par, epoch, hg, hq, s_S, s_rec, stamping ? xs_ : nullptr)
-                    : !persist_exchange<NH, OPQ>(P, par, epoch, hg, hq, s_S, s_rec, s_chunk, s_part, Sx, stamping ? xs_ : nullptr))
+                    : !persist_exchange<NH, OPQ, XR>(P, par, epoch, hg, hq, s_S, s_rec, s_chunk, s_part, Sx, stamping ? xs_ : nullptr))
             return;
         if (stamping) { // inside the exchange: wait before the first sweep / sweeps until complete / record reduction
             stamp_sum[4] += xs_[0] - stamp_last;
@@ -1533,7 +1611,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
         if (single_wg)
             persist_single_workgroup<NH>(s_S, Sx, hq);
         else if (MG ? !persist_exchange_mg<NH>(P, par, epoch, hg, hq, s_S, s_rec)
-                    : !persist_exchange<NH, OPQ>(P, par, epoch, hg, hq, s_S, s_rec, s_chunk, s_part, Sx))
+                    : !persist_exchange<NH, OPQ, XR>(P, par, epoch, hg, hq, s_S, s_rec, s_chunk, s_part, Sx))
             return;
 #endif
     }

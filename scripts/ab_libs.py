@@ -44,8 +44,9 @@ for _ in range(a.rounds):
         r = subprocess.run([sys.executable, "-c", WORKER, a.workload, str(a.variant)], env=env, capture_output=True,
                            text=True, timeout=900)
         if r.returncode != 0:
-            print(lib, "FAILED", r.stderr[-500:], flush=True)
-            continue
+            # nothing more is started on a GPU that a process has just left by a fault, an abort or a time limit
+            print(lib, "FAILED", r.returncode, r.stderr[-500:], flush=True)
+            sys.exit(1)
         res[lib].append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
 for lib, rs in res.items():
     if rs:
