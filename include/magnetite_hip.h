@@ -592,6 +592,76 @@ int mag_get_modal_info(const mag_ctx *ctx, int32_t info[8]);
 /* statistics of inner solve j of the LAST outer step, as mag_get_case_stats */
 int mag_get_modal_stats(const mag_ctx *ctx, int32_t j, mag_stats *stats);
 
+/* ---- linearised buckling: the critical load factors and buckling shapes of a solved member ------------------------
+ * mag_run_buckling: the `modes` pairs of smallest |lambda| of  (K_FF + lambda K_G,FF) phi_F = 0,  phi_P = 0,  on the device.
+ *   Prestress.  u0 is the solution of a solved member: the last mag_run (set = MAG_SET_RUN, member 0) or case `member` of the
+ *     last mag_run_cases (set = MAG_SET_CASES).  sigma_e = D B u0_e (plane stress, the uploaded material: mag_run_stress's
+ *     tensor) and, with g_k the shape function gradients of the element,
+ *       K_G,e[k, l] = t A_e (g_k^T sigma_e g_l) I_2.
+ *   The classical linearised problem.  K is the stiffness at the reference configuration (mag_run_modal's); the
+ *     initial-displacement terms of dK_T / dlambda are dropped.  lambda multiplies EVERYTHING prescribed in that member, forces
+ *     and non-zero support displacements alike (u0 is linear in them).  Prescribed DOFs are supports, as in mag_run_modal.
+ *   Orientation.  As mag_run_modal: an element of signed area <= 0 is refused with MAG_ERR_BAD_ARGS, the element named.
+ *   Both signs are results.  A negative lambda is buckling under the reversed load; a pulled part has only such factors among its
+ *     smallest.  load_factor[k], signed, is ordered by |lambda| ascending.  info[7] counts the positive ones among those returned.
+ *   Results, for modes = p:  load_factor[k];  shape[k] (2N, caller numbering, 0 on P) normalised so that phi_k^T K phi_l =
+ *     delta_kl (K_G is indefinite and cannot normalise), its entry of largest magnitude positive (on a tie the first in caller
+ *     order);  residual[k] = |K_FF phi + lambda K_G,FF phi| / |lambda K_G,FF phi| from the pass's own quantities.
+ * Algorithm: mag_run_modal's subspace iteration (one driver runs both) with -K_G in the place of M, so that it converges to the
+ *   largest |mu|, mu = 1 / lambda;  q = subspace or min(2p, p + 8) when 0;  p >= 1, p <= q <= 32, q <= n_free.
+ *   1. The same hashed start vectors X.  u0 is copied to a buffer of the pass.  Y = -K_G X, prescribed rows zero.
+ *   2. Each outer step: K_FF Z_j = Y_j as ONE member set, as there;  W = -K_G Z;  A = Z^T Y (= Z^T K Z) and B = Z^T W,
+ *      symmetrised;  on the host the pairs of B q = mu A q through the Cholesky factor of A scaled to a unit diagonal and cyclic
+ *      Jacobi, ordered by |mu| descending, Q^T A Q = I (B is indefinite: nothing is factored but A);  lambda = 1 / mu;
+ *      X = Z Q, Y = W Q;  residual[k] from Y_old Q e_k - lambda_k Y_new e_k.
+ *   3. Stop when the largest relative change of the first p factors is <= tol, or after max_outer steps: reaching the cap is no
+ *      error (converged = 0, the last iterate is returned).
+ *   4. The shapes are K-normalised once more, by G = X^T (K_FF X) from one matrix-free product per shape: Z^T Y stands for
+ *      Z^T K Z only as far as the inner solves reach K Z = Y.
+ *   The inner solves run under MAG_STOP_REL with cg_tol, as mag_run_modal's.
+ * mag_run_buckling alters no other result of the context: the run's and the cases' results, statistics and history, every
+ *   derived pass and the modal results stay bit for bit.  A repeat gives the same bits.  The results stay until the next
+ *   mag_upload or the next mag_run_buckling.
+ * Errors, before the iteration: MAG_ERR_BAD_ARGS for a null pointer, modes < 1, subspace not 0 and outside [modes, 32] (or the
+ *   default above 32) or above n_free, max_outer < 0, a tol or cg_tol that is negative or not finite, a set other than
+ *   MAG_SET_RUN / MAG_SET_CASES, a member out of range, a communicator of more than one rank, a clockwise element;
+ *   MAG_ERR_STATE for no upload, for a set that is not solved, for a context with an element stiffness field, for a download or
+ *   query before a completed mag_run_buckling -- and for a prestress that VANISHES (a start column with -K_G x = 0, or an A_jj
+ *   that is not positive at the first step): the chosen member carries no stress, there is nothing to buckle.
+ * Errors of the iteration, all MAG_ERR_NOT_CONVERGED and named: an inner solve that breaks down or stops at its cap; a
+ *   dependent subspace (column and figure named: a K_G of rank below `subspace` causes it, a smaller subspace helps); among the
+ *   first p, a |mu_k| <= 1e-13 |mu_1|: fewer than p buckling modes exist.
+ * Out of scope: a dead-load / live-load split; a shift (factors far from zero); variants as the prestress; fields; ranks; the
+ *   prestress of a nonlinear state (K_T(u) of mag_run_newton as the first matrix); out-of-plane buckling (the model is a
+ *   membrane). */
+typedef struct mag_buckling_options {
+    int32_t modes;      /* p >= 1 */
+    int32_t subspace;   /* q, 0: min(2p, p + 8); p <= q <= 32 */
+    int32_t max_outer;  /* 0: 50 */
+    int32_t set;        /* MAG_SET_RUN or MAG_SET_CASES: whose solution is the prestress */
+    int32_t member;     /* the case of MAG_SET_CASES; 0 for MAG_SET_RUN */
+    int32_t reserved;
+    double tol;         /* relative change of the first p factors; 0: 1e-10 */
+    double cg_tol;      /* MAG_STOP_REL tolerance of the inner solves; 0: 1e-10 */
+} mag_buckling_options; /* 40 bytes */
+typedef struct mag_buckling_result {
+    double *load_factor_out; /* p, NULL: skipped */
+    double *residual_out;    /* p */
+    double *shapes_out;      /* [p][2N] */
+    int32_t memory, reserved;
+} mag_buckling_result;       /* 32 bytes */
+int mag_run_buckling(mag_ctx *ctx, const mag_buckling_options *opt);
+int mag_download_buckling(mag_ctx *ctx, mag_buckling_result *out);
+/* info[0] modes, [1] subspace, [2] outer steps, [3] converged, [4] vectors per on-chip launch (0: one after another),
+ * [5] on-chip launches of all steps, [6] vectors redone alone, [7] positive factors among the modes returned */
+int mag_get_buckling_info(const mag_ctx *ctx, int32_t info[8]);
+/* statistics of inner solve j of the LAST outer step, as mag_get_case_stats */
+int mag_get_buckling_stats(const mag_ctx *ctx, int32_t j, mag_stats *stats);
+/* values_out = K_G(sigma(u0)) of the solved member (set, member as above) in the layout of mag_assemble_csr's val (its rowptr /
+ * col apply; the off-diagonal entries of every 2 x 2 block are zero); memory: MAG_MEM_DEVICE for a device-resident values_out.
+ * Every block is summed in the order of its row node's incidence list.  Alters no result of the context. */
+int mag_assemble_geometric(mag_ctx *ctx, int32_t set, int32_t member, double *values_out, int32_t memory);
+
 /* ---- transient dynamics: Newmark time stepping of the uploaded part, on the device ------------------------------
  * mag_run_transient: Newmark's method in acceleration form on the uploaded mesh and material, with density rho.
  *   Mass.  M is the consistent mass, or the lumped one (lumped != 0), as in mag_run_modal.  Damping: C = alpha M + eta K
@@ -1078,6 +1148,10 @@ int mag_apply_operator(mag_ctx *ctx, const double *x, double *y, int32_t masked)
  * DOF numbering); masked != 0 applies P M P with P zeroing prescribed-displacement DOFs, as mag_apply_operator does (M_FF
  * embedded in full length).  Alters no result of the context. */
 int mag_apply_mass(mag_ctx *ctx, double density, int32_t lumped, const double *x, double *y, int32_t masked);
+/* y = K_G(sigma(u0)) x with the geometric stiffness operator of mag_run_buckling, u0 the solution of the solved member (set,
+ * member as in mag_buckling_options) (x, y: host, 2N, caller's DOF numbering); masked != 0 applies P K_G P, as mag_apply_mass
+ * does.  Reads no matrix.  Alters no result of the context. */
+int mag_apply_geometric(mag_ctx *ctx, int32_t set, int32_t member, const double *x, double *y, int32_t masked);
 /* Bench helper: `reps` back-to-back launches of the CG iteration kernel (cg_variant 1: the fused
  * iteration kernel; 0: the operator kernel of the two-launch iteration) on the context's stream
  * between two HIP events; *ms_per_launch = elapsed / reps.  Needs an uploaded problem, not a solve: straight after

@@ -159,6 +159,21 @@ struct ModalSpec {
     double density = 0.0, tol = 0.0, cg_tol = 0.0;
 };
 
+// The options of solver::buckling (include/magnetite_hip.h, mag_buckling_options); 0: the library's default.
+struct BucklingSpec {
+    std::int32_t modes = 4, subspace = 0, max_outer = 0;
+    double tol = 0.0, cg_tol = 0.0;
+};
+
+// What solver::buckling returns: the outputs of mag_download_buckling -- load_factor (signed, by magnitude ascending), residual,
+// shapes (modes rows of 2N values in the order of `nodes`, K-normalised, 0 on prescribed DOFs) --, mag_get_buckling_info's words by
+// name and critical: the smallest positive factor, if there is one.
+struct BucklingModes {
+    std::vector<double> load_factor, residual, shapes;
+    std::int32_t modes = 0, subspace = 0, outer = 0, converged = 0, vectors_per_launch = 0, launches = 0, redone = 0, positive = 0;
+    std::optional<double> critical;
+};
+
 // The options of solver::transient (include/magnetite_hip.h, mag_transient_options); 0: the library's default.  amplitude: steps + 1
 // values or empty (ones); u0, v0: 2N values in the order of `nodes` or empty (zero); probes: DOF indices 2 * node + axis.
 struct TransientSpec {
@@ -791,6 +806,105 @@ inline Result modal(const std::vector<Node> &nodes, const std::vector<Element> &
     out.vectors_per_launch = info[4];
     out.launches = info[5];
     out.redone = info[6];
+    mag_destroy(ctx);
+    return std::nullopt;
+}
+
+namespace detail {
+
+// the part uploaded and solved once (mag_run): the prestress of the buckling entry points.  The context is the caller's on success
+inline Result solved_part(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                          const mag_options *options, mag_ctx *&ctx)
+{
+    const std::size_t N = nodes.size();
+    std::vector<double> xy, u_in(2 * N), f_in(2 * N);
+    std::vector<std::uint8_t> u_known;
+    std::vector<std::int32_t> conn;
+    if (Result e = flatten_nodes(nodes, xy, u_known, u_in.data(), f_in.data())) return e;
+    if (Result e = flatten_elements(elements, N, conn)) return e;
+    ctx = mag_create(options);
+    if (!ctx) return solver_error("mag_create failed");
+    const mag_problem p = host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
+    if (mag_upload(ctx, &p) != MAG_OK || mag_run(ctx) != MAG_OK) return fail_and_destroy(ctx);
+    return std::nullopt;
+}
+
+} // namespace detail
+
+// Linearised buckling (mag_run_buckling) of the part under its own loads: the part is solved, then the spec.modes load factors of
+// smallest magnitude of (K_FF + lambda K_G,FF) phi = 0 with their shapes.  The DOFs of `nodes` with a displacement are supports;
+// lambda multiplies every force and every non-zero support displacement.  Reaching the cap of outer steps is no error:
+// out.converged == 0.
+inline Result buckling(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                       const BucklingSpec &spec, BucklingModes &out, const mag_options *options = nullptr)
+{
+    const std::size_t N = nodes.size();
+    mag_ctx *ctx = nullptr;
+    if (Result e = detail::solved_part(nodes, elements, model_metadata, options, ctx)) return e;
+    mag_buckling_options o{};
+    o.modes = spec.modes;
+    o.subspace = spec.subspace;
+    o.max_outer = spec.max_outer;
+    o.set = MAG_SET_RUN;
+    o.tol = spec.tol;
+    o.cg_tol = spec.cg_tol;
+    if (mag_run_buckling(ctx, &o) != MAG_OK) return detail::fail_and_destroy(ctx);
+    std::int32_t info[8] = {};
+    if (mag_get_buckling_info(ctx, info) != MAG_OK) return detail::fail_and_destroy(ctx);
+    const std::size_t P = (std::size_t)info[0];
+    out = BucklingModes{};
+    out.load_factor.resize(P);
+    out.residual.resize(P);
+    out.shapes.resize(P * 2 * N);
+    mag_buckling_result d{};
+    d.load_factor_out = out.load_factor.data();
+    d.residual_out = out.residual.data();
+    d.shapes_out = out.shapes.data();
+    d.memory = MAG_MEM_HOST;
+    if (mag_download_buckling(ctx, &d) != MAG_OK) return detail::fail_and_destroy(ctx);
+    out.modes = info[0];
+    out.subspace = info[1];
+    out.outer = info[2];
+    out.converged = info[3];
+    out.vectors_per_launch = info[4];
+    out.launches = info[5];
+    out.redone = info[6];
+    out.positive = info[7];
+    for (double l : out.load_factor)
+        if (l > 0.0 && (!out.critical || l < *out.critical)) out.critical = l;
+    mag_destroy(ctx);
+    return std::nullopt;
+}
+
+// y = K_G(sigma(u0)) x (2N values each, in the order of `nodes`) with the geometric stiffness of the solved part's stress
+// (mag_apply_geometric); masked: prescribed DOFs zeroed on both sides.
+inline Result apply_geometric(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                              const std::vector<double> &x, std::vector<double> &y, bool masked = false, const mag_options *options = nullptr)
+{
+    if (x.size() != 2 * nodes.size()) return detail::solver_error("x has another length than 2 N");
+    mag_ctx *ctx = nullptr;
+    if (Result e = detail::solved_part(nodes, elements, model_metadata, options, ctx)) return e;
+    y.resize(x.size());
+    if (mag_apply_geometric(ctx, MAG_SET_RUN, 0, x.data(), y.data(), masked ? 1 : 0) != MAG_OK) return detail::fail_and_destroy(ctx);
+    mag_destroy(ctx);
+    return std::nullopt;
+}
+
+// The geometric stiffness K_G(sigma(u0)) of the solved part's stress as a CSR matrix with mag_assemble_csr's pattern
+// (mag_assemble_geometric).
+inline Result assemble_geometric(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
+                                 std::vector<std::int32_t> &rowptr, std::vector<std::int32_t> &col, std::vector<double> &val,
+                                 const mag_options *options = nullptr)
+{
+    mag_ctx *ctx = nullptr;
+    if (Result e = detail::solved_part(nodes, elements, model_metadata, options, ctx)) return e;
+    std::int64_t nnz = 0;
+    if (mag_assemble_csr(ctx, &nnz, nullptr, nullptr, nullptr) != MAG_OK) return detail::fail_and_destroy(ctx);
+    rowptr.resize(2 * nodes.size() + 1);
+    col.resize((std::size_t)nnz);
+    val.resize((std::size_t)nnz);
+    if (mag_assemble_csr(ctx, &nnz, rowptr.data(), col.data(), nullptr) != MAG_OK) return detail::fail_and_destroy(ctx);
+    if (mag_assemble_geometric(ctx, MAG_SET_RUN, 0, val.data(), MAG_MEM_HOST) != MAG_OK) return detail::fail_and_destroy(ctx);
     mag_destroy(ctx);
     return std::nullopt;
 }

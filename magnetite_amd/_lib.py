@@ -41,6 +41,8 @@ SYMBOLS = [
     "mag_run_objective", "mag_download_objective",
     "mag_run_stress", "mag_download_stress",
     "mag_run_modal", "mag_download_modal", "mag_get_modal_info", "mag_get_modal_stats", "mag_apply_mass",
+    "mag_run_buckling", "mag_download_buckling", "mag_get_buckling_info", "mag_get_buckling_stats", "mag_apply_geometric",
+    "mag_assemble_geometric",
     "mag_default_transient_options", "mag_run_transient", "mag_download_transient", "mag_get_transient_info", "mag_assemble_effective",
     "mag_default_explicit_options", "mag_run_explicit", "mag_explicit_dt", "mag_internal_force",
     "mag_default_newton_options", "mag_run_newton", "mag_download_newton", "mag_get_newton_info", "mag_assemble_tangent",
@@ -120,6 +122,16 @@ class ModalOptions(C.Structure):
 
 class ModalResult(C.Structure):
     _fields_ = [("lambda_out", C.c_void_p), ("frequency_out", C.c_void_p), ("residual_out", C.c_void_p), ("shapes_out", C.c_void_p),
+                ("memory", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BucklingOptions(C.Structure):
+    _fields_ = [("modes", C.c_int32), ("subspace", C.c_int32), ("max_outer", C.c_int32), ("set", C.c_int32),
+                ("member", C.c_int32), ("reserved", C.c_int32), ("tol", C.c_double), ("cg_tol", C.c_double)]
+
+
+class BucklingResult(C.Structure):
+    _fields_ = [("load_factor_out", C.c_void_p), ("residual_out", C.c_void_p), ("shapes_out", C.c_void_p),
                 ("memory", C.c_int32), ("reserved", C.c_int32)]
 
 
@@ -285,6 +297,13 @@ def lib():
         L.mag_get_modal_info.argtypes = [vp, ip]
         L.mag_get_modal_stats.argtypes = [vp, C.c_int32, C.POINTER(Stats)]
         L.mag_apply_mass.argtypes = [vp, C.c_double, C.c_int32, dp, dp, C.c_int32]
+    if hasattr(L, "mag_run_buckling"):  # (likewise: scripts/buckling_probe.py)
+        L.mag_run_buckling.argtypes = [vp, C.POINTER(BucklingOptions)]
+        L.mag_download_buckling.argtypes = [vp, C.POINTER(BucklingResult)]
+        L.mag_get_buckling_info.argtypes = [vp, ip]
+        L.mag_get_buckling_stats.argtypes = [vp, C.c_int32, C.POINTER(Stats)]
+        L.mag_apply_geometric.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, C.c_int32]
+        L.mag_assemble_geometric.argtypes = [vp, C.c_int32, C.c_int32, dp, C.c_int32]
     if hasattr(L, "mag_run_transient"):  # (likewise: scripts/transient_probe.py)
         L.mag_default_transient_options.argtypes = [C.POINTER(TransientOptions)]
         L.mag_default_transient_options.restype = None

@@ -27,6 +27,7 @@
 #include "adjoint.h"
 #include "modal.h"
 #include "modal_host.h"
+#include "buckling.h"
 #include "objective.h"
 #include "design.h"
 #include "recover.h"
@@ -89,6 +90,24 @@ struct MemberSet {
     {
         have = have_run = false;
         count = 0;
+    }
+};
+
+// What a subspace iteration (subspace_iteration: mag_run_modal, mag_run_buckling) owns: the q vectors of the subspace as one more
+// member set (u_in = 0, f_in = Y, solved as load cases are and, like an adjoint set, dropping nothing); the rotated vectors x (the
+// shapes, at the end), w = the second operator on Z, the rotation's second Y, the residual vectors, the Gram partials, and Q, the
+// values, the Gram matrices and the norms in `small`; the results on the host.
+struct SubspacePass {
+    MemberSet set;
+    DevBuf x, w, y2, r, part, small, bad;
+    bool have = false;
+    int32_t info[8] = {};
+    std::vector<double> lambda, residual;
+    SubspacePass(const char *noun, const char *fn) : set{noun, fn, MAG_SET_CASES, true} {}
+    void reset()
+    {
+        set.reset();
+        have = false;
     }
 };
 
@@ -294,15 +313,15 @@ struct mag_ctx {
     // factors and member factors of ONE chunk of members (the nu terms and partial sums are the sensitivities')
     DevBuf obj_w, obj_target, obj_terms, obj_helem, obj_factor;
 
-    // modal analysis (mag_run_modal): the q vectors of the subspace as one more member set -- u_in = 0, f_in = Y = M X, solved as
-    // load cases are and, like an adjoint set, dropping nothing; the rotated vectors X (the modes, at the end), W = M Z, the
-    // rotation's second Y, the residual vectors, the Gram partials, and Q, lambda, the Gram matrices and norms in modal_small.
-    // The results hang on the upload only: a new mag_upload drops them, a new mag_run_modal replaces them
-    MemberSet modal{"mode vector", "mag_run_modal", MAG_SET_CASES, true};
-    DevBuf modal_x, modal_w, modal_y2, modal_r, modal_part, modal_small, modal_bad;
-    bool modal_have = false;
-    int32_t modal_info[8] = {};
-    std::vector<double> modal_lambda, modal_residual;
+    // modal analysis (mag_run_modal): the state of its subspace iteration (SubspacePass) -- f_in = Y = M X, W = M Z, the values are
+    // the eigenvalues.  The results hang on the upload only: a new mag_upload drops them, a new mag_run_modal replaces them
+    SubspacePass modal{"mode vector", "mag_run_modal"};
+
+    // linearised buckling (mag_run_buckling): the same state once more -- f_in = Y = -K_G X, the values are the load factors -- and
+    // the prestress u0, copied from the solved member before the first inner solve (the inner solves run through the context's
+    // own vectors); bk_kg: mag_assemble_geometric's values.  A new mag_upload drops the results, a new mag_run_buckling replaces them
+    SubspacePass buckling{"buckling vector", "mag_run_buckling"};
+    DevBuf bk_u0, bk_kg;
 
     // mesh refinement (mag_run_refine): the tables of the pass (rf_tab: one allocation, carved up per call), the caller's marks
     // or indicator while they are read, rocPRIM's temporary of its sorts and scans (its own: the ordering phase's stays as it is),
@@ -2656,7 +2675,7 @@ int mag_upload(mag_ctx *ctx, const mag_problem *p)
     ctx->cases.reset();
     ctx->variants.reset();
     ctx->modal.reset();
-    ctx->modal_have = false;
+    ctx->buckling.reset();
     ctx->tr_have = false;
     ctx->nt_have = false;
     ctx->tt_have = false;
@@ -4075,11 +4094,12 @@ int mag_download_stress(mag_ctx *ctx, int32_t set, int32_t index, mag_stress_fie
                          o->scalars);
 }
 
-// ---- modal analysis (modal.hip, modal_host.h): subspace iteration for the lowest pairs of K_FF phi = lambda M_FF phi, the inner
-// solves through the member-set driver as one more set, the Rayleigh-Ritz step on the host ----
+// ---- the subspace iteration of modal analysis and of linearised buckling (modal.hip, buckling.hip, modal_host.h): the pairs of
+// K_FF phi = lambda S_FF phi at the lower end, S the pass's second operator (the mass M; minus the geometric stiffness K_G), the
+// inner solves through the member-set driver as one more set, the Rayleigh-Ritz step on the host.  One driver, two callers ----
 namespace {
 
-// The inner solves of mag_run_modal run under MAG_STOP_REL with cg_tol, silently: the context's stop rule, tolerance and
+// The inner solves of the iteration run under MAG_STOP_REL with cg_tol, silently: the context's stop rule, tolerance and
 // verbosity (read at every solve) are swapped here and come back on every exit path; the history is KeptRun's.
 struct ModalStopRule {
     mag_ctx *ctx;
@@ -4128,76 +4148,173 @@ int mass_batch(mag_ctx *ctx, double density, int32_t lumped, int32_t masked, int
     return MAG_OK;
 }
 
-} // namespace
-
-int mag_run_modal(mag_ctx *ctx, const mag_modal_options *mo)
+// ... and as the geometric stiffness pass takes them, under the prestress u0 (2N, on the device)
+int geometric_batch(mag_ctx *ctx, const double *u0, double sign, int32_t masked, int32_t count, const double *x, double *y, magk::GeomBatch &gb)
 {
-    if (!ctx) return MAG_ERR_BAD_ARGS;
-    if (ctx->field_on) return field_refuses(ctx, "mag_run_modal");
-    if (!mo) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_modal: null options");
-    const int32_t p = mo->modes;
-    if (p < 1) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_modal: modes = %d: at least one mode", (int)p);
-    const int32_t q = mo->subspace != 0 ? mo->subspace : std::min(2 * p, p + 8);
-    if (q < p || q > magk::kModalMaxQ)
-        return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_modal: subspace = %d outside [modes = %d, %d]", (int)q, (int)p, magk::kModalMaxQ);
-    if (mo->max_outer < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_modal: max_outer = %d is negative", (int)mo->max_outer);
-    if (!(mo->tol >= 0.0) || !std::isfinite(mo->tol) || !(mo->cg_tol >= 0.0) || !std::isfinite(mo->cg_tol))
-        return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_modal: tol %g / cg_tol %g is negative or not finite", mo->tol, mo->cg_tol);
-    if (int rc = mass_refused(ctx, "mag_run_modal", mo->density)) return rc;
-    if (int rc = enter(ctx)) return rc;
-    const int32_t max_outer = mo->max_outer != 0 ? mo->max_outer : 50;
-    const double tol = mo->tol != 0.0 ? mo->tol : 1e-10, cg_tol = mo->cg_tol != 0.0 ? mo->cg_tol : 1e-10;
+    MemberView mv;
+    if (int rc = member_view(ctx, MAG_SET_RUN, mv)) return rc; // (the uploaded material, on the device)
+    gb = {};
+    gb.count = count;
+    gb.mat = mv.mat;
+    gb.mat_stride = 0;
+    gb.xy = ctx->xy.as<double>();
+    gb.xy_stride = 0;
+    gb.u = x;
+    gb.u0 = u0;
+    gb.y = y;
+    gb.sign = sign;
+    gb.masked = masked ? 1 : 0;
+    return MAG_OK;
+}
+
+// What a pass hands the driver: its name for messages, its state, the sizes and tolerances (defaults filled in) and
+//   second(mesh, count, x, y)        enqueues y = S x for `count` vectors, rows of prescribed DOFs zero (mesh: the tables as they
+//                                    are now -- a run of the set redoes the ordering),
+//   ritz(step, A, B, values, Q)      the Rayleigh-Ritz step on A = Z^T K Z and B = Z^T S Z (q x q, symmetrised): the q values by
+//                                    which convergence is judged and the residual formed, in the pass's order, and Q (column k =
+//                                    Ritz vector k); MAG_OK, or the status with the message set,
+//   start(Y, norms)                  (may be empty) judges the start Y = S X in front of the first inner solve; norms: device
+//                                    scratch of 2 q doubles,
+//   first_gram(A)                    (may be empty) judges the first step's A in front of its Ritz step,
+//   k_normalise                      the pass normalises its shapes by K (buckling: through A = Z^T Y, which stands for Z^T K Z only
+//                                    as far as the inner solves reach K Z = Y): the shapes are normalised once more at the end, by
+//                                    one product K X (k_normalise_shapes).
+struct SubspaceProblem {
+    const char *fn;
+    SubspacePass &pass;
+    int32_t p, q, max_outer;
+    double tol, cg_tol;
+    std::function<int(const magk::SensMesh &, int32_t, const double *, double *)> second;
+    std::function<int(int32_t, const double *, const double *, double *, double *)> ritz;
+    std::function<int(const double *, double *)> start;
+    std::function<int(const double *)> first_gram;
+    bool k_normalise = false;
+};
+
+// the status of a Ritz function of modal_host.h under the pass's name (hint: what the pass adds on dependent vectors)
+int ritz_status(mag_ctx *ctx, const char *fn, int32_t step, int eig, int pivot, double least, const char *hint)
+{
+    if (eig == magh::EIG_DEPENDENT)
+        return fail(ctx, MAG_ERR_NOT_CONVERGED,
+                    "%s: outer step %d: the vectors of the subspace are linearly dependent (pivot %d of the Gram matrices: %.3g against a "
+                    "unit diagonal, refused at or below %.3g)%s",
+                    fn, (int)step + 1, pivot, least, magh::kEigPivotTol, hint);
+    if (eig != magh::EIG_OK) return fail(ctx, MAG_ERR_NOT_CONVERGED, "%s: outer step %d: the Rayleigh-Ritz step did not converge", fn, (int)step + 1);
+    return MAG_OK;
+}
+
+// X^T K X = I for the p shapes X of a pass that normalises by K, exactly: G = X^T (K_FF X) by one matrix-free product per shape
+// (mag_apply_operator's path, in the CG's scratch vectors) and the Gram kernel, G = L L^T on the host, X <- X L^-T and Y <- Y L^-T
+// by the rotation kernel.  Through A = Z^T Y alone the shapes are K-orthonormal as far as the inner solves reach K Z = Y: where
+// Y = -K_G X is rough and Z smooth, |Z| |Y| / Z^T Y is large and a CG residual of 1e-12 |Y| left 1.7e-10 on a 16:1 column.
+// The correction is of that size: the factors and the residual vectors stay.
+int k_normalise_shapes(mag_ctx *ctx, const char *fn, SubspacePass &ps, int32_t p, double *Y, double *Y2, double *d_qs, double *d_gram)
+{
+    constexpr int MQ = magk::kModalMaxQ;
+    hipStream_t s = ctx->stream;
+    const int64_t N = ctx->N;
+    const size_t vb = 16 * (size_t)N;
+    double *X = ps.x.as<double>(), *KX = ps.w.as<double>();
+    if (int rc = ensure_full_order(ctx)) return rc;
+    if (int rc = reserve_cg(ctx)) return rc;
+    for (int32_t k = 0; k < p; ++k) {
+        magk::to_hilbert(X + 2 * N * k, ctx->iperm.as<int32_t>(), ctx->uknown.as<uint8_t>(), 1, N, ctx->tmpP.as<double>(), s);
+        if (int rc = apply_plain(ctx, ctx->tmpP.as<double>(), ctx->q.as<double>(), 1)) return rc;
+        magk::from_hilbert(ctx->q.as<double>(), ctx->iperm.as<int32_t>(), N, KX + 2 * N * k, s);
+    }
+    std::vector<double> G(2 * (size_t)p * p), L((size_t)p * p, 0.0), h_qs(MQ * MQ + MQ, 0.0);
+    magk::gram(X, KX, KX, N, p, ps.part.as<double>(), d_gram, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(G.data(), d_gram, 8 * G.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int32_t j = 0; j < p; ++j) { // G = L L^T on the mean of both triangles
+        double d = G[(size_t)j * p + j];
+        for (int32_t k = 0; k < j; ++k) d -= L[(size_t)j * p + k] * L[(size_t)j * p + k];
+        if (!(d > 0.0) || !std::isfinite(d))
+            return fail(ctx, MAG_ERR_NOT_CONVERGED, "%s: the shapes are not independent in K's inner product (pivot %d: %.3g)", fn, (int)j, d);
+        L[(size_t)j * p + j] = std::sqrt(d);
+        for (int32_t i = j + 1; i < p; ++i) {
+            double t = 0.5 * (G[(size_t)i * p + j] + G[(size_t)j * p + i]);
+            for (int32_t k = 0; k < j; ++k) t -= L[(size_t)i * p + k] * L[(size_t)j * p + k];
+            L[(size_t)i * p + j] = t / L[(size_t)j * p + j];
+        }
+    }
+    for (int32_t k = 0; k < p; ++k) { // column k of L^-T: L^T c = e_k, from the last row up (upper triangular: zero below k)
+        double c[MQ] = {};
+        for (int32_t i = k; i >= 0; --i) {
+            double t = i == k ? 1.0 : 0.0;
+            for (int32_t m = i + 1; m <= k; ++m) t -= L[(size_t)m * p + i] * c[m];
+            c[i] = t / L[(size_t)i * p + i];
+        }
+        for (int32_t i = 0; i <= k; ++i) h_qs[(size_t)i * MQ + k] = c[i];
+    }
+    HIPCHK(hipMemcpyAsync(d_qs, h_qs.data(), 8 * h_qs.size(), hipMemcpyHostToDevice, s));
+    magk::rotate(X, Y, Y, d_qs, N, p, p, KX, Y2, nullptr, s); // (K X is done with: the new shapes go there first)
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(X, KX, vb * p, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(Y, Y2, vb * p, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipStreamSynchronize(s)); // (h_qs is done with)
+    return MAG_OK;
+}
+
+// The iteration, past the pass's argument checks and inside the context: the ordering, the orientation check, the buffers, the
+// start vectors, the outer steps, the residuals and signs; leaves pass.have, pass.info[0..6], pass.lambda (the first p values)
+// and pass.residual.
+int subspace_iteration(mag_ctx *ctx, const SubspaceProblem &sp)
+{
+    const char *fn = sp.fn;
+    SubspacePass &ps = sp.pass;
+    const int32_t p = sp.p, q = sp.q, max_outer = sp.max_outer;
     hipStream_t s = ctx->stream;
     const int64_t N = ctx->N;
     const size_t vb = 16 * (size_t)N;
     constexpr int MQ = magk::kModalMaxQ;
-    ctx->modal_have = false;
-    MemberSet &set = ctx->modal;
+    ps.have = false;
+    MemberSet &set = ps.set;
     set.have = set.have_run = false;
 
     if (int rc = ensure_full_order(ctx)) return rc; // (validates conn, counts the free DOFs, leaves the bounding box)
-    if (q > ctx->nf)
-        return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_modal: subspace = %d exceeds the %lld free DOFs", (int)q, (long long)ctx->nf);
-    HIPCHK(ctx->modal_bad.reserve(8));
+    if (q > ctx->nf) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: subspace = %d exceeds the %lld free DOFs", fn, (int)q, (long long)ctx->nf);
+    HIPCHK(ps.bad.reserve(8));
     unsigned long long bad = ~0ull;
-    magk::orientation(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), N, ctx->E, ctx->modal_bad.as<unsigned long long>(), s);
+    magk::orientation(ctx->xy.as<double>(), ctx->conn.as<int32_t>(), N, ctx->E, ps.bad.as<unsigned long long>(), s);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&bad, ctx->modal_bad.p, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&bad, ps.bad.p, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (bad != ~0ull)
         return fail(ctx, MAG_ERR_BAD_ARGS,
-                    "mag_run_modal: element %lld has a signed area <= 0 (the stiffness carries the signed area: modal analysis needs "
+                    "%s: element %lld has a signed area <= 0 (the stiffness carries the signed area: modal analysis needs "
                     "counter-clockwise elements)",
-                    (long long)bad);
+                    fn, (long long)bad);
 
-    // Q [MQ][MQ], lambda [MQ], then A and B [q][q] each, then the norms [p][2]
+    // Q [MQ][MQ], lambda [MQ], then A and B [q][q] each, then the norms [q][2]
     const size_t small_doubles = MQ * MQ + MQ + 2 * (size_t)MQ * MQ + 2 * MQ;
     HIPCHK(set.uin.reserve(vb * q));
     HIPCHK(set.fin.reserve(vb * q));
-    HIPCHK(ctx->modal_x.reserve(vb * q));
-    HIPCHK(ctx->modal_w.reserve(vb * q));
-    HIPCHK(ctx->modal_y2.reserve(vb * q));
-    HIPCHK(ctx->modal_r.reserve(vb * p));
-    HIPCHK(ctx->modal_part.reserve(8 * 2 * magk::kModalGramCols * (size_t)magk::kSensBlocks * (size_t)magk::gram_rows(q)));
-    HIPCHK(ctx->modal_small.reserve(8 * small_doubles));
-    double *d_qs = ctx->modal_small.as<double>(), *d_gram = d_qs + MQ * MQ + MQ, *d_norms = d_gram + 2 * MQ * MQ;
-    double *X = ctx->modal_x.as<double>(), *Y = set.fin.as<double>(), *W = ctx->modal_w.as<double>(), *Y2 = ctx->modal_y2.as<double>();
+    HIPCHK(ps.x.reserve(vb * q));
+    HIPCHK(ps.w.reserve(vb * q));
+    HIPCHK(ps.y2.reserve(vb * q));
+    HIPCHK(ps.r.reserve(vb * p));
+    HIPCHK(ps.part.reserve(8 * 2 * magk::kModalGramCols * (size_t)magk::kSensBlocks * (size_t)magk::gram_rows(q)));
+    HIPCHK(ps.small.reserve(8 * small_doubles));
+    double *d_qs = ps.small.as<double>(), *d_gram = d_qs + MQ * MQ + MQ, *d_norms = d_gram + 2 * MQ * MQ;
+    double *X = ps.x.as<double>(), *Y = set.fin.as<double>(), *W = ps.w.as<double>(), *Y2 = ps.y2.as<double>();
 
-    // ---- 1. the start vectors and Y = M X
+    // ---- 1. the start vectors and Y = S X
     magk::SensMesh mesh;
-    magk::MassBatch mb;
     if (int rc = sens_mesh(ctx, mesh)) return rc;
     HIPCHK(hipMemsetAsync(set.uin.p, 0, vb * q, s));
     magk::start_vectors(ctx->xy.as<double>(), ctx->uknown.as<uint8_t>(), N, q, X, s);
-    if (int rc = mass_batch(ctx, mo->density, mo->lumped, 1, q, X, Y, mb)) return rc;
-    magk::mass_apply(mesh, mb, s);
+    if (int rc = sp.second(mesh, q, X, Y)) return rc;
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
+    if (sp.start)
+        if (int rc = sp.start(Y, d_norms)) return rc;
     set.count = q;
     set.have = true;
 
     // ---- 2. the outer steps
-    int32_t *info = ctx->modal_info;
+    int32_t *info = ps.info;
     for (int k = 0; k < 8; ++k) info[k] = 0;
     info[0] = p;
     info[1] = q;
@@ -4208,7 +4325,7 @@ int mag_run_modal(mag_ctx *ctx, const mag_modal_options *mo)
         {
             KeptRun kept(ctx);
             if (int rc = kept.keep()) return rc;
-            ModalStopRule rule(ctx, cg_tol);
+            ModalStopRule rule(ctx, sp.cg_tol);
             status = run_case_set(ctx, set);
         }
         info[2] = step + 1;
@@ -4217,19 +4334,18 @@ int mag_run_modal(mag_ctx *ctx, const mag_modal_options *mo)
         info[6] += set.info[3];
         if (status != MAG_OK) { // (the inner solve's own status and words, under this entry point's name)
             const std::string why = ctx->err;
-            return fail(ctx, status, "mag_run_modal: outer step %d: %s", (int)step + 1, why.c_str());
+            return fail(ctx, status, "%s: outer step %d: %s", fn, (int)step + 1, why.c_str());
         }
         for (int32_t j = 0; j < q; ++j)
             if (!set.stats[(size_t)j].converged)
                 return fail(ctx, MAG_ERR_NOT_CONVERGED,
-                            "mag_run_modal: outer step %d, vector %d: the inner solve stopped at the iteration cap after %lld iterations "
+                            "%s: outer step %d, vector %d: the inner solve stopped at the iteration cap after %lld iterations "
                             "(a part without enough supports has a singular K_FF)",
-                            (int)step + 1, (int)j, (long long)set.stats[(size_t)j].iterations);
+                            fn, (int)step + 1, (int)j, (long long)set.stats[(size_t)j].iterations);
         const double *Z = set.u.as<double>();
         if (int rc = sens_mesh(ctx, mesh)) return rc; // (the run has redone the ordering: the tile-local table with it)
-        if (int rc = mass_batch(ctx, mo->density, mo->lumped, 1, q, Z, W, mb)) return rc;
-        magk::mass_apply(mesh, mb, s);
-        magk::gram(Z, Y, W, N, q, ctx->modal_part.as<double>(), d_gram, s);
+        if (int rc = sp.second(mesh, q, Z, W)) return rc;
+        magk::gram(Z, Y, W, N, q, ps.part.as<double>(), d_gram, s);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(h_gram.data(), d_gram, 8 * h_gram.size(), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
@@ -4238,19 +4354,13 @@ int mag_run_modal(mag_ctx *ctx, const mag_modal_options *mo)
                 A[(size_t)i * q + j] = 0.5 * (h_gram[(size_t)i * q + j] + h_gram[(size_t)j * q + i]);
                 B[(size_t)i * q + j] = 0.5 * (h_gram[(size_t)q * q + (size_t)i * q + j] + h_gram[(size_t)q * q + (size_t)j * q + i]);
             }
-        int pivot = -1;
-        double least = 0.0;
-        const int eig = magh::sym_def_eig(q, A.data(), B.data(), lambda.data(), Qm.data(), &pivot, &least);
-        if (eig == magh::EIG_DEPENDENT)
-            return fail(ctx, MAG_ERR_NOT_CONVERGED,
-                        "mag_run_modal: outer step %d: the vectors of the subspace are linearly dependent (pivot %d of the Gram matrices: %.3g against a "
-                        "unit diagonal, refused at or below %.3g)",
-                        (int)step + 1, pivot, least, magh::kEigPivotTol);
-        if (eig != magh::EIG_OK) return fail(ctx, MAG_ERR_NOT_CONVERGED, "mag_run_modal: outer step %d: the Rayleigh-Ritz step did not converge", (int)step + 1);
+        if (step == 0 && sp.first_gram)
+            if (int rc = sp.first_gram(A.data())) return rc;
+        if (int rc = sp.ritz(step, A.data(), B.data(), lambda.data(), Qm.data())) return rc;
         if (!prev.empty()) {
             double change = 0.0;
             for (int32_t k = 0; k < p; ++k) change = std::max(change, std::fabs(lambda[(size_t)k] - prev[(size_t)k]) / std::fabs(lambda[(size_t)k]));
-            converged = change <= tol; // (a NaN is no convergence)
+            converged = change <= sp.tol; // (a NaN is no convergence)
         }
         prev = lambda;
         const bool last = converged || step + 1 == max_outer;
@@ -4259,31 +4369,88 @@ int mag_run_modal(mag_ctx *ctx, const mag_modal_options *mo)
             for (int32_t j = 0; j < q; ++j) h_qs[(size_t)i * MQ + j] = Qm[(size_t)i * q + j];
         for (int32_t k = 0; k < q; ++k) h_qs[(size_t)MQ * MQ + k] = lambda[(size_t)k];
         HIPCHK(hipMemcpyAsync(d_qs, h_qs.data(), 8 * h_qs.size(), hipMemcpyHostToDevice, s));
-        magk::rotate(Z, W, Y, d_qs, N, q, p, X, Y2, last ? ctx->modal_r.as<double>() : nullptr, s);
+        magk::rotate(Z, W, Y, d_qs, N, q, p, X, Y2, last ? ps.r.as<double>() : nullptr, s);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(Y, Y2, vb * q, hipMemcpyDeviceToDevice, s));
         HIPCHK(hipStreamSynchronize(s)); // (h_qs is done with)
         if (last) break;
     }
 
-    // ---- 3. the residuals from the pass's own quantities, the modes' signs
+    // ---- 3. the residuals from the pass's own quantities, the shapes' signs
+    if (sp.k_normalise)
+        if (int rc = k_normalise_shapes(ctx, fn, ps, p, Y, Y2, d_qs, d_gram)) return rc;
     std::vector<double> norms(2 * (size_t)p);
-    magk::residual_norms(ctx->modal_r.as<double>(), Y, N, p, ctx->modal_part.as<double>(), d_norms, s);
+    magk::residual_norms(ps.r.as<double>(), Y, N, p, ps.part.as<double>(), d_norms, s);
     magk::fix_signs(X, N, p, s);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(norms.data(), d_norms, 8 * norms.size(), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    ctx->modal_lambda.assign(lambda.begin(), lambda.begin() + p);
-    ctx->modal_residual.assign((size_t)p, 0.0);
+    ps.lambda.assign(lambda.begin(), lambda.begin() + p);
+    ps.residual.assign((size_t)p, 0.0);
     for (int32_t k = 0; k < p; ++k) {
         const double den = std::fabs(lambda[(size_t)k]) * std::sqrt(norms[2 * (size_t)k + 1]);
-        ctx->modal_residual[(size_t)k] = den > 0.0 ? std::sqrt(norms[2 * (size_t)k]) / den : 0.0;
+        ps.residual[(size_t)k] = den > 0.0 ? std::sqrt(norms[2 * (size_t)k]) / den : 0.0;
     }
     info[3] = converged ? 1 : 0;
-    ctx->modal_have = true;
+    ps.have = true;
     if (!converged)
-        ctx->err = "mag_run_modal stopped at the cap of " + std::to_string((int)max_outer) + " outer steps above the tolerance: last iterate returned";
+        ctx->err = std::string(fn) + " stopped at the cap of " + std::to_string((int)max_outer) + " outer steps above the tolerance: last iterate returned";
     return MAG_OK;
+}
+
+// the argument checks both passes share, behind the null checks: sizes and tolerances; *q: the subspace with its default
+int subspace_args_refused(mag_ctx *ctx, const char *fn, int32_t p, int32_t subspace, int32_t max_outer, double tol, double cg_tol, int32_t *q)
+{
+    if (p < 1) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: modes = %d: at least one mode", fn, (int)p);
+    *q = subspace != 0 ? subspace : std::min(2 * p, p + 8);
+    if (*q < p || *q > magk::kModalMaxQ)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: subspace = %d outside [modes = %d, %d]", fn, (int)*q, (int)p, magk::kModalMaxQ);
+    if (max_outer < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: max_outer = %d is negative", fn, (int)max_outer);
+    if (!(tol >= 0.0) || !std::isfinite(tol) || !(cg_tol >= 0.0) || !std::isfinite(cg_tol))
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: tol %g / cg_tol %g is negative or not finite", fn, tol, cg_tol);
+    return MAG_OK;
+}
+
+// the results of a pass to the caller: values, residuals, shapes
+int subspace_download(mag_ctx *ctx, const SubspacePass &ps, int32_t memory, double *values_out, double *residual_out, double *shapes_out)
+{
+    const int32_t p = ps.info[0];
+    const auto [kind, hkind] = out_kinds(memory);
+    hipStream_t s = ctx->stream;
+    if (values_out) HIPCHK(hipMemcpyAsync(values_out, ps.lambda.data(), 8 * (size_t)p, hkind, s));
+    if (residual_out) HIPCHK(hipMemcpyAsync(residual_out, ps.residual.data(), 8 * (size_t)p, hkind, s));
+    if (shapes_out) HIPCHK(hipMemcpyAsync(shapes_out, ps.x.p, 16 * (size_t)ctx->N * (size_t)p, kind, s));
+    return MAG_OK;
+}
+
+} // namespace
+
+int mag_run_modal(mag_ctx *ctx, const mag_modal_options *mo)
+{
+    const char *fn = "mag_run_modal";
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (ctx->field_on) return field_refuses(ctx, fn);
+    if (!mo) return fail(ctx, MAG_ERR_BAD_ARGS, "mag_run_modal: null options");
+    int32_t q = 0;
+    if (int rc = subspace_args_refused(ctx, fn, mo->modes, mo->subspace, mo->max_outer, mo->tol, mo->cg_tol, &q)) return rc;
+    if (int rc = mass_refused(ctx, fn, mo->density)) return rc;
+    if (int rc = enter(ctx)) return rc;
+    hipStream_t s = ctx->stream;
+    SubspaceProblem sp = {fn, ctx->modal, mo->modes, q, mo->max_outer != 0 ? mo->max_outer : 50, mo->tol != 0.0 ? mo->tol : 1e-10,
+                          mo->cg_tol != 0.0 ? mo->cg_tol : 1e-10, {}, {}, {}, {}};
+    sp.second = [&](const magk::SensMesh &mesh, int32_t count, const double *x, double *y) -> int {
+        magk::MassBatch mb;
+        if (int rc = mass_batch(ctx, mo->density, mo->lumped, 1, count, x, y, mb)) return rc;
+        magk::mass_apply(mesh, mb, s);
+        return MAG_OK;
+    };
+    sp.ritz = [&](int32_t step, const double *A, const double *B, double *lambda, double *Q) -> int {
+        int pivot = -1;
+        double least = 0.0;
+        const int eig = magh::sym_def_eig(q, A, B, lambda, Q, &pivot, &least);
+        return ritz_status(ctx, fn, step, eig, pivot, least, "");
+    };
+    return subspace_iteration(ctx, sp);
 }
 
 int mag_download_modal(mag_ctx *ctx, mag_modal_result *o)
@@ -4293,17 +4460,14 @@ int mag_download_modal(mag_ctx *ctx, mag_modal_result *o)
     if (int rc = memory_refused(ctx, o->memory, "mag_download_modal")) return rc;
     if (ctx->comm.nranks > 1)
         return fail(ctx, MAG_ERR_BAD_ARGS, "modal analysis runs on one GPU: this context has a communicator of %d ranks", ctx->comm.nranks);
-    if (!ctx->have_problem || !ctx->modal_have) return fail(ctx, MAG_ERR_STATE, "mag_download_modal before a completed mag_run_modal");
+    if (!ctx->have_problem || !ctx->modal.have) return fail(ctx, MAG_ERR_STATE, "mag_download_modal before a completed mag_run_modal");
     if (int rc = enter(ctx)) return rc;
-    const int32_t p = ctx->modal_info[0];
-    const auto [kind, hkind] = out_kinds(o->memory);
+    const int32_t p = ctx->modal.info[0];
     hipStream_t s = ctx->stream;
     std::vector<double> freq((size_t)p);
-    for (int32_t k = 0; k < p; ++k) freq[(size_t)k] = std::sqrt(ctx->modal_lambda[(size_t)k]) / (2.0 * M_PI);
-    if (o->lambda_out) HIPCHK(hipMemcpyAsync(o->lambda_out, ctx->modal_lambda.data(), 8 * (size_t)p, hkind, s));
-    if (o->frequency_out) HIPCHK(hipMemcpyAsync(o->frequency_out, freq.data(), 8 * (size_t)p, hkind, s));
-    if (o->residual_out) HIPCHK(hipMemcpyAsync(o->residual_out, ctx->modal_residual.data(), 8 * (size_t)p, hkind, s));
-    if (o->shapes_out) HIPCHK(hipMemcpyAsync(o->shapes_out, ctx->modal_x.p, 16 * (size_t)ctx->N * (size_t)p, kind, s));
+    for (int32_t k = 0; k < p; ++k) freq[(size_t)k] = std::sqrt(ctx->modal.lambda[(size_t)k]) / (2.0 * M_PI);
+    if (o->frequency_out) HIPCHK(hipMemcpyAsync(o->frequency_out, freq.data(), 8 * (size_t)p, out_kinds(o->memory).host, s));
+    if (int rc = subspace_download(ctx, ctx->modal, o->memory, o->lambda_out, o->residual_out, o->shapes_out)) return rc;
     HIPCHK(hipStreamSynchronize(s));
     return MAG_OK;
 }
@@ -4311,16 +4475,16 @@ int mag_download_modal(mag_ctx *ctx, mag_modal_result *o)
 int mag_get_modal_info(const mag_ctx *ctx, int32_t info[8])
 {
     if (!ctx || !info || ctx->comm.nranks > 1) return MAG_ERR_BAD_ARGS;
-    if (!ctx->have_problem || !ctx->modal_have) return MAG_ERR_STATE;
-    for (int k = 0; k < 8; ++k) info[k] = ctx->modal_info[k];
+    if (!ctx->have_problem || !ctx->modal.have) return MAG_ERR_STATE;
+    for (int k = 0; k < 8; ++k) info[k] = ctx->modal.info[k];
     return MAG_OK;
 }
 
 int mag_get_modal_stats(const mag_ctx *ctx, int32_t j, mag_stats *st)
 {
     if (!ctx || !st || j < 0 || ctx->comm.nranks > 1) return MAG_ERR_BAD_ARGS;
-    if (!ctx->have_problem || !ctx->modal_have) return MAG_ERR_STATE;
-    return member_stats(ctx->modal, j, st);
+    if (!ctx->have_problem || !ctx->modal.have) return MAG_ERR_STATE;
+    return member_stats(ctx->modal.set, j, st);
 }
 
 int mag_apply_mass(mag_ctx *ctx, double density, int32_t lumped, const double *x, double *y, int32_t masked)
@@ -4334,17 +4498,201 @@ int mag_apply_mass(mag_ctx *ctx, double density, int32_t lumped, const double *x
     const size_t vb = 16 * (size_t)N;
     hipStream_t s = ctx->stream;
     // (staged in the iteration's scratch vectors: the modes, like every other result, stay as they are)
-    HIPCHK(ctx->modal_w.reserve(vb));
-    HIPCHK(ctx->modal_y2.reserve(vb));
+    HIPCHK(ctx->modal.w.reserve(vb));
+    HIPCHK(ctx->modal.y2.reserve(vb));
     magk::SensMesh mesh;
     magk::MassBatch mb;
     if (int rc = sens_mesh(ctx, mesh)) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->modal_w.p, x, vb, hipMemcpyHostToDevice, s));
-    if (masked) magk::mask_vectors(ctx->uknown.as<uint8_t>(), N, 1, ctx->modal_w.as<double>(), s);
-    if (int rc = mass_batch(ctx, density, lumped, masked, 1, ctx->modal_w.as<double>(), ctx->modal_y2.as<double>(), mb)) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->modal.w.p, x, vb, hipMemcpyHostToDevice, s));
+    if (masked) magk::mask_vectors(ctx->uknown.as<uint8_t>(), N, 1, ctx->modal.w.as<double>(), s);
+    if (int rc = mass_batch(ctx, density, lumped, masked, 1, ctx->modal.w.as<double>(), ctx->modal.y2.as<double>(), mb)) return rc;
     magk::mass_apply(mesh, mb, s);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(y, ctx->modal_y2.p, vb, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(y, ctx->modal.y2.p, vb, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
+// ---- linearised buckling (buckling.hip): the driver above with S = -K_G(sigma(u0)) and the pencil's Ritz step ----
+namespace {
+
+magk::Pattern transient_pattern(const mag_ctx *ctx); // (with the transient pass, below)
+
+// the checks mag_run_buckling, mag_apply_geometric and mag_assemble_geometric share, before any HIP call: the context and the
+// solved member whose solution is the prestress
+int prestress_refused(mag_ctx *ctx, const char *fn, int32_t set, int32_t member)
+{
+    if (set != MAG_SET_RUN && set != MAG_SET_CASES)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: set %d: the prestress is a member of MAG_SET_RUN or MAG_SET_CASES", fn, (int)set);
+    if (ctx->comm.nranks > 1)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: buckling analysis runs on one GPU: this context has a communicator of %d ranks", fn, ctx->comm.nranks);
+    const bool ran = set == MAG_SET_RUN ? ctx->have_run : ctx->cases.have_run;
+    if (!ctx->have_problem) return fail(ctx, MAG_ERR_STATE, "%s before mag_upload", fn);
+    if (!ran) return fail(ctx, MAG_ERR_STATE, "%s before a completed %s", fn, kSetRun[set]);
+    const int32_t count = set == MAG_SET_RUN ? 1 : ctx->cases.count;
+    if (member < 0 || member >= count) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: member %d outside the set's %d", fn, (int)member, (int)count);
+    return MAG_OK;
+}
+
+// the solved member's displacements (2N, caller numbering, on the device), copied into bk_u0: nothing that runs later moves them
+int prestress_copy(mag_ctx *ctx, int32_t set, int32_t member)
+{
+    const size_t vb = 16 * (size_t)ctx->N;
+    const char *u = set == MAG_SET_RUN ? ctx->u.as<char>() : ctx->cases.u.as<char>() + vb * (size_t)member;
+    HIPCHK(ctx->bk_u0.reserve(vb));
+    HIPCHK(hipMemcpyAsync(ctx->bk_u0.p, u, vb, hipMemcpyDeviceToDevice, ctx->stream));
+    return MAG_OK;
+}
+
+} // namespace
+
+int mag_run_buckling(mag_ctx *ctx, const mag_buckling_options *bo)
+{
+    const char *fn = "mag_run_buckling";
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (ctx->field_on) return field_refuses(ctx, fn);
+    if (!bo) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null options", fn);
+    int32_t q = 0;
+    if (int rc = subspace_args_refused(ctx, fn, bo->modes, bo->subspace, bo->max_outer, bo->tol, bo->cg_tol, &q)) return rc;
+    if (int rc = prestress_refused(ctx, fn, bo->set, bo->member)) return rc;
+    if (int rc = enter(ctx)) return rc;
+    hipStream_t s = ctx->stream;
+    const int64_t N = ctx->N;
+    const int32_t p = bo->modes;
+    SubspacePass &ps = ctx->buckling;
+    ps.have = false;
+    if (int rc = prestress_copy(ctx, bo->set, bo->member)) return rc;
+    const double *u0 = ctx->bk_u0.as<double>();
+    const auto no_stress = [&](const char *what, int32_t j) {
+        return fail(ctx, MAG_ERR_STATE, "%s: the prestress vanishes (%s of start vector %d is not positive): member %d of set %d carries no stress", fn,
+                    what, (int)j, (int)bo->member, (int)bo->set);
+    };
+    SubspaceProblem sp = {fn, ps, p, q, bo->max_outer != 0 ? bo->max_outer : 50, bo->tol != 0.0 ? bo->tol : 1e-10,
+                          bo->cg_tol != 0.0 ? bo->cg_tol : 1e-10, {}, {}, {}, {}};
+    sp.second = [&](const magk::SensMesh &mesh, int32_t count, const double *x, double *y) -> int {
+        magk::GeomBatch gb;
+        if (int rc = geometric_batch(ctx, u0, -1.0, 1, count, x, y, gb)) return rc;
+        HIPCHK(magk::geometric_apply(mesh, gb, s));
+        return MAG_OK;
+    };
+    sp.start = [&](const double *Y, double *d_norms) -> int { // (a right-hand side of zero is no system to solve)
+        std::vector<double> norms(2 * (size_t)q);
+        magk::residual_norms(Y, Y, N, q, ps.part.as<double>(), d_norms, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(norms.data(), d_norms, 8 * norms.size(), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (int32_t j = 0; j < q; ++j)
+            if (!(norms[2 * (size_t)j] > 0.0)) return no_stress("|K_G x|", j);
+        return MAG_OK;
+    };
+    sp.first_gram = [&](const double *A) -> int {
+        for (int32_t j = 0; j < q; ++j)
+            if (!(A[(size_t)j * q + j] > 0.0)) return no_stress("A_jj", j);
+        return MAG_OK;
+    };
+    sp.ritz = [&](int32_t step, const double *A, const double *B, double *lambda, double *Q) -> int {
+        int pivot = -1;
+        double least = 0.0, mu[magh::kEigMaxN];
+        const int eig = magh::sym_pencil_eig(q, A, B, mu, Q, &pivot, &least);
+        if (int rc = ritz_status(ctx, fn, step, eig, pivot, least,
+                                 ": a K_G of rank below the subspace's size causes it, a smaller subspace helps"))
+            return rc;
+        for (int32_t k = 0; k < p; ++k)
+            if (!(std::fabs(mu[k]) > magh::kEigPivotTol * std::fabs(mu[0])))
+                return fail(ctx, MAG_ERR_NOT_CONVERGED,
+                            "%s: outer step %d: fewer than %d buckling modes exist (|mu_%d| = %.3g against |mu_1| = %.3g, refused at or below %.3g of it)",
+                            fn, (int)step + 1, (int)p, (int)k + 1, std::fabs(mu[k]), std::fabs(mu[0]), magh::kEigPivotTol);
+        for (int32_t k = 0; k < q; ++k) lambda[k] = 1.0 / mu[k]; // (a guard vector's mu may be 0: its factor is infinite and unused)
+        return MAG_OK;
+    };
+    sp.k_normalise = true;
+    if (int rc = subspace_iteration(ctx, sp)) return rc;
+    for (int32_t k = 0; k < p; ++k) ps.info[7] += ps.lambda[(size_t)k] > 0.0 ? 1 : 0;
+    return MAG_OK;
+}
+
+int mag_download_buckling(mag_ctx *ctx, mag_buckling_result *o)
+{
+    const char *fn = "mag_download_buckling";
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (!o) return fail(ctx, MAG_ERR_BAD_ARGS, "null buckling result");
+    if (int rc = memory_refused(ctx, o->memory, fn)) return rc;
+    if (ctx->comm.nranks > 1)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: buckling analysis runs on one GPU: this context has a communicator of %d ranks", fn, ctx->comm.nranks);
+    if (!ctx->have_problem || !ctx->buckling.have) return fail(ctx, MAG_ERR_STATE, "%s before a completed mag_run_buckling", fn);
+    if (int rc = enter(ctx)) return rc;
+    if (int rc = subspace_download(ctx, ctx->buckling, o->memory, o->load_factor_out, o->residual_out, o->shapes_out)) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MAG_OK;
+}
+
+int mag_get_buckling_info(const mag_ctx *ctx, int32_t info[8])
+{
+    if (!ctx || !info || ctx->comm.nranks > 1) return MAG_ERR_BAD_ARGS;
+    if (!ctx->have_problem || !ctx->buckling.have) return MAG_ERR_STATE;
+    for (int k = 0; k < 8; ++k) info[k] = ctx->buckling.info[k];
+    return MAG_OK;
+}
+
+int mag_get_buckling_stats(const mag_ctx *ctx, int32_t j, mag_stats *st)
+{
+    if (!ctx || !st || j < 0 || ctx->comm.nranks > 1) return MAG_ERR_BAD_ARGS;
+    if (!ctx->have_problem || !ctx->buckling.have) return MAG_ERR_STATE;
+    return member_stats(ctx->buckling.set, j, st);
+}
+
+int mag_apply_geometric(mag_ctx *ctx, int32_t set, int32_t member, const double *x, double *y, int32_t masked)
+{
+    const char *fn = "mag_apply_geometric";
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (ctx->field_on) return field_refuses(ctx, fn);
+    if (!x || !y) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null vector", fn);
+    if (int rc = prestress_refused(ctx, fn, set, member)) return rc;
+    if (int rc = enter(ctx)) return rc;
+    if (int rc = ensure_full_order(ctx)) return rc;
+    const int64_t N = ctx->N;
+    const size_t vb = 16 * (size_t)N;
+    hipStream_t s = ctx->stream;
+    // (staged in the iteration's scratch vectors: the shapes, like every other result, stay as they are)
+    HIPCHK(ctx->buckling.w.reserve(vb));
+    HIPCHK(ctx->buckling.y2.reserve(vb));
+    magk::SensMesh mesh;
+    magk::GeomBatch gb;
+    if (int rc = sens_mesh(ctx, mesh)) return rc;
+    if (int rc = prestress_copy(ctx, set, member)) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->buckling.w.p, x, vb, hipMemcpyHostToDevice, s));
+    if (masked) magk::mask_vectors(ctx->uknown.as<uint8_t>(), N, 1, ctx->buckling.w.as<double>(), s);
+    if (int rc = geometric_batch(ctx, ctx->bk_u0.as<double>(), 1.0, masked, 1, ctx->buckling.w.as<double>(), ctx->buckling.y2.as<double>(), gb))
+        return rc;
+    HIPCHK(magk::geometric_apply(mesh, gb, s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(y, ctx->buckling.y2.p, vb, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MAG_OK;
+}
+
+int mag_assemble_geometric(mag_ctx *ctx, int32_t set, int32_t member, double *values_out, int32_t memory)
+{
+    const char *fn = "mag_assemble_geometric";
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (ctx->field_on) return field_refuses(ctx, fn);
+    if (!values_out) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null values_out", fn);
+    if (int rc = memory_refused(ctx, memory, fn)) return rc;
+    if (int rc = prestress_refused(ctx, fn, set, member)) return rc;
+    if (ctx->opt.assemble_csr == 0) return fail(ctx, MAG_ERR_STATE, "%s: needs K's pattern: this context has assemble_csr = 0", fn);
+    if (int rc = enter(ctx)) return rc;
+    if (int rc = ensure_csr(ctx)) return rc;
+    hipStream_t s = ctx->stream;
+    const size_t ab = 32 * (size_t)ctx->nb;
+    HIPCHK(ctx->bk_kg.reserve(ab));
+    magk::SensMesh mesh;
+    MemberView mv;
+    if (int rc = sens_mesh(ctx, mesh)) return rc;
+    if (int rc = member_view(ctx, MAG_SET_RUN, mv)) return rc; // (the uploaded material, on the device)
+    if (int rc = prestress_copy(ctx, set, member)) return rc;
+    magk::geometric_values(mesh, transient_pattern(ctx), ctx->xy.as<double>(), mv.mat, ctx->bk_u0.as<double>(), ctx->bk_kg.as<double>(), s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(values_out, ctx->bk_kg.p, ab, out_kinds(memory).dev, s));
     HIPCHK(hipStreamSynchronize(s));
     return MAG_OK;
 }

@@ -715,6 +715,81 @@ class Context:
                                            1 if masked else 0))
         return y
 
+    # -- linearised buckling: the critical load factors and buckling shapes of a solved member ------------
+    BUCKLING_INFO = ("modes", "subspace", "outer", "converged", "vectors_per_launch", "launches", "redone", "positive")
+    BUCKLING_SETS = {"run": _lib.MAG_SET_RUN, "cases": _lib.MAG_SET_CASES}
+
+    def _prestress(self, what, set, member):
+        if set not in self.BUCKLING_SETS:
+            raise MagnetiteError("Solver", f"{what}: set must be one of {sorted(self.BUCKLING_SETS)} (the prestress is a solved run or load case)")
+        if int(member) != member or member < 0:
+            raise MagnetiteError("Solver", f"{what}: member {member!r} is no index of a solved member")
+        return self.BUCKLING_SETS[set], int(member)
+
+    def run_buckling(self, modes=4, set="run", member=0, subspace=0, tol=0.0, cg_tol=0.0, max_outer=0, allow_not_converged=False):
+        """mag_run_buckling under the prestress of a solved member (the last run(), or case `member` of the last run_cases()):
+        the `modes` pairs of smallest |lambda| of (K_FF + lambda K_G,FF) phi = 0.  Reaching max_outer is no error
+        (buckling_info()["converged"] == 0)."""
+        sid, member = self._prestress("buckling", set, member)
+        o = _lib.BucklingOptions(int(modes), int(subspace), int(max_outer), sid, member, 0, float(tol), float(cg_tol))
+        allow = (MAG_ERR_NOT_CONVERGED,) if allow_not_converged else ()
+        return self._check(self._L.mag_run_buckling(self._h, C.byref(o)), allow)
+
+    def buckling_info(self):
+        """dict(modes, subspace, outer, converged, vectors_per_launch (0: one after another), launches, redone, positive)."""
+        info = (C.c_int32 * 8)()
+        self._check(self._L.mag_get_buckling_info(self._h, info))
+        return dict(zip(self.BUCKLING_INFO, info))
+
+    def buckling_stats(self, j):
+        """The statistics of inner solve j of the last outer step (mag_get_buckling_stats)."""
+        return self._stats_at(self._L.mag_get_buckling_stats, j)
+
+    def download_buckling(self):
+        """dict(load_factor (p), residual (p), shapes (p, 2N)) of the last run_buckling()."""
+        p = self.buckling_info()["modes"]
+        lam, res, shapes = np.empty(p), np.empty(p), np.empty((p, 2 * self.N))
+        o = _lib.BucklingResult(lam.ctypes.data, res.ctypes.data, shapes.ctypes.data, MAG_MEM_HOST, 0)
+        self._check(self._L.mag_download_buckling(self._h, C.byref(o)))
+        return {"load_factor": lam, "residual": res, "shapes": shapes}
+
+    def buckling(self, prob=None, modes=4, set="run", member=0, subspace=0, tol=0.0, cg_tol=0.0, max_outer=0):
+        """The `modes` load factors of smallest magnitude, signed and ordered by magnitude, and the buckling shapes under the
+        prestress of a solved member (prob, when given, is uploaded and run first): dict(load_factor, residual, shapes (modes,
+        2N), critical -- the smallest positive factor, or None -- and the words of buckling_info() by name).  A negative factor
+        is buckling under the reversed load.  shapes are K-normalised, phi_k^T K phi_l = delta_kl, and 0 on prescribed DOFs,
+        which act as supports (include/magnetite_hip.h)."""
+        self._prestress("buckling", set, member)
+        if prob is not None:
+            self.upload_problem(prob)
+            self.run()
+        self.run_buckling(modes, set, member, subspace, tol, cg_tol, max_outer)
+        out = self.download_buckling()
+        out.update(self.buckling_info())
+        positive = out["load_factor"][out["load_factor"] > 0.0]
+        out["critical"] = float(positive.min()) if positive.size else None
+        return out
+
+    def apply_geometric(self, x, set="run", member=0, masked=False):
+        """y = K_G(sigma(u0)) x with the geometric stiffness operator of run_buckling, u0 the solution of the solved member
+        (test entry point mag_apply_geometric)."""
+        sid, member = self._prestress("apply_geometric", set, member)
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        if x.size != 2 * self.N:
+            raise MagnetiteError("Solver", f"apply_geometric: an array of {x.size} entries where {2 * self.N} are expected")
+        y = np.empty(2 * self.N)
+        self._check(self._L.mag_apply_geometric(self._h, sid, member, _p(x, C.c_double), _p(y, C.c_double), 1 if masked else 0))
+        return y
+
+    def assemble_geometric(self, set="run", member=0):
+        """The values of K_G(sigma(u0)) in the layout of assemble_csr() (mag_assemble_geometric)."""
+        sid, member = self._prestress("assemble_geometric", set, member)
+        nnz = C.c_int64(0)
+        self._check(self._L.mag_assemble_csr(self._h, C.byref(nnz), None, None, None))
+        val = np.empty(nnz.value)
+        self._check(self._L.mag_assemble_geometric(self._h, sid, member, _p(val, C.c_double), MAG_MEM_HOST))
+        return val
+
     # -- transient dynamics: Newmark time stepping of the uploaded part ----------------------------------
     TRANSIENT_INFO = ("steps", "cg_kernel", "preconditioner", "cg_iterations", "max_step_iterations", "snapshots_kept", "resumed", "converged")
 

@@ -7,13 +7,16 @@
 //   * MSH-4 ASCII           mesher.rs:536-704   + check_ccw with its `< 1.0` quirk (mesher.rs:522-526)
 //   * nodes.csv/elements.csv post_processor.rs:18-83, floats as Rust's `{}` prints them
 // Usage: magnetite_gpu <input.json> <mesh.msh> [--nodes nodes.csv] [--elements elements.csv] [--dry-run] [--rel TOL]
-//                      [--stress-recovery] [--modal P --density RHO] [--adapt R [--refine-fraction T] [--refine-split 1|3]]
+//                      [--stress-recovery] [--modal P --density RHO] [--buckling P [--subspace Q]] [--adapt R [--refine-fraction T] [--refine-split 1|3]]
 //                      [--transient STEPS --dt DT --density RHO [--rayleigh A,E] [--probe DOF]... [--kinematics linear|tl [--newton-tol T]]]
 //                      [--explicit STEPS --density RHO [--dt DT | --dt-scale S] [--rayleigh A,E] [--probe DOF]... [--record-every K]
 //                       [--kinematics linear|tl]]
 //                      [--nonlinear INCREMENTS [--newton-tol T] [--line-search H] [--probe DOF]...]
 //   --dry-run  stop before the solver and print what was parsed (no GPU needed)
 //   --rel TOL  stop CG on relative residual TOL instead of the reference's absolute 1e-4
+//   --buckling P [--subspace Q]  after the linear solve, also print "info: buckling mode k load factor L residual R" for the P load
+//              factors of smallest magnitude under the input's own loads (negative: buckling under the reversed load) and write
+//              buckling_modes.csv (id,ux1,uy1,...,uxP,uyP) next to nodes.csv -- solver::buckling
 //   --modal P --density RHO  also print "info: mode k frequency F Hz residual R" for the P lowest modes and write modes.csv
 //              (id,ux1,uy1,...,uxP,uyP) next to nodes.csv -- solver::modal; the input JSON has no density, hence the flag
 //   --transient STEPS --dt DT --density RHO  also run STEPS steps of Newmark's method from rest under the loads applied at t = 0
@@ -385,24 +388,35 @@ std::string modes_name(const std::string &nodes_output)
     return (slash == std::string::npos ? std::string() : nodes_output.substr(0, slash + 1)) + "modes.csv";
 }
 
-// the shapes of solver::modal, a row per node, floats as csv_output prints them
-void modes_output(const Modes &m, size_t num_nodes, const std::string &path)
+// "dir/nodes.csv" -> "dir/buckling_modes.csv"
+std::string buckling_modes_name(const std::string &nodes_output)
+{
+    const size_t slash = nodes_output.find_last_of('/');
+    return (slash == std::string::npos ? std::string() : nodes_output.substr(0, slash + 1)) + "buckling_modes.csv";
+}
+
+// P shapes of solver::modal or solver::buckling, a row per node, floats as csv_output prints them
+void shapes_output(const std::vector<double> &shapes, size_t P, size_t num_nodes, const std::string &path, const char *what)
 {
     std::FILE *mf = std::fopen(path.c_str(), "w");
-    if (!mf) die({MagnetiteError::Solver, "Failed to create modes.csv: " + path});
-    const size_t P = m.lambda.size();
+    if (!mf) die({MagnetiteError::Solver, "Failed to create " + path});
     std::fputs("id", mf);
     for (size_t k = 1; k <= P; ++k) std::fprintf(mf, ",ux%zu,uy%zu", k, k);
     std::fputs("\n", mf);
     for (size_t i = 0; i < num_nodes; ++i) {
         std::fprintf(mf, "%zu", i);
         for (size_t k = 0; k < P; ++k)
-            std::fprintf(mf, ",%s,%s", rust_display(m.shapes[k * 2 * num_nodes + 2 * i]).c_str(),
-                         rust_display(m.shapes[k * 2 * num_nodes + 2 * i + 1]).c_str());
+            std::fprintf(mf, ",%s,%s", rust_display(shapes[k * 2 * num_nodes + 2 * i]).c_str(),
+                         rust_display(shapes[k * 2 * num_nodes + 2 * i + 1]).c_str());
         std::fputs("\n", mf);
     }
     std::fclose(mf);
-    std::printf("info: wrote mode shapes to %s\n", path.c_str());
+    std::printf("info: wrote %s to %s\n", what, path.c_str());
+}
+
+void modes_output(const Modes &m, size_t num_nodes, const std::string &path)
+{
+    shapes_output(m.shapes, m.lambda.size(), num_nodes, path, "mode shapes");
 }
 
 // "dir/nodes.csv" -> "dir/history.csv"
@@ -498,7 +512,7 @@ int main(int argc, char **argv)
 {
     std::string input, mesh, nodes_out = "nodes.csv", elements_out = "elements.csv";
     bool dry = false, recover = false;
-    int modal_modes = 0, adapt = 0, refine_split = 1, topopt = 0, penal = 3, filter_passes = 1, field_cg = 0, transient_steps = 0;
+    int modal_modes = 0, buckling_modes = 0, buckling_subspace = 0, adapt = 0, refine_split = 1, topopt = 0, penal = 3, filter_passes = 1, field_cg = 0, transient_steps = 0;
     double rel = 0.0, density = 0.0, refine_fraction = 0.2, volume_fraction = 0.5, dt = 0.0, rayleigh_mass = 0.0, rayleigh_stiffness = 0.0;
     bool transient = false, explicit_run = false;
     int nonlinear = -1, line_search = 0;
@@ -512,6 +526,8 @@ int main(int argc, char **argv)
         if (a == "--dry-run") dry = true;
         else if (a == "--stress-recovery") recover = true;
         else if (a == "--modal" && i + 1 < argc) modal_modes = std::atoi(argv[++i]);
+        else if (a == "--buckling" && i + 1 < argc) buckling_modes = std::atoi(argv[++i]);
+        else if (a == "--subspace" && i + 1 < argc) buckling_subspace = std::atoi(argv[++i]);
         else if (a == "--density" && i + 1 < argc) density = std::atof(argv[++i]);
         else if (a == "--transient" && i + 1 < argc) transient = true, transient_steps = std::atoi(argv[++i]);
         else if (a == "--dt" && i + 1 < argc) dt = std::atof(argv[++i]);
@@ -550,6 +566,8 @@ int main(int argc, char **argv)
         return 2;
     }
     if (modal_modes < 0 || (modal_modes > 0 && !(density > 0.0))) die({MagnetiteError::Input, "--modal P needs P >= 1 and --density RHO > 0"});
+    if (buckling_modes < 0 || buckling_subspace < 0 || (buckling_subspace > 0 && buckling_modes < 1))
+        die({MagnetiteError::Input, "--buckling P needs P >= 1, and --subspace Q goes with it"});
     if (transient && (transient_steps < 1 || !(dt > 0.0) || !(density > 0.0) || rayleigh_mass < 0.0 || rayleigh_stiffness < 0.0))
         die({MagnetiteError::Input, "--transient STEPS needs STEPS >= 1, --dt DT > 0, --density RHO > 0 and --rayleigh A,E >= 0"});
     if (explicit_run && (explicit_steps < 1 || dt < 0.0 || dt_scale < 0.0 || (dt > 0.0 && dt_scale > 0.0) || !(density > 0.0) || rayleigh_mass < 0.0 ||
@@ -640,7 +658,7 @@ int main(int argc, char **argv)
         opt.stop_mode = MAG_STOP_REL;
         opt.tol = rel;
     }
-    std::vector<Node> posed = recover || modal_modes > 0 || topopt > 0 || transient || explicit_run || nonlinear_run ? nodes : std::vector<Node>();  // (run() fills every value in)
+    std::vector<Node> posed = recover || modal_modes > 0 || buckling_modes > 0 || topopt > 0 || transient || explicit_run || nonlinear_run ? nodes : std::vector<Node>();  // (run() fills every value in)
     if (adapt > 0) {
         RefineSpec spec;
         spec.theta = refine_fraction;
@@ -711,6 +729,23 @@ int main(int argc, char **argv)
             std::printf("info: mode %zu frequency %s Hz residual %s\n", k + 1, rust_display(modes.frequency[k]).c_str(),
                         rust_display(modes.residual[k]).c_str());
         modes_output(modes, posed.size(), modes_name(nodes_out));
+    }
+    if (buckling_modes > 0) {
+        // The pass needs every element counter-clockwise, as the modal analysis does: the elements go in by their true sign.
+        std::vector<Element> ccw = elements;
+        for (Element &e : ccw)
+            if (solver::compute_element_area(e, posed) < 0.0) std::swap(e.nodes[0], e.nodes[2]);
+        opt.verbose = 0;
+        BucklingSpec spec;
+        spec.modes = buckling_modes;
+        spec.subspace = buckling_subspace;
+        BucklingModes bm;
+        if (Result err = solver::buckling(posed, ccw, meta, spec, bm, &opt)) die(*err);
+        for (size_t k = 0; k < bm.load_factor.size(); ++k)
+            std::printf("info: buckling mode %zu load factor %s residual %s\n", k + 1, rust_display(bm.load_factor[k]).c_str(),
+                        rust_display(bm.residual[k]).c_str());
+        if (!bm.converged) std::printf("warning: buckling: stopped at the cap of outer steps above the tolerance\n");
+        shapes_output(bm.shapes, bm.load_factor.size(), posed.size(), buckling_modes_name(nodes_out), "buckling shapes");
     }
     if (transient_tl) {
         // The pass needs every element counter-clockwise, as the modal analysis does: the elements go in by their true sign.
