@@ -44,8 +44,8 @@ extern "C" {
                              variants (mag_set_variants ... mag_get_variants_info), sensitivities (mag_run_sensitivities,
                              mag_download_sensitivity), adjoint sensitivities (mag_run_adjoint ... mag_get_adjoint_info) and
                              mesh refinement (mag_run_refine ... mag_upload_refined), the element stiffness field
-                             (mag_set_element_scale) and the density design update (mag_design_init ... mag_download_design)
-                             likewise */
+                             (mag_set_element_scale), the density design update (mag_design_init ... mag_download_design)
+                             and the material law (mag_set_material_law, mag_get_material_law) likewise */
 
 /* solver.rs:17-19 */
 #define MAG_DOF 2
@@ -785,7 +785,7 @@ int mag_assemble_effective(mag_ctx *ctx, double c_K, double c_M, double density,
  *   A step is ONE launch where the context has tile-local tables, and reads no matrix: the ring walk of the matrix-free operator
  *     with the force above per triangle.  A node's sum runs in its ring's order, which depends on tile_nodes: the same bits for
  *     every grid, a repeat and a resumed run, not across tile sizes.  Without the tables a step is four launches (info[2] = 0).
- *   Out of scope: other materials (neo-Hooke, plasticity); stiffness-proportional damping; an updated step bound during the run;
+ *   Out of scope: plasticity, other hyperelastic laws; stiffness-proportional damping; an updated step bound during the run;
  *     follower loads; contact; fields, variants and ranks; several steps per launch.  (The implicit pass: mag_run_transient_tl.)
  * mag_internal_force: f_out = f_int(u) for all 2N DOFs in caller numbering (u, f_out: 2N doubles in `memory`), scalars_out[0] =
  *   W(u), scalars_out[1] = 1 if some element has det F <= 0, else 0 (written on the host).  The residual of a caller's own
@@ -854,7 +854,7 @@ int mag_internal_force(mag_ctx *ctx, const double *u, double *f_out, double scal
  *   a negative max_newton, line_search, num_probes, a newton_tol or cg_tol negative or not finite, cg outside 0..4, num_probes > 0
  *   with NULL probes, a `memory` outside enum mag_memory, more than one rank; MAG_ERR_STATE for no upload, an element stiffness
  *   field, assemble_csr = 0 or precision = 1.  After the first device work: an element of signed area <= 0, a probe outside [0, 2N).
- * Out of scope: arc-length and limit points; follower loads; other materials; a warm-started or inexact inner solve; the on-chip
+ * Out of scope: arc-length and limit points; follower loads; plasticity, other hyperelastic laws; a warm-started or inexact inner solve; the on-chip
  *   CG on K_T; a matrix-free tangent operator; fields, variants and ranks.  (The implicit dynamic pass on the tangent:
  *   mag_run_transient_tl below.) */
 typedef struct mag_newton_options {
@@ -932,7 +932,7 @@ int mag_assemble_tangent(mag_ctx *ctx, const double *u, double *values_out, int3
  *   finite, a negative max_newton, cg outside 0..4; then mag_run_transient's for the records, the context and the resume rule;
  *   after the first device work an element of signed area <= 0, a probe outside [0, 2N), records beyond device memory.
  * Out of scope: a line search; modified or quasi-Newton; a warm-started or inexact inner solve; stiffness-proportional damping;
- *   HHT / generalised-alpha; adaptive dt; time-varying supports; follower loads; other materials; the on-chip CG on A_T; fields,
+ *   HHT / generalised-alpha; adaptive dt; time-varying supports; follower loads; plasticity, other hyperelastic laws; the on-chip CG on A_T; fields,
  *   variants and ranks. */
 typedef struct mag_transient_tl_options {
     int32_t steps, resume, lumped, cg, energies, snapshot_every, num_probes, memory, max_newton, reserved;
@@ -953,6 +953,43 @@ int mag_download_transient_tl(mag_ctx *ctx, mag_transient_tl_result *out);
 int mag_get_transient_tl_info(const mag_ctx *ctx, int32_t info[8]);
 int mag_assemble_effective_tangent(mag_ctx *ctx, const double *u, double c_K, double c_M, double density, int32_t lumped, double *values_out,
                                    int32_t memory);
+
+/* ---- the material of the total-Lagrangian passes: St. Venant-Kirchhoff or compressible neo-Hooke -----------------
+ * mag_set_material_law: the law that mag_run_explicit with kinematics = MAG_KIN_TOTAL_LAGRANGIAN, mag_internal_force,
+ *   mag_run_newton, mag_assemble_tangent, mag_run_transient_tl and mag_assemble_effective_tangent read -- those six and nothing
+ *   else.  It is context state like an option: MAG_LAW_SVK (0) by default, kept across mag_upload and mag_upload_refined, and
+ *   setting it changes no stored result of any pass.  mag_get_material_law reads it back.  MAG_LAW_SVK is S = D E above, bit for
+ *   bit: right for large rotations at strains of a few percent, wrong once a part is squeezed (its nominal stress in uniaxial
+ *   compression peaks at stretch 0.577 and its tangent is indefinite beyond).
+ * MAG_LAW_NEO_HOOKE: compressible neo-Hooke with the plane-stress condition enforced per element, on the upload's two constants
+ *   mu = E / (2 (1 + nu)),  Lambda = E nu / ((1 + nu)(1 - 2 nu)).  With H, F = I + H, Exx, Eyy, Gxy, 2A, g_k and V = A t as above:
+ *     energy       W = mu/2 (tr C + C33 - 3) - mu ln J + Lambda/2 (ln J)^2,   C = F^T F,  j2 = det C,  J^2 = j2 C33
+ *     S33 = 0      mu (C33 - 1) + Lambda ln J = 0, a scalar equation for d = C33 - 1:
+ *                  g(d) = mu d + Lambda/2 (log1p(j2m1) + log1p(d)) = 0,   j2m1 = j2 - 1 = 2 (Exx + Eyy) + 4 Exx Eyy - Gxy^2
+ *                  g is increasing and concave (nu >= 0); Newton's method from d0 = min(0, -j2m1 / j2) starts at g <= 0 and rises
+ *                  monotonically to the root: a counted loop, while the iterate still increases, of at most 40 iterations (at
+ *                  most 15 over j2 = 1e-6 .. 1e6 and nu up to 0.499).  For nu < 0 g is convex and the iterates fall to the root
+ *                  after the first step; the loop then runs while they fall.  u = 0 gives d = 0 exactly, nu = 0 gives d = 0 always.
+ *     stress       S = mu (I - C33 C^-1), the Sxx, Syy, Sxy of the element rows
+ *     force        on corner k:  V mu (F g_k - C33 h_k),  h_k = F^-T g_k  (= V F S g_k; exactly zero at u = 0)
+ *     tangent      2 dS/dC = 2 mu C33 (kappa C^-1 (x) C^-1 + I_{C^-1}),  kappa = Lambda / (2 mu C33 + Lambda);  the block of corners
+ *                  (k, l):  K_T[k, l] = V (mu (g_k . g_l) I + mu C33 (2 kappa h_k h_l^T + h_l h_k^T));  K_T(0) = K
+ *     W_e          V W, from 2 (Exx + Eyy), d, log1p(j2m1) and log1p(d)
+ *   A rigid motion gives zero force; the linearisation at u = 0 is K.
+ *   An element with det F <= 0 raises the inverted flags exactly as under MAG_LAW_SVK, and nothing else is special-cased: det F < 0
+ *     gives finite numbers from j2 = (det F)^2; det F = 0 gives non-finite ones, which the passes' existing checks catch (the line
+ *     search rejects an inverted trial state; the finite checks on the final state and in the CG do the rest).
+ *   rayleigh_stiffness, dt_bound and every other rule of the six entry points stay as they are.  dt_bound remains the linear bound at
+ *     the reference configuration: neo-Hooke stiffens under compression as well as under tension, and the caller lowers dt_scale
+ *     for either.  The three stepping passes may resume each other's state across laws (the state is u, v, a): a resumed run uses
+ *     the law it finds.  A step stays one launch and a tangent one launch; every sum keeps its fixed order.
+ * Errors: a law that is neither value: MAG_ERR_BAD_ARGS, the law stays.  Under MAG_LAW_NEO_HOOKE each of the six entry points
+ *   refuses an upload with nu >= 0.5 or nu <= -1 with MAG_ERR_BAD_ARGS before any device work (the message names nu).
+ * Out of scope: plasticity and other hyperelastic laws; the incompressible limit; the thickness stretch as an output; a step
+ *   bound that follows the state. */
+enum { MAG_LAW_SVK = 0, MAG_LAW_NEO_HOOKE = 1 };
+int mag_set_material_law(mag_ctx *ctx, int32_t law);
+int mag_get_material_law(const mag_ctx *ctx, int32_t *law);
 
 /* ---- adaptive mesh refinement: longest-edge bisection with conformity closure (Rivara) of the uploaded mesh, on the device ----
  * What acts on the ZZ indicator of mag_run_stress: solve -> mag_run_stress -> mag_run_refine -> mag_upload_refined -> solve, the

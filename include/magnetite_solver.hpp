@@ -989,6 +989,24 @@ inline Result transient(const std::vector<Node> &nodes, const std::vector<Elemen
     return std::nullopt;
 }
 
+// The material law of the total-Lagrangian functions below (run_explicit with MAG_KIN_TOTAL_LAGRANGIAN, internal_force, run_newton,
+// assemble_tangent, transient_tl, assemble_effective_tangent): every context they create is given it (mag_set_material_law).
+// MAG_LAW_SVK by default; MAG_LAW_NEO_HOOKE: compressible neo-Hooke, plane stress enforced per element (include/magnetite_hip.h).
+namespace detail {
+inline std::int32_t &law_slot()
+{
+    static std::int32_t law = MAG_LAW_SVK;
+    return law;
+}
+} // namespace detail
+inline std::int32_t material_law() { return detail::law_slot(); }
+inline Result set_material_law(std::int32_t law)
+{
+    if (law != MAG_LAW_SVK && law != MAG_LAW_NEO_HOOKE) return detail::solver_error("the material law is neither MAG_LAW_SVK nor MAG_LAW_NEO_HOOKE");
+    detail::law_slot() = law;
+    return std::nullopt;
+}
+
 // Explicit dynamics (mag_run_explicit) of the part: spec.steps central-difference steps on the lumped mass, one fused launch a
 // step; supports, loads and the start as solver::transient.  (`explicit` is a keyword: hence the names.)
 inline Result run_explicit(const std::vector<Node> &nodes, const std::vector<Element> &elements, const ModelMetadata &model_metadata,
@@ -1008,6 +1026,7 @@ inline Result run_explicit(const std::vector<Node> &nodes, const std::vector<Ele
     if (!ctx) return detail::solver_error("mag_create failed");
     const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
     if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    if (mag_set_material_law(ctx, material_law()) != MAG_OK) return detail::fail_and_destroy(ctx);
     mag_explicit_options o;
     mag_default_explicit_options(&o);
     o.steps = spec.steps;
@@ -1084,6 +1103,7 @@ inline Result internal_force(const std::vector<Node> &nodes, const std::vector<E
     if (!ctx) return detail::solver_error("mag_create failed");
     const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
     if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    if (mag_set_material_law(ctx, material_law()) != MAG_OK) return detail::fail_and_destroy(ctx);
     out = InternalForce{};
     out.f.resize(2 * N);
     double scalars[2] = {};
@@ -1112,6 +1132,7 @@ inline Result run_newton(const std::vector<Node> &nodes, const std::vector<Eleme
     if (!ctx) return detail::solver_error("mag_create failed");
     const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
     if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    if (mag_set_material_law(ctx, material_law()) != MAG_OK) return detail::fail_and_destroy(ctx);
     mag_newton_options o;
     mag_default_newton_options(&o);
     o.increments = spec.increments;
@@ -1184,6 +1205,7 @@ inline Result assemble_tangent(const std::vector<Node> &nodes, const std::vector
     if (!ctx) return detail::solver_error("mag_create failed");
     const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
     if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    if (mag_set_material_law(ctx, material_law()) != MAG_OK) return detail::fail_and_destroy(ctx);
     std::int64_t nnz = 0;
     if (mag_assemble_csr(ctx, &nnz, nullptr, nullptr, nullptr) != MAG_OK) return detail::fail_and_destroy(ctx);
     rowptr.resize(2 * N + 1);
@@ -1216,6 +1238,7 @@ inline Result transient_tl(const std::vector<Node> &nodes, const std::vector<Ele
     if (!ctx) return detail::solver_error("mag_create failed");
     const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
     if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    if (mag_set_material_law(ctx, material_law()) != MAG_OK) return detail::fail_and_destroy(ctx);
     mag_transient_tl_options o;
     mag_default_transient_tl_options(&o);
     o.steps = spec.steps;
@@ -1316,6 +1339,7 @@ inline Result assemble_effective_tangent(const std::vector<Node> &nodes, const s
     if (!ctx) return detail::solver_error("mag_create failed");
     const mag_problem p = detail::host_problem(xy, conn, u_known, u_in.data(), f_in.data(), model_metadata);
     if (mag_upload(ctx, &p) != MAG_OK) return detail::fail_and_destroy(ctx);
+    if (mag_set_material_law(ctx, material_law()) != MAG_OK) return detail::fail_and_destroy(ctx);
     std::int64_t nnz = 0;
     if (mag_assemble_csr(ctx, &nnz, nullptr, nullptr, nullptr) != MAG_OK) return detail::fail_and_destroy(ctx);
     rowptr.resize(2 * N + 1);

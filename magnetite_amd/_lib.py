@@ -21,6 +21,7 @@ MAG_FIELD_CG_PLAIN, MAG_FIELD_CG_JACOBI, MAG_FIELD_CG_BLOCK_JACOBI = 1, 2, 3
 MAG_TERM_NONE, MAG_TERM_TARGET_COST, MAG_TERM_MAX_ITERS, MAG_TERM_BREAKDOWN = 0, 1, 2, 3
 MAG_MEM_HOST, MAG_MEM_DEVICE = 0, 1
 MAG_KIN_LINEAR, MAG_KIN_TOTAL_LAGRANGIAN = 0, 1
+MAG_LAW_SVK, MAG_LAW_NEO_HOOKE = 0, 1
 MAG_SET_RUN, MAG_SET_CASES, MAG_SET_VARIANTS = 0, 1, 2
 MAG_OBJ_DISP_LSQ, MAG_OBJ_STRESS_PNORM = 0, 1
 MAG_REFINE_MARKS, MAG_REFINE_MAX_FRACTION, MAG_REFINE_TOP_FRACTION = 0, 1, 2
@@ -48,6 +49,7 @@ SYMBOLS = [
     "mag_default_newton_options", "mag_run_newton", "mag_download_newton", "mag_get_newton_info", "mag_assemble_tangent",
     "mag_default_transient_tl_options", "mag_run_transient_tl", "mag_download_transient_tl", "mag_get_transient_tl_info",
     "mag_assemble_effective_tangent",
+    "mag_set_material_law", "mag_get_material_law",
     "mag_run_refine", "mag_get_refine_info", "mag_download_refine", "mag_upload_refined",
     "mag_set_element_scale", "mag_design_init", "mag_design_step", "mag_get_design_info", "mag_download_design",
     "mag_comm_get_unique_id", "mag_comm_init_rccl", "mag_comm_query", "mag_comm_init_callback", "mag_comm_set_window", "mag_comm_inbox_create", "mag_comm_inbox_open",
@@ -332,6 +334,9 @@ def lib():
         L.mag_download_transient_tl.argtypes = [vp, C.POINTER(TransientTlResult)]
         L.mag_get_transient_tl_info.argtypes = [vp, ip]
         L.mag_assemble_effective_tangent.argtypes = [vp, dp, C.c_double, C.c_double, C.c_double, C.c_int32, dp, C.c_int32]
+    if hasattr(L, "mag_set_material_law"):  # (likewise: scripts/hyper_probe.py)
+        L.mag_set_material_law.argtypes = [vp, C.c_int32]
+        L.mag_get_material_law.argtypes = [vp, ip]
     if hasattr(L, "mag_run_refine"):  # (likewise: scripts/refine_probe.py)
         L.mag_run_refine.argtypes = [vp, C.POINTER(RefineOptions)]
         L.mag_get_refine_info.argtypes = [vp, C.POINTER(C.c_int64)]

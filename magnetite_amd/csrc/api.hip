@@ -179,6 +179,7 @@ struct mag_ctx {
     // problem (caller numbering)
     int64_t N = 0, E = 0;
     double youngs = 0, nu = 0, thick = 0;
+    int32_t law = MAG_LAW_SVK; // mag_set_material_law: the material of the total-Lagrangian passes; kept across uploads
     bool have_problem = false, have_order = false, have_csr = false, have_run = false;
     // (perm, the incidence lists, the tiles and their halo lists hang on the connectivity and the uploaded coordinates only: they
     // outlive have_order, which a variants run drops because xyP and K may be a variant's)
@@ -621,6 +622,26 @@ void set_material(const mag_ctx *ctx, Params &P)
     P.c0 = (F)(ctx->youngs * ctx->thick / (2.0 * (1.0 - ctx->nu * ctx->nu)));
     P.nu = (F)ctx->nu;
     P.h = (F)((1.0 - ctx->nu) / 2.0);
+}
+
+// the material constants of the total-Lagrangian kernels (explicit_tl.h) under the context's law: St. Venant-Kirchhoff takes
+// set_material's; neo-Hooke c0 = mu t / 2, nu = Lambda / mu, h unread
+template <class Params>
+void set_tl_material(const mag_ctx *ctx, Params &P)
+{
+    set_material(ctx, P);
+    P.law = ctx->law;
+    if (ctx->law == MAG_LAW_NEO_HOOKE) {
+        P.c0 = ctx->youngs * ctx->thick / (4.0 * (1.0 + ctx->nu));
+        P.nu = 2.0 * ctx->nu / (1.0 - 2.0 * ctx->nu);
+        P.h = 0.0;
+    }
+}
+
+// the factor of the element rows' stresses (newton_elements): E / (1 - nu^2), under neo-Hooke mu
+double tl_stress_scale(const mag_ctx *ctx)
+{
+    return ctx->law == MAG_LAW_NEO_HOOKE ? ctx->youngs / (2.0 * (1.0 + ctx->nu)) : ctx->youngs / (1.0 - ctx->nu * ctx->nu);
 }
 
 // ---- symbolic phase 1: Hilbert order, incidence lists, per-tile ELL table ----
@@ -4834,6 +4855,14 @@ int transient_refused(mag_ctx *ctx, const char *fn)
     return MAG_OK;
 }
 
+// the uploads the context's material law does not cover, before any device work (the six total-Lagrangian entry points)
+int law_refused(mag_ctx *ctx, const char *fn)
+{
+    if (ctx->law == MAG_LAW_NEO_HOOKE && !(ctx->nu < 0.5 && ctx->nu > -1.0))
+        return fail(ctx, MAG_ERR_BAD_ARGS, "%s: nu = %g is outside (-1, 0.5): MAG_LAW_NEO_HOOKE needs a compressible material", fn, ctx->nu);
+    return MAG_OK;
+}
+
 magk::Pattern transient_pattern(const mag_ctx *ctx) { return {ctx->bptr.as<int32_t>(), ctx->bcol.as<int32_t>(), ctx->N, ctx->nb}; }
 
 // K assembled, and M in its pattern (tr_mval); room for A (tr_aval)
@@ -5080,7 +5109,7 @@ magk::TlMesh tl_mesh(const mag_ctx *ctx)
     m.N = ctx->N, m.E = ctx->E;
     m.perm = ctx->perm.as<uint32_t>(), m.inc_off = ctx->inc_off.as<int32_t>(), m.inc = ctx->inc.as<uint32_t>();
     m.conn = ctx->conn.as<int32_t>(), m.xy = ctx->xy.as<double2>();
-    set_material(ctx, m);
+    set_tl_material(ctx, m);
     return m;
 }
 
@@ -5396,6 +5425,22 @@ int explicit_bounds(mag_ctx *ctx, double eta, double out[4])
 
 } // namespace
 
+int mag_set_material_law(mag_ctx *ctx, int32_t law)
+{
+    if (!ctx) return MAG_ERR_BAD_ARGS;
+    if (law != MAG_LAW_SVK && law != MAG_LAW_NEO_HOOKE)
+        return fail(ctx, MAG_ERR_BAD_ARGS, "mag_set_material_law: law = %d is neither MAG_LAW_SVK nor MAG_LAW_NEO_HOOKE", (int)law);
+    ctx->law = law; // (read by the total-Lagrangian entry points alone: no stored result changes)
+    return MAG_OK;
+}
+
+int mag_get_material_law(const mag_ctx *ctx, int32_t *law)
+{
+    if (!ctx || !law) return MAG_ERR_BAD_ARGS;
+    *law = ctx->law;
+    return MAG_OK;
+}
+
 void mag_default_explicit_options(mag_explicit_options *o)
 {
     if (!o) return;
@@ -5435,6 +5480,8 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
     if (o->record_every < 0) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: record_every = %d is negative", fn, (int)o->record_every);
     const StepOptions so = {o->steps, o->snapshot_every, o->num_probes, o->probes, o->memory, o->resume, o->amplitude, o->u0, o->v0};
     if (int rc = step_args_tail(ctx, fn, so)) return rc;
+    if (o->kinematics == MAG_KIN_TOTAL_LAGRANGIAN)
+        if (int rc = law_refused(ctx, fn)) return rc;
 
     const bool resume = o->resume != 0, energies = o->energies != 0, tl = o->kinematics == MAG_KIN_TOTAL_LAGRANGIAN;
     const int32_t steps = o->steps, np = o->num_probes, se = o->snapshot_every, re = o->record_every > 0 ? o->record_every : 1;
@@ -5513,10 +5560,10 @@ int mag_run_explicit(mag_ctx *ctx, const mag_explicit_options *o)
         Q.xyP = ctx->xyP.as<double2>(), Q.halo_xy = ctx->halo_xy.as<double2>();
         Q.tile_deg = ctx->tile_rdeg.as<int32_t>(), Q.tile_off = ctx->tile_off.as<int64_t>(), Q.ell16 = ctx->ell.as<uint32_t>();
         Q.tile_hoff = ctx->tile_hoff.as<int32_t>();
-        set_material(ctx, Q);
+        set_tl_material(ctx, Q);
         Q.inverted = d_inverted;
     }
-    if (fused) grid = tl ? magk::explicit_tl_grid(ctx->B, ctx->cap, ctx->T) : magk::explicit_grid(ctx->B, ctx->cap, ctx->T);
+    if (fused) grid = tl ? magk::explicit_tl_grid(ctx->B, ctx->cap, ctx->T, ctx->law) : magk::explicit_grid(ctx->B, ctx->cap, ctx->T);
     long long launches = 0;
     bool expanded = true; // (tr_u, tr_v, tr_a hold the current state)
     // one step of h (the start: h = 0) under amplitude[amp_at]
@@ -5624,6 +5671,7 @@ int mag_internal_force(mag_ctx *ctx, const double *u, double *f_out, double scal
     if (!scalars_out) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null scalars_out", fn);
     if (int rc = memory_refused(ctx, memory, fn)) return rc;
     if (int rc = transient_refused(ctx, fn)) return rc;
+    if (int rc = law_refused(ctx, fn)) return rc;
     if (int rc = enter(ctx)) return rc;
     if (int rc = ensure_order(ctx)) return rc;
     const size_t vb = 16 * (size_t)ctx->N;
@@ -5659,6 +5707,7 @@ int mag_assemble_tangent(mag_ctx *ctx, const double *u, double *values_out, int3
     if (!values_out) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: null values_out", fn);
     if (int rc = memory_refused(ctx, memory, fn)) return rc;
     if (int rc = transient_refused(ctx, fn)) return rc;
+    if (int rc = law_refused(ctx, fn)) return rc;
     if (int rc = enter(ctx)) return rc;
     if (int rc = ensure_csr(ctx)) return rc;
     const size_t ab = 32 * (size_t)ctx->nb;
@@ -5683,6 +5732,7 @@ int mag_run_newton(mag_ctx *ctx, const mag_newton_options *o)
     if (o->cg < 0 || o->cg > 4) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: cg = %d outside 0..4", fn, (int)o->cg);
     const StepOptions so = {o->increments, 0, o->num_probes, o->probes, o->memory, 0, nullptr, o->u0, nullptr};
     if (int rc = step_args_tail(ctx, fn, so)) return rc;
+    if (int rc = law_refused(ctx, fn)) return rc;
 
     const int32_t incs = o->increments, np = o->num_probes, H = o->line_search;
     const int32_t cap = o->max_newton > 0 ? o->max_newton : 25;
@@ -5848,7 +5898,7 @@ int mag_run_newton(mag_ctx *ctx, const mag_newton_options *o)
     int32_t *d_flag = (int32_t *)(d_scal + 1);
     magk::tl_force(mesh, d_uc, d_f, d_flag, d_part, nullptr, s);
     magk::tl_reactions(d_known, d_fin, d_load, done, d_f, n2, ctx->nt_fout.as<double>(), s);
-    magk::newton_elements(mesh, d_uc, ctx->youngs / (1.0 - ctx->nu * ctx->nu), ctx->nt_elem.as<double>(), d_flag, s);
+    magk::newton_elements(mesh, d_uc, tl_stress_scale(ctx), ctx->nt_elem.as<double>(), d_flag, s);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
 
@@ -5941,6 +5991,7 @@ int mag_assemble_effective_tangent(mag_ctx *ctx, const double *u, double c_K, do
     if (int rc = need_pos(ctx, fn, {{"density", density}})) return rc;
     if (int rc = memory_refused(ctx, memory, fn)) return rc;
     if (int rc = transient_refused(ctx, fn)) return rc;
+    if (int rc = law_refused(ctx, fn)) return rc;
     if (int rc = enter(ctx)) return rc;
     if (int rc = transient_matrices(ctx, density, lumped)) return rc;
     const size_t ab = 32 * (size_t)ctx->nb;
@@ -5971,6 +6022,7 @@ int mag_run_transient_tl(mag_ctx *ctx, const mag_transient_tl_options *o)
     if (o->cg < 0 || o->cg > 4) return fail(ctx, MAG_ERR_BAD_ARGS, "%s: cg = %d outside 0..4", fn, (int)o->cg);
     const StepOptions so = {o->steps, o->snapshot_every, o->num_probes, o->probes, o->memory, o->resume, o->amplitude, o->u0, o->v0};
     if (int rc = step_args_tail(ctx, fn, so)) return rc;
+    if (int rc = law_refused(ctx, fn)) return rc;
 
     const bool resume = o->resume != 0, energies = o->energies != 0;
     const int32_t steps = o->steps, np = o->num_probes, se = o->snapshot_every;
@@ -6136,7 +6188,7 @@ int mag_run_transient_tl(mag_ctx *ctx, const mag_transient_tl_options *o)
     int32_t *d_flag = (int32_t *)(d_scal + 1);
     magk::tl_force(mesh, st.u, d_fint, d_flag, nullptr, nullptr, s);
     magk::tl_dynamic_reactions(pat, d_m, st.known, d_f, d_amp, done, d_fint, st.a, st.v, alpha, ctx->tr_f.as<double>(), s);
-    magk::newton_elements(mesh, st.u, ctx->youngs / (1.0 - ctx->nu * ctx->nu), ctx->tt_elem.as<double>(), d_flag, s);
+    magk::newton_elements(mesh, st.u, tl_stress_scale(ctx), ctx->tt_elem.as<double>(), d_flag, s);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
 

@@ -15,7 +15,7 @@ constexpr int kTlSlotRegs = 5; // ring words kept in registers, as cg.hip's kSlo
 // Persistent over tiles, one lane per owned node.  A launch reads P.f.in and writes P.f.out, so a tile never sees a neighbour's new
 // state; a halo node's predictor is recomputed from the same inputs as its owner's: the same bits.  LDS: cap * 32 bytes (the
 // images of the reference coordinates and of ut).
-template <int B>
+template <int B, int LAW>
 __global__ void __launch_bounds__(B) k_explicit_tl_step(const ExplicitTlParams P)
 {
     extern __shared__ __attribute__((aligned(16))) double2 s_tl[];
@@ -63,7 +63,7 @@ __global__ void __launch_bounds__(B) k_explicit_tl_step(const ExplicitTlParams P
         {
             double2 rd = ca, ru = ut; // the previous ring entry, relative to this node; every fan starts with the break bit
             auto tri = [&](const double2 db, const double2 ub, const double2 dc, const double2 uc) {
-                fan_force_tl(db, ub, dc, uc, c0, nu, h, fx, fy, inverted);
+                fan_force_tl<LAW>(db, ub, dc, uc, c0, nu, h, fx, fy, inverted);
             };
 #pragma unroll
             for (int k = 0; k < kTlSlotRegs; ++k) ring_word(w[k], s_xy, s_u, ca, ut, rd, ru, tri);
@@ -77,23 +77,29 @@ __global__ void __launch_bounds__(B) k_explicit_tl_step(const ExplicitTlParams P
 static size_t explicit_tl_lds(int32_t cap) { return (size_t)cap * 32; }
 
 typedef void (*explicit_tl_fn)(const ExplicitTlParams);
-static explicit_tl_fn explicit_tl_pick(int32_t B)
+template <int LAW>
+static explicit_tl_fn explicit_tl_pick_b(int32_t B)
 {
-    return B == 256 ? k_explicit_tl_step<256> : (B == 1024 ? k_explicit_tl_step<1024> : k_explicit_tl_step<512>);
+    return B == 256 ? k_explicit_tl_step<256, LAW> : (B == 1024 ? k_explicit_tl_step<1024, LAW> : k_explicit_tl_step<512, LAW>);
+}
+static explicit_tl_fn explicit_tl_pick(int32_t B, int32_t law)
+{
+    return law == kLawNeoHooke ? explicit_tl_pick_b<kLawNeoHooke>(B) : explicit_tl_pick_b<kLawSvk>(B);
 }
 
-int explicit_tl_grid(int32_t B, int32_t cap, int32_t tiles)
+int explicit_tl_grid(int32_t B, int32_t cap, int32_t tiles, int32_t law)
 {
-    return step_grid((const void *)explicit_tl_pick(B), step_threads(B), explicit_tl_lds(cap), tiles);
+    return step_grid((const void *)explicit_tl_pick(B, law), step_threads(B), explicit_tl_lds(cap), tiles);
 }
 
 void explicit_tl_step(const ExplicitTlParams &P, int32_t B, int32_t grid, hipStream_t s)
 {
-    explicit_tl_pick(B)<<<grid, step_threads(B), explicit_tl_lds(P.f.cap), s>>>(P);
+    explicit_tl_pick(B, P.law)<<<grid, step_threads(B), explicit_tl_lds(P.f.cap), s>>>(P);
 }
 
 // ---- f_int(u) in caller numbering: lane g takes the node at Hilbert position g and fetches every corner through conn.
 // inc[k] = 3e + (the corner of e that is this node); the triangle is taken from that corner on, counter-clockwise
+template <int LAW>
 __global__ void __launch_bounds__(256) k_tl_force(TlMesh m, const double2 *u, double2 *f, int32_t *inverted)
 {
     const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -108,17 +114,18 @@ __global__ void __launch_bounds__(256) k_tl_force(TlMesh m, const double2 *u, do
         const int a = (int)(w - 3u * (uint32_t)e);
         const int64_t b = m.conn[3 * e + (a + 1) % 3], c = m.conn[3 * e + (a + 2) % 3];
         const double2 cb = m.xy[b], cc = m.xy[c], pb = u[b], pc = u[c];
-        fan_force_tl(make_double2(cb.x - ca.x, cb.y - ca.y), make_double2(pb.x - ua.x, pb.y - ua.y), make_double2(cc.x - ca.x, cc.y - ca.y),
-                     make_double2(pc.x - ua.x, pc.y - ua.y), m.c0, m.nu, m.h, fx, fy, inverted);
+        fan_force_tl<LAW>(make_double2(cb.x - ca.x, cb.y - ca.y), make_double2(pb.x - ua.x, pb.y - ua.y), make_double2(cc.x - ca.x, cc.y - ca.y),
+                          make_double2(pc.x - ua.x, pc.y - ua.y), m.c0, m.nu, m.h, fx, fy, inverted);
     }
     f[i] = make_double2(fx, fy);
 }
 
 // ---- W(u): stage one over the elements, stage two over the kSensBlocks partial records
+template <int LAW>
 __global__ void __launch_bounds__(256) k_tl_energy_partials(TlMesh m, const double2 *u, int32_t *inverted, double *partials)
 {
     double acc[1] = {0.0};
-    share_sum(m.E, acc, [&](int64_t e, double (&a)[1]) { a[0] += tl_element_energy(m, u, e, inverted); });
+    share_sum(m.E, acc, [&](int64_t e, double (&a)[1]) { a[0] += tl_element_energy<LAW>(m, u, e, inverted); });
     store_partials(acc, partials);
 }
 
@@ -129,9 +136,12 @@ __global__ void __launch_bounds__(256) k_tl_energy_sum(const double *partials, d
 
 void tl_force(const TlMesh &m, const double *u, double *f, int32_t *inverted, double *partials, double *energy, hipStream_t s)
 {
-    k_tl_force<<<dim3((unsigned)((m.N + 255) / 256)), 256, 0, s>>>(m, (const double2 *)u, (double2 *)f, inverted);
+    const bool neo = m.law == kLawNeoHooke;
+    (neo ? k_tl_force<kLawNeoHooke> : k_tl_force<kLawSvk>)<<<dim3((unsigned)((m.N + 255) / 256)), 256, 0, s>>>(m, (const double2 *)u, (double2 *)f,
+                                                                                                      inverted);
     if (!energy) return;
-    k_tl_energy_partials<<<dim3(kSensBlocks, 1), 256, 0, s>>>(m, (const double2 *)u, inverted, partials);
+    (neo ? k_tl_energy_partials<kLawNeoHooke> : k_tl_energy_partials<kLawSvk>)<<<dim3(kSensBlocks, 1), 256, 0, s>>>(m, (const double2 *)u, inverted,
+                                                                                                                partials);
     k_tl_energy_sum<<<dim3(1, 1), 256, 0, s>>>(partials, energy);
 }
 
@@ -167,6 +177,7 @@ void tl_reactions(const uint8_t *known, const double *f, const double *amplitude
 
 // ---- an energy row: the kinetic energy and the load's work over the 2N DOFs, the strain energy over the elements, each thread
 // its fixed share of either
+template <int LAW>
 __global__ void __launch_bounds__(256) k_tl_row_partials(TlMesh m, Pattern pat, const double *mval, const uint8_t *known, const double *u,
                                                          const double *v, const double *f, int32_t *inverted, double *partials)
 {
@@ -176,7 +187,7 @@ __global__ void __launch_bounds__(256) k_tl_row_partials(TlMesh m, Pattern pat, 
         a[0] += v[r] * (mm * v[r]);
         a[2] += known[r] ? 0.0 : f[r] * u[r];
     });
-    share_sum(m.E, acc, [&](int64_t e, double (&a)[3]) { a[1] += tl_element_energy(m, (const double2 *)u, e, inverted); });
+    share_sum(m.E, acc, [&](int64_t e, double (&a)[3]) { a[1] += tl_element_energy<LAW>(m, (const double2 *)u, e, inverted); });
     store_partials(acc, partials);
 }
 
@@ -197,7 +208,8 @@ void tl_row_sum(const double *partials, const double *amplitude, int64_t amp_at,
 void tl_energies(const TlMesh &m, const Pattern &pat, const double *mval, const uint8_t *known, const double *u, const double *v, const double *f,
                  const double *amplitude, int64_t amp_at, int32_t *inverted, double *partials, double *out, hipStream_t s)
 {
-    k_tl_row_partials<<<dim3(kSensBlocks, 1), 256, 0, s>>>(m, pat, mval, known, u, v, f, inverted, partials);
+    (m.law == kLawNeoHooke ? k_tl_row_partials<kLawNeoHooke> : k_tl_row_partials<kLawSvk>)<<<dim3(kSensBlocks, 1), 256, 0, s>>>(
+        m, pat, mval, known, u, v, f, inverted, partials);
     tl_row_sum(partials, amplitude, amp_at, out, s);
 }
 

@@ -10,6 +10,15 @@
 // With F = I and S = 0 this is the project's K.  In the kernel's constants (c0 = c t / 2, s = S / c): V c = 2A c0, and the block is
 // 2A c0 (B_k^T (D / c) B_l + (g_k^T s g_l) I).
 //
+// Under kLawNeoHooke (explicit_tl.h) the material tangent is 2 dS/dC = 2 mu C33 (kappa C^-1 (x) C^-1 + I_{C^-1}) with
+// kappa = Lambda / (2 mu C33 + Lambda).  Put through B_k^T DD B_l + (g_k^T S g_l) I, the (h_k . h_l) I terms of the material and the
+// geometric part cancel, h_k = F^-T g_k being the spatial gradient, and the block is
+//   K_T[k, l] = V (mu (g_k . g_l) I + mu C33 (2 kappa h_k h_l^T + h_l h_k^T))
+// The kernel uses this compact form (the tests' twin the B^T DD B form): in its constants (c0 = mu t / 2, lr = Lambda / mu)
+// V mu = 2A c0 and kappa = lr / (2 C33 + lr).  K_T[l, k] = K_T[k, l]^T; at u = 0 it is the project's K (2 mu kappa is the
+// plane-stress lambda).  F^-T divides by det F: an element with det F = 0 gives non-finite entries, which the CG's finite check
+// catches; one with det F < 0 finite ones.
+//
 // The loop (api.hip, mag_run_newton).  Increment k under lambda = load[k]:  f_int(u)_F = lambda f_F,  u_P = lambda u_in.
 //   first iteration    dU_P = lambda u_in - u on P;   K_T,FF du_F = (lambda f - f_int(u))_F - (K_T dU_P)_F;   u += s (du_F + dU_P)
 //   later iterations   K_T,FF du_F = (lambda f - f_int(u))_F;   u += s du_F
@@ -35,7 +44,7 @@ void tl_tangent(const TlMesh &m, const Pattern &pat, const double *u, double *kv
 // zeroed, then every incident triangle adds its three blocks of this node's row, in list order.  The triangle is always taken
 // from its first corner on, so that its three rows see the same H, F and S.  EFFECTIVE (transient_tl.hip): the lane then finishes
 // the row in place with effective_values's expression, val = c_K val + c_M mval on the blocks' diagonals -- no K_T is kept.
-template <bool EFFECTIVE>
+template <int LAW, bool EFFECTIVE>
 __device__ inline void tl_tangent_row(const TlMesh &m, const Pattern &pat, const double2 *u, int64_t g, double *val, int32_t *inverted,
                                       const double *mval, double c_K, double c_M)
 {
@@ -52,13 +61,42 @@ __device__ inline void tl_tangent_row(const TlMesh &m, const Pattern &pat, const
         const int32_t n0 = m.conn[3 * e], n1 = m.conn[3 * e + 1], n2 = m.conn[3 * e + 2];
         const double2 x0 = m.xy[n0], x1 = m.xy[n1], x2 = m.xy[n2], u0 = u[n0], u1 = u[n1], u2 = u[n2];
         const double2 db = make_double2(x1.x - x0.x, x1.y - x0.y), dc = make_double2(x2.x - x0.x, x2.y - x0.y);
-        const TlStrain s = tl_strain(db, make_double2(u1.x - u0.x, u1.y - u0.y), dc, make_double2(u2.x - u0.x, u2.y - u0.y), nu, h, inverted);
+        TlNeo neo;
+        const TlStrain s = tl_strain<LAW>(db, make_double2(u1.x - u0.x, u1.y - u0.y), dc, make_double2(u2.x - u0.x, u2.y - u0.y), nu, h, inverted, &neo);
         const double r = ring_rcp<double>(s.twoA);
         const double2 g0 = make_double2((db.y - dc.y) * r, (dc.x - db.x) * r), g1 = make_double2(dc.y * r, -(dc.x * r)),
                       g2 = make_double2(-(db.y * r), db.x * r);
         const double F11 = 1.0 + s.H11, F12 = s.H12, F21 = s.H21, F22 = 1.0 + s.H22;
         const double wv = s.twoA * m.c0; // V c
         const double2 gk = a == 0 ? g0 : (a == 1 ? g1 : g2);
+        if constexpr (LAW == kLawNeoHooke) {
+            // h_k = F^-T g_k = (F22 g.x - F21 g.y, F11 g.y - F12 g.x) / det F; the row's corner carries mu C33 too
+            const double ri = 1.0 / fma(F11, F22, -(F12 * F21));
+            const double c33 = 1.0 + neo.d;
+            const double k2 = 2.0 * (nu / fma(2.0, c33, nu)); // 2 kappa (nu holds Lambda / mu)
+            const double wc = c33 * ri;
+            const double hkx = wc * fma(F22, gk.x, -(F21 * gk.y)), hky = wc * fma(F11, gk.y, -(F12 * gk.x));
+#pragma unroll
+            for (int l = 0; l < 3; ++l) {
+                const double2 gl = l == 0 ? g0 : (l == 1 ? g1 : g2);
+                const int32_t j = l == 0 ? n0 : (l == 1 ? n1 : n2);
+                const double hlx = ri * fma(F22, gl.x, -(F21 * gl.y)), hly = ri * fma(F11, gl.y, -(F12 * gl.x));
+                const double gg = fma(gk.x, gl.x, gk.y * gl.y);
+                const double k00 = wv * (fma(k2, hkx * hlx, hlx * hkx) + gg);
+                const double k01 = wv * fma(k2, hkx * hly, hlx * hky);
+                const double k10 = wv * fma(k2, hky * hlx, hly * hkx);
+                const double k11 = wv * (fma(k2, hky * hly, hly * hky) + gg);
+                for (int32_t k = 0; k < cnt; ++k)
+                    if (pat.bcol[p + k] == j) {
+                        row0[2 * k] = row0[2 * k] + k00;
+                        row0[2 * k + 1] = row0[2 * k + 1] + k01;
+                        row1[2 * k] = row1[2 * k] + k10;
+                        row1[2 * k + 1] = row1[2 * k + 1] + k11;
+                        break;
+                    }
+            }
+            continue;
+        }
         // (D / c) B_k, column d: (p0 + nu p1, p1 + nu p0, h p2) of p = (F_d1 gk.x, F_d2 gk.y, F_d1 gk.y + F_d2 gk.x)
         const double pa0 = F11 * gk.x, pa1 = F12 * gk.y, pa2 = fma(F11, gk.y, F12 * gk.x);
         const double pb0 = F21 * gk.x, pb1 = F22 * gk.y, pb2 = fma(F21, gk.y, F22 * gk.x);

@@ -10,16 +10,18 @@ namespace magk {
 
 // ---- the tangent in the pattern: one thread per row node (Hilbert position g, caller id perm[g]), as k_tr_mass_pattern; the
 // row itself is newton.h's tl_tangent_row, which transient_tl.hip finishes as the effective matrix
+template <int LAW>
 __global__ void __launch_bounds__(256) k_tl_tangent(TlMesh m, Pattern pat, const double2 *u, double *kval, int32_t *inverted)
 {
     const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (g >= m.N) return;
-    tl_tangent_row<false>(m, pat, u, g, kval, inverted, nullptr, 0.0, 0.0);
+    tl_tangent_row<LAW, false>(m, pat, u, g, kval, inverted, nullptr, 0.0, 0.0);
 }
 
 void tl_tangent(const TlMesh &m, const Pattern &pat, const double *u, double *kval, int32_t *inverted, hipStream_t s)
 {
-    k_tl_tangent<<<dim3((unsigned)((m.N + 255) / 256)), 256, 0, s>>>(m, pat, (const double2 *)u, kval, inverted);
+    (m.law == kLawNeoHooke ? k_tl_tangent<kLawNeoHooke> : k_tl_tangent<kLawSvk>)<<<dim3((unsigned)((m.N + 255) / 256)), 256, 0, s>>>(
+        m, pat, (const double2 *)u, kval, inverted);
 }
 
 // ---- the right-hand side: one thread per DOF, the row in ascending column order
@@ -122,15 +124,18 @@ void newton_record(const double *u, const int32_t *probes, int32_t num_probes, i
     k_nt_record<<<dim3((unsigned)((n2 + num_probes + 255) / 256)), 256, 0, s>>>(u, probes, num_probes, row, probe_u, snap, n2);
 }
 
-// ---- the per-element row: strains, stresses, det F and the strain energy, from the element's first corner
+// ---- the per-element row: strains, stresses, det F and the strain energy, from the element's first corner (cs: the factor of
+// tl_strain's s -- E / (1 - nu^2), under kLawNeoHooke mu)
+template <int LAW>
 __global__ void __launch_bounds__(256) k_nt_elements(TlMesh m, const double2 *u, double cs, double *elem, int32_t *inverted)
 {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= m.E) return;
     const int64_t a = m.conn[3 * e], b = m.conn[3 * e + 1], c = m.conn[3 * e + 2];
     const double2 ca = m.xy[a], cb = m.xy[b], cc = m.xy[c], ua = u[a], pb = u[b], pc = u[c];
-    const TlStrain s = tl_strain(make_double2(cb.x - ca.x, cb.y - ca.y), make_double2(pb.x - ua.x, pb.y - ua.y),
-                                 make_double2(cc.x - ca.x, cc.y - ca.y), make_double2(pc.x - ua.x, pc.y - ua.y), m.nu, m.h, inverted);
+    TlNeo neo;
+    const TlStrain s = tl_strain<LAW>(make_double2(cb.x - ca.x, cb.y - ca.y), make_double2(pb.x - ua.x, pb.y - ua.y),
+                                      make_double2(cc.x - ca.x, cc.y - ca.y), make_double2(pc.x - ua.x, pc.y - ua.y), m.nu, m.h, inverted, &neo);
     double *o = elem + 8 * e;
     o[0] = s.Exx;
     o[1] = s.Eyy;
@@ -139,12 +144,16 @@ __global__ void __launch_bounds__(256) k_nt_elements(TlMesh m, const double2 *u,
     o[4] = cs * s.sy;
     o[5] = cs * s.tq;
     o[6] = fma(1.0 + s.H11, 1.0 + s.H22, -(s.H12 * s.H21));
-    o[7] = tl_energy(s, m.c0);
+    if constexpr (LAW == kLawSvk)
+        o[7] = tl_energy(s, m.c0);
+    else
+        o[7] = neo_energy(s, neo, m.c0, m.nu);
 }
 
 void newton_elements(const TlMesh &m, const double *u, double cs, double *elem, int32_t *inverted, hipStream_t s)
 {
-    k_nt_elements<<<dim3((unsigned)((m.E + 255) / 256)), 256, 0, s>>>(m, (const double2 *)u, cs, elem, inverted);
+    (m.law == kLawNeoHooke ? k_nt_elements<kLawNeoHooke> : k_nt_elements<kLawSvk>)<<<dim3((unsigned)((m.E + 255) / 256)), 256, 0, s>>>(
+        m, (const double2 *)u, cs, elem, inverted);
 }
 
 } // namespace magk

@@ -10,18 +10,20 @@
 namespace magk {
 
 // ---- A_T = c_K K_T(u) + c_M M: k_tl_tangent with the row finished by its lane
+template <int LAW>
 __global__ void __launch_bounds__(256) k_tt_effective_tangent(TlMesh m, Pattern pat, const double2 *u, const double *mval, double c_K, double c_M,
                                                               double *aval, int32_t *inverted)
 {
     const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (g >= m.N) return;
-    tl_tangent_row<true>(m, pat, u, g, aval, inverted, mval, c_K, c_M);
+    tl_tangent_row<LAW, true>(m, pat, u, g, aval, inverted, mval, c_K, c_M);
 }
 
 void tl_effective_tangent(const TlMesh &m, const Pattern &pat, const double *u, const double *mval, double c_K, double c_M, double *aval,
                           int32_t *inverted, hipStream_t s)
 {
-    k_tt_effective_tangent<<<dim3((unsigned)((m.N + 255) / 256)), 256, 0, s>>>(m, pat, (const double2 *)u, mval, c_K, c_M, aval, inverted);
+    (m.law == kLawNeoHooke ? k_tt_effective_tangent<kLawNeoHooke> : k_tt_effective_tangent<kLawSvk>)<<<dim3((unsigned)((m.N + 255) / 256)), 256, 0, s>>>(
+        m, pat, (const double2 *)u, mval, c_K, c_M, aval, inverted);
 }
 
 // ---- the trial state: one thread per DOF
@@ -116,6 +118,7 @@ void tl_dynamic_reactions(const Pattern &pat, const double *mval, const uint8_t 
 
 // ---- an energy row: the kinetic energy and the load's work over the 2N DOFs, the strain energy over the elements (explicit_tl.h's
 // tl_element_energy), each thread its fixed share of either
+template <int LAW>
 __global__ void __launch_bounds__(256) k_tt_energy_partials(TlMesh m, Pattern pat, const double *mval, const uint8_t *known, const double *u,
                                                             const double *v, const double *f, int32_t *inverted, double *partials)
 {
@@ -124,7 +127,7 @@ __global__ void __launch_bounds__(256) k_tt_energy_partials(TlMesh m, Pattern pa
         s[0] = fma(v[r], inertia_row(pat, mval, r, v, v, 0.0), s[0]);
         s[2] += known[r] ? 0.0 : f[r] * u[r];
     });
-    share_sum(m.E, acc, [&](int64_t e, double (&s)[3]) { s[1] += tl_element_energy(m, (const double2 *)u, e, inverted); });
+    share_sum(m.E, acc, [&](int64_t e, double (&s)[3]) { s[1] += tl_element_energy<LAW>(m, (const double2 *)u, e, inverted); });
     store_partials(acc, partials);
 }
 
@@ -132,7 +135,8 @@ void tl_dynamic_energies(const TlMesh &m, const Pattern &pat, const double *mval
                          const double *f, const double *amplitude, int64_t amp_at, int32_t *inverted, double *partials, double *out,
                          hipStream_t s)
 {
-    k_tt_energy_partials<<<dim3(kSensBlocks, 1), 256, 0, s>>>(m, pat, mval, known, u, v, f, inverted, partials);
+    (m.law == kLawNeoHooke ? k_tt_energy_partials<kLawNeoHooke> : k_tt_energy_partials<kLawSvk>)<<<dim3(kSensBlocks, 1), 256, 0, s>>>(
+        m, pat, mval, known, u, v, f, inverted, partials);
     tl_row_sum(partials, amplitude, amp_at, out, s);
 }
 

@@ -892,6 +892,7 @@ class Context:
             out.update(self.download_transient_tl())
             out.update(self.transient_tl_info())
             out["inverted"] = bool(out["inverted"])
+            out["material"] = self.material_law()
             if not out["converged"]:
                 out["message"] = self._L.mag_last_error(self._h).decode()
             return out
@@ -1001,6 +1002,7 @@ class Context:
         out.update(zip(self.EXPLICIT_INFO, (int(v) for v in info)))
         if kinematics == "tl":
             out["inverted"] = info[7] == 0
+            out["material"] = self.material_law()
         out["time"] = out["t_start"] + out["dt"] * (out["record_every"] * np.arange(len(out["iterations"])))
         return out
 
@@ -1013,6 +1015,23 @@ class Context:
         f, scalars = np.empty(2 * self.N), np.empty(2)
         self._check(self._L.mag_internal_force(self._h, _p(u, C.c_double), _p(f, C.c_double), _p(scalars, C.c_double), MAG_MEM_HOST))
         return f, float(scalars[0]), bool(scalars[1] != 0.0)
+
+    # -- the material of the total-Lagrangian passes -----------------------------------------------------
+    MATERIAL_LAWS = {"svk": _lib.MAG_LAW_SVK, "neo_hooke": _lib.MAG_LAW_NEO_HOOKE}
+
+    def set_material_law(self, law):
+        """mag_set_material_law: "svk" (St. Venant-Kirchhoff, the default) or "neo_hooke" (compressible neo-Hooke, plane stress
+        enforced per element) for explicit(kinematics="tl"), internal_force, newton, assemble_tangent, transient(kinematics="tl")
+        and assemble_effective_tangent.  Context state: kept across uploads; no stored result changes."""
+        if law not in self.MATERIAL_LAWS:
+            raise ValueError(f"set_material_law: law {law!r} is none of {sorted(self.MATERIAL_LAWS)}")
+        self._check(self._L.mag_set_material_law(self._h, self.MATERIAL_LAWS[law]))
+
+    def material_law(self):
+        """The law of mag_get_material_law by name."""
+        law = C.c_int32(-1)
+        self._check(self._L.mag_get_material_law(self._h, C.byref(law)))
+        return {v: k for k, v in self.MATERIAL_LAWS.items()}[law.value]
 
     # -- nonlinear statics: Newton's method on the total-Lagrangian tangent, in load increments ----------
     NEWTON_INFO = ("increments_converged", "cg_kernel", "preconditioner", "newton_iterations_total", "cg_iterations_total", "halvings",
@@ -1089,6 +1108,7 @@ class Context:
         out["newton_iterations_total"] = info.pop("newton_iterations_total")
         out["cg_iterations_total"] = info.pop("cg_iterations_total")
         out.update(info)
+        out["material"] = self.material_law()
         if not out["converged"]:
             out["message"] = self._L.mag_last_error(self._h).decode()
         return out

@@ -12,6 +12,7 @@
 //                      [--explicit STEPS --density RHO [--dt DT | --dt-scale S] [--rayleigh A,E] [--probe DOF]... [--record-every K]
 //                       [--kinematics linear|tl]]
 //                      [--nonlinear INCREMENTS [--newton-tol T] [--line-search H] [--probe DOF]...]
+//                      [--material svk|neo-hooke]
 //   --dry-run  stop before the solver and print what was parsed (no GPU needed)
 //   --rel TOL  stop CG on relative residual TOL instead of the reference's absolute 1e-4
 //   --buckling P [--subspace Q]  after the linear solve, also print "info: buckling mode k load factor L residual R" for the P load
@@ -37,6 +38,8 @@
 //              newton I cg C residual R" per converged increment, write nodes.csv / elements.csv from the NONLINEAR result (u; the
 //              von Mises value of the second Piola-Kirchhoff stress) and load_path.csv (increment,load,newton,W,Pi, then u per
 //              --probe DOF) next to nodes.csv
+//   --material svk|neo-hooke  the material law of the total-Lagrangian passes (solver::set_material_law): with --nonlinear, or with
+//              --explicit / --transient under --kinematics tl; prints "info: material neo-hooke".  Refused with the linear passes
 //   --stress-recovery  also write nodes_stress.csv (id,sx,sy,txy,vm) and elements_stress.csv (id,sx,sy,txy,vm,eta2) next to the
 //              two files -- solver::stress_recovery: the tensor per element, the nodal field, the ZZ error indicator -- and
 //              print eta_rel; without it nothing changes
@@ -519,7 +522,7 @@ int main(int argc, char **argv)
     double newton_tol = 0.0;
     int explicit_steps = 0, record_every = 1;
     double dt_scale = 0.0;
-    std::string kinematics;
+    std::string kinematics, material;
     std::vector<std::int32_t> probes;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -535,6 +538,7 @@ int main(int argc, char **argv)
         else if (a == "--dt-scale" && i + 1 < argc) dt_scale = std::atof(argv[++i]);
         else if (a == "--record-every" && i + 1 < argc) record_every = std::atoi(argv[++i]);
         else if (a == "--kinematics" && i + 1 < argc) kinematics = argv[++i];
+        else if (a == "--material" && i + 1 < argc) material = argv[++i];
         else if (a == "--nonlinear" && i + 1 < argc) nonlinear = std::atoi(argv[++i]);
         else if (a == "--newton-tol" && i + 1 < argc) newton_tol = std::atof(argv[++i]);
         else if (a == "--line-search" && i + 1 < argc) line_search = std::atoi(argv[++i]);
@@ -562,7 +566,7 @@ int main(int argc, char **argv)
         else die({MagnetiteError::Input, "Unrecognized argument " + a});
     }
     if (input.empty() || mesh.empty()) {
-        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery] [--modal P --density RHO] [--transient STEPS --dt DT --density RHO [--rayleigh A,E] [--probe DOF]... [--kinematics linear|tl [--newton-tol T]]] [--explicit STEPS --density RHO [--dt DT | --dt-scale S] [--rayleigh A,E] [--probe DOF]... [--record-every K] [--kinematics linear|tl]] [--nonlinear INCREMENTS [--newton-tol T] [--line-search H] [--probe DOF]...] [--adapt R [--refine-fraction T] [--refine-split 1|3]] [--topopt ITERS [--volume-fraction F] [--penal P] [--filter-passes K] [--field-cg 0..3]]\n");
+        std::fprintf(stderr, "usage: magnetite_gpu <input.json> <mesh.msh> [--nodes F] [--elements F] [--dry-run] [--rel TOL] [--stress-recovery] [--modal P --density RHO] [--transient STEPS --dt DT --density RHO [--rayleigh A,E] [--probe DOF]... [--kinematics linear|tl [--newton-tol T]]] [--explicit STEPS --density RHO [--dt DT | --dt-scale S] [--rayleigh A,E] [--probe DOF]... [--record-every K] [--kinematics linear|tl]] [--nonlinear INCREMENTS [--newton-tol T] [--line-search H] [--probe DOF]...] [--material svk|neo-hooke] [--adapt R [--refine-fraction T] [--refine-split 1|3]] [--topopt ITERS [--volume-fraction F] [--penal P] [--filter-passes K] [--field-cg 0..3]]\n");
         return 2;
     }
     if (modal_modes < 0 || (modal_modes > 0 && !(density > 0.0))) die({MagnetiteError::Input, "--modal P needs P >= 1 and --density RHO > 0"});
@@ -590,6 +594,10 @@ int main(int argc, char **argv)
     if (!nonlinear_run && ((newton_tol != 0.0 && !transient_tl) || line_search != 0))
         die({MagnetiteError::Input, "--newton-tol and --line-search need --nonlinear INCREMENTS (--newton-tol also goes with --transient STEPS --kinematics tl)"});
     if (nonlinear_run && (transient || explicit_run)) die({MagnetiteError::Input, "--nonlinear shares --probe with --transient and --explicit: one of them at a time"});
+    if (!material.empty() && material != "svk" && material != "neo-hooke") die({MagnetiteError::Input, "--material " + material + ": svk or neo-hooke"});
+    if (!material.empty() && !nonlinear_run && !total_lagrangian)
+        die({MagnetiteError::Input, "--material needs --nonlinear INCREMENTS, or --explicit STEPS / --transient STEPS with --kinematics tl: the linear passes read no material law"});
+    const bool neo_hooke = material == "neo-hooke";
     if (nonlinear_run && adapt > 0) die({MagnetiteError::Input, "--nonlinear solves on the mesh as given: not together with --adapt"});
     if (!transient && !explicit_run && (dt != 0.0 || (!probes.empty() && !nonlinear_run) || rayleigh_mass != 0.0 || rayleigh_stiffness != 0.0))
         die({MagnetiteError::Input, "--dt, --rayleigh and --probe need --transient STEPS"});
@@ -645,6 +653,7 @@ int main(int argc, char **argv)
         if (transient && !kinematics.empty())
             std::printf("dry-run: transient kinematics %s newton_tol %s\n", total_lagrangian ? "total-lagrangian" : "linear",
                         rust_display(newton_tol).c_str());
+        if (!material.empty()) std::printf("dry-run: material %s\n", material.c_str());
         if (nonlinear_run)
             std::printf("dry-run: nonlinear increments %d newton_tol %s line_search %d probes %zu\n", nonlinear, rust_display(newton_tol).c_str(),
                         line_search, probes.size());
@@ -670,6 +679,10 @@ int main(int argc, char **argv)
                         rust_display(history[r].eta_rel).c_str());
     } else if (Result err = solver::run(nodes, elements, meta, &opt)) {
         die(*err);
+    }
+    if (!material.empty()) { // (the law of the total-Lagrangian pass asked for below: solver::set_material_law)
+        if (Result err = solver::set_material_law(neo_hooke ? MAG_LAW_NEO_HOOKE : MAG_LAW_SVK)) die(*err);
+        std::printf("info: material %s\n", material.c_str());
     }
     if (nonlinear_run) {
         // The pass needs every element counter-clockwise, as the modal analysis does: the elements go in by their true sign.
