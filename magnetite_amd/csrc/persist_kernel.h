@@ -942,6 +942,14 @@ constexpr bool persist_own_piece_reduction(int B, bool MG, int EBM, bool ONE, in
     return persist_update_loads(B, MG, EBM, ONE, NPT) && !LC;
 }
 
+// The loop's bookkeeping at compile time and in scalar words (DESIGN LS): a slot's tile and position without a division, the
+// wave-uniform facts of a slot's flags as bits of one scalar.  On where persist_own_piece_reduction is on, and nowhere else: every
+// other instantiation keeps its code, instruction for instruction.
+constexpr bool persist_loop_scalars(int B, bool MG, int EBM, bool ONE, int NPT, bool LC)
+{
+    return persist_own_piece_reduction(B, MG, EBM, ONE, NPT, LC);
+}
+
 // EBM: 0 the triangle walk, 1 edge blocks in registers (every row of the mesh a fan of at most six blocks: structured meshes),
 // 2 edge blocks with OVERFLOW (round 4: rows that are one fan of any length -- what gmsh's frontal meshes look like, a quarter
 // of their nodes with seven neighbours: blocks beyond the six in registers sit in an LDS pool of 32-byte records).
@@ -993,9 +1001,20 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
     double *s_part = s_chunk + 4 * 32; // persist_block_sum: the rows' partials of the four sums
     // overflow records (OV): two double2 each; several ranks: behind the interface words (s_opk, below)
     [[maybe_unused]] double2 *s_pool = (double2 *)(s_part + kPersistPartDoubles) + (MG ? NPT * THREADS / 4 : 0);
-    // slot s of this lane: local node s * THREADS + tid, in local tile (s * THREADS + tid) / B (a scalar: wave-uniform)
-    auto t_loc = [&](int s) { return __builtin_amdgcn_readfirstlane((s * THREADS + tid) / B); };
-    auto t_lt = [&](int s) { return (s * THREADS + tid) % B; };
+    // slot s of this lane: local node s * THREADS + tid, in local tile (s * THREADS + tid) / B (a scalar: wave-uniform) at position
+    // (s * THREADS + tid) % B.  LS (B == THREADS): these are s and tid, and they are written so -- the compiler does not know that
+    // tid < THREADS, and computed every use's tile with a v_readfirstlane of s * THREADS + tid, a signed division by B in five
+    // scalar instructions and an s_mul_i32 by tile_words, in front of the first LDS load of every walk (DESIGN LS).
+    constexpr bool LS = persist_loop_scalars(B, MG, EBM, ONE, NPTX ? NPTX : kPersistNpt, LC);
+    static_assert(!LS || B == THREADS, "a slot is a tile");
+    auto t_loc = [&](int s) {
+        if constexpr (LS) return s;
+        else return __builtin_amdgcn_readfirstlane((s * THREADS + tid) / B);
+    };
+    auto t_lt = [&](int s) {
+        if constexpr (LS) return tid;
+        else return (s * THREADS + tid) % B;
+    };
     auto t_xy = [&](int s) { return smem + (size_t)t_loc(s) * tile_words; };
 
     const int cgrid = (int)gridDim.x - (MG ? P.comm_wg : 0); // compute workgroups (an exchange workgroup may follow them)
@@ -1043,6 +1062,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
         if (!(l < P.tiles_per_wg && t < (MG ? P.t1 : P.T))) {
             // (UL) a dead slot is updated like a live one, without a test: its r, q and p are zeros and stay zeros
             if constexpr (UL) xy[lt] = pim[lt] = make_double2(0.0, 0.0);
+            if constexpr (LS) xs[lt] = make_double2(0.0, 0.0); // (LS) ... and so is its x: the x update has no test either
             continue;
         }
         const TileMeta tm = P.meta[t];
@@ -1240,6 +1260,25 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
         }
         __syncthreads(); // s_red and s_rec go back to their day jobs
     }
+    // (LS) What a WAVE needs to know of its slots' flags, as bits of one scalar word: the loop branches on them and makes the
+    // lane masks it still needs from the flag register where it uses them.  As loop-invariant lane masks -- `flags & 8`, `& 1`,
+    // `& 2`, `(flags & 20) == 20` per slot -- they were 61 spilled SGPRs, read back by v_readlane_b32 in front of every use.
+    // Bit s: slot s carries a live tile (B == THREADS: one tile per slot, the same for the whole workgroup); 4 + s: some lane of
+    // this wave has a prescribed or an invalid node there (q is zeroed for it); 8 + s: some lane publishes its q; 12: this wave is
+    // one of waves 4-7; 16 + s: the tile has ring entries.
+    [[maybe_unused]] uint32_t lsw = 0;
+    if constexpr (LS) {
+#pragma unroll
+        for (int s = 0; s < NPT; ++s) {
+            const uint32_t f = flags[s];
+            lsw |= (__any((f & 8u) ? 1 : 0) ? 1u : 0u) << s;
+            lsw |= (__any(((f & 3u) || !(f & 16u)) ? 1 : 0) ? 1u : 0u) << (4 + s);
+            lsw |= (__any((f & 20u) == 20u ? 1 : 0) ? 1u : 0u) << (8 + s);
+            lsw |= (ent[s] > 0 ? 1u : 0u) << (16 + s);
+        }
+        lsw |= (uint32_t)((tid >> 8) & 1) << 12;
+        lsw = (uint32_t)__builtin_amdgcn_readfirstlane((int)lsw);
+    }
     if (blockIdx.x == 0 && tid == 0) acc[1] = 1.0; // "p.q" > 0: alpha finite, multiplies q = 0
     persist_block_sum<OPQ>(acc, s_part);
     int par = 0;
@@ -1339,6 +1378,9 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
         // alpha nor beta nor the sums -- q has been final in LDS since the walks -- and are in flight while the chains below run.
         // A loop that breaks below leaves them unused.  Pinned where they stand, as ring_walk_blocks pins its gathers.
         [[maybe_unused]] double2 uq[NPT], up[NPT];
+        // (LS) the flag register and the scalar word behind empty asms: nothing made from them is loop-invariant, so no lane mask
+        // and no tested bit is kept across the iteration (and spilled)
+        if constexpr (LS) asm volatile("" : "+v"(flags.v), "+s"(lsw));
         if constexpr (UL) {
 #pragma unroll
             for (int s = 0; s < NPT; ++s) uq[s] = t_xy(s)[t_lt(s)];
@@ -1397,7 +1439,8 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
         if (xnow) { // x += alpha p here, on the critical path, only when it cannot be rebuilt later
 #pragma unroll
             for (int s = 0; s < NPT; ++s) {
-                if (!(flags[s] & 8)) continue;
+                if constexpr (!LS) // (LS: a dead slot's p and x are zeros and stay zeros)
+                    if (!(flags[s] & 8)) continue;
                 const int lt = t_lt(s);
                 double2 *xy = t_xy(s), *pim = xy + capx, *xs = pim + cap + maxh;
                 const double2 po = pim[lt];
@@ -1458,7 +1501,9 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
                 if (flags[s] & 8) update_slot(s);
         }
 #pragma unroll
-        for (int e = 0; e < NH; ++e)
+        for (int e = 0; e < NH; ++e) {
+            // (LS: the lane mask made here, from the register, not kept in scalars across the loop -- hidden in place: no copy)
+            if constexpr (LS) asm volatile("" : "+v"(hg[e]));
             if (hg[e] != -1) {
                 double2 *hbase = smem + hloc[e]; // = tile base + position: coordinates at [B], p image at [cap + B], ...
                 double2 hrv = hbase[capx + cap], hpv = hbase[capx + B]; // the halo node's p lives in the p image itself
@@ -1469,6 +1514,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
                 hbase[capx + cap] = hrv;
                 hbase[capx + B] = hpv;
             }
+        }
         MAG_STAMP(0) // scalars + vector updates issued
         __syncthreads();
         MAG_STAMP(1) // ... landed in LDS for everybody (workgroup barrier)
@@ -1497,20 +1543,26 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
             // the partners finish within 0.8 us of each other.  Twelve other schedules (static priority, alternating per
             // slot or pair, one or three slots, three levels, priority during the vector updates) were measured and are in
             // profiles/r03_persist_ab.txt (q0-q16): none better.
-            if (((tid >> 8) & 1) && s >= NPT / 2) __builtin_amdgcn_s_setprio(1);
+            if constexpr (LS) {
+                if (((lsw >> 12) & 1u) && s >= NPT / 2) __builtin_amdgcn_s_setprio(1);
+            } else if (((tid >> 8) & 1) && s >= NPT / 2) __builtin_amdgcn_s_setprio(1);
             // (OV) a wave that carries this slot's long rows -- the valence partition gives every wave one such slot --
             // takes priority 2 for it: it is the one the workgroup's sums will wait for (frontal1m: 6.39 without, 6.31 at
             // priority 1, 6.30 at 2 us per iteration)
             if (OV && ovmax[s] > 0) __builtin_amdgcn_s_setprio(2);
             else if (OV && !(((tid >> 8) & 1) && s >= NPT / 2)) __builtin_amdgcn_s_setprio(0);
-            if (!(flags[s] & 8)) continue;
+            // (LS: a live tile is the whole workgroup's -- a scalar branch, every lane enabled in the walk)
+            if constexpr (LS) {
+                if (!((lsw >> s) & 1u)) continue;
+            } else if (!(flags[s] & 8)) continue;
             const int lt = t_lt(s);
             const double2 *xy = t_xy(s), *pim = xy + capx;
             const double2 ca = xy[lt], pa = pim[lt];
             double fx = 0.0, fy = 0.0;
             {
-                const int32_t nent = __builtin_amdgcn_readfirstlane(ent[s]); // one tile per wave: a scalar
-                if (nent > 0) { // entries are biased slots relative to this tile (see the remap at the top)
+                // one tile per wave: a scalar (LS: a bit of the scalar word)
+                [[maybe_unused]] const int32_t nent = LS ? 0 : __builtin_amdgcn_readfirstlane(ent[s]);
+                if (LS ? ((lsw >> (16 + s)) & 1u) != 0 : nent > 0) { // entries are biased slots relative to this tile (see the remap at the top)
                     const uint32_t toff = (uint32_t)(SB * tile_words);
                     if (OV) {
                         const uint32_t oc = (ovpk[s >> 1] >> (16 * (s & 1))) & 0xffffu;
@@ -1526,12 +1578,18 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
                                                                      fx, fy, toff);
                 }
             }
-            if ((flags[s] & 1) || !(flags[s] & 16)) fx = 0.0;
-            if ((flags[s] & 2) || !(flags[s] & 16)) fy = 0.0;
+            // q of a prescribed DOF, and of a node slot beyond the mesh's last node, is zero.  (LS) On the 1M mesh almost no
+            // wave-slot has such a lane: the selects, and their masks, run only where the wave has one.
+            if (!LS || ((lsw >> (4 + s)) & 1u)) {
+                if ((flags[s] & 1) || !(flags[s] & 16)) fx = 0.0;
+                if ((flags[s] & 2) || !(flags[s] & 16)) fy = 0.0;
+            }
             const double2 qn = make_double2(fx, fy);
             if (QL) t_xy(s)[lt] = qn;
             else q[s] = qn;
-            if ((flags[s] & 20) == 20) // (2 x 32 N bytes of granules: below 4 GB for every mesh the chip can hold)
+            // (2 x 32 N bytes of granules: below 4 GB for every mesh the chip can hold; LS: a wave none of whose lanes publishes
+            // jumps over the block)
+            if ((!LS || ((lsw >> (8 + s)) & 1u)) && (flags[s] & 20) == 20)
                 put_granules_at(P.qg, 32u * ((uint32_t)(par ^ 1) * (uint32_t)P.N + (uint32_t)node_of(s)), epoch + 1, qn);
             if (MG && (flags[s] & 64u)) {
                 const uint32_t opk = s_opk[s * THREADS + tid];
@@ -1577,7 +1635,7 @@ __global__ void __launch_bounds__(THREADS) k_cg_persist(const PersistParams Pk)
                 xo.y = fma(ab, pj.y + rv.y, xo.y);
                 xs[lt] = xo;
             };
-            if (all_live) {
+            if (LS || all_live) { // (LS: a dead slot's x, p and r are zeros and stay zeros)
 #pragma unroll
                 for (int s = 0; s < NPT; ++s) x_slot(s);
             } else {
